@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- rays/sec + B-mode frames/sec of the ray-tracing hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload random1m|sphere|liver]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload random1m|sphere|liver] [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up (at least W steps and 1 s), times ONE region of exactly K steps, writes the outputs of its last step when
+`--dump-outputs DIR` is given (DIR/bmode.npy: the scan-converted B-mode image [400][500]; DIR/rf.npy: the convolved +
+enveloped RF image [E][R]; float32, rank 0's; the reference's NaN bins written as 0 and marked in DIR/<name>_nonfinite.npy),
+and prints the result line.  Everything else below -- the repeated timed
+region (`--min-time`, median repeat), `per_rank`, the counted work and the roofline with its live PMC passes, the
+per-kernel block, the one-frame-at-a-time / moving-probe / steady-state legs, the CPU baseline and the inline parity
+check -- runs only under `--full`.
 
 A "step" is one whole B-mode frame of the hot path over synthetic input already resident in HBM
 (main.cpp:102-148): clear -> trace (BVH closest-hit + interface sampling) -> RF accumulation ->
@@ -17,12 +25,12 @@ consecutive frames' rays; images are bit-identical to one-at-a-time tracing); K 
 the fewest, evenly sized passes.  Passes are DOUBLE-BUFFERED: the all-gather + PSF convolution of
 pass k run on a second stream beside the trace of pass k+1.  The timed region is EXACTLY K steps
 between barrier + synchronize pairs; it is repeated (at least 5 times, at least ~0.6 s in total)
-and the MEDIAN repeat is reported.  `--frames-in-flight 1` is the strict latency mode, also
+and the MEDIAN repeat is reported (`--full`; a plain run times the K steps once).  `--frames-in-flight 1` is the strict latency mode, also
 reported as `one_frame_at_a_time`; `sweep` is the same pass with a different probe pose in every
 frame (mcrt_trace_frames_poses: the moving probe of transducer.h:82-118).  `per_rank` carries every
 rank's trace / gather / post-processing time per step (HIP events on the streams they run on).
 
-The JSON line carries
+Under `--full` the JSON line also carries
   roofline      the dominant kernel (the BVH walk) against the guide's architectural VALU issue rate (`frac`), its
                 lane-level share, the measured HBM share (`hbm.measured_frac`: fabric bytes from rocprofv3 PMC
                 passes of this same command, taken live in child processes at the same pass size; `traffic`),
@@ -54,6 +62,8 @@ MIN_SPLIT_PASS = 48     # N > 1: a timed region is cut into two passes (gather +
 TRACE_KERNELS = ("k_trace_lane<false", "k_trace_lane_wide", "k_trace_packet")   # the walk of the timed build, pooled: the lane walk's five-wavefront form (k_trace_lane_wide: the default since round 6) and its four-wavefront form (large trees, CU-masked streams) and bounce 1's ray packets
 KERNEL_FAMILIES = {"walk": TRACE_KERNELS, "march": ("k_march<false",), "shade": ("k_shade<false",)}
 ARCH_IPC = 0.5          # MI355X_MICROARCH.md: a wave64 VALU instruction issues in 2 cycles on the SIMD-32 -> 0.5 instructions per cycle and SIMD
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+WARMUP_MIN_S = 1.0      # a plain run's warm-up lasts at least this long (whole timed regions, at least --warmup steps)
 
 
 def build_workload(m, name):
@@ -91,7 +101,11 @@ def parse_args():
                     help="frames traced per pass (mcrt_trace_frames): a step is still ONE frame, but every kernel launch then carries the "
                          "rays of this many consecutive frames (1 = strict one-frame-at-a-time latency mode)")
     ap.add_argument("--bvh", default=None, choices=["sah", "lbvh"], help="BVH builder: host binned SAH (default; random16m: the device LBVH) or the device LBVH")
-    ap.add_argument("--min-time", type=float, default=0.6, help="the K-step timed region is repeated until this many seconds are covered (>= 5 repeats)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: repeated timed regions, per-rank stage times, counted work + roofline "
+                                                        "(live PMC passes), per-kernel block, latency / sweep / steady-state legs, CPU baseline + parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's B-mode image and RF image to DIR/<name>.npy (float32, finite) "
+                                                                           "and where they were not finite to DIR/<name>_nonfinite.npy")
+    ap.add_argument("--min-time", type=float, default=0.6, help="--full: the K-step timed region is repeated until this many seconds are covered (>= 5 repeats)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency-leg", action="store_true", help="skip the extra one-frame-at-a-time and moving-probe measurements (profiling runs)")
     ap.add_argument("--no-pmc", action="store_true", help="do not take the live rocprofv3 PMC passes (HBM traffic, VALU instructions of k_trace)")
@@ -112,6 +126,34 @@ def passes(count, F):
     n_pass = -(-count // F)
     base, rem = divmod(count, n_pass)
     return [base + (1 if i < rem else 0) for i in range(n_pass)]
+
+
+def any_rank(flag, world, dist, torch, backend):
+    """`flag` of any rank, on every rank (so that every rank runs the same passes, and with them the same collectives)"""
+    if world == 1:
+        return bool(flag)
+    t = torch.tensor([1.0 if flag else 0.0], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
+    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    return float(t.item()) > 0.0
+
+
+def dump_outputs(d, arrays, limit=DUMP_LIMIT_BYTES):
+    """write every tensor of `arrays` as two finite float32 files: d/<name>.npy, its values with every non-finite element written
+    as 0, and d/<name>_nonfinite.npy, which says where those were (0 finite, 1 NaN, 2 +inf, 3 -inf) -- the pair holds the array
+    exactly.  (The reference's total internal reflection makes NaN echoes, which the contract keeps: about 5 % of the headline
+    workload's RF bins are NaN, and the PSF and the scan conversion spread them.)  An array larger than its share of `limit`
+    (both files counted) is replaced by a fixed, seeded sample of its elements (flattened, in index order), so that two runs of
+    the same command write the same sample."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = limit // max(1, 2 * len(arrays))
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32)
+        if a.nbytes > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(12345).choice(a.size, share // 4, replace=False))]
+        code = np.select([np.isnan(a), a == np.inf, a == -np.inf], [1.0, 2.0, 3.0], 0.0).astype(np.float32)
+        np.save(os.path.join(d, name + ".npy"), np.where(code == 0.0, a, np.float32(0.0)).astype(np.float32))
+        np.save(os.path.join(d, name + "_nonfinite.npy"), code)
 
 
 class Pipeline:
@@ -274,31 +316,47 @@ def main():
     # ---- counted algorithmic work of the K timed frames (counting build of the same kernels, untimed) ----
     # (the counting build walks every ray once, i.e. exactly the oracle's node/triangle visits: the timed kernel may cut the
     #  rays of a small bounce into pieces, whose extra visits are overhead, not algorithmic work)
-    ctx.enable_stats(True); ctx.get_stats(reset=True)
-    pipe.run_steps(0, K); pipe.sync()
-    st = ctx.get_stats(reset=True)
-    ctx.enable_stats(False)
-    # Algorithmic bytes (adapted to the BVH4 nodes the walk reads: 64 B with half-float boxes for the lane-per-ray
-    # walk, 128 B for the quad walk).  The dominant kernel is the walk, launched once per bounce and pass: per closest-hit query
-    # nodes*64 B + triangles*48 B + the 32-B ray read and 32-B hit record written.
-    node_bytes = 64
-    trace_bytes_frame = (st["nodes_visited"] * node_bytes + st["tris_tested"] * 48 + st["queries"] * 64) / K
-    # the rest of the frame, for the record: 64-B segment written + read, 8-B texture gather per RF step, RF block + bins
-    other_bytes_frame = (st["segments"] * 128 + st["rf_steps"] * 8) / K + E_local * R * (4 + 8)
+    full = args.full
+    if full:
+        ctx.enable_stats(True); ctx.get_stats(reset=True)
+        pipe.run_steps(0, K); pipe.sync()
+        st = ctx.get_stats(reset=True)
+        ctx.enable_stats(False)
+        # Algorithmic bytes (adapted to the BVH4 nodes the walk reads: 64 B with half-float boxes for the lane-per-ray
+        # walk, 128 B for the quad walk).  The dominant kernel is the walk, launched once per bounce and pass: per closest-hit query
+        # nodes*64 B + triangles*48 B + the 32-B ray read and 32-B hit record written.
+        node_bytes = 64
+        trace_bytes_frame = (st["nodes_visited"] * node_bytes + st["tris_tested"] * 48 + st["queries"] * 64) / K
+        # the rest of the frame, for the record: 64-B segment written + read, 8-B texture gather per RF step, RF block + bins
+        other_bytes_frame = (st["segments"] * 128 + st["rf_steps"] * 8) / K + E_local * R * (4 + 8)
 
-    # ---- the timed region: EXACTLY K steps between barrier + synchronize pairs, repeated; the median repeat is reported ----
+    # ---- the timed region: EXACTLY K steps between barrier + synchronize pairs (--full: repeated, the median repeat is reported) ----
     # (warm-up: at least W steps, rounded up to whole timed regions, so that the first timed repeat finds every buffer at its size)
     W_run = -(-max(W, 1) // K) * K
-    ctx.enable_timing(True)                                    # (before the warm-up: its HIP events are created there, not in the first timed repeat)
-    pipe.timing = True
+    if full:
+        ctx.enable_timing(True)                                # (before the warm-up: its HIP events are created there, not in the first timed repeat)
+        pipe.timing = True
+    if not full:
+        gc.collect(); gc.disable()                             # (here, not between the warm-up and the timed region: see below)
+    t_warm = time.perf_counter()
     for w0 in range(0, W_run, K):
         pipe.run_steps(1000 + w0, K)
     pipe.sync()
-    ctx.kernel_time(reset=True); pipe.times(1)
+    if not full:
+        # a plain run times ONE region, so it starts that region at steady state: whole regions more until the warm-up has lasted
+        # WARMUP_MIN_S, and no idle gap before the region (the first repeat of a --full run, which follows the tens of ms of gc.collect()
+        # with the GPU idle, is its slowest: 4-8 % above the median at 20 steps)
+        while any_rank(time.perf_counter() - t_warm < WARMUP_MIN_S, world, dist, torch, args.backend):
+            pipe.run_steps(1000 + W_run, K); W_run += K
+            pipe.sync()
+    if full:
+        ctx.kernel_time(reset=True); pipe.times(1)
     reps, total, n_rep, k_sum, k_n = [], 0.0, 0, 0.0, 0
     stage = {"trace_ms": 0.0, "gather_ms": 0.0, "post_ms": 0.0}
-    gc.collect(); gc.disable()                                 # (as timeit does: a full collection of the interpreter's heap is tens of ms, a whole repeat at this size)
-    while n_rep < 5 or (total < args.min_time and n_rep < 200):
+    min_reps, min_time = (5, args.min_time) if full else (1, 0.0)
+    if full:
+        gc.collect(); gc.disable()                             # (as timeit does: a full collection of the interpreter's heap is tens of ms, a whole repeat at this size)
+    while n_rep < min_reps or (total < min_time and n_rep < 200):
         pipe.sync()
         t0 = time.perf_counter()
         pipe.run_steps(0, K)
@@ -310,22 +368,27 @@ def main():
             dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)       # MAX over ranks (every rank then takes the same loop decisions)
         dt = float(dt_t.item())
         reps.append(dt); total += dt; n_rep += 1
-        a_ms, a_n = ctx.kernel_time(reset=True)                # harvested per repeat (outside the clock), so the same HIP events serve every repeat
-        k_sum += a_ms * a_n; k_n += a_n
-        for k_, v_ in pipe.times(1).items():
-            stage[k_] += v_
+        if full:
+            a_ms, a_n = ctx.kernel_time(reset=True)            # harvested per repeat (outside the clock), so the same HIP events serve every repeat
+            k_sum += a_ms * a_n; k_n += a_n
+            for k_, v_ in pipe.times(1).items():
+                stage[k_] += v_
     gc.enable()
-    k_ms = k_sum / max(k_n, 1)                                 # HIP events around every k_trace launch, on the launching stream
-    ctx.enable_timing(False)
-    pipe.timing = False
-    mine = dict({k_: v_ / (K * n_rep) for k_, v_ in stage.items()}, rank=rank, scan_lines=[e0, e1])
-    per_rank = [mine]
-    if world > 1:
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, mine)
     dt = statistics.median(reps)
-    launches_per_frame = k_n / (K * n_rep)                     # max_depth bounces / frames per pass
-    alg_bytes = trace_bytes_frame / launches_per_frame
+    if args.dump_outputs and rank == 0:
+        # what the timed path handed its caller in its last step (frame K - 1): the B-mode image and the RF image it was converted from
+        dump_outputs(args.dump_outputs, {"bmode": pipe.images[-1], "rf": pipe.frames[-1]})
+    if full:
+        k_ms = k_sum / max(k_n, 1)                             # HIP events around every k_trace launch, on the launching stream
+        ctx.enable_timing(False)
+        pipe.timing = False
+        mine = dict({k_: v_ / (K * n_rep) for k_, v_ in stage.items()}, rank=rank, scan_lines=[e0, e1])
+        per_rank = [mine]
+        if world > 1:
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, mine)
+        launches_per_frame = k_n / (K * n_rep)                 # max_depth bounces / frames per pass
+        alg_bytes = trace_bytes_frame / launches_per_frame
 
     if rank == 0:
         gather_check = None
@@ -343,7 +406,6 @@ def main():
                             "frames": nf, "first_frame": f0, "scan_lines": E, "ranks": world, "backend": args.backend,
                             "nonzero": int(torch.count_nonzero(alone).item()), "nonzero_bmode": int(torch.count_nonzero(alone_img).item())}
         rays = E * S * K
-        alg_gbs = alg_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
         pass_sizes = passes(K, F)
         out = {
             "metric": "rays/sec (Monte-Carlo sample paths traced + accumulated into whole B-mode frames: PSF, envelope, scan conversion)",
@@ -356,19 +418,22 @@ def main():
                        "timed_seconds_total": total, "repeat_ms_per_step_min_median_max": [min(reps) / K * 1e3, dt / K * 1e3, max(reps) / K * 1e3], "slowest_repeat": reps.index(max(reps)),
                        "overlap_gather_psf_with_next_trace": not args.no_overlap, "bvh_builder": args.bvh, "bvh_build_s": round(t_bvh, 3),
                        "warmup_steps_run": W_run, "step": "clear, trace, accumulate, [all-gather], PSF, envelope, scan conversion to %dx%d" % (pipe.OUT_ROWS, pipe.OUT_COLS)},
-            "ranks_seen": world, "per_rank": per_rank,
+            "ranks_seen": world,
         }
-        per_frame = {k: v / K for k, v in st.items()}
-        pmc = None
-        if world == 1 and not args.no_pmc:
-            pmc = live_pmc(args)
-        if pmc is None:
-            pmc = committed_pmc(args, pass_sizes, per_frame["queries"] / launches_per_frame)
-        roof = roofline_from(pmc, k_ms, alg_gbs, alg_bytes)
-        roof.update({"kernel": "the walk, one launch per bounce, pooled: k_trace_lane_wide (a lane per ray, five wavefronts per SIMD: every launch since round 6; k_trace_lane<false>, the four-wavefront form, for trees past half the Infinity Cache) and k_trace_packet (bounce 1 of passes of >= 262144 paths: a wavefront per ray packet)", "kernel_ms": k_ms, "launches": k_n,
-                     "launches_per_frame": launches_per_frame, "algorithmic_bytes_per_launch": alg_bytes, "algorithmic_GBps_cache_served": alg_gbs, "node_bytes": node_bytes,
-                     "trace_bytes_per_frame": trace_bytes_frame, "other_stage_bytes_per_frame": other_bytes_frame, "per_frame": per_frame})
-        if world == 1 and not args.no_latency_leg:
+        if full:
+            out["per_rank"] = per_rank
+            alg_gbs = alg_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+            per_frame = {k: v / K for k, v in st.items()}
+            pmc = None
+            if world == 1 and not args.no_pmc:
+                pmc = live_pmc(args)
+            if pmc is None:
+                pmc = committed_pmc(args, pass_sizes, per_frame["queries"] / launches_per_frame)
+            roof = roofline_from(pmc, k_ms, alg_gbs, alg_bytes)
+            roof.update({"kernel": "the walk, one launch per bounce, pooled: k_trace_lane_wide (a lane per ray, five wavefronts per SIMD: every launch since round 6; k_trace_lane<false>, the four-wavefront form, for trees past half the Infinity Cache) and k_trace_packet (bounce 1 of passes of >= 262144 paths: a wavefront per ray packet)", "kernel_ms": k_ms, "launches": k_n,
+                         "launches_per_frame": launches_per_frame, "algorithmic_bytes_per_launch": alg_bytes, "algorithmic_GBps_cache_served": alg_gbs, "node_bytes": node_bytes,
+                         "trace_bytes_per_frame": trace_bytes_frame, "other_stage_bytes_per_frame": other_bytes_frame, "per_frame": per_frame})
+        if full and world == 1 and not args.no_latency_leg:
             # ---- the bounce's OTHER kernels: one more region with k_shade's and k_march's launches bracketed too (untimed: the timed
             # region carries the walk's events only), and the same region on a context whose kernels do not overlap (each alone on the GPU)
             ctx.enable_timing(2); ctx.kernel_times(reset=True)
@@ -411,9 +476,10 @@ def main():
                                         t_over["shade"][0], t_alone["shade"][0], other.get("shade"), per_frame["queries"] * 212.0 / lpf, clock,
                                         note="algorithmic bytes = 212 B per ray (state in and out 96, march record 48, winning triangle 3 x 16, keys / queue / counts 20)"),
             }
-        roof["salu"] = salu_block(pmc)
-        out["roofline"] = roof
-        if world == 1 and F > 1 and not args.no_latency_leg:
+        if full:
+            roof["salu"] = salu_block(pmc)
+            out["roofline"] = roof
+        if full and world == 1 and F > 1 and not args.no_latency_leg:
             # the same workload strictly one frame at a time (each launch carries one frame's rays), for the record
             pipe.run_steps(2000, min(W, 16), F=1)
             lat = []
@@ -437,7 +503,7 @@ def main():
             dts = statistics.median(lat)
             out["sweep"] = {"value": E * S * K / dts, "unit": "rays/s", "ms_per_step": dts / K * 1e3, "frames_per_sec": K / dts, "frames_in_flight": F,
                             "what": "the timed region with a different probe pose in every frame of a pass (mcrt_trace_frames_poses)"}
-        if world == 1 and not args.no_latency_leg and pipe.F >= 2:
+        if full and world == 1 and not args.no_latency_leg and pipe.F >= 2:
             # the STEADY STATE, for the record beside the driver's pass size: whole passes of min(128, frames-in-flight) frames, outside
             # the timed region like the two legs above -- what a caller who keeps the GPU fed sees per frame (tails of a launch amortised over more rays)
             P = min(128, pipe.F)
@@ -452,13 +518,13 @@ def main():
             out["pass%d" % P] = {"value": E * S * P / dtp, "unit": "rays/s", "ms_per_step": dtp / P * 1e3, "frames_per_sec": P / dtp, "frames_in_flight": P, "repeats": len(lat),
                                  "ms_per_step_min_max": [min(lat) / P * 1e3, max(lat) / P * 1e3],
                                  "what": "one pass of %d frames per repeat (whole B-mode frames: trace, accumulate, PSF, envelope, scan conversion), median of %d" % (P, len(lat))}
-        if world > 1 and not args.no_cpu_baseline:
+        if full and world > 1 and not args.no_cpu_baseline:
             # N > 1: the oracle on rank 0's OWN shard (seconds), so that a scaling line carries oracle evidence and not only gather_check
             ctx.set_stream(pipe.s_trace.cuda_stream)
             ctx.trace_frames(0, pass_sizes[0], pipe.buf[0], e0, e1)
             torch.cuda.synchronize(); ctx.synchronize()
             out["parity_check"] = shard_parity(m, sd, tr, ctx, S, R, pipe.buf[0][0].cpu().numpy(), e0, e1)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             # frame 0 of the timed workload, traced the way the timed region traces it (first pass), before the PSF
             ctx.set_stream(pipe.s_trace.cuda_stream)
             ctx.trace_frames(0, pass_sizes[0], pipe.buf[0], e0, e1)

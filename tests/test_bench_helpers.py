@@ -67,3 +67,27 @@ def test_usable_cores_is_bounded_by_the_machine():
     b = _bench()
     n, info = b.usable_cores()
     assert 1 <= n <= (os.cpu_count() or 1) and info["cpu_count"] >= n
+
+
+def test_dump_outputs_writes_float32_within_the_budget(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float32, finite, with <name>_nonfinite.npy marking where it was NaN / +inf / -inf
+    (the pair gives the array back exactly); one past its share of the budget becomes a fixed, seeded sample"""
+    import numpy as np
+    import torch
+    b = _bench()
+    small = torch.arange(12, dtype=torch.float32).reshape(3, 4)
+    small[0, 1], small[1, 2], small[2, 3] = float("nan"), float("inf"), float("-inf")
+    big = torch.arange(4096, dtype=torch.float64)
+    b.dump_outputs(str(tmp_path / "a"), {"small": small, "big": big}, limit=16384)
+    b.dump_outputs(str(tmp_path / "b"), {"small": small, "big": big}, limit=16384)
+    ld = lambda run, f: np.load(str(tmp_path / run / (f + ".npy")))
+    s, m = ld("a", "small"), ld("a", "small_nonfinite")
+    assert s.dtype == np.float32 and m.dtype == np.float32 and np.isfinite(s).all() and np.isfinite(m).all()
+    assert m.tolist() == [[0, 1, 0, 0], [0, 0, 2, 0], [0, 0, 0, 3]] and s[0, 1] == s[1, 2] == s[2, 3] == 0.0
+    back = np.where(m == 1, np.float32(np.nan), np.where(m == 2, np.float32(np.inf), np.where(m == 3, np.float32(-np.inf), s)))
+    assert np.array_equal(back, small.numpy(), equal_nan=True)
+    g = ld("a", "big")
+    assert g.dtype == np.float32 and g.shape == (1024,) and np.all(np.diff(g) > 0) and set(g.tolist()) <= set(range(4096))
+    assert not ld("a", "big_nonfinite").any()
+    assert np.array_equal(g, ld("b", "big")) and np.array_equal(s, ld("b", "small")) and np.array_equal(m, ld("b", "small_nonfinite"))
+    assert b.DUMP_LIMIT_BYTES == 64 << 20

@@ -773,7 +773,7 @@ def test_two_ranks_gather_equals_single_process():
     warnings.warn("two-rank gather on this box ran over backend=%s%s" % (g["backend"], " (RCCL)" if g["backend"] == "nccl" else
                   " (host-staged; RCCL did not carry two ranks on one device: %s)" % _why(tried[0][2])))
     # strong scaling: a fixed 24-scan-line frame over the two ranks
-    r, out = _run_bench([a for a in small if a not in ("--scanlines", "16")] + ["--scanlines-total", "24", "--backend", g["backend"]], nproc=2, timeout=300)
+    r, out = _run_bench([a for a in small if a not in ("--scanlines", "16")] + ["--scanlines-total", "24", "--backend", g["backend"], "--full"], nproc=2, timeout=300)
     assert r is not None and r.returncode == 0 and out is not None, "" if r is None else (r.stderr or "")[-800:]
     assert out["scaling"] == "strong" and out["config"]["scan_lines_total"] == 24 and out["gather_check"]["equal"]
     assert out["ranks_seen"] == 2 and [p["rank"] for p in out["per_rank"]] == [0, 1] and all(p["trace_ms"] > 0 for p in out["per_rank"])
@@ -781,7 +781,7 @@ def test_two_ranks_gather_equals_single_process():
     # BASELINE C4's shape as it is sharded over GPUs: the 1 M-triangle scene, 256 scan-lines x 8192 rays over the two ranks; the
     # gathered whole B-mode frames (PSF, envelope, scan conversion after the gather) equal one process's, and the line explains itself
     r, out = _run_bench(["--workload", "random1m", "--scanlines-total", "256", "--rays", "8192", "--steps", "2", "--warmup", "2", "--frames-in-flight", "2",
-                         "--no-cpu-baseline", "--no-latency-leg", "--no-pmc", "--same-gpu", "--check-gather", "--min-time", "0.05", "--backend", g["backend"]], nproc=2, timeout=500)
+                         "--full", "--no-cpu-baseline", "--no-latency-leg", "--no-pmc", "--same-gpu", "--check-gather", "--min-time", "0.05", "--backend", g["backend"]], nproc=2, timeout=500)
     assert r is not None and r.returncode == 0 and out is not None, "" if r is None else (r.stderr or "")[-800:]
     assert out["scaling"] == "strong" and out["config"]["scan_lines_total"] == 256 and out["config"]["rays_per_scan_line"] == 8192
     assert out["gather_check"]["equal"] and out["gather_check"]["nonzero_bmode"] > 10000 and out["ranks_seen"] == 2
@@ -794,7 +794,7 @@ def test_eight_ranks_weak_and_ragged_strong():
     ragged split (100 scan-lines = four ranks of 13 and four of 12).  ranks_seen == 8, the gathered whole B-mode frames equal one process's bit
     for bit, and the N > 1 line carries the oracle's word on rank 0's own shard (`parity_check`), not only `gather_check`."""
     small = ["--workload", "sphere", "--rays", "64", "--steps", "4", "--warmup", "2", "--frames-in-flight", "2",
-             "--no-latency-leg", "--no-pmc", "--same-gpu", "--check-gather", "--min-time", "0.05", "--backend", "gloo"]
+             "--full", "--no-latency-leg", "--no-pmc", "--same-gpu", "--check-gather", "--min-time", "0.05", "--backend", "gloo"]
     r, out = _run_bench(small + ["--scanlines", "16"], nproc=8, timeout=900)
     assert r is not None and r.returncode == 0 and out is not None, "" if r is None else _why((r.stderr or "")[-6000:])
     assert out["n_gpus"] == 8 and out["ranks_seen"] == 8 and out["scaling"] == "weak" and out["config"]["scan_lines_total"] == 128
@@ -856,7 +856,7 @@ def test_bench_line_contract_and_inline_parity():
     """a small single-GPU bench run: the JSON contract keys, the inline parity check against the oracle, a VALU roofline with
     frac <= 1"""
     r, out = _run_bench(["--workload", "sphere", "--scanlines", "16", "--rays", "256", "--steps", "8", "--warmup", "4", "--frames-in-flight", "4",
-                         "--no-pmc", "--min-time", "0.05", "--check-gather"], timeout=300)
+                         "--full", "--no-pmc", "--min-time", "0.05", "--check-gather"], timeout=300)
     assert r is not None and r.returncode == 0 and out is not None, "" if r is None else (r.stderr or "")[-800:]
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "parity_check"):
         assert k in out, k
@@ -864,6 +864,30 @@ def test_bench_line_contract_and_inline_parity():
     assert out["parity_check"]["rf_bit_exact"] is True and out["parity_check"]["scan_lines"] == 16
     assert out["gather_check"]["equal"]
     assert out["roofline"]["bound"] == "valu" and out["cpu_baseline"]["kind"] == "port" and out["cpu_baseline"]["seconds"] >= 5.0
+
+
+def test_plain_bench_run_times_its_steps_once_and_dumps_its_outputs(tmp_path):
+    """a plain bench run (no --full): ONE timed region of exactly --steps steps, the headline keys and nothing of the --full legs; with
+    --dump-outputs the last step's B-mode and RF images as finite float32 .npy (+ where they were not finite), the same bits in two runs"""
+    args = ["--workload", "sphere", "--scanlines", "16", "--rays", "256", "--steps", "6", "--warmup", "3", "--frames-in-flight", "4"]
+    got = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r, out = _run_bench(args + ["--dump-outputs", str(d)], timeout=300)
+        assert r is not None and r.returncode == 0 and out is not None, "" if r is None else (r.stderr or "")[-800:]
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in out, key
+        assert out["steps"] == 6 and out["config"]["timed_region_repeats"] == 1 and out["config"]["passes_per_timed_region"] == [3, 3]
+        assert abs(out["value"] - 16 * 256 * 1e3 / out["ms_per_step"]) <= 1e-6 * out["value"]
+        for key in ("roofline", "cpu_baseline", "parity_check", "per_rank", "one_frame_at_a_time", "sweep"):
+            assert key not in out, key
+        files = [np.load(str(d / (f + ".npy"))) for f in ("bmode", "rf", "bmode_nonfinite", "rf_nonfinite")]
+        bmode, rf = files[0], files[1]
+        assert bmode.shape == files[2].shape == (400, 500) and rf.shape == files[3].shape == (16, 465)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files)
+        assert np.count_nonzero(rf) > 100 and np.count_nonzero(bmode) > 100
+        got.append(files)
+    assert all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(*got))
 
 
 def test_host_shim_surface(mcrt, orc, tex256, tmp_path):

@@ -12,7 +12,7 @@ except Exception as e: print(sys.argv[2], sys.argv[3], 'FAILED', e)
 PY
 }
 for lib in default licm default licm; do
-run C2 $lib --workload sphere --scanlines 128 --rays 1024 --rows 512 --steps 128 --warmup 128
-run C3 $lib --workload liver --scanlines 128 --rays 4096 --steps 32 --warmup 16 --frames-in-flight 16
-run C5 $lib --workload liver --scanlines 512 --rays 16384 --steps 4 --warmup 2 --frames-in-flight 2
+run C2 $lib --full --workload sphere --scanlines 128 --rays 1024 --rows 512 --steps 128 --warmup 128
+run C3 $lib --full --workload liver --scanlines 128 --rays 4096 --steps 32 --warmup 16 --frames-in-flight 16
+run C5 $lib --full --workload liver --scanlines 512 --rays 16384 --steps 4 --warmup 2 --frames-in-flight 2
 done

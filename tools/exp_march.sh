@@ -10,7 +10,7 @@ for name in "$@"; do
   echo "$name: pytest $(tail -1 $out/pytest_$name.log)" | tee -a $out/summary.txt
   fi
   for steps in ${STEPS:-20 128}; do
-    env MCRT_TUNING=1 $lib timeout 200 python bench.py --steps $steps --warmup $steps --no-cpu-baseline --no-pmc > $out/bench_${name}_$steps.log 2>&1
+    env MCRT_TUNING=1 $lib timeout 200 python bench.py --full --steps $steps --warmup $steps --no-cpu-baseline --no-pmc > $out/bench_${name}_$steps.log 2>&1
     python3 - $out/bench_${name}_$steps.log "$name" $steps <<'PY' | tee -a $out/summary.txt
 import json, sys
 try:

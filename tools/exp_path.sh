@@ -4,7 +4,7 @@
 out=gpurun_out/exp_path; mkdir -p $out
 for F in "${@:-1 2 3 4}"; do
   for pm in 0 100000000; do
-    env MCRT_TUNING=1 MCRT_PATH_MAX=$pm timeout 200 python bench.py --steps 24 --warmup 24 --frames-in-flight $F --no-cpu-baseline --no-pmc --no-latency-leg ${BENCH_ARGS} > $out/bench_${F}_$pm.log 2>&1
+    env MCRT_TUNING=1 MCRT_PATH_MAX=$pm timeout 200 python bench.py --full --steps 24 --warmup 24 --frames-in-flight $F --no-cpu-baseline --no-pmc --no-latency-leg ${BENCH_ARGS} > $out/bench_${F}_$pm.log 2>&1
     python3 - $out/bench_${F}_$pm.log $F $pm <<'PY' | tee -a $out/summary.txt
 import json, sys
 try:

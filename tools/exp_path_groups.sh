@@ -2,7 +2,7 @@
 out=gpurun_out/exp_path2; mkdir -p $out; rm -f $out/summary.txt
 for lib in default o32w4; do for G in 1 2 4 8; do
   L=""; [ $lib != default ] && L="MCRT_LIB=$PWD/mcray-tracing_amd/build/libmcrt_hip_$lib.so"
-  env MCRT_TUNING=1 MCRT_PATH_GROUPS=$G $L timeout 200 python bench.py --steps 24 --warmup 24 --frames-in-flight 1 --no-cpu-baseline --no-pmc --no-latency-leg > $out/b_${lib}_$G.log 2>&1
+  env MCRT_TUNING=1 MCRT_PATH_GROUPS=$G $L timeout 200 python bench.py --full --steps 24 --warmup 24 --frames-in-flight 1 --no-cpu-baseline --no-pmc --no-latency-leg > $out/b_${lib}_$G.log 2>&1
   python3 - $out/b_${lib}_$G.log $lib $G <<'PY' | tee -a $out/summary.txt
 import json, sys
 try:

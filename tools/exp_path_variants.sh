@@ -3,7 +3,7 @@
 out=gpurun_out/exp_path_variants; mkdir -p $out
 for lib in "$@"; do
   L=""; [ $lib != default ] && L="MCRT_LIB=$PWD/mcray-tracing_amd/build/libmcrt_hip_$lib.so"
-  env MCRT_TUNING=1 $L timeout 200 python bench.py --steps 24 --warmup 24 --frames-in-flight 1 --no-cpu-baseline --no-pmc --no-latency-leg > $out/b_${lib}.log 2>&1
+  env MCRT_TUNING=1 $L timeout 200 python bench.py --full --steps 24 --warmup 24 --frames-in-flight 1 --no-cpu-baseline --no-pmc --no-latency-leg > $out/b_${lib}.log 2>&1
   python3 - $out/b_${lib}.log $lib <<'PY' | tee -a $out/summary.txt
 import json, sys
 try:

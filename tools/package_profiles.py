@@ -114,15 +114,15 @@ box and packaged by `tools/package_profiles.py`, which also wrote this file from
 
 | file | what |
 |---|---|
-| `bench_unprofiled.json` | `python bench.py`: the JSON line (live PMC passes in child processes, CPU baseline, inline parity check, the per-kernel block `roofline.kernels`) |
-| `bench_driver_cmd.json` | `python bench.py --gpus 1 --steps 20 --warmup 5` (the driver's command: one 20-frame pass per timed region) |
+| `bench_unprofiled.json` | `python bench.py --full`: the JSON line (live PMC passes in child processes, CPU baseline, inline parity check, the per-kernel block `roofline.kernels`) |
+| `bench_driver_cmd.json` | `python bench.py --full --gpus 1 --steps 20 --warmup 5` (the driver's command: one 20-frame pass per timed region) |
 | `pmc_bench.json` | the PMC block of `bench_unprofiled.json`, the labelled fall-back `bench.py` reads when it cannot profile itself (N > 1) |
 | `kernel_stats.csv` | `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps @FIF@ --warmup @FIF@ --no-cpu-baseline --no-latency-leg --no-pmc` (kernels overlap as in production) |
 | `kernels_standalone.txt` | the same with `MCRT_TUNING=1 MCRT_NO_OVERLAP=1`: every kernel alone on the GPU |
 | `pmc_k_trace_lane.json`, `pmc_k_march.json`, `pmc_k_shade.json` | separate `--pmc` passes (tools/pmc.sh), per-launch averages + derived figures; the walk = `k_trace_lane<false>`, `k_trace_lane_wide` and bounce 1's `k_trace_packet`, pooled |
 | `frame_timeline.txt`, `frame_timeline_one_frame.txt` | start / duration of every launch of one pass: @FIF@ frames in flight, and one frame at a time |
 | `baseline_configs.txt` | the five BASELINE.json configurations on one GPU (tools/configs.sh) |
-| `bench_random16m.json` | `python bench.py --workload random16m`: the STREAMING regime (16 M triangles, 2 GB of BVH past the Infinity Cache) |
+| `bench_random16m.json` | `python bench.py --full --workload random16m`: the STREAMING regime (16 M triangles, 2 GB of BVH past the Infinity Cache) |
 | `group_bench.json` | `tools/group_bench.py 0,0`: whole B-mode frames through `mcrt_group_*` (two ranks sharing the GPU) against one context |
 | `bench_driver_cmd_k_path.json`, `bench_driver_cmd_wide.json`, `bench_driver_cmd_final.json` | the driver's command at three milestones of the round (the last: one frame at a time 0.872 ms): with `k_path` (one frame at a time 1.48 -> 1.11 ms), and with the kernels built without machine LICM + the five-wavefront walk from the first ray (0.386 -> 0.3595 ms per frame, one frame at a time 0.915 ms) |
 | `march_layout_count_random1m.json`, `exp_march_layout.txt` | `tools/march_layout_count.py` (CPU): 128-byte lines and 4-KiB regions `k_march`'s gathers touch for six device layouts of the 256^3 texture; the layouts built and measured (all slower: recorded loss) |

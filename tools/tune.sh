@@ -1,6 +1,7 @@
 #!/bin/bash
 # tuning sweep on the GPU box: parity first, then bench.py per spec.  spec = name[:VAR=VAL[,VAR=VAL...]]
 # (VAR LIB=<variant> selects mcray-tracing_amd/build/libmcrt_hip_<variant>.so)
+BENCH_ARGS="--full ${BENCH_ARGS}"      # (the summary line reads the roofline block, which only a --full run carries)
 mkdir -p gpurun_out/tune
 if [ -z "$SKIP_TESTS" ]; then
 (timeout 600 python -m pytest tests -m gpu -x -q --timeout 240 > gpurun_out/tune/pytest.log 2>&1; echo "pytest rc=$?" >> gpurun_out/tune/pytest.log); tail -4 gpurun_out/tune/pytest.log
