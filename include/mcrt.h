@@ -85,7 +85,7 @@ typedef struct {
 
 /* 128-byte BVH4 node, the BUILDERS' form: four 32-byte child records with float boxes -- what mcrt_build_bvh4 and the device builder
  * emit, what a refit updates and what this ABI exports.  The GPU walk reads a 64-byte copy made from it after every build / refit
- * (child-transposed half-float boxes rounded outwards, csrc/mcrt_kernels.hip k_nodes_walk); mcrt_get_bvh4 hands out that copy decoded
+ * (child-transposed half-float boxes rounded outwards, csrc/mcrt_walk.hip k_nodes_walk); mcrt_get_bvh4 hands out that copy decoded
  * back into this form, i.e. the tree exactly as walked.  ref: >= 0 inner node; < 0 leaf (as in mcrt_bvh_node, at most 4 triangles);
  * MCRT_BVH4_EMPTY = unused slot.  Built by collapsing the SAH BVH2. */
 #define MCRT_BVH4_EMPTY ((int32_t)0x80000000)

@@ -1,5 +1,5 @@
 // mcrt_api.cpp -- the C-ABI of include/mcrt.h: context, uploads, frame orchestration.
-// Host C++ only; kernels live in mcrt_kernels.hip.  No CPU fallback exists: every compute entry point
+// Host C++ only; kernels live in the mcrt_*.hip files (map: mcrt_kernels.h).  No CPU fallback exists: every compute entry point
 // needs the GPU context.
 #include "../../include/mcrt.h"
 #include "mcrt_internal.h"

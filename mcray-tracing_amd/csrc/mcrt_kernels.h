@@ -1,4 +1,17 @@
-// mcrt_kernels.h -- kernel argument blocks and launchers (mcrt_kernels.hip <-> mcrt_api.cpp)
+// mcrt_kernels.h -- kernel argument blocks and launchers: the interface between mcrt_api.cpp (plain C++) and the gfx950 kernels.
+//
+// The hot path's kernels, one translation unit per pipeline stage, each kernel beside its launcher:
+//   mcrt_walk.hip    k_trace_lane / k_trace_lane_wide (closest hit, one lane per ray), k_trace_packet (one wavefront per ray packet),
+//                    k_nodes_walk / k_nodes_walk_decode (the walk's 64-byte nodes)
+//   mcrt_shade.hip   k_init (the first ray of every path), k_shade (interface physics of a bounce, survivors compacted into the next queue)
+//   mcrt_path.hip    k_path (the latency form: every bounce of every path in one launch)
+//   mcrt_march.hip   k_march (RF accumulation of the segments), k_material_table
+//   mcrt_post.hip    k_finalize, k_clear_flags, k_conv_*, k_envelope, k_remap, k_transpose, k_blocks_to_frames
+//   mcrt_scene.hip   k_tris_by_id, k_expand_tris; the probes k_math_probe, k_verify_div, k_philox_probe
+//   mcrt_lbvh.hip    the device BVH builder (mcrt_lbvh.h)
+// Shared device code: mcrt_device.h (primitives and the knobs more than one unit reads), mcrt_walk.h (the lane walk's steps, also k_path's),
+// mcrt_shade.h (shade_path, also k_path's).  Everything is scalar fp32/fp64 VALU + integer work -- no dense contraction, hence no MFMA --
+// and the arithmetic follows the parity contract expression by expression (compiled -ffp-contract=off).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

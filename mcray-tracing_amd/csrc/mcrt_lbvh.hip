@@ -63,7 +63,7 @@ __global__ void k_scale(const float *tri, size_t n9, Scal *s)
 
 __global__ void k_pad(Scal *s) { s->pad_abs = 4e-6f * fmaxf(__uint_as_float(s->scale_bits), 1e-3f); }   // == mcrt_build_bvh
 
-// padded bounds of triangle t -- bit for bit what k_expand_tris (mcrt_kernels.hip) and mcrt_build_bvh (mcrt_host.cpp) compute
+// padded bounds of triangle t -- bit for bit what k_expand_tris (mcrt_scene.hip) and mcrt_build_bvh (mcrt_host.cpp) compute
 __global__ void k_prims(const float *tri, uint32_t n, Scal *s, float4 *plo, float4 *phi, float4 *pc)
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -283,7 +283,7 @@ __global__ void k_refit_records(const float *tri, const float4 *old_rec, uint32_
     const uint32_t id = __float_as_uint(id_rec.w);
     const float *v = tri + (size_t)id * 9;
     const float v0x = v[0], v0y = v[1], v0z = v[2], v1x = v[3], v1y = v[4], v1z = v[5], v2x = v[6], v2y = v[7], v2z = v[8];
-    // the contract's expressions, exactly as k_expand_tris (mcrt_kernels.hip) evaluates them
+    // the contract's expressions, exactly as k_expand_tris (mcrt_scene.hip) evaluates them
     const float ax = v1x - v0x, ay = v1y - v0y, az = v1z - v0z, bx = v2x - v0x, by = v2y - v0y, bz = v2z - v0z;
     const float nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
     const float edge_tol = (nx * nx + ny * ny + nz * nz) * -0.0001f;

@@ -1,0 +1,203 @@
+// mcrt_post.hip -- after the accumulation: k_finalize (fixed-point RF bins -> float image, rf_image::clear rfimage.h:161), k_conv_*
+// (rf_image::convolve, rfimage.h:93-123), k_envelope (rfimage.h:54-91), k_remap (the scan conversion of rf_image::postprocess,
+// rfimage.h:125-140), k_transpose, and k_blocks_to_frames (the ranks' blocks of an mcrt_group laid out as frames).
+#include "mcrt_device.h"
+
+namespace mcrt {
+
+// fixed-point bins -> float RF image [ne][R]; clears the bins for the next frame.  A frame whose launches set the context's device
+// error word (a persistent kernel abandoned by its watchdog, a traversal stack that ran out) is written as NaN throughout: a caller that
+// synchronises on its own stream and never asks mcrt_synchronize cannot mistake it for an image.
+__global__ void k_finalize(long long *acc, uint32_t *flags, float *rf, uint32_t ne, uint32_t R, const uint32_t *error_flag)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)ne * R) return;
+    const uint32_t e = (uint32_t)(i / R), r = (uint32_t)(i % R);
+    const uint32_t nf = (R + 31u) >> 5;
+    const bool bad = ((flags[(size_t)e * nf + (r >> 5)] >> (r & 31)) & 1u) || *error_flag != 0u;
+    const long long v = acc[i];
+    rf[i] = bad ? __uint_as_float(0x7fc00000u) : (float)((double)v * 0x1p-40);
+    acc[i] = 0;
+}
+__global__ void k_clear_flags(uint32_t *flags, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) flags[i] = 0u;
+}
+
+// rfimage.h:96-108 on the scan-line-major image: tmp[e][row] = sum_k img[e][row+k]*ax[k], row in [na, R-na)
+// (both passes take a stack of n_img images [n_img][E][R] at once: one launch for all the frames of a pass)
+__global__ void k_conv_axial(const float *img, float *tmp, uint32_t n_img, uint32_t E, uint32_t R, ConvTaps taps)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n_img * E * R) return;
+    const int row = (int)(i % R), na = (int)taps.n_ax;
+    if (row < na || row >= (int)R - na) return;
+    float conv = 0;
+    for (int k = 0; k < na; k++) conv += img[i + k] * taps.ax[k];
+    tmp[i] = conv;
+}
+// rfimage.h:111-122: img[col][row] = sum_k tmp[col+k][row]*lat[k], row in [na,R-na), col in [nl/2, E-nl)
+__global__ void k_conv_lateral(const float *tmp, float *img, uint32_t n_img, uint32_t E, uint32_t R, ConvTaps taps)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n_img * E * R) return;
+    const int row = (int)(i % R), col = (int)((i / R) % E), na = (int)taps.n_ax, nl = (int)taps.n_lat;
+    if (row < na || row >= (int)R - na) return;
+    if (col < nl / 2 || col >= (int)E - nl) return;
+    float conv = 0;
+    for (int k = 0; k < nl; k++) conv += tmp[i + (size_t)k * R] * taps.lat[k];
+    img[i] = conv;
+}
+
+// rfimage.h:54-91, one WAVEFRONT per scan-line.  The reference walks a column once: whenever the signal stops ascending at row i
+// (a concave peak), the rows [last peak, i) are overwritten with the line from |last peak| to |c[i]|.  The comparisons only ever
+// read rows the walk has not overwritten yet, so the peaks are a pure function of the input column:
+//     peak(i) = (c[i-1] < c[i]) && !(c[i] < c[i+1]),  1 <= i <= R-2      (`ascending` after step j is exactly c[j] < c[j+1])
+// and row j becomes  last*(1-alpha) + next*alpha  with last / next the peaks around it (prev <= j < next; before the first peak
+// `last` is the signed c[0] at row 0, rfimage.h:64), rows after the last peak stay.  Same float expressions as the sequential loop,
+// evaluated by 64 lanes from an LDS copy of the column: previous / next peak by a wave-wide max / min scan over lane-contiguous chunks.
+// (One lane per column, the round-2 kernel, is a chain of 465 dependent global loads: 650 us per call however few the columns.)
+__global__ void __launch_bounds__(64) k_envelope(float *img, uint32_t E, uint32_t R)
+{
+    __shared__ float col[MCRT_MAX_ROWS];
+    __shared__ unsigned short prv[MCRT_MAX_ROWS], nxt[MCRT_MAX_ROWS];
+    const uint32_t lane = threadIdx.x;
+    if (blockIdx.x >= E || R < 2) return;
+    float *c = img + (size_t)blockIdx.x * R;
+    for (uint32_t r = lane; r < R; r += 64u) col[r] = c[r];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier();
+    const uint32_t per = (R + 63u) / 64u, r0 = min(R, lane * per), r1 = min(R, r0 + per);
+    constexpr uint32_t NONE = 0xffffu;
+    auto peak = [&](uint32_t i) { return i >= 1u && i + 1u < R && (col[i - 1u] < col[i]) && !(col[i] < col[i + 1u]); };
+    // last peak at or before each row (0 = the start of the column), first peak after it
+    uint32_t last = 0u, first = NONE;
+    for (uint32_t i = r0; i < r1; i++) if (peak(i)) { last = i; if (first == NONE) first = i; }
+    uint32_t before = last, after = first;                    // inclusive scans over the lanes' chunks ...
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)before, d, 64), dn = (uint32_t)__shfl_down((int)after, d, 64);
+        if ((int)lane >= d) before = max(before, up);
+        if ((int)lane + d < 64) after = min(after, dn);
+    }
+    uint32_t run_prev = (uint32_t)__shfl_up((int)before, 1, 64), run_next = (uint32_t)__shfl_down((int)after, 1, 64);      // ... made exclusive
+    if (lane == 0u) run_prev = 0u;
+    if (lane == 63u) run_next = NONE;
+    for (uint32_t i = r0; i < r1; i++) { if (peak(i)) run_prev = i; prv[i] = (unsigned short)run_prev; }
+    for (uint32_t i = r1; i > r0; i--) { nxt[i - 1u] = (unsigned short)run_next; if (peak(i - 1u)) run_next = i - 1u; }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier();
+    for (uint32_t j = lane; j < R; j += 64u) {
+        const uint32_t p = prv[j], q = nxt[j];
+        if (q == NONE) continue;                               // past the last peak: untouched
+        const float last_peak = p == 0u ? col[0] : fabsf(col[p]), new_peak = fabsf(col[q]);
+        const float alpha = ((float)j - (float)p) / ((float)q - (float)p);
+        c[j] = last_peak * (1 - alpha) + new_peak * alpha;
+    }
+}
+
+// cv::remap(src, dst, map_y, map_x, INTER_LINEAR, BORDER_CONSTANT 0) with precomputed maps (rfimage.h:139):
+// mx = column coordinate (scan-line), my = row coordinate.  src is [E][R] scan-line-major.
+__global__ void k_remap(const float *img, uint32_t E, uint32_t R, const float *map_col, const float *map_row, float *out, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    img += (size_t)blockIdx.y * E * R; out += (size_t)blockIdx.y * n;          // image blockIdx.y of a stack [n_img][E][R] -> [n_img][n]
+    const float mx = map_col[i], my = map_row[i];
+    const float fx = floorf(mx), fy = floorf(my);
+    const float ax = mx - fx, ay = my - fy;
+    const long long x0 = (long long)fx, y0 = (long long)fy;
+    float v[2][2];
+#pragma unroll
+    for (int dy = 0; dy < 2; dy++)
+#pragma unroll
+        for (int dx = 0; dx < 2; dx++) {
+            const long long xx = x0 + dx, yy = y0 + dy;
+            const bool in = (mx == mx) && (my == my) && xx >= 0 && yy >= 0 && xx < (long long)E && yy < (long long)R;
+            v[dy][dx] = in ? img[(size_t)xx * R + (size_t)yy] : 0.0f;
+        }
+    const float top = v[0][0] * (1.0f - ax) + v[0][1] * ax;
+    const float bot = v[1][0] * (1.0f - ax) + v[1][1] * ax;
+    out[i] = top * (1.0f - ay) + bot * ay;
+}
+
+// [E][R] -> [R][E]
+__global__ void k_transpose(const float *in, float *out, uint32_t E, uint32_t R)
+{
+    __shared__ float tile[32][33];
+    const uint32_t r0 = blockIdx.x * 32, e0 = blockIdx.y * 32;
+    for (int j = threadIdx.y; j < 32; j += blockDim.y) {
+        const uint32_t e = e0 + j, r = r0 + threadIdx.x;
+        if (e < E && r < R) tile[j][threadIdx.x] = in[(size_t)e * R + r];
+    }
+    __syncthreads();
+    for (int j = threadIdx.y; j < 32; j += blockDim.y) {
+        const uint32_t r = r0 + j, e = e0 + threadIdx.x;
+        if (e < E && r < R) out[(size_t)r * E + e] = tile[threadIdx.x][j];
+    }
+}
+
+// The ranks' blocks, as they arrive from the other GPUs -- rank g's [F][ne_g][R] one after the other -- laid out as the frames
+// [F][E][R] a single context would have written (mcrt_group_trace_frames): one float4 per lane where R allows, else scalars.
+// off[g] = first scan-line of rank g (off[G] = E); the block of rank g starts at float offset F * off[g] * R of `blocks`.
+struct GroupOffsets { uint32_t off[65]; };
+template <typename V>
+__global__ void k_blocks_to_frames(const V *blocks, V *frames, uint32_t F, uint32_t E, uint32_t Rv, uint32_t G, GroupOffsets o)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;          // element of `frames`
+    if (i >= (size_t)F * E * Rv) return;
+    const uint32_t r = (uint32_t)(i % Rv), e = (uint32_t)((i / Rv) % E), f = (uint32_t)(i / ((size_t)Rv * E));
+    uint32_t g = 0;
+    while (g + 1u < G && e >= o.off[g + 1u]) g++;
+    const uint32_t ne = o.off[g + 1u] - o.off[g];
+    frames[i] = blocks[((size_t)F * o.off[g] + (size_t)f * ne + (e - o.off[g])) * Rv + r];
+}
+
+hipError_t launch_finalize(long long *acc, uint32_t *flags, float *rf, uint32_t ne, uint32_t R, const uint32_t *error_flag, hipStream_t st)
+{
+    const size_t n = (size_t)ne * R;
+    hipLaunchKernelGGL(k_finalize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, acc, flags, rf, ne, R, error_flag);
+    const size_t nf = (size_t)ne * ((R + 31u) >> 5);
+    hipLaunchKernelGGL(k_clear_flags, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, flags, nf);
+    return hipGetLastError();
+}
+
+hipError_t launch_convolve(float *img, float *tmp, uint32_t n_img, uint32_t E, uint32_t R, const ConvTaps &taps, hipStream_t st)
+{
+    const size_t n = (size_t)n_img * E * R;
+    const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
+    hipLaunchKernelGGL(k_conv_axial, grid, blk, 0, st, (const float *)img, tmp, n_img, E, R, taps);
+    hipLaunchKernelGGL(k_conv_lateral, grid, blk, 0, st, (const float *)tmp, img, n_img, E, R, taps);
+    return hipGetLastError();
+}
+
+hipError_t launch_envelope(float *img, uint32_t E, uint32_t R, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_envelope, dim3(E), dim3(64), 0, st, img, E, R);
+    return hipGetLastError();
+}
+
+hipError_t launch_remap(const float *img, uint32_t n_img, uint32_t E, uint32_t R, const float *map_col, const float *map_row, float *out, uint32_t n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_remap, dim3((n + 255) / 256, n_img), dim3(256), 0, st, img, E, R, map_col, map_row, out, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_blocks_to_frames(const float *blocks, float *frames, uint32_t F, uint32_t E, uint32_t R, uint32_t G, const uint32_t *off, hipStream_t st)
+{
+    GroupOffsets o;
+    for (uint32_t g = 0; g <= G && g < 65u; g++) o.off[g] = off[g];
+    const bool vec = (R % 4u) == 0u && ((uintptr_t)blocks % 16u) == 0u && ((uintptr_t)frames % 16u) == 0u;
+    const uint32_t Rv = vec ? R / 4u : R;
+    const size_t n = (size_t)F * E * Rv;
+    if (vec) hipLaunchKernelGGL((k_blocks_to_frames<float4>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float4 *)blocks, (float4 *)frames, F, E, Rv, G, o);
+    else hipLaunchKernelGGL((k_blocks_to_frames<float>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, blocks, frames, F, E, Rv, G, o);
+    return hipGetLastError();
+}
+
+hipError_t launch_transpose(const float *in, float *out, uint32_t E, uint32_t R, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_transpose, dim3((R + 31) / 32, (E + 31) / 32), dim3(32, 8), 0, st, in, out, E, R);
+    return hipGetLastError();
+}
+
+}  // namespace mcrt

@@ -1,0 +1,164 @@
+// mcrt_shade.hip -- the stages of the wavefront pipeline around the walk: k_init (the first ray of every path) and k_shade (the interface
+// physics of a bounce's live rays, survivors compacted into the next bounce's queue).
+#include "mcrt_device.h"
+#include "mcrt_shade.h"
+
+#ifndef MCRT_SHADE_WAVES
+#define MCRT_SHADE_WAVES 5             // k_shade wavefronts per SIMD the register budget is set for
+#endif
+
+namespace mcrt {
+
+// =============================================================================================================
+// The frame is a WAVEFRONT pipeline that mirrors the reference's own structure (scene::cast_rays produces segments,
+// main.cpp:106-144 consumes them), one launch per stage and bounce, queues of live paths in HBM between stages:
+//
+//   k_init            first_ray of every (scan-line, sample) path, scene.cpp:83-101            1 lane  / path
+//   for bounce b:
+//     k_trace_lane    closest hit of every live ray: BVH4 walk                                  1 lane  / ray
+//     k_shade         thickness draw, travel, hit_boundary, segment record, next ray;           1 lane  / ray
+//                     survivors are compacted into the next bounce's queue (wave ballot + prefix)
+//   k_march           RF accumulation of every segment (main.cpp:112-140)                       2 lanes / segment
+//
+// Every stage therefore runs with full wavefronts of lanes doing the same thing: dead paths cost nothing after the
+// bounce they die in, the fp64-heavy interface physics is not replicated, and the lean walk kernel keeps 5 waves/SIMD.
+// Paths draw random numbers from their own (scan-line, sample, bounce) counter and RF bins are integer sums, so the
+// image does not depend on queue order.  Path state, rays and closest-hit words live in QUEUE ORDER and are compacted with
+// the queue every bounce (ping-pong halves by bounce parity): every launch reads and writes them densely and coalesced.
+// (Round 3 measured the alternative the sample loop of scene.cpp:102-110 suggests -- queues SORTED into bundles of the sample
+// paths of a scan-line with the same reflect / refract history, path state in place by path id: 58 vs 56 % of the walk's lanes
+// active, the pass 8 % slower; DESIGN.md A.4, profiles/round3/exp_*.)
+// =============================================================================================================
+
+__global__ void __launch_bounds__(256) k_init(FrameArgs a)
+{
+    const uint32_t pos = blockIdx.x * blockDim.x + threadIdx.x;          // this thread fills queue position `pos`
+    const uint32_t np = a.ne * a.S;
+    if (pos == 0) { a.counts[0] = np; for (uint32_t b = 1; b <= a.B; b++) a.counts[b] = 0u; }
+    if (pos < MCRT_MAX_BOUNCES * MCRT_XCDS) a.cursors[(size_t)pos * MCRT_CURSOR_STRIDE] = 0u;   // k_trace_lane's queue cursors (relative, see there)
+    if (pos >= np) return;
+    // Queue position -> path.  Paths are numbered frame-major (pid = (frame * ne_frame + scan-line) * S + sample) but QUEUED
+    // scan-line-major: the F frames of a scan-line sit next to each other.  The queue is swept in order, so the rays in flight
+    // then belong to a few scan-lines (times all frames) and walk the same part of the BVH; later bounces inherit the order
+    // from the order-preserving compaction of k_shade.
+    const uint32_t F = a.ne / a.ne_frame;
+    const uint32_t qline = pos / a.S, sample = pos % a.S;
+    const uint32_t scan = qline / F, fr = qline % F;
+    const uint32_t pid = (fr * a.ne_frame + scan) * a.S + sample;
+    const size_t pe = (size_t)fr * a.pose_stride + a.e_begin + scan;      // pose_stride = 0: one probe pose for every frame of the pass (transducer.h:64-67)
+    const f3 from = mk(a.el_pos[3 * pe], a.el_pos[3 * pe + 1], a.el_pos[3 * pe + 2]);
+    const f3 dir = mk(a.el_dir[3 * pe], a.el_dir[3 * pe + 1], a.el_dir[3 * pe + 2]);
+    const float intensity = a.I0 / (float)a.S;
+    // Every sample path of a scan-line starts as a copy of the same first_ray (scene.cpp:83-101): the state of bounce 0 is written ONCE per queued
+    // (scan-line, frame), at its first sample's position -- where the walk reads it (ray_stride) and where k_shade / k_path look it up for all S samples
+    // (MCRT_STATE0_AT) -- instead of S times (48 B x 2.6 M paths per 20-frame pass written here and read back by k_shade).
+    if (sample == 0u) {
+        a.st0[pos] = make_float4(from.x, from.y, from.z, ray_len(intensity, a.mats[2 * a.start_mat].y, a));   // origin | length factor of the ray (ray_of)
+        a.st1[pos] = make_float4(dir.x, dir.y, dir.z, __int_as_float((int)a.start_mat));
+        a.st2[pos] = make_float4(0.0f, 0.0f, __int_as_float(OUT_NONE), intensity);  // distance_traveled (double) | outside | intensity
+    }
+    a.queue[pos] = pid;                                  // queue of bounce 0 (buffer 0 of two)
+    a.seg_count[pid] = 0u;
+    if (pos < a.ne) a.key0[pos] = MCRT_KEY_MISS;          // bounce 0: one closest-hit word per queued (scan-line, frame)
+}
+
+// ---- interface interaction of a bounce's live rays: one lane per ray ----
+template <bool STATS>
+__global__ void __launch_bounds__(256, MCRT_SHADE_WAVES) k_shade(FrameArgs a, uint32_t b)
+{
+    const uint32_t n = a.counts[b];
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (blockIdx.x * blockDim.x >= n) return;
+    const int lane = threadIdx.x & 63;
+    // the scene's material and mesh tables in LDS when they fit (they nearly always do: the reference's scenes have 9 materials and <= 11 meshes):
+    // a ray looks up five material rows and one mesh row -- a quarter of this kernel's cache accesses, and the frame is bound by their sum
+    __shared__ float4 mats_l[2 * MCRT_SHADE_TABLE];
+    __shared__ uint4 meshes_l[MCRT_SHADE_TABLE];
+    const bool tables_in_lds = a.n_mat <= (uint32_t)MCRT_SHADE_TABLE && a.n_mesh <= (uint32_t)MCRT_SHADE_TABLE;
+    if (tables_in_lds) {
+        for (uint32_t r = threadIdx.x; r < 2u * a.n_mat; r += blockDim.x) mats_l[r] = a.mats[r];
+        for (uint32_t r = threadIdx.x; r < a.n_mesh; r += blockDim.x) meshes_l[r] = a.meshes[r];
+        __syncthreads();
+    }
+    const ShadeTables tb = { a.mats, a.meshes, mats_l, meshes_l, tables_in_lds };
+    // two queue buffers, ping-pong by bounce parity (like the path state)
+    const uint32_t *q_in = a.queue + (size_t)(b & 1u) * a.ne * a.S;
+    uint32_t *q_out = a.queue + (size_t)((b + 1u) & 1u) * a.ne * a.S;
+    const bool valid = i < n;
+    bool alive = false, reflected = false;
+    uint32_t pid = 0;
+    PathState ps; ps.from = mk(0, 0, 0); ps.dir = mk(0, 0, 1); ps.intensity = 0.0f; ps.media = 0; ps.outside = OUT_NONE; ps.dist_mm = 0.0;
+    unsigned long long st_seg = 0, st_hits = 0;
+    if (valid) {
+        pid = q_in[i];
+        // path state lives in queue order (ping-pong halves by bounce parity), so a wavefront reads and writes it coalesced
+        const size_t sin = (size_t)(b & 1u) * a.ne * a.S + (b == 0u ? MCRT_STATE0_AT(i, a.S) : i);
+        const float4 s0 = a.st0[sin], s1 = a.st1[sin], s2 = a.st2[sin];
+        ps.from = mk(s0.x, s0.y, s0.z); ps.intensity = s2.w;
+        ps.dir = mk(s1.x, s1.y, s1.z); ps.media = __float_as_int(s1.w);
+        ps.dist_mm = __hiloint2double(__float_as_int(s2.y), __float_as_int(s2.x));
+        ps.outside = __float_as_int(s2.z);
+        const Ray ry = ray_of(ps.from, ps.dir, s0.w, a);          // the segment the walk tested (same expressions, same bits)
+        const f3 f2 = ry.f2, to = ry.to;
+        const size_t hi = (b == 0u) ? (size_t)(i / a.S) : (size_t)i;            // bounce 0: one walk per queued (scan-line, frame) (see k_trace_lane, k_init)
+        const unsigned long long key = ((b & 1u) ? a.key1 : a.key0)[hi];
+        alive = shade_path<STATS>(a, tb, b, pid, ps, f2, to, key, reflected, st_seg, st_hits);
+    }
+    const f3 from = ps.from, dir = ps.dir; const float intensity = ps.intensity; const int media = ps.media, outside = ps.outside; const double dist_mm = ps.dist_mm;
+
+    // survivors -> next bounce's queue (ballot + prefix; ONE atomic per workgroup: tens of thousands of returning atomics on the
+    // single counter would serialise in L2 and bound the kernel).  Inside a workgroup's block the reflected rays
+    // come first, then the refracted ones, each in queue order: the samples of a scan-line that took the same decisions stay
+    // adjacent, so the rays of a k_trace_lane wavefront mostly belong to a few tight bundles (same nodes, similar walk length).
+    __shared__ uint32_t wave_live[4], wave_refl[4], block_base;
+    const unsigned long long live = __ballot(alive);
+    const unsigned long long live_refl = __ballot(alive && reflected);
+    const int wv = threadIdx.x >> 6;
+    if (lane == 0) { wave_live[wv] = (uint32_t)__popcll(live); wave_refl[wv] = (uint32_t)__popcll(live_refl); }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t total = wave_live[0] + wave_live[1] + wave_live[2] + wave_live[3];
+        block_base = total ? atomicAdd(&a.counts[b + 1u], total) : 0u;
+    }
+    __syncthreads();
+    if (live) {
+        // (round 5: reflected-first over the WORKGROUP's 256 rays, not per wavefront -- three of the next bounce's four 64-ray blocks are then of one history,
+        //  which is what a ray packet wants, k_trace_packet)
+        const uint32_t refl_all = wave_refl[0] + wave_refl[1] + wave_refl[2] + wave_refl[3];
+        uint32_t refl_before = 0, refr_before = 0;
+        for (int w = 0; w < wv; w++) { refl_before += wave_refl[w]; refr_before += wave_live[w] - wave_refl[w]; }
+        if (alive) {
+            const unsigned long long below = (1ull << lane) - 1ull;
+            const uint32_t pos = block_base + (reflected ? refl_before + (uint32_t)__popcll(live_refl & below)
+                                                         : refl_all + refr_before + (uint32_t)__popcll(live & ~live_refl & below));
+            q_out[pos] = pid;
+            ((b & 1u) ? a.key0 : a.key1)[pos] = MCRT_KEY_MISS;            // the next bounce's closest-hit word of this ray
+            const size_t so = (size_t)((b + 1u) & 1u) * a.ne * a.S + pos;
+            a.st0[so] = make_float4(from.x, from.y, from.z, ray_len(intensity, tb.mat(2 * media).y, a));   // origin | the next ray's length factor
+            a.st1[so] = make_float4(dir.x, dir.y, dir.z, __int_as_float(media));
+            a.st2[so] = make_float4(__int_as_float(__double2loint(dist_mm)), __int_as_float(__double2hiint(dist_mm)), __int_as_float(outside), intensity);
+        }
+    }
+    if (STATS) {
+        long long x = wave_sum_i64((long long)st_seg), y = wave_sum_i64((long long)st_hits);
+        if (lane == 0) { if (x) atomicAdd(&a.stats[3], (unsigned long long)x); if (y) atomicAdd(&a.stats[5], (unsigned long long)y); }
+    }
+}
+
+hipError_t launch_init(const FrameArgs &a, hipStream_t st)
+{
+    const uint32_t np = a.ne * a.S;
+    hipLaunchKernelGGL(k_init, dim3((np + 255u) / 256u), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_shade(const FrameArgs &a, uint32_t b, bool stats, hipStream_t st)
+{
+    const uint32_t np = a.ne * a.S;
+    const dim3 grid((np + 255u) / 256u), blk(256);
+    if (stats) hipLaunchKernelGGL((k_shade<true>), grid, blk, 0, st, a, b);
+    else hipLaunchKernelGGL((k_shade<false>), grid, blk, 0, st, a, b);
+    return hipGetLastError();
+}
+
+}  // namespace mcrt

@@ -99,3 +99,15 @@ def test_walk_kernel_keeps_its_register_budget():
     assert getw("VGPRs") <= 80 and getw("SGPRs Spill") == 0 and getw(r"ScratchSize \[bytes/lane\]") <= 64, wide[0][:900]
     march = [b for b in blocks if b.startswith("_ZN4mcrt7k_marchILb0ELi2ELb1EEE")]
     assert march and int(re.search(r"VGPRs: (\d+)", march[0]).group(1)) <= 80
+    # the other kernels of the frame: nothing spilled to scratch, and at least the wavefronts per SIMD their source budgets registers for
+    # (k_march spills scalar registers into vector lanes, which costs no scratch: its SGPR spills are not asserted on)
+    src = "".join(open(os.path.join(pkg, "csrc", f)).read() for f in ("mcrt_walk.hip", "mcrt_shade.hip", "mcrt_path.hip", "mcrt_march.hip"))
+    waves = lambda knob: int(re.search(r"#define " + knob + r" (\d+)", src).group(1))
+    budgets = {"_ZN4mcrt17k_trace_lane_wide": waves("MCRT_LANE_WIDE_WAVES"), "_ZN4mcrt14k_trace_packetE": 1,
+               "_ZN4mcrt7k_shadeILb0EEE": waves("MCRT_SHADE_WAVES"), "_ZN4mcrt6k_pathE": waves("MCRT_PATH_WAVES"), "_ZN4mcrt7k_marchI": waves("MCRT_MARCH_WAVES")}
+    for prefix, budget in budgets.items():
+        found = [b for b in blocks if b.startswith(prefix)]
+        assert len(found) == (6 if prefix == "_ZN4mcrt7k_marchI" else 1), (prefix, out[-2000:])
+        for b in found:
+            val = lambda key: int(re.search(key + r": (\d+)", b).group(1))
+            assert val("VGPRs Spill") == 0 and val(r"ScratchSize \[bytes/lane\]") == 0 and val(r"Occupancy \[waves/SIMD\]") >= budget, b[:900]

@@ -128,7 +128,7 @@ __global__ void __launch_bounds__(256) k_roof(Stamp *out, int iters, float seed,
                 : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(a3), "+v"(px), "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a4), "+v"(a5), "+v"(u0), "+v"(u1), "+v"(u2)
                 : "v"(x), "v"(y), "v"(a6), "v"(a7) : "vcc", "s10", "s11");
         } else if constexpr (KIND == WALK_MIX_LANE) {
-            // the register-only part of lane_node_step (mcrt_kernels.hip) as rounds 3-4 compile it, in its dependency structure -- 91 VALU:
+            // the register-only part of lane_node_step (mcrt_walk.h) as rounds 3-4 compile it, in its dependency structure -- 91 VALU:
             // 12 v_cndmask (near / far packed plane words by the sign of the reciprocal direction), 24 v_fma_mix_f32 (plane distances from the
             // half operands), per child v_max / v_max3 / v_min / v_min3 / v_cmp_le (20), per child key = v_and_or + v_cndmask (8), 3 v_min_u32
             // (nearest key), v_cmp_eq (no hit child), 4 v_cmp_ne (children to push), 3 v_cndmask + 2 v_add (store offsets of the branch-free
