@@ -29,10 +29,11 @@
 extern "C" {
 #endif
 
-#define MCRT_VERSION 106   /* round 3: + mcrt_trace_frames_poses, mcrt_envelope_frames, mcrt_scan_convert_frames; the slab rule of the closest-hit contract is one fma per plane;
+#define MCRT_VERSION 107   /* round 3: + mcrt_trace_frames_poses, mcrt_envelope_frames, mcrt_scan_convert_frames; the slab rule of the closest-hit contract is one fma per plane;
                               104: + the test hooks mcrt_debug_set_error, mcrt_debug_fast_paths; RF images are NaN while the device error word is set;
                               105 (round 4): + mcrt_group_* (several GPUs behind one call), mcrt_scan_maps; the scan-conversion maps follow the reference's float promotions;
-                              106 (round 5): environment knobs are only read under MCRT_TUNING=1; the HIP-graph replay of passes (MCRT_GRAPH) is gone */
+                              106 (round 5): environment knobs are only read under MCRT_TUNING=1; the HIP-graph replay of passes (MCRT_GRAPH) is gone;
+                              107: + mcrt_default_bmode, mcrt_bmode_frames (log-compressed 8-bit B-mode frames: dynamic range, gain, TGC, persistence) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -207,6 +208,52 @@ int mcrt_scan_maps(uint32_t n_elements, uint32_t n_rows, double radius_mm, doubl
 int mcrt_scan_convert_frames(mcrt_ctx *ctx, const float *rf_dev, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
                              double radius_mm, double total_angle_rad, float *out_dev, uint32_t out_rows, uint32_t out_cols);
 
+/* ---- the displayed picture: log-compressed 8-bit B-mode frames (rfimage.h:131-136 planned it and left it commented out; rfimage.h:142-147
+ * saves 8-bit grey).  An opt-in stage after mcrt_convolve_frames / mcrt_envelope_frames, in place of mcrt_scan_convert_frames. */
+enum { MCRT_BMODE_DB = 0,        /* decibels below a reference amplitude: the clinical display                  */
+       MCRT_BMODE_REF_LOG = 1 }; /* log10(a+1)/log10(ref+1): the reference's commented-out rfimage.h:131-136     */
+typedef struct {
+    uint32_t mode;               /* MCRT_BMODE_*                                                  (DB)       */
+    float    dynamic_range_db;   /* DB: grey 0 at -DR dB below ref, > 0 and finite                (60)       */
+    float    gain_db;            /* DB: added before the range is applied, finite                 (0)        */
+    float    ref;                /* reference amplitude; <= 0: each frame's own peak (auto)       (0)        */
+    float    persistence;        /* alpha in [0,1): temporal smoothing across frames              (0)        */
+    uint32_t reset_state;        /* 1: the first frame of this call starts the smoothing afresh   (1)        */
+    uint32_t out_rows, out_cols; /* scan-converted size                                           (400, 500) */
+    double   radius_mm, total_angle_rad;  /* as mcrt_scan_convert                                (30, pi/3) */
+} mcrt_bmode_params;             /* 48 bytes; the doubles at offsets 32 and 40 */
+/* the defaults above; host only, no GPU needed */
+int mcrt_default_bmode(mcrt_bmode_params *p);
+/* rf_dev: device float [n_frames][n_elements][n_rows] (any image; normally enveloped) -> out_dev: device bytes [n_frames][out_rows][out_cols],
+ * the row-major layout of mcrt_scan_convert_frames with one byte per pixel.  Asynchronous on the context's stream; every launch covers all the
+ * frames (the grey level of each RF tap, then their scan conversion; the peaks first with the automatic reference).  For each frame f and
+ * each RF tap v at (scan-line e, row r):
+ *   1. amplitude   a = |v| * k[r], k[r] = (float)pow(10.0, tgc_db[r] / 20.0) computed in double on the host (1 without tgc_db); a NaN or
+ *                  infinite a counts as no echo, a = 0 (the reference's NaN scan-lines, sanitize_tir = 0, neither blank a frame nor set its peak)
+ *   2. reference   ref_f = p->ref if p->ref > 0, else the largest a of the frame (exact; order-independent).  ref_f == 0: the frame is black.
+ *                  peak_dev[f] = ref_f when peak_dev is given.
+ *   3. grey level  per tap, in float:  DB       g = a > 0 ? clamp((20.0f * log10f(a / ref_f) + gain_db + DR) / DR, 0, 1) : 0
+ *                                      REF_LOG  g = clamp(log10f(a + 1.0f) / log10f(ref_f + 1.0f), 0, 1)
+ *                  (clamp = fminf(fmaxf(x, 0), 1): a NaN quotient is 0)
+ *   4. scan conversion of g: mcrt_scan_convert's bilinear expression, masks and maps (mcrt_scan_maps); taps outside the sector are 0.
+ *                  Compression runs before interpolation, as on a scanner.
+ *   5. persistence y_f = fmaf(alpha, y_{f-1}, (1 - alpha) * s_f), s_f = step 4's value; y_{-1} = state_dev unless reset_state is set or
+ *                  state_dev is NULL, then y_{-1} = s_0.  state_dev (float [out_rows][out_cols], values in [0,1]) receives y_{n_frames-1}: two
+ *                  calls of 2 frames equal one call of 4.  alpha = 0: y_f = s_f and the state is not read.
+ *   6. quantisation out = (uint8_t)(y * 255.0f + 0.5f).
+ * The log10f of the device may differ from a correctly rounded one in the last place: a grey level can then differ by one.
+ * Limits: n_rows <= 2048 and n_frames <= 65535 (MCRT_ERR_LIMIT).  MCRT_ERR_INVALID, with a message, for a null rf_dev / out_dev / p, zero sizes,
+ * an unknown mode, a dynamic range <= 0 or not finite, a gain or ref that is not finite, persistence outside [0,1), a non-finite tgc_db
+ * entry, bad scan geometry.  On any error nothing is launched and out_dev, state_dev and peak_dev are untouched.
+ * tgc_db is host memory [n_rows] and may be rewritten once the call returns; the factors live on the device until they change (a new
+ * curve waits for the upload of the previous one).  The grey levels of a pass live in the context's scratch (the one mcrt_convolve uses,
+ * grown to the largest pass); nothing is allocated once that and the maps of a geometry (shared with mcrt_scan_convert_frames) exist. */
+int mcrt_bmode_frames(mcrt_ctx *ctx, const float *rf_dev, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
+                      const mcrt_bmode_params *p, const float *tgc_db /* host [n_rows] dB per RF row, or NULL */,
+                      float *state_dev /* [out_rows][out_cols] smoothing state, or NULL */,
+                      float *peak_dev  /* [n_frames]: the ref each frame used, or NULL */,
+                      uint8_t *out_dev /* [n_frames][out_rows][out_cols] */);
+
 /* device [E][R]  ->  host [R][E] row-major (the cv::Mat layout of rfimage.h:217); synchronous */
 int mcrt_export_rf(mcrt_ctx *ctx, const float *rf_dev, uint32_t n_elements, uint32_t n_rows, float *host_rows_by_cols);
 
@@ -221,8 +268,8 @@ int mcrt_import_rf(mcrt_ctx *ctx, const float *host_rows_by_cols, uint32_t n_ele
  * texture and transducer replicated; every rank's [F][E_g][R] block then crosses xGMI once (hipMemcpyPeerAsync on the rank's own copy
  * stream) into GPU devices[0], where one kernel lays the blocks out as the [F][E][R] frames a single context would have produced, bit
  * for bit (RF bins are integer sums: no partition changes them).  PSF, envelope and scan conversion need neighbouring columns
- * (rfimage.h:113-118) and run on the gathered frames: call mcrt_convolve_frames / mcrt_envelope_frames / mcrt_scan_convert_frames on
- * mcrt_group_root().
+ * (rfimage.h:113-118) and run on the gathered frames: call mcrt_convolve_frames / mcrt_envelope_frames / mcrt_scan_convert_frames, or
+ * mcrt_bmode_frames for the 8-bit display, on mcrt_group_root() -- no group call of their own is needed.
  * A group owns one tracing context per listed device (each driven by its own host thread, so G GPUs are fed in parallel) and a root
  * context on devices[0] for the gathered frames.  A device may be listed more than once: its contexts then share that GPU (how the
  * one-GPU test box runs a two-rank group).  Passes are DOUBLE-BUFFERED: mcrt_group_trace_frames returns once everything is enqueued,

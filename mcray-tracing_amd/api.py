@@ -10,7 +10,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 
 # ------------------------------------------------------------------ host-side pieces (no GPU)
@@ -78,6 +78,21 @@ def host_scan_maps(n_elements, n_rows, radius_mm=30.0, total_angle=1.04719755119
     mr = np.zeros((out_rows, out_cols), np.float32); mc = np.zeros((out_rows, out_cols), np.float32)
     check(load_library().mcrt_scan_maps(n_elements, n_rows, radius_mm, total_angle, max_travel_us, speed_of_sound, out_rows, out_cols, ptr(mr), ptr(mc)))
     return mr, mc
+
+
+BMODE_MODES = {"db": 0, "ref_log": 1}
+
+
+def bmode_params(mode="db", dynamic_range_db=60.0, gain_db=0.0, ref=None, persistence=0.0, reset_state=True, radius_mm=30.0,
+                 total_angle=1.0471975511965976, out_rows=400, out_cols=500):
+    """mcrt_bmode_params from keywords (mode "db" / "ref_log", or the MCRT_BMODE_* number)"""
+    p = BmodeParams()
+    check(load_library().mcrt_default_bmode(C.byref(p)))
+    p.mode = BMODE_MODES[mode] if isinstance(mode, str) else int(mode)
+    p.dynamic_range_db, p.gain_db, p.ref, p.persistence = dynamic_range_db, gain_db, 0.0 if ref is None else ref, persistence
+    p.reset_state = 1 if reset_state else 0
+    p.out_rows, p.out_cols, p.radius_mm, p.total_angle_rad = out_rows, out_cols, radius_mm, total_angle
+    return p
 
 
 class Transducer:
@@ -288,6 +303,20 @@ class Context:
     def scan_convert(self, rf_dev, n_elements, n_rows, out_dev, radius_mm=30.0, total_angle=1.0471975511965976, out_rows=400, out_cols=500):
         check(self.L.mcrt_scan_convert(self.h, ptr(rf_dev), n_elements, n_rows, radius_mm, total_angle, ptr(out_dev), out_rows, out_cols))
 
+    def bmode_frames(self, rf_dev, n_frames, n_elements, n_rows, out_dev, *, mode="db", dynamic_range_db=60.0, gain_db=0.0, ref=None, tgc_db=None,
+                     persistence=0.0, state_dev=None, reset_state=True, peak_dev=None, radius_mm=30.0, total_angle=1.0471975511965976,
+                     out_rows=400, out_cols=500):
+        """mcrt_bmode_frames: [n_frames][E][R] device floats -> [n_frames][out_rows][out_cols] device bytes (log-compressed B-mode).
+        mode "db" or "ref_log"; ref None (or <= 0): each frame's own peak; tgc_db: dB per RF row (n_rows values) or None."""
+        p = bmode_params(mode=mode, dynamic_range_db=dynamic_range_db, gain_db=gain_db, ref=ref, persistence=persistence, reset_state=reset_state,
+                         radius_mm=radius_mm, total_angle=total_angle, out_rows=out_rows, out_cols=out_cols)
+        tgc = None
+        if tgc_db is not None:
+            tgc = np.ascontiguousarray(tgc_db, np.float32)
+            if tgc.shape != (n_rows,):
+                raise ValueError("tgc_db needs one value per RF row: %d, got shape %s" % (n_rows, tgc.shape))
+        check(self.L.mcrt_bmode_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(p), ptr(tgc), ptr(state_dev), ptr(peak_dev), ptr(out_dev)))
+
     def export_rf(self, rf_dev, n_elements, n_rows):
         out = np.empty((n_rows, n_elements), np.float32)
         check(self.L.mcrt_export_rf(self.h, ptr(rf_dev), n_elements, n_rows, ptr(out)))
@@ -463,6 +492,20 @@ class Simulator:
 
     def convolve(self):
         self.ctx.convolve(self.rf_dev, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_kernel)
+
+    def bmode(self, frame_id=0, **display):
+        """trace -> convolve -> envelope -> mcrt_bmode_frames -> host: the displayed 8-bit frame, uint8 [out_rows][out_cols].
+        display: the keywords of Context.bmode_frames (mode, dynamic_range_db, gain_db, ref, tgc_db, ...)"""
+        rows, cols = display.get("out_rows", 400), display.get("out_cols", 500)
+        self.trace(frame_id)
+        self.convolve()
+        self.ctx.envelope(self.rf_dev, self.E, self.R)
+        out = self.ctx.alloc(rows * cols)
+        try:
+            self.ctx.bmode_frames(self.rf_dev, 1, self.E, self.R, out, **display)
+            return self.ctx.d2h(out, (rows, cols), np.uint8)
+        finally:
+            self.ctx.free(out)
 
     def frame(self, frame_id=0, convolve=True):
         self.trace(frame_id)

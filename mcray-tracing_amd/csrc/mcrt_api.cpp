@@ -134,6 +134,9 @@ struct mcrt_ctx {
     float4 *d_mtab = nullptr; uint32_t mtab_n = 0; float mtab_key[2] = { 0.0f, 0.0f }; bool mtab_valid = false;
     // scan-conversion maps
     float *d_map_col = nullptr, *d_map_row = nullptr; uint32_t map_key[6] = { 0, 0, 0, 0, 0, 0 }; double map_keyd[2] = { 0, 0 };
+    // B-mode display (mcrt_bmode_frames): device TGC factors [MCRT_MAX_ROWS] + the peaks of a pass [65535] in one buffer, the factors' pinned
+    // staging and the curve now on the device (its upload is waited for only when the next curve differs)
+    float *d_disp = nullptr, *h_tgc = nullptr; std::vector<float> tgc_on_dev; hipEvent_t ev_tgc = nullptr; bool tgc_copy_pending = false;
     // instrumentation
     unsigned long long *d_stats = nullptr; bool stats_on = false;
     bool timing_on = false; int timing_level = 0;       // 1: the walk's launches are bracketed by HIP events; 2: k_shade's and k_march's too
@@ -356,6 +359,8 @@ extern "C" int mcrt_destroy(mcrt_ctx *c)
     if (c->ev_pose) hipEventDestroy(c->ev_pose);
     if (c->ev_scene) hipEventDestroy(c->ev_scene);
     hipFree(c->d_tex); hipFree(c->d_pos); hipFree(c->d_dir); hipFree(c->d_acc); hipFree(c->d_flags); hipFree(c->d_tmp);
+    hipFree(c->d_disp); if (c->h_tgc) hipHostFree(c->h_tgc);
+    if (c->ev_tgc) hipEventDestroy(c->ev_tgc);
     hipFree(c->d_map_col); hipFree(c->d_map_row); hipFree(c->d_stats); hipFree(c->d_row_thr); hipFree(c->d_error); hipFree(c->d_mtab);
     for (auto &e : c->ev) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     if (c->ev_start) hipEventDestroy(c->ev_start);
@@ -1132,12 +1137,10 @@ extern "C" int mcrt_envelope(mcrt_ctx *c, float *rf_dev, uint32_t E, uint32_t R)
     return mcrt_envelope_frames(c, rf_dev, 1, E, R);
 }
 
-extern "C" int mcrt_scan_convert_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, double radius_mm, double total_angle,
-                                        float *out_dev, uint32_t orows, uint32_t ocols)
+// the scan-conversion maps of a geometry on the device (mcrt_scan_convert_frames, mcrt_bmode_frames): made on the host and uploaded
+// when the geometry changes, reused as they are otherwise
+static int ensure_maps(mcrt_ctx *c, uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t orows, uint32_t ocols)
 {
-    CTX_TRY(c);
-    if (!rf_dev || !out_dev || E == 0 || R == 0 || orows == 0 || ocols == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "mcrt_scan_convert: bad arguments");
-    if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "mcrt_scan_convert: at most 65535 images per call");
     const uint32_t key[6] = { E, R, orows, ocols, c->p.speed_of_sound, 1u };
     const double keyd[2] = { radius_mm * 1e6 + total_angle, c->c.max_travel_us };
     if (memcmp(key, c->map_key, sizeof key) || memcmp(keyd, c->map_keyd, sizeof keyd)) {
@@ -1151,6 +1154,16 @@ extern "C" int mcrt_scan_convert_frames(mcrt_ctx *c, const float *rf_dev, uint32
         HIP_TRY(hipMemcpy(c->d_map_row, mr.data(), mr.size() * 4, hipMemcpyHostToDevice));
         memcpy(c->map_key, key, sizeof key); memcpy(c->map_keyd, keyd, sizeof keyd);
     }
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_scan_convert_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, double radius_mm, double total_angle,
+                                        float *out_dev, uint32_t orows, uint32_t ocols)
+{
+    CTX_TRY(c);
+    if (!rf_dev || !out_dev || E == 0 || R == 0 || orows == 0 || ocols == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "mcrt_scan_convert: bad arguments");
+    if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "mcrt_scan_convert: at most 65535 images per call");
+    { int rc = ensure_maps(c, E, R, radius_mm, total_angle, orows, ocols); if (rc) return rc; }
     HIP_TRY(mcrt::launch_remap(rf_dev, n_frames, E, R, c->d_map_col, c->d_map_row, out_dev, orows * ocols, c->stream));
     return MCRT_OK;
 }
@@ -1159,6 +1172,82 @@ extern "C" int mcrt_scan_convert(mcrt_ctx *c, const float *rf_dev, uint32_t E, u
                                  float *out_dev, uint32_t orows, uint32_t ocols)
 {
     return mcrt_scan_convert_frames(c, rf_dev, 1, E, R, radius_mm, total_angle, out_dev, orows, ocols);
+}
+
+extern "C" int mcrt_default_bmode(mcrt_bmode_params *p)
+{
+    if (!p) return set_error(MCRT_ERR_INVALID, "null params");
+    memset(p, 0, sizeof *p);
+    p->mode = MCRT_BMODE_DB; p->dynamic_range_db = 60.0f; p->gain_db = 0.0f; p->ref = 0.0f; p->persistence = 0.0f; p->reset_state = 1u;
+    p->out_rows = 400u; p->out_cols = 500u; p->radius_mm = 30.0; p->total_angle_rad = 1.0471975511965976;
+    return MCRT_OK;
+}
+
+// The contract is in include/mcrt.h.  Everything is checked before anything is launched; then, on the context's stream: the TGC factors
+// (only when they differ from the ones on the device), with the automatic reference the peaks (memset + k_bmode_peak), the grey level of
+// every RF tap (k_bmode_grey, into the context's scratch) and their scan conversion, persistence and quantisation (k_bmode).
+extern "C" int mcrt_bmode_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_bmode_params *p,
+                                 const float *tgc_db, float *state_dev, float *peak_dev, uint8_t *out_dev)
+{
+    CTX_TRY(c);
+    if (!p) return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: null params");
+    if (!rf_dev || !out_dev) return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: null %s", rf_dev ? "out_dev" : "rf_dev");
+    if (E == 0 || R == 0 || n_frames == 0 || p->out_rows == 0 || p->out_cols == 0) return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: zero sizes");
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "mcrt_bmode_frames: at most %d rows", MCRT_MAX_ROWS);
+    if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "mcrt_bmode_frames: at most 65535 frames per call");
+    if ((uint64_t)p->out_rows * p->out_cols > 0x7ffffffcull) return set_error(MCRT_ERR_LIMIT, "mcrt_bmode_frames: output image too large");
+    if (p->mode != MCRT_BMODE_DB && p->mode != MCRT_BMODE_REF_LOG) return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: unknown mode %u", p->mode);
+    if (!(std::isfinite(p->dynamic_range_db) && p->dynamic_range_db > 0.0f))
+        return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: dynamic_range_db must be finite and > 0 (%g)", (double)p->dynamic_range_db);
+    if (!std::isfinite(p->gain_db)) return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: gain_db must be finite");
+    if (!std::isfinite(p->ref)) return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: ref must be finite");
+    if (!(p->persistence >= 0.0f && p->persistence < 1.0f)) return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: persistence must be in [0,1) (%g)", (double)p->persistence);
+    std::vector<float> k;
+    if (tgc_db) {
+        k.resize(R);
+        for (uint32_t r = 0; r < R; r++) {
+            if (!std::isfinite(tgc_db[r])) return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: tgc_db[%u] is not finite", r);
+            k[r] = (float)std::pow(10.0, (double)tgc_db[r] / 20.0);
+        }
+    }
+    { int rc = ensure_maps(c, E, R, p->radius_mm, p->total_angle_rad, p->out_rows, p->out_cols); if (rc) return rc; }
+    constexpr size_t MAX_PEAKS = 65536;
+    if (!c->d_disp) {                                   // once per context
+        HIP_TRY(hipMalloc(&c->d_disp, 4 * (MCRT_MAX_ROWS + MAX_PEAKS)));
+        HIP_TRY(hipHostMalloc((void **)&c->h_tgc, 4 * MCRT_MAX_ROWS, hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&c->ev_tgc, hipEventDisableTiming));
+    }
+    float *d_tgc = c->d_disp, *d_peak = c->d_disp + MCRT_MAX_ROWS;
+    if (tgc_db && k != c->tgc_on_dev) {
+        if (c->tgc_copy_pending) HIP_TRY(hipEventSynchronize(c->ev_tgc));     // the staging buffer still feeds the previous curve's copy
+        memcpy(c->h_tgc, k.data(), 4 * (size_t)R);
+        HIP_TRY(hipMemcpyAsync(d_tgc, c->h_tgc, 4 * (size_t)R, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipEventRecord(c->ev_tgc, c->stream));
+        c->tgc_copy_pending = true;
+        c->tgc_on_dev = k;
+    }
+    const size_t taps = (size_t)n_frames * E * R;
+    { int rc = ensure_tmp(c, taps); if (rc) return rc; }     // the grey levels of the pass (the scratch mcrt_convolve uses too)
+    const float *tgc = tgc_db ? d_tgc : nullptr;
+    if (p->ref > 0.0f) HIP_TRY(mcrt::launch_bmode_grey(rf_dev, n_frames, E, R, tgc, nullptr, p->ref, peak_dev, p->mode, p->gain_db, p->dynamic_range_db, c->d_tmp, c->stream));
+    else {
+        float *peak = peak_dev ? peak_dev : d_peak;
+        HIP_TRY(hipMemsetAsync(peak, 0, 4 * (size_t)n_frames, c->stream));
+        HIP_TRY(mcrt::launch_bmode_peak(rf_dev, n_frames, E, R, tgc, peak, c->stream));
+        HIP_TRY(mcrt::launch_bmode_grey(rf_dev, n_frames, E, R, tgc, peak, 0.0f, nullptr, p->mode, p->gain_db, p->dynamic_range_db, c->d_tmp, c->stream));
+    }
+    mcrt::BmodeArgs a;
+    a.grey = c->d_tmp; a.map_col = c->d_map_col; a.map_row = c->d_map_row; a.state = state_dev; a.out = out_dev; a.alpha = p->persistence;
+    a.E = E; a.R = R; a.n = p->out_rows * p->out_cols; a.F = n_frames; a.reset = p->reset_state ? 1u : 0u;
+    // without persistence the frames are independent: they are cut into chunks (grid.y) so that a pass has about 16384 wavefronts (the
+    // lanes wait for their gathers; at 400 x 500 a chunk is one frame)
+    a.frames_per_chunk = n_frames;
+    if (a.alpha == 0.0f) {
+        const uint32_t waves = (a.n + 255u) / 256u, chunks = std::max(1u, std::min(n_frames, (16384u + waves - 1u) / waves));
+        a.frames_per_chunk = (n_frames + chunks - 1u) / chunks;
+    }
+    HIP_TRY(mcrt::launch_bmode(a, c->stream));
+    return MCRT_OK;
 }
 
 extern "C" int mcrt_export_rf(mcrt_ctx *c, const float *rf_dev, uint32_t E, uint32_t R, float *host)

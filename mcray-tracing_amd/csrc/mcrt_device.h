@@ -185,6 +185,48 @@ MCRT_DEV Ray ray_of(f3 from, f3 dir, float Ls, const FrameArgs &a)
 
 #define MCRT_STATE0_AT(pos, S) ((pos) - (pos) % (S))      /* queue position of the bounce-0 state of the path queued at pos: its scan-line's first sample (k_init) */
 
+// cv::remap(src, dst, map_y, map_x, INTER_LINEAR, BORDER_CONSTANT 0) at one output pixel (rfimage.h:139), exact bilinear: mx = column
+// coordinate (scan-line), my = row coordinate.  remap_taps gathers the four taps -- tap(x, y) (long long) is the source value at scan-line x,
+// row y, asked for only inside the E x R image, 0 elsewhere -- and remap_blend weighs them.  The one statement of the scan conversion:
+// k_remap gathers the float image with remap_bilinear, k_bmode the grey levels with the two halves (the taps of the next frame are in flight
+// while a frame is blended).
+struct RemapPoint { float mx, my, ax, ay; long long x0, y0; };
+MCRT_DEV RemapPoint remap_point(float mx, float my)
+{
+    RemapPoint p;
+    const float fx = floorf(mx), fy = floorf(my);
+    p.mx = mx; p.my = my; p.ax = mx - fx; p.ay = my - fy;
+    p.x0 = (long long)fx; p.y0 = (long long)fy;
+    return p;
+}
+template <typename Tap>
+MCRT_DEV void remap_taps(const RemapPoint &p, uint32_t E, uint32_t R, Tap tap, float v[2][2])
+{
+    const bool mapped = (p.mx == p.mx) && (p.my == p.my);
+#pragma unroll
+    for (int dy = 0; dy < 2; dy++)
+#pragma unroll
+        for (int dx = 0; dx < 2; dx++) {
+            const long long xx = p.x0 + dx, yy = p.y0 + dy;
+            const bool in = mapped && xx >= 0 && yy >= 0 && xx < (long long)E && yy < (long long)R;
+            v[dy][dx] = in ? tap(xx, yy) : 0.0f;
+        }
+}
+MCRT_DEV float remap_blend(const RemapPoint &p, const float v[2][2])
+{
+    const float top = v[0][0] * (1.0f - p.ax) + v[0][1] * p.ax;
+    const float bot = v[1][0] * (1.0f - p.ax) + v[1][1] * p.ax;
+    return top * (1.0f - p.ay) + bot * p.ay;
+}
+template <typename Tap>
+MCRT_DEV float remap_bilinear(float mx, float my, uint32_t E, uint32_t R, Tap tap)
+{
+    const RemapPoint p = remap_point(mx, my);
+    float v[2][2];
+    remap_taps(p, E, R, tap, v);
+    return remap_blend(p, v);
+}
+
 // population count of a wave mask as a 32-bit SCALAR (a comparison of __popcll's 64-bit result is compiled to a vector instruction)
 MCRT_DEV uint32_t popc_mask(unsigned long long m)
 {

@@ -7,6 +7,7 @@
 //   mcrt_path.hip    k_path (the latency form: every bounce of every path in one launch)
 //   mcrt_march.hip   k_march (RF accumulation of the segments), k_material_table
 //   mcrt_post.hip    k_finalize, k_clear_flags, k_conv_*, k_envelope, k_remap, k_transpose, k_blocks_to_frames
+//   mcrt_display.hip k_bmode_peak, k_bmode_grey, k_bmode (mcrt_bmode_frames: log-compressed 8-bit B-mode frames)
 //   mcrt_scene.hip   k_tris_by_id, k_expand_tris; the probes k_math_probe, k_verify_div, k_philox_probe
 //   mcrt_lbvh.hip    the device BVH builder (mcrt_lbvh.h)
 // Shared device code: mcrt_device.h (primitives and the knobs more than one unit reads), mcrt_walk.h (the lane walk's steps, also k_path's),
@@ -61,6 +62,16 @@ constexpr uint32_t MCRT_ALL_BOUNCES = 0xffffffffu;   // launch_march: accumulate
 
 struct ConvTaps { float ax[16]; float lat[32]; uint32_t n_ax, n_lat; };
 
+// k_bmode (mcrt_bmode_frames): the grey levels [F][E][R] of k_bmode_grey -> bytes [F][n], n = out_rows * out_cols
+struct BmodeArgs {
+    const float *grey;                  // [F][E][R]
+    const float *map_col, *map_row;     // [n] the context's scan-conversion maps
+    float *state;                       // [n] persistence state, or null
+    uint8_t *out;                       // [F][n]
+    float alpha;
+    uint32_t E, R, n, F, frames_per_chunk, reset;
+};
+
 hipError_t launch_init(const FrameArgs &a, hipStream_t st);
 hipError_t launch_trace(const FrameArgs &a, uint32_t b, bool stats, hipStream_t st);
 hipError_t launch_nodes_walk(const float4 *nodes, uint32_t n_nodes, uint4 *out, hipStream_t st);
@@ -75,6 +86,10 @@ hipError_t launch_finalize(long long *acc, uint32_t *flags, float *rf, uint32_t 
 hipError_t launch_convolve(float *img, float *tmp, uint32_t n_img, uint32_t E, uint32_t R, const ConvTaps &taps, hipStream_t st);
 hipError_t launch_envelope(float *img, uint32_t E, uint32_t R, hipStream_t st);
 hipError_t launch_remap(const float *img, uint32_t n_img, uint32_t E, uint32_t R, const float *map_col, const float *map_row, float *out, uint32_t n, hipStream_t st);
+hipError_t launch_bmode_peak(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, float *peak, hipStream_t st);   // peak[F] zeroed before
+hipError_t launch_bmode_grey(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, const float *peak /*[F] or null: ref*/, float ref,
+                             float *peak_out /*[F] or null*/, uint32_t mode, float gain, float dr, float *grey, hipStream_t st);
+hipError_t launch_bmode(const BmodeArgs &a, hipStream_t st);
 hipError_t launch_blocks_to_frames(const float *blocks, float *frames, uint32_t F, uint32_t E, uint32_t R, uint32_t G, const uint32_t *off /*[G+1]*/, hipStream_t st);   // at most 64 ranks
 hipError_t launch_transpose(const float *in, float *out, uint32_t E, uint32_t R, hipStream_t st);
 hipError_t launch_math_probe(int op, const double *x, const double *y, double *out, uint32_t n, hipStream_t st);

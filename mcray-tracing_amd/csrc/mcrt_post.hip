@@ -96,28 +96,13 @@ __global__ void __launch_bounds__(64) k_envelope(float *img, uint32_t E, uint32_
 }
 
 // cv::remap(src, dst, map_y, map_x, INTER_LINEAR, BORDER_CONSTANT 0) with precomputed maps (rfimage.h:139):
-// mx = column coordinate (scan-line), my = row coordinate.  src is [E][R] scan-line-major.
+// src is [E][R] scan-line-major; the tap-and-blend is remap_bilinear (mcrt_device.h), shared with k_bmode.
 __global__ void k_remap(const float *img, uint32_t E, uint32_t R, const float *map_col, const float *map_row, float *out, uint32_t n)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     img += (size_t)blockIdx.y * E * R; out += (size_t)blockIdx.y * n;          // image blockIdx.y of a stack [n_img][E][R] -> [n_img][n]
-    const float mx = map_col[i], my = map_row[i];
-    const float fx = floorf(mx), fy = floorf(my);
-    const float ax = mx - fx, ay = my - fy;
-    const long long x0 = (long long)fx, y0 = (long long)fy;
-    float v[2][2];
-#pragma unroll
-    for (int dy = 0; dy < 2; dy++)
-#pragma unroll
-        for (int dx = 0; dx < 2; dx++) {
-            const long long xx = x0 + dx, yy = y0 + dy;
-            const bool in = (mx == mx) && (my == my) && xx >= 0 && yy >= 0 && xx < (long long)E && yy < (long long)R;
-            v[dy][dx] = in ? img[(size_t)xx * R + (size_t)yy] : 0.0f;
-        }
-    const float top = v[0][0] * (1.0f - ax) + v[0][1] * ax;
-    const float bot = v[1][0] * (1.0f - ax) + v[1][1] * ax;
-    out[i] = top * (1.0f - ay) + bot * ay;
+    out[i] = remap_bilinear(map_col[i], map_row[i], E, R, [=](long long x, long long y) { return img[(size_t)x * R + (size_t)y]; });
 }
 
 // [E][R] -> [R][E]

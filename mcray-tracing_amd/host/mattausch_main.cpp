@@ -1,9 +1,14 @@
 // mattausch_hip -- the reference's program (main.cpp:42-161) on the MI355X library:
 //     mattausch_hip <scene.json> [frames] [samples] [out.pgm] [rf.bin] [--gpus N | --devices 0,1,...]
+//                   [--db DR] [--gain G] [--ref-log] [--persistence A]
 // --gpus N: the first N GPUs of the node, the frame's scan-lines sharded over them (mcrt_group_*: one tracing context and host thread per
 // GPU, the blocks gathered on GPU 0); --devices lists them explicitly, and may repeat one (two ranks sharing a GPU: the one-GPU test).
 // Same constants (main.cpp:23-37), same frame loop body; instead of blocking on imshow/waitKey every frame it
 // runs `frames` frames, prints rays/s and frames/s, and writes the last B-mode image as a PGM.
+// Without display options the PGM is the linear float scan conversion times 255 (rf_image::save).  With any of them every frame is
+// log-compressed to 8-bit grey on the GPU (mcrt_bmode_frames) and the PGM holds those bytes: --db DR decibels of dynamic range below each
+// frame's peak (60 when only another option is given), --gain G dB, --ref-log the reference's log10(v+1)/log10(max+1) instead of
+// decibels, --persistence A temporal smoothing y = A y_prev + (1-A) s across the frames of the run.
 #include "mcrt_host.hpp"
 #include <chrono>
 #include <cstring>
@@ -23,10 +28,17 @@ using transducer_ = transducer<transducer_elements>;
 int main(int argc, char **argv)
 {
     std::vector<int> devices{ 0 };
+    mcrt_bmode_params display; mcrt_default_bmode(&display);
+    display.reset_state = 0;                          // the persistence state runs on from frame to frame
+    bool bmode = false;
     {   // the options, taken out of the positional arguments
         int keep = 1;
         for (int i = 1; i < argc; i++) {
-            if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) { devices.clear(); for (int d = 0; d < std::max(1, std::atoi(argv[i + 1])); d++) devices.push_back(d); i++; }
+            if (!std::strcmp(argv[i], "--db") && i + 1 < argc) { display.dynamic_range_db = (float)std::atof(argv[++i]); bmode = true; }
+            else if (!std::strcmp(argv[i], "--gain") && i + 1 < argc) { display.gain_db = (float)std::atof(argv[++i]); bmode = true; }
+            else if (!std::strcmp(argv[i], "--ref-log")) { display.mode = MCRT_BMODE_REF_LOG; bmode = true; }
+            else if (!std::strcmp(argv[i], "--persistence") && i + 1 < argc) { display.persistence = (float)std::atof(argv[++i]); bmode = true; }
+            else if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) { devices.clear(); for (int d = 0; d < std::max(1, std::atoi(argv[i + 1])); d++) devices.push_back(d); i++; }
             else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {
                 devices.clear();
                 for (const char *q = argv[i + 1]; *q;) { devices.push_back(std::atoi(q)); while (*q && *q != ',') q++; if (*q == ',') q++; }
@@ -59,12 +71,13 @@ int main(int argc, char **argv)
             rf_image.trace((uint32_t)f);      // clear + cast_rays + accumulation (main.cpp:102-144)
             rf_image.convolve(psf);           // main.cpp:146
             rf_image.envelope();              // main.cpp:147
-            rf_image.postprocess();           // main.cpp:148
+            if (bmode) rf_image.postprocess(display);   // main.cpp:148, log-compressed to 8-bit grey
+            else rf_image.postprocess();      // main.cpp:148
         }
         check(dev->synchronize(), "mcrt_synchronize");
         const double dt = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
         std::cout << frames / dt << " frames/s, " << (double)frames * transducer_elements * samples / dt << " rays/s on " << devices.size() << " GPU context(s)" << std::endl;
-        if (argc > 4) rf_image.save(argv[4]);
+        if (argc > 4) { if (bmode) rf_image.save_bmode(argv[4]); else rf_image.save(argv[4]); }
         if (argc > 5) {   // the last frame's RF image after main.cpp:146-147, row-major [465][512] float32 (for the parity test)
             const auto img = rf_image.intensities();
             std::ofstream f(argv[5], std::ios::binary);

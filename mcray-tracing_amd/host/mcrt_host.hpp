@@ -543,7 +543,12 @@ public:
         check(mcrt_alloc(this->dev->ctx, sizeof(float) * 400 * 500, (void **)&scan_dev), "mcrt_alloc");
     }
     rf_image(std::shared_ptr<device> dev_, double radius_mm, double angle_rad) : rf_image(radius_mm, angle_rad, std::move(dev_)) {}
-    ~rf_image() { mcrt_free(dev->ctx, rf_dev); mcrt_free(dev->ctx, scan_dev); }
+    ~rf_image()
+    {
+        mcrt_free(dev->ctx, rf_dev); mcrt_free(dev->ctx, scan_dev);
+        if (bmode_dev) mcrt_free(dev->ctx, bmode_dev);
+        if (state_dev) mcrt_free(dev->ctx, state_dev);
+    }
     rf_image(const rf_image &) = delete; rf_image &operator=(const rf_image &) = delete;
 
     // rfimage.h:33-40: row = micros / (axial_resolution / speed_of_sound), integer micrometres over um/us
@@ -581,6 +586,41 @@ public:
     }
     void envelope() { to_device(); check(mcrt_envelope(dev->ctx, rf_dev, columns, max_rows), "mcrt_envelope"); }
     void postprocess() { to_device(); check(mcrt_scan_convert(dev->ctx, rf_dev, columns, max_rows, radius_mm, angle, scan_dev, 400, 500), "mcrt_scan_convert"); }
+    // the displayed picture instead of the float scan conversion: log compression (dynamic range, gain, TGC) and 8-bit grey on the GPU
+    // (mcrt_bmode_frames; rfimage.h:131-136 planned it).  tgc_db: max_rows dB values or nullptr.  The persistence state lives here and is
+    // carried from one call to the next: it starts afresh on the first call and whenever bp.reset_state is set (mcrt_default_bmode sets it;
+    // pass 0 to smooth across frames).  The size is bp.out_rows x bp.out_cols; the sector is this image's own (the constructor's radius and
+    // angle, as postprocess() uses: bp.radius_mm / total_angle_rad are not read).  save_bmode() writes the last frame.
+    void postprocess(const mcrt_bmode_params &bp, const float *tgc_db = nullptr)
+    {
+        to_device();
+        const size_t n = (size_t)bp.out_rows * bp.out_cols;
+        if (n != bmode_n) {
+            if (bmode_dev) { mcrt_free(dev->ctx, bmode_dev); bmode_dev = nullptr; }
+            if (state_dev) { mcrt_free(dev->ctx, state_dev); state_dev = nullptr; }
+            check(mcrt_alloc(dev->ctx, n, (void **)&bmode_dev), "mcrt_alloc");
+            check(mcrt_alloc(dev->ctx, sizeof(float) * n, (void **)&state_dev), "mcrt_alloc");
+            bmode_n = n; state_valid = false;
+        }
+        mcrt_bmode_params p = bp;
+        p.radius_mm = radius_mm; p.total_angle_rad = angle;
+        p.reset_state = (bp.reset_state || !state_valid) ? 1u : 0u;
+        check(mcrt_bmode_frames(dev->ctx, rf_dev, 1, columns, max_rows, &p, tgc_db, state_dev, nullptr, bmode_dev), "mcrt_bmode_frames");
+        state_valid = true; bmode_rows = bp.out_rows; bmode_cols = bp.out_cols;
+    }
+    std::vector<unsigned char> bmode() const   // the last postprocess(bmode_params) frame, row-major [out_rows][out_cols]
+    {
+        std::vector<unsigned char> h(bmode_n);
+        if (bmode_n) check(mcrt_memcpy_d2h(dev->ctx, h.data(), bmode_dev, h.size()), "mcrt_memcpy_d2h");
+        return h;
+    }
+    void save_bmode(const std::string &filename) const   // that frame as a binary PGM, the bytes as they are
+    {
+        const auto img = bmode();
+        std::ofstream f(filename, std::ios::binary);
+        f << "P5\n" << bmode_cols << " " << bmode_rows << "\n255\n";
+        f.write((const char *)img.data(), (std::streamsize)img.size());
+    }
     void show() const {}   // rfimage.h:150-158 opens an OpenCV window and blocks on a key: out of scope
     std::vector<float> intensities() const   // row-major [max_rows][columns], the cv::Mat of rfimage.h:217
     {
@@ -616,6 +656,8 @@ private:
     std::vector<float> host;                     // [max_rows][columns]
     enum { on_host, on_device } where = on_host;
     float *rf_dev = nullptr, *scan_dev = nullptr;
+    unsigned char *bmode_dev = nullptr; float *state_dev = nullptr;   // postprocess(bmode_params): the 8-bit frame and the persistence state
+    size_t bmode_n = 0; uint32_t bmode_rows = 0, bmode_cols = 0; bool state_valid = false;
 };
 
 }  // namespace mcrt_host
