@@ -191,7 +191,8 @@ int mcrt_convolve(mcrt_ctx *ctx, float *rf_dev, uint32_t n_elements, uint32_t n_
 int mcrt_convolve_frames(mcrt_ctx *ctx, float *rf_dev, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
                          const float *axial, uint32_t n_ax, const float *lateral, uint32_t n_lat);
 /* rf_image::envelope (rfimage.h:54-91) in place on a device image [E][R].  n_rows <= 2048 (MCRT_ERR_LIMIT beyond: a wavefront holds
- * its scan-line in LDS) -- the limit mcrt_params.n_rows has anyway; an image brought in through mcrt_import_rf is bound by it too. */
+ * its scan-line in LDS) -- the limit mcrt_params.n_rows has anyway; an image brought in through mcrt_import_rf is bound by it too.
+ * An image of n_rows < 2 has no peak to find and is left unchanged. */
 int mcrt_envelope(mcrt_ctx *ctx, float *rf_dev, uint32_t n_elements, uint32_t n_rows);
 /* the same on the n_frames images [n_frames][E][R] of a pass (main.cpp:147 once per frame), one launch */
 int mcrt_envelope_frames(mcrt_ctx *ctx, float *rf_dev, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows);

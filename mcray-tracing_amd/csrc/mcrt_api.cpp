@@ -133,7 +133,7 @@ struct mcrt_ctx {
     // per-material table of k_march (depends on the materials, the axial step and the frequency)
     float4 *d_mtab = nullptr; uint32_t mtab_n = 0; float mtab_key[2] = { 0.0f, 0.0f }; bool mtab_valid = false;
     // scan-conversion maps
-    float *d_map_col = nullptr, *d_map_row = nullptr; uint32_t map_key[6] = { 0, 0, 0, 0, 0, 0 }; double map_keyd[2] = { 0, 0 };
+    float *d_map_col = nullptr, *d_map_row = nullptr; uint32_t map_key[6] = { 0, 0, 0, 0, 0, 0 }; double map_keyd[3] = { 0, 0, 0 };
     // B-mode display (mcrt_bmode_frames): device TGC factors [MCRT_MAX_ROWS] + the peaks of a pass [65535] in one buffer, the factors' pinned
     // staging and the curve now on the device (its upload is waited for only when the next curve differs)
     float *d_disp = nullptr, *h_tgc = nullptr; std::vector<float> tgc_on_dev; hipEvent_t ev_tgc = nullptr; bool tgc_copy_pending = false;
@@ -1138,11 +1138,12 @@ extern "C" int mcrt_envelope(mcrt_ctx *c, float *rf_dev, uint32_t E, uint32_t R)
 }
 
 // the scan-conversion maps of a geometry on the device (mcrt_scan_convert_frames, mcrt_bmode_frames): made on the host and uploaded
-// when the geometry changes, reused as they are otherwise
+// when the geometry changes, reused as they are otherwise.  The doubles of the key are compared bit for bit, each on its own (a key
+// folded into one double, radius_mm * 1e6 + total_angle, made (30 mm, 1 rad) and (29.999999 mm, 2 rad) the same geometry)
 static int ensure_maps(mcrt_ctx *c, uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t orows, uint32_t ocols)
 {
     const uint32_t key[6] = { E, R, orows, ocols, c->p.speed_of_sound, 1u };
-    const double keyd[2] = { radius_mm * 1e6 + total_angle, c->c.max_travel_us };
+    const double keyd[3] = { radius_mm, total_angle, c->c.max_travel_us };
     if (memcmp(key, c->map_key, sizeof key) || memcmp(keyd, c->map_keyd, sizeof keyd)) {
         std::vector<float> mc((size_t)orows * ocols), mr((size_t)orows * ocols);
         // (the rf_image template parameter is max_travel_time.to<unsigned int>(), main.cpp:36 -- the same truncation as max_rows uses)

@@ -1160,6 +1160,7 @@ void orc_convolve(float *img, float *tmp, uint32_t rows_, uint32_t cols_,
 void orc_envelope(float *img, uint32_t rows, uint32_t cols)
 {
 #define AT(r, c) img[(size_t)(r) * cols + (c)]
+    if (rows < 2) return;              /* the reference's first comparison reads row 1: a column of fewer rows is left as it is */
     for (uint32_t column = 0; column < cols; column++) {
         int ascending = AT(0, column) < AT(1, column);
         size_t last_peak_pos = 0;

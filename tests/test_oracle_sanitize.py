@@ -31,6 +31,8 @@ def test_oracle_runs_clean_under_asan_ubsan(mcrt):
         ax, lat = orc.psf()
         img = orc.envelope(orc.convolve(np.nan_to_num(outs[0]["rf"]), ax, lat))
         sc = orc.scan_convert(img)
+        one_row = np.array([[1.0, -2.0, 3.0]], np.float32)
+        assert np.array_equal(orc.envelope(one_row), one_row)          # rows == 1: nothing read past the image
         # the test entry points into the physics, the counting walk and the analysis walks (tools/seed_count.py, tools/packet_count.py) as well
         osc.counting(True)
         oc = osc.trace_frame(p, tr.pos, tr.dir, tex, use_bvh=2, want_segs=True); osc.counting(False)
