@@ -15,12 +15,50 @@
 #include <string>
 #include <vector>
 #include <algorithm>
+#include <memory>
+#include <utility>
 
 using mcrt::set_error;
 
 // (an allocation the device cannot satisfy is MCRT_ERR_NOMEM, every other HIP failure MCRT_ERR_HIP)
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipGetLastError(); return set_error(e_ == hipErrorOutOfMemory ? MCRT_ERR_NOMEM : MCRT_ERR_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } } while (0)
 #define CTX_TRY(ctx) do { if (!(ctx)) return set_error(MCRT_ERR_INVALID, "null context"); HIP_TRY(hipSetDevice((ctx)->device)); } while (0)
+
+// Owners of the context's HIP resources, released in their destructors (on the current device: the context's, see mcrt_destroy).
+// A buffer holds `cap` elements.  alloc(n) replaces it by one of exactly n, grow(n) only when n exceeds the capacity; on failure it
+// holds nothing.  Neither waits: whatever may still use the old buffer is waited for by the caller, who knows which wait that is.
+template <class T, bool Pinned = false> struct Buf {
+    T *p = nullptr; size_t cap = 0;
+    Buf() = default;
+    Buf(const Buf &) = delete; Buf &operator=(const Buf &) = delete;
+    Buf(Buf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); }
+    Buf &operator=(Buf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~Buf() { reset(); }
+    void reset() { if (p) { if (Pinned) hipHostFree(p); else hipFree(p); } p = nullptr; cap = 0; }
+    void adopt(T *q, size_t n) { reset(); p = q; cap = q ? n : 0; }
+    hipError_t alloc(size_t n)
+    {
+        reset();
+        if (n == 0) return hipSuccess;
+        const hipError_t e = Pinned ? hipHostMalloc((void **)&p, sizeof(T) * n, hipHostMallocDefault) : hipMalloc((void **)&p, sizeof(T) * n);
+        if (e != hipSuccess) p = nullptr; else cap = n;
+        return e;
+    }
+    hipError_t grow(size_t n) { return n > cap ? alloc(n) : hipSuccess; }
+    operator T *() const { return p; }
+};
+template <class T> using PinnedBuf = Buf<T, true>;
+template <class H, hipError_t (*Destroy)(H)> struct Handle {   // an event or a stream: created by the caller into .h
+    H h = nullptr;
+    Handle() = default;
+    Handle(const Handle &) = delete; Handle &operator=(const Handle &) = delete;
+    Handle(Handle &&o) noexcept { std::swap(h, o.h); }
+    Handle &operator=(Handle &&o) noexcept { std::swap(h, o.h); return *this; }
+    ~Handle() { if (h) Destroy(h); }
+    operator H() const { return h; }
+};
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
 
 struct Consts {   // main.cpp:23-37, rfimage.h:48-51,178-180 evaluated at run time
     float axial_res_f; double axial_res_mm, time_step_us, row_dt_us, max_travel_us; uint32_t axial_res_um, max_rows;
@@ -42,16 +80,19 @@ static Consts derive_consts(const mcrt_params &p)
 // streams it runs on (k_march of bounce b runs on a low-priority side stream beside k_trace of bounce b+1).  A context can own
 // several, to trace the scan-lines of a pass as independent groups on separate streams (MCRT_GROUPS, a tuning knob: one group
 // measured best).
+struct PathBufs {   // sized for `paths` paths of `depth` bounces
+    Buf<float4> st0, st1, st2, mrec;
+    Buf<unsigned long long> key0, key1;
+    Buf<uint32_t> q, counts, seg_count, cursors;
+    size_t paths = 0; uint32_t depth = 0;
+};
 struct Work {
-    hipStream_t stream = nullptr, side[MCRT_SIDE_STREAMS] = {};   // k_march of bounce b runs on side[b % n] (n = 1, or 2 in large passes: side_streams)
-    hipEvent_t ev_bounce[MCRT_MAX_BOUNCES] = {}, ev_join[MCRT_SIDE_STREAMS] = {}, ev_done = nullptr;
-    float4 *d_st0 = nullptr, *d_st1 = nullptr, *d_st2 = nullptr;
-    unsigned long long *d_key0 = nullptr, *d_key1 = nullptr;
-    int *d_stack_ovf = nullptr; size_t ovf_cap = 0;            // traversal-stack overflow of THIS work set's walk (its launches run beside the other groups')
-    uint32_t *d_q = nullptr, *d_counts = nullptr, *d_seg_count = nullptr, *d_cursors = nullptr;
-    mcrt_segment *d_segs = nullptr; size_t segs_cap = 0;       // [paths][depth], only for the callers that ask for segments
-    int32_t *d_hits = nullptr; size_t hits_cap = 0;            // [paths][depth], only for the callers that ask for hit indices
-    float4 *d_mrec = nullptr; size_t paths = 0; uint32_t depth = 0;
+    Stream stream, side[MCRT_SIDE_STREAMS];   // k_march of bounce b runs on side[b % n] (n: Plan::sides)
+    Event ev_bounce[MCRT_MAX_BOUNCES], ev_join[MCRT_SIDE_STREAMS], ev_done;
+    Buf<int> stack_ovf;                       // traversal-stack overflow of THIS work set's walk (its launches run beside the other groups')
+    Buf<mcrt_segment> segs;                   // [paths][depth], only for the callers that ask for segments
+    Buf<int32_t> hits;                        // [paths][depth], only for the callers that ask for hit indices
+    PathBufs b;
 };
 
 // tuning knobs from the environment, read ONCE at mcrt_create (never on the frame path) -- and only in a process started with
@@ -62,8 +103,6 @@ struct Knobs {
     uint32_t path_groups = MCRT_PATH_GROUPS_DEFAULT;   // ... as this many scan-line groups on their own streams: a group's accumulation runs beside the other groups' last walks
     uint32_t path_max = MCRT_PATH_MAX_DEFAULT;    // passes of at most this many paths run as ONE launch that carries every path through all of its bounces (k_path: the latency form)
     uint32_t packet_mask = MCRT_PACKET_MASK_DEFAULT, packet_from = MCRT_PACKET_FROM;   // bit b: bounce b is walked by k_trace_packet (one wavefront per packet of 64 queue neighbours), in passes of at least packet_from paths
-    uint32_t march_cus = 0;                    // CUs the accumulation's side stream is confined to (0 = no mask); the mask's bit order is the driver's
-    bool main_mask = false;                    // with march_cus: the walk / shade chain runs on its own stream confined to the OTHER CUs
     bool test_hooks = false;                   // MCRT_TEST_HOOKS: mcrt_debug_set_error may poison the context (tests only)
 };
 static Knobs read_knobs()
@@ -84,30 +123,30 @@ static Knobs read_knobs()
     if (const char *e = tuning_env("MCRT_MARCH_BLOCKS")) { int v = atoi(e); if (v >= 1) k.march_blocks = (uint32_t)v; }
     k.no_overlap = tuning_env("MCRT_NO_OVERLAP") != nullptr; k.no_priority = tuning_env("MCRT_NO_PRIORITY") != nullptr;
     k.no_fast_div = tuning_env("MCRT_NO_FAST_DIV") != nullptr; k.no_lean = tuning_env("MCRT_NO_LEAN") != nullptr;
-    if (const char *e = tuning_env("MCRT_MARCH_CUS")) { int v = atoi(e); if (v >= 0 && v <= 248) k.march_cus = (uint32_t)v; }
-    k.main_mask = tuning_env("MCRT_MAIN_MASK") != nullptr;
     k.test_hooks = tuning_env("MCRT_TEST_HOOKS") != nullptr;
     return k;
 }
 
+struct TimedLaunch { Event start, end; int kind = 0; };   // kind 0: the walk (k_trace*, k_path), 1: k_shade, 2: k_march
+
 struct mcrt_ctx {
     int device = 0;
     Knobs knobs;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    std::vector<Work> work;                               // one per concurrent scan-line group (see mcrt_trace_frame)
-    hipEvent_t ev_start = nullptr;
+    Stream own_stream; hipStream_t stream = nullptr;
+    std::vector<Work> work;                               // one per concurrent scan-line group (see plan_pass); never moves once a pass holds pointers into it
+    Event ev_start;
     mcrt_params p{};
     Consts c{};
     // scene
     mcrt_bvh bvh{};
     mcrt_bvh4 bvh4{};
-    uint32_t *d_error = nullptr;
-    float4 *d_nodes = nullptr, *d_tris = nullptr, *d_mats = nullptr;
+    Buf<uint32_t> d_error;
+    Buf<float4> d_nodes, d_tris, d_mats;
     mcrt_bvh4_node *walked_nodes = nullptr; bool walked_stale = true;   // host copy of the tree as the lane walk sees it (mcrt_get_bvh4)
-    uint4 *d_nodes_walk = nullptr; uint32_t nodes_walk_cap = 0;   // the walk's child-transposed half-float nodes
-    uint4 *d_meshes = nullptr;
-    uint32_t *d_tri_slot = nullptr;
-    float4 *d_tris_id = nullptr; uint32_t tris_id_cap = 0;      // the triangle records in id order (refresh_soa)
+    Buf<uint4> d_nodes_walk;                              // the walk's child-transposed half-float nodes
+    Buf<uint4> d_meshes;
+    Buf<uint32_t> d_tri_slot;
+    Buf<float4> d_tris_id;                                // the triangle records in id order (refresh_soa)
     uint32_t n_mesh = 0, n_mat = 0, start_mat = 0, n_cu = 256;
     int builder = MCRT_BVH_HOST_SAH; bool host_bvh_stale = false;   // device-built tree: host copies are downloaded on demand
     std::vector<uint32_t> tri_mesh;   // per-triangle mesh index of the uploaded scene (for mcrt_update_triangles)
@@ -115,32 +154,33 @@ struct mcrt_ctx {
     float spacing[3] = { 1, 1, 1 };
     bool have_scene = false;
     // texture
-    float2 *d_tex = nullptr; uint32_t tex_n = 0; bool tex_finite = false;
+    Buf<float2> d_tex; uint32_t tex_n = 0; bool tex_finite = false;
     // transducer
-    float *d_pos = nullptr, *d_dir = nullptr; uint32_t n_el = 0;
+    Buf<float> d_pos, d_dir; uint32_t n_el = 0;
     const float *pose_pos = nullptr, *pose_dir = nullptr;      // set for the duration of mcrt_trace_frames_poses: device [F][E][3] per-frame probe poses
-    float *d_pose[2] = { nullptr, nullptr }; size_t pose_cap[2] = { 0, 0 };   // staging for pose tables handed over as host memory:
-    float *h_pose[2] = { nullptr, nullptr }; hipEvent_t ev_pose = nullptr; bool pose_copy_pending = false;   // the caller's table is copied into pinned memory the context owns before the call returns
-    hipEvent_t ev_scene = nullptr; hipStream_t scene_stream = nullptr; bool scene_pending = false;   // the last scene update's device work (refresh_soa), for traces issued on ANOTHER stream
+    Buf<float> d_pose[2];                                      // staging for pose tables handed over as host memory:
+    PinnedBuf<float> h_pose[2]; Event ev_pose; bool pose_copy_pending = false;   // the caller's table is copied into pinned memory the context owns before the call returns
+    Event ev_scene; hipStream_t scene_stream = nullptr; bool scene_pending = false;   // the last scene update's device work (refresh_soa), for traces issued on ANOTHER stream
     // accumulators
-    long long *d_acc = nullptr; uint32_t *d_flags = nullptr; size_t acc_cap = 0, flag_cap = 0;
+    Buf<long long> d_acc; Buf<uint32_t> d_flags;
     uint32_t acc_clean_ne = 0, acc_clean_rows = 0;   // bins known to be all-zero for this shape (k_finalize leaves them so)
-    float *d_tmp = nullptr; size_t tmp_cap = 0;
+    Buf<float> d_tmp;
     // row thresholds (exact replacement of the per-echo double division) and the verified fast division by tex_res
-    double *d_row_thr = nullptr; uint32_t thr_rows = 0; double thr_dt = 0.0;
+    Buf<double> d_row_thr; uint32_t thr_rows = 0; double thr_dt = 0.0;
     float verified_res = 0.0f; bool fast_div = false, fast_div_all = false;
     float last_lean_bound = 0.0f; uint32_t last_march_rows = 0;   // what the last frame's kernels were given (mcrt_debug_fast_paths)
     // per-material table of k_march (depends on the materials, the axial step and the frequency)
-    float4 *d_mtab = nullptr; uint32_t mtab_n = 0; float mtab_key[2] = { 0.0f, 0.0f }; bool mtab_valid = false;
+    Buf<float4> d_mtab; float mtab_key[2] = { 0.0f, 0.0f }; bool mtab_valid = false;
     // scan-conversion maps
-    float *d_map_col = nullptr, *d_map_row = nullptr; uint32_t map_key[6] = { 0, 0, 0, 0, 0, 0 }; double map_keyd[3] = { 0, 0, 0 };
+    Buf<float> d_map_col, d_map_row; uint32_t map_key[6] = { 0, 0, 0, 0, 0, 0 }; double map_keyd[3] = { 0, 0, 0 };
     // B-mode display (mcrt_bmode_frames): device TGC factors [MCRT_MAX_ROWS] + the peaks of a pass [65535] in one buffer, the factors' pinned
     // staging and the curve now on the device (its upload is waited for only when the next curve differs)
-    float *d_disp = nullptr, *h_tgc = nullptr; std::vector<float> tgc_on_dev; hipEvent_t ev_tgc = nullptr; bool tgc_copy_pending = false;
+    Buf<float> d_disp; PinnedBuf<float> h_tgc; std::vector<float> tgc_on_dev; Event ev_tgc; bool tgc_copy_pending = false;
     // instrumentation
-    unsigned long long *d_stats = nullptr; bool stats_on = false;
+    Buf<unsigned long long> d_stats; bool stats_on = false;
     bool timing_on = false; int timing_level = 0;       // 1: the walk's launches are bracketed by HIP events; 2: k_shade's and k_march's too
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; std::vector<unsigned char> ev_kind; size_t ev_used = 0;
+    std::vector<TimedLaunch> ev; size_t ev_used = 0;
+    ~mcrt_ctx() { free(walked_nodes); mcrt_free_bvh(&bvh); mcrt_free_bvh4(&bvh4); }   // (the HIP resources release themselves)
 };
 
 
@@ -150,30 +190,28 @@ static int prepare_tables(mcrt_ctx *c)
         std::vector<double> thr((size_t)c->p.n_rows + 1);
         { int rc = mcrt_row_thresholds(c->c.row_dt_us, c->p.n_rows, thr.data()); if (rc) return rc; }
         HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->d_row_thr); c->d_row_thr = nullptr;
-        HIP_TRY(hipMalloc(&c->d_row_thr, thr.size() * 8));
+        c->thr_rows = 0;
+        HIP_TRY(c->d_row_thr.alloc(thr.size()));
         HIP_TRY(hipMemcpy(c->d_row_thr, thr.data(), thr.size() * 8, hipMemcpyHostToDevice));
         c->thr_rows = c->p.n_rows; c->thr_dt = c->c.row_dt_us;
     }
     if (c->verified_res != c->p.tex_res) {
         // the GPU checks, exhaustively, that its fma-corrected reciprocal multiply IS IEEE division by tex_res
-        unsigned long long *d_bad = nullptr, bad = 1;
-        HIP_TRY(hipMalloc(&d_bad, 8));
+        Buf<unsigned long long> d_bad; unsigned long long bad = 1;
+        HIP_TRY(d_bad.alloc(1));
         HIP_TRY(hipMemsetAsync(d_bad, 0, 8, c->stream));
         HIP_TRY(mcrt::launch_verify_div(c->p.tex_res, 1.0f / c->p.tex_res, d_bad, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         HIP_TRY(hipMemcpy(&bad, d_bad, 8, hipMemcpyDeviceToHost));
-        hipFree(d_bad);
         c->fast_div = (bad == 0) && !c->knobs.no_fast_div;
         c->fast_div_all = c->fast_div && c->p.tex_res > 1e-16f && !c->knobs.no_lean;
         c->verified_res = c->p.tex_res;
     }
     if (c->have_scene && (!c->mtab_valid || c->mtab_key[0] != c->c.axial_res_f || c->mtab_key[1] != c->p.frequency)) {
-        if (c->mtab_n < c->n_mat) {
+        c->mtab_valid = false;
+        if (c->d_mtab.cap < c->n_mat) {
             HIP_TRY(hipStreamSynchronize(c->stream));
-            hipFree(c->d_mtab); c->d_mtab = nullptr; c->mtab_n = 0;
-            HIP_TRY(hipMalloc(&c->d_mtab, 16 * (size_t)c->n_mat));
-            c->mtab_n = c->n_mat;
+            HIP_TRY(c->d_mtab.alloc(c->n_mat));
         }
         HIP_TRY(mcrt::launch_material_table(c->d_mats, c->n_mat, c->c.axial_res_f, c->p.frequency, c->d_mtab, c->stream));
         c->mtab_key[0] = c->c.axial_res_f; c->mtab_key[1] = c->p.frequency; c->mtab_valid = true;
@@ -212,47 +250,25 @@ extern "C" int mcrt_create(int device, mcrt_ctx **out)
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     if (!strstr(prop.gcnArchName, "gfx950"))
         return set_error(MCRT_ERR_NO_DEVICE, "device %d is %s; this library carries gfx950 (MI355X) code only", device, prop.gcnArchName);
-    mcrt_ctx *c = new (std::nothrow) mcrt_ctx();
+    std::unique_ptr<mcrt_ctx> c(new (std::nothrow) mcrt_ctx());   // (a failure below releases whatever was made)
     if (!c) return set_error(MCRT_ERR_NOMEM, "out of host memory");
     c->device = device;
     c->knobs = read_knobs();
     if (prop.multiProcessorCount > 0) c->n_cu = (uint32_t)prop.multiProcessorCount;
-    if (c->knobs.march_cus + 8u > c->n_cu) c->knobs.march_cus = c->n_cu > 8u ? c->n_cu - 8u : 0u;   // (the CU-mask knobs always leave both sides at least 8 CUs)
-    if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) { delete c; return set_error(MCRT_ERR_HIP, "hipStreamCreate failed"); }
+    HIP_TRY(hipStreamCreateWithFlags(&c->own_stream.h, hipStreamNonBlocking));
     c->stream = c->own_stream;
-    hipEventCreateWithFlags(&c->ev_start, hipEventDisableTiming);
+    HIP_TRY(hipEventCreateWithFlags(&c->ev_start.h, hipEventDisableTiming));
     c->work.reserve(16);   // pointers into this vector are held across get_work() calls; never more than 16 groups
     mcrt_default_params(&c->p);
     c->c = derive_consts(c->p);
-    c->stream = c->own_stream;
-    if (hipMalloc(&c->d_stats, MCRT_STATS_WORDS * sizeof(unsigned long long)) != hipSuccess || hipMemsetAsync(c->d_stats, 0, MCRT_STATS_WORDS * sizeof(unsigned long long), c->stream) != hipSuccess ||
-        hipMalloc(&c->d_error, 4) != hipSuccess || hipMemsetAsync(c->d_error, 0, 4, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
-        hipStreamDestroy(c->own_stream); delete c; return set_error(MCRT_ERR_HIP, "hipMalloc failed");
-    }
-    { int rc = prepare_tables(c); if (rc) { mcrt_destroy(c); return rc; } }
-    *out = c;
+    HIP_TRY(c->d_stats.alloc(MCRT_STATS_WORDS));
+    HIP_TRY(hipMemsetAsync(c->d_stats, 0, MCRT_STATS_WORDS * sizeof(unsigned long long), c->stream));
+    HIP_TRY(c->d_error.alloc(1));
+    HIP_TRY(hipMemsetAsync(c->d_error, 0, 4, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    { int rc = prepare_tables(c.get()); if (rc) return rc; }
+    *out = c.release();
     return MCRT_OK;
-}
-
-static void free_work_buffers(Work &w)
-{
-    hipFree(w.d_st0); hipFree(w.d_st1); hipFree(w.d_st2); hipFree(w.d_key0); hipFree(w.d_key1);
-    hipFree(w.d_q); hipFree(w.d_counts); hipFree(w.d_seg_count); hipFree(w.d_cursors); w.d_cursors = nullptr; hipFree(w.d_segs); hipFree(w.d_hits); hipFree(w.d_mrec);
-    w.d_st0 = w.d_st1 = w.d_st2 = nullptr; w.d_key0 = w.d_key1 = nullptr; w.d_q = w.d_counts = w.d_seg_count = nullptr;
-    w.d_segs = nullptr; w.segs_cap = 0; w.d_hits = nullptr; w.hits_cap = 0; w.d_mrec = nullptr; w.paths = 0; w.depth = 0;
-}
-
-static void free_work(mcrt_ctx *c)
-{
-    for (Work &w : c->work) {
-        free_work_buffers(w);
-        hipFree(w.d_stack_ovf); w.d_stack_ovf = nullptr; w.ovf_cap = 0;
-        for (int i = 0; i < MCRT_MAX_BOUNCES; i++) { if (w.ev_bounce[i]) hipEventDestroy(w.ev_bounce[i]); }
-        for (int i = 0; i < MCRT_SIDE_STREAMS; i++) { if (w.ev_join[i]) hipEventDestroy(w.ev_join[i]); if (w.side[i]) hipStreamDestroy(w.side[i]); }
-        if (w.ev_done) hipEventDestroy(w.ev_done);
-        if (w.stream) hipStreamDestroy(w.stream);
-    }
-    c->work.clear();
 }
 
 // work set g (created on first use).  Streams are created only when a pipeline asks for them (work_stream / side_stream):
@@ -262,31 +278,19 @@ static int get_work(mcrt_ctx *c, size_t g, Work **out)
 {
     while (c->work.size() <= g) {
         Work w;
-        for (int i = 0; i < MCRT_SIDE_STREAMS; i++) HIP_TRY(hipEventCreateWithFlags(&w.ev_join[i], hipEventDisableTiming));
-        for (int i = 0; i < MCRT_MAX_BOUNCES; i++) HIP_TRY(hipEventCreateWithFlags(&w.ev_bounce[i], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&w.ev_done, hipEventDisableTiming));
-        c->work.push_back(w);
+        for (Event &e : w.ev_join) HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
+        for (Event &e : w.ev_bounce) HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&w.ev_done.h, hipEventDisableTiming));
+        c->work.push_back(std::move(w));
     }
     *out = &c->work[g];
     return MCRT_OK;
 }
-// a stream confined to CUs [lo, hi) of the device (hipExtStreamCreateWithCUMask; bit i of the mask = CU i in the driver's numbering)
-static int masked_stream(mcrt_ctx *c, uint32_t lo, uint32_t hi, hipStream_t *out)
-{
-    uint32_t mask[16] = {};
-    const uint32_t words = (c->n_cu + 31u) / 32u;
-    for (uint32_t i = lo; i < hi && i < c->n_cu; i++) mask[i >> 5] |= 1u << (i & 31u);
-    HIP_TRY(hipExtStreamCreateWithCUMask(out, words, mask));
-    return MCRT_OK;
-}
 
-// the stream of scan-line group g of the wavefront pipeline: group 0 runs on the context's stream, the others on their own
-static int work_stream(mcrt_ctx *c, Work &w, bool first, hipStream_t *out)
+// the stream of scan-line group g >= 1 of a pass (group 0 runs on the context's stream)
+static int work_stream(Work &w, hipStream_t *out)
 {
-    const bool masked = c->knobs.march_cus && c->knobs.main_mask;
-    if (first && !masked) { *out = c->stream; return MCRT_OK; }
-    if (!w.stream && masked) { int rc = masked_stream(c, 0, c->n_cu - c->knobs.march_cus, &w.stream); if (rc) return rc; }
-    if (!w.stream) HIP_TRY(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+    if (!w.stream) HIP_TRY(hipStreamCreateWithFlags(&w.stream.h, hipStreamNonBlocking));
     *out = w.stream;
     return MCRT_OK;
 }
@@ -294,12 +298,11 @@ static int work_stream(mcrt_ctx *c, Work &w, bool first, hipStream_t *out)
 // not queue behind k_march's (measured: k_shade took 0.4-0.7 ms instead of 0.1 ms when they did)
 static int side_stream(mcrt_ctx *c, Work &w, uint32_t i, hipStream_t *out)
 {
-    if (!w.side[i] && c->knobs.march_cus) { int rc = masked_stream(c, c->n_cu - c->knobs.march_cus, c->n_cu, &w.side[i]); if (rc) return rc; }
     if (!w.side[i]) {
         int prio_low = 0, prio_high = 0;
         HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
         if (c->knobs.no_priority) prio_low = 0;   // tuning knob
-        HIP_TRY(hipStreamCreateWithPriority(&w.side[i], hipStreamNonBlocking, prio_low));
+        HIP_TRY(hipStreamCreateWithPriority(&w.side[i].h, hipStreamNonBlocking, prio_low));
     }
     *out = w.side[i];
     return MCRT_OK;
@@ -309,40 +312,25 @@ static int side_stream(mcrt_ctx *c, Work &w, uint32_t i, hipStream_t *out)
 // node count stays (a refit -- the per-frame path of a deforming scene -- then costs one kernel on the context's stream and no
 // allocation HERE; mcrt_refit_triangles itself still frees its staging copy of the vertices, which synchronises the device).
 // Nothing here waits: the rebuild is ordered on the stream it was issued on, and an event recorded behind it orders a trace that
-// is issued on ANOTHER stream after mcrt_set_stream (enqueue_frame waits for it).
+// is issued on ANOTHER stream after mcrt_set_stream (enqueue_pass waits for it).
 static int refresh_soa(mcrt_ctx *c)
 {
     c->walked_stale = true;
-    if (c->bvh4.n_nodes == 0) { hipFree(c->d_nodes_walk); c->d_nodes_walk = nullptr; c->nodes_walk_cap = 0; return MCRT_OK; }
-    if (c->nodes_walk_cap != c->bvh4.n_nodes) {
+    if (c->bvh4.n_nodes == 0) { c->d_nodes_walk.reset(); return MCRT_OK; }
+    if (c->d_nodes_walk.cap != 4 * (size_t)c->bvh4.n_nodes) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->d_nodes_walk); c->d_nodes_walk = nullptr; c->nodes_walk_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_nodes_walk, 64 * (size_t)c->bvh4.n_nodes));
-        c->nodes_walk_cap = c->bvh4.n_nodes;
+        HIP_TRY(c->d_nodes_walk.alloc(4 * (size_t)c->bvh4.n_nodes));
     }
     HIP_TRY(mcrt::launch_nodes_walk(c->d_nodes, c->bvh4.n_nodes, c->d_nodes_walk, c->stream));
-    if (c->tris_id_cap != c->bvh.n_tri) {
+    if (c->d_tris_id.cap != MCRT_TRI_PIECES * (size_t)c->bvh.n_tri) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->d_tris_id); c->d_tris_id = nullptr; c->tris_id_cap = 0;
-        if (c->bvh.n_tri) { HIP_TRY(hipMalloc(&c->d_tris_id, 16 * (size_t)MCRT_TRI_PIECES * c->bvh.n_tri)); c->tris_id_cap = c->bvh.n_tri; }
+        HIP_TRY(c->d_tris_id.alloc(MCRT_TRI_PIECES * (size_t)c->bvh.n_tri));
     }
     HIP_TRY(mcrt::launch_tris_by_id((const float4 *)c->d_tris, c->bvh.n_tri, c->d_tris_id, c->stream));
-    if (!c->ev_scene) HIP_TRY(hipEventCreateWithFlags(&c->ev_scene, hipEventDisableTiming));
+    if (!c->ev_scene) HIP_TRY(hipEventCreateWithFlags(&c->ev_scene.h, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(c->ev_scene, c->stream));
     c->scene_stream = c->stream; c->scene_pending = true;
     return MCRT_OK;
-}
-
-static void free_scene(mcrt_ctx *c)
-{
-    free(c->walked_nodes); c->walked_nodes = nullptr; c->walked_stale = true;
-    hipFree(c->d_tris_id); c->d_tris_id = nullptr; c->tris_id_cap = 0;
-    hipFree(c->d_nodes_walk); c->d_nodes_walk = nullptr; c->nodes_walk_cap = 0;
-    hipFree(c->d_nodes); hipFree(c->d_tris); hipFree(c->d_mats); hipFree(c->d_meshes); hipFree(c->d_tri_slot); c->d_tri_slot = nullptr;
-    c->d_nodes = c->d_tris = c->d_mats = nullptr; c->d_meshes = nullptr;
-    mcrt_free_bvh(&c->bvh);
-    mcrt_free_bvh4(&c->bvh4);
-    c->have_scene = false;
 }
 
 extern "C" int mcrt_destroy(mcrt_ctx *c)
@@ -350,21 +338,6 @@ extern "C" int mcrt_destroy(mcrt_ctx *c)
     if (!c) return MCRT_OK;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    free_scene(c);
-    free_work(c);
-    free(c->walked_nodes); c->walked_nodes = nullptr;
-    hipFree(c->d_pose[0]); hipFree(c->d_pose[1]);
-    if (c->h_pose[0]) hipHostFree(c->h_pose[0]);
-    if (c->h_pose[1]) hipHostFree(c->h_pose[1]);
-    if (c->ev_pose) hipEventDestroy(c->ev_pose);
-    if (c->ev_scene) hipEventDestroy(c->ev_scene);
-    hipFree(c->d_tex); hipFree(c->d_pos); hipFree(c->d_dir); hipFree(c->d_acc); hipFree(c->d_flags); hipFree(c->d_tmp);
-    hipFree(c->d_disp); if (c->h_tgc) hipHostFree(c->h_tgc);
-    if (c->ev_tgc) hipEventDestroy(c->ev_tgc);
-    hipFree(c->d_map_col); hipFree(c->d_map_row); hipFree(c->d_stats); hipFree(c->d_row_thr); hipFree(c->d_error); hipFree(c->d_mtab);
-    for (auto &e : c->ev) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
-    if (c->ev_start) hipEventDestroy(c->ev_start);
-    hipStreamDestroy(c->own_stream);
     delete c;
     return MCRT_OK;
 }
@@ -421,28 +394,27 @@ static int index_triangles(mcrt_ctx *c, const float *tri, uint32_t n_tri, const 
 {
     // k_trace addresses nodes (64 B as walked) and triangle records (64 B) with 32-bit byte offsets
     if (n_tri >= (1u << 25)) return set_error(MCRT_ERR_LIMIT, "%u triangles: the walk addresses at most 2^25 (32-bit byte offsets into 64-byte nodes and records)", n_tri);
-    hipFree(c->d_nodes); hipFree(c->d_tris); hipFree(c->d_tri_slot); c->d_nodes = c->d_tris = nullptr; c->d_tri_slot = nullptr;
+    c->d_nodes.reset(); c->d_tris.reset(); c->d_tri_slot.reset();
     mcrt_free_bvh(&c->bvh); mcrt_free_bvh4(&c->bvh4);
     c->host_bvh_stale = false;
     if (c->builder == MCRT_BVH_DEVICE_LBVH) {
-        float *d_tri = nullptr; uint32_t *d_mesh = nullptr;
-        HIP_TRY(hipMalloc(&d_tri, 36 * (size_t)n_tri));
-        if (hipMalloc(&d_mesh, 4 * (size_t)n_tri) != hipSuccess) { hipFree(d_tri); return set_error(MCRT_ERR_NOMEM, "out of device memory"); }
         mcrt::LbvhResult r;
-        int rc = MCRT_OK;
-        if (hipMemcpyAsync(d_tri, tri, 36 * (size_t)n_tri, hipMemcpyDefault, c->stream) != hipSuccess ||
-            hipMemcpyAsync(d_mesh, c->tri_mesh.data(), 4 * (size_t)n_tri, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-            rc = set_error(MCRT_ERR_HIP, "triangle upload failed");
-        if (!rc) rc = mcrt::lbvh_build(d_tri, d_mesh, n_tri, c->stream, &r);
-        hipFree(d_tri); hipFree(d_mesh);
-        if (rc) return rc;
-        c->d_nodes = r.d_nodes; c->d_tri_slot = r.d_tri_slot;
+        {
+            Buf<float> d_tri; Buf<uint32_t> d_mesh;
+            HIP_TRY(d_tri.alloc(9 * (size_t)n_tri));
+            HIP_TRY(d_mesh.alloc(n_tri));
+            if (hipMemcpyAsync(d_tri, tri, 36 * (size_t)n_tri, hipMemcpyDefault, c->stream) != hipSuccess ||
+                hipMemcpyAsync(d_mesh, c->tri_mesh.data(), 4 * (size_t)n_tri, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+                return set_error(MCRT_ERR_HIP, "triangle upload failed");
+            int rc = mcrt::lbvh_build(d_tri, d_mesh, n_tri, c->stream, &r);
+            if (rc) return rc;
+        }
+        c->d_nodes.adopt(r.d_nodes, 8 * (size_t)r.n_nodes4); c->d_tri_slot.adopt(r.d_tri_slot, n_tri);
         {   // the walk's 64-byte records from the builder's 48-byte leaf-order array
-            hipError_t e = hipMalloc(&c->d_tris, 16 * MCRT_TRI_PIECES * (size_t)n_tri);
-            if (e == hipSuccess) e = mcrt::launch_expand_tris(r.d_tris, n_tri, c->d_tris, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            hipFree(r.d_tris);
-            if (e != hipSuccess) return set_error(MCRT_ERR_HIP, "triangle records: %s", hipGetErrorString(e));
+            Buf<float4> leaf; leaf.adopt(r.d_tris, 3 * (size_t)n_tri);
+            HIP_TRY(c->d_tris.alloc(MCRT_TRI_PIECES * (size_t)n_tri));
+            HIP_TRY(mcrt::launch_expand_tris(leaf, n_tri, c->d_tris, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
         }
         c->bvh.n_nodes = 0; c->bvh.n_tri = n_tri; c->bvh.max_depth = r.max_depth; c->bvh.pad_abs = r.pad_abs; c->bvh.nodes = nullptr; c->bvh.tri = nullptr;
         c->bvh4.n_nodes = r.n_nodes4; c->bvh4.max_stack = r.max_stack; c->bvh4.nodes = nullptr;
@@ -483,22 +455,20 @@ static int index_triangles(mcrt_ctx *c, const float *tri, uint32_t n_tri, const 
     if (c->bvh4.max_stack > MCRT_STACK)
         return set_error(MCRT_ERR_LIMIT, "BVH4 needs a %u-entry traversal stack, the kernel has %d", c->bvh4.max_stack, MCRT_STACK);
     if (c->bvh4.n_nodes >= (1u << 25)) return set_error(MCRT_ERR_LIMIT, "%u BVH4 nodes: the walk addresses at most 2^25", c->bvh4.n_nodes);
-    HIP_TRY(hipMalloc(&c->d_nodes, sizeof(mcrt_bvh4_node) * (size_t)c->bvh4.n_nodes));
+    HIP_TRY(c->d_nodes.alloc(sizeof(mcrt_bvh4_node) / 16 * (size_t)c->bvh4.n_nodes));
     HIP_TRY(hipMemcpy(c->d_nodes, c->bvh4.nodes, sizeof(mcrt_bvh4_node) * (size_t)c->bvh4.n_nodes, hipMemcpyHostToDevice));
     {   // the walk's 64-byte records from the builder's 48-byte leaf-order array
-        float4 *d_in = nullptr;
-        HIP_TRY(hipMalloc(&d_in, 48 * (size_t)n_tri));
-        hipError_t e = hipMalloc(&c->d_tris, 16 * MCRT_TRI_PIECES * (size_t)n_tri);
-        if (e == hipSuccess) e = hipMemcpy(d_in, c->bvh.tri, 48 * (size_t)n_tri, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = mcrt::launch_expand_tris(d_in, n_tri, c->d_tris, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        hipFree(d_in);
-        if (e != hipSuccess) return set_error(MCRT_ERR_HIP, "triangle records: %s", hipGetErrorString(e));
+        Buf<float4> d_in;
+        HIP_TRY(d_in.alloc(3 * (size_t)n_tri));
+        HIP_TRY(c->d_tris.alloc(MCRT_TRI_PIECES * (size_t)n_tri));
+        HIP_TRY(hipMemcpy(d_in, c->bvh.tri, 48 * (size_t)n_tri, hipMemcpyHostToDevice));
+        HIP_TRY(mcrt::launch_expand_tris(d_in, n_tri, c->d_tris, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
     }
     {   // triangle id -> leaf-order slot (k_shade re-derives the winning triangle's normal from its vertices)
         std::vector<uint32_t> slot(n_tri);
         for (uint32_t k = 0; k < n_tri; k++) { uint32_t id; memcpy(&id, &c->bvh.tri[(size_t)k * 12 + 3], 4); slot[id] = k; }
-        HIP_TRY(hipMalloc(&c->d_tri_slot, 4 * (size_t)n_tri));
+        HIP_TRY(c->d_tri_slot.alloc(n_tri));
         HIP_TRY(hipMemcpy(c->d_tri_slot, slot.data(), 4 * (size_t)n_tri, hipMemcpyHostToDevice));
     }
     return MCRT_OK;
@@ -557,13 +527,13 @@ extern "C" int mcrt_refit_triangles(mcrt_ctx *c, const float *tri, uint32_t n_tr
     if (!tri) return set_error(MCRT_ERR_INVALID, "null triangles");
     if (n_tri != c->bvh.n_tri || n_tri == 0) return set_error(MCRT_ERR_INVALID, "the scene has %u triangles, the update has %u", c->bvh.n_tri, n_tri);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    float *d_tri = nullptr;
-    HIP_TRY(hipMalloc(&d_tri, 36 * (size_t)n_tri));
+    Buf<float> d_tri;
+    HIP_TRY(d_tri.alloc(9 * (size_t)n_tri));
     int rc = MCRT_OK;
     if (hipMemcpyAsync(d_tri, tri, 36 * (size_t)n_tri, hipMemcpyDefault, c->stream) != hipSuccess) rc = set_error(MCRT_ERR_HIP, "triangle upload failed");
     float pad = 0.0f, lo[3], hi[3];
     if (!rc) rc = mcrt::bvh_refit(d_tri, n_tri, c->d_nodes, c->bvh4.n_nodes, c->d_tris, c->stream, &pad, lo, hi);
-    hipFree(d_tri);
+    d_tri.reset();
     if (!rc) rc = refresh_soa(c);
     if (rc) { c->have_scene = false; return rc; }           // a failed refit leaves no scene
     c->bvh.pad_abs = pad;
@@ -589,15 +559,19 @@ static int upload_scene(mcrt_ctx *c, const float *tri, const uint32_t *tri_mesh,
     for (uint32_t i = 0; i < n_tri; i++)
         if (tri_mesh[i] >= n_mesh) return set_error(MCRT_ERR_INVALID, "triangle %u references mesh %u out of range", i, tri_mesh[i]);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    free_scene(c);
+    free(c->walked_nodes); c->walked_nodes = nullptr; c->walked_stale = true;
+    mcrt_free_bvh(&c->bvh); mcrt_free_bvh4(&c->bvh4);
+    c->have_scene = false;
     if (n_tri) {
         c->tri_mesh.assign(tri_mesh, tri_mesh + n_tri);
         int rc = index_triangles(c, tri, n_tri, pre); if (rc) return rc;
         rc = refresh_soa(c); if (rc) return rc;
+    } else {
+        c->d_nodes.reset(); c->d_tris.reset(); c->d_tri_slot.reset(); c->d_nodes_walk.reset(); c->d_tris_id.reset();
     }
-    HIP_TRY(hipMalloc(&c->d_mats, 32 * (size_t)n_mat));
+    HIP_TRY(c->d_mats.alloc(2 * (size_t)n_mat));
     HIP_TRY(hipMemcpy(c->d_mats, mats, 32 * (size_t)n_mat, hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&c->d_meshes, sizeof(mcrt_mesh) * (size_t)n_mesh));
+    HIP_TRY(c->d_meshes.alloc(n_mesh));
     HIP_TRY(hipMemcpy(c->d_meshes, meshes, sizeof(mcrt_mesh) * (size_t)n_mesh, hipMemcpyHostToDevice));
     c->n_mesh = n_mesh; c->n_mat = n_mat; c->start_mat = start_mat;
     for (int i = 0; i < 3; i++) c->spacing[i] = spacing[i];
@@ -639,14 +613,14 @@ extern "C" int mcrt_get_bvh4(mcrt_ctx *c, mcrt_bvh4 *out)
         // the tree AS WALKED: the lane-per-ray walk reads half-float boxes rounded outwards; decoded back into the builders' layout
         if (c->walked_stale || !c->walked_nodes) {
             const size_t bytes = sizeof(mcrt_bvh4_node) * (size_t)c->bvh4.n_nodes;
-            float4 *d_tmp = nullptr;
-            HIP_TRY(hipMalloc(&d_tmp, bytes));
+            Buf<float4> d_tmp;
+            HIP_TRY(d_tmp.alloc(bytes / 16));
             hipError_t e = mcrt::launch_nodes_walk_decode(c->d_nodes_walk, c->bvh4.n_nodes, d_tmp, c->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
             free(c->walked_nodes);
             c->walked_nodes = (mcrt_bvh4_node *)malloc(bytes);
             if (e == hipSuccess && c->walked_nodes) e = hipMemcpy(c->walked_nodes, d_tmp, bytes, hipMemcpyDeviceToHost);
-            hipFree(d_tmp);
+            d_tmp.reset();
             if (!c->walked_nodes) return set_error(MCRT_ERR_NOMEM, "out of memory");
             if (e != hipSuccess) return set_error(MCRT_ERR_HIP, "mcrt_get_bvh4: %s", hipGetErrorString(e));
             c->walked_stale = false;
@@ -675,8 +649,8 @@ extern "C" int mcrt_upload_texture(mcrt_ctx *c, const float *vox, uint32_t n)
         for (size_t i = 0; i < total * 2; i++) if (!std::isfinite(vox[i])) { finite = false; break; }
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    hipFree(c->d_tex); c->d_tex = nullptr;
-    HIP_TRY(hipMalloc(&c->d_tex, total * 8));
+    c->tex_n = 0;
+    HIP_TRY(c->d_tex.alloc(total));
     HIP_TRY(hipMemcpy(c->d_tex, vox, total * 8, hipMemcpyHostToDevice));
     c->tex_n = n; c->tex_finite = finite;
     return MCRT_OK;
@@ -688,9 +662,9 @@ extern "C" int mcrt_set_transducer(mcrt_ctx *c, const float *pos, const float *d
     if (!pos || !dir || n == 0) return set_error(MCRT_ERR_INVALID, "mcrt_set_transducer: bad arguments");
     if (n != c->n_el) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->d_pos); hipFree(c->d_dir); c->d_pos = c->d_dir = nullptr;
-        HIP_TRY(hipMalloc(&c->d_pos, 12 * (size_t)n));
-        HIP_TRY(hipMalloc(&c->d_dir, 12 * (size_t)n));
+        c->n_el = 0;                                   // (set again once both tables are held)
+        HIP_TRY(c->d_pos.alloc(3 * (size_t)n));
+        HIP_TRY(c->d_dir.alloc(3 * (size_t)n));
         c->n_el = n;
     }
     HIP_TRY(hipMemcpyAsync(c->d_pos, pos, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream));
@@ -702,17 +676,10 @@ extern "C" int mcrt_set_transducer(mcrt_ctx *c, const float *pos, const float *d
 static int ensure_acc(mcrt_ctx *c, uint32_t ne)
 {
     const size_t need = (size_t)ne * c->p.n_rows, needf = (size_t)ne * ((c->p.n_rows + 31u) >> 5);
-    if (need > c->acc_cap) {
+    if (need > c->d_acc.cap || needf > c->d_flags.cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->d_acc); c->d_acc = nullptr; c->acc_cap = 0; c->acc_clean_ne = 0;
-        HIP_TRY(hipMalloc(&c->d_acc, need * 8));
-        c->acc_cap = need;
-    }
-    if (needf > c->flag_cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->d_flags); c->d_flags = nullptr; c->flag_cap = 0; c->acc_clean_ne = 0;
-        HIP_TRY(hipMalloc(&c->d_flags, needf * 4));
-        c->flag_cap = needf;
+        c->acc_clean_ne = 0;
+        HIP_TRY(c->d_acc.grow(need)); HIP_TRY(c->d_flags.grow(needf));
     }
     // k_finalize leaves the bins zeroed; only a shape change (or a failed frame) needs an explicit clear
     if (c->acc_clean_ne != ne || c->acc_clean_rows != c->p.n_rows) {
@@ -736,81 +703,88 @@ static int check_ready(mcrt_ctx *c, uint32_t e0, uint32_t e1)
     return MCRT_OK;
 }
 
-// out: 0 = RF image only, 1 = + hit indices, 2 = + the segment table (64 B per path and bounce: only allocated when asked for)
-static int ensure_work(mcrt_ctx *c, Work &w, uint32_t ne_frame, uint32_t n_frames, int out)
+// How one traced pass runs, decided here and nowhere else: the work sets are sized, the overflow stacks checked and the kernels
+// launched from this plan, so they cannot disagree.  A pass that cannot fill the GPU runs in its LATENCY form: one launch carries every
+// path through all of its bounces (k_path), one more accumulates every bounce's segments -- instead of a walk / shade launch pair per
+// bounce, each as long as its slowest wavefront.  Every other pass runs STAGED: per bounce the walk and k_shade on the group's stream,
+// k_march of the finished segments on a side stream beside the next bounce's walk.
+struct Plan {
+    bool latency = false;
+    uint32_t groups = 1;                          // independent scan-line groups, each with its own work set and stream
+    uint32_t trace_blocks = 0, trace_blocks_wide = 0;   // the staged walk's grids: k_trace_lane, k_trace_lane_wide (0: not taken)
+    uint32_t e[17] = {};                          // group g traces scan-lines [e[g], e[g+1])
+    uint32_t sides[16] = {};                      // side streams group g's accumulations rotate over (none in the latency form: its own stream)
+    size_t ovf[16] = {};                          // traversal-stack overflow entries group g's work set is sized for
+};
+
+// one_group: the caller reads the per-path tables of work set 0 (mcrt_trace_frame_debug, mcrt_cast_rays)
+static Plan plan_pass(const mcrt_ctx *c, uint32_t e0, uint32_t e1, uint32_t n_frames, bool one_group)
 {
-    const uint32_t ne = ne_frame * n_frames;
-    const size_t np = (size_t)ne * c->p.n_samples;
-    const uint32_t B = c->p.max_depth;
-    if (out >= 2 && w.segs_cap < np * B) {
-        HIP_TRY(hipDeviceSynchronize());
-        hipFree(w.d_segs); w.d_segs = nullptr; w.segs_cap = 0;
-        HIP_TRY(hipMalloc(&w.d_segs, sizeof(mcrt_segment) * np * B));
-        w.segs_cap = np * B;
+    Plan P;
+    const uint32_t ne = e1 - e0, S = c->p.n_samples;
+    P.latency = !c->stats_on && (uint64_t)ne * n_frames * S <= c->knobs.path_max;
+    uint32_t groups = (one_group || c->stats_on) ? 1u : c->knobs.groups;
+    if (!one_group && groups == 1u && P.latency) groups = c->knobs.path_groups;
+    P.groups = std::max(1u, std::min({ groups, ne, 16u }));
+    for (uint32_t g = 0; g <= P.groups; g++) P.e[g] = e0 + (uint32_t)(((uint64_t)ne * g) / P.groups);
+    P.trace_blocks = c->knobs.trace_blocks ? c->knobs.trace_blocks : c->n_cu * 4u;   // persistent k_trace: 4 four-wave workgroups per CU (1024 on the MI355X's 256 CUs) of the 5 its registers and LDS allow --
+                                                                                  // the fifth's registers go to a k_march wavefront beside them (since k_march's fast path: 0.446 -> 0.428 ms per frame on a 20-frame pass, 0.366 -> 0.364 at 128)
+    P.trace_blocks_wide = c->knobs.trace_blocks_wide ? c->knobs.trace_blocks_wide : c->n_cu * 5u;      // k_trace_lane_wide: five workgroups per CU
+    // ... while the tree is served from the caches: with 16 M triangles (460 MB of walked nodes, past the Infinity Cache) a fifth wavefront per SIMD only
+    // adds misses -- 0.667 against 0.638 ms per frame -- where the 1 M-triangle scene (29 MB) gains 3-4 %; the line is drawn at half the Infinity Cache
+    if ((uint64_t)c->bvh4.n_nodes * 64ull > (uint64_t)c->knobs.wide_max_tree_mb * 1048576ull) P.trace_blocks_wide = 0;
+    const uint32_t lds_part = mcrt::lane_stack_entries();
+    const size_t deep = c->bvh4.max_stack > lds_part ? c->bvh4.max_stack - lds_part : 0;
+    for (uint32_t g = 0; g < P.groups; g++) {
+        const uint64_t np = (uint64_t)(P.e[g + 1] - P.e[g]) * n_frames * S;
+        // (two side streams only where the walk runs from the caches -- the five-wavefront form's own criterion --: on the 16 M-triangle streaming scene the walks
+        //  are the longer chain and a second accumulation beside them costs 1.5 %: 0.607 against 0.598 ms per frame)
+        if (!P.latency) P.sides[g] = c->knobs.march_streams ? c->knobs.march_streams : (P.trace_blocks_wide != 0u && np >= (uint64_t)MCRT_SIDE_STREAMS_TWO_FROM) ? 2u : 1u;
+        uint32_t blocks = std::max({ c->knobs.trace_blocks, c->knobs.trace_blocks_wide, c->n_cu * 5u });   // (the larger of the walk's two forms)
+        if (P.latency) blocks = std::max(blocks, mcrt::path_blocks(np));                                     // (... and k_path's grid)
+        P.ovf[g] = deep * blocks * 256;
     }
-    if (out >= 1 && w.hits_cap < np * B) {
-        HIP_TRY(hipDeviceSynchronize());
-        hipFree(w.d_hits); w.d_hits = nullptr; w.hits_cap = 0;
-        HIP_TRY(hipMalloc(&w.d_hits, 4 * np * B));
-        w.hits_cap = np * B;
-    }
-    {   // traversal-stack entries beyond the LDS part, one slot per thread of THIS work set's walk launches
-        const uint32_t lds_part = mcrt::lane_stack_entries();
-        uint32_t blocks = std::max(std::max(c->knobs.trace_blocks, c->knobs.trace_blocks_wide), c->n_cu * 5u);      // (the larger of the walk's two forms)
-        if (np <= c->knobs.path_max) blocks = std::max(blocks, mcrt::path_blocks(np));                                   // (... and k_path's grid, when this pass takes the latency form)
-        const size_t need = c->bvh4.max_stack > lds_part ? (size_t)(c->bvh4.max_stack - lds_part) * blocks * 256 : 0;
-        if (need > w.ovf_cap) {
-            HIP_TRY(hipDeviceSynchronize());
-            hipFree(w.d_stack_ovf); w.d_stack_ovf = nullptr; w.ovf_cap = 0;
-            HIP_TRY(hipMalloc(&w.d_stack_ovf, 4 * need));
-            w.ovf_cap = need;
-        }
-    }
-    if (np <= w.paths && B <= w.depth) return MCRT_OK;
+    return P;
+}
+
+// out: 0 = RF image only, 1 = + hit indices, 2 = + the segment table (64 B per path and bounce: only allocated when asked for)
+static int ensure_work(Work &w, size_t np, uint32_t B, size_t ovf, int out)
+{
+    if (out >= 2 && w.segs.cap < np * B) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(w.segs.alloc(np * B)); }
+    if (out >= 1 && w.hits.cap < np * B) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(w.hits.alloc(np * B)); }
+    if (ovf > w.stack_ovf.cap) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(w.stack_ovf.alloc(ovf)); }
+    if (np <= w.b.paths && B <= w.b.depth) return MCRT_OK;
     HIP_TRY(hipDeviceSynchronize());
-    {   // (the optional tables survive a re-allocation of the rest when they are large enough)
-        mcrt_segment *sg = w.d_segs; const size_t sc = w.segs_cap; int32_t *ht = w.d_hits; const size_t hc = w.hits_cap;
-        w.d_segs = nullptr; w.d_hits = nullptr;
-        free_work_buffers(w);
-        w.d_segs = sg; w.segs_cap = sc; w.d_hits = ht; w.hits_cap = hc;
-    }
-    HIP_TRY(hipMalloc(&w.d_st0, 32 * np)); HIP_TRY(hipMalloc(&w.d_st1, 32 * np)); HIP_TRY(hipMalloc(&w.d_st2, 32 * np));   // two halves: bounce parity
-    HIP_TRY(hipMalloc(&w.d_key0, 8 * np)); HIP_TRY(hipMalloc(&w.d_key1, 8 * np));
-    HIP_TRY(hipMalloc(&w.d_q, 8 * np)); HIP_TRY(hipMalloc(&w.d_seg_count, 4 * np));
-    HIP_TRY(hipMalloc(&w.d_counts, 4 * (MCRT_MAX_BOUNCES + 1)));
-    HIP_TRY(hipMalloc(&w.d_cursors, 4 * (size_t)MCRT_MAX_BOUNCES * MCRT_XCDS * MCRT_CURSOR_STRIDE));
-    HIP_TRY(hipMalloc(&w.d_mrec, 48 * np * B));
-    w.paths = np; w.depth = B;
+    w.b = PathBufs();                   // (the optional tables survive a re-allocation of the rest when they are large enough)
+    PathBufs &b = w.b;
+    HIP_TRY(b.st0.alloc(2 * np)); HIP_TRY(b.st1.alloc(2 * np)); HIP_TRY(b.st2.alloc(2 * np));   // two halves: bounce parity
+    HIP_TRY(b.key0.alloc(np)); HIP_TRY(b.key1.alloc(np));
+    HIP_TRY(b.q.alloc(2 * np)); HIP_TRY(b.seg_count.alloc(np));
+    HIP_TRY(b.counts.alloc(MCRT_MAX_BOUNCES + 1));
+    HIP_TRY(b.cursors.alloc((size_t)MCRT_MAX_BOUNCES * MCRT_XCDS * MCRT_CURSOR_STRIDE));
+    HIP_TRY(b.mrec.alloc(3 * np * B));
+    b.paths = np; b.depth = B;
     return MCRT_OK;
 }
 
-// kernel arguments for scan-lines [e0,e1) traced with work set w; acc_e0 = first scan-line of the frame's RF block
-static void fill_args(mcrt_ctx *c, const Work &w, mcrt::FrameArgs &a, uint32_t frame, uint32_t n_frames, uint32_t e0, uint32_t e1, uint32_t acc_e0, uint32_t acc_ne)
+// the kernel arguments every group of a pass shares (acc_ne: scan-lines of the frame's RF block); fill_group adds each group's own
+static void fill_pass(mcrt_ctx *c, const Plan &P, mcrt::FrameArgs &a, uint32_t frame, uint32_t acc_ne, int out)
 {
     memset(&a, 0, sizeof a);
-    a.nodes_walk = c->d_nodes_walk; a.stack_ovf = w.d_stack_ovf; a.tris = c->d_tris; a.meshes = c->d_meshes; a.mats = c->d_mats; a.tex = c->d_tex;
+    a.nodes_walk = c->d_nodes_walk; a.tris = c->d_tris; a.meshes = c->d_meshes; a.mats = c->d_mats; a.tex = c->d_tex;
     a.el_pos = c->pose_pos ? c->pose_pos : c->d_pos; a.el_dir = c->pose_pos ? c->pose_dir : c->d_dir; a.pose_stride = c->pose_pos ? c->p.n_elements : 0u;
     a.row_thr = c->d_row_thr;
-    a.acc = c->d_acc; a.flags = c->d_flags;                 // the frame block [n_frames][acc_ne][R]; this group owns columns e0-acc_e0 ...
-    a.acc_stride = acc_ne; a.acc_off = e0 - acc_e0;
-    a.st0 = w.d_st0; a.st1 = w.d_st1; a.st2 = w.d_st2; a.queue = w.d_q;
-    a.key0 = w.d_key0; a.key1 = w.d_key1; a.tri_slot = c->d_tri_slot; a.tris_id = c->d_tris_id; a.counts = w.d_counts; a.cursors = w.d_cursors; a.segs = w.d_segs; a.hits = w.d_hits; a.mrec = w.d_mrec; a.mtab = c->d_mtab; a.seg_count = w.d_seg_count;
+    a.acc = c->d_acc; a.flags = c->d_flags; a.acc_stride = acc_ne;   // the frame block [n_frames][acc_ne][R]
+    a.tri_slot = c->d_tri_slot; a.tris_id = c->d_tris_id; a.mtab = c->d_mtab;
     a.stats = c->d_stats; a.error_flag = c->d_error; a.stamps = c->d_stats + 8;
     a.n_mat = c->n_mat; a.n_mesh = c->n_mesh; a.n_nodes = c->bvh4.n_nodes; a.S = c->p.n_samples; a.B = c->p.max_depth; a.R = c->p.n_rows;
-    a.e_begin = e0; a.ne_frame = e1 - e0; a.ne = (e1 - e0) * n_frames;   // n_frames consecutive frame ids traced as one pass
     a.ksplit_limit = c->knobs.ksplit_limit;   // bounces with fewer rays than this are cut into pieces (see k_trace)
     if (c->stats_on) a.ksplit_limit = 0;   // counting mode = one walk per ray, so the counts are those of a plain closest-hit walk
     for (int i = 0; i < 3; i++) { a.scene_lo[i] = c->scene_lo[i]; a.scene_hi[i] = c->scene_hi[i]; }
-    a.trace_blocks = c->knobs.trace_blocks ? c->knobs.trace_blocks : (c->n_cu - (c->knobs.main_mask ? c->knobs.march_cus : 0u)) * 4u;   // persistent k_trace: 4 four-wave workgroups per CU (1024 on the MI355X's 256 CUs) of the 5 its registers and LDS allow --
-                                                                                  // the fifth's registers go to a k_march wavefront beside them (since k_march's fast path: 0.446 -> 0.428 ms per frame on a 20-frame pass, 0.366 -> 0.364 at 128)
-    a.trace_blocks_wide = c->knobs.trace_blocks_wide ? c->knobs.trace_blocks_wide : c->n_cu * 5u;      // k_trace_lane_wide: five workgroups per CU
+    a.trace_blocks = P.trace_blocks; a.trace_blocks_wide = P.trace_blocks_wide;
     a.wide_from = c->knobs.wide_from ? c->knobs.wide_from : mcrt::lane_wide_from();
-    // ... while the tree is served from the caches: with 16 M triangles (460 MB of walked nodes, past the Infinity Cache) a fifth wavefront per SIMD only
-    // adds misses -- 0.667 against 0.638 ms per frame -- where the 1 M-triangle scene (29 MB) gains 3-4 %; the line is drawn at half the Infinity Cache
-    if ((uint64_t)c->bvh4.n_nodes * 64ull > (uint64_t)c->knobs.wide_max_tree_mb * 1048576ull) a.trace_blocks_wide = 0;
-    if (c->knobs.main_mask) a.trace_blocks_wide = 0;                                                   // (CU-masked streams: the four-wavefront form only)
     a.march_blocks = c->knobs.march_blocks;
-    a.packet_mask = (c->stats_on || (uint64_t)a.ne * a.S < c->knobs.packet_from) ? 0u : c->knobs.packet_mask;   // bounces walked a wavefront per ray packet (k_trace_packet); the counting build walks ray by ray
+    a.want_segs = out >= 2 ? 1u : 0u;
     a.frame = frame; a.seed = c->p.seed; a.start_mat = c->start_mat; a.tex_n = c->tex_n; a.tex_mask = (c->tex_n & (c->tex_n - 1u)) == 0u ? c->tex_n - 1u : 0u;
     a.sanitize = c->p.sanitize_tir; a.tex_finite = c->tex_finite ? 1u : 0u;
     a.freq = c->p.frequency; a.eps = c->p.intensity_epsilon; a.I0 = c->p.initial_intensity; a.offs = c->p.ray_start_offset;
@@ -838,130 +812,94 @@ static void fill_args(mcrt_ctx *c, const Work &w, mcrt::FrameArgs &a, uint32_t f
     c->last_lean_bound = a.lean_bound; c->last_march_rows = a.march_rows;
 }
 
-static uint32_t side_streams(const mcrt_ctx *c, const mcrt::FrameArgs &a)
+// group g's own arguments: its scan-lines [b0,b1) of the pass's n_frames frames, its columns of the RF block (which begins at acc_e0), its work set
+static void fill_group(const mcrt_ctx *c, const Work &w, mcrt::FrameArgs &a, uint32_t n_frames, uint32_t b0, uint32_t b1, uint32_t acc_e0, int out)
 {
-    if (c->knobs.march_streams) return c->knobs.march_streams;
-    // (two only where the walk runs from the caches -- the five-wavefront form's own criterion, fill_args --: on the 16 M-triangle streaming scene the walks are the longer chain and a
-    //  second accumulation beside them costs 1.5 %: 0.607 against 0.598 ms per frame)
-    return (a.trace_blocks_wide != 0u && (uint64_t)a.ne * a.S >= (uint64_t)MCRT_SIDE_STREAMS_TWO_FROM) ? 2u : 1u;
+    a.stack_ovf = w.stack_ovf; a.segs = w.segs; a.hits = out >= 1 ? (int32_t *)w.hits : nullptr;
+    a.st0 = w.b.st0; a.st1 = w.b.st1; a.st2 = w.b.st2; a.queue = w.b.q; a.key0 = w.b.key0; a.key1 = w.b.key1;
+    a.counts = w.b.counts; a.cursors = w.b.cursors; a.mrec = w.b.mrec; a.seg_count = w.b.seg_count;
+    a.acc_off = b0 - acc_e0;
+    a.e_begin = b0; a.ne_frame = b1 - b0; a.ne = (b1 - b0) * n_frames;   // n_frames consecutive frame ids traced as one pass
+    a.packet_mask = (c->stats_on || (uint64_t)a.ne * a.S < c->knobs.packet_from) ? 0u : c->knobs.packet_mask;   // bounces walked a wavefront per ray packet (k_trace_packet); the counting build walks ray by ray
 }
 
-static int timing_events(mcrt_ctx *c, int kind, hipEvent_t *e0, hipEvent_t *e1);
+// The walk kernels (k_trace_lane*, k_path) index their traversal-stack overflow with stride gridDim.x * 256 and check no bound: the
+// largest grid a group's walks can take must fit its work set, or nothing is launched
+static int check_overflow(const mcrt_ctx *c, const Plan &P, const mcrt::FrameArgs &a, const Work &w)
+{
+    const uint32_t lds_part = mcrt::lane_stack_entries();
+    if (c->bvh4.max_stack <= lds_part) return MCRT_OK;
+    const uint32_t blocks = P.latency ? mcrt::path_blocks((size_t)a.ne * a.S) : std::max(a.trace_blocks, a.trace_blocks_wide);
+    const size_t need = (size_t)(c->bvh4.max_stack - lds_part) * blocks * 256;
+    if (need > w.stack_ovf.cap) return set_error(MCRT_ERR_LIMIT, "traversal-stack overflow: %zu entries needed, the work set holds %zu", need, w.stack_ovf.cap);
+    return MCRT_OK;
+}
 
-// one bounce of one group: k_trace_lane + k_shade on the group's stream, k_march of the finished segments on its side stream.
-// With timing enabled every k_trace launch (the dominant kernel) is bracketed by HIP events on the stream it is launched on.
+// one launch on stream st; when its kind is timed (0: the walk, 1: k_shade, 2: k_march -- see mcrt_enable_timing) bracketed by HIP events on st
+template <class Launch> static int timed_launch(mcrt_ctx *c, int kind, hipStream_t st, Launch launch)
+{
+    if (!c->timing_on || (kind != 0 && c->timing_level < 2)) { HIP_TRY(launch()); return MCRT_OK; }
+    if (c->ev_used == c->ev.size()) {
+        if (c->ev.size() >= 65536) return set_error(MCRT_ERR_LIMIT, "timing buffer full: call mcrt_get_kernel_time(reset=1)");
+        TimedLaunch t;
+        HIP_TRY(hipEventCreate(&t.start.h)); HIP_TRY(hipEventCreate(&t.end.h));
+        c->ev.push_back(std::move(t));
+    }
+    TimedLaunch &t = c->ev[c->ev_used];
+    HIP_TRY(hipEventRecord(t.start, st));
+    HIP_TRY(launch());
+    HIP_TRY(hipEventRecord(t.end, st));
+    t.kind = kind; c->ev_used++;
+    return MCRT_OK;
+}
+
+// one bounce of one group of a staged pass: the walk + k_shade on the group's stream, k_march of the finished segments on its side stream.
 // (Round 4 tried holding k_march of bounce b back until the walk of bounce b+1 had claimed its last ray -- a device word raised by the walk, waited
 //  for with hipStreamWaitValue32, which the command processor releases ~1 us after the store --: 0.360 against 0.343 ms per frame at 128 frames in
 //  flight, 0.414 against 0.405 on the driver's pass, and a hang under `rocprofv3 --pmc`.  Removed; DESIGN.md A.6, profiles/round4/exp_round4_kernels.txt.)
-static int run_bounce(mcrt_ctx *c, Work &w, hipStream_t st, const mcrt::FrameArgs &a, uint32_t b, bool accumulate, bool overlap)
+static int run_bounce(mcrt_ctx *c, Work &w, hipStream_t st, const mcrt::FrameArgs &a, uint32_t b, uint32_t sides, bool accumulate, bool overlap)
 {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    { int rc = timing_events(c, 0, &e0, &e1); if (rc) return rc; }
-    if (e0) HIP_TRY(hipEventRecord(e0, st));
-    HIP_TRY(mcrt::launch_trace(a, b, c->stats_on, st));
-    if (e1) HIP_TRY(hipEventRecord(e1, st));
-    { int rc = timing_events(c, 1, &e0, &e1); if (rc) return rc; }
-    if (e0) HIP_TRY(hipEventRecord(e0, st));
-    HIP_TRY(mcrt::launch_shade(a, b, c->stats_on, st));
-    if (e1) HIP_TRY(hipEventRecord(e1, st));
-    if (accumulate && overlap) {   // the segments of bounce b are final: accumulate them beside the next bounce's walk
+    int rc = timed_launch(c, 0, st, [&] { return mcrt::launch_trace(a, b, c->stats_on, st); }); if (rc) return rc;
+    rc = timed_launch(c, 1, st, [&] { return mcrt::launch_shade(a, b, c->stats_on, st); }); if (rc) return rc;
+    if (!accumulate) return MCRT_OK;
+    hipStream_t ms = st;
+    if (overlap) {   // the segments of bounce b are final: accumulate them beside the next bounce's walk
         HIP_TRY(hipEventRecord(w.ev_bounce[b], st));
-        hipStream_t side;
-        { int rc = side_stream(c, w, b % side_streams(c, a), &side); if (rc) return rc; }
-        HIP_TRY(hipStreamWaitEvent(side, w.ev_bounce[b], 0));
-        { int rc = timing_events(c, 2, &e0, &e1); if (rc) return rc; }
-        if (e0) HIP_TRY(hipEventRecord(e0, side));
-        HIP_TRY(mcrt::launch_march(a, b, c->stats_on, side));
-        if (e1) HIP_TRY(hipEventRecord(e1, side));
-    } else if (accumulate) {
-        { int rc = timing_events(c, 2, &e0, &e1); if (rc) return rc; }
-        if (e0) HIP_TRY(hipEventRecord(e0, st));
-        HIP_TRY(mcrt::launch_march(a, b, c->stats_on, st));
-        if (e1) HIP_TRY(hipEventRecord(e1, st));
+        rc = side_stream(c, w, b % sides, &ms); if (rc) return rc;
+        HIP_TRY(hipStreamWaitEvent(ms, w.ev_bounce[b], 0));
     }
-    return MCRT_OK;
+    return timed_launch(c, 2, ms, [&] { return mcrt::launch_march(a, b, c->stats_on, ms); });
 }
 
-// a pair of events for a launch of kind 0 (the walk), 1 (k_shade) or 2 (k_march) -- or none when that kind is not being timed
-static int timing_events(mcrt_ctx *c, int kind, hipEvent_t *e0, hipEvent_t *e1)
+static int enqueue_pass(mcrt_ctx *c, const Plan &P, const mcrt::FrameArgs *args, Work *const *ws, bool accumulate)
 {
-    *e0 = *e1 = nullptr;
-    if (!c->timing_on || (kind != 0 && c->timing_level < 2)) return MCRT_OK;
-    if (c->ev_used == c->ev.size()) {
-        if (c->ev.size() >= 65536) return set_error(MCRT_ERR_LIMIT, "timing buffer full: call mcrt_get_kernel_time(reset=1)");
-        hipEvent_t x, y;
-        HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventCreate(&y));
-        c->ev.emplace_back(x, y); c->ev_kind.push_back(0);
-    }
-    *e0 = c->ev[c->ev_used].first; *e1 = c->ev[c->ev_used].second; c->ev_kind[c->ev_used] = (unsigned char)kind; c->ev_used++;
-    return MCRT_OK;
-}
-
-// scene::cast_rays (scene.cpp:50-183) [+ the accumulation loop] for scan-lines [e0,e1), split into `groups` independent
-// scan-line blocks.  Everything is ordered after what is already queued on the context's stream, and the context's stream
-// waits for all of it.
-// (prepare_frame: buffers and kernel arguments of the groups; enqueue_frame: the launches)
-static int prepare_frame(mcrt_ctx *c, uint32_t frame, uint32_t n_frames, uint32_t e0, uint32_t e1, uint32_t &groups, int out,
-                         std::vector<mcrt::FrameArgs> &args, std::vector<Work *> &ws)
-{
-    const uint32_t ne = e1 - e0;
-    if (groups > ne) groups = ne;
-    if (groups < 1) groups = 1;
-    if (groups > 16) groups = 16;
-    args.resize(groups); ws.resize(groups);
-    for (uint32_t g = 0; g < groups; g++) {
-        int rc = get_work(c, g, &ws[g]); if (rc) return rc;
-        const uint32_t b0 = e0 + (uint32_t)(((uint64_t)ne * g) / groups), b1 = e0 + (uint32_t)(((uint64_t)ne * (g + 1)) / groups);
-        rc = ensure_work(c, *ws[g], b1 - b0, n_frames, out); if (rc) return rc;
-        fill_args(c, *ws[g], args[g], frame, n_frames, b0, b1, e0, ne);
-        args[g].want_segs = out >= 2 ? 1u : 0u;
-        if (out < 1) args[g].hits = nullptr;
-    }
-    return MCRT_OK;
-}
-
-static int enqueue_frame(mcrt_ctx *c, const std::vector<mcrt::FrameArgs> &args, const std::vector<Work *> &ws, bool accumulate)
-{
-    const uint32_t groups = (uint32_t)args.size();
     const bool overlap = !c->knobs.no_overlap;
-    std::vector<hipStream_t> gst(groups);
-    for (uint32_t g = 0; g < groups; g++) { int rc = work_stream(c, *ws[g], g == 0, &gst[g]); if (rc) return rc; }
+    hipStream_t gst[16] = { c->stream };
+    for (uint32_t g = 1; g < P.groups; g++) { int rc = work_stream(*ws[g], &gst[g]); if (rc) return rc; }
     if (c->scene_pending && c->scene_stream != c->stream) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_scene, 0));   // a scene update issued on another stream
     HIP_TRY(hipEventRecord(c->ev_start, c->stream));
-    for (uint32_t g = 0; g < groups; g++) {
+    for (uint32_t g = 0; g < P.groups; g++) {
         if (gst[g] != c->stream) HIP_TRY(hipStreamWaitEvent(gst[g], c->ev_start, 0));
         HIP_TRY(mcrt::launch_init(args[g], gst[g]));
     }
-    // A pass that cannot fill the GPU runs in its LATENCY form: one launch carries every path through all of its bounces (k_path), one more
-    // accumulates every bounce's segments -- instead of a walk / shade launch pair per bounce, each as long as its slowest wavefront.
-    uint64_t paths = 0;
-    for (uint32_t g = 0; g < groups; g++) paths += (uint64_t)args[g].ne * args[g].S;
-    const bool fused = !c->stats_on && paths <= c->knobs.path_max;
-    for (uint32_t g = 0; g < groups && fused; g++) {          // (every group's k_path first, then the accumulations: the second group must not wait for the host to enqueue the first's k_march)
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        { int rc = timing_events(c, 0, &e0, &e1); if (rc) return rc; }
-        if (e0) HIP_TRY(hipEventRecord(e0, gst[g]));
-        HIP_TRY(mcrt::launch_path(args[g], gst[g]));
-        if (e1) HIP_TRY(hipEventRecord(e1, gst[g]));
-    }
-    for (uint32_t g = 0; g < groups && fused && accumulate; g++) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        { int rc = timing_events(c, 2, &e0, &e1); if (rc) return rc; }
-        if (e0) HIP_TRY(hipEventRecord(e0, gst[g]));
-        HIP_TRY(mcrt::launch_march(args[g], mcrt::MCRT_ALL_BOUNCES, false, gst[g]));
-        if (e1) HIP_TRY(hipEventRecord(e1, gst[g]));
-    }
-    for (uint32_t b = 0; b < c->p.max_depth && !fused; b++)
-        for (uint32_t g = 0; g < groups; g++) {
-            int rc = run_bounce(c, *ws[g], gst[g], args[g], b, accumulate, overlap); if (rc) return rc;
+    if (P.latency) {
+        for (uint32_t g = 0; g < P.groups; g++) {          // (every group's k_path first, then the accumulations: the second group must not wait for the host to enqueue the first's k_march)
+            int rc = timed_launch(c, 0, gst[g], [&] { return mcrt::launch_path(args[g], gst[g]); }); if (rc) return rc;
         }
-    for (uint32_t g = 0; g < groups; g++) {
-        if (accumulate && overlap) {
-            for (uint32_t i = 0; i < side_streams(c, args[g]); i++) {
-                if (!ws[g]->side[i]) continue;
-                HIP_TRY(hipEventRecord(ws[g]->ev_join[i], ws[g]->side[i]));
-                HIP_TRY(hipStreamWaitEvent(gst[g], ws[g]->ev_join[i], 0));
+        for (uint32_t g = 0; g < P.groups && accumulate; g++) {
+            int rc = timed_launch(c, 2, gst[g], [&] { return mcrt::launch_march(args[g], mcrt::MCRT_ALL_BOUNCES, false, gst[g]); }); if (rc) return rc;
+        }
+    } else {
+        for (uint32_t b = 0; b < c->p.max_depth; b++)
+            for (uint32_t g = 0; g < P.groups; g++) {
+                int rc = run_bounce(c, *ws[g], gst[g], args[g], b, P.sides[g], accumulate, overlap); if (rc) return rc;
             }
+    }
+    for (uint32_t g = 0; g < P.groups; g++) {
+        for (uint32_t i = 0; i < P.sides[g] && accumulate && overlap; i++) {
+            if (!ws[g]->side[i]) continue;
+            HIP_TRY(hipEventRecord(ws[g]->ev_join[i], ws[g]->side[i]));
+            HIP_TRY(hipStreamWaitEvent(gst[g], ws[g]->ev_join[i], 0));
         }
         if (gst[g] != c->stream) {
             HIP_TRY(hipEventRecord(ws[g]->ev_done, gst[g]));
@@ -971,16 +909,23 @@ static int enqueue_frame(mcrt_ctx *c, const std::vector<mcrt::FrameArgs> &args, 
     return MCRT_OK;
 }
 
-static int run_frame(mcrt_ctx *c, uint32_t frame, uint32_t n_frames, uint32_t e0, uint32_t e1, bool accumulate, uint32_t groups, int out)
+// scene::cast_rays (scene.cpp:50-183) [+ the accumulation loop] for scan-lines [e0,e1) of n_frames frames, in the form and the
+// scan-line groups plan_pass chooses.  Everything is ordered after what is already queued on the context's stream, and the
+// context's stream waits for all of it.
+static int run_pass(mcrt_ctx *c, uint32_t frame, uint32_t n_frames, uint32_t e0, uint32_t e1, bool accumulate, bool one_group, int out)
 {
-    std::vector<mcrt::FrameArgs> args; std::vector<Work *> ws;
-    int rc = prepare_frame(c, frame, n_frames, e0, e1, groups, out, args, ws); if (rc) return rc;
-    return enqueue_frame(c, args, ws, accumulate);
-}
-
-static uint32_t frame_groups(const mcrt_ctx *c)
-{
-    return c->stats_on ? 1u : c->knobs.groups;
+    const Plan P = plan_pass(c, e0, e1, n_frames, one_group);
+    mcrt::FrameArgs pass, args[16];
+    Work *ws[16];
+    fill_pass(c, P, pass, frame, e1 - e0, out);
+    for (uint32_t g = 0; g < P.groups; g++) {
+        int rc = get_work(c, g, &ws[g]); if (rc) return rc;
+        rc = ensure_work(*ws[g], (size_t)(P.e[g + 1] - P.e[g]) * n_frames * c->p.n_samples, c->p.max_depth, P.ovf[g], out); if (rc) return rc;
+        args[g] = pass;
+        fill_group(c, *ws[g], args[g], n_frames, P.e[g], P.e[g + 1], e0, out);
+        rc = check_overflow(c, P, args[g], *ws[g]); if (rc) return rc;
+    }
+    return enqueue_pass(c, P, args, ws, accumulate);
 }
 
 extern "C" int mcrt_trace_frames(mcrt_ctx *c, uint32_t frame, uint32_t n_frames, uint32_t e0, uint32_t e1, float *rf_dev)
@@ -993,9 +938,7 @@ extern "C" int mcrt_trace_frames(mcrt_ctx *c, uint32_t frame, uint32_t n_frames,
         return set_error(MCRT_ERR_LIMIT, "%u frames x %u scan-lines x %u samples: more than 2^27 paths in one pass", n_frames, e1 - e0, c->p.n_samples);
     const uint32_t lines = (e1 - e0) * n_frames;
     rc = ensure_acc(c, lines); if (rc) return rc;
-    uint32_t groups = frame_groups(c);
-    if (groups == 1u && !c->stats_on && (uint64_t)lines * c->p.n_samples <= c->knobs.path_max) groups = c->knobs.path_groups;      // the latency form (enqueue_frame)
-    rc = run_frame(c, frame, n_frames, e0, e1, true, groups, 0); if (rc) return rc;
+    rc = run_pass(c, frame, n_frames, e0, e1, true, false, 0); if (rc) return rc;
     HIP_TRY(mcrt::launch_finalize(c->d_acc, c->d_flags, rf_dev, lines, c->p.n_rows, c->d_error, c->stream));
     c->acc_clean_ne = lines; c->acc_clean_rows = c->p.n_rows;
     return MCRT_OK;
@@ -1027,20 +970,16 @@ extern "C" int mcrt_trace_frames_poses(mcrt_ctx *c, uint32_t frame, uint32_t n_f
         if (hipPointerGetAttributes(&at, src[k]) == hipSuccess && at.type == hipMemoryTypeDevice) { dev[k] = src[k]; continue; }
         (void)hipGetLastError();
         if (c->pose_copy_pending) { HIP_TRY(hipEventSynchronize(c->ev_pose)); c->pose_copy_pending = false; }
-        if (c->pose_cap[k] < bytes) {
+        if (c->d_pose[k].cap < bytes / 4 || c->h_pose[k].cap < bytes / 4) {
             HIP_TRY(hipStreamSynchronize(c->stream));
-            hipFree(c->d_pose[k]); c->d_pose[k] = nullptr; c->pose_cap[k] = 0;
-            if (c->h_pose[k]) { hipHostFree(c->h_pose[k]); c->h_pose[k] = nullptr; }
-            HIP_TRY(hipMalloc(&c->d_pose[k], bytes));
-            HIP_TRY(hipHostMalloc((void **)&c->h_pose[k], bytes, hipHostMallocDefault));
-            c->pose_cap[k] = bytes;
+            HIP_TRY(c->d_pose[k].grow(bytes / 4)); HIP_TRY(c->h_pose[k].grow(bytes / 4));
         }
         memcpy(c->h_pose[k], src[k], bytes);
         HIP_TRY(hipMemcpyAsync(c->d_pose[k], c->h_pose[k], bytes, hipMemcpyHostToDevice, c->stream));
         dev[k] = c->d_pose[k]; staged = true;
     }
     if (staged) {
-        if (!c->ev_pose) HIP_TRY(hipEventCreateWithFlags(&c->ev_pose, hipEventDisableTiming));
+        if (!c->ev_pose) HIP_TRY(hipEventCreateWithFlags(&c->ev_pose.h, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(c->ev_pose, c->stream));
         c->pose_copy_pending = true;
     }
@@ -1059,14 +998,14 @@ static int copy_out(mcrt_ctx *c, uint32_t ne, int32_t *hits, mcrt_segment *segs,
     int rc = check_device_error(c); if (rc) return rc;
     std::vector<uint32_t> cnt;
     if (!seg_count && (hits || segs)) { cnt.resize(np); seg_count = cnt.data(); }
-    if (seg_count) HIP_TRY(hipMemcpy(seg_count, w.d_seg_count, np * 4, hipMemcpyDeviceToHost));
+    if (seg_count) HIP_TRY(hipMemcpy(seg_count, w.b.seg_count, np * 4, hipMemcpyDeviceToHost));
     if (segs) {
-        HIP_TRY(hipMemcpy(segs, w.d_segs, np * B * sizeof(mcrt_segment), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(segs, w.segs, np * B * sizeof(mcrt_segment), hipMemcpyDeviceToHost));
         for (size_t p = 0; p < np; p++)                         // slots beyond a path's end are unspecified on the device
             for (size_t b = seg_count[p]; b < B; b++) memset(&segs[p * B + b], 0, sizeof(mcrt_segment));
     }
     if (hits) {
-        HIP_TRY(hipMemcpy(hits, w.d_hits, np * B * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hits, w.hits, np * B * 4, hipMemcpyDeviceToHost));
         for (size_t p = 0; p < np; p++)
             for (size_t b = seg_count[p]; b < B; b++) hits[p * B + b] = -2;
     }
@@ -1080,7 +1019,7 @@ extern "C" int mcrt_trace_frame_debug(mcrt_ctx *c, uint32_t frame, uint32_t e0, 
     int rc = check_ready(c, e0, e1); if (rc) return rc;
     if (!rf_dev) return set_error(MCRT_ERR_INVALID, "null rf_dev");
     rc = ensure_acc(c, e1 - e0); if (rc) return rc;
-    rc = run_frame(c, frame, 1, e0, e1, true, 1, segs ? 2 : 1); if (rc) return rc;   // one group: the per-path tables are contiguous
+    rc = run_pass(c, frame, 1, e0, e1, true, true, segs ? 2 : 1); if (rc) return rc;   // one group: the per-path tables are contiguous
     HIP_TRY(mcrt::launch_finalize(c->d_acc, c->d_flags, rf_dev, e1 - e0, c->p.n_rows, c->d_error, c->stream));
     c->acc_clean_ne = e1 - e0; c->acc_clean_rows = c->p.n_rows;
     return copy_out(c, e1 - e0, hits, segs, seg_count);
@@ -1090,17 +1029,15 @@ extern "C" int mcrt_cast_rays(mcrt_ctx *c, uint32_t frame, uint32_t e0, uint32_t
 {
     CTX_TRY(c);
     int rc = check_ready(c, e0, e1); if (rc) return rc;
-    rc = run_frame(c, frame, 1, e0, e1, false, 1, segs ? 2 : 1); if (rc) return rc;
+    rc = run_pass(c, frame, 1, e0, e1, false, true, segs ? 2 : 1); if (rc) return rc;
     return copy_out(c, e1 - e0, hits, segs, seg_count);
 }
 
 static int ensure_tmp(mcrt_ctx *c, size_t n)
 {
-    if (n > c->tmp_cap) {
+    if (n > c->d_tmp.cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->d_tmp); c->d_tmp = nullptr; c->tmp_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_tmp, n * 4));
-        c->tmp_cap = n;
+        HIP_TRY(c->d_tmp.alloc(n));
     }
     return MCRT_OK;
 }
@@ -1149,8 +1086,8 @@ static int ensure_maps(mcrt_ctx *c, uint32_t E, uint32_t R, double radius_mm, do
         // (the rf_image template parameter is max_travel_time.to<unsigned int>(), main.cpp:36 -- the same truncation as max_rows uses)
         { int rc = mcrt_scan_maps(E, R, radius_mm, total_angle, (uint32_t)c->c.max_travel_us, c->p.speed_of_sound, orows, ocols, mr.data(), mc.data()); if (rc) return rc; }
         HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->d_map_col); hipFree(c->d_map_row); c->d_map_col = c->d_map_row = nullptr;
-        HIP_TRY(hipMalloc(&c->d_map_col, mc.size() * 4)); HIP_TRY(hipMalloc(&c->d_map_row, mr.size() * 4));
+        memset(c->map_key, 0, sizeof key);                  // (no geometry until both maps are on the device)
+        HIP_TRY(c->d_map_col.alloc(mc.size())); HIP_TRY(c->d_map_row.alloc(mr.size()));
         HIP_TRY(hipMemcpy(c->d_map_col, mc.data(), mc.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c->d_map_row, mr.data(), mr.size() * 4, hipMemcpyHostToDevice));
         memcpy(c->map_key, key, sizeof key); memcpy(c->map_keyd, keyd, sizeof keyd);
@@ -1213,12 +1150,14 @@ extern "C" int mcrt_bmode_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_fr
     }
     { int rc = ensure_maps(c, E, R, p->radius_mm, p->total_angle_rad, p->out_rows, p->out_cols); if (rc) return rc; }
     constexpr size_t MAX_PEAKS = 65536;
-    if (!c->d_disp) {                                   // once per context
-        HIP_TRY(hipMalloc(&c->d_disp, 4 * (MCRT_MAX_ROWS + MAX_PEAKS)));
-        HIP_TRY(hipHostMalloc((void **)&c->h_tgc, 4 * MCRT_MAX_ROWS, hipHostMallocDefault));
-        HIP_TRY(hipEventCreateWithFlags(&c->ev_tgc, hipEventDisableTiming));
+    if (!c->d_disp) {                                   // once per context, all three or none
+        Buf<float> disp; PinnedBuf<float> tgc; Event ev;
+        HIP_TRY(disp.alloc(MCRT_MAX_ROWS + MAX_PEAKS));
+        HIP_TRY(tgc.alloc(MCRT_MAX_ROWS));
+        HIP_TRY(hipEventCreateWithFlags(&ev.h, hipEventDisableTiming));
+        c->d_disp = std::move(disp); c->h_tgc = std::move(tgc); c->ev_tgc = std::move(ev);
     }
-    float *d_tgc = c->d_disp, *d_peak = c->d_disp + MCRT_MAX_ROWS;
+    float *d_tgc = c->d_disp, *d_peak = d_tgc + MCRT_MAX_ROWS;
     if (tgc_db && k != c->tgc_on_dev) {
         if (c->tgc_copy_pending) HIP_TRY(hipEventSynchronize(c->ev_tgc));     // the staging buffer still feeds the previous curve's copy
         memcpy(c->h_tgc, k.data(), 4 * (size_t)R);
@@ -1352,16 +1291,15 @@ extern "C" int mcrt_enable_timing(mcrt_ctx *c, int on) { CTX_TRY(c); c->timing_o
 extern "C" int mcrt_get_kernel_times(mcrt_ctx *c, double avg_ms[3], uint32_t n[3], int reset)
 {
     CTX_TRY(c);
-    // level 1: every event was recorded on the context's stream -- wait for that stream only (a caller polling the walk's time must not stall on other
-    // contexts of the device: a group's other ranks on the root GPU, a host application's own streams); level 2: k_march's events live on the side streams,
-    // so each recorded pair is waited for by itself
-    if (c->timing_level < 2) HIP_TRY(hipStreamSynchronize(c->stream));
-    else for (size_t i = 0; i < c->ev_used; i++) HIP_TRY(hipEventSynchronize(c->ev[i].second));
+    // each recorded pair is waited for by itself: the pairs live on the streams their launches ran on (the groups' own, the side streams), not
+    // only on the one current now -- and a caller polling the walk's time does not stall on other contexts of the device
     double sum[3] = { 0, 0, 0 }; uint32_t cnt[3] = { 0, 0, 0 };
     for (size_t i = 0; i < c->ev_used; i++) {
-        float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, c->ev[i].first, c->ev[i].second));
-        const int k = c->ev_kind[i] < 3 ? c->ev_kind[i] : 0;
-        sum[k] += ms; cnt[k]++;
+        const TimedLaunch &t = c->ev[i];
+        float ms = 0;
+        HIP_TRY(hipEventSynchronize(t.end));
+        HIP_TRY(hipEventElapsedTime(&ms, t.start, t.end));
+        sum[t.kind] += ms; cnt[t.kind]++;
     }
     for (int k = 0; k < 3; k++) { if (avg_ms) avg_ms[k] = cnt[k] ? sum[k] / (double)cnt[k] : 0.0; if (n) n[k] = cnt[k]; }
     if (reset) c->ev_used = 0;
@@ -1380,25 +1318,23 @@ extern "C" int mcrt_debug_math(mcrt_ctx *c, int op, const double *x, const doubl
 {
     CTX_TRY(c);
     if (!x || !out || n == 0) return set_error(MCRT_ERR_INVALID, "mcrt_debug_math: bad arguments");
-    double *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc(&dx, 8 * (size_t)n)); HIP_TRY(hipMalloc(&dout, 8 * (size_t)n));
+    Buf<double> dx, dy, dout;
+    HIP_TRY(dx.alloc(n)); HIP_TRY(dout.alloc(n));
     HIP_TRY(hipMemcpy(dx, x, 8 * (size_t)n, hipMemcpyHostToDevice));
-    if (y) { HIP_TRY(hipMalloc(&dy, 8 * (size_t)n)); HIP_TRY(hipMemcpy(dy, y, 8 * (size_t)n, hipMemcpyHostToDevice)); }
+    if (y) { HIP_TRY(dy.alloc(n)); HIP_TRY(hipMemcpy(dy, y, 8 * (size_t)n, hipMemcpyHostToDevice)); }
     HIP_TRY(mcrt::launch_math_probe(op, dx, dy, dout, n, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(out, dout, 8 * (size_t)n, hipMemcpyDeviceToHost));
-    hipFree(dx); hipFree(dy); hipFree(dout);
     return MCRT_OK;
 }
 
 extern "C" int mcrt_debug_philox(mcrt_ctx *c, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4])
 {
     CTX_TRY(c);
-    uint32_t *d = nullptr;
-    HIP_TRY(hipMalloc(&d, 16));
+    Buf<uint32_t> d;
+    HIP_TRY(d.alloc(4));
     HIP_TRY(mcrt::launch_philox_probe(ctr, key, d, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(out, d, 16, hipMemcpyDeviceToHost));
-    hipFree(d);
     return MCRT_OK;
 }

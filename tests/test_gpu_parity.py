@@ -923,8 +923,7 @@ def test_host_shim_surface(mcrt, orc, tex256, tmp_path):
 
 def test_schedules_do_not_change_anything(mcrt, orc, tex256, monkeypatch):
     """how a pass is scheduled is free (counter-keyed RNG, integer RF bins): the default, scan-line groups on their own streams, rays
-    of small bounces cut into pieces or not, every bounce walked a wavefront per ray packet (k_trace_packet) or none, the accumulation (and the walk)
-    confined to their own CUs, everything on one stream, the walk in its five-wavefronts-per-SIMD form (k_trace_lane_wide, which large launches take by themselves) -- all give bit-identical hits,
+    of small bounces cut into pieces or not, every bounce walked a wavefront per ray packet (k_trace_packet) or none, everything on one stream, the walk in its five-wavefronts-per-SIMD form (k_trace_lane_wide, which large launches take by themselves) -- all give bit-identical hits,
     segments, RF images and visit counts, equal to the oracle's."""
     cfg, meshes = mcrt.synth.random_scene(60000, 8, seed=5)
     sd = mcrt.scene_io.build_scene(cfg, meshes)
@@ -934,12 +933,11 @@ def test_schedules_do_not_change_anything(mcrt, orc, tex256, monkeypatch):
     staged = {"MCRT_PATH_MAX": "0"}
     variants = (("default", {}), ("staged", {}), ("packets_every_bounce", {"MCRT_PACKET_BOUNCES": "0xfffe", "MCRT_PACKET_FROM": "0"}), ("no_packets", {"MCRT_PACKET_BOUNCES": "0"}),
                 ("two_groups", {"MCRT_GROUPS": "2"}), ("three_groups_no_split", {"MCRT_GROUPS": "3", "MCRT_KSPLIT_LIMIT": "0"}),
-                ("masked", {"MCRT_MARCH_CUS": "64", "MCRT_MAIN_MASK": "1"}), ("march_masked", {"MCRT_MARCH_CUS": "96"}), ("no_overlap", {"MCRT_NO_OVERLAP": "1"}),
+                ("no_overlap", {"MCRT_NO_OVERLAP": "1"}),
                 ("wide_walk", {"MCRT_WIDE_FROM": "1"}), ("wide_walk_two_groups_no_split", {"MCRT_WIDE_FROM": "1", "MCRT_GROUPS": "2", "MCRT_KSPLIT_LIMIT": "0"}),
-                ("narrow_walk", {"MCRT_WIDE_FROM": "4294967295"}), ("narrow_walk_two_groups", {"MCRT_WIDE_FROM": "4294967295", "MCRT_GROUPS": "2"}),      # (round 6: the five-wavefront form is the default from the first ray)
-                ("latency_form_masked", {"MCRT_MARCH_CUS": "64", "MCRT_MAIN_MASK": "1", "MCRT_PATH_MAX": "1000000"}))
+                ("narrow_walk", {"MCRT_WIDE_FROM": "4294967295"}), ("narrow_walk_two_groups", {"MCRT_WIDE_FROM": "4294967295", "MCRT_GROUPS": "2"}))      # (round 6: the five-wavefront form is the default from the first ray)
     for name, env in variants:
-        for k in ("MCRT_KSPLIT_LIMIT", "MCRT_GROUPS", "MCRT_MARCH_CUS", "MCRT_MAIN_MASK", "MCRT_NO_OVERLAP", "MCRT_WIDE_FROM", "MCRT_PACKET_BOUNCES", "MCRT_PACKET_FROM", "MCRT_PATH_MAX"):
+        for k in ("MCRT_KSPLIT_LIMIT", "MCRT_GROUPS", "MCRT_NO_OVERLAP", "MCRT_WIDE_FROM", "MCRT_PACKET_BOUNCES", "MCRT_PACKET_FROM", "MCRT_PATH_MAX"):
             monkeypatch.delenv(k, raising=False)
         for k, v in (env if name == "default" else dict(staged, **env)).items():
             monkeypatch.setenv(k, v)                               # (the library reads its knobs once, at mcrt_create)
@@ -957,7 +955,7 @@ def test_schedules_do_not_change_anything(mcrt, orc, tex256, monkeypatch):
         nodes4 = sim.ctx.get_bvh4()[0]
         sim.close()
         got[name] = (hits, segs.tobytes(), cnt, rf, st, batch[1].T.copy(), nodes4)
-    for k in ("MCRT_KSPLIT_LIMIT", "MCRT_GROUPS", "MCRT_MARCH_CUS", "MCRT_MAIN_MASK", "MCRT_NO_OVERLAP", "MCRT_WIDE_FROM", "MCRT_PACKET_BOUNCES", "MCRT_PACKET_FROM", "MCRT_PATH_MAX"):
+    for k in ("MCRT_KSPLIT_LIMIT", "MCRT_GROUPS", "MCRT_NO_OVERLAP", "MCRT_WIDE_FROM", "MCRT_PACKET_BOUNCES", "MCRT_PACKET_FROM", "MCRT_PATH_MAX"):
         monkeypatch.delenv(k, raising=False)
     a = got["default"]
     for name in [v[0] for v in variants[1:]]:
@@ -977,6 +975,56 @@ def test_schedules_do_not_change_anything(mcrt, orc, tex256, monkeypatch):
     o0 = osc.trace_frame(p0, tr.pos, tr.dir, tex256, frame_id=frame, use_bvh=2, n_threads=16, want_ref=False, want_fix=False)["stats"]
     for k in ("queries", "nodes_visited", "tris_tested"):
         assert a[4][k] == o["stats"][k] - o0[k] + o0[k] // S, k
+
+
+
+def test_kernel_times_count_the_launches():
+    """mcrt_get_kernel_times at timing levels 1 and 2: a staged pass walks, shades and accumulates once per bounce; the latency form, as two
+    scan-line groups, is one k_path and one accumulation per group; level 1 times the walk alone; every timed kind has a positive average.
+    Once the context's stream is switched to a torch stream between tracing and reading, without a synchronisation (as bench.py does):
+    the second group's events live on its own stream, and each pair is waited for by itself.  (A child process that starts torch
+    first, as bench.py does.)"""
+    import subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    child = r"""
+import os, sys, torch
+sys.path.insert(0, %r)
+torch.cuda.set_device(0)
+other = torch.cuda.Stream()
+import mcray_tracing_amd as m
+cfg, meshes = m.synth.sphere_scene(3)
+sd = m.scene_io.build_scene(cfg, meshes)
+E, S = 8, 64
+tr = m.Transducer(E, position=cfg["transducerPosition"], angles_deg=cfg["transducerAngles"])
+for form, path_max in (("staged", "0"), ("latency", None)):
+    os.environ.pop("MCRT_PATH_MAX", None)
+    if path_max is not None:
+        os.environ["MCRT_PATH_MAX"] = path_max                    # (the library reads its knobs once, at mcrt_create)
+    sim = m.Simulator(sd, tr, n_samples=S, texture=m.host_texture(32), tex_n=32)
+    B = sim.ctx.params.max_depth
+    for level in (1, 2):
+        sim.ctx.enable_timing(level)
+        sim.ctx.kernel_times(reset=True)
+        sim.trace(3)
+        switch = form == "latency" and level == 1
+        if switch:
+            sim.ctx.set_stream(other.cuda_stream)
+        t = sim.ctx.kernel_times(reset=True)
+        if switch:
+            sim.ctx.set_stream(None)
+        want = {"walk": B, "shade": B, "march": B} if form == "staged" else {"walk": 2, "shade": 0, "march": 2}
+        if level == 1:
+            want.update(shade=0, march=0)
+        assert {k: v[1] for k, v in t.items()} == want, (form, level, t)
+        assert all(ms > 0.0 for ms, n in t.values() if n), (form, level, t)
+    sim.ctx.enable_timing(False)
+    sim.close()
+print("kernel times ok")
+""" % root
+    env = {k: v for k, v in os.environ.items() if k not in ("MCRT_PATH_MAX", "MCRT_PATH_GROUPS", "MCRT_GROUPS", "MCRT_NO_OVERLAP")}
+    env["MCRT_TUNING"] = "1"
+    r = subprocess.run([sys.executable, "-c", child], env=env, cwd=root, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0 and "kernel times ok" in r.stdout, (r.stdout[-400:], r.stderr[-3000:])
 
 
 def test_deep_tree_overflow_stacks_of_two_groups(mcrt, orc, tex256, monkeypatch):
