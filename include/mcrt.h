@@ -29,11 +29,12 @@
 extern "C" {
 #endif
 
-#define MCRT_VERSION 107   /* round 3: + mcrt_trace_frames_poses, mcrt_envelope_frames, mcrt_scan_convert_frames; the slab rule of the closest-hit contract is one fma per plane;
+#define MCRT_VERSION 108   /* round 3: + mcrt_trace_frames_poses, mcrt_envelope_frames, mcrt_scan_convert_frames; the slab rule of the closest-hit contract is one fma per plane;
                               104: + the test hooks mcrt_debug_set_error, mcrt_debug_fast_paths; RF images are NaN while the device error word is set;
                               105 (round 4): + mcrt_group_* (several GPUs behind one call), mcrt_scan_maps; the scan-conversion maps follow the reference's float promotions;
                               106 (round 5): environment knobs are only read under MCRT_TUNING=1; the HIP-graph replay of passes (MCRT_GRAPH) is gone;
-                              107: + mcrt_default_bmode, mcrt_bmode_frames (log-compressed 8-bit B-mode frames: dynamic range, gain, TGC, persistence) */
+                              107: + mcrt_default_bmode, mcrt_bmode_frames (log-compressed 8-bit B-mode frames: dynamic range, gain, TGC, persistence);
+                              108: + mcrt_focus, mcrt_psf_focus_kernels, mcrt_convolve_frames_depth (focal zones: a lateral PSF per RF row) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -190,6 +191,40 @@ int mcrt_convolve(mcrt_ctx *ctx, float *rf_dev, uint32_t n_elements, uint32_t n_
 /* the same on the n_frames images [n_frames][E][R] of an mcrt_trace_frames pass, in one launch per convolution pass */
 int mcrt_convolve_frames(mcrt_ctx *ctx, float *rf_dev, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
                          const float *axial, uint32_t n_ax, const float *lateral, uint32_t n_lat);
+/* ---- focal zones: a depth-dependent lateral PSF (psf.h:17-24 plans it: "lateral and elevation ranges vary according to distance to
+ * the transducer"; psf.h:34-58 builds one constant kernel).  The axial taps stay mcrt_psf_kernels' own.  RF row r lies at depth
+ * z_r = r * row_mm (path length, as the reference's row index; row_mm = the context's axial resolution in mm, 0.322 at 4.5 MHz) and gets
+ * its own n_lat lateral taps, at mcrt_psf_kernels' positions and spacing (res_um):
+ *   z_f(r)    the focus nearest to z_r (on a tie the shallower one); none when n_focus = 0
+ *   q         (z_r - z_f(r)) / focal_range_mm, in double; q = 0 when n_focus = 0
+ *   var(r)    (double)var_y * (1 + q*q)
+ *   g         sqrt(var_y / var(r))                         the area-preserving gain of a widening Gaussian
+ *   lat[r][i] (float)(g * exp(-0.5f * (y_i^2 / var(r))))    y_i as mcrt_psf_kernels, y_i^2 in double
+ * At a focal row (q = 0), and on every row when n_focus = 0, var(r) == var_y and g == 1: the row equals mcrt_psf_kernels' lateral taps
+ * bit for bit.  focal_range_mm sets how fast the beam widens away from a focus; it has no default that the reference backs (a Gaussian
+ * beam's Rayleigh range from var_y = 0.2 mm^2 at 4.5 MHz, about 3.8 mm, blurs nearly the whole image): the wrappers use 20 mm, a display
+ * choice no measurement backs.  The elevation kernel (var_z) is not modelled. */
+typedef struct {
+    uint32_t n_focus;            /* 0..8                                                    */
+    float    focus_mm[8];        /* the first n_focus: finite, >= 0, strictly ascending      */
+    float    focal_range_mm;     /* > 0 and finite when n_focus > 0                         */
+} mcrt_focus;                    /* 40 bytes: n_focus at offset 0, focus_mm at 4, focal_range_mm at 36 */
+/* the table lat_rows [n_rows][n_lat] (row-major) of the model above; host only, no GPU needed.  MCRT_ERR_INVALID for a null f / lat_rows,
+ * n_focus > 8, foci that are not finite, negative or not strictly ascending, focal_range_mm <= 0 or not finite (when n_focus > 0), var_y
+ * <= 0 or not finite, row_mm <= 0 or not finite, n_lat outside 1..32; MCRT_ERR_LIMIT for n_rows > 2048.  On an error lat_rows is untouched. */
+int mcrt_psf_focus_kernels(float var_y, uint32_t res_um, const mcrt_focus *f, uint32_t n_rows, double row_mm,
+                           float *lat_rows /* [n_rows][n_lat] */, uint32_t n_lat);
+/* mcrt_convolve_frames with one row of lateral taps per RF row: lat_rows is host memory [n_rows][n_lat] (mcrt_psf_focus_kernels, or any
+ * table).  The reference's index ranges and order of operations: the axial pass of mcrt_convolve_frames unchanged, then for output rows
+ * [n_ax, R-n_ax) and columns [n_lat/2, E-n_lat)  img[col][row] = sum_k tmp[col+k][row] * lat_rows[row][k], summed in k order with one
+ * rounding per multiply and per add.  A table whose rows all equal `lateral` gives mcrt_convolve_frames' image bit for bit.  Pixels
+ * outside those ranges keep their bits.  Limits and errors are mcrt_convolve_frames' (taps 1..16 axial and 1..32 lateral, MCRT_ERR_LIMIT),
+ * plus MCRT_ERR_INVALID for a null lat_rows and MCRT_ERR_LIMIT for n_rows > 2048; on any error nothing is launched and the image is
+ * untouched.  Asynchronous on the context's stream; lat_rows may be rewritten once the call returns.  The table is copied to the device
+ * only when it differs from the one there (a new table waits for the upload of the previous one); nothing is allocated once the table
+ * buffer (2048 x 32 floats, made by the first call) and the scratch of mcrt_convolve exist.  Groups: call it on mcrt_group_root(). */
+int mcrt_convolve_frames_depth(mcrt_ctx *ctx, float *rf_dev, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
+                               const float *axial, uint32_t n_ax, const float *lat_rows /* host [n_rows][n_lat] */, uint32_t n_lat);
 /* rf_image::envelope (rfimage.h:54-91) in place on a device image [E][R].  n_rows <= 2048 (MCRT_ERR_LIMIT beyond: a wavefront holds
  * its scan-line in LDS) -- the limit mcrt_params.n_rows has anyway; an image brought in through mcrt_import_rf is bound by it too.
  * An image of n_rows < 2 has no peak to find and is left unchanged. */
@@ -269,7 +304,7 @@ int mcrt_import_rf(mcrt_ctx *ctx, const float *host_rows_by_cols, uint32_t n_ele
  * texture and transducer replicated; every rank's [F][E_g][R] block then crosses xGMI once (hipMemcpyPeerAsync on the rank's own copy
  * stream) into GPU devices[0], where one kernel lays the blocks out as the [F][E][R] frames a single context would have produced, bit
  * for bit (RF bins are integer sums: no partition changes them).  PSF, envelope and scan conversion need neighbouring columns
- * (rfimage.h:113-118) and run on the gathered frames: call mcrt_convolve_frames / mcrt_envelope_frames / mcrt_scan_convert_frames, or
+ * (rfimage.h:113-118) and run on the gathered frames: call mcrt_convolve_frames (or mcrt_convolve_frames_depth) / mcrt_envelope_frames / mcrt_scan_convert_frames, or
  * mcrt_bmode_frames for the 8-bit display, on mcrt_group_root() -- no group call of their own is needed.
  * A group owns one tracing context per listed device (each driven by its own host thread, so G GPUs are fed in parallel) and a root
  * context on devices[0] for the gathered frames.  A device may be listed more than once: its contexts then share that GPU (how the

@@ -53,20 +53,25 @@ class BmodeParams(C.Structure):
                 ("reset_state", C.c_uint32), ("out_rows", C.c_uint32), ("out_cols", C.c_uint32), ("radius_mm", C.c_double), ("total_angle_rad", C.c_double)]
 
 
+class Focus(C.Structure):
+    """mcrt_focus (include/mcrt.h): 40 bytes, focus_mm at offset 4, focal_range_mm at 36"""
+    _fields_ = [("n_focus", C.c_uint32), ("focus_mm", C.c_float * 8), ("focal_range_mm", C.c_float)]
+
+
 NODE_DTYPE = np.dtype([("lo0", "<f4", 3), ("c0", "<i4"), ("hi0", "<f4", 3), ("c1", "<i4"),
                        ("lo1", "<f4", 3), ("pad0", "<u4"), ("hi1", "<f4", 3), ("pad1", "<u4")])
 SEGMENT_DTYPE = np.dtype([("from", "<f4", 3), ("to", "<f4", 3), ("dir", "<f4", 3),
                           ("reflected_intensity", "<f4"), ("initial_intensity", "<f4"), ("attenuation", "<f4"),
                           ("distance_traveled", "<f8"), ("media", "<i4"), ("tri", "<i4")])
-assert NODE_DTYPE.itemsize == 64 and SEGMENT_DTYPE.itemsize == 64 and C.sizeof(BvhNode) == 64 and C.sizeof(BmodeParams) == 48
+assert NODE_DTYPE.itemsize == 64 and SEGMENT_DTYPE.itemsize == 64 and C.sizeof(BvhNode) == 64 and C.sizeof(BmodeParams) == 48 and C.sizeof(Focus) == 40
 
 # every symbol include/mcrt.h declares (tests/test_abi.py checks the .so exports each one)
 SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create", "mcrt_destroy", "mcrt_set_stream",
            "mcrt_synchronize", "mcrt_default_params", "mcrt_set_params", "mcrt_get_params", "mcrt_import_rf", "mcrt_set_bvh_builder", "mcrt_upload_scene", "mcrt_update_triangles", "mcrt_refit_triangles", "mcrt_upload_texture",
-           "mcrt_set_transducer", "mcrt_trace_frame", "mcrt_trace_frames", "mcrt_trace_frames_poses", "mcrt_envelope_frames", "mcrt_scan_convert_frames", "mcrt_trace_frame_debug", "mcrt_cast_rays", "mcrt_convolve", "mcrt_convolve_frames",
+           "mcrt_set_transducer", "mcrt_trace_frame", "mcrt_trace_frames", "mcrt_trace_frames_poses", "mcrt_envelope_frames", "mcrt_scan_convert_frames", "mcrt_trace_frame_debug", "mcrt_cast_rays", "mcrt_convolve", "mcrt_convolve_frames", "mcrt_convolve_frames_depth",
            "mcrt_envelope", "mcrt_scan_convert", "mcrt_default_bmode", "mcrt_bmode_frames", "mcrt_export_rf", "mcrt_alloc", "mcrt_free", "mcrt_memcpy_d2h",
            "mcrt_memcpy_h2d", "mcrt_enable_stats", "mcrt_get_stats", "mcrt_enable_timing", "mcrt_get_kernel_time", "mcrt_get_kernel_times",
-           "mcrt_build_bvh", "mcrt_free_bvh", "mcrt_get_bvh", "mcrt_build_bvh4", "mcrt_free_bvh4", "mcrt_get_bvh4", "mcrt_row_thresholds", "mcrt_generate_texture", "mcrt_psf_kernels",
+           "mcrt_build_bvh", "mcrt_free_bvh", "mcrt_get_bvh", "mcrt_build_bvh4", "mcrt_free_bvh4", "mcrt_get_bvh4", "mcrt_row_thresholds", "mcrt_generate_texture", "mcrt_psf_kernels", "mcrt_psf_focus_kernels",
            "mcrt_transducer_elements", "mcrt_debug_math", "mcrt_debug_philox", "mcrt_debug_stamps", "mcrt_debug_tail_histograms", "mcrt_debug_set_error", "mcrt_debug_fast_paths", "mcrt_scan_maps",
            "mcrt_group_create", "mcrt_group_destroy", "mcrt_group_size", "mcrt_group_root", "mcrt_group_member", "mcrt_group_shard", "mcrt_group_set_params",
            "mcrt_group_set_bvh_builder", "mcrt_group_upload_scene", "mcrt_group_update_triangles", "mcrt_group_refit_triangles", "mcrt_group_upload_texture",
@@ -102,7 +107,7 @@ def load_library():
         "mcrt_cast_rays": [vp, u32, u32, u32, vp, vp, vp],
         "mcrt_convolve": [vp, vp, u32, u32, vp, u32, vp, u32], "mcrt_envelope": [vp, vp, u32, u32],
         "mcrt_scan_convert": [vp, vp, u32, u32, C.c_double, C.c_double, vp, u32, u32],
-        "mcrt_convolve_frames": [vp, vp, u32, u32, u32, vp, u32, vp, u32],
+        "mcrt_convolve_frames": [vp, vp, u32, u32, u32, vp, u32, vp, u32], "mcrt_convolve_frames_depth": [vp, vp, u32, u32, u32, vp, u32, vp, u32],
         "mcrt_trace_frames_poses": [vp, u32, u32, u32, u32, vp, vp, vp], "mcrt_envelope_frames": [vp, vp, u32, u32, u32],
         "mcrt_scan_convert_frames": [vp, vp, u32, u32, u32, C.c_double, C.c_double, vp, u32, u32],
         "mcrt_default_bmode": [C.POINTER(BmodeParams)], "mcrt_bmode_frames": [vp, vp, u32, u32, u32, C.POINTER(BmodeParams), vp, vp, vp, vp],
@@ -115,6 +120,7 @@ def load_library():
         "mcrt_build_bvh4": [C.POINTER(Bvh), C.POINTER(Bvh4)], "mcrt_free_bvh4": [C.POINTER(Bvh4)], "mcrt_get_bvh4": [vp, C.POINTER(Bvh4)],
         "mcrt_row_thresholds": [C.c_double, u32, vp],
         "mcrt_generate_texture": [vp, u32], "mcrt_psf_kernels": [C.c_float, C.c_float, C.c_float, u32, vp, u32, vp, u32],
+        "mcrt_psf_focus_kernels": [C.c_float, u32, C.POINTER(Focus), u32, C.c_double, vp, u32],
         "mcrt_transducer_elements": [u32, C.c_double, C.c_double, vp, vp, vp, vp],
         "mcrt_debug_math": [vp, i32, vp, vp, vp, u32], "mcrt_debug_philox": [vp, vp, vp, vp], "mcrt_debug_stamps": [vp, vp, i32], "mcrt_debug_tail_histograms": [vp, vp, i32], "mcrt_debug_set_error": [vp, u32], "mcrt_debug_fast_paths": [vp, vp],
         "mcrt_scan_maps": [u32, u32, C.c_double, C.c_double, u32, u32, u32, u32, vp, vp],

@@ -10,7 +10,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 
 # ------------------------------------------------------------------ host-side pieces (no GPU)
@@ -64,6 +64,33 @@ def host_psf(freq=4.5, var_x=0.05, var_y=0.2, res_um=145, n_ax=7, n_lat=13):
     ax = np.zeros(n_ax, np.float32); lat = np.zeros(n_lat, np.float32)
     check(load_library().mcrt_psf_kernels(freq, var_x, var_y, res_um, ptr(ax), n_ax, ptr(lat), n_lat))
     return ax, lat
+
+
+def focus_struct(focus_mm=(), focal_range_mm=20.0):
+    """mcrt_focus from a sequence of focal depths [mm] (more than 8 give n_focus > 8, which the library refuses)"""
+    f = Focus()
+    fm = [float(x) for x in (focus_mm or ())]
+    f.n_focus = len(fm)
+    for i, x in enumerate(fm[:8]):
+        f.focus_mm[i] = x
+    f.focal_range_mm = focal_range_mm
+    return f
+
+
+def host_psf_focus(var_y, res_um, n_rows, row_mm, focus_mm, focal_range_mm=20.0, n_lat=13):
+    """mcrt_psf_focus_kernels: the lateral taps of every RF row, float32 [n_rows][n_lat] (focal zones; the model is in include/mcrt.h).
+    focal_range_mm = 20 is a display choice that no measurement backs."""
+    out = np.zeros((n_rows, n_lat), np.float32)
+    f = focus_struct(focus_mm, focal_range_mm)
+    check(load_library().mcrt_psf_focus_kernels(var_y, res_um, C.byref(f), n_rows, row_mm, ptr(out), n_lat))
+    return out
+
+
+def row_pitch_mm(frequency):
+    """the RF row pitch [mm] of a context at `frequency` MHz: axial_res_um / 1000 with axial_res_um = (unsigned)(1.45f / f * 1000.0f)
+    (main.cpp:25,36; 0.322 at 4.5 MHz)"""
+    res_f = np.float32(np.float32(1.45) / np.float32(frequency))
+    return int(np.float32(res_f * np.float32(1000.0))) / 1000.0
 
 
 def host_transducer(n_elements, radius_cm, sep_mm, position, angles_deg):
@@ -120,10 +147,27 @@ class Transducer:
 
 
 class Psf:
-    """psf<axial,lateral,elevation,resolution_um>{freq, var_x, var_y, var_z} -- psf.h:34-58"""
+    """psf<axial,lateral,elevation,resolution_um>{freq, var_x, var_y, var_z} -- psf.h:34-58.
+    focus_mm: focal depths [mm] (up to 8, ascending) for a lateral kernel per RF row (focal zones, include/mcrt.h); None or empty: the
+    reference's one constant kernel.  focal_range_mm = 20 is a display choice that no measurement backs."""
 
-    def __init__(self, freq=4.5, var_x=0.05, var_y=0.2, var_z=0.1, axial_size=7, lateral_size=13, resolution_um=145):
+    def __init__(self, freq=4.5, var_x=0.05, var_y=0.2, var_z=0.1, axial_size=7, lateral_size=13, resolution_um=145, focus_mm=None, focal_range_mm=20.0):
         self.axial_kernel, self.lateral_kernel = host_psf(freq, var_x, var_y, resolution_um, axial_size, lateral_size)
+        self.var_y, self.resolution_um = var_y, resolution_um
+        self.focus_mm = tuple(float(x) for x in focus_mm) if focus_mm is not None else ()
+        self.focal_range_mm = focal_range_mm
+        self._rows = {}
+
+    @property
+    def has_focus(self):
+        return len(self.focus_mm) > 0
+
+    def lateral_rows(self, n_rows, row_mm):
+        """the lateral taps of every RF row, float32 [n_rows][lateral_size], for rows row_mm apart (Simulator.row_mm)"""
+        key = (n_rows, row_mm)
+        if key not in self._rows:
+            self._rows[key] = host_psf_focus(self.var_y, self.resolution_um, n_rows, row_mm, self.focus_mm, self.focal_range_mm, self.lateral_kernel.size)
+        return self._rows[key]
 
 
 # ------------------------------------------------------------------ C-ABI context
@@ -286,6 +330,13 @@ class Context:
         """rf_image::convolve on the [n_frames][E][R] images of a trace_frames pass, one launch per convolution pass"""
         ax = np.ascontiguousarray(axial, np.float32); lat = np.ascontiguousarray(lateral, np.float32)
         check(self.L.mcrt_convolve_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, ptr(ax), ax.size, ptr(lat), lat.size))
+
+    def convolve_frames_depth(self, rf_dev, n_frames, n_elements, n_rows, axial, lat_rows):
+        """mcrt_convolve_frames_depth: the convolution with the lateral taps of each RF row, lat_rows [n_rows][n_lat] (focal zones)"""
+        ax = np.ascontiguousarray(axial, np.float32); lat = np.ascontiguousarray(lat_rows, np.float32)
+        if lat.ndim != 2 or lat.shape[0] != n_rows:
+            raise ValueError("lat_rows needs one row of taps per RF row: (%d, n_lat), got shape %s" % (n_rows, lat.shape))
+        check(self.L.mcrt_convolve_frames_depth(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, ptr(ax), ax.size, ptr(lat), lat.shape[1]))
 
     def convolve(self, rf_dev, n_elements, n_rows, axial, lateral):
         ax = np.ascontiguousarray(axial, np.float32); lat = np.ascontiguousarray(lateral, np.float32)
@@ -490,8 +541,16 @@ class Simulator:
     def trace(self, frame_id=0):
         self.ctx.trace_frame(frame_id, self.rf_dev)
 
+    @property
+    def row_mm(self):
+        """the RF row pitch [mm]: the depth of row r is r * row_mm (path length, as the reference's row index)"""
+        return row_pitch_mm(self.ctx.params.frequency)
+
     def convolve(self):
-        self.ctx.convolve(self.rf_dev, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_kernel)
+        if self.psf.has_focus:
+            self.ctx.convolve_frames_depth(self.rf_dev, 1, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_rows(self.R, self.row_mm))
+        else:
+            self.ctx.convolve(self.rf_dev, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_kernel)
 
     def bmode(self, frame_id=0, **display):
         """trace -> convolve -> envelope -> mcrt_bmode_frames -> host: the displayed 8-bit frame, uint8 [out_rows][out_cols].

@@ -176,6 +176,9 @@ struct mcrt_ctx {
     // B-mode display (mcrt_bmode_frames): device TGC factors [MCRT_MAX_ROWS] + the peaks of a pass [65535] in one buffer, the factors' pinned
     // staging and the curve now on the device (its upload is waited for only when the next curve differs)
     Buf<float> d_disp; PinnedBuf<float> h_tgc; std::vector<float> tgc_on_dev; Event ev_tgc; bool tgc_copy_pending = false;
+    // focal zones (mcrt_convolve_frames_depth): the device table [n_lat][R] (room for MCRT_MAX_ROWS x 32), its pinned staging, and the
+    // table now on the device with its shape (its upload is waited for only when the next table differs)
+    Buf<float> d_lat_rows; PinnedBuf<float> h_lat_rows; std::vector<float> lat_on_dev; uint32_t lat_key[2] = { 0, 0 }; Event ev_lat; bool lat_copy_pending = false;
     // instrumentation
     Buf<unsigned long long> d_stats; bool stats_on = false;
     bool timing_on = false; int timing_level = 0;       // 1: the walk's launches are bracketed by HIP events; 2: k_shade's and k_march's too
@@ -1057,6 +1060,44 @@ extern "C" int mcrt_convolve_frames(mcrt_ctx *c, float *rf_dev, uint32_t n_frame
 extern "C" int mcrt_convolve(mcrt_ctx *c, float *rf_dev, uint32_t E, uint32_t R, const float *ax, uint32_t n_ax, const float *lat, uint32_t n_lat)
 {
     return mcrt_convolve_frames(c, rf_dev, 1, E, R, ax, n_ax, lat, n_lat);
+}
+
+// The contract is in include/mcrt.h.  Everything is checked before anything is launched; the caller's table [R][n_lat] is compared bit
+// for bit with the one on the device and, only when it differs, transposed tap-major [n_lat][R] into the pinned staging and uploaded.
+extern "C" int mcrt_convolve_frames_depth(mcrt_ctx *c, float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const float *ax, uint32_t n_ax,
+                                          const float *lat_rows, uint32_t n_lat)
+{
+    CTX_TRY(c);
+    if (!rf_dev || !ax || !lat_rows || E == 0 || R == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "mcrt_convolve_frames_depth: bad arguments");
+    if (n_ax == 0 || n_ax > 16 || n_lat == 0 || n_lat > 32) return set_error(MCRT_ERR_LIMIT, "kernel sizes must be 1..16 axial, 1..32 lateral");
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "mcrt_convolve_frames_depth: at most %d rows", MCRT_MAX_ROWS);
+    { int rc = ensure_tmp(c, (size_t)n_frames * E * R); if (rc) return rc; }
+    constexpr size_t TABLE = (size_t)MCRT_MAX_ROWS * 32;
+    if (!c->d_lat_rows) {                               // once per context, all three or none
+        Buf<float> d; PinnedBuf<float> h; Event ev;
+        HIP_TRY(d.alloc(TABLE));
+        HIP_TRY(h.alloc(TABLE));
+        HIP_TRY(hipEventCreateWithFlags(&ev.h, hipEventDisableTiming));
+        c->d_lat_rows = std::move(d); c->h_lat_rows = std::move(h); c->ev_lat = std::move(ev);
+        c->lat_on_dev.assign(TABLE, 0.0f); c->lat_key[0] = c->lat_key[1] = 0;
+    }
+    const size_t n = (size_t)n_lat * R;
+    if (c->lat_key[0] != R || c->lat_key[1] != n_lat || memcmp(lat_rows, c->lat_on_dev.data(), 4 * n)) {   // (lat_on_dev: the caller's layout)
+        if (c->lat_copy_pending) HIP_TRY(hipEventSynchronize(c->ev_lat));     // the staging buffer still feeds the previous table's copy
+        float *h = c->h_lat_rows;
+        for (uint32_t r = 0; r < R; r++)
+            for (uint32_t k = 0; k < n_lat; k++) h[(size_t)k * R + r] = lat_rows[(size_t)r * n_lat + k];
+        c->lat_key[0] = c->lat_key[1] = 0;              // (no table until its copy is enqueued)
+        HIP_TRY(hipMemcpyAsync(c->d_lat_rows, h, 4 * n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipEventRecord(c->ev_lat, c->stream));
+        c->lat_copy_pending = true;
+        memcpy(c->lat_on_dev.data(), lat_rows, 4 * n);
+        c->lat_key[0] = R; c->lat_key[1] = n_lat;
+    }
+    mcrt::ConvTaps t; memset(&t, 0, sizeof t);
+    memcpy(t.ax, ax, 4 * n_ax); t.n_ax = n_ax; t.n_lat = n_lat;
+    HIP_TRY(mcrt::launch_convolve_depth(rf_dev, c->d_tmp, n_frames, E, R, t, c->d_lat_rows, c->stream));
+    return MCRT_OK;
 }
 
 extern "C" int mcrt_envelope_frames(mcrt_ctx *c, float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R)

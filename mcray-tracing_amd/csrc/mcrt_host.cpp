@@ -343,6 +343,45 @@ extern "C" int mcrt_psf_kernels(float freq, float var_x, float var_y, uint32_t r
     return MCRT_OK;
 }
 
+// Focal zones (the model is in include/mcrt.h): mcrt_psf_kernels' lateral taps per RF row, widened by the row's distance to the nearest
+// focus and scaled by g = sqrt(var_y / var) to keep their area.  At q = 0, var == var_y and g == 1 exactly, so the row is
+// mcrt_psf_kernels' own expression bit for bit.
+extern "C" int mcrt_psf_focus_kernels(float var_y, uint32_t res_um, const mcrt_focus *f, uint32_t n_rows, double row_mm, float *lat_rows, uint32_t n_lat)
+{
+    if (!f || !lat_rows) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_focus_kernels: null %s", f ? "lat_rows" : "focus");
+    if (n_lat == 0 || n_lat > 32) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_focus_kernels: n_lat must be 1..32 (%u)", n_lat);
+    if (!(std::isfinite(var_y) && var_y > 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_focus_kernels: var_y must be finite and > 0");
+    if (!(std::isfinite(row_mm) && row_mm > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_focus_kernels: row_mm must be finite and > 0");
+    if (f->n_focus > 8) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_focus_kernels: at most 8 foci (%u)", f->n_focus);
+    for (uint32_t j = 0; j < f->n_focus; j++) {
+        if (!(std::isfinite(f->focus_mm[j]) && f->focus_mm[j] >= 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_focus_kernels: focus_mm[%u] must be finite and >= 0", j);
+        if (j > 0 && !(f->focus_mm[j] > f->focus_mm[j - 1])) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_focus_kernels: foci must be strictly ascending");
+    }
+    if (f->n_focus > 0 && !(std::isfinite(f->focal_range_mm) && f->focal_range_mm > 0.0f))
+        return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_focus_kernels: focal_range_mm must be finite and > 0");
+    if (n_rows > MCRT_MAX_ROWS) return mcrt::set_error(MCRT_ERR_LIMIT, "mcrt_psf_focus_kernels: at most %d rows", MCRT_MAX_ROWS);
+    const float res = (float)res_um / 1000.0f;
+    const float half_lat = (float)((size_t)n_lat * res_um) / 1000.0f / 2.0f;
+    for (uint32_t r = 0; r < n_rows; r++) {
+        const double z = (double)r * row_mm;
+        double var = (double)var_y, g = 1.0;
+        if (f->n_focus > 0) {
+            uint32_t best = 0;
+            for (uint32_t j = 1; j < f->n_focus; j++)          // strictly nearer only: a tie keeps the shallower focus
+                if (std::fabs(z - (double)f->focus_mm[j]) < std::fabs(z - (double)f->focus_mm[best])) best = j;
+            const double q = (z - (double)f->focus_mm[best]) / (double)f->focal_range_mm;
+            var = (double)var_y * (1.0 + q * q);
+            g = std::sqrt((double)var_y / var);
+        }
+        for (uint32_t i = 0; i < n_lat; i++) {
+            const float y = (float)i * res - half_lat;
+            const double y2 = (double)y * (double)y;
+            lat_rows[(size_t)r * n_lat + i] = (float)(g * std::exp(-0.5f * (y2 / var)));
+        }
+    }
+    return MCRT_OK;
+}
+
 // ---- transducer<N>::transducer (transducer.h:24-62) -------------------------------------------
 namespace {
 struct F3 { float x, y, z; };

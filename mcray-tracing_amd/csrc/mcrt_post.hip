@@ -1,5 +1,5 @@
 // mcrt_post.hip -- after the accumulation: k_finalize (fixed-point RF bins -> float image, rf_image::clear rfimage.h:161), k_conv_*
-// (rf_image::convolve, rfimage.h:93-123), k_envelope (rfimage.h:54-91), k_remap (the scan conversion of rf_image::postprocess,
+// (rf_image::convolve, rfimage.h:93-123; k_conv_lateral_rows its lateral pass with a tap row per RF row: focal zones), k_envelope (rfimage.h:54-91), k_remap (the scan conversion of rf_image::postprocess,
 // rfimage.h:125-140), k_transpose, and k_blocks_to_frames (the ranks' blocks of an mcrt_group laid out as frames).
 #include "mcrt_device.h"
 
@@ -48,6 +48,51 @@ __global__ void k_conv_lateral(const float *tmp, float *img, uint32_t n_img, uin
     float conv = 0;
     for (int k = 0; k < nl; k++) conv += tmp[i + (size_t)k * R] * taps.lat[k];
     img[i] = conv;
+}
+
+// The lateral pass of mcrt_convolve_frames_depth: rfimage.h:111-122 with taps of their own per row (focal zones),
+//     img[col][row] = sum_k tmp[col+k][row] * lat[k][row],  row in [na, R-na), col in [nl/2, E-nl),
+// lat tap-major [nl][R] (the host transposes the caller's [R][nl]).  A lane owns one row of a strip of MCRT_CONV_STRIP neighbouring
+// columns: it loads each tap once for the whole strip, and the strip's window slides by one column per tap, so the sums of a strip
+// read nl + STRIP - 1 values of tmp instead of STRIP * nl.  Neighbouring lanes are neighbouring rows, so every tap and window load of
+// a wavefront is one contiguous line.  Each sum is still sequential over k from 0, one rounding per multiply and per add.
+// (8 columns measured best: 20 x 128 x 465 images 9.0 us at 2, 4 or 8 columns, 12.8 at one; 128 frames 20.3 us at 8, 29.7 at 4,
+// 42.3 at 2, 67.2 at 1; k_conv_lateral 11.3 and 59.8 us -- DESIGN 5.5)
+#ifndef MCRT_CONV_STRIP
+#define MCRT_CONV_STRIP 8
+#endif
+__global__ void k_conv_lateral_rows(const float *tmp, float *img, uint32_t n_img, uint32_t E, uint32_t R, uint32_t na, uint32_t nl,
+                                    uint32_t n_strips, const float *lat)
+{
+    constexpr int C = MCRT_CONV_STRIP;
+    const uint32_t nr = R - 2u * na;                                            // rows of the window (> 0: the launcher checks)
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n_img * n_strips * nr) return;
+    const uint32_t row = na + (uint32_t)(i % nr);
+    const size_t sf = i / nr;                                                   // frame * n_strips + strip
+    const uint32_t strip = (uint32_t)(sf % n_strips), f = (uint32_t)(sf / n_strips);
+    const uint32_t col0 = nl / 2u + strip * (uint32_t)C, col_end = E - nl;      // this strip's first column, the window's end
+    const float *t = tmp + ((size_t)f * E) * R + row;                           // column c of frame f at t[c * R]
+    float win[C], conv[C];
+#pragma unroll
+    for (int j = 0; j < C; j++) {                                               // columns past the image's last are never summed: 0
+        conv[j] = 0.0f;
+        win[j] = col0 + (uint32_t)j < E ? t[(size_t)(col0 + j) * R] : 0.0f;
+    }
+    for (uint32_t k = 0; k < nl; k++) {
+        const float w = lat[(size_t)k * R + row];
+        const uint32_t c = col0 + (uint32_t)C + k;                              // the column the window takes in for tap k + 1
+        const float next = (k + 1u < nl && c < E) ? t[(size_t)c * R] : 0.0f;
+#pragma unroll
+        for (int j = 0; j < C; j++) conv[j] += win[j] * w;
+#pragma unroll
+        for (int j = 0; j < C - 1; j++) win[j] = win[j + 1];                    // slide: win[j] = tmp[col0 + j + k + 1]
+        win[C - 1] = next;
+    }
+    float *o = img + ((size_t)f * E) * R + row;
+#pragma unroll
+    for (int j = 0; j < C; j++)
+        if (col0 + (uint32_t)j < col_end) o[(size_t)(col0 + j) * R] = conv[j];
 }
 
 // rfimage.h:54-91, one WAVEFRONT per scan-line.  The reference walks a column once: whenever the signal stops ascending at row i
@@ -152,6 +197,19 @@ hipError_t launch_convolve(float *img, float *tmp, uint32_t n_img, uint32_t E, u
     const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
     hipLaunchKernelGGL(k_conv_axial, grid, blk, 0, st, (const float *)img, tmp, n_img, E, R, taps);
     hipLaunchKernelGGL(k_conv_lateral, grid, blk, 0, st, (const float *)tmp, img, n_img, E, R, taps);
+    return hipGetLastError();
+}
+
+hipError_t launch_convolve_depth(float *img, float *tmp, uint32_t n_img, uint32_t E, uint32_t R, const ConvTaps &taps, const float *lat, hipStream_t st)
+{
+    const size_t n = (size_t)n_img * E * R;
+    hipLaunchKernelGGL(k_conv_axial, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float *)img, tmp, n_img, E, R, taps);
+    const uint32_t na = taps.n_ax, nl = taps.n_lat;
+    if (R > 2u * na && E > nl + nl / 2u) {                                      // else the lateral window is empty (as in k_conv_lateral)
+        const uint32_t n_strips = (E - nl - nl / 2u + MCRT_CONV_STRIP - 1u) / MCRT_CONV_STRIP;
+        const size_t m = (size_t)n_img * n_strips * (R - 2u * na);
+        hipLaunchKernelGGL(k_conv_lateral_rows, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const float *)tmp, img, n_img, E, R, na, nl, n_strips, lat);
+    }
     return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 // mattausch_hip -- the reference's program (main.cpp:42-161) on the MI355X library:
 //     mattausch_hip <scene.json> [frames] [samples] [out.pgm] [rf.bin] [--gpus N | --devices 0,1,...]
-//                   [--db DR] [--gain G] [--ref-log] [--persistence A]
+//                   [--db DR] [--gain G] [--ref-log] [--persistence A] [--focus-mm F1[,F2,...]] [--focal-range-mm R]
 // --gpus N: the first N GPUs of the node, the frame's scan-lines sharded over them (mcrt_group_*: one tracing context and host thread per
 // GPU, the blocks gathered on GPU 0); --devices lists them explicitly, and may repeat one (two ranks sharing a GPU: the one-GPU test).
 // Same constants (main.cpp:23-37), same frame loop body; instead of blocking on imshow/waitKey every frame it
@@ -9,6 +9,9 @@
 // log-compressed to 8-bit grey on the GPU (mcrt_bmode_frames) and the PGM holds those bytes: --db DR decibels of dynamic range below each
 // frame's peak (60 when only another option is given), --gain G dB, --ref-log the reference's log10(v+1)/log10(max+1) instead of
 // decibels, --persistence A temporal smoothing y = A y_prev + (1-A) s across the frames of the run.
+// --focus-mm 40 (or 30,60,90: up to 8, ascending) places focal zones: every RF row gets its own lateral PSF, narrowest at the nearest
+// focus and widening with the distance to it over --focal-range-mm R (20 mm, a display choice; mcrt_psf_focus_kernels).  Without
+// --focus-mm the reference's one lateral kernel is used and --focal-range-mm has no effect.
 #include "mcrt_host.hpp"
 #include <chrono>
 #include <cstring>
@@ -31,6 +34,7 @@ int main(int argc, char **argv)
     mcrt_bmode_params display; mcrt_default_bmode(&display);
     display.reset_state = 0;                          // the persistence state runs on from frame to frame
     bool bmode = false;
+    std::vector<float> focus_mm; float focal_range_mm = 20.0f;
     {   // the options, taken out of the positional arguments
         int keep = 1;
         for (int i = 1; i < argc; i++) {
@@ -38,6 +42,12 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--gain") && i + 1 < argc) { display.gain_db = (float)std::atof(argv[++i]); bmode = true; }
             else if (!std::strcmp(argv[i], "--ref-log")) { display.mode = MCRT_BMODE_REF_LOG; bmode = true; }
             else if (!std::strcmp(argv[i], "--persistence") && i + 1 < argc) { display.persistence = (float)std::atof(argv[++i]); bmode = true; }
+            else if (!std::strcmp(argv[i], "--focus-mm") && i + 1 < argc) {
+                focus_mm.clear();
+                for (const char *q = argv[i + 1]; *q;) { focus_mm.push_back((float)std::atof(q)); while (*q && *q != ',') q++; if (*q == ',') q++; }
+                i++;
+            }
+            else if (!std::strcmp(argv[i], "--focal-range-mm") && i + 1 < argc) focal_range_mm = (float)std::atof(argv[++i]);
             else if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) { devices.clear(); for (int d = 0; d < std::max(1, std::atoi(argv[i + 1])); d++) devices.push_back(d); i++; }
             else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {
                 devices.clear();
@@ -54,7 +64,11 @@ int main(int argc, char **argv)
     const unsigned samples = argc > 3 ? (unsigned)std::atoi(argv[3]) : 5;   // samples_te (main.cpp:27)
     try {
         const json cfg = load_json(argv[1]);
-        const psf_ psf{ transducer_frequency, 0.05f, 0.2f, 0.1f };
+        const psf_ psf = [&] {
+            psf_ p{ transducer_frequency, 0.05f, 0.2f, 0.1f };
+            if (!focus_mm.empty()) p.set_focus(focus_mm.data(), (uint32_t)focus_mm.size(), focal_range_mm);
+            return p;
+        }();
         const auto &t_pos = cfg.at("transducerPosition");
         const auto &t_dir = cfg.at("transducerAngles");
         // millimeter_t sep = amplitude.to<float>() * radius / elements (main.cpp:66): float * cm -> cm, then -> mm

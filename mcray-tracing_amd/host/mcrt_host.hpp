@@ -292,9 +292,31 @@ template <size_t axial_size, size_t lateral_size, size_t elevation_size, unsigne
 class psf {
     static_assert(axial_size % 2 && lateral_size % 2 && elevation_size % 2, "kernel sizes must be odd");
 public:
-    psf(float freq, float var_x, float var_y, float /*var_z*/)
+    psf(float freq, float var_x, float var_y, float /*var_z*/) : var_y(var_y)
     {
         check(mcrt_psf_kernels(freq, var_x, var_y, resolution_micrometers, axial_kernel.data(), axial_size, lateral_kernel.data(), lateral_size), "psf");
+    }
+    // focal zones (psf.h:17-24 plans them): up to 8 ascending focal depths [mm]; rf_image::convolve then gives every RF row its own lateral
+    // taps (mcrt_psf_focus_kernels, the model in mcrt.h).  n = 0 goes back to the reference's one constant kernel.  focal_range_mm = 20 is
+    // a display choice that no measurement backs.  The foci are checked when the table is made (by the first convolve).
+    void set_focus(const float *focus_mm, uint32_t n, float focal_range_mm = 20.0f)
+    {
+        focus = mcrt_focus{};
+        focus.n_focus = n;
+        for (uint32_t i = 0; i < n && i < 8; i++) focus.focus_mm[i] = focus_mm[i];
+        focus.focal_range_mm = focal_range_mm;
+        table.clear(); table_rows = 0;
+    }
+    bool has_focus() const { return focus.n_focus > 0; }
+    // the lateral taps of every RF row [n_rows][lateral_size] for rows row_mm apart; made once per (n_rows, row_mm)
+    const std::vector<float> &lateral_rows(uint32_t n_rows, double row_mm) const
+    {
+        if (table.empty() || table_rows != n_rows || table_row_mm != row_mm) {
+            std::vector<float> t((size_t)n_rows * lateral_size);
+            check(mcrt_psf_focus_kernels(var_y, resolution_micrometers, &focus, n_rows, row_mm, t.data(), (uint32_t)lateral_size), "psf focus");
+            table = std::move(t); table_rows = n_rows; table_row_mm = row_mm;
+        }
+        return table;
     }
     constexpr size_t get_axial_size() const { return axial_size; }
     constexpr size_t get_lateral_size() const { return lateral_size; }
@@ -302,6 +324,10 @@ public:
     std::array<float, axial_size> axial_kernel;
     std::array<float, lateral_size> lateral_kernel;
     std::array<float, elevation_size> elevation_kernel{};   // declared and never filled in the reference (psf.h:77)
+    float var_y;
+private:
+    mcrt_focus focus{};
+    mutable std::vector<float> table; mutable uint32_t table_rows = 0; mutable double table_row_mm = 0.0;
 };
 
 // ---------------------------------------------------------------- GPU context shared by scene and rf_image
@@ -582,6 +608,11 @@ public:
     template <typename psf_> void convolve(const psf_ &p)
     {
         to_device();
+        if (p.has_focus()) {   // focal zones: a lateral kernel per row, rows axial_resolution_um / 1000 mm apart
+            const std::vector<float> &lat = p.lateral_rows(max_rows, (double)axial_resolution_um / 1000.0);
+            check(mcrt_convolve_frames_depth(dev->ctx, rf_dev, 1, columns, max_rows, p.axial_kernel.data(), (uint32_t)p.get_axial_size(), lat.data(), (uint32_t)p.get_lateral_size()), "mcrt_convolve_frames_depth");
+            return;
+        }
         check(mcrt_convolve(dev->ctx, rf_dev, columns, max_rows, p.axial_kernel.data(), (uint32_t)p.get_axial_size(), p.lateral_kernel.data(), (uint32_t)p.get_lateral_size()), "mcrt_convolve");
     }
     void envelope() { to_device(); check(mcrt_envelope(dev->ctx, rf_dev, columns, max_rows), "mcrt_envelope"); }
