@@ -29,12 +29,14 @@
 extern "C" {
 #endif
 
-#define MCRT_VERSION 108   /* round 3: + mcrt_trace_frames_poses, mcrt_envelope_frames, mcrt_scan_convert_frames; the slab rule of the closest-hit contract is one fma per plane;
+#define MCRT_VERSION 109  /* round 3: + mcrt_trace_frames_poses, mcrt_envelope_frames, mcrt_scan_convert_frames; the slab rule of the closest-hit contract is one fma per plane;
                               104: + the test hooks mcrt_debug_set_error, mcrt_debug_fast_paths; RF images are NaN while the device error word is set;
                               105 (round 4): + mcrt_group_* (several GPUs behind one call), mcrt_scan_maps; the scan-conversion maps follow the reference's float promotions;
                               106 (round 5): environment knobs are only read under MCRT_TUNING=1; the HIP-graph replay of passes (MCRT_GRAPH) is gone;
                               107: + mcrt_default_bmode, mcrt_bmode_frames (log-compressed 8-bit B-mode frames: dynamic range, gain, TGC, persistence);
-                              108: + mcrt_focus, mcrt_psf_focus_kernels, mcrt_convolve_frames_depth (focal zones: a lateral PSF per RF row) */
+                              108: + mcrt_focus, mcrt_psf_focus_kernels, mcrt_convolve_frames_depth (focal zones: a lateral PSF per RF row);
+                              109: + mcrt_transducer_elevation_axis, mcrt_elevation_planes, mcrt_psf_elevation_kernels, mcrt_elevation_frames (slice thickness:
+                                   elevation planes traced as one pose pass and folded with the elevation PSF) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -203,7 +205,7 @@ int mcrt_convolve_frames(mcrt_ctx *ctx, float *rf_dev, uint32_t n_frames, uint32
  * At a focal row (q = 0), and on every row when n_focus = 0, var(r) == var_y and g == 1: the row equals mcrt_psf_kernels' lateral taps
  * bit for bit.  focal_range_mm sets how fast the beam widens away from a focus; it has no default that the reference backs (a Gaussian
  * beam's Rayleigh range from var_y = 0.2 mm^2 at 4.5 MHz, about 3.8 mm, blurs nearly the whole image): the wrappers use 20 mm, a display
- * choice no measurement backs.  The elevation kernel (var_z) is not modelled. */
+ * choice no measurement backs.  The elevation kernel (var_z) is modelled by the slice-thickness block below (elevation planes). */
 typedef struct {
     uint32_t n_focus;            /* 0..8                                                    */
     float    focus_mm[8];        /* the first n_focus: finite, >= 0, strictly ascending      */
@@ -225,6 +227,57 @@ int mcrt_psf_focus_kernels(float var_y, uint32_t res_um, const mcrt_focus *f, ui
  * buffer (2048 x 32 floats, made by the first call) and the scratch of mcrt_convolve exist.  Groups: call it on mcrt_group_root(). */
 int mcrt_convolve_frames_depth(mcrt_ctx *ctx, float *rf_dev, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
                                const float *axial, uint32_t n_ax, const float *lat_rows /* host [n_rows][n_lat] */, uint32_t n_lat);
+/* ---- slice thickness: elevation planes and the elevation PSF (psf.h:16-18 names the elevation range, psf.h:42 takes var_z, psf.h:77
+ * declares elevation_kernel; the reference never fills or applies it: its rf_image is two-dimensional, every frame the echo of an
+ * infinitely thin sheet).  A frame with slice thickness is K parallel copies of the probe, spread along its elevation direction, traced
+ * as ONE pose pass (mcrt_trace_frames_poses / mcrt_group_trace_frames_poses) into a stack [K][E][R] and folded into one RF image with the
+ * elevation weights BEFORE mcrt_convolve*: a target beside the image plane then shows up in the picture (the partial-volume artefact).
+ * The planes are parallel: the rays are not steered in elevation, the lens is modelled by the weights alone.
+ *
+ * The frame-id rule (applied by the wrappers: Simulator(elevation=True), rf_image::trace(frame, transducer, psf), mattausch_hip
+ * --elevation): image f of a pass that starts at frame id f0 traces its plane k with frame id (f0 + f) * K + k -- every plane has its own
+ * random streams (the tissue beside the plane is other tissue), and frame f is the same picture traced alone or inside a pass.  The
+ * limits of mcrt_trace_frames_poses then apply to n_frames * K (1024 frames, 2^27 paths). */
+/* (psf.h:16-18,42,77) the probe's elevation direction: the vector (0,0,1) taken through the three rotations of mcrt_transducer_elements,
+ * in its order and float arithmetic (about z by angles_deg[2], about x by angles_deg[0], about y by angles_deg[1]).  Exactly (0,0,1) for
+ * angles (0,0,a).  Host only.  MCRT_ERR_INVALID for a null pointer. */
+int mcrt_transducer_elevation_axis(const float angles_deg[3], float axis[3]);
+/* (psf.h:16-18,42,77) K parallel copies of an element table, plane k shifted along `axis` by
+ *   z_k = (float)(((double)k - (double)((K - 1) / 2)) * (double)pitch_um / 1000.0)   [mm]   ((K - 1) / 2 an integer division: z = 0 at plane (K-1)/2)
+ *   o_k = (float)((double)z_k / 10.0)                                                 scene units (cm, as the radius of transducer.h:24-62)
+ *   pos_out[k][e][c] = pos[e][c] + o_k * axis[c]   one float multiply and one float add, not fused;   dir_out[k][e] = dir[e]
+ * z_mm_out [K] receives z_k (may be NULL).  K = 1 is the probe's own plane: the input table bit for bit.  CENTRED positions are a deliberate
+ * departure from the off-centre tap positions of psf.h:40-57 (i * res - size * res / 2): those belong to the forward-looking windows of
+ * rf_image::convolve, while a plane is a place in the scene.  Host only.  MCRT_ERR_INVALID for a null pos / dir / axis / pos_out / dir_out,
+ * n_elements == 0, K outside 1..32, pitch_um == 0, an axis that is not finite; on an error nothing is written. */
+int mcrt_elevation_planes(const float *pos /*[E][3]*/, const float *dir /*[E][3]*/, uint32_t n_elements, const float axis[3], uint32_t n_planes,
+                          uint32_t pitch_um, float *pos_out /*[K][E][3]*/, float *dir_out /*[K][E][3]*/, float *z_mm_out /*[K] or NULL*/);
+/* (psf.h:16-18,42,77) the elevation weights w_rows [n_rows][K] (row-major), one row per RF row: the depth model of mcrt_psf_focus_kernels
+ * (z_r = r * row_mm, the nearest focus, q, var(r) = var_z (1 + q*q), g = sqrt(var_z / var(r)), all in double; f == NULL or n_focus == 0:
+ * q = 0 on every row -- an acoustic lens has one fixed elevation focus, so n_focus is normally 0 or 1) at the plane positions z_k of
+ * mcrt_elevation_planes:
+ *   v[r][k] = g * exp(-0.5 * (z_k^2 / var(r)))      in double, z_k^2 in double from the float z_k
+ *   w[r][k] = (float)v[r][k]                        normalize == 0: as the reference leaves its lateral taps; the centre weight is exactly 1 without foci
+ *   w[r][k] = (float)(v[r][k] / (v[r][0] + v[r][1] + ...))   normalize != 0: the sum in k order and the division in double, one rounding;
+ *                                                   tissue that does not vary across the slice keeps its brightness
+ * Rows are symmetric bit for bit for odd K.  Host only.  MCRT_ERR_INVALID for a null w_rows, K outside 1..32, pitch_um == 0, var_z <= 0 or not
+ * finite, row_mm <= 0 or not finite, and mcrt_psf_focus_kernels' conditions on *f when it is given; MCRT_ERR_LIMIT for n_rows > 2048.  On an
+ * error w_rows is untouched. */
+int mcrt_psf_elevation_kernels(float var_z, uint32_t pitch_um, const mcrt_focus *f /* or NULL */, uint32_t n_rows, double row_mm, int normalize,
+                               float *w_rows /* [n_rows][K] */, uint32_t n_planes);
+/* (psf.h:16-18,42,77) folds the K plane images of every frame:
+ *   rf[f][e][r] = sum over k = 0..K-1 of planes[f][k][e][r] * w_rows[r][k]
+ * summed in k order starting from 0.0f, one float rounding per multiply and per add, no fma (the rule of mcrt_convolve_frames_depth).
+ * So a NaN or an infinity in any plane reaches the output even under a zero weight (a scan-line the reference turns NaN by total internal
+ * reflection stays NaN), and K = 1 with weight 1 copies the image (a -0.0 becomes +0.0).  Every (f, e, r) is written: there are no borders.
+ * planes_dev [n_frames][K][E][R] and rf_dev [n_frames][E][R] are device memory and must not overlap (MCRT_ERR_INVALID); w_rows is host
+ * memory (mcrt_psf_elevation_kernels, or any table) and may be rewritten once the call returns.  Asynchronous on the context's stream.
+ * MCRT_ERR_INVALID for null pointers and zero sizes, MCRT_ERR_LIMIT for K > 32, n_rows > 2048 or a stack of 2^40 floats or more; on an
+ * error nothing is launched and rf_dev is untouched.  The table lives on the device (tap-major, a buffer of its own beside the focal zones'
+ * so that a frame using both uploads neither) and is copied only when it differs from the one there (a new table waits for the upload of
+ * the previous one); nothing is allocated after the first call.  Groups: call it on mcrt_group_root() after mcrt_group_trace_frames_poses. */
+int mcrt_elevation_frames(mcrt_ctx *ctx, const float *planes_dev /* [n_frames][K][E][R] */, uint32_t n_frames, uint32_t n_planes,
+                          uint32_t n_elements, uint32_t n_rows, const float *w_rows /* host [n_rows][K] */, float *rf_dev /* [n_frames][E][R] */);
 /* rf_image::envelope (rfimage.h:54-91) in place on a device image [E][R].  n_rows <= 2048 (MCRT_ERR_LIMIT beyond: a wavefront holds
  * its scan-line in LDS) -- the limit mcrt_params.n_rows has anyway; an image brought in through mcrt_import_rf is bound by it too.
  * An image of n_rows < 2 has no peak to find and is left unchanged. */

@@ -5,7 +5,7 @@ Python here is plumbing for tests and bench.py (ctypes over libmcrt_hip.so); the
 HIP library in csrc/ and the C++ host mirror of the reference API in host/.
 """
 from ._lib import load_library, build_library, McrtError, Params, MeshRec, BvhNode, Stats, BmodeParams, Focus, SEGMENT_DTYPE  # noqa: F401
-from .api import Context, Group, shard_range, Simulator, bmode_params, Transducer, Psf, host_build_bvh, host_build_bvh4, host_row_thresholds, host_texture, host_psf, host_psf_focus, focus_struct, row_pitch_mm, host_transducer, host_scan_maps  # noqa: F401
+from .api import Context, Group, shard_range, Simulator, bmode_params, Transducer, Psf, host_build_bvh, host_build_bvh4, host_row_thresholds, host_texture, host_psf, host_psf_focus, focus_struct, row_pitch_mm, host_transducer, host_scan_maps, host_elevation_axis, host_elevation_planes, host_psf_elevation  # noqa: F401
 from . import synth, scene_io  # noqa: F401
 
 

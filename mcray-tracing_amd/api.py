@@ -100,6 +100,31 @@ def host_transducer(n_elements, radius_cm, sep_mm, position, angles_deg):
     return pos, d
 
 
+def host_elevation_axis(angles_deg):
+    """mcrt_transducer_elevation_axis: the probe's elevation direction, float32 [3] ((0,0,1) through the probe's rotations)"""
+    a = np.asarray(angles_deg, np.float32); out = np.zeros(3, np.float32)
+    check(load_library().mcrt_transducer_elevation_axis(ptr(a), ptr(out)))
+    return out
+
+
+def host_elevation_planes(pos, dirs, axis, n_planes, pitch_um):
+    """mcrt_elevation_planes: K parallel copies of an element table spread along `axis` -> (pos [K][E][3], dir [K][E][3], z_mm [K])"""
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3); dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    axis = np.ascontiguousarray(axis, np.float32)
+    E, K = pos.shape[0], max(int(n_planes), 0)
+    po = np.zeros((K, E, 3), np.float32); do = np.zeros((K, E, 3), np.float32); z = np.zeros(K, np.float32)
+    check(load_library().mcrt_elevation_planes(ptr(pos), ptr(dirs), E, ptr(axis), n_planes, pitch_um, ptr(po), ptr(do), ptr(z)))
+    return po, do, z
+
+
+def host_psf_elevation(var_z, pitch_um, n_rows, row_mm, focus_mm=(), focal_range_mm=20.0, n_planes=7, normalize=True):
+    """mcrt_psf_elevation_kernels: the elevation weights of every RF row, float32 [n_rows][n_planes] (slice thickness; include/mcrt.h)"""
+    out = np.zeros((n_rows, max(int(n_planes), 0)), np.float32)
+    f = focus_struct(focus_mm, focal_range_mm)
+    check(load_library().mcrt_psf_elevation_kernels(var_z, pitch_um, C.byref(f), n_rows, row_mm, 1 if normalize else 0, ptr(out), n_planes))
+    return out
+
+
 def host_scan_maps(n_elements, n_rows, radius_mm=30.0, total_angle=1.0471975511965976, max_travel_us=100, speed_of_sound=1500, out_rows=400, out_cols=500):
     """rf_image::create_mapping (rfimage.h:183-215) as the library evaluates it: (map_row, map_col), each [out_rows][out_cols]"""
     mr = np.zeros((out_rows, out_cols), np.float32); mc = np.zeros((out_rows, out_cols), np.float32)
@@ -145,18 +170,44 @@ class Transducer:
     def element(self, i):
         return self.pos[i], self.dir[i]
 
+    def planes(self, n_planes, pitch_um):
+        """the element tables of n_planes parallel elevation planes pitch_um apart, centred on the probe's own plane
+        (mcrt_elevation_planes along mcrt_transducer_elevation_axis): (pos [K][E][3], dir [K][E][3], z_mm [K])"""
+        return host_elevation_planes(self.pos, self.dir, host_elevation_axis(self.angles), n_planes, pitch_um)
+
 
 class Psf:
     """psf<axial,lateral,elevation,resolution_um>{freq, var_x, var_y, var_z} -- psf.h:34-58.
     focus_mm: focal depths [mm] (up to 8, ascending) for a lateral kernel per RF row (focal zones, include/mcrt.h); None or empty: the
-    reference's one constant kernel.  focal_range_mm = 20 is a display choice that no measurement backs."""
+    reference's one constant kernel.  focal_range_mm = 20 is a display choice that no measurement backs.
+    Slice thickness (psf.h:16-18,42,77; include/mcrt.h): elevation_size planes elevation_pitch_um apart (None: resolution_um) weighted with
+    var_z.  elevation_kernel is the constant kernel exp(-z_k^2 / (2 var_z)) as the reference leaves its lateral taps (centre 1);
+    elevation_rows() the table mcrt_elevation_frames takes: a row per RF row, widening away from elevation_focus_mm (None: the same row
+    everywhere), each divided by its sum unless elevation_normalize is False."""
 
-    def __init__(self, freq=4.5, var_x=0.05, var_y=0.2, var_z=0.1, axial_size=7, lateral_size=13, resolution_um=145, focus_mm=None, focal_range_mm=20.0):
+    def __init__(self, freq=4.5, var_x=0.05, var_y=0.2, var_z=0.1, axial_size=7, lateral_size=13, resolution_um=145, focus_mm=None, focal_range_mm=20.0,
+                 elevation_size=7, elevation_pitch_um=None, elevation_focus_mm=None, elevation_normalize=True):
         self.axial_kernel, self.lateral_kernel = host_psf(freq, var_x, var_y, resolution_um, axial_size, lateral_size)
         self.var_y, self.resolution_um = var_y, resolution_um
         self.focus_mm = tuple(float(x) for x in focus_mm) if focus_mm is not None else ()
         self.focal_range_mm = focal_range_mm
         self._rows = {}
+        self.var_z, self.elevation_size = var_z, elevation_size
+        self.elevation_pitch_um = resolution_um if elevation_pitch_um is None else elevation_pitch_um
+        self.elevation_focus_mm = tuple(float(x) for x in elevation_focus_mm) if elevation_focus_mm is not None else ()
+        self.elevation_normalize = bool(elevation_normalize)
+        # (a var_z the model refuses leaves the kernel zero, as the reference leaves it: only elevation_rows() then fails)
+        self.elevation_kernel = (host_psf_elevation(var_z, self.elevation_pitch_um, 1, 1.0, (), focal_range_mm, elevation_size, False)[0]
+                                 if var_z > 0 and math.isfinite(var_z) else np.zeros(elevation_size, np.float32))
+        self._elev_rows = {}
+
+    def elevation_rows(self, n_rows, row_mm):
+        """the elevation weights of every RF row, float32 [n_rows][elevation_size], for rows row_mm apart (Simulator.row_mm)"""
+        key = (n_rows, row_mm)
+        if key not in self._elev_rows:
+            self._elev_rows[key] = host_psf_elevation(self.var_z, self.elevation_pitch_um, n_rows, row_mm, self.elevation_focus_mm, self.focal_range_mm,
+                                                      self.elevation_size, self.elevation_normalize)
+        return self._elev_rows[key]
 
     @property
     def has_focus(self):
@@ -338,8 +389,15 @@ class Context:
             raise ValueError("lat_rows needs one row of taps per RF row: (%d, n_lat), got shape %s" % (n_rows, lat.shape))
         check(self.L.mcrt_convolve_frames_depth(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, ptr(ax), ax.size, ptr(lat), lat.shape[1]))
 
+    def elevation_frames(self, planes_dev, n_frames, n_planes, n_elements, n_rows, w_rows, rf_dev):
+        """mcrt_elevation_frames: the plane stacks [n_frames][K][E][R] folded into rf_dev [n_frames][E][R] with w_rows [n_rows][K]"""
+        w = np.ascontiguousarray(w_rows, np.float32)
+        if w.shape != (n_rows, n_planes):
+            raise ValueError("w_rows needs one row of weights per RF row: (%d, %d), got shape %s" % (n_rows, n_planes, w.shape))
+        check(self.L.mcrt_elevation_frames(self.h, ptr(planes_dev), n_frames, n_planes, n_elements, n_rows, ptr(w), ptr(rf_dev)))
+
     def convolve(self, rf_dev, n_elements, n_rows, axial, lateral):
-        ax = np.ascontiguousarray(axial, np.float32); lat = np.ascontiguousarray(lateral, np.float32)
+        ax =np.ascontiguousarray(axial, np.float32); lat = np.ascontiguousarray(lateral, np.float32)
         check(self.L.mcrt_convolve(self.h, ptr(rf_dev), n_elements, n_rows, ptr(ax), ax.size, ptr(lat), lat.size))
 
     def envelope(self, rf_dev, n_elements, n_rows):
@@ -519,7 +577,10 @@ class Simulator:
     """
 
     def __init__(self, scene_data, transducer, n_samples=5, n_rows=None, device=0, seed=0x5EED, psf=None, texture=None,
-                 max_depth=10, sanitize_tir=0, tex_n=256, bvh_builder="sah"):
+                 max_depth=10, sanitize_tir=0, tex_n=256, bvh_builder="sah", elevation=False):
+        """elevation=True: slice thickness.  trace() then traces the psf's elevation_size planes of the frame as one pose pass -- plane k of
+        frame f with frame id f * K + k, the frame-id rule of include/mcrt.h -- and folds them into rf_dev with psf.elevation_rows();
+        everything after (convolve, bmode, frame) is unchanged."""
         self.ctx = Context(device)
         self.ctx.set_bvh_builder(bvh_builder)
         self.tr = transducer
@@ -532,14 +593,25 @@ class Simulator:
         self.ctx.set_transducer(transducer.pos, transducer.dir)
         self.psf = psf or Psf(freq=transducer.frequency)
         self.rf_dev = self.ctx.alloc(E * self.R * 4)
+        self.elevation, self.planes_dev = bool(elevation), None
+        if self.elevation:
+            self.K = self.psf.elevation_size
+            self.plane_pos, self.plane_dir, self.plane_z_mm = transducer.planes(self.K, self.psf.elevation_pitch_um)
+            self.planes_dev = self.ctx.alloc(self.K * E * self.R * 4)
 
     def close(self):
         if self.ctx.h:
             self.ctx.free(self.rf_dev)
+            if self.planes_dev:
+                self.ctx.free(self.planes_dev)
             self.ctx.close()
 
     def trace(self, frame_id=0):
-        self.ctx.trace_frame(frame_id, self.rf_dev)
+        if not self.elevation:
+            self.ctx.trace_frame(frame_id, self.rf_dev)
+            return
+        self.ctx.trace_frames_poses(frame_id * self.K, self.plane_pos, self.plane_dir, self.planes_dev)
+        self.ctx.elevation_frames(self.planes_dev, 1, self.K, self.E, self.R, self.psf.elevation_rows(self.R, self.row_mm), self.rf_dev)
 
     @property
     def row_mm(self):

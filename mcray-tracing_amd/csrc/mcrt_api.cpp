@@ -179,6 +179,9 @@ struct mcrt_ctx {
     // focal zones (mcrt_convolve_frames_depth): the device table [n_lat][R] (room for MCRT_MAX_ROWS x 32), its pinned staging, and the
     // table now on the device with its shape (its upload is waited for only when the next table differs)
     Buf<float> d_lat_rows; PinnedBuf<float> h_lat_rows; std::vector<float> lat_on_dev; uint32_t lat_key[2] = { 0, 0 }; Event ev_lat; bool lat_copy_pending = false;
+    // slice thickness (mcrt_elevation_frames): the elevation table [K][R] (room for 32 x MCRT_MAX_ROWS) under the same scheme, in buffers of
+    // its own -- a frame uses this table and the focal zones' in turn, and one shared buffer would upload both on every frame
+    Buf<float> d_elev_rows; PinnedBuf<float> h_elev_rows; std::vector<float> elev_on_dev; uint32_t elev_key[2] = { 0, 0 }; Event ev_elev; bool elev_copy_pending = false;
     // instrumentation
     Buf<unsigned long long> d_stats; bool stats_on = false;
     bool timing_on = false; int timing_level = 0;       // 1: the walk's launches are bracketed by HIP events; 2: k_shade's and k_march's too
@@ -1097,6 +1100,47 @@ extern "C" int mcrt_convolve_frames_depth(mcrt_ctx *c, float *rf_dev, uint32_t n
     mcrt::ConvTaps t; memset(&t, 0, sizeof t);
     memcpy(t.ax, ax, 4 * n_ax); t.n_ax = n_ax; t.n_lat = n_lat;
     HIP_TRY(mcrt::launch_convolve_depth(rf_dev, c->d_tmp, n_frames, E, R, t, c->d_lat_rows, c->stream));
+    return MCRT_OK;
+}
+
+// The contract is in include/mcrt.h.  Everything is checked before anything is launched; the weight table follows the scheme of
+// mcrt_convolve_frames_depth (compared bit for bit with the one on the device, transposed tap-major [K][R] into pinned staging and
+// uploaded only when it differs).
+extern "C" int mcrt_elevation_frames(mcrt_ctx *c, const float *planes_dev, uint32_t n_frames, uint32_t K, uint32_t E, uint32_t R,
+                                     const float *w_rows, float *rf_dev)
+{
+    CTX_TRY(c);
+    if (!planes_dev || !rf_dev || !w_rows || n_frames == 0 || K == 0 || E == 0 || R == 0) return set_error(MCRT_ERR_INVALID, "mcrt_elevation_frames: bad arguments");
+    if (K > 32) return set_error(MCRT_ERR_LIMIT, "mcrt_elevation_frames: at most 32 planes (%u)", K);
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "mcrt_elevation_frames: at most %d rows", MCRT_MAX_ROWS);
+    if ((double)n_frames * (double)K * (double)E * (double)R >= 0x1p40) return set_error(MCRT_ERR_LIMIT, "mcrt_elevation_frames: the plane stack is too large");
+    {
+        const uintptr_t a0 = (uintptr_t)planes_dev, a1 = a0 + 4 * (size_t)n_frames * K * E * R, b0 = (uintptr_t)rf_dev, b1 = b0 + 4 * (size_t)n_frames * E * R;
+        if (a0 < b1 && b0 < a1) return set_error(MCRT_ERR_INVALID, "mcrt_elevation_frames: planes_dev and rf_dev overlap");
+    }
+    constexpr size_t TABLE = (size_t)MCRT_MAX_ROWS * 32;
+    if (!c->d_elev_rows) {                              // once per context, all three or none
+        Buf<float> d; PinnedBuf<float> h; Event ev;
+        HIP_TRY(d.alloc(TABLE));
+        HIP_TRY(h.alloc(TABLE));
+        HIP_TRY(hipEventCreateWithFlags(&ev.h, hipEventDisableTiming));
+        c->d_elev_rows = std::move(d); c->h_elev_rows = std::move(h); c->ev_elev = std::move(ev);
+        c->elev_on_dev.assign(TABLE, 0.0f); c->elev_key[0] = c->elev_key[1] = 0;
+    }
+    const size_t n = (size_t)K * R;
+    if (c->elev_key[0] != R || c->elev_key[1] != K || memcmp(w_rows, c->elev_on_dev.data(), 4 * n)) {   // (elev_on_dev: the caller's layout)
+        if (c->elev_copy_pending) HIP_TRY(hipEventSynchronize(c->ev_elev));   // the staging buffer still feeds the previous table's copy
+        float *h = c->h_elev_rows;
+        for (uint32_t r = 0; r < R; r++)
+            for (uint32_t k = 0; k < K; k++) h[(size_t)k * R + r] = w_rows[(size_t)r * K + k];
+        c->elev_key[0] = c->elev_key[1] = 0;            // (no table until its copy is enqueued)
+        HIP_TRY(hipMemcpyAsync(c->d_elev_rows, h, 4 * n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipEventRecord(c->ev_elev, c->stream));
+        c->elev_copy_pending = true;
+        memcpy(c->elev_on_dev.data(), w_rows, 4 * n);
+        c->elev_key[0] = R; c->elev_key[1] = K;
+    }
+    HIP_TRY(mcrt::launch_elevation(planes_dev, rf_dev, n_frames, K, E, R, c->d_elev_rows, c->stream));
     return MCRT_OK;
 }
 

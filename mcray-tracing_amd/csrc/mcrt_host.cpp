@@ -418,6 +418,90 @@ extern "C" int mcrt_transducer_elements(uint32_t n, double radius_cm, double sep
     return MCRT_OK;
 }
 
+// ---- slice thickness (psf.h:16-18,42,77; the contracts are in include/mcrt.h) -------------------
+// the probe's elevation direction: (0,0,1) through the rotations mcrt_transducer_elements applies to an element's direction
+extern "C" int mcrt_transducer_elevation_axis(const float angles_deg[3], float axis[3])
+{
+    if (!angles_deg || !axis) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_transducer_elevation_axis: null %s", angles_deg ? "axis" : "angles");
+    const double pi = 3.14159265358979323846264338327950288419716939937510;   // units.h:360
+    const double xa = (angles_deg[0] * pi * 1.0) / 180.0, ya = (angles_deg[1] * pi * 1.0) / 180.0, za = (angles_deg[2] * pi * 1.0) / 180.0;
+    F3 d{ 0.f, 0.f, 1.f };
+    d = rot(d, F3{ 0, 0, 1 }, (float)za);
+    d = rot(d, F3{ 1, 0, 0 }, (float)xa);
+    d = rot(d, F3{ 0, 1, 0 }, (float)ya);
+    axis[0] = d.x; axis[1] = d.y; axis[2] = d.z;
+    return MCRT_OK;
+}
+
+namespace {
+inline float plane_z_mm(uint32_t k, uint32_t K, uint32_t pitch_um)   // centred: plane (K-1)/2 lies in the probe's own plane
+{
+    return (float)(((double)k - (double)((K - 1u) / 2u)) * (double)pitch_um / 1000.0);
+}
+}  // namespace
+
+extern "C" int mcrt_elevation_planes(const float *pos, const float *dir, uint32_t n, const float axis[3], uint32_t K, uint32_t pitch_um,
+                                     float *pos_out, float *dir_out, float *z_mm_out)
+{
+    if (!pos || !dir || !axis || !pos_out || !dir_out) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_elevation_planes: null pointer");
+    if (n == 0) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_elevation_planes: no elements");
+    if (K == 0 || K > 32) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_elevation_planes: n_planes must be 1..32 (%u)", K);
+    if (pitch_um == 0) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_elevation_planes: pitch_um must be > 0");
+    if (!(std::isfinite(axis[0]) && std::isfinite(axis[1]) && std::isfinite(axis[2]))) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_elevation_planes: the axis must be finite");
+    const float ax[3] = { axis[0], axis[1], axis[2] };                    // (axis may alias an output)
+    for (uint32_t k = 0; k < K; k++) {
+        const float z = plane_z_mm(k, K, pitch_um);
+        const float o = (float)((double)z / 10.0);                        // mm -> scene units (cm)
+        if (z_mm_out) z_mm_out[k] = z;
+        for (uint32_t e = 0; e < n; e++)
+            for (int c = 0; c < 3; c++) {
+                const size_t i = 3 * (size_t)e + (size_t)c, j = 3 * ((size_t)k * n + e) + (size_t)c;
+                const float shift = o * ax[c];
+                pos_out[j] = pos[i] + shift;
+                dir_out[j] = dir[i];
+            }
+    }
+    return MCRT_OK;
+}
+
+// mcrt_psf_focus_kernels' depth model with var_z, evaluated at the plane positions of mcrt_elevation_planes
+extern "C" int mcrt_psf_elevation_kernels(float var_z, uint32_t pitch_um, const mcrt_focus *f, uint32_t n_rows, double row_mm, int normalize,
+                                          float *w_rows, uint32_t K)
+{
+    if (!w_rows) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_elevation_kernels: null w_rows");
+    if (K == 0 || K > 32) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_elevation_kernels: n_planes must be 1..32 (%u)", K);
+    if (pitch_um == 0) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_elevation_kernels: pitch_um must be > 0");
+    if (!(std::isfinite(var_z) && var_z > 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_elevation_kernels: var_z must be finite and > 0");
+    if (!(std::isfinite(row_mm) && row_mm > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_elevation_kernels: row_mm must be finite and > 0");
+    const uint32_t n_focus = f ? f->n_focus : 0u;
+    if (n_focus > 8) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_elevation_kernels: at most 8 foci (%u)", n_focus);
+    for (uint32_t j = 0; j < n_focus; j++) {
+        if (!(std::isfinite(f->focus_mm[j]) && f->focus_mm[j] >= 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_elevation_kernels: focus_mm[%u] must be finite and >= 0", j);
+        if (j > 0 && !(f->focus_mm[j] > f->focus_mm[j - 1])) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_elevation_kernels: foci must be strictly ascending");
+    }
+    if (n_focus > 0 && !(std::isfinite(f->focal_range_mm) && f->focal_range_mm > 0.0f))
+        return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_elevation_kernels: focal_range_mm must be finite and > 0");
+    if (n_rows > MCRT_MAX_ROWS) return mcrt::set_error(MCRT_ERR_LIMIT, "mcrt_psf_elevation_kernels: at most %d rows", MCRT_MAX_ROWS);
+    double z2[32];
+    for (uint32_t k = 0; k < K; k++) { const float z = plane_z_mm(k, K, pitch_um); z2[k] = (double)z * (double)z; }
+    for (uint32_t r = 0; r < n_rows; r++) {
+        const double z = (double)r * row_mm;
+        double var = (double)var_z, g = 1.0;
+        if (n_focus > 0) {
+            uint32_t best = 0;
+            for (uint32_t j = 1; j < n_focus; j++)             // strictly nearer only: a tie keeps the shallower focus
+                if (std::fabs(z - (double)f->focus_mm[j]) < std::fabs(z - (double)f->focus_mm[best])) best = j;
+            const double q = (z - (double)f->focus_mm[best]) / (double)f->focal_range_mm;
+            var = (double)var_z * (1.0 + q * q);
+            g = std::sqrt((double)var_z / var);
+        }
+        double v[32], sum = 0.0;
+        for (uint32_t k = 0; k < K; k++) { v[k] = g * std::exp(-0.5 * (z2[k] / var)); sum += v[k]; }
+        for (uint32_t k = 0; k < K; k++) w_rows[(size_t)r * K + k] = normalize ? (float)(v[k] / sum) : (float)v[k];
+    }
+    return MCRT_OK;
+}
+
 // rfimage.h:183-215 create_mapping, evaluated once per geometry on the host (as the reference does in its constructor).
 // Operand types as C++ gives them to the reference's statements (pinned by tests/golden/ref_probe.json "scan_maps_*": the same
 // statements evaluated with the reference's own unit types, compiled from its units.h):

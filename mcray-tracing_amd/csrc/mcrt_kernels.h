@@ -6,7 +6,7 @@
 //   mcrt_shade.hip   k_init (the first ray of every path), k_shade (interface physics of a bounce, survivors compacted into the next queue)
 //   mcrt_path.hip    k_path (the latency form: every bounce of every path in one launch)
 //   mcrt_march.hip   k_march (RF accumulation of the segments), k_material_table
-//   mcrt_post.hip    k_finalize, k_clear_flags, k_conv_* (k_conv_lateral_rows: focal zones), k_envelope, k_remap, k_transpose, k_blocks_to_frames
+//   mcrt_post.hip    k_finalize, k_clear_flags, k_conv_* (k_conv_lateral_rows: focal zones), k_elevation (slice thickness), k_envelope, k_remap, k_transpose, k_blocks_to_frames
 //   mcrt_display.hip k_bmode_peak, k_bmode_grey, k_bmode (mcrt_bmode_frames: log-compressed 8-bit B-mode frames)
 //   mcrt_scene.hip   k_tris_by_id, k_expand_tris; the probes k_math_probe, k_verify_div, k_philox_probe
 //   mcrt_lbvh.hip    the device BVH builder (mcrt_lbvh.h)
@@ -86,6 +86,8 @@ hipError_t launch_finalize(long long *acc, uint32_t *flags, float *rf, uint32_t 
 hipError_t launch_convolve(float *img, float *tmp, uint32_t n_img, uint32_t E, uint32_t R, const ConvTaps &taps, hipStream_t st);
 // k_conv_axial, then k_conv_lateral_rows with the device table lat [taps.n_lat][R] (tap-major); taps.lat is not read
 hipError_t launch_convolve_depth(float *img, float *tmp, uint32_t n_img, uint32_t E, uint32_t R, const ConvTaps &taps, const float *lat, hipStream_t st);
+// k_elevation: planes [F][K][E][R] folded into rf [F][E][R] with the device table w [K][R] (tap-major); float4 lanes where E*R and the pointers allow
+hipError_t launch_elevation(const float *planes, float *rf, uint32_t F, uint32_t K, uint32_t E, uint32_t R, const float *w, hipStream_t st);
 hipError_t launch_envelope(float *img, uint32_t E, uint32_t R, hipStream_t st);
 hipError_t launch_remap(const float *img, uint32_t n_img, uint32_t E, uint32_t R, const float *map_col, const float *map_row, float *out, uint32_t n, hipStream_t st);
 hipError_t launch_bmode_peak(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, float *peak, hipStream_t st);   // peak[F] zeroed before

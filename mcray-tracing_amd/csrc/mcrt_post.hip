@@ -1,6 +1,6 @@
 // mcrt_post.hip -- after the accumulation: k_finalize (fixed-point RF bins -> float image, rf_image::clear rfimage.h:161), k_conv_*
 // (rf_image::convolve, rfimage.h:93-123; k_conv_lateral_rows its lateral pass with a tap row per RF row: focal zones), k_envelope (rfimage.h:54-91), k_remap (the scan conversion of rf_image::postprocess,
-// rfimage.h:125-140), k_transpose, and k_blocks_to_frames (the ranks' blocks of an mcrt_group laid out as frames).
+// rfimage.h:125-140), k_elevation (the elevation planes of a frame folded into one image: slice thickness), k_transpose, and k_blocks_to_frames (the ranks' blocks of an mcrt_group laid out as frames).
 #include "mcrt_device.h"
 
 namespace mcrt {
@@ -93,6 +93,46 @@ __global__ void k_conv_lateral_rows(const float *tmp, float *img, uint32_t n_img
 #pragma unroll
     for (int j = 0; j < C; j++)
         if (col0 + (uint32_t)j < col_end) o[(size_t)(col0 + j) * R] = conv[j];
+}
+
+// mcrt_elevation_frames (psf.h:16-18,42,77; the contract is in mcrt.h): the K elevation planes of every frame folded into one RF image,
+//     rf[f][e][r] = sum_k planes[f][k][e][r] * w[k][r],   w tap-major [K][R] (the host transposes the caller's [R][K]),
+// summed in k order from 0.0f, one rounding per multiply and per add.  A pure stream: F*K*E*R floats read once, F*E*R written.  A lane
+// owns one V (a float4 = 4 consecutive floats of the flattened [E*R] image, or one float) and loads its planes in batches of
+// MCRT_ELEV_BATCH before the first multiply of the batch, so that up to 8 loads of 16 bytes are in flight per lane (K = 7: all of them).
+// A batch's loads are unconditional -- past the last plane they repeat it, which stays inside the stack -- and only the sums are guarded:
+// a plane that does not exist must not reach the sum (0 * NaN).  nv = E*R / (floats per V); rows wrap inside a float4 when R % 4 != 0.
+#define MCRT_ELEV_BATCH 8
+__device__ __forceinline__ void elev_fold(float4 &a, const float4 &v, const float *wk, const uint32_t *r)
+{
+    a.x += v.x * wk[r[0]]; a.y += v.y * wk[r[1]]; a.z += v.z * wk[r[2]]; a.w += v.w * wk[r[3]];
+}
+__device__ __forceinline__ void elev_fold(float &a, const float &v, const float *wk, const uint32_t *r) { a += v * wk[r[0]]; }
+__device__ __forceinline__ void elev_zero(float4 &a) { a = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+__device__ __forceinline__ void elev_zero(float &a) { a = 0.0f; }
+template <typename V>
+__global__ void k_elevation(const V *planes, V *rf, uint32_t F, uint32_t K, size_t nv, uint32_t R, const float *w)
+{
+    constexpr uint32_t W = sizeof(V) / 4u;
+    constexpr uint32_t B = MCRT_ELEV_BATCH;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;            // element of `rf`
+    if (i >= (size_t)F * nv) return;
+    const size_t f = i / nv, j = i % nv;
+    const V *p = planes + f * K * nv + j;                                      // plane k of this lane at p[k * nv]
+    uint32_t r[W];
+    r[0] = (uint32_t)((j * W) % R);
+#pragma unroll
+    for (uint32_t c = 1; c < W; c++) r[c] = r[c - 1u] + 1u == R ? 0u : r[c - 1u] + 1u;
+    V acc; elev_zero(acc);
+    for (uint32_t k0 = 0; k0 < K; k0 += B) {
+        V v[B];
+#pragma unroll
+        for (uint32_t b = 0; b < B; b++) v[b] = p[(size_t)min(k0 + b, K - 1u) * nv];
+#pragma unroll
+        for (uint32_t b = 0; b < B; b++)
+            if (k0 + b < K) elev_fold(acc, v[b], w + (size_t)(k0 + b) * R, r);
+    }
+    rf[i] = acc;
 }
 
 // rfimage.h:54-91, one WAVEFRONT per scan-line.  The reference walks a column once: whenever the signal stops ascending at row i
@@ -210,6 +250,17 @@ hipError_t launch_convolve_depth(float *img, float *tmp, uint32_t n_img, uint32_
         const size_t m = (size_t)n_img * n_strips * (R - 2u * na);
         hipLaunchKernelGGL(k_conv_lateral_rows, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const float *)tmp, img, n_img, E, R, na, nl, n_strips, lat);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_elevation(const float *planes, float *rf, uint32_t F, uint32_t K, uint32_t E, uint32_t R, const float *w, hipStream_t st)
+{
+    const size_t ER = (size_t)E * R;
+    const bool vec = (ER % 4u) == 0u && ((uintptr_t)planes % 16u) == 0u && ((uintptr_t)rf % 16u) == 0u;   // every plane then starts 16-byte aligned
+    const size_t nv = vec ? ER / 4u : ER, n = (size_t)F * nv;
+    const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
+    if (vec) hipLaunchKernelGGL((k_elevation<float4>), grid, blk, 0, st, (const float4 *)planes, (float4 *)rf, F, K, nv, R, w);
+    else hipLaunchKernelGGL((k_elevation<float>), grid, blk, 0, st, planes, rf, F, K, nv, R, w);
     return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 // mattausch_hip -- the reference's program (main.cpp:42-161) on the MI355X library:
 //     mattausch_hip <scene.json> [frames] [samples] [out.pgm] [rf.bin] [--gpus N | --devices 0,1,...]
 //                   [--db DR] [--gain G] [--ref-log] [--persistence A] [--focus-mm F1[,F2,...]] [--focal-range-mm R]
+//                   [--elevation K] [--elevation-pitch-um P] [--var-z V]
 // --gpus N: the first N GPUs of the node, the frame's scan-lines sharded over them (mcrt_group_*: one tracing context and host thread per
 // GPU, the blocks gathered on GPU 0); --devices lists them explicitly, and may repeat one (two ranks sharing a GPU: the one-GPU test).
 // Same constants (main.cpp:23-37), same frame loop body; instead of blocking on imshow/waitKey every frame it
@@ -12,6 +13,10 @@
 // --focus-mm 40 (or 30,60,90: up to 8, ascending) places focal zones: every RF row gets its own lateral PSF, narrowest at the nearest
 // focus and widening with the distance to it over --focal-range-mm R (20 mm, a display choice; mcrt_psf_focus_kernels).  Without
 // --focus-mm the reference's one lateral kernel is used and --focal-range-mm has no effect.
+// --elevation K (odd, 1..31) gives the picture its slice thickness (psf.h:16-18,42,77): every frame is traced in K parallel planes
+// --elevation-pitch-um P apart (145) around the probe's own, as one pass, and folded with the elevation PSF of variance --var-z V (0.1 mm^2,
+// main.cpp:54; mcrt_elevation_frames) before the convolution.  Without --elevation the frame is the reference's thin sheet and the other
+// two options have no effect; --elevation 1 is that sheet again.
 #include "mcrt_host.hpp"
 #include <chrono>
 #include <cstring>
@@ -35,6 +40,8 @@ int main(int argc, char **argv)
     display.reset_state = 0;                          // the persistence state runs on from frame to frame
     bool bmode = false;
     std::vector<float> focus_mm; float focal_range_mm = 20.0f;
+    int elevation = 0; long elevation_pitch_um = 145; float var_z = 0.1f;      // elevation 0: off
+    bool elevation_given = false;
     {   // the options, taken out of the positional arguments
         int keep = 1;
         for (int i = 1; i < argc; i++) {
@@ -48,6 +55,9 @@ int main(int argc, char **argv)
                 i++;
             }
             else if (!std::strcmp(argv[i], "--focal-range-mm") && i + 1 < argc) focal_range_mm = (float)std::atof(argv[++i]);
+            else if (!std::strcmp(argv[i], "--elevation") && i + 1 < argc) { elevation = std::atoi(argv[++i]); elevation_given = true; }
+            else if (!std::strcmp(argv[i], "--elevation-pitch-um") && i + 1 < argc) elevation_pitch_um = std::atol(argv[++i]);
+            else if (!std::strcmp(argv[i], "--var-z") && i + 1 < argc) var_z = (float)std::atof(argv[++i]);
             else if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) { devices.clear(); for (int d = 0; d < std::max(1, std::atoi(argv[i + 1])); d++) devices.push_back(d); i++; }
             else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {
                 devices.clear();
@@ -63,10 +73,15 @@ int main(int argc, char **argv)
     const int frames = argc > 2 ? std::atoi(argv[2]) : 10;
     const unsigned samples = argc > 3 ? (unsigned)std::atoi(argv[3]) : 5;   // samples_te (main.cpp:27)
     try {
+        if (elevation_given && (elevation < 1 || elevation > 31 || elevation % 2 == 0))
+            throw std::invalid_argument("--elevation takes an odd number of planes, 1..31");
+        if (elevation_given && (elevation_pitch_um < 1 || elevation_pitch_um > 0xffffffffl))
+            throw std::invalid_argument("--elevation-pitch-um must be a positive number of micrometres");
         const json cfg = load_json(argv[1]);
         const psf_ psf = [&] {
-            psf_ p{ transducer_frequency, 0.05f, 0.2f, 0.1f };
+            psf_ p{ transducer_frequency, 0.05f, 0.2f, var_z };
             if (!focus_mm.empty()) p.set_focus(focus_mm.data(), (uint32_t)focus_mm.size(), focal_range_mm);
+            if (elevation_given) p.set_elevation((uint32_t)elevation_pitch_um);
             return p;
         }();
         const auto &t_pos = cfg.at("transducerPosition");
@@ -82,7 +97,8 @@ int main(int argc, char **argv)
 
         const auto t0 = std::chrono::high_resolution_clock::now();
         for (int f = 0; f < frames; f++) {
-            rf_image.trace((uint32_t)f);      // clear + cast_rays + accumulation (main.cpp:102-144)
+            if (elevation_given) rf_image.trace((uint32_t)f, transducer, psf, (uint32_t)elevation);   // ... in K elevation planes, folded
+            else rf_image.trace((uint32_t)f);      // clear + cast_rays + accumulation (main.cpp:102-144)
             rf_image.convolve(psf);           // main.cpp:146
             rf_image.envelope();              // main.cpp:147
             if (bmode) rf_image.postprocess(display);   // main.cpp:148, log-compressed to 8-bit grey

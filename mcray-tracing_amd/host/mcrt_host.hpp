@@ -274,6 +274,19 @@ public:
             std::cout << v.x() << "," << v.z() << std::endl;
         }
     }
+    // slice thickness: the element tables of n_planes parallel elevation planes pitch_um apart, centred on the probe's own plane
+    // (mcrt_elevation_planes along mcrt_transducer_elevation_axis): pos / dir [K][N][3], z_mm [K]
+    struct plane_tables { std::vector<float> pos, dir, z_mm; };
+    plane_tables planes(uint32_t n_planes, uint32_t pitch_um) const
+    {
+        float axis[3];
+        check(mcrt_transducer_elevation_axis(angles.data(), axis), "transducer elevation axis");
+        plane_tables t;
+        const size_t K = n_planes >= 1 && n_planes <= 32 ? n_planes : 1;      // (the library refuses other counts before it writes)
+        t.pos.resize(K * 3 * transducer_elements); t.dir.resize(K * 3 * transducer_elements); t.z_mm.resize(K);
+        check(mcrt_elevation_planes(pos.data(), dir.data(), (uint32_t)transducer_elements, axis, n_planes, pitch_um, t.pos.data(), t.dir.data(), t.z_mm.data()), "transducer planes");
+        return t;
+    }
     void setPosition(const vec3 &p) { position = p; }
     void setAngles(const std::array<float, 3> &a) { angles = a; }
     vec3 getPosition() const { return position; }
@@ -292,9 +305,38 @@ template <size_t axial_size, size_t lateral_size, size_t elevation_size, unsigne
 class psf {
     static_assert(axial_size % 2 && lateral_size % 2 && elevation_size % 2, "kernel sizes must be odd");
 public:
-    psf(float freq, float var_x, float var_y, float /*var_z*/) : var_y(var_y)
+    psf(float freq, float var_x, float var_y, float var_z) : var_y(var_y), var_z(var_z)
     {
         check(mcrt_psf_kernels(freq, var_x, var_y, resolution_micrometers, axial_kernel.data(), axial_size, lateral_kernel.data(), lateral_size), "psf");
+        // psf.h:42,77: the constant elevation kernel exp(-z_k^2 / (2 var_z)) at the plane positions of mcrt_elevation_planes, unnormalised as the
+        // lateral taps are (a var_z the model refuses leaves it zero, as the reference leaves it: only elevation_rows() then fails)
+        if (var_z > 0.0f && std::isfinite(var_z) && elevation_size <= 32)
+            check(mcrt_psf_elevation_kernels(var_z, resolution_micrometers, nullptr, 1, 1.0, 0, elevation_kernel.data(), (uint32_t)elevation_size), "psf elevation");
+    }
+    // slice thickness (psf.h:16-18,42,77; the model in mcrt.h): the pitch of the elevation planes [um] (default: resolution_micrometers), whether
+    // every row of weights is divided by its sum, and an optional elevation focus (a lens has one) away from which the slice thickens.
+    // elevation_kernel is refilled for the new pitch.
+    void set_elevation(uint32_t pitch_um, bool normalize = true, const float *focus_mm = nullptr, uint32_t n = 0, float focal_range_mm = 20.0f)
+    {
+        elev_pitch_um = pitch_um; elev_normalize = normalize;
+        elev_focus = mcrt_focus{};
+        elev_focus.n_focus = focus_mm ? n : 0u;
+        for (uint32_t i = 0; i < elev_focus.n_focus && i < 8; i++) elev_focus.focus_mm[i] = focus_mm[i];
+        elev_focus.focal_range_mm = focal_range_mm;
+        elev_table.clear(); elev_rows = 0;
+        check(mcrt_psf_elevation_kernels(var_z, pitch_um, nullptr, 1, 1.0, 0, elevation_kernel.data(), (uint32_t)elevation_size), "psf elevation");
+    }
+    uint32_t elevation_pitch_um() const { return elev_pitch_um; }
+    // the elevation weights of every RF row [n_rows][n_planes] for rows row_mm apart (n_planes = 0: elevation_size); made once per shape
+    const std::vector<float> &elevation_rows(uint32_t n_rows, double row_mm, uint32_t n_planes = 0) const
+    {
+        const uint32_t K = n_planes ? n_planes : (uint32_t)elevation_size;
+        if (elev_table.empty() || elev_rows != n_rows || elev_row_mm != row_mm || elev_planes != K) {
+            std::vector<float> t((size_t)n_rows * K);
+            check(mcrt_psf_elevation_kernels(var_z, elev_pitch_um, &elev_focus, n_rows, row_mm, elev_normalize ? 1 : 0, t.data(), K), "psf elevation");
+            elev_table = std::move(t); elev_rows = n_rows; elev_row_mm = row_mm; elev_planes = K;
+        }
+        return elev_table;
     }
     // focal zones (psf.h:17-24 plans them): up to 8 ascending focal depths [mm]; rf_image::convolve then gives every RF row its own lateral
     // taps (mcrt_psf_focus_kernels, the model in mcrt.h).  n = 0 goes back to the reference's one constant kernel.  focal_range_mm = 20 is
@@ -323,11 +365,13 @@ public:
     constexpr size_t get_elevation_size() const { return elevation_size; }
     std::array<float, axial_size> axial_kernel;
     std::array<float, lateral_size> lateral_kernel;
-    std::array<float, elevation_size> elevation_kernel{};   // declared and never filled in the reference (psf.h:77)
-    float var_y;
+    std::array<float, elevation_size> elevation_kernel{};   // declared and never filled in the reference (psf.h:77); here the constant elevation kernel
+    float var_y, var_z;
 private:
     mcrt_focus focus{};
     mutable std::vector<float> table; mutable uint32_t table_rows = 0; mutable double table_row_mm = 0.0;
+    mcrt_focus elev_focus{}; uint32_t elev_pitch_um = resolution_micrometers; bool elev_normalize = true;
+    mutable std::vector<float> elev_table; mutable uint32_t elev_rows = 0, elev_planes = 0; mutable double elev_row_mm = 0.0;
 };
 
 // ---------------------------------------------------------------- GPU context shared by scene and rf_image
@@ -356,6 +400,10 @@ struct device {
     int trace_frames(uint32_t frame, uint32_t n_frames, uint32_t columns, float *rf_dev)
     {
         return group ? mcrt_group_trace_frames(group, frame, n_frames, rf_dev) : mcrt_trace_frames(ctx, frame, n_frames, 0, columns, rf_dev);
+    }
+    int trace_frames_poses(uint32_t frame, uint32_t n_frames, uint32_t columns, const float *pos, const float *dir, float *rf_dev)   // host tables [n_frames][columns][3]
+    {
+        return group ? mcrt_group_trace_frames_poses(group, frame, n_frames, pos, dir, rf_dev) : mcrt_trace_frames_poses(ctx, frame, n_frames, 0, columns, pos, dir, rf_dev);
     }
     int synchronize() { return group ? mcrt_group_synchronize(group) : mcrt_synchronize(ctx); }
     mcrt_ctx *ctx = nullptr;
@@ -574,6 +622,7 @@ public:
         mcrt_free(dev->ctx, rf_dev); mcrt_free(dev->ctx, scan_dev);
         if (bmode_dev) mcrt_free(dev->ctx, bmode_dev);
         if (state_dev) mcrt_free(dev->ctx, state_dev);
+        if (planes_dev) mcrt_free(dev->ctx, planes_dev);
     }
     rf_image(const rf_image &) = delete; rf_image &operator=(const rf_image &) = delete;
 
@@ -603,6 +652,31 @@ public:
             check(dev->set_params(&p), "mcrt_set_params");
         }
         check(dev->trace_frames(frame_id, 1, columns, rf_dev), "mcrt_trace_frame");       // (every GPU of a group traces its scan-line shard)
+        where = on_device;
+    }
+    // the same with slice thickness (psf.h:16-18,42,77; mcrt.h): the frame's n_planes elevation planes (0: the psf's elevation_size), spread
+    // p.elevation_pitch_um() apart around the transducer's own plane, traced as ONE pose pass -- plane k with frame id frame_id * K + k, the
+    // frame-id rule of mcrt.h -- and folded into this image with p.elevation_rows() (mcrt_elevation_frames).  trace(frame_id) keeps its meaning.
+    template <size_t N, typename psf_> void trace(uint32_t frame_id, const transducer<N> &t, const psf_ &p, uint32_t n_planes = 0)
+    {
+        static_assert(N == columns, "one scan-line per transducer element");
+        const uint32_t K = n_planes ? n_planes : (uint32_t)p.get_elevation_size();
+        const auto tables = t.planes(K, p.elevation_pitch_um());
+        const std::vector<float> &w = p.elevation_rows(max_rows, (double)axial_resolution_um / 1000.0, K);
+        if ((uint64_t)frame_id * K + K > 0xffffffffull) throw std::out_of_range("rf_image::trace: frame_id * n_planes does not fit a frame id");
+        mcrt_params prm; check(mcrt_get_params(dev->ctx, &prm), "mcrt_get_params");
+        if (prm.n_rows != max_rows || prm.n_elements != columns) {
+            prm.n_rows = max_rows; prm.n_elements = columns; prm.speed_of_sound = speed_of_sound;
+            check(dev->set_params(&prm), "mcrt_set_params");
+        }
+        const size_t need = (size_t)K * columns * max_rows;
+        if (need > planes_n) {
+            if (planes_dev) { mcrt_free(dev->ctx, planes_dev); planes_dev = nullptr; planes_n = 0; }
+            check(mcrt_alloc(dev->ctx, sizeof(float) * need, (void **)&planes_dev), "mcrt_alloc");
+            planes_n = need;
+        }
+        check(dev->trace_frames_poses(frame_id * K, K, columns, tables.pos.data(), tables.dir.data(), planes_dev), "mcrt_trace_frames_poses");
+        check(mcrt_elevation_frames(dev->ctx, planes_dev, 1, K, columns, max_rows, w.data(), rf_dev), "mcrt_elevation_frames");
         where = on_device;
     }
     template <typename psf_> void convolve(const psf_ &p)
@@ -689,6 +763,7 @@ private:
     float *rf_dev = nullptr, *scan_dev = nullptr;
     unsigned char *bmode_dev = nullptr; float *state_dev = nullptr;   // postprocess(bmode_params): the 8-bit frame and the persistence state
     size_t bmode_n = 0; uint32_t bmode_rows = 0, bmode_cols = 0; bool state_valid = false;
+    float *planes_dev = nullptr; size_t planes_n = 0;                 // trace(frame, transducer, psf): the plane stack [K][columns][max_rows], grown to the largest K
 };
 
 }  // namespace mcrt_host
