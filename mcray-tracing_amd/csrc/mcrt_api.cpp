@@ -103,6 +103,9 @@ struct Knobs {
     uint32_t path_groups = MCRT_PATH_GROUPS_DEFAULT;   // ... as this many scan-line groups on their own streams: a group's accumulation runs beside the other groups' last walks
     uint32_t path_max = MCRT_PATH_MAX_DEFAULT;    // passes of at most this many paths run as ONE launch that carries every path through all of its bounces (k_path: the latency form)
     uint32_t packet_mask = MCRT_PACKET_MASK_DEFAULT, packet_from = MCRT_PACKET_FROM;   // bit b: bounce b is walked by k_trace_packet (one wavefront per packet of 64 queue neighbours), in passes of at least packet_from paths
+    bool retire_late = true;                   // MCRT_RETIRE_LATE=0: paths past the image are traced to their end, as before (FrameArgs::retire_late)
+    bool fold_b0 = false;                      // MCRT_FOLD_B0=1: bounce 0 of a silent start medium is accumulated by k_shade itself (FrameArgs::fold_b0).  Bit-identical, one launch and
+                                               // 48 B per path less, and no faster on the MI355X (profiles/retire_fold): off until a pass is found that it helps
     bool test_hooks = false;                   // MCRT_TEST_HOOKS: mcrt_debug_set_error may poison the context (tests only)
 };
 static Knobs read_knobs()
@@ -124,6 +127,8 @@ static Knobs read_knobs()
     k.no_overlap = tuning_env("MCRT_NO_OVERLAP") != nullptr; k.no_priority = tuning_env("MCRT_NO_PRIORITY") != nullptr;
     k.no_fast_div = tuning_env("MCRT_NO_FAST_DIV") != nullptr; k.no_lean = tuning_env("MCRT_NO_LEAN") != nullptr;
     k.test_hooks = tuning_env("MCRT_TEST_HOOKS") != nullptr;
+    if (const char *e = tuning_env("MCRT_RETIRE_LATE")) k.retire_late = atoi(e) != 0;
+    if (const char *e = tuning_env("MCRT_FOLD_B0")) k.fold_b0 = atoi(e) != 0;
     return k;
 }
 
@@ -148,6 +153,7 @@ struct mcrt_ctx {
     Buf<uint32_t> d_tri_slot;
     Buf<float4> d_tris_id;                                // the triangle records in id order (refresh_soa)
     uint32_t n_mesh = 0, n_mat = 0, start_mat = 0, n_cu = 256;
+    bool start_silent = false;                            // the start material has mu0 == sigma == 0: its segments' step echoes are +0 in a finite texture (k_march's `silent`)
     int builder = MCRT_BVH_HOST_SAH; bool host_bvh_stale = false;   // device-built tree: host copies are downloaded on demand
     std::vector<uint32_t> tri_mesh;   // per-triangle mesh index of the uploaded scene (for mcrt_update_triangles)
     float scene_lo[3] = { 0, 0, 0 }, scene_hi[3] = { 0, 0, 0 };
@@ -166,7 +172,7 @@ struct mcrt_ctx {
     uint32_t acc_clean_ne = 0, acc_clean_rows = 0;   // bins known to be all-zero for this shape (k_finalize leaves them so)
     Buf<float> d_tmp;
     // row thresholds (exact replacement of the per-echo double division) and the verified fast division by tex_res
-    Buf<double> d_row_thr; uint32_t thr_rows = 0; double thr_dt = 0.0;
+    Buf<double> d_row_thr; uint32_t thr_rows = 0; double thr_dt = 0.0, thr_end = 0.0;   // thr_end: the table's last entry, the first time past the image
     float verified_res = 0.0f; bool fast_div = false, fast_div_all = false;
     float last_lean_bound = 0.0f; uint32_t last_march_rows = 0;   // what the last frame's kernels were given (mcrt_debug_fast_paths)
     // per-material table of k_march (depends on the materials, the axial step and the frequency)
@@ -199,7 +205,7 @@ static int prepare_tables(mcrt_ctx *c)
         c->thr_rows = 0;
         HIP_TRY(c->d_row_thr.alloc(thr.size()));
         HIP_TRY(hipMemcpy(c->d_row_thr, thr.data(), thr.size() * 8, hipMemcpyHostToDevice));
-        c->thr_rows = c->p.n_rows; c->thr_dt = c->c.row_dt_us;
+        c->thr_rows = c->p.n_rows; c->thr_dt = c->c.row_dt_us; c->thr_end = thr.back();
     }
     if (c->verified_res != c->p.tex_res) {
         // the GPU checks, exhaustively, that its fma-corrected reciprocal multiply IS IEEE division by tex_res
@@ -580,6 +586,7 @@ static int upload_scene(mcrt_ctx *c, const float *tri, const uint32_t *tri_mesh,
     HIP_TRY(c->d_meshes.alloc(n_mesh));
     HIP_TRY(hipMemcpy(c->d_meshes, meshes, sizeof(mcrt_mesh) * (size_t)n_mesh, hipMemcpyHostToDevice));
     c->n_mesh = n_mesh; c->n_mat = n_mat; c->start_mat = start_mat;
+    c->start_silent = mats[8 * (size_t)start_mat + 2] == 0.0f && mats[8 * (size_t)start_mat + 4] == 0.0f;
     for (int i = 0; i < 3; i++) c->spacing[i] = spacing[i];
     c->have_scene = true; c->mtab_valid = false;
     return prepare_tables(c);
@@ -774,7 +781,7 @@ static int ensure_work(Work &w, size_t np, uint32_t B, size_t ovf, int out)
 }
 
 // the kernel arguments every group of a pass shares (acc_ne: scan-lines of the frame's RF block); fill_group adds each group's own
-static void fill_pass(mcrt_ctx *c, const Plan &P, mcrt::FrameArgs &a, uint32_t frame, uint32_t acc_ne, int out)
+static void fill_pass(mcrt_ctx *c, const Plan &P, mcrt::FrameArgs &a, uint32_t frame, uint32_t acc_ne, bool accumulate, int out)
 {
     memset(&a, 0, sizeof a);
     a.nodes_walk = c->d_nodes_walk; a.tris = c->d_tris; a.meshes = c->d_meshes; a.mats = c->d_mats; a.tex = c->d_tex;
@@ -816,6 +823,13 @@ static void fill_pass(mcrt_ctx *c, const Plan &P, mcrt::FrameArgs &a, uint32_t f
         }
     }
     c->last_lean_bound = a.lean_bound; c->last_march_rows = a.march_rows;
+    // Work the image does not need, left out where only the image is asked for: a counting pass and the hit / segment tables show every path to its end.
+    const bool image_only = !c->stats_on && out == 0;
+    a.thr_end = c->thr_end;
+    a.retire_late = image_only && c->knobs.retire_late ? 1u : 0u;
+    // bounce 0 folded into k_shade: the staged form, an RF block to add into, the start material silent by k_march's own test, and a workgroup
+    // of k_shade(0) within one queued scan-line
+    a.fold_b0 = image_only && c->knobs.fold_b0 && !P.latency && accumulate && c->tex_finite && c->start_silent && c->p.n_samples % 256u == 0u ? 1u : 0u;
 }
 
 // group g's own arguments: its scan-lines [b0,b1) of the pass's n_frames frames, its columns of the RF block (which begins at acc_e0), its work set
@@ -867,7 +881,7 @@ static int run_bounce(mcrt_ctx *c, Work &w, hipStream_t st, const mcrt::FrameArg
 {
     int rc = timed_launch(c, 0, st, [&] { return mcrt::launch_trace(a, b, c->stats_on, st); }); if (rc) return rc;
     rc = timed_launch(c, 1, st, [&] { return mcrt::launch_shade(a, b, c->stats_on, st); }); if (rc) return rc;
-    if (!accumulate) return MCRT_OK;
+    if (!accumulate || (a.fold_b0 && b == 0u)) return MCRT_OK;      // (bounce 0 folded: k_shade has added its echoes; later bounces keep their side streams)
     hipStream_t ms = st;
     if (overlap) {   // the segments of bounce b are final: accumulate them beside the next bounce's walk
         HIP_TRY(hipEventRecord(w.ev_bounce[b], st));
@@ -923,7 +937,7 @@ static int run_pass(mcrt_ctx *c, uint32_t frame, uint32_t n_frames, uint32_t e0,
     const Plan P = plan_pass(c, e0, e1, n_frames, one_group);
     mcrt::FrameArgs pass, args[16];
     Work *ws[16];
-    fill_pass(c, P, pass, frame, e1 - e0, out);
+    fill_pass(c, P, pass, frame, e1 - e0, accumulate, out);
     for (uint32_t g = 0; g < P.groups; g++) {
         int rc = get_work(c, g, &ws[g]); if (rc) return rc;
         rc = ensure_work(*ws[g], (size_t)(P.e[g + 1] - P.e[g]) * n_frames * c->p.n_samples, c->p.max_depth, P.ovf[g], out); if (rc) return rc;

@@ -3,7 +3,8 @@
 // The hot path's kernels, one translation unit per pipeline stage, each kernel beside its launcher:
 //   mcrt_walk.hip    k_trace_lane / k_trace_lane_wide (closest hit, one lane per ray), k_trace_packet (one wavefront per ray packet),
 //                    k_nodes_walk / k_nodes_walk_decode (the walk's 64-byte nodes)
-//   mcrt_shade.hip   k_init (the first ray of every path), k_shade (interface physics of a bounce, survivors compacted into the next queue)
+//   mcrt_shade.hip   k_init (the first ray of every path), k_shade (interface physics of a bounce, survivors compacted into the next queue),
+//                    k_shade_fold (k_shade of bounce 0 with the boundary echoes of a silent start medium added in the kernel)
 //   mcrt_path.hip    k_path (the latency form: every bounce of every path in one launch)
 //   mcrt_march.hip   k_march (RF accumulation of the segments), k_material_table
 //   mcrt_post.hip    k_finalize, k_clear_flags, k_conv_* (k_conv_lateral_rows: focal zones), k_elevation (slice thickness), k_envelope, k_remap, k_transpose, k_blocks_to_frames
@@ -56,6 +57,9 @@ struct FrameArgs {
     float scene_lo[3], scene_hi[3];   // bounds of the whole BVH
     float freq, eps, I0, offs, sx, sy, sz, tex_res, axial_res_f, pad_abs, tex_rcp, lean_bound;
     double axial_res_mm, time_step, row_dt, max_travel, sos_d, inv_row_dt;
+    double thr_end;            // row_thr[R]: the first time past the image
+    uint32_t retire_late;      // shade_path ends a path whose next segment would start past max_travel and past the image (off for counting and debug passes)
+    uint32_t fold_b0;          // staged pass in a silent start medium: k_shade(b = 0) adds bounce 0's boundary echoes itself, writes no march record, no k_march(0)
 };
 
 constexpr uint32_t MCRT_ALL_BOUNCES = 0xffffffffu;   // launch_march: accumulate the segments of every bounce in one launch

@@ -20,9 +20,12 @@ struct ShadeTables {
     MCRT_DEV float4 mat(uint32_t r) const { float4 v; if (lds) { v = mats_l[r]; asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); } else v = mats_g[r]; return v; }
     MCRT_DEV uint4 mesh(uint32_t r) const { uint4 v; if (lds) { v = meshes_l[r]; asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); } else v = meshes_g[r]; return v; }
 };
-template <bool STATS>
+// FOLD (k_shade of bounce 0 in a silent start medium, FrameArgs::fold_b0): the segment's march record is not written; what its boundary echo
+// needs is handed back in *fo and the caller adds the echo itself.
+struct FoldEcho { float refl; uint32_t steps; double t_start; };
+template <bool STATS, bool FOLD = false>
 MCRT_DEV bool shade_path(const FrameArgs &a, const ShadeTables &tb, uint32_t b, uint32_t pid, PathState &ps, f3 f2, f3 to, unsigned long long key, bool &reflected,
-                         unsigned long long &st_seg, unsigned long long &st_hits)
+                         unsigned long long &st_seg, unsigned long long &st_hits, FoldEcho *fo = nullptr)
 {
     bool alive = false;
     f3 from = ps.from, dir = ps.dir;
@@ -139,10 +142,13 @@ MCRT_DEV bool shade_path(const FrameArgs &a, const ShadeTables &tb, uint32_t b, 
             const float dist_f = sqrtf(dot(df, df)) * 10.0f;
             const uint32_t steps = steps_from((double)dist_f / a.axial_res_mm);
             const double t_start = (seg_dist * 1000.0) / a.sos_d;
-            float4 *mr = a.mrec + 3 * ((size_t)b * a.ne * a.S + pid);    // [bounce][path]: neighbouring paths are neighbours in memory
-            mr[0] = make_float4(seg_from.x, seg_from.y, seg_from.z, seg_refl);
-            mr[1] = make_float4(a.axial_res_f * seg_dir.x, a.axial_res_f * seg_dir.y, a.axial_res_f * seg_dir.z, seg_init);
-            mr[2] = make_float4(__int_as_float(__double2loint(t_start)), __int_as_float(__double2hiint(t_start)), __uint_as_float(steps), __int_as_float(seg_media));
+            if (FOLD) { fo->refl = seg_refl; fo->steps = steps; fo->t_start = t_start; }
+            else {
+                float4 *mr = a.mrec + 3 * ((size_t)b * a.ne * a.S + pid);    // [bounce][path]: neighbouring paths are neighbours in memory
+                mr[0] = make_float4(seg_from.x, seg_from.y, seg_from.z, seg_refl);
+                mr[1] = make_float4(a.axial_res_f * seg_dir.x, a.axial_res_f * seg_dir.y, a.axial_res_f * seg_dir.z, seg_init);
+                mr[2] = make_float4(__int_as_float(__double2loint(t_start)), __int_as_float(__double2hiint(t_start)), __uint_as_float(steps), __int_as_float(seg_media));
+            }
         }
         // ray_physics::segment (ray.h:28-36) -> slot [path][bounce], for the callers that ask for the segments themselves
         if (a.want_segs) {
@@ -157,6 +163,17 @@ MCRT_DEV bool shade_path(const FrameArgs &a, const ShadeTables &tb, uint32_t b, 
         if (a.hits) a.hits[(size_t)pid * a.B + b] = seg_tri;
         a.seg_count[pid] = b + 1u;
         alive = alive && (b + 1u < a.B);
+        // RETIRE a path that can no longer reach the image (FrameArgs::retire_late): t_next is the very expression the next bounce would store as
+        // its t_start.  Once it is past BOTH limits -- max_travel, which gates the steps, and the image's end thr_end = row_thr[R], which gates
+        // every echo's row; n_rows is a parameter, so neither implies the other -- the rest of the path adds nothing: dist_mm only grows (mm is a
+        // non-negative square root, or NaN; rounding is monotone and sos_d, time_step > 0), so every later t_start is >= t_next or NaN.  The
+        // accumulation loop's test `t < max_travel` then fails at step 0 of every later segment, and every later boundary echo's time
+        // t_start + time_step * (steps - 1) is >= t_start (huge when steps == 0, through the unsigned wrap) or NaN: outside [0, thr_end), no row.
+        // A NaN t_next is not retired (`t_next == t_next`): left to the loop as before.  The segment that CROSSES the limit is this one: untouched.
+        if (alive && a.retire_late) {
+            const double t_next = (dist_mm * 1000.0) / a.sos_d;
+            if (!(t_next < a.max_travel) && !(t_next < a.thr_end) && t_next == t_next) alive = false;
+        }
     }
     ps.from = from; ps.dir = dir; ps.intensity = intensity; ps.media = media; ps.outside = outside; ps.dist_mm = dist_mm;
     return alive;

@@ -62,9 +62,24 @@ __global__ void __launch_bounds__(256) k_init(FrameArgs a)
     if (pos < a.ne) a.key0[pos] = MCRT_KEY_MISS;          // bounce 0: one closest-hit word per queued (scan-line, frame)
 }
 
+// row = (int)(t / row_dt) if that quotient is < R, else -1 (rfimage.h:33-40), from the threshold table in memory: k_march's row_of, which reads its LDS image
+MCRT_DEV int row_of_thr(double t, const double *thr, uint32_t R, double inv_dt, double thr_end)
+{
+    if (!(t < thr_end) || !(t >= 0.0)) return -1;
+    int r = (int)(t * inv_dt);                                   // within one row of the answer
+    r = r < 0 ? 0 : (r > (int)R - 1 ? (int)R - 1 : r);
+    while (t < thr[r]) r--;
+    while (t >= thr[r + 1]) r++;
+    return r;
+}
+
 // ---- interface interaction of a bounce's live rays: one lane per ray ----
-template <bool STATS>
-__global__ void __launch_bounds__(256, MCRT_SHADE_WAVES) k_shade(FrameArgs a, uint32_t b)
+// FOLD (launched for b == 0 only, FrameArgs::fold_b0): the start medium is silent, so all that bounce 0 adds to the image is every path's boundary
+// echo (main.cpp:139).  The workgroup -- 256 paths of ONE queued scan-line, S % 256 == 0 -- adds them into LDS bins exactly as k_march's rf_add
+// does and flushes with the same global integer atomics into the same row: integer sums commute, the image is bit-identical.  No march record of
+// bounce 0 is written (48 B per path) and no k_march(0) sorts, hands out and reloads them.
+template <bool STATS, bool FOLD>
+MCRT_DEV void shade_bounce(const FrameArgs &a, uint32_t b)
 {
     const uint32_t n = a.counts[b];
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -78,6 +93,13 @@ __global__ void __launch_bounds__(256, MCRT_SHADE_WAVES) k_shade(FrameArgs a, ui
     if (tables_in_lds) {
         for (uint32_t r = threadIdx.x; r < 2u * a.n_mat; r += blockDim.x) mats_l[r] = a.mats[r];
         for (uint32_t r = threadIdx.x; r < a.n_mesh; r += blockDim.x) meshes_l[r] = a.meshes[r];
+        __syncthreads();
+    }
+    __shared__ long long fold_bin[FOLD ? MCRT_MAX_ROWS : 1];
+    __shared__ uint32_t fold_flag[FOLD ? MCRT_MAX_ROWS / 32 : 1];
+    if (FOLD) {
+        for (uint32_t r = threadIdx.x; r < a.R; r += blockDim.x) fold_bin[r] = 0;
+        for (uint32_t r = threadIdx.x; r < (a.R + 31u) >> 5; r += blockDim.x) fold_flag[r] = 0u;
         __syncthreads();
     }
     const ShadeTables tb = { a.mats, a.meshes, mats_l, meshes_l, tables_in_lds };
@@ -102,7 +124,18 @@ __global__ void __launch_bounds__(256, MCRT_SHADE_WAVES) k_shade(FrameArgs a, ui
         const f3 f2 = ry.f2, to = ry.to;
         const size_t hi = (b == 0u) ? (size_t)(i / a.S) : (size_t)i;            // bounce 0: one walk per queued (scan-line, frame) (see k_trace_lane, k_init)
         const unsigned long long key = ((b & 1u) ? a.key1 : a.key0)[hi];
-        alive = shade_path<STATS>(a, tb, b, pid, ps, f2, to, key, reflected, st_seg, st_hits);
+        FoldEcho fo;
+        alive = shade_path<STATS, FOLD>(a, tb, b, pid, ps, f2, to, key, reflected, st_seg, st_hits, &fo);
+        if (FOLD) {
+            // the boundary echo of the finished segment, as k_march adds it: time, row, rf_add
+            const double te = fo.t_start + a.time_step * (double)(uint32_t)(fo.steps - 1u);
+            const int row = row_of_thr(te, a.row_thr, a.R, a.inv_row_dt, a.thr_end);
+            if (row >= 0) {
+                const float echo = fo.refl / (float)a.S;
+                if (!(fabsf(echo) < 1024.0f)) atomicOr(&fold_flag[row >> 5], 1u << (row & 31));
+                else { const long long v = fix40(echo); if (v != 0) atomicAdd((unsigned long long *)&fold_bin[row], (unsigned long long)v); }
+            }
+        }
     }
     const f3 from = ps.from, dir = ps.dir; const float intensity = ps.intensity; const int media = ps.media, outside = ps.outside; const double dist_mm = ps.dist_mm;
 
@@ -143,7 +176,25 @@ __global__ void __launch_bounds__(256, MCRT_SHADE_WAVES) k_shade(FrameArgs a, ui
         long long x = wave_sum_i64((long long)st_seg), y = wave_sum_i64((long long)st_hits);
         if (lane == 0) { if (x) atomicAdd(&a.stats[3], (unsigned long long)x); if (y) atomicAdd(&a.stats[5], (unsigned long long)y); }
     }
+    if (FOLD) {
+        // (the barriers above are past every echo's LDS add.)  The workgroup's queue positions are those of ONE queued scan-line (k_init's order: the F frames of
+        // a scan-line next to each other); its row of the frames' RF block as in k_march's epilogue
+        const uint32_t F = a.ne / a.ne_frame, ql = (blockIdx.x * blockDim.x) / a.S;
+        const uint32_t line = (ql % F) * a.ne_frame + ql / F;
+        const size_t row = (size_t)(line / a.ne_frame) * a.acc_stride + a.acc_off + line % a.ne_frame;
+        const uint32_t nf = (a.R + 31u) >> 5;
+        for (uint32_t r = threadIdx.x; r < a.R; r += blockDim.x) {
+            const long long v = fold_bin[r];
+            if (v != 0) atomicAdd((unsigned long long *)&a.acc[row * a.R + r], (unsigned long long)v);
+        }
+        for (uint32_t r = threadIdx.x; r < nf; r += blockDim.x) { const uint32_t f = fold_flag[r]; if (f) atomicOr(&a.flags[row * nf + r], f); }
+    }
 }
+
+template <bool STATS>
+__global__ void __launch_bounds__(256, MCRT_SHADE_WAVES) k_shade(FrameArgs a, uint32_t b) { shade_bounce<STATS, false>(a, b); }
+// bounce 0 with its boundary echoes folded in: a kernel of its own, so that k_shade keeps its registers (64, eight wavefronts per SIMD; this one 67, seven)
+__global__ void __launch_bounds__(256, MCRT_SHADE_WAVES) k_shade_fold(FrameArgs a) { shade_bounce<false, true>(a, 0u); }
 
 hipError_t launch_init(const FrameArgs &a, hipStream_t st)
 {
@@ -157,6 +208,7 @@ hipError_t launch_shade(const FrameArgs &a, uint32_t b, bool stats, hipStream_t 
     const uint32_t np = a.ne * a.S;
     const dim3 grid((np + 255u) / 256u), blk(256);
     if (stats) hipLaunchKernelGGL((k_shade<true>), grid, blk, 0, st, a, b);
+    else if (a.fold_b0 && b == 0u) hipLaunchKernelGGL(k_shade_fold, grid, blk, 0, st, a);      // (fill_pass sets fold_b0 only where S % 256 == 0 and nothing is counted)
     else hipLaunchKernelGGL((k_shade<false>), grid, blk, 0, st, a, b);
     return hipGetLastError();
 }
