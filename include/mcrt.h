@@ -36,7 +36,9 @@ extern "C" {
                               107: + mcrt_default_bmode, mcrt_bmode_frames (log-compressed 8-bit B-mode frames: dynamic range, gain, TGC, persistence);
                               108: + mcrt_focus, mcrt_psf_focus_kernels, mcrt_convolve_frames_depth (focal zones: a lateral PSF per RF row);
                               109: + mcrt_transducer_elevation_axis, mcrt_elevation_planes, mcrt_psf_elevation_kernels, mcrt_elevation_frames (slice thickness:
-                                   elevation planes traced as one pose pass and folded with the elevation PSF) */
+                                   elevation planes traced as one pose pass and folded with the elevation PSF);
+                                   + mcrt_compound, mcrt_transducer_steered, mcrt_compound_maps, mcrt_compound_frames, mcrt_bmode_compound_frames (spatial
+                                   compounding: steered views of one plane traced as one pose pass and averaged in image space) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -342,6 +344,66 @@ int mcrt_bmode_frames(mcrt_ctx *ctx, const float *rf_dev, uint32_t n_frames, uin
                       float *state_dev /* [out_rows][out_cols] smoothing state, or NULL */,
                       float *peak_dev  /* [n_frames]: the ref each frame used, or NULL */,
                       uint8_t *out_dev /* [n_frames][out_rows][out_cols] */);
+
+/* ---- spatial compounding: the same plane insonified from several in-plane steering angles and the views averaged in image space, as every
+ * current scanner does (speckle decorrelates between the looks, shadows narrow, oblique interfaces light up).  The reference has one look
+ * direction: its beams leave the arc along its normals (transducer.h:24-62) and create_mapping (rfimage.h:183-215) knows only those.  A
+ * compounded frame is N steered copies of the probe traced as ONE pose pass (mcrt_trace_frames_poses / mcrt_group_trace_frames_poses) into
+ * a stack [N][E][R]; convolution and envelope run over the N views as over N frames; the views then meet in one gather through N map pairs.
+ *
+ * The frame-id rule (applied by the wrappers: Simulator(compound=...), rf_image::trace(frame, transducer, steers), mattausch_hip --compound):
+ * view n of image f of a pass that starts at frame id f0 is traced with frame id (f0 + f) * N + n -- every look has its own random streams.
+ * With elevation planes the views are outer: ((f0 + f) * N + n) * K + k; the fold then sees F * N frames and writes the [F][N][E][R] stack. */
+typedef struct { uint32_t n_views;      /* 1..16 */
+                 float    steer_rad[16];/* the first n_views: finite, |steer| < pi/2; any order, duplicates allowed */
+} mcrt_compound;                        /* 68 bytes: n_views at offset 0, steer_rad at 4 */
+/* mcrt_transducer_elements with every beam tilted in the image plane by steer_rad: the statements of mcrt_transducer_elements, except that
+ * the DIRECTION is built from as = (float)(angle + (double)steer_rad) -- (sin(as), cos(as), 0) through the same three rotations -- while the
+ * POSITION still uses a = (float)angle.  The beams pivot on their elements; a positive steer tilts towards higher element numbers.
+ * steer_rad == 0 gives mcrt_transducer_elements' tables bit for bit.  Host only.  Errors: mcrt_transducer_elements' own, plus
+ * MCRT_ERR_INVALID for a steer that is not finite or has |steer| >= pi/2; on an error nothing is written. */
+int mcrt_transducer_steered(uint32_t n_elements, double radius_cm, double separation_mm, const float position[3], const float angles_deg[3],
+                            float steer_rad, float *pos, float *dir);
+/* the scan-conversion maps of a steered view (layout and arguments of mcrt_scan_maps).  steer_rad == 0 CALLS mcrt_scan_maps: the unsteered
+ * maps bit for bit.  Otherwise ratio, shift_y, half_width, fi, fj, radius_f and depth_mm_f are mcrt_scan_maps' own floats; everything else
+ * is double, rounded once to float at the end:
+ *   x = (double)fj * ratio,  y = (double)fi * ratio           the pixel, mm from the arc's centre
+ *   rho = sqrt(x*x + y*y),   alpha = atan2(x, y),   q = radius_mm * sin(steer)
+ *   phi = alpha - steer + asin(q / rho)                       arc angle of the element whose steered beam passes the pixel
+ *   t   = sqrt(rho*rho - q*q) - radius_mm * cos(steer)        path length along that beam, mm
+ *   map_row = (float)(t / depth_mm_f * R),   map_col = (float)((phi + total_angle/2) / total_angle * (double)(float)E)
+ * (P = radius u(phi) + t u(phi + steer); crossing with u(phi + steer): rho sin(phi + steer - alpha) = radius sin(steer); the principal
+ * branch is the forward beam.)  Where rho < |q| no beam passes the pixel: both maps are NaN, which the gather treats as unmapped.  The
+ * half-scan-line offset of the reference's column convention (rfimage.h:212) is kept.  Host only.  MCRT_ERR_INVALID for mcrt_scan_maps'
+ * conditions and a steer that is not finite or has |steer| >= pi/2; on an error nothing is written. */
+int mcrt_compound_maps(uint32_t n_elements, uint32_t n_rows, double radius_mm, double total_angle_rad, uint32_t max_travel_us,
+                       uint32_t speed_of_sound, uint32_t out_rows, uint32_t out_cols, float steer_rad, float *map_row, float *map_col);
+/* The N views of every frame gathered through their N map pairs into one float image.  rf_dev: device float [n_frames][N][E][R];
+ * out_dev: device float [n_frames][out_rows][out_cols].  Asynchronous on the context's stream, one launch.  Per frame f and output pixel:
+ *   sum = 0.0f; cnt = 0
+ *   for n = 0..N-1:  p = the pixel's point in view n's maps (mcrt_scan_convert's floor and fractions)
+ *                    covered = both maps not NaN && p.x0 >= -1 && p.x0 < E && p.y0 >= -1 && p.y0 < R        (at least one tap inside)
+ *                    if covered: sum = sum + (mcrt_scan_convert's bilinear expression on view n of frame f);  cnt++
+ *   out = cnt ? sum / (float)cnt : 0.0f
+ * in n order, one rounding per operation, no fma.  A NaN tap reaches its pixel, as in mcrt_scan_convert.  N = 1 with steer 0 equals
+ * mcrt_scan_convert_frames bit for bit, except that a -0.0 becomes +0.0.  No per-view weights or apodisation, no max / median compounding.
+ * MCRT_ERR_INVALID for null pointers, zero sizes, n_views outside 1..16, a steer that is not finite or has |steer| >= pi/2, bad scan
+ * geometry, rf_dev overlapping out_dev; MCRT_ERR_LIMIT for n_rows > 2048 or n_frames * N > 65535.  On any error nothing is launched and
+ * out_dev is untouched.  The N map pairs live on the device in a buffer of their own beside the plain maps (alternating this call with
+ * mcrt_scan_convert_frames uploads neither), keyed like those plus N and the steer bits, every double and float compared on its own;
+ * nothing is allocated once the maps of a geometry exist.  Groups: call it on mcrt_group_root() after mcrt_group_trace_frames_poses. */
+int mcrt_compound_frames(mcrt_ctx *ctx, const float *rf_dev /* [n_frames][N][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
+                         double radius_mm, double total_angle_rad, const mcrt_compound *cp, float *out_dev /* [n_frames][out_rows][out_cols] */,
+                         uint32_t out_rows, uint32_t out_cols);
+/* mcrt_bmode_frames over compounded views: rf_dev is [n_frames][N][E][R].  Steps 1-3 run over the N views of a frame TOGETHER: the
+ * automatic reference, and peak_dev[f], is the largest amplitude over all N views of frame f.  Step 4 is mcrt_compound_frames' expression
+ * applied to the grey levels; steps 5-6 are unchanged (two calls of 2 frames equal one call of 4).  N = 1 with steer 0 gives
+ * mcrt_bmode_frames' bytes bit for bit.  Errors and limits: mcrt_bmode_frames' and mcrt_compound_frames' (n_frames * N <= 65535), and
+ * MCRT_ERR_LIMIT for N * n_elements >= 2^32; on any error nothing is launched and out_dev, state_dev and peak_dev are untouched. */
+int mcrt_bmode_compound_frames(mcrt_ctx *ctx, const float *rf_dev /* [n_frames][N][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
+                               const mcrt_bmode_params *p, const mcrt_compound *cp, const float *tgc_db /* host [n_rows] or NULL */,
+                               float *state_dev /* [out_rows][out_cols] or NULL */, float *peak_dev /* [n_frames] or NULL */,
+                               uint8_t *out_dev /* [n_frames][out_rows][out_cols] */);
 
 /* device [E][R]  ->  host [R][E] row-major (the cv::Mat layout of rfimage.h:217); synchronous */
 int mcrt_export_rf(mcrt_ctx *ctx, const float *rf_dev, uint32_t n_elements, uint32_t n_rows, float *host_rows_by_cols);

@@ -10,7 +10,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 
 # ------------------------------------------------------------------ host-side pieces (no GPU)
@@ -132,6 +132,34 @@ def host_scan_maps(n_elements, n_rows, radius_mm=30.0, total_angle=1.04719755119
     return mr, mc
 
 
+def host_transducer_steered(n_elements, radius_cm, sep_mm, position, angles_deg, steer_rad):
+    """mcrt_transducer_steered: mcrt_transducer_elements with every beam tilted in the image plane by steer_rad (the beams pivot on their
+    elements; a positive steer tilts towards higher element numbers)"""
+    pos = np.zeros((n_elements, 3), np.float32); d = np.zeros((n_elements, 3), np.float32)
+    p = np.asarray(position, np.float32); a = np.asarray(angles_deg, np.float32)
+    check(load_library().mcrt_transducer_steered(n_elements, radius_cm, sep_mm, ptr(p), ptr(a), steer_rad, ptr(pos), ptr(d)))
+    return pos, d
+
+
+def host_compound_maps(n_elements, n_rows, steer_rad, radius_mm=30.0, total_angle=1.0471975511965976, max_travel_us=100, speed_of_sound=1500, out_rows=400,
+                       out_cols=500):
+    """mcrt_compound_maps: the scan-conversion maps of a view steered by steer_rad, (map_row, map_col), each [out_rows][out_cols]; NaN where
+    no beam of the view passes the pixel.  steer_rad == 0: host_scan_maps' maps bit for bit."""
+    mr = np.zeros((out_rows, out_cols), np.float32); mc = np.zeros((out_rows, out_cols), np.float32)
+    check(load_library().mcrt_compound_maps(n_elements, n_rows, radius_mm, total_angle, max_travel_us, speed_of_sound, out_rows, out_cols, steer_rad, ptr(mr), ptr(mc)))
+    return mr, mc
+
+
+def compound_struct(steer_rad):
+    """mcrt_compound from a sequence of steering angles [rad] (more than 16 give n_views > 16, which the library refuses)"""
+    st = [float(x) for x in steer_rad]
+    cp = Compound()
+    cp.n_views = len(st)
+    for i, x in enumerate(st[:16]):
+        cp.steer_rad[i] = x
+    return cp
+
+
 BMODE_MODES = {"db": 0, "ref_log": 1}
 
 
@@ -174,6 +202,12 @@ class Transducer:
         """the element tables of n_planes parallel elevation planes pitch_um apart, centred on the probe's own plane
         (mcrt_elevation_planes along mcrt_transducer_elevation_axis): (pos [K][E][3], dir [K][E][3], z_mm [K])"""
         return host_elevation_planes(self.pos, self.dir, host_elevation_axis(self.angles), n_planes, pitch_um)
+
+    def steered(self, steer_rad_list):
+        """the element tables of the views of a compounded frame, one per steering angle [rad] (mcrt_transducer_steered):
+        (pos [N][E][3], dir [N][E][3]); the positions are the probe's own in every view"""
+        tabs = [host_transducer_steered(self.n_elements, self.radius_cm, self.separation_mm, self.position, self.angles, float(s)) for s in steer_rad_list]
+        return np.stack([t[0] for t in tabs]), np.stack([t[1] for t in tabs])
 
 
 class Psf:
@@ -426,6 +460,28 @@ class Context:
                 raise ValueError("tgc_db needs one value per RF row: %d, got shape %s" % (n_rows, tgc.shape))
         check(self.L.mcrt_bmode_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(p), ptr(tgc), ptr(state_dev), ptr(peak_dev), ptr(out_dev)))
 
+    def compound_frames(self, rf_dev, n_frames, n_elements, n_rows, steer_rad, out_dev, radius_mm=30.0, total_angle=1.0471975511965976, out_rows=400, out_cols=500):
+        """mcrt_compound_frames: the views [n_frames][N][E][R] of steer_rad's N angles -> device floats [n_frames][out_rows][out_cols], every
+        pixel the mean of the views that cover it"""
+        cp = compound_struct(steer_rad)
+        check(self.L.mcrt_compound_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, radius_mm, total_angle, C.byref(cp), ptr(out_dev), out_rows, out_cols))
+
+    def bmode_compound_frames(self, rf_dev, n_frames, n_elements, n_rows, steer_rad, out_dev, *, mode="db", dynamic_range_db=60.0, gain_db=0.0, ref=None,
+                              tgc_db=None, persistence=0.0, state_dev=None, reset_state=True, peak_dev=None, radius_mm=30.0,
+                              total_angle=1.0471975511965976, out_rows=400, out_cols=500):
+        """mcrt_bmode_compound_frames: bmode_frames over the views [n_frames][N][E][R] of steer_rad's N angles; the automatic reference of a
+        frame is the peak over all its views"""
+        p = bmode_params(mode=mode, dynamic_range_db=dynamic_range_db, gain_db=gain_db, ref=ref, persistence=persistence, reset_state=reset_state,
+                         radius_mm=radius_mm, total_angle=total_angle, out_rows=out_rows, out_cols=out_cols)
+        cp = compound_struct(steer_rad)
+        tgc = None
+        if tgc_db is not None:
+            tgc = np.ascontiguousarray(tgc_db, np.float32)
+            if tgc.shape != (n_rows,):
+                raise ValueError("tgc_db needs one value per RF row: %d, got shape %s" % (n_rows, tgc.shape))
+        check(self.L.mcrt_bmode_compound_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(p), C.byref(cp), ptr(tgc), ptr(state_dev),
+                                                ptr(peak_dev), ptr(out_dev)))
+
     def export_rf(self, rf_dev, n_elements, n_rows):
         out = np.empty((n_rows, n_elements), np.float32)
         check(self.L.mcrt_export_rf(self.h, ptr(rf_dev), n_elements, n_rows, ptr(out)))
@@ -577,10 +633,16 @@ class Simulator:
     """
 
     def __init__(self, scene_data, transducer, n_samples=5, n_rows=None, device=0, seed=0x5EED, psf=None, texture=None,
-                 max_depth=10, sanitize_tir=0, tex_n=256, bvh_builder="sah", elevation=False):
+                 max_depth=10, sanitize_tir=0, tex_n=256, bvh_builder="sah", elevation=False, compound=None):
         """elevation=True: slice thickness.  trace() then traces the psf's elevation_size planes of the frame as one pose pass -- plane k of
         frame f with frame id f * K + k, the frame-id rule of include/mcrt.h -- and folds them into rf_dev with psf.elevation_rows();
-        everything after (convolve, bmode, frame) is unchanged."""
+        everything after (convolve, bmode, frame) is unchanged.
+        compound=(steer_rad, ...): spatial compounding.  trace() then traces the N steered views of the frame as one pose pass -- view n of
+        frame f with frame id f * N + n, with elevation its plane k with (f * N + n) * K + k -- into views_dev [N][E][R] (folded per view
+        with elevation=True); convolve() and the envelope run over the N views, bmode() ends in mcrt_bmode_compound_frames and
+        compound_image() in mcrt_compound_frames.  frame() returns RF, which a compounded frame does not have: it raises."""
+        if compound is not None and not 1 <= len(tuple(compound)) <= 16:
+            raise ValueError("compound takes 1..16 steering angles, got %d" % len(tuple(compound)))
         self.ctx = Context(device)
         self.ctx.set_bvh_builder(bvh_builder)
         self.tr = transducer
@@ -594,19 +656,37 @@ class Simulator:
         self.psf = psf or Psf(freq=transducer.frequency)
         self.rf_dev = self.ctx.alloc(E * self.R * 4)
         self.elevation, self.planes_dev = bool(elevation), None
+        self.steers = tuple(float(x) for x in compound) if compound is not None else None
+        self.N, self.views_dev = (len(self.steers), None) if self.steers is not None else (1, None)
+        if self.steers is not None:
+            self.view_pos, self.view_dir = transducer.steered(self.steers)
+            self.views_dev = self.ctx.alloc(self.N * E * self.R * 4)
         if self.elevation:
             self.K = self.psf.elevation_size
             self.plane_pos, self.plane_dir, self.plane_z_mm = transducer.planes(self.K, self.psf.elevation_pitch_um)
-            self.planes_dev = self.ctx.alloc(self.K * E * self.R * 4)
+            if self.steers is not None:                 # the views are outer: [N][K][E][3]
+                axis = host_elevation_axis(transducer.angles)
+                tabs = [host_elevation_planes(self.view_pos[n], self.view_dir[n], axis, self.K, self.psf.elevation_pitch_um) for n in range(self.N)]
+                self.plane_pos = np.concatenate([t[0] for t in tabs]); self.plane_dir = np.concatenate([t[1] for t in tabs])
+            self.planes_dev = self.ctx.alloc(self.N * self.K * E * self.R * 4)
 
     def close(self):
         if self.ctx.h:
             self.ctx.free(self.rf_dev)
             if self.planes_dev:
                 self.ctx.free(self.planes_dev)
+            if self.views_dev:
+                self.ctx.free(self.views_dev)
             self.ctx.close()
 
     def trace(self, frame_id=0):
+        if self.steers is not None:
+            if not self.elevation:
+                self.ctx.trace_frames_poses(frame_id * self.N, self.view_pos, self.view_dir, self.views_dev)
+                return
+            self.ctx.trace_frames_poses(frame_id * self.N * self.K, self.plane_pos, self.plane_dir, self.planes_dev)
+            self.ctx.elevation_frames(self.planes_dev, self.N, self.K, self.E, self.R, self.psf.elevation_rows(self.R, self.row_mm), self.views_dev)
+            return
         if not self.elevation:
             self.ctx.trace_frame(frame_id, self.rf_dev)
             return
@@ -619,10 +699,38 @@ class Simulator:
         return row_pitch_mm(self.ctx.params.frequency)
 
     def convolve(self):
-        if self.psf.has_focus:
+        if self.steers is not None:                     # the N views as N frames
+            if self.psf.has_focus:
+                self.ctx.convolve_frames_depth(self.views_dev, self.N, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_rows(self.R, self.row_mm))
+            else:
+                self.ctx.convolve_frames(self.views_dev, self.N, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_kernel)
+        elif self.psf.has_focus:
             self.ctx.convolve_frames_depth(self.rf_dev, 1, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_rows(self.R, self.row_mm))
         else:
             self.ctx.convolve(self.rf_dev, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_kernel)
+
+    def envelope(self):
+        if self.steers is not None:
+            self.ctx.envelope_frames(self.views_dev, self.N, self.E, self.R)
+        else:
+            self.ctx.envelope(self.rf_dev, self.E, self.R)
+
+    def compound_image(self, frame_id=0, convolve=True, envelope=True, radius_mm=30.0, total_angle=1.0471975511965976, out_rows=400, out_cols=500):
+        """trace -> convolve -> envelope -> mcrt_compound_frames -> host: the compounded float picture [out_rows][out_cols] (compound= only)"""
+        if self.steers is None:
+            raise RuntimeError("compound_image() needs Simulator(compound=...)")
+        self.trace(frame_id)
+        if convolve:
+            self.convolve()
+        if envelope:
+            self.envelope()
+        out = self.ctx.alloc(out_rows * out_cols * 4)
+        try:
+            self.ctx.compound_frames(self.views_dev, 1, self.E, self.R, self.steers, out, radius_mm=radius_mm, total_angle=total_angle, out_rows=out_rows,
+                                     out_cols=out_cols)
+            return self.ctx.d2h(out, (out_rows, out_cols), np.float32)
+        finally:
+            self.ctx.free(out)
 
     def bmode(self, frame_id=0, **display):
         """trace -> convolve -> envelope -> mcrt_bmode_frames -> host: the displayed 8-bit frame, uint8 [out_rows][out_cols].
@@ -630,15 +738,20 @@ class Simulator:
         rows, cols = display.get("out_rows", 400), display.get("out_cols", 500)
         self.trace(frame_id)
         self.convolve()
-        self.ctx.envelope(self.rf_dev, self.E, self.R)
+        self.envelope()
         out = self.ctx.alloc(rows * cols)
         try:
-            self.ctx.bmode_frames(self.rf_dev, 1, self.E, self.R, out, **display)
+            if self.steers is not None:
+                self.ctx.bmode_compound_frames(self.views_dev, 1, self.E, self.R, self.steers, out, **display)
+            else:
+                self.ctx.bmode_frames(self.rf_dev, 1, self.E, self.R, out, **display)
             return self.ctx.d2h(out, (rows, cols), np.uint8)
         finally:
             self.ctx.free(out)
 
     def frame(self, frame_id=0, convolve=True):
+        if self.steers is not None:
+            raise RuntimeError("frame() returns one RF image; a compounded frame has N views and meets only as a picture: use compound_image() or bmode()")
         self.trace(frame_id)
         if convolve:
             self.convolve()

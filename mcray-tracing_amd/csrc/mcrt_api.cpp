@@ -179,6 +179,9 @@ struct mcrt_ctx {
     Buf<float4> d_mtab; float mtab_key[2] = { 0.0f, 0.0f }; bool mtab_valid = false;
     // scan-conversion maps
     Buf<float> d_map_col, d_map_row; uint32_t map_key[6] = { 0, 0, 0, 0, 0, 0 }; double map_keyd[3] = { 0, 0, 0 };
+    // spatial compounding (mcrt_compound_frames, mcrt_bmode_compound_frames): the N map pairs of a geometry and a steer list, [N][2][n_pad] (per view
+    // the column map, then the row map; n_pad = out_rows * out_cols rounded up to 256, zero-padded), in a buffer of their own beside the plain maps
+    Buf<float> d_cmaps; uint32_t cmap_key[7] = { 0, 0, 0, 0, 0, 0, 0 }; double cmap_keyd[3] = { 0, 0, 0 }; uint32_t cmap_steer[16] = {};
     // B-mode display (mcrt_bmode_frames): device TGC factors [MCRT_MAX_ROWS] + the peaks of a pass [65535] in one buffer, the factors' pinned
     // staging and the curve now on the device (its upload is waited for only when the next curve differs)
     Buf<float> d_disp; PinnedBuf<float> h_tgc; std::vector<float> tgc_on_dev; Event ev_tgc; bool tgc_copy_pending = false;
@@ -1220,34 +1223,38 @@ extern "C" int mcrt_default_bmode(mcrt_bmode_params *p)
     return MCRT_OK;
 }
 
-// The contract is in include/mcrt.h.  Everything is checked before anything is launched; then, on the context's stream: the TGC factors
-// (only when they differ from the ones on the device), with the automatic reference the peaks (memset + k_bmode_peak), the grey level of
-// every RF tap (k_bmode_grey, into the context's scratch) and their scan conversion, persistence and quantisation (k_bmode).
-extern "C" int mcrt_bmode_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_bmode_params *p,
-                                 const float *tgc_db, float *state_dev, float *peak_dev, uint8_t *out_dev)
+// what mcrt_bmode_frames and mcrt_bmode_compound_frames check alike (fn: the caller's name, for the message); k receives the TGC factors
+static int bmode_check(const char *fn, const float *rf_dev, const void *out_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_bmode_params *p,
+                       const float *tgc_db, std::vector<float> &k)
 {
-    CTX_TRY(c);
-    if (!p) return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: null params");
-    if (!rf_dev || !out_dev) return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: null %s", rf_dev ? "out_dev" : "rf_dev");
-    if (E == 0 || R == 0 || n_frames == 0 || p->out_rows == 0 || p->out_cols == 0) return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: zero sizes");
-    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "mcrt_bmode_frames: at most %d rows", MCRT_MAX_ROWS);
-    if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "mcrt_bmode_frames: at most 65535 frames per call");
-    if ((uint64_t)p->out_rows * p->out_cols > 0x7ffffffcull) return set_error(MCRT_ERR_LIMIT, "mcrt_bmode_frames: output image too large");
-    if (p->mode != MCRT_BMODE_DB && p->mode != MCRT_BMODE_REF_LOG) return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: unknown mode %u", p->mode);
+    if (!p) return set_error(MCRT_ERR_INVALID, "%s: null params", fn);
+    if (!rf_dev || !out_dev) return set_error(MCRT_ERR_INVALID, "%s: null %s", fn, rf_dev ? "out_dev" : "rf_dev");
+    if (E == 0 || R == 0 || n_frames == 0 || p->out_rows == 0 || p->out_cols == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes", fn);
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: at most %d rows", fn, MCRT_MAX_ROWS);
+    if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 frames per call", fn);
+    if ((uint64_t)p->out_rows * p->out_cols > 0x7ffffffcull) return set_error(MCRT_ERR_LIMIT, "%s: output image too large", fn);
+    if (p->mode != MCRT_BMODE_DB && p->mode != MCRT_BMODE_REF_LOG) return set_error(MCRT_ERR_INVALID, "%s: unknown mode %u", fn, p->mode);
     if (!(std::isfinite(p->dynamic_range_db) && p->dynamic_range_db > 0.0f))
-        return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: dynamic_range_db must be finite and > 0 (%g)", (double)p->dynamic_range_db);
-    if (!std::isfinite(p->gain_db)) return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: gain_db must be finite");
-    if (!std::isfinite(p->ref)) return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: ref must be finite");
-    if (!(p->persistence >= 0.0f && p->persistence < 1.0f)) return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: persistence must be in [0,1) (%g)", (double)p->persistence);
-    std::vector<float> k;
+        return set_error(MCRT_ERR_INVALID, "%s: dynamic_range_db must be finite and > 0 (%g)", fn, (double)p->dynamic_range_db);
+    if (!std::isfinite(p->gain_db)) return set_error(MCRT_ERR_INVALID, "%s: gain_db must be finite", fn);
+    if (!std::isfinite(p->ref)) return set_error(MCRT_ERR_INVALID, "%s: ref must be finite", fn);
+    if (!(p->persistence >= 0.0f && p->persistence < 1.0f)) return set_error(MCRT_ERR_INVALID, "%s: persistence must be in [0,1) (%g)", fn, (double)p->persistence);
     if (tgc_db) {
         k.resize(R);
         for (uint32_t r = 0; r < R; r++) {
-            if (!std::isfinite(tgc_db[r])) return set_error(MCRT_ERR_INVALID, "mcrt_bmode_frames: tgc_db[%u] is not finite", r);
+            if (!std::isfinite(tgc_db[r])) return set_error(MCRT_ERR_INVALID, "%s: tgc_db[%u] is not finite", fn, r);
             k[r] = (float)std::pow(10.0, (double)tgc_db[r] / 20.0);
         }
     }
-    { int rc = ensure_maps(c, E, R, p->radius_mm, p->total_angle_rad, p->out_rows, p->out_cols); if (rc) return rc; }
+    return MCRT_OK;
+}
+
+// steps 1-3 of mcrt_bmode_frames on the context's stream, over n_frames images of `lines` scan-lines each (the N views of a compounded frame
+// are one image of N * E scan-lines): the TGC factors (only when they differ from the ones on the device), with the automatic reference
+// the peaks (memset + k_bmode_peak), the grey level of every RF tap (k_bmode_grey, into the context's scratch)
+static int bmode_grey_pass(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t lines, uint32_t R, const mcrt_bmode_params *p, const float *tgc_db,
+                           const std::vector<float> &k, float *peak_dev)
+{
     constexpr size_t MAX_PEAKS = 65536;
     if (!c->d_disp) {                                   // once per context, all three or none
         Buf<float> disp; PinnedBuf<float> tgc; Event ev;
@@ -1265,27 +1272,131 @@ extern "C" int mcrt_bmode_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_fr
         c->tgc_copy_pending = true;
         c->tgc_on_dev = k;
     }
-    const size_t taps = (size_t)n_frames * E * R;
+    const size_t taps = (size_t)n_frames * lines * R;
     { int rc = ensure_tmp(c, taps); if (rc) return rc; }     // the grey levels of the pass (the scratch mcrt_convolve uses too)
     const float *tgc = tgc_db ? d_tgc : nullptr;
-    if (p->ref > 0.0f) HIP_TRY(mcrt::launch_bmode_grey(rf_dev, n_frames, E, R, tgc, nullptr, p->ref, peak_dev, p->mode, p->gain_db, p->dynamic_range_db, c->d_tmp, c->stream));
+    if (p->ref > 0.0f) HIP_TRY(mcrt::launch_bmode_grey(rf_dev, n_frames, lines, R, tgc, nullptr, p->ref, peak_dev, p->mode, p->gain_db, p->dynamic_range_db, c->d_tmp, c->stream));
     else {
         float *peak = peak_dev ? peak_dev : d_peak;
         HIP_TRY(hipMemsetAsync(peak, 0, 4 * (size_t)n_frames, c->stream));
-        HIP_TRY(mcrt::launch_bmode_peak(rf_dev, n_frames, E, R, tgc, peak, c->stream));
-        HIP_TRY(mcrt::launch_bmode_grey(rf_dev, n_frames, E, R, tgc, peak, 0.0f, nullptr, p->mode, p->gain_db, p->dynamic_range_db, c->d_tmp, c->stream));
+        HIP_TRY(mcrt::launch_bmode_peak(rf_dev, n_frames, lines, R, tgc, peak, c->stream));
+        HIP_TRY(mcrt::launch_bmode_grey(rf_dev, n_frames, lines, R, tgc, peak, 0.0f, nullptr, p->mode, p->gain_db, p->dynamic_range_db, c->d_tmp, c->stream));
     }
+    return MCRT_OK;
+}
+
+// without persistence the frames are independent: they are cut into chunks (grid.y) so that a pass has about 16384 wavefronts (the
+// lanes wait for their gathers; at 400 x 500 a chunk is one frame)
+static uint32_t display_frames_per_chunk(uint32_t n_frames, uint32_t n, float alpha)
+{
+    if (alpha != 0.0f) return n_frames;
+    const uint32_t waves = (n + 255u) / 256u, chunks = std::max(1u, std::min(n_frames, (16384u + waves - 1u) / waves));
+    return (n_frames + chunks - 1u) / chunks;
+}
+
+// The contract is in include/mcrt.h.  Everything is checked before anything is launched; then, on the context's stream: the TGC factors
+// (only when they differ from the ones on the device), with the automatic reference the peaks (memset + k_bmode_peak), the grey level of
+// every RF tap (k_bmode_grey, into the context's scratch) and their scan conversion, persistence and quantisation (k_bmode).
+extern "C" int mcrt_bmode_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_bmode_params *p,
+                                 const float *tgc_db, float *state_dev, float *peak_dev, uint8_t *out_dev)
+{
+    CTX_TRY(c);
+    std::vector<float> k;
+    { int rc = bmode_check("mcrt_bmode_frames", rf_dev, out_dev, n_frames, E, R, p, tgc_db, k); if (rc) return rc; }
+    { int rc = ensure_maps(c, E, R, p->radius_mm, p->total_angle_rad, p->out_rows, p->out_cols); if (rc) return rc; }
+    { int rc = bmode_grey_pass(c, rf_dev, n_frames, E, R, p, tgc_db, k, peak_dev); if (rc) return rc; }
     mcrt::BmodeArgs a;
     a.grey = c->d_tmp; a.map_col = c->d_map_col; a.map_row = c->d_map_row; a.state = state_dev; a.out = out_dev; a.alpha = p->persistence;
     a.E = E; a.R = R; a.n = p->out_rows * p->out_cols; a.F = n_frames; a.reset = p->reset_state ? 1u : 0u;
-    // without persistence the frames are independent: they are cut into chunks (grid.y) so that a pass has about 16384 wavefronts (the
-    // lanes wait for their gathers; at 400 x 500 a chunk is one frame)
-    a.frames_per_chunk = n_frames;
-    if (a.alpha == 0.0f) {
-        const uint32_t waves = (a.n + 255u) / 256u, chunks = std::max(1u, std::min(n_frames, (16384u + waves - 1u) / waves));
-        a.frames_per_chunk = (n_frames + chunks - 1u) / chunks;
-    }
+    a.frames_per_chunk = display_frames_per_chunk(n_frames, a.n, a.alpha);
     HIP_TRY(mcrt::launch_bmode(a, c->stream));
+    return MCRT_OK;
+}
+
+// ---- spatial compounding (the contracts are in include/mcrt.h) ----
+static int compound_check(const char *fn, const mcrt_compound *cp, uint32_t n_frames)
+{
+    if (!cp) return set_error(MCRT_ERR_INVALID, "%s: null mcrt_compound", fn);
+    if (cp->n_views == 0 || cp->n_views > 16) return set_error(MCRT_ERR_INVALID, "%s: n_views must be 1..16 (%u)", fn, cp->n_views);
+    for (uint32_t n = 0; n < cp->n_views; n++)
+        if (!(std::isfinite(cp->steer_rad[n]) && std::fabs((double)cp->steer_rad[n]) < 1.57079632679489661923))
+            return set_error(MCRT_ERR_INVALID, "%s: steer_rad[%u] must be finite and |steer| < pi/2 (%g)", fn, n, (double)cp->steer_rad[n]);
+    if ((uint64_t)n_frames * cp->n_views > 65535ull) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 views per call (%u frames x %u)", fn, n_frames, cp->n_views);
+    return MCRT_OK;
+}
+
+static bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + a_bytes, b0 = (uintptr_t)b, b1 = b0 + b_bytes;
+    return a0 < b1 && b0 < a1;
+}
+
+// the N map pairs of a geometry and a steer list on the device: ensure_maps' scheme and key, plus N and the steer bits, each compared on its own
+static int ensure_compound_maps(mcrt_ctx *c, uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t orows, uint32_t ocols, const mcrt_compound *cp)
+{
+    const uint32_t N = cp->n_views;
+    const uint32_t key[7] = { E, R, orows, ocols, c->p.speed_of_sound, 1u, N };
+    const double keyd[3] = { radius_mm, total_angle, c->c.max_travel_us };
+    uint32_t steer[16] = {};
+    memcpy(steer, cp->steer_rad, 4 * (size_t)N);
+    if (memcmp(key, c->cmap_key, sizeof key) || memcmp(keyd, c->cmap_keyd, sizeof keyd) || memcmp(steer, c->cmap_steer, sizeof steer)) {
+        const size_t n = (size_t)orows * ocols, n_pad = (n + 255u) & ~(size_t)255u;
+        std::vector<float> maps(2 * (size_t)N * n_pad, 0.0f), mr(n), mc(n);
+        for (uint32_t v = 0; v < N; v++) {
+            int rc = mcrt_compound_maps(E, R, radius_mm, total_angle, (uint32_t)c->c.max_travel_us, c->p.speed_of_sound, orows, ocols, cp->steer_rad[v], mr.data(), mc.data());
+            if (rc) return rc;
+            memcpy(&maps[(size_t)(2u * v) * n_pad], mc.data(), 4 * n);
+            memcpy(&maps[(size_t)(2u * v + 1u) * n_pad], mr.data(), 4 * n);
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        memset(c->cmap_key, 0, sizeof key);                 // (no geometry until the maps are on the device)
+        HIP_TRY(c->d_cmaps.grow(maps.size()));
+        HIP_TRY(hipMemcpy(c->d_cmaps, maps.data(), maps.size() * 4, hipMemcpyHostToDevice));
+        memcpy(c->cmap_key, key, sizeof key); memcpy(c->cmap_keyd, keyd, sizeof keyd); memcpy(c->cmap_steer, steer, sizeof steer);
+    }
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_compound_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, double radius_mm, double total_angle,
+                                    const mcrt_compound *cp, float *out_dev, uint32_t orows, uint32_t ocols)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_compound_frames";
+    if (!rf_dev || !out_dev || E == 0 || R == 0 || orows == 0 || ocols == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "%s: bad arguments", fn);
+    if (!(total_angle > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: total_angle_rad must be > 0", fn);
+    { int rc = compound_check(fn, cp, n_frames); if (rc) return rc; }
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: at most %d rows", fn, MCRT_MAX_ROWS);
+    if ((uint64_t)orows * ocols > 0x7ffffffcull) return set_error(MCRT_ERR_LIMIT, "%s: output image too large", fn);
+    const uint32_t N = cp->n_views, n = orows * ocols;
+    if (ranges_overlap(rf_dev, 4 * (size_t)n_frames * N * E * R, out_dev, 4 * (size_t)n_frames * n)) return set_error(MCRT_ERR_INVALID, "%s: rf_dev and out_dev overlap", fn);
+    { int rc = ensure_compound_maps(c, E, R, radius_mm, total_angle, orows, ocols, cp); if (rc) return rc; }
+    mcrt::CompoundArgs a;
+    a.src = rf_dev; a.maps = c->d_cmaps; a.state = nullptr; a.out = out_dev; a.alpha = 0.0f;
+    a.E = E; a.R = R; a.n = n; a.n_pad = (n + 255u) & ~255u; a.F = n_frames; a.N = N; a.reset = 1u;
+    a.frames_per_chunk = display_frames_per_chunk(n_frames, n, 0.0f);
+    HIP_TRY(mcrt::launch_compound(a, false, c->stream));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_bmode_compound_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_bmode_params *p,
+                                          const mcrt_compound *cp, const float *tgc_db, float *state_dev, float *peak_dev, uint8_t *out_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_bmode_compound_frames";
+    std::vector<float> k;
+    { int rc = bmode_check(fn, rf_dev, out_dev, n_frames, E, R, p, tgc_db, k); if (rc) return rc; }
+    if (!(p->total_angle_rad > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: total_angle_rad must be > 0", fn);
+    { int rc = compound_check(fn, cp, n_frames); if (rc) return rc; }
+    const uint32_t N = cp->n_views, n = p->out_rows * p->out_cols;
+    if ((uint64_t)N * E > 0xffffffffull) return set_error(MCRT_ERR_LIMIT, "%s: too many scan-lines (%u views x %u)", fn, N, E);   // (a frame is N * E scan-lines to steps 1-3)
+    if (ranges_overlap(rf_dev, 4 * (size_t)n_frames * N * E * R, out_dev, (size_t)n_frames * n)) return set_error(MCRT_ERR_INVALID, "%s: rf_dev and out_dev overlap", fn);
+    { int rc = ensure_compound_maps(c, E, R, p->radius_mm, p->total_angle_rad, p->out_rows, p->out_cols, cp); if (rc) return rc; }
+    { int rc = bmode_grey_pass(c, rf_dev, n_frames, N * E, R, p, tgc_db, k, peak_dev); if (rc) return rc; }
+    mcrt::CompoundArgs a;
+    a.src = c->d_tmp; a.maps = c->d_cmaps; a.state = state_dev; a.out = out_dev; a.alpha = p->persistence;
+    a.E = E; a.R = R; a.n = n; a.n_pad = (n + 255u) & ~255u; a.F = n_frames; a.N = N; a.reset = p->reset_state ? 1u : 0u;
+    a.frames_per_chunk = display_frames_per_chunk(n_frames, n, a.alpha);
+    HIP_TRY(mcrt::launch_compound(a, true, c->stream));
     return MCRT_OK;
 }
 

@@ -1,6 +1,7 @@
 // mcrt_display.hip -- the displayed picture (mcrt_bmode_frames, contract in include/mcrt.h): k_bmode_peak (each frame's reference amplitude),
 // k_bmode_grey (TGC and log compression of every RF tap) and k_bmode (the scan conversion of the grey levels, persistence and 8-bit
-// quantisation, every frame of a pass in one launch).
+// quantisation, every frame of a pass in one launch).  Spatial compounding (mcrt_compound_frames, mcrt_bmode_compound_frames): k_compound, the
+// N steered views of every frame gathered through their N map pairs into one float or 8-bit picture.
 // The reference stops at rfimage.h:131-136 (log10(v+1)/log10(max+1), commented out) and rfimage.h:142-147 (convertTo CV_8U, 255).
 #include "mcrt_device.h"
 
@@ -162,6 +163,116 @@ __global__ void __launch_bounds__(256) k_bmode(BmodeArgs a)
     }
 }
 
+// Spatial compounding (contract in include/mcrt.h): out[f][p] = the mean, over the views n that cover pixel p, of view n of frame f blended
+// at the point view n's maps give for p -- k_remap's expression per view, summed in n order, one rounding per operation.  OUT8 = false
+// writes that float (mcrt_compound_frames); OUT8 = true takes the grey levels of k_bmode_grey and goes on as k_bmode does: persistence as
+// a register recurrence, quantisation, one 32-bit store per frame and lane (mcrt_bmode_compound_frames).
+// A wavefront owns 256 consecutive pixels, a lane the four pixels wb + 64 j + lane, j = 0..3: in every gather the 64 lanes then ask for 64
+// NEIGHBOURING pixels, as k_remap's do.  (With four consecutive pixels per lane, k_bmode's layout, the lanes of one gather are four pixels
+// apart and reach 2.5 times as many scan-lines, each a cache line of its own: measured)  The lane walks the frames [f0, f1)
+// of its chunk (blockIdx.y) in groups of up to 8.  The loop of a group is VIEWS-outer: a view's 4 points are made once per group (16 views'
+// points at once would take 16 x 4 x 6 registers), then that view is gathered and blended for each frame of the group into per-frame sums
+// in registers.  Which views cover a pixel depends on the maps alone, so the count is made once per group.  The maps are padded to a
+// multiple of 256 pixels per view (zeros: the pixels past the picture's end read tap (0, 0), which exists, and are not stored).  The float
+// form stores 256 contiguous bytes per instruction as it is; the 8-bit form first turns the wavefront's 4 x 64 bytes round with four
+// ds_bpermute, so that lane L holds the bytes of pixels wb + 4 L .. 4 L + 3 and stores them as one word (VEC_OUT: the picture's size and
+// the output pointer keep them aligned; a wavefront at the picture's end stores its bytes one by one).  Frames are cut into chunks only
+// without persistence, as in k_bmode.
+constexpr int COMPOUND_GROUP = 8;
+template <bool OUT8, bool VEC_OUT>
+__global__ void __launch_bounds__(256) k_compound(CompoundArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wb = blockIdx.x * 1024u + (threadIdx.x >> 6) * 256u;      // the wavefront's first pixel
+    if (wb >= a.n) return;                                                    // (the whole wavefront)
+    const uint32_t p0 = wb + lane, E = a.E, R = a.R, N = a.N;                 // the lane's pixels: p0 + 64 j
+    const bool whole = wb + 256u <= a.n;
+    const size_t view = (size_t)E * R;
+    const uint32_t f0 = blockIdx.y * a.frames_per_chunk, f1 = min(a.F, f0 + a.frames_per_chunk);
+    const bool smooth = OUT8 && a.alpha > 0.0f;
+    float y[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+    bool have_prev = false;
+    if (smooth && a.state && !a.reset) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) y[j] = p0 + 64u * j < a.n ? a.state[p0 + 64u * j] : 0.0f;
+        have_prev = true;
+    }
+    for (uint32_t g0 = f0; g0 < f1; g0 += (uint32_t)COMPOUND_GROUP) {
+        const uint32_t ng = min((uint32_t)COMPOUND_GROUP, f1 - g0);
+        float sum[COMPOUND_GROUP][4];
+        float looks[4] = { 0.0f, 0.0f, 0.0f, 0.0f };       // views that cover each pixel (at most 16: exact in float)
+#pragma unroll
+        for (int k = 0; k < COMPOUND_GROUP; k++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) sum[k][j] = 0.0f;
+        for (uint32_t n = 0; n < N; n++) {
+            const float *mc = a.maps + (size_t)(2u * n) * a.n_pad + p0, *mr = mc + a.n_pad;   // (n_pad % 256 == 0: p0 + 192 < n_pad)
+            RemapPoint pt[4];
+            bool covered[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const float mx = mc[64 * j], my = mr[64 * j];
+                pt[j] = remap_point(mx, my);
+                covered[j] = (mx == mx) && (my == my) && pt[j].x0 >= -1 && pt[j].x0 < (long long)E && pt[j].y0 >= -1 && pt[j].y0 < (long long)R;
+                looks[j] = covered[j] ? looks[j] + 1.0f : looks[j];
+            }
+#pragma unroll
+            for (int k = 0; k < COMPOUND_GROUP; k++) {
+                if ((uint32_t)k < ng) {                     // (the same in every lane)
+                    const float *g = a.src + ((size_t)(g0 + (uint32_t)k) * N + n) * view;
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        float t[2][2];
+                        remap_taps(pt[j], E, R, [=](long long x, long long yy) { return g[(size_t)x * R + (size_t)yy]; }, t);
+                        const float s = remap_blend(pt[j], t);
+                        sum[k][j] = covered[j] ? sum[k][j] + s : sum[k][j];
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < COMPOUND_GROUP; k++) {
+            if ((uint32_t)k < ng) {
+                const uint32_t f = g0 + (uint32_t)k;
+                float v[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) v[j] = looks[j] > 0.0f ? sum[k][j] / looks[j] : 0.0f;
+                if (OUT8) {
+                    uint32_t bytes = 0u;                    // byte j: pixel p0 + 64 j
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        if (!smooth) y[j] = v[j];
+                        else y[j] = fmaf(a.alpha, have_prev ? y[j] : v[j], (1.0f - a.alpha) * v[j]);
+                        bytes |= (uint32_t)(uint8_t)(y[j] * 255.0f + 0.5f) << (8 * j);
+                    }
+                    have_prev = true;
+                    uint8_t *o = (uint8_t *)a.out + (size_t)f * a.n;
+                    if (VEC_OUT && whole) {                 // pixel wb + 4 L + i is byte L / 16 of lane (4 L + i) % 64: every lane is active here
+                        uint32_t word = 0u;
+#pragma unroll
+                        for (int i = 0; i < 4; i++) {
+                            const uint32_t got = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((4u * lane + (uint32_t)i) & 63u) * 4u), (int)bytes);
+                            word |= ((got >> (8u * (lane >> 4))) & 0xffu) << (8 * i);
+                        }
+                        *(uint32_t *)(o + wb + 4u * lane) = word;
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; j++) if (p0 + 64u * j < a.n) o[p0 + 64u * j] = (uint8_t)(bytes >> (8 * j));
+                    }
+                } else {
+                    float *o = (float *)a.out + (size_t)f * a.n;
+#pragma unroll
+                    for (int j = 0; j < 4; j++) if (p0 + 64u * j < a.n) o[p0 + 64u * j] = v[j];
+                }
+            }
+        }
+    }
+    if (OUT8 && a.state && f1 == a.F && f0 < f1) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) if (p0 + 64u * j < a.n) a.state[p0 + 64u * j] = y[j];
+    }
+}
+
 hipError_t launch_bmode_peak(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, float *peak, hipStream_t st)
 {
     const size_t n = (size_t)E * R;
@@ -194,6 +305,17 @@ hipError_t launch_bmode(const BmodeArgs &a, hipStream_t st)
     const bool vec = a.n % 4u == 0u && (uintptr_t)a.out % 4u == 0u;
     if (vec) hipLaunchKernelGGL((k_bmode<true>), grid, blk, 0, st, a);
     else hipLaunchKernelGGL((k_bmode<false>), grid, blk, 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_compound(const CompoundArgs &a, bool out8, hipStream_t st)
+{
+    const uint32_t chunks = (a.F + a.frames_per_chunk - 1u) / a.frames_per_chunk;
+    const dim3 grid((a.n + 1023u) / 1024u, chunks), blk(256);
+    const bool vec = a.n % 4u == 0u && (uintptr_t)a.out % 4u == 0u;          // the 8-bit form's one word per lane
+    if (!out8) hipLaunchKernelGGL((k_compound<false, false>), grid, blk, 0, st, a);
+    else if (vec) hipLaunchKernelGGL((k_compound<true, true>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((k_compound<true, false>), grid, blk, 0, st, a);
     return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -396,9 +397,9 @@ inline F3 rot(F3 v, F3 ax, float ang)   // btVector3::rotate
 }
 }  // namespace
 
-extern "C" int mcrt_transducer_elements(uint32_t n, double radius_cm, double sep_mm, const float position[3], const float angles_deg[3], float *pos, float *dir)
+// transducer.h:24-62; steer (mcrt_transducer_steered) tilts the directions alone: the beams pivot on their elements
+static void transducer_tables(uint32_t n, double radius_cm, double sep_mm, const float position[3], const float angles_deg[3], float steer, float *pos, float *dir)
 {
-    if (!pos || !dir || !position || !angles_deg || n == 0) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_transducer_elements: bad arguments");
     const double pi = 3.14159265358979323846264338327950288419716939937510;   // units.h:360
     const double xa = (angles_deg[0] * pi * 1.0) / 180.0, ya = (angles_deg[1] * pi * 1.0) / 180.0, za = (angles_deg[2] * pi * 1.0) / 180.0;
     const float amp = (float)(((sep_mm / radius_cm) * 1.0) / 10.0);   // mm/cm -> scalar
@@ -412,9 +413,34 @@ extern "C" int mcrt_transducer_elements(uint32_t n, double radius_cm, double sep
         d = rot(d, F3{ 1, 0, 0 }, (float)xa);
         d = rot(d, F3{ 0, 1, 0 }, (float)ya);
         pos[3 * t] = position[0] + rf * d.x; pos[3 * t + 1] = position[1] + rf * d.y; pos[3 * t + 2] = position[2] + rf * d.z;
+        if (steer != 0.0f) {
+            const float as = (float)(angle + (double)steer);
+            d = F3{ std::sin(as), std::cos(as), 0.f };
+            d = rot(d, F3{ 0, 0, 1 }, (float)za);
+            d = rot(d, F3{ 1, 0, 0 }, (float)xa);
+            d = rot(d, F3{ 0, 1, 0 }, (float)ya);
+        }
         dir[3 * t] = d.x; dir[3 * t + 1] = d.y; dir[3 * t + 2] = d.z;
         angle = angle + amplitude;
     }
+}
+
+extern "C" int mcrt_transducer_elements(uint32_t n, double radius_cm, double sep_mm, const float position[3], const float angles_deg[3], float *pos, float *dir)
+{
+    if (!pos || !dir || !position || !angles_deg || n == 0) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_transducer_elements: bad arguments");
+    transducer_tables(n, radius_cm, sep_mm, position, angles_deg, 0.0f, pos, dir);
+    return MCRT_OK;
+}
+
+// ---- spatial compounding (the contracts are in include/mcrt.h) ----------------------------------
+static bool steer_ok(float s) { return std::isfinite(s) && std::fabs((double)s) < 1.57079632679489661923; }
+
+extern "C" int mcrt_transducer_steered(uint32_t n, double radius_cm, double sep_mm, const float position[3], const float angles_deg[3], float steer_rad,
+                                       float *pos, float *dir)
+{
+    if (!pos || !dir || !position || !angles_deg || n == 0) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_transducer_steered: bad arguments");
+    if (!steer_ok(steer_rad)) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_transducer_steered: steer_rad must be finite and |steer| < pi/2 (%g)", (double)steer_rad);
+    transducer_tables(n, radius_cm, sep_mm, position, angles_deg, steer_rad, pos, dir);
     return MCRT_OK;
 }
 
@@ -529,6 +555,37 @@ extern "C" int mcrt_scan_maps(uint32_t E, uint32_t R, double radius_mm, double t
             const double angle = (double)std::atan2(fj, fi);
             map_row[(size_t)i * ocols + j] = (r * ratio - radius_f) / depth_mm_f * (float)R;
             map_col[(size_t)i * ocols + j] = (float)(((angle - (-total_angle / 2)) / total_angle) * (double)(float)E);
+        }
+    return MCRT_OK;
+}
+
+// mcrt_scan_maps for a view whose beams are tilted by steer_rad (include/mcrt.h): the pixel grid is mcrt_scan_maps' own floats, the
+// inverse of P = radius u(phi) + t u(phi + steer) is evaluated in double and rounded once
+extern "C" int mcrt_compound_maps(uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t max_travel_us, uint32_t speed_of_sound,
+                                  uint32_t orows, uint32_t ocols, float steer_rad, float *map_row, float *map_col)
+{
+    if (!map_row || !map_col || E == 0 || R == 0 || orows == 0 || ocols == 0 || !(total_angle > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_compound_maps: bad arguments");
+    if (!steer_ok(steer_rad)) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_compound_maps: steer_rad must be finite and |steer| < pi/2 (%g)", (double)steer_rad);
+    if (steer_rad == 0.0f) return mcrt_scan_maps(E, R, radius_mm, total_angle, max_travel_us, speed_of_sound, orows, ocols, map_row, map_col);
+    const float radius_f = (float)radius_mm, ta_f = (float)total_angle;
+    const float depth_mm_f = (float)(uint32_t)(max_travel_us * speed_of_sound) * 0.001f;
+    const float ratio = (float)(((double)(depth_mm_f + radius_f) - (double)radius_f * std::cos((double)ta_f / 2.0)) / (double)(int)orows);
+    const double shift_y = radius_mm * (double)std::cos(ta_f / 2.0f);
+    const float half_width = (float)(int)ocols / 2.0f;
+    const double steer = (double)steer_rad, q = radius_mm * std::sin(steer), along = radius_mm * std::cos(steer);
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    for (uint32_t j = 0; j < ocols; j++)
+        for (uint32_t i = 0; i < orows; i++) {
+            const float fi = (float)(int)i + (float)shift_y / ratio;
+            const float fj = (float)(int)j - half_width;
+            const double x = (double)fj * (double)ratio, y = (double)fi * (double)ratio;
+            const double rho = std::sqrt(x * x + y * y), alpha = std::atan2(x, y);
+            const size_t o = (size_t)i * ocols + j;
+            if (rho < std::fabs(q)) { map_row[o] = nan; map_col[o] = nan; continue; }   // no beam of this view passes the pixel
+            const double phi = alpha - steer + std::asin(q / rho);
+            const double t = std::sqrt(rho * rho - q * q) - along;
+            map_row[o] = (float)(t / (double)depth_mm_f * (double)R);
+            map_col[o] = (float)((phi + total_angle / 2) / total_angle * (double)(float)E);
         }
     return MCRT_OK;
 }

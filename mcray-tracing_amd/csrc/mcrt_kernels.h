@@ -8,7 +8,8 @@
 //   mcrt_path.hip    k_path (the latency form: every bounce of every path in one launch)
 //   mcrt_march.hip   k_march (RF accumulation of the segments), k_material_table
 //   mcrt_post.hip    k_finalize, k_clear_flags, k_conv_* (k_conv_lateral_rows: focal zones), k_elevation (slice thickness), k_envelope, k_remap, k_transpose, k_blocks_to_frames
-//   mcrt_display.hip k_bmode_peak, k_bmode_grey, k_bmode (mcrt_bmode_frames: log-compressed 8-bit B-mode frames)
+//   mcrt_display.hip k_bmode_peak, k_bmode_grey, k_bmode (mcrt_bmode_frames: log-compressed 8-bit B-mode frames), k_compound (spatial compounding:
+//                    mcrt_compound_frames, mcrt_bmode_compound_frames)
 //   mcrt_scene.hip   k_tris_by_id, k_expand_tris; the probes k_math_probe, k_verify_div, k_philox_probe
 //   mcrt_lbvh.hip    the device BVH builder (mcrt_lbvh.h)
 // Shared device code: mcrt_device.h (primitives and the knobs more than one unit reads), mcrt_walk.h (the lane walk's steps, also k_path's),
@@ -76,6 +77,17 @@ struct BmodeArgs {
     uint32_t E, R, n, F, frames_per_chunk, reset;
 };
 
+// k_compound (mcrt_compound_frames / mcrt_bmode_compound_frames): the views [F][N][E][R] (RF floats, or the grey levels of k_bmode_grey)
+// -> floats or bytes [F][n], n = out_rows * out_cols
+struct CompoundArgs {
+    const float *src;                   // [F][N][E][R]
+    const float *maps;                  // [N][2][n_pad] the context's compound maps: per view the column map, then the row map, zero-padded to n_pad = n rounded up to 256
+    float *state;                       // [n] persistence state, or null (8-bit form only)
+    void *out;                          // float or uint8_t [F][n]
+    float alpha;
+    uint32_t E, R, n, n_pad, F, N, frames_per_chunk, reset;
+};
+
 hipError_t launch_init(const FrameArgs &a, hipStream_t st);
 hipError_t launch_trace(const FrameArgs &a, uint32_t b, bool stats, hipStream_t st);
 hipError_t launch_nodes_walk(const float4 *nodes, uint32_t n_nodes, uint4 *out, hipStream_t st);
@@ -98,6 +110,7 @@ hipError_t launch_bmode_peak(const float *rf, uint32_t F, uint32_t E, uint32_t R
 hipError_t launch_bmode_grey(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, const float *peak /*[F] or null: ref*/, float ref,
                              float *peak_out /*[F] or null*/, uint32_t mode, float gain, float dr, float *grey, hipStream_t st);
 hipError_t launch_bmode(const BmodeArgs &a, hipStream_t st);
+hipError_t launch_compound(const CompoundArgs &a, bool out8, hipStream_t st);
 hipError_t launch_blocks_to_frames(const float *blocks, float *frames, uint32_t F, uint32_t E, uint32_t R, uint32_t G, const uint32_t *off /*[G+1]*/, hipStream_t st);   // at most 64 ranks
 hipError_t launch_transpose(const float *in, float *out, uint32_t E, uint32_t R, hipStream_t st);
 hipError_t launch_math_probe(int op, const double *x, const double *y, double *out, uint32_t n, hipStream_t st);

@@ -1,7 +1,7 @@
 // mattausch_hip -- the reference's program (main.cpp:42-161) on the MI355X library:
 //     mattausch_hip <scene.json> [frames] [samples] [out.pgm] [rf.bin] [--gpus N | --devices 0,1,...]
 //                   [--db DR] [--gain G] [--ref-log] [--persistence A] [--focus-mm F1[,F2,...]] [--focal-range-mm R]
-//                   [--elevation K] [--elevation-pitch-um P] [--var-z V]
+//                   [--elevation K] [--elevation-pitch-um P] [--var-z V] [--compound N] [--compound-step-deg D]
 // --gpus N: the first N GPUs of the node, the frame's scan-lines sharded over them (mcrt_group_*: one tracing context and host thread per
 // GPU, the blocks gathered on GPU 0); --devices lists them explicitly, and may repeat one (two ranks sharing a GPU: the one-GPU test).
 // Same constants (main.cpp:23-37), same frame loop body; instead of blocking on imshow/waitKey every frame it
@@ -17,8 +17,14 @@
 // --elevation-pitch-um P apart (145) around the probe's own, as one pass, and folded with the elevation PSF of variance --var-z V (0.1 mm^2,
 // main.cpp:54; mcrt_elevation_frames) before the convolution.  Without --elevation the frame is the reference's thin sheet and the other
 // two options have no effect; --elevation 1 is that sheet again.
+// --compound N (odd, 1..15) compounds every frame from N views steered in the image plane, --compound-step-deg D apart (5) and centred on
+// the unsteered one: the views are traced as one pass, convolved and enveloped as N frames and averaged where they cover a pixel
+// (mcrt_compound_frames, or mcrt_bmode_compound_frames with a display option).  rf.bin then holds the unsteered view.  Without --compound
+// nothing changes and --compound-step-deg has no effect; --compound 1 is the plain run again.  It does not combine with --elevation here
+// (the Python Simulator does both).
 #include "mcrt_host.hpp"
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <iostream>
 
@@ -42,6 +48,8 @@ int main(int argc, char **argv)
     std::vector<float> focus_mm; float focal_range_mm = 20.0f;
     int elevation = 0; long elevation_pitch_um = 145; float var_z = 0.1f;      // elevation 0: off
     bool elevation_given = false;
+    int compound = 0; double compound_step_deg = 5.0;                         // compound 0: off
+    bool compound_given = false;
     {   // the options, taken out of the positional arguments
         int keep = 1;
         for (int i = 1; i < argc; i++) {
@@ -58,6 +66,8 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--elevation") && i + 1 < argc) { elevation = std::atoi(argv[++i]); elevation_given = true; }
             else if (!std::strcmp(argv[i], "--elevation-pitch-um") && i + 1 < argc) elevation_pitch_um = std::atol(argv[++i]);
             else if (!std::strcmp(argv[i], "--var-z") && i + 1 < argc) var_z = (float)std::atof(argv[++i]);
+            else if (!std::strcmp(argv[i], "--compound") && i + 1 < argc) { compound = std::atoi(argv[++i]); compound_given = true; }
+            else if (!std::strcmp(argv[i], "--compound-step-deg") && i + 1 < argc) compound_step_deg = std::atof(argv[++i]);
             else if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) { devices.clear(); for (int d = 0; d < std::max(1, std::atoi(argv[i + 1])); d++) devices.push_back(d); i++; }
             else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {
                 devices.clear();
@@ -77,6 +87,13 @@ int main(int argc, char **argv)
             throw std::invalid_argument("--elevation takes an odd number of planes, 1..31");
         if (elevation_given && (elevation_pitch_um < 1 || elevation_pitch_um > 0xffffffffl))
             throw std::invalid_argument("--elevation-pitch-um must be a positive number of micrometres");
+        if (compound_given && (compound < 1 || compound > 15 || compound % 2 == 0))
+            throw std::invalid_argument("--compound takes an odd number of views, 1..15");
+        if (compound_given && elevation_given) throw std::invalid_argument("--compound and --elevation do not combine in this program");
+        std::vector<float> steers;                    // centred on the unsteered view, ascending
+        for (int n = 0; n < compound; n++) steers.push_back((float)((double)(n - (compound - 1) / 2) * compound_step_deg * 3.14159265358979323846 / 180.0));
+        for (float s : steers)
+            if (!(std::isfinite(s) && std::fabs((double)s) < 1.5707963267948966)) throw std::invalid_argument("--compound-step-deg: every view must be steered by less than 90 degrees");
         const json cfg = load_json(argv[1]);
         const psf_ psf = [&] {
             psf_ p{ transducer_frequency, 0.05f, 0.2f, var_z };
@@ -97,11 +114,13 @@ int main(int argc, char **argv)
 
         const auto t0 = std::chrono::high_resolution_clock::now();
         for (int f = 0; f < frames; f++) {
-            if (elevation_given) rf_image.trace((uint32_t)f, transducer, psf, (uint32_t)elevation);   // ... in K elevation planes, folded
+            if (compound_given) rf_image.trace((uint32_t)f, transducer, steers);                    // ... in N steered views
+            else if (elevation_given) rf_image.trace((uint32_t)f, transducer, psf, (uint32_t)elevation);   // ... in K elevation planes, folded
             else rf_image.trace((uint32_t)f);      // clear + cast_rays + accumulation (main.cpp:102-144)
             rf_image.convolve(psf);           // main.cpp:146
             rf_image.envelope();              // main.cpp:147
-            if (bmode) rf_image.postprocess(display);   // main.cpp:148, log-compressed to 8-bit grey
+            if (compound_given) { if (bmode) rf_image.postprocess(display, steers); else rf_image.postprocess(steers); }   // the views averaged
+            else if (bmode) rf_image.postprocess(display);   // main.cpp:148, log-compressed to 8-bit grey
             else rf_image.postprocess();      // main.cpp:148
         }
         check(dev->synchronize(), "mcrt_synchronize");
@@ -109,7 +128,7 @@ int main(int argc, char **argv)
         std::cout << frames / dt << " frames/s, " << (double)frames * transducer_elements * samples / dt << " rays/s on " << devices.size() << " GPU context(s)" << std::endl;
         if (argc > 4) { if (bmode) rf_image.save_bmode(argv[4]); else rf_image.save(argv[4]); }
         if (argc > 5) {   // the last frame's RF image after main.cpp:146-147, row-major [465][512] float32 (for the parity test)
-            const auto img = rf_image.intensities();
+            const auto img = compound_given ? rf_image.view_intensities((uint32_t)(compound - 1) / 2u) : rf_image.intensities();
             std::ofstream f(argv[5], std::ios::binary);
             f.write((const char *)img.data(), (std::streamsize)(img.size() * sizeof(float)));
         }

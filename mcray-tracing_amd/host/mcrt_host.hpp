@@ -287,6 +287,18 @@ public:
         check(mcrt_elevation_planes(pos.data(), dir.data(), (uint32_t)transducer_elements, axis, n_planes, pitch_um, t.pos.data(), t.dir.data(), t.z_mm.data()), "transducer planes");
         return t;
     }
+    // spatial compounding: the element tables of the views of a compounded frame, one per in-plane steering angle [rad]
+    // (mcrt_transducer_steered: the beams pivot on their elements): pos / dir [views][N][3]; z_mm stays empty
+    plane_tables steered(const std::vector<float> &steer_rad) const
+    {
+        plane_tables t;
+        const size_t one = 3 * transducer_elements;
+        t.pos.resize(steer_rad.size() * one); t.dir.resize(steer_rad.size() * one);
+        for (size_t n = 0; n < steer_rad.size(); n++)
+            check(mcrt_transducer_steered((uint32_t)transducer_elements, radius_cm, separation_mm, position.v, angles.data(), steer_rad[n], t.pos.data() + n * one,
+                                          t.dir.data() + n * one), "transducer steered");
+        return t;
+    }
     void setPosition(const vec3 &p) { position = p; }
     void setAngles(const std::array<float, 3> &a) { angles = a; }
     vec3 getPosition() const { return position; }
@@ -623,6 +635,7 @@ public:
         if (bmode_dev) mcrt_free(dev->ctx, bmode_dev);
         if (state_dev) mcrt_free(dev->ctx, state_dev);
         if (planes_dev) mcrt_free(dev->ctx, planes_dev);
+        if (views_dev) mcrt_free(dev->ctx, views_dev);
     }
     rf_image(const rf_image &) = delete; rf_image &operator=(const rf_image &) = delete;
 
@@ -652,7 +665,7 @@ public:
             check(dev->set_params(&p), "mcrt_set_params");
         }
         check(dev->trace_frames(frame_id, 1, columns, rf_dev), "mcrt_trace_frame");       // (every GPU of a group traces its scan-line shard)
-        where = on_device;
+        where = on_device; n_views = 0;
     }
     // the same with slice thickness (psf.h:16-18,42,77; mcrt.h): the frame's n_planes elevation planes (0: the psf's elevation_size), spread
     // p.elevation_pitch_um() apart around the transducer's own plane, traced as ONE pose pass -- plane k with frame id frame_id * K + k, the
@@ -677,19 +690,58 @@ public:
         }
         check(dev->trace_frames_poses(frame_id * K, K, columns, tables.pos.data(), tables.dir.data(), planes_dev), "mcrt_trace_frames_poses");
         check(mcrt_elevation_frames(dev->ctx, planes_dev, 1, K, columns, max_rows, w.data(), rf_dev), "mcrt_elevation_frames");
-        where = on_device;
+        where = on_device; n_views = 0;
+    }
+    // spatial compounding (mcrt.h): the frame's views, one per steering angle [rad] of steer_rad (1..16), traced as ONE pose pass -- view n with
+    // frame id frame_id * N + n, the frame-id rule of mcrt.h -- into a stack [N][columns][max_rows] this image owns.  convolve() and envelope()
+    // then run over the N views, and the views meet in postprocess(steer_rad) / postprocess(bmode_params, steer_rad).  The RF image of
+    // trace(frame_id) is left as it is; the next trace(frame_id ...) without a steer list ends the compounded state.
+    template <size_t N> void trace(uint32_t frame_id, const transducer<N> &t, const std::vector<float> &steer_rad)
+    {
+        static_assert(N == columns, "one scan-line per transducer element");
+        const uint32_t V = (uint32_t)steer_rad.size();
+        if (V == 0 || V > 16) throw std::invalid_argument("rf_image::trace: 1..16 steering angles");
+        const auto tables = t.steered(steer_rad);
+        if ((uint64_t)frame_id * V + V > 0xffffffffull) throw std::out_of_range("rf_image::trace: frame_id * views does not fit a frame id");
+        mcrt_params prm; check(mcrt_get_params(dev->ctx, &prm), "mcrt_get_params");
+        if (prm.n_rows != max_rows || prm.n_elements != columns) {
+            prm.n_rows = max_rows; prm.n_elements = columns; prm.speed_of_sound = speed_of_sound;
+            check(dev->set_params(&prm), "mcrt_set_params");
+        }
+        const size_t need = (size_t)V * columns * max_rows;
+        if (need > views_cap) {
+            if (views_dev) { mcrt_free(dev->ctx, views_dev); views_dev = nullptr; views_cap = 0; }
+            check(mcrt_alloc(dev->ctx, sizeof(float) * need, (void **)&views_dev), "mcrt_alloc");
+            views_cap = need;
+        }
+        check(dev->trace_frames_poses(frame_id * V, V, columns, tables.pos.data(), tables.dir.data(), views_dev), "mcrt_trace_frames_poses");
+        n_views = V;
     }
     template <typename psf_> void convolve(const psf_ &p)
     {
-        to_device();
+        float *img = rf_dev; uint32_t frames = 1;
+        if (n_views) { img = views_dev; frames = n_views; }     // the views of a compounded frame as so many frames
+        else to_device();
         if (p.has_focus()) {   // focal zones: a lateral kernel per row, rows axial_resolution_um / 1000 mm apart
             const std::vector<float> &lat = p.lateral_rows(max_rows, (double)axial_resolution_um / 1000.0);
-            check(mcrt_convolve_frames_depth(dev->ctx, rf_dev, 1, columns, max_rows, p.axial_kernel.data(), (uint32_t)p.get_axial_size(), lat.data(), (uint32_t)p.get_lateral_size()), "mcrt_convolve_frames_depth");
+            check(mcrt_convolve_frames_depth(dev->ctx, img, frames, columns, max_rows, p.axial_kernel.data(), (uint32_t)p.get_axial_size(), lat.data(), (uint32_t)p.get_lateral_size()), "mcrt_convolve_frames_depth");
             return;
         }
-        check(mcrt_convolve(dev->ctx, rf_dev, columns, max_rows, p.axial_kernel.data(), (uint32_t)p.get_axial_size(), p.lateral_kernel.data(), (uint32_t)p.get_lateral_size()), "mcrt_convolve");
+        if (n_views) check(mcrt_convolve_frames(dev->ctx, img, frames, columns, max_rows, p.axial_kernel.data(), (uint32_t)p.get_axial_size(), p.lateral_kernel.data(), (uint32_t)p.get_lateral_size()), "mcrt_convolve_frames");
+        else check(mcrt_convolve(dev->ctx, rf_dev, columns, max_rows, p.axial_kernel.data(), (uint32_t)p.get_axial_size(), p.lateral_kernel.data(), (uint32_t)p.get_lateral_size()), "mcrt_convolve");
     }
-    void envelope() { to_device(); check(mcrt_envelope(dev->ctx, rf_dev, columns, max_rows), "mcrt_envelope"); }
+    void envelope()
+    {
+        if (n_views) { check(mcrt_envelope_frames(dev->ctx, views_dev, n_views, columns, max_rows), "mcrt_envelope_frames"); return; }
+        to_device(); check(mcrt_envelope(dev->ctx, rf_dev, columns, max_rows), "mcrt_envelope");
+    }
+    // the views of trace(frame, transducer, steer_rad) compounded into the float picture scan_converted() / save() read (mcrt_compound_frames):
+    // every pixel the mean of the views that cover it
+    void postprocess(const std::vector<float> &steer_rad)
+    {
+        const mcrt_compound cp = compound_of(steer_rad);
+        check(mcrt_compound_frames(dev->ctx, views_dev, 1, columns, max_rows, radius_mm, angle, &cp, scan_dev, 400, 500), "mcrt_compound_frames");
+    }
     void postprocess() { to_device(); check(mcrt_scan_convert(dev->ctx, rf_dev, columns, max_rows, radius_mm, angle, scan_dev, 400, 500), "mcrt_scan_convert"); }
     // the displayed picture instead of the float scan conversion: log compression (dynamic range, gain, TGC) and 8-bit grey on the GPU
     // (mcrt_bmode_frames; rfimage.h:131-136 planned it).  tgc_db: max_rows dB values or nullptr.  The persistence state lives here and is
@@ -699,18 +751,16 @@ public:
     void postprocess(const mcrt_bmode_params &bp, const float *tgc_db = nullptr)
     {
         to_device();
-        const size_t n = (size_t)bp.out_rows * bp.out_cols;
-        if (n != bmode_n) {
-            if (bmode_dev) { mcrt_free(dev->ctx, bmode_dev); bmode_dev = nullptr; }
-            if (state_dev) { mcrt_free(dev->ctx, state_dev); state_dev = nullptr; }
-            check(mcrt_alloc(dev->ctx, n, (void **)&bmode_dev), "mcrt_alloc");
-            check(mcrt_alloc(dev->ctx, sizeof(float) * n, (void **)&state_dev), "mcrt_alloc");
-            bmode_n = n; state_valid = false;
-        }
-        mcrt_bmode_params p = bp;
-        p.radius_mm = radius_mm; p.total_angle_rad = angle;
-        p.reset_state = (bp.reset_state || !state_valid) ? 1u : 0u;
+        const mcrt_bmode_params p = bmode_prepare(bp);
         check(mcrt_bmode_frames(dev->ctx, rf_dev, 1, columns, max_rows, &p, tgc_db, state_dev, nullptr, bmode_dev), "mcrt_bmode_frames");
+        state_valid = true; bmode_rows = bp.out_rows; bmode_cols = bp.out_cols;
+    }
+    // the same over the views of trace(frame, transducer, steer_rad) (mcrt_bmode_compound_frames): one reference per frame, the peak of all views
+    void postprocess(const mcrt_bmode_params &bp, const std::vector<float> &steer_rad, const float *tgc_db = nullptr)
+    {
+        const mcrt_compound cp = compound_of(steer_rad);
+        const mcrt_bmode_params p = bmode_prepare(bp);
+        check(mcrt_bmode_compound_frames(dev->ctx, views_dev, 1, columns, max_rows, &p, &cp, tgc_db, state_dev, nullptr, bmode_dev), "mcrt_bmode_compound_frames");
         state_valid = true; bmode_rows = bp.out_rows; bmode_cols = bp.out_cols;
     }
     std::vector<unsigned char> bmode() const   // the last postprocess(bmode_params) frame, row-major [out_rows][out_cols]
@@ -732,6 +782,13 @@ public:
         if (where == on_host) return host;
         std::vector<float> h((size_t)columns * max_rows);
         check(mcrt_export_rf(dev->ctx, rf_dev, columns, max_rows, h.data()), "mcrt_export_rf");
+        return h;
+    }
+    std::vector<float> view_intensities(uint32_t n) const   // view n of the last compounded trace, row-major [max_rows][columns]
+    {
+        if (n >= n_views) throw std::out_of_range("rf_image::view_intensities");
+        std::vector<float> h((size_t)columns * max_rows);
+        check(mcrt_export_rf(dev->ctx, views_dev + (size_t)n * columns * max_rows, columns, max_rows, h.data()), "mcrt_export_rf");
         return h;
     }
     std::vector<float> scan_converted() const
@@ -757,6 +814,30 @@ private:
     {
         if (where == on_device) { check(mcrt_export_rf(dev->ctx, rf_dev, columns, max_rows, host.data()), "mcrt_export_rf"); where = on_host; }
     }
+    // the buffers of postprocess(bmode_params ...) for bp's size, and bp with this image's sector and the reset rule applied
+    mcrt_bmode_params bmode_prepare(const mcrt_bmode_params &bp)
+    {
+        const size_t n = (size_t)bp.out_rows * bp.out_cols;
+        if (n != bmode_n) {
+            if (bmode_dev) { mcrt_free(dev->ctx, bmode_dev); bmode_dev = nullptr; }
+            if (state_dev) { mcrt_free(dev->ctx, state_dev); state_dev = nullptr; }
+            check(mcrt_alloc(dev->ctx, n, (void **)&bmode_dev), "mcrt_alloc");
+            check(mcrt_alloc(dev->ctx, sizeof(float) * n, (void **)&state_dev), "mcrt_alloc");
+            bmode_n = n; state_valid = false;
+        }
+        mcrt_bmode_params p = bp;
+        p.radius_mm = radius_mm; p.total_angle_rad = angle;
+        p.reset_state = (bp.reset_state || !state_valid) ? 1u : 0u;
+        return p;
+    }
+    mcrt_compound compound_of(const std::vector<float> &steer_rad) const
+    {
+        if (n_views == 0 || steer_rad.size() != n_views) throw std::invalid_argument("rf_image::postprocess: the steer list is not the one the views were traced with");
+        mcrt_compound cp{};
+        cp.n_views = n_views;
+        for (uint32_t n = 0; n < n_views; n++) cp.steer_rad[n] = steer_rad[n];
+        return cp;
+    }
     double radius_mm, angle;
     std::vector<float> host;                     // [max_rows][columns]
     enum { on_host, on_device } where = on_host;
@@ -764,6 +845,7 @@ private:
     unsigned char *bmode_dev = nullptr; float *state_dev = nullptr;   // postprocess(bmode_params): the 8-bit frame and the persistence state
     size_t bmode_n = 0; uint32_t bmode_rows = 0, bmode_cols = 0; bool state_valid = false;
     float *planes_dev = nullptr; size_t planes_n = 0;                 // trace(frame, transducer, psf): the plane stack [K][columns][max_rows], grown to the largest K
+    float *views_dev = nullptr; size_t views_cap = 0; uint32_t n_views = 0;   // trace(frame, transducer, steer_rad): the views [N][columns][max_rows]; n_views > 0: compounded
 };
 
 }  // namespace mcrt_host
