@@ -256,6 +256,30 @@ class Psf:
 
 
 # ------------------------------------------------------------------ C-ABI context
+def _scene_tables(sd):
+    """(mcrt_mesh records, their count, spacing float32 [3]) of a scene, as mcrt_upload_scene / mcrt_group_upload_scene take them"""
+    meshes = (MeshRec * len(sd.meshes))(*[MeshRec(a, b, c, 0) for a, b, c in sd.meshes])
+    return meshes, len(sd.meshes), np.asarray(sd.spacing, np.float32)
+
+
+def _tri9(tri):
+    """(triangles, their count) of new vertex positions [T,9]: a numpy array is made contiguous float32, a CUDA torch tensor goes as it is"""
+    if isinstance(tri, np.ndarray):
+        tri = np.ascontiguousarray(tri, np.float32).reshape(-1, 9)
+        return tri, tri.shape[0]
+    return tri, tri.numel() // 9
+
+
+def _tgc_rows(tgc_db, n_rows):
+    """the TGC curve as float32 [n_rows], or None"""
+    if tgc_db is None:
+        return None
+    tgc = np.ascontiguousarray(tgc_db, np.float32)
+    if tgc.shape != (n_rows,):
+        raise ValueError("tgc_db needs one value per RF row: %d, got shape %s" % (n_rows, tgc.shape))
+    return tgc
+
+
 class Context:
     def __init__(self, device=0, _borrowed=None):
         self.L = load_library()
@@ -305,9 +329,8 @@ class Context:
         check(self.L.mcrt_debug_set_error(self.h, int(bits)))
 
     def upload_scene(self, sd):
-        meshes = (MeshRec * len(sd.meshes))(*[MeshRec(a, b, c, 0) for a, b, c in sd.meshes])
-        sp = np.asarray(sd.spacing, np.float32)
-        check(self.L.mcrt_upload_scene(self.h, ptr(sd.tri), ptr(sd.tri_mesh), sd.n_tri, C.cast(meshes, C.c_void_p), len(sd.meshes),
+        meshes, n_mesh, sp = _scene_tables(sd)
+        check(self.L.mcrt_upload_scene(self.h, ptr(sd.tri), ptr(sd.tri_mesh), sd.n_tri, C.cast(meshes, C.c_void_p), n_mesh,
                                        ptr(sd.materials), sd.materials.shape[0], sd.start_mat, ptr(sp)))
 
     def set_bvh_builder(self, builder):
@@ -317,20 +340,12 @@ class Context:
 
     def update_triangles(self, tri):
         """new vertex positions [T,9] (numpy array, or a CUDA torch tensor) for the uploaded scene's triangles"""
-        if isinstance(tri, np.ndarray):
-            tri = np.ascontiguousarray(tri, np.float32).reshape(-1, 9)
-            n = tri.shape[0]
-        else:
-            n = tri.numel() // 9
+        tri, n = _tri9(tri)
         check(self.L.mcrt_update_triangles(self.h, ptr(tri), n))
 
     def refit_triangles(self, tri):
         """new vertex positions [T,9] for the uploaded triangles, keeping the tree: boxes are refitted on the GPU"""
-        if isinstance(tri, np.ndarray):
-            tri = np.ascontiguousarray(tri, np.float32).reshape(-1, 9)
-            n = tri.shape[0]
-        else:
-            n = tri.numel() // 9
+        tri, n = _tri9(tri)
         check(self.L.mcrt_refit_triangles(self.h, ptr(tri), n))
 
     def upload_texture(self, vox=None, n=256):
@@ -453,11 +468,7 @@ class Context:
         mode "db" or "ref_log"; ref None (or <= 0): each frame's own peak; tgc_db: dB per RF row (n_rows values) or None."""
         p = bmode_params(mode=mode, dynamic_range_db=dynamic_range_db, gain_db=gain_db, ref=ref, persistence=persistence, reset_state=reset_state,
                          radius_mm=radius_mm, total_angle=total_angle, out_rows=out_rows, out_cols=out_cols)
-        tgc = None
-        if tgc_db is not None:
-            tgc = np.ascontiguousarray(tgc_db, np.float32)
-            if tgc.shape != (n_rows,):
-                raise ValueError("tgc_db needs one value per RF row: %d, got shape %s" % (n_rows, tgc.shape))
+        tgc = _tgc_rows(tgc_db, n_rows)
         check(self.L.mcrt_bmode_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(p), ptr(tgc), ptr(state_dev), ptr(peak_dev), ptr(out_dev)))
 
     def compound_frames(self, rf_dev, n_frames, n_elements, n_rows, steer_rad, out_dev, radius_mm=30.0, total_angle=1.0471975511965976, out_rows=400, out_cols=500):
@@ -474,11 +485,7 @@ class Context:
         p = bmode_params(mode=mode, dynamic_range_db=dynamic_range_db, gain_db=gain_db, ref=ref, persistence=persistence, reset_state=reset_state,
                          radius_mm=radius_mm, total_angle=total_angle, out_rows=out_rows, out_cols=out_cols)
         cp = compound_struct(steer_rad)
-        tgc = None
-        if tgc_db is not None:
-            tgc = np.ascontiguousarray(tgc_db, np.float32)
-            if tgc.shape != (n_rows,):
-                raise ValueError("tgc_db needs one value per RF row: %d, got shape %s" % (n_rows, tgc.shape))
+        tgc = _tgc_rows(tgc_db, n_rows)
         check(self.L.mcrt_bmode_compound_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(p), C.byref(cp), ptr(tgc), ptr(state_dev),
                                                 ptr(peak_dev), ptr(out_dev)))
 
@@ -578,9 +585,8 @@ class Group:
         check(self.L.mcrt_group_set_bvh_builder(self.h, kind))
 
     def upload_scene(self, sd):
-        meshes = (MeshRec * len(sd.meshes))(*[MeshRec(a, b, c, 0) for a, b, c in sd.meshes])
-        sp = np.asarray(sd.spacing, np.float32)
-        check(self.L.mcrt_group_upload_scene(self.h, ptr(sd.tri), ptr(sd.tri_mesh), sd.n_tri, C.cast(meshes, C.c_void_p), len(sd.meshes),
+        meshes, n_mesh, sp = _scene_tables(sd)
+        check(self.L.mcrt_group_upload_scene(self.h, ptr(sd.tri), ptr(sd.tri_mesh), sd.n_tri, C.cast(meshes, C.c_void_p), n_mesh,
                                              ptr(sd.materials), sd.materials.shape[0], sd.start_mat, ptr(sp)))
 
     def update_triangles(self, tri):

@@ -1,8 +1,9 @@
 // mcrt_api.cpp -- the C-ABI of include/mcrt.h: context, uploads, frame orchestration.
-// Host C++ only; kernels live in the mcrt_*.hip files (map: mcrt_kernels.h).  No CPU fallback exists: every compute entry point
-// needs the GPU context.
+// Host C++ only; kernels live in the mcrt_*.hip files (map: mcrt_kernels.h), the owners of the HIP resources in mcrt_hip.h.  No CPU
+// fallback exists: every compute entry point needs the GPU context.
 #include "../../include/mcrt.h"
 #include "mcrt_internal.h"
+#include "mcrt_hip.h"
 #include "mcrt_kernels.h"
 #include "mcrt_lbvh.h"
 
@@ -20,45 +21,7 @@
 
 using mcrt::set_error;
 
-// (an allocation the device cannot satisfy is MCRT_ERR_NOMEM, every other HIP failure MCRT_ERR_HIP)
-#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipGetLastError(); return set_error(e_ == hipErrorOutOfMemory ? MCRT_ERR_NOMEM : MCRT_ERR_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } } while (0)
 #define CTX_TRY(ctx) do { if (!(ctx)) return set_error(MCRT_ERR_INVALID, "null context"); HIP_TRY(hipSetDevice((ctx)->device)); } while (0)
-
-// Owners of the context's HIP resources, released in their destructors (on the current device: the context's, see mcrt_destroy).
-// A buffer holds `cap` elements.  alloc(n) replaces it by one of exactly n, grow(n) only when n exceeds the capacity; on failure it
-// holds nothing.  Neither waits: whatever may still use the old buffer is waited for by the caller, who knows which wait that is.
-template <class T, bool Pinned = false> struct Buf {
-    T *p = nullptr; size_t cap = 0;
-    Buf() = default;
-    Buf(const Buf &) = delete; Buf &operator=(const Buf &) = delete;
-    Buf(Buf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); }
-    Buf &operator=(Buf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
-    ~Buf() { reset(); }
-    void reset() { if (p) { if (Pinned) hipHostFree(p); else hipFree(p); } p = nullptr; cap = 0; }
-    void adopt(T *q, size_t n) { reset(); p = q; cap = q ? n : 0; }
-    hipError_t alloc(size_t n)
-    {
-        reset();
-        if (n == 0) return hipSuccess;
-        const hipError_t e = Pinned ? hipHostMalloc((void **)&p, sizeof(T) * n, hipHostMallocDefault) : hipMalloc((void **)&p, sizeof(T) * n);
-        if (e != hipSuccess) p = nullptr; else cap = n;
-        return e;
-    }
-    hipError_t grow(size_t n) { return n > cap ? alloc(n) : hipSuccess; }
-    operator T *() const { return p; }
-};
-template <class T> using PinnedBuf = Buf<T, true>;
-template <class H, hipError_t (*Destroy)(H)> struct Handle {   // an event or a stream: created by the caller into .h
-    H h = nullptr;
-    Handle() = default;
-    Handle(const Handle &) = delete; Handle &operator=(const Handle &) = delete;
-    Handle(Handle &&o) noexcept { std::swap(h, o.h); }
-    Handle &operator=(Handle &&o) noexcept { std::swap(h, o.h); return *this; }
-    ~Handle() { if (h) Destroy(h); }
-    operator H() const { return h; }
-};
-using Event = Handle<hipEvent_t, hipEventDestroy>;
-using Stream = Handle<hipStream_t, hipStreamDestroy>;
 
 struct Consts {   // main.cpp:23-37, rfimage.h:48-51,178-180 evaluated at run time
     float axial_res_f; double axial_res_mm, time_step_us, row_dt_us, max_travel_us; uint32_t axial_res_um, max_rows;
@@ -132,6 +95,46 @@ static Knobs read_knobs()
     return k;
 }
 
+// A float table [R][n] that a caller hands over as HOST memory with every call, on the device as [n][R] (n == 1: as it is), uploaded only
+// when its bits or its shape differ from what is there.  put() is the whole contract: the device buffer, the pinned staging and the event
+// are made on first use, all or none; the comparison is bitwise, on the caller's layout; the staging buffer is rewritten only after the
+// previous copy's event; the table has no shape until its copy is enqueued; nothing else waits for the device; and the caller's array is
+// free the moment put() returns.
+struct StagedTable {
+    Buf<float> dev; PinnedBuf<float> pin; Event ev; bool pending = false;
+    std::vector<float> on_dev; uint32_t key[2] = { 0, 0 };   // what the device holds (or is about to): the caller's bits, and R, n
+    int put(const float *src, uint32_t R, uint32_t n, size_t room, hipStream_t st)   // room: floats of the largest table this one may be given
+    {
+        if (!dev) {
+            Buf<float> d; PinnedBuf<float> h; Event e;
+            HIP_TRY(d.alloc(room));
+            HIP_TRY(h.alloc(room));
+            HIP_TRY(ensure_event(e));
+            dev = std::move(d); pin = std::move(h); ev = std::move(e);
+            on_dev.assign(room, 0.0f); key[0] = key[1] = 0;
+        }
+        const size_t len = (size_t)n * R;
+        if (key[0] == R && key[1] == n && !memcmp(src, on_dev.data(), 4 * len)) return MCRT_OK;
+        if (pending) HIP_TRY(hipEventSynchronize(ev));   // the staging buffer still feeds the previous table's copy
+        for (uint32_t r = 0; r < R; r++)
+            for (uint32_t k = 0; k < n; k++) pin[(size_t)k * R + r] = src[(size_t)r * n + k];
+        key[0] = key[1] = 0;
+        HIP_TRY(hipMemcpyAsync(dev, pin, 4 * len, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(ev, st));
+        pending = true;
+        memcpy(on_dev.data(), src, 4 * len);
+        key[0] = R; key[1] = n;
+        return MCRT_OK;
+    }
+};
+
+// The scan-conversion maps of a geometry on the device, [N][2][n_pad]: per view the column map, then the row map; n_pad = out_rows * out_cols
+// rounded up to 256 floats and zero-padded, so every map is 16-byte aligned.  Filled by ensure_maps, which owns the key.
+struct MapCache {
+    Buf<float> d; uint32_t key[7] = {}; double keyd[3] = {}; uint32_t steer[16] = {};
+    static size_t pad(size_t n) { return (n + 255u) & ~(size_t)255u; }
+};
+
 struct TimedLaunch { Event start, end; int kind = 0; };   // kind 0: the walk (k_trace*, k_path), 1: k_shade, 2: k_march
 
 struct mcrt_ctx {
@@ -177,20 +180,14 @@ struct mcrt_ctx {
     float last_lean_bound = 0.0f; uint32_t last_march_rows = 0;   // what the last frame's kernels were given (mcrt_debug_fast_paths)
     // per-material table of k_march (depends on the materials, the axial step and the frequency)
     Buf<float4> d_mtab; float mtab_key[2] = { 0.0f, 0.0f }; bool mtab_valid = false;
-    // scan-conversion maps
-    Buf<float> d_map_col, d_map_row; uint32_t map_key[6] = { 0, 0, 0, 0, 0, 0 }; double map_keyd[3] = { 0, 0, 0 };
-    // spatial compounding (mcrt_compound_frames, mcrt_bmode_compound_frames): the N map pairs of a geometry and a steer list, [N][2][n_pad] (per view
-    // the column map, then the row map; n_pad = out_rows * out_cols rounded up to 256, zero-padded), in a buffer of their own beside the plain maps
-    Buf<float> d_cmaps; uint32_t cmap_key[7] = { 0, 0, 0, 0, 0, 0, 0 }; double cmap_keyd[3] = { 0, 0, 0 }; uint32_t cmap_steer[16] = {};
-    // B-mode display (mcrt_bmode_frames): device TGC factors [MCRT_MAX_ROWS] + the peaks of a pass [65535] in one buffer, the factors' pinned
-    // staging and the curve now on the device (its upload is waited for only when the next curve differs)
-    Buf<float> d_disp; PinnedBuf<float> h_tgc; std::vector<float> tgc_on_dev; Event ev_tgc; bool tgc_copy_pending = false;
-    // focal zones (mcrt_convolve_frames_depth): the device table [n_lat][R] (room for MCRT_MAX_ROWS x 32), its pinned staging, and the
-    // table now on the device with its shape (its upload is waited for only when the next table differs)
-    Buf<float> d_lat_rows; PinnedBuf<float> h_lat_rows; std::vector<float> lat_on_dev; uint32_t lat_key[2] = { 0, 0 }; Event ev_lat; bool lat_copy_pending = false;
-    // slice thickness (mcrt_elevation_frames): the elevation table [K][R] (room for 32 x MCRT_MAX_ROWS) under the same scheme, in buffers of
-    // its own -- a frame uses this table and the focal zones' in turn, and one shared buffer would upload both on every frame
-    Buf<float> d_elev_rows; PinnedBuf<float> h_elev_rows; std::vector<float> elev_on_dev; uint32_t elev_key[2] = { 0, 0 }; Event ev_elev; bool elev_copy_pending = false;
+    // scan-conversion maps: of the plain geometry (mcrt_scan_convert_frames, mcrt_bmode_frames; one unsteered view) and of a steer list (spatial
+    // compounding: mcrt_compound_frames, mcrt_bmode_compound_frames), each in a cache of its own so that alternating calls do not evict each other
+    MapCache maps, cmaps;
+    // B-mode display (mcrt_bmode_frames): the peaks of a pass [65536], and the TGC factors [R] of the last curve
+    Buf<float> d_disp; StagedTable tgc;
+    // focal zones (mcrt_convolve_frames_depth): the lateral taps [n_lat][R], and slice thickness (mcrt_elevation_frames): the elevation weights
+    // [K][R] (room for MCRT_MAX_ROWS x 32 each).  Two tables: a frame uses both in turn, and one shared buffer would upload both on every frame
+    StagedTable lat_rows, elev_rows;
     // instrumentation
     Buf<unsigned long long> d_stats; bool stats_on = false;
     bool timing_on = false; int timing_level = 0;       // 1: the walk's launches are bracketed by HIP events; 2: k_shade's and k_march's too
@@ -203,7 +200,7 @@ static int prepare_tables(mcrt_ctx *c)
 {
     if (c->thr_rows != c->p.n_rows || c->thr_dt != c->c.row_dt_us || !c->d_row_thr) {
         std::vector<double> thr((size_t)c->p.n_rows + 1);
-        { int rc = mcrt_row_thresholds(c->c.row_dt_us, c->p.n_rows, thr.data()); if (rc) return rc; }
+        MCRT_TRY(mcrt_row_thresholds(c->c.row_dt_us, c->p.n_rows, thr.data()));
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->thr_rows = 0;
         HIP_TRY(c->d_row_thr.alloc(thr.size()));
@@ -272,7 +269,7 @@ extern "C" int mcrt_create(int device, mcrt_ctx **out)
     if (prop.multiProcessorCount > 0) c->n_cu = (uint32_t)prop.multiProcessorCount;
     HIP_TRY(hipStreamCreateWithFlags(&c->own_stream.h, hipStreamNonBlocking));
     c->stream = c->own_stream;
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_start.h, hipEventDisableTiming));
+    HIP_TRY(ensure_event(c->ev_start));
     c->work.reserve(16);   // pointers into this vector are held across get_work() calls; never more than 16 groups
     mcrt_default_params(&c->p);
     c->c = derive_consts(c->p);
@@ -281,7 +278,7 @@ extern "C" int mcrt_create(int device, mcrt_ctx **out)
     HIP_TRY(c->d_error.alloc(1));
     HIP_TRY(hipMemsetAsync(c->d_error, 0, 4, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    { int rc = prepare_tables(c.get()); if (rc) return rc; }
+    MCRT_TRY(prepare_tables(c.get()));
     *out = c.release();
     return MCRT_OK;
 }
@@ -293,9 +290,9 @@ static int get_work(mcrt_ctx *c, size_t g, Work **out)
 {
     while (c->work.size() <= g) {
         Work w;
-        for (Event &e : w.ev_join) HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
-        for (Event &e : w.ev_bounce) HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&w.ev_done.h, hipEventDisableTiming));
+        for (Event &e : w.ev_join) HIP_TRY(ensure_event(e));
+        for (Event &e : w.ev_bounce) HIP_TRY(ensure_event(e));
+        HIP_TRY(ensure_event(w.ev_done));
         c->work.push_back(std::move(w));
     }
     *out = &c->work[g];
@@ -342,7 +339,7 @@ static int refresh_soa(mcrt_ctx *c)
         HIP_TRY(c->d_tris_id.alloc(MCRT_TRI_PIECES * (size_t)c->bvh.n_tri));
     }
     HIP_TRY(mcrt::launch_tris_by_id((const float4 *)c->d_tris, c->bvh.n_tri, c->d_tris_id, c->stream));
-    if (!c->ev_scene) HIP_TRY(hipEventCreateWithFlags(&c->ev_scene.h, hipEventDisableTiming));
+    HIP_TRY(ensure_event(c->ev_scene));
     HIP_TRY(hipEventRecord(c->ev_scene, c->stream));
     c->scene_stream = c->stream; c->scene_pending = true;
     return MCRT_OK;
@@ -412,7 +409,9 @@ static int index_triangles(mcrt_ctx *c, const float *tri, uint32_t n_tri, const 
     c->d_nodes.reset(); c->d_tris.reset(); c->d_tri_slot.reset();
     mcrt_free_bvh(&c->bvh); mcrt_free_bvh4(&c->bvh4);
     c->host_bvh_stale = false;
-    if (c->builder == MCRT_BVH_DEVICE_LBVH) {
+    const bool on_device = c->builder == MCRT_BVH_DEVICE_LBVH;
+    Buf<float4> leaf;                                   // the builder's 48-byte leaf-order triangle array, on the device
+    if (on_device) {
         mcrt::LbvhResult r;
         {
             Buf<float> d_tri; Buf<uint32_t> d_mesh;
@@ -421,71 +420,51 @@ static int index_triangles(mcrt_ctx *c, const float *tri, uint32_t n_tri, const 
             if (hipMemcpyAsync(d_tri, tri, 36 * (size_t)n_tri, hipMemcpyDefault, c->stream) != hipSuccess ||
                 hipMemcpyAsync(d_mesh, c->tri_mesh.data(), 4 * (size_t)n_tri, hipMemcpyHostToDevice, c->stream) != hipSuccess)
                 return set_error(MCRT_ERR_HIP, "triangle upload failed");
-            int rc = mcrt::lbvh_build(d_tri, d_mesh, n_tri, c->stream, &r);
-            if (rc) return rc;
+            MCRT_TRY(mcrt::lbvh_build(d_tri, d_mesh, n_tri, c->stream, &r));
         }
-        c->d_nodes.adopt(r.d_nodes, 8 * (size_t)r.n_nodes4); c->d_tri_slot.adopt(r.d_tri_slot, n_tri);
-        {   // the walk's 64-byte records from the builder's 48-byte leaf-order array
-            Buf<float4> leaf; leaf.adopt(r.d_tris, 3 * (size_t)n_tri);
-            HIP_TRY(c->d_tris.alloc(MCRT_TRI_PIECES * (size_t)n_tri));
-            HIP_TRY(mcrt::launch_expand_tris(leaf, n_tri, c->d_tris, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        }
+        c->d_nodes = std::move(r.nodes); c->d_tri_slot = std::move(r.tri_slot); leaf = std::move(r.tris);
         c->bvh.n_nodes = 0; c->bvh.n_tri = n_tri; c->bvh.max_depth = r.max_depth; c->bvh.pad_abs = r.pad_abs; c->bvh.nodes = nullptr; c->bvh.tri = nullptr;
         c->bvh4.n_nodes = r.n_nodes4; c->bvh4.max_stack = r.max_stack; c->bvh4.nodes = nullptr;
         c->host_bvh_stale = true;
         for (int i = 0; i < 3; i++) { c->scene_lo[i] = r.lo[i]; c->scene_hi[i] = r.hi[i]; }
-        if (c->bvh4.max_stack > MCRT_STACK)
-            return set_error(MCRT_ERR_LIMIT, "device-built BVH4 needs a %u-entry traversal stack, the kernel has %d", c->bvh4.max_stack, MCRT_STACK);
-        if (c->bvh4.n_nodes >= (1u << 25)) return set_error(MCRT_ERR_LIMIT, "%u BVH4 nodes: the walk addresses at most 2^25", c->bvh4.n_nodes);
-        return MCRT_OK;
-    }
-    std::vector<float> host_copy;
-    if (!pre) {   // the host builder reads host memory
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, tri) == hipSuccess && at.type == hipMemoryTypeDevice) {
+    } else if (pre) {
+        if (pre->bvh->n_tri != n_tri) return set_error(MCRT_ERR_INVALID, "prebuilt tree has %u triangles, the scene %u", pre->bvh->n_tri, n_tri);
+        MCRT_TRY(copy_tree(*pre, &c->bvh, &c->bvh4));
+    } else {
+        std::vector<float> host_copy;
+        if (is_device_pointer(tri)) {   // the host builder reads host memory
             host_copy.resize((size_t)n_tri * 9);
             HIP_TRY(hipMemcpy(host_copy.data(), tri, 36 * (size_t)n_tri, hipMemcpyDeviceToHost));
             tri = host_copy.data();
-        } else (void)hipGetLastError();
-    }
-    int rc;
-    if (pre) {
-        if (pre->bvh->n_tri != n_tri) return set_error(MCRT_ERR_INVALID, "prebuilt tree has %u triangles, the scene %u", pre->bvh->n_tri, n_tri);
-        rc = copy_tree(*pre, &c->bvh, &c->bvh4);
-        if (rc) return rc;
-    } else {
-        rc = mcrt_build_bvh(tri, c->tri_mesh.data(), n_tri, &c->bvh);
-        if (rc) return rc;
-        rc = mcrt_build_bvh4(&c->bvh, &c->bvh4);
-        if (rc) return rc;
-    }
-    for (int i = 0; i < 3; i++) { c->scene_lo[i] = INFINITY; c->scene_hi[i] = -INFINITY; }
-    for (int k = 0; k < 4; k++) {
-        const mcrt_bvh4_child &ch = c->bvh4.nodes[0].c[k];
-        if (ch.ref == MCRT_BVH4_EMPTY) continue;
-        const float hi[3] = { ch.hi_x, ch.hi_y, ch.hi_z };
-        for (int i = 0; i < 3; i++) { c->scene_lo[i] = std::min(c->scene_lo[i], ch.lo[i]); c->scene_hi[i] = std::max(c->scene_hi[i], hi[i]); }
+        }
+        MCRT_TRY(mcrt_build_bvh(tri, c->tri_mesh.data(), n_tri, &c->bvh));
+        MCRT_TRY(mcrt_build_bvh4(&c->bvh, &c->bvh4));
     }
     if (c->bvh4.max_stack > MCRT_STACK)
-        return set_error(MCRT_ERR_LIMIT, "BVH4 needs a %u-entry traversal stack, the kernel has %d", c->bvh4.max_stack, MCRT_STACK);
+        return set_error(MCRT_ERR_LIMIT, "%sBVH4 needs a %u-entry traversal stack, the kernel has %d", on_device ? "device-built " : "", c->bvh4.max_stack, MCRT_STACK);
     if (c->bvh4.n_nodes >= (1u << 25)) return set_error(MCRT_ERR_LIMIT, "%u BVH4 nodes: the walk addresses at most 2^25", c->bvh4.n_nodes);
-    HIP_TRY(c->d_nodes.alloc(sizeof(mcrt_bvh4_node) / 16 * (size_t)c->bvh4.n_nodes));
-    HIP_TRY(hipMemcpy(c->d_nodes, c->bvh4.nodes, sizeof(mcrt_bvh4_node) * (size_t)c->bvh4.n_nodes, hipMemcpyHostToDevice));
-    {   // the walk's 64-byte records from the builder's 48-byte leaf-order array
-        Buf<float4> d_in;
-        HIP_TRY(d_in.alloc(3 * (size_t)n_tri));
-        HIP_TRY(c->d_tris.alloc(MCRT_TRI_PIECES * (size_t)n_tri));
-        HIP_TRY(hipMemcpy(d_in, c->bvh.tri, 48 * (size_t)n_tri, hipMemcpyHostToDevice));
-        HIP_TRY(mcrt::launch_expand_tris(d_in, n_tri, c->d_tris, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    {   // triangle id -> leaf-order slot (k_shade re-derives the winning triangle's normal from its vertices)
+    if (!on_device) {   // the host-built tree: its bounds, and its arrays go to the device
+        for (int i = 0; i < 3; i++) { c->scene_lo[i] = INFINITY; c->scene_hi[i] = -INFINITY; }
+        for (int k = 0; k < 4; k++) {
+            const mcrt_bvh4_child &ch = c->bvh4.nodes[0].c[k];
+            if (ch.ref == MCRT_BVH4_EMPTY) continue;
+            const float hi[3] = { ch.hi_x, ch.hi_y, ch.hi_z };
+            for (int i = 0; i < 3; i++) { c->scene_lo[i] = std::min(c->scene_lo[i], ch.lo[i]); c->scene_hi[i] = std::max(c->scene_hi[i], hi[i]); }
+        }
+        HIP_TRY(c->d_nodes.alloc(sizeof(mcrt_bvh4_node) / 16 * (size_t)c->bvh4.n_nodes));
+        HIP_TRY(hipMemcpy(c->d_nodes, c->bvh4.nodes, sizeof(mcrt_bvh4_node) * (size_t)c->bvh4.n_nodes, hipMemcpyHostToDevice));
+        HIP_TRY(leaf.alloc(3 * (size_t)n_tri));
+        HIP_TRY(hipMemcpy(leaf, c->bvh.tri, 48 * (size_t)n_tri, hipMemcpyHostToDevice));
+        // triangle id -> leaf-order slot (k_shade re-derives the winning triangle's normal from its vertices)
         std::vector<uint32_t> slot(n_tri);
         for (uint32_t k = 0; k < n_tri; k++) { uint32_t id; memcpy(&id, &c->bvh.tri[(size_t)k * 12 + 3], 4); slot[id] = k; }
         HIP_TRY(c->d_tri_slot.alloc(n_tri));
         HIP_TRY(hipMemcpy(c->d_tri_slot, slot.data(), 4 * (size_t)n_tri, hipMemcpyHostToDevice));
     }
+    // the walk's 64-byte records from the builder's 48-byte leaf-order array
+    HIP_TRY(c->d_tris.alloc(MCRT_TRI_PIECES * (size_t)n_tri));
+    HIP_TRY(mcrt::launch_expand_tris(leaf, n_tri, c->d_tris, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return MCRT_OK;
 }
 
@@ -520,16 +499,23 @@ extern "C" int mcrt_set_bvh_builder(mcrt_ctx *c, int builder)
     return MCRT_OK;
 }
 
-static int update_triangles(mcrt_ctx *c, const float *tri, uint32_t n_tri, const mcrt::HostTree *pre)
+// what mcrt_update_triangles and mcrt_refit_triangles ask alike: new positions for exactly the uploaded triangles, and an idle stream
+static int check_new_positions(mcrt_ctx *c, const float *tri, uint32_t n_tri)
 {
     CTX_TRY(c);
     if (!c->have_scene) return set_error(MCRT_ERR_INVALID, "no scene uploaded");
     if (!tri) return set_error(MCRT_ERR_INVALID, "null triangles");
     if (n_tri != c->bvh.n_tri || n_tri == 0) return set_error(MCRT_ERR_INVALID, "the scene has %u triangles, the update has %u", c->bvh.n_tri, n_tri);
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return MCRT_OK;
+}
+
+static int update_triangles(mcrt_ctx *c, const float *tri, uint32_t n_tri, const mcrt::HostTree *pre)
+{
+    MCRT_TRY(check_new_positions(c, tri, n_tri));
     c->have_scene = false;                           // a failed rebuild leaves no scene
-    int rc = index_triangles(c, tri, n_tri, pre); if (rc) return rc;
-    rc = refresh_soa(c); if (rc) return rc;
+    MCRT_TRY(index_triangles(c, tri, n_tri, pre));
+    MCRT_TRY(refresh_soa(c));
     c->have_scene = true;
     return MCRT_OK;
 }
@@ -537,11 +523,7 @@ extern "C" int mcrt_update_triangles(mcrt_ctx *c, const float *tri, uint32_t n_t
 
 extern "C" int mcrt_refit_triangles(mcrt_ctx *c, const float *tri, uint32_t n_tri)
 {
-    CTX_TRY(c);
-    if (!c->have_scene) return set_error(MCRT_ERR_INVALID, "no scene uploaded");
-    if (!tri) return set_error(MCRT_ERR_INVALID, "null triangles");
-    if (n_tri != c->bvh.n_tri || n_tri == 0) return set_error(MCRT_ERR_INVALID, "the scene has %u triangles, the update has %u", c->bvh.n_tri, n_tri);
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    MCRT_TRY(check_new_positions(c, tri, n_tri));
     Buf<float> d_tri;
     HIP_TRY(d_tri.alloc(9 * (size_t)n_tri));
     int rc = MCRT_OK;
@@ -579,8 +561,8 @@ static int upload_scene(mcrt_ctx *c, const float *tri, const uint32_t *tri_mesh,
     c->have_scene = false;
     if (n_tri) {
         c->tri_mesh.assign(tri_mesh, tri_mesh + n_tri);
-        int rc = index_triangles(c, tri, n_tri, pre); if (rc) return rc;
-        rc = refresh_soa(c); if (rc) return rc;
+        MCRT_TRY(index_triangles(c, tri, n_tri, pre));
+        MCRT_TRY(refresh_soa(c));
     } else {
         c->d_nodes.reset(); c->d_tris.reset(); c->d_tri_slot.reset(); c->d_nodes_walk.reset(); c->d_tris_id.reset();
     }
@@ -615,7 +597,7 @@ extern "C" int mcrt_get_bvh(mcrt_ctx *c, mcrt_bvh *out)
 {
     if (!c || !out) return set_error(MCRT_ERR_INVALID, "null argument");
     if (!c->have_scene) return set_error(MCRT_ERR_INVALID, "no scene uploaded");
-    { int rc = download_bvh(c); if (rc) return rc; }
+    MCRT_TRY(download_bvh(c));
     *out = c->bvh;
     return MCRT_OK;
 }
@@ -644,7 +626,7 @@ extern "C" int mcrt_get_bvh4(mcrt_ctx *c, mcrt_bvh4 *out)
         out->n_nodes = c->bvh4.n_nodes; out->max_stack = c->bvh4.max_stack; out->nodes = c->walked_nodes;
         return MCRT_OK;
     }
-    { int rc = download_bvh(c); if (rc) return rc; }
+    MCRT_TRY(download_bvh(c));
     *out = c->bvh4;
     return MCRT_OK;
 }
@@ -658,8 +640,7 @@ extern "C" int mcrt_upload_texture(mcrt_ctx *c, const float *vox, uint32_t n)
     bool finite = true;
     if (!vox) {
         gen.resize(total * 2);
-        int rc = mcrt_generate_texture(gen.data(), n);
-        if (rc) return rc;
+        MCRT_TRY(mcrt_generate_texture(gen.data(), n));
         vox = gen.data();
     } else {
         for (size_t i = 0; i < total * 2; i++) if (!std::isfinite(vox[i])) { finite = false; break; }
@@ -882,13 +863,13 @@ template <class Launch> static int timed_launch(mcrt_ctx *c, int kind, hipStream
 //  flight, 0.414 against 0.405 on the driver's pass, and a hang under `rocprofv3 --pmc`.  Removed; DESIGN.md A.6, profiles/round4/exp_round4_kernels.txt.)
 static int run_bounce(mcrt_ctx *c, Work &w, hipStream_t st, const mcrt::FrameArgs &a, uint32_t b, uint32_t sides, bool accumulate, bool overlap)
 {
-    int rc = timed_launch(c, 0, st, [&] { return mcrt::launch_trace(a, b, c->stats_on, st); }); if (rc) return rc;
-    rc = timed_launch(c, 1, st, [&] { return mcrt::launch_shade(a, b, c->stats_on, st); }); if (rc) return rc;
+    MCRT_TRY(timed_launch(c, 0, st, [&] { return mcrt::launch_trace(a, b, c->stats_on, st); }));
+    MCRT_TRY(timed_launch(c, 1, st, [&] { return mcrt::launch_shade(a, b, c->stats_on, st); }));
     if (!accumulate || (a.fold_b0 && b == 0u)) return MCRT_OK;      // (bounce 0 folded: k_shade has added its echoes; later bounces keep their side streams)
     hipStream_t ms = st;
     if (overlap) {   // the segments of bounce b are final: accumulate them beside the next bounce's walk
         HIP_TRY(hipEventRecord(w.ev_bounce[b], st));
-        rc = side_stream(c, w, b % sides, &ms); if (rc) return rc;
+        MCRT_TRY(side_stream(c, w, b % sides, &ms));
         HIP_TRY(hipStreamWaitEvent(ms, w.ev_bounce[b], 0));
     }
     return timed_launch(c, 2, ms, [&] { return mcrt::launch_march(a, b, c->stats_on, ms); });
@@ -898,7 +879,7 @@ static int enqueue_pass(mcrt_ctx *c, const Plan &P, const mcrt::FrameArgs *args,
 {
     const bool overlap = !c->knobs.no_overlap;
     hipStream_t gst[16] = { c->stream };
-    for (uint32_t g = 1; g < P.groups; g++) { int rc = work_stream(*ws[g], &gst[g]); if (rc) return rc; }
+    for (uint32_t g = 1; g < P.groups; g++) MCRT_TRY(work_stream(*ws[g], &gst[g]));
     if (c->scene_pending && c->scene_stream != c->stream) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_scene, 0));   // a scene update issued on another stream
     HIP_TRY(hipEventRecord(c->ev_start, c->stream));
     for (uint32_t g = 0; g < P.groups; g++) {
@@ -907,15 +888,15 @@ static int enqueue_pass(mcrt_ctx *c, const Plan &P, const mcrt::FrameArgs *args,
     }
     if (P.latency) {
         for (uint32_t g = 0; g < P.groups; g++) {          // (every group's k_path first, then the accumulations: the second group must not wait for the host to enqueue the first's k_march)
-            int rc = timed_launch(c, 0, gst[g], [&] { return mcrt::launch_path(args[g], gst[g]); }); if (rc) return rc;
+            MCRT_TRY(timed_launch(c, 0, gst[g], [&] { return mcrt::launch_path(args[g], gst[g]); }));
         }
         for (uint32_t g = 0; g < P.groups && accumulate; g++) {
-            int rc = timed_launch(c, 2, gst[g], [&] { return mcrt::launch_march(args[g], mcrt::MCRT_ALL_BOUNCES, false, gst[g]); }); if (rc) return rc;
+            MCRT_TRY(timed_launch(c, 2, gst[g], [&] { return mcrt::launch_march(args[g], mcrt::MCRT_ALL_BOUNCES, false, gst[g]); }));
         }
     } else {
         for (uint32_t b = 0; b < c->p.max_depth; b++)
             for (uint32_t g = 0; g < P.groups; g++) {
-                int rc = run_bounce(c, *ws[g], gst[g], args[g], b, P.sides[g], accumulate, overlap); if (rc) return rc;
+                MCRT_TRY(run_bounce(c, *ws[g], gst[g], args[g], b, P.sides[g], accumulate, overlap));
             }
     }
     for (uint32_t g = 0; g < P.groups; g++) {
@@ -942,29 +923,35 @@ static int run_pass(mcrt_ctx *c, uint32_t frame, uint32_t n_frames, uint32_t e0,
     Work *ws[16];
     fill_pass(c, P, pass, frame, e1 - e0, accumulate, out);
     for (uint32_t g = 0; g < P.groups; g++) {
-        int rc = get_work(c, g, &ws[g]); if (rc) return rc;
-        rc = ensure_work(*ws[g], (size_t)(P.e[g + 1] - P.e[g]) * n_frames * c->p.n_samples, c->p.max_depth, P.ovf[g], out); if (rc) return rc;
+        MCRT_TRY(get_work(c, g, &ws[g]));
+        MCRT_TRY(ensure_work(*ws[g], (size_t)(P.e[g + 1] - P.e[g]) * n_frames * c->p.n_samples, c->p.max_depth, P.ovf[g], out));
         args[g] = pass;
         fill_group(c, *ws[g], args[g], n_frames, P.e[g], P.e[g + 1], e0, out);
-        rc = check_overflow(c, P, args[g], *ws[g]); if (rc) return rc;
+        MCRT_TRY(check_overflow(c, P, args[g], *ws[g]));
     }
     return enqueue_pass(c, P, args, ws, accumulate);
+}
+
+// the traced block's accumulators [lines][R] into rf_dev; k_finalize leaves them zeroed (ensure_acc)
+static int finalize(mcrt_ctx *c, float *rf_dev, uint32_t lines)
+{
+    HIP_TRY(mcrt::launch_finalize(c->d_acc, c->d_flags, rf_dev, lines, c->p.n_rows, c->d_error, c->stream));
+    c->acc_clean_ne = lines; c->acc_clean_rows = c->p.n_rows;
+    return MCRT_OK;
 }
 
 extern "C" int mcrt_trace_frames(mcrt_ctx *c, uint32_t frame, uint32_t n_frames, uint32_t e0, uint32_t e1, float *rf_dev)
 {
     CTX_TRY(c);
-    int rc = check_ready(c, e0, e1); if (rc) return rc;
+    MCRT_TRY(check_ready(c, e0, e1));
     if (!rf_dev) return set_error(MCRT_ERR_INVALID, "null rf_dev");
     if (n_frames == 0 || n_frames > 1024) return set_error(MCRT_ERR_LIMIT, "n_frames must be 1..1024");
     if ((uint64_t)(e1 - e0) * n_frames * c->p.n_samples > (1ull << 27))        // (~600 bytes of work buffers per path)
         return set_error(MCRT_ERR_LIMIT, "%u frames x %u scan-lines x %u samples: more than 2^27 paths in one pass", n_frames, e1 - e0, c->p.n_samples);
     const uint32_t lines = (e1 - e0) * n_frames;
-    rc = ensure_acc(c, lines); if (rc) return rc;
-    rc = run_pass(c, frame, n_frames, e0, e1, true, false, 0); if (rc) return rc;
-    HIP_TRY(mcrt::launch_finalize(c->d_acc, c->d_flags, rf_dev, lines, c->p.n_rows, c->d_error, c->stream));
-    c->acc_clean_ne = lines; c->acc_clean_rows = c->p.n_rows;
-    return MCRT_OK;
+    MCRT_TRY(ensure_acc(c, lines));
+    MCRT_TRY(run_pass(c, frame, n_frames, e0, e1, true, false, 0));
+    return finalize(c, rf_dev, lines);
 }
 
 extern "C" int mcrt_trace_frame(mcrt_ctx *c, uint32_t frame, uint32_t e0, uint32_t e1, float *rf_dev)
@@ -989,9 +976,7 @@ extern "C" int mcrt_trace_frames_poses(mcrt_ctx *c, uint32_t frame, uint32_t n_f
     // reused: the copy of the previous call (an early node of the previous pass, not the pass) is waited for first.
     bool staged = false;
     for (int k = 0; k < 2; k++) {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, src[k]) == hipSuccess && at.type == hipMemoryTypeDevice) { dev[k] = src[k]; continue; }
-        (void)hipGetLastError();
+        if (is_device_pointer(src[k])) { dev[k] = src[k]; continue; }
         if (c->pose_copy_pending) { HIP_TRY(hipEventSynchronize(c->ev_pose)); c->pose_copy_pending = false; }
         if (c->d_pose[k].cap < bytes / 4 || c->h_pose[k].cap < bytes / 4) {
             HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1002,7 +987,7 @@ extern "C" int mcrt_trace_frames_poses(mcrt_ctx *c, uint32_t frame, uint32_t n_f
         dev[k] = c->d_pose[k]; staged = true;
     }
     if (staged) {
-        if (!c->ev_pose) HIP_TRY(hipEventCreateWithFlags(&c->ev_pose.h, hipEventDisableTiming));
+        HIP_TRY(ensure_event(c->ev_pose));
         HIP_TRY(hipEventRecord(c->ev_pose, c->stream));
         c->pose_copy_pending = true;
     }
@@ -1018,7 +1003,7 @@ static int copy_out(mcrt_ctx *c, uint32_t ne, int32_t *hits, mcrt_segment *segs,
     const size_t np = (size_t)ne * c->p.n_samples, B = c->p.max_depth;
     const Work &w = c->work[0];
     HIP_TRY(hipStreamSynchronize(c->stream));
-    int rc = check_device_error(c); if (rc) return rc;
+    MCRT_TRY(check_device_error(c));
     std::vector<uint32_t> cnt;
     if (!seg_count && (hits || segs)) { cnt.resize(np); seg_count = cnt.data(); }
     if (seg_count) HIP_TRY(hipMemcpy(seg_count, w.b.seg_count, np * 4, hipMemcpyDeviceToHost));
@@ -1039,21 +1024,26 @@ extern "C" int mcrt_trace_frame_debug(mcrt_ctx *c, uint32_t frame, uint32_t e0, 
                                       int32_t *hits, mcrt_segment *segs, uint32_t *seg_count)
 {
     CTX_TRY(c);
-    int rc = check_ready(c, e0, e1); if (rc) return rc;
+    MCRT_TRY(check_ready(c, e0, e1));
     if (!rf_dev) return set_error(MCRT_ERR_INVALID, "null rf_dev");
-    rc = ensure_acc(c, e1 - e0); if (rc) return rc;
-    rc = run_pass(c, frame, 1, e0, e1, true, true, segs ? 2 : 1); if (rc) return rc;   // one group: the per-path tables are contiguous
-    HIP_TRY(mcrt::launch_finalize(c->d_acc, c->d_flags, rf_dev, e1 - e0, c->p.n_rows, c->d_error, c->stream));
-    c->acc_clean_ne = e1 - e0; c->acc_clean_rows = c->p.n_rows;
+    MCRT_TRY(ensure_acc(c, e1 - e0));
+    MCRT_TRY(run_pass(c, frame, 1, e0, e1, true, true, segs ? 2 : 1));   // one group: the per-path tables are contiguous
+    MCRT_TRY(finalize(c, rf_dev, e1 - e0));
     return copy_out(c, e1 - e0, hits, segs, seg_count);
 }
 
 extern "C" int mcrt_cast_rays(mcrt_ctx *c, uint32_t frame, uint32_t e0, uint32_t e1, mcrt_segment *segs, uint32_t *seg_count, int32_t *hits)
 {
     CTX_TRY(c);
-    int rc = check_ready(c, e0, e1); if (rc) return rc;
-    rc = run_pass(c, frame, 1, e0, e1, false, true, segs ? 2 : 1); if (rc) return rc;
+    MCRT_TRY(check_ready(c, e0, e1));
+    MCRT_TRY(run_pass(c, frame, 1, e0, e1, false, true, segs ? 2 : 1));
     return copy_out(c, e1 - e0, hits, segs, seg_count);
+}
+
+static bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + a_bytes, b0 = (uintptr_t)b, b1 = b0 + b_bytes;
+    return a0 < b1 && b0 < a1;
 }
 
 static int ensure_tmp(mcrt_ctx *c, size_t n)
@@ -1070,7 +1060,7 @@ extern "C" int mcrt_convolve_frames(mcrt_ctx *c, float *rf_dev, uint32_t n_frame
     CTX_TRY(c);
     if (!rf_dev || !ax || !lat || E == 0 || R == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "mcrt_convolve: bad arguments");
     if (n_ax == 0 || n_ax > 16 || n_lat == 0 || n_lat > 32) return set_error(MCRT_ERR_LIMIT, "kernel sizes must be 1..16 axial, 1..32 lateral");
-    int rc = ensure_tmp(c, (size_t)n_frames * E * R); if (rc) return rc;
+    MCRT_TRY(ensure_tmp(c, (size_t)n_frames * E * R));
     mcrt::ConvTaps t; memset(&t, 0, sizeof t);
     memcpy(t.ax, ax, 4 * n_ax); memcpy(t.lat, lat, 4 * n_lat); t.n_ax = n_ax; t.n_lat = n_lat;
     HIP_TRY(mcrt::launch_convolve(rf_dev, c->d_tmp, n_frames, E, R, t, c->stream));
@@ -1082,8 +1072,8 @@ extern "C" int mcrt_convolve(mcrt_ctx *c, float *rf_dev, uint32_t E, uint32_t R,
     return mcrt_convolve_frames(c, rf_dev, 1, E, R, ax, n_ax, lat, n_lat);
 }
 
-// The contract is in include/mcrt.h.  Everything is checked before anything is launched; the caller's table [R][n_lat] is compared bit
-// for bit with the one on the device and, only when it differs, transposed tap-major [n_lat][R] into the pinned staging and uploaded.
+// The contract is in include/mcrt.h.  Everything is checked before anything is launched; the caller's table [R][n_lat] goes to the device
+// tap-major [n_lat][R] (StagedTable).
 extern "C" int mcrt_convolve_frames_depth(mcrt_ctx *c, float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const float *ax, uint32_t n_ax,
                                           const float *lat_rows, uint32_t n_lat)
 {
@@ -1091,38 +1081,16 @@ extern "C" int mcrt_convolve_frames_depth(mcrt_ctx *c, float *rf_dev, uint32_t n
     if (!rf_dev || !ax || !lat_rows || E == 0 || R == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "mcrt_convolve_frames_depth: bad arguments");
     if (n_ax == 0 || n_ax > 16 || n_lat == 0 || n_lat > 32) return set_error(MCRT_ERR_LIMIT, "kernel sizes must be 1..16 axial, 1..32 lateral");
     if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "mcrt_convolve_frames_depth: at most %d rows", MCRT_MAX_ROWS);
-    { int rc = ensure_tmp(c, (size_t)n_frames * E * R); if (rc) return rc; }
-    constexpr size_t TABLE = (size_t)MCRT_MAX_ROWS * 32;
-    if (!c->d_lat_rows) {                               // once per context, all three or none
-        Buf<float> d; PinnedBuf<float> h; Event ev;
-        HIP_TRY(d.alloc(TABLE));
-        HIP_TRY(h.alloc(TABLE));
-        HIP_TRY(hipEventCreateWithFlags(&ev.h, hipEventDisableTiming));
-        c->d_lat_rows = std::move(d); c->h_lat_rows = std::move(h); c->ev_lat = std::move(ev);
-        c->lat_on_dev.assign(TABLE, 0.0f); c->lat_key[0] = c->lat_key[1] = 0;
-    }
-    const size_t n = (size_t)n_lat * R;
-    if (c->lat_key[0] != R || c->lat_key[1] != n_lat || memcmp(lat_rows, c->lat_on_dev.data(), 4 * n)) {   // (lat_on_dev: the caller's layout)
-        if (c->lat_copy_pending) HIP_TRY(hipEventSynchronize(c->ev_lat));     // the staging buffer still feeds the previous table's copy
-        float *h = c->h_lat_rows;
-        for (uint32_t r = 0; r < R; r++)
-            for (uint32_t k = 0; k < n_lat; k++) h[(size_t)k * R + r] = lat_rows[(size_t)r * n_lat + k];
-        c->lat_key[0] = c->lat_key[1] = 0;              // (no table until its copy is enqueued)
-        HIP_TRY(hipMemcpyAsync(c->d_lat_rows, h, 4 * n, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipEventRecord(c->ev_lat, c->stream));
-        c->lat_copy_pending = true;
-        memcpy(c->lat_on_dev.data(), lat_rows, 4 * n);
-        c->lat_key[0] = R; c->lat_key[1] = n_lat;
-    }
+    MCRT_TRY(ensure_tmp(c, (size_t)n_frames * E * R));
+    MCRT_TRY(c->lat_rows.put(lat_rows, R, n_lat, (size_t)MCRT_MAX_ROWS * 32, c->stream));
     mcrt::ConvTaps t; memset(&t, 0, sizeof t);
     memcpy(t.ax, ax, 4 * n_ax); t.n_ax = n_ax; t.n_lat = n_lat;
-    HIP_TRY(mcrt::launch_convolve_depth(rf_dev, c->d_tmp, n_frames, E, R, t, c->d_lat_rows, c->stream));
+    HIP_TRY(mcrt::launch_convolve_depth(rf_dev, c->d_tmp, n_frames, E, R, t, c->lat_rows.dev, c->stream));
     return MCRT_OK;
 }
 
-// The contract is in include/mcrt.h.  Everything is checked before anything is launched; the weight table follows the scheme of
-// mcrt_convolve_frames_depth (compared bit for bit with the one on the device, transposed tap-major [K][R] into pinned staging and
-// uploaded only when it differs).
+// The contract is in include/mcrt.h.  Everything is checked before anything is launched; the caller's weights [R][K] go to the device
+// tap-major [K][R] (StagedTable).
 extern "C" int mcrt_elevation_frames(mcrt_ctx *c, const float *planes_dev, uint32_t n_frames, uint32_t K, uint32_t E, uint32_t R,
                                      const float *w_rows, float *rf_dev)
 {
@@ -1131,33 +1099,9 @@ extern "C" int mcrt_elevation_frames(mcrt_ctx *c, const float *planes_dev, uint3
     if (K > 32) return set_error(MCRT_ERR_LIMIT, "mcrt_elevation_frames: at most 32 planes (%u)", K);
     if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "mcrt_elevation_frames: at most %d rows", MCRT_MAX_ROWS);
     if ((double)n_frames * (double)K * (double)E * (double)R >= 0x1p40) return set_error(MCRT_ERR_LIMIT, "mcrt_elevation_frames: the plane stack is too large");
-    {
-        const uintptr_t a0 = (uintptr_t)planes_dev, a1 = a0 + 4 * (size_t)n_frames * K * E * R, b0 = (uintptr_t)rf_dev, b1 = b0 + 4 * (size_t)n_frames * E * R;
-        if (a0 < b1 && b0 < a1) return set_error(MCRT_ERR_INVALID, "mcrt_elevation_frames: planes_dev and rf_dev overlap");
-    }
-    constexpr size_t TABLE = (size_t)MCRT_MAX_ROWS * 32;
-    if (!c->d_elev_rows) {                              // once per context, all three or none
-        Buf<float> d; PinnedBuf<float> h; Event ev;
-        HIP_TRY(d.alloc(TABLE));
-        HIP_TRY(h.alloc(TABLE));
-        HIP_TRY(hipEventCreateWithFlags(&ev.h, hipEventDisableTiming));
-        c->d_elev_rows = std::move(d); c->h_elev_rows = std::move(h); c->ev_elev = std::move(ev);
-        c->elev_on_dev.assign(TABLE, 0.0f); c->elev_key[0] = c->elev_key[1] = 0;
-    }
-    const size_t n = (size_t)K * R;
-    if (c->elev_key[0] != R || c->elev_key[1] != K || memcmp(w_rows, c->elev_on_dev.data(), 4 * n)) {   // (elev_on_dev: the caller's layout)
-        if (c->elev_copy_pending) HIP_TRY(hipEventSynchronize(c->ev_elev));   // the staging buffer still feeds the previous table's copy
-        float *h = c->h_elev_rows;
-        for (uint32_t r = 0; r < R; r++)
-            for (uint32_t k = 0; k < K; k++) h[(size_t)k * R + r] = w_rows[(size_t)r * K + k];
-        c->elev_key[0] = c->elev_key[1] = 0;            // (no table until its copy is enqueued)
-        HIP_TRY(hipMemcpyAsync(c->d_elev_rows, h, 4 * n, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipEventRecord(c->ev_elev, c->stream));
-        c->elev_copy_pending = true;
-        memcpy(c->elev_on_dev.data(), w_rows, 4 * n);
-        c->elev_key[0] = R; c->elev_key[1] = K;
-    }
-    HIP_TRY(mcrt::launch_elevation(planes_dev, rf_dev, n_frames, K, E, R, c->d_elev_rows, c->stream));
+    if (ranges_overlap(planes_dev, 4 * (size_t)n_frames * K * E * R, rf_dev, 4 * (size_t)n_frames * E * R)) return set_error(MCRT_ERR_INVALID, "mcrt_elevation_frames: planes_dev and rf_dev overlap");
+    MCRT_TRY(c->elev_rows.put(w_rows, R, K, (size_t)MCRT_MAX_ROWS * 32, c->stream));
+    HIP_TRY(mcrt::launch_elevation(planes_dev, rf_dev, n_frames, K, E, R, c->elev_rows.dev, c->stream));
     return MCRT_OK;
 }
 
@@ -1176,24 +1120,33 @@ extern "C" int mcrt_envelope(mcrt_ctx *c, float *rf_dev, uint32_t E, uint32_t R)
     return mcrt_envelope_frames(c, rf_dev, 1, E, R);
 }
 
-// the scan-conversion maps of a geometry on the device (mcrt_scan_convert_frames, mcrt_bmode_frames): made on the host and uploaded
-// when the geometry changes, reused as they are otherwise.  The doubles of the key are compared bit for bit, each on its own (a key
-// folded into one double, radius_mm * 1e6 + total_angle, made (30 mm, 1 rad) and (29.999999 mm, 2 rad) the same geometry)
-static int ensure_maps(mcrt_ctx *c, uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t orows, uint32_t ocols)
+// the scan-conversion maps of a geometry on the device, in cache m: the plain maps (cp null: mcrt_scan_maps, one view) or the N views of a steer
+// list (mcrt_compound_maps).  Made on the host and uploaded when the geometry changes, reused as they are otherwise.  Every part of the key is
+// compared bit for bit on its own (a key folded into one double, radius_mm * 1e6 + total_angle, made (30 mm, 1 rad) and (29.999999 mm, 2 rad)
+// the same geometry)
+static int ensure_maps(mcrt_ctx *c, MapCache &m, uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t orows, uint32_t ocols, const mcrt_compound *cp = nullptr)
 {
-    const uint32_t key[6] = { E, R, orows, ocols, c->p.speed_of_sound, 1u };
+    const uint32_t N = cp ? cp->n_views : 1u;
+    const uint32_t key[7] = { E, R, orows, ocols, c->p.speed_of_sound, 1u, N };
     const double keyd[3] = { radius_mm, total_angle, c->c.max_travel_us };
-    if (memcmp(key, c->map_key, sizeof key) || memcmp(keyd, c->map_keyd, sizeof keyd)) {
-        std::vector<float> mc((size_t)orows * ocols), mr((size_t)orows * ocols);
-        // (the rf_image template parameter is max_travel_time.to<unsigned int>(), main.cpp:36 -- the same truncation as max_rows uses)
-        { int rc = mcrt_scan_maps(E, R, radius_mm, total_angle, (uint32_t)c->c.max_travel_us, c->p.speed_of_sound, orows, ocols, mr.data(), mc.data()); if (rc) return rc; }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        memset(c->map_key, 0, sizeof key);                  // (no geometry until both maps are on the device)
-        HIP_TRY(c->d_map_col.alloc(mc.size())); HIP_TRY(c->d_map_row.alloc(mr.size()));
-        HIP_TRY(hipMemcpy(c->d_map_col, mc.data(), mc.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_map_row, mr.data(), mr.size() * 4, hipMemcpyHostToDevice));
-        memcpy(c->map_key, key, sizeof key); memcpy(c->map_keyd, keyd, sizeof keyd);
+    uint32_t steer[16] = {};
+    if (cp) memcpy(steer, cp->steer_rad, 4 * (size_t)N);
+    if (!memcmp(key, m.key, sizeof key) && !memcmp(keyd, m.keyd, sizeof keyd) && !memcmp(steer, m.steer, sizeof steer)) return MCRT_OK;
+    const size_t n = (size_t)orows * ocols, n_pad = MapCache::pad(n);
+    std::vector<float> maps(2 * (size_t)N * n_pad, 0.0f), mr(n), mc(n);
+    // (the rf_image template parameter is max_travel_time.to<unsigned int>(), main.cpp:36 -- the same truncation as max_rows uses)
+    const uint32_t travel = (uint32_t)c->c.max_travel_us, sos = c->p.speed_of_sound;
+    for (uint32_t v = 0; v < N; v++) {
+        MCRT_TRY(cp ? mcrt_compound_maps(E, R, radius_mm, total_angle, travel, sos, orows, ocols, cp->steer_rad[v], mr.data(), mc.data())
+                    : mcrt_scan_maps(E, R, radius_mm, total_angle, travel, sos, orows, ocols, mr.data(), mc.data()));
+        memcpy(&maps[(size_t)(2u * v) * n_pad], mc.data(), 4 * n);
+        memcpy(&maps[(size_t)(2u * v + 1u) * n_pad], mr.data(), 4 * n);
     }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memset(m.key, 0, sizeof key);                       // (no geometry until the maps are on the device)
+    HIP_TRY(m.d.grow(maps.size()));
+    HIP_TRY(hipMemcpy(m.d, maps.data(), maps.size() * 4, hipMemcpyHostToDevice));
+    memcpy(m.key, key, sizeof key); memcpy(m.keyd, keyd, sizeof keyd); memcpy(m.steer, steer, sizeof steer);
     return MCRT_OK;
 }
 
@@ -1203,8 +1156,8 @@ extern "C" int mcrt_scan_convert_frames(mcrt_ctx *c, const float *rf_dev, uint32
     CTX_TRY(c);
     if (!rf_dev || !out_dev || E == 0 || R == 0 || orows == 0 || ocols == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "mcrt_scan_convert: bad arguments");
     if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "mcrt_scan_convert: at most 65535 images per call");
-    { int rc = ensure_maps(c, E, R, radius_mm, total_angle, orows, ocols); if (rc) return rc; }
-    HIP_TRY(mcrt::launch_remap(rf_dev, n_frames, E, R, c->d_map_col, c->d_map_row, out_dev, orows * ocols, c->stream));
+    MCRT_TRY(ensure_maps(c, c->maps, E, R, radius_mm, total_angle, orows, ocols));
+    HIP_TRY(mcrt::launch_remap(rf_dev, n_frames, E, R, c->maps.d, c->maps.d + MapCache::pad((size_t)orows * ocols), out_dev, orows * ocols, c->stream));
     return MCRT_OK;
 }
 
@@ -1255,29 +1208,14 @@ static int bmode_check(const char *fn, const float *rf_dev, const void *out_dev,
 static int bmode_grey_pass(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t lines, uint32_t R, const mcrt_bmode_params *p, const float *tgc_db,
                            const std::vector<float> &k, float *peak_dev)
 {
-    constexpr size_t MAX_PEAKS = 65536;
-    if (!c->d_disp) {                                   // once per context, all three or none
-        Buf<float> disp; PinnedBuf<float> tgc; Event ev;
-        HIP_TRY(disp.alloc(MCRT_MAX_ROWS + MAX_PEAKS));
-        HIP_TRY(tgc.alloc(MCRT_MAX_ROWS));
-        HIP_TRY(hipEventCreateWithFlags(&ev.h, hipEventDisableTiming));
-        c->d_disp = std::move(disp); c->h_tgc = std::move(tgc); c->ev_tgc = std::move(ev);
-    }
-    float *d_tgc = c->d_disp, *d_peak = d_tgc + MCRT_MAX_ROWS;
-    if (tgc_db && k != c->tgc_on_dev) {
-        if (c->tgc_copy_pending) HIP_TRY(hipEventSynchronize(c->ev_tgc));     // the staging buffer still feeds the previous curve's copy
-        memcpy(c->h_tgc, k.data(), 4 * (size_t)R);
-        HIP_TRY(hipMemcpyAsync(d_tgc, c->h_tgc, 4 * (size_t)R, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipEventRecord(c->ev_tgc, c->stream));
-        c->tgc_copy_pending = true;
-        c->tgc_on_dev = k;
-    }
+    if (!c->d_disp) HIP_TRY(c->d_disp.alloc(65536));   // (the peaks of the largest pass: 65535 frames)
+    if (tgc_db) MCRT_TRY(c->tgc.put(k.data(), R, 1, MCRT_MAX_ROWS, c->stream));
     const size_t taps = (size_t)n_frames * lines * R;
-    { int rc = ensure_tmp(c, taps); if (rc) return rc; }     // the grey levels of the pass (the scratch mcrt_convolve uses too)
-    const float *tgc = tgc_db ? d_tgc : nullptr;
+    MCRT_TRY(ensure_tmp(c, taps));     // the grey levels of the pass (the scratch mcrt_convolve uses too)
+    const float *tgc = tgc_db ? c->tgc.dev.p : nullptr;
     if (p->ref > 0.0f) HIP_TRY(mcrt::launch_bmode_grey(rf_dev, n_frames, lines, R, tgc, nullptr, p->ref, peak_dev, p->mode, p->gain_db, p->dynamic_range_db, c->d_tmp, c->stream));
     else {
-        float *peak = peak_dev ? peak_dev : d_peak;
+        float *peak = peak_dev ? peak_dev : c->d_disp.p;
         HIP_TRY(hipMemsetAsync(peak, 0, 4 * (size_t)n_frames, c->stream));
         HIP_TRY(mcrt::launch_bmode_peak(rf_dev, n_frames, lines, R, tgc, peak, c->stream));
         HIP_TRY(mcrt::launch_bmode_grey(rf_dev, n_frames, lines, R, tgc, peak, 0.0f, nullptr, p->mode, p->gain_db, p->dynamic_range_db, c->d_tmp, c->stream));
@@ -1302,11 +1240,11 @@ extern "C" int mcrt_bmode_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_fr
 {
     CTX_TRY(c);
     std::vector<float> k;
-    { int rc = bmode_check("mcrt_bmode_frames", rf_dev, out_dev, n_frames, E, R, p, tgc_db, k); if (rc) return rc; }
-    { int rc = ensure_maps(c, E, R, p->radius_mm, p->total_angle_rad, p->out_rows, p->out_cols); if (rc) return rc; }
-    { int rc = bmode_grey_pass(c, rf_dev, n_frames, E, R, p, tgc_db, k, peak_dev); if (rc) return rc; }
+    MCRT_TRY(bmode_check("mcrt_bmode_frames", rf_dev, out_dev, n_frames, E, R, p, tgc_db, k));
+    MCRT_TRY(ensure_maps(c, c->maps, E, R, p->radius_mm, p->total_angle_rad, p->out_rows, p->out_cols));
+    MCRT_TRY(bmode_grey_pass(c, rf_dev, n_frames, E, R, p, tgc_db, k, peak_dev));
     mcrt::BmodeArgs a;
-    a.grey = c->d_tmp; a.map_col = c->d_map_col; a.map_row = c->d_map_row; a.state = state_dev; a.out = out_dev; a.alpha = p->persistence;
+    a.grey = c->d_tmp; a.map_col = c->maps.d; a.map_row = c->maps.d + MapCache::pad((size_t)p->out_rows * p->out_cols); a.state = state_dev; a.out = out_dev; a.alpha = p->persistence;
     a.E = E; a.R = R; a.n = p->out_rows * p->out_cols; a.F = n_frames; a.reset = p->reset_state ? 1u : 0u;
     a.frames_per_chunk = display_frames_per_chunk(n_frames, a.n, a.alpha);
     HIP_TRY(mcrt::launch_bmode(a, c->stream));
@@ -1325,38 +1263,6 @@ static int compound_check(const char *fn, const mcrt_compound *cp, uint32_t n_fr
     return MCRT_OK;
 }
 
-static bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
-{
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + a_bytes, b0 = (uintptr_t)b, b1 = b0 + b_bytes;
-    return a0 < b1 && b0 < a1;
-}
-
-// the N map pairs of a geometry and a steer list on the device: ensure_maps' scheme and key, plus N and the steer bits, each compared on its own
-static int ensure_compound_maps(mcrt_ctx *c, uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t orows, uint32_t ocols, const mcrt_compound *cp)
-{
-    const uint32_t N = cp->n_views;
-    const uint32_t key[7] = { E, R, orows, ocols, c->p.speed_of_sound, 1u, N };
-    const double keyd[3] = { radius_mm, total_angle, c->c.max_travel_us };
-    uint32_t steer[16] = {};
-    memcpy(steer, cp->steer_rad, 4 * (size_t)N);
-    if (memcmp(key, c->cmap_key, sizeof key) || memcmp(keyd, c->cmap_keyd, sizeof keyd) || memcmp(steer, c->cmap_steer, sizeof steer)) {
-        const size_t n = (size_t)orows * ocols, n_pad = (n + 255u) & ~(size_t)255u;
-        std::vector<float> maps(2 * (size_t)N * n_pad, 0.0f), mr(n), mc(n);
-        for (uint32_t v = 0; v < N; v++) {
-            int rc = mcrt_compound_maps(E, R, radius_mm, total_angle, (uint32_t)c->c.max_travel_us, c->p.speed_of_sound, orows, ocols, cp->steer_rad[v], mr.data(), mc.data());
-            if (rc) return rc;
-            memcpy(&maps[(size_t)(2u * v) * n_pad], mc.data(), 4 * n);
-            memcpy(&maps[(size_t)(2u * v + 1u) * n_pad], mr.data(), 4 * n);
-        }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        memset(c->cmap_key, 0, sizeof key);                 // (no geometry until the maps are on the device)
-        HIP_TRY(c->d_cmaps.grow(maps.size()));
-        HIP_TRY(hipMemcpy(c->d_cmaps, maps.data(), maps.size() * 4, hipMemcpyHostToDevice));
-        memcpy(c->cmap_key, key, sizeof key); memcpy(c->cmap_keyd, keyd, sizeof keyd); memcpy(c->cmap_steer, steer, sizeof steer);
-    }
-    return MCRT_OK;
-}
-
 extern "C" int mcrt_compound_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, double radius_mm, double total_angle,
                                     const mcrt_compound *cp, float *out_dev, uint32_t orows, uint32_t ocols)
 {
@@ -1364,15 +1270,15 @@ extern "C" int mcrt_compound_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n
     static const char fn[] = "mcrt_compound_frames";
     if (!rf_dev || !out_dev || E == 0 || R == 0 || orows == 0 || ocols == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "%s: bad arguments", fn);
     if (!(total_angle > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: total_angle_rad must be > 0", fn);
-    { int rc = compound_check(fn, cp, n_frames); if (rc) return rc; }
+    MCRT_TRY(compound_check(fn, cp, n_frames));
     if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: at most %d rows", fn, MCRT_MAX_ROWS);
     if ((uint64_t)orows * ocols > 0x7ffffffcull) return set_error(MCRT_ERR_LIMIT, "%s: output image too large", fn);
     const uint32_t N = cp->n_views, n = orows * ocols;
     if (ranges_overlap(rf_dev, 4 * (size_t)n_frames * N * E * R, out_dev, 4 * (size_t)n_frames * n)) return set_error(MCRT_ERR_INVALID, "%s: rf_dev and out_dev overlap", fn);
-    { int rc = ensure_compound_maps(c, E, R, radius_mm, total_angle, orows, ocols, cp); if (rc) return rc; }
+    MCRT_TRY(ensure_maps(c, c->cmaps, E, R, radius_mm, total_angle, orows, ocols, cp));
     mcrt::CompoundArgs a;
-    a.src = rf_dev; a.maps = c->d_cmaps; a.state = nullptr; a.out = out_dev; a.alpha = 0.0f;
-    a.E = E; a.R = R; a.n = n; a.n_pad = (n + 255u) & ~255u; a.F = n_frames; a.N = N; a.reset = 1u;
+    a.src = rf_dev; a.maps = c->cmaps.d; a.state = nullptr; a.out = out_dev; a.alpha = 0.0f;
+    a.E = E; a.R = R; a.n = n; a.n_pad = (uint32_t)MapCache::pad(n); a.F = n_frames; a.N = N; a.reset = 1u;
     a.frames_per_chunk = display_frames_per_chunk(n_frames, n, 0.0f);
     HIP_TRY(mcrt::launch_compound(a, false, c->stream));
     return MCRT_OK;
@@ -1384,17 +1290,17 @@ extern "C" int mcrt_bmode_compound_frames(mcrt_ctx *c, const float *rf_dev, uint
     CTX_TRY(c);
     static const char fn[] = "mcrt_bmode_compound_frames";
     std::vector<float> k;
-    { int rc = bmode_check(fn, rf_dev, out_dev, n_frames, E, R, p, tgc_db, k); if (rc) return rc; }
+    MCRT_TRY(bmode_check(fn, rf_dev, out_dev, n_frames, E, R, p, tgc_db, k));
     if (!(p->total_angle_rad > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: total_angle_rad must be > 0", fn);
-    { int rc = compound_check(fn, cp, n_frames); if (rc) return rc; }
+    MCRT_TRY(compound_check(fn, cp, n_frames));
     const uint32_t N = cp->n_views, n = p->out_rows * p->out_cols;
     if ((uint64_t)N * E > 0xffffffffull) return set_error(MCRT_ERR_LIMIT, "%s: too many scan-lines (%u views x %u)", fn, N, E);   // (a frame is N * E scan-lines to steps 1-3)
     if (ranges_overlap(rf_dev, 4 * (size_t)n_frames * N * E * R, out_dev, (size_t)n_frames * n)) return set_error(MCRT_ERR_INVALID, "%s: rf_dev and out_dev overlap", fn);
-    { int rc = ensure_compound_maps(c, E, R, p->radius_mm, p->total_angle_rad, p->out_rows, p->out_cols, cp); if (rc) return rc; }
-    { int rc = bmode_grey_pass(c, rf_dev, n_frames, N * E, R, p, tgc_db, k, peak_dev); if (rc) return rc; }
+    MCRT_TRY(ensure_maps(c, c->cmaps, E, R, p->radius_mm, p->total_angle_rad, p->out_rows, p->out_cols, cp));
+    MCRT_TRY(bmode_grey_pass(c, rf_dev, n_frames, N * E, R, p, tgc_db, k, peak_dev));
     mcrt::CompoundArgs a;
-    a.src = c->d_tmp; a.maps = c->d_cmaps; a.state = state_dev; a.out = out_dev; a.alpha = p->persistence;
-    a.E = E; a.R = R; a.n = n; a.n_pad = (n + 255u) & ~255u; a.F = n_frames; a.N = N; a.reset = p->reset_state ? 1u : 0u;
+    a.src = c->d_tmp; a.maps = c->cmaps.d; a.state = state_dev; a.out = out_dev; a.alpha = p->persistence;
+    a.E = E; a.R = R; a.n = n; a.n_pad = (uint32_t)MapCache::pad(n); a.F = n_frames; a.N = N; a.reset = p->reset_state ? 1u : 0u;
     a.frames_per_chunk = display_frames_per_chunk(n_frames, n, a.alpha);
     HIP_TRY(mcrt::launch_compound(a, true, c->stream));
     return MCRT_OK;
@@ -1404,7 +1310,7 @@ extern "C" int mcrt_export_rf(mcrt_ctx *c, const float *rf_dev, uint32_t E, uint
 {
     CTX_TRY(c);
     if (!rf_dev || !host || E == 0 || R == 0) return set_error(MCRT_ERR_INVALID, "mcrt_export_rf: bad arguments");
-    int rc = ensure_tmp(c, (size_t)E * R); if (rc) return rc;
+    MCRT_TRY(ensure_tmp(c, (size_t)E * R));
     HIP_TRY(mcrt::launch_transpose(rf_dev, c->d_tmp, E, R, c->stream));
     HIP_TRY(hipMemcpyAsync(host, c->d_tmp, (size_t)E * R * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1415,7 +1321,7 @@ extern "C" int mcrt_import_rf(mcrt_ctx *c, const float *host, uint32_t E, uint32
 {
     CTX_TRY(c);
     if (!rf_dev || !host || E == 0 || R == 0) return set_error(MCRT_ERR_INVALID, "mcrt_import_rf: bad arguments");
-    int rc = ensure_tmp(c, (size_t)E * R); if (rc) return rc;
+    MCRT_TRY(ensure_tmp(c, (size_t)E * R));
     HIP_TRY(hipMemcpyAsync(c->d_tmp, host, (size_t)E * R * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(mcrt::launch_transpose(c->d_tmp, rf_dev, R, E, c->stream));          // [R][E] -> [E][R]
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1446,35 +1352,31 @@ extern "C" int mcrt_memcpy_h2d(mcrt_ctx *c, void *dev, const void *host, size_t 
 }
 
 extern "C" int mcrt_enable_stats(mcrt_ctx *c, int on) { CTX_TRY(c); c->stats_on = on != 0; return MCRT_OK; }
-extern "C" int mcrt_get_stats(mcrt_ctx *c, mcrt_stats *out, int reset)
+// words [first, first + n) of the context's counter block, once the stream is idle; zeroed afterwards on request
+static int read_stats(mcrt_ctx *c, size_t first, size_t n, void *out, int reset)
 {
     CTX_TRY(c);
     HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(out, c->d_stats + first, n * 8, hipMemcpyDeviceToHost));
+    if (reset) { HIP_TRY(hipMemsetAsync(c->d_stats + first, 0, n * 8, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream)); }
+    return MCRT_OK;
+}
+extern "C" int mcrt_get_stats(mcrt_ctx *c, mcrt_stats *out, int reset)
+{
     unsigned long long v[6];
-    HIP_TRY(hipMemcpy(v, c->d_stats, sizeof v, hipMemcpyDeviceToHost));
+    MCRT_TRY(read_stats(c, 0, 6, v, reset));
     if (out) { out->queries = v[0]; out->nodes_visited = v[1]; out->tris_tested = v[2]; out->segments = v[3]; out->rf_steps = v[4]; out->hits = v[5]; }
-    if (reset) { HIP_TRY(hipMemsetAsync(c->d_stats, 0, sizeof v, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream)); }
     return MCRT_OK;
 }
 
 // diagnostic builds (-DMCRT_STAMP): per-phase cycle sums of k_trace [0,16) and its per-bounce launch timeline [16,120), k_march's sections [120,130) (the timeline alone: -DMCRT_STAMP_LITE); zeros otherwise
-extern "C" int mcrt_debug_stamps(mcrt_ctx *c, uint64_t out[200], int reset)
-{
-    CTX_TRY(c);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(out, c->d_stats + 8, 200 * 8, hipMemcpyDeviceToHost));
-    if (reset) { HIP_TRY(hipMemsetAsync(c->d_stats + 8, 0, 200 * 8, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream)); }
-    return MCRT_OK;
-}
+extern "C" int mcrt_debug_stamps(mcrt_ctx *c, uint64_t out[200], int reset) { return read_stats(c, 8, 200, out, reset); }
 
 extern "C" int mcrt_debug_tail_histograms(mcrt_ctx *c, uint64_t out[2560], int reset)
 {
     CTX_TRY(c);
     if (!out) return set_error(MCRT_ERR_INVALID, "null out pointer");
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(out, c->d_stats + 256, 2560 * 8, hipMemcpyDeviceToHost));
-    if (reset) { HIP_TRY(hipMemsetAsync(c->d_stats + 256, 0, 2560 * 8, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream)); }
-    return MCRT_OK;
+    return read_stats(c, 256, 2560, out, reset);
 }
 
 extern "C" int mcrt_debug_fast_paths(mcrt_ctx *c, uint32_t out[4])
@@ -1518,7 +1420,7 @@ extern "C" int mcrt_get_kernel_times(mcrt_ctx *c, double avg_ms[3], uint32_t n[3
 extern "C" int mcrt_get_kernel_time(mcrt_ctx *c, double *avg_ms, uint32_t *n, int reset)
 {
     double a[3]; uint32_t k[3];
-    const int rc = mcrt_get_kernel_times(c, a, k, reset); if (rc) return rc;
+    MCRT_TRY(mcrt_get_kernel_times(c, a, k, reset));
     if (avg_ms) *avg_ms = a[0];
     if (n) *n = k[0];
     return MCRT_OK;

@@ -15,6 +15,7 @@
 // path, one process per GPU under torch.distributed, gathers the same blocks with one RCCL collective: mcray-tracing_amd/dist.py).
 #include "../../include/mcrt.h"
 #include "mcrt_internal.h"
+#include "mcrt_hip.h"
 #include "mcrt_kernels.h"
 
 #include <hip/hip_runtime.h>
@@ -33,16 +34,14 @@ namespace mcrt {
 hipStream_t ctx_stream(mcrt_ctx *c);      // mcrt_api.cpp
 }
 
-#define G_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipGetLastError(); return set_error(e_ == hipErrorOutOfMemory ? MCRT_ERR_NOMEM : MCRT_ERR_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } } while (0)
-
 namespace {
 struct Member {
     int device = 0;
     mcrt_ctx *ctx = nullptr;
-    hipStream_t trace = nullptr, copy = nullptr;
-    hipEvent_t ev_t0[2] = {}, ev_traced[2] = {}, ev_c0[2] = {}, ev_copied[2] = {};
+    Stream trace, copy;
+    Event ev_t0[2], ev_traced[2], ev_c0[2], ev_copied[2];   // TIMING events (mcrt_group_last_pass_ms)
     bool used[2] = { false, false };                 // the events of slot i have been recorded at least once
-    float *blk[2] = { nullptr, nullptr }; size_t blk_cap[2] = { 0, 0 };
+    Buf<float> blk[2];
     int last_slot = -1;
     uint64_t copied_pass = 0;                        // the pass (1-based) whose peer copy this rank enqueued last
 };
@@ -53,8 +52,8 @@ struct mcrt_group {
     int root_device = 0;
     mcrt_ctx *root = nullptr;
     mcrt_params p{};
-    float *stage[2] = { nullptr, nullptr }; size_t stage_cap[2] = { 0, 0 };
-    hipEvent_t ev_reordered[2] = {}, ev_root_now[2] = {}; bool reordered_used[2] = { false, false };
+    Buf<float> stage[2];
+    Event ev_reordered[2], ev_root_now[2]; bool reordered_used[2] = { false, false };   // ordering events
     uint64_t pass = 0;
     int builder = MCRT_BVH_HOST_SAH;                 // what mcrt_group_set_bvh_builder last set on every rank
     std::vector<uint32_t> tri_mesh;                  // per-triangle mesh index of the uploaded scene (the host builder of mcrt_group_update_triangles needs it)
@@ -123,25 +122,40 @@ extern "C" int mcrt_group_destroy(mcrt_group *g)
     }
     for (auto &t : g->threads) if (t.joinable()) t.join();
     for (Member &m : g->mem) {
+        if (!m.ctx) continue;                                // a rank a failed mcrt_group_create never reached: nothing to release, and its device may not exist
         (void)hipSetDevice(m.device);
         if (m.copy) (void)hipStreamSynchronize(m.copy);
         if (m.trace) (void)hipStreamSynchronize(m.trace);
-        if (m.ctx) mcrt_destroy(m.ctx);                      // (waits for the device)
-        for (int i = 0; i < 2; i++) {
-            if (m.blk[i]) (void)hipFree(m.blk[i]);
-            for (hipEvent_t e : { m.ev_t0[i], m.ev_traced[i], m.ev_c0[i], m.ev_copied[i] }) if (e) (void)hipEventDestroy(e);
+        mcrt_destroy(m.ctx);                                 // (waits for the device)
+        m = Member();                                        // its blocks, events and streams go while its device is current
+    }
+    if (g->root) { (void)hipSetDevice(g->root_device); mcrt_destroy(g->root); }   // (without a root nothing else of the group was made)
+    delete g;                                                // (the staging buffers and the root's events, on the root's device)
+    return MCRT_OK;
+}
+
+// rank m's streams and events, made on its device (which stays current)
+static int member_resources(Member &m, int root_device)
+{
+    HIP_TRY(hipSetDevice(m.device));
+    HIP_TRY(hipStreamCreateWithFlags(&m.trace.h, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&m.copy.h, hipStreamNonBlocking));
+    for (int i = 0; i < 2; i++)
+        for (Event *e : { &m.ev_t0[i], &m.ev_traced[i], &m.ev_c0[i], &m.ev_copied[i] }) HIP_TRY(hipEventCreate(&e->h));
+    if (m.device != root_device) {          // xGMI peer mapping where the platform offers it (the peer copy works either way)
+        int can = 0;
+        if (hipDeviceCanAccessPeer(&can, m.device, root_device) == hipSuccess && can) {
+            const hipError_t pe = hipDeviceEnablePeerAccess(root_device, 0);
+            if (pe != hipSuccess) (void)hipGetLastError();          // (already enabled by another rank of this process: fine)
         }
-        if (m.copy) (void)hipStreamDestroy(m.copy);
-        if (m.trace) (void)hipStreamDestroy(m.trace);
     }
-    (void)hipSetDevice(g->root_device);
-    if (g->root) mcrt_destroy(g->root);
-    for (int i = 0; i < 2; i++) {
-        if (g->stage[i]) (void)hipFree(g->stage[i]);
-        if (g->ev_reordered[i]) (void)hipEventDestroy(g->ev_reordered[i]);
-        if (g->ev_root_now[i]) (void)hipEventDestroy(g->ev_root_now[i]);
-    }
-    delete g;
+    return MCRT_OK;
+}
+
+static int root_events(mcrt_group *g)
+{
+    HIP_TRY(hipSetDevice(g->root_device));
+    for (int i = 0; i < 2; i++) { HIP_TRY(ensure_event(g->ev_reordered[i])); HIP_TRY(ensure_event(g->ev_root_now[i])); }
     return MCRT_OK;
 }
 
@@ -160,33 +174,10 @@ extern "C" int mcrt_group_create(const int *devices, uint32_t n, mcrt_group **ou
         m.device = devices[r];
         rc = mcrt_create(m.device, &m.ctx);
         if (rc) break;
-        hipError_t e = hipSetDevice(m.device);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&m.trace, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&m.copy, hipStreamNonBlocking);
-        for (int i = 0; i < 2 && e == hipSuccess; i++) {
-            e = hipEventCreate(&m.ev_t0[i]);
-            if (e == hipSuccess) e = hipEventCreate(&m.ev_traced[i]);
-            if (e == hipSuccess) e = hipEventCreate(&m.ev_c0[i]);
-            if (e == hipSuccess) e = hipEventCreate(&m.ev_copied[i]);
-        }
-        if (e == hipSuccess && m.device != g->root_device) {          // xGMI peer mapping where the platform offers it (the peer copy works either way)
-            int can = 0;
-            if (hipDeviceCanAccessPeer(&can, m.device, g->root_device) == hipSuccess && can) {
-                const hipError_t pe = hipDeviceEnablePeerAccess(g->root_device, 0);
-                if (pe != hipSuccess) (void)hipGetLastError();          // (already enabled by another rank of this process: fine)
-            }
-        }
-        if (e != hipSuccess) { (void)hipGetLastError(); rc = set_error(MCRT_ERR_HIP, "mcrt_group_create: rank %u on device %d: %s", r, m.device, hipGetErrorString(e)); break; }
+        if (member_resources(m, g->root_device)) { const std::string why = mcrt_last_error(); rc = set_error(MCRT_ERR_HIP, "mcrt_group_create: rank %u on device %d: %s", r, m.device, why.c_str()); break; }
         rc = mcrt_set_stream(m.ctx, m.trace);
     }
-    if (!rc) {
-        hipError_t e = hipSetDevice(g->root_device);
-        for (int i = 0; i < 2 && e == hipSuccess; i++) {
-            e = hipEventCreateWithFlags(&g->ev_reordered[i], hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&g->ev_root_now[i], hipEventDisableTiming);
-        }
-        if (e != hipSuccess) { (void)hipGetLastError(); rc = set_error(MCRT_ERR_HIP, "mcrt_group_create: %s", hipGetErrorString(e)); }
-    }
+    if (!rc && root_events(g)) { const std::string why = mcrt_last_error(); rc = set_error(MCRT_ERR_HIP, "mcrt_group_create: %s", why.c_str()); }
     if (rc) { const std::string keep = mcrt_last_error(); mcrt_group_destroy(g); return set_error(rc, "%s", keep.c_str()); }
     mcrt_get_params(g->root, &g->p);
     for (uint32_t r = 0; r < n; r++) g->threads.emplace_back(worker, g, r);
@@ -229,10 +220,7 @@ extern "C" int mcrt_group_set_bvh_builder(mcrt_group *g, int builder)
 
 static int host_pointer_only(const void *p, const char *who)
 {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice)
-        return set_error(MCRT_ERR_INVALID, "%s: a device pointer belongs to one GPU; the group calls take host memory", who);
-    (void)hipGetLastError();
+    if (is_device_pointer(p)) return set_error(MCRT_ERR_INVALID, "%s: a device pointer belongs to one GPU; the group calls take host memory", who);
     return MCRT_OK;
 }
 
@@ -260,13 +248,13 @@ extern "C" int mcrt_group_upload_scene(mcrt_group *g, const float *tri, const ui
 {
     GRP_TRY(g);
     if (n_tri && (!tri || !tri_mesh)) return set_error(MCRT_ERR_INVALID, "mcrt_group_upload_scene: missing triangles");
-    if (tri) { int rc = host_pointer_only(tri, "mcrt_group_upload_scene"); if (rc) return rc; }
+    if (tri) MCRT_TRY(host_pointer_only(tri, "mcrt_group_upload_scene"));
     BuiltOnce once;
     const double t0 = now_s();
     if (n_tri && g->builder == MCRT_BVH_HOST_SAH) {
         for (uint32_t i = 0; i < n_tri; i++)          // (mcrt_upload_scene's own check, needed before the builder reads the table)
             if (tri_mesh[i] >= n_mesh) return set_error(MCRT_ERR_INVALID, "triangle %u references mesh %u out of range", i, tri_mesh[i]);
-        int rc = once.build(tri, tri_mesh, n_tri); if (rc) return rc;
+        MCRT_TRY(once.build(tri, tri_mesh, n_tri));
     }
     const double t1 = now_s();
     const mcrt::HostTree *pre = once.tree.bvh ? &once.tree : nullptr;
@@ -280,11 +268,11 @@ extern "C" int mcrt_group_update_triangles(mcrt_group *g, const float *tri, uint
 {
     GRP_TRY(g);
     if (!tri) return set_error(MCRT_ERR_INVALID, "null triangles");
-    { int rc = host_pointer_only(tri, "mcrt_group_update_triangles"); if (rc) return rc; }
+    MCRT_TRY(host_pointer_only(tri, "mcrt_group_update_triangles"));
     BuiltOnce once;
     const double t0 = now_s();
     if (g->builder == MCRT_BVH_HOST_SAH && n_tri != 0 && n_tri == g->tri_mesh.size()) {      // (a wrong count is the ranks' error to report)
-        int rc = once.build(tri, g->tri_mesh.data(), n_tri); if (rc) return rc;
+        MCRT_TRY(once.build(tri, g->tri_mesh.data(), n_tri));
     }
     const double t1 = now_s();
     const mcrt::HostTree *pre = once.tree.bvh ? &once.tree : nullptr;
@@ -305,7 +293,7 @@ extern "C" int mcrt_group_refit_triangles(mcrt_group *g, const float *tri, uint3
 {
     GRP_TRY(g);
     if (!tri) return set_error(MCRT_ERR_INVALID, "null triangles");
-    { int rc = host_pointer_only(tri, "mcrt_group_refit_triangles"); if (rc) return rc; }
+    MCRT_TRY(host_pointer_only(tri, "mcrt_group_refit_triangles"));
     return run_all(g, [=](uint32_t r) { return mcrt_refit_triangles(g->mem[r].ctx, tri, n_tri); });
 }
 
@@ -316,7 +304,7 @@ extern "C" int mcrt_group_upload_texture(mcrt_group *g, const float *vox, uint32
     std::vector<float> gen;
     if (!vox) {                                  // volume<>::volume() (volume.h:19-35) once, not once per rank
         gen.resize((size_t)n * n * n * 2);
-        int rc = mcrt_generate_texture(gen.data(), n); if (rc) return rc;
+        MCRT_TRY(mcrt_generate_texture(gen.data(), n));
         vox = gen.data();
     }
     return run_all(g, [=](uint32_t r) { return mcrt_upload_texture(g->mem[r].ctx, vox, n); });
@@ -328,15 +316,12 @@ extern "C" int mcrt_group_set_transducer(mcrt_group *g, const float *pos, const 
     return run_all(g, [=](uint32_t r) { return mcrt_set_transducer(g->mem[r].ctx, pos, dir, n); });
 }
 
-static int ensure_dev(float **buf, size_t *cap, size_t bytes, int device)
+static int ensure_dev(Buf<float> &buf, size_t n, int device)
 {
-    if (*cap >= bytes) return MCRT_OK;
-    G_HIP(hipSetDevice(device));
-    G_HIP(hipDeviceSynchronize());                  // (a growing buffer: rare; everything that may still read the old one is waited for)
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr; *cap = 0;
-    G_HIP(hipMalloc((void **)buf, bytes));
-    *cap = bytes;
+    if (buf.cap >= n) return MCRT_OK;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipDeviceSynchronize());                  // (a growing buffer: rare; everything that may still read the old one is waited for)
+    HIP_TRY(buf.grow(n));
     return MCRT_OK;
 }
 
@@ -355,45 +340,44 @@ static int group_trace(mcrt_group *g, uint32_t frame, uint32_t F, const float *p
     // one frame (or one rank): the blocks are contiguous pieces of the frame and land in place; otherwise they are staged on the root
     // device rank after rank and one kernel interleaves them into frames
     const bool staged = F > 1 && G > 1;
-    const size_t frame_bytes = (size_t)E * R * sizeof(float);
-    if (staged) { int rc = ensure_dev(&g->stage[i], &g->stage_cap[i], frame_bytes * F, g->root_device); if (rc) return rc; }
-    G_HIP(hipSetDevice(g->root_device));
+    if (staged) MCRT_TRY(ensure_dev(g->stage[i], (size_t)E * R * F, g->root_device));
+    HIP_TRY(hipSetDevice(g->root_device));
     hipStream_t root_stream = mcrt::ctx_stream(g->root);
-    G_HIP(hipEventRecord(g->ev_root_now[i], root_stream));        // what the root's stream holds NOW (earlier readers of rf_dev) precedes the copies into it
+    HIP_TRY(hipEventRecord(g->ev_root_now[i], root_stream));        // what the root's stream holds NOW (earlier readers of rf_dev) precedes the copies into it
     float *const stage = g->stage[i];
     int rc = run_all(g, [=](uint32_t r) -> int {
         Member &m = g->mem[r];
         const uint32_t ne = off[r + 1] - off[r];
         const size_t bytes = (size_t)F * ne * R * sizeof(float);
-        { int rc2 = ensure_dev(&m.blk[i], &m.blk_cap[i], bytes, m.device); if (rc2) return rc2; }
-        G_HIP(hipSetDevice(m.device));
-        if (m.used[i]) G_HIP(hipStreamWaitEvent(m.trace, m.ev_copied[i], 0));          // the copy of two passes ago has left this block buffer
-        G_HIP(hipEventRecord(m.ev_t0[i], m.trace));
+        MCRT_TRY(ensure_dev(m.blk[i], bytes / sizeof(float), m.device));
+        HIP_TRY(hipSetDevice(m.device));
+        if (m.used[i]) HIP_TRY(hipStreamWaitEvent(m.trace, m.ev_copied[i], 0));          // the copy of two passes ago has left this block buffer
+        HIP_TRY(hipEventRecord(m.ev_t0[i], m.trace));
         const int rc2 = pos ? mcrt_trace_frames_poses(m.ctx, frame, F, off[r], off[r + 1], pos, dir, m.blk[i])
                             : mcrt_trace_frames(m.ctx, frame, F, off[r], off[r + 1], m.blk[i]);
         if (rc2) return rc2;
-        G_HIP(hipEventRecord(m.ev_traced[i], m.trace));
-        G_HIP(hipStreamWaitEvent(m.copy, m.ev_traced[i], 0));
-        if (staged) { if (g->reordered_used[i]) G_HIP(hipStreamWaitEvent(m.copy, g->ev_reordered[i], 0)); }   // the staging buffer's last reader
-        else G_HIP(hipStreamWaitEvent(m.copy, g->ev_root_now[i], 0));
+        HIP_TRY(hipEventRecord(m.ev_traced[i], m.trace));
+        HIP_TRY(hipStreamWaitEvent(m.copy, m.ev_traced[i], 0));
+        if (staged) { if (g->reordered_used[i]) HIP_TRY(hipStreamWaitEvent(m.copy, g->ev_reordered[i], 0)); }   // the staging buffer's last reader
+        else HIP_TRY(hipStreamWaitEvent(m.copy, g->ev_root_now[i], 0));
         float *dst = staged ? stage + (size_t)F * off[r] * R : rf_dev + (size_t)off[r] * R;
-        G_HIP(hipEventRecord(m.ev_c0[i], m.copy));
-        if (m.device == g->root_device) G_HIP(hipMemcpyAsync(dst, m.blk[i], bytes, hipMemcpyDeviceToDevice, m.copy));
-        else G_HIP(hipMemcpyPeerAsync(dst, g->root_device, m.blk[i], m.device, bytes, m.copy));
-        G_HIP(hipEventRecord(m.ev_copied[i], m.copy));
+        HIP_TRY(hipEventRecord(m.ev_c0[i], m.copy));
+        if (m.device == g->root_device) HIP_TRY(hipMemcpyAsync(dst, m.blk[i], bytes, hipMemcpyDeviceToDevice, m.copy));
+        else HIP_TRY(hipMemcpyPeerAsync(dst, g->root_device, m.blk[i], m.device, bytes, m.copy));
+        HIP_TRY(hipEventRecord(m.ev_copied[i], m.copy));
         m.used[i] = true; m.last_slot = i; m.copied_pass = this_pass;
         return MCRT_OK;
     });
     // Also when a rank failed: the ranks that succeeded have peer copies into rf_dev / the staging buffer in flight on their own copy streams.
     // The root's stream is ordered behind every copy that WAS enqueued in this pass, so a caller that handles the error by reusing or freeing
     // rf_dev behind the root's stream (mcrt_synchronize(mcrt_group_root(g)), or more work on that stream) does not race with them.
-    G_HIP(hipSetDevice(g->root_device));
+    HIP_TRY(hipSetDevice(g->root_device));
     for (uint32_t r = 0; r < G; r++)
-        if (g->mem[r].copied_pass == this_pass) G_HIP(hipStreamWaitEvent(root_stream, g->mem[r].ev_copied[i], 0));
+        if (g->mem[r].copied_pass == this_pass) HIP_TRY(hipStreamWaitEvent(root_stream, g->mem[r].ev_copied[i], 0));
     if (rc) return rc;
     if (staged) {
-        G_HIP(mcrt::launch_blocks_to_frames(stage, rf_dev, F, E, R, G, off.data(), root_stream));
-        G_HIP(hipEventRecord(g->ev_reordered[i], root_stream));
+        HIP_TRY(mcrt::launch_blocks_to_frames(stage, rf_dev, F, E, R, G, off.data(), root_stream));
+        HIP_TRY(hipEventRecord(g->ev_reordered[i], root_stream));
         g->reordered_used[i] = true;
     }
     return MCRT_OK;
@@ -407,8 +391,8 @@ extern "C" int mcrt_group_trace_frames(mcrt_group *g, uint32_t frame, uint32_t n
 extern "C" int mcrt_group_trace_frames_poses(mcrt_group *g, uint32_t frame, uint32_t n_frames, const float *pos, const float *dir, float *rf_dev)
 {
     if (!pos || !dir) return set_error(MCRT_ERR_INVALID, "mcrt_group_trace_frames_poses: null pose tables");
-    { int rc = host_pointer_only(pos, "mcrt_group_trace_frames_poses"); if (rc) return rc; }
-    { int rc = host_pointer_only(dir, "mcrt_group_trace_frames_poses"); if (rc) return rc; }
+    MCRT_TRY(host_pointer_only(pos, "mcrt_group_trace_frames_poses"));
+    MCRT_TRY(host_pointer_only(dir, "mcrt_group_trace_frames_poses"));
     return group_trace(g, frame, n_frames, pos, dir, rf_dev);
 }
 
@@ -417,9 +401,9 @@ extern "C" int mcrt_group_synchronize(mcrt_group *g)
     GRP_TRY(g);
     int rc = run_all(g, [g](uint32_t r) -> int {
         Member &m = g->mem[r];
-        G_HIP(hipSetDevice(m.device));
+        HIP_TRY(hipSetDevice(m.device));
         const int rc2 = mcrt_synchronize(m.ctx);                // the rank's trace stream + its device error word
-        G_HIP(hipStreamSynchronize(m.copy));
+        HIP_TRY(hipStreamSynchronize(m.copy));
         return rc2;
     });
     const int rc_root = mcrt_synchronize(g->root);
@@ -435,10 +419,10 @@ extern "C" int mcrt_group_last_pass_ms(mcrt_group *g, float *trace_ms, float *co
         if (copy_ms) copy_ms[r] = 0.0f;
         if (m.last_slot < 0 || !m.used[m.last_slot]) continue;      // (no pass yet, or its events were never recorded: a pass that failed on this rank)
         const int i = m.last_slot;
-        G_HIP(hipSetDevice(m.device));
-        G_HIP(hipEventSynchronize(m.ev_copied[i]));
-        if (trace_ms) G_HIP(hipEventElapsedTime(&trace_ms[r], m.ev_t0[i], m.ev_traced[i]));
-        if (copy_ms) G_HIP(hipEventElapsedTime(&copy_ms[r], m.ev_c0[i], m.ev_copied[i]));
+        HIP_TRY(hipSetDevice(m.device));
+        HIP_TRY(hipEventSynchronize(m.ev_copied[i]));
+        if (trace_ms) HIP_TRY(hipEventElapsedTime(&trace_ms[r], m.ev_t0[i], m.ev_traced[i]));
+        if (copy_ms) HIP_TRY(hipEventElapsedTime(&copy_ms[r], m.ev_c0[i], m.ev_copied[i]));
     }
     return MCRT_OK;
 }

@@ -1,4 +1,4 @@
-// mcrt_kernels.h -- kernel argument blocks and launchers: the interface between mcrt_api.cpp (plain C++) and the gfx950 kernels.
+// mcrt_kernels.h -- kernel argument blocks and launchers: the interface between the host C++ (mcrt_api.cpp, mcrt_group.cpp; mcrt_hip.h owns their HIP resources) and the gfx950 kernels.
 //
 // The hot path's kernels, one translation unit per pipeline stage, each kernel beside its launcher:
 //   mcrt_walk.hip    k_trace_lane / k_trace_lane_wide (closest hit, one lane per ray), k_trace_packet (one wavefront per ray packet),
@@ -70,7 +70,7 @@ struct ConvTaps { float ax[16]; float lat[32]; uint32_t n_ax, n_lat; };
 // k_bmode (mcrt_bmode_frames): the grey levels [F][E][R] of k_bmode_grey -> bytes [F][n], n = out_rows * out_cols
 struct BmodeArgs {
     const float *grey;                  // [F][E][R]
-    const float *map_col, *map_row;     // [n] the context's scan-conversion maps
+    const float *map_col, *map_row;     // [n] the context's scan-conversion maps (16-byte aligned: the two halves of a [2][n_pad] buffer)
     float *state;                       // [n] persistence state, or null
     uint8_t *out;                       // [F][n]
     float alpha;

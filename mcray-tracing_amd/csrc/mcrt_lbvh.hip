@@ -354,10 +354,9 @@ __global__ void k_refit_nodes(float4 *nodes, uint32_t n4, const float4 *rec, con
     }
 }
 
-struct Temp {
-    std::vector<void *> p;
-    ~Temp() { for (void *x : p) hipFree(x); }
-    template <class T> hipError_t get(T **out, size_t count) { void *x = nullptr; hipError_t e = hipMalloc(&x, count * sizeof(T) + 16); if (e == hipSuccess) { p.push_back(x); *out = (T *)x; } return e; }
+struct Temp {   // scratch of one build or refit, every piece 16 bytes longer than asked for
+    std::vector<Buf<uint8_t>> p;
+    template <class T> hipError_t get(T **out, size_t count) { Buf<uint8_t> b; hipError_t e = b.alloc(count * sizeof(T) + 16); if (e == hipSuccess) { *out = (T *)b.p; p.push_back(std::move(b)); } return e; }
 };
 
 #define LB_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return set_error(MCRT_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
@@ -409,13 +408,10 @@ int lbvh_build(const float *tri_dev, const uint32_t *mesh_dev, uint32_t n_tri, h
     LB_TRY(hipStreamSynchronize(st));
     const uint32_t n4 = last_id + last_flag;
 
-    float4 *nodes = nullptr, *tris = nullptr; uint32_t *slot = nullptr;
-    LB_TRY(hipMalloc(&nodes, 128 * (size_t)n4));
-    if (hipMalloc(&tris, 48 * (size_t)n_tri) != hipSuccess || hipMalloc(&slot, 4 * (size_t)n_tri) != hipSuccess) {
-        hipFree(nodes); hipFree(tris); return set_error(MCRT_ERR_NOMEM, "device LBVH: out of device memory");
-    }
-    hipLaunchKernelGGL(k_emit4, grid_t, blk, 0, st, child, range, is4, id4, v1, plo, phi, ilo, ihi, n, leaf_max, nodes, k4);
-    hipLaunchKernelGGL(k_emit_tris, grid_t, blk, 0, st, tri_dev, mesh_dev, v1, n_tri, tris, slot);
+    LB_TRY(out->nodes.alloc(8 * (size_t)n4));
+    if (out->tris.alloc(3 * (size_t)n_tri) != hipSuccess || out->tri_slot.alloc(n_tri) != hipSuccess) return set_error(MCRT_ERR_NOMEM, "device LBVH: out of device memory");
+    hipLaunchKernelGGL(k_emit4, grid_t, blk, 0, st, child, range, is4, id4, v1, plo, phi, ilo, ihi, n, leaf_max, out->nodes.p, k4);
+    hipLaunchKernelGGL(k_emit_tris, grid_t, blk, 0, st, tri_dev, mesh_dev, v1, n_tri, out->tris.p, out->tri_slot.p);
     hipLaunchKernelGGL(k_stack, grid_t, blk, 0, st, par_i, is4, k4, n, s);
     Scal hs; float4 root_lo, root_hi;
     hipError_t e = hipMemcpyAsync(&hs, s, sizeof hs, hipMemcpyDeviceToHost, st);
@@ -423,8 +419,7 @@ int lbvh_build(const float *tri_dev, const uint32_t *mesh_dev, uint32_t n_tri, h
     if (e == hipSuccess) e = hipMemcpyAsync(&root_hi, ihi, 16, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) { hipFree(nodes); hipFree(tris); hipFree(slot); return set_error(MCRT_ERR_HIP, "device LBVH: %s", hipGetErrorString(e)); }
-    out->d_nodes = nodes; out->d_tris = tris; out->d_tri_slot = slot;
+    if (e != hipSuccess) return set_error(MCRT_ERR_HIP, "device LBVH: %s", hipGetErrorString(e));
     out->n_nodes4 = n4; out->max_stack = hs.max_stack; out->max_depth = hs.max_depth; out->pad_abs = hs.pad_abs;
     out->lo[0] = root_lo.x; out->lo[1] = root_lo.y; out->lo[2] = root_lo.z;
     out->hi[0] = root_hi.x; out->hi[1] = root_hi.y; out->hi[2] = root_hi.z;

@@ -119,6 +119,40 @@ def test_invariances(mcrt, orc, ctx):
         dev.close()
 
 
+def test_back_to_back_calls_each_get_their_own_tgc_curve(mcrt, orc, ctx):
+    """five calls with no synchronisation between them -- curves A, B, A, C of one length, then a curve of another -- every curve handed over
+    in ONE host array that is overwritten as soon as each call returns: every frame shows its own curve, and the peaks are its own bit for bit"""
+    e, rows, cols = 16, 33, 35
+    rng = np.random.default_rng(5)
+    curves = [rng.uniform(-6.0, 12.0, r).astype(np.float32) for r in (64, 64, 64, 128)]
+    order = [curves[0], curves[1], curves[0], curves[2], curves[3]]
+    frames = [(rng.rayleigh(1.0, (1, e, c.size)) * rng.choice([-1.0, 1.0], (1, e, c.size))).astype(np.float32) for c in order]
+    dev = Dev(ctx)
+    try:
+        rfs = []
+        for fr in frames:
+            rfs.append(dev(fr.nbytes)); ctx.h2d(rfs[-1], fr)
+        outs = [dev(rows * cols, 0xA5) for _ in order]; peaks = [dev(4, 0xA5) for _ in order]
+        ctx.synchronize()
+        buf = np.empty(128, np.float32)
+        for rf, c, out, peak in zip(rfs, order, outs, peaks):
+            buf[:c.size] = c
+            ctx.bmode_frames(rf, 1, e, c.size, out, peak_dev=peak, tgc_db=buf[:c.size], dynamic_range_db=48.0, out_rows=rows, out_cols=cols)
+            buf[:] = np.nan                            # the call has returned: the curve is the caller's again
+        ctx.synchronize()
+        for i, (fr, c, out, peak) in enumerate(zip(frames, order, outs, peaks)):
+            want, refs, _ = bm.bmode(orc, fr, tgc_db=c, dynamic_range_db=48.0, out_rows=rows, out_cols=cols)
+            got = ctx.d2h(out, (rows, cols), np.uint8)
+            print("call %d: %d of %d pixels differ from the mirror" % (i, np.count_nonzero(got != want[0]), got.size))
+            bm.assert_close(got, want[0])
+            assert got.any()
+            assert np.array_equal(ctx.d2h(peak, (1,), np.float32).view(np.uint32), refs.view(np.uint32)), i
+        assert not np.array_equal(bm.bmode(orc, frames[1], tgc_db=curves[0], dynamic_range_db=48.0, out_rows=rows, out_cols=cols)[0],
+                                  bm.bmode(orc, frames[1], tgc_db=curves[1], dynamic_range_db=48.0, out_rows=rows, out_cols=cols)[0])   # (a wrong curve would show)
+    finally:
+        dev.close()
+
+
 def _traced(mcrt, sphere, tex256, F, **kw):
     cfg, sd = sphere
     Es, S = 64, 48

@@ -115,6 +115,45 @@ def test_group_equals_single_context(mcrt, sphere, tex256, ranks, E):
 
 
 @pytest.mark.gpu
+def test_group_resources_through_failure_and_regrowth(mcrt, sphere, tex256):
+    """a group that fails half-way through its creation (its second rank names a device that does not exist) releases what it had made and
+    the next group works; passes of 3, 5 (both staged) and 1 frames (the blocks land in place), then 3 and 5 again -- successive passes alternate
+    between the two buffer slots, so it is the LAST pass that grows buffers made for 3 frames to 5; a second group made after the first was
+    closed gives the same frames.  All bit for bit one context's."""
+    cfg, sd = sphere
+    E, S = 16, 32
+    tr = mcrt.Transducer(E, position=cfg["transducerPosition"], angles_deg=cfg["transducerAngles"])
+    one = mcrt.Context(0); _setup(one, mcrt, sd, tr, S, tex256)
+    R = one.params.n_rows
+    ref_dev = one.alloc(5 * E * R * 4)
+    want = {}
+    for F in (3, 5, 1):
+        one.trace_frames(20, F, ref_dev)
+        want[F] = one.d2h(ref_dev, (F, E, R))
+    assert np.abs(want[3]).sum() > 0
+    one.free(ref_dev); one.close()
+
+    n = mcrt.load_library().mcrt_device_count()
+    with pytest.raises(mcrt.McrtError) as ex:
+        mcrt.Group([0, n])
+    assert ex.value.code == -1 and "out of range" in str(ex.value)
+
+    def passes(frames):
+        grp = mcrt.Group([0, 0]); _setup(grp, mcrt, sd, tr, S, tex256)
+        dev = grp.root.alloc(5 * E * R * 4)
+        try:
+            for F in frames:
+                grp.trace_frames(20, F, dev); grp.synchronize()
+                assert np.array_equal(grp.root.d2h(dev, (F, E, R)).view(np.uint32), want[F].view(np.uint32)), F
+        finally:
+            grp.root.free(dev)
+            grp.close()
+
+    passes((3, 5, 1, 3, 5))
+    passes((3,))
+
+
+@pytest.mark.gpu
 def test_group_moving_geometry_and_device_builder(mcrt, sphere, tex256):
     """mcrt_group_set_bvh_builder / _update_triangles / _refit_triangles reach every rank: frames equal a single context's"""
     cfg, sd = sphere
