@@ -38,7 +38,9 @@ extern "C" {
                               109: + mcrt_transducer_elevation_axis, mcrt_elevation_planes, mcrt_psf_elevation_kernels, mcrt_elevation_frames (slice thickness:
                                    elevation planes traced as one pose pass and folded with the elevation PSF);
                                    + mcrt_compound, mcrt_transducer_steered, mcrt_compound_maps, mcrt_compound_frames, mcrt_bmode_compound_frames (spatial
-                                   compounding: steered views of one plane traced as one pose pass and averaged in image space) */
+                                   compounding: steered views of one plane traced as one pose pass and averaged in image space);
+                                   + mcrt_compound_opts, mcrt_default_compound_opts, mcrt_compound_weights, mcrt_compound_frames_opts,
+                                   mcrt_bmode_compound_frames_opts (compounding modes: per-view weights, a lateral edge ramp, max, median; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -386,7 +388,8 @@ int mcrt_compound_maps(uint32_t n_elements, uint32_t n_rows, double radius_mm, d
  *                    if covered: sum = sum + (mcrt_scan_convert's bilinear expression on view n of frame f);  cnt++
  *   out = cnt ? sum / (float)cnt : 0.0f
  * in n order, one rounding per operation, no fma.  A NaN tap reaches its pixel, as in mcrt_scan_convert.  N = 1 with steer 0 equals
- * mcrt_scan_convert_frames bit for bit, except that a -0.0 becomes +0.0.  No per-view weights or apodisation, no max / median compounding.
+ * mcrt_scan_convert_frames bit for bit, except that a -0.0 becomes +0.0.  Per-view weights, a lateral edge ramp, max and median compounding:
+ * mcrt_compound_frames_opts below; this call is that one with the default options.
  * MCRT_ERR_INVALID for null pointers, zero sizes, n_views outside 1..16, a steer that is not finite or has |steer| >= pi/2, bad scan
  * geometry, rf_dev overlapping out_dev; MCRT_ERR_LIMIT for n_rows > 2048 or n_frames * N > 65535.  On any error nothing is launched and
  * out_dev is untouched.  The N map pairs live on the device in a buffer of their own beside the plain maps (alternating this call with
@@ -404,6 +407,54 @@ int mcrt_bmode_compound_frames(mcrt_ctx *ctx, const float *rf_dev /* [n_frames][
                                const mcrt_bmode_params *p, const mcrt_compound *cp, const float *tgc_db /* host [n_rows] or NULL */,
                                float *state_dev /* [out_rows][out_cols] or NULL */, float *peak_dev /* [n_frames] or NULL */,
                                uint8_t *out_dev /* [n_frames][out_rows][out_cols] */);
+
+/* ---- compounding modes: per-view weights, a lateral edge ramp (apodisation) that hides where a steered view's coverage ends, and the
+ * maximum or the median of the looks in place of their mean (the maximum keeps oblique interfaces bright, the median rejects a look that is
+ * an outlier, such as a reverberation seen from one angle only). */
+enum { MCRT_COMPOUND_MEAN = 0, MCRT_COMPOUND_MAX = 1, MCRT_COMPOUND_MEDIAN = 2 };
+typedef struct { uint32_t mode;            /* MCRT_COMPOUND_*                                   (MEAN) */
+                 float    feather_lines;   /* lateral edge ramp in scan-lines, 0 = off          (0)    */
+                 float    view_weight[16]; /* the first n_views are read                        (1)    */
+} mcrt_compound_opts;                      /* 72 bytes: mode at 0, feather_lines at 4, view_weight at 8 */
+int mcrt_default_compound_opts(mcrt_compound_opts *o);                       /* host only */
+/* mcrt_compound_frames with options (o == NULL: the defaults).  Per frame, output pixel and view n: the point p, the four taps, the blend s
+ * and `covered` are mcrt_compound_frames' own, and mx is view n's column map at the pixel.  Then, in float, one rounding per operation, no fma:
+ *   a = feather_lines > 0 ? fminf(fmaxf(fminf(mx, (float)(E - 1) - mx) / feather_lines, 0), 1) : 1
+ *   w = view_weight[n] * a
+ *   contributes = covered && w > 0
+ *   MEAN    sum = sum + w * s;  wsum = wsum + w        (the contributing views, in n order from 0.0f)
+ *           out = wsum > 0 ? sum / wsum : 0.0f
+ *   MAX     m = the first contributing s, then s > m ? s : m   (in n order)
+ *           out = m + 0.0f
+ *   MEDIAN  the contributing s ordered by <; c of them
+ *           out = (c odd ? v[(c-1)/2] : (v[c/2-1] + v[c/2]) * 0.5f) + 0.0f
+ *   MAX, MEDIAN: any contributing s that is NaN -> out is NaN.  No contributing view: out = +0.0f.
+ * In MAX and MEDIAN the weights only gate (a view with w > 0 counts fully).  With feathering on, the ramp removes the half-covered rim:
+ * mx <= 0 or mx >= E-1 gives a = 0, so a view contributes only where both its neighbouring scan-lines exist, and n_elements == 1 with
+ * feathering on is a black picture.  The ramp is lateral only: the picture's bottom edge, where a steered view ends a few pixels above the
+ * unsteered one, is not feathered.
+ * Defaults -- o == NULL, or MEAN with feather_lines 0 and every one of the first n_views weights equal to 1.0f -- give mcrt_compound_frames
+ * bit for bit (w * s == s, wsum is the count) and run its kernel.  Errors: mcrt_compound_frames' own, and MCRT_ERR_INVALID, the message
+ * naming the field, for an unknown mode, a feather_lines that is negative or not finite, a weight among the first n_views that is negative
+ * or not finite, and all of those weights being zero.  On any error nothing is launched and out_dev is untouched.  Nothing new is uploaded:
+ * the weights are made in the kernel from the maps of mcrt_compound_frames. */
+int mcrt_compound_frames_opts(mcrt_ctx *ctx, const float *rf_dev /* [n_frames][N][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
+                              double radius_mm, double total_angle_rad, const mcrt_compound *cp, float *out_dev /* [n_frames][out_rows][out_cols] */,
+                              uint32_t out_rows, uint32_t out_cols, const mcrt_compound_opts *o /* NULL = defaults */);
+/* mcrt_bmode_compound_frames with options: the rule above applied to the grey levels in place of step 4; steps 1-3 and 5-6 are unchanged, the
+ * persistence state carries across calls as before.  Defaults give mcrt_bmode_compound_frames' bytes.  Errors: that call's own and the four
+ * above; on any error nothing is launched and out_dev, state_dev and peak_dev are untouched. */
+int mcrt_bmode_compound_frames_opts(mcrt_ctx *ctx, const float *rf_dev /* [n_frames][N][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
+                                    const mcrt_bmode_params *p, const mcrt_compound *cp, const float *tgc_db /* host [n_rows] or NULL */,
+                                    float *state_dev /* [out_rows][out_cols] or NULL */, float *peak_dev /* [n_frames] or NULL */,
+                                    uint8_t *out_dev /* [n_frames][out_rows][out_cols] */, const mcrt_compound_opts *o /* NULL = defaults */);
+/* what one view contributes with, per pixel: w [out_rows][out_cols] = contributes ? w : 0 of the rule above, the same float expression
+ * the kernel evaluates, over mcrt_compound_maps' maps of the view (its arguments, then the view's weight and feather_lines).  Host only.
+ * MCRT_ERR_INVALID for mcrt_compound_maps' conditions, a null w, a view_weight or feather_lines that is negative or not finite; on an error
+ * nothing is written. */
+int mcrt_compound_weights(uint32_t n_elements, uint32_t n_rows, double radius_mm, double total_angle_rad, uint32_t max_travel_us,
+                          uint32_t speed_of_sound, uint32_t out_rows, uint32_t out_cols, float steer_rad, float view_weight, float feather_lines,
+                          float *w /* [out_rows][out_cols] */);
 
 /* device [E][R]  ->  host [R][E] row-major (the cv::Mat layout of rfimage.h:217); synchronous */
 int mcrt_export_rf(mcrt_ctx *ctx, const float *rf_dev, uint32_t n_elements, uint32_t n_rows, float *host_rows_by_cols);

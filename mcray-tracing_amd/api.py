@@ -10,7 +10,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, CompoundOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 
 # ------------------------------------------------------------------ host-side pieces (no GPU)
@@ -158,6 +158,40 @@ def compound_struct(steer_rad):
     for i, x in enumerate(st[:16]):
         cp.steer_rad[i] = x
     return cp
+
+
+COMPOUND_MODES = {"mean": 0, "max": 1, "median": 2}
+
+
+def compound_opts_struct(mode="mean", view_weights=None, feather_lines=0.0):
+    """mcrt_compound_opts from keywords: mode "mean" / "max" / "median" (or the MCRT_COMPOUND_* number), view_weights a sequence of up to 16
+    weights (None: every view 1; the views past the sequence keep 1), feather_lines the lateral edge ramp in scan-lines (0: off)"""
+    o = CompoundOpts()
+    check(load_library().mcrt_default_compound_opts(C.byref(o)))
+    o.mode = COMPOUND_MODES[mode] if isinstance(mode, str) else int(mode)
+    o.feather_lines = float(feather_lines)
+    if view_weights is not None:
+        w = [float(x) for x in view_weights]
+        if len(w) > 16:
+            raise ValueError("at most 16 view weights, got %d" % len(w))
+        for i, x in enumerate(w):
+            o.view_weight[i] = x
+    return o
+
+
+def _compound_defaults(mode, view_weights, feather_lines):
+    """every compounding keyword at its default: the caller then uses the entry point without options"""
+    return mode in ("mean", 0) and view_weights is None and feather_lines == 0.0
+
+
+def host_compound_weights(n_elements, n_rows, steer_rad, view_weight=1.0, feather_lines=0.0, radius_mm=30.0, total_angle=1.0471975511965976,
+                          max_travel_us=100, speed_of_sound=1500, out_rows=400, out_cols=500):
+    """mcrt_compound_weights: what the view steered by steer_rad contributes with at every pixel, float32 [out_rows][out_cols] -- its weight
+    times the lateral edge ramp where it covers the pixel, 0 elsewhere (the expression the kernel evaluates)"""
+    w = np.zeros((out_rows, out_cols), np.float32)
+    check(load_library().mcrt_compound_weights(n_elements, n_rows, radius_mm, total_angle, max_travel_us, speed_of_sound, out_rows, out_cols, steer_rad,
+                                               view_weight, feather_lines, ptr(w)))
+    return w
 
 
 BMODE_MODES = {"db": 0, "ref_log": 1}
@@ -471,23 +505,36 @@ class Context:
         tgc = _tgc_rows(tgc_db, n_rows)
         check(self.L.mcrt_bmode_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(p), ptr(tgc), ptr(state_dev), ptr(peak_dev), ptr(out_dev)))
 
-    def compound_frames(self, rf_dev, n_frames, n_elements, n_rows, steer_rad, out_dev, radius_mm=30.0, total_angle=1.0471975511965976, out_rows=400, out_cols=500):
+    def compound_frames(self, rf_dev, n_frames, n_elements, n_rows, steer_rad, out_dev, radius_mm=30.0, total_angle=1.0471975511965976, out_rows=400, out_cols=500,
+                        mode="mean", view_weights=None, feather_lines=0.0):
         """mcrt_compound_frames: the views [n_frames][N][E][R] of steer_rad's N angles -> device floats [n_frames][out_rows][out_cols], every
-        pixel the mean of the views that cover it"""
+        pixel the mean of the views that cover it.  mode "mean" / "max" / "median", view_weights and feather_lines (a lateral edge ramp in
+        scan-lines) go through mcrt_compound_frames_opts; with all three at their defaults the call is mcrt_compound_frames."""
         cp = compound_struct(steer_rad)
-        check(self.L.mcrt_compound_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, radius_mm, total_angle, C.byref(cp), ptr(out_dev), out_rows, out_cols))
+        if _compound_defaults(mode, view_weights, feather_lines):
+            check(self.L.mcrt_compound_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, radius_mm, total_angle, C.byref(cp), ptr(out_dev), out_rows, out_cols))
+            return
+        o = compound_opts_struct(mode, view_weights, feather_lines)
+        check(self.L.mcrt_compound_frames_opts(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, radius_mm, total_angle, C.byref(cp), ptr(out_dev), out_rows, out_cols,
+                                               C.byref(o)))
 
     def bmode_compound_frames(self, rf_dev, n_frames, n_elements, n_rows, steer_rad, out_dev, *, mode="db", dynamic_range_db=60.0, gain_db=0.0, ref=None,
                               tgc_db=None, persistence=0.0, state_dev=None, reset_state=True, peak_dev=None, radius_mm=30.0,
-                              total_angle=1.0471975511965976, out_rows=400, out_cols=500):
+                              total_angle=1.0471975511965976, out_rows=400, out_cols=500, compound_mode="mean", view_weights=None, feather_lines=0.0):
         """mcrt_bmode_compound_frames: bmode_frames over the views [n_frames][N][E][R] of steer_rad's N angles; the automatic reference of a
-        frame is the peak over all its views"""
+        frame is the peak over all its views.  compound_mode "mean" / "max" / "median" (mode is the grey curve's), view_weights and
+        feather_lines go through mcrt_bmode_compound_frames_opts; with all three at their defaults the call is mcrt_bmode_compound_frames."""
         p = bmode_params(mode=mode, dynamic_range_db=dynamic_range_db, gain_db=gain_db, ref=ref, persistence=persistence, reset_state=reset_state,
                          radius_mm=radius_mm, total_angle=total_angle, out_rows=out_rows, out_cols=out_cols)
         cp = compound_struct(steer_rad)
         tgc = _tgc_rows(tgc_db, n_rows)
-        check(self.L.mcrt_bmode_compound_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(p), C.byref(cp), ptr(tgc), ptr(state_dev),
-                                                ptr(peak_dev), ptr(out_dev)))
+        if _compound_defaults(compound_mode, view_weights, feather_lines):
+            check(self.L.mcrt_bmode_compound_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(p), C.byref(cp), ptr(tgc), ptr(state_dev),
+                                                    ptr(peak_dev), ptr(out_dev)))
+            return
+        o = compound_opts_struct(compound_mode, view_weights, feather_lines)
+        check(self.L.mcrt_bmode_compound_frames_opts(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(p), C.byref(cp), ptr(tgc), ptr(state_dev),
+                                                     ptr(peak_dev), ptr(out_dev), C.byref(o)))
 
     def export_rf(self, rf_dev, n_elements, n_rows):
         out = np.empty((n_rows, n_elements), np.float32)
@@ -639,14 +686,17 @@ class Simulator:
     """
 
     def __init__(self, scene_data, transducer, n_samples=5, n_rows=None, device=0, seed=0x5EED, psf=None, texture=None,
-                 max_depth=10, sanitize_tir=0, tex_n=256, bvh_builder="sah", elevation=False, compound=None):
+                 max_depth=10, sanitize_tir=0, tex_n=256, bvh_builder="sah", elevation=False, compound=None, compound_mode="mean", compound_weights=None,
+                 compound_feather=0.0):
         """elevation=True: slice thickness.  trace() then traces the psf's elevation_size planes of the frame as one pose pass -- plane k of
         frame f with frame id f * K + k, the frame-id rule of include/mcrt.h -- and folds them into rf_dev with psf.elevation_rows();
         everything after (convolve, bmode, frame) is unchanged.
         compound=(steer_rad, ...): spatial compounding.  trace() then traces the N steered views of the frame as one pose pass -- view n of
         frame f with frame id f * N + n, with elevation its plane k with (f * N + n) * K + k -- into views_dev [N][E][R] (folded per view
         with elevation=True); convolve() and the envelope run over the N views, bmode() ends in mcrt_bmode_compound_frames and
-        compound_image() in mcrt_compound_frames.  frame() returns RF, which a compounded frame does not have: it raises."""
+        compound_image() in mcrt_compound_frames.  frame() returns RF, which a compounded frame does not have: it raises.
+        compound_mode ("mean" / "max" / "median"), compound_weights (one weight per view) and compound_feather (a lateral edge ramp in
+        scan-lines) are carried into compound_image() and bmode(): the keywords of Context.compound_frames."""
         if compound is not None and not 1 <= len(tuple(compound)) <= 16:
             raise ValueError("compound takes 1..16 steering angles, got %d" % len(tuple(compound)))
         self.ctx = Context(device)
@@ -664,6 +714,12 @@ class Simulator:
         self.elevation, self.planes_dev = bool(elevation), None
         self.steers = tuple(float(x) for x in compound) if compound is not None else None
         self.N, self.views_dev = (len(self.steers), None) if self.steers is not None else (1, None)
+        if compound_weights is not None and (self.steers is None or len(tuple(compound_weights)) != len(self.steers)):
+            raise ValueError("compound_weights takes one weight per steering angle of compound=")
+        if self.steers is None and not _compound_defaults(compound_mode, None, compound_feather):
+            raise ValueError("compound_mode and compound_feather need compound=")
+        self.compound_opts = dict(mode=compound_mode, view_weights=tuple(float(x) for x in compound_weights) if compound_weights is not None else None,
+                                  feather_lines=float(compound_feather))
         if self.steers is not None:
             self.view_pos, self.view_dir = transducer.steered(self.steers)
             self.views_dev = self.ctx.alloc(self.N * E * self.R * 4)
@@ -733,7 +789,7 @@ class Simulator:
         out = self.ctx.alloc(out_rows * out_cols * 4)
         try:
             self.ctx.compound_frames(self.views_dev, 1, self.E, self.R, self.steers, out, radius_mm=radius_mm, total_angle=total_angle, out_rows=out_rows,
-                                     out_cols=out_cols)
+                                     out_cols=out_cols, **self.compound_opts)
             return self.ctx.d2h(out, (out_rows, out_cols), np.float32)
         finally:
             self.ctx.free(out)
@@ -748,7 +804,9 @@ class Simulator:
         out = self.ctx.alloc(rows * cols)
         try:
             if self.steers is not None:
-                self.ctx.bmode_compound_frames(self.views_dev, 1, self.E, self.R, self.steers, out, **display)
+                o = self.compound_opts
+                self.ctx.bmode_compound_frames(self.views_dev, 1, self.E, self.R, self.steers, out, compound_mode=o["mode"], view_weights=o["view_weights"],
+                                               feather_lines=o["feather_lines"], **display)
             else:
                 self.ctx.bmode_frames(self.rf_dev, 1, self.E, self.R, out, **display)
             return self.ctx.d2h(out, (rows, cols), np.uint8)

@@ -1263,8 +1263,39 @@ static int compound_check(const char *fn, const mcrt_compound *cp, uint32_t n_fr
     return MCRT_OK;
 }
 
-extern "C" int mcrt_compound_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, double radius_mm, double total_angle,
-                                    const mcrt_compound *cp, float *out_dev, uint32_t orows, uint32_t ocols)
+// the options of the two *_opts calls, checked alike (null: the defaults), turned into the kernel's mode and weights.  Defaults -- the mean,
+// no feathering, every weight of the first n_views 1.0f -- are COMPOUND_PLAIN: the kernel mcrt_compound_frames has always run
+static int compound_opts_check(const char *fn, const mcrt_compound_opts *o, uint32_t N, mcrt::CompoundArgs &a)
+{
+    a.mode = mcrt::COMPOUND_PLAIN; a.feather = 0.0f;
+    for (float &w : a.weight) w = 1.0f;
+    if (!o) return MCRT_OK;
+    if (o->mode != MCRT_COMPOUND_MEAN && o->mode != MCRT_COMPOUND_MAX && o->mode != MCRT_COMPOUND_MEDIAN) return set_error(MCRT_ERR_INVALID, "%s: unknown mode %u", fn, o->mode);
+    if (!(std::isfinite(o->feather_lines) && o->feather_lines >= 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: feather_lines must be finite and >= 0 (%g)", fn, (double)o->feather_lines);
+    bool ones = true, any = false;
+    for (uint32_t n = 0; n < N; n++) {
+        const float w = o->view_weight[n];
+        if (!(std::isfinite(w) && w >= 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: view_weight[%u] must be finite and >= 0 (%g)", fn, n, (double)w);
+        ones = ones && w == 1.0f; any = any || w > 0.0f;
+    }
+    if (!any) return set_error(MCRT_ERR_INVALID, "%s: view_weight: every one of the %u views has weight 0", fn, N);
+    if (o->mode == MCRT_COMPOUND_MEAN && o->feather_lines == 0.0f && ones) return MCRT_OK;
+    a.mode = o->mode == MCRT_COMPOUND_MAX ? mcrt::COMPOUND_MAX : o->mode == MCRT_COMPOUND_MEDIAN ? mcrt::COMPOUND_MEDIAN : mcrt::COMPOUND_WEIGHTED;
+    a.feather = o->feather_lines;
+    for (uint32_t n = 0; n < N; n++) a.weight[n] = o->view_weight[n];
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_default_compound_opts(mcrt_compound_opts *o)
+{
+    if (!o) return set_error(MCRT_ERR_INVALID, "mcrt_default_compound_opts: null options");
+    o->mode = MCRT_COMPOUND_MEAN; o->feather_lines = 0.0f;
+    for (float &w : o->view_weight) w = 1.0f;
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_compound_frames_opts(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, double radius_mm, double total_angle,
+                                         const mcrt_compound *cp, float *out_dev, uint32_t orows, uint32_t ocols, const mcrt_compound_opts *o)
 {
     CTX_TRY(c);
     static const char fn[] = "mcrt_compound_frames";
@@ -1275,8 +1306,9 @@ extern "C" int mcrt_compound_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n
     if ((uint64_t)orows * ocols > 0x7ffffffcull) return set_error(MCRT_ERR_LIMIT, "%s: output image too large", fn);
     const uint32_t N = cp->n_views, n = orows * ocols;
     if (ranges_overlap(rf_dev, 4 * (size_t)n_frames * N * E * R, out_dev, 4 * (size_t)n_frames * n)) return set_error(MCRT_ERR_INVALID, "%s: rf_dev and out_dev overlap", fn);
-    MCRT_TRY(ensure_maps(c, c->cmaps, E, R, radius_mm, total_angle, orows, ocols, cp));
     mcrt::CompoundArgs a;
+    MCRT_TRY(compound_opts_check(fn, o, N, a));
+    MCRT_TRY(ensure_maps(c, c->cmaps, E, R, radius_mm, total_angle, orows, ocols, cp));
     a.src = rf_dev; a.maps = c->cmaps.d; a.state = nullptr; a.out = out_dev; a.alpha = 0.0f;
     a.E = E; a.R = R; a.n = n; a.n_pad = (uint32_t)MapCache::pad(n); a.F = n_frames; a.N = N; a.reset = 1u;
     a.frames_per_chunk = display_frames_per_chunk(n_frames, n, 0.0f);
@@ -1284,8 +1316,15 @@ extern "C" int mcrt_compound_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n
     return MCRT_OK;
 }
 
-extern "C" int mcrt_bmode_compound_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_bmode_params *p,
-                                          const mcrt_compound *cp, const float *tgc_db, float *state_dev, float *peak_dev, uint8_t *out_dev)
+extern "C" int mcrt_compound_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, double radius_mm, double total_angle,
+                                    const mcrt_compound *cp, float *out_dev, uint32_t orows, uint32_t ocols)
+{
+    return mcrt_compound_frames_opts(c, rf_dev, n_frames, E, R, radius_mm, total_angle, cp, out_dev, orows, ocols, nullptr);
+}
+
+extern "C" int mcrt_bmode_compound_frames_opts(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_bmode_params *p,
+                                               const mcrt_compound *cp, const float *tgc_db, float *state_dev, float *peak_dev, uint8_t *out_dev,
+                                               const mcrt_compound_opts *o)
 {
     CTX_TRY(c);
     static const char fn[] = "mcrt_bmode_compound_frames";
@@ -1296,14 +1335,21 @@ extern "C" int mcrt_bmode_compound_frames(mcrt_ctx *c, const float *rf_dev, uint
     const uint32_t N = cp->n_views, n = p->out_rows * p->out_cols;
     if ((uint64_t)N * E > 0xffffffffull) return set_error(MCRT_ERR_LIMIT, "%s: too many scan-lines (%u views x %u)", fn, N, E);   // (a frame is N * E scan-lines to steps 1-3)
     if (ranges_overlap(rf_dev, 4 * (size_t)n_frames * N * E * R, out_dev, (size_t)n_frames * n)) return set_error(MCRT_ERR_INVALID, "%s: rf_dev and out_dev overlap", fn);
+    mcrt::CompoundArgs a;
+    MCRT_TRY(compound_opts_check(fn, o, N, a));
     MCRT_TRY(ensure_maps(c, c->cmaps, E, R, p->radius_mm, p->total_angle_rad, p->out_rows, p->out_cols, cp));
     MCRT_TRY(bmode_grey_pass(c, rf_dev, n_frames, N * E, R, p, tgc_db, k, peak_dev));
-    mcrt::CompoundArgs a;
     a.src = c->d_tmp; a.maps = c->cmaps.d; a.state = state_dev; a.out = out_dev; a.alpha = p->persistence;
     a.E = E; a.R = R; a.n = n; a.n_pad = (uint32_t)MapCache::pad(n); a.F = n_frames; a.N = N; a.reset = p->reset_state ? 1u : 0u;
     a.frames_per_chunk = display_frames_per_chunk(n_frames, n, a.alpha);
     HIP_TRY(mcrt::launch_compound(a, true, c->stream));
     return MCRT_OK;
+}
+
+extern "C" int mcrt_bmode_compound_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_bmode_params *p,
+                                          const mcrt_compound *cp, const float *tgc_db, float *state_dev, float *peak_dev, uint8_t *out_dev)
+{
+    return mcrt_bmode_compound_frames_opts(c, rf_dev, n_frames, E, R, p, cp, tgc_db, state_dev, peak_dev, out_dev, nullptr);
 }
 
 extern "C" int mcrt_export_rf(mcrt_ctx *c, const float *rf_dev, uint32_t E, uint32_t R, float *host)

@@ -178,8 +178,75 @@ __global__ void __launch_bounds__(256) k_bmode(BmodeArgs a)
 // ds_bpermute, so that lane L holds the bytes of pixels wb + 4 L .. 4 L + 3 and stores them as one word (VEC_OUT: the picture's size and
 // the output pointer keep them aligned; a wavefront at the picture's end stores its bytes one by one).  Frames are cut into chunks only
 // without persistence, as in k_bmode.
+//
+// MODE (mcrt_compound_frames_opts / mcrt_bmode_compound_frames_opts; the default options run COMPOUND_PLAIN, the loop described above):
+//   COMPOUND_WEIGHTED  the weighted, feathered mean.  A view's weight at a pixel (compound_weight: its view weight times the lateral edge
+//                      ramp of its column map) is made with the view's points, once per view and group; the count becomes the sum of the
+//                      weights, the per-frame accumulator sum + w * s.  A view whose weight is not > 0 does not contribute.
+//   COMPOUND_MAX       the same loop with the accumulator m = max(m, s) from -inf (the first contributing s, then s > m ? s : m); a NaN
+//                      stays: once m is NaN nothing replaces it, and a NaN s replaces any number.  The weights only gate.
+//   COMPOUND_MEDIAN    a loop of its own: 16 values x 4 pixels x 8 frames do not fit a lane's registers, so the median walks its frames ONE
+//                      at a time and makes the points of every view again for each frame (the maps come from the cache: two coalesced
+//                      loads per view and pixel beside the four gathered taps).  The views loop is unrolled over the N bucket NB (4, 8 or
+//                      16, chosen by the launcher) so that every value has a register of its own: slot n holds view n's blend, +inf where
+//                      the view does not contribute, the slot is past N or the blend is NaN (the NaN is remembered in a flag beside the
+//                      values).  MEDIAN_PIX pixels of the lane's four are in flight at a time.  The values are ordered by Batcher's
+//                      odd-even merge network (5, 19, 63 compare-exchanges of one v_min and one v_max each; the pads end up on top), and
+//                      the middle one or two are picked by a select chain on the count.
 constexpr int COMPOUND_GROUP = 8;
-template <bool OUT8, bool VEC_OUT>
+#ifndef MCRT_MEDIAN_PIX
+#define MCRT_MEDIAN_PIX 4                  // pixels of a lane's four that the median holds values for at once: 4, 2 or 1 (measured)
+#endif
+constexpr int MEDIAN_PIX = MCRT_MEDIAN_PIX;
+static_assert(MEDIAN_PIX == 1 || MEDIAN_PIX == 2 || MEDIAN_PIX == 4, "MCRT_MEDIAN_PIX divides the lane's four pixels");
+
+// a view's weight at a pixel whose column map is mx: one rounding per operation (include/mcrt.h; mcrt_compound_weights is the host's copy)
+MCRT_DEV float compound_weight(float mx, float last_line, float view_weight, float feather)
+{
+    const float a = feather > 0.0f ? fminf(fmaxf(fminf(mx, last_line - mx) / feather, 0.0f), 1.0f) : 1.0f;
+    return view_weight * a;
+}
+
+// Batcher's odd-even merge sort of NB values (any NB; the kernel uses 4, 8 and 16) as a list of compare-exchanges (lo, hi), made at compile time: every index the kernel
+// uses is a constant, so the values stay in registers
+template <int NB> struct SortNet {
+    int lo[NB * 4], hi[NB * 4], n;
+    constexpr SortNet() : lo(), hi(), n(0)
+    {
+        for (int p = 1; p < NB; p *= 2)
+            for (int k = p; k >= 1; k /= 2)
+                for (int j = k % p; j <= NB - 1 - k; j += 2 * k)
+                    for (int i = 0; i <= (k - 1 < NB - j - k - 1 ? k - 1 : NB - j - k - 1); i++)
+                        if ((i + j) / (2 * p) == (i + j + k) / (2 * p)) { lo[n] = i + j; hi[n] = i + j + k; n++; }
+    }
+};
+template <int NB, int I> struct SortStep { static constexpr SortNet<NB> net = SortNet<NB>(); static constexpr int lo = net.lo[I], hi = net.hi[I]; };
+template <int NB, int PIX, int I> MCRT_DEV void sort_steps(float (&v)[NB][PIX])
+{
+    if constexpr (I < SortNet<NB>().n) {
+        constexpr int lo = SortStep<NB, I>::lo, hi = SortStep<NB, I>::hi;
+#pragma unroll
+        for (int q = 0; q < PIX; q++) {
+            const float a = v[lo][q], b = v[hi][q];
+            v[lo][q] = fminf(a, b); v[hi][q] = fmaxf(a, b);
+        }
+        sort_steps<NB, PIX, I + 1>(v);
+    }
+}
+// the median of the c smallest of NB ordered values (c <= NB): v[(c-1)/2] for an odd c, the mean of v[c/2-1] and v[c/2] for an even one
+template <int NB, int PIX> MCRT_DEV float median_pick(const float (&v)[NB][PIX], int q, uint32_t c)
+{
+    const uint32_t il = (c - 1u) >> 1, ih = c >> 1;        // (c odd: the same slot)
+    float lo = v[0][q], hi = v[0][q];
+#pragma unroll
+    for (int i = 1; i <= NB / 2; i++) {
+        if (i < NB / 2) lo = il == (uint32_t)i ? v[i][q] : lo;
+        hi = ih == (uint32_t)i ? v[i][q] : hi;
+    }
+    return (c & 1u) ? lo : (lo + hi) * 0.5f;
+}
+
+template <bool OUT8, bool VEC_OUT, int MODE = COMPOUND_PLAIN, int NB = 0>
 __global__ void __launch_bounds__(256) k_compound(CompoundArgs a)
 {
     const uint32_t lane = threadIdx.x & 63u;
@@ -197,72 +264,134 @@ __global__ void __launch_bounds__(256) k_compound(CompoundArgs a)
         for (int j = 0; j < 4; j++) y[j] = p0 + 64u * j < a.n ? a.state[p0 + 64u * j] : 0.0f;
         have_prev = true;
     }
-    for (uint32_t g0 = f0; g0 < f1; g0 += (uint32_t)COMPOUND_GROUP) {
-        const uint32_t ng = min((uint32_t)COMPOUND_GROUP, f1 - g0);
-        float sum[COMPOUND_GROUP][4];
-        float looks[4] = { 0.0f, 0.0f, 0.0f, 0.0f };       // views that cover each pixel (at most 16: exact in float)
-#pragma unroll
-        for (int k = 0; k < COMPOUND_GROUP; k++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) sum[k][j] = 0.0f;
-        for (uint32_t n = 0; n < N; n++) {
-            const float *mc = a.maps + (size_t)(2u * n) * a.n_pad + p0, *mr = mc + a.n_pad;   // (n_pad % 256 == 0: p0 + 192 < n_pad)
-            RemapPoint pt[4];
-            bool covered[4];
+    // frame f's four compounded values of this lane leave: persistence, quantisation and the word store, or the floats
+    auto emit = [&](uint32_t f, const float (&v)[4]) {
+        if (OUT8) {
+            uint32_t bytes = 0u;                    // byte j: pixel p0 + 64 j
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                const float mx = mc[64 * j], my = mr[64 * j];
-                pt[j] = remap_point(mx, my);
-                covered[j] = (mx == mx) && (my == my) && pt[j].x0 >= -1 && pt[j].x0 < (long long)E && pt[j].y0 >= -1 && pt[j].y0 < (long long)R;
-                looks[j] = covered[j] ? looks[j] + 1.0f : looks[j];
+                if (!smooth) y[j] = v[j];
+                else y[j] = fmaf(a.alpha, have_prev ? y[j] : v[j], (1.0f - a.alpha) * v[j]);
+                bytes |= (uint32_t)(uint8_t)(y[j] * 255.0f + 0.5f) << (8 * j);
             }
+            have_prev = true;
+            uint8_t *o = (uint8_t *)a.out + (size_t)f * a.n;
+            if (VEC_OUT && whole) {                 // pixel wb + 4 L + i is byte L / 16 of lane (4 L + i) % 64: every lane is active here
+                uint32_t word = 0u;
 #pragma unroll
-            for (int k = 0; k < COMPOUND_GROUP; k++) {
-                if ((uint32_t)k < ng) {                     // (the same in every lane)
-                    const float *g = a.src + ((size_t)(g0 + (uint32_t)k) * N + n) * view;
+                for (int i = 0; i < 4; i++) {
+                    const uint32_t got = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((4u * lane + (uint32_t)i) & 63u) * 4u), (int)bytes);
+                    word |= ((got >> (8u * (lane >> 4))) & 0xffu) << (8 * i);
+                }
+                *(uint32_t *)(o + wb + 4u * lane) = word;
+            } else {
 #pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        float t[2][2];
-                        remap_taps(pt[j], E, R, [=](long long x, long long yy) { return g[(size_t)x * R + (size_t)yy]; }, t);
-                        const float s = remap_blend(pt[j], t);
-                        sum[k][j] = covered[j] ? sum[k][j] + s : sum[k][j];
+                for (int j = 0; j < 4; j++) if (p0 + 64u * j < a.n) o[p0 + 64u * j] = (uint8_t)(bytes >> (8 * j));
+            }
+        } else {
+            float *o = (float *)a.out + (size_t)f * a.n;
+#pragma unroll
+            for (int j = 0; j < 4; j++) if (p0 + 64u * j < a.n) o[p0 + 64u * j] = v[j];
+        }
+    };
+    if constexpr (MODE == COMPOUND_MEDIAN) {
+        const float last_line = (float)(E - 1u), inf = __builtin_inff();
+        for (uint32_t f = f0; f < f1; f++) {
+            float v[4];
+#pragma unroll
+            for (int j0 = 0; j0 < 4; j0 += MEDIAN_PIX) {
+                float s[NB][MEDIAN_PIX];
+                uint32_t cnt[MEDIAN_PIX];
+                bool bad[MEDIAN_PIX];
+#pragma unroll
+                for (int q = 0; q < MEDIAN_PIX; q++) { cnt[q] = 0u; bad[q] = false; }
+#pragma unroll
+                for (int n = 0; n < NB; n++) {
+                    if ((uint32_t)n < N) {                  // (the same in every lane)
+                        const float *mc = a.maps + (size_t)(2u * n) * a.n_pad + p0, *mr = mc + a.n_pad;
+                        const float *g = a.src + ((size_t)f * N + (uint32_t)n) * view;
+                        const float wv = a.weight[n];
+#pragma unroll
+                        for (int q = 0; q < MEDIAN_PIX; q++) {
+                            const float mx = mc[64 * (j0 + q)], my = mr[64 * (j0 + q)];
+                            const RemapPoint pt = remap_point(mx, my);
+                            const bool in = (mx == mx) && (my == my) && pt.x0 >= -1 && pt.x0 < (long long)E && pt.y0 >= -1 && pt.y0 < (long long)R
+                                            && compound_weight(mx, last_line, wv, a.feather) > 0.0f;
+                            float t[2][2];
+                            remap_taps(pt, E, R, [=](long long x, long long yy) { return g[(size_t)x * R + (size_t)yy]; }, t);
+                            const float b = remap_blend(pt, t);
+                            const bool number = b == b;
+                            cnt[q] = in ? cnt[q] + 1u : cnt[q];
+                            bad[q] = bad[q] || (in && !number);
+                            s[n][q] = in && number ? b : inf;
+                        }
+                    } else {
+#pragma unroll
+                        for (int q = 0; q < MEDIAN_PIX; q++) s[n][q] = inf;
+                    }
+                }
+                sort_steps<NB, MEDIAN_PIX, 0>(s);
+#pragma unroll
+                for (int q = 0; q < MEDIAN_PIX; q++) {
+                    const float m = median_pick<NB, MEDIAN_PIX>(s, q, cnt[q]);
+                    v[j0 + q] = cnt[q] == 0u ? 0.0f : bad[q] ? __builtin_nanf("") : m + 0.0f;
+                }
+            }
+            emit(f, v);
+        }
+    } else {
+        const float last_line = (float)(E - 1u);
+        for (uint32_t g0 = f0; g0 < f1; g0 += (uint32_t)COMPOUND_GROUP) {
+            const uint32_t ng = min((uint32_t)COMPOUND_GROUP, f1 - g0);
+            float sum[COMPOUND_GROUP][4];
+            float looks[4] = { 0.0f, 0.0f, 0.0f, 0.0f };       // views that cover each pixel (at most 16: exact in float); WEIGHTED: the sum of their weights
+#pragma unroll
+            for (int k = 0; k < COMPOUND_GROUP; k++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) sum[k][j] = MODE == COMPOUND_MAX ? -__builtin_inff() : 0.0f;
+            for (uint32_t n = 0; n < N; n++) {
+                const float *mc = a.maps + (size_t)(2u * n) * a.n_pad + p0, *mr = mc + a.n_pad;   // (n_pad % 256 == 0: p0 + 192 < n_pad)
+                RemapPoint pt[4];
+                bool covered[4];
+                float w[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const float mx = mc[64 * j], my = mr[64 * j];
+                    pt[j] = remap_point(mx, my);
+                    covered[j] = (mx == mx) && (my == my) && pt[j].x0 >= -1 && pt[j].x0 < (long long)E && pt[j].y0 >= -1 && pt[j].y0 < (long long)R;
+                    if constexpr (MODE == COMPOUND_PLAIN) { w[j] = 1.0f; looks[j] = covered[j] ? looks[j] + 1.0f : looks[j]; }
+                    else {
+                        w[j] = compound_weight(mx, last_line, a.weight[n], a.feather);
+                        covered[j] = covered[j] && w[j] > 0.0f;
+                        looks[j] = covered[j] ? looks[j] + (MODE == COMPOUND_WEIGHTED ? w[j] : 1.0f) : looks[j];
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < COMPOUND_GROUP; k++) {
+                    if ((uint32_t)k < ng) {                     // (the same in every lane)
+                        const float *g = a.src + ((size_t)(g0 + (uint32_t)k) * N + n) * view;
+#pragma unroll
+                        for (int j = 0; j < 4; j++) {
+                            float t[2][2];
+                            remap_taps(pt[j], E, R, [=](long long x, long long yy) { return g[(size_t)x * R + (size_t)yy]; }, t);
+                            const float s = remap_blend(pt[j], t);
+                            if constexpr (MODE == COMPOUND_PLAIN) sum[k][j] = covered[j] ? sum[k][j] + s : sum[k][j];
+                            else if constexpr (MODE == COMPOUND_WEIGHTED) sum[k][j] = covered[j] ? sum[k][j] + w[j] * s : sum[k][j];
+                            else sum[k][j] = covered[j] && (sum[k][j] == sum[k][j]) && !(s <= sum[k][j]) ? s : sum[k][j];
+                        }
                     }
                 }
             }
-        }
 #pragma unroll
-        for (int k = 0; k < COMPOUND_GROUP; k++) {
-            if ((uint32_t)k < ng) {
-                const uint32_t f = g0 + (uint32_t)k;
-                float v[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) v[j] = looks[j] > 0.0f ? sum[k][j] / looks[j] : 0.0f;
-                if (OUT8) {
-                    uint32_t bytes = 0u;                    // byte j: pixel p0 + 64 j
+            for (int k = 0; k < COMPOUND_GROUP; k++) {
+                if ((uint32_t)k < ng) {
+                    float v[4];
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
-                        if (!smooth) y[j] = v[j];
-                        else y[j] = fmaf(a.alpha, have_prev ? y[j] : v[j], (1.0f - a.alpha) * v[j]);
-                        bytes |= (uint32_t)(uint8_t)(y[j] * 255.0f + 0.5f) << (8 * j);
+                        if constexpr (MODE == COMPOUND_MAX) v[j] = looks[j] > 0.0f ? sum[k][j] + 0.0f : 0.0f;
+                        else v[j] = looks[j] > 0.0f ? sum[k][j] / looks[j] : 0.0f;
                     }
-                    have_prev = true;
-                    uint8_t *o = (uint8_t *)a.out + (size_t)f * a.n;
-                    if (VEC_OUT && whole) {                 // pixel wb + 4 L + i is byte L / 16 of lane (4 L + i) % 64: every lane is active here
-                        uint32_t word = 0u;
-#pragma unroll
-                        for (int i = 0; i < 4; i++) {
-                            const uint32_t got = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((4u * lane + (uint32_t)i) & 63u) * 4u), (int)bytes);
-                            word |= ((got >> (8u * (lane >> 4))) & 0xffu) << (8 * i);
-                        }
-                        *(uint32_t *)(o + wb + 4u * lane) = word;
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 4; j++) if (p0 + 64u * j < a.n) o[p0 + 64u * j] = (uint8_t)(bytes >> (8 * j));
-                    }
-                } else {
-                    float *o = (float *)a.out + (size_t)f * a.n;
-#pragma unroll
-                    for (int j = 0; j < 4; j++) if (p0 + 64u * j < a.n) o[p0 + 64u * j] = v[j];
+                    emit(g0 + (uint32_t)k, v);
                 }
             }
         }
@@ -308,14 +437,28 @@ hipError_t launch_bmode(const BmodeArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
+// a.mode picks the instantiation; the median's views loop is unrolled over the smallest bucket that holds a.N
 hipError_t launch_compound(const CompoundArgs &a, bool out8, hipStream_t st)
 {
     const uint32_t chunks = (a.F + a.frames_per_chunk - 1u) / a.frames_per_chunk;
     const dim3 grid((a.n + 1023u) / 1024u, chunks), blk(256);
     const bool vec = a.n % 4u == 0u && (uintptr_t)a.out % 4u == 0u;          // the 8-bit form's one word per lane
-    if (!out8) hipLaunchKernelGGL((k_compound<false, false>), grid, blk, 0, st, a);
-    else if (vec) hipLaunchKernelGGL((k_compound<true, true>), grid, blk, 0, st, a);
-    else hipLaunchKernelGGL((k_compound<true, false>), grid, blk, 0, st, a);
+#define MCRT_COMPOUND(...) do { \
+        if (!out8) hipLaunchKernelGGL((k_compound<false, false, __VA_ARGS__>), grid, blk, 0, st, a); \
+        else if (vec) hipLaunchKernelGGL((k_compound<true, true, __VA_ARGS__>), grid, blk, 0, st, a); \
+        else hipLaunchKernelGGL((k_compound<true, false, __VA_ARGS__>), grid, blk, 0, st, a); } while (0)
+    switch (a.mode) {
+    case COMPOUND_PLAIN: MCRT_COMPOUND(COMPOUND_PLAIN, 0); break;
+    case COMPOUND_WEIGHTED: MCRT_COMPOUND(COMPOUND_WEIGHTED, 0); break;
+    case COMPOUND_MAX: MCRT_COMPOUND(COMPOUND_MAX, 0); break;
+    case COMPOUND_MEDIAN:
+        if (a.N <= 4u) MCRT_COMPOUND(COMPOUND_MEDIAN, 4);
+        else if (a.N <= 8u) MCRT_COMPOUND(COMPOUND_MEDIAN, 8);
+        else MCRT_COMPOUND(COMPOUND_MEDIAN, 16);
+        break;
+    default: return hipErrorInvalidValue;
+    }
+#undef MCRT_COMPOUND
     return hipGetLastError();
 }
 

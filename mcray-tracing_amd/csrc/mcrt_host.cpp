@@ -444,6 +444,31 @@ extern "C" int mcrt_transducer_steered(uint32_t n, double radius_cm, double sep_
     return MCRT_OK;
 }
 
+// the weight view `steer_rad` contributes with at every pixel (include/mcrt.h): k_compound's own float expression -- the coverage rule on the
+// floors of the maps, the lateral ramp of the column map, the view weight -- over mcrt_compound_maps' maps
+extern "C" int mcrt_compound_weights(uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t max_travel_us, uint32_t speed_of_sound,
+                                     uint32_t orows, uint32_t ocols, float steer_rad, float view_weight, float feather_lines, float *w)
+{
+    if (!w) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_compound_weights: null w");
+    if (!(std::isfinite(view_weight) && view_weight >= 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_compound_weights: view_weight must be finite and >= 0 (%g)", (double)view_weight);
+    if (!(std::isfinite(feather_lines) && feather_lines >= 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_compound_weights: feather_lines must be finite and >= 0 (%g)", (double)feather_lines);
+    if (E == 0 || R == 0 || orows == 0 || ocols == 0) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_compound_weights: bad arguments");
+    const size_t n = (size_t)orows * ocols;
+    std::vector<float> mr(n), mc(n);
+    const int rc = mcrt_compound_maps(E, R, radius_mm, total_angle, max_travel_us, speed_of_sound, orows, ocols, steer_rad, mr.data(), mc.data());
+    if (rc != MCRT_OK) return rc;
+    const float last_line = (float)(E - 1u);
+    for (size_t i = 0; i < n; i++) {
+        const float mx = mc[i], my = mr[i];
+        const float fx = std::floor(mx), fy = std::floor(my);           // (compared as floats: the kernel's integer comparisons without the conversion)
+        const bool covered = (mx == mx) && (my == my) && fx >= -1.0f && (double)fx < (double)E && fy >= -1.0f && (double)fy < (double)R;
+        const float a = feather_lines > 0.0f ? std::fmin(std::fmax(std::fmin(mx, last_line - mx) / feather_lines, 0.0f), 1.0f) : 1.0f;
+        const float wt = view_weight * a;
+        w[i] = covered && wt > 0.0f ? wt : 0.0f;
+    }
+    return MCRT_OK;
+}
+
 // ---- slice thickness (psf.h:16-18,42,77; the contracts are in include/mcrt.h) -------------------
 // the probe's elevation direction: (0,0,1) through the rotations mcrt_transducer_elements applies to an element's direction
 extern "C" int mcrt_transducer_elevation_axis(const float angles_deg[3], float axis[3])

@@ -86,7 +86,12 @@ struct CompoundArgs {
     void *out;                          // float or uint8_t [F][n]
     float alpha;
     uint32_t E, R, n, n_pad, F, N, frames_per_chunk, reset;
+    uint32_t mode;                      // COMPOUND_*: which k_compound runs
+    float feather;                      // mcrt_compound_opts::feather_lines (COMPOUND_PLAIN does not read it)
+    float weight[16];                   // mcrt_compound_opts::view_weight, the first N (COMPOUND_PLAIN does not read them)
 };
+// COMPOUND_PLAIN is the mean of mcrt_compound_frames (every weight 1, no feathering); the others are mcrt_compound_opts' modes
+enum { COMPOUND_PLAIN = 0, COMPOUND_WEIGHTED = 1, COMPOUND_MAX = 2, COMPOUND_MEDIAN = 3 };
 
 hipError_t launch_init(const FrameArgs &a, hipStream_t st);
 hipError_t launch_trace(const FrameArgs &a, uint32_t b, bool stats, hipStream_t st);
@@ -110,7 +115,7 @@ hipError_t launch_bmode_peak(const float *rf, uint32_t F, uint32_t E, uint32_t R
 hipError_t launch_bmode_grey(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, const float *peak /*[F] or null: ref*/, float ref,
                              float *peak_out /*[F] or null*/, uint32_t mode, float gain, float dr, float *grey, hipStream_t st);
 hipError_t launch_bmode(const BmodeArgs &a, hipStream_t st);
-hipError_t launch_compound(const CompoundArgs &a, bool out8, hipStream_t st);
+hipError_t launch_compound(const CompoundArgs &a, bool out8, hipStream_t st);   // a.mode: the instantiation
 hipError_t launch_blocks_to_frames(const float *blocks, float *frames, uint32_t F, uint32_t E, uint32_t R, uint32_t G, const uint32_t *off /*[G+1]*/, hipStream_t st);   // at most 64 ranks
 hipError_t launch_transpose(const float *in, float *out, uint32_t E, uint32_t R, hipStream_t st);
 hipError_t launch_math_probe(int op, const double *x, const double *y, double *out, uint32_t n, hipStream_t st);

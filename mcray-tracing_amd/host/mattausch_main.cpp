@@ -2,6 +2,7 @@
 //     mattausch_hip <scene.json> [frames] [samples] [out.pgm] [rf.bin] [--gpus N | --devices 0,1,...]
 //                   [--db DR] [--gain G] [--ref-log] [--persistence A] [--focus-mm F1[,F2,...]] [--focal-range-mm R]
 //                   [--elevation K] [--elevation-pitch-um P] [--var-z V] [--compound N] [--compound-step-deg D]
+//                   [--compound-mode mean|max|median] [--compound-feather LINES] [--compound-weights w0,w1,...]
 // --gpus N: the first N GPUs of the node, the frame's scan-lines sharded over them (mcrt_group_*: one tracing context and host thread per
 // GPU, the blocks gathered on GPU 0); --devices lists them explicitly, and may repeat one (two ranks sharing a GPU: the one-GPU test).
 // Same constants (main.cpp:23-37), same frame loop body; instead of blocking on imshow/waitKey every frame it
@@ -22,6 +23,10 @@
 // (mcrt_compound_frames, or mcrt_bmode_compound_frames with a display option).  rf.bin then holds the unsteered view.  Without --compound
 // nothing changes and --compound-step-deg has no effect; --compound 1 is the plain run again.  It does not combine with --elevation here
 // (the Python Simulator does both).
+// --compound-mode max or median takes the largest or the middle look of every pixel in place of their mean; --compound-feather LINES ramps
+// every view's weight up over its first and last LINES scan-lines, which hides where a steered view's coverage ends; --compound-weights
+// gives each of the N views a weight (mcrt_compound_opts).  Each of the three needs --compound; at their defaults (mean, 0, all 1) the
+// picture is the plain compound's byte for byte.
 #include "mcrt_host.hpp"
 #include <chrono>
 #include <cmath>
@@ -50,6 +55,8 @@ int main(int argc, char **argv)
     bool elevation_given = false;
     int compound = 0; double compound_step_deg = 5.0;                         // compound 0: off
     bool compound_given = false;
+    mcrt_compound_opts copts; mcrt_default_compound_opts(&copts);
+    const char *compound_mode = nullptr, *compound_feather = nullptr, *compound_weights = nullptr;   // the options as given
     {   // the options, taken out of the positional arguments
         int keep = 1;
         for (int i = 1; i < argc; i++) {
@@ -68,6 +75,9 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--var-z") && i + 1 < argc) var_z = (float)std::atof(argv[++i]);
             else if (!std::strcmp(argv[i], "--compound") && i + 1 < argc) { compound = std::atoi(argv[++i]); compound_given = true; }
             else if (!std::strcmp(argv[i], "--compound-step-deg") && i + 1 < argc) compound_step_deg = std::atof(argv[++i]);
+            else if (!std::strcmp(argv[i], "--compound-mode") && i + 1 < argc) compound_mode = argv[++i];
+            else if (!std::strcmp(argv[i], "--compound-feather") && i + 1 < argc) compound_feather = argv[++i];
+            else if (!std::strcmp(argv[i], "--compound-weights") && i + 1 < argc) compound_weights = argv[++i];
             else if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) { devices.clear(); for (int d = 0; d < std::max(1, std::atoi(argv[i + 1])); d++) devices.push_back(d); i++; }
             else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {
                 devices.clear();
@@ -90,6 +100,25 @@ int main(int argc, char **argv)
         if (compound_given && (compound < 1 || compound > 15 || compound % 2 == 0))
             throw std::invalid_argument("--compound takes an odd number of views, 1..15");
         if (compound_given && elevation_given) throw std::invalid_argument("--compound and --elevation do not combine in this program");
+        if (!compound_given && (compound_mode || compound_feather || compound_weights))
+            throw std::invalid_argument(std::string(compound_mode ? "--compound-mode" : compound_feather ? "--compound-feather" : "--compound-weights") + " needs --compound");
+        if (compound_mode) {
+            if (!std::strcmp(compound_mode, "mean")) copts.mode = MCRT_COMPOUND_MEAN;
+            else if (!std::strcmp(compound_mode, "max")) copts.mode = MCRT_COMPOUND_MAX;
+            else if (!std::strcmp(compound_mode, "median")) copts.mode = MCRT_COMPOUND_MEDIAN;
+            else throw std::invalid_argument("--compound-mode takes mean, max or median");
+        }
+        if (compound_feather) {
+            copts.feather_lines = (float)std::atof(compound_feather);
+            if (!(std::isfinite(copts.feather_lines) && copts.feather_lines >= 0.0f)) throw std::invalid_argument("--compound-feather takes a number of scan-lines >= 0");
+        }
+        if (compound_weights) {
+            std::vector<float> w;
+            for (const char *q = compound_weights; *q;) { w.push_back((float)std::atof(q)); while (*q && *q != ',') q++; if (*q == ',') q++; }
+            if ((int)w.size() != compound) throw std::invalid_argument("--compound-weights takes one weight per view of --compound (" + std::to_string(compound) + ")");
+            for (size_t n = 0; n < w.size(); n++) copts.view_weight[n] = w[n];
+        }
+        const mcrt_compound_opts *opts = compound_mode || compound_feather || compound_weights ? &copts : nullptr;
         std::vector<float> steers;                    // centred on the unsteered view, ascending
         for (int n = 0; n < compound; n++) steers.push_back((float)((double)(n - (compound - 1) / 2) * compound_step_deg * 3.14159265358979323846 / 180.0));
         for (float s : steers)
@@ -119,7 +148,7 @@ int main(int argc, char **argv)
             else rf_image.trace((uint32_t)f);      // clear + cast_rays + accumulation (main.cpp:102-144)
             rf_image.convolve(psf);           // main.cpp:146
             rf_image.envelope();              // main.cpp:147
-            if (compound_given) { if (bmode) rf_image.postprocess(display, steers); else rf_image.postprocess(steers); }   // the views averaged
+            if (compound_given) { if (bmode) rf_image.postprocess(display, steers, nullptr, opts); else rf_image.postprocess(steers, opts); }   // the views averaged (or opts' mode)
             else if (bmode) rf_image.postprocess(display);   // main.cpp:148, log-compressed to 8-bit grey
             else rf_image.postprocess();      // main.cpp:148
         }

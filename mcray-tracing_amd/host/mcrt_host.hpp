@@ -736,11 +736,13 @@ public:
         to_device(); check(mcrt_envelope(dev->ctx, rf_dev, columns, max_rows), "mcrt_envelope");
     }
     // the views of trace(frame, transducer, steer_rad) compounded into the float picture scan_converted() / save() read (mcrt_compound_frames):
-    // every pixel the mean of the views that cover it
-    void postprocess(const std::vector<float> &steer_rad)
+    // every pixel the mean of the views that cover it; with opts (mcrt_compound_opts: weights per view, a lateral edge ramp, max or median)
+    // through mcrt_compound_frames_opts
+    void postprocess(const std::vector<float> &steer_rad, const mcrt_compound_opts *opts = nullptr)
     {
         const mcrt_compound cp = compound_of(steer_rad);
-        check(mcrt_compound_frames(dev->ctx, views_dev, 1, columns, max_rows, radius_mm, angle, &cp, scan_dev, 400, 500), "mcrt_compound_frames");
+        if (opts) check(mcrt_compound_frames_opts(dev->ctx, views_dev, 1, columns, max_rows, radius_mm, angle, &cp, scan_dev, 400, 500, opts), "mcrt_compound_frames_opts");
+        else check(mcrt_compound_frames(dev->ctx, views_dev, 1, columns, max_rows, radius_mm, angle, &cp, scan_dev, 400, 500), "mcrt_compound_frames");
     }
     void postprocess() { to_device(); check(mcrt_scan_convert(dev->ctx, rf_dev, columns, max_rows, radius_mm, angle, scan_dev, 400, 500), "mcrt_scan_convert"); }
     // the displayed picture instead of the float scan conversion: log compression (dynamic range, gain, TGC) and 8-bit grey on the GPU
@@ -756,11 +758,13 @@ public:
         state_valid = true; bmode_rows = bp.out_rows; bmode_cols = bp.out_cols;
     }
     // the same over the views of trace(frame, transducer, steer_rad) (mcrt_bmode_compound_frames): one reference per frame, the peak of all views
-    void postprocess(const mcrt_bmode_params &bp, const std::vector<float> &steer_rad, const float *tgc_db = nullptr)
+    // (opts: as above, through mcrt_bmode_compound_frames_opts)
+    void postprocess(const mcrt_bmode_params &bp, const std::vector<float> &steer_rad, const float *tgc_db = nullptr, const mcrt_compound_opts *opts = nullptr)
     {
         const mcrt_compound cp = compound_of(steer_rad);
         const mcrt_bmode_params p = bmode_prepare(bp);
-        check(mcrt_bmode_compound_frames(dev->ctx, views_dev, 1, columns, max_rows, &p, &cp, tgc_db, state_dev, nullptr, bmode_dev), "mcrt_bmode_compound_frames");
+        if (opts) check(mcrt_bmode_compound_frames_opts(dev->ctx, views_dev, 1, columns, max_rows, &p, &cp, tgc_db, state_dev, nullptr, bmode_dev, opts), "mcrt_bmode_compound_frames_opts");
+        else check(mcrt_bmode_compound_frames(dev->ctx, views_dev, 1, columns, max_rows, &p, &cp, tgc_db, state_dev, nullptr, bmode_dev), "mcrt_bmode_compound_frames");
         state_valid = true; bmode_rows = bp.out_rows; bmode_cols = bp.out_cols;
     }
     std::vector<unsigned char> bmode() const   // the last postprocess(bmode_params) frame, row-major [out_rows][out_cols]
