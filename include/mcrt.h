@@ -40,7 +40,9 @@ extern "C" {
                                    + mcrt_compound, mcrt_transducer_steered, mcrt_compound_maps, mcrt_compound_frames, mcrt_bmode_compound_frames (spatial
                                    compounding: steered views of one plane traced as one pose pass and averaged in image space);
                                    + mcrt_compound_opts, mcrt_default_compound_opts, mcrt_compound_weights, mcrt_compound_frames_opts,
-                                   mcrt_bmode_compound_frames_opts (compounding modes: per-view weights, a lateral edge ramp, max, median; additive) */
+                                   mcrt_bmode_compound_frames_opts (compounding modes: per-view weights, a lateral edge ramp, max, median; additive);
+                                   + mcrt_sweep, mcrt_volume_grid, mcrt_transducer_swept, mcrt_volume_maps, mcrt_volume_frames, mcrt_bmode_volume_frames
+                                   (volume imaging: a probe swept in elevation, 3-D scan conversion into voxels or any cut; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -455,6 +457,86 @@ int mcrt_bmode_compound_frames_opts(mcrt_ctx *ctx, const float *rf_dev /* [n_fra
 int mcrt_compound_weights(uint32_t n_elements, uint32_t n_rows, double radius_mm, double total_angle_rad, uint32_t max_travel_us,
                           uint32_t speed_of_sound, uint32_t out_rows, uint32_t out_cols, float steer_rad, float view_weight, float feather_lines,
                           float *w /* [out_rows][out_cols] */);
+
+/* ---- volume imaging: the curved array that wobbles in elevation (the "4D" abdominal or obstetric probe) and the pictures no 2-D probe can
+ * show: the C-plane (a cut at constant depth), the sagittal cut, any oblique cut, or a whole block of voxels.  The reference has one plane.
+ * A volume is K tilted copies of the probe traced as ONE pose pass (mcrt_trace_frames_poses / mcrt_group_trace_frames_poses) into a stack
+ * [K][E][R]; convolution and envelope run over the K planes as over K frames; then every output point is gathered from the stack through
+ * three maps (plane, row, column): a trilinear scan conversion.  Parallel planes need nothing of this: mcrt_elevation_planes followed by
+ * mcrt_scan_convert_frames already is that volume.
+ *
+ * The probe-local frame: millimetres, origin at the arc's centre, x lateral (the direction of growing element number), y the arc's axis
+ * (element angle 0), z elevation -- the frame BEFORE mcrt_transducer_elements' three rotations and `position`.
+ * A sweep has K planes; plane k is the array tilted about the line parallel to x through (0, pivot_mm, 0) by
+ *   theta_k = (k - (K-1)/2.0) * step_rad
+ * The centring is real-valued: an even K has no plane at tilt 0 (K = 2: -step/2 and +step/2).
+ * Forward geometry, the specification of everything below: the point at path length t on the beam of the element at arc angle phi in a
+ * plane tilted by theta is, with a = radius + t,
+ *   P = ( a sin(phi),   pivot + (a cos(phi) - pivot) cos(theta),   (a cos(phi) - pivot) sin(theta) )
+ *
+ * The frame-id rule (applied by the wrappers: Simulator(sweep=...), rf_image::trace(frame, transducer, sweep), mattausch_hip --sweep): plane k
+ * of volume f of a pass that starts at frame id f0 is traced with frame id (f0 + f) * K + k. */
+typedef struct { uint32_t n_planes;     /* K, 1..256 */
+                 float    step_rad;     /* finite, > 0, and (K-1)/2 * step_rad < pi/2 */
+                 float    pivot_mm;     /* finite; where on the arc's axis the wobble's axis crosses (0: the arc's centre, radius_mm: the apex) */
+} mcrt_sweep;                           /* 12 bytes: n_planes 0, step_rad 4, pivot_mm 8 */
+/* the output points, in the probe-local frame: point (i, j, l) = ((origin + i*du) + j*dv) + l*dw per component, evaluated in double in
+ * exactly that order; i < nu, j < nv, l < nw.  The output layout is [nw][nv][nu], u fastest.  nw = 1 is a cut -- any plane in any
+ * orientation; a volume and a cut are the same call.  Every entry must be finite; the axes need be neither orthogonal nor of equal length. */
+typedef struct { double origin_mm[3], du_mm[3], dv_mm[3], dw_mm[3];
+                 uint32_t nu, nv, nw, _pad;
+} mcrt_volume_grid;                     /* 112 bytes: origin_mm 0, du_mm 24, dv_mm 48, dw_mm 72, nu 96, nv 100, nw 104 */
+/* mcrt_transducer_elements with the array tilted by tilt_rad about the sweep's axis.  tilt_rad == 0 takes mcrt_transducer_elements' path:
+ * its tables bit for bit.  Otherwise, with mcrt_transducer_elements' own `angle` and rf = (float)radius_cm:
+ *   a = (float)angle,  s = sinf(a),  c = cosf(a),  ct = cosf(tilt_rad),  st = sinf(tilt_rad),  yp = (float)(pivot_mm / 10.0)       [cm]
+ *   local direction (s, c*ct, c*st);   local position (rf*s, yp + (rf*c - yp)*ct, (rf*c - yp)*st)
+ * one float rounding per operation, each through the same three rotations, pos = position + rot(local position).  Host only.
+ * MCRT_ERR_INVALID for null pointers, n_elements == 0, a tilt that is not finite or has |tilt| >= pi/2, a pivot that is not finite; on an
+ * error nothing is written. */
+int mcrt_transducer_swept(uint32_t n_elements, double radius_cm, double separation_mm, const float position[3], const float angles_deg[3],
+                          float tilt_rad, float pivot_mm, float *pos, float *dir);
+/* the three maps of a grid, each [nw][nv][nu]: where in the stack [K][E][R] an output point (X, Y, Z) lies.  depth_mm_f is mcrt_scan_maps'
+ * own float; everything else is double, rounded once to float at the end:
+ *   h = sqrt((Y-pivot)^2 + Z^2),   theta = atan2(Z, Y-pivot),   y = pivot + h,   rho = sqrt(X^2 + y^2),   alpha = atan2(X, y)
+ *   map_plane = (float)(theta / step + (K-1)/2.0)
+ *   map_row   = (float)((rho - radius_mm) / depth_mm_f * R)
+ *   map_col   = (float)((alpha + total_angle/2) / total_angle * (double)(float)E)
+ * (the inverse of the forward geometry above; the column convention is mcrt_compound_maps', half-scan-line offset kept).  A point behind
+ * the pivot or beside the sweep gets a map_plane outside [0, K-1], which the gather treats plane by plane.  Host only.  MCRT_ERR_INVALID
+ * for mcrt_scan_maps' conditions (null maps, zero n_elements / n_rows, total_angle_rad not > 0), a null sweep or grid, a sweep outside the
+ * conditions of mcrt_sweep, a zero nu, nv or nw, a grid entry that is not finite; MCRT_ERR_LIMIT for nu*nv*nw >= 2^31.  On an error
+ * nothing is written. */
+int mcrt_volume_maps(uint32_t n_elements, uint32_t n_rows, double radius_mm, double total_angle_rad, uint32_t max_travel_us, uint32_t speed_of_sound,
+                     const mcrt_sweep *sweep, const mcrt_volume_grid *grid, float *map_plane, float *map_row, float *map_col);
+/* The K planes of every frame gathered into the grid's points.  rf_dev: device float [n_frames][K][E][R]; out_dev: device float
+ * [n_frames][nw][nv][nu].  Asynchronous on the context's stream, one launch.  Per frame and output point, with p, the four taps and the
+ * blend mcrt_scan_convert's own (floor and fractions of map_col and map_row):
+ *   mapped = none of the three maps is NaN
+ *   fz = floorf(map_plane);  az = map_plane - fz;  z0 = (long long)fz
+ *   v[d] = (mapped && 0 <= z0+d < K) ? (mcrt_scan_convert's bilinear expression at p on plane z0+d of the frame) : 0.0f        d = 0, 1
+ *   out  = v[0] * (1.0f - az) + v[1] * az
+ * one rounding per operation, no fma.  A plane outside the sweep is not read.  A NaN tap of a plane inside the sweep reaches its point even
+ * under weight 0, as in mcrt_scan_convert.  The maps are mcrt_volume_maps' with the context's max_travel_time and speed of sound.
+ * MCRT_ERR_INVALID for null pointers, zero sizes, a bad sweep, a bad grid or bad scan geometry, rf_dev overlapping out_dev; MCRT_ERR_LIMIT
+ * for n_rows > 2048, n_frames * K > 65535, or 2^31 points and more.  On any error nothing is launched and out_dev is untouched.
+ * The maps live on the device, [3][n_pad] per grid, keyed by the scan geometry, the sweep and the grid -- every double, float and integer
+ * compared on its own.  The context keeps the four most recently used grids: a volume and three orthogonal cuts per frame upload nothing
+ * after the first round, and nothing is allocated once a grid's maps exist.  Groups: call it on mcrt_group_root() after
+ * mcrt_group_trace_frames_poses. */
+int mcrt_volume_frames(mcrt_ctx *ctx, const float *rf_dev /* [n_frames][K][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
+                       double radius_mm, double total_angle_rad, const mcrt_sweep *sweep, const mcrt_volume_grid *grid,
+                       float *out_dev /* [n_frames][nw][nv][nu] */);
+/* mcrt_bmode_frames over a swept volume: rf_dev is [n_frames][K][E][R].  Steps 1-3 run over the K planes of a frame TOGETHER (the stack is
+ * n_frames images of K * E scan-lines): the automatic reference, and peak_dev[f], is the largest amplitude over the whole sweep of frame f.
+ * Step 4 is mcrt_volume_frames' expression applied to the grey levels; step 6 is unchanged.  p->persistence must be 0 (MCRT_ERR_INVALID
+ * otherwise: a volume-sized state is out of scope), and p->reset_state is not read.  The picture is the grid's: p->out_rows and p->out_cols
+ * are ignored (they may be 0); p->radius_mm and p->total_angle_rad describe the probe and are used.  Errors and limits: mcrt_bmode_frames'
+ * and mcrt_volume_frames', and MCRT_ERR_LIMIT for K * n_elements >= 2^32; on any error nothing is launched and out_dev and peak_dev are
+ * untouched. */
+int mcrt_bmode_volume_frames(mcrt_ctx *ctx, const float *rf_dev /* [n_frames][K][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
+                             const mcrt_bmode_params *p, const mcrt_sweep *sweep, const mcrt_volume_grid *grid,
+                             const float *tgc_db /* host [n_rows] or NULL */, float *peak_dev /* [n_frames] or NULL */,
+                             uint8_t *out_dev /* [n_frames][nw][nv][nu] */);
 
 /* device [E][R]  ->  host [R][E] row-major (the cv::Mat layout of rfimage.h:217); synchronous */
 int mcrt_export_rf(mcrt_ctx *ctx, const float *rf_dev, uint32_t n_elements, uint32_t n_rows, float *host_rows_by_cols);

@@ -10,7 +10,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, CompoundOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 
 # ------------------------------------------------------------------ host-side pieces (no GPU)
@@ -194,6 +194,64 @@ def host_compound_weights(n_elements, n_rows, steer_rad, view_weight=1.0, feathe
     return w
 
 
+def host_transducer_swept(n_elements, radius_cm, sep_mm, position, angles_deg, tilt_rad, pivot_mm=0.0):
+    """mcrt_transducer_swept: mcrt_transducer_elements with the array tilted by tilt_rad about the line parallel to the lateral axis through
+    (0, pivot_mm, 0) of the probe-local frame (tilt 0: the plain tables bit for bit)"""
+    pos = np.zeros((n_elements, 3), np.float32); d = np.zeros((n_elements, 3), np.float32)
+    p = np.asarray(position, np.float32); a = np.asarray(angles_deg, np.float32)
+    check(load_library().mcrt_transducer_swept(n_elements, radius_cm, sep_mm, ptr(p), ptr(a), tilt_rad, pivot_mm, ptr(pos), ptr(d)))
+    return pos, d
+
+
+def sweep_struct(n_planes, step_rad, pivot_mm=0.0):
+    """mcrt_sweep: n_planes planes step_rad apart, centred on tilt 0 (an even count has no plane AT 0), about the axis through (0, pivot_mm, 0)"""
+    sw = Sweep()
+    sw.n_planes, sw.step_rad, sw.pivot_mm = int(n_planes), float(step_rad), float(pivot_mm)
+    return sw
+
+
+def sweep_tilts(n_planes, step_rad):
+    """the planes' tilts [rad], float32: theta_k = (k - (K-1)/2.0) * step_rad with step_rad as the float the library is given"""
+    step = float(np.float32(step_rad))
+    return np.array([(k - (n_planes - 1) / 2.0) * step for k in range(n_planes)], np.float32)
+
+
+def volume_grid(origin_mm, du, dv, dw, nu, nv, nw=1):
+    """mcrt_volume_grid: point (i, j, l) = origin + i*du + j*dv + l*dw [mm, the probe-local frame: x lateral, y the arc's axis, z elevation];
+    the output is [nw][nv][nu].  nw = 1 is a cut."""
+    g = VolumeGrid()
+    for dst, src in ((g.origin_mm, origin_mm), (g.du_mm, du), (g.dv_mm, dv), (g.dw_mm, dw)):
+        for i in range(3):
+            dst[i] = float(src[i])
+    g.nu, g.nv, g.nw, g._pad = int(nu), int(nv), int(nw), 0
+    return g
+
+
+def cplane_grid(depth_mm, nu, nv, pitch_mm, x0_mm=None, z0_mm=None):
+    """the C-plane: the x-z picture at axial position y = depth_mm (from the arc's centre), [nv][nu] with u along x and v along z, pitch_mm
+    apart, centred on the arc's axis unless x0_mm / z0_mm give the first point"""
+    x0 = -(nu - 1) * pitch_mm / 2.0 if x0_mm is None else x0_mm
+    z0 = -(nv - 1) * pitch_mm / 2.0 if z0_mm is None else z0_mm
+    return volume_grid((x0, depth_mm, z0), (pitch_mm, 0, 0), (0, 0, pitch_mm), (0, 0, 0), nu, nv, 1)
+
+
+def sagittal_grid(x_mm, nu, nv, pitch_mm, y0_mm, z0_mm=None):
+    """the sagittal cut: the y-z picture at lateral position x = x_mm, [nv][nu] with u along z and v along y (depth downwards), pitch_mm apart,
+    from axial position y0_mm on, centred in elevation unless z0_mm gives the first point"""
+    z0 = -(nu - 1) * pitch_mm / 2.0 if z0_mm is None else z0_mm
+    return volume_grid((x_mm, y0_mm, z0), (0, 0, pitch_mm), (0, pitch_mm, 0), (0, 0, 0), nu, nv, 1)
+
+
+def host_volume_maps(n_elements, n_rows, sweep, grid, radius_mm=30.0, total_angle=1.0471975511965976, max_travel_us=100, speed_of_sound=1500):
+    """mcrt_volume_maps: where in the stack [K][E][R] every point of grid lies, (map_plane, map_row, map_col), each [nw][nv][nu].
+    sweep: an mcrt_sweep (sweep_struct) or (K, step_rad[, pivot_mm])"""
+    sw = sweep if isinstance(sweep, Sweep) else sweep_struct(*sweep)
+    shape = (grid.nw, grid.nv, grid.nu)
+    mz = np.zeros(shape, np.float32); mr = np.zeros(shape, np.float32); mc = np.zeros(shape, np.float32)
+    check(load_library().mcrt_volume_maps(n_elements, n_rows, radius_mm, total_angle, max_travel_us, speed_of_sound, C.byref(sw), C.byref(grid), ptr(mz), ptr(mr), ptr(mc)))
+    return mz, mr, mc
+
+
 BMODE_MODES = {"db": 0, "ref_log": 1}
 
 
@@ -241,6 +299,12 @@ class Transducer:
         """the element tables of the views of a compounded frame, one per steering angle [rad] (mcrt_transducer_steered):
         (pos [N][E][3], dir [N][E][3]); the positions are the probe's own in every view"""
         tabs = [host_transducer_steered(self.n_elements, self.radius_cm, self.separation_mm, self.position, self.angles, float(s)) for s in steer_rad_list]
+        return np.stack([t[0] for t in tabs]), np.stack([t[1] for t in tabs])
+
+    def swept(self, n_planes, step_rad, pivot_mm=0.0):
+        """the element tables of the planes of a sweep (mcrt_transducer_swept at sweep_tilts' angles): (pos [K][E][3], dir [K][E][3])"""
+        tabs = [host_transducer_swept(self.n_elements, self.radius_cm, self.separation_mm, self.position, self.angles, float(t), pivot_mm)
+                for t in sweep_tilts(n_planes, step_rad)]
         return np.stack([t[0] for t in tabs]), np.stack([t[1] for t in tabs])
 
 
@@ -536,6 +600,27 @@ class Context:
         check(self.L.mcrt_bmode_compound_frames_opts(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(p), C.byref(cp), ptr(tgc), ptr(state_dev),
                                                      ptr(peak_dev), ptr(out_dev), C.byref(o)))
 
+    def volume_frames(self, rf_dev, n_frames, n_elements, n_rows, sweep, grid, out_dev, radius_mm=30.0, total_angle=1.0471975511965976):
+        """mcrt_volume_frames: the planes [n_frames][K][E][R] of a sweep -> device floats [n_frames][nw][nv][nu] at grid's points.
+        sweep: an mcrt_sweep (sweep_struct) or (K, step_rad[, pivot_mm])"""
+        sw = sweep if isinstance(sweep, Sweep) else sweep_struct(*sweep)
+        check(self.L.mcrt_volume_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, radius_mm, total_angle, C.byref(sw), C.byref(grid), ptr(out_dev)))
+
+    def bmode_volume_frames(self, rf_dev, n_frames, n_elements, n_rows, sweep, grid, out_dev, *, mode="db", dynamic_range_db=60.0, gain_db=0.0, ref=None,
+                            tgc_db=None, persistence=0.0, peak_dev=None, radius_mm=30.0, total_angle=1.0471975511965976):
+        """mcrt_bmode_volume_frames: bmode_frames over the planes [n_frames][K][E][R] of a sweep, bytes [n_frames][nw][nv][nu]; the automatic
+        reference of a frame is the peak over its whole sweep.  persistence must stay 0 (the library refuses anything else)"""
+        p = bmode_params(mode=mode, dynamic_range_db=dynamic_range_db, gain_db=gain_db, ref=ref, persistence=persistence, radius_mm=radius_mm,
+                         total_angle=total_angle, out_rows=0, out_cols=0)
+        sw = sweep if isinstance(sweep, Sweep) else sweep_struct(*sweep)
+        tgc = None
+        if tgc_db is not None:
+            tgc = np.ascontiguousarray(tgc_db, np.float32)
+            if tgc.shape != (n_rows,):
+                raise ValueError("tgc_db needs one value per RF row: %d, got shape %s" % (n_rows, tgc.shape))
+        check(self.L.mcrt_bmode_volume_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(p), C.byref(sw), C.byref(grid), ptr(tgc), ptr(peak_dev),
+                                              ptr(out_dev)))
+
     def export_rf(self, rf_dev, n_elements, n_rows):
         out = np.empty((n_rows, n_elements), np.float32)
         check(self.L.mcrt_export_rf(self.h, ptr(rf_dev), n_elements, n_rows, ptr(out)))
@@ -687,7 +772,7 @@ class Simulator:
 
     def __init__(self, scene_data, transducer, n_samples=5, n_rows=None, device=0, seed=0x5EED, psf=None, texture=None,
                  max_depth=10, sanitize_tir=0, tex_n=256, bvh_builder="sah", elevation=False, compound=None, compound_mode="mean", compound_weights=None,
-                 compound_feather=0.0):
+                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0):
         """elevation=True: slice thickness.  trace() then traces the psf's elevation_size planes of the frame as one pose pass -- plane k of
         frame f with frame id f * K + k, the frame-id rule of include/mcrt.h -- and folds them into rf_dev with psf.elevation_rows();
         everything after (convolve, bmode, frame) is unchanged.
@@ -696,7 +781,13 @@ class Simulator:
         with elevation=True); convolve() and the envelope run over the N views, bmode() ends in mcrt_bmode_compound_frames and
         compound_image() in mcrt_compound_frames.  frame() returns RF, which a compounded frame does not have: it raises.
         compound_mode ("mean" / "max" / "median"), compound_weights (one weight per view) and compound_feather (a lateral edge ramp in
-        scan-lines) are carried into compound_image() and bmode(): the keywords of Context.compound_frames."""
+        scan-lines) are carried into compound_image() and bmode(): the keywords of Context.compound_frames.
+        sweep=(K, step_rad): volume imaging with a probe swept in elevation about the axis through (0, sweep_pivot_mm, 0).  trace() then traces
+        the K tilted planes as one pose pass -- plane k of volume f with frame id f * K + k -- into sweep_dev [K][E][R]; convolve() and the
+        envelope run over the K planes; volume() and bmode_volume() gather them at a grid's points.  frame(), bmode() and compound_image()
+        raise.  It does not combine with compound= or elevation=."""
+        if sweep is not None and (compound is not None or elevation):
+            raise ValueError("sweep= does not combine with compound= or elevation=")
         if compound is not None and not 1 <= len(tuple(compound)) <= 16:
             raise ValueError("compound takes 1..16 steering angles, got %d" % len(tuple(compound)))
         self.ctx = Context(device)
@@ -723,6 +814,11 @@ class Simulator:
         if self.steers is not None:
             self.view_pos, self.view_dir = transducer.steered(self.steers)
             self.views_dev = self.ctx.alloc(self.N * E * self.R * 4)
+        self.sweep, self.sweep_dev = None, None
+        if sweep is not None:
+            self.sweep = sweep_struct(sweep[0], sweep[1], sweep_pivot_mm)
+            self.sweep_pos, self.sweep_dir = transducer.swept(self.sweep.n_planes, self.sweep.step_rad, self.sweep.pivot_mm)
+            self.sweep_dev = self.ctx.alloc(self.sweep.n_planes * E * self.R * 4)
         if self.elevation:
             self.K = self.psf.elevation_size
             self.plane_pos, self.plane_dir, self.plane_z_mm = transducer.planes(self.K, self.psf.elevation_pitch_um)
@@ -739,9 +835,14 @@ class Simulator:
                 self.ctx.free(self.planes_dev)
             if self.views_dev:
                 self.ctx.free(self.views_dev)
+            if self.sweep_dev:
+                self.ctx.free(self.sweep_dev)
             self.ctx.close()
 
     def trace(self, frame_id=0):
+        if self.sweep is not None:
+            self.ctx.trace_frames_poses(frame_id * self.sweep.n_planes, self.sweep_pos, self.sweep_dir, self.sweep_dev)
+            return
         if self.steers is not None:
             if not self.elevation:
                 self.ctx.trace_frames_poses(frame_id * self.N, self.view_pos, self.view_dir, self.views_dev)
@@ -761,7 +862,12 @@ class Simulator:
         return row_pitch_mm(self.ctx.params.frequency)
 
     def convolve(self):
-        if self.steers is not None:                     # the N views as N frames
+        if self.sweep is not None:                      # the K planes as K frames
+            if self.psf.has_focus:
+                self.ctx.convolve_frames_depth(self.sweep_dev, self.sweep.n_planes, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_rows(self.R, self.row_mm))
+            else:
+                self.ctx.convolve_frames(self.sweep_dev, self.sweep.n_planes, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_kernel)
+        elif self.steers is not None:                   # the N views as N frames
             if self.psf.has_focus:
                 self.ctx.convolve_frames_depth(self.views_dev, self.N, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_rows(self.R, self.row_mm))
             else:
@@ -772,7 +878,9 @@ class Simulator:
             self.ctx.convolve(self.rf_dev, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_kernel)
 
     def envelope(self):
-        if self.steers is not None:
+        if self.sweep is not None:
+            self.ctx.envelope_frames(self.sweep_dev, self.sweep.n_planes, self.E, self.R)
+        elif self.steers is not None:
             self.ctx.envelope_frames(self.views_dev, self.N, self.E, self.R)
         else:
             self.ctx.envelope(self.rf_dev, self.E, self.R)
@@ -794,9 +902,44 @@ class Simulator:
         finally:
             self.ctx.free(out)
 
+    def volume(self, frame_id, grid, convolve=True, envelope=True, radius_mm=30.0, total_angle=1.0471975511965976):
+        """trace -> convolve -> envelope -> mcrt_volume_frames -> host: the float voxels [nw][nv][nu] of grid, a volume or any cut (sweep= only)"""
+        if self.sweep is None:
+            raise RuntimeError("volume() needs Simulator(sweep=...)")
+        self.trace(frame_id)
+        if convolve:
+            self.convolve()
+        if envelope:
+            self.envelope()
+        shape = (grid.nw, grid.nv, grid.nu)
+        out = self.ctx.alloc(shape[0] * shape[1] * shape[2] * 4)
+        try:
+            self.ctx.volume_frames(self.sweep_dev, 1, self.E, self.R, self.sweep, grid, out, radius_mm=radius_mm, total_angle=total_angle)
+            return self.ctx.d2h(out, shape, np.float32)
+        finally:
+            self.ctx.free(out)
+
+    def bmode_volume(self, frame_id, grid, **display):
+        """trace -> convolve -> envelope -> mcrt_bmode_volume_frames -> host: the displayed 8-bit voxels, uint8 [nw][nv][nu] (sweep= only).
+        display: the keywords of Context.bmode_volume_frames (mode, dynamic_range_db, gain_db, ref, tgc_db, radius_mm, total_angle)"""
+        if self.sweep is None:
+            raise RuntimeError("bmode_volume() needs Simulator(sweep=...)")
+        self.trace(frame_id)
+        self.convolve()
+        self.envelope()
+        shape = (grid.nw, grid.nv, grid.nu)
+        out = self.ctx.alloc(shape[0] * shape[1] * shape[2])
+        try:
+            self.ctx.bmode_volume_frames(self.sweep_dev, 1, self.E, self.R, self.sweep, grid, out, **display)
+            return self.ctx.d2h(out, shape, np.uint8)
+        finally:
+            self.ctx.free(out)
+
     def bmode(self, frame_id=0, **display):
         """trace -> convolve -> envelope -> mcrt_bmode_frames -> host: the displayed 8-bit frame, uint8 [out_rows][out_cols].
         display: the keywords of Context.bmode_frames (mode, dynamic_range_db, gain_db, ref, tgc_db, ...)"""
+        if self.sweep is not None:
+            raise RuntimeError("a swept probe has K planes and meets only at a grid's points: use volume() or bmode_volume()")
         rows, cols = display.get("out_rows", 400), display.get("out_cols", 500)
         self.trace(frame_id)
         self.convolve()
@@ -814,6 +957,8 @@ class Simulator:
             self.ctx.free(out)
 
     def frame(self, frame_id=0, convolve=True):
+        if self.sweep is not None:
+            raise RuntimeError("a swept probe has K planes and meets only at a grid's points: use volume() or bmode_volume()")
         if self.steers is not None:
             raise RuntimeError("frame() returns one RF image; a compounded frame has N views and meets only as a picture: use compound_image() or bmode()")
         self.trace(frame_id)

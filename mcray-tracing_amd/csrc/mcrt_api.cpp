@@ -135,6 +135,14 @@ struct MapCache {
     static size_t pad(size_t n) { return (n + 255u) & ~(size_t)255u; }
 };
 
+// The maps of volume imaging (mcrt_volume_frames, mcrt_bmode_volume_frames) on the device: per grid [3][n_pad], plane, column, row, in
+// MapCache's padding.  The four most recently used grids stay (a volume and three orthogonal cuts per frame); ensure_volume_maps owns the
+// keys: the integers and float bits in key, the doubles in keyd, each compared bit for bit on its own.  used: the slot's last call, 0 = empty.
+struct VolumeMapCache {
+    struct Slot { Buf<float> d; uint32_t key[9] = {}; double keyd[15] = {}; uint64_t used = 0; };
+    Slot slot[4]; uint64_t clock = 0;
+};
+
 struct TimedLaunch { Event start, end; int kind = 0; };   // kind 0: the walk (k_trace*, k_path), 1: k_shade, 2: k_march
 
 struct mcrt_ctx {
@@ -183,6 +191,7 @@ struct mcrt_ctx {
     // scan-conversion maps: of the plain geometry (mcrt_scan_convert_frames, mcrt_bmode_frames; one unsteered view) and of a steer list (spatial
     // compounding: mcrt_compound_frames, mcrt_bmode_compound_frames), each in a cache of its own so that alternating calls do not evict each other
     MapCache maps, cmaps;
+    VolumeMapCache vmaps;
     // B-mode display (mcrt_bmode_frames): the peaks of a pass [65536], and the TGC factors [R] of the last curve
     Buf<float> d_disp; StagedTable tgc;
     // focal zones (mcrt_convolve_frames_depth): the lateral taps [n_lat][R], and slice thickness (mcrt_elevation_frames): the elevation weights
@@ -1350,6 +1359,90 @@ extern "C" int mcrt_bmode_compound_frames(mcrt_ctx *c, const float *rf_dev, uint
                                           const mcrt_compound *cp, const float *tgc_db, float *state_dev, float *peak_dev, uint8_t *out_dev)
 {
     return mcrt_bmode_compound_frames_opts(c, rf_dev, n_frames, E, R, p, cp, tgc_db, state_dev, peak_dev, out_dev, nullptr);
+}
+
+// ---- volume imaging (the contracts are in include/mcrt.h) ----
+// the three maps of a grid on the device: the slot that holds them, or the least recently used one refilled (made on the host by
+// mcrt_volume_maps and uploaded; a slot's buffer only ever grows)
+static int ensure_volume_maps(mcrt_ctx *c, uint32_t E, uint32_t R, double radius_mm, double total_angle, const mcrt_sweep *sw, const mcrt_volume_grid *g, const float **maps)
+{
+    uint32_t key[9] = { E, R, c->p.speed_of_sound, sw->n_planes, g->nu, g->nv, g->nw, 0u, 0u };
+    memcpy(&key[7], &sw->step_rad, 4); memcpy(&key[8], &sw->pivot_mm, 4);
+    double keyd[15] = { radius_mm, total_angle, c->c.max_travel_us };
+    memcpy(&keyd[3], g->origin_mm, 12 * sizeof(double));                     // origin_mm, du_mm, dv_mm, dw_mm are contiguous (mcrt.h gives the offsets)
+    VolumeMapCache &vc = c->vmaps;
+    VolumeMapCache::Slot *lru = &vc.slot[0];
+    for (VolumeMapCache::Slot &s : vc.slot) {
+        if (s.used && !memcmp(key, s.key, sizeof key) && !memcmp(keyd, s.keyd, sizeof keyd)) { s.used = ++vc.clock; *maps = s.d; return MCRT_OK; }
+        if (s.used < lru->used) lru = &s;
+    }
+    const size_t n = (size_t)g->nu * g->nv * g->nw, n_pad = MapCache::pad(n);
+    std::vector<float> m(3 * n_pad, 0.0f);
+    MCRT_TRY(mcrt_volume_maps(E, R, radius_mm, total_angle, (uint32_t)c->c.max_travel_us, c->p.speed_of_sound, sw, g, &m[0], &m[2 * n_pad], &m[n_pad]));
+    HIP_TRY(hipStreamSynchronize(c->stream));                                // (the evicted grid's last gather)
+    lru->used = 0;                                                            // (no grid until the maps are on the device)
+    HIP_TRY(lru->d.grow(m.size()));
+    HIP_TRY(hipMemcpy(lru->d, m.data(), m.size() * 4, hipMemcpyHostToDevice));
+    memcpy(lru->key, key, sizeof key); memcpy(lru->keyd, keyd, sizeof keyd); lru->used = ++vc.clock;
+    *maps = lru->d;
+    return MCRT_OK;
+}
+
+// what the two entry points check of the stack and the grid before anything else happens
+static int volume_args_check(const char *fn, uint32_t n_frames, uint32_t E, uint32_t R, double total_angle, const mcrt_sweep *sw, const mcrt_volume_grid *g)
+{
+    if (E == 0 || R == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes", fn);
+    if (!(total_angle > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: total_angle_rad must be > 0", fn);
+    MCRT_TRY(mcrt::volume_check(fn, sw, g));
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: at most %d rows", fn, MCRT_MAX_ROWS);
+    if ((uint64_t)n_frames * sw->n_planes > 65535ull) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 planes per call (%u frames x %u)", fn, n_frames, sw->n_planes);
+    return MCRT_OK;
+}
+
+static mcrt::VolumeArgs volume_args(const float *src, const float *maps, void *out, uint32_t n_frames, uint32_t E, uint32_t R, uint32_t K, uint32_t n, bool out8)
+{
+    mcrt::VolumeArgs a;
+    a.src = src; a.maps = maps; a.out = out; a.E = E; a.R = R; a.K = K; a.n = n; a.n_pad = (uint32_t)MapCache::pad(n); a.F = n_frames;
+    a.frames_per_chunk = display_frames_per_chunk(n_frames, n, 0.0f);
+    a.vec = out8 && n % 4u == 0u && (uintptr_t)out % 4u == 0u ? 1u : 0u;
+    return a;
+}
+
+extern "C" int mcrt_volume_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, double radius_mm, double total_angle,
+                                  const mcrt_sweep *sw, const mcrt_volume_grid *g, float *out_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_volume_frames";
+    if (!rf_dev || !out_dev) return set_error(MCRT_ERR_INVALID, "%s: null %s", fn, rf_dev ? "out_dev" : "rf_dev");
+    MCRT_TRY(volume_args_check(fn, n_frames, E, R, total_angle, sw, g));
+    const uint32_t K = sw->n_planes, n = g->nu * g->nv * g->nw;
+    if (ranges_overlap(rf_dev, 4 * (size_t)n_frames * K * E * R, out_dev, 4 * (size_t)n_frames * n)) return set_error(MCRT_ERR_INVALID, "%s: rf_dev and out_dev overlap", fn);
+    const float *maps = nullptr;
+    MCRT_TRY(ensure_volume_maps(c, E, R, radius_mm, total_angle, sw, g, &maps));
+    HIP_TRY(mcrt::launch_volume(volume_args(rf_dev, maps, out_dev, n_frames, E, R, K, n, false), false, c->stream));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_bmode_volume_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_bmode_params *p,
+                                        const mcrt_sweep *sw, const mcrt_volume_grid *g, const float *tgc_db, float *peak_dev, uint8_t *out_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_bmode_volume_frames";
+    if (!p) return set_error(MCRT_ERR_INVALID, "%s: null params", fn);
+    mcrt_bmode_params q = *p;
+    q.out_rows = q.out_cols = 1u;                       // the picture is the grid's: p's own size is not looked at
+    std::vector<float> k;
+    MCRT_TRY(bmode_check(fn, rf_dev, out_dev, n_frames, E, R, &q, tgc_db, k));
+    if (p->persistence != 0.0f) return set_error(MCRT_ERR_INVALID, "%s: persistence must be 0 on a volume (%g)", fn, (double)p->persistence);
+    MCRT_TRY(volume_args_check(fn, n_frames, E, R, p->total_angle_rad, sw, g));
+    const uint32_t K = sw->n_planes, n = g->nu * g->nv * g->nw;
+    if ((uint64_t)K * E > 0xffffffffull) return set_error(MCRT_ERR_LIMIT, "%s: too many scan-lines (%u planes x %u)", fn, K, E);   // (a frame is K * E scan-lines to steps 1-3)
+    if (ranges_overlap(rf_dev, 4 * (size_t)n_frames * K * E * R, out_dev, (size_t)n_frames * n)) return set_error(MCRT_ERR_INVALID, "%s: rf_dev and out_dev overlap", fn);
+    const float *maps = nullptr;
+    MCRT_TRY(ensure_volume_maps(c, E, R, p->radius_mm, p->total_angle_rad, sw, g, &maps));
+    MCRT_TRY(bmode_grey_pass(c, rf_dev, n_frames, K * E, R, &q, tgc_db, k, peak_dev));
+    HIP_TRY(mcrt::launch_volume(volume_args(c->d_tmp, maps, out_dev, n_frames, E, R, K, n, true), true, c->stream));
+    return MCRT_OK;
 }
 
 extern "C" int mcrt_export_rf(mcrt_ctx *c, const float *rf_dev, uint32_t E, uint32_t R, float *host)

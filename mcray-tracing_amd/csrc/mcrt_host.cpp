@@ -397,8 +397,10 @@ inline F3 rot(F3 v, F3 ax, float ang)   // btVector3::rotate
 }
 }  // namespace
 
-// transducer.h:24-62; steer (mcrt_transducer_steered) tilts the directions alone: the beams pivot on their elements
-static void transducer_tables(uint32_t n, double radius_cm, double sep_mm, const float position[3], const float angles_deg[3], float steer, float *pos, float *dir)
+// transducer.h:24-62; steer (mcrt_transducer_steered) tilts the directions alone: the beams pivot on their elements; tilt (mcrt_transducer_swept)
+// turns the whole array about the line parallel to x through (0, pivot_cm, 0) of the probe-local frame.  At most one of the two is non-zero
+static void transducer_tables(uint32_t n, double radius_cm, double sep_mm, const float position[3], const float angles_deg[3], float steer, float *pos, float *dir,
+                              float tilt = 0.0f, float pivot_cm = 0.0f)
 {
     const double pi = 3.14159265358979323846264338327950288419716939937510;   // units.h:360
     const double xa = (angles_deg[0] * pi * 1.0) / 180.0, ya = (angles_deg[1] * pi * 1.0) / 180.0, za = (angles_deg[2] * pi * 1.0) / 180.0;
@@ -408,6 +410,17 @@ static void transducer_tables(uint32_t n, double radius_cm, double sep_mm, const
     const float rf = (float)radius_cm;
     for (uint32_t t = 0; t < n; t++) {
         const float a = (float)angle;
+        if (tilt != 0.0f) {
+            const float s = std::sin(a), c = std::cos(a), ct = std::cos(tilt), st = std::sin(tilt), yp = pivot_cm;
+            F3 d{ s, c * ct, c * st }, q{ rf * s, yp + (rf * c - yp) * ct, (rf * c - yp) * st };
+            d = rot(d, F3{ 0, 0, 1 }, (float)za); q = rot(q, F3{ 0, 0, 1 }, (float)za);
+            d = rot(d, F3{ 1, 0, 0 }, (float)xa); q = rot(q, F3{ 1, 0, 0 }, (float)xa);
+            d = rot(d, F3{ 0, 1, 0 }, (float)ya); q = rot(q, F3{ 0, 1, 0 }, (float)ya);
+            pos[3 * t] = position[0] + q.x; pos[3 * t + 1] = position[1] + q.y; pos[3 * t + 2] = position[2] + q.z;
+            dir[3 * t] = d.x; dir[3 * t + 1] = d.y; dir[3 * t + 2] = d.z;
+            angle = angle + amplitude;
+            continue;
+        }
         F3 d{ std::sin(a), std::cos(a), 0.f };
         d = rot(d, F3{ 0, 0, 1 }, (float)za);
         d = rot(d, F3{ 1, 0, 0 }, (float)xa);
@@ -612,5 +625,57 @@ extern "C" int mcrt_compound_maps(uint32_t E, uint32_t R, double radius_mm, doub
             map_row[o] = (float)(t / (double)depth_mm_f * (double)R);
             map_col[o] = (float)((phi + total_angle / 2) / total_angle * (double)(float)E);
         }
+    return MCRT_OK;
+}
+
+// ---- volume imaging (the contracts are in include/mcrt.h) ---------------------------------------
+extern "C" int mcrt_transducer_swept(uint32_t n, double radius_cm, double sep_mm, const float position[3], const float angles_deg[3], float tilt_rad,
+                                     float pivot_mm, float *pos, float *dir)
+{
+    if (!pos || !dir || !position || !angles_deg || n == 0) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_transducer_swept: bad arguments");
+    if (!steer_ok(tilt_rad)) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_transducer_swept: tilt_rad must be finite and |tilt| < pi/2 (%g)", (double)tilt_rad);
+    if (!std::isfinite(pivot_mm)) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_transducer_swept: pivot_mm must be finite");
+    transducer_tables(n, radius_cm, sep_mm, position, angles_deg, 0.0f, pos, dir, tilt_rad, (float)(pivot_mm / 10.0));
+    return MCRT_OK;
+}
+
+// what every volume call checks of its sweep and grid (fn: the caller's name, for the message)
+int mcrt::volume_check(const char *fn, const mcrt_sweep *sw, const mcrt_volume_grid *g)
+{
+    if (!sw || !g) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null %s", fn, sw ? "grid" : "sweep");
+    if (sw->n_planes == 0 || sw->n_planes > 256) return mcrt::set_error(MCRT_ERR_INVALID, "%s: n_planes must be 1..256 (%u)", fn, sw->n_planes);
+    if (!(std::isfinite(sw->step_rad) && sw->step_rad > 0.0f && (double)(sw->n_planes - 1u) / 2.0 * (double)sw->step_rad < 1.57079632679489661923))
+        return mcrt::set_error(MCRT_ERR_INVALID, "%s: step_rad must be finite, > 0 and keep every plane's tilt below pi/2 (%g x %u planes)", fn, (double)sw->step_rad, sw->n_planes);
+    if (!std::isfinite(sw->pivot_mm)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: pivot_mm must be finite", fn);
+    if (g->nu == 0 || g->nv == 0 || g->nw == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: zero grid size (%u x %u x %u)", fn, g->nu, g->nv, g->nw);
+    for (int i = 0; i < 3; i++)
+        if (!(std::isfinite(g->origin_mm[i]) && std::isfinite(g->du_mm[i]) && std::isfinite(g->dv_mm[i]) && std::isfinite(g->dw_mm[i])))
+            return mcrt::set_error(MCRT_ERR_INVALID, "%s: the grid has an entry that is not finite (component %d)", fn, i);
+    if ((double)g->nu * (double)g->nv * (double)g->nw >= 0x1p31) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: 2^31 output points or more (%u x %u x %u)", fn, g->nu, g->nv, g->nw);
+    return MCRT_OK;
+}
+
+// the inverse of the swept probe's forward geometry at every grid point, in double, rounded once
+extern "C" int mcrt_volume_maps(uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t max_travel_us, uint32_t speed_of_sound,
+                                const mcrt_sweep *sw, const mcrt_volume_grid *g, float *map_plane, float *map_row, float *map_col)
+{
+    if (!map_plane || !map_row || !map_col || E == 0 || R == 0 || !(total_angle > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_volume_maps: bad arguments");
+    { const int rc = mcrt::volume_check("mcrt_volume_maps", sw, g); if (rc != MCRT_OK) return rc; }
+    const float depth_mm_f = (float)(uint32_t)(max_travel_us * speed_of_sound) * 0.001f;
+    const double pivot = (double)sw->pivot_mm, step = (double)sw->step_rad, mid = (double)(sw->n_planes - 1u) / 2.0;
+    size_t o = 0;
+    for (uint32_t l = 0; l < g->nw; l++)
+        for (uint32_t j = 0; j < g->nv; j++)
+            for (uint32_t i = 0; i < g->nu; i++, o++) {
+                double P[3];
+                for (int k = 0; k < 3; k++) P[k] = ((g->origin_mm[k] + (double)i * g->du_mm[k]) + (double)j * g->dv_mm[k]) + (double)l * g->dw_mm[k];
+                const double yr = P[1] - pivot;
+                const double h = std::sqrt(yr * yr + P[2] * P[2]), theta = std::atan2(P[2], yr);
+                const double y = pivot + h;
+                const double rho = std::sqrt(P[0] * P[0] + y * y), alpha = std::atan2(P[0], y);
+                map_plane[o] = (float)(theta / step + mid);
+                map_row[o] = (float)((rho - radius_mm) / (double)depth_mm_f * (double)R);
+                map_col[o] = (float)((alpha + total_angle / 2) / total_angle * (double)(float)E);
+            }
     return MCRT_OK;
 }

@@ -45,5 +45,7 @@ int ctx_bvh_builder(const mcrt_ctx *c);
 int upload_scene_with_tree(mcrt_ctx *c, const float *tri, const uint32_t *tri_mesh, uint32_t n_tri, const mcrt_mesh *meshes, uint32_t n_mesh,
                            const float *mats, uint32_t n_mat, uint32_t start_mat, const float spacing[3], const HostTree *pre);
 int update_triangles_with_tree(mcrt_ctx *c, const float *tri, uint32_t n_tri, const HostTree *pre);
+// mcrt_host.cpp: the conditions on a sweep and a grid that mcrt_volume_maps and the two device entry points share
+int volume_check(const char *fn, const mcrt_sweep *sw, const mcrt_volume_grid *g);
 }
 #endif

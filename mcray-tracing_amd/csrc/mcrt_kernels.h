@@ -10,6 +10,7 @@
 //   mcrt_post.hip    k_finalize, k_clear_flags, k_conv_* (k_conv_lateral_rows: focal zones), k_elevation (slice thickness), k_envelope, k_remap, k_transpose, k_blocks_to_frames
 //   mcrt_display.hip k_bmode_peak, k_bmode_grey, k_bmode (mcrt_bmode_frames: log-compressed 8-bit B-mode frames), k_compound (spatial compounding:
 //                    mcrt_compound_frames, mcrt_bmode_compound_frames)
+//   mcrt_volume.hip  k_volume (volume imaging: mcrt_volume_frames, mcrt_bmode_volume_frames)
 //   mcrt_scene.hip   k_tris_by_id, k_expand_tris; the probes k_math_probe, k_verify_div, k_philox_probe
 //   mcrt_lbvh.hip    the device BVH builder (mcrt_lbvh.h)
 // Shared device code: mcrt_device.h (primitives and the knobs more than one unit reads), mcrt_walk.h (the lane walk's steps, also k_path's),
@@ -93,6 +94,16 @@ struct CompoundArgs {
 // COMPOUND_PLAIN is the mean of mcrt_compound_frames (every weight 1, no feathering); the others are mcrt_compound_opts' modes
 enum { COMPOUND_PLAIN = 0, COMPOUND_WEIGHTED = 1, COMPOUND_MAX = 2, COMPOUND_MEDIAN = 3 };
 
+// k_volume (mcrt_volume_frames / mcrt_bmode_volume_frames): the planes [F][K][E][R] of a swept probe (RF floats, or the grey levels of
+// k_bmode_grey) -> floats or bytes [F][n], n = nu * nv * nw
+struct VolumeArgs {
+    const float *src;                   // [F][K][E][R]
+    const float *maps;                  // [3][n_pad] the grid's maps: plane, column, row; zero-padded to n_pad = n rounded up to 256
+    void *out;                          // float or uint8_t [F][n]
+    uint32_t E, R, K, n, n_pad, F, frames_per_chunk;
+    uint32_t vec;                       // 8-bit form: n % 4 == 0 and out is word-aligned, so a lane may store a word per frame
+};
+
 hipError_t launch_init(const FrameArgs &a, hipStream_t st);
 hipError_t launch_trace(const FrameArgs &a, uint32_t b, bool stats, hipStream_t st);
 hipError_t launch_nodes_walk(const float4 *nodes, uint32_t n_nodes, uint4 *out, hipStream_t st);
@@ -116,6 +127,7 @@ hipError_t launch_bmode_grey(const float *rf, uint32_t F, uint32_t E, uint32_t R
                              float *peak_out /*[F] or null*/, uint32_t mode, float gain, float dr, float *grey, hipStream_t st);
 hipError_t launch_bmode(const BmodeArgs &a, hipStream_t st);
 hipError_t launch_compound(const CompoundArgs &a, bool out8, hipStream_t st);   // a.mode: the instantiation
+hipError_t launch_volume(const VolumeArgs &a, bool out8, hipStream_t st);
 hipError_t launch_blocks_to_frames(const float *blocks, float *frames, uint32_t F, uint32_t E, uint32_t R, uint32_t G, const uint32_t *off /*[G+1]*/, hipStream_t st);   // at most 64 ranks
 hipError_t launch_transpose(const float *in, float *out, uint32_t E, uint32_t R, hipStream_t st);
 hipError_t launch_math_probe(int op, const double *x, const double *y, double *out, uint32_t n, hipStream_t st);

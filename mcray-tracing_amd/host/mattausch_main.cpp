@@ -3,6 +3,7 @@
 //                   [--db DR] [--gain G] [--ref-log] [--persistence A] [--focus-mm F1[,F2,...]] [--focal-range-mm R]
 //                   [--elevation K] [--elevation-pitch-um P] [--var-z V] [--compound N] [--compound-step-deg D]
 //                   [--compound-mode mean|max|median] [--compound-feather LINES] [--compound-weights w0,w1,...]
+//                   [--sweep K --sweep-step-deg D [--sweep-pivot-mm P] (--cplane-mm Y | --sagittal-mm X)]
 // --gpus N: the first N GPUs of the node, the frame's scan-lines sharded over them (mcrt_group_*: one tracing context and host thread per
 // GPU, the blocks gathered on GPU 0); --devices lists them explicitly, and may repeat one (two ranks sharing a GPU: the one-GPU test).
 // Same constants (main.cpp:23-37), same frame loop body; instead of blocking on imshow/waitKey every frame it
@@ -27,6 +28,14 @@
 // every view's weight up over its first and last LINES scan-lines, which hides where a steered view's coverage ends; --compound-weights
 // gives each of the N views a weight (mcrt_compound_opts).  Each of the three needs --compound; at their defaults (mean, 0, all 1) the
 // picture is the plain compound's byte for byte.
+// --sweep K (1..256) makes the probe a volume probe: the array wobbles in elevation about the line parallel to the lateral axis through the
+// point --sweep-pivot-mm P (0: the arc's centre) on the arc's axis, and every frame is traced in K planes --sweep-step-deg D apart, centred
+// on tilt 0, as one pass; the planes are convolved and enveloped as K frames.  The picture is then a cut through the volume no 2-D probe
+// shows (mcrt_volume_frames, or mcrt_bmode_volume_frames with a display option), written as the PGM: --cplane-mm Y, the x-z picture at axial
+// position Y mm from the arc's centre (500 columns along x, 400 rows along z, 0.25 mm apart, centred on the arc's axis), or --sagittal-mm X,
+// the y-z picture at lateral position X mm (400 columns along z centred on the probe's plane, 500 rows along y from the arc's apex down,
+// 0.25 mm apart).  rf.bin then holds plane K / 2.  --sweep needs one of the two cuts and --sweep-step-deg; it does not combine with
+// --compound or --elevation, and --persistence has no volume form.
 #include "mcrt_host.hpp"
 #include <chrono>
 #include <cmath>
@@ -57,6 +66,8 @@ int main(int argc, char **argv)
     bool compound_given = false;
     mcrt_compound_opts copts; mcrt_default_compound_opts(&copts);
     const char *compound_mode = nullptr, *compound_feather = nullptr, *compound_weights = nullptr;   // the options as given
+    int sweep_planes = 0; double sweep_step_deg = 0.0, sweep_pivot_mm = 0.0, cut_mm = 0.0;   // sweep_planes 0: off
+    bool sweep_given = false, sweep_step_given = false, cplane_given = false, sagittal_given = false;
     {   // the options, taken out of the positional arguments
         int keep = 1;
         for (int i = 1; i < argc; i++) {
@@ -78,6 +89,11 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--compound-mode") && i + 1 < argc) compound_mode = argv[++i];
             else if (!std::strcmp(argv[i], "--compound-feather") && i + 1 < argc) compound_feather = argv[++i];
             else if (!std::strcmp(argv[i], "--compound-weights") && i + 1 < argc) compound_weights = argv[++i];
+            else if (!std::strcmp(argv[i], "--sweep") && i + 1 < argc) { sweep_planes = std::atoi(argv[++i]); sweep_given = true; }
+            else if (!std::strcmp(argv[i], "--sweep-step-deg") && i + 1 < argc) { sweep_step_deg = std::atof(argv[++i]); sweep_step_given = true; }
+            else if (!std::strcmp(argv[i], "--sweep-pivot-mm") && i + 1 < argc) sweep_pivot_mm = std::atof(argv[++i]);
+            else if (!std::strcmp(argv[i], "--cplane-mm") && i + 1 < argc) { cut_mm = std::atof(argv[++i]); cplane_given = true; }
+            else if (!std::strcmp(argv[i], "--sagittal-mm") && i + 1 < argc) { cut_mm = std::atof(argv[++i]); sagittal_given = true; }
             else if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) { devices.clear(); for (int d = 0; d < std::max(1, std::atoi(argv[i + 1])); d++) devices.push_back(d); i++; }
             else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {
                 devices.clear();
@@ -118,6 +134,25 @@ int main(int argc, char **argv)
             if ((int)w.size() != compound) throw std::invalid_argument("--compound-weights takes one weight per view of --compound (" + std::to_string(compound) + ")");
             for (size_t n = 0; n < w.size(); n++) copts.view_weight[n] = w[n];
         }
+        if (sweep_given && (compound_given || elevation_given)) throw std::invalid_argument("--sweep does not combine with --compound or --elevation");
+        if (!sweep_given && (sweep_step_given || cplane_given || sagittal_given)) throw std::invalid_argument("--sweep-step-deg, --cplane-mm and --sagittal-mm need --sweep");
+        mcrt_sweep sweep{ 0, 0.0f, 0.0f };
+        mcrt_volume_grid cut{};
+        if (sweep_given) {
+            if (sweep_planes < 1 || sweep_planes > 256) throw std::invalid_argument("--sweep takes 1..256 planes");
+            if (!sweep_step_given) throw std::invalid_argument("--sweep needs --sweep-step-deg");
+            if (cplane_given == sagittal_given) throw std::invalid_argument("--sweep needs one of --cplane-mm and --sagittal-mm");
+            sweep.n_planes = (uint32_t)sweep_planes; sweep.step_rad = (float)(sweep_step_deg * 3.14159265358979323846 / 180.0); sweep.pivot_mm = (float)sweep_pivot_mm;
+            if (!(std::isfinite(sweep.step_rad) && sweep.step_rad > 0.0f && (double)(sweep_planes - 1) / 2.0 * (double)sweep.step_rad < 1.5707963267948966))
+                throw std::invalid_argument("--sweep-step-deg must be > 0 and keep every plane's tilt below 90 degrees");
+            if (!std::isfinite(sweep.pivot_mm) || !std::isfinite(cut_mm)) throw std::invalid_argument("--sweep-pivot-mm and the cut's position must be finite");
+            if (display.persistence != 0.0f) throw std::invalid_argument("--persistence has no volume form: it does not combine with --sweep");
+            const double pitch = 0.25;
+            if (cplane_given) { cut.origin_mm[0] = -(500 - 1) * pitch / 2.0; cut.origin_mm[1] = cut_mm; cut.origin_mm[2] = -(400 - 1) * pitch / 2.0; cut.du_mm[0] = pitch; cut.dv_mm[2] = pitch; cut.nu = 500; cut.nv = 400; }
+            else { cut.origin_mm[0] = cut_mm; cut.origin_mm[1] = transducer_radius_cm * 10.0; cut.origin_mm[2] = -(400 - 1) * pitch / 2.0; cut.du_mm[2] = pitch; cut.dv_mm[1] = pitch; cut.nu = 400; cut.nv = 500; }
+            cut.nw = 1;
+        }
+        std::vector<unsigned char> cut_bytes;         // the last frame's cut, as the PGM holds it
         const mcrt_compound_opts *opts = compound_mode || compound_feather || compound_weights ? &copts : nullptr;
         std::vector<float> steers;                    // centred on the unsteered view, ascending
         for (int n = 0; n < compound; n++) steers.push_back((float)((double)(n - (compound - 1) / 2) * compound_step_deg * 3.14159265358979323846 / 180.0));
@@ -143,21 +178,35 @@ int main(int argc, char **argv)
 
         const auto t0 = std::chrono::high_resolution_clock::now();
         for (int f = 0; f < frames; f++) {
-            if (compound_given) rf_image.trace((uint32_t)f, transducer, steers);                    // ... in N steered views
+            if (sweep_given) rf_image.trace((uint32_t)f, transducer, sweep);                        // ... in K tilted planes
+            else if (compound_given) rf_image.trace((uint32_t)f, transducer, steers);               // ... in N steered views
             else if (elevation_given) rf_image.trace((uint32_t)f, transducer, psf, (uint32_t)elevation);   // ... in K elevation planes, folded
             else rf_image.trace((uint32_t)f);      // clear + cast_rays + accumulation (main.cpp:102-144)
             rf_image.convolve(psf);           // main.cpp:146
             rf_image.envelope();              // main.cpp:147
-            if (compound_given) { if (bmode) rf_image.postprocess(display, steers, nullptr, opts); else rf_image.postprocess(steers, opts); }   // the views averaged (or opts' mode)
+            if (sweep_given) {                // the cut through the swept volume
+                if (bmode) cut_bytes = rf_image.volume(display, cut);
+                else {
+                    cut_bytes.clear();
+                    for (float v : rf_image.volume(cut)) { float x = v * 255.0f; cut_bytes.push_back((unsigned char)(x != x || x < 0 ? 0 : x > 255 ? 255 : x)); }   // (as rf_image::save)
+                }
+            }
+            else if (compound_given) { if (bmode) rf_image.postprocess(display, steers, nullptr, opts); else rf_image.postprocess(steers, opts); }   // the views averaged (or opts' mode)
             else if (bmode) rf_image.postprocess(display);   // main.cpp:148, log-compressed to 8-bit grey
             else rf_image.postprocess();      // main.cpp:148
         }
         check(dev->synchronize(), "mcrt_synchronize");
         const double dt = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
         std::cout << frames / dt << " frames/s, " << (double)frames * transducer_elements * samples / dt << " rays/s on " << devices.size() << " GPU context(s)" << std::endl;
-        if (argc > 4) { if (bmode) rf_image.save_bmode(argv[4]); else rf_image.save(argv[4]); }
+        if (argc > 4 && sweep_given) {
+            std::ofstream f(argv[4], std::ios::binary);
+            f << "P5\n" << cut.nu << " " << cut.nv << "\n255\n";
+            f.write((const char *)cut_bytes.data(), (std::streamsize)cut_bytes.size());
+        }
+        else if (argc > 4) { if (bmode) rf_image.save_bmode(argv[4]); else rf_image.save(argv[4]); }
         if (argc > 5) {   // the last frame's RF image after main.cpp:146-147, row-major [465][512] float32 (for the parity test)
-            const auto img = compound_given ? rf_image.view_intensities((uint32_t)(compound - 1) / 2u) : rf_image.intensities();
+            const auto img = sweep_given ? rf_image.view_intensities((uint32_t)sweep_planes / 2u)
+                             : compound_given ? rf_image.view_intensities((uint32_t)(compound - 1) / 2u) : rf_image.intensities();
             std::ofstream f(argv[5], std::ios::binary);
             f.write((const char *)img.data(), (std::streamsize)(img.size() * sizeof(float)));
         }

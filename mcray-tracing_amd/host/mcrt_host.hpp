@@ -299,6 +299,20 @@ public:
                                           t.dir.data() + n * one), "transducer steered");
         return t;
     }
+    // volume imaging: the element tables of the planes of a sweep (mcrt_transducer_swept at theta_k = (k - (K-1)/2.0) * step_rad, the array
+    // tilted about the line parallel to x through (0, pivot_mm, 0) of the probe-local frame): pos / dir [K][N][3]; z_mm stays empty
+    plane_tables swept(const mcrt_sweep &sw) const
+    {
+        plane_tables t;
+        const size_t one = 3 * transducer_elements;
+        t.pos.resize(sw.n_planes * one); t.dir.resize(sw.n_planes * one);
+        for (uint32_t k = 0; k < sw.n_planes; k++) {
+            const float tilt = (float)(((double)k - (double)(sw.n_planes - 1u) / 2.0) * (double)sw.step_rad);
+            check(mcrt_transducer_swept((uint32_t)transducer_elements, radius_cm, separation_mm, position.v, angles.data(), tilt, sw.pivot_mm, t.pos.data() + k * one,
+                                        t.dir.data() + k * one), "transducer swept");
+        }
+        return t;
+    }
     void setPosition(const vec3 &p) { position = p; }
     void setAngles(const std::array<float, 3> &a) { angles = a; }
     vec3 getPosition() const { return position; }
@@ -636,6 +650,7 @@ public:
         if (state_dev) mcrt_free(dev->ctx, state_dev);
         if (planes_dev) mcrt_free(dev->ctx, planes_dev);
         if (views_dev) mcrt_free(dev->ctx, views_dev);
+        if (volume_dev) mcrt_free(dev->ctx, volume_dev);
     }
     rf_image(const rf_image &) = delete; rf_image &operator=(const rf_image &) = delete;
 
@@ -703,19 +718,24 @@ public:
         if (V == 0 || V > 16) throw std::invalid_argument("rf_image::trace: 1..16 steering angles");
         const auto tables = t.steered(steer_rad);
         if ((uint64_t)frame_id * V + V > 0xffffffffull) throw std::out_of_range("rf_image::trace: frame_id * views does not fit a frame id");
-        mcrt_params prm; check(mcrt_get_params(dev->ctx, &prm), "mcrt_get_params");
-        if (prm.n_rows != max_rows || prm.n_elements != columns) {
-            prm.n_rows = max_rows; prm.n_elements = columns; prm.speed_of_sound = speed_of_sound;
-            check(dev->set_params(&prm), "mcrt_set_params");
-        }
-        const size_t need = (size_t)V * columns * max_rows;
-        if (need > views_cap) {
-            if (views_dev) { mcrt_free(dev->ctx, views_dev); views_dev = nullptr; views_cap = 0; }
-            check(mcrt_alloc(dev->ctx, sizeof(float) * need, (void **)&views_dev), "mcrt_alloc");
-            views_cap = need;
-        }
+        stack_prepare(V);
         check(dev->trace_frames_poses(frame_id * V, V, columns, tables.pos.data(), tables.dir.data(), views_dev), "mcrt_trace_frames_poses");
-        n_views = V;
+        n_views = V; sweep.n_planes = 0;
+    }
+    // volume imaging (mcrt.h): the K planes of a probe swept in elevation, traced as ONE pose pass -- plane k with frame id frame_id * K + k, the
+    // frame-id rule of mcrt.h -- into the stack [K][columns][max_rows] the views of a compounded frame use.  convolve() and envelope() then run
+    // over the K planes, and volume(grid) / volume(bmode_params, grid) gather them at a grid's points.  The next trace of another kind ends
+    // the swept state.
+    template <size_t N> void trace(uint32_t frame_id, const transducer<N> &t, const mcrt_sweep &sw)
+    {
+        static_assert(N == columns, "one scan-line per transducer element");
+        const uint32_t K = sw.n_planes;
+        if (K == 0 || K > 256) throw std::invalid_argument("rf_image::trace: a sweep has 1..256 planes");
+        const auto tables = t.swept(sw);
+        if ((uint64_t)frame_id * K + K > 0xffffffffull) throw std::out_of_range("rf_image::trace: frame_id * planes does not fit a frame id");
+        stack_prepare(K);
+        check(dev->trace_frames_poses(frame_id * K, K, columns, tables.pos.data(), tables.dir.data(), views_dev), "mcrt_trace_frames_poses");
+        n_views = K; sweep = sw;
     }
     template <typename psf_> void convolve(const psf_ &p)
     {
@@ -766,6 +786,27 @@ public:
         if (opts) check(mcrt_bmode_compound_frames_opts(dev->ctx, views_dev, 1, columns, max_rows, &p, &cp, tgc_db, state_dev, nullptr, bmode_dev, opts), "mcrt_bmode_compound_frames_opts");
         else check(mcrt_bmode_compound_frames(dev->ctx, views_dev, 1, columns, max_rows, &p, &cp, tgc_db, state_dev, nullptr, bmode_dev), "mcrt_bmode_compound_frames");
         state_valid = true; bmode_rows = bp.out_rows; bmode_cols = bp.out_cols;
+    }
+    // the planes of trace(frame, transducer, sweep) gathered at grid's points (mcrt_volume_frames): floats [nw][nv][nu], a volume or any cut
+    std::vector<float> volume(const mcrt_volume_grid &grid)
+    {
+        const size_t n = volume_prepare(grid, sizeof(float));
+        check(mcrt_volume_frames(dev->ctx, views_dev, 1, columns, max_rows, radius_mm, angle, &sweep, &grid, (float *)volume_dev), "mcrt_volume_frames");
+        std::vector<float> h(n);
+        check(mcrt_memcpy_d2h(dev->ctx, h.data(), volume_dev, n * sizeof(float)), "mcrt_memcpy_d2h");
+        return h;
+    }
+    // the same as the displayed 8-bit voxels (mcrt_bmode_volume_frames): one reference per volume, the peak of the whole sweep.  The sector is
+    // this image's own; bp.out_rows / out_cols are not read (the picture is the grid's) and bp.persistence must be 0
+    std::vector<unsigned char> volume(const mcrt_bmode_params &bp, const mcrt_volume_grid &grid, const float *tgc_db = nullptr)
+    {
+        const size_t n = volume_prepare(grid, 1);
+        mcrt_bmode_params p = bp;
+        p.radius_mm = radius_mm; p.total_angle_rad = angle;
+        check(mcrt_bmode_volume_frames(dev->ctx, views_dev, 1, columns, max_rows, &p, &sweep, &grid, tgc_db, nullptr, (uint8_t *)volume_dev), "mcrt_bmode_volume_frames");
+        std::vector<unsigned char> h(n);
+        check(mcrt_memcpy_d2h(dev->ctx, h.data(), volume_dev, n), "mcrt_memcpy_d2h");
+        return h;
     }
     std::vector<unsigned char> bmode() const   // the last postprocess(bmode_params) frame, row-major [out_rows][out_cols]
     {
@@ -834,9 +875,37 @@ private:
         p.reset_state = (bp.reset_state || !state_valid) ? 1u : 0u;
         return p;
     }
+    // before a pose pass of n images into views_dev: this image's shape in the context's parameters, and room for the stack (grown, never shrunk)
+    void stack_prepare(uint32_t n)
+    {
+        mcrt_params prm; check(mcrt_get_params(dev->ctx, &prm), "mcrt_get_params");
+        if (prm.n_rows != max_rows || prm.n_elements != columns) {
+            prm.n_rows = max_rows; prm.n_elements = columns; prm.speed_of_sound = speed_of_sound;
+            check(dev->set_params(&prm), "mcrt_set_params");
+        }
+        const size_t need = (size_t)n * columns * max_rows;
+        if (need > views_cap) {
+            if (views_dev) { mcrt_free(dev->ctx, views_dev); views_dev = nullptr; views_cap = 0; }
+            check(mcrt_alloc(dev->ctx, sizeof(float) * need, (void **)&views_dev), "mcrt_alloc");
+            views_cap = need;
+        }
+    }
+    // the device buffer of volume(): room for grid's points of `size` bytes each (grown, never shrunk); returns the number of points
+    size_t volume_prepare(const mcrt_volume_grid &grid, size_t size)
+    {
+        if (sweep.n_planes == 0 || n_views != sweep.n_planes) throw std::invalid_argument("rf_image::volume: trace(frame, transducer, sweep) first");
+        const size_t n = (size_t)grid.nu * grid.nv * grid.nw;
+        if (n == 0 || n >= ((size_t)1 << 31)) throw std::invalid_argument("rf_image::volume: the grid needs 1 .. 2^31 - 1 points");
+        if (n * size > volume_cap) {
+            if (volume_dev) { mcrt_free(dev->ctx, volume_dev); volume_dev = nullptr; volume_cap = 0; }
+            check(mcrt_alloc(dev->ctx, n * size, &volume_dev), "mcrt_alloc");
+            volume_cap = n * size;
+        }
+        return n;
+    }
     mcrt_compound compound_of(const std::vector<float> &steer_rad) const
     {
-        if (n_views == 0 || steer_rad.size() != n_views) throw std::invalid_argument("rf_image::postprocess: the steer list is not the one the views were traced with");
+        if (n_views == 0 || sweep.n_planes != 0 || steer_rad.size() != n_views) throw std::invalid_argument("rf_image::postprocess: the steer list is not the one the views were traced with");
         mcrt_compound cp{};
         cp.n_views = n_views;
         for (uint32_t n = 0; n < n_views; n++) cp.steer_rad[n] = steer_rad[n];
@@ -850,6 +919,8 @@ private:
     size_t bmode_n = 0; uint32_t bmode_rows = 0, bmode_cols = 0; bool state_valid = false;
     float *planes_dev = nullptr; size_t planes_n = 0;                 // trace(frame, transducer, psf): the plane stack [K][columns][max_rows], grown to the largest K
     float *views_dev = nullptr; size_t views_cap = 0; uint32_t n_views = 0;   // trace(frame, transducer, steer_rad): the views [N][columns][max_rows]; n_views > 0: compounded
+    mcrt_sweep sweep{ 0, 0.0f, 0.0f };                                // trace(frame, transducer, sweep): n_planes > 0: the stack holds a sweep's planes (n_views == n_planes)
+    void *volume_dev = nullptr; size_t volume_cap = 0;                // volume(): the gathered points, floats or bytes
 };
 
 }  // namespace mcrt_host
