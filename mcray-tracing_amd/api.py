@@ -210,6 +210,11 @@ def sweep_struct(n_planes, step_rad, pivot_mm=0.0):
     return sw
 
 
+def _as_sweep(sweep):
+    """an mcrt_sweep from what the wrappers take: one as it is, or (K, step_rad[, pivot_mm])"""
+    return sweep if isinstance(sweep, Sweep) else sweep_struct(*sweep)
+
+
 def sweep_tilts(n_planes, step_rad):
     """the planes' tilts [rad], float32: theta_k = (k - (K-1)/2.0) * step_rad with step_rad as the float the library is given"""
     step = float(np.float32(step_rad))
@@ -245,7 +250,7 @@ def sagittal_grid(x_mm, nu, nv, pitch_mm, y0_mm, z0_mm=None):
 def host_volume_maps(n_elements, n_rows, sweep, grid, radius_mm=30.0, total_angle=1.0471975511965976, max_travel_us=100, speed_of_sound=1500):
     """mcrt_volume_maps: where in the stack [K][E][R] every point of grid lies, (map_plane, map_row, map_col), each [nw][nv][nu].
     sweep: an mcrt_sweep (sweep_struct) or (K, step_rad[, pivot_mm])"""
-    sw = sweep if isinstance(sweep, Sweep) else sweep_struct(*sweep)
+    sw = _as_sweep(sweep)
     shape = (grid.nw, grid.nv, grid.nu)
     mz = np.zeros(shape, np.float32); mr = np.zeros(shape, np.float32); mc = np.zeros(shape, np.float32)
     check(load_library().mcrt_volume_maps(n_elements, n_rows, radius_mm, total_angle, max_travel_us, speed_of_sound, C.byref(sw), C.byref(grid), ptr(mz), ptr(mr), ptr(mc)))
@@ -603,7 +608,7 @@ class Context:
     def volume_frames(self, rf_dev, n_frames, n_elements, n_rows, sweep, grid, out_dev, radius_mm=30.0, total_angle=1.0471975511965976):
         """mcrt_volume_frames: the planes [n_frames][K][E][R] of a sweep -> device floats [n_frames][nw][nv][nu] at grid's points.
         sweep: an mcrt_sweep (sweep_struct) or (K, step_rad[, pivot_mm])"""
-        sw = sweep if isinstance(sweep, Sweep) else sweep_struct(*sweep)
+        sw = _as_sweep(sweep)
         check(self.L.mcrt_volume_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, radius_mm, total_angle, C.byref(sw), C.byref(grid), ptr(out_dev)))
 
     def bmode_volume_frames(self, rf_dev, n_frames, n_elements, n_rows, sweep, grid, out_dev, *, mode="db", dynamic_range_db=60.0, gain_db=0.0, ref=None,
@@ -612,12 +617,8 @@ class Context:
         reference of a frame is the peak over its whole sweep.  persistence must stay 0 (the library refuses anything else)"""
         p = bmode_params(mode=mode, dynamic_range_db=dynamic_range_db, gain_db=gain_db, ref=ref, persistence=persistence, radius_mm=radius_mm,
                          total_angle=total_angle, out_rows=0, out_cols=0)
-        sw = sweep if isinstance(sweep, Sweep) else sweep_struct(*sweep)
-        tgc = None
-        if tgc_db is not None:
-            tgc = np.ascontiguousarray(tgc_db, np.float32)
-            if tgc.shape != (n_rows,):
-                raise ValueError("tgc_db needs one value per RF row: %d, got shape %s" % (n_rows, tgc.shape))
+        sw = _as_sweep(sweep)
+        tgc = _tgc_rows(tgc_db, n_rows)
         check(self.L.mcrt_bmode_volume_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(p), C.byref(sw), C.byref(grid), ptr(tgc), ptr(peak_dev),
                                               ptr(out_dev)))
 

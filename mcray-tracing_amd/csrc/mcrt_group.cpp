@@ -31,7 +31,7 @@
 using mcrt::set_error;
 
 namespace mcrt {
-hipStream_t ctx_stream(mcrt_ctx *c);      // mcrt_api.cpp
+hipStream_t ctx_stream(mcrt_ctx *c);      // mcrt_api.cpp (the context itself: mcrt_ctx.h)
 }
 
 namespace {

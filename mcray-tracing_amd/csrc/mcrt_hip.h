@@ -1,7 +1,8 @@
-// mcrt_hip.h -- host side only: the status macros and the owners of HIP resources that mcrt_api.cpp, mcrt_group.cpp and the host half of
-// mcrt_lbvh.hip share.  Nothing here launches or waits.
+// mcrt_hip.h -- host side only: the status macros and the owners of HIP resources that the context (mcrt_ctx.h: mcrt_api.cpp,
+// mcrt_trace.cpp, mcrt_image.cpp), mcrt_group.cpp and the host half of mcrt_lbvh.hip share.  Nothing here launches, and only Staging waits.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <utility>
 #include "../../include/mcrt.h"
 #include "mcrt_internal.h"
@@ -57,3 +58,33 @@ inline bool is_device_pointer(const void *p)
     (void)hipGetLastError();
     return false;
 }
+
+// A host array of the caller's on the device by way of pinned memory its owner keeps, so that the caller's array is free the moment the
+// call returns (the lifetime rule of include/mcrt.h).  begin(n) makes room for n floats -- the device buffer, the pinned buffer and the
+// event together, all or none; a buffer that is replaced may still be read by what is queued on st, so st is waited for first, which a
+// first allocation has no need of --, waits for the previous copy's event, whose source the pinned buffer still is, and hands out the
+// pinned pointer.  The caller fills it; commit(n) enqueues the copy on st and records the event.  Nothing else waits for the device.
+struct Staging {
+    Buf<float> dev; PinnedBuf<float> pin; Event ev; bool pending = false;
+    int begin(size_t n, hipStream_t st, float **out)
+    {
+        if (pending) { HIP_TRY(hipEventSynchronize(ev)); pending = false; }
+        if (n > dev.cap) {
+            if (dev) HIP_TRY(hipStreamSynchronize(st));
+            Buf<float> d; PinnedBuf<float> h; Event e;
+            HIP_TRY(d.alloc(n));
+            HIP_TRY(h.alloc(n));
+            HIP_TRY(ensure_event(e));
+            dev = std::move(d); pin = std::move(h); ev = std::move(e);
+        }
+        *out = pin;
+        return MCRT_OK;
+    }
+    int commit(size_t n, hipStream_t st)
+    {
+        HIP_TRY(hipMemcpyAsync(dev, pin, 4 * n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(ev, st));
+        pending = true;
+        return MCRT_OK;
+    }
+};

@@ -1,0 +1,411 @@
+// mcrt_image.cpp -- the image stages of the C-ABI (include/mcrt.h): PSF, elevation, envelope, scan conversion, B-mode, compounding,
+// volume imaging, RF export / import.  Host C++ only.  Of a context (mcrt_ctx.h) these read its device, its stream, p.speed_of_sound,
+// c.max_travel_us and the image stages' own state (ImageStages), nothing else.
+#include "mcrt_ctx.h"
+#include "mcrt_kernels.h"
+
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstring>
+#include <vector>
+#include <algorithm>
+
+using mcrt::set_error;
+
+static bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + a_bytes, b0 = (uintptr_t)b, b1 = b0 + b_bytes;
+    return a0 < b1 && b0 < a1;
+}
+
+static int ensure_tmp(mcrt_ctx *c, size_t n)
+{
+    if (n > c->img.d_tmp.cap) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(c->img.d_tmp.alloc(n));
+    }
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_convolve_frames(mcrt_ctx *c, float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const float *ax, uint32_t n_ax, const float *lat, uint32_t n_lat)
+{
+    CTX_TRY(c);
+    if (!rf_dev || !ax || !lat || E == 0 || R == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "mcrt_convolve: bad arguments");
+    if (n_ax == 0 || n_ax > 16 || n_lat == 0 || n_lat > 32) return set_error(MCRT_ERR_LIMIT, "kernel sizes must be 1..16 axial, 1..32 lateral");
+    MCRT_TRY(ensure_tmp(c, (size_t)n_frames * E * R));
+    mcrt::ConvTaps t; memset(&t, 0, sizeof t);
+    memcpy(t.ax, ax, 4 * n_ax); memcpy(t.lat, lat, 4 * n_lat); t.n_ax = n_ax; t.n_lat = n_lat;
+    HIP_TRY(mcrt::launch_convolve(rf_dev, c->img.d_tmp, n_frames, E, R, t, c->stream));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_convolve(mcrt_ctx *c, float *rf_dev, uint32_t E, uint32_t R, const float *ax, uint32_t n_ax, const float *lat, uint32_t n_lat)
+{
+    return mcrt_convolve_frames(c, rf_dev, 1, E, R, ax, n_ax, lat, n_lat);
+}
+
+// The contract is in include/mcrt.h.  Everything is checked before anything is launched; the caller's table [R][n_lat] goes to the device
+// tap-major [n_lat][R] (StagedTable).
+extern "C" int mcrt_convolve_frames_depth(mcrt_ctx *c, float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const float *ax, uint32_t n_ax,
+                                          const float *lat_rows, uint32_t n_lat)
+{
+    CTX_TRY(c);
+    if (!rf_dev || !ax || !lat_rows || E == 0 || R == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "mcrt_convolve_frames_depth: bad arguments");
+    if (n_ax == 0 || n_ax > 16 || n_lat == 0 || n_lat > 32) return set_error(MCRT_ERR_LIMIT, "kernel sizes must be 1..16 axial, 1..32 lateral");
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "mcrt_convolve_frames_depth: at most %d rows", MCRT_MAX_ROWS);
+    MCRT_TRY(ensure_tmp(c, (size_t)n_frames * E * R));
+    MCRT_TRY(c->img.lat_rows.put(lat_rows, R, n_lat, (size_t)MCRT_MAX_ROWS * 32, c->stream));
+    mcrt::ConvTaps t; memset(&t, 0, sizeof t);
+    memcpy(t.ax, ax, 4 * n_ax); t.n_ax = n_ax; t.n_lat = n_lat;
+    HIP_TRY(mcrt::launch_convolve_depth(rf_dev, c->img.d_tmp, n_frames, E, R, t, c->img.lat_rows.dev, c->stream));
+    return MCRT_OK;
+}
+
+// The contract is in include/mcrt.h.  Everything is checked before anything is launched; the caller's weights [R][K] go to the device
+// tap-major [K][R] (StagedTable).
+extern "C" int mcrt_elevation_frames(mcrt_ctx *c, const float *planes_dev, uint32_t n_frames, uint32_t K, uint32_t E, uint32_t R,
+                                     const float *w_rows, float *rf_dev)
+{
+    CTX_TRY(c);
+    if (!planes_dev || !rf_dev || !w_rows || n_frames == 0 || K == 0 || E == 0 || R == 0) return set_error(MCRT_ERR_INVALID, "mcrt_elevation_frames: bad arguments");
+    if (K > 32) return set_error(MCRT_ERR_LIMIT, "mcrt_elevation_frames: at most 32 planes (%u)", K);
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "mcrt_elevation_frames: at most %d rows", MCRT_MAX_ROWS);
+    if ((double)n_frames * (double)K * (double)E * (double)R >= 0x1p40) return set_error(MCRT_ERR_LIMIT, "mcrt_elevation_frames: the plane stack is too large");
+    if (ranges_overlap(planes_dev, 4 * (size_t)n_frames * K * E * R, rf_dev, 4 * (size_t)n_frames * E * R)) return set_error(MCRT_ERR_INVALID, "mcrt_elevation_frames: planes_dev and rf_dev overlap");
+    MCRT_TRY(c->img.elev_rows.put(w_rows, R, K, (size_t)MCRT_MAX_ROWS * 32, c->stream));
+    HIP_TRY(mcrt::launch_elevation(planes_dev, rf_dev, n_frames, K, E, R, c->img.elev_rows.dev, c->stream));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_envelope_frames(mcrt_ctx *c, float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R)
+{
+    CTX_TRY(c);
+    if (!rf_dev || E == 0 || R == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "mcrt_envelope: bad arguments");
+    if ((uint64_t)n_frames * E > 0x7fffffffull) return set_error(MCRT_ERR_LIMIT, "mcrt_envelope: too many scan-lines");
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "mcrt_envelope: at most %d rows", MCRT_MAX_ROWS);
+    HIP_TRY(mcrt::launch_envelope(rf_dev, n_frames * E, R, c->stream));      // the scan-lines of all images are independent columns
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_envelope(mcrt_ctx *c, float *rf_dev, uint32_t E, uint32_t R)
+{
+    return mcrt_envelope_frames(c, rf_dev, 1, E, R);
+}
+
+// the scan-conversion maps of a geometry on the device, in cache m: the plain maps (cp null: mcrt_scan_maps, one view) or the N views of a steer
+// list (mcrt_compound_maps), [N][2][n_pad]
+static int ensure_maps(mcrt_ctx *c, MapCache &m, uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t orows, uint32_t ocols, const mcrt_compound *cp, const float **maps)
+{
+    const uint32_t N = cp ? cp->n_views : 1u, sos = c->p.speed_of_sound;
+    MapCache::Key key;
+    key.add(E).add(R).add(orows).add(ocols).add(sos).add(N).add(radius_mm).add(total_angle).add(c->c.max_travel_us);
+    if (cp) key.add(cp->steer_rad, 4 * (size_t)N);
+    const size_t n = (size_t)orows * ocols, n_pad = MapCache::pad(n);
+    return m.get(key, 2 * (size_t)N * n_pad, c->stream, [&](std::vector<float> &out) -> int {
+        // (the rf_image template parameter is max_travel_time.to<unsigned int>(), main.cpp:36 -- the same truncation as max_rows uses)
+        const uint32_t travel = (uint32_t)c->c.max_travel_us;
+        for (uint32_t v = 0; v < N; v++) {
+            float *mc = &out[(size_t)(2u * v) * n_pad], *mr = mc + n_pad;
+            MCRT_TRY(cp ? mcrt_compound_maps(E, R, radius_mm, total_angle, travel, sos, orows, ocols, cp->steer_rad[v], mr, mc)
+                        : mcrt_scan_maps(E, R, radius_mm, total_angle, travel, sos, orows, ocols, mr, mc));
+        }
+        return MCRT_OK;
+    }, maps);
+}
+
+extern "C" int mcrt_scan_convert_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, double radius_mm, double total_angle,
+                                        float *out_dev, uint32_t orows, uint32_t ocols)
+{
+    CTX_TRY(c);
+    if (!rf_dev || !out_dev || E == 0 || R == 0 || orows == 0 || ocols == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "mcrt_scan_convert: bad arguments");
+    if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "mcrt_scan_convert: at most 65535 images per call");
+    const float *maps = nullptr;
+    MCRT_TRY(ensure_maps(c, c->img.maps, E, R, radius_mm, total_angle, orows, ocols, nullptr, &maps));
+    HIP_TRY(mcrt::launch_remap(rf_dev, n_frames, E, R, maps, maps + MapCache::pad((size_t)orows * ocols), out_dev, orows * ocols, c->stream));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_scan_convert(mcrt_ctx *c, const float *rf_dev, uint32_t E, uint32_t R, double radius_mm, double total_angle,
+                                 float *out_dev, uint32_t orows, uint32_t ocols)
+{
+    return mcrt_scan_convert_frames(c, rf_dev, 1, E, R, radius_mm, total_angle, out_dev, orows, ocols);
+}
+
+extern "C" int mcrt_default_bmode(mcrt_bmode_params *p)
+{
+    if (!p) return set_error(MCRT_ERR_INVALID, "null params");
+    memset(p, 0, sizeof *p);
+    p->mode = MCRT_BMODE_DB; p->dynamic_range_db = 60.0f; p->gain_db = 0.0f; p->ref = 0.0f; p->persistence = 0.0f; p->reset_state = 1u;
+    p->out_rows = 400u; p->out_cols = 500u; p->radius_mm = 30.0; p->total_angle_rad = 1.0471975511965976;
+    return MCRT_OK;
+}
+
+// what mcrt_bmode_frames and mcrt_bmode_compound_frames check alike (fn: the caller's name, for the message); k receives the TGC factors
+static int bmode_check(const char *fn, const float *rf_dev, const void *out_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_bmode_params *p,
+                       const float *tgc_db, std::vector<float> &k)
+{
+    if (!p) return set_error(MCRT_ERR_INVALID, "%s: null params", fn);
+    if (!rf_dev || !out_dev) return set_error(MCRT_ERR_INVALID, "%s: null %s", fn, rf_dev ? "out_dev" : "rf_dev");
+    if (E == 0 || R == 0 || n_frames == 0 || p->out_rows == 0 || p->out_cols == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes", fn);
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: at most %d rows", fn, MCRT_MAX_ROWS);
+    if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 frames per call", fn);
+    if ((uint64_t)p->out_rows * p->out_cols > 0x7ffffffcull) return set_error(MCRT_ERR_LIMIT, "%s: output image too large", fn);
+    if (p->mode != MCRT_BMODE_DB && p->mode != MCRT_BMODE_REF_LOG) return set_error(MCRT_ERR_INVALID, "%s: unknown mode %u", fn, p->mode);
+    if (!(std::isfinite(p->dynamic_range_db) && p->dynamic_range_db > 0.0f))
+        return set_error(MCRT_ERR_INVALID, "%s: dynamic_range_db must be finite and > 0 (%g)", fn, (double)p->dynamic_range_db);
+    if (!std::isfinite(p->gain_db)) return set_error(MCRT_ERR_INVALID, "%s: gain_db must be finite", fn);
+    if (!std::isfinite(p->ref)) return set_error(MCRT_ERR_INVALID, "%s: ref must be finite", fn);
+    if (!(p->persistence >= 0.0f && p->persistence < 1.0f)) return set_error(MCRT_ERR_INVALID, "%s: persistence must be in [0,1) (%g)", fn, (double)p->persistence);
+    if (tgc_db) {
+        k.resize(R);
+        for (uint32_t r = 0; r < R; r++) {
+            if (!std::isfinite(tgc_db[r])) return set_error(MCRT_ERR_INVALID, "%s: tgc_db[%u] is not finite", fn, r);
+            k[r] = (float)std::pow(10.0, (double)tgc_db[r] / 20.0);
+        }
+    }
+    return MCRT_OK;
+}
+
+// steps 1-3 of mcrt_bmode_frames on the context's stream, over n_frames images of `lines` scan-lines each (the N views of a compounded frame
+// are one image of N * E scan-lines): the TGC factors (only when they differ from the ones on the device), with the automatic reference
+// the peaks (memset + k_bmode_peak), the grey level of every RF tap (k_bmode_grey, into the context's scratch)
+static int bmode_grey_pass(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t lines, uint32_t R, const mcrt_bmode_params *p, const float *tgc_db,
+                           const std::vector<float> &k, float *peak_dev)
+{
+    if (!c->img.d_disp) HIP_TRY(c->img.d_disp.alloc(65536));   // (the peaks of the largest pass: 65535 frames)
+    if (tgc_db) MCRT_TRY(c->img.tgc.put(k.data(), R, 1, MCRT_MAX_ROWS, c->stream));
+    const size_t taps = (size_t)n_frames * lines * R;
+    MCRT_TRY(ensure_tmp(c, taps));     // the grey levels of the pass (the scratch mcrt_convolve uses too)
+    const float *tgc = tgc_db ? c->img.tgc.dev.p : nullptr;
+    if (p->ref > 0.0f) HIP_TRY(mcrt::launch_bmode_grey(rf_dev, n_frames, lines, R, tgc, nullptr, p->ref, peak_dev, p->mode, p->gain_db, p->dynamic_range_db, c->img.d_tmp, c->stream));
+    else {
+        float *peak = peak_dev ? peak_dev : c->img.d_disp.p;
+        HIP_TRY(hipMemsetAsync(peak, 0, 4 * (size_t)n_frames, c->stream));
+        HIP_TRY(mcrt::launch_bmode_peak(rf_dev, n_frames, lines, R, tgc, peak, c->stream));
+        HIP_TRY(mcrt::launch_bmode_grey(rf_dev, n_frames, lines, R, tgc, peak, 0.0f, nullptr, p->mode, p->gain_db, p->dynamic_range_db, c->img.d_tmp, c->stream));
+    }
+    return MCRT_OK;
+}
+
+// without persistence the frames are independent: they are cut into chunks (grid.y) so that a pass has about 16384 wavefronts (the
+// lanes wait for their gathers; at 400 x 500 a chunk is one frame)
+static uint32_t display_frames_per_chunk(uint32_t n_frames, uint32_t n, float alpha)
+{
+    if (alpha != 0.0f) return n_frames;
+    const uint32_t waves = (n + 255u) / 256u, chunks = std::max(1u, std::min(n_frames, (16384u + waves - 1u) / waves));
+    return (n_frames + chunks - 1u) / chunks;
+}
+
+// The contract is in include/mcrt.h.  Everything is checked before anything is launched; then, on the context's stream: the TGC factors
+// (only when they differ from the ones on the device), with the automatic reference the peaks (memset + k_bmode_peak), the grey level of
+// every RF tap (k_bmode_grey, into the context's scratch) and their scan conversion, persistence and quantisation (k_bmode).
+extern "C" int mcrt_bmode_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_bmode_params *p,
+                                 const float *tgc_db, float *state_dev, float *peak_dev, uint8_t *out_dev)
+{
+    CTX_TRY(c);
+    std::vector<float> k;
+    MCRT_TRY(bmode_check("mcrt_bmode_frames", rf_dev, out_dev, n_frames, E, R, p, tgc_db, k));
+    const float *maps = nullptr;
+    MCRT_TRY(ensure_maps(c, c->img.maps, E, R, p->radius_mm, p->total_angle_rad, p->out_rows, p->out_cols, nullptr, &maps));
+    MCRT_TRY(bmode_grey_pass(c, rf_dev, n_frames, E, R, p, tgc_db, k, peak_dev));
+    mcrt::BmodeArgs a;
+    a.grey = c->img.d_tmp; a.map_col = maps; a.map_row = maps + MapCache::pad((size_t)p->out_rows * p->out_cols); a.state = state_dev; a.out = out_dev; a.alpha = p->persistence;
+    a.E = E; a.R = R; a.n = p->out_rows * p->out_cols; a.F = n_frames; a.reset = p->reset_state ? 1u : 0u;
+    a.frames_per_chunk = display_frames_per_chunk(n_frames, a.n, a.alpha);
+    HIP_TRY(mcrt::launch_bmode(a, c->stream));
+    return MCRT_OK;
+}
+
+// ---- spatial compounding (the contracts are in include/mcrt.h) ----
+static int compound_check(const char *fn, const mcrt_compound *cp, uint32_t n_frames)
+{
+    if (!cp) return set_error(MCRT_ERR_INVALID, "%s: null mcrt_compound", fn);
+    if (cp->n_views == 0 || cp->n_views > 16) return set_error(MCRT_ERR_INVALID, "%s: n_views must be 1..16 (%u)", fn, cp->n_views);
+    for (uint32_t n = 0; n < cp->n_views; n++)
+        if (!(std::isfinite(cp->steer_rad[n]) && std::fabs((double)cp->steer_rad[n]) < 1.57079632679489661923))
+            return set_error(MCRT_ERR_INVALID, "%s: steer_rad[%u] must be finite and |steer| < pi/2 (%g)", fn, n, (double)cp->steer_rad[n]);
+    if ((uint64_t)n_frames * cp->n_views > 65535ull) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 views per call (%u frames x %u)", fn, n_frames, cp->n_views);
+    return MCRT_OK;
+}
+
+// the options of the two *_opts calls, checked alike (null: the defaults), turned into the kernel's mode and weights.  Defaults -- the mean,
+// no feathering, every weight of the first n_views 1.0f -- are COMPOUND_PLAIN: the kernel mcrt_compound_frames has always run
+static int compound_opts_check(const char *fn, const mcrt_compound_opts *o, uint32_t N, mcrt::CompoundArgs &a)
+{
+    a.mode = mcrt::COMPOUND_PLAIN; a.feather = 0.0f;
+    for (float &w : a.weight) w = 1.0f;
+    if (!o) return MCRT_OK;
+    if (o->mode != MCRT_COMPOUND_MEAN && o->mode != MCRT_COMPOUND_MAX && o->mode != MCRT_COMPOUND_MEDIAN) return set_error(MCRT_ERR_INVALID, "%s: unknown mode %u", fn, o->mode);
+    if (!(std::isfinite(o->feather_lines) && o->feather_lines >= 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: feather_lines must be finite and >= 0 (%g)", fn, (double)o->feather_lines);
+    bool ones = true, any = false;
+    for (uint32_t n = 0; n < N; n++) {
+        const float w = o->view_weight[n];
+        if (!(std::isfinite(w) && w >= 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: view_weight[%u] must be finite and >= 0 (%g)", fn, n, (double)w);
+        ones = ones && w == 1.0f; any = any || w > 0.0f;
+    }
+    if (!any) return set_error(MCRT_ERR_INVALID, "%s: view_weight: every one of the %u views has weight 0", fn, N);
+    if (o->mode == MCRT_COMPOUND_MEAN && o->feather_lines == 0.0f && ones) return MCRT_OK;
+    a.mode = o->mode == MCRT_COMPOUND_MAX ? mcrt::COMPOUND_MAX : o->mode == MCRT_COMPOUND_MEDIAN ? mcrt::COMPOUND_MEDIAN : mcrt::COMPOUND_WEIGHTED;
+    a.feather = o->feather_lines;
+    for (uint32_t n = 0; n < N; n++) a.weight[n] = o->view_weight[n];
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_default_compound_opts(mcrt_compound_opts *o)
+{
+    if (!o) return set_error(MCRT_ERR_INVALID, "mcrt_default_compound_opts: null options");
+    o->mode = MCRT_COMPOUND_MEAN; o->feather_lines = 0.0f;
+    for (float &w : o->view_weight) w = 1.0f;
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_compound_frames_opts(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, double radius_mm, double total_angle,
+                                         const mcrt_compound *cp, float *out_dev, uint32_t orows, uint32_t ocols, const mcrt_compound_opts *o)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_compound_frames";
+    if (!rf_dev || !out_dev || E == 0 || R == 0 || orows == 0 || ocols == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "%s: bad arguments", fn);
+    if (!(total_angle > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: total_angle_rad must be > 0", fn);
+    MCRT_TRY(compound_check(fn, cp, n_frames));
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: at most %d rows", fn, MCRT_MAX_ROWS);
+    if ((uint64_t)orows * ocols > 0x7ffffffcull) return set_error(MCRT_ERR_LIMIT, "%s: output image too large", fn);
+    const uint32_t N = cp->n_views, n = orows * ocols;
+    if (ranges_overlap(rf_dev, 4 * (size_t)n_frames * N * E * R, out_dev, 4 * (size_t)n_frames * n)) return set_error(MCRT_ERR_INVALID, "%s: rf_dev and out_dev overlap", fn);
+    mcrt::CompoundArgs a;
+    MCRT_TRY(compound_opts_check(fn, o, N, a));
+    MCRT_TRY(ensure_maps(c, c->img.cmaps, E, R, radius_mm, total_angle, orows, ocols, cp, &a.maps));
+    a.src = rf_dev; a.state = nullptr; a.out = out_dev; a.alpha = 0.0f;
+    a.E = E; a.R = R; a.n = n; a.n_pad = (uint32_t)MapCache::pad(n); a.F = n_frames; a.N = N; a.reset = 1u;
+    a.frames_per_chunk = display_frames_per_chunk(n_frames, n, 0.0f);
+    HIP_TRY(mcrt::launch_compound(a, false, c->stream));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_compound_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, double radius_mm, double total_angle,
+                                    const mcrt_compound *cp, float *out_dev, uint32_t orows, uint32_t ocols)
+{
+    return mcrt_compound_frames_opts(c, rf_dev, n_frames, E, R, radius_mm, total_angle, cp, out_dev, orows, ocols, nullptr);
+}
+
+extern "C" int mcrt_bmode_compound_frames_opts(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_bmode_params *p,
+                                               const mcrt_compound *cp, const float *tgc_db, float *state_dev, float *peak_dev, uint8_t *out_dev,
+                                               const mcrt_compound_opts *o)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_bmode_compound_frames";
+    std::vector<float> k;
+    MCRT_TRY(bmode_check(fn, rf_dev, out_dev, n_frames, E, R, p, tgc_db, k));
+    if (!(p->total_angle_rad > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: total_angle_rad must be > 0", fn);
+    MCRT_TRY(compound_check(fn, cp, n_frames));
+    const uint32_t N = cp->n_views, n = p->out_rows * p->out_cols;
+    if ((uint64_t)N * E > 0xffffffffull) return set_error(MCRT_ERR_LIMIT, "%s: too many scan-lines (%u views x %u)", fn, N, E);   // (a frame is N * E scan-lines to steps 1-3)
+    if (ranges_overlap(rf_dev, 4 * (size_t)n_frames * N * E * R, out_dev, (size_t)n_frames * n)) return set_error(MCRT_ERR_INVALID, "%s: rf_dev and out_dev overlap", fn);
+    mcrt::CompoundArgs a;
+    MCRT_TRY(compound_opts_check(fn, o, N, a));
+    MCRT_TRY(ensure_maps(c, c->img.cmaps, E, R, p->radius_mm, p->total_angle_rad, p->out_rows, p->out_cols, cp, &a.maps));
+    MCRT_TRY(bmode_grey_pass(c, rf_dev, n_frames, N * E, R, p, tgc_db, k, peak_dev));
+    a.src = c->img.d_tmp; a.state = state_dev; a.out = out_dev; a.alpha = p->persistence;
+    a.E = E; a.R = R; a.n = n; a.n_pad = (uint32_t)MapCache::pad(n); a.F = n_frames; a.N = N; a.reset = p->reset_state ? 1u : 0u;
+    a.frames_per_chunk = display_frames_per_chunk(n_frames, n, a.alpha);
+    HIP_TRY(mcrt::launch_compound(a, true, c->stream));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_bmode_compound_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_bmode_params *p,
+                                          const mcrt_compound *cp, const float *tgc_db, float *state_dev, float *peak_dev, uint8_t *out_dev)
+{
+    return mcrt_bmode_compound_frames_opts(c, rf_dev, n_frames, E, R, p, cp, tgc_db, state_dev, peak_dev, out_dev, nullptr);
+}
+
+// ---- volume imaging (the contracts are in include/mcrt.h) ----
+// the three maps of a grid on the device, [3][n_pad]: plane, column, row (mcrt_volume_maps)
+static int ensure_volume_maps(mcrt_ctx *c, uint32_t E, uint32_t R, double radius_mm, double total_angle, const mcrt_sweep *sw, const mcrt_volume_grid *g, const float **maps)
+{
+    const uint32_t sos = c->p.speed_of_sound;
+    MapCache::Key key;
+    key.add(E).add(R).add(sos).add(sw->n_planes).add(sw->step_rad).add(sw->pivot_mm).add(g->nu).add(g->nv).add(g->nw);
+    key.add(radius_mm).add(total_angle).add(c->c.max_travel_us).add(g->origin_mm).add(g->du_mm).add(g->dv_mm).add(g->dw_mm);
+    const size_t n_pad = MapCache::pad((size_t)g->nu * g->nv * g->nw);
+    return c->img.vmaps.get(key, 3 * n_pad, c->stream, [&](std::vector<float> &m) {
+        return mcrt_volume_maps(E, R, radius_mm, total_angle, (uint32_t)c->c.max_travel_us, sos, sw, g, &m[0], &m[2 * n_pad], &m[n_pad]);
+    }, maps);
+}
+
+// what the two entry points check of the stack and the grid before anything else happens
+static int volume_args_check(const char *fn, uint32_t n_frames, uint32_t E, uint32_t R, double total_angle, const mcrt_sweep *sw, const mcrt_volume_grid *g)
+{
+    if (E == 0 || R == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes", fn);
+    if (!(total_angle > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: total_angle_rad must be > 0", fn);
+    MCRT_TRY(mcrt::volume_check(fn, sw, g));
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: at most %d rows", fn, MCRT_MAX_ROWS);
+    if ((uint64_t)n_frames * sw->n_planes > 65535ull) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 planes per call (%u frames x %u)", fn, n_frames, sw->n_planes);
+    return MCRT_OK;
+}
+
+static mcrt::VolumeArgs volume_args(const float *src, const float *maps, void *out, uint32_t n_frames, uint32_t E, uint32_t R, uint32_t K, uint32_t n, bool out8)
+{
+    mcrt::VolumeArgs a;
+    a.src = src; a.maps = maps; a.out = out; a.E = E; a.R = R; a.K = K; a.n = n; a.n_pad = (uint32_t)MapCache::pad(n); a.F = n_frames;
+    a.frames_per_chunk = display_frames_per_chunk(n_frames, n, 0.0f);
+    a.vec = out8 && n % 4u == 0u && (uintptr_t)out % 4u == 0u ? 1u : 0u;
+    return a;
+}
+
+extern "C" int mcrt_volume_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, double radius_mm, double total_angle,
+                                  const mcrt_sweep *sw, const mcrt_volume_grid *g, float *out_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_volume_frames";
+    if (!rf_dev || !out_dev) return set_error(MCRT_ERR_INVALID, "%s: null %s", fn, rf_dev ? "out_dev" : "rf_dev");
+    MCRT_TRY(volume_args_check(fn, n_frames, E, R, total_angle, sw, g));
+    const uint32_t K = sw->n_planes, n = g->nu * g->nv * g->nw;
+    if (ranges_overlap(rf_dev, 4 * (size_t)n_frames * K * E * R, out_dev, 4 * (size_t)n_frames * n)) return set_error(MCRT_ERR_INVALID, "%s: rf_dev and out_dev overlap", fn);
+    const float *maps = nullptr;
+    MCRT_TRY(ensure_volume_maps(c, E, R, radius_mm, total_angle, sw, g, &maps));
+    HIP_TRY(mcrt::launch_volume(volume_args(rf_dev, maps, out_dev, n_frames, E, R, K, n, false), false, c->stream));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_bmode_volume_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_bmode_params *p,
+                                        const mcrt_sweep *sw, const mcrt_volume_grid *g, const float *tgc_db, float *peak_dev, uint8_t *out_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_bmode_volume_frames";
+    if (!p) return set_error(MCRT_ERR_INVALID, "%s: null params", fn);
+    mcrt_bmode_params q = *p;
+    q.out_rows = q.out_cols = 1u;                       // the picture is the grid's: p's own size is not looked at
+    std::vector<float> k;
+    MCRT_TRY(bmode_check(fn, rf_dev, out_dev, n_frames, E, R, &q, tgc_db, k));
+    if (p->persistence != 0.0f) return set_error(MCRT_ERR_INVALID, "%s: persistence must be 0 on a volume (%g)", fn, (double)p->persistence);
+    MCRT_TRY(volume_args_check(fn, n_frames, E, R, p->total_angle_rad, sw, g));
+    const uint32_t K = sw->n_planes, n = g->nu * g->nv * g->nw;
+    if ((uint64_t)K * E > 0xffffffffull) return set_error(MCRT_ERR_LIMIT, "%s: too many scan-lines (%u planes x %u)", fn, K, E);   // (a frame is K * E scan-lines to steps 1-3)
+    if (ranges_overlap(rf_dev, 4 * (size_t)n_frames * K * E * R, out_dev, (size_t)n_frames * n)) return set_error(MCRT_ERR_INVALID, "%s: rf_dev and out_dev overlap", fn);
+    const float *maps = nullptr;
+    MCRT_TRY(ensure_volume_maps(c, E, R, p->radius_mm, p->total_angle_rad, sw, g, &maps));
+    MCRT_TRY(bmode_grey_pass(c, rf_dev, n_frames, K * E, R, &q, tgc_db, k, peak_dev));
+    HIP_TRY(mcrt::launch_volume(volume_args(c->img.d_tmp, maps, out_dev, n_frames, E, R, K, n, true), true, c->stream));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_export_rf(mcrt_ctx *c, const float *rf_dev, uint32_t E, uint32_t R, float *host)
+{
+    CTX_TRY(c);
+    if (!rf_dev || !host || E == 0 || R == 0) return set_error(MCRT_ERR_INVALID, "mcrt_export_rf: bad arguments");
+    MCRT_TRY(ensure_tmp(c, (size_t)E * R));
+    HIP_TRY(mcrt::launch_transpose(rf_dev, c->img.d_tmp, E, R, c->stream));
+    HIP_TRY(hipMemcpyAsync(host, c->img.d_tmp, (size_t)E * R * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_import_rf(mcrt_ctx *c, const float *host, uint32_t E, uint32_t R, float *rf_dev)
+{
+    CTX_TRY(c);
+    if (!rf_dev || !host || E == 0 || R == 0) return set_error(MCRT_ERR_INVALID, "mcrt_import_rf: bad arguments");
+    MCRT_TRY(ensure_tmp(c, (size_t)E * R));
+    HIP_TRY(hipMemcpyAsync(c->img.d_tmp, host, (size_t)E * R * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(mcrt::launch_transpose(c->img.d_tmp, rf_dev, R, E, c->stream));          // [R][E] -> [E][R]
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MCRT_OK;
+}

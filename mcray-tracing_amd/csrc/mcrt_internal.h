@@ -37,7 +37,7 @@ int set_error(int code, const char *fmt, ...);
 const char *tuning_env(const char *name);
 }
 #ifdef MCRT_H
-// mcrt_api.cpp <-> mcrt_group.cpp: a scene (or a triangle update) installed with a tree the HOST builder has already made of exactly
+// mcrt_api.cpp <-> mcrt_group.cpp (what crosses between mcrt_api.cpp, mcrt_trace.cpp and mcrt_image.cpp is in mcrt_ctx.h): a scene (or a triangle update) installed with a tree the HOST builder has already made of exactly
 // these triangles -- a group builds once on the calling thread and every rank copies and uploads (the device builder ignores it)
 namespace mcrt {
 struct HostTree { const mcrt_bvh *bvh; const mcrt_bvh4 *bvh4; };

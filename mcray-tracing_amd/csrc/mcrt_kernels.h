@@ -1,4 +1,4 @@
-// mcrt_kernels.h -- kernel argument blocks and launchers: the interface between the host C++ (mcrt_api.cpp, mcrt_group.cpp; mcrt_hip.h owns their HIP resources) and the gfx950 kernels.
+// mcrt_kernels.h -- kernel argument blocks and launchers: the interface between the host C++ (mcrt_api.cpp, mcrt_trace.cpp, mcrt_image.cpp, mcrt_group.cpp; mcrt_hip.h owns their HIP resources) and the gfx950 kernels.
 //
 // The hot path's kernels, one translation unit per pipeline stage, each kernel beside its launcher:
 //   mcrt_walk.hip    k_trace_lane / k_trace_lane_wide (closest hit, one lane per ray), k_trace_packet (one wavefront per ray packet),

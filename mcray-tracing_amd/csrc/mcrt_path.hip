@@ -172,7 +172,7 @@ __global__ void __launch_bounds__(256, MCRT_PATH_WAVES) k_path(FrameArgs a)
 #undef MCRT_WORD
 }
 
-// every bounce of every path in one launch (k_path): the latency form, for passes of at most path_max paths (mcrt_api.cpp)
+// every bounce of every path in one launch (k_path): the latency form, for passes of at most path_max paths (mcrt_trace.cpp)
 uint32_t path_blocks(size_t np) { return (uint32_t)((np + 4u * MCRT_PATH_OWNERS - 1u) / (4u * MCRT_PATH_OWNERS)); }      // workgroups of a k_path launch over np paths
 hipError_t launch_path(const FrameArgs &a, hipStream_t st)
 {

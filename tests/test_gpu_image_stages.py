@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 
 import bmode_mirror as bm
+import compound_mirror as cm
 import image_cases as ic
+import volume_mirror as vm
 
 pytestmark = pytest.mark.gpu
 
@@ -212,6 +214,45 @@ def test_bmode_shares_the_map_cache(mcrt, orc):
                 got = c.d2h(out, (1, orows, ocols), np.uint8)
                 want, _, _ = bm.bmode(orc, frames, radius_mm=radius, total_angle=angle, out_rows=orows, out_cols=ocols)
                 bm.assert_close(got[0], want[0])
+    finally:
+        d.close()
+        c.close()
+
+
+def test_the_three_map_caches_do_not_evict_each_other(mcrt, orc):
+    """scan conversion, a two-view compound, a volume of two planes and a B-mode frame in turn on one context, twice round, nothing waited
+    for between the calls: the plain, the compound and the volume maps live in three caches of one type, and every output of both rounds
+    equals its mirror (merged into one pool of slots, a later call's maps would replace an earlier call's)"""
+    c = mcrt.Context(0)
+    d = Dev(c)
+    try:
+        E, R, rows, cols, K = 16, 64, 20, 24, 2                # 480 pixels: one whole wavefront of 256 and a tail
+        radius, angle = ic.SCAN_GEOMETRIES[0][:2]
+        geom = dict(radius_mm=radius, total_angle=angle, out_rows=rows, out_cols=cols)
+        steers, sweep = (0.0, 0.1), (K, vm.STEP, 0.0)
+        g = vm.grid_for(mcrt, (9, 7, 2), E, R, K, 0.0)
+        img = ic.scan_image(E, R)
+        views = np.stack([ic.scan_image(E, R, seed=1 + n) for n in range(2)])[None]
+        planes = np.stack([ic.scan_image(E, R, seed=3 + k) for k in range(K)])[None]
+        frames = bmode_frames(E, R, 1)
+        p_img, p_views, p_planes, p_frames = d.upload(img), d.upload(views), d.upload(planes), d.upload(frames)
+        n, nv = rows * cols, g.nu * g.nv * g.nw
+        outs = [(d(4 * n, 0xA5), d(4 * n, 0xA5), d(4 * nv, 0xA5), d(n, 0xA5)) for _ in range(2)]
+        for scan, comp, vol, grey in outs:
+            c.scan_convert_frames(p_img, 1, E, R, scan, **geom)
+            c.compound_frames(p_views, 1, E, R, steers, comp, **geom)
+            c.volume_frames(p_planes, 1, E, R, sweep, g, vol, radius_mm=radius, total_angle=angle)
+            c.bmode_frames(p_frames, 1, E, R, grey, **geom)
+        c.synchronize()
+        want_scan = _want(orc, img, (radius, angle, rows, cols))
+        want_comp = cm.compound_frames(views, [mcrt.host_compound_maps(E, R, s, radius, angle, out_rows=rows, out_cols=cols) for s in steers])
+        want_vol = vm.volume_frames(planes, mcrt.host_volume_maps(E, R, sweep, g, radius_mm=radius, total_angle=angle))
+        want_grey, _, _ = bm.bmode(orc, frames, **geom)
+        for i, (scan, comp, vol, grey) in enumerate(outs):
+            ic.assert_same_bits(c.d2h(scan, (rows, cols)), want_scan, "scan conversion, round %d" % i)
+            ic.assert_same_bits(c.d2h(comp, (1, rows, cols)), want_comp, "compound, round %d" % i)
+            ic.assert_same_bits(c.d2h(vol, (1, g.nw, g.nv, g.nu)), want_vol, "volume, round %d" % i)
+            bm.assert_close(c.d2h(grey, (1, rows, cols), np.uint8)[0], want_grey[0])
     finally:
         d.close()
         c.close()
