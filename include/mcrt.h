@@ -42,7 +42,9 @@ extern "C" {
                                    + mcrt_compound_opts, mcrt_default_compound_opts, mcrt_compound_weights, mcrt_compound_frames_opts,
                                    mcrt_bmode_compound_frames_opts (compounding modes: per-view weights, a lateral edge ramp, max, median; additive);
                                    + mcrt_sweep, mcrt_volume_grid, mcrt_transducer_swept, mcrt_volume_maps, mcrt_volume_frames, mcrt_bmode_volume_frames
-                                   (volume imaging: a probe swept in elevation, 3-D scan conversion into voxels or any cut; additive) */
+                                   (volume imaging: a probe swept in elevation, 3-D scan conversion into voxels or any cut; additive);
+                                   + mcrt_label_opts, mcrt_default_label_opts, mcrt_label_frames, mcrt_label_scan_convert_frames, mcrt_label_volume_frames
+                                   (ground-truth label maps: tissue and interface per scan-line sample, pixel and voxel; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -536,6 +538,79 @@ int mcrt_volume_frames(mcrt_ctx *ctx, const float *rf_dev /* [n_frames][K][E][R]
 int mcrt_bmode_volume_frames(mcrt_ctx *ctx, const float *rf_dev /* [n_frames][K][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
                              const mcrt_bmode_params *p, const mcrt_sweep *sweep, const mcrt_volume_grid *grid,
                              const float *tgc_db /* host [n_rows] or NULL */, float *peak_dev /* [n_frames] or NULL */,
+                             uint8_t *out_dev /* [n_frames][nw][nv][nu] */);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Ground-truth label maps: what is in the picture.  The tracer knows the anatomy exactly; these calls hand it out aligned with every
+ * image the library makes -- sample by sample along each scan-line (mcrt_label_frames), pixel by pixel in the sector
+ * (mcrt_label_scan_convert_frames), voxel by voxel in a swept volume (mcrt_label_volume_frames).  The reference draws pictures only:
+ * ray.cpp:13-47 decides the medium behind a boundary, rfimage.h:33-40 the row of an echo, rfimage.h:183-215 the sector's maps,
+ * scene.cpp:115 the start offset of a ray; it keeps no map of what it drew.
+ *
+ * mcrt_label_frames walks the CENTRAL BEAM of every scan-line -- the straight line along the element's direction, which is bounce 0 of
+ * every sample path -- deterministically: it does not depend on n_samples, the seed, the frame id or the texture.  Per scan-line, every
+ * float operation rounded on its own (no fma), spacing the scene's, R = n_rows:
+ *   state   from = el_pos, dir = el_dir, dist = 0.0 (double), b_prev = 0, k = 0;
+ *           TRACED: media = start_mat, outside = none;   GEOMETRIC: an empty stack of mesh ids (capacity 16), media = start_mat
+ *   loop    1. Ls = (float)(2.0 * depth_cm);  to = from + Ls * (spacing * dir);  f2 = from + offs * dir      [per component: the tracer's
+ *              own segment arithmetic; offs = start_offset, or the context's ray_start_offset]
+ *           2. when k == MCRT_LABEL_MAX_CROSSINGS stop (no further query is made; bit 31 of crossings is set).  Take the closest hit of
+ *              the segment (f2, to) under the closest-hit contract; on a miss stop
+ *           3. p = (1-frac)*f2 + frac*to, the contract's own hit point
+ *           4. mm = distance_in_mm(from, p) = sqrt(xd^2 + yd^2 + zd^2) * 10 in double, xd = |from.x - p.x| * spacing.x in float (travel,
+ *              ray.cpp:99-103);  dist += mm
+ *           5. t = ((dist * 1000.0) / 1.0) / (double)speed_of_sound
+ *           6. stop when !(t < max_travel_us)
+ *           7. b = the row of t by add_echo's rule, (int)(t / row_dt) (rfimage.h:33-40, through mcrt_row_thresholds); stop when it is not < R
+ *           8. rows [b_prev, b) get media;  interface[b] gets the hit triangle's mesh id if it still holds -1 (the shallowest boundary of a
+ *              row wins);  the medium is updated (below);  b_prev = b, from = p, k++
+ *   after   rows [b_prev, R) get media;  crossings = k, bit 31 set when the walk stopped at the cap or (GEOMETRIC) the stack overflowed
+ * Row ownership: the row that contains a boundary belongs to the medium BEHIND the boundary; a layer thinner than a row owns no row and
+ * shows in `interface` only.  The tracer deposits a boundary's own echo up to one row EARLIER, at t_start + time_step * (steps - 1): the
+ * last whole axial step before the boundary, not the boundary's own time.  And where the material behind a boundary has a non-zero
+ * thickness, the tracer's path length runs to the hit point plus a random penetration along the ray (scene.cpp:132-139), so its later
+ * boundaries' echoes lie that much deeper than the rows given here, which are measured to the hit points themselves.
+ * The medium update.  MCRT_LABEL_TRACED: exactly the four branches of hit_boundary that make the medium and the vascular memory of the
+ * refracted ray (ray.cpp:13-47), quirk 1 included -- leaving a non-vascular mesh keeps its mat_inside.  This map explains the picture the
+ * tracer draws.  MCRT_LABEL_GEOMETRIC: if the hit mesh is on the stack it is removed (the beam leaves it), else pushed (it enters);
+ * media = stack empty ? start_mat : mat_inside(top).  This is the anatomy, for closed, nested meshes whatever their orientation.  On
+ * overflow the entry is dropped and bit 31 of crossings is set.
+ * A start_offset larger than a wall's thickness skips the far wall in either rule -- the tracer's own behaviour at its 0.1 --: GEOMETRIC
+ * callers should pass a small offset such as 1e-3.
+ * pos == NULL means the context's transducer (mcrt_set_transducer), and then n_frames must be 1; otherwise pos and dir are pose tables
+ * [n_frames][n_elements][3], host or device, with the lifetime rules of mcrt_trace_frames_poses.  Outputs, each a device pointer or
+ * NULL, ne = e_end - e_begin: tissue_dev uint8 [n_frames][ne][R] material indices; interface_dev int32 [n_frames][ne][R] mesh ids, -1
+ * where no boundary falls; crossings_dev uint32 [n_frames][ne].  Asynchronous on the context's stream, one launch; nothing is allocated
+ * after the first call of a size.
+ * MCRT_ERR_INVALID: a null context, no scene, no transducer (pos NULL), e_begin >= e_end or e_end > n_elements, only one of pos / dir, all
+ * three outputs NULL, an unknown rule, a start_offset that is not finite or is 0, n_frames != 1 with pos NULL, n_frames == 0.
+ * MCRT_ERR_LIMIT: more than 254 materials (255 is MCRT_LABEL_NONE), n_frames > 1024.  On an error nothing is launched and nothing is
+ * written.  The traversal stack is sized from the tree as in the traced pass; a walk that runs away sets the context's error word.
+ * Groups: there is no group call -- the root context has no scene.  Take labels on mcrt_group_member(grp, 0), which shares the root's GPU,
+ * and mcrt_synchronize it before the root reads them. */
+enum { MCRT_LABEL_TRACED = 0, MCRT_LABEL_GEOMETRIC = 1 };
+#define MCRT_LABEL_NONE 255u          /* tissue value of "no data" (outside the sector / sweep) */
+#define MCRT_LABEL_MAX_CROSSINGS 64u
+typedef struct { uint32_t rule;          /* MCRT_LABEL_*                                                  (TRACED) */
+                 float    start_offset;  /* scene units; < 0: the context's ray_start_offset              (-1)     */
+} mcrt_label_opts;                       /* 8 bytes: rule at 0, start_offset at 4 */
+int mcrt_default_label_opts(mcrt_label_opts *o);                             /* host only */
+int mcrt_label_frames(mcrt_ctx *ctx, uint32_t n_frames, uint32_t e_begin, uint32_t e_end,
+                      const float *pos /* [n_frames][E][3] host or device, or NULL */, const float *dir /* same */,
+                      const mcrt_label_opts *o /* NULL = defaults */,
+                      uint8_t *tissue_dev /* [n_frames][ne][R] or NULL */, int32_t *interface_dev /* [n_frames][ne][R] or NULL */,
+                      uint32_t *crossings_dev /* [n_frames][ne] or NULL */);
+/* Labels as pictures: a NEAREST-NEIGHBOUR gather (labels cannot be interpolated) of tissue maps through the cached maps of
+ * mcrt_scan_convert_frames / mcrt_volume_frames -- the same device buffers under the same keys, so alternating a picture and its labels
+ * uploads nothing.  Per map coordinate m of an output point, in float:
+ *   f = floorf(m);  a = m - f;  i = (long long)f + (a >= 0.5f);   inside when 0 <= i < extent      [extents: E, R and, for the volume, K]
+ * out = every coordinate inside ? tissue[..][i_col][i_row] : MCRT_LABEL_NONE; a NaN map value is outside.  Every output element is written.
+ * Errors and limits are those of the float calls they mirror (tissue_dev in rf_dev's place).  Interface maps are NOT scan-converted: a
+ * one-row arc does not survive a nearest gather at the display's pixel pitch. */
+int mcrt_label_scan_convert_frames(mcrt_ctx *ctx, const uint8_t *tissue_dev /* [n_frames][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
+                                   double radius_mm, double total_angle_rad, uint8_t *out_dev /* [n_frames][out_rows][out_cols] */, uint32_t out_rows, uint32_t out_cols);
+int mcrt_label_volume_frames(mcrt_ctx *ctx, const uint8_t *tissue_dev /* [n_frames][K][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
+                             double radius_mm, double total_angle_rad, const mcrt_sweep *sweep, const mcrt_volume_grid *grid,
                              uint8_t *out_dev /* [n_frames][nw][nv][nu] */);
 
 /* device [E][R]  ->  host [R][E] row-major (the cv::Mat layout of rfimage.h:217); synchronous */

@@ -79,13 +79,18 @@ class VolumeGrid(C.Structure):
                 ("nu", C.c_uint32), ("nv", C.c_uint32), ("nw", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class LabelOpts(C.Structure):
+    """mcrt_label_opts (include/mcrt.h): 8 bytes, start_offset at offset 4"""
+    _fields_ = [("rule", C.c_uint32), ("start_offset", C.c_float)]
+
+
 NODE_DTYPE = np.dtype([("lo0", "<f4", 3), ("c0", "<i4"), ("hi0", "<f4", 3), ("c1", "<i4"),
                        ("lo1", "<f4", 3), ("pad0", "<u4"), ("hi1", "<f4", 3), ("pad1", "<u4")])
 SEGMENT_DTYPE = np.dtype([("from", "<f4", 3), ("to", "<f4", 3), ("dir", "<f4", 3),
                           ("reflected_intensity", "<f4"), ("initial_intensity", "<f4"), ("attenuation", "<f4"),
                           ("distance_traveled", "<f8"), ("media", "<i4"), ("tri", "<i4")])
 assert NODE_DTYPE.itemsize == 64 and SEGMENT_DTYPE.itemsize == 64 and C.sizeof(BvhNode) == 64 and C.sizeof(BmodeParams) == 48 and C.sizeof(Focus) == 40 and C.sizeof(Compound) == 68 and C.sizeof(CompoundOpts) == 72
-assert C.sizeof(Sweep) == 12 and C.sizeof(VolumeGrid) == 112
+assert C.sizeof(Sweep) == 12 and C.sizeof(VolumeGrid) == 112 and C.sizeof(LabelOpts) == 8
 
 # every symbol include/mcrt.h declares (tests/test_abi.py checks the .so exports each one)
 SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create", "mcrt_destroy", "mcrt_set_stream",
@@ -100,7 +105,8 @@ SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create"
            "mcrt_group_set_transducer", "mcrt_group_trace_frames", "mcrt_group_trace_frames_poses", "mcrt_group_synchronize", "mcrt_group_last_pass_ms", "mcrt_group_last_scene_seconds",
            "mcrt_transducer_steered", "mcrt_compound_maps", "mcrt_compound_frames", "mcrt_bmode_compound_frames",
            "mcrt_default_compound_opts", "mcrt_compound_weights", "mcrt_compound_frames_opts", "mcrt_bmode_compound_frames_opts",
-           "mcrt_transducer_swept", "mcrt_volume_maps", "mcrt_volume_frames", "mcrt_bmode_volume_frames"]
+           "mcrt_transducer_swept", "mcrt_volume_maps", "mcrt_volume_frames", "mcrt_bmode_volume_frames",
+           "mcrt_default_label_opts", "mcrt_label_frames", "mcrt_label_scan_convert_frames", "mcrt_label_volume_frames"]
 
 
 def build_library(force=False):
@@ -162,6 +168,10 @@ def load_library():
         "mcrt_volume_maps": [u32, u32, C.c_double, C.c_double, u32, u32, C.POINTER(Sweep), C.POINTER(VolumeGrid), vp, vp, vp],
         "mcrt_volume_frames": [vp, vp, u32, u32, u32, C.c_double, C.c_double, C.POINTER(Sweep), C.POINTER(VolumeGrid), vp],
         "mcrt_bmode_volume_frames": [vp, vp, u32, u32, u32, C.POINTER(BmodeParams), C.POINTER(Sweep), C.POINTER(VolumeGrid), vp, vp, vp],
+        "mcrt_default_label_opts": [C.POINTER(LabelOpts)],
+        "mcrt_label_frames": [vp, u32, u32, u32, vp, vp, C.POINTER(LabelOpts), vp, vp, vp],
+        "mcrt_label_scan_convert_frames": [vp, vp, u32, u32, u32, C.c_double, C.c_double, vp, u32, u32],
+        "mcrt_label_volume_frames": [vp, vp, u32, u32, u32, C.c_double, C.c_double, C.POINTER(Sweep), C.POINTER(VolumeGrid), vp],
         "mcrt_debug_math": [vp, i32, vp, vp, vp, u32], "mcrt_debug_philox": [vp, vp, vp, vp], "mcrt_debug_stamps": [vp, vp, i32], "mcrt_debug_tail_histograms": [vp, vp, i32], "mcrt_debug_set_error": [vp, u32], "mcrt_debug_fast_paths": [vp, vp],
         "mcrt_scan_maps": [u32, u32, C.c_double, C.c_double, u32, u32, u32, u32, vp, vp],
         "mcrt_group_create": [vp, u32, C.POINTER(vp)], "mcrt_group_destroy": [vp], "mcrt_group_size": [vp], "mcrt_group_root": [vp], "mcrt_group_member": [vp, u32],

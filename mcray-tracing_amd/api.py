@@ -10,7 +10,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 
 # ------------------------------------------------------------------ host-side pieces (no GPU)
@@ -258,6 +258,23 @@ def host_volume_maps(n_elements, n_rows, sweep, grid, radius_mm=30.0, total_angl
 
 
 BMODE_MODES = {"db": 0, "ref_log": 1}
+
+
+LABEL_RULES = {"traced": 0, "geometric": 1}
+LABEL_NONE = 255            # MCRT_LABEL_NONE: the tissue value of "no data" (outside the sector / sweep)
+LABEL_MAX_CROSSINGS = 64    # MCRT_LABEL_MAX_CROSSINGS
+LABEL_CAPPED = 1 << 31      # bit 31 of a crossings word: the walk stopped at the cap, or the GEOMETRIC stack overflowed
+
+
+def label_opts_struct(rule="traced", start_offset=None):
+    """mcrt_label_opts from keywords: rule "traced" (the media the tracer's rays carry, quirks included) / "geometric" (the anatomy of closed,
+    nested meshes) or the MCRT_LABEL_* number; start_offset in scene units (None: the context's ray_start_offset)"""
+    o = LabelOpts()
+    check(load_library().mcrt_default_label_opts(C.byref(o)))
+    o.rule = LABEL_RULES[rule] if isinstance(rule, str) else int(rule)
+    if start_offset is not None:
+        o.start_offset = float(start_offset)
+    return o
 
 
 def bmode_params(mode="db", dynamic_range_db=60.0, gain_db=0.0, ref=None, persistence=0.0, reset_state=True, radius_mm=30.0,
@@ -622,6 +639,34 @@ class Context:
         check(self.L.mcrt_bmode_volume_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(p), C.byref(sw), C.byref(grid), ptr(tgc), ptr(peak_dev),
                                               ptr(out_dev)))
 
+    def label_frames(self, pos=None, dirs=None, *, rule="traced", start_offset=None, e_begin=0, e_end=None, n_frames=None, tissue_dev=None,
+                     interface_dev=None, crossings_dev=None):
+        """mcrt_label_frames: the central beam of every scan-line walked through the scene.  pos / dirs None: the context's transducer (one
+        frame); else pose tables [F][E][3] as trace_frames_poses takes them (raw device pointers need n_frames).  Each output is a device pointer or None: tissue uint8
+        [F][ne][R], interface int32 [F][ne][R], crossings uint32 [F][ne]"""
+        e_end = self.params.n_elements if e_end is None else e_end
+        if isinstance(pos, np.ndarray):
+            pos = np.ascontiguousarray(pos, np.float32); dirs = np.ascontiguousarray(dirs, np.float32)
+        if n_frames is None:
+            if pos is not None and not hasattr(pos, "shape"):
+                raise ValueError("label_frames: n_frames is required with raw device pointers for pos / dirs")
+            n_frames = 1 if pos is None else pos.shape[0]
+            if pos is not None:
+                assert tuple(pos.shape) == (n_frames, self.params.n_elements, 3) and tuple(dirs.shape) == tuple(pos.shape)
+        o = label_opts_struct(rule, start_offset)
+        check(self.L.mcrt_label_frames(self.h, n_frames, e_begin, e_end, ptr(pos), ptr(dirs), C.byref(o), ptr(tissue_dev), ptr(interface_dev), ptr(crossings_dev)))
+
+    def label_scan_convert_frames(self, tissue_dev, n_frames, n_elements, n_rows, out_dev, radius_mm=30.0, total_angle=1.0471975511965976, out_rows=400, out_cols=500):
+        """mcrt_label_scan_convert_frames: tissue maps [n_frames][E][R] -> bytes [n_frames][out_rows][out_cols], nearest neighbour through
+        scan_convert_frames' own maps; LABEL_NONE outside the sector"""
+        check(self.L.mcrt_label_scan_convert_frames(self.h, ptr(tissue_dev), n_frames, n_elements, n_rows, radius_mm, total_angle, ptr(out_dev), out_rows, out_cols))
+
+    def label_volume_frames(self, tissue_dev, n_frames, n_elements, n_rows, sweep, grid, out_dev, radius_mm=30.0, total_angle=1.0471975511965976):
+        """mcrt_label_volume_frames: the tissue maps [n_frames][K][E][R] of a sweep -> bytes [n_frames][nw][nv][nu] at grid's points, nearest
+        neighbour through volume_frames' own maps; LABEL_NONE outside the sweep"""
+        sw = _as_sweep(sweep)
+        check(self.L.mcrt_label_volume_frames(self.h, ptr(tissue_dev), n_frames, n_elements, n_rows, radius_mm, total_angle, C.byref(sw), C.byref(grid), ptr(out_dev)))
+
     def export_rf(self, rf_dev, n_elements, n_rows):
         out = np.empty((n_rows, n_elements), np.float32)
         check(self.L.mcrt_export_rf(self.h, ptr(rf_dev), n_elements, n_rows, ptr(out)))
@@ -935,6 +980,60 @@ class Simulator:
             return self.ctx.d2h(out, shape, np.uint8)
         finally:
             self.ctx.free(out)
+
+    def _label_pass(self, rule, start_offset, want_rows=True):
+        """the label pass of this probe into fresh device buffers -> (F, tissue_dev, interface_dev, crossings_dev): the K planes of a sweep, else
+        the unsteered probe in its own plane, whatever compound= and elevation= are"""
+        F = self.sweep.n_planes if self.sweep is not None else 1
+        n = F * self.E * self.R
+        bufs = [self.ctx.alloc(n), self.ctx.alloc(4 * n) if want_rows else None, self.ctx.alloc(4 * F * self.E) if want_rows else None]
+        try:
+            pos, dirs = (self.sweep_pos, self.sweep_dir) if self.sweep is not None else (None, None)
+            self.ctx.label_frames(pos, dirs, rule=rule, start_offset=start_offset, tissue_dev=bufs[0], interface_dev=bufs[1], crossings_dev=bufs[2])
+        except Exception:
+            for b in bufs:
+                if b:
+                    self.ctx.free(b)
+            raise
+        return F, bufs
+
+    def labels(self, rule="traced", start_offset=None, picture=True, radius_mm=30.0, total_angle=1.0471975511965976, out_rows=400, out_cols=500):
+        """the ground truth of this probe's pictures -> dict(tissue uint8 [E][R], interface int32 [E][R], crossings uint32 [E], picture uint8
+        [out_rows][out_cols] or None): material index per scan-line sample, mesh id of the boundary in it (-1: none), boundaries per
+        scan-line (bit 31: LABEL_CAPPED), and the tissue map scan-converted like the B-mode picture (LABEL_NONE outside the sector).  It is
+        the unsteered probe's central beam per scan-line, whatever compound= is; with elevation= the probe's own plane.  With sweep= the
+        arrays gain a leading axis of the K planes and there is no sector picture: use label_volume()."""
+        F, bufs = self._label_pass(rule, start_offset)
+        lead = (F,) if self.sweep is not None else ()
+        pic_dev = None
+        try:
+            out = dict(tissue=self.ctx.d2h(bufs[0], lead + (self.E, self.R), np.uint8), interface=self.ctx.d2h(bufs[1], lead + (self.E, self.R), np.int32),
+                       crossings=self.ctx.d2h(bufs[2], lead + (self.E,), np.uint32), picture=None)
+            if picture and self.sweep is None:
+                pic_dev = self.ctx.alloc(out_rows * out_cols)
+                self.ctx.label_scan_convert_frames(bufs[0], 1, self.E, self.R, pic_dev, radius_mm=radius_mm, total_angle=total_angle, out_rows=out_rows, out_cols=out_cols)
+                out["picture"] = self.ctx.d2h(pic_dev, (out_rows, out_cols), np.uint8)
+            return out
+        finally:
+            for b in bufs + [pic_dev]:
+                if b:
+                    self.ctx.free(b)
+
+    def label_volume(self, grid, rule="traced", start_offset=None, radius_mm=30.0, total_angle=1.0471975511965976):
+        """the tissue of every point of grid, uint8 [nw][nv][nu]: the labels of volume() / bmode_volume() (sweep= only; LABEL_NONE outside the sweep)"""
+        if self.sweep is None:
+            raise RuntimeError("label_volume() needs Simulator(sweep=...)")
+        F, bufs = self._label_pass(rule, start_offset, want_rows=False)
+        shape = (grid.nw, grid.nv, grid.nu)
+        out = None
+        try:
+            out = self.ctx.alloc(shape[0] * shape[1] * shape[2])
+            self.ctx.label_volume_frames(bufs[0], 1, self.E, self.R, self.sweep, grid, out, radius_mm=radius_mm, total_angle=total_angle)
+            return self.ctx.d2h(out, shape, np.uint8)
+        finally:
+            for b in bufs + [out]:
+                if b:
+                    self.ctx.free(b)
 
     def bmode(self, frame_id=0, **display):
         """trace -> convolve -> envelope -> mcrt_bmode_frames -> host: the displayed 8-bit frame, uint8 [out_rows][out_cols].

@@ -176,7 +176,8 @@ struct mcrt_ctx {
     Scene scene;
     Buf<float2> d_tex; uint32_t tex_n = 0; bool tex_finite = false;
     Buf<float> d_pos, d_dir; uint32_t n_el = 0;          // the transducer
-    Staging pose_stage[2];                                // per-frame probe poses handed over as host memory: positions, directions (mcrt_trace_frames_poses)
+    Buf<int> label_ovf;                                   // traversal-stack overflow of k_label's walk (mcrt_label_frames)
+    Staging pose_stage[2];                                // per-frame probe poses handed over as host memory: positions, directions (mcrt_trace_frames_poses, mcrt_label_frames)
     Tables tab;
     Accumulators acc;
     ImageStages img;

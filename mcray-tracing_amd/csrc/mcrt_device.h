@@ -161,6 +161,17 @@ MCRT_DEV long long fix40(float echo)
     return (long long)__double_as_longlong(x) - (long long)__double_as_longlong(0x1.8p52);
 }
 
+// row = (int)(t / row_dt) if that quotient is < R, else -1 (rfimage.h:33-40), from the threshold table in memory (k_shade's folded bounce 0, k_label): k_march's row_of, which reads its LDS image
+MCRT_DEV int row_of_thr(double t, const double *thr, uint32_t R, double inv_dt, double thr_end)
+{
+    if (!(t < thr_end) || !(t >= 0.0)) return -1;
+    int r = (int)(t * inv_dt);                                   // within one row of the answer
+    r = r < 0 ? 0 : (r > (int)R - 1 ? (int)R - 1 : r);
+    while (t < thr[r]) r--;
+    while (t >= thr[r + 1]) r++;
+    return r;
+}
+
 struct Ray { f3 f2, to; };
 
 #define MCRT_KEY_MISS ((0x3f800000ull << 32) | 0xffffffffull)   // fraction 1.0, no triangle

@@ -388,6 +388,49 @@ extern "C" int mcrt_bmode_volume_frames(mcrt_ctx *c, const float *rf_dev, uint32
     return MCRT_OK;
 }
 
+// ---- labels as pictures (the contracts are in include/mcrt.h): nearest-neighbour gathers through the float calls' own cached maps ----
+static mcrt::LabelGatherArgs label_gather_args(const uint8_t *src, const float *plane, const float *col, const float *row, uint8_t *out, uint32_t n_frames, uint32_t E, uint32_t R,
+                                               uint32_t K, uint32_t n)
+{
+    mcrt::LabelGatherArgs a;
+    a.src = src; a.map_plane = plane; a.map_col = col; a.map_row = row; a.out = out; a.E = E; a.R = R; a.K = K; a.n = n; a.F = n_frames;
+    a.frames_per_chunk = display_frames_per_chunk(n_frames, n, 0.0f);
+    a.vec = n % 4u == 0u && (uintptr_t)out % 4u == 0u ? 1u : 0u;
+    return a;
+}
+
+extern "C" int mcrt_label_scan_convert_frames(mcrt_ctx *c, const uint8_t *tissue_dev, uint32_t n_frames, uint32_t E, uint32_t R, double radius_mm, double total_angle,
+                                              uint8_t *out_dev, uint32_t orows, uint32_t ocols)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_label_scan_convert_frames";
+    if (!tissue_dev || !out_dev || E == 0 || R == 0 || orows == 0 || ocols == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "%s: bad arguments", fn);
+    if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 images per call", fn);
+    if ((uint64_t)orows * ocols > 0x7ffffffcull) return set_error(MCRT_ERR_LIMIT, "%s: output image too large", fn);
+    const uint32_t n = orows * ocols;
+    if (ranges_overlap(tissue_dev, (size_t)n_frames * E * R, out_dev, (size_t)n_frames * n)) return set_error(MCRT_ERR_INVALID, "%s: tissue_dev and out_dev overlap", fn);
+    const float *maps = nullptr;
+    MCRT_TRY(ensure_maps(c, c->img.maps, E, R, radius_mm, total_angle, orows, ocols, nullptr, &maps));
+    HIP_TRY(mcrt::launch_label_gather(label_gather_args(tissue_dev, nullptr, maps, maps + MapCache::pad(n), out_dev, n_frames, E, R, 1u, n), c->stream));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_label_volume_frames(mcrt_ctx *c, const uint8_t *tissue_dev, uint32_t n_frames, uint32_t E, uint32_t R, double radius_mm, double total_angle,
+                                        const mcrt_sweep *sw, const mcrt_volume_grid *g, uint8_t *out_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_label_volume_frames";
+    if (!tissue_dev || !out_dev) return set_error(MCRT_ERR_INVALID, "%s: null %s", fn, tissue_dev ? "out_dev" : "tissue_dev");
+    MCRT_TRY(volume_args_check(fn, n_frames, E, R, total_angle, sw, g));
+    const uint32_t K = sw->n_planes, n = g->nu * g->nv * g->nw;
+    if (ranges_overlap(tissue_dev, (size_t)n_frames * K * E * R, out_dev, (size_t)n_frames * n)) return set_error(MCRT_ERR_INVALID, "%s: tissue_dev and out_dev overlap", fn);
+    const float *maps = nullptr;
+    MCRT_TRY(ensure_volume_maps(c, E, R, radius_mm, total_angle, sw, g, &maps));
+    const size_t n_pad = MapCache::pad(n);
+    HIP_TRY(mcrt::launch_label_gather(label_gather_args(tissue_dev, maps, maps + n_pad, maps + 2 * n_pad, out_dev, n_frames, E, R, K, n), c->stream));
+    return MCRT_OK;
+}
+
 extern "C" int mcrt_export_rf(mcrt_ctx *c, const float *rf_dev, uint32_t E, uint32_t R, float *host)
 {
     CTX_TRY(c);

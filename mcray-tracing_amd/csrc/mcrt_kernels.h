@@ -11,6 +11,7 @@
 //   mcrt_display.hip k_bmode_peak, k_bmode_grey, k_bmode (mcrt_bmode_frames: log-compressed 8-bit B-mode frames), k_compound (spatial compounding:
 //                    mcrt_compound_frames, mcrt_bmode_compound_frames)
 //   mcrt_volume.hip  k_volume (volume imaging: mcrt_volume_frames, mcrt_bmode_volume_frames)
+//   mcrt_label.hip   k_label (ground-truth label maps: mcrt_label_frames), k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames)
 //   mcrt_scene.hip   k_tris_by_id, k_expand_tris; the probes k_math_probe, k_verify_div, k_philox_probe
 //   mcrt_lbvh.hip    the device BVH builder (mcrt_lbvh.h)
 // Shared device code: mcrt_device.h (primitives and the knobs more than one unit reads), mcrt_walk.h (the lane walk's steps, also k_path's),
@@ -104,6 +105,27 @@ struct VolumeArgs {
     uint32_t vec;                       // 8-bit form: n % 4 == 0 and out is word-aligned, so a lane may store a word per frame
 };
 
+// k_label (mcrt_label_frames): beside these, a FrameArgs of which it reads the scene, the probe (el_pos, el_dir, pose_stride, e_begin, ne_frame,
+// ne = ne_frame * frames), the row table (row_thr, R, inv_row_dt, thr_end, max_travel, sos_d), start_mat, offs, the spacing, pad_abs, stack_ovf
+// (label_stack_entries() in LDS, the rest [..][label_blocks * 64]) and error_flag
+struct LabelArgs {
+    uint8_t *tissue;                    // [F][ne][R] or null
+    int32_t *interface;                 // [F][ne][R] or null
+    uint32_t *crossings;                // [F][ne] or null
+    uint32_t rule;                      // MCRT_LABEL_TRACED / MCRT_LABEL_GEOMETRIC
+    float Ls;                           // the beam's length factor: (float)(2.0 * depth_cm)
+};
+
+// k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames): the tissue maps [F][K][E][R] -> bytes [F][n] through the float
+// calls' own maps (map_plane null: one plane, K = 1)
+struct LabelGatherArgs {
+    const uint8_t *src;                 // [F][K][E][R]
+    const float *map_plane, *map_col, *map_row;   // [n_pad] each, n_pad = n rounded up to 256
+    uint8_t *out;                       // [F][n]
+    uint32_t E, R, K, n, F, frames_per_chunk;
+    uint32_t vec;                       // n % 4 == 0 and out is word-aligned, so a lane may store a word per frame
+};
+
 hipError_t launch_init(const FrameArgs &a, hipStream_t st);
 hipError_t launch_trace(const FrameArgs &a, uint32_t b, bool stats, hipStream_t st);
 hipError_t launch_nodes_walk(const float4 *nodes, uint32_t n_nodes, uint4 *out, hipStream_t st);
@@ -128,6 +150,10 @@ hipError_t launch_bmode_grey(const float *rf, uint32_t F, uint32_t E, uint32_t R
 hipError_t launch_bmode(const BmodeArgs &a, hipStream_t st);
 hipError_t launch_compound(const CompoundArgs &a, bool out8, hipStream_t st);   // a.mode: the instantiation
 hipError_t launch_volume(const VolumeArgs &a, bool out8, hipStream_t st);
+uint32_t label_blocks(size_t lines);                              // workgroups of a k_label launch over `lines` (frame, scan-line) beams (sizes the overflow stacks)
+uint32_t label_stack_entries();
+hipError_t launch_label(const FrameArgs &a, const LabelArgs &l, hipStream_t st);
+hipError_t launch_label_gather(const LabelGatherArgs &a, hipStream_t st);
 hipError_t launch_blocks_to_frames(const float *blocks, float *frames, uint32_t F, uint32_t E, uint32_t R, uint32_t G, const uint32_t *off /*[G+1]*/, hipStream_t st);   // at most 64 ranks
 hipError_t launch_transpose(const float *in, float *out, uint32_t E, uint32_t R, hipStream_t st);
 hipError_t launch_math_probe(int op, const double *x, const double *y, double *out, uint32_t n, hipStream_t st);

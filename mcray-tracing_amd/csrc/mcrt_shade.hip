@@ -62,17 +62,6 @@ __global__ void __launch_bounds__(256) k_init(FrameArgs a)
     if (pos < a.ne) a.key0[pos] = MCRT_KEY_MISS;          // bounce 0: one closest-hit word per queued (scan-line, frame)
 }
 
-// row = (int)(t / row_dt) if that quotient is < R, else -1 (rfimage.h:33-40), from the threshold table in memory: k_march's row_of, which reads its LDS image
-MCRT_DEV int row_of_thr(double t, const double *thr, uint32_t R, double inv_dt, double thr_end)
-{
-    if (!(t < thr_end) || !(t >= 0.0)) return -1;
-    int r = (int)(t * inv_dt);                                   // within one row of the answer
-    r = r < 0 ? 0 : (r > (int)R - 1 ? (int)R - 1 : r);
-    while (t < thr[r]) r--;
-    while (t >= thr[r + 1]) r++;
-    return r;
-}
-
 // ---- interface interaction of a bounce's live rays: one lane per ray ----
 // FOLD (launched for b == 0 only, FrameArgs::fold_b0): the start medium is silent, so all that bounce 0 adds to the image is every path's boundary
 // echo (main.cpp:139).  The workgroup -- 256 paths of ONE queued scan-line, S % 256 == 0 -- adds them into LDS bins exactly as k_march's rf_add

@@ -4,6 +4,7 @@
 #include "mcrt_kernels.h"
 
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstring>
 #include <vector>
 #include <algorithm>
@@ -344,6 +345,21 @@ extern "C" int mcrt_trace_frame(mcrt_ctx *c, uint32_t frame, uint32_t e0, uint32
     return mcrt_trace_frames(c, frame, 1, e0, e1, rf_dev);
 }
 
+// the pose tables of a pass on the device: a table in host memory is staged (see mcrt_trace_frames_poses), a device table is used as it is
+static int stage_poses(mcrt_ctx *c, uint32_t n_frames, const float *dev[2])
+{
+    const size_t len = 3 * (size_t)n_frames * c->p.n_elements;
+    for (int k = 0; k < 2; k++) {
+        if (is_device_pointer(dev[k])) continue;
+        float *h = nullptr;
+        MCRT_TRY(c->pose_stage[k].begin(len, c->stream, &h));
+        memcpy(h, dev[k], 4 * len);
+        MCRT_TRY(c->pose_stage[k].commit(len, c->stream));
+        dev[k] = c->pose_stage[k].dev;
+    }
+    return MCRT_OK;
+}
+
 // A pass whose frames each have their own probe pose (transducer.h:82-118 update() between the frames of main.cpp:92-152).  A table in
 // HOST memory belongs to the caller and may be pageable: it is staged in the context (Staging: copied into pinned memory before this call
 // returns, so that the caller may free or rewrite it at once, and to the device from there on the stream; the copy of the previous call
@@ -354,16 +370,8 @@ extern "C" int mcrt_trace_frames_poses(mcrt_ctx *c, uint32_t frame, uint32_t n_f
     CTX_TRY(c);
     if (!pos || !dir) return set_error(MCRT_ERR_INVALID, "mcrt_trace_frames_poses: null pose tables");
     if (n_frames == 0 || n_frames > 1024) return set_error(MCRT_ERR_LIMIT, "n_frames must be 1..1024");
-    const size_t len = 3 * (size_t)n_frames * c->p.n_elements;
     const float *dev[2] = { pos, dir };
-    for (int k = 0; k < 2; k++) {
-        if (is_device_pointer(dev[k])) continue;
-        float *h = nullptr;
-        MCRT_TRY(c->pose_stage[k].begin(len, c->stream, &h));
-        memcpy(h, dev[k], 4 * len);
-        MCRT_TRY(c->pose_stage[k].commit(len, c->stream));
-        dev[k] = c->pose_stage[k].dev;
-    }
+    MCRT_TRY(stage_poses(c, n_frames, dev));
     return trace_frames(c, frame, n_frames, e0, e1, dev[0], dev[1], rf_dev);
 }
 
@@ -408,4 +416,59 @@ extern "C" int mcrt_cast_rays(mcrt_ctx *c, uint32_t frame, uint32_t e0, uint32_t
     MCRT_TRY(check_ready(c, e0, e1));
     MCRT_TRY(run_pass(c, frame, 1, e0, e1, false, true, segs ? 2 : 1));
     return copy_out(c, e1 - e0, hits, segs, seg_count);
+}
+
+// ---- ground-truth label maps (the contract is in include/mcrt.h) ----
+extern "C" int mcrt_default_label_opts(mcrt_label_opts *o)
+{
+    if (!o) return set_error(MCRT_ERR_INVALID, "mcrt_default_label_opts: null options");
+    o->rule = MCRT_LABEL_TRACED; o->start_offset = -1.0f;
+    return MCRT_OK;
+}
+
+// Everything is checked before anything is staged or launched.  k_label walks with the lane walk's steps, so its traversal stack is sized
+// as the traced pass sizes its own: label_stack_entries() in LDS, the tree's worst case beyond that in the context's overflow array.
+extern "C" int mcrt_label_frames(mcrt_ctx *c, uint32_t n_frames, uint32_t e0, uint32_t e1, const float *pos, const float *dir, const mcrt_label_opts *o,
+                                 uint8_t *tissue_dev, int32_t *interface_dev, uint32_t *crossings_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_label_frames";
+    mcrt_label_opts d;
+    mcrt_default_label_opts(&d);
+    if (!o) o = &d;
+    if (!c->scene.have) return set_error(MCRT_ERR_INVALID, "%s: no scene uploaded", fn);
+    if ((pos == nullptr) != (dir == nullptr)) return set_error(MCRT_ERR_INVALID, "%s: pos and dir go together (null %s)", fn, pos ? "dir" : "pos");
+    if (!pos) {
+        if (!c->d_pos) return set_error(MCRT_ERR_INVALID, "%s: no transducer set", fn);
+        if (c->n_el != c->p.n_elements) return set_error(MCRT_ERR_INVALID, "%s: transducer has %u elements but params say %u", fn, c->n_el, c->p.n_elements);
+        if (n_frames != 1) return set_error(MCRT_ERR_INVALID, "%s: the context's transducer is one pose: n_frames must be 1 (%u)", fn, n_frames);
+    }
+    if (e0 >= e1 || e1 > c->p.n_elements) return set_error(MCRT_ERR_INVALID, "%s: scan-line range [%u,%u) invalid for %u elements", fn, e0, e1, c->p.n_elements);
+    if (!tissue_dev && !interface_dev && !crossings_dev) return set_error(MCRT_ERR_INVALID, "%s: no output asked for", fn);
+    if (o->rule != MCRT_LABEL_TRACED && o->rule != MCRT_LABEL_GEOMETRIC) return set_error(MCRT_ERR_INVALID, "%s: unknown rule %u", fn, o->rule);
+    if (!std::isfinite(o->start_offset) || o->start_offset == 0.0f) return set_error(MCRT_ERR_INVALID, "%s: start_offset must be finite and not 0 (%g)", fn, (double)o->start_offset);
+    if (n_frames == 0) return set_error(MCRT_ERR_INVALID, "%s: n_frames must be 1..1024", fn);
+    if (n_frames > 1024) return set_error(MCRT_ERR_LIMIT, "%s: n_frames must be 1..1024 (%u)", fn, n_frames);
+    if (c->scene.n_mat > 254) return set_error(MCRT_ERR_LIMIT, "%s: at most 254 materials fit a tissue byte (%u)", fn, c->scene.n_mat);
+    const uint32_t lines = (e1 - e0) * n_frames, blocks = mcrt::label_blocks(lines), lds_part = mcrt::label_stack_entries();
+    const size_t ovf = c->scene.bvh4.max_stack > lds_part ? (size_t)(c->scene.bvh4.max_stack - lds_part) * blocks * 64 : 0;
+    if (ovf > c->label_ovf.cap) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(c->label_ovf.alloc(ovf)); }      // (as ensure_work: an earlier pass may run on a stream the context has left)
+    const float *dev[2] = { pos, dir };
+    if (pos) MCRT_TRY(stage_poses(c, n_frames, dev));
+    if (c->scene.update_pending && c->scene.update_stream != c->stream) HIP_TRY(hipStreamWaitEvent(c->stream, c->scene.ev_update, 0));   // a scene update issued on another stream
+    mcrt::FrameArgs a;
+    memset(&a, 0, sizeof a);
+    a.nodes_walk = c->scene.d_nodes_walk; a.tris = c->scene.d_tris; a.tris_id = c->scene.d_tris_id; a.meshes = c->scene.d_meshes; a.n_nodes = c->scene.bvh4.n_nodes;
+    a.n_mat = c->scene.n_mat; a.n_mesh = c->scene.n_mesh; a.start_mat = c->scene.start_mat; a.pad_abs = c->scene.bvh.pad_abs;
+    a.sx = c->scene.spacing[0]; a.sy = c->scene.spacing[1]; a.sz = c->scene.spacing[2];
+    a.el_pos = pos ? dev[0] : c->d_pos; a.el_dir = pos ? dev[1] : c->d_dir; a.pose_stride = pos ? c->p.n_elements : 0u;
+    a.e_begin = e0; a.ne_frame = e1 - e0; a.ne = lines;
+    a.row_thr = c->tab.d_row_thr; a.R = c->p.n_rows; a.thr_end = c->tab.thr_end; a.inv_row_dt = 1.0 / c->c.row_dt_us;
+    a.max_travel = c->c.max_travel_us; a.sos_d = (double)c->p.speed_of_sound;
+    a.offs = o->start_offset < 0.0f ? c->p.ray_start_offset : o->start_offset;
+    a.stack_ovf = c->label_ovf; a.error_flag = c->d_error;
+    mcrt::LabelArgs l;
+    l.tissue = tissue_dev; l.interface = interface_dev; l.crossings = crossings_dev; l.rule = o->rule; l.Ls = (float)(2.0 * c->p.depth_cm);
+    HIP_TRY(mcrt::launch_label(a, l, c->stream));
+    return MCRT_OK;
 }

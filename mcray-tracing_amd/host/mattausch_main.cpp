@@ -4,6 +4,7 @@
 //                   [--elevation K] [--elevation-pitch-um P] [--var-z V] [--compound N] [--compound-step-deg D]
 //                   [--compound-mode mean|max|median] [--compound-feather LINES] [--compound-weights w0,w1,...]
 //                   [--sweep K --sweep-step-deg D [--sweep-pivot-mm P] (--cplane-mm Y | --sagittal-mm X)]
+//                   [--labels FILE.pgm [--label-rule traced|geometric] [--label-offset X]]
 // --gpus N: the first N GPUs of the node, the frame's scan-lines sharded over them (mcrt_group_*: one tracing context and host thread per
 // GPU, the blocks gathered on GPU 0); --devices lists them explicitly, and may repeat one (two ranks sharing a GPU: the one-GPU test).
 // Same constants (main.cpp:23-37), same frame loop body; instead of blocking on imshow/waitKey every frame it
@@ -36,6 +37,13 @@
 // the y-z picture at lateral position X mm (400 columns along z centred on the probe's plane, 500 rows along y from the arc's apex down,
 // 0.25 mm apart).  rf.bin then holds plane K / 2.  --sweep needs one of the two cuts and --sweep-step-deg; it does not combine with
 // --compound or --elevation, and --persistence has no volume form.
+// --labels FILE.pgm writes the ground truth of the picture as a PGM of material indices (their order in the scene file; 255 outside the
+// sector or the sweep): the tissue under every pixel, from the central beam of every scan-line of the unsteered probe walked through the
+// scene (mcrt_label_frames) and scan-converted nearest neighbour (mcrt_label_scan_convert_frames) -- with --sweep the cut of --cplane-mm /
+// --sagittal-mm through the K planes' labels (mcrt_label_volume_frames).  --label-rule traced (the default) names the medium the tracer's
+// rays carry, its quirks included -- the map that explains the picture --, geometric the anatomy of closed, nested meshes; --label-offset X
+// restarts the beam X scene units behind every boundary (default: the tracer's 0.1; geometric wants a small one such as 1e-3, which does
+// not step over thin walls).  Both need --labels.
 #include "mcrt_host.hpp"
 #include <chrono>
 #include <cmath>
@@ -68,6 +76,8 @@ int main(int argc, char **argv)
     const char *compound_mode = nullptr, *compound_feather = nullptr, *compound_weights = nullptr;   // the options as given
     int sweep_planes = 0; double sweep_step_deg = 0.0, sweep_pivot_mm = 0.0, cut_mm = 0.0;   // sweep_planes 0: off
     bool sweep_given = false, sweep_step_given = false, cplane_given = false, sagittal_given = false;
+    const char *labels_file = nullptr, *label_rule = nullptr, *label_offset = nullptr;
+    mcrt_label_opts lopts; mcrt_default_label_opts(&lopts);
     {   // the options, taken out of the positional arguments
         int keep = 1;
         for (int i = 1; i < argc; i++) {
@@ -94,6 +104,9 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--sweep-pivot-mm") && i + 1 < argc) sweep_pivot_mm = std::atof(argv[++i]);
             else if (!std::strcmp(argv[i], "--cplane-mm") && i + 1 < argc) { cut_mm = std::atof(argv[++i]); cplane_given = true; }
             else if (!std::strcmp(argv[i], "--sagittal-mm") && i + 1 < argc) { cut_mm = std::atof(argv[++i]); sagittal_given = true; }
+            else if (!std::strcmp(argv[i], "--labels") && i + 1 < argc) labels_file = argv[++i];
+            else if (!std::strcmp(argv[i], "--label-rule") && i + 1 < argc) label_rule = argv[++i];
+            else if (!std::strcmp(argv[i], "--label-offset") && i + 1 < argc) label_offset = argv[++i];
             else if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) { devices.clear(); for (int d = 0; d < std::max(1, std::atoi(argv[i + 1])); d++) devices.push_back(d); i++; }
             else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {
                 devices.clear();
@@ -152,6 +165,16 @@ int main(int argc, char **argv)
             else { cut.origin_mm[0] = cut_mm; cut.origin_mm[1] = transducer_radius_cm * 10.0; cut.origin_mm[2] = -(400 - 1) * pitch / 2.0; cut.du_mm[2] = pitch; cut.dv_mm[1] = pitch; cut.nu = 400; cut.nv = 500; }
             cut.nw = 1;
         }
+        if (!labels_file && (label_rule || label_offset)) throw std::invalid_argument(std::string(label_rule ? "--label-rule" : "--label-offset") + " needs --labels");
+        if (label_rule) {
+            if (!std::strcmp(label_rule, "traced")) lopts.rule = MCRT_LABEL_TRACED;
+            else if (!std::strcmp(label_rule, "geometric")) lopts.rule = MCRT_LABEL_GEOMETRIC;
+            else throw std::invalid_argument("--label-rule takes traced or geometric");
+        }
+        if (label_offset) {
+            lopts.start_offset = (float)std::atof(label_offset);
+            if (!(std::isfinite(lopts.start_offset) && lopts.start_offset > 0.0f)) throw std::invalid_argument("--label-offset takes a finite offset > 0");
+        }
         std::vector<unsigned char> cut_bytes;         // the last frame's cut, as the PGM holds it
         const mcrt_compound_opts *opts = compound_mode || compound_feather || compound_weights ? &copts : nullptr;
         std::vector<float> steers;                    // centred on the unsteered view, ascending
@@ -204,6 +227,13 @@ int main(int argc, char **argv)
             f.write((const char *)cut_bytes.data(), (std::streamsize)cut_bytes.size());
         }
         else if (argc > 4) { if (bmode) rf_image.save_bmode(argv[4]); else rf_image.save(argv[4]); }
+        if (labels_file) {   // what is in that picture: the tissue under every pixel
+            rf_image.labels(transducer, &lopts);
+            const std::vector<unsigned char> lab = sweep_given ? rf_image.label_volume(cut) : rf_image.label_picture();
+            std::ofstream f(labels_file, std::ios::binary);
+            f << "P5\n" << (sweep_given ? cut.nu : 500u) << " " << (sweep_given ? cut.nv : 400u) << "\n255\n";
+            f.write((const char *)lab.data(), (std::streamsize)lab.size());
+        }
         if (argc > 5) {   // the last frame's RF image after main.cpp:146-147, row-major [465][512] float32 (for the parity test)
             const auto img = sweep_given ? rf_image.view_intensities((uint32_t)sweep_planes / 2u)
                              : compound_given ? rf_image.view_intensities((uint32_t)(compound - 1) / 2u) : rf_image.intensities();

@@ -651,6 +651,7 @@ public:
         if (planes_dev) mcrt_free(dev->ctx, planes_dev);
         if (views_dev) mcrt_free(dev->ctx, views_dev);
         if (volume_dev) mcrt_free(dev->ctx, volume_dev);
+        if (label_dev) mcrt_free(dev->ctx, label_dev);
     }
     rf_image(const rf_image &) = delete; rf_image &operator=(const rf_image &) = delete;
 
@@ -808,6 +809,70 @@ public:
         check(mcrt_memcpy_d2h(dev->ctx, h.data(), volume_dev, n), "mcrt_memcpy_d2h");
         return h;
     }
+    // ground-truth label maps (mcrt.h: mcrt_label_frames): the central beam of every scan-line of t walked through the scene -- of the K planes of
+    // the sweep when the last trace was trace(frame, transducer, sweep), else of t's own plane, whatever was traced before (the unsteered probe
+    // of a compounded frame, the probe's own plane of an elevation pass).  opts: null = the tracer's rule at the tracer's start offset.  The
+    // maps stay on the device for label_picture() / label_volume(grid).  With several GPUs the pass runs on rank 0's context, which shares the
+    // root's GPU, and is waited for here.
+    struct label_maps {
+        uint32_t planes = 1;                     // the leading axis of the three tables: 1, or the sweep's K
+        std::vector<unsigned char> tissue;       // [planes][columns][max_rows]  material index per scan-line sample
+        std::vector<int32_t> interface;          // [planes][columns][max_rows]  mesh id of the boundary in a sample, -1: none
+        std::vector<uint32_t> crossings;         // [planes][columns]            boundaries per scan-line; bit 31: stopped at the cap
+    };
+    template <size_t N> label_maps labels(const transducer<N> &t, const mcrt_label_opts *opts = nullptr)
+    {
+        static_assert(N == columns, "one scan-line per transducer element");
+        const bool swept = sweep.n_planes != 0 && n_views == sweep.n_planes;
+        const uint32_t K = swept ? sweep.n_planes : 1u;
+        mcrt_params prm; check(mcrt_get_params(dev->ctx, &prm), "mcrt_get_params");
+        if (prm.n_rows != max_rows || prm.n_elements != columns) {
+            prm.n_rows = max_rows; prm.n_elements = columns; prm.speed_of_sound = speed_of_sound;
+            check(dev->set_params(&prm), "mcrt_set_params");
+        }
+        const size_t lines = (size_t)K * columns, taps = lines * max_rows, need = taps + 4 * taps + 4 * lines;   // bytes: tissue, interface, crossings
+        if (need > label_cap) {
+            if (label_dev) { mcrt_free(dev->ctx, label_dev); label_dev = nullptr; label_cap = 0; }
+            check(mcrt_alloc(dev->ctx, need, &label_dev), "mcrt_alloc");
+            label_cap = need;
+        }
+        unsigned char *tissue_dev = (unsigned char *)label_dev + 4 * taps + 4 * lines;      // (the 32-bit tables first: aligned)
+        int32_t *interface_dev = (int32_t *)label_dev; uint32_t *crossings_dev = (uint32_t *)label_dev + taps;
+        std::vector<float> pos, dir;
+        if (swept) { auto tab = t.swept(sweep); pos = std::move(tab.pos); dir = std::move(tab.dir); }
+        else { pos = t.pos; dir = t.dir; }
+        mcrt_ctx *tracer = dev->tracer();
+        check(mcrt_label_frames(tracer, K, 0, columns, pos.data(), dir.data(), opts, tissue_dev, interface_dev, crossings_dev), "mcrt_label_frames");
+        check(mcrt_synchronize(tracer), "mcrt_synchronize");
+        label_maps m;
+        m.planes = K; m.tissue.resize(taps); m.interface.resize(taps); m.crossings.resize(lines);
+        check(mcrt_memcpy_d2h(dev->ctx, m.tissue.data(), tissue_dev, taps), "mcrt_memcpy_d2h");
+        check(mcrt_memcpy_d2h(dev->ctx, m.interface.data(), interface_dev, 4 * taps), "mcrt_memcpy_d2h");
+        check(mcrt_memcpy_d2h(dev->ctx, m.crossings.data(), crossings_dev, 4 * lines), "mcrt_memcpy_d2h");
+        label_planes = K; label_tissue_dev = tissue_dev;
+        return m;
+    }
+    // the tissue map of labels() scan-converted like the picture, nearest neighbour (mcrt_label_scan_convert_frames): bytes [400][500],
+    // MCRT_LABEL_NONE outside the sector.  The interface map has no picture: a one-row arc does not survive a nearest gather
+    std::vector<unsigned char> label_picture()
+    {
+        if (label_planes != 1 || (sweep.n_planes != 0 && n_views == sweep.n_planes)) throw std::invalid_argument("rf_image::label_picture: labels(transducer) of an unswept probe first");
+        const size_t n = volume_prepare_points(400 * 500, 1);
+        check(mcrt_label_scan_convert_frames(dev->ctx, label_tissue_dev, 1, columns, max_rows, radius_mm, angle, (uint8_t *)volume_dev, 400, 500), "mcrt_label_scan_convert_frames");
+        std::vector<unsigned char> h(n);
+        check(mcrt_memcpy_d2h(dev->ctx, h.data(), volume_dev, n), "mcrt_memcpy_d2h");
+        return h;
+    }
+    // the tissue maps of labels() over a sweep gathered at grid's points (mcrt_label_volume_frames): bytes [nw][nv][nu], the labels of volume(grid)
+    std::vector<unsigned char> label_volume(const mcrt_volume_grid &grid)
+    {
+        const size_t n = volume_prepare(grid, 1);
+        if (label_planes != sweep.n_planes) throw std::invalid_argument("rf_image::label_volume: labels(transducer) after trace(frame, transducer, sweep) first");
+        check(mcrt_label_volume_frames(dev->ctx, label_tissue_dev, 1, columns, max_rows, radius_mm, angle, &sweep, &grid, (uint8_t *)volume_dev), "mcrt_label_volume_frames");
+        std::vector<unsigned char> h(n);
+        check(mcrt_memcpy_d2h(dev->ctx, h.data(), volume_dev, n), "mcrt_memcpy_d2h");
+        return h;
+    }
     std::vector<unsigned char> bmode() const   // the last postprocess(bmode_params) frame, row-major [out_rows][out_cols]
     {
         std::vector<unsigned char> h(bmode_n);
@@ -896,6 +961,10 @@ private:
         if (sweep.n_planes == 0 || n_views != sweep.n_planes) throw std::invalid_argument("rf_image::volume: trace(frame, transducer, sweep) first");
         const size_t n = (size_t)grid.nu * grid.nv * grid.nw;
         if (n == 0 || n >= ((size_t)1 << 31)) throw std::invalid_argument("rf_image::volume: the grid needs 1 .. 2^31 - 1 points");
+        return volume_prepare_points(n, size);
+    }
+    size_t volume_prepare_points(size_t n, size_t size)
+    {
         if (n * size > volume_cap) {
             if (volume_dev) { mcrt_free(dev->ctx, volume_dev); volume_dev = nullptr; volume_cap = 0; }
             check(mcrt_alloc(dev->ctx, n * size, &volume_dev), "mcrt_alloc");
@@ -920,7 +989,9 @@ private:
     float *planes_dev = nullptr; size_t planes_n = 0;                 // trace(frame, transducer, psf): the plane stack [K][columns][max_rows], grown to the largest K
     float *views_dev = nullptr; size_t views_cap = 0; uint32_t n_views = 0;   // trace(frame, transducer, steer_rad): the views [N][columns][max_rows]; n_views > 0: compounded
     mcrt_sweep sweep{ 0, 0.0f, 0.0f };                                // trace(frame, transducer, sweep): n_planes > 0: the stack holds a sweep's planes (n_views == n_planes)
-    void *volume_dev = nullptr; size_t volume_cap = 0;                // volume(): the gathered points, floats or bytes
+    void *volume_dev = nullptr; size_t volume_cap = 0;                // volume(), label_picture(), label_volume(): the gathered points, floats or bytes
+    void *label_dev = nullptr; size_t label_cap = 0;                  // labels(): interface, crossings and tissue tables, one allocation (grown, never shrunk)
+    unsigned char *label_tissue_dev = nullptr; uint32_t label_planes = 0;   // ... its tissue table and leading axis; 0: no labels taken yet
 };
 
 }  // namespace mcrt_host
