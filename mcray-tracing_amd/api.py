@@ -5,12 +5,15 @@
   Simulator   <-> scene + rf_image + the frame loop body of main.cpp:102-148
   Context     <-> thin 1:1 wrapper of include/mcrt.h
 """
+import contextlib
 import ctypes as C
 import math
 import numpy as np
 
 from . import _lib
 from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+
+DEFAULT_ANGLE = 1.0471975511965976      # the sector of main.cpp:28: 60 degrees [rad]
 
 
 # ------------------------------------------------------------------ host-side pieces (no GPU)
@@ -93,11 +96,16 @@ def row_pitch_mm(frequency):
     return int(np.float32(res_f * np.float32(1000.0))) / 1000.0
 
 
-def host_transducer(n_elements, radius_cm, sep_mm, position, angles_deg):
+def _element_tables(fn, n_elements, radius_cm, sep_mm, position, angles_deg, *how):
+    """(pos, dir), each float32 [n_elements][3], of mcrt_transducer_elements or a kin of it that takes `how` after the angles"""
     pos = np.zeros((n_elements, 3), np.float32); d = np.zeros((n_elements, 3), np.float32)
     p = np.asarray(position, np.float32); a = np.asarray(angles_deg, np.float32)
-    check(load_library().mcrt_transducer_elements(n_elements, radius_cm, sep_mm, ptr(p), ptr(a), ptr(pos), ptr(d)))
+    check(getattr(load_library(), fn)(n_elements, radius_cm, sep_mm, ptr(p), ptr(a), *how, ptr(pos), ptr(d)))
     return pos, d
+
+
+def host_transducer(n_elements, radius_cm, sep_mm, position, angles_deg):
+    return _element_tables("mcrt_transducer_elements", n_elements, radius_cm, sep_mm, position, angles_deg)
 
 
 def host_elevation_axis(angles_deg):
@@ -125,29 +133,28 @@ def host_psf_elevation(var_z, pitch_um, n_rows, row_mm, focus_mm=(), focal_range
     return out
 
 
-def host_scan_maps(n_elements, n_rows, radius_mm=30.0, total_angle=1.0471975511965976, max_travel_us=100, speed_of_sound=1500, out_rows=400, out_cols=500):
+def host_scan_maps(n_elements, n_rows, radius_mm=30.0, total_angle=DEFAULT_ANGLE, max_travel_us=100, speed_of_sound=1500, out_rows=400, out_cols=500):
     """rf_image::create_mapping (rfimage.h:183-215) as the library evaluates it: (map_row, map_col), each [out_rows][out_cols]"""
+    return _sector_maps("mcrt_scan_maps", n_elements, n_rows, radius_mm, total_angle, max_travel_us, speed_of_sound, out_rows, out_cols)
+
+
+def _sector_maps(fn, n_elements, n_rows, radius_mm, total_angle, max_travel_us, speed_of_sound, out_rows, out_cols, *steer):
     mr = np.zeros((out_rows, out_cols), np.float32); mc = np.zeros((out_rows, out_cols), np.float32)
-    check(load_library().mcrt_scan_maps(n_elements, n_rows, radius_mm, total_angle, max_travel_us, speed_of_sound, out_rows, out_cols, ptr(mr), ptr(mc)))
+    check(getattr(load_library(), fn)(n_elements, n_rows, radius_mm, total_angle, max_travel_us, speed_of_sound, out_rows, out_cols, *steer, ptr(mr), ptr(mc)))
     return mr, mc
 
 
 def host_transducer_steered(n_elements, radius_cm, sep_mm, position, angles_deg, steer_rad):
     """mcrt_transducer_steered: mcrt_transducer_elements with every beam tilted in the image plane by steer_rad (the beams pivot on their
     elements; a positive steer tilts towards higher element numbers)"""
-    pos = np.zeros((n_elements, 3), np.float32); d = np.zeros((n_elements, 3), np.float32)
-    p = np.asarray(position, np.float32); a = np.asarray(angles_deg, np.float32)
-    check(load_library().mcrt_transducer_steered(n_elements, radius_cm, sep_mm, ptr(p), ptr(a), steer_rad, ptr(pos), ptr(d)))
-    return pos, d
+    return _element_tables("mcrt_transducer_steered", n_elements, radius_cm, sep_mm, position, angles_deg, steer_rad)
 
 
-def host_compound_maps(n_elements, n_rows, steer_rad, radius_mm=30.0, total_angle=1.0471975511965976, max_travel_us=100, speed_of_sound=1500, out_rows=400,
+def host_compound_maps(n_elements, n_rows, steer_rad, radius_mm=30.0, total_angle=DEFAULT_ANGLE, max_travel_us=100, speed_of_sound=1500, out_rows=400,
                        out_cols=500):
     """mcrt_compound_maps: the scan-conversion maps of a view steered by steer_rad, (map_row, map_col), each [out_rows][out_cols]; NaN where
     no beam of the view passes the pixel.  steer_rad == 0: host_scan_maps' maps bit for bit."""
-    mr = np.zeros((out_rows, out_cols), np.float32); mc = np.zeros((out_rows, out_cols), np.float32)
-    check(load_library().mcrt_compound_maps(n_elements, n_rows, radius_mm, total_angle, max_travel_us, speed_of_sound, out_rows, out_cols, steer_rad, ptr(mr), ptr(mc)))
-    return mr, mc
+    return _sector_maps("mcrt_compound_maps", n_elements, n_rows, radius_mm, total_angle, max_travel_us, speed_of_sound, out_rows, out_cols, steer_rad)
 
 
 def compound_struct(steer_rad):
@@ -184,7 +191,7 @@ def _compound_defaults(mode, view_weights, feather_lines):
     return mode in ("mean", 0) and view_weights is None and feather_lines == 0.0
 
 
-def host_compound_weights(n_elements, n_rows, steer_rad, view_weight=1.0, feather_lines=0.0, radius_mm=30.0, total_angle=1.0471975511965976,
+def host_compound_weights(n_elements, n_rows, steer_rad, view_weight=1.0, feather_lines=0.0, radius_mm=30.0, total_angle=DEFAULT_ANGLE,
                           max_travel_us=100, speed_of_sound=1500, out_rows=400, out_cols=500):
     """mcrt_compound_weights: what the view steered by steer_rad contributes with at every pixel, float32 [out_rows][out_cols] -- its weight
     times the lateral edge ramp where it covers the pixel, 0 elsewhere (the expression the kernel evaluates)"""
@@ -197,10 +204,7 @@ def host_compound_weights(n_elements, n_rows, steer_rad, view_weight=1.0, feathe
 def host_transducer_swept(n_elements, radius_cm, sep_mm, position, angles_deg, tilt_rad, pivot_mm=0.0):
     """mcrt_transducer_swept: mcrt_transducer_elements with the array tilted by tilt_rad about the line parallel to the lateral axis through
     (0, pivot_mm, 0) of the probe-local frame (tilt 0: the plain tables bit for bit)"""
-    pos = np.zeros((n_elements, 3), np.float32); d = np.zeros((n_elements, 3), np.float32)
-    p = np.asarray(position, np.float32); a = np.asarray(angles_deg, np.float32)
-    check(load_library().mcrt_transducer_swept(n_elements, radius_cm, sep_mm, ptr(p), ptr(a), tilt_rad, pivot_mm, ptr(pos), ptr(d)))
-    return pos, d
+    return _element_tables("mcrt_transducer_swept", n_elements, radius_cm, sep_mm, position, angles_deg, tilt_rad, pivot_mm)
 
 
 def sweep_struct(n_planes, step_rad, pivot_mm=0.0):
@@ -247,7 +251,7 @@ def sagittal_grid(x_mm, nu, nv, pitch_mm, y0_mm, z0_mm=None):
     return volume_grid((x_mm, y0_mm, z0), (0, 0, pitch_mm), (0, pitch_mm, 0), (0, 0, 0), nu, nv, 1)
 
 
-def host_volume_maps(n_elements, n_rows, sweep, grid, radius_mm=30.0, total_angle=1.0471975511965976, max_travel_us=100, speed_of_sound=1500):
+def host_volume_maps(n_elements, n_rows, sweep, grid, radius_mm=30.0, total_angle=DEFAULT_ANGLE, max_travel_us=100, speed_of_sound=1500):
     """mcrt_volume_maps: where in the stack [K][E][R] every point of grid lies, (map_plane, map_row, map_col), each [nw][nv][nu].
     sweep: an mcrt_sweep (sweep_struct) or (K, step_rad[, pivot_mm])"""
     sw = _as_sweep(sweep)
@@ -278,7 +282,7 @@ def label_opts_struct(rule="traced", start_offset=None):
 
 
 def bmode_params(mode="db", dynamic_range_db=60.0, gain_db=0.0, ref=None, persistence=0.0, reset_state=True, radius_mm=30.0,
-                 total_angle=1.0471975511965976, out_rows=400, out_cols=500):
+                 total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
     """mcrt_bmode_params from keywords (mode "db" / "ref_log", or the MCRT_BMODE_* number)"""
     p = BmodeParams()
     check(load_library().mcrt_default_bmode(C.byref(p)))
@@ -400,7 +404,52 @@ def _tgc_rows(tgc_db, n_rows):
     return tgc
 
 
-class Context:
+def _pose_tables(what, pos, dirs, n_frames, n_elements):
+    """(pos, dirs, n_frames) of pose tables [F][E][3] as the library takes them: numpy arrays made contiguous float32, CUDA torch tensors as they
+    are -- n_frames, unless given, is their leading axis and their shape is checked --, or raw device pointers, which need n_frames"""
+    if isinstance(pos, np.ndarray):
+        pos = np.ascontiguousarray(pos, np.float32); dirs = np.ascontiguousarray(dirs, np.float32)
+    if n_frames is None:
+        if not hasattr(pos, "shape"):
+            raise ValueError("%s: n_frames is required with raw device pointers for pos / dirs" % what)
+        n_frames = pos.shape[0]
+        assert tuple(pos.shape) == (n_frames, n_elements, 3) and tuple(dirs.shape) == tuple(pos.shape)
+    return pos, dirs, n_frames
+
+
+class _SceneCalls:
+    """the scene-level calls a Context and a Group share: mcrt_<name> on the one, mcrt_group_<name> on the other (PREFIX)"""
+
+    def _call(self, name, *args):
+        check(getattr(self.L, self.PREFIX + name)(self.h, *args))
+
+    def _assign_params(self, kw):
+        for k, v in kw.items():
+            if not hasattr(self.params, k):
+                raise AttributeError(k)
+            setattr(self.params, k, v)
+
+    def set_bvh_builder(self, builder):
+        """'sah' (host, default) or 'lbvh' (built on the GPU); applies to the next upload_scene / update_triangles"""
+        self._call("set_bvh_builder", {"sah": 0, "lbvh": 1}[builder] if isinstance(builder, str) else int(builder))
+
+    def upload_scene(self, sd):
+        meshes, n_mesh, sp = _scene_tables(sd)
+        self._call("upload_scene", ptr(sd.tri), ptr(sd.tri_mesh), sd.n_tri, C.cast(meshes, C.c_void_p), n_mesh, ptr(sd.materials), sd.materials.shape[0], sd.start_mat, ptr(sp))
+
+    def upload_texture(self, vox=None, n=256):
+        if vox is not None:
+            vox = np.ascontiguousarray(vox, np.float32)
+        self._call("upload_texture", ptr(vox), n)
+
+    def set_transducer(self, pos, d):
+        pos = np.ascontiguousarray(pos, np.float32); d = np.ascontiguousarray(d, np.float32)
+        self._call("set_transducer", ptr(pos), ptr(d), pos.shape[0])
+
+
+class Context(_SceneCalls):
+    PREFIX = "mcrt_"
+
     def __init__(self, device=0, _borrowed=None):
         self.L = load_library()
         self.owned = _borrowed is None
@@ -426,10 +475,7 @@ class Context:
             pass
 
     def set_params(self, **kw):
-        for k, v in kw.items():
-            if not hasattr(self.params, k):
-                raise AttributeError(k)
-            setattr(self.params, k, v)
+        self._assign_params(kw)
         check(self.L.mcrt_set_params(self.h, C.byref(self.params)))
 
     def set_stream(self, stream_ptr):
@@ -448,16 +494,6 @@ class Context:
         """test hook: mark the context as an abandoned launch would (mcrt_debug_set_error)"""
         check(self.L.mcrt_debug_set_error(self.h, int(bits)))
 
-    def upload_scene(self, sd):
-        meshes, n_mesh, sp = _scene_tables(sd)
-        check(self.L.mcrt_upload_scene(self.h, ptr(sd.tri), ptr(sd.tri_mesh), sd.n_tri, C.cast(meshes, C.c_void_p), n_mesh,
-                                       ptr(sd.materials), sd.materials.shape[0], sd.start_mat, ptr(sp)))
-
-    def set_bvh_builder(self, builder):
-        """'sah' (host, default) or 'lbvh' (built on the GPU); applies to the next upload_scene / update_triangles"""
-        kind = {"sah": 0, "lbvh": 1}[builder] if isinstance(builder, str) else int(builder)
-        check(self.L.mcrt_set_bvh_builder(self.h, kind))
-
     def update_triangles(self, tri):
         """new vertex positions [T,9] (numpy array, or a CUDA torch tensor) for the uploaded scene's triangles"""
         tri, n = _tri9(tri)
@@ -467,15 +503,6 @@ class Context:
         """new vertex positions [T,9] for the uploaded triangles, keeping the tree: boxes are refitted on the GPU"""
         tri, n = _tri9(tri)
         check(self.L.mcrt_refit_triangles(self.h, ptr(tri), n))
-
-    def upload_texture(self, vox=None, n=256):
-        if vox is not None:
-            vox = np.ascontiguousarray(vox, np.float32)
-        check(self.L.mcrt_upload_texture(self.h, ptr(vox), n))
-
-    def set_transducer(self, pos, d):
-        pos = np.ascontiguousarray(pos, np.float32); d = np.ascontiguousarray(d, np.float32)
-        check(self.L.mcrt_set_transducer(self.h, ptr(pos), ptr(d), pos.shape[0]))
 
     def get_bvh(self):
         b = Bvh()
@@ -498,6 +525,15 @@ class Context:
 
     def free(self, dev):
         check(self.L.mcrt_free(self.h, C.c_void_p(dev)))
+
+    @contextlib.contextmanager
+    def temp(self, nbytes):
+        """`with ctx.temp(nbytes) as p:` -- device memory for the block, freed when it ends or raises"""
+        p = self.alloc(nbytes)
+        try:
+            yield p
+        finally:
+            self.free(p)
 
     def d2h(self, dev, shape, dtype=np.float32):
         out = np.empty(shape, dtype)
@@ -522,11 +558,7 @@ class Context:
         """a pass with a probe pose per frame: pos / dirs [F][E][3] (numpy arrays, CUDA torch tensors, or raw device pointers with
         n_frames given); rf_dev [F][e_end-e_begin][R]"""
         e_end = self.params.n_elements if e_end is None else e_end
-        if isinstance(pos, np.ndarray):
-            pos = np.ascontiguousarray(pos, np.float32); dirs = np.ascontiguousarray(dirs, np.float32)
-        if n_frames is None:
-            n_frames = pos.shape[0]
-            assert tuple(pos.shape) == (n_frames, self.params.n_elements, 3) and tuple(dirs.shape) == tuple(pos.shape)
+        pos, dirs, n_frames = _pose_tables("trace_frames_poses", pos, dirs, n_frames, self.params.n_elements)
         check(self.L.mcrt_trace_frames_poses(self.h, frame_id, n_frames, e_begin, e_end, ptr(pos), ptr(dirs), ptr(rf_dev)))
 
     def trace_frame_debug(self, frame_id, rf_dev, e_begin=0, e_end=None, want_hits=True, want_segs=False):
@@ -575,14 +607,14 @@ class Context:
     def envelope_frames(self, rf_dev, n_frames, n_elements, n_rows):
         check(self.L.mcrt_envelope_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows))
 
-    def scan_convert_frames(self, rf_dev, n_frames, n_elements, n_rows, out_dev, radius_mm=30.0, total_angle=1.0471975511965976, out_rows=400, out_cols=500):
+    def scan_convert_frames(self, rf_dev, n_frames, n_elements, n_rows, out_dev, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         check(self.L.mcrt_scan_convert_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, radius_mm, total_angle, ptr(out_dev), out_rows, out_cols))
 
-    def scan_convert(self, rf_dev, n_elements, n_rows, out_dev, radius_mm=30.0, total_angle=1.0471975511965976, out_rows=400, out_cols=500):
+    def scan_convert(self, rf_dev, n_elements, n_rows, out_dev, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         check(self.L.mcrt_scan_convert(self.h, ptr(rf_dev), n_elements, n_rows, radius_mm, total_angle, ptr(out_dev), out_rows, out_cols))
 
     def bmode_frames(self, rf_dev, n_frames, n_elements, n_rows, out_dev, *, mode="db", dynamic_range_db=60.0, gain_db=0.0, ref=None, tgc_db=None,
-                     persistence=0.0, state_dev=None, reset_state=True, peak_dev=None, radius_mm=30.0, total_angle=1.0471975511965976,
+                     persistence=0.0, state_dev=None, reset_state=True, peak_dev=None, radius_mm=30.0, total_angle=DEFAULT_ANGLE,
                      out_rows=400, out_cols=500):
         """mcrt_bmode_frames: [n_frames][E][R] device floats -> [n_frames][out_rows][out_cols] device bytes (log-compressed B-mode).
         mode "db" or "ref_log"; ref None (or <= 0): each frame's own peak; tgc_db: dB per RF row (n_rows values) or None."""
@@ -591,7 +623,7 @@ class Context:
         tgc = _tgc_rows(tgc_db, n_rows)
         check(self.L.mcrt_bmode_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(p), ptr(tgc), ptr(state_dev), ptr(peak_dev), ptr(out_dev)))
 
-    def compound_frames(self, rf_dev, n_frames, n_elements, n_rows, steer_rad, out_dev, radius_mm=30.0, total_angle=1.0471975511965976, out_rows=400, out_cols=500,
+    def compound_frames(self, rf_dev, n_frames, n_elements, n_rows, steer_rad, out_dev, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500,
                         mode="mean", view_weights=None, feather_lines=0.0):
         """mcrt_compound_frames: the views [n_frames][N][E][R] of steer_rad's N angles -> device floats [n_frames][out_rows][out_cols], every
         pixel the mean of the views that cover it.  mode "mean" / "max" / "median", view_weights and feather_lines (a lateral edge ramp in
@@ -606,7 +638,7 @@ class Context:
 
     def bmode_compound_frames(self, rf_dev, n_frames, n_elements, n_rows, steer_rad, out_dev, *, mode="db", dynamic_range_db=60.0, gain_db=0.0, ref=None,
                               tgc_db=None, persistence=0.0, state_dev=None, reset_state=True, peak_dev=None, radius_mm=30.0,
-                              total_angle=1.0471975511965976, out_rows=400, out_cols=500, compound_mode="mean", view_weights=None, feather_lines=0.0):
+                              total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500, compound_mode="mean", view_weights=None, feather_lines=0.0):
         """mcrt_bmode_compound_frames: bmode_frames over the views [n_frames][N][E][R] of steer_rad's N angles; the automatic reference of a
         frame is the peak over all its views.  compound_mode "mean" / "max" / "median" (mode is the grey curve's), view_weights and
         feather_lines go through mcrt_bmode_compound_frames_opts; with all three at their defaults the call is mcrt_bmode_compound_frames."""
@@ -622,14 +654,14 @@ class Context:
         check(self.L.mcrt_bmode_compound_frames_opts(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(p), C.byref(cp), ptr(tgc), ptr(state_dev),
                                                      ptr(peak_dev), ptr(out_dev), C.byref(o)))
 
-    def volume_frames(self, rf_dev, n_frames, n_elements, n_rows, sweep, grid, out_dev, radius_mm=30.0, total_angle=1.0471975511965976):
+    def volume_frames(self, rf_dev, n_frames, n_elements, n_rows, sweep, grid, out_dev, radius_mm=30.0, total_angle=DEFAULT_ANGLE):
         """mcrt_volume_frames: the planes [n_frames][K][E][R] of a sweep -> device floats [n_frames][nw][nv][nu] at grid's points.
         sweep: an mcrt_sweep (sweep_struct) or (K, step_rad[, pivot_mm])"""
         sw = _as_sweep(sweep)
         check(self.L.mcrt_volume_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, radius_mm, total_angle, C.byref(sw), C.byref(grid), ptr(out_dev)))
 
     def bmode_volume_frames(self, rf_dev, n_frames, n_elements, n_rows, sweep, grid, out_dev, *, mode="db", dynamic_range_db=60.0, gain_db=0.0, ref=None,
-                            tgc_db=None, persistence=0.0, peak_dev=None, radius_mm=30.0, total_angle=1.0471975511965976):
+                            tgc_db=None, persistence=0.0, peak_dev=None, radius_mm=30.0, total_angle=DEFAULT_ANGLE):
         """mcrt_bmode_volume_frames: bmode_frames over the planes [n_frames][K][E][R] of a sweep, bytes [n_frames][nw][nv][nu]; the automatic
         reference of a frame is the peak over its whole sweep.  persistence must stay 0 (the library refuses anything else)"""
         p = bmode_params(mode=mode, dynamic_range_db=dynamic_range_db, gain_db=gain_db, ref=ref, persistence=persistence, radius_mm=radius_mm,
@@ -645,23 +677,19 @@ class Context:
         frame); else pose tables [F][E][3] as trace_frames_poses takes them (raw device pointers need n_frames).  Each output is a device pointer or None: tissue uint8
         [F][ne][R], interface int32 [F][ne][R], crossings uint32 [F][ne]"""
         e_end = self.params.n_elements if e_end is None else e_end
-        if isinstance(pos, np.ndarray):
-            pos = np.ascontiguousarray(pos, np.float32); dirs = np.ascontiguousarray(dirs, np.float32)
-        if n_frames is None:
-            if pos is not None and not hasattr(pos, "shape"):
-                raise ValueError("label_frames: n_frames is required with raw device pointers for pos / dirs")
-            n_frames = 1 if pos is None else pos.shape[0]
-            if pos is not None:
-                assert tuple(pos.shape) == (n_frames, self.params.n_elements, 3) and tuple(dirs.shape) == tuple(pos.shape)
+        if pos is None:
+            n_frames = 1 if n_frames is None else n_frames
+        else:
+            pos, dirs, n_frames = _pose_tables("label_frames", pos, dirs, n_frames, self.params.n_elements)
         o = label_opts_struct(rule, start_offset)
         check(self.L.mcrt_label_frames(self.h, n_frames, e_begin, e_end, ptr(pos), ptr(dirs), C.byref(o), ptr(tissue_dev), ptr(interface_dev), ptr(crossings_dev)))
 
-    def label_scan_convert_frames(self, tissue_dev, n_frames, n_elements, n_rows, out_dev, radius_mm=30.0, total_angle=1.0471975511965976, out_rows=400, out_cols=500):
+    def label_scan_convert_frames(self, tissue_dev, n_frames, n_elements, n_rows, out_dev, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         """mcrt_label_scan_convert_frames: tissue maps [n_frames][E][R] -> bytes [n_frames][out_rows][out_cols], nearest neighbour through
         scan_convert_frames' own maps; LABEL_NONE outside the sector"""
         check(self.L.mcrt_label_scan_convert_frames(self.h, ptr(tissue_dev), n_frames, n_elements, n_rows, radius_mm, total_angle, ptr(out_dev), out_rows, out_cols))
 
-    def label_volume_frames(self, tissue_dev, n_frames, n_elements, n_rows, sweep, grid, out_dev, radius_mm=30.0, total_angle=1.0471975511965976):
+    def label_volume_frames(self, tissue_dev, n_frames, n_elements, n_rows, sweep, grid, out_dev, radius_mm=30.0, total_angle=DEFAULT_ANGLE):
         """mcrt_label_volume_frames: the tissue maps [n_frames][K][E][R] of a sweep -> bytes [n_frames][nw][nv][nu] at grid's points, nearest
         neighbour through volume_frames' own maps; LABEL_NONE outside the sweep"""
         sw = _as_sweep(sweep)
@@ -716,9 +744,10 @@ def shard_range(rank, n_ranks, n_elements):
     return int(b.value), int(e.value)
 
 
-class Group:
+class Group(_SceneCalls):
     """mcrt_group: one tracing context per listed device (a device may repeat), scan-lines cut into contiguous shards, the blocks
     gathered on devices[0].  `root` is the context that owns the gathered frames (post-processing, alloc, exports)."""
+    PREFIX = "mcrt_group_"
 
     def __init__(self, devices):
         self.L = load_library()
@@ -747,25 +776,13 @@ class Group:
             pass
 
     def set_params(self, **kw):
-        for k, v in kw.items():
-            if not hasattr(self.params, k):
-                raise AttributeError(k)
-            setattr(self.params, k, v)
+        self._assign_params(kw)
         try:
             check(self.L.mcrt_group_set_params(self.h, C.byref(self.params)))
         finally:       # (refused parameters leave every context on the old ones: read back what the group really holds)
             for c in [self.root] + self.members:
                 check(self.L.mcrt_get_params(c.h, C.byref(c.params)))
             check(self.L.mcrt_get_params(self.root.h, C.byref(self.params)))
-
-    def set_bvh_builder(self, builder):
-        kind = {"sah": 0, "lbvh": 1}[builder] if isinstance(builder, str) else int(builder)
-        check(self.L.mcrt_group_set_bvh_builder(self.h, kind))
-
-    def upload_scene(self, sd):
-        meshes, n_mesh, sp = _scene_tables(sd)
-        check(self.L.mcrt_group_upload_scene(self.h, ptr(sd.tri), ptr(sd.tri_mesh), sd.n_tri, C.cast(meshes, C.c_void_p), n_mesh,
-                                             ptr(sd.materials), sd.materials.shape[0], sd.start_mat, ptr(sp)))
 
     def update_triangles(self, tri):
         tri = np.ascontiguousarray(tri, np.float32).reshape(-1, 9)
@@ -774,15 +791,6 @@ class Group:
     def refit_triangles(self, tri):
         tri = np.ascontiguousarray(tri, np.float32).reshape(-1, 9)
         check(self.L.mcrt_group_refit_triangles(self.h, ptr(tri), tri.shape[0]))
-
-    def upload_texture(self, vox=None, n=256):
-        if vox is not None:
-            vox = np.ascontiguousarray(vox, np.float32)
-        check(self.L.mcrt_group_upload_texture(self.h, ptr(vox), n))
-
-    def set_transducer(self, pos, d):
-        pos = np.ascontiguousarray(pos, np.float32); d = np.ascontiguousarray(d, np.float32)
-        check(self.L.mcrt_group_set_transducer(self.h, ptr(pos), ptr(d), pos.shape[0]))
 
     def trace_frames(self, frame_id, n_frames, rf_dev):
         """rf_dev: [n_frames][E][R] on devices[0]; complete on the root context's stream"""
@@ -848,24 +856,28 @@ class Simulator:
         self.ctx.set_transducer(transducer.pos, transducer.dir)
         self.psf = psf or Psf(freq=transducer.frequency)
         self.rf_dev = self.ctx.alloc(E * self.R * 4)
-        self.elevation, self.planes_dev = bool(elevation), None
+        self.elevation, self.planes_dev, self.views_dev, self.sweep, self.sweep_dev = bool(elevation), None, None, None, None
         self.steers = tuple(float(x) for x in compound) if compound is not None else None
-        self.N, self.views_dev = (len(self.steers), None) if self.steers is not None else (1, None)
+        self.N = len(self.steers) if self.steers is not None else 1
         if compound_weights is not None and (self.steers is None or len(tuple(compound_weights)) != len(self.steers)):
             raise ValueError("compound_weights takes one weight per steering angle of compound=")
         if self.steers is None and not _compound_defaults(compound_mode, None, compound_feather):
             raise ValueError("compound_mode and compound_feather need compound=")
         self.compound_opts = dict(mode=compound_mode, view_weights=tuple(float(x) for x in compound_weights) if compound_weights is not None else None,
                                   feather_lines=float(compound_feather))
+        # decided here, once: the image stack (device buffer, images) that convolve(), envelope() and the pictures read, and the pose pass
+        # (pos, dirs, destination, images per frame) that trace() fills it with -- None: the context's own transducer, mcrt_trace_frame
+        self._stack, self._pass = (self.rf_dev, 1), None
         if self.steers is not None:
             self.view_pos, self.view_dir = transducer.steered(self.steers)
             self.views_dev = self.ctx.alloc(self.N * E * self.R * 4)
-        self.sweep, self.sweep_dev = None, None
+            self._stack, self._pass = (self.views_dev, self.N), (self.view_pos, self.view_dir, self.views_dev, self.N)
         if sweep is not None:
             self.sweep = sweep_struct(sweep[0], sweep[1], sweep_pivot_mm)
             self.sweep_pos, self.sweep_dir = transducer.swept(self.sweep.n_planes, self.sweep.step_rad, self.sweep.pivot_mm)
             self.sweep_dev = self.ctx.alloc(self.sweep.n_planes * E * self.R * 4)
-        if self.elevation:
+            self._stack, self._pass = (self.sweep_dev, self.sweep.n_planes), (self.sweep_pos, self.sweep_dir, self.sweep_dev, self.sweep.n_planes)
+        if self.elevation:                              # the pose pass goes to the plane stacks, which trace() folds into the image stack
             self.K = self.psf.elevation_size
             self.plane_pos, self.plane_dir, self.plane_z_mm = transducer.planes(self.K, self.psf.elevation_pitch_um)
             if self.steers is not None:                 # the views are outer: [N][K][E][3]
@@ -873,34 +885,23 @@ class Simulator:
                 tabs = [host_elevation_planes(self.view_pos[n], self.view_dir[n], axis, self.K, self.psf.elevation_pitch_um) for n in range(self.N)]
                 self.plane_pos = np.concatenate([t[0] for t in tabs]); self.plane_dir = np.concatenate([t[1] for t in tabs])
             self.planes_dev = self.ctx.alloc(self.N * self.K * E * self.R * 4)
+            self._pass = (self.plane_pos, self.plane_dir, self.planes_dev, self.N * self.K)
 
     def close(self):
         if self.ctx.h:
-            self.ctx.free(self.rf_dev)
-            if self.planes_dev:
-                self.ctx.free(self.planes_dev)
-            if self.views_dev:
-                self.ctx.free(self.views_dev)
-            if self.sweep_dev:
-                self.ctx.free(self.sweep_dev)
+            for d in (self.rf_dev, self.planes_dev, self.views_dev, self.sweep_dev):
+                if d:
+                    self.ctx.free(d)
             self.ctx.close()
 
     def trace(self, frame_id=0):
-        if self.sweep is not None:
-            self.ctx.trace_frames_poses(frame_id * self.sweep.n_planes, self.sweep_pos, self.sweep_dir, self.sweep_dev)
-            return
-        if self.steers is not None:
-            if not self.elevation:
-                self.ctx.trace_frames_poses(frame_id * self.N, self.view_pos, self.view_dir, self.views_dev)
-                return
-            self.ctx.trace_frames_poses(frame_id * self.N * self.K, self.plane_pos, self.plane_dir, self.planes_dev)
-            self.ctx.elevation_frames(self.planes_dev, self.N, self.K, self.E, self.R, self.psf.elevation_rows(self.R, self.row_mm), self.views_dev)
-            return
-        if not self.elevation:
+        if self._pass is None:
             self.ctx.trace_frame(frame_id, self.rf_dev)
             return
-        self.ctx.trace_frames_poses(frame_id * self.K, self.plane_pos, self.plane_dir, self.planes_dev)
-        self.ctx.elevation_frames(self.planes_dev, 1, self.K, self.E, self.R, self.psf.elevation_rows(self.R, self.row_mm), self.rf_dev)
+        pos, dirs, dest, per_frame = self._pass
+        self.ctx.trace_frames_poses(frame_id * per_frame, pos, dirs, dest)
+        if self.elevation:
+            self.ctx.elevation_frames(self.planes_dev, self._stack[1], self.K, self.E, self.R, self.psf.elevation_rows(self.R, self.row_mm), self._stack[0])
 
     @property
     def row_mm(self):
@@ -908,132 +909,90 @@ class Simulator:
         return row_pitch_mm(self.ctx.params.frequency)
 
     def convolve(self):
-        if self.sweep is not None:                      # the K planes as K frames
-            if self.psf.has_focus:
-                self.ctx.convolve_frames_depth(self.sweep_dev, self.sweep.n_planes, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_rows(self.R, self.row_mm))
-            else:
-                self.ctx.convolve_frames(self.sweep_dev, self.sweep.n_planes, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_kernel)
-        elif self.steers is not None:                   # the N views as N frames
-            if self.psf.has_focus:
-                self.ctx.convolve_frames_depth(self.views_dev, self.N, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_rows(self.R, self.row_mm))
-            else:
-                self.ctx.convolve_frames(self.views_dev, self.N, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_kernel)
-        elif self.psf.has_focus:
-            self.ctx.convolve_frames_depth(self.rf_dev, 1, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_rows(self.R, self.row_mm))
+        """over the stack's images as so many frames (mcrt_convolve is mcrt_convolve_frames of one)"""
+        if self.psf.has_focus:
+            self.ctx.convolve_frames_depth(*self._stack, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_rows(self.R, self.row_mm))
         else:
-            self.ctx.convolve(self.rf_dev, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_kernel)
+            self.ctx.convolve_frames(*self._stack, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_kernel)
 
     def envelope(self):
-        if self.sweep is not None:
-            self.ctx.envelope_frames(self.sweep_dev, self.sweep.n_planes, self.E, self.R)
-        elif self.steers is not None:
-            self.ctx.envelope_frames(self.views_dev, self.N, self.E, self.R)
-        else:
-            self.ctx.envelope(self.rf_dev, self.E, self.R)
+        self.ctx.envelope_frames(*self._stack, self.E, self.R)
 
-    def compound_image(self, frame_id=0, convolve=True, envelope=True, radius_mm=30.0, total_angle=1.0471975511965976, out_rows=400, out_cols=500):
+    def _run(self, frame_id, convolve=True, envelope=True):
+        self.trace(frame_id)
+        if convolve:
+            self.convolve()
+        if envelope:
+            self.envelope()
+
+    def compound_image(self, frame_id=0, convolve=True, envelope=True, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         """trace -> convolve -> envelope -> mcrt_compound_frames -> host: the compounded float picture [out_rows][out_cols] (compound= only)"""
         if self.steers is None:
             raise RuntimeError("compound_image() needs Simulator(compound=...)")
-        self.trace(frame_id)
-        if convolve:
-            self.convolve()
-        if envelope:
-            self.envelope()
-        out = self.ctx.alloc(out_rows * out_cols * 4)
-        try:
+        self._run(frame_id, convolve, envelope)
+        with self.ctx.temp(out_rows * out_cols * 4) as out:
             self.ctx.compound_frames(self.views_dev, 1, self.E, self.R, self.steers, out, radius_mm=radius_mm, total_angle=total_angle, out_rows=out_rows,
                                      out_cols=out_cols, **self.compound_opts)
             return self.ctx.d2h(out, (out_rows, out_cols), np.float32)
-        finally:
-            self.ctx.free(out)
 
-    def volume(self, frame_id, grid, convolve=True, envelope=True, radius_mm=30.0, total_angle=1.0471975511965976):
+    def volume(self, frame_id, grid, convolve=True, envelope=True, radius_mm=30.0, total_angle=DEFAULT_ANGLE):
         """trace -> convolve -> envelope -> mcrt_volume_frames -> host: the float voxels [nw][nv][nu] of grid, a volume or any cut (sweep= only)"""
         if self.sweep is None:
             raise RuntimeError("volume() needs Simulator(sweep=...)")
-        self.trace(frame_id)
-        if convolve:
-            self.convolve()
-        if envelope:
-            self.envelope()
+        self._run(frame_id, convolve, envelope)
         shape = (grid.nw, grid.nv, grid.nu)
-        out = self.ctx.alloc(shape[0] * shape[1] * shape[2] * 4)
-        try:
+        with self.ctx.temp(shape[0] * shape[1] * shape[2] * 4) as out:
             self.ctx.volume_frames(self.sweep_dev, 1, self.E, self.R, self.sweep, grid, out, radius_mm=radius_mm, total_angle=total_angle)
             return self.ctx.d2h(out, shape, np.float32)
-        finally:
-            self.ctx.free(out)
 
     def bmode_volume(self, frame_id, grid, **display):
         """trace -> convolve -> envelope -> mcrt_bmode_volume_frames -> host: the displayed 8-bit voxels, uint8 [nw][nv][nu] (sweep= only).
         display: the keywords of Context.bmode_volume_frames (mode, dynamic_range_db, gain_db, ref, tgc_db, radius_mm, total_angle)"""
         if self.sweep is None:
             raise RuntimeError("bmode_volume() needs Simulator(sweep=...)")
-        self.trace(frame_id)
-        self.convolve()
-        self.envelope()
+        self._run(frame_id)
         shape = (grid.nw, grid.nv, grid.nu)
-        out = self.ctx.alloc(shape[0] * shape[1] * shape[2])
-        try:
+        with self.ctx.temp(shape[0] * shape[1] * shape[2]) as out:
             self.ctx.bmode_volume_frames(self.sweep_dev, 1, self.E, self.R, self.sweep, grid, out, **display)
             return self.ctx.d2h(out, shape, np.uint8)
-        finally:
-            self.ctx.free(out)
 
+    @contextlib.contextmanager
     def _label_pass(self, rule, start_offset, want_rows=True):
-        """the label pass of this probe into fresh device buffers -> (F, tissue_dev, interface_dev, crossings_dev): the K planes of a sweep, else
-        the unsteered probe in its own plane, whatever compound= and elevation= are"""
+        """the label pass of this probe into device buffers that live as long as the block -> (F, [tissue_dev, interface_dev, crossings_dev]): the K
+        planes of a sweep, else the unsteered probe in its own plane, whatever compound= and elevation= are"""
         F = self.sweep.n_planes if self.sweep is not None else 1
         n = F * self.E * self.R
-        bufs = [self.ctx.alloc(n), self.ctx.alloc(4 * n) if want_rows else None, self.ctx.alloc(4 * F * self.E) if want_rows else None]
-        try:
+        with contextlib.ExitStack() as held:
+            sizes = (n, 4 * n, 4 * F * self.E) if want_rows else (n, 0, 0)
+            bufs = [held.enter_context(self.ctx.temp(size)) if size else None for size in sizes]
             pos, dirs = (self.sweep_pos, self.sweep_dir) if self.sweep is not None else (None, None)
             self.ctx.label_frames(pos, dirs, rule=rule, start_offset=start_offset, tissue_dev=bufs[0], interface_dev=bufs[1], crossings_dev=bufs[2])
-        except Exception:
-            for b in bufs:
-                if b:
-                    self.ctx.free(b)
-            raise
-        return F, bufs
+            yield F, bufs
 
-    def labels(self, rule="traced", start_offset=None, picture=True, radius_mm=30.0, total_angle=1.0471975511965976, out_rows=400, out_cols=500):
+    def labels(self, rule="traced", start_offset=None, picture=True, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         """the ground truth of this probe's pictures -> dict(tissue uint8 [E][R], interface int32 [E][R], crossings uint32 [E], picture uint8
         [out_rows][out_cols] or None): material index per scan-line sample, mesh id of the boundary in it (-1: none), boundaries per
         scan-line (bit 31: LABEL_CAPPED), and the tissue map scan-converted like the B-mode picture (LABEL_NONE outside the sector).  It is
         the unsteered probe's central beam per scan-line, whatever compound= is; with elevation= the probe's own plane.  With sweep= the
         arrays gain a leading axis of the K planes and there is no sector picture: use label_volume()."""
-        F, bufs = self._label_pass(rule, start_offset)
-        lead = (F,) if self.sweep is not None else ()
-        pic_dev = None
-        try:
+        with self._label_pass(rule, start_offset) as (F, bufs):
+            lead = (F,) if self.sweep is not None else ()
             out = dict(tissue=self.ctx.d2h(bufs[0], lead + (self.E, self.R), np.uint8), interface=self.ctx.d2h(bufs[1], lead + (self.E, self.R), np.int32),
                        crossings=self.ctx.d2h(bufs[2], lead + (self.E,), np.uint32), picture=None)
             if picture and self.sweep is None:
-                pic_dev = self.ctx.alloc(out_rows * out_cols)
-                self.ctx.label_scan_convert_frames(bufs[0], 1, self.E, self.R, pic_dev, radius_mm=radius_mm, total_angle=total_angle, out_rows=out_rows, out_cols=out_cols)
-                out["picture"] = self.ctx.d2h(pic_dev, (out_rows, out_cols), np.uint8)
+                with self.ctx.temp(out_rows * out_cols) as pic_dev:
+                    self.ctx.label_scan_convert_frames(bufs[0], 1, self.E, self.R, pic_dev, radius_mm=radius_mm, total_angle=total_angle, out_rows=out_rows, out_cols=out_cols)
+                    out["picture"] = self.ctx.d2h(pic_dev, (out_rows, out_cols), np.uint8)
             return out
-        finally:
-            for b in bufs + [pic_dev]:
-                if b:
-                    self.ctx.free(b)
 
-    def label_volume(self, grid, rule="traced", start_offset=None, radius_mm=30.0, total_angle=1.0471975511965976):
+    def label_volume(self, grid, rule="traced", start_offset=None, radius_mm=30.0, total_angle=DEFAULT_ANGLE):
         """the tissue of every point of grid, uint8 [nw][nv][nu]: the labels of volume() / bmode_volume() (sweep= only; LABEL_NONE outside the sweep)"""
         if self.sweep is None:
             raise RuntimeError("label_volume() needs Simulator(sweep=...)")
-        F, bufs = self._label_pass(rule, start_offset, want_rows=False)
         shape = (grid.nw, grid.nv, grid.nu)
-        out = None
-        try:
-            out = self.ctx.alloc(shape[0] * shape[1] * shape[2])
+        with self._label_pass(rule, start_offset, want_rows=False) as (F, bufs), self.ctx.temp(shape[0] * shape[1] * shape[2]) as out:
             self.ctx.label_volume_frames(bufs[0], 1, self.E, self.R, self.sweep, grid, out, radius_mm=radius_mm, total_angle=total_angle)
             return self.ctx.d2h(out, shape, np.uint8)
-        finally:
-            for b in bufs + [out]:
-                if b:
-                    self.ctx.free(b)
 
     def bmode(self, frame_id=0, **display):
         """trace -> convolve -> envelope -> mcrt_bmode_frames -> host: the displayed 8-bit frame, uint8 [out_rows][out_cols].
@@ -1041,11 +1000,8 @@ class Simulator:
         if self.sweep is not None:
             raise RuntimeError("a swept probe has K planes and meets only at a grid's points: use volume() or bmode_volume()")
         rows, cols = display.get("out_rows", 400), display.get("out_cols", 500)
-        self.trace(frame_id)
-        self.convolve()
-        self.envelope()
-        out = self.ctx.alloc(rows * cols)
-        try:
+        self._run(frame_id)
+        with self.ctx.temp(rows * cols) as out:
             if self.steers is not None:
                 o = self.compound_opts
                 self.ctx.bmode_compound_frames(self.views_dev, 1, self.E, self.R, self.steers, out, compound_mode=o["mode"], view_weights=o["view_weights"],
@@ -1053,15 +1009,11 @@ class Simulator:
             else:
                 self.ctx.bmode_frames(self.rf_dev, 1, self.E, self.R, out, **display)
             return self.ctx.d2h(out, (rows, cols), np.uint8)
-        finally:
-            self.ctx.free(out)
 
     def frame(self, frame_id=0, convolve=True):
         if self.sweep is not None:
             raise RuntimeError("a swept probe has K planes and meets only at a grid's points: use volume() or bmode_volume()")
         if self.steers is not None:
             raise RuntimeError("frame() returns one RF image; a compounded frame has N views and meets only as a picture: use compound_image() or bmode()")
-        self.trace(frame_id)
-        if convolve:
-            self.convolve()
+        self._run(frame_id, convolve, envelope=False)
         return self.ctx.export_rf(self.rf_dev, self.E, self.R)

@@ -49,6 +49,7 @@
 #include <cmath>
 #include <cstring>
 #include <iostream>
+#include <type_traits>
 
 using namespace mcrt_host;
 
@@ -60,6 +61,13 @@ constexpr unsigned int resolution = 145;                      // [um]
 using psf_ = psf<7, 13, 7, resolution>;
 using rf_image_ = rf_image<transducer_elements, 100, 322>;    // max_travel_time 100 us, axial resolution 322 um (main.cpp:31,36)
 using transducer_ = transducer<transducer_elements>;
+
+template <typename T> static std::vector<T> comma_list(const char *q)   // "a,b,...": atoi (an integer T) or atof of every item
+{
+    std::vector<T> v;
+    while (*q) { v.push_back(std::is_integral<T>::value ? (T)std::atoi(q) : (T)std::atof(q)); while (*q && *q != ',') q++; if (*q == ',') q++; }
+    return v;
+}
 
 int main(int argc, char **argv)
 {
@@ -85,11 +93,7 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--gain") && i + 1 < argc) { display.gain_db = (float)std::atof(argv[++i]); bmode = true; }
             else if (!std::strcmp(argv[i], "--ref-log")) { display.mode = MCRT_BMODE_REF_LOG; bmode = true; }
             else if (!std::strcmp(argv[i], "--persistence") && i + 1 < argc) { display.persistence = (float)std::atof(argv[++i]); bmode = true; }
-            else if (!std::strcmp(argv[i], "--focus-mm") && i + 1 < argc) {
-                focus_mm.clear();
-                for (const char *q = argv[i + 1]; *q;) { focus_mm.push_back((float)std::atof(q)); while (*q && *q != ',') q++; if (*q == ',') q++; }
-                i++;
-            }
+            else if (!std::strcmp(argv[i], "--focus-mm") && i + 1 < argc) focus_mm = comma_list<float>(argv[++i]);
             else if (!std::strcmp(argv[i], "--focal-range-mm") && i + 1 < argc) focal_range_mm = (float)std::atof(argv[++i]);
             else if (!std::strcmp(argv[i], "--elevation") && i + 1 < argc) { elevation = std::atoi(argv[++i]); elevation_given = true; }
             else if (!std::strcmp(argv[i], "--elevation-pitch-um") && i + 1 < argc) elevation_pitch_um = std::atol(argv[++i]);
@@ -109,10 +113,8 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--label-offset") && i + 1 < argc) label_offset = argv[++i];
             else if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) { devices.clear(); for (int d = 0; d < std::max(1, std::atoi(argv[i + 1])); d++) devices.push_back(d); i++; }
             else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {
-                devices.clear();
-                for (const char *q = argv[i + 1]; *q;) { devices.push_back(std::atoi(q)); while (*q && *q != ',') q++; if (*q == ',') q++; }
+                devices = comma_list<int>(argv[++i]);
                 if (devices.empty()) devices.push_back(0);
-                i++;
             }
             else argv[keep++] = argv[i];
         }
@@ -142,8 +144,7 @@ int main(int argc, char **argv)
             if (!(std::isfinite(copts.feather_lines) && copts.feather_lines >= 0.0f)) throw std::invalid_argument("--compound-feather takes a number of scan-lines >= 0");
         }
         if (compound_weights) {
-            std::vector<float> w;
-            for (const char *q = compound_weights; *q;) { w.push_back((float)std::atof(q)); while (*q && *q != ',') q++; if (*q == ',') q++; }
+            const std::vector<float> w = comma_list<float>(compound_weights);
             if ((int)w.size() != compound) throw std::invalid_argument("--compound-weights takes one weight per view of --compound (" + std::to_string(compound) + ")");
             for (size_t n = 0; n < w.size(); n++) copts.view_weight[n] = w[n];
         }
@@ -207,13 +208,8 @@ int main(int argc, char **argv)
             else rf_image.trace((uint32_t)f);      // clear + cast_rays + accumulation (main.cpp:102-144)
             rf_image.convolve(psf);           // main.cpp:146
             rf_image.envelope();              // main.cpp:147
-            if (sweep_given) {                // the cut through the swept volume
-                if (bmode) cut_bytes = rf_image.volume(display, cut);
-                else {
-                    cut_bytes.clear();
-                    for (float v : rf_image.volume(cut)) { float x = v * 255.0f; cut_bytes.push_back((unsigned char)(x != x || x < 0 ? 0 : x > 255 ? 255 : x)); }   // (as rf_image::save)
-                }
-            }
+            if (sweep_given)                  // the cut through the swept volume
+                cut_bytes = bmode ? rf_image.volume(display, cut) : to_bytes(rf_image.volume(cut));   // (as rf_image::save)
             else if (compound_given) { if (bmode) rf_image.postprocess(display, steers, nullptr, opts); else rf_image.postprocess(steers, opts); }   // the views averaged (or opts' mode)
             else if (bmode) rf_image.postprocess(display);   // main.cpp:148, log-compressed to 8-bit grey
             else rf_image.postprocess();      // main.cpp:148
@@ -221,18 +217,12 @@ int main(int argc, char **argv)
         check(dev->synchronize(), "mcrt_synchronize");
         const double dt = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
         std::cout << frames / dt << " frames/s, " << (double)frames * transducer_elements * samples / dt << " rays/s on " << devices.size() << " GPU context(s)" << std::endl;
-        if (argc > 4 && sweep_given) {
-            std::ofstream f(argv[4], std::ios::binary);
-            f << "P5\n" << cut.nu << " " << cut.nv << "\n255\n";
-            f.write((const char *)cut_bytes.data(), (std::streamsize)cut_bytes.size());
-        }
+        if (argc > 4 && sweep_given) write_pgm(argv[4], cut.nu, cut.nv, cut_bytes);
         else if (argc > 4) { if (bmode) rf_image.save_bmode(argv[4]); else rf_image.save(argv[4]); }
         if (labels_file) {   // what is in that picture: the tissue under every pixel
             rf_image.labels(transducer, &lopts);
-            const std::vector<unsigned char> lab = sweep_given ? rf_image.label_volume(cut) : rf_image.label_picture();
-            std::ofstream f(labels_file, std::ios::binary);
-            f << "P5\n" << (sweep_given ? cut.nu : 500u) << " " << (sweep_given ? cut.nv : 400u) << "\n255\n";
-            f.write((const char *)lab.data(), (std::streamsize)lab.size());
+            if (sweep_given) write_pgm(labels_file, cut.nu, cut.nv, rf_image.label_volume(cut));
+            else write_pgm(labels_file, 500, 400, rf_image.label_picture());
         }
         if (argc > 5) {   // the last frame's RF image after main.cpp:146-147, row-major [465][512] float32 (for the parity test)
             const auto img = sweep_given ? rf_image.view_intensities((uint32_t)sweep_planes / 2u)

@@ -625,6 +625,43 @@ private:
     }
 };
 
+// ---------------------------------------------------------------- what rf_image is made of
+// A device allocation of a context, freed with it.  Move-only; it keeps the context alive.
+class device_buffer {
+public:
+    explicit device_buffer(std::shared_ptr<device> dev_) : dev(std::move(dev_)) {}
+    device_buffer(device_buffer &&o) noexcept : dev(std::move(o.dev)), p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    ~device_buffer() { release(); }
+    void reserve(size_t bytes)   // room for `bytes`: grown, never shrunk
+    {
+        if (p && bytes <= cap) return;
+        release();
+        check(mcrt_alloc(dev->ctx, bytes, &p), "mcrt_alloc");
+        cap = bytes;
+    }
+    void release() { if (p) mcrt_free(dev->ctx, p); p = nullptr; cap = 0; }
+    template <typename T> T *as() const { return static_cast<T *>(p); }
+private:
+    std::shared_ptr<device> dev;
+    void *p = nullptr;
+    size_t cap = 0;
+};
+
+// a float picture as the 8-bit image of rfimage.h:142-148: times 255, clamped, NaN black
+inline std::vector<unsigned char> to_bytes(const std::vector<float> &img)
+{
+    std::vector<unsigned char> b;
+    b.reserve(img.size());
+    for (float v : img) { const float x = v * 255.0f; b.push_back((unsigned char)(x != x || x < 0 ? 0 : x > 255 ? 255 : x)); }
+    return b;
+}
+inline void write_pgm(const std::string &path, uint32_t cols, uint32_t rows, const std::vector<unsigned char> &bytes)   // binary PGM, the bytes as they are
+{
+    std::ofstream f(path, std::ios::binary);
+    f << "P5\n" << cols << " " << rows << "\n255\n";
+    f.write((const char *)bytes.data(), (std::streamsize)bytes.size());
+}
+
 // ---------------------------------------------------------------- rf_image (rfimage.h)
 // Two ways to fill it, both the reference's semantics:
 //   trace(frame)            clear + cast_rays + the accumulation loop of main.cpp:102-144 fused on the GPU (the fast path)
@@ -636,23 +673,14 @@ public:
     static constexpr unsigned int max_rows = (speed_of_sound * max_travel_time_us) / axial_resolution_um;   // rfimage.h:180
 
     rf_image(double radius_mm, double angle_rad, std::shared_ptr<device> dev_ = nullptr)
-        : dev(dev_ ? std::move(dev_) : default_device()), radius_mm(radius_mm), angle(angle_rad), host((size_t)columns * max_rows, 0.0f)
+        : dev(dev_ ? std::move(dev_) : default_device()), radius_mm(radius_mm), angle(angle_rad), host((size_t)columns * max_rows, 0.0f),
+          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), label(dev)
     {
         std::cout << "rf_image: " << max_rows << ", " << columns << std::endl;          // rfimage.h:30
-        check(mcrt_alloc(this->dev->ctx, sizeof(float) * columns * max_rows, (void **)&rf_dev), "mcrt_alloc");
-        check(mcrt_alloc(this->dev->ctx, sizeof(float) * 400 * 500, (void **)&scan_dev), "mcrt_alloc");
+        rf.reserve(sizeof(float) * columns * max_rows);
+        scan.reserve(sizeof(float) * 400 * 500);
     }
     rf_image(std::shared_ptr<device> dev_, double radius_mm, double angle_rad) : rf_image(radius_mm, angle_rad, std::move(dev_)) {}
-    ~rf_image()
-    {
-        mcrt_free(dev->ctx, rf_dev); mcrt_free(dev->ctx, scan_dev);
-        if (bmode_dev) mcrt_free(dev->ctx, bmode_dev);
-        if (state_dev) mcrt_free(dev->ctx, state_dev);
-        if (planes_dev) mcrt_free(dev->ctx, planes_dev);
-        if (views_dev) mcrt_free(dev->ctx, views_dev);
-        if (volume_dev) mcrt_free(dev->ctx, volume_dev);
-        if (label_dev) mcrt_free(dev->ctx, label_dev);
-    }
     rf_image(const rf_image &) = delete; rf_image &operator=(const rf_image &) = delete;
 
     // rfimage.h:33-40: row = micros / (axial_resolution / speed_of_sound), integer micrometres over um/us
@@ -675,13 +703,9 @@ public:
     // clear() + cast_rays + the accumulation loop of main.cpp:102-144 in one call, on the GPU
     void trace(uint32_t frame_id)
     {
-        mcrt_params p; check(mcrt_get_params(dev->ctx, &p), "mcrt_get_params");
-        if (p.n_rows != max_rows || p.n_elements != columns) {       // the image's shape is the kernel's: rows from THIS image's template arguments
-            p.n_rows = max_rows; p.n_elements = columns; p.speed_of_sound = speed_of_sound;
-            check(dev->set_params(&p), "mcrt_set_params");
-        }
-        check(dev->trace_frames(frame_id, 1, columns, rf_dev), "mcrt_trace_frame");       // (every GPU of a group traces its scan-line shard)
-        where = on_device; n_views = 0;
+        shape_params();
+        check(dev->trace_frames(frame_id, 1, columns, rf.as<float>()), "mcrt_trace_frame");       // (every GPU of a group traces its scan-line shard)
+        where = on_device; holds = stack_of::nothing; n_views = 0;
     }
     // the same with slice thickness (psf.h:16-18,42,77; mcrt.h): the frame's n_planes elevation planes (0: the psf's elevation_size), spread
     // p.elevation_pitch_um() apart around the transducer's own plane, traced as ONE pose pass -- plane k with frame id frame_id * K + k, the
@@ -692,21 +716,9 @@ public:
         const uint32_t K = n_planes ? n_planes : (uint32_t)p.get_elevation_size();
         const auto tables = t.planes(K, p.elevation_pitch_um());
         const std::vector<float> &w = p.elevation_rows(max_rows, (double)axial_resolution_um / 1000.0, K);
-        if ((uint64_t)frame_id * K + K > 0xffffffffull) throw std::out_of_range("rf_image::trace: frame_id * n_planes does not fit a frame id");
-        mcrt_params prm; check(mcrt_get_params(dev->ctx, &prm), "mcrt_get_params");
-        if (prm.n_rows != max_rows || prm.n_elements != columns) {
-            prm.n_rows = max_rows; prm.n_elements = columns; prm.speed_of_sound = speed_of_sound;
-            check(dev->set_params(&prm), "mcrt_set_params");
-        }
-        const size_t need = (size_t)K * columns * max_rows;
-        if (need > planes_n) {
-            if (planes_dev) { mcrt_free(dev->ctx, planes_dev); planes_dev = nullptr; planes_n = 0; }
-            check(mcrt_alloc(dev->ctx, sizeof(float) * need, (void **)&planes_dev), "mcrt_alloc");
-            planes_n = need;
-        }
-        check(dev->trace_frames_poses(frame_id * K, K, columns, tables.pos.data(), tables.dir.data(), planes_dev), "mcrt_trace_frames_poses");
-        check(mcrt_elevation_frames(dev->ctx, planes_dev, 1, K, columns, max_rows, w.data(), rf_dev), "mcrt_elevation_frames");
-        where = on_device; n_views = 0;
+        pose_pass(frame_id, K, tables, planes, "rf_image::trace: frame_id * n_planes does not fit a frame id");
+        check(mcrt_elevation_frames(dev->ctx, planes.as<float>(), 1, K, columns, max_rows, w.data(), rf.as<float>()), "mcrt_elevation_frames");
+        where = on_device; holds = stack_of::nothing; n_views = 0;
     }
     // spatial compounding (mcrt.h): the frame's views, one per steering angle [rad] of steer_rad (1..16), traced as ONE pose pass -- view n with
     // frame id frame_id * N + n, the frame-id rule of mcrt.h -- into a stack [N][columns][max_rows] this image owns.  convolve() and envelope()
@@ -717,11 +729,8 @@ public:
         static_assert(N == columns, "one scan-line per transducer element");
         const uint32_t V = (uint32_t)steer_rad.size();
         if (V == 0 || V > 16) throw std::invalid_argument("rf_image::trace: 1..16 steering angles");
-        const auto tables = t.steered(steer_rad);
-        if ((uint64_t)frame_id * V + V > 0xffffffffull) throw std::out_of_range("rf_image::trace: frame_id * views does not fit a frame id");
-        stack_prepare(V);
-        check(dev->trace_frames_poses(frame_id * V, V, columns, tables.pos.data(), tables.dir.data(), views_dev), "mcrt_trace_frames_poses");
-        n_views = V; sweep.n_planes = 0;
+        pose_pass(frame_id, V, t.steered(steer_rad), stack, "rf_image::trace: frame_id * views does not fit a frame id");
+        holds = stack_of::views; n_views = V;
     }
     // volume imaging (mcrt.h): the K planes of a probe swept in elevation, traced as ONE pose pass -- plane k with frame id frame_id * K + k, the
     // frame-id rule of mcrt.h -- into the stack [K][columns][max_rows] the views of a compounded frame use.  convolve() and envelope() then run
@@ -730,18 +739,14 @@ public:
     template <size_t N> void trace(uint32_t frame_id, const transducer<N> &t, const mcrt_sweep &sw)
     {
         static_assert(N == columns, "one scan-line per transducer element");
-        const uint32_t K = sw.n_planes;
-        if (K == 0 || K > 256) throw std::invalid_argument("rf_image::trace: a sweep has 1..256 planes");
-        const auto tables = t.swept(sw);
-        if ((uint64_t)frame_id * K + K > 0xffffffffull) throw std::out_of_range("rf_image::trace: frame_id * planes does not fit a frame id");
-        stack_prepare(K);
-        check(dev->trace_frames_poses(frame_id * K, K, columns, tables.pos.data(), tables.dir.data(), views_dev), "mcrt_trace_frames_poses");
-        n_views = K; sweep = sw;
+        if (sw.n_planes == 0 || sw.n_planes > 256) throw std::invalid_argument("rf_image::trace: a sweep has 1..256 planes");
+        pose_pass(frame_id, sw.n_planes, t.swept(sw), stack, "rf_image::trace: frame_id * planes does not fit a frame id");
+        holds = stack_of::sweep_planes; n_views = sw.n_planes; sweep = sw;
     }
     template <typename psf_> void convolve(const psf_ &p)
     {
-        float *img = rf_dev; uint32_t frames = 1;
-        if (n_views) { img = views_dev; frames = n_views; }     // the views of a compounded frame as so many frames
+        float *img = rf.as<float>(); uint32_t frames = 1;
+        if (n_views) { img = stack.as<float>(); frames = n_views; }     // the views of a compounded frame (the planes of a sweep) as so many frames
         else to_device();
         if (p.has_focus()) {   // focal zones: a lateral kernel per row, rows axial_resolution_um / 1000 mm apart
             const std::vector<float> &lat = p.lateral_rows(max_rows, (double)axial_resolution_um / 1000.0);
@@ -749,12 +754,12 @@ public:
             return;
         }
         if (n_views) check(mcrt_convolve_frames(dev->ctx, img, frames, columns, max_rows, p.axial_kernel.data(), (uint32_t)p.get_axial_size(), p.lateral_kernel.data(), (uint32_t)p.get_lateral_size()), "mcrt_convolve_frames");
-        else check(mcrt_convolve(dev->ctx, rf_dev, columns, max_rows, p.axial_kernel.data(), (uint32_t)p.get_axial_size(), p.lateral_kernel.data(), (uint32_t)p.get_lateral_size()), "mcrt_convolve");
+        else check(mcrt_convolve(dev->ctx, img, columns, max_rows, p.axial_kernel.data(), (uint32_t)p.get_axial_size(), p.lateral_kernel.data(), (uint32_t)p.get_lateral_size()), "mcrt_convolve");
     }
     void envelope()
     {
-        if (n_views) { check(mcrt_envelope_frames(dev->ctx, views_dev, n_views, columns, max_rows), "mcrt_envelope_frames"); return; }
-        to_device(); check(mcrt_envelope(dev->ctx, rf_dev, columns, max_rows), "mcrt_envelope");
+        if (n_views) { check(mcrt_envelope_frames(dev->ctx, stack.as<float>(), n_views, columns, max_rows), "mcrt_envelope_frames"); return; }
+        to_device(); check(mcrt_envelope(dev->ctx, rf.as<float>(), columns, max_rows), "mcrt_envelope");
     }
     // the views of trace(frame, transducer, steer_rad) compounded into the float picture scan_converted() / save() read (mcrt_compound_frames):
     // every pixel the mean of the views that cover it; with opts (mcrt_compound_opts: weights per view, a lateral edge ramp, max or median)
@@ -762,10 +767,10 @@ public:
     void postprocess(const std::vector<float> &steer_rad, const mcrt_compound_opts *opts = nullptr)
     {
         const mcrt_compound cp = compound_of(steer_rad);
-        if (opts) check(mcrt_compound_frames_opts(dev->ctx, views_dev, 1, columns, max_rows, radius_mm, angle, &cp, scan_dev, 400, 500, opts), "mcrt_compound_frames_opts");
-        else check(mcrt_compound_frames(dev->ctx, views_dev, 1, columns, max_rows, radius_mm, angle, &cp, scan_dev, 400, 500), "mcrt_compound_frames");
+        if (opts) check(mcrt_compound_frames_opts(dev->ctx, stack.as<float>(), 1, columns, max_rows, radius_mm, angle, &cp, scan.as<float>(), 400, 500, opts), "mcrt_compound_frames_opts");
+        else check(mcrt_compound_frames(dev->ctx, stack.as<float>(), 1, columns, max_rows, radius_mm, angle, &cp, scan.as<float>(), 400, 500), "mcrt_compound_frames");
     }
-    void postprocess() { to_device(); check(mcrt_scan_convert(dev->ctx, rf_dev, columns, max_rows, radius_mm, angle, scan_dev, 400, 500), "mcrt_scan_convert"); }
+    void postprocess() { to_device(); check(mcrt_scan_convert(dev->ctx, rf.as<float>(), columns, max_rows, radius_mm, angle, scan.as<float>(), 400, 500), "mcrt_scan_convert"); }
     // the displayed picture instead of the float scan conversion: log compression (dynamic range, gain, TGC) and 8-bit grey on the GPU
     // (mcrt_bmode_frames; rfimage.h:131-136 planned it).  tgc_db: max_rows dB values or nullptr.  The persistence state lives here and is
     // carried from one call to the next: it starts afresh on the first call and whenever bp.reset_state is set (mcrt_default_bmode sets it;
@@ -775,7 +780,7 @@ public:
     {
         to_device();
         const mcrt_bmode_params p = bmode_prepare(bp);
-        check(mcrt_bmode_frames(dev->ctx, rf_dev, 1, columns, max_rows, &p, tgc_db, state_dev, nullptr, bmode_dev), "mcrt_bmode_frames");
+        check(mcrt_bmode_frames(dev->ctx, rf.as<float>(), 1, columns, max_rows, &p, tgc_db, state.as<float>(), nullptr, bmode_buf.as<uint8_t>()), "mcrt_bmode_frames");
         state_valid = true; bmode_rows = bp.out_rows; bmode_cols = bp.out_cols;
     }
     // the same over the views of trace(frame, transducer, steer_rad) (mcrt_bmode_compound_frames): one reference per frame, the peak of all views
@@ -784,18 +789,17 @@ public:
     {
         const mcrt_compound cp = compound_of(steer_rad);
         const mcrt_bmode_params p = bmode_prepare(bp);
-        if (opts) check(mcrt_bmode_compound_frames_opts(dev->ctx, views_dev, 1, columns, max_rows, &p, &cp, tgc_db, state_dev, nullptr, bmode_dev, opts), "mcrt_bmode_compound_frames_opts");
-        else check(mcrt_bmode_compound_frames(dev->ctx, views_dev, 1, columns, max_rows, &p, &cp, tgc_db, state_dev, nullptr, bmode_dev), "mcrt_bmode_compound_frames");
+        float *views = stack.as<float>(), *st = state.as<float>(); uint8_t *out = bmode_buf.as<uint8_t>();
+        if (opts) check(mcrt_bmode_compound_frames_opts(dev->ctx, views, 1, columns, max_rows, &p, &cp, tgc_db, st, nullptr, out, opts), "mcrt_bmode_compound_frames_opts");
+        else check(mcrt_bmode_compound_frames(dev->ctx, views, 1, columns, max_rows, &p, &cp, tgc_db, st, nullptr, out), "mcrt_bmode_compound_frames");
         state_valid = true; bmode_rows = bp.out_rows; bmode_cols = bp.out_cols;
     }
     // the planes of trace(frame, transducer, sweep) gathered at grid's points (mcrt_volume_frames): floats [nw][nv][nu], a volume or any cut
     std::vector<float> volume(const mcrt_volume_grid &grid)
     {
         const size_t n = volume_prepare(grid, sizeof(float));
-        check(mcrt_volume_frames(dev->ctx, views_dev, 1, columns, max_rows, radius_mm, angle, &sweep, &grid, (float *)volume_dev), "mcrt_volume_frames");
-        std::vector<float> h(n);
-        check(mcrt_memcpy_d2h(dev->ctx, h.data(), volume_dev, n * sizeof(float)), "mcrt_memcpy_d2h");
-        return h;
+        check(mcrt_volume_frames(dev->ctx, stack.as<float>(), 1, columns, max_rows, radius_mm, angle, &sweep, &grid, points.as<float>()), "mcrt_volume_frames");
+        return download<float>(points, n);
     }
     // the same as the displayed 8-bit voxels (mcrt_bmode_volume_frames): one reference per volume, the peak of the whole sweep.  The sector is
     // this image's own; bp.out_rows / out_cols are not read (the picture is the grid's) and bp.persistence must be 0
@@ -804,10 +808,8 @@ public:
         const size_t n = volume_prepare(grid, 1);
         mcrt_bmode_params p = bp;
         p.radius_mm = radius_mm; p.total_angle_rad = angle;
-        check(mcrt_bmode_volume_frames(dev->ctx, views_dev, 1, columns, max_rows, &p, &sweep, &grid, tgc_db, nullptr, (uint8_t *)volume_dev), "mcrt_bmode_volume_frames");
-        std::vector<unsigned char> h(n);
-        check(mcrt_memcpy_d2h(dev->ctx, h.data(), volume_dev, n), "mcrt_memcpy_d2h");
-        return h;
+        check(mcrt_bmode_volume_frames(dev->ctx, stack.as<float>(), 1, columns, max_rows, &p, &sweep, &grid, tgc_db, nullptr, points.as<uint8_t>()), "mcrt_bmode_volume_frames");
+        return download<unsigned char>(points, n);
     }
     // ground-truth label maps (mcrt.h: mcrt_label_frames): the central beam of every scan-line of t walked through the scene -- of the K planes of
     // the sweep when the last trace was trace(frame, transducer, sweep), else of t's own plane, whatever was traced before (the unsteered probe
@@ -823,21 +825,13 @@ public:
     template <size_t N> label_maps labels(const transducer<N> &t, const mcrt_label_opts *opts = nullptr)
     {
         static_assert(N == columns, "one scan-line per transducer element");
-        const bool swept = sweep.n_planes != 0 && n_views == sweep.n_planes;
+        const bool swept = holds == stack_of::sweep_planes;
         const uint32_t K = swept ? sweep.n_planes : 1u;
-        mcrt_params prm; check(mcrt_get_params(dev->ctx, &prm), "mcrt_get_params");
-        if (prm.n_rows != max_rows || prm.n_elements != columns) {
-            prm.n_rows = max_rows; prm.n_elements = columns; prm.speed_of_sound = speed_of_sound;
-            check(dev->set_params(&prm), "mcrt_set_params");
-        }
-        const size_t lines = (size_t)K * columns, taps = lines * max_rows, need = taps + 4 * taps + 4 * lines;   // bytes: tissue, interface, crossings
-        if (need > label_cap) {
-            if (label_dev) { mcrt_free(dev->ctx, label_dev); label_dev = nullptr; label_cap = 0; }
-            check(mcrt_alloc(dev->ctx, need, &label_dev), "mcrt_alloc");
-            label_cap = need;
-        }
-        unsigned char *tissue_dev = (unsigned char *)label_dev + 4 * taps + 4 * lines;      // (the 32-bit tables first: aligned)
-        int32_t *interface_dev = (int32_t *)label_dev; uint32_t *crossings_dev = (uint32_t *)label_dev + taps;
+        shape_params();
+        const size_t lines = (size_t)K * columns, taps = lines * max_rows;
+        label.reserve(taps + 4 * taps + 4 * lines);      // bytes: tissue, interface, crossings
+        unsigned char *tissue_dev = label.as<unsigned char>() + 4 * taps + 4 * lines;      // (the 32-bit tables first: aligned)
+        int32_t *interface_dev = label.as<int32_t>(); uint32_t *crossings_dev = label.as<uint32_t>() + taps;
         std::vector<float> pos, dir;
         if (swept) { auto tab = t.swept(sweep); pos = std::move(tab.pos); dir = std::move(tab.dir); }
         else { pos = t.pos; dir = t.dir; }
@@ -845,94 +839,92 @@ public:
         check(mcrt_label_frames(tracer, K, 0, columns, pos.data(), dir.data(), opts, tissue_dev, interface_dev, crossings_dev), "mcrt_label_frames");
         check(mcrt_synchronize(tracer), "mcrt_synchronize");
         label_maps m;
-        m.planes = K; m.tissue.resize(taps); m.interface.resize(taps); m.crossings.resize(lines);
-        check(mcrt_memcpy_d2h(dev->ctx, m.tissue.data(), tissue_dev, taps), "mcrt_memcpy_d2h");
-        check(mcrt_memcpy_d2h(dev->ctx, m.interface.data(), interface_dev, 4 * taps), "mcrt_memcpy_d2h");
-        check(mcrt_memcpy_d2h(dev->ctx, m.crossings.data(), crossings_dev, 4 * lines), "mcrt_memcpy_d2h");
-        label_planes = K; label_tissue_dev = tissue_dev;
+        m.planes = K;
+        m.tissue = download<unsigned char>(tissue_dev, taps); m.interface = download<int32_t>(interface_dev, taps); m.crossings = download<uint32_t>(crossings_dev, lines);
+        labelled = K == 1 ? labels_of::one_plane : labels_of::sweep_planes; label_planes = K; label_tissue = tissue_dev;
         return m;
     }
     // the tissue map of labels() scan-converted like the picture, nearest neighbour (mcrt_label_scan_convert_frames): bytes [400][500],
     // MCRT_LABEL_NONE outside the sector.  The interface map has no picture: a one-row arc does not survive a nearest gather
     std::vector<unsigned char> label_picture()
     {
-        if (label_planes != 1 || (sweep.n_planes != 0 && n_views == sweep.n_planes)) throw std::invalid_argument("rf_image::label_picture: labels(transducer) of an unswept probe first");
-        const size_t n = volume_prepare_points(400 * 500, 1);
-        check(mcrt_label_scan_convert_frames(dev->ctx, label_tissue_dev, 1, columns, max_rows, radius_mm, angle, (uint8_t *)volume_dev, 400, 500), "mcrt_label_scan_convert_frames");
-        std::vector<unsigned char> h(n);
-        check(mcrt_memcpy_d2h(dev->ctx, h.data(), volume_dev, n), "mcrt_memcpy_d2h");
-        return h;
+        if (labelled != labels_of::one_plane || holds == stack_of::sweep_planes) throw std::invalid_argument("rf_image::label_picture: labels(transducer) of an unswept probe first");
+        points.reserve(400 * 500);
+        check(mcrt_label_scan_convert_frames(dev->ctx, label_tissue, 1, columns, max_rows, radius_mm, angle, points.as<uint8_t>(), 400, 500), "mcrt_label_scan_convert_frames");
+        return download<unsigned char>(points, 400 * 500);
     }
-    // the tissue maps of labels() over a sweep gathered at grid's points (mcrt_label_volume_frames): bytes [nw][nv][nu], the labels of volume(grid)
+    // the tissue maps of labels() over a sweep gathered at grid's points (mcrt_label_volume_frames): bytes [nw][nv][nu], the labels of volume(grid).
+    // Only the plane count is compared, so two stale tables pass (known, kept): the labels of a K-plane sweep after a re-trace with the same K
+    // and another step, and the labels of the unswept probe under a 1-plane sweep.
     std::vector<unsigned char> label_volume(const mcrt_volume_grid &grid)
     {
         const size_t n = volume_prepare(grid, 1);
         if (label_planes != sweep.n_planes) throw std::invalid_argument("rf_image::label_volume: labels(transducer) after trace(frame, transducer, sweep) first");
-        check(mcrt_label_volume_frames(dev->ctx, label_tissue_dev, 1, columns, max_rows, radius_mm, angle, &sweep, &grid, (uint8_t *)volume_dev), "mcrt_label_volume_frames");
-        std::vector<unsigned char> h(n);
-        check(mcrt_memcpy_d2h(dev->ctx, h.data(), volume_dev, n), "mcrt_memcpy_d2h");
-        return h;
+        check(mcrt_label_volume_frames(dev->ctx, label_tissue, 1, columns, max_rows, radius_mm, angle, &sweep, &grid, points.as<uint8_t>()), "mcrt_label_volume_frames");
+        return download<unsigned char>(points, n);
     }
-    std::vector<unsigned char> bmode() const   // the last postprocess(bmode_params) frame, row-major [out_rows][out_cols]
-    {
-        std::vector<unsigned char> h(bmode_n);
-        if (bmode_n) check(mcrt_memcpy_d2h(dev->ctx, h.data(), bmode_dev, h.size()), "mcrt_memcpy_d2h");
-        return h;
-    }
-    void save_bmode(const std::string &filename) const   // that frame as a binary PGM, the bytes as they are
-    {
-        const auto img = bmode();
-        std::ofstream f(filename, std::ios::binary);
-        f << "P5\n" << bmode_cols << " " << bmode_rows << "\n255\n";
-        f.write((const char *)img.data(), (std::streamsize)img.size());
-    }
+    std::vector<unsigned char> bmode() const { return download<unsigned char>(bmode_buf, bmode_n); }   // the last postprocess(bmode_params) frame, row-major [out_rows][out_cols]
+    void save_bmode(const std::string &filename) const { write_pgm(filename, bmode_cols, bmode_rows, bmode()); }   // that frame as a binary PGM, the bytes as they are
     void show() const {}   // rfimage.h:150-158 opens an OpenCV window and blocks on a key: out of scope
     std::vector<float> intensities() const   // row-major [max_rows][columns], the cv::Mat of rfimage.h:217
     {
-        if (where == on_host) return host;
-        std::vector<float> h((size_t)columns * max_rows);
-        check(mcrt_export_rf(dev->ctx, rf_dev, columns, max_rows, h.data()), "mcrt_export_rf");
-        return h;
+        return where == on_host ? host : export_rf(rf.as<float>());
     }
     std::vector<float> view_intensities(uint32_t n) const   // view n of the last compounded trace, row-major [max_rows][columns]
     {
         if (n >= n_views) throw std::out_of_range("rf_image::view_intensities");
-        std::vector<float> h((size_t)columns * max_rows);
-        check(mcrt_export_rf(dev->ctx, views_dev + (size_t)n * columns * max_rows, columns, max_rows, h.data()), "mcrt_export_rf");
-        return h;
+        return export_rf(stack.as<float>() + (size_t)n * columns * max_rows);
     }
-    std::vector<float> scan_converted() const
-    {
-        std::vector<float> h(400 * 500);
-        check(mcrt_memcpy_d2h(dev->ctx, h.data(), scan_dev, h.size() * 4), "mcrt_memcpy_d2h");
-        return h;
-    }
-    void save(const std::string &filename) const   // rfimage.h:142-148 writes an 8-bit image; here: binary PGM
-    {
-        const auto img = scan_converted();
-        std::ofstream f(filename, std::ios::binary);
-        f << "P5\n500 400\n255\n";
-        for (float v : img) { float x = v * 255.0f; unsigned char c = (unsigned char)(x != x || x < 0 ? 0 : x > 255 ? 255 : x); f.put((char)c); }
-    }
+    std::vector<float> scan_converted() const { return download<float>(scan, 400 * 500); }
+    void save(const std::string &filename) const { write_pgm(filename, 500, 400, to_bytes(scan_converted())); }   // rfimage.h:142-148 writes an 8-bit image; here: binary PGM
     std::shared_ptr<device> dev;
 private:
     void to_device()
     {
-        if (where == on_host) { check(mcrt_import_rf(dev->ctx, host.data(), columns, max_rows, rf_dev), "mcrt_import_rf"); where = on_device; }
+        if (where == on_host) { check(mcrt_import_rf(dev->ctx, host.data(), columns, max_rows, rf.as<float>()), "mcrt_import_rf"); where = on_device; }
     }
     void to_host()
     {
-        if (where == on_device) { check(mcrt_export_rf(dev->ctx, rf_dev, columns, max_rows, host.data()), "mcrt_export_rf"); where = on_host; }
+        if (where == on_device) { host = export_rf(rf.as<float>()); where = on_host; }
     }
-    // the buffers of postprocess(bmode_params ...) for bp's size, and bp with this image's sector and the reset rule applied
+    std::vector<float> export_rf(const float *img) const   // one device image [columns][max_rows] as the host's [max_rows][columns]
+    {
+        std::vector<float> h((size_t)columns * max_rows);
+        check(mcrt_export_rf(dev->ctx, img, columns, max_rows, h.data()), "mcrt_export_rf");
+        return h;
+    }
+    template <typename T> std::vector<T> download(const void *src, size_t n) const   // n elements of T from device memory
+    {
+        std::vector<T> h(n);
+        if (n) check(mcrt_memcpy_d2h(dev->ctx, h.data(), src, n * sizeof(T)), "mcrt_memcpy_d2h");
+        return h;
+    }
+    template <typename T> std::vector<T> download(const device_buffer &b, size_t n) const { return download<T>(b.as<const void>(), n); }
+    // this image's shape in the context's parameters: the image's shape is the kernel's, rows from THIS image's template arguments
+    void shape_params()
+    {
+        mcrt_params p; check(mcrt_get_params(dev->ctx, &p), "mcrt_get_params");
+        if (p.n_rows != max_rows || p.n_elements != columns) {
+            p.n_rows = max_rows; p.n_elements = columns; p.speed_of_sound = speed_of_sound;
+            check(dev->set_params(&p), "mcrt_set_params");
+        }
+    }
+    // one pose pass of n images into buf [n][columns][max_rows] (grown, never shrunk), image k with frame id frame_id * n + k
+    template <typename tables_> void pose_pass(uint32_t frame_id, uint32_t n, const tables_ &t, device_buffer &buf, const char *overflow)
+    {
+        if ((uint64_t)frame_id * n + n > 0xffffffffull) throw std::out_of_range(overflow);
+        shape_params();
+        buf.reserve(sizeof(float) * n * columns * max_rows);
+        check(dev->trace_frames_poses(frame_id * n, n, columns, t.pos.data(), t.dir.data(), buf.as<float>()), "mcrt_trace_frames_poses");
+    }
+    // the buffers of postprocess(bmode_params ...) for bp's size -- exactly that size: another size reallocates both and forgets the state --,
+    // and bp with this image's sector and the reset rule applied
     mcrt_bmode_params bmode_prepare(const mcrt_bmode_params &bp)
     {
         const size_t n = (size_t)bp.out_rows * bp.out_cols;
         if (n != bmode_n) {
-            if (bmode_dev) { mcrt_free(dev->ctx, bmode_dev); bmode_dev = nullptr; }
-            if (state_dev) { mcrt_free(dev->ctx, state_dev); state_dev = nullptr; }
-            check(mcrt_alloc(dev->ctx, n, (void **)&bmode_dev), "mcrt_alloc");
-            check(mcrt_alloc(dev->ctx, sizeof(float) * n, (void **)&state_dev), "mcrt_alloc");
+            bmode_buf.release(); state.release();
+            bmode_buf.reserve(n); state.reserve(sizeof(float) * n);
             bmode_n = n; state_valid = false;
         }
         mcrt_bmode_params p = bp;
@@ -940,41 +932,18 @@ private:
         p.reset_state = (bp.reset_state || !state_valid) ? 1u : 0u;
         return p;
     }
-    // before a pose pass of n images into views_dev: this image's shape in the context's parameters, and room for the stack (grown, never shrunk)
-    void stack_prepare(uint32_t n)
-    {
-        mcrt_params prm; check(mcrt_get_params(dev->ctx, &prm), "mcrt_get_params");
-        if (prm.n_rows != max_rows || prm.n_elements != columns) {
-            prm.n_rows = max_rows; prm.n_elements = columns; prm.speed_of_sound = speed_of_sound;
-            check(dev->set_params(&prm), "mcrt_set_params");
-        }
-        const size_t need = (size_t)n * columns * max_rows;
-        if (need > views_cap) {
-            if (views_dev) { mcrt_free(dev->ctx, views_dev); views_dev = nullptr; views_cap = 0; }
-            check(mcrt_alloc(dev->ctx, sizeof(float) * need, (void **)&views_dev), "mcrt_alloc");
-            views_cap = need;
-        }
-    }
-    // the device buffer of volume(): room for grid's points of `size` bytes each (grown, never shrunk); returns the number of points
+    // before volume() / label_volume(): the stack holds a sweep's planes, and `points` has room for grid's points of `size` bytes each; returns their number
     size_t volume_prepare(const mcrt_volume_grid &grid, size_t size)
     {
-        if (sweep.n_planes == 0 || n_views != sweep.n_planes) throw std::invalid_argument("rf_image::volume: trace(frame, transducer, sweep) first");
+        if (holds != stack_of::sweep_planes) throw std::invalid_argument("rf_image::volume: trace(frame, transducer, sweep) first");
         const size_t n = (size_t)grid.nu * grid.nv * grid.nw;
         if (n == 0 || n >= ((size_t)1 << 31)) throw std::invalid_argument("rf_image::volume: the grid needs 1 .. 2^31 - 1 points");
-        return volume_prepare_points(n, size);
-    }
-    size_t volume_prepare_points(size_t n, size_t size)
-    {
-        if (n * size > volume_cap) {
-            if (volume_dev) { mcrt_free(dev->ctx, volume_dev); volume_dev = nullptr; volume_cap = 0; }
-            check(mcrt_alloc(dev->ctx, n * size, &volume_dev), "mcrt_alloc");
-            volume_cap = n * size;
-        }
+        points.reserve(n * size);
         return n;
     }
     mcrt_compound compound_of(const std::vector<float> &steer_rad) const
     {
-        if (n_views == 0 || sweep.n_planes != 0 || steer_rad.size() != n_views) throw std::invalid_argument("rf_image::postprocess: the steer list is not the one the views were traced with");
+        if (holds != stack_of::views || steer_rad.size() != n_views) throw std::invalid_argument("rf_image::postprocess: the steer list is not the one the views were traced with");
         mcrt_compound cp{};
         cp.n_views = n_views;
         for (uint32_t n = 0; n < n_views; n++) cp.steer_rad[n] = steer_rad[n];
@@ -983,15 +952,18 @@ private:
     double radius_mm, angle;
     std::vector<float> host;                     // [max_rows][columns]
     enum { on_host, on_device } where = on_host;
-    float *rf_dev = nullptr, *scan_dev = nullptr;
-    unsigned char *bmode_dev = nullptr; float *state_dev = nullptr;   // postprocess(bmode_params): the 8-bit frame and the persistence state
+    device_buffer rf, scan;                      // the RF image [columns][max_rows] and the float picture [400][500]
+    device_buffer bmode_buf, state;              // postprocess(bmode_params): the 8-bit frame and the persistence state
     size_t bmode_n = 0; uint32_t bmode_rows = 0, bmode_cols = 0; bool state_valid = false;
-    float *planes_dev = nullptr; size_t planes_n = 0;                 // trace(frame, transducer, psf): the plane stack [K][columns][max_rows], grown to the largest K
-    float *views_dev = nullptr; size_t views_cap = 0; uint32_t n_views = 0;   // trace(frame, transducer, steer_rad): the views [N][columns][max_rows]; n_views > 0: compounded
-    mcrt_sweep sweep{ 0, 0.0f, 0.0f };                                // trace(frame, transducer, sweep): n_planes > 0: the stack holds a sweep's planes (n_views == n_planes)
-    void *volume_dev = nullptr; size_t volume_cap = 0;                // volume(), label_picture(), label_volume(): the gathered points, floats or bytes
-    void *label_dev = nullptr; size_t label_cap = 0;                  // labels(): interface, crossings and tissue tables, one allocation (grown, never shrunk)
-    unsigned char *label_tissue_dev = nullptr; uint32_t label_planes = 0;   // ... its tissue table and leading axis; 0: no labels taken yet
+    device_buffer planes;                        // trace(frame, transducer, psf): the plane stack [K][columns][max_rows]
+    device_buffer stack;                         // trace(frame, transducer, steer_rad | sweep): the images [n_views][columns][max_rows]
+    enum class stack_of { nothing, views, sweep_planes } holds = stack_of::nothing;   // ... what the last trace left in it
+    uint32_t n_views = 0;                        // ... and how many (nothing: 0)
+    mcrt_sweep sweep{ 0, 0.0f, 0.0f };           // ... the sweep of sweep_planes
+    device_buffer points;                        // volume(), label_picture(), label_volume(): the gathered points, floats or bytes
+    device_buffer label;                         // labels(): interface, crossings and tissue tables in one allocation
+    enum class labels_of { nothing, one_plane, sweep_planes } labelled = labels_of::nothing;   // ... what they hold (one_plane: a 1-plane sweep's too)
+    uint32_t label_planes = 0; const unsigned char *label_tissue = nullptr;   // ... their leading axis (nothing: 0) and the tissue table
 };
 
 }  // namespace mcrt_host
