@@ -44,7 +44,9 @@ extern "C" {
                                    + mcrt_sweep, mcrt_volume_grid, mcrt_transducer_swept, mcrt_volume_maps, mcrt_volume_frames, mcrt_bmode_volume_frames
                                    (volume imaging: a probe swept in elevation, 3-D scan conversion into voxels or any cut; additive);
                                    + mcrt_label_opts, mcrt_default_label_opts, mcrt_label_frames, mcrt_label_scan_convert_frames, mcrt_label_volume_frames
-                                   (ground-truth label maps: tissue and interface per scan-line sample, pixel and voxel; additive) */
+                                   (ground-truth label maps: tissue and interface per scan-line sample, pixel and voxel; additive);
+                                   + mcrt_render_view, mcrt_render_opts, mcrt_default_render_opts, mcrt_render_view_for_grid, mcrt_render_frames
+                                   (volume rendering: MIP, mean and surface views of a block of voxels seen from a direction; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -539,6 +541,84 @@ int mcrt_bmode_volume_frames(mcrt_ctx *ctx, const float *rf_dev /* [n_frames][K]
                              const mcrt_bmode_params *p, const mcrt_sweep *sweep, const mcrt_volume_grid *grid,
                              const float *tgc_db /* host [n_rows] or NULL */, float *peak_dev /* [n_frames] or NULL */,
                              uint8_t *out_dev /* [n_frames][nw][nv][nu] */);
+
+/* ---- volume rendering: the block of voxels seen from a direction -- the maximum-intensity view of a vessel tree, the mean ("X-ray") view,
+ * the surface picture of a fetal face.  The reference has one plane and draws none of this.  The input is a voxel block on the device,
+ * [n_frames][nw][nv][nu] with u fastest: exactly what mcrt_volume_frames (float) or mcrt_bmode_volume_frames (uint8) wrote.  The renderer works
+ * in the block's INDEX SPACE (u, v, w): a ray per pixel, orthographic, n_steps samples along it, each a trilinear blend of 8 voxels.  The
+ * kernel needs no geometry beyond the twelve floats of the view; mcrt_render_view_for_grid makes them from a direction in millimetres.
+ *
+ * Derived floats, computed on the host:
+ *   inv_range = (float)(1.0 / ((double)hi - (double)lo)),   inv_ramp = (float)(1.0 / (double)ramp),
+ *   inv_steps = n_steps > 1 ? (float)(1.0 / (double)(n_steps - 1)) : 0.0f
+ * The rule, per frame and pixel (i, j), i < nx, j < ny; everything in float, every operation rounded once, no fma:
+ *   m = 0, arg = -1;  sum = 0, cnt = 0;  C = 0, T = 1, depth = -1
+ *   for s = 0 .. n_steps-1:
+ *       p_c = ((origin_c + (float)i * di_c) + (float)j * dj_c) + (float)s * ds_c              c = u, v, w   (not a running sum)
+ *       f_c = floorf(p_c);  a_c = p_c - f_c
+ *       covered = no p_c is NaN  &&  -1 <= f_c < n_c for every c        (compared in float; at least one tap can lie inside)
+ *       if !covered: continue                                           (the step neither contributes nor counts, in every mode)
+ *       t[dw][dv][du] = the voxel at (f_u+du, f_v+dv, f_w+dw) where that index is inside the block, else 0.0f and not read;
+ *                       a uint8 voxel b is (float)b
+ *       c[dw][dv] = t[dw][dv][0] * (1 - a_u) + t[dw][dv][1] * a_u
+ *       e[dw]     = c[dw][0] * (1 - a_v) + c[dw][1] * a_v
+ *       v         = e[0] * (1 - a_w) + e[1] * a_w;      v = (v == v) ? v : 0.0f        (a NaN sample is no echo, as step 1 of mcrt_bmode_frames)
+ *       x = fminf(fmaxf((v - lo) * inv_range, 0), 1)
+ *       MIP      if x > m: m = x, arg = s
+ *       MEAN     sum = sum + x;  cnt++
+ *       SURFACE  a = fminf(fmaxf((x - threshold) * inv_ramp, 0), 1) * opacity
+ *                shade = 1.0f - depth_cue * ((float)s * inv_steps)
+ *                C = C + (T * a) * (x * shade);   T = T * (1.0f - a)
+ *                if depth < 0 && T <= 0.5f: depth = (float)s
+ *                if T < t_cut: break
+ *   out   = MIP: m      MEAN: cnt ? sum / (float)cnt : 0.0f      SURFACE: C
+ *   depth = MIP: (float)arg      MEAN: -1.0f      SURFACE: depth          (the step index of what is seen; -1: nothing)
+ *   out8  = (uint8_t)(fminf(fmaxf(out, 0), 1) * 255.0f + 0.5f)
+ * Every pixel of every requested output is written.  SURFACE is front-to-back compositing: a sample's opacity rises from 0 at x = threshold
+ * to `opacity` at x = threshold + ramp, its brightness falls with depth by depth_cue; the early stop (t_cut) is part of the contract because
+ * it is visible in the bits.  `depth` is what a caller needs to shade the surface from the depth buffer's gradient, or to ask a label block
+ * what tissue the surface belongs to.
+ * The defaults of threshold, ramp, opacity and depth_cue are display choices that no measurement backs (as focal_range_mm's 20 mm). */
+enum { MCRT_RENDER_MIP = 0, MCRT_RENDER_MEAN = 1, MCRT_RENDER_SURFACE = 2 };
+typedef struct { float origin[3], di[3], dj[3], ds[3];   /* index units; component order u, v, w; all finite */
+                 uint32_t nx, ny, n_steps, _pad;          /* the picture [ny][nx]; n_steps 1..4096 */
+} mcrt_render_view;                                       /* 64 bytes: origin 0, di 12, dj 24, ds 36, nx 48, ny 52, n_steps 56 */
+typedef struct { uint32_t mode;       /* MCRT_RENDER_*                                                       (SURFACE) */
+                 float lo, hi;        /* window: finite, hi > lo               (float input 0, 1; uint8 input 0, 255) */
+                 float threshold;     /* SURFACE: opacity starts at x = threshold, in [0,1)   (0.25) */
+                 float ramp;          /* SURFACE: width of the opacity ramp in x, in (0,1]    (0.25) */
+                 float opacity;       /* SURFACE: in (0,1]                                    (1)    */
+                 float depth_cue;     /* SURFACE: in [0,1]                                    (0.5)  */
+                 float t_cut;         /* SURFACE: in [0,1); 0 = never stop early              (0)    */
+} mcrt_render_opts;                   /* 32 bytes: mode 0, lo 4, hi 8, threshold 12, ramp 16, opacity 20, depth_cue 24, t_cut 28 */
+/* the defaults above (in_u8 != 0: the window of a uint8 block); host only.  MCRT_ERR_INVALID for a null o */
+int mcrt_default_render_opts(mcrt_render_opts *o, int in_u8);
+/* An orthographic camera in the probe-local mm frame of mcrt_volume_grid, looking along dir_mm at the block's centre; nx x ny pixels pixel_mm
+ * apart, samples step_mm apart along the whole of the block's longest diagonal.  Everything in double, the twelve floats rounded once at the end:
+ *   dn = dir/|dir|;   right = normalize(dn x up);   down = -(right x dn)          (picture rows run against `up`)
+ *   C  = the grid point at index ((nu-1)/2, (nv-1)/2, (nw-1)/2)
+ *   L  = half the longest of the block's four space diagonals |(nu-1) du +- (nv-1) dv +- (nw-1) dw|
+ *   n_steps = floor(2L / step_mm) + 1
+ *   P0 = C - L dn - (nx-1)/2 pixel_mm right - (ny-1)/2 pixel_mm down
+ *   origin = M^-1 (P0 - g->origin_mm),   di = M^-1 (pixel_mm right),   dj = M^-1 (pixel_mm down),   ds = M^-1 (step_mm dn)
+ *   M  = the matrix with the columns du, dv, dw
+ * Picture columns run along the viewer's right, dn x up: looking along +dw with up = dv in a right-handed grid that is -du, di = (-1, 0, 0);
+ * picture rows run against up.  The view is only a way to make the floats: a caller may fill mcrt_render_view by hand.  Host only.  MCRT_ERR_INVALID for null pointers, a
+ * zero nx, ny, nu, nv or nw, a grid entry that is not finite, a dir that is zero or not finite, an up that is not finite or parallel to dir,
+ * pixel_mm or step_mm not > 0 and finite, a grid whose three axes do not span space (a cut has dw = 0 and cannot be rendered);
+ * MCRT_ERR_LIMIT for n_steps > 4096.  On an error *out is untouched. */
+int mcrt_render_view_for_grid(const mcrt_volume_grid *g, const double dir_mm[3], const double up_mm[3], double pixel_mm, double step_mm,
+                              uint32_t nx, uint32_t ny, mcrt_render_view *out);
+/* The rule above over n_frames blocks: vol_dev is float (in_u8 == 0) or uint8 (in_u8 != 0) [n_frames][nw][nv][nu]; each output is a device
+ * pointer [n_frames][ny][nx] or NULL.  Asynchronous on the context's stream, one launch; uploads nothing and allocates nothing.
+ * MCRT_ERR_INVALID, the message naming the field: null ctx / vol_dev / view, all three outputs NULL, a zero n_frames, nu, nv, nw, nx or ny, a
+ * view entry that is not finite, an unknown mode, a window that is not finite or has hi <= lo, threshold, ramp, opacity, depth_cue or t_cut
+ * outside the ranges above, a window or a ramp so narrow that inv_range or inv_ramp is no finite float (a subnormal width), an output
+ * overlapping the block.  MCRT_ERR_LIMIT: n_steps outside 1..4096, nu, nv or nw >= 2^24, nu*nv*nw or
+ * nx*ny >= 2^31, n_frames > 65535.  On any error nothing is launched and nothing is written.  Groups: call it on mcrt_group_root(). */
+int mcrt_render_frames(mcrt_ctx *ctx, const void *vol_dev, int in_u8, uint32_t n_frames, uint32_t nu, uint32_t nv, uint32_t nw,
+                       const mcrt_render_view *view, const mcrt_render_opts *o /* NULL = defaults for in_u8 */,
+                       float *out_dev /* [F][ny][nx] or NULL */, uint8_t *out8_dev /* same or NULL */, float *depth_dev /* same or NULL */);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
  * Ground-truth label maps: what is in the picture.  The tracer knows the anatomy exactly; these calls hand it out aligned with every

@@ -84,13 +84,25 @@ class LabelOpts(C.Structure):
     _fields_ = [("rule", C.c_uint32), ("start_offset", C.c_float)]
 
 
+class RenderView(C.Structure):
+    """mcrt_render_view (include/mcrt.h): 64 bytes, di at 12, dj at 24, ds at 36, nx at 48"""
+    _fields_ = [("origin", C.c_float * 3), ("di", C.c_float * 3), ("dj", C.c_float * 3), ("ds", C.c_float * 3),
+                ("nx", C.c_uint32), ("ny", C.c_uint32), ("n_steps", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class RenderOpts(C.Structure):
+    """mcrt_render_opts (include/mcrt.h): 32 bytes"""
+    _fields_ = [("mode", C.c_uint32), ("lo", C.c_float), ("hi", C.c_float), ("threshold", C.c_float), ("ramp", C.c_float), ("opacity", C.c_float),
+                ("depth_cue", C.c_float), ("t_cut", C.c_float)]
+
+
 NODE_DTYPE = np.dtype([("lo0", "<f4", 3), ("c0", "<i4"), ("hi0", "<f4", 3), ("c1", "<i4"),
                        ("lo1", "<f4", 3), ("pad0", "<u4"), ("hi1", "<f4", 3), ("pad1", "<u4")])
 SEGMENT_DTYPE = np.dtype([("from", "<f4", 3), ("to", "<f4", 3), ("dir", "<f4", 3),
                           ("reflected_intensity", "<f4"), ("initial_intensity", "<f4"), ("attenuation", "<f4"),
                           ("distance_traveled", "<f8"), ("media", "<i4"), ("tri", "<i4")])
 assert NODE_DTYPE.itemsize == 64 and SEGMENT_DTYPE.itemsize == 64 and C.sizeof(BvhNode) == 64 and C.sizeof(BmodeParams) == 48 and C.sizeof(Focus) == 40 and C.sizeof(Compound) == 68 and C.sizeof(CompoundOpts) == 72
-assert C.sizeof(Sweep) == 12 and C.sizeof(VolumeGrid) == 112 and C.sizeof(LabelOpts) == 8
+assert C.sizeof(Sweep) == 12 and C.sizeof(VolumeGrid) == 112 and C.sizeof(LabelOpts) == 8 and C.sizeof(RenderView) == 64 and C.sizeof(RenderOpts) == 32
 
 # every symbol include/mcrt.h declares (tests/test_abi.py checks the .so exports each one)
 SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create", "mcrt_destroy", "mcrt_set_stream",
@@ -106,7 +118,8 @@ SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create"
            "mcrt_transducer_steered", "mcrt_compound_maps", "mcrt_compound_frames", "mcrt_bmode_compound_frames",
            "mcrt_default_compound_opts", "mcrt_compound_weights", "mcrt_compound_frames_opts", "mcrt_bmode_compound_frames_opts",
            "mcrt_transducer_swept", "mcrt_volume_maps", "mcrt_volume_frames", "mcrt_bmode_volume_frames",
-           "mcrt_default_label_opts", "mcrt_label_frames", "mcrt_label_scan_convert_frames", "mcrt_label_volume_frames"]
+           "mcrt_default_label_opts", "mcrt_label_frames", "mcrt_label_scan_convert_frames", "mcrt_label_volume_frames",
+           "mcrt_default_render_opts", "mcrt_render_view_for_grid", "mcrt_render_frames"]
 
 
 def build_library(force=False):
@@ -172,6 +185,9 @@ def load_library():
         "mcrt_label_frames": [vp, u32, u32, u32, vp, vp, C.POINTER(LabelOpts), vp, vp, vp],
         "mcrt_label_scan_convert_frames": [vp, vp, u32, u32, u32, C.c_double, C.c_double, vp, u32, u32],
         "mcrt_label_volume_frames": [vp, vp, u32, u32, u32, C.c_double, C.c_double, C.POINTER(Sweep), C.POINTER(VolumeGrid), vp],
+        "mcrt_default_render_opts": [C.POINTER(RenderOpts), i32],
+        "mcrt_render_view_for_grid": [C.POINTER(VolumeGrid), vp, vp, C.c_double, C.c_double, u32, u32, C.POINTER(RenderView)],
+        "mcrt_render_frames": [vp, vp, i32, u32, u32, u32, u32, C.POINTER(RenderView), C.POINTER(RenderOpts), vp, vp, vp],
         "mcrt_debug_math": [vp, i32, vp, vp, vp, u32], "mcrt_debug_philox": [vp, vp, vp, vp], "mcrt_debug_stamps": [vp, vp, i32], "mcrt_debug_tail_histograms": [vp, vp, i32], "mcrt_debug_set_error": [vp, u32], "mcrt_debug_fast_paths": [vp, vp],
         "mcrt_scan_maps": [u32, u32, C.c_double, C.c_double, u32, u32, u32, u32, vp, vp],
         "mcrt_group_create": [vp, u32, C.POINTER(vp)], "mcrt_group_destroy": [vp], "mcrt_group_size": [vp], "mcrt_group_root": [vp], "mcrt_group_member": [vp, u32],

@@ -11,7 +11,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, RenderView, RenderOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 DEFAULT_ANGLE = 1.0471975511965976      # the sector of main.cpp:28: 60 degrees [rad]
 
@@ -262,6 +262,31 @@ def host_volume_maps(n_elements, n_rows, sweep, grid, radius_mm=30.0, total_angl
 
 
 BMODE_MODES = {"db": 0, "ref_log": 1}
+
+
+RENDER_MODES = {"mip": 0, "mean": 1, "surface": 2}
+
+
+def render_view(grid, direction, up=(0, 0, 1), pixel_mm=0.25, step_mm=0.25, nx=500, ny=400):
+    """mcrt_render_view_for_grid: an orthographic camera on grid's block [mm, the probe-local frame], looking along `direction` at the block's
+    centre with `up` towards the picture's top; nx x ny pixels pixel_mm apart, samples step_mm apart along the block's longest diagonal.
+    -> RenderView: twelve floats in the block's index space, which may also be filled by hand"""
+    v = RenderView()
+    d = (C.c_double * 3)(*[float(x) for x in direction]); u = (C.c_double * 3)(*[float(x) for x in up])
+    check(load_library().mcrt_render_view_for_grid(C.byref(grid), d, u, float(pixel_mm), float(step_mm), int(nx), int(ny), C.byref(v)))
+    return v
+
+
+def render_opts_struct(in_u8=False, mode=None, lo=None, hi=None, threshold=None, ramp=None, opacity=None, depth_cue=None, t_cut=None):
+    """mcrt_render_opts from keywords over mcrt_default_render_opts(in_u8): mode "mip" / "mean" / "surface" or the MCRT_RENDER_* number"""
+    o = RenderOpts()
+    check(load_library().mcrt_default_render_opts(C.byref(o), 1 if in_u8 else 0))
+    if mode is not None:
+        o.mode = RENDER_MODES[mode] if isinstance(mode, str) else int(mode)
+    for name, val in (("lo", lo), ("hi", hi), ("threshold", threshold), ("ramp", ramp), ("opacity", opacity), ("depth_cue", depth_cue), ("t_cut", t_cut)):
+        if val is not None:
+            setattr(o, name, float(val))
+    return o
 
 
 LABEL_RULES = {"traced": 0, "geometric": 1}
@@ -671,6 +696,15 @@ class Context(_SceneCalls):
         check(self.L.mcrt_bmode_volume_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(p), C.byref(sw), C.byref(grid), ptr(tgc), ptr(peak_dev),
                                               ptr(out_dev)))
 
+    def render_frames(self, vol_dev, n_frames, shape, view, out_dev=None, out8_dev=None, depth_dev=None, in_u8=False, **opts):
+        """mcrt_render_frames: the voxel blocks [n_frames][nw][nv][nu] (shape = (nw, nv, nu); floats, or bytes with in_u8) seen through view
+        (render_view, or a RenderView filled by hand) -> device floats, bytes and step indices [n_frames][ny][nx], each where a pointer is
+        given.  opts: the keywords of render_opts_struct (mode, lo, hi, threshold, ramp, opacity, depth_cue, t_cut)"""
+        nw, nv, nu = shape
+        o = render_opts_struct(in_u8, **opts)
+        check(self.L.mcrt_render_frames(self.h, ptr(vol_dev), 1 if in_u8 else 0, n_frames, nu, nv, nw, C.byref(view), C.byref(o), ptr(out_dev), ptr(out8_dev),
+                                        ptr(depth_dev)))
+
     def label_frames(self, pos=None, dirs=None, *, rule="traced", start_offset=None, e_begin=0, e_end=None, n_frames=None, tissue_dev=None,
                      interface_dev=None, crossings_dev=None):
         """mcrt_label_frames: the central beam of every scan-line walked through the scene.  pos / dirs None: the context's transducer (one
@@ -955,6 +989,24 @@ class Simulator:
         with self.ctx.temp(shape[0] * shape[1] * shape[2]) as out:
             self.ctx.bmode_volume_frames(self.sweep_dev, 1, self.E, self.R, self.sweep, grid, out, **display)
             return self.ctx.d2h(out, shape, np.uint8)
+
+    def render(self, frame_id, grid, direction, up=(0, 0, 1), size=(500, 400), pixel_mm=0.25, step_mm=0.25, mode="surface", **opts):
+        """trace -> convolve -> envelope -> mcrt_bmode_volume_frames -> mcrt_render_frames -> host: grid's displayed voxels seen along
+        `direction`, uint8 [ny][nx] with size = (nx, ny) (sweep= only).  opts: the display keywords of Context.bmode_volume_frames
+        (dynamic_range_db, gain_db, ref, tgc_db, radius_mm, total_angle; bmode_mode for its grey curve) and the render keywords of
+        Context.render_frames (lo, hi, threshold, ramp, opacity, depth_cue, t_cut)"""
+        if self.sweep is None:
+            raise RuntimeError("render() needs Simulator(sweep=...)")
+        ropts = {k: opts.pop(k) for k in ("lo", "hi", "threshold", "ramp", "opacity", "depth_cue", "t_cut") if k in opts}
+        if "bmode_mode" in opts:
+            opts["mode"] = opts.pop("bmode_mode")
+        view = render_view(grid, direction, up, pixel_mm, step_mm, size[0], size[1])
+        self._run(frame_id)
+        shape = (grid.nw, grid.nv, grid.nu)
+        with self.ctx.temp(shape[0] * shape[1] * shape[2]) as vox, self.ctx.temp(size[0] * size[1]) as out:
+            self.ctx.bmode_volume_frames(self.sweep_dev, 1, self.E, self.R, self.sweep, grid, vox, **opts)
+            self.ctx.render_frames(vox, 1, shape, view, out8_dev=out, in_u8=True, mode=mode, **ropts)
+            return self.ctx.d2h(out, (size[1], size[0]), np.uint8)
 
     @contextlib.contextmanager
     def _label_pass(self, rule, start_offset, want_rows=True):

@@ -51,6 +51,7 @@ static Knobs read_knobs()
     k.test_hooks = tuning_env("MCRT_TEST_HOOKS") != nullptr;
     if (const char *e = tuning_env("MCRT_RETIRE_LATE")) k.retire_late = atoi(e) != 0;
     if (const char *e = tuning_env("MCRT_FOLD_B0")) k.fold_b0 = atoi(e) != 0;
+    if (const char *e = tuning_env("MCRT_RENDER_ROW_TILE")) k.render_row_tile = atoi(e) != 0;
     return k;
 }
 

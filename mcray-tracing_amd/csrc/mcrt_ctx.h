@@ -46,6 +46,7 @@ struct Knobs {
     bool retire_late = true;                   // MCRT_RETIRE_LATE=0: paths past the image are traced to their end, as before (FrameArgs::retire_late)
     bool fold_b0 = false;                      // MCRT_FOLD_B0=1: bounce 0 of a silent start medium is accumulated by k_shade itself (FrameArgs::fold_b0).  Bit-identical, one launch and
                                                // 48 B per path less, and no faster on the MI355X (profiles/retire_fold): off until a pass is found that it helps
+    bool render_row_tile = false;              // MCRT_RENDER_ROW_TILE=1: a wavefront of k_render owns 64 pixels of one picture row in place of an 8 x 8 tile (RenderArgs::row_tile)
     bool test_hooks = false;                   // MCRT_TEST_HOOKS: mcrt_debug_set_error may poison the context (tests only)
 };
 

@@ -679,3 +679,78 @@ extern "C" int mcrt_volume_maps(uint32_t E, uint32_t R, double radius_mm, double
             }
     return MCRT_OK;
 }
+
+// ---- volume rendering (the contract is in include/mcrt.h) ---------------------------------------
+extern "C" int mcrt_default_render_opts(mcrt_render_opts *o, int in_u8)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_render_opts: null options");
+    o->mode = MCRT_RENDER_SURFACE; o->lo = 0.0f; o->hi = in_u8 ? 255.0f : 1.0f;
+    o->threshold = 0.25f; o->ramp = 0.25f; o->opacity = 1.0f; o->depth_cue = 0.5f; o->t_cut = 0.0f;
+    return MCRT_OK;
+}
+
+// an orthographic camera on a grid's block, in double; the twelve floats are rounded once at the end
+extern "C" int mcrt_render_view_for_grid(const mcrt_volume_grid *g, const double dir_mm[3], const double up_mm[3], double pixel_mm, double step_mm,
+                                         uint32_t nx, uint32_t ny, mcrt_render_view *out)
+{
+    static const char fn[] = "mcrt_render_view_for_grid";
+    if (!g || !dir_mm || !up_mm || !out) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null %s", fn, !g ? "grid" : !dir_mm ? "dir_mm" : !up_mm ? "up_mm" : "out");
+    if (nx == 0 || ny == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: zero picture size (nx %u, ny %u)", fn, nx, ny);
+    if (g->nu == 0 || g->nv == 0 || g->nw == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: zero grid size (%u x %u x %u)", fn, g->nu, g->nv, g->nw);
+    for (int i = 0; i < 3; i++)
+        if (!(std::isfinite(g->origin_mm[i]) && std::isfinite(g->du_mm[i]) && std::isfinite(g->dv_mm[i]) && std::isfinite(g->dw_mm[i])))
+            return mcrt::set_error(MCRT_ERR_INVALID, "%s: the grid has an entry that is not finite (component %d)", fn, i);
+    if (!(std::isfinite(pixel_mm) && pixel_mm > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: pixel_mm must be finite and > 0 (%g)", fn, pixel_mm);
+    if (!(std::isfinite(step_mm) && step_mm > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: step_mm must be finite and > 0 (%g)", fn, step_mm);
+    auto norm = [](const double v[3]) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
+    auto cross = [](const double a[3], const double b[3], double o[3]) { o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0]; };
+    const double nd = norm(dir_mm), nup = norm(up_mm);
+    if (!(std::isfinite(nd) && nd > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: dir_mm must be finite and not zero", fn);
+    if (!(std::isfinite(nup) && nup > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: up_mm must be finite and not zero", fn);
+    double dn[3], right[3], down[3];
+    for (int i = 0; i < 3; i++) dn[i] = dir_mm[i] / nd;
+    cross(dn, up_mm, right);
+    const double nr = norm(right);
+    if (!(nr > 1e-12 * nup)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: up_mm is parallel to dir_mm", fn);
+    for (int i = 0; i < 3; i++) right[i] /= nr;
+    cross(right, dn, down);
+    for (int i = 0; i < 3; i++) down[i] = -down[i];
+    // M^-1 by cofactors: row r of the inverse is (the cross product of the other two columns) / det
+    const double *du = g->du_mm, *dv = g->dv_mm, *dw = g->dw_mm;
+    double r0[3], r1[3], r2[3];
+    cross(dv, dw, r0); cross(dw, du, r1); cross(du, dv, r2);
+    const double det = du[0] * r0[0] + du[1] * r0[1] + du[2] * r0[2];
+    if (!(std::isfinite(det) && std::fabs(det) > 1e-12 * norm(du) * norm(dv) * norm(dw)))
+        return mcrt::set_error(MCRT_ERR_INVALID, "%s: the grid's axes du_mm, dv_mm, dw_mm do not span space (a cut cannot be rendered)", fn);
+    auto to_index = [&](const double v[3], float o[3]) {
+        o[0] = (float)((r0[0] * v[0] + r0[1] * v[1] + r0[2] * v[2]) / det);
+        o[1] = (float)((r1[0] * v[0] + r1[1] * v[1] + r1[2] * v[2]) / det);
+        o[2] = (float)((r2[0] * v[0] + r2[1] * v[1] + r2[2] * v[2]) / det);
+    };
+    const double eu = (double)(g->nu - 1u), ev = (double)(g->nv - 1u), ew = (double)(g->nw - 1u);
+    double L = 0.0;
+    for (int sv = -1; sv <= 1; sv += 2)
+        for (int sw = -1; sw <= 1; sw += 2) {
+            double d[3];
+            for (int i = 0; i < 3; i++) d[i] = eu * du[i] + sv * ev * dv[i] + sw * ew * dw[i];
+            L = std::max(L, norm(d) / 2.0);
+        }
+    const double steps = std::floor(2.0 * L / step_mm) + 1.0;
+    if (!(steps <= 4096.0)) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: n_steps must be 1..4096 (the diagonal %g mm at step_mm %g)", fn, 2.0 * L, step_mm);
+    double P0[3], vi[3], vj[3], vs[3];
+    const double hx = (double)(nx - 1u) / 2.0 * pixel_mm, hy = (double)(ny - 1u) / 2.0 * pixel_mm;
+    for (int i = 0; i < 3; i++) {
+        const double centre = eu / 2.0 * du[i] + ev / 2.0 * dv[i] + ew / 2.0 * dw[i];         // C - g->origin_mm
+        P0[i] = centre - L * dn[i] - hx * right[i] - hy * down[i];
+        vi[i] = pixel_mm * right[i]; vj[i] = pixel_mm * down[i]; vs[i] = step_mm * dn[i];
+    }
+    mcrt_render_view v;
+    memset(&v, 0, sizeof v);
+    to_index(P0, v.origin); to_index(vi, v.di); to_index(vj, v.dj); to_index(vs, v.ds);
+    v.nx = nx; v.ny = ny; v.n_steps = (uint32_t)steps;
+    for (int i = 0; i < 3; i++)
+        if (!(std::isfinite(v.origin[i]) && std::isfinite(v.di[i]) && std::isfinite(v.dj[i]) && std::isfinite(v.ds[i])))
+            return mcrt::set_error(MCRT_ERR_INVALID, "%s: the view does not fit a float (component %d)", fn, i);
+    *out = v;
+    return MCRT_OK;
+}

@@ -1,6 +1,6 @@
 // mcrt_image.cpp -- the image stages of the C-ABI (include/mcrt.h): PSF, elevation, envelope, scan conversion, B-mode, compounding,
-// volume imaging, RF export / import.  Host C++ only.  Of a context (mcrt_ctx.h) these read its device, its stream, p.speed_of_sound,
-// c.max_travel_us and the image stages' own state (ImageStages), nothing else.
+// volume imaging and rendering, RF export / import.  Host C++ only.  Of a context (mcrt_ctx.h) these read its device, its stream, p.speed_of_sound,
+// c.max_travel_us, knobs.render_row_tile and the image stages' own state (ImageStages), nothing else.
 #include "mcrt_ctx.h"
 #include "mcrt_kernels.h"
 
@@ -385,6 +385,54 @@ extern "C" int mcrt_bmode_volume_frames(mcrt_ctx *c, const float *rf_dev, uint32
     MCRT_TRY(ensure_volume_maps(c, E, R, p->radius_mm, p->total_angle_rad, sw, g, &maps));
     MCRT_TRY(bmode_grey_pass(c, rf_dev, n_frames, K * E, R, &q, tgc_db, k, peak_dev));
     HIP_TRY(mcrt::launch_volume(volume_args(c->img.d_tmp, maps, out_dev, n_frames, E, R, K, n, true), true, c->stream));
+    return MCRT_OK;
+}
+
+// ---- volume rendering (the contract is in include/mcrt.h; the defaults and the view helper are host code: mcrt_host.cpp) ----
+// Everything is checked before anything is launched; the derived floats are made here, in double, rounded once.
+extern "C" int mcrt_render_frames(mcrt_ctx *c, const void *vol_dev, int in_u8, uint32_t n_frames, uint32_t nu, uint32_t nv, uint32_t nw,
+                                  const mcrt_render_view *view, const mcrt_render_opts *o, float *out_dev, uint8_t *out8_dev, float *depth_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_render_frames";
+    if (!vol_dev || !view) return set_error(MCRT_ERR_INVALID, "%s: null %s", fn, vol_dev ? "view" : "vol_dev");
+    if (!out_dev && !out8_dev && !depth_dev) return set_error(MCRT_ERR_INVALID, "%s: out_dev, out8_dev and depth_dev are all null", fn);
+    if (n_frames == 0 || nu == 0 || nv == 0 || nw == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, block %u x %u x %u)", fn, n_frames, nu, nv, nw);
+    if (view->nx == 0 || view->ny == 0) return set_error(MCRT_ERR_INVALID, "%s: view: zero picture size (nx %u, ny %u)", fn, view->nx, view->ny);
+    for (int k = 0; k < 3; k++)
+        if (!(std::isfinite(view->origin[k]) && std::isfinite(view->di[k]) && std::isfinite(view->dj[k]) && std::isfinite(view->ds[k])))
+            return set_error(MCRT_ERR_INVALID, "%s: view: origin, di, dj or ds has an entry that is not finite (component %d)", fn, k);
+    mcrt_render_opts d;
+    if (!o) { mcrt_default_render_opts(&d, in_u8); o = &d; }
+    if (o->mode != MCRT_RENDER_MIP && o->mode != MCRT_RENDER_MEAN && o->mode != MCRT_RENDER_SURFACE) return set_error(MCRT_ERR_INVALID, "%s: unknown mode %u", fn, o->mode);
+    if (!(std::isfinite(o->lo) && std::isfinite(o->hi) && o->hi > o->lo)) return set_error(MCRT_ERR_INVALID, "%s: lo, hi must be finite with hi > lo (%g, %g)", fn, (double)o->lo, (double)o->hi);
+    if (!(o->threshold >= 0.0f && o->threshold < 1.0f)) return set_error(MCRT_ERR_INVALID, "%s: threshold must be in [0,1) (%g)", fn, (double)o->threshold);
+    if (!(o->ramp > 0.0f && o->ramp <= 1.0f)) return set_error(MCRT_ERR_INVALID, "%s: ramp must be in (0,1] (%g)", fn, (double)o->ramp);
+    const float inv_range = (float)(1.0 / ((double)o->hi - (double)o->lo)), inv_ramp = (float)(1.0 / (double)o->ramp);
+    if (!std::isfinite(inv_range)) return set_error(MCRT_ERR_INVALID, "%s: lo, hi: the window is too narrow, 1 / (hi - lo) is no finite float (%g, %g)", fn, (double)o->lo, (double)o->hi);
+    if (!std::isfinite(inv_ramp)) return set_error(MCRT_ERR_INVALID, "%s: ramp is too small, 1 / ramp is no finite float (%g)", fn, (double)o->ramp);
+    if (!(o->opacity > 0.0f && o->opacity <= 1.0f)) return set_error(MCRT_ERR_INVALID, "%s: opacity must be in (0,1] (%g)", fn, (double)o->opacity);
+    if (!(o->depth_cue >= 0.0f && o->depth_cue <= 1.0f)) return set_error(MCRT_ERR_INVALID, "%s: depth_cue must be in [0,1] (%g)", fn, (double)o->depth_cue);
+    if (!(o->t_cut >= 0.0f && o->t_cut < 1.0f)) return set_error(MCRT_ERR_INVALID, "%s: t_cut must be in [0,1) (%g)", fn, (double)o->t_cut);
+    if (view->n_steps == 0 || view->n_steps > 4096u) return set_error(MCRT_ERR_LIMIT, "%s: view: n_steps must be 1..4096 (%u)", fn, view->n_steps);
+    if (nu >= (1u << 24) || nv >= (1u << 24) || nw >= (1u << 24)) return set_error(MCRT_ERR_LIMIT, "%s: nu, nv and nw must be below 2^24 (%u x %u x %u)", fn, nu, nv, nw);
+    if ((double)nu * (double)nv * (double)nw >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: 2^31 voxels or more (%u x %u x %u)", fn, nu, nv, nw);
+    if ((uint64_t)view->nx * view->ny >= 0x80000000ull) return set_error(MCRT_ERR_LIMIT, "%s: view: 2^31 pixels or more (%u x %u)", fn, view->nx, view->ny);
+    if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 frames per call (%u)", fn, n_frames);
+    const size_t nvox = (size_t)nu * nv * nw, npix = (size_t)view->nx * view->ny, vol_bytes = (in_u8 ? 1u : 4u) * (size_t)n_frames * nvox;
+    const struct { const void *p; size_t bytes; const char *name; } outs[3] = { { out_dev, 4 * n_frames * npix, "out_dev" }, { out8_dev, n_frames * npix, "out8_dev" },
+                                                                               { depth_dev, 4 * n_frames * npix, "depth_dev" } };
+    for (const auto &q : outs)
+        if (q.p && ranges_overlap(vol_dev, vol_bytes, q.p, q.bytes)) return set_error(MCRT_ERR_INVALID, "%s: vol_dev and %s overlap", fn, q.name);
+    mcrt::RenderArgs a;
+    a.vol = vol_dev; a.out = out_dev; a.out8 = out8_dev; a.depth = depth_dev;
+    for (int k = 0; k < 3; k++) { a.origin[k] = view->origin[k]; a.di[k] = view->di[k]; a.dj[k] = view->dj[k]; a.ds[k] = view->ds[k]; }
+    a.nx = view->nx; a.ny = view->ny; a.n_steps = view->n_steps; a.F = n_frames; a.nu = nu; a.nv = nv; a.nw = nw;
+    a.mode = o->mode; a.row_tile = c->knobs.render_row_tile ? 1u : 0u;
+    a.lo = o->lo; a.inv_range = inv_range;
+    a.threshold = o->threshold; a.inv_ramp = inv_ramp; a.opacity = o->opacity; a.depth_cue = o->depth_cue; a.t_cut = o->t_cut;
+    a.inv_steps = view->n_steps > 1u ? (float)(1.0 / (double)(view->n_steps - 1u)) : 0.0f;
+    HIP_TRY(mcrt::launch_render(a, in_u8 != 0, c->stream));
     return MCRT_OK;
 }
 

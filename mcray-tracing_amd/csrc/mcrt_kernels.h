@@ -11,6 +11,7 @@
 //   mcrt_display.hip k_bmode_peak, k_bmode_grey, k_bmode (mcrt_bmode_frames: log-compressed 8-bit B-mode frames), k_compound (spatial compounding:
 //                    mcrt_compound_frames, mcrt_bmode_compound_frames)
 //   mcrt_volume.hip  k_volume (volume imaging: mcrt_volume_frames, mcrt_bmode_volume_frames)
+//   mcrt_render.hip  k_render (volume rendering: mcrt_render_frames)
 //   mcrt_label.hip   k_label (ground-truth label maps: mcrt_label_frames), k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames)
 //   mcrt_scene.hip   k_tris_by_id, k_expand_tris; the probes k_math_probe, k_verify_div, k_philox_probe
 //   mcrt_lbvh.hip    the device BVH builder (mcrt_lbvh.h)
@@ -105,6 +106,19 @@ struct VolumeArgs {
     uint32_t vec;                       // 8-bit form: n % 4 == 0 and out is word-aligned, so a lane may store a word per frame
 };
 
+// k_render (mcrt_render_frames): the voxel blocks [F][nw][nv][nu] (floats or bytes) -> floats, bytes and step indices [F][ny][nx]
+struct RenderArgs {
+    const void *vol;                    // float or uint8_t [F][nw][nv][nu]
+    float *out;                         // [F][ny][nx] or null
+    uint8_t *out8;                      // same or null
+    float *depth;                       // same or null
+    float origin[3], di[3], dj[3], ds[3];   // mcrt_render_view, component order u, v, w
+    uint32_t nx, ny, n_steps, F, nu, nv, nw;
+    uint32_t mode;                      // MCRT_RENDER_*
+    uint32_t row_tile;                  // 0: a wavefront owns an 8 x 8 tile of the picture; 1: 64 pixels of one row
+    float lo, inv_range, threshold, inv_ramp, opacity, depth_cue, t_cut, inv_steps;
+};
+
 // k_label (mcrt_label_frames): beside these, a FrameArgs of which it reads the scene, the probe (el_pos, el_dir, pose_stride, e_begin, ne_frame,
 // ne = ne_frame * frames), the row table (row_thr, R, inv_row_dt, thr_end, max_travel, sos_d), start_mat, offs, the spacing, pad_abs, stack_ovf
 // (label_stack_entries() in LDS, the rest [..][label_blocks * 64]) and error_flag
@@ -150,6 +164,7 @@ hipError_t launch_bmode_grey(const float *rf, uint32_t F, uint32_t E, uint32_t R
 hipError_t launch_bmode(const BmodeArgs &a, hipStream_t st);
 hipError_t launch_compound(const CompoundArgs &a, bool out8, hipStream_t st);   // a.mode: the instantiation
 hipError_t launch_volume(const VolumeArgs &a, bool out8, hipStream_t st);
+hipError_t launch_render(const RenderArgs &a, bool in8, hipStream_t st);
 uint32_t label_blocks(size_t lines);                              // workgroups of a k_label launch over `lines` (frame, scan-line) beams (sizes the overflow stacks)
 uint32_t label_stack_entries();
 hipError_t launch_label(const FrameArgs &a, const LabelArgs &l, hipStream_t st);

@@ -3,7 +3,8 @@
 //                   [--db DR] [--gain G] [--ref-log] [--persistence A] [--focus-mm F1[,F2,...]] [--focal-range-mm R]
 //                   [--elevation K] [--elevation-pitch-um P] [--var-z V] [--compound N] [--compound-step-deg D]
 //                   [--compound-mode mean|max|median] [--compound-feather LINES] [--compound-weights w0,w1,...]
-//                   [--sweep K --sweep-step-deg D [--sweep-pivot-mm P] (--cplane-mm Y | --sagittal-mm X)]
+//                   [--sweep K --sweep-step-deg D [--sweep-pivot-mm P] (--cplane-mm Y | --sagittal-mm X | --render DX,DY,DZ ...)]
+//                   [--render DX,DY,DZ --render-box-mm X0,Y0,Z0,X1,Y1,Z1 --render-voxel-mm P [--render-mode mip|mean|surface] [--render-size NX,NY]]
 //                   [--labels FILE.pgm [--label-rule traced|geometric] [--label-offset X]]
 // --gpus N: the first N GPUs of the node, the frame's scan-lines sharded over them (mcrt_group_*: one tracing context and host thread per
 // GPU, the blocks gathered on GPU 0); --devices lists them explicitly, and may repeat one (two ranks sharing a GPU: the one-GPU test).
@@ -37,6 +38,13 @@
 // the y-z picture at lateral position X mm (400 columns along z centred on the probe's plane, 500 rows along y from the arc's apex down,
 // 0.25 mm apart).  rf.bin then holds plane K / 2.  --sweep needs one of the two cuts and --sweep-step-deg; it does not combine with
 // --compound or --elevation, and --persistence has no volume form.
+// --render DX,DY,DZ, with --sweep, writes a rendered view in place of a cut: the box --render-box-mm X0,Y0,Z0,X1,Y1,Z1 of the probe-local frame
+// (mm: x lateral, y the arc's axis from its centre, z elevation) is gathered into cubic voxels --render-voxel-mm P apart, log-compressed to
+// 8-bit grey (mcrt_bmode_volume_frames with the display options, 60 dB without one) and seen along the direction DX,DY,DZ by an orthographic
+// camera that looks at the box's centre with the z axis up (the y axis when the direction is along z): pixels and steps P apart, --render-size
+// NX,NY pixels (500,400), --render-mode mip (the brightest voxel on each ray), mean, or surface (the default: front-to-back compositing with
+// depth cueing; mcrt_render_frames).  It needs --sweep, the box and the voxel size, and takes the place of --cplane-mm / --sagittal-mm;
+// --labels does not combine with it.
 // --labels FILE.pgm writes the ground truth of the picture as a PGM of material indices (their order in the scene file; 255 outside the
 // sector or the sweep): the tissue under every pixel, from the central beam of every scan-line of the unsteered probe walked through the
 // scene (mcrt_label_frames) and scan-converted nearest neighbour (mcrt_label_scan_convert_frames) -- with --sweep the cut of --cplane-mm /
@@ -84,6 +92,7 @@ int main(int argc, char **argv)
     const char *compound_mode = nullptr, *compound_feather = nullptr, *compound_weights = nullptr;   // the options as given
     int sweep_planes = 0; double sweep_step_deg = 0.0, sweep_pivot_mm = 0.0, cut_mm = 0.0;   // sweep_planes 0: off
     bool sweep_given = false, sweep_step_given = false, cplane_given = false, sagittal_given = false;
+    const char *render_dir = nullptr, *render_box = nullptr, *render_voxel = nullptr, *render_mode = nullptr, *render_size = nullptr;   // the options as given
     const char *labels_file = nullptr, *label_rule = nullptr, *label_offset = nullptr;
     mcrt_label_opts lopts; mcrt_default_label_opts(&lopts);
     {   // the options, taken out of the positional arguments
@@ -108,6 +117,11 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--sweep-pivot-mm") && i + 1 < argc) sweep_pivot_mm = std::atof(argv[++i]);
             else if (!std::strcmp(argv[i], "--cplane-mm") && i + 1 < argc) { cut_mm = std::atof(argv[++i]); cplane_given = true; }
             else if (!std::strcmp(argv[i], "--sagittal-mm") && i + 1 < argc) { cut_mm = std::atof(argv[++i]); sagittal_given = true; }
+            else if (!std::strcmp(argv[i], "--render") && i + 1 < argc) render_dir = argv[++i];
+            else if (!std::strcmp(argv[i], "--render-box-mm") && i + 1 < argc) render_box = argv[++i];
+            else if (!std::strcmp(argv[i], "--render-voxel-mm") && i + 1 < argc) render_voxel = argv[++i];
+            else if (!std::strcmp(argv[i], "--render-mode") && i + 1 < argc) render_mode = argv[++i];
+            else if (!std::strcmp(argv[i], "--render-size") && i + 1 < argc) render_size = argv[++i];
             else if (!std::strcmp(argv[i], "--labels") && i + 1 < argc) labels_file = argv[++i];
             else if (!std::strcmp(argv[i], "--label-rule") && i + 1 < argc) label_rule = argv[++i];
             else if (!std::strcmp(argv[i], "--label-offset") && i + 1 < argc) label_offset = argv[++i];
@@ -150,21 +164,52 @@ int main(int argc, char **argv)
         }
         if (sweep_given && (compound_given || elevation_given)) throw std::invalid_argument("--sweep does not combine with --compound or --elevation");
         if (!sweep_given && (sweep_step_given || cplane_given || sagittal_given)) throw std::invalid_argument("--sweep-step-deg, --cplane-mm and --sagittal-mm need --sweep");
+        if (!sweep_given && (render_dir || render_box || render_voxel || render_mode || render_size)) throw std::invalid_argument("--render and its options need --sweep");
+        if (!render_dir && (render_box || render_voxel || render_mode || render_size)) throw std::invalid_argument("--render-box-mm, --render-voxel-mm, --render-mode and --render-size need --render (with --sweep)");
         mcrt_sweep sweep{ 0, 0.0f, 0.0f };
         mcrt_volume_grid cut{};
+        mcrt_render_view view{};
+        mcrt_render_opts ropts; mcrt_default_render_opts(&ropts, 1);
         if (sweep_given) {
             if (sweep_planes < 1 || sweep_planes > 256) throw std::invalid_argument("--sweep takes 1..256 planes");
             if (!sweep_step_given) throw std::invalid_argument("--sweep needs --sweep-step-deg");
-            if (cplane_given == sagittal_given) throw std::invalid_argument("--sweep needs one of --cplane-mm and --sagittal-mm");
+            if ((int)cplane_given + (int)sagittal_given + (render_dir ? 1 : 0) != 1) throw std::invalid_argument("--sweep needs one of --cplane-mm, --sagittal-mm and --render");
             sweep.n_planes = (uint32_t)sweep_planes; sweep.step_rad = (float)(sweep_step_deg * 3.14159265358979323846 / 180.0); sweep.pivot_mm = (float)sweep_pivot_mm;
             if (!(std::isfinite(sweep.step_rad) && sweep.step_rad > 0.0f && (double)(sweep_planes - 1) / 2.0 * (double)sweep.step_rad < 1.5707963267948966))
                 throw std::invalid_argument("--sweep-step-deg must be > 0 and keep every plane's tilt below 90 degrees");
             if (!std::isfinite(sweep.pivot_mm) || !std::isfinite(cut_mm)) throw std::invalid_argument("--sweep-pivot-mm and the cut's position must be finite");
             if (display.persistence != 0.0f) throw std::invalid_argument("--persistence has no volume form: it does not combine with --sweep");
             const double pitch = 0.25;
-            if (cplane_given) { cut.origin_mm[0] = -(500 - 1) * pitch / 2.0; cut.origin_mm[1] = cut_mm; cut.origin_mm[2] = -(400 - 1) * pitch / 2.0; cut.du_mm[0] = pitch; cut.dv_mm[2] = pitch; cut.nu = 500; cut.nv = 400; }
+            if (render_dir) {
+                if (!render_box || !render_voxel) throw std::invalid_argument("--render (with --sweep) needs --render-box-mm and --render-voxel-mm");
+                if (labels_file) throw std::invalid_argument("--labels does not combine with --render (with --sweep): a rendered view has no label picture");
+                const std::vector<double> dir = comma_list<double>(render_dir), box = comma_list<double>(render_box);
+                const std::vector<int> size = render_size ? comma_list<int>(render_size) : std::vector<int>{ 500, 400 };
+                const double voxel = std::atof(render_voxel);
+                if (dir.size() != 3 || box.size() != 6 || size.size() != 2) throw std::invalid_argument("--render (with --sweep) takes DX,DY,DZ, --render-box-mm six numbers, --render-size NX,NY");
+                if (!(std::isfinite(voxel) && voxel > 0.0)) throw std::invalid_argument("--render-voxel-mm (with --sweep --render) must be > 0");
+                if (size[0] < 1 || size[1] < 1) throw std::invalid_argument("--render-size (with --sweep --render) takes two positive numbers");
+                uint32_t n[3];
+                for (int k = 0; k < 3; k++) {
+                    const double cells = std::floor((box[3 + k] - box[k]) / voxel);
+                    if (!(cells >= 0.0 && cells < 16777215.0)) throw std::invalid_argument("--render-box-mm (with --sweep --render): X1 >= X0, Y1 >= Y0, Z1 >= Z0, and fewer than 2^24 voxels along an axis");
+                    n[k] = (uint32_t)cells + 1u; cut.origin_mm[k] = box[k];
+                }
+                cut.du_mm[0] = cut.dv_mm[1] = cut.dw_mm[2] = voxel; cut.nu = n[0]; cut.nv = n[1]; cut.nw = n[2];
+                if (render_mode) {
+                    if (!std::strcmp(render_mode, "mip")) ropts.mode = MCRT_RENDER_MIP;
+                    else if (!std::strcmp(render_mode, "mean")) ropts.mode = MCRT_RENDER_MEAN;
+                    else if (!std::strcmp(render_mode, "surface")) ropts.mode = MCRT_RENDER_SURFACE;
+                    else throw std::invalid_argument("--render-mode (with --sweep --render) takes mip, mean or surface");
+                }
+                const double along_z[3] = { 0.0, 0.0, 1.0 }, along_y[3] = { 0.0, 1.0, 0.0 };
+                const bool dir_is_z = dir[0] == 0.0 && dir[1] == 0.0;
+                if (mcrt_render_view_for_grid(&cut, dir.data(), dir_is_z ? along_y : along_z, voxel, voxel, (uint32_t)size[0], (uint32_t)size[1], &view) != MCRT_OK)
+                    throw std::invalid_argument(std::string("--render (with --sweep): ") + mcrt_last_error());
+            }
+            else if (cplane_given) { cut.origin_mm[0] = -(500 - 1) * pitch / 2.0; cut.origin_mm[1] = cut_mm; cut.origin_mm[2] = -(400 - 1) * pitch / 2.0; cut.du_mm[0] = pitch; cut.dv_mm[2] = pitch; cut.nu = 500; cut.nv = 400; }
             else { cut.origin_mm[0] = cut_mm; cut.origin_mm[1] = transducer_radius_cm * 10.0; cut.origin_mm[2] = -(400 - 1) * pitch / 2.0; cut.du_mm[2] = pitch; cut.dv_mm[1] = pitch; cut.nu = 400; cut.nv = 500; }
-            cut.nw = 1;
+            if (!render_dir) cut.nw = 1;
         }
         if (!labels_file && (label_rule || label_offset)) throw std::invalid_argument(std::string(label_rule ? "--label-rule" : "--label-offset") + " needs --labels");
         if (label_rule) {
@@ -208,7 +253,8 @@ int main(int argc, char **argv)
             else rf_image.trace((uint32_t)f);      // clear + cast_rays + accumulation (main.cpp:102-144)
             rf_image.convolve(psf);           // main.cpp:146
             rf_image.envelope();              // main.cpp:147
-            if (sweep_given)                  // the cut through the swept volume
+            if (render_dir) cut_bytes = rf_image.render(cut, view, &ropts, &display);               // the box seen from a direction
+            else if (sweep_given)             // the cut through the swept volume
                 cut_bytes = bmode ? rf_image.volume(display, cut) : to_bytes(rf_image.volume(cut));   // (as rf_image::save)
             else if (compound_given) { if (bmode) rf_image.postprocess(display, steers, nullptr, opts); else rf_image.postprocess(steers, opts); }   // the views averaged (or opts' mode)
             else if (bmode) rf_image.postprocess(display);   // main.cpp:148, log-compressed to 8-bit grey
@@ -217,7 +263,8 @@ int main(int argc, char **argv)
         check(dev->synchronize(), "mcrt_synchronize");
         const double dt = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
         std::cout << frames / dt << " frames/s, " << (double)frames * transducer_elements * samples / dt << " rays/s on " << devices.size() << " GPU context(s)" << std::endl;
-        if (argc > 4 && sweep_given) write_pgm(argv[4], cut.nu, cut.nv, cut_bytes);
+        if (argc > 4 && render_dir) write_pgm(argv[4], view.nx, view.ny, cut_bytes);
+        else if (argc > 4 && sweep_given) write_pgm(argv[4], cut.nu, cut.nv, cut_bytes);
         else if (argc > 4) { if (bmode) rf_image.save_bmode(argv[4]); else rf_image.save(argv[4]); }
         if (labels_file) {   // what is in that picture: the tissue under every pixel
             rf_image.labels(transducer, &lopts);

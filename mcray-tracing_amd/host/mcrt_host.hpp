@@ -674,7 +674,7 @@ public:
 
     rf_image(double radius_mm, double angle_rad, std::shared_ptr<device> dev_ = nullptr)
         : dev(dev_ ? std::move(dev_) : default_device()), radius_mm(radius_mm), angle(angle_rad), host((size_t)columns * max_rows, 0.0f),
-          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), label(dev)
+          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev)
     {
         std::cout << "rf_image: " << max_rows << ", " << columns << std::endl;          // rfimage.h:30
         rf.reserve(sizeof(float) * columns * max_rows);
@@ -810,6 +810,23 @@ public:
         p.radius_mm = radius_mm; p.total_angle_rad = angle;
         check(mcrt_bmode_volume_frames(dev->ctx, stack.as<float>(), 1, columns, max_rows, &p, &sweep, &grid, tgc_db, nullptr, points.as<uint8_t>()), "mcrt_bmode_volume_frames");
         return download<unsigned char>(points, n);
+    }
+    // volume rendering (mcrt.h: mcrt_render_frames): the displayed voxels of volume(bp, grid) seen through `view` -- mcrt_render_view_for_grid's, or
+    // twelve floats filled by hand -- as the bytes of the picture [view.ny][view.nx].  The voxels stay on the device.  opts: null = the defaults
+    // for a byte block (the surface view); bp: null = mcrt_default_bmode; the sector is this image's own, as in volume(bp, grid)
+    std::vector<unsigned char> render(const mcrt_volume_grid &grid, const mcrt_render_view &view, const mcrt_render_opts *opts = nullptr,
+                                      const mcrt_bmode_params *bp = nullptr, const float *tgc_db = nullptr)
+    {
+        volume_prepare(grid, 1);
+        const size_t npix = (size_t)view.nx * view.ny;
+        if (npix == 0) throw std::invalid_argument("rf_image::render: the view has no pixels");
+        mcrt_bmode_params p;
+        if (bp) p = *bp; else mcrt_default_bmode(&p);
+        p.radius_mm = radius_mm; p.total_angle_rad = angle;
+        check(mcrt_bmode_volume_frames(dev->ctx, stack.as<float>(), 1, columns, max_rows, &p, &sweep, &grid, tgc_db, nullptr, points.as<uint8_t>()), "mcrt_bmode_volume_frames");
+        rendered.reserve(npix);
+        check(mcrt_render_frames(dev->ctx, points.as<uint8_t>(), 1, 1, grid.nu, grid.nv, grid.nw, &view, opts, nullptr, rendered.as<uint8_t>(), nullptr), "mcrt_render_frames");
+        return download<unsigned char>(rendered, npix);
     }
     // ground-truth label maps (mcrt.h: mcrt_label_frames): the central beam of every scan-line of t walked through the scene -- of the K planes of
     // the sweep when the last trace was trace(frame, transducer, sweep), else of t's own plane, whatever was traced before (the unsteered probe
@@ -961,6 +978,7 @@ private:
     uint32_t n_views = 0;                        // ... and how many (nothing: 0)
     mcrt_sweep sweep{ 0, 0.0f, 0.0f };           // ... the sweep of sweep_planes
     device_buffer points;                        // volume(), label_picture(), label_volume(): the gathered points, floats or bytes
+    device_buffer rendered;                      // render(): the picture's bytes
     device_buffer label;                         // labels(): interface, crossings and tissue tables in one allocation
     enum class labels_of { nothing, one_plane, sweep_planes } labelled = labels_of::nothing;   // ... what they hold (one_plane: a 1-plane sweep's too)
     uint32_t label_planes = 0; const unsigned char *label_tissue = nullptr;   // ... their leading axis (nothing: 0) and the tissue table
