@@ -46,7 +46,9 @@ extern "C" {
                                    + mcrt_label_opts, mcrt_default_label_opts, mcrt_label_frames, mcrt_label_scan_convert_frames, mcrt_label_volume_frames
                                    (ground-truth label maps: tissue and interface per scan-line sample, pixel and voxel; additive);
                                    + mcrt_render_view, mcrt_render_opts, mcrt_default_render_opts, mcrt_render_view_for_grid, mcrt_render_frames
-                                   (volume rendering: MIP, mean and surface views of a block of voxels seen from a direction; additive) */
+                                   (volume rendering: MIP, mean and surface views of a block of voxels seen from a direction; additive);
+                                   + mcrt_speckle_opts, mcrt_default_speckle_opts, mcrt_speckle_tables, mcrt_speckle_frames
+                                   (speckle reduction: speckle-reducing anisotropic diffusion over a stack of float frames; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -619,6 +621,55 @@ int mcrt_render_view_for_grid(const mcrt_volume_grid *g, const double dir_mm[3],
 int mcrt_render_frames(mcrt_ctx *ctx, const void *vol_dev, int in_u8, uint32_t n_frames, uint32_t nu, uint32_t nv, uint32_t nw,
                        const mcrt_render_view *view, const mcrt_render_opts *o /* NULL = defaults for in_u8 */,
                        float *out_dev /* [F][ny][nx] or NULL */, uint8_t *out8_dev /* same or NULL */, float *depth_dev /* same or NULL */);
+
+/* ---- speckle reduction: the despeckle filter every scanner has ("SRI", "XRES").  The reference has none.  The algorithm is Yu & Acton's
+ * speckle-reducing anisotropic diffusion (SRAD, IEEE Trans. Image Processing 11(11), 2002) in its usual conservative 4-neighbour
+ * discretisation.  The input is a stack [n_frames][height][width] of floats on the device, width contiguous: the enveloped RF stack
+ * (height = E scan-lines, width = R rows) or a scan-converted float stack alike -- the filter works in index space and knows no geometry.
+ *
+ * Host tables, computed in double and rounded once (mcrt_speckle_tables):
+ *   q_t = q0 * exp(-rho * t),   q0sq[t] = (float)(q_t*q_t),   kq[t] = (float)(1 / (q_t*q_t * (1 + q_t*q_t))),   t = 0 .. n_iter-1
+ *   lam4 = (float)(0.25 * lambda)
+ * Options of which a table entry is not finite or is 0 (a q_t that has decayed to nothing) are refused: MCRT_ERR_INVALID.
+ * The rule, per frame; everything in float, every multiply, add and divide rounded once, no fma:
+ *   0. X = |v| where v is finite, else 0        (step 1 of mcrt_bmode_frames: a NaN scan-line is no echo -- and does not spread 2 pixels per iteration)
+ *   1. for t = 0 .. n_iter-1, over the whole frame, iteration t reading only iteration t-1's X; neighbour indices are clamped,
+ *      iN = max(i-1, 0), iS = min(i+1, H-1), jW = max(j-1, 0), jE = min(j+1, W-1):
+ *        dN = X[iN][j] - X[i][j],  dS = X[iS][j] - X[i][j],  dW = X[i][jW] - X[i][j],  dE = X[i][jE] - X[i][j]
+ *        S1 = ((dN + dS) + dW) + dE
+ *        S2 = ((dN*dN + dS*dS) + dW*dW) + dE*dE
+ *        m  = X[i][j] + 0.25f*S1                                  (the neighbours' mean: the rule never divides by the pixel itself)
+ *        q2 = (0.5f*S2 - 0.0625f*(S1*S1)) / (m*m)
+ *        c[i][j] = fminf(fmaxf(1.0f / (1.0f + (q2 - q0sq[t]) * kq[t]), 0.0f), 1.0f)
+ *            0/0 (a flat zero patch): NaN, which fmaxf turns into c = 0 -- moot, every d there is 0;  x/0, x > 0 (an isolated spike): q2 = inf,
+ *            c = 0;  S2 overflowing: c = 0
+ *        D = ((c[i][j]*dN + c[iS][j]*dS) + c[i][j]*dW) + c[i][jE]*dE
+ *        X'[i][j] = X[i][j] + lam4 * D
+ * What follows: the flux across every interior edge is antisymmetric, so a frame's sum is kept up to rounding; with lambda <= 1 and c in
+ * [0,1] every X' is a convex combination of X and its neighbours; a constant frame keeps its bits; scaling the input by a power of two
+ * scales the output exactly (while nothing overflows or goes subnormal).  n_iter = 0: out = in bit for bit (step 0 is not applied).
+ * q0 is the coefficient of variation of fully developed speckle of a Rayleigh amplitude and rho the paper's decay; n_iter and lambda are
+ * display choices that no measurement backs (a CPU prototype on synthetic speckle, where the effect saturates near 20 iterations). */
+typedef struct { uint32_t n_iter;   /* 0..256; 0: out = in bit for bit                                            (20)        */
+                 float q0;          /* speckle scale at t = 0, > 0, finite                 (0.5227232 = sqrt(4/pi - 1))       */
+                 float rho;         /* decay of the scale per iteration, >= 0, finite                             (1/6)       */
+                 float lambda;      /* time step, in (0, 1]                                                       (0.5)       */
+} mcrt_speckle_opts;                /* 16 bytes: n_iter 0, q0 4, rho 8, lambda 12 */
+/* the defaults above; host only.  MCRT_ERR_INVALID for a null o */
+int mcrt_default_speckle_opts(mcrt_speckle_opts *o);
+/* the tables above; host only.  q0sq and kq may be null when n_iter == 0.  MCRT_ERR_INVALID: null o, q0sq, kq or lam4, q0 not > 0 and finite, rho
+ * not >= 0 and finite, lambda outside (0, 1], a table entry that is not finite or is 0;  MCRT_ERR_LIMIT: n_iter > 256.  On an error nothing is written */
+int mcrt_speckle_tables(const mcrt_speckle_opts *o, float *q0sq /* [n_iter] */, float *kq /* [n_iter] */, float *lam4 /* [1] */);
+/* The rule above over n_frames frames: in_dev -> out_dev, both [n_frames][height][width] on the device.  out_dev == in_dev (in place) is
+ * allowed; any other overlap is MCRT_ERR_INVALID.  o: NULL = the defaults.  Asynchronous on the context's stream: ceil(n_iter / T) launches
+ * of T fused iterations, the last one running the remainder, ping-ponging between out_dev and the context's scratch (the one mcrt_convolve
+ * uses, grown to the largest stack: nothing is allocated once it exists) so that the last launch lands in out_dev; in place with an odd
+ * number of launches the stack is first copied into the scratch.  The per-iteration floats are kernel arguments.  n_iter == 0: a device copy when the buffers differ,
+ * nothing otherwise.  MCRT_ERR_INVALID: null ctx, in_dev or out_dev, a zero n_frames, height or width, options that mcrt_speckle_tables
+ * refuses, buffers that overlap without being the same;  MCRT_ERR_LIMIT: n_iter > 256, a stack of 2^31 floats or more.  On an error nothing is
+ * launched and out_dev is untouched.  Groups: call it on mcrt_group_root(). */
+int mcrt_speckle_frames(mcrt_ctx *ctx, const float *in_dev, uint32_t n_frames, uint32_t height, uint32_t width,
+                        const mcrt_speckle_opts *o /* NULL = defaults */, float *out_dev);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
  * Ground-truth label maps: what is in the picture.  The tracer knows the anatomy exactly; these calls hand it out aligned with every

@@ -11,7 +11,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, RenderView, RenderOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, RenderView, RenderOpts, SpeckleOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 DEFAULT_ANGLE = 1.0471975511965976      # the sector of main.cpp:28: 60 degrees [rad]
 
@@ -287,6 +287,33 @@ def render_opts_struct(in_u8=False, mode=None, lo=None, hi=None, threshold=None,
         if val is not None:
             setattr(o, name, float(val))
     return o
+
+
+def speckle_opts_struct(n_iter=None, q0=None, rho=None, lambda_=None, **kw):
+    """mcrt_speckle_opts from keywords over mcrt_default_speckle_opts: n_iter, q0, rho and the time step, lambda_ (or lam, or "lambda" in a
+    dict: the word is Python's)"""
+    o = SpeckleOpts()
+    check(load_library().mcrt_default_speckle_opts(C.byref(o)))
+    for k in ("lambda", "lam"):
+        if k in kw:
+            lambda_ = kw.pop(k)
+    if kw:
+        raise TypeError("unknown speckle options: %s" % ", ".join(sorted(kw)))
+    if n_iter is not None:
+        o.n_iter = int(n_iter)
+    for name, val in (("q0", q0), ("rho", rho), ("lambda_", lambda_)):
+        if val is not None:
+            setattr(o, name, float(val))
+    return o
+
+
+def host_speckle_tables(opts=None, **kw):
+    """mcrt_speckle_tables: the floats k_srad is given -> (q0sq [n_iter], kq [n_iter], lam4); opts: a SpeckleOpts, or the keywords of speckle_opts_struct"""
+    o = opts if opts is not None else speckle_opts_struct(**kw)
+    n = min(int(o.n_iter), 256)
+    q0sq = np.zeros(n, np.float32); kq = np.zeros(n, np.float32); lam4 = np.zeros(1, np.float32)
+    check(load_library().mcrt_speckle_tables(C.byref(o), ptr(q0sq), ptr(kq), ptr(lam4)))
+    return q0sq, kq, np.float32(lam4[0])
 
 
 LABEL_RULES = {"traced": 0, "geometric": 1}
@@ -705,6 +732,13 @@ class Context(_SceneCalls):
         check(self.L.mcrt_render_frames(self.h, ptr(vol_dev), 1 if in_u8 else 0, n_frames, nu, nv, nw, C.byref(view), C.byref(o), ptr(out_dev), ptr(out8_dev),
                                         ptr(depth_dev)))
 
+    def speckle_frames(self, in_dev, n_frames, height, width, out_dev=None, **opts):
+        """mcrt_speckle_frames: speckle-reducing anisotropic diffusion over the float stack [n_frames][height][width] (width contiguous: the
+        enveloped RF stack is height = E, width = R) -> out_dev (None: in place).  opts: the keywords of speckle_opts_struct (n_iter, q0, rho,
+        lambda_)"""
+        o = speckle_opts_struct(**opts)
+        check(self.L.mcrt_speckle_frames(self.h, ptr(in_dev), n_frames, height, width, C.byref(o), ptr(in_dev if out_dev is None else out_dev)))
+
     def label_frames(self, pos=None, dirs=None, *, rule="traced", start_offset=None, e_begin=0, e_end=None, n_frames=None, tissue_dev=None,
                      interface_dev=None, crossings_dev=None):
         """mcrt_label_frames: the central beam of every scan-line walked through the scene.  pos / dirs None: the context's transducer (one
@@ -860,7 +894,7 @@ class Simulator:
 
     def __init__(self, scene_data, transducer, n_samples=5, n_rows=None, device=0, seed=0x5EED, psf=None, texture=None,
                  max_depth=10, sanitize_tir=0, tex_n=256, bvh_builder="sah", elevation=False, compound=None, compound_mode="mean", compound_weights=None,
-                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0):
+                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0, speckle=None):
         """elevation=True: slice thickness.  trace() then traces the psf's elevation_size planes of the frame as one pose pass -- plane k of
         frame f with frame id f * K + k, the frame-id rule of include/mcrt.h -- and folds them into rf_dev with psf.elevation_rows();
         everything after (convolve, bmode, frame) is unchanged.
@@ -873,11 +907,15 @@ class Simulator:
         sweep=(K, step_rad): volume imaging with a probe swept in elevation about the axis through (0, sweep_pivot_mm, 0).  trace() then traces
         the K tilted planes as one pose pass -- plane k of volume f with frame id f * K + k -- into sweep_dev [K][E][R]; convolve() and the
         envelope run over the K planes; volume() and bmode_volume() gather them at a grid's points.  frame(), bmode() and compound_image()
-        raise.  It does not combine with compound= or elevation=."""
+        raise.  It does not combine with compound= or elevation=.
+        speckle=True, or a dict of the keywords of speckle_opts_struct (n_iter, q0, rho, lambda): speckle reduction.  Every picture that
+        runs the envelope (bmode, compound_image, volume, bmode_volume, render) then passes the enveloped stack through
+        mcrt_speckle_frames in place (despeckle()) before anything reads it.  frame() returns RF and is left alone."""
         if sweep is not None and (compound is not None or elevation):
             raise ValueError("sweep= does not combine with compound= or elevation=")
         if compound is not None and not 1 <= len(tuple(compound)) <= 16:
             raise ValueError("compound takes 1..16 steering angles, got %d" % len(tuple(compound)))
+        self.speckle = None if speckle is None or speckle is False else speckle_opts_struct(**({} if speckle is True else dict(speckle)))
         self.ctx = Context(device)
         self.ctx.set_bvh_builder(bvh_builder)
         self.tr = transducer
@@ -952,12 +990,19 @@ class Simulator:
     def envelope(self):
         self.ctx.envelope_frames(*self._stack, self.E, self.R)
 
+    def despeckle(self):
+        """mcrt_speckle_frames over the stack's images, in place, with the options of speckle= (the defaults without one)"""
+        o = self.speckle if self.speckle is not None else speckle_opts_struct()
+        self.ctx.speckle_frames(*self._stack, self.E, self.R, n_iter=o.n_iter, q0=o.q0, rho=o.rho, lambda_=o.lambda_)
+
     def _run(self, frame_id, convolve=True, envelope=True):
         self.trace(frame_id)
         if convolve:
             self.convolve()
         if envelope:
             self.envelope()
+            if self.speckle is not None:
+                self.despeckle()
 
     def compound_image(self, frame_id=0, convolve=True, envelope=True, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         """trace -> convolve -> envelope -> mcrt_compound_frames -> host: the compounded float picture [out_rows][out_cols] (compound= only)"""

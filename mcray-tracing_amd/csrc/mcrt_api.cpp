@@ -52,6 +52,7 @@ static Knobs read_knobs()
     if (const char *e = tuning_env("MCRT_RETIRE_LATE")) k.retire_late = atoi(e) != 0;
     if (const char *e = tuning_env("MCRT_FOLD_B0")) k.fold_b0 = atoi(e) != 0;
     if (const char *e = tuning_env("MCRT_RENDER_ROW_TILE")) k.render_row_tile = atoi(e) != 0;
+    if (const char *e = tuning_env("MCRT_SPECKLE_FUSE")) { int v = atoi(e); if (v == 2 || v == 4) k.speckle_fuse = (uint32_t)v; }
     return k;
 }
 

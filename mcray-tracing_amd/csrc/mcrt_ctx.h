@@ -37,6 +37,7 @@ struct Work {
 
 // tuning knobs from the environment, read ONCE at mcrt_create (never on the frame path) -- and only in a process started with
 // MCRT_TUNING=1 (mcrt::tuning_env): linked into someone else's program the library has its defaults and nothing else.
+#define MCRT_SPECKLE_FUSE_DEFAULT 2u
 struct Knobs {
     uint32_t ksplit_limit = MCRT_KSPLIT_DEFAULT, trace_blocks = 0, trace_blocks_wide = 0, wide_from = 0 /* 0: the kernels' own default */, wide_max_tree_mb = 128, groups = MCRT_GROUPS_DEFAULT, march_streams = MCRT_SIDE_STREAMS_DEFAULT, march_blocks = 0;   // march_blocks 0: launch_march picks
     bool no_overlap = false, no_priority = false, no_fast_div = false, no_lean = false;
@@ -47,6 +48,7 @@ struct Knobs {
     bool fold_b0 = false;                      // MCRT_FOLD_B0=1: bounce 0 of a silent start medium is accumulated by k_shade itself (FrameArgs::fold_b0).  Bit-identical, one launch and
                                                // 48 B per path less, and no faster on the MI355X (profiles/retire_fold): off until a pass is found that it helps
     bool render_row_tile = false;              // MCRT_RENDER_ROW_TILE=1: a wavefront of k_render owns 64 pixels of one picture row in place of an 8 x 8 tile (RenderArgs::row_tile)
+    uint32_t speckle_fuse = MCRT_SPECKLE_FUSE_DEFAULT;   // MCRT_SPECKLE_FUSE=2|4: iterations of mcrt_speckle_frames per launch of k_srad; 4 is faster for one frame, 2 for a stack
     bool test_hooks = false;                   // MCRT_TEST_HOOKS: mcrt_debug_set_error may poison the context (tests only)
 };
 

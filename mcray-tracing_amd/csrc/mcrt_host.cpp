@@ -680,6 +680,38 @@ extern "C" int mcrt_volume_maps(uint32_t E, uint32_t R, double radius_mm, double
     return MCRT_OK;
 }
 
+// ---- speckle reduction (the contract is in include/mcrt.h) ---------------------------------------
+extern "C" int mcrt_default_speckle_opts(mcrt_speckle_opts *o)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_speckle_opts: null options");
+    o->n_iter = 20u; o->q0 = 0.5227232f; o->rho = (float)(1.0 / 6.0); o->lambda = 0.5f;
+    return MCRT_OK;
+}
+
+// in double, each float rounded once; everything is checked before anything is written
+extern "C" int mcrt_speckle_tables(const mcrt_speckle_opts *o, float *q0sq, float *kq, float *lam4)
+{
+    static const char fn[] = "mcrt_speckle_tables";
+    if (!o || !lam4) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null %s", fn, o ? "lam4" : "options");
+    if (o->n_iter > 256u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: n_iter must be 0..256 (%u)", fn, o->n_iter);
+    if (o->n_iter && (!q0sq || !kq)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null %s", fn, q0sq ? "kq" : "q0sq");
+    if (!(std::isfinite(o->q0) && o->q0 > 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: q0 must be finite and > 0 (%g)", fn, (double)o->q0);
+    if (!(std::isfinite(o->rho) && o->rho >= 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: rho must be finite and >= 0 (%g)", fn, (double)o->rho);
+    if (!(o->lambda > 0.0f && o->lambda <= 1.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: lambda must be in (0,1] (%g)", fn, (double)o->lambda);
+    float a[256], b[256];
+    const float l4 = (float)(0.25 * (double)o->lambda);
+    if (!(std::isfinite(l4) && l4 != 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: lambda is too small, 0.25 * lambda is no float above 0 (%g)", fn, (double)o->lambda);
+    for (uint32_t t = 0; t < o->n_iter; t++) {
+        const double q = (double)o->q0 * std::exp(-(double)o->rho * (double)t), q2 = q * q;
+        a[t] = (float)q2; b[t] = (float)(1.0 / (q2 * (1.0 + q2)));
+        if (!(std::isfinite(a[t]) && a[t] != 0.0f && std::isfinite(b[t]) && b[t] != 0.0f))
+            return mcrt::set_error(MCRT_ERR_INVALID, "%s: q0, rho: the speckle scale of iteration %u has no finite non-zero tables (q_t^2 %g)", fn, t, q2);
+    }
+    for (uint32_t t = 0; t < o->n_iter; t++) { q0sq[t] = a[t]; kq[t] = b[t]; }
+    *lam4 = l4;
+    return MCRT_OK;
+}
+
 // ---- volume rendering (the contract is in include/mcrt.h) ---------------------------------------
 extern "C" int mcrt_default_render_opts(mcrt_render_opts *o, int in_u8)
 {

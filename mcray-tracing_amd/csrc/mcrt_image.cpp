@@ -1,6 +1,6 @@
 // mcrt_image.cpp -- the image stages of the C-ABI (include/mcrt.h): PSF, elevation, envelope, scan conversion, B-mode, compounding,
-// volume imaging and rendering, RF export / import.  Host C++ only.  Of a context (mcrt_ctx.h) these read its device, its stream, p.speed_of_sound,
-// c.max_travel_us, knobs.render_row_tile and the image stages' own state (ImageStages), nothing else.
+// volume imaging and rendering, speckle reduction, RF export / import.  Host C++ only.  Of a context (mcrt_ctx.h) these read its device, its stream,
+// p.speed_of_sound, c.max_travel_us, knobs.render_row_tile, knobs.speckle_fuse and the image stages' own state (ImageStages), nothing else.
 #include "mcrt_ctx.h"
 #include "mcrt_kernels.h"
 
@@ -433,6 +433,49 @@ extern "C" int mcrt_render_frames(mcrt_ctx *c, const void *vol_dev, int in_u8, u
     a.threshold = o->threshold; a.inv_ramp = inv_ramp; a.opacity = o->opacity; a.depth_cue = o->depth_cue; a.t_cut = o->t_cut;
     a.inv_steps = view->n_steps > 1u ? (float)(1.0 / (double)(view->n_steps - 1u)) : 0.0f;
     HIP_TRY(mcrt::launch_render(a, in_u8 != 0, c->stream));
+    return MCRT_OK;
+}
+
+// ---- speckle reduction (the contract is in include/mcrt.h; the defaults and the tables are host code: mcrt_host.cpp) ----
+// Everything is checked before anything is launched.  L = ceil(n_iter / T) launches of T = knobs.speckle_fuse iterations; launch k = 1..L
+// writes out_dev when L - k is even and the scratch when it is odd, and reads what launch k - 1 wrote: the last one lands in out_dev and no
+// launch reads what it writes.  The first launch reads in_dev -- in place with an odd L that is the buffer it writes, so the stack is
+// first copied into the scratch, which then is both the input and the other half of the ping-pong.
+extern "C" int mcrt_speckle_frames(mcrt_ctx *c, const float *in_dev, uint32_t n_frames, uint32_t height, uint32_t width, const mcrt_speckle_opts *o, float *out_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_speckle_frames";
+    if (!in_dev || !out_dev) return set_error(MCRT_ERR_INVALID, "%s: null %s", fn, in_dev ? "out_dev" : "in_dev");
+    if (n_frames == 0 || height == 0 || width == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, height %u, width %u)", fn, n_frames, height, width);
+    mcrt_speckle_opts d;
+    if (!o) { mcrt_default_speckle_opts(&d); o = &d; }
+    float q0sq[256], kq[256], lam4 = 0.0f;
+    MCRT_TRY(mcrt_speckle_tables(o, q0sq, kq, &lam4));
+    if ((double)n_frames * (double)height * (double)width >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: a stack of 2^31 floats or more (%u x %u x %u)", fn, n_frames, height, width);
+    const size_t n = (size_t)n_frames * height * width;
+    if (in_dev != out_dev && ranges_overlap(in_dev, 4 * n, out_dev, 4 * n)) return set_error(MCRT_ERR_INVALID, "%s: in_dev and out_dev overlap without being the same buffer", fn);
+    if (o->n_iter == 0u) {
+        if (in_dev != out_dev) HIP_TRY(hipMemcpyAsync(out_dev, in_dev, 4 * n, hipMemcpyDeviceToDevice, c->stream));
+        return MCRT_OK;
+    }
+    const uint32_t T = c->knobs.speckle_fuse, L = (o->n_iter + T - 1u) / T;
+    if (L > 1u || in_dev == out_dev) MCRT_TRY(ensure_tmp(c, n));
+    float *tmp = c->img.d_tmp;
+    const float *src = in_dev;
+    if (in_dev == out_dev && (L & 1u)) {
+        HIP_TRY(hipMemcpyAsync(tmp, in_dev, 4 * n, hipMemcpyDeviceToDevice, c->stream));
+        src = tmp;
+    }
+    for (uint32_t k = 1; k <= L; k++) {
+        mcrt::SpeckleArgs a;
+        memset(&a, 0, sizeof a);
+        const uint32_t t0 = (k - 1u) * T;
+        a.src = src; a.dst = ((L - k) & 1u) ? tmp : out_dev;
+        a.H = height; a.W = width; a.n = std::min(T, o->n_iter - t0); a.first = k == 1u ? 1u : 0u; a.lam4 = lam4;
+        for (uint32_t s = 0; s < a.n; s++) { a.q0sq[s] = q0sq[t0 + s]; a.kq[s] = kq[t0 + s]; }
+        HIP_TRY(mcrt::launch_srad(a, n_frames, T, c->stream));
+        src = a.dst;
+    }
     return MCRT_OK;
 }
 

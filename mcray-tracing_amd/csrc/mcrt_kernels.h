@@ -12,6 +12,7 @@
 //                    mcrt_compound_frames, mcrt_bmode_compound_frames)
 //   mcrt_volume.hip  k_volume (volume imaging: mcrt_volume_frames, mcrt_bmode_volume_frames)
 //   mcrt_render.hip  k_render (volume rendering: mcrt_render_frames)
+//   mcrt_speckle.hip k_srad (speckle reduction: mcrt_speckle_frames)
 //   mcrt_label.hip   k_label (ground-truth label maps: mcrt_label_frames), k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames)
 //   mcrt_scene.hip   k_tris_by_id, k_expand_tris; the probes k_math_probe, k_verify_div, k_philox_probe
 //   mcrt_lbvh.hip    the device BVH builder (mcrt_lbvh.h)
@@ -119,6 +120,25 @@ struct RenderArgs {
     float lo, inv_range, threshold, inv_ramp, opacity, depth_cue, t_cut, inv_steps;
 };
 
+// k_srad (mcrt_speckle_frames): one launch carries every frame of the stack [F][H][W] through n <= SRAD_FUSE_MAX iterations, src -> dst (two buffers)
+#ifndef SRAD_TH             // (make variant DEFS=-DSRAD_TH=...: the tile is a tuning build's to change)
+#define SRAD_TH 16          // a workgroup's tile: rows ...
+#endif
+#ifndef SRAD_TW
+#define SRAD_TW 64          // ... and columns (W is contiguous)
+#endif
+#define SRAD_FUSE_MAX 4     // iterations per launch: k_srad<2> and <4> are built
+struct SpeckleArgs {
+    const float *src;                   // [F][H][W]
+    float *dst;                         // [F][H][W], not src
+    uint32_t H, W;
+    uint32_t n;                         // iterations of this launch, 1 .. the instantiation's TT
+    uint32_t first;                     // the call's first launch: step 0 of the contract (|v|, or 0 where v is not finite) is applied while staging
+    uint32_t tx, ty;                    // tiles along W and H (launch_srad fills them)
+    float lam4;
+    float q0sq[SRAD_FUSE_MAX], kq[SRAD_FUSE_MAX];   // mcrt_speckle_tables' entries of these n iterations
+};
+
 // k_label (mcrt_label_frames): beside these, a FrameArgs of which it reads the scene, the probe (el_pos, el_dir, pose_stride, e_begin, ne_frame,
 // ne = ne_frame * frames), the row table (row_thr, R, inv_row_dt, thr_end, max_travel, sos_d), start_mat, offs, the spacing, pad_abs, stack_ovf
 // (label_stack_entries() in LDS, the rest [..][label_blocks * 64]) and error_flag
@@ -165,6 +185,7 @@ hipError_t launch_bmode(const BmodeArgs &a, hipStream_t st);
 hipError_t launch_compound(const CompoundArgs &a, bool out8, hipStream_t st);   // a.mode: the instantiation
 hipError_t launch_volume(const VolumeArgs &a, bool out8, hipStream_t st);
 hipError_t launch_render(const RenderArgs &a, bool in8, hipStream_t st);
+hipError_t launch_srad(SpeckleArgs a, uint32_t F, uint32_t fuse, hipStream_t st);   // fuse: 2 or 4 (the instantiation); a.n <= fuse
 uint32_t label_blocks(size_t lines);                              // workgroups of a k_label launch over `lines` (frame, scan-line) beams (sizes the overflow stacks)
 uint32_t label_stack_entries();
 hipError_t launch_label(const FrameArgs &a, const LabelArgs &l, hipStream_t st);

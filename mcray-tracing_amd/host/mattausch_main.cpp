@@ -6,6 +6,7 @@
 //                   [--sweep K --sweep-step-deg D [--sweep-pivot-mm P] (--cplane-mm Y | --sagittal-mm X | --render DX,DY,DZ ...)]
 //                   [--render DX,DY,DZ --render-box-mm X0,Y0,Z0,X1,Y1,Z1 --render-voxel-mm P [--render-mode mip|mean|surface] [--render-size NX,NY]]
 //                   [--labels FILE.pgm [--label-rule traced|geometric] [--label-offset X]]
+//                   [--speckle N [--speckle-q0 X] [--speckle-rho X] [--speckle-lambda X]]
 // --gpus N: the first N GPUs of the node, the frame's scan-lines sharded over them (mcrt_group_*: one tracing context and host thread per
 // GPU, the blocks gathered on GPU 0); --devices lists them explicitly, and may repeat one (two ranks sharing a GPU: the one-GPU test).
 // Same constants (main.cpp:23-37), same frame loop body; instead of blocking on imshow/waitKey every frame it
@@ -52,6 +53,11 @@
 // rays carry, its quirks included -- the map that explains the picture --, geometric the anatomy of closed, nested meshes; --label-offset X
 // restarts the beam X scene units behind every boundary (default: the tracer's 0.1; geometric wants a small one such as 1e-3, which does
 // not step over thin walls).  Both need --labels.
+// --speckle N runs N iterations (0..256) of speckle-reducing anisotropic diffusion over every enveloped image before the picture is made
+// (mcrt_speckle_frames: the despeckle filter of a scanner), on every path above -- the plain picture, the display options, the views of
+// --compound, the planes of --sweep, --render; rf.bin holds the filtered image too.  --speckle-q0 X is the speckle scale (0.5227232, fully
+// developed speckle), --speckle-rho X its decay per iteration (1/6), --speckle-lambda X the time step in (0, 1] (0.5); the three need
+// --speckle.  Without --speckle nothing changes.
 #include "mcrt_host.hpp"
 #include <chrono>
 #include <cmath>
@@ -95,6 +101,8 @@ int main(int argc, char **argv)
     const char *render_dir = nullptr, *render_box = nullptr, *render_voxel = nullptr, *render_mode = nullptr, *render_size = nullptr;   // the options as given
     const char *labels_file = nullptr, *label_rule = nullptr, *label_offset = nullptr;
     mcrt_label_opts lopts; mcrt_default_label_opts(&lopts);
+    const char *speckle_n = nullptr, *speckle_q0 = nullptr, *speckle_rho = nullptr, *speckle_lambda = nullptr;   // the options as given
+    mcrt_speckle_opts sopts; mcrt_default_speckle_opts(&sopts);
     {   // the options, taken out of the positional arguments
         int keep = 1;
         for (int i = 1; i < argc; i++) {
@@ -125,6 +133,10 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--labels") && i + 1 < argc) labels_file = argv[++i];
             else if (!std::strcmp(argv[i], "--label-rule") && i + 1 < argc) label_rule = argv[++i];
             else if (!std::strcmp(argv[i], "--label-offset") && i + 1 < argc) label_offset = argv[++i];
+            else if (!std::strcmp(argv[i], "--speckle") && i + 1 < argc) speckle_n = argv[++i];
+            else if (!std::strcmp(argv[i], "--speckle-q0") && i + 1 < argc) speckle_q0 = argv[++i];
+            else if (!std::strcmp(argv[i], "--speckle-rho") && i + 1 < argc) speckle_rho = argv[++i];
+            else if (!std::strcmp(argv[i], "--speckle-lambda") && i + 1 < argc) speckle_lambda = argv[++i];
             else if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) { devices.clear(); for (int d = 0; d < std::max(1, std::atoi(argv[i + 1])); d++) devices.push_back(d); i++; }
             else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {
                 devices = comma_list<int>(argv[++i]);
@@ -221,6 +233,17 @@ int main(int argc, char **argv)
             lopts.start_offset = (float)std::atof(label_offset);
             if (!(std::isfinite(lopts.start_offset) && lopts.start_offset > 0.0f)) throw std::invalid_argument("--label-offset takes a finite offset > 0");
         }
+        if (!speckle_n && (speckle_q0 || speckle_rho || speckle_lambda)) throw std::invalid_argument("--speckle-q0, --speckle-rho and --speckle-lambda need --speckle");
+        if (speckle_n) {
+            const long n = std::atol(speckle_n);
+            if (n < 0 || n > 256) throw std::invalid_argument("--speckle takes 0..256 iterations");
+            sopts.n_iter = (uint32_t)n;
+            if (speckle_q0) sopts.q0 = (float)std::atof(speckle_q0);
+            if (speckle_rho) sopts.rho = (float)std::atof(speckle_rho);
+            if (speckle_lambda) sopts.lambda = (float)std::atof(speckle_lambda);
+            float q0sq[256], kq[256], lam4;
+            if (mcrt_speckle_tables(&sopts, q0sq, kq, &lam4) != MCRT_OK) throw std::invalid_argument(std::string("--speckle: ") + mcrt_last_error());
+        }
         std::vector<unsigned char> cut_bytes;         // the last frame's cut, as the PGM holds it
         const mcrt_compound_opts *opts = compound_mode || compound_feather || compound_weights ? &copts : nullptr;
         std::vector<float> steers;                    // centred on the unsteered view, ascending
@@ -253,6 +276,7 @@ int main(int argc, char **argv)
             else rf_image.trace((uint32_t)f);      // clear + cast_rays + accumulation (main.cpp:102-144)
             rf_image.convolve(psf);           // main.cpp:146
             rf_image.envelope();              // main.cpp:147
+            if (speckle_n) rf_image.despeckle(sopts);   // the despeckle filter, on whatever the envelope ran over
             if (render_dir) cut_bytes = rf_image.render(cut, view, &ropts, &display);               // the box seen from a direction
             else if (sweep_given)             // the cut through the swept volume
                 cut_bytes = bmode ? rf_image.volume(display, cut) : to_bytes(rf_image.volume(cut));   // (as rf_image::save)

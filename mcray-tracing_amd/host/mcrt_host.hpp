@@ -761,6 +761,13 @@ public:
         if (n_views) { check(mcrt_envelope_frames(dev->ctx, stack.as<float>(), n_views, columns, max_rows), "mcrt_envelope_frames"); return; }
         to_device(); check(mcrt_envelope(dev->ctx, rf.as<float>(), columns, max_rows), "mcrt_envelope");
     }
+    // speckle reduction (mcrt.h: mcrt_speckle_frames): speckle-reducing anisotropic diffusion over the enveloped image -- the views of a
+    // compounded frame, the planes of a sweep --, in place; it goes after envelope() and before whatever makes the picture
+    void despeckle(const mcrt_speckle_opts &o)
+    {
+        if (n_views) { check(mcrt_speckle_frames(dev->ctx, stack.as<float>(), n_views, columns, max_rows, &o, stack.as<float>()), "mcrt_speckle_frames"); return; }
+        to_device(); check(mcrt_speckle_frames(dev->ctx, rf.as<float>(), 1, columns, max_rows, &o, rf.as<float>()), "mcrt_speckle_frames");
+    }
     // the views of trace(frame, transducer, steer_rad) compounded into the float picture scan_converted() / save() read (mcrt_compound_frames):
     // every pixel the mean of the views that cover it; with opts (mcrt_compound_opts: weights per view, a lateral edge ramp, max or median)
     // through mcrt_compound_frames_opts
