@@ -48,7 +48,9 @@ extern "C" {
                                    + mcrt_render_view, mcrt_render_opts, mcrt_default_render_opts, mcrt_render_view_for_grid, mcrt_render_frames
                                    (volume rendering: MIP, mean and surface views of a block of voxels seen from a direction; additive);
                                    + mcrt_speckle_opts, mcrt_default_speckle_opts, mcrt_speckle_tables, mcrt_speckle_frames
-                                   (speckle reduction: speckle-reducing anisotropic diffusion over a stack of float frames; additive) */
+                                   (speckle reduction: speckle-reducing anisotropic diffusion over a stack of float frames; additive);
+                                   + mcrt_recon_opts, mcrt_default_recon_opts, mcrt_recon_transform, mcrt_recon_frames
+                                   (freehand 3-D reconstruction: tracked frames binned into voxels by their poses, with hole filling; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -670,6 +672,72 @@ int mcrt_speckle_tables(const mcrt_speckle_opts *o, float *q0sq /* [n_iter] */, 
  * launched and out_dev is untouched.  Groups: call it on mcrt_group_root(). */
 int mcrt_speckle_frames(mcrt_ctx *ctx, const float *in_dev, uint32_t n_frames, uint32_t height, uint32_t width,
                         const mcrt_speckle_opts *o /* NULL = defaults */, float *out_dev);
+
+/* ---- freehand 3-D reconstruction: a tracked 2-D probe moved by hand over the patient, its frames binned into voxels from their poses --
+ * pixel-nearest-neighbour binning with hole filling (Rohling, Gee, Berman: "A comparison of freehand three-dimensional ultrasound
+ * reconstruction techniques", Medical Image Analysis 3(4), 1999; the default of PLUS / 3D Slicer).  The reference has one plane.  The input
+ * is the stack [F][E][R] that mcrt_trace_frames_poses left on the device (convolved, enveloped, despeckled or not) and the very pose
+ * tables [F][E][3] it was traced with; the output is a voxel block [nw][nv][nu], u fastest, as mcrt_render_frames and (slice by slice)
+ * mcrt_speckle_frames take it.  The grid is an mcrt_volume_grid read in the WORLD frame, in millimetres: voxel (i, j, l) has its centre
+ * at origin + i*du + j*dv + l*dw.  unit_mm is the length of a scene unit in millimetres (10: the tables are in cm).  Row r of a scan-line
+ * lies at path length r * row_mm from the element's position; the wrappers pass depth_mm_f / R, the convention of mcrt_volume_maps'
+ * map_row, so that a reconstruction of a swept pass lies where mcrt_volume_frames puts it.
+ *
+ * Host floats (mcrt_recon_transform), computed in double and rounded once.  M has the columns du, dv, dw; its inverse by cofactors:
+ *   r_u = dv x dw,  r_v = dw x du,  r_w = du x dv,  det = du . r_u,  Minv[c][k] = r_c[k] / det
+ *   A[c][k] = (float)(Minv[c][k] * unit_mm),   b[c] = (float)(-((Minv[c][0]*o_x + Minv[c][1]*o_y) + Minv[c][2]*o_z)),   o = origin_mm
+ *   row_u = (float)(row_mm / unit_mm),   qscale = 2^31 / (double)value_max   (a double)
+ * The rule per sample (f, e, r) with value v; everything in float, one rounding per operation, no fma:
+ *   t   = (float)r * row_u
+ *   P_k = pos[f][e][k] + dir[f][e][k] * t                                k = x, y, z
+ *   x_c = ((b[c] + P_x*A[c][0]) + P_y*A[c][1]) + P_z*A[c][2]             c = u, v, w
+ *   i_c = floorf(x_c + 0.5f)
+ *   inside = 0 <= i_c < n_c for every c            (compared in float; a NaN is not inside)
+ *   usable = v is finite && fabsf(v) < value_max
+ *   if !inside: stats[0]++          else if !usable: stats[1]++
+ *   else: q = (long long)((double)v * qscale)      (truncation)
+ *         count[voxel]++;   MEAN: sum[voxel] += q;   MAX: qmax[voxel] = max(qmax[voxel], q)
+ * F*E*R < 2^31 and |q| < 2^31, so neither sum (int64) nor count (uint32) can overflow; integer sums commute, so the result does not
+ * depend on the order in which the device adds.
+ * Resolve: a voxel with count > 0 is (float)((double)sum / ((double)count * qscale)) in MEAN mode, (float)((double)qmax / qscale) in MAX mode.
+ * Hole filling, for a voxel with count == 0 when fill_radius H > 0:
+ *   for h = 1..H:
+ *       s = 0.0f, n = 0
+ *       over dw, dv, du in [-h, h]   (w outermost, u innermost, ascending):
+ *           if the neighbour is inside the block and its count > 0:  s = s + its resolved value;  n++
+ *       if n >= fill_min: value = s / (float)n;  stop
+ *   if no h succeeded (or H == 0): value = empty
+ * Only sampled voxels are read, never filled ones: the result does not depend on any order.  count_dev gets the sample counts; a filled
+ * hole keeps 0.  stats_dev[0] counts the samples outside the block, stats_dev[1] the unusable ones inside it.  Every voxel of every
+ * requested output is written.
+ * value_max bounds what is binned and fixes the fixed-point step (value_max * 2^-31); fill_radius and fill_min are display choices. */
+enum { MCRT_RECON_MEAN = 0, MCRT_RECON_MAX = 1 };
+typedef struct { uint32_t mode;        /* MCRT_RECON_*                                          (MEAN) */
+                 float    value_max;   /* finite, > 0: a sample with |v| >= value_max is skipped (1024) */
+                 uint32_t fill_radius; /* H, 0..3: 0 = no hole filling                           (1)    */
+                 uint32_t fill_min;    /* >= 1: sampled neighbours a hole needs                  (1)    */
+                 float    empty;       /* finite: the value of a voxel nothing reached           (0)    */
+} mcrt_recon_opts;                     /* 20 bytes: mode 0, value_max 4, fill_radius 8, fill_min 12, empty 16 */
+/* the defaults above; host only.  MCRT_ERR_INVALID for a null o */
+int mcrt_default_recon_opts(mcrt_recon_opts *o);
+/* A [3][3] (row c = u, v, w) and b [3] above; host only.  MCRT_ERR_INVALID: a null pointer, a grid entry that is not finite, a zero nu, nv
+ * or nw, a unit_mm that is not finite or not > 0, axes that do not span space (|det| <= 1e-12 |du| |dv| |dw|), an A or b entry that is no
+ * finite float.  On an error nothing is written */
+int mcrt_recon_transform(const mcrt_volume_grid *grid_world_mm, double unit_mm, float A[9], float b[3]);
+/* The rule above.  stack_dev: device float [F][E][R]; pos, dir: [F][E][3], host or device, with the lifetime rule of
+ * mcrt_trace_frames_poses; out_dev: device float [nw][nv][nu]; count_dev: device uint32, same shape, or NULL; stats_dev: device uint32 [2]
+ * or NULL.  Asynchronous on the context's stream: a clear of the accumulators, k_recon_splat, k_recon_resolve.  The accumulators (12 bytes
+ * per voxel) are a scratch buffer of the context that grows to the largest grid: nothing is allocated on a repeat.  Everything is checked
+ * before anything is launched.  MCRT_ERR_INVALID, the message naming the field: a null ctx, stack_dev, pos, dir, grid or out_dev; a zero
+ * n_frames, n_elements or n_rows; row_mm or unit_mm not finite or not > 0; an unknown mode, a value_max that is not finite and > 0, a
+ * fill_radius above 3, a fill_min of 0, an empty that is not finite; a grid that mcrt_recon_transform refuses; an output that overlaps the
+ * stack or another output.  MCRT_ERR_LIMIT: n_rows > 2048, n_frames > 65535, F*E*R >= 2^31, nu*nv*nw >= 2^31, and a block so
+ * thin that ceil(nu/32) * ceil(nv/8) * ceil(nw/8) >= 2^24 (1 x 1 x N from N = 2^27).  On any error nothing is
+ * written.  Groups: call it on mcrt_group_root(). */
+int mcrt_recon_frames(mcrt_ctx *ctx, const float *stack_dev /* [F][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
+                      const float *pos /* [F][E][3] host or device */, const float *dir /* same */, double row_mm, double unit_mm,
+                      const mcrt_volume_grid *grid /* WORLD frame, mm */, const mcrt_recon_opts *o /* NULL = defaults */,
+                      float *out_dev /* [nw][nv][nu] */, uint32_t *count_dev /* same or NULL */, uint32_t *stats_dev /* [2] or NULL */);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
  * Ground-truth label maps: what is in the picture.  The tracer knows the anatomy exactly; these calls hand it out aligned with every

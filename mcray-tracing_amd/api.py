@@ -11,7 +11,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, RenderView, RenderOpts, SpeckleOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, RenderView, RenderOpts, SpeckleOpts, ReconOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 DEFAULT_ANGLE = 1.0471975511965976      # the sector of main.cpp:28: 60 degrees [rad]
 
@@ -316,6 +316,37 @@ def host_speckle_tables(opts=None, **kw):
     return q0sq, kq, np.float32(lam4[0])
 
 
+RECON_MODES = {"mean": 0, "max": 1}
+
+
+def recon_opts_struct(mode=None, value_max=None, fill_radius=None, fill_min=None, empty=None):
+    """mcrt_recon_opts from keywords over mcrt_default_recon_opts: mode "mean" / "max" or the MCRT_RECON_* number, value_max, fill_radius (0..3),
+    fill_min, empty"""
+    o = ReconOpts()
+    check(load_library().mcrt_default_recon_opts(C.byref(o)))
+    if mode is not None:
+        o.mode = RECON_MODES[mode] if isinstance(mode, str) else int(mode)
+    for name, val, kind in (("value_max", value_max, float), ("fill_radius", fill_radius, int), ("fill_min", fill_min, int), ("empty", empty, float)):
+        if val is not None:
+            setattr(o, name, kind(val))
+    return o
+
+
+def host_recon_transform(grid, unit_mm=10.0):
+    """mcrt_recon_transform: the floats k_recon_splat is given -> (A [3][3], b [3]): voxel index = b + A . P for a point P in scene units
+    (unit_mm millimetres each) and a grid in world millimetres"""
+    A = np.zeros((3, 3), np.float32); b = np.zeros(3, np.float32)
+    check(load_library().mcrt_recon_transform(C.byref(grid), float(unit_mm), ptr(A), ptr(b)))
+    return A, b
+
+
+def _depth_mm_f(depth_cm, speed_of_sound):
+    """the image depth [mm] as the scan-conversion and volume maps take it (mcrt_scan_maps' depth_mm_f): the float
+    (float)(unsigned)(max_travel_us * speed_of_sound) * 0.001f with max_travel_us = (unsigned)(depth_cm / speed_of_sound * 10000)"""
+    travel = int((depth_cm / float(speed_of_sound)) * 10000.0)
+    return float(np.float32(np.float32((travel * int(speed_of_sound)) & 0xffffffff) * np.float32(0.001)))
+
+
 LABEL_RULES = {"traced": 0, "geometric": 1}
 LABEL_NONE = 255            # MCRT_LABEL_NONE: the tissue value of "no data" (outside the sector / sweep)
 LABEL_MAX_CROSSINGS = 64    # MCRT_LABEL_MAX_CROSSINGS
@@ -383,6 +414,15 @@ class Transducer:
         """the element tables of the planes of a sweep (mcrt_transducer_swept at sweep_tilts' angles): (pos [K][E][3], dir [K][E][3])"""
         tabs = [host_transducer_swept(self.n_elements, self.radius_cm, self.separation_mm, self.position, self.angles, float(t), pivot_mm)
                 for t in sweep_tilts(n_planes, step_rad)]
+        return np.stack([t[0] for t in tabs]), np.stack([t[1] for t in tabs])
+
+    def poses(self, positions, angles_deg):
+        """the element tables of a freehand sweep, one pose (position [3] in scene units, angles_deg [3]) per frame -- this probe moved by hand,
+        mcrt_transducer_elements per frame: (pos [F][E][3], dir [F][E][3])"""
+        positions = np.asarray(positions, np.float32).reshape(-1, 3); angles_deg = np.asarray(angles_deg, np.float32).reshape(-1, 3)
+        if positions.shape != angles_deg.shape:
+            raise ValueError("poses takes one position and one set of angles per frame")
+        tabs = [host_transducer(self.n_elements, self.radius_cm, self.separation_mm, p, a) for p, a in zip(positions, angles_deg)]
         return np.stack([t[0] for t in tabs]), np.stack([t[1] for t in tabs])
 
 
@@ -739,6 +779,19 @@ class Context(_SceneCalls):
         o = speckle_opts_struct(**opts)
         check(self.L.mcrt_speckle_frames(self.h, ptr(in_dev), n_frames, height, width, C.byref(o), ptr(in_dev if out_dev is None else out_dev)))
 
+    def recon_frames(self, stack_dev, pos, dirs, n_frames, n_elements, n_rows, grid, out_dev, count_dev=None, stats_dev=None, row_mm=None, unit_mm=10.0,
+                     **opts):
+        """mcrt_recon_frames: the tracked stack [n_frames][n_elements][n_rows] binned into grid's voxels (a VolumeGrid in the WORLD frame, mm)
+        by the pose tables pos / dirs [F][E][3] it was traced with (numpy arrays, CUDA torch tensors or raw device pointers) -> out_dev float
+        [nw][nv][nu], count_dev uint32 the same, stats_dev uint32 [2].  row_mm None: depth_mm_f / n_rows, the row pitch of mcrt_volume_maps.
+        opts: the keywords of recon_opts_struct (mode, value_max, fill_radius, fill_min, empty)"""
+        o = recon_opts_struct(**opts)
+        if row_mm is None:
+            row_mm = _depth_mm_f(self.params.depth_cm, self.params.speed_of_sound) / n_rows
+        pos, dirs, n_frames = _pose_tables("recon_frames", pos, dirs, n_frames, n_elements)
+        check(self.L.mcrt_recon_frames(self.h, ptr(stack_dev), n_frames, n_elements, n_rows, ptr(pos), ptr(dirs), float(row_mm), float(unit_mm), C.byref(grid),
+                                       C.byref(o), ptr(out_dev), ptr(count_dev), ptr(stats_dev)))
+
     def label_frames(self, pos=None, dirs=None, *, rule="traced", start_offset=None, e_begin=0, e_end=None, n_frames=None, tissue_dev=None,
                      interface_dev=None, crossings_dev=None):
         """mcrt_label_frames: the central beam of every scan-line walked through the scene.  pos / dirs None: the context's transducer (one
@@ -1052,6 +1105,32 @@ class Simulator:
             self.ctx.bmode_volume_frames(self.sweep_dev, 1, self.E, self.R, self.sweep, grid, vox, **opts)
             self.ctx.render_frames(vox, 1, shape, view, out8_dev=out, in_u8=True, mode=mode, **ropts)
             return self.ctx.d2h(out, (size[1], size[0]), np.uint8)
+
+    def freehand(self, frame_id, pos, dirs, grid, convolve=True, envelope=True, counts=False, row_mm=None, unit_mm=10.0, **opts):
+        """a freehand sweep and its volume: the F poses pos / dirs [F][E][3] (Transducer.poses) traced as one pose pass into a temporary stack
+        -- pose f with frame id frame_id * F + f -- -> convolve -> envelope (-> despeckle with speckle=) -> mcrt_recon_frames -> host: the float
+        voxels [nw][nv][nu] of grid (a VolumeGrid in the WORLD frame, mm); with counts=True (voxels, sample counts uint32 of the same shape).
+        opts: the keywords of recon_opts_struct.  It raises under compound=, sweep= or elevation=."""
+        if self.steers is not None or self.sweep is not None or self.elevation:
+            raise RuntimeError("freehand() does not combine with compound=, sweep= or elevation=")
+        pos, dirs, F = _pose_tables("freehand", np.asarray(pos), np.asarray(dirs), None, self.E)
+        shape = (grid.nw, grid.nv, grid.nu)
+        n = shape[0] * shape[1] * shape[2]
+        with self.ctx.temp(F * self.E * self.R * 4) as stack_dev, self.ctx.temp(n * 4) as out, self.ctx.temp(n * 4) as cnt:
+            self.ctx.trace_frames_poses(frame_id * F, pos, dirs, stack_dev)
+            held, self._stack = self._stack, (stack_dev, F)
+            try:
+                if convolve:
+                    self.convolve()
+                if envelope:
+                    self.envelope()
+                    if self.speckle is not None:
+                        self.despeckle()
+            finally:
+                self._stack = held
+            self.ctx.recon_frames(stack_dev, pos, dirs, F, self.E, self.R, grid, out, count_dev=cnt if counts else None, row_mm=row_mm, unit_mm=unit_mm, **opts)
+            vox = self.ctx.d2h(out, shape, np.float32)
+            return (vox, self.ctx.d2h(cnt, shape, np.uint32)) if counts else vox
 
     @contextlib.contextmanager
     def _label_pass(self, rule, start_offset, want_rows=True):

@@ -712,6 +712,47 @@ extern "C" int mcrt_speckle_tables(const mcrt_speckle_opts *o, float *q0sq, floa
     return MCRT_OK;
 }
 
+// ---- freehand 3-D reconstruction (the contract is in include/mcrt.h) ---------------------------------------
+extern "C" int mcrt_default_recon_opts(mcrt_recon_opts *o)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_recon_opts: null options");
+    o->mode = MCRT_RECON_MEAN; o->value_max = 1024.0f; o->fill_radius = 1u; o->fill_min = 1u; o->empty = 0.0f;
+    return MCRT_OK;
+}
+
+// world millimetres -> voxel index, as floats that take scene units: in double, each float rounded once; checked before anything is written
+extern "C" int mcrt_recon_transform(const mcrt_volume_grid *g, double unit_mm, float A[9], float b[3])
+{
+    static const char fn[] = "mcrt_recon_transform";
+    if (!g || !A || !b) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null %s", fn, !g ? "grid" : !A ? "A" : "b");
+    if (!(std::isfinite(unit_mm) && unit_mm > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: unit_mm must be finite and > 0 (%g)", fn, unit_mm);
+    if (g->nu == 0 || g->nv == 0 || g->nw == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: grid: zero size (%u x %u x %u)", fn, g->nu, g->nv, g->nw);
+    for (int i = 0; i < 3; i++)
+        if (!(std::isfinite(g->origin_mm[i]) && std::isfinite(g->du_mm[i]) && std::isfinite(g->dv_mm[i]) && std::isfinite(g->dw_mm[i])))
+            return mcrt::set_error(MCRT_ERR_INVALID, "%s: grid: an entry is not finite (component %d)", fn, i);
+    auto norm = [](const double v[3]) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
+    auto cross = [](const double x[3], const double y[3], double o[3]) { o[0] = x[1] * y[2] - x[2] * y[1]; o[1] = x[2] * y[0] - x[0] * y[2]; o[2] = x[0] * y[1] - x[1] * y[0]; };
+    const double *du = g->du_mm, *dv = g->dv_mm, *dw = g->dw_mm, *org = g->origin_mm;
+    double r[3][3];
+    cross(dv, dw, r[0]); cross(dw, du, r[1]); cross(du, dv, r[2]);
+    const double det = du[0] * r[0][0] + du[1] * r[0][1] + du[2] * r[0][2];
+    if (!(std::isfinite(det) && std::fabs(det) > 1e-12 * norm(du) * norm(dv) * norm(dw)))
+        return mcrt::set_error(MCRT_ERR_INVALID, "%s: grid: the axes du_mm, dv_mm, dw_mm do not span space", fn);
+    float fa[9], fb[3];
+    for (int c = 0; c < 3; c++) {
+        double m[3];
+        for (int k = 0; k < 3; k++) { m[k] = r[c][k] / det; fa[3 * c + k] = (float)(m[k] * unit_mm); }
+        fb[c] = (float)(-((m[0] * org[0] + m[1] * org[1]) + m[2] * org[2]));
+    }
+    for (int i = 0; i < 9; i++)
+        if (!std::isfinite(fa[i])) return mcrt::set_error(MCRT_ERR_INVALID, "%s: grid: entry %d of A is no finite float (%g)", fn, i, (double)fa[i]);
+    for (int i = 0; i < 3; i++)
+        if (!std::isfinite(fb[i])) return mcrt::set_error(MCRT_ERR_INVALID, "%s: grid: entry %d of b is no finite float (%g)", fn, i, (double)fb[i]);
+    for (int i = 0; i < 9; i++) A[i] = fa[i];
+    for (int i = 0; i < 3; i++) b[i] = fb[i];
+    return MCRT_OK;
+}
+
 // ---- volume rendering (the contract is in include/mcrt.h) ---------------------------------------
 extern "C" int mcrt_default_render_opts(mcrt_render_opts *o, int in_u8)
 {

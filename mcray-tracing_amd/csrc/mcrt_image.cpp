@@ -1,6 +1,7 @@
 // mcrt_image.cpp -- the image stages of the C-ABI (include/mcrt.h): PSF, elevation, envelope, scan conversion, B-mode, compounding,
-// volume imaging and rendering, speckle reduction, RF export / import.  Host C++ only.  Of a context (mcrt_ctx.h) these read its device, its stream,
-// p.speed_of_sound, c.max_travel_us, knobs.render_row_tile, knobs.speckle_fuse and the image stages' own state (ImageStages), nothing else.
+// volume imaging and rendering, speckle reduction, freehand reconstruction, RF export / import.  Host C++ only.  Of a context (mcrt_ctx.h) these read
+// its device, its stream, p.speed_of_sound, c.max_travel_us, knobs.render_row_tile, knobs.speckle_fuse, the pose staging (pose_stage:
+// mcrt_recon_frames) and the image stages' own state (ImageStages), nothing else.
 #include "mcrt_ctx.h"
 #include "mcrt_kernels.h"
 
@@ -476,6 +477,75 @@ extern "C" int mcrt_speckle_frames(mcrt_ctx *c, const float *in_dev, uint32_t n_
         HIP_TRY(mcrt::launch_srad(a, n_frames, T, c->stream));
         src = a.dst;
     }
+    return MCRT_OK;
+}
+
+// ---- freehand 3-D reconstruction (the contract is in include/mcrt.h; the defaults and the transform are host code: mcrt_host.cpp) ----
+// Everything is checked before anything is launched.  Then, on the context's stream: host pose tables through the context's pose staging
+// (as mcrt_trace_frames_poses stages them), one clear of the accumulators (and of stats_dev), k_recon_splat, k_recon_resolve.
+extern "C" int mcrt_recon_frames(mcrt_ctx *c, const float *stack_dev, uint32_t n_frames, uint32_t E, uint32_t R, const float *pos, const float *dir,
+                                 double row_mm, double unit_mm, const mcrt_volume_grid *g, const mcrt_recon_opts *o, float *out_dev, uint32_t *count_dev,
+                                 uint32_t *stats_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_recon_frames";
+    if (!stack_dev || !pos || !dir || !g || !out_dev)
+        return set_error(MCRT_ERR_INVALID, "%s: null %s", fn, !stack_dev ? "stack_dev" : !pos ? "pos" : !dir ? "dir" : !g ? "grid" : "out_dev");
+    if (n_frames == 0 || E == 0 || R == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, n_elements %u, n_rows %u)", fn, n_frames, E, R);
+    if (!(std::isfinite(row_mm) && row_mm > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: row_mm must be finite and > 0 (%g)", fn, row_mm);
+    if (!(std::isfinite(unit_mm) && unit_mm > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: unit_mm must be finite and > 0 (%g)", fn, unit_mm);
+    mcrt_recon_opts d;
+    if (!o) { mcrt_default_recon_opts(&d); o = &d; }
+    if (o->mode != MCRT_RECON_MEAN && o->mode != MCRT_RECON_MAX) return set_error(MCRT_ERR_INVALID, "%s: unknown mode %u", fn, o->mode);
+    if (!(std::isfinite(o->value_max) && o->value_max > 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: value_max must be finite and > 0 (%g)", fn, (double)o->value_max);
+    if (o->fill_radius > RECON_MAX_FILL) return set_error(MCRT_ERR_INVALID, "%s: fill_radius must be 0..%d (%u)", fn, RECON_MAX_FILL, o->fill_radius);
+    if (o->fill_min == 0u) return set_error(MCRT_ERR_INVALID, "%s: fill_min must be >= 1", fn);
+    if (!std::isfinite(o->empty)) return set_error(MCRT_ERR_INVALID, "%s: empty must be finite", fn);
+    mcrt::ReconArgs a;
+    memset(&a, 0, sizeof a);
+    MCRT_TRY(mcrt_recon_transform(g, unit_mm, a.A, a.b));
+    a.row_u = (float)(row_mm / unit_mm);
+    a.qscale = 0x1p31 / (double)o->value_max;
+    if (!(std::isfinite(a.row_u) && std::isfinite(a.qscale))) return set_error(MCRT_ERR_INVALID, "%s: row_mm / unit_mm or 2^31 / value_max is not finite (%g, %g)", fn, (double)a.row_u, a.qscale);
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: at most %d rows (%u)", fn, MCRT_MAX_ROWS, R);
+    if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 frames per call (%u)", fn, n_frames);
+    if ((double)n_frames * (double)E * (double)R >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: a stack of 2^31 samples or more (%u x %u x %u)", fn, n_frames, E, R);
+    if ((double)g->nu * (double)g->nv * (double)g->nw >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: grid: 2^31 voxels or more (%u x %u x %u)", fn, g->nu, g->nv, g->nw);
+    const uint64_t tiles = (uint64_t)((g->nu + RECON_TU - 1u) / RECON_TU) * ((g->nv + RECON_TV - 1u) / RECON_TV) * ((g->nw + RECON_TW - 1u) / RECON_TW);
+    if (tiles >= RECON_MAX_TILES)
+        return set_error(MCRT_ERR_LIMIT, "%s: grid: 2^24 tiles of %d x %d x %d voxels or more (%u x %u x %u): too thin a block", fn, RECON_TU, RECON_TV, RECON_TW, g->nu, g->nv, g->nw);
+    const size_t ns = (size_t)n_frames * E * R, n = (size_t)g->nu * g->nv * g->nw, lines = (size_t)n_frames * E;
+    const struct { const void *p; size_t bytes; const char *name; } outs[3] = { { out_dev, 4 * n, "out_dev" }, { count_dev, 4 * n, "count_dev" }, { stats_dev, 8, "stats_dev" } };
+    for (int i = 0; i < 3; i++) {
+        if (!outs[i].p) continue;
+        if (ranges_overlap(stack_dev, 4 * ns, outs[i].p, outs[i].bytes)) return set_error(MCRT_ERR_INVALID, "%s: stack_dev and %s overlap", fn, outs[i].name);
+        for (int j = 0; j < i; j++)
+            if (outs[j].p && ranges_overlap(outs[j].p, outs[j].bytes, outs[i].p, outs[i].bytes)) return set_error(MCRT_ERR_INVALID, "%s: %s and %s overlap", fn, outs[j].name, outs[i].name);
+    }
+    const size_t words = n + (n + 1u) / 2u;               // n sums, then n counts
+    if (words > c->img.d_recon.cap) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(c->img.d_recon.alloc(words));
+    }
+    const float *tab[2] = { pos, dir };
+    for (int k = 0; k < 2; k++) {
+        if (is_device_pointer(tab[k])) continue;
+        float *h = nullptr;
+        MCRT_TRY(c->pose_stage[k].begin(3 * lines, c->stream, &h));
+        memcpy(h, tab[k], 12 * lines);
+        MCRT_TRY(c->pose_stage[k].commit(3 * lines, c->stream));
+        tab[k] = c->pose_stage[k].dev;
+    }
+    a.stack = stack_dev; a.pos = tab[0]; a.dir = tab[1];
+    a.sum = c->img.d_recon; a.count = (uint32_t *)(c->img.d_recon.p + n);
+    a.out = out_dev; a.count_out = count_dev; a.stats = stats_dev;
+    a.R = R; a.n_samples = (uint32_t)ns; a.nu = g->nu; a.nv = g->nv; a.nw = g->nw;
+    a.mode = o->mode; a.fill_radius = o->fill_radius; a.fill_min = o->fill_min;
+    a.value_max = o->value_max; a.empty = o->empty;
+    HIP_TRY(hipMemsetAsync(c->img.d_recon, 0, 8 * words, c->stream));
+    if (stats_dev) HIP_TRY(hipMemsetAsync(stats_dev, 0, 8, c->stream));
+    HIP_TRY(mcrt::launch_recon_splat(a, c->stream));
+    HIP_TRY(mcrt::launch_recon_resolve(a, c->stream));
     return MCRT_OK;
 }
 

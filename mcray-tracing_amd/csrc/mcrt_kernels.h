@@ -13,6 +13,7 @@
 //   mcrt_volume.hip  k_volume (volume imaging: mcrt_volume_frames, mcrt_bmode_volume_frames)
 //   mcrt_render.hip  k_render (volume rendering: mcrt_render_frames)
 //   mcrt_speckle.hip k_srad (speckle reduction: mcrt_speckle_frames)
+//   mcrt_recon.hip   k_recon_splat, k_recon_resolve (freehand 3-D reconstruction: mcrt_recon_frames)
 //   mcrt_label.hip   k_label (ground-truth label maps: mcrt_label_frames), k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames)
 //   mcrt_scene.hip   k_tris_by_id, k_expand_tris; the probes k_math_probe, k_verify_div, k_philox_probe
 //   mcrt_lbvh.hip    the device BVH builder (mcrt_lbvh.h)
@@ -139,6 +140,30 @@ struct SpeckleArgs {
     float q0sq[SRAD_FUSE_MAX], kq[SRAD_FUSE_MAX];   // mcrt_speckle_tables' entries of these n iterations
 };
 
+// k_recon_splat and k_recon_resolve (mcrt_recon_frames): the stack [F][E][R] binned into the accumulators of n = nu * nv * nw voxels, then the
+// accumulators resolved and the holes filled into out [nw][nv][nu]
+#define RECON_TU 32         // k_recon_resolve: a workgroup's tile of voxels along u (contiguous) ...
+#define RECON_TV 8          // ... along v ...
+#define RECON_TW 8          // ... and along w; staged in LDS with a halo of fill_radius on every side
+#define RECON_MAX_FILL 3    // the largest fill_radius (the LDS image is sized per launch: 5 bytes per staged voxel)
+#define RECON_MAX_TILES (1u << 24)   // a grid must need fewer resolve tiles than this: a launch holds fewer than 2^32 lanes
+struct ReconArgs {
+    const float *stack;                 // [F][E][R]
+    const float *pos, *dir;             // [F][E][3]
+    unsigned long long *sum;            // [n] MEAN: the int64 sum of q;  MAX: the largest q, biased by 2^63 so that a cleared word is "none yet"
+    uint32_t *count;                    // [n]
+    float *out;                         // [nw][nv][nu]
+    uint32_t *count_out;                // same, or null
+    uint32_t *stats;                    // [2] or null: samples outside the block, unusable samples inside it
+    uint32_t R, n_samples;              // n_samples = F * E * R < 2^31
+    uint32_t nu, nv, nw;
+    uint32_t mode, fill_radius, fill_min;
+    uint32_t tu, tv;                    // tiles along u and v (launch_recon_resolve fills them)
+    float A[9], b[3];                   // mcrt_recon_transform
+    float row_u, value_max, empty;
+    double qscale;
+};
+
 // k_label (mcrt_label_frames): beside these, a FrameArgs of which it reads the scene, the probe (el_pos, el_dir, pose_stride, e_begin, ne_frame,
 // ne = ne_frame * frames), the row table (row_thr, R, inv_row_dt, thr_end, max_travel, sos_d), start_mat, offs, the spacing, pad_abs, stack_ovf
 // (label_stack_entries() in LDS, the rest [..][label_blocks * 64]) and error_flag
@@ -186,6 +211,8 @@ hipError_t launch_compound(const CompoundArgs &a, bool out8, hipStream_t st);   
 hipError_t launch_volume(const VolumeArgs &a, bool out8, hipStream_t st);
 hipError_t launch_render(const RenderArgs &a, bool in8, hipStream_t st);
 hipError_t launch_srad(SpeckleArgs a, uint32_t F, uint32_t fuse, hipStream_t st);   // fuse: 2 or 4 (the instantiation); a.n <= fuse
+hipError_t launch_recon_splat(const ReconArgs &a, hipStream_t st);
+hipError_t launch_recon_resolve(ReconArgs a, hipStream_t st);
 uint32_t label_blocks(size_t lines);                              // workgroups of a k_label launch over `lines` (frame, scan-line) beams (sizes the overflow stacks)
 uint32_t label_stack_entries();
 hipError_t launch_label(const FrameArgs &a, const LabelArgs &l, hipStream_t st);

@@ -7,6 +7,8 @@
 //                   [--render DX,DY,DZ --render-box-mm X0,Y0,Z0,X1,Y1,Z1 --render-voxel-mm P [--render-mode mip|mean|surface] [--render-size NX,NY]]
 //                   [--labels FILE.pgm [--label-rule traced|geometric] [--label-offset X]]
 //                   [--speckle N [--speckle-q0 X] [--speckle-rho X] [--speckle-lambda X]]
+//                   [--freehand N --freehand-step-mm D [--freehand-fan-deg A] --freehand-box-mm X0,Y0,Z0,X1,Y1,Z1 --freehand-voxel-mm P --freehand-out FILE.raw
+//                    [--freehand-mode mean|max] [--freehand-fill H]]
 // --gpus N: the first N GPUs of the node, the frame's scan-lines sharded over them (mcrt_group_*: one tracing context and host thread per
 // GPU, the blocks gathered on GPU 0); --devices lists them explicitly, and may repeat one (two ranks sharing a GPU: the one-GPU test).
 // Same constants (main.cpp:23-37), same frame loop body; instead of blocking on imshow/waitKey every frame it
@@ -58,6 +60,13 @@
 // --compound, the planes of --sweep, --render; rf.bin holds the filtered image too.  --speckle-q0 X is the speckle scale (0.5227232, fully
 // developed speckle), --speckle-rho X its decay per iteration (1/6), --speckle-lambda X the time step in (0, 1] (0.5); the three need
 // --speckle.  Without --speckle nothing changes.
+// --freehand N (1..1024) adds a freehand 3-D acquisition after the frames of the run: the probe is moved by hand, here along its elevation axis
+// in N steps of --freehand-step-mm D centred on the scene's pose, step k tilted by (k - (N-1)/2) x --freehand-fan-deg A (0) about the line through
+// the arc's apex; the N frames are traced as one pass with the last frame's number, convolved, enveloped (and despeckled with --speckle) and
+// binned into the cubic voxels --freehand-voxel-mm P of the box --freehand-box-mm X0,Y0,Z0,X1,Y1,Z1 of the WORLD frame (mm: scene units are cm)
+// from their poses, holes filled from sampled voxels up to --freehand-fill H voxels away (0..3, default 1), every voxel the mean of its
+// samples or with --freehand-mode max the largest (mcrt_recon_frames).  --freehand-out FILE.raw receives the block as little-endian float32,
+// [nw][nv][nu] with x fastest; its sizes are printed.  The picture of the positional arguments is written as without the option.
 #include "mcrt_host.hpp"
 #include <chrono>
 #include <cmath>
@@ -103,6 +112,9 @@ int main(int argc, char **argv)
     mcrt_label_opts lopts; mcrt_default_label_opts(&lopts);
     const char *speckle_n = nullptr, *speckle_q0 = nullptr, *speckle_rho = nullptr, *speckle_lambda = nullptr;   // the options as given
     mcrt_speckle_opts sopts; mcrt_default_speckle_opts(&sopts);
+    const char *freehand_n = nullptr, *freehand_step = nullptr, *freehand_fan = nullptr, *freehand_box = nullptr, *freehand_voxel = nullptr, *freehand_out = nullptr,
+               *freehand_mode = nullptr, *freehand_fill = nullptr;   // the options as given
+    mcrt_recon_opts fopts; mcrt_default_recon_opts(&fopts);
     {   // the options, taken out of the positional arguments
         int keep = 1;
         for (int i = 1; i < argc; i++) {
@@ -137,6 +149,14 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--speckle-q0") && i + 1 < argc) speckle_q0 = argv[++i];
             else if (!std::strcmp(argv[i], "--speckle-rho") && i + 1 < argc) speckle_rho = argv[++i];
             else if (!std::strcmp(argv[i], "--speckle-lambda") && i + 1 < argc) speckle_lambda = argv[++i];
+            else if (!std::strcmp(argv[i], "--freehand") && i + 1 < argc) freehand_n = argv[++i];
+            else if (!std::strcmp(argv[i], "--freehand-step-mm") && i + 1 < argc) freehand_step = argv[++i];
+            else if (!std::strcmp(argv[i], "--freehand-fan-deg") && i + 1 < argc) freehand_fan = argv[++i];
+            else if (!std::strcmp(argv[i], "--freehand-box-mm") && i + 1 < argc) freehand_box = argv[++i];
+            else if (!std::strcmp(argv[i], "--freehand-voxel-mm") && i + 1 < argc) freehand_voxel = argv[++i];
+            else if (!std::strcmp(argv[i], "--freehand-out") && i + 1 < argc) freehand_out = argv[++i];
+            else if (!std::strcmp(argv[i], "--freehand-mode") && i + 1 < argc) freehand_mode = argv[++i];
+            else if (!std::strcmp(argv[i], "--freehand-fill") && i + 1 < argc) freehand_fill = argv[++i];
             else if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) { devices.clear(); for (int d = 0; d < std::max(1, std::atoi(argv[i + 1])); d++) devices.push_back(d); i++; }
             else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {
                 devices = comma_list<int>(argv[++i]);
@@ -244,6 +264,44 @@ int main(int argc, char **argv)
             float q0sq[256], kq[256], lam4;
             if (mcrt_speckle_tables(&sopts, q0sq, kq, &lam4) != MCRT_OK) throw std::invalid_argument(std::string("--speckle: ") + mcrt_last_error());
         }
+        if (!freehand_n && (freehand_step || freehand_fan || freehand_box || freehand_voxel || freehand_out || freehand_mode || freehand_fill))
+            throw std::invalid_argument("--freehand-step-mm, --freehand-fan-deg, --freehand-box-mm, --freehand-voxel-mm, --freehand-out, --freehand-mode and --freehand-fill need --freehand");
+        long freehand_frames = 0; double freehand_step_mm = 0.0, freehand_fan_deg = 0.0;
+        mcrt_volume_grid fgrid{};
+        if (freehand_n) {
+            freehand_frames = std::atol(freehand_n);
+            if (freehand_frames < 1 || freehand_frames > 1024) throw std::invalid_argument("--freehand takes 1..1024 frames");
+            if (!freehand_step || !freehand_box || !freehand_voxel || !freehand_out)
+                throw std::invalid_argument("--freehand needs --freehand-step-mm, --freehand-box-mm, --freehand-voxel-mm and --freehand-out");
+            freehand_step_mm = std::atof(freehand_step); freehand_fan_deg = freehand_fan ? std::atof(freehand_fan) : 0.0;
+            if (!std::isfinite(freehand_step_mm)) throw std::invalid_argument("--freehand-step-mm must be finite");
+            if (!(std::isfinite(freehand_fan_deg) && std::fabs((double)(freehand_frames - 1) / 2.0 * freehand_fan_deg) < 90.0))
+                throw std::invalid_argument("--freehand-fan-deg must keep every frame's tilt below 90 degrees");
+            const std::vector<double> box = comma_list<double>(freehand_box);
+            const double voxel = std::atof(freehand_voxel);
+            if (box.size() != 6) throw std::invalid_argument("--freehand-box-mm takes six numbers");
+            if (!(std::isfinite(voxel) && voxel > 0.0)) throw std::invalid_argument("--freehand-voxel-mm must be > 0");
+            uint32_t n[3];
+            for (int k = 0; k < 3; k++) {
+                const double cells = std::floor((box[3 + k] - box[k]) / voxel);
+                if (!(cells >= 0.0 && cells < 16777215.0)) throw std::invalid_argument("--freehand-box-mm: X1 >= X0, Y1 >= Y0, Z1 >= Z0, and fewer than 2^24 voxels along an axis");
+                n[k] = (uint32_t)cells + 1u; fgrid.origin_mm[k] = box[k];
+            }
+            fgrid.du_mm[0] = fgrid.dv_mm[1] = fgrid.dw_mm[2] = voxel; fgrid.nu = n[0]; fgrid.nv = n[1]; fgrid.nw = n[2];
+            if (freehand_mode) {
+                if (!std::strcmp(freehand_mode, "mean")) fopts.mode = MCRT_RECON_MEAN;
+                else if (!std::strcmp(freehand_mode, "max")) fopts.mode = MCRT_RECON_MAX;
+                else throw std::invalid_argument("--freehand-mode takes mean or max");
+            }
+            if (freehand_fill) {
+                const long h = std::atol(freehand_fill);
+                if (h < 0 || h > 3) throw std::invalid_argument("--freehand-fill takes 0..3 voxels");
+                fopts.fill_radius = (uint32_t)h;
+            }
+            float A[9], b[3];
+            if (mcrt_recon_transform(&fgrid, 10.0, A, b) != MCRT_OK) throw std::invalid_argument(std::string("--freehand: ") + mcrt_last_error());
+            if ((double)fgrid.nu * fgrid.nv * fgrid.nw >= 2147483648.0) throw std::invalid_argument("--freehand-box-mm: 2^31 voxels or more");
+        }
         std::vector<unsigned char> cut_bytes;         // the last frame's cut, as the PGM holds it
         const mcrt_compound_opts *opts = compound_mode || compound_feather || compound_weights ? &copts : nullptr;
         std::vector<float> steers;                    // centred on the unsteered view, ascending
@@ -287,6 +345,23 @@ int main(int argc, char **argv)
         check(dev->synchronize(), "mcrt_synchronize");
         const double dt = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
         std::cout << frames / dt << " frames/s, " << (double)frames * transducer_elements * samples / dt << " rays/s on " << devices.size() << " GPU context(s)" << std::endl;
+        if (freehand_n) {   // the freehand sweep and its volume, in an image of its own: the picture below is the run's
+            rf_image_ tracked{ dev, transducer_radius_cm * 10.0, transducer_amplitude };
+            const auto poses = transducer.freehand((uint32_t)freehand_frames, freehand_step_mm, freehand_fan_deg);
+            tracked.trace((uint32_t)std::max(frames - 1, 0), poses.pos, poses.dir);
+            tracked.convolve(psf);
+            tracked.envelope();
+            if (speckle_n) tracked.despeckle(sopts);
+            const std::vector<float> vox = tracked.reconstruct(fgrid, &fopts);
+            std::ofstream f(freehand_out, std::ios::binary);
+            for (float v : vox) {
+                uint32_t w; std::memcpy(&w, &v, 4);
+                const unsigned char le[4] = { (unsigned char)w, (unsigned char)(w >> 8), (unsigned char)(w >> 16), (unsigned char)(w >> 24) };
+                f.write((const char *)le, 4);
+            }
+            if (!f) throw std::runtime_error(std::string("cannot write ") + freehand_out);
+            std::cout << "freehand volume: " << fgrid.nu << " x " << fgrid.nv << " x " << fgrid.nw << " voxels (x, y, z), float32 [nw][nv][nu], " << freehand_frames << " frames" << std::endl;
+        }
         if (argc > 4 && render_dir) write_pgm(argv[4], view.nx, view.ny, cut_bytes);
         else if (argc > 4 && sweep_given) write_pgm(argv[4], cut.nu, cut.nv, cut_bytes);
         else if (argc > 4) { if (bmode) rf_image.save_bmode(argv[4]); else rf_image.save(argv[4]); }

@@ -313,6 +313,27 @@ public:
         }
         return t;
     }
+    // freehand 3-D: the element tables of a hand-held sweep of n_frames frames -- the probe translated along its elevation axis
+    // (mcrt_transducer_elevation_axis) in steps of step_mm centred on its own pose, step k tilted by (k - (n-1)/2) * fan_deg about the line
+    // through the arc's apex (mcrt_transducer_swept with the pivot at the radius): pos / dir [n_frames][N][3]; z_mm the offsets [mm]
+    plane_tables freehand(uint32_t n_frames, double step_mm, double fan_deg = 0.0) const
+    {
+        float axis[3];
+        check(mcrt_transducer_elevation_axis(angles.data(), axis), "transducer elevation axis");
+        plane_tables t;
+        const size_t one = 3 * transducer_elements;
+        t.pos.resize(n_frames * one); t.dir.resize(n_frames * one); t.z_mm.resize(n_frames);
+        for (uint32_t k = 0; k < n_frames; k++) {
+            const double kk = (double)k - (double)(n_frames - 1u) / 2.0;
+            const float s = (float)(kk * step_mm / 10.0), tilt = (float)(kk * fan_deg * 3.14159265358979323846 / 180.0);
+            float p[3];
+            for (int i = 0; i < 3; i++) { const float d = axis[i] * s; p[i] = position.v[i] + d; }
+            t.z_mm[k] = (float)(kk * step_mm);
+            check(mcrt_transducer_swept((uint32_t)transducer_elements, radius_cm, separation_mm, p, angles.data(), tilt, (float)(radius_cm * 10.0), t.pos.data() + k * one,
+                                        t.dir.data() + k * one), "transducer freehand");
+        }
+        return t;
+    }
     void setPosition(const vec3 &p) { position = p; }
     void setAngles(const std::array<float, 3> &a) { angles = a; }
     vec3 getPosition() const { return position; }
@@ -743,6 +764,40 @@ public:
         pose_pass(frame_id, sw.n_planes, t.swept(sw), stack, "rf_image::trace: frame_id * planes does not fit a frame id");
         holds = stack_of::sweep_planes; n_views = sw.n_planes; sweep = sw;
     }
+    // freehand 3-D (mcrt.h: mcrt_recon_frames): the frames of a tracked probe moved by hand, one pose per frame -- a vector of transducers, or the
+    // two tables [F][columns][3] (transducer::freehand makes a regular one) --, traced as ONE pose pass -- pose f with frame id frame_id * F + f
+    // -- into the stack the views of a compounded frame use.  convolve(), envelope() and despeckle() then run over the F frames, and
+    // reconstruct(grid) bins them into voxels.  The tables are kept for it.  The next trace of another kind ends the tracked state.
+    void trace(uint32_t frame_id, const std::vector<float> &pos, const std::vector<float> &dir)
+    {
+        const size_t one = 3 * (size_t)columns, F = pos.size() / one;
+        if (F == 0 || F > 65535 || pos.size() != F * one || dir.size() != pos.size()) throw std::invalid_argument("rf_image::trace: pose tables [F][columns][3], F = 1..65535");
+        tracked.pos = pos; tracked.dir = dir;
+        pose_pass(frame_id, (uint32_t)F, tracked, stack, "rf_image::trace: frame_id * poses does not fit a frame id");
+        holds = stack_of::tracked_frames; n_views = (uint32_t)F;
+    }
+    template <size_t N> void trace(uint32_t frame_id, const std::vector<transducer<N>> &poses)
+    {
+        static_assert(N == columns, "one scan-line per transducer element");
+        std::vector<float> pos, dir;
+        for (const auto &t : poses) { pos.insert(pos.end(), t.pos.begin(), t.pos.end()); dir.insert(dir.end(), t.dir.begin(), t.dir.end()); }
+        trace(frame_id, pos, dir);
+    }
+    // the frames of trace(frame, poses) binned into grid's voxels (a grid in the WORLD frame, mm; scene units are cm) with hole filling: floats
+    // [nw][nv][nu].  opts: null = mcrt_default_recon_opts; counts: the samples per voxel, when asked for.  A row of a scan-line is
+    // depth_mm_f / max_rows long, the row pitch of volume(grid)'s maps
+    std::vector<float> reconstruct(const mcrt_volume_grid &grid, const mcrt_recon_opts *opts = nullptr, std::vector<uint32_t> *counts = nullptr)
+    {
+        if (holds != stack_of::tracked_frames) throw std::invalid_argument("rf_image::reconstruct: trace(frame, poses) first");
+        const size_t n = (size_t)grid.nu * grid.nv * grid.nw;
+        if (n == 0 || n >= ((size_t)1 << 31)) throw std::invalid_argument("rf_image::reconstruct: the grid needs 1 .. 2^31 - 1 voxels");
+        points.reserve(8 * n);
+        const float depth_mm_f = (float)(uint32_t)(max_travel_time_us * speed_of_sound) * 0.001f;
+        check(mcrt_recon_frames(dev->ctx, stack.as<float>(), n_views, columns, max_rows, tracked.pos.data(), tracked.dir.data(), (double)depth_mm_f / (double)max_rows, 10.0,
+                                &grid, opts, points.as<float>(), counts ? points.as<uint32_t>() + n : nullptr, nullptr), "mcrt_recon_frames");
+        if (counts) *counts = download<uint32_t>(points.as<uint32_t>() + n, n);
+        return download<float>(points, n);
+    }
     template <typename psf_> void convolve(const psf_ &p)
     {
         float *img = rf.as<float>(); uint32_t frames = 1;
@@ -981,9 +1036,10 @@ private:
     size_t bmode_n = 0; uint32_t bmode_rows = 0, bmode_cols = 0; bool state_valid = false;
     device_buffer planes;                        // trace(frame, transducer, psf): the plane stack [K][columns][max_rows]
     device_buffer stack;                         // trace(frame, transducer, steer_rad | sweep): the images [n_views][columns][max_rows]
-    enum class stack_of { nothing, views, sweep_planes } holds = stack_of::nothing;   // ... what the last trace left in it
+    enum class stack_of { nothing, views, sweep_planes, tracked_frames } holds = stack_of::nothing;   // ... what the last trace left in it
     uint32_t n_views = 0;                        // ... and how many (nothing: 0)
     mcrt_sweep sweep{ 0, 0.0f, 0.0f };           // ... the sweep of sweep_planes
+    struct pose_tables { std::vector<float> pos, dir; } tracked;   // ... the poses of tracked_frames, [n_views][columns][3] each
     device_buffer points;                        // volume(), label_picture(), label_volume(): the gathered points, floats or bytes
     device_buffer rendered;                      // render(): the picture's bytes
     device_buffer label;                         // labels(): interface, crossings and tissue tables in one allocation
