@@ -3,7 +3,7 @@
 // quantisation, every frame of a pass in one launch).  Spatial compounding (mcrt_compound_frames, mcrt_bmode_compound_frames): k_compound, the
 // N steered views of every frame gathered through their N map pairs into one float or 8-bit picture.
 // The reference stops at rfimage.h:131-136 (log10(v+1)/log10(max+1), commented out) and rfimage.h:142-147 (convertTo CV_8U, 255).
-#include "mcrt_device.h"
+#include "mcrt_pixels.h"
 
 namespace mcrt {
 
@@ -101,8 +101,8 @@ __global__ void __launch_bounds__(256) k_bmode_grey(const float *rf, uint32_t E,
 }
 
 // Steps 4-6.  Each lane owns the 4 consecutive output pixels 4q .. 4q+3 (fewer at the end of a frame) and walks the frames [f0, f1) of its
-// chunk (blockIdx.y): the maps are read once, persistence is a register recurrence, and each frame's 4 pixels leave as one 32-bit store
-// where the frame size and the output pointer keep them aligned (VEC_OUT).  The 16 taps of frame f+1 are loaded before frame f is blended
+// chunk (mcrt_pixels.h: frame_window): the maps are read once, persistence is a register recurrence, and each frame's 4 pixels leave as one
+// 32-bit store where the frame size and the output pointer keep them aligned (VEC_OUT: pass.vec).  The 16 taps of frame f+1 are loaded before frame f is blended
 // (the recurrence is short; the gathers are what a lane waits for).  Frames are cut into chunks only without persistence (alpha = 0),
 // where every frame stands alone.  The blend is remap_bilinear, k_remap's own expression, over the grey levels of k_bmode_grey.
 template <bool VEC_OUT>
@@ -110,9 +110,10 @@ __global__ void __launch_bounds__(256) k_bmode(BmodeArgs a)
 {
     const uint32_t q = blockIdx.x * 256u + threadIdx.x;
     const uint32_t p0 = 4u * q;
-    if (p0 >= a.n) return;
-    const uint32_t cnt = min(4u, a.n - p0), E = a.E, R = a.R;
-    float mx[4], my[4], y[4];
+    const uint32_t n = a.pass.n;
+    if (p0 >= n) return;
+    const uint32_t cnt = min(4u, n - p0), E = a.E, R = a.R;
+    float mx[4], my[4];
     RemapPoint pt[4];
     if (cnt == 4u) {                                    // the maps are hipMalloc'd and p0 % 4 == 0: 16-byte aligned
         const float4 c4 = *(const float4 *)(a.map_col + p0), r4 = *(const float4 *)(a.map_row + p0);
@@ -124,14 +125,11 @@ __global__ void __launch_bounds__(256) k_bmode(BmodeArgs a)
     }
 #pragma unroll
     for (int j = 0; j < 4; j++) pt[j] = remap_point(mx[j], my[j]);
-    const uint32_t f0 = blockIdx.y * a.frames_per_chunk, f1 = min(a.F, f0 + a.frames_per_chunk);
+    uint32_t f0, f1;
+    frame_window(a.pass, f0, f1);
     const bool smooth = a.alpha > 0.0f;
-    bool have_prev = false;
-    if (smooth && a.state && !a.reset) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) y[j] = (uint32_t)j < cnt ? a.state[p0 + j] : 0.0f;
-        have_prev = true;
-    }
+    float y[4];
+    bool have_prev = persist_load(y, smooth, a.state, a.reset, p0, 1u, n);
     const size_t frame = (size_t)E * R;
     float t[4][2][2], tn[4][2][2];                      // the taps of frame f and of frame f+1
     auto gather = [&](uint32_t f, float (*dst)[2][2]) {
@@ -142,22 +140,18 @@ __global__ void __launch_bounds__(256) k_bmode(BmodeArgs a)
     if (f0 < f1) gather(f0, t);
     for (uint32_t f = f0; f < f1; f++) {
         if (f + 1u < f1) gather(f + 1u, tn);
-        uint32_t bytes = 0u;
+        float s[4];
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const float s = remap_blend(pt[j], t[j]);
-            if (!smooth) y[j] = s;
-            else y[j] = fmaf(a.alpha, have_prev ? y[j] : s, (1.0f - a.alpha) * s);
-            bytes |= (uint32_t)(uint8_t)(y[j] * 255.0f + 0.5f) << (8 * j);
-        }
-        have_prev = true;
-        uint8_t *o = a.out + (size_t)f * a.n + p0;
+        for (int j = 0; j < 4; j++) s[j] = remap_blend(pt[j], t[j]);
+        persist_step(y, have_prev, smooth, a.alpha, s);
+        const uint32_t bytes = quantise4(y);
+        uint8_t *o = a.out + (size_t)f * n + p0;
         if (VEC_OUT && cnt == 4u) *(uint32_t *)o = bytes;
         else for (uint32_t j = 0; j < cnt; j++) o[j] = (uint8_t)(bytes >> (8 * j));
 #pragma unroll
         for (int j = 0; j < 4; j++) { t[j][0][0] = tn[j][0][0]; t[j][0][1] = tn[j][0][1]; t[j][1][0] = tn[j][1][0]; t[j][1][1] = tn[j][1][1]; }
     }
-    if (a.state && f1 == a.F && f0 < f1) {
+    if (a.state && f1 == a.pass.F && f0 < f1) {
 #pragma unroll
         for (int j = 0; j < 4; j++) if ((uint32_t)j < cnt) a.state[p0 + j] = y[j];
     }
@@ -167,17 +161,12 @@ __global__ void __launch_bounds__(256) k_bmode(BmodeArgs a)
 // at the point view n's maps give for p -- k_remap's expression per view, summed in n order, one rounding per operation.  OUT8 = false
 // writes that float (mcrt_compound_frames); OUT8 = true takes the grey levels of k_bmode_grey and goes on as k_bmode does: persistence as
 // a register recurrence, quantisation, one 32-bit store per frame and lane (mcrt_bmode_compound_frames).
-// A wavefront owns 256 consecutive pixels, a lane the four pixels wb + 64 j + lane, j = 0..3: in every gather the 64 lanes then ask for 64
-// NEIGHBOURING pixels, as k_remap's do.  (With four consecutive pixels per lane, k_bmode's layout, the lanes of one gather are four pixels
-// apart and reach 2.5 times as many scan-lines, each a cache line of its own: measured)  The lane walks the frames [f0, f1)
-// of its chunk (blockIdx.y) in groups of up to 8.  The loop of a group is VIEWS-outer: a view's 4 points are made once per group (16 views'
-// points at once would take 16 x 4 x 6 registers), then that view is gathered and blended for each frame of the group into per-frame sums
-// in registers.  Which views cover a pixel depends on the maps alone, so the count is made once per group.  The maps are padded to a
-// multiple of 256 pixels per view (zeros: the pixels past the picture's end read tap (0, 0), which exists, and are not stored).  The float
-// form stores 256 contiguous bytes per instruction as it is; the 8-bit form first turns the wavefront's 4 x 64 bytes round with four
-// ds_bpermute, so that lane L holds the bytes of pixels wb + 4 L .. 4 L + 3 and stores them as one word (VEC_OUT: the picture's size and
-// the output pointer keep them aligned; a wavefront at the picture's end stores its bytes one by one).  Frames are cut into chunks only
-// without persistence, as in k_bmode.
+// The layout, the frame chunks and the stores are the pixel tile's (mcrt_pixels.h; with k_bmode's four consecutive pixels per lane the lanes
+// of one gather reach 2.5 times as many scan-lines: measured).  The lane walks the frames [f0, f1) of its chunk in groups of up
+// to 8.  The loop of a group is VIEWS-outer: a view's 4 points are made once per group (16 views' points at once would take 16 x 4 x 6
+// registers), then that view is gathered and blended for each frame of the group into per-frame sums in registers.  Which views cover a
+// pixel depends on the maps alone, so the count is made once per group.  VEC_OUT is pass.vec.  Frames are cut into chunks only without
+// persistence, as in k_bmode.
 //
 // MODE (mcrt_compound_frames_opts / mcrt_bmode_compound_frames_opts; the default options run COMPOUND_PLAIN, the loop described above):
 //   COMPOUND_WEIGHTED  the weighted, feathered mean.  A view's weight at a pixel (compound_weight: its view weight times the lateral edge
@@ -249,50 +238,19 @@ template <int NB, int PIX> MCRT_DEV float median_pick(const float (&v)[NB][PIX],
 template <bool OUT8, bool VEC_OUT, int MODE = COMPOUND_PLAIN, int NB = 0>
 __global__ void __launch_bounds__(256) k_compound(CompoundArgs a)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wb = blockIdx.x * 1024u + (threadIdx.x >> 6) * 256u;      // the wavefront's first pixel
-    if (wb >= a.n) return;                                                    // (the whole wavefront)
-    const uint32_t p0 = wb + lane, E = a.E, R = a.R, N = a.N;                 // the lane's pixels: p0 + 64 j
-    const bool whole = wb + 256u <= a.n;
+    PixelTile tile;
+    if (!pixel_tile(a.pass, tile)) return;
+    const uint32_t p0 = tile.p0, f0 = tile.f0, f1 = tile.f1, pixels = a.pass.n, n_pad = a.pass.n_pad, E = a.E, R = a.R, N = a.N;
     const size_t view = (size_t)E * R;
-    const uint32_t f0 = blockIdx.y * a.frames_per_chunk, f1 = min(a.F, f0 + a.frames_per_chunk);
     const bool smooth = OUT8 && a.alpha > 0.0f;
-    float y[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-    bool have_prev = false;
-    if (smooth && a.state && !a.reset) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) y[j] = p0 + 64u * j < a.n ? a.state[p0 + 64u * j] : 0.0f;
-        have_prev = true;
-    }
-    // frame f's four compounded values of this lane leave: persistence, quantisation and the word store, or the floats
+    float y[4];
+    bool have_prev = persist_load(y, smooth, a.state, a.reset, p0, 64u, pixels);
+    // frame f's four compounded values of this lane leave: persistence, quantisation and the byte store, or the floats
     auto emit = [&](uint32_t f, const float (&v)[4]) {
         if (OUT8) {
-            uint32_t bytes = 0u;                    // byte j: pixel p0 + 64 j
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                if (!smooth) y[j] = v[j];
-                else y[j] = fmaf(a.alpha, have_prev ? y[j] : v[j], (1.0f - a.alpha) * v[j]);
-                bytes |= (uint32_t)(uint8_t)(y[j] * 255.0f + 0.5f) << (8 * j);
-            }
-            have_prev = true;
-            uint8_t *o = (uint8_t *)a.out + (size_t)f * a.n;
-            if (VEC_OUT && whole) {                 // pixel wb + 4 L + i is byte L / 16 of lane (4 L + i) % 64: every lane is active here
-                uint32_t word = 0u;
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const uint32_t got = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((4u * lane + (uint32_t)i) & 63u) * 4u), (int)bytes);
-                    word |= ((got >> (8u * (lane >> 4))) & 0xffu) << (8 * i);
-                }
-                *(uint32_t *)(o + wb + 4u * lane) = word;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; j++) if (p0 + 64u * j < a.n) o[p0 + 64u * j] = (uint8_t)(bytes >> (8 * j));
-            }
-        } else {
-            float *o = (float *)a.out + (size_t)f * a.n;
-#pragma unroll
-            for (int j = 0; j < 4; j++) if (p0 + 64u * j < a.n) o[p0 + 64u * j] = v[j];
-        }
+            persist_step(y, have_prev, smooth, a.alpha, v);
+            tile_store_u8((uint8_t *)a.out + (size_t)f * pixels, tile, pixels, quantise4(y), VEC_OUT);
+        } else tile_store_f32((float *)a.out + (size_t)f * pixels, tile, pixels, v);
     };
     if constexpr (MODE == COMPOUND_MEDIAN) {
         const float last_line = (float)(E - 1u), inf = __builtin_inff();
@@ -308,7 +266,7 @@ __global__ void __launch_bounds__(256) k_compound(CompoundArgs a)
 #pragma unroll
                 for (int n = 0; n < NB; n++) {
                     if ((uint32_t)n < N) {                  // (the same in every lane)
-                        const float *mc = a.maps + (size_t)(2u * n) * a.n_pad + p0, *mr = mc + a.n_pad;
+                        const float *mc = a.maps + (size_t)(2u * n) * n_pad + p0, *mr = mc + n_pad;
                         const float *g = a.src + ((size_t)f * N + (uint32_t)n) * view;
                         const float wv = a.weight[n];
 #pragma unroll
@@ -350,7 +308,7 @@ __global__ void __launch_bounds__(256) k_compound(CompoundArgs a)
 #pragma unroll
                 for (int j = 0; j < 4; j++) sum[k][j] = MODE == COMPOUND_MAX ? -__builtin_inff() : 0.0f;
             for (uint32_t n = 0; n < N; n++) {
-                const float *mc = a.maps + (size_t)(2u * n) * a.n_pad + p0, *mr = mc + a.n_pad;   // (n_pad % 256 == 0: p0 + 192 < n_pad)
+                const float *mc = a.maps + (size_t)(2u * n) * n_pad + p0, *mr = mc + n_pad;
                 RemapPoint pt[4];
                 bool covered[4];
                 float w[4];
@@ -396,9 +354,9 @@ __global__ void __launch_bounds__(256) k_compound(CompoundArgs a)
             }
         }
     }
-    if (OUT8 && a.state && f1 == a.F && f0 < f1) {
+    if (OUT8 && a.state && f1 == a.pass.F && f0 < f1) {
 #pragma unroll
-        for (int j = 0; j < 4; j++) if (p0 + 64u * j < a.n) a.state[p0 + 64u * j] = y[j];
+        for (int j = 0; j < 4; j++) if (p0 + 64u * j < pixels) a.state[p0 + 64u * j] = y[j];
     }
 }
 
@@ -429,10 +387,8 @@ hipError_t launch_bmode_grey(const float *rf, uint32_t F, uint32_t E, uint32_t R
 
 hipError_t launch_bmode(const BmodeArgs &a, hipStream_t st)
 {
-    const uint32_t groups = (a.n + 3u) / 4u, chunks = (a.F + a.frames_per_chunk - 1u) / a.frames_per_chunk;
-    const dim3 grid((groups + 255u) / 256u, chunks), blk(256);
-    const bool vec = a.n % 4u == 0u && (uintptr_t)a.out % 4u == 0u;
-    if (vec) hipLaunchKernelGGL((k_bmode<true>), grid, blk, 0, st, a);
+    const dim3 grid = pixel_grid(a.pass), blk(256);
+    if (a.pass.vec) hipLaunchKernelGGL((k_bmode<true>), grid, blk, 0, st, a);
     else hipLaunchKernelGGL((k_bmode<false>), grid, blk, 0, st, a);
     return hipGetLastError();
 }
@@ -440,12 +396,10 @@ hipError_t launch_bmode(const BmodeArgs &a, hipStream_t st)
 // a.mode picks the instantiation; the median's views loop is unrolled over the smallest bucket that holds a.N
 hipError_t launch_compound(const CompoundArgs &a, bool out8, hipStream_t st)
 {
-    const uint32_t chunks = (a.F + a.frames_per_chunk - 1u) / a.frames_per_chunk;
-    const dim3 grid((a.n + 1023u) / 1024u, chunks), blk(256);
-    const bool vec = a.n % 4u == 0u && (uintptr_t)a.out % 4u == 0u;          // the 8-bit form's one word per lane
+    const dim3 grid = pixel_grid(a.pass), blk(256);
 #define MCRT_COMPOUND(...) do { \
         if (!out8) hipLaunchKernelGGL((k_compound<false, false, __VA_ARGS__>), grid, blk, 0, st, a); \
-        else if (vec) hipLaunchKernelGGL((k_compound<true, true, __VA_ARGS__>), grid, blk, 0, st, a); \
+        else if (a.pass.vec) hipLaunchKernelGGL((k_compound<true, true, __VA_ARGS__>), grid, blk, 0, st, a); \
         else hipLaunchKernelGGL((k_compound<true, false, __VA_ARGS__>), grid, blk, 0, st, a); } while (0)
     switch (a.mode) {
     case COMPOUND_PLAIN: MCRT_COMPOUND(COMPOUND_PLAIN, 0); break;

@@ -197,6 +197,14 @@ static uint32_t display_frames_per_chunk(uint32_t n_frames, uint32_t n, float al
     return (n_frames + chunks - 1u) / chunks;
 }
 
+// the pass description of k_bmode, k_compound, k_volume and k_label_gather: n_frames pictures of n points, out_elem_bytes each (1: a lane
+// may store a word per frame where the picture's size and the pointer keep it aligned)
+static mcrt::PixelPass pixel_pass(uint32_t n_frames, uint32_t n, float alpha, const void *out, uint32_t out_elem_bytes)
+{
+    const uint32_t vec = out_elem_bytes == 1u && n % 4u == 0u && (uintptr_t)out % 4u == 0u ? 1u : 0u;
+    return mcrt::PixelPass{ n, (uint32_t)MapCache::pad(n), n_frames, display_frames_per_chunk(n_frames, n, alpha), vec };
+}
+
 // The contract is in include/mcrt.h.  Everything is checked before anything is launched; then, on the context's stream: the TGC factors
 // (only when they differ from the ones on the device), with the automatic reference the peaks (memset + k_bmode_peak), the grey level of
 // every RF tap (k_bmode_grey, into the context's scratch) and their scan conversion, persistence and quantisation (k_bmode).
@@ -211,8 +219,7 @@ extern "C" int mcrt_bmode_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_fr
     MCRT_TRY(bmode_grey_pass(c, rf_dev, n_frames, E, R, p, tgc_db, k, peak_dev));
     mcrt::BmodeArgs a;
     a.grey = c->img.d_tmp; a.map_col = maps; a.map_row = maps + MapCache::pad((size_t)p->out_rows * p->out_cols); a.state = state_dev; a.out = out_dev; a.alpha = p->persistence;
-    a.E = E; a.R = R; a.n = p->out_rows * p->out_cols; a.F = n_frames; a.reset = p->reset_state ? 1u : 0u;
-    a.frames_per_chunk = display_frames_per_chunk(n_frames, a.n, a.alpha);
+    a.E = E; a.R = R; a.reset = p->reset_state ? 1u : 0u; a.pass = pixel_pass(n_frames, p->out_rows * p->out_cols, a.alpha, out_dev, 1u);
     HIP_TRY(mcrt::launch_bmode(a, c->stream));
     return MCRT_OK;
 }
@@ -276,8 +283,7 @@ extern "C" int mcrt_compound_frames_opts(mcrt_ctx *c, const float *rf_dev, uint3
     MCRT_TRY(compound_opts_check(fn, o, N, a));
     MCRT_TRY(ensure_maps(c, c->img.cmaps, E, R, radius_mm, total_angle, orows, ocols, cp, &a.maps));
     a.src = rf_dev; a.state = nullptr; a.out = out_dev; a.alpha = 0.0f;
-    a.E = E; a.R = R; a.n = n; a.n_pad = (uint32_t)MapCache::pad(n); a.F = n_frames; a.N = N; a.reset = 1u;
-    a.frames_per_chunk = display_frames_per_chunk(n_frames, n, 0.0f);
+    a.E = E; a.R = R; a.N = N; a.reset = 1u; a.pass = pixel_pass(n_frames, n, 0.0f, out_dev, 4u);
     HIP_TRY(mcrt::launch_compound(a, false, c->stream));
     return MCRT_OK;
 }
@@ -306,8 +312,7 @@ extern "C" int mcrt_bmode_compound_frames_opts(mcrt_ctx *c, const float *rf_dev,
     MCRT_TRY(ensure_maps(c, c->img.cmaps, E, R, p->radius_mm, p->total_angle_rad, p->out_rows, p->out_cols, cp, &a.maps));
     MCRT_TRY(bmode_grey_pass(c, rf_dev, n_frames, N * E, R, p, tgc_db, k, peak_dev));
     a.src = c->img.d_tmp; a.state = state_dev; a.out = out_dev; a.alpha = p->persistence;
-    a.E = E; a.R = R; a.n = n; a.n_pad = (uint32_t)MapCache::pad(n); a.F = n_frames; a.N = N; a.reset = p->reset_state ? 1u : 0u;
-    a.frames_per_chunk = display_frames_per_chunk(n_frames, n, a.alpha);
+    a.E = E; a.R = R; a.N = N; a.reset = p->reset_state ? 1u : 0u; a.pass = pixel_pass(n_frames, n, a.alpha, out_dev, 1u);
     HIP_TRY(mcrt::launch_compound(a, true, c->stream));
     return MCRT_OK;
 }
@@ -346,9 +351,7 @@ static int volume_args_check(const char *fn, uint32_t n_frames, uint32_t E, uint
 static mcrt::VolumeArgs volume_args(const float *src, const float *maps, void *out, uint32_t n_frames, uint32_t E, uint32_t R, uint32_t K, uint32_t n, bool out8)
 {
     mcrt::VolumeArgs a;
-    a.src = src; a.maps = maps; a.out = out; a.E = E; a.R = R; a.K = K; a.n = n; a.n_pad = (uint32_t)MapCache::pad(n); a.F = n_frames;
-    a.frames_per_chunk = display_frames_per_chunk(n_frames, n, 0.0f);
-    a.vec = out8 && n % 4u == 0u && (uintptr_t)out % 4u == 0u ? 1u : 0u;
+    a.src = src; a.maps = maps; a.out = out; a.E = E; a.R = R; a.K = K; a.pass = pixel_pass(n_frames, n, 0.0f, out, out8 ? 1u : 4u);
     return a;
 }
 
@@ -554,9 +557,7 @@ static mcrt::LabelGatherArgs label_gather_args(const uint8_t *src, const float *
                                                uint32_t K, uint32_t n)
 {
     mcrt::LabelGatherArgs a;
-    a.src = src; a.map_plane = plane; a.map_col = col; a.map_row = row; a.out = out; a.E = E; a.R = R; a.K = K; a.n = n; a.F = n_frames;
-    a.frames_per_chunk = display_frames_per_chunk(n_frames, n, 0.0f);
-    a.vec = n % 4u == 0u && (uintptr_t)out % 4u == 0u ? 1u : 0u;
+    a.src = src; a.map_plane = plane; a.map_col = col; a.map_row = row; a.out = out; a.E = E; a.R = R; a.K = K; a.pass = pixel_pass(n_frames, n, 0.0f, out, 1u);
     return a;
 }
 

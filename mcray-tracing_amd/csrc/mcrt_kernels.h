@@ -18,8 +18,10 @@
 //   mcrt_scene.hip   k_tris_by_id, k_expand_tris; the probes k_math_probe, k_verify_div, k_philox_probe
 //   mcrt_lbvh.hip    the device BVH builder (mcrt_lbvh.h)
 // Shared device code: mcrt_device.h (primitives and the knobs more than one unit reads), mcrt_walk.h (the lane walk's steps, also k_path's),
-// mcrt_shade.h (shade_path, also k_path's).  Everything is scalar fp32/fp64 VALU + integer work -- no dense contraction, hence no MFMA --
-// and the arithmetic follows the parity contract expression by expression (compiled -ffp-contract=off).
+// mcrt_shade.h (shade_path, also k_path's), mcrt_pixels.h (the pixel tile of k_bmode, k_compound, k_volume and k_label_gather and the byte
+// k_render writes: layout, frame chunks, persistence, quantisation, the word store -- included by mcrt_display / volume / label / render.hip
+// only).  Everything is scalar fp32/fp64 VALU + integer work -- no dense contraction, hence no MFMA -- and the arithmetic follows the
+// parity contract expression by expression (compiled -ffp-contract=off).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -72,6 +74,10 @@ constexpr uint32_t MCRT_ALL_BOUNCES = 0xffffffffu;   // launch_march: accumulate
 
 struct ConvTaps { float ax[16]; float lat[32]; uint32_t n_ax, n_lat; };
 
+// What the host says about a pass over F pictures of n points (pixel_pass in mcrt_image.cpp fills it, mcrt_pixels.h reads it): n_pad is n rounded
+// up to 256, the length of every map; blockIdx.y is a chunk of frames_per_chunk frames; vec: 8-bit output, n % 4 == 0 and out word-aligned
+struct PixelPass { uint32_t n, n_pad, F, frames_per_chunk, vec; };
+
 // k_bmode (mcrt_bmode_frames): the grey levels [F][E][R] of k_bmode_grey -> bytes [F][n], n = out_rows * out_cols
 struct BmodeArgs {
     const float *grey;                  // [F][E][R]
@@ -79,7 +85,8 @@ struct BmodeArgs {
     float *state;                       // [n] persistence state, or null
     uint8_t *out;                       // [F][n]
     float alpha;
-    uint32_t E, R, n, F, frames_per_chunk, reset;
+    uint32_t E, R, reset;
+    PixelPass pass;
 };
 
 // k_compound (mcrt_compound_frames / mcrt_bmode_compound_frames): the views [F][N][E][R] (RF floats, or the grey levels of k_bmode_grey)
@@ -90,7 +97,9 @@ struct CompoundArgs {
     float *state;                       // [n] persistence state, or null (8-bit form only)
     void *out;                          // float or uint8_t [F][n]
     float alpha;
-    uint32_t E, R, n, n_pad, F, N, frames_per_chunk, reset;
+    uint32_t E, R;
+    PixelPass pass;
+    uint32_t N, reset;
     uint32_t mode;                      // COMPOUND_*: which k_compound runs
     float feather;                      // mcrt_compound_opts::feather_lines (COMPOUND_PLAIN does not read it)
     float weight[16];                   // mcrt_compound_opts::view_weight, the first N (COMPOUND_PLAIN does not read them)
@@ -104,8 +113,8 @@ struct VolumeArgs {
     const float *src;                   // [F][K][E][R]
     const float *maps;                  // [3][n_pad] the grid's maps: plane, column, row; zero-padded to n_pad = n rounded up to 256
     void *out;                          // float or uint8_t [F][n]
-    uint32_t E, R, K, n, n_pad, F, frames_per_chunk;
-    uint32_t vec;                       // 8-bit form: n % 4 == 0 and out is word-aligned, so a lane may store a word per frame
+    uint32_t E, R, K;
+    PixelPass pass;
 };
 
 // k_render (mcrt_render_frames): the voxel blocks [F][nw][nv][nu] (floats or bytes) -> floats, bytes and step indices [F][ny][nx]
@@ -181,8 +190,8 @@ struct LabelGatherArgs {
     const uint8_t *src;                 // [F][K][E][R]
     const float *map_plane, *map_col, *map_row;   // [n_pad] each, n_pad = n rounded up to 256
     uint8_t *out;                       // [F][n]
-    uint32_t E, R, K, n, F, frames_per_chunk;
-    uint32_t vec;                       // n % 4 == 0 and out is word-aligned, so a lane may store a word per frame
+    uint32_t E, R, K;
+    PixelPass pass;
 };
 
 hipError_t launch_init(const FrameArgs &a, hipStream_t st);

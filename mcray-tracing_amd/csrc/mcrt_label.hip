@@ -3,7 +3,7 @@
 // interface met in it; k_label_gather gathers a tissue map through the scan-conversion and volume maps, nearest neighbour.
 // The reference draws pictures only (ray.cpp:13-47 decides the medium behind a boundary, rfimage.h:33-40 the row of a time,
 // rfimage.h:183-215 the sector's maps); it keeps no map of what it drew.
-#include "mcrt_device.h"
+#include "mcrt_pixels.h"
 #include "mcrt_walk.h"
 
 #ifndef MCRT_LABEL_STACK
@@ -167,9 +167,8 @@ hipError_t launch_label(const FrameArgs &a, const LabelArgs &l, hipStream_t st)
 // =============================================================================================================
 // the nearest-neighbour gathers: labels cannot be interpolated.  Per coordinate m of an output point: f = floorf(m), i = (long long)f +
 // (m - f >= 0.5f), inside when 0 <= i < extent; a NaN coordinate or one outside gives MCRT_LABEL_NONE.  The maps are the float calls' own
-// buffers (k_remap's two maps, k_volume's three, padded to a multiple of 256 points), the layout k_volume's: a wavefront owns 256
-// consecutive points, a lane the four points wb + 64 j + lane -- in every gather the 64 lanes ask for 64 neighbouring points -- and the
-// wavefront's 4 x 64 bytes are turned round with four ds_bpermute so that a lane stores one word (a.vec; byte by byte at the grid's end).
+// buffers (k_remap's two maps, k_volume's three, padded to a multiple of 256 points); the layout, the frame chunks and the byte store are
+// the pixel tile's (mcrt_pixels.h).
 // =============================================================================================================
 MCRT_DEV bool label_nearest(float m, uint32_t extent, uint32_t &i_o)
 {
@@ -181,47 +180,31 @@ MCRT_DEV bool label_nearest(float m, uint32_t extent, uint32_t &i_o)
 
 __global__ void __launch_bounds__(256) k_label_gather(LabelGatherArgs a)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wb = blockIdx.x * 1024u + (threadIdx.x >> 6) * 256u;      // the wavefront's first point
-    if (wb >= a.n) return;                                                    // (the whole wavefront)
-    const uint32_t p0 = wb + lane;
-    const bool whole = wb + 256u <= a.n;
+    PixelTile tile;
+    if (!pixel_tile(a.pass, tile)) return;
+    const uint32_t p0 = tile.p0, n = a.pass.n;
     const size_t plane = (size_t)a.E * a.R, frame = plane * a.K;
-    const uint32_t f0 = blockIdx.y * a.frames_per_chunk, f1 = min(a.F, f0 + a.frames_per_chunk);
     size_t at[4]; bool in[4];
 #pragma unroll
-    for (int j = 0; j < 4; j++) {      // (n_pad % 256 == 0: p0 + 192 < n_pad)
+    for (int j = 0; j < 4; j++) {
         uint32_t z = 0u, x, y;
         in[j] = label_nearest(a.map_col[p0 + 64 * j], a.E, x);
         in[j] = label_nearest(a.map_row[p0 + 64 * j], a.R, y) && in[j];
         if (a.map_plane) in[j] = label_nearest(a.map_plane[p0 + 64 * j], a.K, z) && in[j];
         at[j] = in[j] ? (size_t)z * plane + (size_t)x * a.R + y : 0;
     }
-    for (uint32_t f = f0; f < f1; f++) {
+    for (uint32_t f = tile.f0; f < tile.f1; f++) {
         const uint8_t *src = a.src + (size_t)f * frame;
         uint32_t bytes = 0u;                                // byte j: point p0 + 64 j
 #pragma unroll
         for (int j = 0; j < 4; j++) bytes |= (in[j] ? (uint32_t)src[at[j]] : MCRT_LABEL_NONE) << (8 * j);
-        uint8_t *o = a.out + (size_t)f * a.n;
-        if (a.vec && whole) {                               // point wb + 4 L + i is byte L / 16 of lane (4 L + i) % 64: every lane is active here
-            uint32_t word = 0u;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const uint32_t got = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((4u * lane + (uint32_t)i) & 63u) * 4u), (int)bytes);
-                word |= ((got >> (8u * (lane >> 4))) & 0xffu) << (8 * i);
-            }
-            *(uint32_t *)(o + wb + 4u * lane) = word;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; j++) if (p0 + 64u * j < a.n) o[p0 + 64u * j] = (uint8_t)(bytes >> (8 * j));
-        }
+        tile_store_u8(a.out + (size_t)f * n, tile, n, bytes, a.pass.vec != 0u);
     }
 }
 
 hipError_t launch_label_gather(const LabelGatherArgs &a, hipStream_t st)
 {
-    const uint32_t chunks = (a.F + a.frames_per_chunk - 1u) / a.frames_per_chunk;
-    hipLaunchKernelGGL(k_label_gather, dim3((a.n + 1023u) / 1024u, chunks), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_label_gather, pixel_grid(a.pass), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

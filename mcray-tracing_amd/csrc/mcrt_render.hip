@@ -1,7 +1,7 @@
 // mcrt_render.hip -- volume rendering (mcrt_render_frames; contract in include/mcrt.h): k_render, a block of voxels [nw][nv][nu] seen from a
 // direction -- one orthographic ray per pixel, n_steps trilinear samples along it, folded into the maximum, the mean or a front-to-back
 // composited surface.  The reference has one plane and no counterpart.
-#include "mcrt_device.h"
+#include "mcrt_pixels.h"
 
 namespace mcrt {
 
@@ -84,7 +84,7 @@ __global__ void __launch_bounds__(256) k_render(RenderArgs a)
     const float out = mode == MCRT_RENDER_MIP ? m : mode == MCRT_RENDER_MEAN ? (cnt ? sum / (float)cnt : 0.0f) : C;
     const size_t o = ((size_t)f * a.ny + j) * a.nx + i;
     if (a.out) a.out[o] = out;
-    if (a.out8) a.out8[o] = (uint8_t)(fminf(fmaxf(out, 0.0f), 1.0f) * 255.0f + 0.5f);
+    if (a.out8) a.out8[o] = quantise(fminf(fmaxf(out, 0.0f), 1.0f));
     if (a.depth) a.depth[o] = mode == MCRT_RENDER_MEAN ? -1.0f : depth;
 }
 

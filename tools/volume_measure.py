@@ -6,8 +6,9 @@ this library and on the parent commit's (MCRT_LIB) to show that they did not mov
     rocprofv3 --kernel-trace --stats -d DIR -o volume -- python tools/volume_measure.py run LEG
     python tools/volume_measure.py summarise LEG DIR/.../volume_kernel_trace.csv profiles/volume/LEG.csv
 
-LEG: volume_f1, volume_f4 (a 160 x 200 x 96 volume), cplane_f20, cplane_f128 (a 400 x 500 C-plane), existing (k_remap and k_compound as
-tools/compound_measure.py runs them at F = 20 and 128, N = 3).  The summary takes the kernels of the trace in launch order and the median
+LEG: volume_f1, volume_f4 (a 160 x 200 x 96 volume), cplane_f20, cplane_f128 (a 400 x 500 C-plane), label_f20, label_f128 (k_label_gather:
+the same C-plane gathered from a byte stack of the same shape), existing (k_remap and k_compound as tools/compound_measure.py runs them at
+F = 20 and 128, N = 3).  The summary takes the kernels of the trace in launch order and the median
 over the last 30 of each family's 33."""
 import csv
 import os
@@ -19,10 +20,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 E, R, K = 128, 465, 32
 STEP, PIVOT = 0.02, 10.0                      # 32 planes over 0.62 rad about a pivot 20 mm behind the apex
 CALLS, WARM = 33, 3
-LEGS = {"volume_f1": ("volume", 1), "volume_f4": ("volume", 4), "cplane_f20": ("cplane", 20), "cplane_f128": ("cplane", 128), "existing": ("existing", 0)}
+LEGS = {"volume_f1": ("volume", 1), "volume_f4": ("volume", 4), "cplane_f20": ("cplane", 20), "cplane_f128": ("cplane", 128), "label_f20": ("label", 20), "label_f128": ("label", 128),
+        "existing": ("existing", 0)}
 FAMILIES = {"volume": [("k_volume float", lambda k: "k_volume<false" in k), ("k_volume 8-bit", lambda k: "k_volume<true" in k), ("k_remap, same pixels", lambda k: "k_remap(" in k)],
             "existing": [("k_remap F=20x3", None), ("k_compound float F=20 N=3", None), ("k_remap F=128x3", None), ("k_compound float F=128 N=3", None)]}
 FAMILIES["cplane"] = FAMILIES["volume"]
+FAMILIES["label"] = [("k_label_gather", lambda k: "k_label_gather(" in k)]
 
 
 def grid_of(m, what):
@@ -50,8 +53,19 @@ def run(leg):
             ctx.free(src); ctx.free(pic)
         ctx.close()
         return
-    g = grid_of(m, what)
+    g = grid_of(m, "cplane" if what == "label" else what)
     n = g.nu * g.nv * g.nw
+    if what == "label":
+        src = ctx.alloc(F * K * E * R)
+        ctx.h2d(src, rng.integers(0, 200, F * K * E * R).astype(np.uint8))
+        out = ctx.alloc(F * n)
+        ctx.synchronize()
+        for _ in range(CALLS):
+            ctx.label_volume_frames(src, F, E, R, (K, STEP, PIVOT), g, out)
+        ctx.synchronize()
+        ctx.free(src); ctx.free(out)
+        ctx.close()
+        return
     maps = m.host_volume_maps(E, R, (K, STEP, PIVOT), g)
     inside = np.mean((maps[0] >= 0) & (maps[0] < K - 1) & (maps[1] >= 0) & (maps[1] < R - 1) & (maps[2] >= 0) & (maps[2] < E - 1))
     print("%s: %d points, %.3f of them with all eight taps inside" % (leg, n, inside))
@@ -89,10 +103,11 @@ def summarise(leg, trace_csv, out_csv):
             d = us([r for r in rows if match(r["Kernel_Name"])])
             assert len(d) == CALLS, (name, len(d))
             table.append((name, float(np.median(d[WARM:]))))
-    with open(out_csv, "w") as f:
-        f.write("leg,kernel,median_us\n")
+    with open(out_csv, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["leg", "kernel", "median_us"])
         for name, t in table:
-            f.write("%s,%s,%.2f\n" % (leg, name, t))
+            w.writerow([leg, name, "%.2f" % t])
     for name, t in table:
         print("%-12s %-28s %10.2f us" % (leg, name, t))
 
