@@ -50,7 +50,9 @@ extern "C" {
                                    + mcrt_speckle_opts, mcrt_default_speckle_opts, mcrt_speckle_tables, mcrt_speckle_frames
                                    (speckle reduction: speckle-reducing anisotropic diffusion over a stack of float frames; additive);
                                    + mcrt_recon_opts, mcrt_default_recon_opts, mcrt_recon_transform, mcrt_recon_frames
-                                   (freehand 3-D reconstruction: tracked frames binned into voxels by their poses, with hole filling; additive) */
+                                   (freehand 3-D reconstruction: tracked frames binned into voxels by their poses, with hole filling; additive);
+                                   + mcrt_recon_label_opts, mcrt_default_recon_label_opts, mcrt_recon_label_frames, mcrt_render_label_frames
+                                   (3-D ground truth: a freehand label volume by majority vote, the label of what a rendering shows; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -811,6 +813,64 @@ int mcrt_label_scan_convert_frames(mcrt_ctx *ctx, const uint8_t *tissue_dev /* [
 int mcrt_label_volume_frames(mcrt_ctx *ctx, const uint8_t *tissue_dev /* [n_frames][K][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
                              double radius_mm, double total_angle_rad, const mcrt_sweep *sweep, const mcrt_volume_grid *grid,
                              uint8_t *out_dev /* [n_frames][nw][nv][nu] */);
+
+/* Labels in 3-D, I: a freehand label volume -- the ground truth of mcrt_recon_frames' voxels -- by MAJORITY VOTE.  The input is the tissue
+ * stack uint8 [F][E][R] that mcrt_label_frames wrote for the pose tables [F][E][3], those tables, and row_mm, unit_mm and the WORLD-frame
+ * grid exactly as mcrt_recon_frames takes them.  The position of sample (f, e, r) is mcrt_recon_frames' contract word for word: t, P_k, x_c,
+ * i_c = floorf(x_c + 0.5f) and `inside`, with A and b from mcrt_recon_transform and row_u = (float)(row_mm / unit_mm).
+ * The vote, per sample with label l = stack[f][e][r]:
+ *   if !inside: stats[0]++          else if l >= n_labels: stats[1]++     (MCRT_LABEL_NONE and anything else out of range)
+ *   else: votes[voxel][l]++
+ * Resolve: count = the sum of votes[voxel][l] over l.  A voxel with count > 0 gets the label with the most votes, on a tie the SMALLEST such
+ * label; votes_dev gets the winner's votes (the purity of a voxel is votes / count), count_dev gets count.
+ * Hole filling, for a voxel with count == 0 when fill_radius H > 0 -- the structure of mcrt_recon_frames' rule:
+ *   for h = 1..H:
+ *       tally[l] = 0 for every l;  n = 0
+ *       over the cube [-h, h]^3: every neighbour inside the block with count > 0 adds ONE to tally[its winning label];  n++
+ *       if n >= fill_min: label = the label of the largest tally, on a tie the smallest;  stop
+ *   if no h succeeded (or H == 0): MCRT_LABEL_NONE
+ * A filled hole keeps count = 0 and votes = 0.  Only sampled voxels are read, never filled ones, and every sum is an integer: neither the
+ * order in which the device adds nor its tiling shows in the result.  Every voxel of every requested output is written.
+ * What follows: where every float sample is usable (mcrt_recon_frames) and every label is below n_labels, count_dev equals
+ * mcrt_recon_frames' count_dev for the same poses and grid, and a voxel is MCRT_LABEL_NONE exactly where the float volume is `empty` -- the
+ * defaults of fill_radius and fill_min are mcrt_recon_opts' own on purpose, so that the two volumes fill the same holes. */
+typedef struct { uint32_t n_labels;    /* 1..254: labels at or above it do not vote; the scene's material count   (no default) */
+                 uint32_t fill_radius; /* H, 0..3: 0 = no hole filling                                             (1)          */
+                 uint32_t fill_min;    /* >= 1: sampled neighbours a hole needs                                    (1)          */
+} mcrt_recon_label_opts;               /* 12 bytes: n_labels 0, fill_radius 4, fill_min 8 */
+/* n_labels as given, the defaults above; host only.  MCRT_ERR_INVALID for a null o */
+int mcrt_default_recon_label_opts(mcrt_recon_label_opts *o, uint32_t n_labels);
+/* The rule above.  stack_dev: device uint8 [F][E][R]; pos, dir: [F][E][3], host or device, with the lifetime rule of
+ * mcrt_trace_frames_poses.  Outputs, each a device pointer or NULL, at least one given: out_dev uint8 [nw][nv][nu]; count_dev and votes_dev
+ * uint32 of the same shape; stats_dev uint32 [2].  Asynchronous on the context's stream: a clear of the vote table, k_recon_label_splat,
+ * k_recon_label_resolve.  The vote table (n_labels * nu*nv*nw * 4 bytes) is a scratch buffer of the context that grows to the largest call:
+ * nothing is allocated on a repeat.  Everything is checked before anything is enqueued.  MCRT_ERR_INVALID, the message naming the field: a
+ * null ctx, stack_dev, pos, dir, grid or o (n_labels has no default); all four outputs NULL; a zero n_frames, n_elements or n_rows; row_mm or
+ * unit_mm not finite or not > 0; n_labels outside 1..254, a fill_radius above 3, a fill_min of 0; a grid that mcrt_recon_transform refuses;
+ * an output that overlaps the stack or another output.  MCRT_ERR_LIMIT: those of mcrt_recon_frames (n_rows > 2048, n_frames > 65535,
+ * F*E*R >= 2^31, nu*nv*nw >= 2^31, the thin-block tile limit), and nu*nv*nw * n_labels >= 2^31.  On any error nothing is written.
+ * Groups: call it on mcrt_group_root(), with the labels taken on mcrt_group_member(grp, 0) as above. */
+int mcrt_recon_label_frames(mcrt_ctx *ctx, const uint8_t *stack_dev /* [F][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
+                            const float *pos /* [F][E][3] host or device */, const float *dir /* same */, double row_mm, double unit_mm,
+                            const mcrt_volume_grid *grid /* WORLD frame, mm */, const mcrt_recon_label_opts *o,
+                            uint8_t *out_dev /* [nw][nv][nu] or NULL */, uint32_t *count_dev /* same or NULL */, uint32_t *votes_dev /* same or NULL */,
+                            uint32_t *stats_dev /* [2] or NULL */);
+/* Labels in 3-D, II: the label of what a rendering shows.  label_dev is a label block uint8 [n_frames][nw][nv][nu] -- what
+ * mcrt_label_volume_frames wrote for a swept volume, or mcrt_recon_label_frames for a freehand one --, view the mcrt_render_view of the
+ * rendering and depth_dev the [n_frames][ny][nx] that mcrt_render_frames wrote with it (MIP: the step of the maximum; SURFACE: the step at
+ * which the transmittance fell to a half; MEAN: -1, nothing is "seen").  Per frame and pixel (i, j), in float, one rounding per operation,
+ * no fma:
+ *   s = depth;   if !(s >= 0 && s < (float)n_steps): out = MCRT_LABEL_NONE                          (a NaN too)
+ *   p_c = ((origin_c + (float)i * di_c) + (float)j * dj_c) + s * ds_c            c = u, v, w
+ *         (mcrt_render_frames' own expression: for the s it wrote, p is bit for bit the point it sampled at that step)
+ *   f = floorf(p_c);  a = p_c - f;  k_c = f + (a >= 0.5f ? 1 : 0)                (the nearest rule of the label gathers)
+ *   out = 0 <= k_c < n_c for every c (compared in float) ? label[frame][k_w][k_v][k_u] : MCRT_LABEL_NONE
+ * Every output pixel is written.  Asynchronous on the context's stream, one launch; allocates nothing and uploads nothing.  Errors and limits
+ * are mcrt_render_frames' for the block and the view (null ctx / label_dev / view / depth_dev / out_dev, zero sizes, a view entry that is not
+ * finite: MCRT_ERR_INVALID; n_steps outside 1..4096, nu, nv or nw >= 2^24, nu*nv*nw or nx*ny >= 2^31, n_frames > 65535: MCRT_ERR_LIMIT), and
+ * MCRT_ERR_INVALID for an out_dev that overlaps label_dev or depth_dev.  On an error nothing is launched.  Groups: call it on mcrt_group_root(). */
+int mcrt_render_label_frames(mcrt_ctx *ctx, const uint8_t *label_dev /* [n_frames][nw][nv][nu] */, uint32_t n_frames, uint32_t nu, uint32_t nv, uint32_t nw,
+                             const mcrt_render_view *view, const float *depth_dev /* [n_frames][ny][nx] */, uint8_t *out_dev /* [n_frames][ny][nx] */);
 
 /* device [E][R]  ->  host [R][E] row-major (the cv::Mat layout of rfimage.h:217); synchronous */
 int mcrt_export_rf(mcrt_ctx *ctx, const float *rf_dev, uint32_t n_elements, uint32_t n_rows, float *host_rows_by_cols);

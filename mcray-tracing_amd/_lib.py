@@ -106,6 +106,11 @@ class ReconOpts(C.Structure):
     _fields_ = [("mode", C.c_uint32), ("value_max", C.c_float), ("fill_radius", C.c_uint32), ("fill_min", C.c_uint32), ("empty", C.c_float)]
 
 
+class ReconLabelOpts(C.Structure):
+    """mcrt_recon_label_opts (include/mcrt.h): 12 bytes"""
+    _fields_ = [("n_labels", C.c_uint32), ("fill_radius", C.c_uint32), ("fill_min", C.c_uint32)]
+
+
 NODE_DTYPE = np.dtype([("lo0", "<f4", 3), ("c0", "<i4"), ("hi0", "<f4", 3), ("c1", "<i4"),
                        ("lo1", "<f4", 3), ("pad0", "<u4"), ("hi1", "<f4", 3), ("pad1", "<u4")])
 SEGMENT_DTYPE = np.dtype([("from", "<f4", 3), ("to", "<f4", 3), ("dir", "<f4", 3),
@@ -113,6 +118,7 @@ SEGMENT_DTYPE = np.dtype([("from", "<f4", 3), ("to", "<f4", 3), ("dir", "<f4", 3
                           ("distance_traveled", "<f8"), ("media", "<i4"), ("tri", "<i4")])
 assert NODE_DTYPE.itemsize == 64 and SEGMENT_DTYPE.itemsize == 64 and C.sizeof(BvhNode) == 64 and C.sizeof(BmodeParams) == 48 and C.sizeof(Focus) == 40 and C.sizeof(Compound) == 68 and C.sizeof(CompoundOpts) == 72
 assert C.sizeof(Sweep) == 12 and C.sizeof(VolumeGrid) == 112 and C.sizeof(LabelOpts) == 8 and C.sizeof(RenderView) == 64 and C.sizeof(RenderOpts) == 32 and C.sizeof(SpeckleOpts) == 16 and C.sizeof(ReconOpts) == 20
+assert C.sizeof(ReconLabelOpts) == 12
 
 # every symbol include/mcrt.h declares (tests/test_abi.py checks the .so exports each one)
 SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create", "mcrt_destroy", "mcrt_set_stream",
@@ -131,7 +137,8 @@ SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create"
            "mcrt_default_label_opts", "mcrt_label_frames", "mcrt_label_scan_convert_frames", "mcrt_label_volume_frames",
            "mcrt_default_render_opts", "mcrt_render_view_for_grid", "mcrt_render_frames",
            "mcrt_default_speckle_opts", "mcrt_speckle_tables", "mcrt_speckle_frames",
-           "mcrt_default_recon_opts", "mcrt_recon_transform", "mcrt_recon_frames"]
+           "mcrt_default_recon_opts", "mcrt_recon_transform", "mcrt_recon_frames",
+           "mcrt_default_recon_label_opts", "mcrt_recon_label_frames", "mcrt_render_label_frames"]
 
 
 def build_library(force=False):
@@ -206,6 +213,9 @@ def load_library():
         "mcrt_default_recon_opts": [C.POINTER(ReconOpts)],
         "mcrt_recon_transform": [C.POINTER(VolumeGrid), C.c_double, vp, vp],
         "mcrt_recon_frames": [vp, vp, u32, u32, u32, vp, vp, C.c_double, C.c_double, C.POINTER(VolumeGrid), C.POINTER(ReconOpts), vp, vp, vp],
+        "mcrt_default_recon_label_opts": [C.POINTER(ReconLabelOpts), u32],
+        "mcrt_recon_label_frames": [vp, vp, u32, u32, u32, vp, vp, C.c_double, C.c_double, C.POINTER(VolumeGrid), C.POINTER(ReconLabelOpts), vp, vp, vp, vp],
+        "mcrt_render_label_frames": [vp, vp, u32, u32, u32, u32, C.POINTER(RenderView), vp, vp],
         "mcrt_debug_math": [vp, i32, vp, vp, vp, u32], "mcrt_debug_philox": [vp, vp, vp, vp], "mcrt_debug_stamps": [vp, vp, i32], "mcrt_debug_tail_histograms": [vp, vp, i32], "mcrt_debug_set_error": [vp, u32], "mcrt_debug_fast_paths": [vp, vp],
         "mcrt_scan_maps": [u32, u32, C.c_double, C.c_double, u32, u32, u32, u32, vp, vp],
         "mcrt_group_create": [vp, u32, C.POINTER(vp)], "mcrt_group_destroy": [vp], "mcrt_group_size": [vp], "mcrt_group_root": [vp], "mcrt_group_member": [vp, u32],

@@ -11,7 +11,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, RenderView, RenderOpts, SpeckleOpts, ReconOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, RenderView, RenderOpts, SpeckleOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 DEFAULT_ANGLE = 1.0471975511965976      # the sector of main.cpp:28: 60 degrees [rad]
 
@@ -329,6 +329,17 @@ def recon_opts_struct(mode=None, value_max=None, fill_radius=None, fill_min=None
     for name, val, kind in (("value_max", value_max, float), ("fill_radius", fill_radius, int), ("fill_min", fill_min, int), ("empty", empty, float)):
         if val is not None:
             setattr(o, name, kind(val))
+    return o
+
+
+def recon_label_opts_struct(n_labels, fill_radius=None, fill_min=None):
+    """mcrt_recon_label_opts from keywords over mcrt_default_recon_label_opts: n_labels (1..254, the scene's material count: it has no
+    default), fill_radius (0..3), fill_min"""
+    o = ReconLabelOpts()
+    check(load_library().mcrt_default_recon_label_opts(C.byref(o), int(n_labels)))
+    for name, val in (("fill_radius", fill_radius), ("fill_min", fill_min)):
+        if val is not None:
+            setattr(o, name, int(val))
     return o
 
 
@@ -792,6 +803,25 @@ class Context(_SceneCalls):
         check(self.L.mcrt_recon_frames(self.h, ptr(stack_dev), n_frames, n_elements, n_rows, ptr(pos), ptr(dirs), float(row_mm), float(unit_mm), C.byref(grid),
                                        C.byref(o), ptr(out_dev), ptr(count_dev), ptr(stats_dev)))
 
+    def recon_label_frames(self, tissue_dev, pos, dirs, n_frames, n_elements, n_rows, grid, n_labels, out_dev=None, count_dev=None, votes_dev=None,
+                           stats_dev=None, row_mm=None, unit_mm=10.0, **opts):
+        """mcrt_recon_label_frames: the tissue stack uint8 [n_frames][n_elements][n_rows] that label_frames wrote for the pose tables pos / dirs
+        voted into grid's voxels (a VolumeGrid in the WORLD frame, mm) -> out_dev uint8 [nw][nv][nu] (the label with the most votes, holes
+        filled from their sampled neighbours, LABEL_NONE where nothing is near), count_dev uint32 the same (votes per voxel), votes_dev uint32
+        the same (the winner's), stats_dev uint32 [2]; at least one of them.  row_mm None: as recon_frames.  opts: fill_radius, fill_min"""
+        o = recon_label_opts_struct(n_labels, **opts)
+        if row_mm is None:
+            row_mm = _depth_mm_f(self.params.depth_cm, self.params.speed_of_sound) / n_rows
+        pos, dirs, n_frames = _pose_tables("recon_label_frames", pos, dirs, n_frames, n_elements)
+        check(self.L.mcrt_recon_label_frames(self.h, ptr(tissue_dev), n_frames, n_elements, n_rows, ptr(pos), ptr(dirs), float(row_mm), float(unit_mm), C.byref(grid),
+                                             C.byref(o), ptr(out_dev), ptr(count_dev), ptr(votes_dev), ptr(stats_dev)))
+
+    def render_label_frames(self, label_dev, n_frames, shape, view, depth_dev, out_dev):
+        """mcrt_render_label_frames: the label blocks uint8 [n_frames][nw][nv][nu] (shape = (nw, nv, nu)) read where render_frames' depth_dev
+        [n_frames][ny][nx] says the rays of view saw something -> out_dev uint8 [n_frames][ny][nx], LABEL_NONE where nothing was seen"""
+        nw, nv, nu = shape
+        check(self.L.mcrt_render_label_frames(self.h, ptr(label_dev), n_frames, nu, nv, nw, C.byref(view), ptr(depth_dev), ptr(out_dev)))
+
     def label_frames(self, pos=None, dirs=None, *, rule="traced", start_offset=None, e_begin=0, e_end=None, n_frames=None, tissue_dev=None,
                      interface_dev=None, crossings_dev=None):
         """mcrt_label_frames: the central beam of every scan-line walked through the scene.  pos / dirs None: the context's transducer (one
@@ -976,6 +1006,7 @@ class Simulator:
         self.ctx.set_params(n_elements=E, n_samples=n_samples, frequency=transducer.frequency, seed=seed, max_depth=max_depth,
                             sanitize_tir=sanitize_tir, tex_n=tex_n, **({"n_rows": n_rows} if n_rows else {}))
         self.E, self.R, self.S = E, self.ctx.params.n_rows, n_samples
+        self.n_materials = int(scene_data.materials.shape[0])
         self.ctx.upload_scene(scene_data)
         self.ctx.upload_texture(texture, tex_n)
         self.ctx.set_transducer(transducer.pos, transducer.dir)
@@ -1088,11 +1119,15 @@ class Simulator:
             self.ctx.bmode_volume_frames(self.sweep_dev, 1, self.E, self.R, self.sweep, grid, out, **display)
             return self.ctx.d2h(out, shape, np.uint8)
 
-    def render(self, frame_id, grid, direction, up=(0, 0, 1), size=(500, 400), pixel_mm=0.25, step_mm=0.25, mode="surface", **opts):
+    def render(self, frame_id, grid, direction, up=(0, 0, 1), size=(500, 400), pixel_mm=0.25, step_mm=0.25, mode="surface", labels=False, label_rule="traced",
+               label_offset=None, **opts):
         """trace -> convolve -> envelope -> mcrt_bmode_volume_frames -> mcrt_render_frames -> host: grid's displayed voxels seen along
         `direction`, uint8 [ny][nx] with size = (nx, ny) (sweep= only).  opts: the display keywords of Context.bmode_volume_frames
         (dynamic_range_db, gain_db, ref, tgc_db, radius_mm, total_angle; bmode_mode for its grey curve) and the render keywords of
-        Context.render_frames (lo, hi, threshold, ramp, opacity, depth_cue, t_cut)"""
+        Context.render_frames (lo, hi, threshold, ramp, opacity, depth_cue, t_cut).
+        labels=True: (picture, labels) -- the tissue of what every pixel shows, uint8 [ny][nx]: the label block of label_volume() on the
+        same grid (label_rule, label_offset: its rule and start_offset) read through the depth buffer of the same render call; LABEL_NONE
+        where the ray saw nothing (every pixel of mode "mean") or saw it outside the sweep"""
         if self.sweep is None:
             raise RuntimeError("render() needs Simulator(sweep=...)")
         ropts = {k: opts.pop(k) for k in ("lo", "hi", "threshold", "ramp", "opacity", "depth_cue", "t_cut") if k in opts}
@@ -1103,8 +1138,16 @@ class Simulator:
         shape = (grid.nw, grid.nv, grid.nu)
         with self.ctx.temp(shape[0] * shape[1] * shape[2]) as vox, self.ctx.temp(size[0] * size[1]) as out:
             self.ctx.bmode_volume_frames(self.sweep_dev, 1, self.E, self.R, self.sweep, grid, vox, **opts)
-            self.ctx.render_frames(vox, 1, shape, view, out8_dev=out, in_u8=True, mode=mode, **ropts)
-            return self.ctx.d2h(out, (size[1], size[0]), np.uint8)
+            if not labels:
+                self.ctx.render_frames(vox, 1, shape, view, out8_dev=out, in_u8=True, mode=mode, **ropts)
+                return self.ctx.d2h(out, (size[1], size[0]), np.uint8)
+            geometry = {k: opts[k] for k in ("radius_mm", "total_angle") if k in opts}
+            with self.ctx.temp(size[0] * size[1] * 4) as depth, self._label_pass(label_rule, label_offset, want_rows=False) as (F, bufs):
+                self.ctx.render_frames(vox, 1, shape, view, out8_dev=out, depth_dev=depth, in_u8=True, mode=mode, **ropts)
+                picture = self.ctx.d2h(out, (size[1], size[0]), np.uint8)
+                self.ctx.label_volume_frames(bufs[0], 1, self.E, self.R, self.sweep, grid, vox, **geometry)      # (the voxels are rendered: the block is free)
+                self.ctx.render_label_frames(vox, 1, shape, view, depth, out)
+                return picture, self.ctx.d2h(out, (size[1], size[0]), np.uint8)
 
     def freehand(self, frame_id, pos, dirs, grid, convolve=True, envelope=True, counts=False, row_mm=None, unit_mm=10.0, **opts):
         """a freehand sweep and its volume: the F poses pos / dirs [F][E][3] (Transducer.poses) traced as one pose pass into a temporary stack
@@ -1131,6 +1174,26 @@ class Simulator:
             self.ctx.recon_frames(stack_dev, pos, dirs, F, self.E, self.R, grid, out, count_dev=cnt if counts else None, row_mm=row_mm, unit_mm=unit_mm, **opts)
             vox = self.ctx.d2h(out, shape, np.float32)
             return (vox, self.ctx.d2h(cnt, shape, np.uint32)) if counts else vox
+
+    def freehand_labels(self, pos, dirs, grid, rule="traced", start_offset=None, fill_radius=1, fill_min=1, counts=False, votes=False):
+        """the ground truth of freehand()'s volume: the label pass over the F poses pos / dirs [F][E][3] (mcrt_label_frames: the central beam
+        of every scan-line), then mcrt_recon_label_frames with the scene's material count as n_labels -> host: the tissue of every voxel of
+        grid, uint8 [nw][nv][nu] -- the label most of a voxel's samples carry, a hole filled from its sampled neighbours, LABEL_NONE where
+        nothing is near; with counts=True and / or votes=True a tuple (labels[, samples per voxel uint32][, the winner's votes uint32]).
+        Labels depend on neither seed nor frame: there is no frame_id.  row_mm and unit_mm are freehand()'s defaults, fill_radius and
+        fill_min its defaults too, so the two volumes fill the same holes.  It raises under compound=, sweep= or elevation= as freehand()
+        does, and mcrt_label_frames takes at most 1024 poses per pass."""
+        if self.steers is not None or self.sweep is not None or self.elevation:
+            raise RuntimeError("freehand_labels() does not combine with compound=, sweep= or elevation=")
+        pos, dirs, F = _pose_tables("freehand_labels", np.asarray(pos), np.asarray(dirs), None, self.E)
+        shape = (grid.nw, grid.nv, grid.nu)
+        n = shape[0] * shape[1] * shape[2]
+        with self.ctx.temp(F * self.E * self.R) as tissue, self.ctx.temp(n) as out, self.ctx.temp(n * 4) as cnt, self.ctx.temp(n * 4) as win:
+            self.ctx.label_frames(pos, dirs, rule=rule, start_offset=start_offset, tissue_dev=tissue)
+            self.ctx.recon_label_frames(tissue, pos, dirs, F, self.E, self.R, grid, self.n_materials, out, count_dev=cnt if counts else None,
+                                        votes_dev=win if votes else None, fill_radius=fill_radius, fill_min=fill_min)
+            got = (self.ctx.d2h(out, shape, np.uint8),) + ((self.ctx.d2h(cnt, shape, np.uint32),) if counts else ()) + ((self.ctx.d2h(win, shape, np.uint32),) if votes else ())
+            return got if len(got) > 1 else got[0]
 
     @contextlib.contextmanager
     def _label_pass(self, rule, start_offset, want_rows=True):

@@ -161,6 +161,8 @@ struct ImageStages {
     StagedTable lat_rows, elev_rows;
     // freehand reconstruction (mcrt_recon_frames): the accumulators of the largest grid so far, n sums (8 B each), then n counts (4 B each)
     Buf<unsigned long long> d_recon;
+    // freehand label reconstruction (mcrt_recon_label_frames): the vote table of the largest call so far, voxels x n_labels words
+    Buf<uint32_t> d_votes;
 };
 struct Instrumentation {
     Buf<unsigned long long> d_stats; bool stats_on = false;

@@ -753,6 +753,13 @@ extern "C" int mcrt_recon_transform(const mcrt_volume_grid *g, double unit_mm, f
     return MCRT_OK;
 }
 
+extern "C" int mcrt_default_recon_label_opts(mcrt_recon_label_opts *o, uint32_t n_labels)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_recon_label_opts: null options");
+    o->n_labels = n_labels; o->fill_radius = 1u; o->fill_min = 1u;       // (mcrt_default_recon_opts' own: the two volumes fill the same holes)
+    return MCRT_OK;
+}
+
 // ---- volume rendering (the contract is in include/mcrt.h) ---------------------------------------
 extern "C" int mcrt_default_render_opts(mcrt_render_opts *o, int in_u8)
 {

@@ -393,6 +393,26 @@ extern "C" int mcrt_bmode_volume_frames(mcrt_ctx *c, const float *rf_dev, uint32
 }
 
 // ---- volume rendering (the contract is in include/mcrt.h; the defaults and the view helper are host code: mcrt_host.cpp) ----
+// what mcrt_render_frames and mcrt_render_label_frames ask of the block and the view alike: the argument errors, then the limits
+static int render_view_invalid(const char *fn, uint32_t n_frames, uint32_t nu, uint32_t nv, uint32_t nw, const mcrt_render_view *view)
+{
+    if (n_frames == 0 || nu == 0 || nv == 0 || nw == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, block %u x %u x %u)", fn, n_frames, nu, nv, nw);
+    if (view->nx == 0 || view->ny == 0) return set_error(MCRT_ERR_INVALID, "%s: view: zero picture size (nx %u, ny %u)", fn, view->nx, view->ny);
+    for (int k = 0; k < 3; k++)
+        if (!(std::isfinite(view->origin[k]) && std::isfinite(view->di[k]) && std::isfinite(view->dj[k]) && std::isfinite(view->ds[k])))
+            return set_error(MCRT_ERR_INVALID, "%s: view: origin, di, dj or ds has an entry that is not finite (component %d)", fn, k);
+    return MCRT_OK;
+}
+static int render_view_limits(const char *fn, uint32_t n_frames, uint32_t nu, uint32_t nv, uint32_t nw, const mcrt_render_view *view)
+{
+    if (view->n_steps == 0 || view->n_steps > 4096u) return set_error(MCRT_ERR_LIMIT, "%s: view: n_steps must be 1..4096 (%u)", fn, view->n_steps);
+    if (nu >= (1u << 24) || nv >= (1u << 24) || nw >= (1u << 24)) return set_error(MCRT_ERR_LIMIT, "%s: nu, nv and nw must be below 2^24 (%u x %u x %u)", fn, nu, nv, nw);
+    if ((double)nu * (double)nv * (double)nw >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: 2^31 voxels or more (%u x %u x %u)", fn, nu, nv, nw);
+    if ((uint64_t)view->nx * view->ny >= 0x80000000ull) return set_error(MCRT_ERR_LIMIT, "%s: view: 2^31 pixels or more (%u x %u)", fn, view->nx, view->ny);
+    if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 frames per call (%u)", fn, n_frames);
+    return MCRT_OK;
+}
+
 // Everything is checked before anything is launched; the derived floats are made here, in double, rounded once.
 extern "C" int mcrt_render_frames(mcrt_ctx *c, const void *vol_dev, int in_u8, uint32_t n_frames, uint32_t nu, uint32_t nv, uint32_t nw,
                                   const mcrt_render_view *view, const mcrt_render_opts *o, float *out_dev, uint8_t *out8_dev, float *depth_dev)
@@ -401,11 +421,7 @@ extern "C" int mcrt_render_frames(mcrt_ctx *c, const void *vol_dev, int in_u8, u
     static const char fn[] = "mcrt_render_frames";
     if (!vol_dev || !view) return set_error(MCRT_ERR_INVALID, "%s: null %s", fn, vol_dev ? "view" : "vol_dev");
     if (!out_dev && !out8_dev && !depth_dev) return set_error(MCRT_ERR_INVALID, "%s: out_dev, out8_dev and depth_dev are all null", fn);
-    if (n_frames == 0 || nu == 0 || nv == 0 || nw == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, block %u x %u x %u)", fn, n_frames, nu, nv, nw);
-    if (view->nx == 0 || view->ny == 0) return set_error(MCRT_ERR_INVALID, "%s: view: zero picture size (nx %u, ny %u)", fn, view->nx, view->ny);
-    for (int k = 0; k < 3; k++)
-        if (!(std::isfinite(view->origin[k]) && std::isfinite(view->di[k]) && std::isfinite(view->dj[k]) && std::isfinite(view->ds[k])))
-            return set_error(MCRT_ERR_INVALID, "%s: view: origin, di, dj or ds has an entry that is not finite (component %d)", fn, k);
+    MCRT_TRY(render_view_invalid(fn, n_frames, nu, nv, nw, view));
     mcrt_render_opts d;
     if (!o) { mcrt_default_render_opts(&d, in_u8); o = &d; }
     if (o->mode != MCRT_RENDER_MIP && o->mode != MCRT_RENDER_MEAN && o->mode != MCRT_RENDER_SURFACE) return set_error(MCRT_ERR_INVALID, "%s: unknown mode %u", fn, o->mode);
@@ -418,11 +434,7 @@ extern "C" int mcrt_render_frames(mcrt_ctx *c, const void *vol_dev, int in_u8, u
     if (!(o->opacity > 0.0f && o->opacity <= 1.0f)) return set_error(MCRT_ERR_INVALID, "%s: opacity must be in (0,1] (%g)", fn, (double)o->opacity);
     if (!(o->depth_cue >= 0.0f && o->depth_cue <= 1.0f)) return set_error(MCRT_ERR_INVALID, "%s: depth_cue must be in [0,1] (%g)", fn, (double)o->depth_cue);
     if (!(o->t_cut >= 0.0f && o->t_cut < 1.0f)) return set_error(MCRT_ERR_INVALID, "%s: t_cut must be in [0,1) (%g)", fn, (double)o->t_cut);
-    if (view->n_steps == 0 || view->n_steps > 4096u) return set_error(MCRT_ERR_LIMIT, "%s: view: n_steps must be 1..4096 (%u)", fn, view->n_steps);
-    if (nu >= (1u << 24) || nv >= (1u << 24) || nw >= (1u << 24)) return set_error(MCRT_ERR_LIMIT, "%s: nu, nv and nw must be below 2^24 (%u x %u x %u)", fn, nu, nv, nw);
-    if ((double)nu * (double)nv * (double)nw >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: 2^31 voxels or more (%u x %u x %u)", fn, nu, nv, nw);
-    if ((uint64_t)view->nx * view->ny >= 0x80000000ull) return set_error(MCRT_ERR_LIMIT, "%s: view: 2^31 pixels or more (%u x %u)", fn, view->nx, view->ny);
-    if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 frames per call (%u)", fn, n_frames);
+    MCRT_TRY(render_view_limits(fn, n_frames, nu, nv, nw, view));
     const size_t nvox = (size_t)nu * nv * nw, npix = (size_t)view->nx * view->ny, vol_bytes = (in_u8 ? 1u : 4u) * (size_t)n_frames * nvox;
     const struct { const void *p; size_t bytes; const char *name; } outs[3] = { { out_dev, 4 * n_frames * npix, "out_dev" }, { out8_dev, n_frames * npix, "out8_dev" },
                                                                                { depth_dev, 4 * n_frames * npix, "depth_dev" } };
@@ -437,6 +449,27 @@ extern "C" int mcrt_render_frames(mcrt_ctx *c, const void *vol_dev, int in_u8, u
     a.threshold = o->threshold; a.inv_ramp = inv_ramp; a.opacity = o->opacity; a.depth_cue = o->depth_cue; a.t_cut = o->t_cut;
     a.inv_steps = view->n_steps > 1u ? (float)(1.0 / (double)(view->n_steps - 1u)) : 0.0f;
     HIP_TRY(mcrt::launch_render(a, in_u8 != 0, c->stream));
+    return MCRT_OK;
+}
+
+// the label of what a rendering shows (the contract is in include/mcrt.h): one launch, nothing allocated or uploaded
+extern "C" int mcrt_render_label_frames(mcrt_ctx *c, const uint8_t *label_dev, uint32_t n_frames, uint32_t nu, uint32_t nv, uint32_t nw, const mcrt_render_view *view,
+                                        const float *depth_dev, uint8_t *out_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_render_label_frames";
+    if (!label_dev || !view || !depth_dev || !out_dev)
+        return set_error(MCRT_ERR_INVALID, "%s: null %s", fn, !label_dev ? "label_dev" : !view ? "view" : !depth_dev ? "depth_dev" : "out_dev");
+    MCRT_TRY(render_view_invalid(fn, n_frames, nu, nv, nw, view));
+    MCRT_TRY(render_view_limits(fn, n_frames, nu, nv, nw, view));
+    const size_t nvox = (size_t)nu * nv * nw, npix = (size_t)view->nx * view->ny;
+    if (ranges_overlap(label_dev, n_frames * nvox, out_dev, n_frames * npix)) return set_error(MCRT_ERR_INVALID, "%s: label_dev and out_dev overlap", fn);
+    if (ranges_overlap(depth_dev, 4 * n_frames * npix, out_dev, n_frames * npix)) return set_error(MCRT_ERR_INVALID, "%s: depth_dev and out_dev overlap", fn);
+    mcrt::RenderLabelArgs a;
+    a.labels = label_dev; a.depth = depth_dev; a.out = out_dev;
+    for (int k = 0; k < 3; k++) { a.origin[k] = view->origin[k]; a.di[k] = view->di[k]; a.dj[k] = view->dj[k]; a.ds[k] = view->ds[k]; }
+    a.nx = view->nx; a.ny = view->ny; a.n_steps = view->n_steps; a.F = n_frames; a.nu = nu; a.nv = nv; a.nw = nw;
+    HIP_TRY(mcrt::launch_render_label(a, c->stream));
     return MCRT_OK;
 }
 
@@ -549,6 +582,69 @@ extern "C" int mcrt_recon_frames(mcrt_ctx *c, const float *stack_dev, uint32_t n
     if (stats_dev) HIP_TRY(hipMemsetAsync(stats_dev, 0, 8, c->stream));
     HIP_TRY(mcrt::launch_recon_splat(a, c->stream));
     HIP_TRY(mcrt::launch_recon_resolve(a, c->stream));
+    return MCRT_OK;
+}
+
+// a freehand label volume by majority vote (the contract is in include/mcrt.h): mcrt_recon_frames' checks with the tissue stack in the float
+// stack's place; then the pose staging, one clear of the vote table (and of stats_dev), k_recon_label_splat, k_recon_label_resolve
+extern "C" int mcrt_recon_label_frames(mcrt_ctx *c, const uint8_t *stack_dev, uint32_t n_frames, uint32_t E, uint32_t R, const float *pos, const float *dir,
+                                       double row_mm, double unit_mm, const mcrt_volume_grid *g, const mcrt_recon_label_opts *o, uint8_t *out_dev,
+                                       uint32_t *count_dev, uint32_t *votes_dev, uint32_t *stats_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_recon_label_frames";
+    if (!stack_dev || !pos || !dir || !g || !o)
+        return set_error(MCRT_ERR_INVALID, "%s: null %s", fn, !stack_dev ? "stack_dev" : !pos ? "pos" : !dir ? "dir" : !g ? "grid" : "options");
+    if (!out_dev && !count_dev && !votes_dev && !stats_dev) return set_error(MCRT_ERR_INVALID, "%s: out_dev, count_dev, votes_dev and stats_dev are all null", fn);
+    if (n_frames == 0 || E == 0 || R == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, n_elements %u, n_rows %u)", fn, n_frames, E, R);
+    if (!(std::isfinite(row_mm) && row_mm > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: row_mm must be finite and > 0 (%g)", fn, row_mm);
+    if (!(std::isfinite(unit_mm) && unit_mm > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: unit_mm must be finite and > 0 (%g)", fn, unit_mm);
+    if (o->n_labels == 0u || o->n_labels > 254u) return set_error(MCRT_ERR_INVALID, "%s: n_labels must be 1..254 (%u)", fn, o->n_labels);
+    if (o->fill_radius > RECON_MAX_FILL) return set_error(MCRT_ERR_INVALID, "%s: fill_radius must be 0..%d (%u)", fn, RECON_MAX_FILL, o->fill_radius);
+    if (o->fill_min == 0u) return set_error(MCRT_ERR_INVALID, "%s: fill_min must be >= 1", fn);
+    mcrt::ReconLabelArgs a;
+    memset(&a, 0, sizeof a);
+    MCRT_TRY(mcrt_recon_transform(g, unit_mm, a.A, a.b));
+    a.row_u = (float)(row_mm / unit_mm);
+    if (!std::isfinite(a.row_u)) return set_error(MCRT_ERR_INVALID, "%s: row_mm / unit_mm is not finite (%g)", fn, (double)a.row_u);
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: at most %d rows (%u)", fn, MCRT_MAX_ROWS, R);
+    if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 frames per call (%u)", fn, n_frames);
+    if ((double)n_frames * (double)E * (double)R >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: a stack of 2^31 samples or more (%u x %u x %u)", fn, n_frames, E, R);
+    if ((double)g->nu * (double)g->nv * (double)g->nw >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: grid: 2^31 voxels or more (%u x %u x %u)", fn, g->nu, g->nv, g->nw);
+    const uint64_t tiles = (uint64_t)((g->nu + RECON_TU - 1u) / RECON_TU) * ((g->nv + RECON_TV - 1u) / RECON_TV) * ((g->nw + RECON_TW - 1u) / RECON_TW);
+    if (tiles >= RECON_MAX_TILES)
+        return set_error(MCRT_ERR_LIMIT, "%s: grid: 2^24 tiles of %d x %d x %d voxels or more (%u x %u x %u): too thin a block", fn, RECON_TU, RECON_TV, RECON_TW, g->nu, g->nv, g->nw);
+    const size_t ns = (size_t)n_frames * E * R, n = (size_t)g->nu * g->nv * g->nw, lines = (size_t)n_frames * E, words = n * o->n_labels;
+    if (words >= 0x80000000ull) return set_error(MCRT_ERR_LIMIT, "%s: a vote table of 2^31 words or more (%u x %u x %u voxels x %u labels)", fn, g->nu, g->nv, g->nw, o->n_labels);
+    const struct { const void *p; size_t bytes; const char *name; } outs[4] = { { out_dev, n, "out_dev" }, { count_dev, 4 * n, "count_dev" }, { votes_dev, 4 * n, "votes_dev" },
+                                                                               { stats_dev, 8, "stats_dev" } };
+    for (int i = 0; i < 4; i++) {
+        if (!outs[i].p) continue;
+        if (ranges_overlap(stack_dev, ns, outs[i].p, outs[i].bytes)) return set_error(MCRT_ERR_INVALID, "%s: stack_dev and %s overlap", fn, outs[i].name);
+        for (int j = 0; j < i; j++)
+            if (outs[j].p && ranges_overlap(outs[j].p, outs[j].bytes, outs[i].p, outs[i].bytes)) return set_error(MCRT_ERR_INVALID, "%s: %s and %s overlap", fn, outs[j].name, outs[i].name);
+    }
+    if (words > c->img.d_votes.cap) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(c->img.d_votes.alloc(words));
+    }
+    const float *tab[2] = { pos, dir };
+    for (int k = 0; k < 2; k++) {
+        if (is_device_pointer(tab[k])) continue;
+        float *h = nullptr;
+        MCRT_TRY(c->pose_stage[k].begin(3 * lines, c->stream, &h));
+        memcpy(h, tab[k], 12 * lines);
+        MCRT_TRY(c->pose_stage[k].commit(3 * lines, c->stream));
+        tab[k] = c->pose_stage[k].dev;
+    }
+    a.stack = stack_dev; a.pos = tab[0]; a.dir = tab[1]; a.votes = c->img.d_votes;
+    a.out = out_dev; a.count_out = count_dev; a.votes_out = votes_dev; a.stats = stats_dev;
+    a.R = R; a.n_samples = (uint32_t)ns; a.nu = g->nu; a.nv = g->nv; a.nw = g->nw; a.n_vox = (uint32_t)n;
+    a.n_labels = o->n_labels; a.fill_radius = o->fill_radius; a.fill_min = o->fill_min;
+    HIP_TRY(hipMemsetAsync(c->img.d_votes, 0, 4 * words, c->stream));
+    if (stats_dev) HIP_TRY(hipMemsetAsync(stats_dev, 0, 8, c->stream));
+    HIP_TRY(mcrt::launch_recon_label_splat(a, c->stream));
+    if (out_dev || count_dev || votes_dev) HIP_TRY(mcrt::launch_recon_label_resolve(a, c->stream));
     return MCRT_OK;
 }
 

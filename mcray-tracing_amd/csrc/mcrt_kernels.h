@@ -15,6 +15,8 @@
 //   mcrt_speckle.hip k_srad (speckle reduction: mcrt_speckle_frames)
 //   mcrt_recon.hip   k_recon_splat, k_recon_resolve (freehand 3-D reconstruction: mcrt_recon_frames)
 //   mcrt_label.hip   k_label (ground-truth label maps: mcrt_label_frames), k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames)
+//   mcrt_label3d.hip k_recon_label_splat, k_recon_label_resolve (a freehand label volume by majority vote: mcrt_recon_label_frames),
+//                    k_render_label (the label of what a rendering shows: mcrt_render_label_frames)
 //   mcrt_scene.hip   k_tris_by_id, k_expand_tris; the probes k_math_probe, k_verify_div, k_philox_probe
 //   mcrt_lbvh.hip    the device BVH builder (mcrt_lbvh.h)
 // Shared device code: mcrt_device.h (primitives and the knobs more than one unit reads), mcrt_walk.h (the lane walk's steps, also k_path's),
@@ -194,6 +196,32 @@ struct LabelGatherArgs {
     PixelPass pass;
 };
 
+// k_recon_label_splat and k_recon_label_resolve (mcrt_recon_label_frames): the tissue stack [F][E][R] voted into a table of n_vox * n_labels
+// words, then the winners resolved and the holes filled into out [nw][nv][nu]; the tile and the limits are k_recon_resolve's (RECON_*)
+struct ReconLabelArgs {
+    const uint8_t *stack;               // [F][E][R]
+    const float *pos, *dir;             // [F][E][3]
+    uint32_t *votes;                    // [n_vox][n_labels], cleared before the splat
+    uint8_t *out;                       // [nw][nv][nu] or null
+    uint32_t *count_out, *votes_out;    // same, or null: the votes of a voxel, the winner's votes
+    uint32_t *stats;                    // [2] or null: samples outside the block, samples inside it whose label is >= n_labels
+    uint32_t R, n_samples;              // n_samples = F * E * R < 2^31
+    uint32_t nu, nv, nw, n_vox;         // n_vox = nu * nv * nw;  n_vox * n_labels < 2^31
+    uint32_t n_labels, fill_radius, fill_min;
+    uint32_t tu, tv;                    // tiles along u and v (launch_recon_label_resolve fills them)
+    float A[9], b[3];                   // mcrt_recon_transform
+    float row_u;
+};
+
+// k_render_label (mcrt_render_label_frames): the label blocks [F][nw][nv][nu] read at the points a depth buffer [F][ny][nx] names -> bytes [F][ny][nx]
+struct RenderLabelArgs {
+    const uint8_t *labels;              // [F][nw][nv][nu]
+    const float *depth;                 // [F][ny][nx]: mcrt_render_frames' depth_dev
+    uint8_t *out;                       // [F][ny][nx]
+    float origin[3], di[3], dj[3], ds[3];   // mcrt_render_view, component order u, v, w
+    uint32_t nx, ny, n_steps, F, nu, nv, nw;
+};
+
 hipError_t launch_init(const FrameArgs &a, hipStream_t st);
 hipError_t launch_trace(const FrameArgs &a, uint32_t b, bool stats, hipStream_t st);
 hipError_t launch_nodes_walk(const float4 *nodes, uint32_t n_nodes, uint4 *out, hipStream_t st);
@@ -222,6 +250,9 @@ hipError_t launch_render(const RenderArgs &a, bool in8, hipStream_t st);
 hipError_t launch_srad(SpeckleArgs a, uint32_t F, uint32_t fuse, hipStream_t st);   // fuse: 2 or 4 (the instantiation); a.n <= fuse
 hipError_t launch_recon_splat(const ReconArgs &a, hipStream_t st);
 hipError_t launch_recon_resolve(ReconArgs a, hipStream_t st);
+hipError_t launch_recon_label_splat(const ReconLabelArgs &a, hipStream_t st);
+hipError_t launch_recon_label_resolve(ReconLabelArgs a, hipStream_t st);
+hipError_t launch_render_label(const RenderLabelArgs &a, hipStream_t st);
 uint32_t label_blocks(size_t lines);                              // workgroups of a k_label launch over `lines` (frame, scan-line) beams (sizes the overflow stacks)
 uint32_t label_stack_entries();
 hipError_t launch_label(const FrameArgs &a, const LabelArgs &l, hipStream_t st);

@@ -5,7 +5,7 @@
 //                   [--compound-mode mean|max|median] [--compound-feather LINES] [--compound-weights w0,w1,...]
 //                   [--sweep K --sweep-step-deg D [--sweep-pivot-mm P] (--cplane-mm Y | --sagittal-mm X | --render DX,DY,DZ ...)]
 //                   [--render DX,DY,DZ --render-box-mm X0,Y0,Z0,X1,Y1,Z1 --render-voxel-mm P [--render-mode mip|mean|surface] [--render-size NX,NY]]
-//                   [--labels FILE.pgm [--label-rule traced|geometric] [--label-offset X]]
+//                   [--labels FILE.pgm [--label-rule traced|geometric] [--label-offset X]] [--render-labels FILE.pgm] [--freehand-labels FILE.raw]
 //                   [--speckle N [--speckle-q0 X] [--speckle-rho X] [--speckle-lambda X]]
 //                   [--freehand N --freehand-step-mm D [--freehand-fan-deg A] --freehand-box-mm X0,Y0,Z0,X1,Y1,Z1 --freehand-voxel-mm P --freehand-out FILE.raw
 //                    [--freehand-mode mean|max] [--freehand-fill H]]
@@ -67,6 +67,12 @@
 // from their poses, holes filled from sampled voxels up to --freehand-fill H voxels away (0..3, default 1), every voxel the mean of its
 // samples or with --freehand-mode max the largest (mcrt_recon_frames).  --freehand-out FILE.raw receives the block as little-endian float32,
 // [nw][nv][nu] with x fastest; its sizes are printed.  The picture of the positional arguments is written as without the option.
+// --freehand-labels FILE.raw, with --freehand, writes that block's ground truth beside it: nu x nv x nw bytes, x fastest, the material most of
+// a voxel's samples lie in (the central beams of the N poses, mcrt_label_frames, voted voxel by voxel: mcrt_recon_label_frames), holes filled
+// up to --freehand-fill voxels away as the float block's, 255 where nothing is near.  --render-labels FILE.pgm, with --sweep ... --render,
+// writes the ground truth of the rendered view: the material of the voxel every pixel shows (mcrt_render_label_frames through the
+// rendering's depth buffer and the label block of the box), 255 where the ray saw nothing -- every pixel of --render-mode mean.
+// --label-rule and --label-offset are taken with either as with --labels.
 #include "mcrt_host.hpp"
 #include <chrono>
 #include <cmath>
@@ -108,7 +114,7 @@ int main(int argc, char **argv)
     int sweep_planes = 0; double sweep_step_deg = 0.0, sweep_pivot_mm = 0.0, cut_mm = 0.0;   // sweep_planes 0: off
     bool sweep_given = false, sweep_step_given = false, cplane_given = false, sagittal_given = false;
     const char *render_dir = nullptr, *render_box = nullptr, *render_voxel = nullptr, *render_mode = nullptr, *render_size = nullptr;   // the options as given
-    const char *labels_file = nullptr, *label_rule = nullptr, *label_offset = nullptr;
+    const char *labels_file = nullptr, *label_rule = nullptr, *label_offset = nullptr, *render_labels = nullptr, *freehand_labels = nullptr;
     mcrt_label_opts lopts; mcrt_default_label_opts(&lopts);
     const char *speckle_n = nullptr, *speckle_q0 = nullptr, *speckle_rho = nullptr, *speckle_lambda = nullptr;   // the options as given
     mcrt_speckle_opts sopts; mcrt_default_speckle_opts(&sopts);
@@ -143,6 +149,8 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--render-mode") && i + 1 < argc) render_mode = argv[++i];
             else if (!std::strcmp(argv[i], "--render-size") && i + 1 < argc) render_size = argv[++i];
             else if (!std::strcmp(argv[i], "--labels") && i + 1 < argc) labels_file = argv[++i];
+            else if (!std::strcmp(argv[i], "--render-labels") && i + 1 < argc) render_labels = argv[++i];
+            else if (!std::strcmp(argv[i], "--freehand-labels") && i + 1 < argc) freehand_labels = argv[++i];
             else if (!std::strcmp(argv[i], "--label-rule") && i + 1 < argc) label_rule = argv[++i];
             else if (!std::strcmp(argv[i], "--label-offset") && i + 1 < argc) label_offset = argv[++i];
             else if (!std::strcmp(argv[i], "--speckle") && i + 1 < argc) speckle_n = argv[++i];
@@ -197,6 +205,8 @@ int main(int argc, char **argv)
         if (sweep_given && (compound_given || elevation_given)) throw std::invalid_argument("--sweep does not combine with --compound or --elevation");
         if (!sweep_given && (sweep_step_given || cplane_given || sagittal_given)) throw std::invalid_argument("--sweep-step-deg, --cplane-mm and --sagittal-mm need --sweep");
         if (!sweep_given && (render_dir || render_box || render_voxel || render_mode || render_size)) throw std::invalid_argument("--render and its options need --sweep");
+        if (render_labels && !render_dir) throw std::invalid_argument("--render-labels needs --render (with --sweep)");
+        if (freehand_labels && !freehand_n) throw std::invalid_argument("--freehand-labels needs --freehand");
         if (!render_dir && (render_box || render_voxel || render_mode || render_size)) throw std::invalid_argument("--render-box-mm, --render-voxel-mm, --render-mode and --render-size need --render (with --sweep)");
         mcrt_sweep sweep{ 0, 0.0f, 0.0f };
         mcrt_volume_grid cut{};
@@ -243,7 +253,7 @@ int main(int argc, char **argv)
             else { cut.origin_mm[0] = cut_mm; cut.origin_mm[1] = transducer_radius_cm * 10.0; cut.origin_mm[2] = -(400 - 1) * pitch / 2.0; cut.du_mm[2] = pitch; cut.dv_mm[1] = pitch; cut.nu = 400; cut.nv = 500; }
             if (!render_dir) cut.nw = 1;
         }
-        if (!labels_file && (label_rule || label_offset)) throw std::invalid_argument(std::string(label_rule ? "--label-rule" : "--label-offset") + " needs --labels");
+        if (!labels_file && !render_labels && !freehand_labels && (label_rule || label_offset)) throw std::invalid_argument(std::string(label_rule ? "--label-rule" : "--label-offset") + " needs --labels");
         if (label_rule) {
             if (!std::strcmp(label_rule, "traced")) lopts.rule = MCRT_LABEL_TRACED;
             else if (!std::strcmp(label_rule, "geometric")) lopts.rule = MCRT_LABEL_GEOMETRIC;
@@ -335,7 +345,11 @@ int main(int argc, char **argv)
             rf_image.convolve(psf);           // main.cpp:146
             rf_image.envelope();              // main.cpp:147
             if (speckle_n) rf_image.despeckle(sopts);   // the despeckle filter, on whatever the envelope ran over
-            if (render_dir) cut_bytes = rf_image.render(cut, view, &ropts, &display);               // the box seen from a direction
+            if (render_dir && render_labels && f == frames - 1) {                                   // the box seen from a direction, and what is seen
+                rf_image.labels(transducer, &lopts);
+                write_pgm(render_labels, view.nx, view.ny, rf_image.render_labels(cut, view, &ropts, &display, nullptr, &cut_bytes));
+            }
+            else if (render_dir) cut_bytes = rf_image.render(cut, view, &ropts, &display);          // the box seen from a direction
             else if (sweep_given)             // the cut through the swept volume
                 cut_bytes = bmode ? rf_image.volume(display, cut) : to_bytes(rf_image.volume(cut));   // (as rf_image::save)
             else if (compound_given) { if (bmode) rf_image.postprocess(display, steers, nullptr, opts); else rf_image.postprocess(steers, opts); }   // the views averaged (or opts' mode)
@@ -360,6 +374,14 @@ int main(int argc, char **argv)
                 f.write((const char *)le, 4);
             }
             if (!f) throw std::runtime_error(std::string("cannot write ") + freehand_out);
+            if (freehand_labels) {   // what tissue every voxel is
+                mcrt_recon_label_opts flopts; mcrt_default_recon_label_opts(&flopts, (uint32_t)scene.materials.size());
+                flopts.fill_radius = fopts.fill_radius; flopts.fill_min = fopts.fill_min;
+                const std::vector<unsigned char> lab = tracked.reconstruct_labels(fgrid, flopts, &lopts);
+                std::ofstream fl(freehand_labels, std::ios::binary);
+                fl.write((const char *)lab.data(), (std::streamsize)lab.size());
+                if (!fl) throw std::runtime_error(std::string("cannot write ") + freehand_labels);
+            }
             std::cout << "freehand volume: " << fgrid.nu << " x " << fgrid.nv << " x " << fgrid.nw << " voxels (x, y, z), float32 [nw][nv][nu], " << freehand_frames << " frames" << std::endl;
         }
         if (argc > 4 && render_dir) write_pgm(argv[4], view.nx, view.ny, cut_bytes);

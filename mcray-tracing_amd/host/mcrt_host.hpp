@@ -798,6 +798,34 @@ public:
         if (counts) *counts = download<uint32_t>(points.as<uint32_t>() + n, n);
         return download<float>(points, n);
     }
+    // the ground truth of reconstruct(grid) (mcrt.h: mcrt_recon_label_frames): the central beams of the poses of trace(frame, poses) walked through
+    // the scene (mcrt_label_frames, at most 1024 poses; lopts: null = the tracer's rule at the tracer's start offset) and voted into grid's voxels:
+    // bytes [nw][nv][nu], the material most of a voxel's samples carry, holes filled as ropts says, MCRT_LABEL_NONE where nothing is near.
+    // ropts.n_labels is the scene's material count (mcrt_default_recon_label_opts(&o, scene.materials.size())).  counts, votes: the samples per
+    // voxel and the winner's share of them, when asked for.  It needs the tracked state as reconstruct() does; the tables of labels() are
+    // overwritten, so label_picture() / label_volume() want a new labels() after it.
+    std::vector<unsigned char> reconstruct_labels(const mcrt_volume_grid &grid, const mcrt_recon_label_opts &ropts, const mcrt_label_opts *lopts = nullptr,
+                                                  std::vector<uint32_t> *counts = nullptr, std::vector<uint32_t> *votes = nullptr)
+    {
+        if (holds != stack_of::tracked_frames) throw std::invalid_argument("rf_image::reconstruct_labels: trace(frame, poses) first");
+        const size_t n = (size_t)grid.nu * grid.nv * grid.nw, taps = (size_t)n_views * columns * max_rows;
+        if (n == 0 || n >= ((size_t)1 << 31)) throw std::invalid_argument("rf_image::reconstruct_labels: the grid needs 1 .. 2^31 - 1 voxels");
+        shape_params();
+        label.reserve(taps);
+        labelled = labels_of::nothing; label_planes = 0; label_tissue = nullptr;
+        mcrt_ctx *tracer = dev->tracer();
+        check(mcrt_label_frames(tracer, n_views, 0, columns, tracked.pos.data(), tracked.dir.data(), lopts, label.as<uint8_t>(), nullptr, nullptr), "mcrt_label_frames");
+        check(mcrt_synchronize(tracer), "mcrt_synchronize");
+        points.reserve(9 * n);                                     // counts, votes, then the labels' bytes (the 32-bit tables first: aligned)
+        uint32_t *count_dev = points.as<uint32_t>(), *votes_dev = count_dev + n;
+        uint8_t *out_dev = points.as<uint8_t>() + 8 * n;
+        const float depth_mm_f = (float)(uint32_t)(max_travel_time_us * speed_of_sound) * 0.001f;
+        check(mcrt_recon_label_frames(dev->ctx, label.as<uint8_t>(), n_views, columns, max_rows, tracked.pos.data(), tracked.dir.data(), (double)depth_mm_f / (double)max_rows,
+                                      10.0, &grid, &ropts, out_dev, counts ? count_dev : nullptr, votes ? votes_dev : nullptr, nullptr), "mcrt_recon_label_frames");
+        if (counts) *counts = download<uint32_t>(count_dev, n);
+        if (votes) *votes = download<uint32_t>(votes_dev, n);
+        return download<unsigned char>(out_dev, n);
+    }
     template <typename psf_> void convolve(const psf_ &p)
     {
         float *img = rf.as<float>(); uint32_t frames = 1;
@@ -879,15 +907,22 @@ public:
     std::vector<unsigned char> render(const mcrt_volume_grid &grid, const mcrt_render_view &view, const mcrt_render_opts *opts = nullptr,
                                       const mcrt_bmode_params *bp = nullptr, const float *tgc_db = nullptr)
     {
+        return download<unsigned char>(rendered, render_pass(grid, view, opts, bp, tgc_db, false));
+    }
+    // the ground truth of render(...) (mcrt.h: mcrt_render_label_frames): the same rendering with its depth buffer kept, the label block of
+    // label_volume(grid), and the label of the voxel every pixel shows -- bytes [view.ny][view.nx], MCRT_LABEL_NONE where the ray saw nothing
+    // (every pixel of the mean view) or saw it outside the sweep.  It needs labels(transducer) after trace(frame, transducer, sweep), as
+    // label_volume() does, with its known stale cases.  picture: the rendering itself, when asked for (the bytes render() returns)
+    std::vector<unsigned char> render_labels(const mcrt_volume_grid &grid, const mcrt_render_view &view, const mcrt_render_opts *opts = nullptr,
+                                             const mcrt_bmode_params *bp = nullptr, const float *tgc_db = nullptr, std::vector<unsigned char> *picture = nullptr)
+    {
         volume_prepare(grid, 1);
-        const size_t npix = (size_t)view.nx * view.ny;
-        if (npix == 0) throw std::invalid_argument("rf_image::render: the view has no pixels");
-        mcrt_bmode_params p;
-        if (bp) p = *bp; else mcrt_default_bmode(&p);
-        p.radius_mm = radius_mm; p.total_angle_rad = angle;
-        check(mcrt_bmode_volume_frames(dev->ctx, stack.as<float>(), 1, columns, max_rows, &p, &sweep, &grid, tgc_db, nullptr, points.as<uint8_t>()), "mcrt_bmode_volume_frames");
-        rendered.reserve(npix);
-        check(mcrt_render_frames(dev->ctx, points.as<uint8_t>(), 1, 1, grid.nu, grid.nv, grid.nw, &view, opts, nullptr, rendered.as<uint8_t>(), nullptr), "mcrt_render_frames");
+        if (label_planes != sweep.n_planes) throw std::invalid_argument("rf_image::render_labels: labels(transducer) after trace(frame, transducer, sweep) first");
+        const size_t npix = render_pass(grid, view, opts, bp, tgc_db, true);
+        if (picture) *picture = download<unsigned char>(rendered, npix);
+        float *depth_dev = rendered.as<float>() + (npix + 3) / 4;
+        check(mcrt_label_volume_frames(dev->ctx, label_tissue, 1, columns, max_rows, radius_mm, angle, &sweep, &grid, points.as<uint8_t>()), "mcrt_label_volume_frames");   // (the voxels are rendered: the block is free)
+        check(mcrt_render_label_frames(dev->ctx, points.as<uint8_t>(), 1, grid.nu, grid.nv, grid.nw, &view, depth_dev, rendered.as<uint8_t>()), "mcrt_render_label_frames");
         return download<unsigned char>(rendered, npix);
     }
     // ground-truth label maps (mcrt.h: mcrt_label_frames): the central beam of every scan-line of t walked through the scene -- of the K planes of
@@ -1020,6 +1055,22 @@ private:
         points.reserve(n * size);
         return n;
     }
+    // render() / render_labels(): grid's displayed voxels into `points`, their picture into `rendered` -- npix bytes, then with want_depth the
+    // depth buffer, npix floats from the next word on; returns npix
+    size_t render_pass(const mcrt_volume_grid &grid, const mcrt_render_view &view, const mcrt_render_opts *opts, const mcrt_bmode_params *bp, const float *tgc_db, bool want_depth)
+    {
+        volume_prepare(grid, 1);
+        const size_t npix = (size_t)view.nx * view.ny;
+        if (npix == 0) throw std::invalid_argument("rf_image::render: the view has no pixels");
+        mcrt_bmode_params p;
+        if (bp) p = *bp; else mcrt_default_bmode(&p);
+        p.radius_mm = radius_mm; p.total_angle_rad = angle;
+        check(mcrt_bmode_volume_frames(dev->ctx, stack.as<float>(), 1, columns, max_rows, &p, &sweep, &grid, tgc_db, nullptr, points.as<uint8_t>()), "mcrt_bmode_volume_frames");
+        rendered.reserve(want_depth ? 4 * ((npix + 3) / 4) + 4 * npix : npix);
+        check(mcrt_render_frames(dev->ctx, points.as<uint8_t>(), 1, 1, grid.nu, grid.nv, grid.nw, &view, opts, nullptr, rendered.as<uint8_t>(),
+                                 want_depth ? rendered.as<float>() + (npix + 3) / 4 : nullptr), "mcrt_render_frames");
+        return npix;
+    }
     mcrt_compound compound_of(const std::vector<float> &steer_rad) const
     {
         if (holds != stack_of::views || steer_rad.size() != n_views) throw std::invalid_argument("rf_image::postprocess: the steer list is not the one the views were traced with");
@@ -1041,8 +1092,8 @@ private:
     mcrt_sweep sweep{ 0, 0.0f, 0.0f };           // ... the sweep of sweep_planes
     struct pose_tables { std::vector<float> pos, dir; } tracked;   // ... the poses of tracked_frames, [n_views][columns][3] each
     device_buffer points;                        // volume(), label_picture(), label_volume(): the gathered points, floats or bytes
-    device_buffer rendered;                      // render(): the picture's bytes
-    device_buffer label;                         // labels(): interface, crossings and tissue tables in one allocation
+    device_buffer rendered;                      // render(), render_labels(): the picture's bytes (then the depth buffer)
+    device_buffer label;                         // labels(): interface, crossings and tissue tables in one allocation; reconstruct_labels(): the tissue stack
     enum class labels_of { nothing, one_plane, sweep_planes } labelled = labels_of::nothing;   // ... what they hold (one_plane: a 1-plane sweep's too)
     uint32_t label_planes = 0; const unsigned char *label_tissue = nullptr;   // ... their leading axis (nothing: 0) and the tissue table
 };
