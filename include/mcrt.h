@@ -52,7 +52,8 @@ extern "C" {
                                    + mcrt_recon_opts, mcrt_default_recon_opts, mcrt_recon_transform, mcrt_recon_frames
                                    (freehand 3-D reconstruction: tracked frames binned into voxels by their poses, with hole filling; additive);
                                    + mcrt_recon_label_opts, mcrt_default_recon_label_opts, mcrt_recon_label_frames, mcrt_render_label_frames
-                                   (3-D ground truth: a freehand label volume by majority vote, the label of what a rendering shows; additive) */
+                                   (3-D ground truth: a freehand label volume by majority vote, the label of what a rendering shows; additive);
+                                   + mcrt_debug_beam (what bounce 1 by beams did in the last pass; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -984,6 +985,11 @@ int mcrt_debug_tail_histograms(mcrt_ctx *ctx, uint64_t out[2560], int reset);
  * exhaustively against IEEE division for params.tex_res), out[1] the branch-free voxel cell, out[2] the entries of the padded
  * { threshold, bin } image of k_march's fast variant (0: generic variant), out[3] reserved (0) */
 int mcrt_debug_fast_paths(mcrt_ctx *ctx, uint32_t out[4]);
+/* what bounce 1 BY BEAMS did in the context's LAST traced pass (its first scan-line group): out[0] 1 when bounce 1 ran by beams -- a staged pass with
+ * one probe pose, where bounce 1 would otherwise run as ray packets --, else 0 and the rest 0; out[1] rays whose closest hit the beams' lists
+ * decided, out[2] leftover rays walked through the tree, out[3] beams whose list is incomplete (cut at its capacity), out[4] beams refused for their spread,
+ * out[5] beams that have rays at all.  Waits for the stream. */
+int mcrt_debug_beam(mcrt_ctx *ctx, uint32_t out[6]);
 /* TEST HOOK, refused (MCRT_ERR_INVALID) unless the context was created with MCRT_TEST_HOOKS set in the environment: ORs `bits` into the
  * context's device error word on its stream, as an abandoned launch would (bit 0: traversal stack ran out, bit 1: kernel watchdog
  * expired) -- what mcrt_synchronize reports and what turns finalised RF images into NaN until it is asked */

@@ -593,6 +593,13 @@ class Context(_SceneCalls):
         check(self.L.mcrt_debug_fast_paths(self.h, out))
         return bool(out[0]), bool(out[1]), int(out[2])
 
+    def debug_beam(self):
+        """(bounce 1 ran by beams, rays the beams decided, leftover rays walked, beams cut at their capacity, beams refused, beams in use) of the last traced pass"""
+        out = (C.c_uint32 * 6)()
+        if hasattr(self.L, "mcrt_debug_beam"):
+            check(self.L.mcrt_debug_beam(self.h, out))
+        return bool(out[0]), int(out[1]), int(out[2]), int(out[3]), int(out[4]), int(out[5])
+
     def debug_set_error(self, bits):
         """test hook: mark the context as an abandoned launch would (mcrt_debug_set_error)"""
         check(self.L.mcrt_debug_set_error(self.h, int(bits)))

@@ -51,6 +51,10 @@ static Knobs read_knobs()
     k.test_hooks = tuning_env("MCRT_TEST_HOOKS") != nullptr;
     if (const char *e = tuning_env("MCRT_RETIRE_LATE")) k.retire_late = atoi(e) != 0;
     if (const char *e = tuning_env("MCRT_FOLD_B0")) k.fold_b0 = atoi(e) != 0;
+    if (const char *e = tuning_env("MCRT_BEAM_B1")) { int v = atoi(e); if (v >= 0 && v <= 2) k.beam_b1 = (uint32_t)v; }
+    if (const char *e = tuning_env("MCRT_BEAM_FROM")) { long long v = atoll(e); if (v >= 0 && v <= 0xffffffffll) k.beam_from = (uint32_t)v; }
+    if (const char *e = tuning_env("MCRT_BEAM_CAP")) { int v = atoi(e); if (v >= 1 && v <= (int)MCRT_BEAM_CAP_MAX) k.beam_cap = (uint32_t)v; }
+    if (const char *e = tuning_env("MCRT_BEAM_NEAR")) { int v = atoi(e); if (v >= 1) k.beam_near = (uint32_t)v; }
     if (const char *e = tuning_env("MCRT_RENDER_ROW_TILE")) k.render_row_tile = atoi(e) != 0;
     if (const char *e = tuning_env("MCRT_SPECKLE_FUSE")) { int v = atoi(e); if (v == 2 || v == 4) k.speckle_fuse = (uint32_t)v; }
     return k;
@@ -549,6 +553,23 @@ extern "C" int mcrt_debug_fast_paths(mcrt_ctx *c, uint32_t out[4])
     CTX_TRY(c);
     if (!out) return set_error(MCRT_ERR_INVALID, "null out pointer");
     out[0] = c->tab.fast_div ? 1u : 0u; out[1] = c->ins.last_lean_bound > 0.0f ? 1u : 0u; out[2] = c->ins.last_march_rows; out[3] = 0u;
+    return MCRT_OK;
+}
+
+// what bounce 1 by beams did in the last traced pass (work set 0): whether it ran, rays it resolved, leftover rays walked, beams incomplete, beams refused, beams in use
+extern "C" int mcrt_debug_beam(mcrt_ctx *c, uint32_t out[6])
+{
+    CTX_TRY(c);
+    if (!out) return set_error(MCRT_ERR_INVALID, "null out pointer");
+    for (int k = 0; k < 6; k++) out[k] = 0u;
+    if (!c->ins.last_beam || c->work.empty()) return MCRT_OK;
+    const Work &w = c->work[0];
+    uint32_t lc[5] = { 0, 0, 0, 0, 0 }, n1 = 0;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(lc, w.beam.lcount, sizeof lc, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&n1, w.b.counts.p + 1, 4, hipMemcpyDeviceToHost));
+    const uint32_t walked = lc[c->knobs.beam_near < c->knobs.beam_cap ? 1 : 0];
+    out[0] = 1u; out[1] = n1 - walked; out[2] = walked; out[3] = lc[2]; out[4] = lc[3]; out[5] = lc[4];
     return MCRT_OK;
 }
 

@@ -1,0 +1,361 @@
+// mcrt_beam.hip -- bounce 1 of a staged pass with ONE probe pose: the rays of a scan-line leave one point (bounce 0 is one ray per scan-line, and the
+// hit point is the next origin) in a few narrow bundles, the same for every frame of the pass.  Instead of walking the tree once per 64 rays
+// (k_trace_packet), the triangles a bundle can meet are collected ONCE per bundle and every ray tests that short list, nearest first:
+//
+//   k_beam_clear    the reduction words, the leftover counters
+//   k_beam_bounds   per BEAM -- scan-line x history (the medium says whether bounce 0 reflected) x dominant axis x its sign -- the bounds of the two
+//                   slopes d_other / |d_dom|, of the start point f2 and of its coordinates' size, over (a sample of) the bounce-1 queue
+//   k_beam_collect  one workgroup per beam: one traversal of the BVH4 with a conservative beam-against-box test, the leaf triangles tested by their own
+//                   padded bounds, sorted by the depth at which they begin, the first `cap` copied into the beam's list
+//   k_beam_test     one lane per ray in queue order: the contract's triangle test (packet_tri_test) over its beam's list in order, until the hit lies
+//                   before everything not yet tested; lanes that cannot be decided are appended to a leftover queue
+//   k_beam_gather, the lane walk, k_beam_scatter     the leftovers, walked as any other queue
+//
+// EXACT: a ray's answer is the smallest (fraction, id) among the triangles that pass the contract's test, whatever the order and
+// whatever else is tested.  A ray counts as a MEMBER of a beam only where comparisons prove it inside the beam's bounds (a NaN proves nothing), the
+// collection keeps every triangle whose padded bounds come within a margin m of the beam's volume -- m = 2^-18 x the largest coordinate of the start
+// points and the scene, 16 x the rounding of the slab test and of the arithmetic here --, and a member is FINAL only when its hit lies more than 2 m before the depth at which
+// the first untested triangle's padded bounds begin: a triangle accepted at a smaller or equal fraction has its hit inside its own padded bounds.
+#include <hip/hip_fp16.h>
+#include "mcrt_device.h"
+#include "mcrt_walk.h"
+
+// (20 KB of LDS in all: a beam's workgroup has to find room on a compute unit beside k_march of bounce 0, which runs on the side stream at that time -- with 40 KB
+//  the launch ended when k_march did)
+#define BEAM_CT 256u          // k_beam_collect: threads of a beam's workgroup (a level of the traversal holds up to a few hundred nodes)
+#define BEAM_QN 512           // k_beam_collect: nodes of one level of the traversal (LDS)
+#define BEAM_EN 1024          // ... and triangles of a beam before the cut to its capacity (LDS; the largest capacity)
+#define BEAM_LN 2048          // ... and triangles of the leaves the traversal reaches, before their own bounds are tested (LDS)
+
+namespace mcrt {
+
+// floats as unsigned words of the same order (atomicMin / atomicMax)
+MCRT_DEV uint32_t ford(float f) { const uint32_t b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
+MCRT_DEV float funord(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
+MCRT_DEV float comp(f3 v, int k) { return k == 0 ? v.x : k == 1 ? v.y : v.z; }
+
+// a queued ray of bounce 1 and the beam it would belong to
+struct BeamRay { f3 f2, to; float u, v, cmax, dd; int dom, bid; bool neg; };
+MCRT_DEV bool beam_ray(const FrameArgs &a, uint32_t i, BeamRay &r)
+{
+    const size_t np = (size_t)a.ne * a.S;
+    const uint32_t pid = a.queue[np + i];
+    const uint32_t line = pid / a.S, scan = line - (line / a.ne_frame) * a.ne_frame;
+    const float4 s0 = a.st0[np + i], s1 = a.st1[np + i];
+    const Ray ry = ray_of(mk(s0.x, s0.y, s0.z), mk(s1.x, s1.y, s1.z), s0.w, a);
+    r.f2 = ry.f2; r.to = ry.to;
+    const f3 D = ry.to - ry.f2;
+    const float ax = fabsf(D.x), ay = fabsf(D.y), az = fabsf(D.z);
+    r.dom = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
+    r.dd = comp(D, r.dom);
+    const float ad = fabsf(r.dd);
+    r.u = comp(D, (r.dom + 1) % 3) / ad; r.v = comp(D, (r.dom + 2) % 3) / ad;
+    r.cmax = fmaxf(fmaxf(fabsf(r.f2.x), fabsf(r.f2.y)), fabsf(r.f2.z));
+    r.neg = r.dd < 0.0f;
+    const uint32_t hist = __float_as_int(s1.w) != (int)a.start_mat ? 1u : 0u;
+    r.bid = (int)((((scan * 2u + hist) * 3u + (uint32_t)r.dom) * 2u) + (r.neg ? 1u : 0u));
+    // every coordinate a number, the dominant component not 0 (then |u|, |v| <= 1)
+    const float sum = fabsf(r.f2.x) + fabsf(r.f2.y) + fabsf(r.f2.z) + fabsf(r.to.x) + fabsf(r.to.y) + fabsf(r.to.z);
+    return sum < 1e30f && ad > 0.0f && fabsf(r.u) <= 1.0f && fabsf(r.v) <= 1.0f;
+}
+
+MCRT_DEV float wave_min(float x) { for (int o = 32; o > 0; o >>= 1) x = fminf(x, __shfl_xor(x, o, 64)); return x; }
+MCRT_DEV float wave_max(float x) { for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64)); return x; }
+
+// reduction words of a beam: 0-4 minima (u, v, f2), 8-13 maxima (u, v, f2, size)
+__global__ void __launch_bounds__(256) k_beam_clear(BeamArgs g)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < g.n_beams * MCRT_BEAM_REC) g.red[i] = (i & 8u) ? 0u : 0xffffffffu;
+    if (i < 8u) g.lcount[i] = 0u;
+    if (i <= MCRT_MAX_BOUNCES) g.l_counts[i] = 0u;
+    if (i < MCRT_MAX_BOUNCES * MCRT_XCDS) g.l_cursors[(size_t)i * MCRT_CURSOR_STRIDE] = 0u;
+}
+
+__global__ void __launch_bounds__(256) k_beam_bounds(FrameArgs a, BeamArgs g)
+{
+    const uint32_t n = a.counts[1];
+    const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    // one packet of 64 queue neighbours out of every `stride` is a sample of its beams -- WHICH one of the stride is a hash of the wavefront's number: k_shade
+    // queues a workgroup's reflected rays first, so a fixed position repeats with the queue's period and can miss a history for good (every 16th packet of
+    // 1024-sample scan-lines left a tenth of the rays without a beam)
+    const uint32_t base = (wave * g.stride + ((wave * 2654435761u) >> 16) % g.stride) * 64u;
+    if (base >= n) return;
+    const uint32_t i = base + lane;
+    BeamRay r; r.bid = -1;
+    const bool live = i < n && beam_ray(a, i, r);
+    unsigned long long todo = __ballot(live);
+    while (todo) {
+        const int cb = __builtin_amdgcn_readlane(r.bid, __ffsll((long long)todo) - 1);
+        const bool mine = live && r.bid == cb;
+        todo &= ~__ballot(mine);
+        const float lo[5] = { r.u, r.v, r.f2.x, r.f2.y, r.f2.z }, hi[6] = { r.u, r.v, r.f2.x, r.f2.y, r.f2.z, r.cmax };
+        uint32_t *w = g.red + (size_t)cb * MCRT_BEAM_REC;
+#pragma unroll
+        // (an atomic only where the word would change: after a beam's first few packets hardly any does, and the packets of a scan-line all meet in the same words)
+        for (int k = 0; k < 5; k++) { const uint32_t m = ford(wave_min(mine ? lo[k] : INFINITY)); if ((int)lane == k && m < __hip_atomic_load(&w[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&w[k], m); }
+#pragma unroll
+        for (int k = 0; k < 6; k++) { const uint32_t m = ford(wave_max(mine ? hi[k] : -INFINITY)); if ((int)lane == 8 + k && m > __hip_atomic_load(&w[8 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&w[8 + k], m); }
+    }
+}
+
+// A beam's volume: at depth s = +-(x_dom - xref) >= 0 a member's point lies at s_r = s - (0 .. w) along ITS ray, and its other two coordinates at
+// f2 + s_r * slope.  Everything is padded by m.
+struct BeamGeom { int dom; bool neg; float xref, w, m, umin, umax, vmin, vmax, alo, ahi, blo, bhi, smax; };
+// does the box come within m of the volume?  s_begin: the depth at which the box begins, less m
+MCRT_DEV bool beam_box(const BeamGeom &B, f3 lo, f3 hi, float &s_begin)
+{
+    const float lod = comp(lo, B.dom), hid = comp(hi, B.dom);
+    const float sb0 = B.neg ? B.xref - hid : lod - B.xref, sb1 = B.neg ? B.xref - lod : hid - B.xref;
+    s_begin = sb0 - B.m;
+    const float s0 = fmaxf(s_begin, -B.m), s1 = fminf(sb1 + B.m, B.smax);
+    if (!(s0 <= s1)) return false;
+    const float sa = s0 - B.w;
+    const int ka = (B.dom + 1) % 3, kb = (B.dom + 2) % 3;
+    {
+        const float p1 = sa * B.umin, p2 = sa * B.umax, p3 = s1 * B.umin, p4 = s1 * B.umax;
+        const float l = B.alo + fminf(fminf(p1, p2), fminf(p3, p4)) - B.m, h = B.ahi + fmaxf(fmaxf(p1, p2), fmaxf(p3, p4)) + B.m;
+        if (!(l <= comp(hi, ka) && h >= comp(lo, ka))) return false;
+    }
+    {
+        const float p1 = sa * B.vmin, p2 = sa * B.vmax, p3 = s1 * B.vmin, p4 = s1 * B.vmax;
+        const float l = B.blo + fminf(fminf(p1, p2), fminf(p3, p4)) - B.m, h = B.bhi + fmaxf(fmaxf(p1, p2), fmaxf(p3, p4)) + B.m;
+        if (!(l <= comp(hi, kb) && h >= comp(lo, kb))) return false;
+    }
+    return true;
+}
+
+// the beam's record, as k_beam_test reads it: 0-3 umin umax vmin vmax | 4-6 f2 lo | 7-9 f2 hi | 10 size | 11 m | 12 xref | 13 s_end | 14 entries | 15 -
+// (a beam without members, or refused: the slope bounds are an empty interval, so that no ray proves itself inside)
+__global__ void __launch_bounds__(BEAM_CT) k_beam_collect(FrameArgs a, BeamArgs g)
+{
+    __shared__ int q[2][BEAM_QN];
+    __shared__ unsigned long long ent[BEAM_EN];
+    __shared__ uint32_t leaf[BEAM_LN];
+    __shared__ uint32_t nq[2], n_leaf, n_ent, overflow;
+    const uint32_t beam = blockIdx.x, lane = threadIdx.x;
+    const uint32_t *w = g.red + (size_t)beam * MCRT_BEAM_REC;
+    uint32_t *rec = g.rec + (size_t)beam * MCRT_BEAM_REC;
+    float umin = funord(w[0]), vmin = funord(w[1]), umax = funord(w[8]), vmax = funord(w[9]);
+    const bool empty = w[0] == 0xffffffffu;
+    const bool refused = !empty && !(umax - umin <= g.spread_cap && vmax - vmin <= g.spread_cap);
+    if (!empty && lane == 0u) atomicAdd(&g.lcount[4], 1u);
+    if (empty || refused) {
+        if (lane < MCRT_BEAM_REC) rec[lane] = lane == 0u || lane == 2u ? __float_as_uint(INFINITY) : lane == 1u || lane == 3u || lane == 13u ? __float_as_uint(-INFINITY) : 0u;
+        if (refused && lane == 0u) atomicAdd(&g.lcount[3], 1u);
+        return;
+    }
+    // the bounds come from a sample of the members: padded a little, and a ray outside them is no member
+    // the size of every coordinate that matters: the start points and the scene.  (Not the rays' far ends, which lie 10^9 cm away in a medium that hardly
+    // attenuates: a plane distance fl(plane * inv + c) is off by 2^-24 of itself and of c = -(o * inv), i.e. the crossing by 2^-24 (|o| + |plane - o|) in space.)
+    float cmax = funord(w[13]);
+    for (int k = 0; k < 3; k++) cmax = fmaxf(cmax, fmaxf(fabsf(a.scene_lo[k]), fabsf(a.scene_hi[k])));
+    cmax *= 1.0625f;
+    const float m = cmax * 0x1p-18f;
+    { const float pu = 0.0625f * (umax - umin) + 1e-6f, pv = 0.0625f * (vmax - vmin) + 1e-6f; umin -= pu; umax += pu; vmin -= pv; vmax += pv; }
+    float flo[3], fhi[3];
+    for (int k = 0; k < 3; k++) { const float l = funord(w[2 + k]), h = funord(w[10 + k]), p = 0.0625f * (h - l) + m; flo[k] = l - p; fhi[k] = h + p; }
+    const uint32_t code = beam % 6u;
+    BeamGeom B;
+    B.dom = (int)(code >> 1); B.neg = (code & 1u) != 0u;
+    const int ka = (B.dom + 1) % 3, kb = (B.dom + 2) % 3;
+    B.xref = B.neg ? fhi[B.dom] : flo[B.dom]; B.w = fhi[B.dom] - flo[B.dom]; B.m = m;
+    B.umin = umin; B.umax = umax; B.vmin = vmin; B.vmax = vmax; B.alo = flo[ka]; B.ahi = fhi[ka]; B.blo = flo[kb]; B.bhi = fhi[kb]; B.smax = 2.0f * cmax + m;
+
+    // one traversal, level by level: a lane per node of the level
+    // (the leaves' triangles are only listed on the way and tested afterwards, a lane each: a level then costs one round trip to memory, the node's)
+    if (lane == 0u) { nq[0] = 1u; nq[1] = 0u; n_leaf = 0u; n_ent = 0u; overflow = 0u; q[0][0] = 0; }
+    __syncthreads();
+    for (uint32_t level = 0; ; level++) {
+        const uint32_t cur = level & 1u, cnt = nq[cur];
+        if (cnt == 0u) break;
+        if (level >= 256u) { if (lane == 0u) overflow = 1u; break; }
+        for (uint32_t t = lane; t < cnt; t += BEAM_CT) {
+            const uint4 *N = a.nodes_walk + 4 * (size_t)(uint32_t)q[cur][t];
+            const uint4 q0 = N[0], q1 = N[1], q2 = N[2], q3 = N[3];
+            const uint32_t wd[12] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w };      // lo.x lo.y lo.z hi.x hi.y hi.z, two words each
+            const int ref[4] = { (int)q3.x, (int)q3.y, (int)q3.z, (int)q3.w };
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                if (ref[c] == MCRT_BVH4_EMPTY) continue;
+                float bx[6];
+#pragma unroll
+                for (int k = 0; k < 6; k++) bx[k] = __half2float(__ushort_as_half((unsigned short)((wd[2 * k + (c >> 1)] >> ((c & 1) * 16)) & 0xffffu)));
+                float sb;
+                if (!beam_box(B, mk(bx[0], bx[1], bx[2]), mk(bx[3], bx[4], bx[5]), sb)) continue;
+                if (ref[c] >= 0) {
+                    const uint32_t at = atomicAdd(&nq[cur ^ 1u], 1u);
+                    if (at < BEAM_QN) q[cur ^ 1u][at] = ref[c]; else overflow = 1u;
+                } else {
+                    const uint32_t v = (uint32_t)~ref[c], first = v >> 3, nt = (v & 7u) + 1u;
+                    const uint32_t at = atomicAdd(&n_leaf, nt);
+                    if (at + nt <= BEAM_LN) { for (uint32_t k = 0; k < nt; k++) leaf[at + k] = first + k; } else overflow = 1u;
+                }
+            }
+        }
+        __syncthreads();
+        if (lane == 0u) nq[cur] = 0u;
+        if (nq[cur ^ 1u] > BEAM_QN) break;                      // (overflow is set)
+        __syncthreads();
+    }
+    __syncthreads();
+    for (uint32_t t = lane; t < (overflow ? 0u : n_leaf); t += BEAM_CT) {
+        const float4 *T = a.tris + (size_t)leaf[t] * MCRT_TRI_PIECES;
+        f3 plo, phi;
+        float sb;
+        tri_padded_bounds(xyz(T[0]), xyz(T[1]), xyz(T[2]), a.pad_abs, plo, phi);
+        if (!beam_box(B, plo, phi, sb)) continue;
+        const uint32_t at = atomicAdd(&n_ent, 1u);
+        if (at < BEAM_EN) ent[at] = ((unsigned long long)ford(sb) << 32) | (unsigned long long)leaf[t]; else overflow = 1u;
+    }
+    __syncthreads();
+    const bool lost = overflow != 0u;
+    const uint32_t N = lost ? 0u : n_ent;
+    // sorted by the depth at which they begin (bitonic, padded with +infinity to a power of two)
+    uint32_t P = 1u; while (P < N) P <<= 1;
+    for (uint32_t t = N + lane; t < P; t += BEAM_CT) ent[t] = ~0ull;
+    __syncthreads();
+    for (uint32_t k = 2u; k <= P; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0u; j >>= 1) {
+            for (uint32_t t = lane; t < P; t += BEAM_CT) {
+                const uint32_t l = t ^ j;
+                if (l > t) {
+                    const unsigned long long x = ent[t], y = ent[l];
+                    if ((x > y) == ((t & k) == 0u)) { ent[t] = y; ent[l] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    const uint32_t keep = N < g.cap ? N : g.cap;
+    for (uint32_t e = lane; e < keep; e += BEAM_CT) {
+        const unsigned long long x = ent[e];
+        const float4 *T = a.tris + (size_t)(uint32_t)x * MCRT_TRI_PIECES;
+        const float4 t0 = T[0], t1 = T[1], t2 = T[2];
+        float4 *L = (float4 *)(g.list + 4 * ((size_t)beam * g.cap + e));
+        L[0] = t0; L[1] = make_float4(t1.x, t1.y, t1.z, funord((uint32_t)(x >> 32))); L[2] = t2; L[3] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    // s_end: the depth up to which the list is complete
+    const float s_end = lost ? -INFINITY : N > g.cap ? funord((uint32_t)(ent[g.cap] >> 32)) : INFINITY;
+    if (lane == 0u) {
+        rec[0] = __float_as_uint(umin); rec[1] = __float_as_uint(umax); rec[2] = __float_as_uint(vmin); rec[3] = __float_as_uint(vmax);
+        for (int k = 0; k < 3; k++) { rec[4 + k] = __float_as_uint(flo[k]); rec[7 + k] = __float_as_uint(fhi[k]); }
+        rec[10] = __float_as_uint(cmax); rec[11] = __float_as_uint(m); rec[12] = __float_as_uint(B.xref); rec[13] = __float_as_uint(s_end); rec[14] = keep; rec[15] = 0u;
+        if (lost || N > g.cap) atomicAdd(&g.lcount[2], 1u);
+    }
+}
+
+// pass 0: every ray of the bounce-1 queue against entries [0, near) of its beam's list; pass 1: the leftovers of pass 0 against the rest
+__global__ void __launch_bounds__(256) k_beam_test(FrameArgs a, BeamArgs g, uint32_t pass)
+{
+    const uint32_t n = pass == 0u ? a.counts[1] : g.lcount[0];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t base = (blockIdx.x * 256u + threadIdx.x) & ~63u;
+    if (base >= n) return;
+    const uint32_t j = base + lane;
+    const bool live = j < n;
+    const uint32_t ray = !live ? 0u : pass == 0u ? j : g.lq0[j];
+    BeamRay r;
+    bool member = beam_ray(a, ray, r) && live;
+    const uint32_t *rec = g.rec + (size_t)(member ? r.bid : 0) * MCRT_BEAM_REC;
+    {
+        const float4 b0 = ((const float4 *)rec)[0], b1 = ((const float4 *)rec)[1], b2 = ((const float4 *)rec)[2];
+        member = member && r.u >= b0.x && r.u <= b0.y && r.v >= b0.z && r.v <= b0.w
+                 && r.f2.x >= b1.x && r.f2.y >= b1.y && r.f2.z >= b1.z && r.f2.x <= b1.w && r.f2.y <= b2.x && r.f2.z <= b2.y && r.cmax <= b2.z;
+    }
+    const f3 f2 = r.f2, to = r.to;
+    const f3 d = to - f2;
+    const f3 inv = mk(rcp_dir(d.x), rcp_dir(d.y), rcp_dir(d.z));
+    const f3 rc = ray_c(f2, inv);
+    unsigned long long *keys = a.key1;
+    Best best; best.frac = 1.0f; best.tri = -1;
+    if (pass != 0u && live) { const unsigned long long k = keys[ray]; best.frac = __uint_as_float((uint32_t)(k >> 32)); best.tri = (int)(uint32_t)k; }
+    const float f2d = comp(f2, r.dom), sg = r.neg ? -1.0f : 1.0f;
+    bool left = live && !member;
+    unsigned long long todo = __ballot(member);
+    const uint32_t first = pass == 0u ? 0u : g.near, cut = pass == 0u ? g.near : 0xffffffffu;
+    while (todo) {
+        const int cb = __builtin_amdgcn_readlane(r.bid, __ffsll((long long)todo) - 1);
+        const bool mine = member && r.bid == cb;
+        todo &= ~__ballot(mine);
+        const u32x4 R = sload4(g.rec + (size_t)cb * MCRT_BEAM_REC + 11);      // m, xref, s_end, entries
+        const float m2 = 2.0f * __uint_as_float(R[0]), xref = __uint_as_float(R[1]);
+        const uint32_t n_ent = R[3];
+        // the depth of the hit, plus the margin: what begins beyond it cannot be accepted before it
+        float reach = best.tri >= 0 ? sg * ((f2d + best.frac * r.dd) - xref) + m2 : INFINITY;
+        float limit = __uint_as_float(R[2]);
+        const char *L = (const char *)(g.list + 4 * (size_t)(uint32_t)cb * g.cap);
+        // (two entries per round trip to the scalar cache; the second of the last pair may lie past the list: it is fetched, not looked at)
+        for (uint32_t k = first; k < n_ent; k += 2u) {
+            u32x8 A, A2; u32x4 C2, C22;
+            const char *E = L + ((size_t)k << 6);
+            asm volatile("s_load_dwordx8 %0, %4, 0x0\n\ts_load_dwordx4 %1, %4, 0x20\n\ts_load_dwordx8 %2, %4, 0x40\n\ts_load_dwordx4 %3, %4, 0x60\n\ts_waitcnt lgkmcnt(0)"
+                         : "=&s"(A), "=&s"(C2), "=&s"(A2), "=&s"(C22) : "s"(E) : "memory");
+            float begin = __uint_as_float(A[7]);
+            if (k >= cut || !__any(mine && !(reach < begin))) { limit = begin; break; }
+            int before = best.tri;
+            packet_tri_test(A, C2, f2, to, inv, rc, a.pad_abs, mine, best);
+            if (best.tri != before) reach = sg * ((f2d + best.frac * r.dd) - xref) + m2;
+            if (k + 1u >= n_ent) break;
+            begin = __uint_as_float(A2[7]);
+            if (k + 1u >= cut || !__any(mine && !(reach < begin))) { limit = begin; break; }
+            before = best.tri;
+            packet_tri_test(A2, C22, f2, to, inv, rc, a.pad_abs, mine, best);
+            if (best.tri != before) reach = sg * ((f2d + best.frac * r.dd) - xref) + m2;
+        }
+        left = left || (mine && !(reach < limit || limit == INFINITY));
+    }
+    if (live && best.tri >= 0) keys[ray] = ((unsigned long long)__float_as_uint(best.frac) << 32) | (unsigned long long)(uint32_t)best.tri;
+    const unsigned long long lm = __ballot(left);
+    if (lm) {
+        uint32_t at = 0;
+        if (lane == 0u) at = atomicAdd(&g.lcount[pass], (uint32_t)__popcll(lm));
+        at = __shfl(at, 0, 64);
+        if (left) (pass == 0u ? g.lq0 : g.lq1)[at + (uint32_t)__popcll(lm & ((1ull << lane) - 1ull))] = ray;
+    }
+}
+
+// the leftovers' state, compact, where the lane walk of an EVEN bounce reads it: half 0 of st0 / st1 and key0, which nothing reads between
+// k_shade(0) and k_shade(1)
+__global__ void __launch_bounds__(256) k_beam_gather(FrameArgs a, BeamArgs g, uint32_t which)
+{
+    const uint32_t n = g.lcount[which];
+    const uint32_t *lq = which == 0u ? g.lq0 : g.lq1;
+    const size_t np = (size_t)a.ne * a.S;
+    if (blockIdx.x == 0u && threadIdx.x == 0u) g.l_counts[MCRT_BEAM_WALK_AS] = n;
+    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < n; j += gridDim.x * 256u) {
+        const uint32_t r = lq[j];
+        a.st0[j] = a.st0[np + r]; a.st1[j] = a.st1[np + r]; a.key0[j] = MCRT_KEY_MISS;
+    }
+}
+__global__ void __launch_bounds__(256) k_beam_scatter(FrameArgs a, BeamArgs g, uint32_t which)
+{
+    const uint32_t n = g.lcount[which];
+    const uint32_t *lq = which == 0u ? g.lq0 : g.lq1;
+    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < n; j += gridDim.x * 256u) a.key1[lq[j]] = a.key0[j];
+}
+
+// bounce 1's closest hits by beams, in place of launch_trace(a, 1): the same key1 words
+hipError_t launch_beam_b1(const FrameArgs &a, const BeamArgs &g, hipStream_t st)
+{
+    const uint32_t np = a.ne * a.S, blocks = (np + 255u) / 256u;
+    const uint32_t words = g.n_beams * MCRT_BEAM_REC, setup = words > MCRT_MAX_BOUNCES * MCRT_XCDS ? words : MCRT_MAX_BOUNCES * MCRT_XCDS;
+    hipLaunchKernelGGL(k_beam_clear, dim3((setup + 255u) / 256u), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(k_beam_bounds, dim3((blocks + g.stride - 1u) / g.stride), dim3(256), 0, st, a, g);
+    hipLaunchKernelGGL(k_beam_collect, dim3(g.n_beams), dim3(BEAM_CT), 0, st, a, g);
+    hipLaunchKernelGGL(k_beam_test, dim3(blocks), dim3(256), 0, st, a, g, 0u);
+    const uint32_t which = g.near < g.cap ? 1u : 0u;
+    if (which) hipLaunchKernelGGL(k_beam_test, dim3(blocks), dim3(256), 0, st, a, g, 1u);
+    const uint32_t few = blocks < 2048u ? blocks : 2048u;
+    hipLaunchKernelGGL(k_beam_gather, dim3(few), dim3(256), 0, st, a, g, which);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    // the leftovers as the queue of an even bounce of their own: counts and cursors of their own, no packets
+    FrameArgs w = a;
+    w.counts = g.l_counts; w.cursors = g.l_cursors; w.packet_mask = 0u;
+    e = launch_trace(w, MCRT_BEAM_WALK_AS, false, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_beam_scatter, dim3(few), dim3(256), 0, st, a, g, which);
+    return hipGetLastError();
+}
+
+}  // namespace mcrt

@@ -26,6 +26,13 @@ struct PathBufs {   // sized for `paths` paths of `depth` bounces
     Buf<uint32_t> q, counts, seg_count, cursors;
     size_t paths = 0; uint32_t depth = 0;
 };
+// bounce 1 by beams (mcrt_beam.hip; BeamArgs in mcrt_kernels.h): the beams' reduction words, records and candidate lists, the leftover counters, and the
+// counts and cursors the leftovers are walked with.  Sized for `beams` beams of `cap` candidates.
+struct BeamBufs {
+    Buf<uint32_t> red, rec, lcount, l_counts, l_cursors;
+    Buf<uint4> list;
+    uint32_t beams = 0, cap = 0;
+};
 struct Work {
     Stream stream, side[MCRT_SIDE_STREAMS];   // k_march of bounce b runs on side[b % n] (n: Plan::sides)
     Event ev_bounce[MCRT_MAX_BOUNCES], ev_join[MCRT_SIDE_STREAMS], ev_done;
@@ -33,6 +40,7 @@ struct Work {
     Buf<mcrt_segment> segs;                   // [paths][depth], only for the callers that ask for segments
     Buf<int32_t> hits;                        // [paths][depth], only for the callers that ask for hit indices
     PathBufs b;
+    BeamBufs beam;
 };
 
 // tuning knobs from the environment, read ONCE at mcrt_create (never on the frame path) -- and only in a process started with
@@ -47,6 +55,10 @@ struct Knobs {
     bool retire_late = true;                   // MCRT_RETIRE_LATE=0: paths past the image are traced to their end, as before (FrameArgs::retire_late)
     bool fold_b0 = false;                      // MCRT_FOLD_B0=1: bounce 0 of a silent start medium is accumulated by k_shade itself (FrameArgs::fold_b0).  Bit-identical, one launch and
                                                // 48 B per path less, and no faster on the MI355X (profiles/retire_fold): off until a pass is found that it helps
+    uint32_t beam_b1 = 1;                      // MCRT_BEAM_B1=0|1|2: bounce 1 of a pass with one probe pose tests each scan-line's rays against its beams' triangles (mcrt_beam.hip) -- 1: where it
+                                               // would run as packets, 2: in every staged pass, 0: never
+    uint32_t beam_from = MCRT_BEAM_FROM;       // MCRT_BEAM_FROM: ... in passes of at least this many paths (MCRT_BEAM_B1=1)
+    uint32_t beam_cap = MCRT_BEAM_CAP_DEFAULT, beam_near = MCRT_BEAM_NEAR_DEFAULT;   // MCRT_BEAM_CAP, MCRT_BEAM_NEAR: candidates a beam's list holds, and how many of them the first pass tests
     bool render_row_tile = false;              // MCRT_RENDER_ROW_TILE=1: a wavefront of k_render owns 64 pixels of one picture row in place of an 8 x 8 tile (RenderArgs::row_tile)
     uint32_t speckle_fuse = MCRT_SPECKLE_FUSE_DEFAULT;   // MCRT_SPECKLE_FUSE=2|4: iterations of mcrt_speckle_frames per launch of k_srad; 4 is faster for one frame, 2 for a stack
     bool test_hooks = false;                   // MCRT_TEST_HOOKS: mcrt_debug_set_error may poison the context (tests only)
@@ -168,6 +180,7 @@ struct Instrumentation {
     Buf<unsigned long long> d_stats; bool stats_on = false;
     bool timing_on = false; int timing_level = 0;       // 1: the walk's launches are bracketed by HIP events; 2: k_shade's and k_march's too
     std::vector<TimedLaunch> ev; size_t ev_used = 0;
+    bool last_beam = false;                             // the last pass ran bounce 1 by beams (mcrt_debug_beam)
     float last_lean_bound = 0.0f; uint32_t last_march_rows = 0;   // what the last frame's kernels were given (mcrt_debug_fast_paths)
 };
 

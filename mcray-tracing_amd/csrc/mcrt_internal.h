@@ -21,6 +21,15 @@
 #define MCRT_PACKET_MASK_DEFAULT 2u   // bounces (bit b) walked a wavefront per ray packet (k_trace_packet): bounce 1 -- every pass size from two frames up and every BASELINE
                                       // configuration gains 0.3-6 % (profiles/round5/exp_packet.txt); bounce 2 is a wash, later bounces lose (packet_count_*.json)
 #define MCRT_PACKET_FROM 262144u      // ... in passes of at least this many paths (one 128 x 1024 frame at a time keeps the lane walk: its launches are cut into pieces, 1.624 vs 1.634 ms)
+#define MCRT_BEAM_FROM 2097152u        // bounce 1 by beams (mcrt_beam.hip) in passes of at least this many paths (16 frames of 128 x 1024), where bounce 1 would run as packets: the stage has fixed parts
+                                       // (one collection per beam, the bounds, seven launches) -- against packets, ms per frame at 6 / 8 / 12 / 16 / 20 / 128 frames: 0.520 / 0.446 / 0.377 / 0.341 / 0.319 / 0.252
+                                       // against 0.511 / 0.441 / 0.370 / 0.341 / 0.320 / 0.272 (profiles/beam/small_pass.txt)
+#define MCRT_BEAM_CAP_DEFAULT 512u     // candidates a beam's list holds (bounce 1 by beams, mcrt_beam.hip), at most MCRT_BEAM_CAP_MAX
+#define MCRT_BEAM_NEAR_DEFAULT 512u    // ... of which the first pass over all rays tests this many; fewer than the capacity: what is undecided then goes on as a compact queue through a second pass
+#define MCRT_BEAM_SPREAD 0.25f         // a beam whose slopes spread further than this is refused: its rays are walked
+#define MCRT_BEAM_SAMPLE_FROM 4194304u // passes of at least this many paths take every MCRT_BEAM_SAMPLE_STRIDE-th packet of the queue as the sample for the beams' bounds
+#define MCRT_BEAM_SAMPLE_STRIDE 16u    // (a ray outside its beam's bounds is a leftover: the sample only has to be large, and 32 frames' worth of a scan-line still give a beam 2000 rays;
+                                       //  which packet of the 16 is taken is hashed per wavefront, k_beam_bounds)
 #define MCRT_PATH_MAX_DEFAULT 655360u  // passes of at most this many paths take the latency form (k_path: one launch for all bounces): five 128 x 1024 frames (ms per frame at 1 / 2 / 3 / 4 / 5 / 6 frames: 0.87 / 0.77 / 0.72 / 0.69 / 0.67 / 0.65 against the staged 1.62 / 1.12 / 0.88 / 0.76 / 0.68 / 0.60)
 #define MCRT_PATH_GROUPS_DEFAULT 2u     // ... traced as this many scan-line groups on their own streams (a group's k_march runs beside the other groups' slowest wavefronts)
 #define MCRT_MAX_ROWS 2048

@@ -207,6 +207,33 @@ static void fill_group(const mcrt_ctx *c, const Work &w, mcrt::FrameArgs &a, uin
     a.packet_mask = (c->ins.stats_on || (uint64_t)a.ne * a.S < c->knobs.packet_from) ? 0u : c->knobs.packet_mask;   // bounces walked a wavefront per ray packet (k_trace_packet); the counting build walks ray by ray
 }
 
+// Bounce 1 by beams (mcrt_beam.hip): where bounce 1 runs as packets today and the pass has ONE probe pose -- every bounce-1 ray of a scan-line then starts at the
+// same point in every frame.  Not in the latency form, a counting pass or a pass with per-frame poses; MCRT_BEAM_B1=2 takes it in every other pass.
+static bool beam_wanted(const mcrt_ctx *c, const Plan &P, const mcrt::FrameArgs &a)
+{
+    if (P.latency || c->ins.stats_on || a.pose_stride != 0u || a.B < 2u || a.n_nodes == 0u) return false;
+    return c->knobs.beam_b1 == 2u || (c->knobs.beam_b1 == 1u && (a.packet_mask & 2u) != 0u && (uint64_t)a.ne * a.S >= c->knobs.beam_from);
+}
+static int fill_beam(const mcrt_ctx *c, Work &w, const mcrt::FrameArgs &a, mcrt::BeamArgs &g)
+{
+    const uint32_t beams = a.ne_frame * MCRT_BEAM_SLOTS, cap = c->knobs.beam_cap;
+    BeamBufs &b = w.beam;
+    if (beams > b.beams || cap != b.cap) {
+        HIP_TRY(hipDeviceSynchronize());
+        b.beams = b.cap = 0;
+        HIP_TRY(b.red.alloc((size_t)beams * MCRT_BEAM_REC)); HIP_TRY(b.rec.alloc((size_t)beams * MCRT_BEAM_REC)); HIP_TRY(b.list.alloc(((size_t)beams * cap + 1) * 4));
+        HIP_TRY(b.lcount.grow(8)); HIP_TRY(b.l_counts.grow(MCRT_MAX_BOUNCES + 1)); HIP_TRY(b.l_cursors.grow((size_t)MCRT_MAX_BOUNCES * MCRT_XCDS * MCRT_CURSOR_STRIDE));
+        b.beams = beams; b.cap = cap;
+    }
+    const size_t np = (size_t)a.ne * a.S;
+    g.red = b.red; g.rec = b.rec; g.list = b.list; g.lcount = b.lcount; g.l_counts = b.l_counts; g.l_cursors = b.l_cursors;
+    g.lq0 = a.queue; g.lq1 = (uint32_t *)a.st2;      // (half 0 of each: dead between k_shade(0) and k_shade(1))
+    g.n_beams = beams; g.cap = cap; g.near = std::min(c->knobs.beam_near, cap);
+    g.stride = np >= MCRT_BEAM_SAMPLE_FROM ? MCRT_BEAM_SAMPLE_STRIDE : 1u;
+    g.spread_cap = MCRT_BEAM_SPREAD;
+    return MCRT_OK;
+}
+
 // The walk kernels (k_trace_lane*, k_path) index their traversal-stack overflow with stride gridDim.x * 256 and check no bound: the
 // largest grid a group's walks can take must fit its work set, or nothing is launched
 static int check_overflow(const mcrt_ctx *c, const Plan &P, const mcrt::FrameArgs &a, const Work &w)
@@ -241,9 +268,10 @@ template <class Launch> static int timed_launch(mcrt_ctx *c, int kind, hipStream
 // (Round 4 tried holding k_march of bounce b back until the walk of bounce b+1 had claimed its last ray -- a device word raised by the walk, waited
 //  for with hipStreamWaitValue32, which the command processor releases ~1 us after the store --: 0.360 against 0.343 ms per frame at 128 frames in
 //  flight, 0.414 against 0.405 on the driver's pass, and a hang under `rocprofv3 --pmc`.  Removed; DESIGN.md A.6, profiles/round4/exp_round4_kernels.txt.)
-static int run_bounce(mcrt_ctx *c, Work &w, hipStream_t st, const mcrt::FrameArgs &a, uint32_t b, uint32_t sides, bool accumulate, bool overlap)
+static int run_bounce(mcrt_ctx *c, Work &w, hipStream_t st, const mcrt::FrameArgs &a, const mcrt::BeamArgs *beam, uint32_t b, uint32_t sides, bool accumulate, bool overlap)
 {
-    MCRT_TRY(timed_launch(c, 0, st, [&] { return mcrt::launch_trace(a, b, c->ins.stats_on, st); }));
+    if (beam && b == 1u) MCRT_TRY(timed_launch(c, 0, st, [&] { return mcrt::launch_beam_b1(a, *beam, st); }));
+    else MCRT_TRY(timed_launch(c, 0, st, [&] { return mcrt::launch_trace(a, b, c->ins.stats_on, st); }));
     MCRT_TRY(timed_launch(c, 1, st, [&] { return mcrt::launch_shade(a, b, c->ins.stats_on, st); }));
     if (!accumulate || (a.fold_b0 && b == 0u)) return MCRT_OK;      // (bounce 0 folded: k_shade has added its echoes; later bounces keep their side streams)
     hipStream_t ms = st;
@@ -255,7 +283,7 @@ static int run_bounce(mcrt_ctx *c, Work &w, hipStream_t st, const mcrt::FrameArg
     return timed_launch(c, 2, ms, [&] { return mcrt::launch_march(a, b, c->ins.stats_on, ms); });
 }
 
-static int enqueue_pass(mcrt_ctx *c, const Plan &P, const mcrt::FrameArgs *args, Work *const *ws, bool accumulate)
+static int enqueue_pass(mcrt_ctx *c, const Plan &P, const mcrt::FrameArgs *args, const mcrt::BeamArgs *const *beams, Work *const *ws, bool accumulate)
 {
     const bool overlap = !c->knobs.no_overlap;
     hipStream_t gst[16] = { c->stream };
@@ -276,7 +304,7 @@ static int enqueue_pass(mcrt_ctx *c, const Plan &P, const mcrt::FrameArgs *args,
     } else {
         for (uint32_t b = 0; b < c->p.max_depth; b++)
             for (uint32_t g = 0; g < P.groups; g++) {
-                MCRT_TRY(run_bounce(c, *ws[g], gst[g], args[g], b, P.sides[g], accumulate, overlap));
+                MCRT_TRY(run_bounce(c, *ws[g], gst[g], args[g], beams[g], b, P.sides[g], accumulate, overlap));
             }
     }
     for (uint32_t g = 0; g < P.groups; g++) {
@@ -300,6 +328,7 @@ static int run_pass(mcrt_ctx *c, uint32_t frame, uint32_t n_frames, uint32_t e0,
 {
     const Plan P = plan_pass(c, e0, e1, n_frames, one_group);
     mcrt::FrameArgs pass, args[16];
+    mcrt::BeamArgs bargs[16]; const mcrt::BeamArgs *beams[16] = {};
     Work *ws[16];
     fill_pass(c, P, pass, frame, e1 - e0, accumulate, out, pose_pos, pose_dir);
     for (uint32_t g = 0; g < P.groups; g++) {
@@ -308,8 +337,10 @@ static int run_pass(mcrt_ctx *c, uint32_t frame, uint32_t n_frames, uint32_t e0,
         args[g] = pass;
         fill_group(c, *ws[g], args[g], n_frames, P.e[g], P.e[g + 1], e0, out);
         MCRT_TRY(check_overflow(c, P, args[g], *ws[g]));
+        if (beam_wanted(c, P, args[g])) { MCRT_TRY(fill_beam(c, *ws[g], args[g], bargs[g])); beams[g] = &bargs[g]; }
     }
-    return enqueue_pass(c, P, args, ws, accumulate);
+    c->ins.last_beam = beams[0] != nullptr;
+    return enqueue_pass(c, P, args, beams, ws, accumulate);
 }
 
 // the traced block's accumulators [lines][R] into rf_dev; k_finalize leaves them zeroed (ensure_acc)

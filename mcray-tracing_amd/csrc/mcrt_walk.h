@@ -156,4 +156,42 @@ template <class LS> MCRT_DEV uint32_t lane_leaf_test(const FrameArgs &a, const L
     return cnt;
 }
 
+// ---- triangles through the SCALAR cache (k_trace_packet's leaves, k_beam_test's candidates): the record is wave-uniform, every lane tests it against ITS ray ----
+typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+MCRT_DEV u32x16 sload16(const void *p) { u32x16 r; asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(p) : "memory"); return r; }
+MCRT_DEV u32x8 sload8(const void *p) { u32x8 r; asm volatile("s_load_dwordx8 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(p) : "memory"); return r; }
+MCRT_DEV u32x4 sload4(const void *p) { u32x4 r; asm volatile("s_load_dwordx4 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(p) : "memory"); return r; }
+
+// the contract's triangle test of one wave-uniform record (A: v0 | id, v1 | -; C2: v2 | edge tolerance) by every lane `on`, with the early exits of a
+// wavefront: lane_leaf_test's expressions, so a lane's closest hit is the lane walk's bit for bit
+MCRT_DEV void packet_tri_test(const u32x8 A, const u32x4 C2, const f3 f2, const f3 to, const f3 inv, const f3 rc, const float pad_abs, const bool on, Best &best)
+{
+    const f3 v0 = mk(__uint_as_float(A[0]), __uint_as_float(A[1]), __uint_as_float(A[2])), v1 = mk(__uint_as_float(A[4]), __uint_as_float(A[5]), __uint_as_float(A[6]));
+    const f3 v2 = mk(__uint_as_float(C2[0]), __uint_as_float(C2[1]), __uint_as_float(C2[2]));
+    const int id = (int)A[3];
+    const float edge_tol = __uint_as_float(C2[3]);
+    const float4 P = tri_plane(v0, v1, v2);
+    const f3 nrm = xyz(P);
+    const float da = dot(nrm, f2) - P.w;
+    const float db = dot(nrm, to) - P.w;
+    bool ok = on && da * db < 0.0f;
+    if (!__any(ok)) return;
+    const float proj = da - db;
+    const float frac = da / proj;
+    ok = ok && (frac < best.frac || (frac == best.frac && id < best.tri)) && frac >= 0.0f;
+    if (!__any(ok)) return;
+    float tmin, tmax;
+    f3 plo, phi;
+    tri_padded_bounds(v0, v1, v2, pad_abs, plo, phi);
+    ok = ok && slab_c(plo, phi, rc, inv, 0.0f, 1.0f, tmin, tmax) && frac >= tmin && frac <= tmax;
+    if (!__any(ok)) return;
+    const float s = 1.0f - frac;
+    const f3 p = mk(s * f2.x + frac * to.x, s * f2.y + frac * to.y, s * f2.z + frac * to.z);
+    const f3 p0 = v0 - p, p1 = v1 - p, p2 = v2 - p;
+    ok = ok && dot(cross(p0, p1), nrm) >= edge_tol && dot(cross(p1, p2), nrm) >= edge_tol && dot(cross(p2, p0), nrm) >= edge_tol;
+    if (ok) { best.frac = frac; best.tri = id; }
+}
+
 }  // namespace mcrt

@@ -431,15 +431,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MCRT_L
 // bounce 1, 1.7 x at bounce 2, 7 x at bounce 9 (a wavefront's 64 neighbours then belong to several histories) -- so launch_trace takes it only
 // for the bounces named in FrameArgs::packet_mask.
 // =============================================================================================================
-typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-MCRT_DEV u32x16 sload16(const void *p) { u32x16 r; asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(p) : "memory"); return r; }
-MCRT_DEV u32x8 sload8(const void *p) { u32x8 r; asm volatile("s_load_dwordx8 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(p) : "memory"); return r; }
 // entry `l` (wave-uniform) of the wavefront's stack register becomes the wave-uniform value `v`: a vector compare and select (v_writelane_b32 wants the lane
 // number in M0 and its moves on the scalar ALU, the pipe this kernel is short of)
 MCRT_DEV int writelane(int v, int l, int old) { return (int)(threadIdx.x & 63u) == l ? v : old; }
-MCRT_DEV u32x4 sload4(const void *p) { u32x4 r; asm volatile("s_load_dwordx4 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(p) : "memory"); return r; }
 
 // the same with the node's packed word in a SCALAR register (k_trace_packet: the node is wave-uniform)
 MCRT_DEV Planes4 planes4_s(uint32_t w01, uint32_t w23, float c, float inv)
@@ -528,30 +522,7 @@ MCRT_DEV void packet_walk(const FrameArgs &a, const LaneRay &lr, const f3 f2, co
             for (uint32_t k = 0; k < cnt; k++) {
                 const char *T = (const char *)a.tris + (size_t)(first + k) * (16u * MCRT_TRI_PIECES);
                 const u32x8 A = sload8(T); const u32x4 C2 = sload4(T + 32);
-                const f3 v0 = mk(__uint_as_float(A[0]), __uint_as_float(A[1]), __uint_as_float(A[2])), v1 = mk(__uint_as_float(A[4]), __uint_as_float(A[5]), __uint_as_float(A[6]));
-                const f3 v2 = mk(__uint_as_float(C2[0]), __uint_as_float(C2[1]), __uint_as_float(C2[2]));
-                const int id = (int)A[3];
-                const float edge_tol = __uint_as_float(C2[3]);
-                const float4 P = tri_plane(v0, v1, v2);
-                const f3 nrm = xyz(P);
-                const float da = dot(nrm, f2) - P.w;
-                const float db = dot(nrm, to) - P.w;
-                bool ok = da * db < 0.0f;
-                if (!__any(ok)) continue;
-                const float proj = da - db;
-                const float frac = da / proj;
-                ok = ok && (frac < best.frac || (frac == best.frac && id < best.tri)) && frac >= 0.0f;
-                if (!__any(ok)) continue;
-                float tmin, tmax;
-                f3 plo, phi;
-                tri_padded_bounds(v0, v1, v2, a.pad_abs, plo, phi);
-                ok = ok && slab_c(plo, phi, rc, inv, 0.0f, 1.0f, tmin, tmax) && frac >= tmin && frac <= tmax;
-                if (!__any(ok)) continue;
-                const float s = 1.0f - frac;
-                const f3 p = mk(s * f2.x + frac * to.x, s * f2.y + frac * to.y, s * f2.z + frac * to.z);
-                const f3 p0 = v0 - p, p1 = v1 - p, p2 = v2 - p;
-                ok = ok && dot(cross(p0, p1), nrm) >= edge_tol && dot(cross(p1, p2), nrm) >= edge_tol && dot(cross(p2, p0), nrm) >= edge_tol;
-                if (ok) { best.frac = frac; best.tri = id; }
+                packet_tri_test(A, C2, f2, to, inv, rc, a.pad_abs, true, best);
             }
         }
         if (sp == 0) break;
