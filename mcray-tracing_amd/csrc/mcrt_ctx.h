@@ -197,7 +197,7 @@ struct mcrt_ctx {
     Buf<float2> d_tex; uint32_t tex_n = 0; bool tex_finite = false;
     Buf<float> d_pos, d_dir; uint32_t n_el = 0;          // the transducer
     Buf<int> label_ovf;                                   // traversal-stack overflow of k_label's walk (mcrt_label_frames)
-    Staging pose_stage[2];                                // per-frame probe poses handed over as host memory: positions, directions (mcrt_trace_frames_poses, mcrt_label_frames)
+    Staging pose_stage[2];                                // per-frame probe poses handed over as host memory: positions, directions (mcrt::stage_poses)
     Tables tab;
     Accumulators acc;
     ImageStages img;
@@ -206,4 +206,5 @@ struct mcrt_ctx {
 
 namespace mcrt {
 int check_device_error(mcrt_ctx *c);   // mcrt_api.cpp: the device's error word, read and cleared (the stream is idle)
+int stage_poses(mcrt_ctx *c, size_t lines, const float *dev[2]);   // mcrt_trace.cpp: host pose tables [lines][3] through pose_stage, positions then directions; dev[k] becomes the device's
 }

@@ -1,9 +1,10 @@
 // mcrt_image.cpp -- the image stages of the C-ABI (include/mcrt.h): PSF, elevation, envelope, scan conversion, B-mode, compounding,
 // volume imaging and rendering, speckle reduction, freehand reconstruction, RF export / import.  Host C++ only.  Of a context (mcrt_ctx.h) these read
-// its device, its stream, p.speed_of_sound, c.max_travel_us, knobs.render_row_tile, knobs.speckle_fuse, the pose staging (pose_stage:
-// mcrt_recon_frames) and the image stages' own state (ImageStages), nothing else.
+// its device, its stream, p.speed_of_sound, c.max_travel_us, knobs.render_row_tile, knobs.speckle_fuse, the pose staging (mcrt::stage_poses:
+// the two recon calls) and the image stages' own state (ImageStages), nothing else.
 #include "mcrt_ctx.h"
 #include "mcrt_kernels.h"
+#include "mcrt_voxels.h"            // recon_tiling
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -17,6 +18,20 @@ static bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t 
 {
     const uintptr_t a0 = (uintptr_t)a, a1 = a0 + a_bytes, b0 = (uintptr_t)b, b1 = b0 + b_bytes;
     return a0 < b1 && b0 < a1;
+}
+
+// A call's input and its optional outputs must not share memory: the input against each output that is there, in turn, and (among) that output against the ones
+// before it.  The first pair that overlaps is the one reported.
+struct Range { const void *p; size_t bytes; const char *name; };
+static int check_overlap(const char *fn, const Range &in, const Range *outs, int n, bool among)
+{
+    for (int i = 0; i < n; i++) {
+        if (!outs[i].p) continue;
+        if (ranges_overlap(in.p, in.bytes, outs[i].p, outs[i].bytes)) return set_error(MCRT_ERR_INVALID, "%s: %s and %s overlap", fn, in.name, outs[i].name);
+        for (int j = 0; among && j < i; j++)
+            if (outs[j].p && ranges_overlap(outs[j].p, outs[j].bytes, outs[i].p, outs[i].bytes)) return set_error(MCRT_ERR_INVALID, "%s: %s and %s overlap", fn, outs[j].name, outs[i].name);
+    }
+    return MCRT_OK;
 }
 
 static int ensure_tmp(mcrt_ctx *c, size_t n)
@@ -412,6 +427,13 @@ static int render_view_limits(const char *fn, uint32_t n_frames, uint32_t nu, ui
     if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 frames per call (%u)", fn, n_frames);
     return MCRT_OK;
 }
+static mcrt::ViewArgs view_args(const mcrt_render_view *view, uint32_t n_frames, uint32_t nu, uint32_t nv, uint32_t nw)
+{
+    mcrt::ViewArgs a;
+    for (int k = 0; k < 3; k++) { a.origin[k] = view->origin[k]; a.di[k] = view->di[k]; a.dj[k] = view->dj[k]; a.ds[k] = view->ds[k]; }
+    a.nx = view->nx; a.ny = view->ny; a.n_steps = view->n_steps; a.F = n_frames; a.nu = nu; a.nv = nv; a.nw = nw;
+    return a;
+}
 
 // Everything is checked before anything is launched; the derived floats are made here, in double, rounded once.
 extern "C" int mcrt_render_frames(mcrt_ctx *c, const void *vol_dev, int in_u8, uint32_t n_frames, uint32_t nu, uint32_t nv, uint32_t nw,
@@ -436,14 +458,10 @@ extern "C" int mcrt_render_frames(mcrt_ctx *c, const void *vol_dev, int in_u8, u
     if (!(o->t_cut >= 0.0f && o->t_cut < 1.0f)) return set_error(MCRT_ERR_INVALID, "%s: t_cut must be in [0,1) (%g)", fn, (double)o->t_cut);
     MCRT_TRY(render_view_limits(fn, n_frames, nu, nv, nw, view));
     const size_t nvox = (size_t)nu * nv * nw, npix = (size_t)view->nx * view->ny, vol_bytes = (in_u8 ? 1u : 4u) * (size_t)n_frames * nvox;
-    const struct { const void *p; size_t bytes; const char *name; } outs[3] = { { out_dev, 4 * n_frames * npix, "out_dev" }, { out8_dev, n_frames * npix, "out8_dev" },
-                                                                               { depth_dev, 4 * n_frames * npix, "depth_dev" } };
-    for (const auto &q : outs)
-        if (q.p && ranges_overlap(vol_dev, vol_bytes, q.p, q.bytes)) return set_error(MCRT_ERR_INVALID, "%s: vol_dev and %s overlap", fn, q.name);
+    const Range outs[3] = { { out_dev, 4 * n_frames * npix, "out_dev" }, { out8_dev, n_frames * npix, "out8_dev" }, { depth_dev, 4 * n_frames * npix, "depth_dev" } };
+    MCRT_TRY(check_overlap(fn, Range{ vol_dev, vol_bytes, "vol_dev" }, outs, 3, false));     // (the outputs are not held against each other)
     mcrt::RenderArgs a;
-    a.vol = vol_dev; a.out = out_dev; a.out8 = out8_dev; a.depth = depth_dev;
-    for (int k = 0; k < 3; k++) { a.origin[k] = view->origin[k]; a.di[k] = view->di[k]; a.dj[k] = view->dj[k]; a.ds[k] = view->ds[k]; }
-    a.nx = view->nx; a.ny = view->ny; a.n_steps = view->n_steps; a.F = n_frames; a.nu = nu; a.nv = nv; a.nw = nw;
+    a.vol = vol_dev; a.out = out_dev; a.out8 = out8_dev; a.depth = depth_dev; a.view = view_args(view, n_frames, nu, nv, nw);
     a.mode = o->mode; a.row_tile = c->knobs.render_row_tile ? 1u : 0u;
     a.lo = o->lo; a.inv_range = inv_range;
     a.threshold = o->threshold; a.inv_ramp = inv_ramp; a.opacity = o->opacity; a.depth_cue = o->depth_cue; a.t_cut = o->t_cut;
@@ -466,9 +484,7 @@ extern "C" int mcrt_render_label_frames(mcrt_ctx *c, const uint8_t *label_dev, u
     if (ranges_overlap(label_dev, n_frames * nvox, out_dev, n_frames * npix)) return set_error(MCRT_ERR_INVALID, "%s: label_dev and out_dev overlap", fn);
     if (ranges_overlap(depth_dev, 4 * n_frames * npix, out_dev, n_frames * npix)) return set_error(MCRT_ERR_INVALID, "%s: depth_dev and out_dev overlap", fn);
     mcrt::RenderLabelArgs a;
-    a.labels = label_dev; a.depth = depth_dev; a.out = out_dev;
-    for (int k = 0; k < 3; k++) { a.origin[k] = view->origin[k]; a.di[k] = view->di[k]; a.dj[k] = view->dj[k]; a.ds[k] = view->ds[k]; }
-    a.nx = view->nx; a.ny = view->ny; a.n_steps = view->n_steps; a.F = n_frames; a.nu = nu; a.nv = nv; a.nw = nw;
+    a.labels = label_dev; a.depth = depth_dev; a.out = out_dev; a.view = view_args(view, n_frames, nu, nv, nw);
     HIP_TRY(mcrt::launch_render_label(a, c->stream));
     return MCRT_OK;
 }
@@ -516,9 +532,56 @@ extern "C" int mcrt_speckle_frames(mcrt_ctx *c, const float *in_dev, uint32_t n_
     return MCRT_OK;
 }
 
-// ---- freehand 3-D reconstruction (the contract is in include/mcrt.h; the defaults and the transform are host code: mcrt_host.cpp) ----
-// Everything is checked before anything is launched.  Then, on the context's stream: host pose tables through the context's pose staging
-// (as mcrt_trace_frames_poses stages them), one clear of the accumulators (and of stats_dev), k_recon_splat, k_recon_resolve.
+// ---- freehand 3-D reconstruction (the contracts are in include/mcrt.h; the defaults and the transform are host code: mcrt_host.cpp) ----
+// What mcrt_recon_frames and mcrt_recon_label_frames ask and do alike, in parts as the view checks are: each call has option checks of its own between them, and
+// which fault of several a call reports is part of its behaviour.  The argument errors, the fill options, the block, the limits, and what is enqueued first.
+static int recon_invalid(const char *fn, uint32_t n_frames, uint32_t E, uint32_t R, double row_mm, double unit_mm)
+{
+    if (n_frames == 0 || E == 0 || R == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, n_elements %u, n_rows %u)", fn, n_frames, E, R);
+    if (!(std::isfinite(row_mm) && row_mm > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: row_mm must be finite and > 0 (%g)", fn, row_mm);
+    if (!(std::isfinite(unit_mm) && unit_mm > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: unit_mm must be finite and > 0 (%g)", fn, unit_mm);
+    return MCRT_OK;
+}
+static int recon_fill_invalid(const char *fn, uint32_t fill_radius, uint32_t fill_min)
+{
+    if (fill_radius > RECON_MAX_FILL) return set_error(MCRT_ERR_INVALID, "%s: fill_radius must be 0..%d (%u)", fn, RECON_MAX_FILL, fill_radius);
+    return fill_min == 0u ? set_error(MCRT_ERR_INVALID, "%s: fill_min must be >= 1", fn) : MCRT_OK;
+}
+// the one place that fills a ReconBlock: the grid's transform (which refuses a grid itself), row_u (the caller says what it says when that is no finite float), the
+// rest as the caller has it.  The limits follow: n_samples is checked before it is used, and pos / dir may still be host tables (recon_begin)
+static int recon_block(mcrt::ReconBlock &k, uint32_t n_frames, uint32_t E, uint32_t R, const float *pos, const float *dir, double row_mm, double unit_mm, const mcrt_volume_grid *g,
+                       uint32_t fill_radius, uint32_t fill_min, uint32_t *stats_dev)
+{
+    MCRT_TRY(mcrt_recon_transform(g, unit_mm, k.A, k.b));
+    k.row_u = (float)(row_mm / unit_mm); k.pos = pos; k.dir = dir; k.stats = stats_dev;
+    k.R = R; k.n_samples = (uint32_t)((size_t)n_frames * E * R); k.nu = g->nu; k.nv = g->nv; k.nw = g->nw; k.fill_radius = fill_radius; k.fill_min = fill_min;
+    return MCRT_OK;
+}
+static int recon_limits(const char *fn, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_volume_grid *g, uint32_t fill_radius)
+{
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: at most %d rows (%u)", fn, MCRT_MAX_ROWS, R);
+    if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 frames per call (%u)", fn, n_frames);
+    if ((double)n_frames * (double)E * (double)R >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: a stack of 2^31 samples or more (%u x %u x %u)", fn, n_frames, E, R);
+    if ((double)g->nu * (double)g->nv * (double)g->nw >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: grid: 2^31 voxels or more (%u x %u x %u)", fn, g->nu, g->nv, g->nw);
+    mcrt::ReconTiling t;
+    if (!mcrt::recon_tiling(g->nu, g->nv, g->nw, fill_radius, t))        // (the radius was looked at before)
+        return set_error(MCRT_ERR_LIMIT, "%s: grid: 2^24 tiles of %d x %d x %d voxels or more (%u x %u x %u): too thin a block", fn, RECON_TU, RECON_TV, RECON_TW, g->nu, g->nv, g->nw);
+    return MCRT_OK;
+}
+// after the last check, what both calls enqueue first: the call's scratch grown to `words` (after a stream synchronise: an earlier call may still be using it), host pose
+// tables through the context's pose staging (as mcrt_trace_frames_poses stages them), one clear of the scratch and one of stats_dev
+template <class T> static int recon_begin(mcrt_ctx *c, mcrt::ReconBlock &k, uint32_t n_frames, uint32_t E, Buf<T> &scratch, size_t words)
+{
+    if (words > scratch.cap) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(scratch.alloc(words)); }
+    const float *tab[2] = { k.pos, k.dir };
+    MCRT_TRY(mcrt::stage_poses(c, (size_t)n_frames * E, tab));
+    k.pos = tab[0]; k.dir = tab[1];
+    HIP_TRY(hipMemsetAsync(scratch, 0, sizeof(T) * words, c->stream));
+    if (k.stats) HIP_TRY(hipMemsetAsync(k.stats, 0, 8, c->stream));
+    return MCRT_OK;
+}
+
+// Everything is checked before anything is launched.  Then, on the context's stream: recon_begin, k_recon_splat, k_recon_resolve.
 extern "C" int mcrt_recon_frames(mcrt_ctx *c, const float *stack_dev, uint32_t n_frames, uint32_t E, uint32_t R, const float *pos, const float *dir,
                                  double row_mm, double unit_mm, const mcrt_volume_grid *g, const mcrt_recon_opts *o, float *out_dev, uint32_t *count_dev,
                                  uint32_t *stats_dev)
@@ -527,66 +590,33 @@ extern "C" int mcrt_recon_frames(mcrt_ctx *c, const float *stack_dev, uint32_t n
     static const char fn[] = "mcrt_recon_frames";
     if (!stack_dev || !pos || !dir || !g || !out_dev)
         return set_error(MCRT_ERR_INVALID, "%s: null %s", fn, !stack_dev ? "stack_dev" : !pos ? "pos" : !dir ? "dir" : !g ? "grid" : "out_dev");
-    if (n_frames == 0 || E == 0 || R == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, n_elements %u, n_rows %u)", fn, n_frames, E, R);
-    if (!(std::isfinite(row_mm) && row_mm > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: row_mm must be finite and > 0 (%g)", fn, row_mm);
-    if (!(std::isfinite(unit_mm) && unit_mm > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: unit_mm must be finite and > 0 (%g)", fn, unit_mm);
+    MCRT_TRY(recon_invalid(fn, n_frames, E, R, row_mm, unit_mm));
     mcrt_recon_opts d;
     if (!o) { mcrt_default_recon_opts(&d); o = &d; }
     if (o->mode != MCRT_RECON_MEAN && o->mode != MCRT_RECON_MAX) return set_error(MCRT_ERR_INVALID, "%s: unknown mode %u", fn, o->mode);
     if (!(std::isfinite(o->value_max) && o->value_max > 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: value_max must be finite and > 0 (%g)", fn, (double)o->value_max);
-    if (o->fill_radius > RECON_MAX_FILL) return set_error(MCRT_ERR_INVALID, "%s: fill_radius must be 0..%d (%u)", fn, RECON_MAX_FILL, o->fill_radius);
-    if (o->fill_min == 0u) return set_error(MCRT_ERR_INVALID, "%s: fill_min must be >= 1", fn);
+    MCRT_TRY(recon_fill_invalid(fn, o->fill_radius, o->fill_min));
     if (!std::isfinite(o->empty)) return set_error(MCRT_ERR_INVALID, "%s: empty must be finite", fn);
     mcrt::ReconArgs a;
     memset(&a, 0, sizeof a);
-    MCRT_TRY(mcrt_recon_transform(g, unit_mm, a.A, a.b));
-    a.row_u = (float)(row_mm / unit_mm);
+    MCRT_TRY(recon_block(a.blk, n_frames, E, R, pos, dir, row_mm, unit_mm, g, o->fill_radius, o->fill_min, stats_dev));
     a.qscale = 0x1p31 / (double)o->value_max;
-    if (!(std::isfinite(a.row_u) && std::isfinite(a.qscale))) return set_error(MCRT_ERR_INVALID, "%s: row_mm / unit_mm or 2^31 / value_max is not finite (%g, %g)", fn, (double)a.row_u, a.qscale);
-    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: at most %d rows (%u)", fn, MCRT_MAX_ROWS, R);
-    if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 frames per call (%u)", fn, n_frames);
-    if ((double)n_frames * (double)E * (double)R >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: a stack of 2^31 samples or more (%u x %u x %u)", fn, n_frames, E, R);
-    if ((double)g->nu * (double)g->nv * (double)g->nw >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: grid: 2^31 voxels or more (%u x %u x %u)", fn, g->nu, g->nv, g->nw);
-    const uint64_t tiles = (uint64_t)((g->nu + RECON_TU - 1u) / RECON_TU) * ((g->nv + RECON_TV - 1u) / RECON_TV) * ((g->nw + RECON_TW - 1u) / RECON_TW);
-    if (tiles >= RECON_MAX_TILES)
-        return set_error(MCRT_ERR_LIMIT, "%s: grid: 2^24 tiles of %d x %d x %d voxels or more (%u x %u x %u): too thin a block", fn, RECON_TU, RECON_TV, RECON_TW, g->nu, g->nv, g->nw);
-    const size_t ns = (size_t)n_frames * E * R, n = (size_t)g->nu * g->nv * g->nw, lines = (size_t)n_frames * E;
-    const struct { const void *p; size_t bytes; const char *name; } outs[3] = { { out_dev, 4 * n, "out_dev" }, { count_dev, 4 * n, "count_dev" }, { stats_dev, 8, "stats_dev" } };
-    for (int i = 0; i < 3; i++) {
-        if (!outs[i].p) continue;
-        if (ranges_overlap(stack_dev, 4 * ns, outs[i].p, outs[i].bytes)) return set_error(MCRT_ERR_INVALID, "%s: stack_dev and %s overlap", fn, outs[i].name);
-        for (int j = 0; j < i; j++)
-            if (outs[j].p && ranges_overlap(outs[j].p, outs[j].bytes, outs[i].p, outs[i].bytes)) return set_error(MCRT_ERR_INVALID, "%s: %s and %s overlap", fn, outs[j].name, outs[i].name);
-    }
+    if (!(std::isfinite(a.blk.row_u) && std::isfinite(a.qscale))) return set_error(MCRT_ERR_INVALID, "%s: row_mm / unit_mm or 2^31 / value_max is not finite (%g, %g)", fn, (double)a.blk.row_u, a.qscale);
+    MCRT_TRY(recon_limits(fn, n_frames, E, R, g, o->fill_radius));
+    const size_t ns = (size_t)n_frames * E * R, n = (size_t)g->nu * g->nv * g->nw;
+    const Range outs[3] = { { out_dev, 4 * n, "out_dev" }, { count_dev, 4 * n, "count_dev" }, { stats_dev, 8, "stats_dev" } };
+    MCRT_TRY(check_overlap(fn, Range{ stack_dev, 4 * ns, "stack_dev" }, outs, 3, true));
     const size_t words = n + (n + 1u) / 2u;               // n sums, then n counts
-    if (words > c->img.d_recon.cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(c->img.d_recon.alloc(words));
-    }
-    const float *tab[2] = { pos, dir };
-    for (int k = 0; k < 2; k++) {
-        if (is_device_pointer(tab[k])) continue;
-        float *h = nullptr;
-        MCRT_TRY(c->pose_stage[k].begin(3 * lines, c->stream, &h));
-        memcpy(h, tab[k], 12 * lines);
-        MCRT_TRY(c->pose_stage[k].commit(3 * lines, c->stream));
-        tab[k] = c->pose_stage[k].dev;
-    }
-    a.stack = stack_dev; a.pos = tab[0]; a.dir = tab[1];
-    a.sum = c->img.d_recon; a.count = (uint32_t *)(c->img.d_recon.p + n);
-    a.out = out_dev; a.count_out = count_dev; a.stats = stats_dev;
-    a.R = R; a.n_samples = (uint32_t)ns; a.nu = g->nu; a.nv = g->nv; a.nw = g->nw;
-    a.mode = o->mode; a.fill_radius = o->fill_radius; a.fill_min = o->fill_min;
-    a.value_max = o->value_max; a.empty = o->empty;
-    HIP_TRY(hipMemsetAsync(c->img.d_recon, 0, 8 * words, c->stream));
-    if (stats_dev) HIP_TRY(hipMemsetAsync(stats_dev, 0, 8, c->stream));
+    MCRT_TRY(recon_begin(c, a.blk, n_frames, E, c->img.d_recon, words));
+    a.stack = stack_dev; a.sum = c->img.d_recon; a.count = (uint32_t *)(c->img.d_recon.p + n); a.out = out_dev; a.count_out = count_dev;
+    a.mode = o->mode; a.value_max = o->value_max; a.empty = o->empty;
     HIP_TRY(mcrt::launch_recon_splat(a, c->stream));
     HIP_TRY(mcrt::launch_recon_resolve(a, c->stream));
     return MCRT_OK;
 }
 
-// a freehand label volume by majority vote (the contract is in include/mcrt.h): mcrt_recon_frames' checks with the tissue stack in the float
-// stack's place; then the pose staging, one clear of the vote table (and of stats_dev), k_recon_label_splat, k_recon_label_resolve
+// a freehand label volume by majority vote: mcrt_recon_frames' checks with the tissue stack in the float stack's place; then recon_begin,
+// k_recon_label_splat, k_recon_label_resolve
 extern "C" int mcrt_recon_label_frames(mcrt_ctx *c, const uint8_t *stack_dev, uint32_t n_frames, uint32_t E, uint32_t R, const float *pos, const float *dir,
                                        double row_mm, double unit_mm, const mcrt_volume_grid *g, const mcrt_recon_label_opts *o, uint8_t *out_dev,
                                        uint32_t *count_dev, uint32_t *votes_dev, uint32_t *stats_dev)
@@ -596,53 +626,21 @@ extern "C" int mcrt_recon_label_frames(mcrt_ctx *c, const uint8_t *stack_dev, ui
     if (!stack_dev || !pos || !dir || !g || !o)
         return set_error(MCRT_ERR_INVALID, "%s: null %s", fn, !stack_dev ? "stack_dev" : !pos ? "pos" : !dir ? "dir" : !g ? "grid" : "options");
     if (!out_dev && !count_dev && !votes_dev && !stats_dev) return set_error(MCRT_ERR_INVALID, "%s: out_dev, count_dev, votes_dev and stats_dev are all null", fn);
-    if (n_frames == 0 || E == 0 || R == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, n_elements %u, n_rows %u)", fn, n_frames, E, R);
-    if (!(std::isfinite(row_mm) && row_mm > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: row_mm must be finite and > 0 (%g)", fn, row_mm);
-    if (!(std::isfinite(unit_mm) && unit_mm > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: unit_mm must be finite and > 0 (%g)", fn, unit_mm);
+    MCRT_TRY(recon_invalid(fn, n_frames, E, R, row_mm, unit_mm));
     if (o->n_labels == 0u || o->n_labels > 254u) return set_error(MCRT_ERR_INVALID, "%s: n_labels must be 1..254 (%u)", fn, o->n_labels);
-    if (o->fill_radius > RECON_MAX_FILL) return set_error(MCRT_ERR_INVALID, "%s: fill_radius must be 0..%d (%u)", fn, RECON_MAX_FILL, o->fill_radius);
-    if (o->fill_min == 0u) return set_error(MCRT_ERR_INVALID, "%s: fill_min must be >= 1", fn);
+    MCRT_TRY(recon_fill_invalid(fn, o->fill_radius, o->fill_min));
     mcrt::ReconLabelArgs a;
     memset(&a, 0, sizeof a);
-    MCRT_TRY(mcrt_recon_transform(g, unit_mm, a.A, a.b));
-    a.row_u = (float)(row_mm / unit_mm);
-    if (!std::isfinite(a.row_u)) return set_error(MCRT_ERR_INVALID, "%s: row_mm / unit_mm is not finite (%g)", fn, (double)a.row_u);
-    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: at most %d rows (%u)", fn, MCRT_MAX_ROWS, R);
-    if (n_frames > 65535u) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 frames per call (%u)", fn, n_frames);
-    if ((double)n_frames * (double)E * (double)R >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: a stack of 2^31 samples or more (%u x %u x %u)", fn, n_frames, E, R);
-    if ((double)g->nu * (double)g->nv * (double)g->nw >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: grid: 2^31 voxels or more (%u x %u x %u)", fn, g->nu, g->nv, g->nw);
-    const uint64_t tiles = (uint64_t)((g->nu + RECON_TU - 1u) / RECON_TU) * ((g->nv + RECON_TV - 1u) / RECON_TV) * ((g->nw + RECON_TW - 1u) / RECON_TW);
-    if (tiles >= RECON_MAX_TILES)
-        return set_error(MCRT_ERR_LIMIT, "%s: grid: 2^24 tiles of %d x %d x %d voxels or more (%u x %u x %u): too thin a block", fn, RECON_TU, RECON_TV, RECON_TW, g->nu, g->nv, g->nw);
-    const size_t ns = (size_t)n_frames * E * R, n = (size_t)g->nu * g->nv * g->nw, lines = (size_t)n_frames * E, words = n * o->n_labels;
+    MCRT_TRY(recon_block(a.blk, n_frames, E, R, pos, dir, row_mm, unit_mm, g, o->fill_radius, o->fill_min, stats_dev));
+    if (!std::isfinite(a.blk.row_u)) return set_error(MCRT_ERR_INVALID, "%s: row_mm / unit_mm is not finite (%g)", fn, (double)a.blk.row_u);
+    MCRT_TRY(recon_limits(fn, n_frames, E, R, g, o->fill_radius));
+    const size_t ns = (size_t)n_frames * E * R, n = (size_t)g->nu * g->nv * g->nw, words = n * o->n_labels;
     if (words >= 0x80000000ull) return set_error(MCRT_ERR_LIMIT, "%s: a vote table of 2^31 words or more (%u x %u x %u voxels x %u labels)", fn, g->nu, g->nv, g->nw, o->n_labels);
-    const struct { const void *p; size_t bytes; const char *name; } outs[4] = { { out_dev, n, "out_dev" }, { count_dev, 4 * n, "count_dev" }, { votes_dev, 4 * n, "votes_dev" },
-                                                                               { stats_dev, 8, "stats_dev" } };
-    for (int i = 0; i < 4; i++) {
-        if (!outs[i].p) continue;
-        if (ranges_overlap(stack_dev, ns, outs[i].p, outs[i].bytes)) return set_error(MCRT_ERR_INVALID, "%s: stack_dev and %s overlap", fn, outs[i].name);
-        for (int j = 0; j < i; j++)
-            if (outs[j].p && ranges_overlap(outs[j].p, outs[j].bytes, outs[i].p, outs[i].bytes)) return set_error(MCRT_ERR_INVALID, "%s: %s and %s overlap", fn, outs[j].name, outs[i].name);
-    }
-    if (words > c->img.d_votes.cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(c->img.d_votes.alloc(words));
-    }
-    const float *tab[2] = { pos, dir };
-    for (int k = 0; k < 2; k++) {
-        if (is_device_pointer(tab[k])) continue;
-        float *h = nullptr;
-        MCRT_TRY(c->pose_stage[k].begin(3 * lines, c->stream, &h));
-        memcpy(h, tab[k], 12 * lines);
-        MCRT_TRY(c->pose_stage[k].commit(3 * lines, c->stream));
-        tab[k] = c->pose_stage[k].dev;
-    }
-    a.stack = stack_dev; a.pos = tab[0]; a.dir = tab[1]; a.votes = c->img.d_votes;
-    a.out = out_dev; a.count_out = count_dev; a.votes_out = votes_dev; a.stats = stats_dev;
-    a.R = R; a.n_samples = (uint32_t)ns; a.nu = g->nu; a.nv = g->nv; a.nw = g->nw; a.n_vox = (uint32_t)n;
-    a.n_labels = o->n_labels; a.fill_radius = o->fill_radius; a.fill_min = o->fill_min;
-    HIP_TRY(hipMemsetAsync(c->img.d_votes, 0, 4 * words, c->stream));
-    if (stats_dev) HIP_TRY(hipMemsetAsync(stats_dev, 0, 8, c->stream));
+    const Range outs[4] = { { out_dev, n, "out_dev" }, { count_dev, 4 * n, "count_dev" }, { votes_dev, 4 * n, "votes_dev" }, { stats_dev, 8, "stats_dev" } };
+    MCRT_TRY(check_overlap(fn, Range{ stack_dev, ns, "stack_dev" }, outs, 4, true));
+    MCRT_TRY(recon_begin(c, a.blk, n_frames, E, c->img.d_votes, words));
+    a.stack = stack_dev; a.votes = c->img.d_votes; a.out = out_dev; a.count_out = count_dev; a.votes_out = votes_dev;
+    a.n_vox = (uint32_t)n; a.n_labels = o->n_labels;
     HIP_TRY(mcrt::launch_recon_label_splat(a, c->stream));
     if (out_dev || count_dev || votes_dev) HIP_TRY(mcrt::launch_recon_label_resolve(a, c->stream));
     return MCRT_OK;

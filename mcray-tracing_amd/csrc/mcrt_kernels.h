@@ -21,7 +21,8 @@
 //   mcrt_scene.hip   k_tris_by_id, k_expand_tris; the probes k_math_probe, k_verify_div, k_philox_probe
 //   mcrt_lbvh.hip    the device BVH builder (mcrt_lbvh.h)
 // Shared device code: mcrt_device.h (primitives and the knobs more than one unit reads), mcrt_walk.h (the lane walk's steps, also k_path's),
-// mcrt_shade.h (shade_path, also k_path's), mcrt_pixels.h (the pixel tile of k_bmode, k_compound, k_volume and k_label_gather and the byte
+// mcrt_shade.h (shade_path, also k_path's), mcrt_voxels.h (the voxel block of the 3-D stages: a sample's voxel, a wavefront's runs,
+// the resolve tile, the picture tile -- included by mcrt_recon / label3d / render.hip and, for recon_tiling, mcrt_image.cpp), mcrt_pixels.h (the pixel tile of k_bmode, k_compound, k_volume and k_label_gather and the byte
 // k_render writes: layout, frame chunks, persistence, quantisation, the word store -- included by mcrt_display / volume / label / render.hip
 // only).  Everything is scalar fp32/fp64 VALU + integer work -- no dense contraction, hence no MFMA -- and the arithmetic follows the
 // parity contract expression by expression (compiled -ffp-contract=off).
@@ -138,14 +139,16 @@ struct VolumeArgs {
     PixelPass pass;
 };
 
+// what k_render and k_render_label know of a view and its block (view_args in mcrt_image.cpp fills it, mcrt_voxels.h reads it)
+struct ViewArgs { float origin[3], di[3], dj[3], ds[3]; uint32_t nx, ny, n_steps, F, nu, nv, nw; };   // origin .. ds: mcrt_render_view, component order u, v, w
+
 // k_render (mcrt_render_frames): the voxel blocks [F][nw][nv][nu] (floats or bytes) -> floats, bytes and step indices [F][ny][nx]
 struct RenderArgs {
     const void *vol;                    // float or uint8_t [F][nw][nv][nu]
     float *out;                         // [F][ny][nx] or null
     uint8_t *out8;                      // same or null
     float *depth;                       // same or null
-    float origin[3], di[3], dj[3], ds[3];   // mcrt_render_view, component order u, v, w
-    uint32_t nx, ny, n_steps, F, nu, nv, nw;
+    ViewArgs view;
     uint32_t mode;                      // MCRT_RENDER_*
     uint32_t row_tile;                  // 0: a wavefront owns an 8 x 8 tile of the picture; 1: 64 pixels of one row
     float lo, inv_range, threshold, inv_ramp, opacity, depth_cue, t_cut, inv_steps;
@@ -177,20 +180,24 @@ struct SpeckleArgs {
 #define RECON_TW 8          // ... and along w; staged in LDS with a halo of fill_radius on every side
 #define RECON_MAX_FILL 3    // the largest fill_radius (the LDS image is sized per launch: 5 bytes per staged voxel)
 #define RECON_MAX_TILES (1u << 24)   // a grid must need fewer resolve tiles than this: a launch holds fewer than 2^32 lanes
+// what the two splats and the two resolves know of the stack's poses and of the block (recon_block in mcrt_image.cpp fills it, mcrt_voxels.h reads it)
+struct ReconBlock {
+    const float *pos, *dir;             // [F][E][3]
+    uint32_t *stats;                    // [2] or null: samples outside the block, samples inside it that are not binned
+    uint32_t R, n_samples;              // n_samples = F * E * R < 2^31
+    uint32_t nu, nv, nw, fill_radius, fill_min;
+    uint32_t tu, tv;                    // tiles along u and v (launch_resolve fills them)
+    float A[9], b[3], row_u;            // mcrt_recon_transform; row_mm / unit_mm
+};
 struct ReconArgs {
     const float *stack;                 // [F][E][R]
-    const float *pos, *dir;             // [F][E][3]
+    ReconBlock blk;                     // stats[1]: unusable samples inside the block
     unsigned long long *sum;            // [n] MEAN: the int64 sum of q;  MAX: the largest q, biased by 2^63 so that a cleared word is "none yet"
     uint32_t *count;                    // [n]
     float *out;                         // [nw][nv][nu]
     uint32_t *count_out;                // same, or null
-    uint32_t *stats;                    // [2] or null: samples outside the block, unusable samples inside it
-    uint32_t R, n_samples;              // n_samples = F * E * R < 2^31
-    uint32_t nu, nv, nw;
-    uint32_t mode, fill_radius, fill_min;
-    uint32_t tu, tv;                    // tiles along u and v (launch_recon_resolve fills them)
-    float A[9], b[3];                   // mcrt_recon_transform
-    float row_u, value_max, empty;
+    uint32_t mode;
+    float value_max, empty;
     double qscale;
 };
 
@@ -219,17 +226,11 @@ struct LabelGatherArgs {
 // words, then the winners resolved and the holes filled into out [nw][nv][nu]; the tile and the limits are k_recon_resolve's (RECON_*)
 struct ReconLabelArgs {
     const uint8_t *stack;               // [F][E][R]
-    const float *pos, *dir;             // [F][E][3]
+    ReconBlock blk;                     // stats[1]: samples inside the block whose label is >= n_labels
     uint32_t *votes;                    // [n_vox][n_labels], cleared before the splat
     uint8_t *out;                       // [nw][nv][nu] or null
     uint32_t *count_out, *votes_out;    // same, or null: the votes of a voxel, the winner's votes
-    uint32_t *stats;                    // [2] or null: samples outside the block, samples inside it whose label is >= n_labels
-    uint32_t R, n_samples;              // n_samples = F * E * R < 2^31
-    uint32_t nu, nv, nw, n_vox;         // n_vox = nu * nv * nw;  n_vox * n_labels < 2^31
-    uint32_t n_labels, fill_radius, fill_min;
-    uint32_t tu, tv;                    // tiles along u and v (launch_recon_label_resolve fills them)
-    float A[9], b[3];                   // mcrt_recon_transform
-    float row_u;
+    uint32_t n_vox, n_labels;           // n_vox = nu * nv * nw;  n_vox * n_labels < 2^31
 };
 
 // k_render_label (mcrt_render_label_frames): the label blocks [F][nw][nv][nu] read at the points a depth buffer [F][ny][nx] names -> bytes [F][ny][nx]
@@ -237,8 +238,7 @@ struct RenderLabelArgs {
     const uint8_t *labels;              // [F][nw][nv][nu]
     const float *depth;                 // [F][ny][nx]: mcrt_render_frames' depth_dev
     uint8_t *out;                       // [F][ny][nx]
-    float origin[3], di[3], dj[3], ds[3];   // mcrt_render_view, component order u, v, w
-    uint32_t nx, ny, n_steps, F, nu, nv, nw;
+    ViewArgs view;
 };
 
 hipError_t launch_init(const FrameArgs &a, hipStream_t st);

@@ -2,6 +2,7 @@
 // direction -- one orthographic ray per pixel, n_steps trilinear samples along it, folded into the maximum, the mean or a front-to-back
 // composited surface.  The reference has one plane and no counterpart.
 #include "mcrt_pixels.h"
+#include "mcrt_voxels.h"
 
 namespace mcrt {
 
@@ -9,14 +10,14 @@ namespace mcrt {
 // three fractions, and whether the step counts at all
 struct RenderSample { float t[8]; float au, av, aw; bool covered; };
 
-// p = b + (float)s * ds per component (b: the pixel's ((origin + i di) + j dj), so that p is the contract's expression and no running sum).
+// p = b + (float)s * ds per component (b: the pixel's base point, pixel_base, so that p is the contract's expression and no running sum).
 // The indices are made only where the step is covered: -1 <= f < n then holds in float, n < 2^24, and (int)f is exact.
 template <bool IN8>
-__device__ __forceinline__ RenderSample render_fetch(const RenderArgs &a, const void *blk, float bu, float bv, float bw, uint32_t s)
+__device__ __forceinline__ RenderSample render_fetch(const ViewArgs &a, const void *blk, const float (&b)[3], uint32_t s)
 {
     RenderSample r;
     const float fs = (float)s;
-    const float pu = bu + fs * a.ds[0], pv = bv + fs * a.ds[1], pw = bw + fs * a.ds[2];
+    const float pu = b[0] + fs * a.ds[0], pv = b[1] + fs * a.ds[1], pw = b[2] + fs * a.ds[2];
     const float fu = floorf(pu), fv = floorf(pv), fw = floorf(pw);
     r.au = pu - fu; r.av = pv - fv; r.aw = pw - fw;
     r.covered = pu == pu && pv == pv && pw == pw && fu >= -1.0f && fu < (float)a.nu && fv >= -1.0f && fv < (float)a.nv && fw >= -1.0f && fw < (float)a.nw;
@@ -43,21 +44,21 @@ __device__ __forceinline__ RenderSample render_fetch(const RenderArgs &a, const 
 template <bool IN8>
 __global__ void __launch_bounds__(256) k_render(RenderArgs a)
 {
-    const uint32_t lane = threadIdx.x & 63u, wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const ViewArgs &vw = a.view;
     uint32_t i, j;
-    if (a.row_tile) { const uint32_t per_row = (a.nx + 63u) / 64u; i = (wave % per_row) * 64u + lane; j = wave / per_row; }
-    else { const uint32_t tx = (a.nx + 7u) / 8u; i = (wave % tx) * 8u + (lane & 7u); j = (wave / tx) * 8u + (lane >> 3); }
-    if (i >= a.nx || j >= a.ny) return;
-    const uint32_t f = blockIdx.y, mode = a.mode, n_steps = a.n_steps;
-    const size_t nvox = (size_t)a.nu * a.nv * a.nw;
+    if (a.row_tile) { const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6), per_row = (vw.nx + 63u) / 64u; i = (wave % per_row) * 64u + (threadIdx.x & 63u); j = wave / per_row; }
+    else picture_tile(vw, i, j);
+    if (i >= vw.nx || j >= vw.ny) return;
+    const uint32_t f = blockIdx.y, mode = a.mode, n_steps = vw.n_steps;
+    const size_t nvox = (size_t)vw.nu * vw.nv * vw.nw;
     const void *blk = IN8 ? (const void *)((const uint8_t *)a.vol + (size_t)f * nvox) : (const void *)((const float *)a.vol + (size_t)f * nvox);
-    const float fi = (float)i, fj = (float)j;
-    const float bu = (a.origin[0] + fi * a.di[0]) + fj * a.dj[0], bv = (a.origin[1] + fi * a.di[1]) + fj * a.dj[1], bw = (a.origin[2] + fi * a.di[2]) + fj * a.dj[2];
+    float b[3];
+    pixel_base(vw, i, j, b);
     float m = 0.0f, depth = -1.0f, sum = 0.0f, C = 0.0f, T = 1.0f;     // (depth is MIP's arg as well)
     uint32_t cnt = 0u;
-    RenderSample cur = render_fetch<IN8>(a, blk, bu, bv, bw, 0u);
+    RenderSample cur = render_fetch<IN8>(vw, blk, b, 0u);
     for (uint32_t s = 0; s < n_steps; s++) {
-        const RenderSample nxt = render_fetch<IN8>(a, blk, bu, bv, bw, min(s + 1u, n_steps - 1u));
+        const RenderSample nxt = render_fetch<IN8>(vw, blk, b, min(s + 1u, n_steps - 1u));
         if (cur.covered) {
             const float wu = 1.0f - cur.au, wv = 1.0f - cur.av, ww = 1.0f - cur.aw;
             const float c00 = cur.t[0] * wu + cur.t[1] * cur.au, c01 = cur.t[2] * wu + cur.t[3] * cur.au;
@@ -82,7 +83,7 @@ __global__ void __launch_bounds__(256) k_render(RenderArgs a)
         cur = nxt;
     }
     const float out = mode == MCRT_RENDER_MIP ? m : mode == MCRT_RENDER_MEAN ? (cnt ? sum / (float)cnt : 0.0f) : C;
-    const size_t o = ((size_t)f * a.ny + j) * a.nx + i;
+    const size_t o = ((size_t)f * vw.ny + j) * vw.nx + i;
     if (a.out) a.out[o] = out;
     if (a.out8) a.out8[o] = quantise(fminf(fmaxf(out, 0.0f), 1.0f));
     if (a.depth) a.depth[o] = mode == MCRT_RENDER_MEAN ? -1.0f : depth;
@@ -90,8 +91,8 @@ __global__ void __launch_bounds__(256) k_render(RenderArgs a)
 
 hipError_t launch_render(const RenderArgs &a, bool in8, hipStream_t st)
 {
-    const uint32_t waves = a.row_tile ? ((a.nx + 63u) / 64u) * a.ny : ((a.nx + 7u) / 8u) * ((a.ny + 7u) / 8u);   // (nx * ny < 2^31: no overflow)
-    const dim3 grid((waves + 3u) / 4u, a.F), blk(256);
+    const uint32_t waves = a.row_tile ? ((a.view.nx + 63u) / 64u) * a.view.ny : picture_tile_waves(a.view.nx, a.view.ny);   // (nx * ny < 2^31: no overflow)
+    const dim3 grid((waves + 3u) / 4u, a.view.F), blk(256);
     if (in8) hipLaunchKernelGGL((k_render<true>), grid, blk, 0, st, a);
     else hipLaunchKernelGGL((k_render<false>), grid, blk, 0, st, a);
     return hipGetLastError();

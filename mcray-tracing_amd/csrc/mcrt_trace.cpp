@@ -376,16 +376,16 @@ extern "C" int mcrt_trace_frame(mcrt_ctx *c, uint32_t frame, uint32_t e0, uint32
     return mcrt_trace_frames(c, frame, 1, e0, e1, rf_dev);
 }
 
-// the pose tables of a pass on the device: a table in host memory is staged (see mcrt_trace_frames_poses), a device table is used as it is
-static int stage_poses(mcrt_ctx *c, uint32_t n_frames, const float *dev[2])
+// the pose tables of `lines` (frame, scan-line) entries on the device: a table in host memory is staged (see mcrt_trace_frames_poses), a
+// device table is used as it is.  Two Staging begin / commit pairs on the context's stream, positions first.
+int mcrt::stage_poses(mcrt_ctx *c, size_t lines, const float *dev[2])
 {
-    const size_t len = 3 * (size_t)n_frames * c->p.n_elements;
     for (int k = 0; k < 2; k++) {
         if (is_device_pointer(dev[k])) continue;
         float *h = nullptr;
-        MCRT_TRY(c->pose_stage[k].begin(len, c->stream, &h));
-        memcpy(h, dev[k], 4 * len);
-        MCRT_TRY(c->pose_stage[k].commit(len, c->stream));
+        MCRT_TRY(c->pose_stage[k].begin(3 * lines, c->stream, &h));
+        memcpy(h, dev[k], 12 * lines);
+        MCRT_TRY(c->pose_stage[k].commit(3 * lines, c->stream));
         dev[k] = c->pose_stage[k].dev;
     }
     return MCRT_OK;
@@ -402,7 +402,7 @@ extern "C" int mcrt_trace_frames_poses(mcrt_ctx *c, uint32_t frame, uint32_t n_f
     if (!pos || !dir) return set_error(MCRT_ERR_INVALID, "mcrt_trace_frames_poses: null pose tables");
     if (n_frames == 0 || n_frames > 1024) return set_error(MCRT_ERR_LIMIT, "n_frames must be 1..1024");
     const float *dev[2] = { pos, dir };
-    MCRT_TRY(stage_poses(c, n_frames, dev));
+    MCRT_TRY(mcrt::stage_poses(c, (size_t)n_frames * c->p.n_elements, dev));
     return trace_frames(c, frame, n_frames, e0, e1, dev[0], dev[1], rf_dev);
 }
 
@@ -485,7 +485,7 @@ extern "C" int mcrt_label_frames(mcrt_ctx *c, uint32_t n_frames, uint32_t e0, ui
     const size_t ovf = c->scene.bvh4.max_stack > lds_part ? (size_t)(c->scene.bvh4.max_stack - lds_part) * blocks * 64 : 0;
     if (ovf > c->label_ovf.cap) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(c->label_ovf.alloc(ovf)); }      // (as ensure_work: an earlier pass may run on a stream the context has left)
     const float *dev[2] = { pos, dir };
-    if (pos) MCRT_TRY(stage_poses(c, n_frames, dev));
+    if (pos) MCRT_TRY(mcrt::stage_poses(c, (size_t)n_frames * c->p.n_elements, dev));
     if (c->scene.update_pending && c->scene.update_stream != c->stream) HIP_TRY(hipStreamWaitEvent(c->stream, c->scene.ev_update, 0));   // a scene update issued on another stream
     mcrt::FrameArgs a;
     memset(&a, 0, sizeof a);

@@ -15,6 +15,8 @@ import recon_label_cases as rc
 import recon_label_mirror as rlm
 import recon_mirror as rm
 import render_mirror as vm
+import test_gpu_label as tgl
+import test_gpu_recon as tgf
 import test_gpu_render as tgr
 from test_gpu_focus import Dev
 from test_gpu_recon import TU, TV, TW
@@ -254,6 +256,41 @@ def test_each_output_left_out_in_turn(mcrt, ctx, dev, sparse):
         same(got, want, "without " + without)
     for only in ALL:
         same(run(ctx, dev, x, pos, dirs, g, 6, want=(only,), fill_radius=2), want, "only " + only)
+
+
+def test_host_pose_tables_of_changing_size_from_every_caller(mcrt):
+    """Every call that takes pose tables stages host tables through one function and one pair of pinned buffers.  On ONE context, host
+    (numpy) tables throughout: label_frames (F = 2: 10 lines; 465 rows, so that the beams reach the sphere), recon_label_frames (3 x 5 x 65: 15 lines; R = 65 crosses a wavefront and runs
+    a scan-line's end into the next), recon_frames (1 x 130 x 7: 130 lines, the staging grows) and the first recon_label_frames again (15
+    lines: it shrinks).  Each result equals the same call with DEVICE tables on a fresh context, and the two label volumes are equal."""
+    cfg, sd = tgl.scene_of(mcrt, "sphere")
+    E, R, LR = 5, 65, 465
+    tr = mcrt.Transducer(E, position=cfg["transducerPosition"], angles_deg=cfg["transducerAngles"])
+    lpos = np.stack([tr.pos, tr.pos + f32(0.05)]).astype(f32); ldirs = np.stack([tr.dir, tr.dir]).astype(f32)
+    x = rc.spoil(rc.random_labels(3, E, R, 6), 6); pos, dirs = rc.poses(3, E)
+    g = rc.grid_about(mcrt, rc.cloud_centre(R), (5, 40, 5), 0.5)
+    v = tgf.values(1, 130, 7); vpos, vdirs = rc.poses(1, 130)
+    gv = rc.grid_about(mcrt, rc.cloud_centre(7), (40, 6, 3), 0.7)
+
+    def calls(tables):
+        ctx = tgl.context(mcrt, sd, n_elements=E, n_rows=LR)
+        d = Dev(ctx)
+        try:
+            lp, ld = (d.upload(lpos), d.upload(ldirs)) if tables == "device" else (lpos, ldirs)
+            tissue = tgl.label(ctx, d, LR, lp, ld, n_frames=2, want=(True, False, False))[0]
+            first = run(ctx, d, x, pos, dirs, g, 6, tables=tables)
+            floats = tgf.run(ctx, d, mcrt, v, vpos, vdirs, gv, tables=tables)
+            return tissue, first, floats, run(ctx, d, x, pos, dirs, g, 6, tables=tables)
+        finally:
+            tgl.done(ctx, d)
+
+    host, want = calls("host"), calls("device")
+    assert (want[0] != tgl.FILL_T).all() and len(np.unique(want[0])) > 1 and (want[0][0] != want[0][1]).any() and want[1][1].sum() > 100 and want[1][3].min() > 0 and want[2][1].sum() > 100
+    assert np.array_equal(host[0], want[0]), "label_frames"
+    same(host[1], want[1], "recon_label_frames, first")
+    tgf.same(host[2], want[2], "recon_frames")
+    same(host[3], want[3], "recon_label_frames, again")
+    same(host[3], host[1], "the first and the last label volume")
 
 
 # ------------------------------------------------------------------ refusals
