@@ -53,7 +53,8 @@ extern "C" {
                                    (freehand 3-D reconstruction: tracked frames binned into voxels by their poses, with hole filling; additive);
                                    + mcrt_recon_label_opts, mcrt_default_recon_label_opts, mcrt_recon_label_frames, mcrt_render_label_frames
                                    (3-D ground truth: a freehand label volume by majority vote, the label of what a rendering shows; additive);
-                                   + mcrt_debug_beam (what bounce 1 by beams did in the last pass; additive) */
+                                   + mcrt_debug_beam (what bounce 1 by beams did in the last pass; additive);
+                                   + mcrt_debug_beam_bounce (the same for any bounce run by beams; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -990,6 +991,10 @@ int mcrt_debug_fast_paths(mcrt_ctx *ctx, uint32_t out[4]);
  * decided, out[2] leftover rays walked through the tree, out[3] beams whose list is incomplete (cut at its capacity), out[4] beams refused for their spread,
  * out[5] beams that have rays at all.  Waits for the stream. */
 int mcrt_debug_beam(mcrt_ctx *ctx, uint32_t out[6]);
+/* mcrt_debug_beam for bounce b (bounce 1, and the bounces 2 .. MCRT_BEAM_LAST whose rays are grouped by the triangle they left): out[0 .. 5] as
+ * mcrt_debug_beam's -- out[1] + out[2] is the bounce's ray count --, out[6] sampled rays whose group found no slot of the group table (their
+ * groups are walked), out[7] slots of the table claimed.  All 0 where bounce b did not run by beams.  Waits for the stream. */
+int mcrt_debug_beam_bounce(mcrt_ctx *ctx, uint32_t b, uint32_t out[8]);
 /* TEST HOOK, refused (MCRT_ERR_INVALID) unless the context was created with MCRT_TEST_HOOKS set in the environment: ORs `bits` into the
  * context's device error word on its stream, as an abandoned launch would (bit 0: traversal stack ran out, bit 1: kernel watchdog
  * expired) -- what mcrt_synchronize reports and what turns finalised RF images into NaN until it is asked */

@@ -600,6 +600,13 @@ class Context(_SceneCalls):
             check(self.L.mcrt_debug_beam(self.h, out))
         return bool(out[0]), int(out[1]), int(out[2]), int(out[3]), int(out[4]), int(out[5])
 
+    def debug_beam_bounce(self, b):
+        """debug_beam for bounce b, and (sampled rays whose group found no slot of the group table, slots claimed): mcrt_debug_beam_bounce"""
+        out = (C.c_uint32 * 8)()
+        if hasattr(self.L, "mcrt_debug_beam_bounce"):
+            check(self.L.mcrt_debug_beam_bounce(self.h, int(b), out))
+        return (bool(out[0]),) + tuple(int(v) for v in out[1:])
+
     def debug_set_error(self, bits):
         """test hook: mark the context as an abandoned launch would (mcrt_debug_set_error)"""
         check(self.L.mcrt_debug_set_error(self.h, int(bits)))

@@ -53,6 +53,9 @@ static Knobs read_knobs()
     if (const char *e = tuning_env("MCRT_FOLD_B0")) k.fold_b0 = atoi(e) != 0;
     if (const char *e = tuning_env("MCRT_BEAM_B1")) { int v = atoi(e); if (v >= 0 && v <= 2) k.beam_b1 = (uint32_t)v; }
     if (const char *e = tuning_env("MCRT_BEAM_FROM")) { long long v = atoll(e); if (v >= 0 && v <= 0xffffffffll) k.beam_from = (uint32_t)v; }
+    if (const char *e = tuning_env("MCRT_BEAM_LAST")) { int v = atoi(e); if (v >= 1 && v < MCRT_MAX_BOUNCES) k.beam_last = (uint32_t)v; }
+    if (const char *e = tuning_env("MCRT_BEAM_DEEP_FROM")) { long long v = atoll(e); if (v >= 0 && v <= 0xffffffffll) k.beam_deep_from = (uint32_t)v; }
+    if (const char *e = tuning_env("MCRT_BEAM_GROUPS")) { long long v = atoll(e); if (v >= 1 && v <= (1 << 20)) k.beam_groups = (uint32_t)v; }
     if (const char *e = tuning_env("MCRT_BEAM_CAP")) { int v = atoi(e); if (v >= 1 && v <= (int)MCRT_BEAM_CAP_MAX) k.beam_cap = (uint32_t)v; }
     if (const char *e = tuning_env("MCRT_BEAM_NEAR")) { int v = atoi(e); if (v >= 1) k.beam_near = (uint32_t)v; }
     if (const char *e = tuning_env("MCRT_RENDER_ROW_TILE")) k.render_row_tile = atoi(e) != 0;
@@ -556,21 +559,35 @@ extern "C" int mcrt_debug_fast_paths(mcrt_ctx *c, uint32_t out[4])
     return MCRT_OK;
 }
 
-// what bounce 1 by beams did in the last traced pass (work set 0): whether it ran, rays it resolved, leftover rays walked, beams incomplete, beams refused, beams in use
+// what bounce b by beams did in the last traced pass (work set 0): whether it ran, rays its lists decided, leftover rays walked, beams incomplete, beams refused,
+// beams in use, sampled rays whose group found no slot, slots claimed
+static int debug_beam(mcrt_ctx *c, uint32_t b, uint32_t out[8])
+{
+    for (int k = 0; k < 8; k++) out[k] = 0u;
+    if (b >= MCRT_MAX_BOUNCES || !((c->ins.last_beam_mask >> b) & 1u) || c->work.empty()) return MCRT_OK;
+    const Work &w = c->work[0];
+    uint32_t lc[MCRT_BEAM_COUNTERS] = {}, n = 0;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(lc, w.beam.lcount.p + (size_t)b * MCRT_BEAM_COUNTERS, sizeof lc, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&n, w.b.counts.p + b, 4, hipMemcpyDeviceToHost));
+    const uint32_t walked = lc[c->ins.last_beam_far ? 1 : 0];
+    out[0] = 1u; out[1] = n - walked; out[2] = walked; out[3] = lc[2]; out[4] = lc[3]; out[5] = lc[4]; out[6] = lc[6]; out[7] = lc[7];
+    return MCRT_OK;
+}
 extern "C" int mcrt_debug_beam(mcrt_ctx *c, uint32_t out[6])
 {
     CTX_TRY(c);
     if (!out) return set_error(MCRT_ERR_INVALID, "null out pointer");
-    for (int k = 0; k < 6; k++) out[k] = 0u;
-    if (!c->ins.last_beam || c->work.empty()) return MCRT_OK;
-    const Work &w = c->work[0];
-    uint32_t lc[5] = { 0, 0, 0, 0, 0 }, n1 = 0;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(lc, w.beam.lcount, sizeof lc, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&n1, w.b.counts.p + 1, 4, hipMemcpyDeviceToHost));
-    const uint32_t walked = lc[c->knobs.beam_near < c->knobs.beam_cap ? 1 : 0];
-    out[0] = 1u; out[1] = n1 - walked; out[2] = walked; out[3] = lc[2]; out[4] = lc[3]; out[5] = lc[4];
+    uint32_t o[8];
+    MCRT_TRY(debug_beam(c, 1u, o));
+    for (int k = 0; k < 6; k++) out[k] = o[k];
     return MCRT_OK;
+}
+extern "C" int mcrt_debug_beam_bounce(mcrt_ctx *c, uint32_t b, uint32_t out[8])
+{
+    CTX_TRY(c);
+    if (!out) return set_error(MCRT_ERR_INVALID, "null out pointer");
+    return debug_beam(c, b, out);
 }
 
 extern "C" int mcrt_debug_set_error(mcrt_ctx *c, uint32_t bits)

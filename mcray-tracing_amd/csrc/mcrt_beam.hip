@@ -1,21 +1,30 @@
-// mcrt_beam.hip -- bounce 1 of a staged pass with ONE probe pose: the rays of a scan-line leave one point (bounce 0 is one ray per scan-line, and the
-// hit point is the next origin) in a few narrow bundles, the same for every frame of the pass.  Instead of walking the tree once per 64 rays
-// (k_trace_packet), the triangles a bundle can meet are collected ONCE per bundle and every ray tests that short list, nearest first:
+// mcrt_beam.hip -- bounces 1 .. MCRT_BEAM_LAST of a staged pass with ONE probe pose.  The rays of a scan-line leave bounce 0's hit point in a few narrow
+// bundles, the same for every frame of the pass; at the next bounces the rays that left ONE triangle of a scan-line in one medium are such bundles again (their
+// origins spread over the triangle).  Instead of walking the tree once per ray or per 64 rays, the triangles a bundle can meet are collected ONCE per bundle and
+// every ray tests that short list, nearest first:
 //
-//   k_beam_clear    the reduction words, the leftover counters
-//   k_beam_bounds   per BEAM -- scan-line x history (the medium says whether bounce 0 reflected) x dominant axis x its sign -- the bounds of the two
-//                   slopes d_other / |d_dom|, of the start point f2 and of its coordinates' size, over (a sample of) the bounce-1 queue
-//   k_beam_collect  one workgroup per beam: one traversal of the BVH4 with a conservative beam-against-box test, the leaf triangles tested by their own
-//                   padded bounds, sorted by the depth at which they begin, the first `cap` copied into the beam's list
-//   k_beam_test     one lane per ray in queue order: the contract's triangle test (packet_tri_test) over its beam's list in order, until the hit lies
-//                   before everything not yet tested; lanes that cannot be decided are appended to a leftover queue
-//   k_beam_gather, the lane walk, k_beam_scatter     the leftovers, walked as any other queue
+//   k_beam_clear    the reduction words, the group table, the bounce's counters, the leftover walk's counts and cursors
+//   k_beam_bounds   per BEAM the bounds of the two slopes d_other / |d_dom|, of the start point f2 and of its coordinates' size, over (a sample of) the bounce's
+//                   queue.  Bounce 1: a beam is scan-line x history (the medium says whether bounce 0 reflected) x dominant axis x its sign, addressed directly.
+//                   Bounce b >= 2: the GROUP (scan-line, the triangle the ray left -- FrameArgs::from_tri, written by k_shade(b - 1) --, medium) claims a slot of
+//                   a hash table with a compare-and-swap on its key word (MCRT_BEAM_PROBES slots are tried); a beam is slot x dominant axis x sign.  A ray whose
+//                   group found no slot, or was not in the sample, is no member of any beam and is walked.
+//   k_beam_collect  one workgroup per beam (bounce b >= 2: per slot, its 6 beams in turn): one traversal of the BVH4 with a conservative beam-against-box test, the leaf triangles tested by their own
+//                   padded bounds, sorted by the depth at which they begin, the first `cap` copied into the beam's list (bounce b >= 2: a list of a pool,
+//                   handed out to the beams that have members)
+//   k_beam_test     one lane per ray in queue order: its beam looked up (the group's key compared), the contract's triangle test (packet_tri_test) over the
+//                   beam's list in order, until the hit lies before everything not yet tested; lanes that cannot be decided are appended to a leftover queue
+//   k_beam_gather, the lane walk, k_beam_scatter     the leftovers, walked as any other queue, in the halves of the other bounce parity
 //
-// EXACT (DESIGN.md A.10): a ray's answer is the smallest (fraction, id) among the triangles that pass the contract's test, whatever the order and
-// whatever else is tested.  A ray counts as a MEMBER of a beam only where comparisons prove it inside the beam's bounds (a NaN proves nothing), the
+// EXACT (DESIGN.md A.10, A.11): a ray's answer is the smallest (fraction, id) among the triangles that pass the contract's test, whatever the order and
+// whatever else is tested.  A ray counts as a MEMBER of a beam only where comparisons prove it inside the beam's bounds (a NaN proves nothing) -- how rays are
+// GROUPED into beams only decides how narrow the beams are --, the
 // collection keeps every triangle whose padded bounds come within a margin m of the beam's volume -- m = 2^-18 x the largest coordinate of the start
 // points and the scene, 16 x the rounding of the slab test and of the arithmetic here --, and a member is FINAL only when its hit lies more than 2 m before the depth at which
 // the first untested triangle's padded bounds begin: a triangle accepted at a smaller or equal fraction has its hit inside its own padded bounds.
+// The origins of a bounce b >= 2 spread over a triangle: the volume starts from the bounds of f2 (w is their extent along the dominant axis), and a ray whose
+// coordinates are larger than the sampled members' is refused by the comparison with the record's size.  The triangle a ray left is among its candidates and is
+// rejected by the contract's test exactly as the walk rejects it.
 #include <hip/hip_fp16.h>
 #include "mcrt_device.h"
 #include "mcrt_walk.h"
@@ -34,14 +43,34 @@ MCRT_DEV uint32_t ford(float f) { const uint32_t b = __float_as_uint(f); return 
 MCRT_DEV float funord(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
 MCRT_DEV float comp(f3 v, int k) { return k == 0 ? v.x : k == 1 ? v.y : v.z; }
 
-// a queued ray of bounce 1 and the beam it would belong to
-struct BeamRay { f3 f2, to; float u, v, cmax, dd; int dom, bid; bool neg; };
-MCRT_DEV bool beam_ray(const FrameArgs &a, uint32_t i, BeamRay &r)
+// the slot of the group table that holds `key`, or -1.  claim: a free slot is taken (one compare-and-swap on its key word).  Slots are never given back during
+// a bounce, so a key that is in the table is found by the same probes that put it there.
+MCRT_DEV int beam_slot(const BeamArgs &g, unsigned long long key, bool claim)
 {
-    const size_t np = (size_t)a.ne * a.S;
-    const uint32_t pid = a.queue[np + i];
+    uint32_t h = ((uint32_t)key ^ (uint32_t)(key >> 32) * 0x9e3779b1u) * 2654435761u;
+    h ^= h >> 15;
+    for (uint32_t p = 0; p < MCRT_BEAM_PROBES; p++) {
+        const uint32_t s = (h + p) & (g.groups - 1u);
+        // (k_beam_test only reads the table: plain loads, served by the vector cache)
+        unsigned long long k = claim ? __hip_atomic_load(&g.gkey[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : g.gkey[s];
+        if (k == 0ull && claim) {
+            k = atomicCAS(&g.gkey[s], 0ull, key);
+            if (k == 0ull) { k = key; atomicAdd(&g.lcount[7], 1u); }
+        }
+        if (k == key) return (int)s;
+        if (k == 0ull) return -1;
+    }
+    return -1;
+}
+
+// a queued ray of bounce g.b and the beam it would belong to (bid < 0: none)
+struct BeamRay { f3 f2, to; float u, v, cmax, dd; int dom, bid; bool neg; };
+MCRT_DEV bool beam_ray(const FrameArgs &a, const BeamArgs &g, uint32_t i, bool claim, BeamRay &r)
+{
+    const size_t half = (size_t)(g.b & 1u) * a.ne * a.S;
+    const uint32_t pid = a.queue[half + i];
     const uint32_t line = pid / a.S, scan = line - (line / a.ne_frame) * a.ne_frame;
-    const float4 s0 = a.st0[np + i], s1 = a.st1[np + i];
+    const float4 s0 = a.st0[half + i], s1 = a.st1[half + i];
     const Ray ry = ray_of(mk(s0.x, s0.y, s0.z), mk(s1.x, s1.y, s1.z), s0.w, a);
     r.f2 = ry.f2; r.to = ry.to;
     const f3 D = ry.to - ry.f2;
@@ -52,11 +81,23 @@ MCRT_DEV bool beam_ray(const FrameArgs &a, uint32_t i, BeamRay &r)
     r.u = comp(D, (r.dom + 1) % 3) / ad; r.v = comp(D, (r.dom + 2) % 3) / ad;
     r.cmax = fmaxf(fmaxf(fabsf(r.f2.x), fabsf(r.f2.y)), fabsf(r.f2.z));
     r.neg = r.dd < 0.0f;
-    const uint32_t hist = __float_as_int(s1.w) != (int)a.start_mat ? 1u : 0u;
-    r.bid = (int)((((scan * 2u + hist) * 3u + (uint32_t)r.dom) * 2u) + (r.neg ? 1u : 0u));
     // every coordinate a number, the dominant component not 0 (then |u|, |v| <= 1)
     const float sum = fabsf(r.f2.x) + fabsf(r.f2.y) + fabsf(r.f2.z) + fabsf(r.to.x) + fabsf(r.to.y) + fabsf(r.to.z);
-    return sum < 1e30f && ad > 0.0f && fabsf(r.u) <= 1.0f && fabsf(r.v) <= 1.0f;
+    const bool ok = sum < 1e30f && ad > 0.0f && fabsf(r.u) <= 1.0f && fabsf(r.v) <= 1.0f;
+    const uint32_t code = (uint32_t)r.dom * 2u + (r.neg ? 1u : 0u);
+    if (g.groups == 0u) {
+        const uint32_t hist = __float_as_int(s1.w) != (int)a.start_mat ? 1u : 0u;
+        r.bid = (int)((scan * 2u + hist) * 6u + code);
+    } else {
+        r.bid = -1;
+        if (ok) {
+            const unsigned long long key = (1ull << 63) | ((unsigned long long)scan << 40) | ((unsigned long long)((uint32_t)__float_as_int(s1.w) & 0xffu) << 32)
+                                           | (unsigned long long)a.from_tri[pid];
+            const int slot = beam_slot(g, key, claim);
+            if (slot >= 0) r.bid = slot * 6 + (int)code;
+        }
+    }
+    return ok;
 }
 
 MCRT_DEV float wave_min(float x) { for (int o = 32; o > 0; o >>= 1) x = fminf(x, __shfl_xor(x, o, 64)); return x; }
@@ -67,14 +108,15 @@ __global__ void __launch_bounds__(256) k_beam_clear(BeamArgs g)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i < g.n_beams * MCRT_BEAM_REC) g.red[i] = (i & 8u) ? 0u : 0xffffffffu;
-    if (i < 8u) g.lcount[i] = 0u;
+    if (i < g.groups) g.gkey[i] = 0ull;
+    if (i < MCRT_BEAM_COUNTERS) g.lcount[i] = 0u;
     if (i <= MCRT_MAX_BOUNCES) g.l_counts[i] = 0u;
     if (i < MCRT_MAX_BOUNCES * MCRT_XCDS) g.l_cursors[(size_t)i * MCRT_CURSOR_STRIDE] = 0u;
 }
 
 __global__ void __launch_bounds__(256) k_beam_bounds(FrameArgs a, BeamArgs g)
 {
-    const uint32_t n = a.counts[1];
+    const uint32_t n = a.counts[g.b];
     const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
     // one packet of 64 queue neighbours out of every `stride` is a sample of its beams -- WHICH one of the stride is a hash of the wavefront's number: k_shade
     // queues a workgroup's reflected rays first, so a fixed position repeats with the queue's period and can miss a history for good (every 16th packet of
@@ -83,7 +125,12 @@ __global__ void __launch_bounds__(256) k_beam_bounds(FrameArgs a, BeamArgs g)
     if (base >= n) return;
     const uint32_t i = base + lane;
     BeamRay r; r.bid = -1;
-    const bool live = i < n && beam_ray(a, i, r);
+    bool live = i < n && beam_ray(a, g, i, true, r);
+    if (g.groups != 0u) {
+        const unsigned long long lost = __ballot(live && r.bid < 0);
+        if (lost && lane == 0u) atomicAdd(&g.lcount[6], (uint32_t)__popcll(lost));
+        live = live && r.bid >= 0;
+    }
     unsigned long long todo = __ballot(live);
     while (todo) {
         const int cb = __builtin_amdgcn_readlane(r.bid, __ffsll((long long)todo) - 1);
@@ -125,21 +172,29 @@ MCRT_DEV bool beam_box(const BeamGeom &B, f3 lo, f3 hi, float &s_begin)
     return true;
 }
 
-// the beam's record, as k_beam_test reads it: 0-3 umin umax vmin vmax | 4-6 f2 lo | 7-9 f2 hi | 10 size | 11 m | 12 xref | 13 s_end | 14 entries | 15 -
+// the beam's record, as k_beam_test reads it: 0-3 umin umax vmin vmax | 4-6 f2 lo | 7-9 f2 hi | 10 size | 11 m | 12 xref | 13 s_end | 14 entries | 15 its list
 // (a beam without members, or refused: the slope bounds are an empty interval, so that no ray proves itself inside)
-__global__ void __launch_bounds__(BEAM_CT) k_beam_collect(FrameArgs a, BeamArgs g)
+MCRT_DEV void beam_collect(const FrameArgs &a, const BeamArgs &g, const uint32_t beam)
 {
     __shared__ int q[2][BEAM_QN];
     __shared__ unsigned long long ent[BEAM_EN];
     __shared__ uint32_t leaf[BEAM_LN];
-    __shared__ uint32_t nq[2], n_leaf, n_ent, overflow;
-    const uint32_t beam = blockIdx.x, lane = threadIdx.x;
+    __shared__ uint32_t nq[2], n_leaf, n_ent, overflow, list_at;
+    const uint32_t lane = threadIdx.x;
     const uint32_t *w = g.red + (size_t)beam * MCRT_BEAM_REC;
     uint32_t *rec = g.rec + (size_t)beam * MCRT_BEAM_REC;
     float umin = funord(w[0]), vmin = funord(w[1]), umax = funord(w[8]), vmax = funord(w[9]);
     const bool empty = w[0] == 0xffffffffu;
-    const bool refused = !empty && !(umax - umin <= g.spread_cap && vmax - vmin <= g.spread_cap);
+    bool refused = !empty && !(umax - umin <= g.spread_cap && vmax - vmin <= g.spread_cap);
     if (!empty && lane == 0u) atomicAdd(&g.lcount[4], 1u);
+    // the beam's list: its own (bounce 1), or the next of the pool -- a beam that finds the pool empty is refused
+    uint32_t li = beam;
+    if (g.groups != 0u) {
+        if (lane == 0u) list_at = (empty || refused) ? 0u : atomicAdd(&g.lcount[5], 1u);
+        __syncthreads();
+        li = list_at;
+        if (li >= g.n_lists) refused = !empty;
+    }
     if (empty || refused) {
         if (lane < MCRT_BEAM_REC) rec[lane] = lane == 0u || lane == 2u ? __float_as_uint(INFINITY) : lane == 1u || lane == 3u || lane == 13u ? __float_as_uint(-INFINITY) : 0u;
         if (refused && lane == 0u) atomicAdd(&g.lcount[3], 1u);
@@ -231,7 +286,7 @@ __global__ void __launch_bounds__(BEAM_CT) k_beam_collect(FrameArgs a, BeamArgs 
         const unsigned long long x = ent[e];
         const float4 *T = a.tris + (size_t)(uint32_t)x * MCRT_TRI_PIECES;
         const float4 t0 = T[0], t1 = T[1], t2 = T[2];
-        float4 *L = (float4 *)(g.list + 4 * ((size_t)beam * g.cap + e));
+        float4 *L = (float4 *)(g.list + 4 * ((size_t)li * g.cap + e));
         L[0] = t0; L[1] = make_float4(t1.x, t1.y, t1.z, funord((uint32_t)(x >> 32))); L[2] = t2; L[3] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
     // s_end: the depth up to which the list is complete
@@ -239,15 +294,26 @@ __global__ void __launch_bounds__(BEAM_CT) k_beam_collect(FrameArgs a, BeamArgs 
     if (lane == 0u) {
         rec[0] = __float_as_uint(umin); rec[1] = __float_as_uint(umax); rec[2] = __float_as_uint(vmin); rec[3] = __float_as_uint(vmax);
         for (int k = 0; k < 3; k++) { rec[4 + k] = __float_as_uint(flo[k]); rec[7 + k] = __float_as_uint(fhi[k]); }
-        rec[10] = __float_as_uint(cmax); rec[11] = __float_as_uint(m); rec[12] = __float_as_uint(B.xref); rec[13] = __float_as_uint(s_end); rec[14] = keep; rec[15] = 0u;
+        rec[10] = __float_as_uint(cmax); rec[11] = __float_as_uint(m); rec[12] = __float_as_uint(B.xref); rec[13] = __float_as_uint(s_end); rec[14] = keep; rec[15] = li;
         if (lost || N > g.cap) atomicAdd(&g.lcount[2], 1u);
     }
 }
 
-// pass 0: every ray of the bounce-1 queue against entries [0, near) of its beam's list; pass 1: the leftovers of pass 0 against the rest
+// bounce 1: a workgroup per beam.  Bounces >= 2: a workgroup per slot of the group table takes the slot's 6 beams in turn -- nearly every group has one dominant
+// axis and sign, and most slots are free: a sixth of the workgroups, which find their beams empty with one load each
+__global__ void __launch_bounds__(BEAM_CT) k_beam_collect(FrameArgs a, BeamArgs g)
+{
+    const uint32_t per = g.groups != 0u ? 6u : 1u;
+    for (uint32_t k = 0; k < per; k++) {
+        beam_collect(a, g, blockIdx.x * per + k);
+        __syncthreads();
+    }
+}
+
+// pass 0: every ray of the bounce's queue against entries [0, near) of its beam's list; pass 1: the leftovers of pass 0 against the rest
 __global__ void __launch_bounds__(256) k_beam_test(FrameArgs a, BeamArgs g, uint32_t pass)
 {
-    const uint32_t n = pass == 0u ? a.counts[1] : g.lcount[0];
+    const uint32_t n = pass == 0u ? a.counts[g.b] : g.lcount[0];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t base = (blockIdx.x * 256u + threadIdx.x) & ~63u;
     if (base >= n) return;
@@ -255,7 +321,7 @@ __global__ void __launch_bounds__(256) k_beam_test(FrameArgs a, BeamArgs g, uint
     const bool live = j < n;
     const uint32_t ray = !live ? 0u : pass == 0u ? j : g.lq0[j];
     BeamRay r;
-    bool member = beam_ray(a, ray, r) && live;
+    bool member = beam_ray(a, g, ray, false, r) && live && r.bid >= 0;
     const uint32_t *rec = g.rec + (size_t)(member ? r.bid : 0) * MCRT_BEAM_REC;
     {
         const float4 b0 = ((const float4 *)rec)[0], b1 = ((const float4 *)rec)[1], b2 = ((const float4 *)rec)[2];
@@ -266,7 +332,7 @@ __global__ void __launch_bounds__(256) k_beam_test(FrameArgs a, BeamArgs g, uint
     const f3 d = to - f2;
     const f3 inv = mk(rcp_dir(d.x), rcp_dir(d.y), rcp_dir(d.z));
     const f3 rc = ray_c(f2, inv);
-    unsigned long long *keys = a.key1;
+    unsigned long long *keys = (g.b & 1u) ? a.key1 : a.key0;
     Best best; best.frac = 1.0f; best.tri = -1;
     if (pass != 0u && live) { const unsigned long long k = keys[ray]; best.frac = __uint_as_float((uint32_t)(k >> 32)); best.tri = (int)(uint32_t)k; }
     const float f2d = comp(f2, r.dom), sg = r.neg ? -1.0f : 1.0f;
@@ -277,13 +343,13 @@ __global__ void __launch_bounds__(256) k_beam_test(FrameArgs a, BeamArgs g, uint
         const int cb = __builtin_amdgcn_readlane(r.bid, __ffsll((long long)todo) - 1);
         const bool mine = member && r.bid == cb;
         todo &= ~__ballot(mine);
-        const u32x4 R = sload4(g.rec + (size_t)cb * MCRT_BEAM_REC + 11);      // m, xref, s_end, entries
-        const float m2 = 2.0f * __uint_as_float(R[0]), xref = __uint_as_float(R[1]);
-        const uint32_t n_ent = R[3];
+        const u32x8 R = sload8(g.rec + (size_t)cb * MCRT_BEAM_REC + 8);      // ..., m, xref, s_end, entries, list
+        const float m2 = 2.0f * __uint_as_float(R[3]), xref = __uint_as_float(R[4]);
+        const uint32_t n_ent = R[6];
         // the depth of the hit, plus the margin: what begins beyond it cannot be accepted before it
         float reach = best.tri >= 0 ? sg * ((f2d + best.frac * r.dd) - xref) + m2 : INFINITY;
-        float limit = __uint_as_float(R[2]);
-        const char *L = (const char *)(g.list + 4 * (size_t)(uint32_t)cb * g.cap);
+        float limit = __uint_as_float(R[5]);
+        const char *L = (const char *)(g.list + 4 * (size_t)R[7] * g.cap);
         // (two entries per round trip to the scalar cache; the second of the last pair may lie past the list: it is fetched, not looked at)
         for (uint32_t k = first; k < n_ent; k += 2u) {
             u32x8 A, A2; u32x4 C2, C22;
@@ -314,34 +380,40 @@ __global__ void __launch_bounds__(256) k_beam_test(FrameArgs a, BeamArgs g, uint
     }
 }
 
-// the leftovers' state, compact, where the lane walk of an EVEN bounce reads it: half 0 of st0 / st1 and key0, which nothing reads between
-// k_shade(0) and k_shade(1)
+// the leftovers' state, compact, where the lane walk of a bounce of the OTHER parity reads it: that half of st0 / st1 and its key words, which nothing reads
+// between k_shade(b - 1) and k_shade(b) (k_march of bounce b - 1, on its side stream, reads mrec and seg_count)
+MCRT_DEV uint32_t beam_walk_as(uint32_t b) { return (b & 1u) ? 2u : 1u; }      // the bounce the leftovers are walked as, in an argument block of their own
 __global__ void __launch_bounds__(256) k_beam_gather(FrameArgs a, BeamArgs g, uint32_t which)
 {
     const uint32_t n = g.lcount[which];
     const uint32_t *lq = which == 0u ? g.lq0 : g.lq1;
-    const size_t np = (size_t)a.ne * a.S;
-    if (blockIdx.x == 0u && threadIdx.x == 0u) g.l_counts[MCRT_BEAM_WALK_AS] = n;
+    const size_t np = (size_t)a.ne * a.S, in = (g.b & 1u) ? np : 0, out = np - in;
+    unsigned long long *keys = (g.b & 1u) ? a.key0 : a.key1;
+    if (blockIdx.x == 0u && threadIdx.x == 0u) g.l_counts[beam_walk_as(g.b)] = n;
     for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < n; j += gridDim.x * 256u) {
         const uint32_t r = lq[j];
-        a.st0[j] = a.st0[np + r]; a.st1[j] = a.st1[np + r]; a.key0[j] = MCRT_KEY_MISS;
+        a.st0[out + j] = a.st0[in + r]; a.st1[out + j] = a.st1[in + r]; keys[j] = MCRT_KEY_MISS;
     }
 }
 __global__ void __launch_bounds__(256) k_beam_scatter(FrameArgs a, BeamArgs g, uint32_t which)
 {
     const uint32_t n = g.lcount[which];
     const uint32_t *lq = which == 0u ? g.lq0 : g.lq1;
-    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < n; j += gridDim.x * 256u) a.key1[lq[j]] = a.key0[j];
+    unsigned long long *keys = (g.b & 1u) ? a.key1 : a.key0;
+    const unsigned long long *walked = (g.b & 1u) ? a.key0 : a.key1;
+    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < n; j += gridDim.x * 256u) keys[lq[j]] = walked[j];
 }
 
-// bounce 1's closest hits by beams, in place of launch_trace(a, 1): the same key1 words
-hipError_t launch_beam_b1(const FrameArgs &a, const BeamArgs &g, hipStream_t st)
+// bounce g.b's closest hits by beams, in place of launch_trace(a, g.b): the same key words
+hipError_t launch_beam(const FrameArgs &a, const BeamArgs &g, hipStream_t st)
 {
     const uint32_t np = a.ne * a.S, blocks = (np + 255u) / 256u;
-    const uint32_t words = g.n_beams * MCRT_BEAM_REC, setup = words > MCRT_MAX_BOUNCES * MCRT_XCDS ? words : MCRT_MAX_BOUNCES * MCRT_XCDS;
+    uint32_t setup = g.n_beams * MCRT_BEAM_REC;
+    if (setup < MCRT_MAX_BOUNCES * MCRT_XCDS) setup = MCRT_MAX_BOUNCES * MCRT_XCDS;
+    if (setup < g.groups) setup = g.groups;
     hipLaunchKernelGGL(k_beam_clear, dim3((setup + 255u) / 256u), dim3(256), 0, st, g);
     hipLaunchKernelGGL(k_beam_bounds, dim3((blocks + g.stride - 1u) / g.stride), dim3(256), 0, st, a, g);
-    hipLaunchKernelGGL(k_beam_collect, dim3(g.n_beams), dim3(BEAM_CT), 0, st, a, g);
+    hipLaunchKernelGGL(k_beam_collect, dim3(g.groups != 0u ? g.groups : g.n_beams), dim3(BEAM_CT), 0, st, a, g);
     hipLaunchKernelGGL(k_beam_test, dim3(blocks), dim3(256), 0, st, a, g, 0u);
     const uint32_t which = g.near < g.cap ? 1u : 0u;
     if (which) hipLaunchKernelGGL(k_beam_test, dim3(blocks), dim3(256), 0, st, a, g, 1u);
@@ -349,10 +421,10 @@ hipError_t launch_beam_b1(const FrameArgs &a, const BeamArgs &g, hipStream_t st)
     hipLaunchKernelGGL(k_beam_gather, dim3(few), dim3(256), 0, st, a, g, which);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    // the leftovers as the queue of an even bounce of their own: counts and cursors of their own, no packets
+    // the leftovers as the queue of a bounce of the other parity: counts and cursors of their own, no packets
     FrameArgs w = a;
     w.counts = g.l_counts; w.cursors = g.l_cursors; w.packet_mask = 0u;
-    e = launch_trace(w, MCRT_BEAM_WALK_AS, false, st);
+    e = launch_trace(w, (g.b & 1u) ? 2u : 1u, false, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_beam_scatter, dim3(few), dim3(256), 0, st, a, g, which);
     return hipGetLastError();

@@ -23,15 +23,17 @@ struct Consts {   // main.cpp:23-37, rfimage.h:48-51,178-180 evaluated at run ti
 struct PathBufs {   // sized for `paths` paths of `depth` bounces
     Buf<float4> st0, st1, st2, mrec;
     Buf<unsigned long long> key0, key1;
-    Buf<uint32_t> q, counts, seg_count, cursors;
+    Buf<uint32_t> q, counts, seg_count, cursors, from_tri;
     size_t paths = 0; uint32_t depth = 0;
 };
-// bounce 1 by beams (mcrt_beam.hip; BeamArgs in mcrt_kernels.h): the beams' reduction words, records and candidate lists, the leftover counters, and the
-// counts and cursors the leftovers are walked with.  Sized for `beams` beams of `cap` candidates.
+// bounces by beams (mcrt_beam.hip; BeamArgs in mcrt_kernels.h): the beams' reduction words, records and candidate lists, the group table of the bounces >= 2,
+// every bounce's counters, and the counts and cursors the leftovers are walked with.  Sized for `beams` beams, `lists` lists of `cap` candidates and `groups`
+// slots; reused from bounce to bounce (stream order).
 struct BeamBufs {
     Buf<uint32_t> red, rec, lcount, l_counts, l_cursors;
     Buf<uint4> list;
-    uint32_t beams = 0, cap = 0;
+    Buf<unsigned long long> gkey;
+    uint32_t beams = 0, lists = 0, groups = 0, cap = 0;
 };
 struct Work {
     Stream stream, side[MCRT_SIDE_STREAMS];   // k_march of bounce b runs on side[b % n] (n: Plan::sides)
@@ -58,6 +60,9 @@ struct Knobs {
     uint32_t beam_b1 = 1;                      // MCRT_BEAM_B1=0|1|2: bounce 1 of a pass with one probe pose tests each scan-line's rays against its beams' triangles (mcrt_beam.hip) -- 1: where it
                                                // would run as packets, 2: in every staged pass, 0: never
     uint32_t beam_from = MCRT_BEAM_FROM;       // MCRT_BEAM_FROM: ... in passes of at least this many paths (MCRT_BEAM_B1=1)
+    uint32_t beam_last = MCRT_BEAM_LAST_DEFAULT;   // MCRT_BEAM_LAST: the last bounce run by beams (1: bounce 1 alone); the bounces 2 .. beam_last of a pass with one probe pose group their rays by the triangle they left
+    uint32_t beam_deep_from = MCRT_BEAM_DEEP_FROM; // MCRT_BEAM_DEEP_FROM: ... in passes of at least this many paths (MCRT_BEAM_B1=1; 2 takes them in every staged pass, 0 in none)
+    uint32_t beam_groups = 0;                  // MCRT_BEAM_GROUPS: slots of the group table (rounded down to a power of two); 0: MCRT_BEAM_GROUPS_PER_LINE per scan-line
     uint32_t beam_cap = MCRT_BEAM_CAP_DEFAULT, beam_near = MCRT_BEAM_NEAR_DEFAULT;   // MCRT_BEAM_CAP, MCRT_BEAM_NEAR: candidates a beam's list holds, and how many of them the first pass tests
     bool render_row_tile = false;              // MCRT_RENDER_ROW_TILE=1: a wavefront of k_render owns 64 pixels of one picture row in place of an 8 x 8 tile (RenderArgs::row_tile)
     uint32_t speckle_fuse = MCRT_SPECKLE_FUSE_DEFAULT;   // MCRT_SPECKLE_FUSE=2|4: iterations of mcrt_speckle_frames per launch of k_srad; 4 is faster for one frame, 2 for a stack
@@ -180,7 +185,8 @@ struct Instrumentation {
     Buf<unsigned long long> d_stats; bool stats_on = false;
     bool timing_on = false; int timing_level = 0;       // 1: the walk's launches are bracketed by HIP events; 2: k_shade's and k_march's too
     std::vector<TimedLaunch> ev; size_t ev_used = 0;
-    bool last_beam = false;                             // the last pass ran bounce 1 by beams (mcrt_debug_beam)
+    uint32_t last_beam_mask = 0;                        // bit b: the last pass ran bounce b by beams (mcrt_debug_beam, mcrt_debug_beam_bounce)
+    bool last_beam_far = false;                         // ... and its leftovers are those of the second pass over the lists
     float last_lean_bound = 0.0f; uint32_t last_march_rows = 0;   // what the last frame's kernels were given (mcrt_debug_fast_paths)
 };
 

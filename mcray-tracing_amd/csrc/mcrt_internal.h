@@ -24,6 +24,14 @@
 #define MCRT_BEAM_FROM 2097152u        // bounce 1 by beams (mcrt_beam.hip) in passes of at least this many paths (16 frames of 128 x 1024), where bounce 1 would run as packets: the stage has fixed parts
                                        // (one collection per beam, the bounds, seven launches) -- against packets, ms per frame at 6 / 8 / 12 / 16 / 20 / 128 frames: 0.520 / 0.446 / 0.377 / 0.341 / 0.319 / 0.252
                                        // against 0.511 / 0.441 / 0.370 / 0.341 / 0.320 / 0.272 (profiles/beam/small_pass.txt)
+#define MCRT_BEAM_LAST_DEFAULT 2u       // the last bounce run by beams (mcrt_beam.hip): bounce 2 by the triangle its rays left.  Bounce 3 added to it measured inside the spread of the runs
+                                       // (0.2423 against 0.2442 ms per frame, spread 0.0045), bounce 4 slower: built, tested, off (profiles/beam_deep)
+#define MCRT_BEAM_DEEP_FROM 6291456u   // ... in passes of at least this many paths (48 frames of 128 x 1024), the smallest pass measured to gain: ms per frame without / with bounce 2 by beams at
+                                       // 20 / 48 / 128 frames 0.3195 / 0.2701 / 0.2512 against 0.3381 / 0.2580 / 0.2432 -- below 4 Mi paths the bounds are taken over the whole queue, and the
+                                       // stage's fixed parts weigh against a shorter walk; nothing was measured between 20 and 48 frames
+#define MCRT_BEAM_GROUPS_PER_LINE 32u  // slots of the group table per scan-line (rounded up to a power of two in all): the headline pass of 128 x 1024 x 128 paths claims 6 / 20 / 30 slots per
+                                       // scan-line at bounces 2 / 3 / 4 (profiles/beam_deep/debug_counters.txt); a group that finds no slot among MCRT_BEAM_PROBES is walked
+#define MCRT_BEAM_LISTS_PER_GROUP 1u   // lists of the pool per slot of the table: nearly every group has one dominant axis and sign
 #define MCRT_BEAM_CAP_DEFAULT 512u     // candidates a beam's list holds (bounce 1 by beams, mcrt_beam.hip), at most MCRT_BEAM_CAP_MAX
 #define MCRT_BEAM_NEAR_DEFAULT 512u    // ... of which the first pass over all rays tests this many; fewer than the capacity: what is undecided then goes on as a compact queue through a second pass
 #define MCRT_BEAM_SPREAD 0.25f         // a beam whose slopes spread further than this is refused: its rays are walked

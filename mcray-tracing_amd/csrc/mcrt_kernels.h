@@ -3,7 +3,7 @@
 // The hot path's kernels, one translation unit per pipeline stage, each kernel beside its launcher:
 //   mcrt_walk.hip    k_trace_lane / k_trace_lane_wide (closest hit, one lane per ray), k_trace_packet (one wavefront per ray packet),
 //                    k_nodes_walk / k_nodes_walk_decode (the walk's 64-byte nodes)
-//   mcrt_beam.hip    k_beam_clear / bounds / collect / test / gather / scatter (bounce 1 of a pass with one probe pose: a scan-line's rays against one beam's triangles)
+//   mcrt_beam.hip    k_beam_clear / bounds / collect / test / gather / scatter (bounces 1 .. MCRT_BEAM_LAST of a pass with one probe pose: the rays of a group against one beam's triangles)
 //   mcrt_shade.hip   k_init (the first ray of every path), k_shade (interface physics of a bounce, survivors compacted into the next queue),
 //                    k_shade_fold (k_shade of bounce 0 with the boundary echoes of a silent start medium added in the kernel)
 //   mcrt_path.hip    k_path (the latency form: every bounce of every path in one launch)
@@ -51,6 +51,7 @@ struct FrameArgs {
                                //         (the walk reads st0 + st1 and rebuilds the ray from them: ray_of)
     uint32_t *queue;           // [2][np] live path ids of bounce b in buffer b & 1
     unsigned long long *key0, *key1;   // [np] closest hit per ray: fraction bits << 32 | triangle id (atomicMin), ping-pong by bounce parity
+    uint32_t *from_tri;        // [np] by path: the triangle its ray of the next bounce leaves; k_shade(b) writes it only where bounce b + 1 runs by beams (beam_mask)
     const uint32_t *tri_slot;  // [T] triangle id -> position in the leaf-order triangle array
     uint32_t *counts;          // [MAX_BOUNCES+1] live rays per bounce
     uint32_t *cursors;         // [MAX_BOUNCES][MCRT_XCDS][MCRT_CURSOR_STRIDE] queue cursors of the persistent walk, one per XCD sub-queue
@@ -71,24 +72,32 @@ struct FrameArgs {
     double axial_res_mm, time_step, row_dt, max_travel, sos_d, inv_row_dt;
     double thr_end;            // row_thr[R]: the first time past the image
     uint32_t retire_late;      // shade_path ends a path whose next segment would start past max_travel and past the image (off for counting and debug passes)
+    uint32_t beam_mask;        // bit b >= 2: bounce b runs by beams (mcrt_beam.hip), so k_shade(b - 1) writes from_tri
     uint32_t fold_b0;          // staged pass in a silent start medium: k_shade(b = 0) adds bounce 0's boundary echoes itself, writes no march record, no k_march(0)
 };
 
-// k_beam_* (mcrt_beam.hip): bounce 1 by beams.  A beam is a scan-line's rays of one history (reflected or refracted at bounce 0), one dominant axis and one
-// sign along it: MCRT_BEAM_SLOTS per scan-line, most of them empty.  Scratch that is dead between k_shade(0) and k_shade(1) carries the leftovers: lq0 is
-// half 0 of the queue, lq1 lies in half 0 of st2, and their compact state is half 0 of st0 / st1 with key0 (launch_beam_b1).
+// k_beam_* (mcrt_beam.hip): a bounce by beams.  A beam of BOUNCE 1 is a scan-line's rays of one history (reflected or refracted at bounce 0), one dominant axis
+// and one sign along it: MCRT_BEAM_SLOTS per scan-line, addressed directly, most of them empty.  A beam of a bounce b >= 2 is the rays of one GROUP -- scan-line,
+// the triangle the ray left (FrameArgs::from_tri), medium -- of one dominant axis and sign: the group claims a slot of a hash table (gkey), 6 beams per slot.
+// Scratch that is dead between k_shade(b - 1) and k_shade(b) -- the halves of the OTHER parity, bounce b - 1's consumed input -- carries the leftovers: lq0 is
+// that half of the queue, lq1 lies in that half of st2, and their compact state is that half of st0 / st1 with its key words (launch_beam).
 #define MCRT_BEAM_SLOTS 12u
 #define MCRT_BEAM_REC 16u            // words of a beam's reduction block and of its record
 #define MCRT_BEAM_CAP_MAX 1024u      // the largest list capacity (k_beam_collect sorts in LDS)
-#define MCRT_BEAM_WALK_AS 2u         // the leftovers are walked as the queue of this (even) bounce of an argument block of their own
+#define MCRT_BEAM_PROBES 4u          // slots of the group table a key is looked for in
+#define MCRT_BEAM_COUNTERS 8u        // counters of one beamed bounce
 struct BeamArgs {
     uint32_t *red;             // [n_beams][MCRT_BEAM_REC] k_beam_bounds' minima and maxima
     uint32_t *rec;             // [n_beams][MCRT_BEAM_REC] the beams as k_beam_test reads them (k_beam_collect)
-    uint4 *list;               // [n_beams][cap][4] (+ one entry of padding) 64-byte candidates, nearest first: v0 | id, v1 | depth at which the padded bounds begin, v2 | edge tolerance, -
+    uint4 *list;               // [n_lists][cap][4] (+ one entry of padding) 64-byte candidates, nearest first: v0 | id, v1 | depth at which the padded bounds begin, v2 | edge tolerance, -
+    unsigned long long *gkey;  // [groups] the group that holds the slot (0: free); bounces >= 2
     uint32_t *lq0, *lq1;       // [np] leftover rays (queue positions) of the near and of the far pass
-    uint32_t *lcount;          // [8] 0, 1: leftovers of the two passes; 2: beams whose list is incomplete; 3: beams refused (spread); 4: beams with members
+    uint32_t *lcount;          // [MCRT_BEAM_COUNTERS] of THIS bounce -- 0, 1: leftovers of the two passes; 2: beams whose list is incomplete; 3: beams refused (spread, or no list left);
+                               // 4: beams with members; 5: lists handed out; 6: sampled rays whose group found no slot; 7: slots claimed
     uint32_t *l_counts, *l_cursors;   // the leftover walk's FrameArgs::counts and cursors
-    uint32_t n_beams, cap, near, stride;   // near: entries of a list the first pass tests; stride: every stride-th packet of the queue is sampled for the bounds
+    uint32_t b;                // the bounce
+    uint32_t groups;           // slots of the group table, a power of two; 0: bounce 1's direct addressing, a beam's list is list[beam]
+    uint32_t n_beams, n_lists, cap, near, stride;   // near: entries of a list the first pass tests; stride: every stride-th packet of the queue is sampled for the bounds
     float spread_cap;          // a beam whose slopes spread further is refused
 };
 
@@ -243,7 +252,7 @@ struct RenderLabelArgs {
 
 hipError_t launch_init(const FrameArgs &a, hipStream_t st);
 hipError_t launch_trace(const FrameArgs &a, uint32_t b, bool stats, hipStream_t st);
-hipError_t launch_beam_b1(const FrameArgs &a, const BeamArgs &g, hipStream_t st);   // bounce 1's closest hits by beams, in place of launch_trace(a, 1)
+hipError_t launch_beam(const FrameArgs &a, const BeamArgs &g, hipStream_t st);   // bounce g.b's closest hits by beams, in place of launch_trace(a, g.b): the same key words
 hipError_t launch_nodes_walk(const float4 *nodes, uint32_t n_nodes, uint4 *out, hipStream_t st);
 hipError_t launch_nodes_walk_decode(const uint4 *walk, uint32_t n_nodes, float4 *out, hipStream_t st);
 uint32_t lane_stack_entries();

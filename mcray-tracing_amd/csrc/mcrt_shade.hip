@@ -113,6 +113,9 @@ MCRT_DEV void shade_bounce(const FrameArgs &a, uint32_t b)
         const f3 f2 = ry.f2, to = ry.to;
         const size_t hi = (b == 0u) ? (size_t)(i / a.S) : (size_t)i;            // bounce 0: one walk per queued (scan-line, frame) (see k_trace_lane, k_init)
         const unsigned long long key = ((b & 1u) ? a.key1 : a.key0)[hi];
+        // the triangle this ray ends on and its successor leaves, for the beams of the next bounce (mcrt_beam.hip), by path -- stored here, before shade_path, so that
+        // nothing more is live across it (k_shade stays at 64 registers), and only where that bounce runs by beams: the branch is wave-uniform
+        if ((a.beam_mask >> (b + 1u)) & 1u) a.from_tri[pid] = (uint32_t)key;
         FoldEcho fo;
         alive = shade_path<STATS, FOLD>(a, tb, b, pid, ps, f2, to, key, reflected, st_seg, st_hits, &fo);
         if (FOLD) {

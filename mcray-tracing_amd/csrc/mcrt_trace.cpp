@@ -135,7 +135,7 @@ static int ensure_work(Work &w, size_t np, uint32_t B, size_t ovf, int out)
     w.b = PathBufs();                   // (the optional tables survive a re-allocation of the rest when they are large enough)
     PathBufs &b = w.b;
     HIP_TRY(b.st0.alloc(2 * np)); HIP_TRY(b.st1.alloc(2 * np)); HIP_TRY(b.st2.alloc(2 * np));   // two halves: bounce parity
-    HIP_TRY(b.key0.alloc(np)); HIP_TRY(b.key1.alloc(np));
+    HIP_TRY(b.key0.alloc(np)); HIP_TRY(b.key1.alloc(np)); HIP_TRY(b.from_tri.alloc(np));
     HIP_TRY(b.q.alloc(2 * np)); HIP_TRY(b.seg_count.alloc(np));
     HIP_TRY(b.counts.alloc(MCRT_MAX_BOUNCES + 1));
     HIP_TRY(b.cursors.alloc((size_t)MCRT_MAX_BOUNCES * MCRT_XCDS * MCRT_CURSOR_STRIDE));
@@ -200,38 +200,69 @@ static void fill_pass(mcrt_ctx *c, const Plan &P, mcrt::FrameArgs &a, uint32_t f
 static void fill_group(const mcrt_ctx *c, const Work &w, mcrt::FrameArgs &a, uint32_t n_frames, uint32_t b0, uint32_t b1, uint32_t acc_e0, int out)
 {
     a.stack_ovf = w.stack_ovf; a.segs = w.segs; a.hits = out >= 1 ? (int32_t *)w.hits : nullptr;
-    a.st0 = w.b.st0; a.st1 = w.b.st1; a.st2 = w.b.st2; a.queue = w.b.q; a.key0 = w.b.key0; a.key1 = w.b.key1;
+    a.st0 = w.b.st0; a.st1 = w.b.st1; a.st2 = w.b.st2; a.queue = w.b.q; a.key0 = w.b.key0; a.key1 = w.b.key1; a.from_tri = w.b.from_tri;
     a.counts = w.b.counts; a.cursors = w.b.cursors; a.mrec = w.b.mrec; a.seg_count = w.b.seg_count;
     a.acc_off = b0 - acc_e0;
     a.e_begin = b0; a.ne_frame = b1 - b0; a.ne = (b1 - b0) * n_frames;   // n_frames consecutive frame ids traced as one pass
     a.packet_mask = (c->ins.stats_on || (uint64_t)a.ne * a.S < c->knobs.packet_from) ? 0u : c->knobs.packet_mask;   // bounces walked a wavefront per ray packet (k_trace_packet); the counting build walks ray by ray
 }
 
-// Bounce 1 by beams (mcrt_beam.hip): where bounce 1 runs as packets today and the pass has ONE probe pose -- every bounce-1 ray of a scan-line then starts at the
-// same point in every frame.  Not in the latency form, a counting pass or a pass with per-frame poses; MCRT_BEAM_B1=2 takes it in every other pass.
-static bool beam_wanted(const mcrt_ctx *c, const Plan &P, const mcrt::FrameArgs &a)
+// Bounces by beams (mcrt_beam.hip), as a mask of bounces.  Bounce 1: where it runs as packets today and the pass has ONE probe pose -- every bounce-1 ray of a
+// scan-line then starts at the same point in every frame.  Bounces 2 .. MCRT_BEAM_LAST: in passes of at least MCRT_BEAM_DEEP_FROM paths with one pose (their rays
+// are grouped by the triangle they left, the same in every frame).  Not in the latency form, a counting pass or a pass with per-frame poses; MCRT_BEAM_B1=2 takes
+// all of them in every other pass, 0 none.
+static uint32_t beam_wanted(const mcrt_ctx *c, const Plan &P, const mcrt::FrameArgs &a)
 {
-    if (P.latency || c->ins.stats_on || a.pose_stride != 0u || a.B < 2u || a.n_nodes == 0u) return false;
-    return c->knobs.beam_b1 == 2u || (c->knobs.beam_b1 == 1u && (a.packet_mask & 2u) != 0u && (uint64_t)a.ne * a.S >= c->knobs.beam_from);
+    if (P.latency || c->ins.stats_on || a.pose_stride != 0u || a.B < 2u || a.n_nodes == 0u || c->knobs.beam_b1 == 0u) return 0u;
+    const bool force = c->knobs.beam_b1 == 2u;
+    const uint64_t np = (uint64_t)a.ne * a.S;
+    uint32_t mask = 0;
+    if (force || ((a.packet_mask & 2u) != 0u && np >= c->knobs.beam_from)) mask |= 2u;
+    if (force || np >= c->knobs.beam_deep_from)
+        for (uint32_t b = 2; b <= c->knobs.beam_last && b < a.B; b++) mask |= 1u << b;
+    return mask;
 }
-static int fill_beam(const mcrt_ctx *c, Work &w, const mcrt::FrameArgs &a, mcrt::BeamArgs &g)
+// what the beamed bounces of a group share: the buffers, sized for the largest of them; beam_args makes bounce b's block of it
+struct BeamPlan { mcrt::BeamArgs g = {}; uint32_t mask = 0, beams_b1 = 0, groups = 0; };
+static int fill_beam(const mcrt_ctx *c, Work &w, const mcrt::FrameArgs &a, uint32_t mask, BeamPlan &bp)
 {
-    const uint32_t beams = a.ne_frame * MCRT_BEAM_SLOTS, cap = c->knobs.beam_cap;
+    const uint32_t cap = c->knobs.beam_cap;
+    bp.mask = mask; bp.beams_b1 = a.ne_frame * MCRT_BEAM_SLOTS; bp.groups = 0;
+    if (mask & ~2u) {      // the group table: a power of two
+        const uint64_t want = c->knobs.beam_groups ? c->knobs.beam_groups : (uint64_t)a.ne_frame * MCRT_BEAM_GROUPS_PER_LINE;
+        bp.groups = 1u;
+        while ((uint64_t)bp.groups * 2u <= want && bp.groups < (1u << 20)) bp.groups *= 2u;
+        if (!c->knobs.beam_groups && bp.groups < want) bp.groups *= 2u;
+    }
+    const uint32_t beams = std::max((mask & 2u) ? bp.beams_b1 : 0u, bp.groups * 6u);
+    const uint32_t lists = std::max((mask & 2u) ? bp.beams_b1 : 0u, bp.groups * MCRT_BEAM_LISTS_PER_GROUP);
     BeamBufs &b = w.beam;
-    if (beams > b.beams || cap != b.cap) {
+    if (beams > b.beams || lists > b.lists || bp.groups > b.groups || cap != b.cap) {
         HIP_TRY(hipDeviceSynchronize());
-        b.beams = b.cap = 0;
-        HIP_TRY(b.red.alloc((size_t)beams * MCRT_BEAM_REC)); HIP_TRY(b.rec.alloc((size_t)beams * MCRT_BEAM_REC)); HIP_TRY(b.list.alloc(((size_t)beams * cap + 1) * 4));
-        HIP_TRY(b.lcount.grow(8)); HIP_TRY(b.l_counts.grow(MCRT_MAX_BOUNCES + 1)); HIP_TRY(b.l_cursors.grow((size_t)MCRT_MAX_BOUNCES * MCRT_XCDS * MCRT_CURSOR_STRIDE));
-        b.beams = beams; b.cap = cap;
+        b.beams = b.lists = b.groups = b.cap = 0;
+        HIP_TRY(b.red.alloc((size_t)beams * MCRT_BEAM_REC)); HIP_TRY(b.rec.alloc((size_t)beams * MCRT_BEAM_REC)); HIP_TRY(b.list.alloc(((size_t)lists * cap + 1) * 4));
+        HIP_TRY(b.gkey.alloc(std::max(bp.groups, 1u)));
+        HIP_TRY(b.lcount.grow((size_t)MCRT_MAX_BOUNCES * MCRT_BEAM_COUNTERS)); HIP_TRY(b.l_counts.grow(MCRT_MAX_BOUNCES + 1)); HIP_TRY(b.l_cursors.grow((size_t)MCRT_MAX_BOUNCES * MCRT_XCDS * MCRT_CURSOR_STRIDE));
+        b.beams = beams; b.lists = lists; b.groups = bp.groups; b.cap = cap;
     }
     const size_t np = (size_t)a.ne * a.S;
-    g.red = b.red; g.rec = b.rec; g.list = b.list; g.lcount = b.lcount; g.l_counts = b.l_counts; g.l_cursors = b.l_cursors;
-    g.lq0 = a.queue; g.lq1 = (uint32_t *)a.st2;      // (half 0 of each: dead between k_shade(0) and k_shade(1))
-    g.n_beams = beams; g.cap = cap; g.near = std::min(c->knobs.beam_near, cap);
+    mcrt::BeamArgs &g = bp.g;
+    g.red = b.red; g.rec = b.rec; g.list = b.list; g.gkey = b.gkey; g.lcount = b.lcount; g.l_counts = b.l_counts; g.l_cursors = b.l_cursors;
+    g.cap = cap; g.near = std::min(c->knobs.beam_near, cap);
     g.stride = np >= MCRT_BEAM_SAMPLE_FROM ? MCRT_BEAM_SAMPLE_STRIDE : 1u;
     g.spread_cap = MCRT_BEAM_SPREAD;
     return MCRT_OK;
+}
+static mcrt::BeamArgs beam_args(const BeamPlan &bp, const mcrt::FrameArgs &a, uint32_t b)
+{
+    mcrt::BeamArgs g = bp.g;
+    const size_t other = (b & 1u) ? 0 : (size_t)a.ne * a.S;      // the halves of the other bounce parity: dead between k_shade(b - 1) and k_shade(b)
+    g.b = b; g.lcount = bp.g.lcount + (size_t)b * MCRT_BEAM_COUNTERS;
+    g.lq0 = a.queue + other; g.lq1 = (uint32_t *)(a.st2 + other);
+    g.groups = b == 1u ? 0u : bp.groups;
+    g.n_beams = b == 1u ? bp.beams_b1 : bp.groups * 6u;
+    g.n_lists = b == 1u ? bp.beams_b1 : bp.groups * MCRT_BEAM_LISTS_PER_GROUP;
+    return g;
 }
 
 // The walk kernels (k_trace_lane*, k_path) index their traversal-stack overflow with stride gridDim.x * 256 and check no bound: the
@@ -268,9 +299,9 @@ template <class Launch> static int timed_launch(mcrt_ctx *c, int kind, hipStream
 // (Round 4 tried holding k_march of bounce b back until the walk of bounce b+1 had claimed its last ray -- a device word raised by the walk, waited
 //  for with hipStreamWaitValue32, which the command processor releases ~1 us after the store --: 0.360 against 0.343 ms per frame at 128 frames in
 //  flight, 0.414 against 0.405 on the driver's pass, and a hang under `rocprofv3 --pmc`.  Removed; DESIGN.md A.6, profiles/round4/exp_round4_kernels.txt.)
-static int run_bounce(mcrt_ctx *c, Work &w, hipStream_t st, const mcrt::FrameArgs &a, const mcrt::BeamArgs *beam, uint32_t b, uint32_t sides, bool accumulate, bool overlap)
+static int run_bounce(mcrt_ctx *c, Work &w, hipStream_t st, const mcrt::FrameArgs &a, const BeamPlan &beam, uint32_t b, uint32_t sides, bool accumulate, bool overlap)
 {
-    if (beam && b == 1u) MCRT_TRY(timed_launch(c, 0, st, [&] { return mcrt::launch_beam_b1(a, *beam, st); }));
+    if ((beam.mask >> b) & 1u) MCRT_TRY(timed_launch(c, 0, st, [&] { return mcrt::launch_beam(a, beam_args(beam, a, b), st); }));
     else MCRT_TRY(timed_launch(c, 0, st, [&] { return mcrt::launch_trace(a, b, c->ins.stats_on, st); }));
     MCRT_TRY(timed_launch(c, 1, st, [&] { return mcrt::launch_shade(a, b, c->ins.stats_on, st); }));
     if (!accumulate || (a.fold_b0 && b == 0u)) return MCRT_OK;      // (bounce 0 folded: k_shade has added its echoes; later bounces keep their side streams)
@@ -283,7 +314,7 @@ static int run_bounce(mcrt_ctx *c, Work &w, hipStream_t st, const mcrt::FrameArg
     return timed_launch(c, 2, ms, [&] { return mcrt::launch_march(a, b, c->ins.stats_on, ms); });
 }
 
-static int enqueue_pass(mcrt_ctx *c, const Plan &P, const mcrt::FrameArgs *args, const mcrt::BeamArgs *const *beams, Work *const *ws, bool accumulate)
+static int enqueue_pass(mcrt_ctx *c, const Plan &P, const mcrt::FrameArgs *args, const BeamPlan *beams, Work *const *ws, bool accumulate)
 {
     const bool overlap = !c->knobs.no_overlap;
     hipStream_t gst[16] = { c->stream };
@@ -328,7 +359,7 @@ static int run_pass(mcrt_ctx *c, uint32_t frame, uint32_t n_frames, uint32_t e0,
 {
     const Plan P = plan_pass(c, e0, e1, n_frames, one_group);
     mcrt::FrameArgs pass, args[16];
-    mcrt::BeamArgs bargs[16]; const mcrt::BeamArgs *beams[16] = {};
+    BeamPlan beams[16];
     Work *ws[16];
     fill_pass(c, P, pass, frame, e1 - e0, accumulate, out, pose_pos, pose_dir);
     for (uint32_t g = 0; g < P.groups; g++) {
@@ -337,9 +368,9 @@ static int run_pass(mcrt_ctx *c, uint32_t frame, uint32_t n_frames, uint32_t e0,
         args[g] = pass;
         fill_group(c, *ws[g], args[g], n_frames, P.e[g], P.e[g + 1], e0, out);
         MCRT_TRY(check_overflow(c, P, args[g], *ws[g]));
-        if (beam_wanted(c, P, args[g])) { MCRT_TRY(fill_beam(c, *ws[g], args[g], bargs[g])); beams[g] = &bargs[g]; }
+        if (const uint32_t mask = beam_wanted(c, P, args[g])) { MCRT_TRY(fill_beam(c, *ws[g], args[g], mask, beams[g])); args[g].beam_mask = mask & ~3u; }
     }
-    c->ins.last_beam = beams[0] != nullptr;
+    c->ins.last_beam_mask = beams[0].mask; c->ins.last_beam_far = c->knobs.beam_near < c->knobs.beam_cap;
     return enqueue_pass(c, P, args, beams, ws, accumulate);
 }
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Bounce 1 as BEAMS, COUNTED on the CPU oracle: what csrc/mcrt_beam.hip shares per scan-line.
+"""A bounce as BEAMS, COUNTED on the CPU oracle: what csrc/mcrt_beam.hip shares per scan-line (bounce 1) and per group (bounce b >= 2).
 
 Every bounce-1 ray of a scan-line starts at bounce 0's hit point.  On frame 0 of a workload this script groups the bounce-1 segments of the
 oracle into beams as the kernels do -- scan-line x history (the medium after bounce 0 is the start medium: reflected) x dominant axis x its
@@ -9,7 +9,15 @@ whether the origin is one point per scan-line; the spread of the slopes; candida
 90 % of the beam's hitting rays have hit ("near"); how many hit triangles are missing from their beam's candidates (must be 0); the share
 of rays that hit nothing.
 
-    python tools/beam_count.py [workload=random1m|liver|sphere] [rays=1024] [scan-lines=128]   -> JSON (profiles/beam/beam_count_*.json)
+With a bounce b >= 2 the group is the kernels' widened key -- scan-line, the triangle the previous segment ended on, medium -- and a beam is a group's rays
+of one dominant axis and sign.  Also counted then, per bounce: the list entries a ray tests before it is final (its hit's depth plus 2 m lies before the next
+entry's begin; a miss tests the whole list), ray-weighted; the same for the slowest ray of every beam among 64 QUEUE NEIGHBOURS, summed over the wavefront's
+beams (what k_beam_test's loop runs through); and the beams per 64 queue neighbours -- in k_shade's queue order: per 256 rays of the previous queue the
+reflected survivors first, then the refracted ones.  `lines` counts only that many scan-lines, spread evenly (the trace covers all of them).  A sixth argument `beams` adds the list of every beam (`per_beam`:
+thousands of lines at the deeper bounces) to the totals.
+
+    python tools/beam_count.py [workload=random1m|liver|sphere] [rays=1024] [scan-lines=128] [bounce=1] [lines=all] [beams]   -> JSON (profiles/beam/beam_count_*.json,
+                                                                                                                          profiles/beam_deep/beam_count_*_b*.json)
 """
 import json, os, sys, time
 import numpy as np
@@ -20,6 +28,10 @@ from oracle import orc
 workload = sys.argv[1] if len(sys.argv) > 1 else "random1m"
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
 E = int(sys.argv[3]) if len(sys.argv) > 3 else 128
+BN = int(sys.argv[4]) if len(sys.argv) > 4 else 1
+NL = int(sys.argv[5]) if len(sys.argv) > 5 else E
+PER_BEAM = len(sys.argv) > 6 and sys.argv[6] == "beams"
+counted = sorted(set(int(round(x)) for x in np.linspace(0, E - 1, min(NL, E))))
 cfg, meshes = {"random1m": lambda: m.synth.random_scene(1_000_000, 8, 12345), "liver": lambda: m.synth.liver_scene(5), "sphere": lambda: m.synth.sphere_scene(5)}[workload]()
 sd = m.scene_io.build_scene(cfg, meshes)
 tr = m.Transducer(E, position=cfg["transducerPosition"], angles_deg=cfg["transducerAngles"])
@@ -42,13 +54,26 @@ scene_abs = float(max(np.abs(plo).max(), np.abs(phi).max()))
 spacing = np.asarray(sd.spacing, np.float64)
 offs = float(p.ray_start_offset)
 
-sg = segs[:, :, 1]
-live = cnt > 1
+sg = segs[:, :, BN]
+live = cnt > BN
+# k_shade's queue order of bounce BN: position of every live (scan-line, sample) in the queue
+order = np.arange(E * S)
+for b in range(BN):
+    alive = (cnt.reshape(-1)[order] > b + 1)
+    refl = segs[:, :, min(b + 1, segs.shape[2] - 1)]["media"].reshape(-1)[order] == segs[:, :, b]["media"].reshape(-1)[order]
+    nxt = []
+    for c0 in range(0, len(order), 256):
+        o, a_, r_ = order[c0:c0 + 256], alive[c0:c0 + 256], refl[c0:c0 + 256]
+        nxt.append(o[a_ & r_]); nxt.append(o[a_ & ~r_])
+    order = np.concatenate(nxt) if nxt else order[:0]
+qpos = np.full(E * S, -1, np.int64); qpos[order] = np.arange(len(order))
+ray_beam = np.full(E * S, -1, np.int64); ray_tested = np.zeros(E * S, np.int64)
 same_origin, beams = 0, []
-missing = hitting = rays = 0
-for e in range(E):
+missing = hitting = rays = small = 0
+for e in counted:
     L = live[e]
     if not L.any(): continue
+    flat = e * S + np.flatnonzero(L)
     fr = sg["from"][e][L].astype(np.float64)
     same_origin += int((sg["from"][e][L].view(np.uint32) == sg["from"][e][L][0].view(np.uint32)).all())
     d = sg["dir"][e][L].astype(np.float64)
@@ -56,12 +81,13 @@ for e in range(E):
     f2 = fr + offs * d
     tri = sg["tri"][e][L]
     to = sg["to"][e][L].astype(np.float64)
-    hist = sg["media"][e][L] != sd.start_mat
+    hist = (sg["media"][e][L] != sd.start_mat) if BN == 1 else (segs[:, :, BN - 1]["tri"][e][L].astype(np.int64) * 4096 + sg["media"][e][L])
     dom = np.abs(D).argmax(1)
     neg = D[np.arange(len(D)), dom] < 0
     ok = np.isfinite(D).all(1)
     for key in np.unique(np.stack([hist, dom, neg], 1)[ok], axis=0):
         sel = ok & (hist == key[0]) & (dom == key[1]) & (neg == bool(key[2]))
+        if sel.sum() < 16: small += int(sel.sum())
         k, ka, kb = int(key[1]), (int(key[1]) + 1) % 3, (int(key[1]) + 2) % 3
         sgn = -1.0 if key[2] else 1.0
         ad = np.abs(D[sel, k])
@@ -85,19 +111,36 @@ for e in range(E):
         missing += int((~np.isin(tri[sel][hit], ids)).sum()); hitting += int(hit.sum()); rays += int(sel.sum())
         depth = sgn * (to[sel, k] - xref)
         d90 = float(np.quantile(depth[hit], 0.9)) if hit.any() else 0.0
-        beams.append({"scan_line": e, "reflected": bool(not key[0]), "axis": k, "negative": bool(key[2]), "rays": int(sel.sum()), "hitting": int(hit.sum()),
+        srt = np.sort(begin)
+        ray_tested[flat[sel]] = np.where(hit, np.searchsorted(srt, depth + 2 * mg, side="right"), len(srt))
+        ray_beam[flat[sel]] = len(beams)
+        beams.append({"scan_line": e, "reflected": bool(not key[0]) if BN == 1 else None, "axis": k, "negative": bool(key[2]), "rays": int(sel.sum()), "hitting": int(hit.sum()),
                       "spread_mrad": [float(1e3 * (u.max() - u.min())), float(1e3 * (v.max() - v.min()))],
                       "candidates": int(cand.sum()), "candidates_near": int((begin <= d90 + 2 * mg).sum()) if hit.any() else 0, "depth_90": d90})
 
 with_hits = [b for b in beams if b["hitting"]]
+# per 64 queue neighbours (wavefronts that lie wholly inside the counted scan-lines' rays count; others are skipped)
+in_beam = ray_beam >= 0
+wave_beams, wave_entries = [], []
+for w0 in range(0, len(order), 64):
+    ids = order[w0:w0 + 64]
+    if not in_beam[ids].all(): continue
+    bs = ray_beam[ids]
+    wave_beams.append(len(np.unique(bs)))
+    wave_entries.append(int(sum(ray_tested[ids][bs == u].max() for u in np.unique(bs))))
 spread = [max(b["spread_mrad"]) for b in beams]
-out = {"workload": workload, "scan_lines": E, "rays_per_line": S, "frame": 0, "oracle_trace_seconds": round(t_trace, 1),
-       "lines_reaching_bounce_1": int(live.any(1).sum()), "lines_with_one_origin": same_origin,
-       "rays_bounce_1": int(live.sum()), "rays_in_beams": rays, "rays_hitting": hitting, "miss_share": 1.0 - hitting / max(rays, 1),
+out = {"workload": workload, "scan_lines": E, "rays_per_line": S, "frame": 0, "bounce": BN, "scan_lines_counted": len(counted),
+       "beams_per_counted_scan_line": len(beams) / max(len(counted), 1), "rays_per_beam_mean": rays / max(len(beams), 1), "share_of_rays_in_beams_of_fewer_than_16": small / max(rays, 1),
+       "entries_tested_per_ray_mean": float(ray_tested[in_beam].mean()) if in_beam.any() else None,
+       "wavefronts_counted": len(wave_beams), "beams_per_64_queue_neighbours_mean_max": [float(np.mean(wave_beams)), int(np.max(wave_beams))] if wave_beams else None,
+       "entries_per_64_queue_neighbours_summed_over_their_beams_mean": float(np.mean(wave_entries)) if wave_entries else None, "oracle_trace_seconds": round(t_trace, 1),
+       "lines_reaching_the_bounce": int(live.any(1).sum()), "lines_with_one_origin": same_origin,
+       "rays_of_the_bounce": int(live.sum()), "rays_in_beams": rays, "rays_hitting": hitting, "miss_share": 1.0 - hitting / max(rays, 1),
        "hit_triangles_missing_from_candidates": missing,
        "beams": len(beams), "beams_with_hits": len(with_hits),
        "spread_mrad_min_median_max": [float(np.min(spread)), float(np.median(spread)), float(np.max(spread))],
        "candidates_to_exit_mean_max": [float(np.mean([b["candidates"] for b in beams])), int(np.max([b["candidates"] for b in beams]))],
        "candidates_near_mean_max": [float(np.mean([b["candidates_near"] for b in with_hits])), int(np.max([b["candidates_near"] for b in with_hits]))] if with_hits else None,
-       "per_beam": beams}
+       }
+if PER_BEAM: out["per_beam"] = beams
 print(json.dumps(out, indent=1))
