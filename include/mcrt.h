@@ -54,7 +54,8 @@ extern "C" {
                                    + mcrt_recon_label_opts, mcrt_default_recon_label_opts, mcrt_recon_label_frames, mcrt_render_label_frames
                                    (3-D ground truth: a freehand label volume by majority vote, the label of what a rendering shows; additive);
                                    + mcrt_debug_beam (what bounce 1 by beams did in the last pass; additive);
-                                   + mcrt_debug_beam_bounce (the same for any bounce run by beams; additive) */
+                                   + mcrt_debug_beam_bounce (the same for any bounce run by beams; additive);
+                                   + mcrt_debug_beam_order, mcrt_debug_beam_layout (the beam order of a bounce run by beams, its layout on the host; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -995,6 +996,16 @@ int mcrt_debug_beam(mcrt_ctx *ctx, uint32_t out[6]);
  * mcrt_debug_beam's -- out[1] + out[2] is the bounce's ray count --, out[6] sampled rays whose group found no slot of the group table (their
  * groups are walked), out[7] slots of the table claimed.  All 0 where bounce b did not run by beams.  Waits for the stream. */
 int mcrt_debug_beam_bounce(mcrt_ctx *ctx, uint32_t b, uint32_t out[8]);
+/* the BEAM ORDER of bounce b in the context's last traced pass (its first scan-line group) -- the permutation of the bounce's queue, grouped by beam,
+ * through which the rays are tested against their beams' lists, a wavefront per 64 words of it: out[0] 1 when bounce b ran by beams and was ordered,
+ * out[1] rays placed (the bounce's ray count), out[2] segments: beams that have rays, the pseudo-beam of the rays without a beam among them, out[3] pad
+ * lanes (every segment is rounded up to whole wavefronts: at most 63 per segment), out[4] the (wavefront, beam) pairs the first pass over the lists met --
+ * counted only in a context created with MCRT_TUNING=1 MCRT_BEAM_PAIRS=1, ordered or not, else 0.  All 0 where bounce b did not run by beams.  Waits for the stream. */
+int mcrt_debug_beam_order(mcrt_ctx *ctx, uint32_t b, uint32_t out[5]);
+/* the layout of a beam order on the HOST, the arithmetic of the kernel that lays it out (no context, no device): counts[n] rays per beam, the last the
+ * pseudo-beam's -> bases[n], where each beam's segment begins (an exclusive prefix over the counts rounded up to multiples of 64; an empty beam has no
+ * words), out[0] rays placed, out[1] segments, out[2] pad lanes, out[3] the order's length.  MCRT_ERR_LIMIT where the length passes 2^32 - 1. */
+int mcrt_debug_beam_layout(const uint32_t *counts, uint32_t n, uint32_t *bases, uint32_t out[4]);
 /* TEST HOOK, refused (MCRT_ERR_INVALID) unless the context was created with MCRT_TEST_HOOKS set in the environment: ORs `bits` into the
  * context's device error word on its stream, as an abandoned launch would (bit 0: traversal stack ran out, bit 1: kernel watchdog
  * expired) -- what mcrt_synchronize reports and what turns finalised RF images into NaN until it is asked */

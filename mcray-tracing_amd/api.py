@@ -133,6 +133,16 @@ def host_psf_elevation(var_z, pitch_um, n_rows, row_mm, focus_mm=(), focal_range
     return out
 
 
+def host_beam_layout(counts):
+    """mcrt_debug_beam_layout: the layout of a beam order (csrc/mcrt_beam.hip, k_beam_scan) for `counts` rays per beam, the last the pseudo-beam's ->
+    (bases uint32 [n], rays placed, segments, pad lanes, the order's length)"""
+    counts = np.ascontiguousarray(counts, np.uint32)
+    bases = np.zeros(len(counts), np.uint32)
+    out = (C.c_uint32 * 4)()
+    check(load_library().mcrt_debug_beam_layout(ptr(counts), len(counts), ptr(bases), out))
+    return bases, int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+
 def host_scan_maps(n_elements, n_rows, radius_mm=30.0, total_angle=DEFAULT_ANGLE, max_travel_us=100, speed_of_sound=1500, out_rows=400, out_cols=500):
     """rf_image::create_mapping (rfimage.h:183-215) as the library evaluates it: (map_row, map_col), each [out_rows][out_cols]"""
     return _sector_maps("mcrt_scan_maps", n_elements, n_rows, radius_mm, total_angle, max_travel_us, speed_of_sound, out_rows, out_cols)
@@ -605,6 +615,14 @@ class Context(_SceneCalls):
         out = (C.c_uint32 * 8)()
         if hasattr(self.L, "mcrt_debug_beam_bounce"):
             check(self.L.mcrt_debug_beam_bounce(self.h, int(b), out))
+        return (bool(out[0]),) + tuple(int(v) for v in out[1:])
+
+    def debug_beam_order(self, b):
+        """(bounce b ran by beams through the beam order, rays placed, segments, pad lanes, (wavefront, beam) pairs the first pass met -- the last only
+        with MCRT_BEAM_PAIRS=1) of the last traced pass: mcrt_debug_beam_order"""
+        out = (C.c_uint32 * 5)()
+        if hasattr(self.L, "mcrt_debug_beam_order"):
+            check(self.L.mcrt_debug_beam_order(self.h, int(b), out))
         return (bool(out[0]),) + tuple(int(v) for v in out[1:])
 
     def debug_set_error(self, bits):

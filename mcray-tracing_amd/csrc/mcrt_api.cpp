@@ -58,6 +58,8 @@ static Knobs read_knobs()
     if (const char *e = tuning_env("MCRT_BEAM_GROUPS")) { long long v = atoll(e); if (v >= 1 && v <= (1 << 20)) k.beam_groups = (uint32_t)v; }
     if (const char *e = tuning_env("MCRT_BEAM_CAP")) { int v = atoi(e); if (v >= 1 && v <= (int)MCRT_BEAM_CAP_MAX) k.beam_cap = (uint32_t)v; }
     if (const char *e = tuning_env("MCRT_BEAM_NEAR")) { int v = atoi(e); if (v >= 1) k.beam_near = (uint32_t)v; }
+    if (const char *e = tuning_env("MCRT_BEAM_ORDER")) { long v = strtol(e, nullptr, 0); if (v >= 0 && v < (1l << MCRT_MAX_BOUNCES)) k.beam_order = (uint32_t)v; }
+    if (const char *e = tuning_env("MCRT_BEAM_PAIRS")) k.beam_pairs = atoi(e) != 0;
     if (const char *e = tuning_env("MCRT_RENDER_ROW_TILE")) k.render_row_tile = atoi(e) != 0;
     if (const char *e = tuning_env("MCRT_SPECKLE_FUSE")) { int v = atoi(e); if (v == 2 || v == 4) k.speckle_fuse = (uint32_t)v; }
     return k;
@@ -588,6 +590,40 @@ extern "C" int mcrt_debug_beam_bounce(mcrt_ctx *c, uint32_t b, uint32_t out[8])
     CTX_TRY(c);
     if (!out) return set_error(MCRT_ERR_INVALID, "null out pointer");
     return debug_beam(c, b, out);
+}
+
+// the beam order of bounce b in the last traced pass (work set 0): whether the bounce was ordered, rays placed, segments (beams with rays, the pseudo-beam of
+// the rays without a beam among them), pad lanes, and the (wavefront, beam) pairs the first pass of k_beam_test met -- counted only in a context created with
+// MCRT_BEAM_PAIRS=1, ordered or not; 0 otherwise
+extern "C" int mcrt_debug_beam_order(mcrt_ctx *c, uint32_t b, uint32_t out[5])
+{
+    CTX_TRY(c);
+    if (!out) return set_error(MCRT_ERR_INVALID, "null out pointer");
+    for (int k = 0; k < 5; k++) out[k] = 0u;
+    if (b >= MCRT_MAX_BOUNCES || !((c->ins.last_beam_mask >> b) & 1u) || c->work.empty()) return MCRT_OK;
+    uint32_t lc[MCRT_BEAM_COUNTERS] = {};
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(lc, c->work[0].beam.lcount.p + (size_t)b * MCRT_BEAM_COUNTERS, sizeof lc, hipMemcpyDeviceToHost));
+    out[0] = (c->ins.last_beam_order >> b) & 1u; out[1] = lc[8]; out[2] = lc[9]; out[3] = lc[10]; out[4] = lc[11];
+    return MCRT_OK;
+}
+
+// k_beam_scan's arithmetic on the host (no context, no device): the segment bases of n counters -- the last is the pseudo-beam's --, and rays placed, segments,
+// pad lanes and the order's length
+extern "C" int mcrt_debug_beam_layout(const uint32_t *counts, uint32_t n, uint32_t *bases, uint32_t out[4])
+{
+    if ((!counts || !bases) && n) return set_error(MCRT_ERR_INVALID, "null pointer");
+    if (!out) return set_error(MCRT_ERR_INVALID, "null out pointer");
+    uint64_t at = 0, placed = 0;
+    uint32_t segments = 0;
+    for (uint32_t k = 0; k < n; k++) {
+        if (at > 0xffffffffull) return set_error(MCRT_ERR_LIMIT, "the beam order is longer than 2^32 words");
+        bases[k] = (uint32_t)at;
+        at += mcrt::beam_segment(counts[k]); placed += counts[k]; segments += counts[k] != 0u ? 1u : 0u;
+    }
+    if (at > 0xffffffffull) return set_error(MCRT_ERR_LIMIT, "the beam order is longer than 2^32 words");
+    out[0] = (uint32_t)placed; out[1] = segments; out[2] = (uint32_t)(at - placed); out[3] = (uint32_t)at;
+    return MCRT_OK;
 }
 
 extern "C" int mcrt_debug_set_error(mcrt_ctx *c, uint32_t bits)

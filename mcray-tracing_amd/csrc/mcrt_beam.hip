@@ -9,10 +9,14 @@
 //                   Bounce b >= 2: the GROUP (scan-line, the triangle the ray left -- FrameArgs::from_tri, written by k_shade(b - 1) --, medium) claims a slot of
 //                   a hash table with a compare-and-swap on its key word (MCRT_BEAM_PROBES slots are tried); a beam is slot x dominant axis x sign.  A ray whose
 //                   group found no slot, or was not in the sample, is no member of any beam and is walked.
+//   k_beam_rank     (bounces of MCRT_BEAM_ORDER) one lane per ray in queue order: its beam looked up, one atomic per (wavefront, beam) on the beam's counter; every ray
+//                   keeps its beam and its rank among the beam's rays.  A ray without a beam is counted into a pseudo-beam behind the last
+//   k_beam_scan     ... one workgroup: where every beam's SEGMENT of the order begins, each rounded up to whole wavefronts; the padding words, the totals
+//   k_beam_place    ... order[base[beam] + rank] = the ray's queue position: a permutation of the queue grouped by beam
 //   k_beam_collect  one workgroup per beam (bounce b >= 2: per slot, its 6 beams in turn): one traversal of the BVH4 with a conservative beam-against-box test, the leaf triangles tested by their own
 //                   padded bounds, sorted by the depth at which they begin, the first `cap` copied into the beam's list (bounce b >= 2: a list of a pool,
 //                   handed out to the beams that have members)
-//   k_beam_test     one lane per ray in queue order: its beam looked up (the group's key compared), the contract's triangle test (packet_tri_test) over the
+//   k_beam_test     one lane per ray in queue order, or through the beam order (then every wavefront holds ONE beam's rays): its beam looked up (the group's key compared), the contract's triangle test (packet_tri_test) over the
 //                   beam's list in order, until the hit lies before everything not yet tested; lanes that cannot be decided are appended to a leftover queue
 //   k_beam_gather, the lane walk, k_beam_scatter     the leftovers, walked as any other queue, in the halves of the other bounce parity
 //
@@ -110,6 +114,7 @@ __global__ void __launch_bounds__(256) k_beam_clear(BeamArgs g)
     if (i < g.n_beams * MCRT_BEAM_REC) g.red[i] = (i & 8u) ? 0u : 0xffffffffu;
     if (i < g.groups) g.gkey[i] = 0ull;
     if (i < MCRT_BEAM_COUNTERS) g.lcount[i] = 0u;
+    if (g.ordered && i <= g.n_beams) g.ocount[i] = 0u;
     if (i <= MCRT_MAX_BOUNCES) g.l_counts[i] = 0u;
     if (i < MCRT_MAX_BOUNCES * MCRT_XCDS) g.l_cursors[(size_t)i * MCRT_CURSOR_STRIDE] = 0u;
 }
@@ -144,6 +149,74 @@ __global__ void __launch_bounds__(256) k_beam_bounds(FrameArgs a, BeamArgs g)
 #pragma unroll
         for (int k = 0; k < 6; k++) { const uint32_t m = ford(wave_max(mine ? hi[k] : -INFINITY)); if ((int)lane == 8 + k && m > __hip_atomic_load(&w[8 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&w[8 + k], m); }
     }
+}
+
+// ---- the beam order: the bounce's queue positions grouped by beam, so that a wavefront of k_beam_test runs ONE list.  The order decides which
+// lanes sit together and nothing else: k_beam_test proves every ray a member by the same comparisons and tests it against the same list under the same rule ----
+#define BEAM_ST 1024u         // k_beam_scan: threads of its one workgroup
+
+// the members of a (wavefront, beam) get consecutive ranks: they land in the order as one run, and the gathers of st0 / st1 through it come in runs
+__global__ void __launch_bounds__(256) k_beam_rank(FrameArgs a, BeamArgs g)
+{
+    const uint32_t n = a.counts[g.b];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t base = (blockIdx.x * 256u + threadIdx.x) & ~63u;
+    if (base >= n) return;
+    const uint32_t i = base + lane;
+    const bool live = i < n;
+    BeamRay r;
+    const bool ok = beam_ray(a, g, live ? i : 0u, false, r);
+    const int bid = ok && r.bid >= 0 ? r.bid : (int)g.n_beams;      // no beam (not a number, no slot): the pseudo-beam, placed last
+    uint32_t rank = 0;
+    unsigned long long todo = __ballot(live);
+    while (todo) {
+        const int first = __ffsll((long long)todo) - 1;
+        const int cb = __builtin_amdgcn_readlane(bid, first);
+        const bool mine = live && bid == cb;
+        const unsigned long long mm = __ballot(mine);
+        todo &= ~mm;
+        uint32_t at = 0;
+        if ((int)lane == first) at = atomicAdd(&g.ocount[cb], (uint32_t)__popcll(mm));
+        at = (uint32_t)__builtin_amdgcn_readlane((int)at, first);
+        if (mine) rank = at + (uint32_t)__popcll(mm & ((1ull << lane) - 1ull));
+    }
+    if (live) { g.rbeam[i] = (uint32_t)bid; g.rrank[i] = rank; }
+}
+
+// exclusive prefix over the n_beams + 1 segments; the pads are written here (a few thousand segments of at most 63 words: cheaper than clearing the order)
+__global__ void __launch_bounds__(BEAM_ST) k_beam_scan(BeamArgs g)
+{
+    __shared__ uint32_t part[BEAM_ST];
+    __shared__ uint32_t stat[2];
+    const uint32_t t = threadIdx.x, n = g.n_beams + 1u, per = (n + BEAM_ST - 1u) / BEAM_ST;
+    const uint32_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
+    uint32_t sum = 0, placed = 0, segs = 0;
+    for (uint32_t k = lo; k < hi; k++) { const uint32_t c = g.ocount[k]; sum += beam_segment(c); placed += c; segs += c != 0u ? 1u : 0u; }
+    part[t] = sum;
+    if (t < 2u) stat[t] = 0u;
+    __syncthreads();
+    for (uint32_t o = 1u; o < BEAM_ST; o <<= 1) {
+        const uint32_t v = t >= o ? part[t - o] : 0u;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint32_t at = part[t] - sum;
+    for (uint32_t k = lo; k < hi; k++) {
+        const uint32_t c = g.ocount[k], w = beam_segment(c);
+        g.obase[k] = at;
+        for (uint32_t j = c; j < w; j++) g.order[at + j] = MCRT_BEAM_PAD;
+        at += w;
+    }
+    if (placed) { atomicAdd(&stat[0], placed); atomicAdd(&stat[1], segs); }
+    __syncthreads();
+    if (t == 0u) { const uint32_t total = part[BEAM_ST - 1u]; g.lcount[8] = stat[0]; g.lcount[9] = stat[1]; g.lcount[10] = total - stat[0]; g.lcount[12] = total; }
+}
+
+__global__ void __launch_bounds__(256) k_beam_place(FrameArgs a, BeamArgs g)
+{
+    const uint32_t n = a.counts[g.b], i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) g.order[g.obase[g.rbeam[i]] + g.rrank[i]] = i;
 }
 
 // A beam's volume: at depth s = +-(x_dom - xref) >= 0 a member's point lies at s_r = s - (0 .. w) along ITS ray, and its other two coordinates at
@@ -310,16 +383,19 @@ __global__ void __launch_bounds__(BEAM_CT) k_beam_collect(FrameArgs a, BeamArgs 
     }
 }
 
-// pass 0: every ray of the bounce's queue against entries [0, near) of its beam's list; pass 1: the leftovers of pass 0 against the rest
+// pass 0: every ray of the bounce's queue against entries [0, near) of its beam's list -- in queue order, or (g.ordered) through the beam order, whose length
+// k_beam_scan left in lcount[12] and whose pad words are lanes without a ray; pass 1: the leftovers of pass 0 against the rest
 __global__ void __launch_bounds__(256) k_beam_test(FrameArgs a, BeamArgs g, uint32_t pass)
 {
-    const uint32_t n = pass == 0u ? a.counts[g.b] : g.lcount[0];
+    const bool ordered = pass == 0u && g.ordered != 0u;
+    const uint32_t n = pass != 0u ? g.lcount[0] : ordered ? g.lcount[12] : a.counts[g.b];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t base = (blockIdx.x * 256u + threadIdx.x) & ~63u;
     if (base >= n) return;
     const uint32_t j = base + lane;
-    const bool live = j < n;
-    const uint32_t ray = !live ? 0u : pass == 0u ? j : g.lq0[j];
+    bool live = j < n;
+    uint32_t ray = !live ? 0u : ordered ? g.order[j] : pass == 0u ? j : g.lq0[j];
+    if (ordered && ray == MCRT_BEAM_PAD) { live = false; ray = 0u; }
     BeamRay r;
     bool member = beam_ray(a, g, ray, false, r) && live && r.bid >= 0;
     const uint32_t *rec = g.rec + (size_t)(member ? r.bid : 0) * MCRT_BEAM_REC;
@@ -338,11 +414,13 @@ __global__ void __launch_bounds__(256) k_beam_test(FrameArgs a, BeamArgs g, uint
     const float f2d = comp(f2, r.dom), sg = r.neg ? -1.0f : 1.0f;
     bool left = live && !member;
     unsigned long long todo = __ballot(member);
+    uint32_t met = 0;
     const uint32_t first = pass == 0u ? 0u : g.near, cut = pass == 0u ? g.near : 0xffffffffu;
     while (todo) {
         const int cb = __builtin_amdgcn_readlane(r.bid, __ffsll((long long)todo) - 1);
         const bool mine = member && r.bid == cb;
         todo &= ~__ballot(mine);
+        met++;
         const u32x8 R = sload8(g.rec + (size_t)cb * MCRT_BEAM_REC + 8);      // ..., m, xref, s_end, entries, list
         const float m2 = 2.0f * __uint_as_float(R[3]), xref = __uint_as_float(R[4]);
         const uint32_t n_ent = R[6];
@@ -370,6 +448,7 @@ __global__ void __launch_bounds__(256) k_beam_test(FrameArgs a, BeamArgs g, uint
         }
         left = left || (mine && !(reach < limit || limit == INFINITY));
     }
+    if (g.pairs && pass == 0u && met && lane == 0u) atomicAdd(&g.lcount[11], met);
     if (live && best.tri >= 0) keys[ray] = ((unsigned long long)__float_as_uint(best.frac) << 32) | (unsigned long long)(uint32_t)best.tri;
     const unsigned long long lm = __ballot(left);
     if (lm) {
@@ -413,8 +492,15 @@ hipError_t launch_beam(const FrameArgs &a, const BeamArgs &g, hipStream_t st)
     if (setup < g.groups) setup = g.groups;
     hipLaunchKernelGGL(k_beam_clear, dim3((setup + 255u) / 256u), dim3(256), 0, st, g);
     hipLaunchKernelGGL(k_beam_bounds, dim3((blocks + g.stride - 1u) / g.stride), dim3(256), 0, st, a, g);
+    if (g.ordered) {      // (the group table holds its keys)
+        hipLaunchKernelGGL(k_beam_rank, dim3(blocks), dim3(256), 0, st, a, g);
+        hipLaunchKernelGGL(k_beam_scan, dim3(1), dim3(BEAM_ST), 0, st, g);
+        hipLaunchKernelGGL(k_beam_place, dim3(blocks), dim3(256), 0, st, a, g);
+    }
     hipLaunchKernelGGL(k_beam_collect, dim3(g.groups != 0u ? g.groups : g.n_beams), dim3(BEAM_CT), 0, st, a, g);
-    hipLaunchKernelGGL(k_beam_test, dim3(blocks), dim3(256), 0, st, a, g, 0u);
+    // (the order's length is a device word: the worst case is launched, and the wavefronts past the length return at once)
+    const uint32_t blocks0 = g.ordered ? (uint32_t)(((size_t)np + 64u * ((size_t)g.n_beams + 1u) + 255u) / 256u) : blocks;
+    hipLaunchKernelGGL(k_beam_test, dim3(blocks0), dim3(256), 0, st, a, g, 0u);
     const uint32_t which = g.near < g.cap ? 1u : 0u;
     if (which) hipLaunchKernelGGL(k_beam_test, dim3(blocks), dim3(256), 0, st, a, g, 1u);
     const uint32_t few = blocks < 2048u ? blocks : 2048u;

@@ -28,12 +28,15 @@ struct PathBufs {   // sized for `paths` paths of `depth` bounces
 };
 // bounces by beams (mcrt_beam.hip; BeamArgs in mcrt_kernels.h): the beams' reduction words, records and candidate lists, the group table of the bounces >= 2,
 // every bounce's counters, and the counts and cursors the leftovers are walked with.  Sized for `beams` beams, `lists` lists of `cap` candidates and `groups`
-// slots; reused from bounce to bounce (stream order).
+// slots; reused from bounce to bounce (stream order).  The beam order (MCRT_BEAM_ORDER; made only where a bounce is ordered): every ray's beam and rank, the beams'
+// counters and segment bases (beams + 1: the pseudo-beam of the rays without a beam), and the order itself, `order_rays` rays and 64 pad words per segment.
 struct BeamBufs {
     Buf<uint32_t> red, rec, lcount, l_counts, l_cursors;
     Buf<uint4> list;
     Buf<unsigned long long> gkey;
-    uint32_t beams = 0, lists = 0, groups = 0, cap = 0;
+    Buf<uint32_t> rbeam, rrank, ocount, obase, order;
+    uint32_t beams = 0, lists = 0, groups = 0, cap = 0, order_beams = 0;
+    size_t order_rays = 0;
 };
 struct Work {
     Stream stream, side[MCRT_SIDE_STREAMS];   // k_march of bounce b runs on side[b % n] (n: Plan::sides)
@@ -64,6 +67,8 @@ struct Knobs {
     uint32_t beam_deep_from = MCRT_BEAM_DEEP_FROM; // MCRT_BEAM_DEEP_FROM: ... in passes of at least this many paths (MCRT_BEAM_B1=1; 2 takes them in every staged pass, 0 in none)
     uint32_t beam_groups = 0;                  // MCRT_BEAM_GROUPS: slots of the group table (rounded down to a power of two); 0: MCRT_BEAM_GROUPS_PER_LINE per scan-line
     uint32_t beam_cap = MCRT_BEAM_CAP_DEFAULT, beam_near = MCRT_BEAM_NEAR_DEFAULT;   // MCRT_BEAM_CAP, MCRT_BEAM_NEAR: candidates a beam's list holds, and how many of them the first pass tests
+    uint32_t beam_order = MCRT_BEAM_ORDER_DEFAULT;   // MCRT_BEAM_ORDER: a mask of bounces -- bit b: where bounce b runs by beams, k_beam_test reads its rays through a permutation of the queue grouped by beam
+    bool beam_pairs = false;                   // MCRT_BEAM_PAIRS=1: k_beam_test counts the (wavefront, beam) pairs it meets (mcrt_debug_beam_order)
     bool render_row_tile = false;              // MCRT_RENDER_ROW_TILE=1: a wavefront of k_render owns 64 pixels of one picture row in place of an 8 x 8 tile (RenderArgs::row_tile)
     uint32_t speckle_fuse = MCRT_SPECKLE_FUSE_DEFAULT;   // MCRT_SPECKLE_FUSE=2|4: iterations of mcrt_speckle_frames per launch of k_srad; 4 is faster for one frame, 2 for a stack
     bool test_hooks = false;                   // MCRT_TEST_HOOKS: mcrt_debug_set_error may poison the context (tests only)
@@ -186,6 +191,7 @@ struct Instrumentation {
     bool timing_on = false; int timing_level = 0;       // 1: the walk's launches are bracketed by HIP events; 2: k_shade's and k_march's too
     std::vector<TimedLaunch> ev; size_t ev_used = 0;
     uint32_t last_beam_mask = 0;                        // bit b: the last pass ran bounce b by beams (mcrt_debug_beam, mcrt_debug_beam_bounce)
+    uint32_t last_beam_order = 0;                       // ... and read its rays through the beam order (mcrt_debug_beam_order)
     bool last_beam_far = false;                         // ... and its leftovers are those of the second pass over the lists
     float last_lean_bound = 0.0f; uint32_t last_march_rows = 0;   // what the last frame's kernels were given (mcrt_debug_fast_paths)
 };

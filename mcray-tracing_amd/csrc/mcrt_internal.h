@@ -24,11 +24,17 @@
 #define MCRT_BEAM_FROM 2097152u        // bounce 1 by beams (mcrt_beam.hip) in passes of at least this many paths (16 frames of 128 x 1024), where bounce 1 would run as packets: the stage has fixed parts
                                        // (one collection per beam, the bounds, seven launches) -- against packets, ms per frame at 6 / 8 / 12 / 16 / 20 / 128 frames: 0.520 / 0.446 / 0.377 / 0.341 / 0.319 / 0.252
                                        // against 0.511 / 0.441 / 0.370 / 0.341 / 0.320 / 0.272 (profiles/beam/small_pass.txt)
-#define MCRT_BEAM_LAST_DEFAULT 2u       // the last bounce run by beams (mcrt_beam.hip): bounce 2 by the triangle its rays left.  Bounce 3 added to it measured inside the spread of the runs
-                                       // (0.2423 against 0.2442 ms per frame, spread 0.0045), bounce 4 slower: built, tested, off (profiles/beam_deep)
+#define MCRT_BEAM_LAST_DEFAULT 3u       // the last bounce run by beams (mcrt_beam.hip): bounces 2 and 3 by the triangle their rays left.  Bounce 3 pays once its rays are tested in the beam order
+                                       // (MCRT_BEAM_ORDER_DEFAULT): ms per frame of the headline pass, min / median / max of five alternating runs, 0.2427 / 0.2435 / 0.2467 with bounce 2 alone against
+                                       // 0.2250 / 0.2269 / 0.2282 with bounce 3 ordered too; in queue order bounce 3 loses (0.2444 / 0.2458 / 0.2467).  Bounce 4 ordered: 0.2219 / 0.2268 / 0.2334 at 32 slots per
+                                       // scan-line, 0.2146 / 0.2190 / 0.2235 at 64 -- a gain of 0.0079 inside a spread of 0.0089, and slower than bounce 3 in a 48-frame pass: built, tested, off
+                                       // (profiles/beam_order/ab_configs.txt)
 #define MCRT_BEAM_DEEP_FROM 6291456u   // ... in passes of at least this many paths (48 frames of 128 x 1024), the smallest pass measured to gain: ms per frame without / with bounce 2 by beams at
                                        // 20 / 48 / 128 frames 0.3195 / 0.2701 / 0.2512 against 0.3381 / 0.2580 / 0.2432 -- below 4 Mi paths the bounds are taken over the whole queue, and the
                                        // stage's fixed parts weigh against a shorter walk; nothing was measured between 20 and 48 frames
+#define MCRT_BEAM_ORDER_DEFAULT 0x8u    // bounces whose rays k_beam_test reads through the beam order (a mask; only where the bounce runs by beams): bounce 3, which it decides (MCRT_BEAM_LAST_DEFAULT).
+                                       // Bounce 2 ordered gains 0.0028 ms per frame at the median (0.2427 / 0.2435 / 0.2467 -> 0.2382 / 0.2407 / 0.2432), inside the runs' spread of 0.005: off.  Bounce 1 ordered
+                                       // (1.2 beams per wavefront) does not pay for the extra pass over its rays: 0.2286 / 0.2301 / 0.2332 against 0.2250 / 0.2269 / 0.2282 (profiles/beam_order/ab_configs.txt)
 #define MCRT_BEAM_GROUPS_PER_LINE 32u  // slots of the group table per scan-line (rounded up to a power of two in all): the headline pass of 128 x 1024 x 128 paths claims 6 / 20 / 30 slots per
                                        // scan-line at bounces 2 / 3 / 4 (profiles/beam_deep/debug_counters.txt); a group that finds no slot among MCRT_BEAM_PROBES is walked
 #define MCRT_BEAM_LISTS_PER_GROUP 1u   // lists of the pool per slot of the table: nearly every group has one dominant axis and sign

@@ -3,7 +3,7 @@
 // The hot path's kernels, one translation unit per pipeline stage, each kernel beside its launcher:
 //   mcrt_walk.hip    k_trace_lane / k_trace_lane_wide (closest hit, one lane per ray), k_trace_packet (one wavefront per ray packet),
 //                    k_nodes_walk / k_nodes_walk_decode (the walk's 64-byte nodes)
-//   mcrt_beam.hip    k_beam_clear / bounds / collect / test / gather / scatter (bounces 1 .. MCRT_BEAM_LAST of a pass with one probe pose: the rays of a group against one beam's triangles)
+//   mcrt_beam.hip    k_beam_clear / bounds / rank / scan / place / collect / test / gather / scatter (bounces 1 .. MCRT_BEAM_LAST of a pass with one probe pose: the rays of a group against one beam's triangles)
 //   mcrt_shade.hip   k_init (the first ray of every path), k_shade (interface physics of a bounce, survivors compacted into the next queue),
 //                    k_shade_fold (k_shade of bounce 0 with the boundary echoes of a silent start medium added in the kernel)
 //   mcrt_path.hip    k_path (the latency form: every bounce of every path in one launch)
@@ -81,11 +81,17 @@ struct FrameArgs {
 // the triangle the ray left (FrameArgs::from_tri), medium -- of one dominant axis and sign: the group claims a slot of a hash table (gkey), 6 beams per slot.
 // Scratch that is dead between k_shade(b - 1) and k_shade(b) -- the halves of the OTHER parity, bounce b - 1's consumed input -- carries the leftovers: lq0 is
 // that half of the queue, lq1 lies in that half of st2, and their compact state is that half of st0 / st1 with its key words (launch_beam).
+// THE BEAM ORDER (`ordered`): in queue order 64 neighbours hold several beams, whose lists k_beam_test runs one after the other.  k_beam_rank counts every beam's rays
+// (one atomic per wavefront and beam) and gives each ray a rank, k_beam_scan lays the beams' segments out -- each padded to whole wavefronts with MCRT_BEAM_PAD,
+// the rays without a beam in a pseudo-beam behind the last --, k_beam_place writes the permutation, and k_beam_test's first pass takes its rays through it: one
+// beam, one list per wavefront.  Buffers of its own (BeamBufs), made only where a bounce is ordered.
 #define MCRT_BEAM_SLOTS 12u
 #define MCRT_BEAM_REC 16u            // words of a beam's reduction block and of its record
 #define MCRT_BEAM_CAP_MAX 1024u      // the largest list capacity (k_beam_collect sorts in LDS)
 #define MCRT_BEAM_PROBES 4u          // slots of the group table a key is looked for in
-#define MCRT_BEAM_COUNTERS 8u        // counters of one beamed bounce
+#define MCRT_BEAM_COUNTERS 16u       // counters of one beamed bounce (0-7: mcrt_debug_beam_bounce's; 8-12: the beam order's, mcrt_debug_beam_order)
+#define MCRT_BEAM_PAD 0xffffffffu    // a word of the beam order that holds no ray: the padding of a beam's segment to whole wavefronts
+constexpr uint32_t beam_segment(uint32_t count) { return (count + 63u) & ~63u; }   // words of a beam's segment of the order: its rays, rounded up to whole wavefronts (k_beam_scan; mcrt_debug_beam_layout)
 struct BeamArgs {
     uint32_t *red;             // [n_beams][MCRT_BEAM_REC] k_beam_bounds' minima and maxima
     uint32_t *rec;             // [n_beams][MCRT_BEAM_REC] the beams as k_beam_test reads them (k_beam_collect)
@@ -94,11 +100,19 @@ struct BeamArgs {
     uint32_t *lq0, *lq1;       // [np] leftover rays (queue positions) of the near and of the far pass
     uint32_t *lcount;          // [MCRT_BEAM_COUNTERS] of THIS bounce -- 0, 1: leftovers of the two passes; 2: beams whose list is incomplete; 3: beams refused (spread, or no list left);
                                // 4: beams with members; 5: lists handed out; 6: sampled rays whose group found no slot; 7: slots claimed
+                               // 8: rays placed in the beam order; 9: its segments (beams with rays, the pseudo-beam of the rays without one included); 10: its pad lanes;
+                               // 11: (wavefront, beam) pairs k_beam_test's first pass met (only with `pairs`); 12: the order's length, pads included (k_beam_test's n)
     uint32_t *l_counts, *l_cursors;   // the leftover walk's FrameArgs::counts and cursors
     uint32_t b;                // the bounce
     uint32_t groups;           // slots of the group table, a power of two; 0: bounce 1's direct addressing, a beam's list is list[beam]
     uint32_t n_beams, n_lists, cap, near, stride;   // near: entries of a list the first pass tests; stride: every stride-th packet of the queue is sampled for the bounds
     float spread_cap;          // a beam whose slopes spread further is refused
+    uint32_t ordered;          // k_beam_test's first pass reads the bounce's rays through `order`: one beam per wavefront (MCRT_BEAM_ORDER)
+    uint32_t pairs;            // count lcount[11] (MCRT_BEAM_PAIRS: a debug flag, off in every timed path)
+    // the beam order (behind everything k_beam_collect reads: its argument offsets stay)
+    uint32_t *rbeam, *rrank;   // [np] by queue position: the ray's beam (n_beams: none) and its rank among the beam's rays (k_beam_rank)
+    uint32_t *ocount, *obase;  // [n_beams + 1] rays of a beam, and where its segment of the order begins (k_beam_scan); the last is the pseudo-beam of the rays without a beam
+    uint32_t *order;           // [np + 64 (n_beams + 1)] queue positions grouped by beam, every segment padded to a multiple of 64 with MCRT_BEAM_PAD (k_beam_place)
 };
 
 constexpr uint32_t MCRT_ALL_BOUNCES = 0xffffffffu;   // launch_march: accumulate the segments of every bounce in one launch

@@ -223,7 +223,7 @@ static uint32_t beam_wanted(const mcrt_ctx *c, const Plan &P, const mcrt::FrameA
     return mask;
 }
 // what the beamed bounces of a group share: the buffers, sized for the largest of them; beam_args makes bounce b's block of it
-struct BeamPlan { mcrt::BeamArgs g = {}; uint32_t mask = 0, beams_b1 = 0, groups = 0; };
+struct BeamPlan { mcrt::BeamArgs g = {}; uint32_t mask = 0, order = 0, beams_b1 = 0, groups = 0; };
 static int fill_beam(const mcrt_ctx *c, Work &w, const mcrt::FrameArgs &a, uint32_t mask, BeamPlan &bp)
 {
     const uint32_t cap = c->knobs.beam_cap;
@@ -246,7 +246,16 @@ static int fill_beam(const mcrt_ctx *c, Work &w, const mcrt::FrameArgs &a, uint3
         b.beams = beams; b.lists = lists; b.groups = bp.groups; b.cap = cap;
     }
     const size_t np = (size_t)a.ne * a.S;
+    bp.order = mask & c->knobs.beam_order;
+    if (bp.order && (np > b.order_rays || beams > b.order_beams)) {      // the beam order: only where a bounce is ordered
+        HIP_TRY(hipDeviceSynchronize());
+        b.order_rays = 0; b.order_beams = 0;
+        HIP_TRY(b.rbeam.alloc(np)); HIP_TRY(b.rrank.alloc(np)); HIP_TRY(b.ocount.alloc((size_t)beams + 1)); HIP_TRY(b.obase.alloc((size_t)beams + 1));
+        HIP_TRY(b.order.alloc(np + 64 * ((size_t)beams + 1)));
+        b.order_rays = np; b.order_beams = beams;
+    }
     mcrt::BeamArgs &g = bp.g;
+    g.rbeam = b.rbeam; g.rrank = b.rrank; g.ocount = b.ocount; g.obase = b.obase; g.order = b.order; g.pairs = c->knobs.beam_pairs ? 1u : 0u;
     g.red = b.red; g.rec = b.rec; g.list = b.list; g.gkey = b.gkey; g.lcount = b.lcount; g.l_counts = b.l_counts; g.l_cursors = b.l_cursors;
     g.cap = cap; g.near = std::min(c->knobs.beam_near, cap);
     g.stride = np >= MCRT_BEAM_SAMPLE_FROM ? MCRT_BEAM_SAMPLE_STRIDE : 1u;
@@ -262,6 +271,7 @@ static mcrt::BeamArgs beam_args(const BeamPlan &bp, const mcrt::FrameArgs &a, ui
     g.groups = b == 1u ? 0u : bp.groups;
     g.n_beams = b == 1u ? bp.beams_b1 : bp.groups * 6u;
     g.n_lists = b == 1u ? bp.beams_b1 : bp.groups * MCRT_BEAM_LISTS_PER_GROUP;
+    g.ordered = (bp.order >> b) & 1u;
     return g;
 }
 
@@ -370,7 +380,7 @@ static int run_pass(mcrt_ctx *c, uint32_t frame, uint32_t n_frames, uint32_t e0,
         MCRT_TRY(check_overflow(c, P, args[g], *ws[g]));
         if (const uint32_t mask = beam_wanted(c, P, args[g])) { MCRT_TRY(fill_beam(c, *ws[g], args[g], mask, beams[g])); args[g].beam_mask = mask & ~3u; }
     }
-    c->ins.last_beam_mask = beams[0].mask; c->ins.last_beam_far = c->knobs.beam_near < c->knobs.beam_cap;
+    c->ins.last_beam_mask = beams[0].mask; c->ins.last_beam_order = beams[0].order; c->ins.last_beam_far = c->knobs.beam_near < c->knobs.beam_cap;
     return enqueue_pass(c, P, args, beams, ws, accumulate);
 }
 

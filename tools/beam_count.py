@@ -13,7 +13,8 @@ With a bounce b >= 2 the group is the kernels' widened key -- scan-line, the tri
 of one dominant axis and sign.  Also counted then, per bounce: the list entries a ray tests before it is final (its hit's depth plus 2 m lies before the next
 entry's begin; a miss tests the whole list), ray-weighted; the same for the slowest ray of every beam among 64 QUEUE NEIGHBOURS, summed over the wavefront's
 beams (what k_beam_test's loop runs through); and the beams per 64 queue neighbours -- in k_shade's queue order: per 256 rays of the previous queue the
-reflected survivors first, then the refracted ones.  `lines` counts only that many scan-lines, spread evenly (the trace covers all of them).  A sixth argument `beams` adds the list of every beam (`per_beam`:
+reflected survivors first, then the refracted ones; and the same two figures for the BEAM ORDER (one beam per wavefront by construction; a beam's rays cut into
+wavefronts, the slowest ray of each), to set against mcrt_debug_beam_order's counter.  `lines` counts only that many scan-lines, spread evenly (the trace covers all of them).  A sixth argument `beams` adds the list of every beam (`per_beam`:
 thousands of lines at the deeper bounces) to the totals.
 
     python tools/beam_count.py [workload=random1m|liver|sphere] [rays=1024] [scan-lines=128] [bounce=1] [lines=all] [beams]   -> JSON (profiles/beam/beam_count_*.json,
@@ -128,12 +129,22 @@ for w0 in range(0, len(order), 64):
     bs = ray_beam[ids]
     wave_beams.append(len(np.unique(bs)))
     wave_entries.append(int(sum(ray_tested[ids][bs == u].max() for u in np.unique(bs))))
+# ... and per 64 words of the BEAM ORDER (k_beam_rank / k_beam_scan / k_beam_place): a beam's rays in queue order, its segment cut into wavefronts -- one beam each by
+# construction, the last of a segment padded.  (Which run of a segment a wavefront's members take depends on atomic timing on the GPU: queue order stands in for it.)
+ordered_entries, ordered_lanes = [], 0
+counted_ids = order[in_beam[order]]
+for u in np.unique(ray_beam[counted_ids]):
+    ids = counted_ids[ray_beam[counted_ids] == u]
+    for w0 in range(0, len(ids), 64):
+        ordered_entries.append(int(ray_tested[ids[w0:w0 + 64]].max())); ordered_lanes += 64
 spread = [max(b["spread_mrad"]) for b in beams]
 out = {"workload": workload, "scan_lines": E, "rays_per_line": S, "frame": 0, "bounce": BN, "scan_lines_counted": len(counted),
        "beams_per_counted_scan_line": len(beams) / max(len(counted), 1), "rays_per_beam_mean": rays / max(len(beams), 1), "share_of_rays_in_beams_of_fewer_than_16": small / max(rays, 1),
        "entries_tested_per_ray_mean": float(ray_tested[in_beam].mean()) if in_beam.any() else None,
        "wavefronts_counted": len(wave_beams), "beams_per_64_queue_neighbours_mean_max": [float(np.mean(wave_beams)), int(np.max(wave_beams))] if wave_beams else None,
        "entries_per_64_queue_neighbours_summed_over_their_beams_mean": float(np.mean(wave_entries)) if wave_entries else None, "oracle_trace_seconds": round(t_trace, 1),
+       "beam_order_wavefronts": len(ordered_entries), "beam_order_beams_per_wavefront": 1.0 if ordered_entries else None,
+       "beam_order_entries_per_wavefront_mean": float(np.mean(ordered_entries)) if ordered_entries else None, "beam_order_pad_lane_share": 1.0 - int(in_beam.sum()) / max(ordered_lanes, 1),
        "lines_reaching_the_bounce": int(live.any(1).sum()), "lines_with_one_origin": same_origin,
        "rays_of_the_bounce": int(live.sum()), "rays_in_beams": rays, "rays_hitting": hitting, "miss_share": 1.0 - hitting / max(rays, 1),
        "hit_triangles_missing_from_candidates": missing,
