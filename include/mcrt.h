@@ -55,7 +55,8 @@ extern "C" {
                                    (3-D ground truth: a freehand label volume by majority vote, the label of what a rendering shows; additive);
                                    + mcrt_debug_beam (what bounce 1 by beams did in the last pass; additive);
                                    + mcrt_debug_beam_bounce (the same for any bounce run by beams; additive);
-                                   + mcrt_debug_beam_order, mcrt_debug_beam_layout (the beam order of a bounce run by beams, its layout on the host; additive) */
+                                   + mcrt_debug_beam_order, mcrt_debug_beam_layout (the beam order of a bounce run by beams, its layout on the host; additive);
+                                   + mcrt_debug_beam_scan (the kernel that lays a beam order out, run alone on given counters; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -1006,6 +1007,12 @@ int mcrt_debug_beam_order(mcrt_ctx *ctx, uint32_t b, uint32_t out[5]);
  * pseudo-beam's -> bases[n], where each beam's segment begins (an exclusive prefix over the counts rounded up to multiples of 64; an empty beam has no
  * words), out[0] rays placed, out[1] segments, out[2] pad lanes, out[3] the order's length.  MCRT_ERR_LIMIT where the length passes 2^32 - 1. */
 int mcrt_debug_beam_layout(const uint32_t *counts, uint32_t n, uint32_t *bases, uint32_t out[4]);
+/* the same layout by the DEVICE kernel that lays a beam order out, run alone: counts[n] are uploaded as the beams' counters, an order buffer of
+ * mcrt_debug_beam_layout's length (out[3]) and 64 words more is filled with MCRT_DEBUG_BEAM_SENTINEL, the kernel runs, and bases[n], out[4] (as mcrt_debug_beam_layout's) and
+ * the order buffer come back: order_words[out[3] + 64] holds the pad word 0xffffffff in the padding of every segment and the sentinel wherever the kernel wrote
+ * nothing (the rays' own places, and the 64 guard words past the length).  order_words may be null.  n >= 1; MCRT_ERR_LIMIT as mcrt_debug_beam_layout.  Buffers of its own; waits for the device. */
+#define MCRT_DEBUG_BEAM_SENTINEL 0x5eed5eedu
+int mcrt_debug_beam_scan(mcrt_ctx *ctx, const uint32_t *counts, uint32_t n, uint32_t *bases, uint32_t out[4], uint32_t *order_words);
 /* TEST HOOK, refused (MCRT_ERR_INVALID) unless the context was created with MCRT_TEST_HOOKS set in the environment: ORs `bits` into the
  * context's device error word on its stream, as an abandoned launch would (bit 0: traversal stack ran out, bit 1: kernel watchdog
  * expired) -- what mcrt_synchronize reports and what turns finalised RF images into NaN until it is asked */

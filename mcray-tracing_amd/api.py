@@ -133,6 +133,10 @@ def host_psf_elevation(var_z, pitch_um, n_rows, row_mm, focus_mm=(), focal_range
     return out
 
 
+BEAM_PAD = 0xffffffff                 # MCRT_BEAM_PAD: a word of a beam order that holds no ray
+BEAM_SCAN_SENTINEL = 0x5eed5eed       # MCRT_DEBUG_BEAM_SENTINEL: what mcrt_debug_beam_scan fills its order buffer with
+
+
 def host_beam_layout(counts):
     """mcrt_debug_beam_layout: the layout of a beam order (csrc/mcrt_beam.hip, k_beam_scan) for `counts` rays per beam, the last the pseudo-beam's ->
     (bases uint32 [n], rays placed, segments, pad lanes, the order's length)"""
@@ -624,6 +628,17 @@ class Context(_SceneCalls):
         if hasattr(self.L, "mcrt_debug_beam_order"):
             check(self.L.mcrt_debug_beam_order(self.h, int(b), out))
         return (bool(out[0]),) + tuple(int(v) for v in out[1:])
+
+    def debug_beam_scan(self, counts):
+        """mcrt_debug_beam_scan: the kernel that lays a beam order out (csrc/mcrt_beam.hip, k_beam_scan) run alone on `counts` rays per beam, the last the
+        pseudo-beam's -> (bases uint32 [n], rays placed, segments, pad lanes, the order's length, the order buffer uint32 [length + 64]: BEAM_PAD in the padding
+        of every segment, BEAM_SCAN_SENTINEL wherever the kernel wrote nothing -- the rays' places and the 64 guard words past the length)"""
+        counts = np.ascontiguousarray(counts, np.uint32)
+        bases = np.zeros(len(counts), np.uint32)
+        order = np.zeros(host_beam_layout(counts)[4] + 64, np.uint32)
+        out = (C.c_uint32 * 4)()
+        check(self.L.mcrt_debug_beam_scan(self.h, ptr(counts), len(counts), ptr(bases), out, ptr(order)))
+        return bases, int(out[0]), int(out[1]), int(out[2]), int(out[3]), order
 
     def debug_set_error(self, bits):
         """test hook: mark the context as an abandoned launch would (mcrt_debug_set_error)"""

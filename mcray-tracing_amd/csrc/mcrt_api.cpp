@@ -55,6 +55,7 @@ static Knobs read_knobs()
     if (const char *e = tuning_env("MCRT_BEAM_FROM")) { long long v = atoll(e); if (v >= 0 && v <= 0xffffffffll) k.beam_from = (uint32_t)v; }
     if (const char *e = tuning_env("MCRT_BEAM_LAST")) { int v = atoi(e); if (v >= 1 && v < MCRT_MAX_BOUNCES) k.beam_last = (uint32_t)v; }
     if (const char *e = tuning_env("MCRT_BEAM_DEEP_FROM")) { long long v = atoll(e); if (v >= 0 && v <= 0xffffffffll) k.beam_deep_from = (uint32_t)v; }
+    if (const char *e = tuning_env("MCRT_BEAM_B4_FROM")) { long long v = atoll(e); if (v >= 0 && v <= 0xffffffffll) k.beam_b4_from = (uint32_t)v; }
     if (const char *e = tuning_env("MCRT_BEAM_GROUPS")) { long long v = atoll(e); if (v >= 1 && v <= (1 << 20)) k.beam_groups = (uint32_t)v; }
     if (const char *e = tuning_env("MCRT_BEAM_CAP")) { int v = atoi(e); if (v >= 1 && v <= (int)MCRT_BEAM_CAP_MAX) k.beam_cap = (uint32_t)v; }
     if (const char *e = tuning_env("MCRT_BEAM_NEAR")) { int v = atoi(e); if (v >= 1) k.beam_near = (uint32_t)v; }
@@ -623,6 +624,36 @@ extern "C" int mcrt_debug_beam_layout(const uint32_t *counts, uint32_t n, uint32
     }
     if (at > 0xffffffffull) return set_error(MCRT_ERR_LIMIT, "the beam order is longer than 2^32 words");
     out[0] = (uint32_t)placed; out[1] = segments; out[2] = (uint32_t)(at - placed); out[3] = (uint32_t)at;
+    return MCRT_OK;
+}
+
+// k_beam_scan alone (mcrt_beam.hip) on `counts` as the beams' counters, in buffers of its own: the bases, the four totals and the order buffer, which is filled
+// with a sentinel before -- what the kernel wrote there are the pads
+extern "C" int mcrt_debug_beam_scan(mcrt_ctx *c, const uint32_t *counts, uint32_t n, uint32_t *bases, uint32_t out[4], uint32_t *order_words)
+{
+    CTX_TRY(c);
+    if (!counts || !bases || !out) return set_error(MCRT_ERR_INVALID, "null pointer");
+    if (n == 0u) return set_error(MCRT_ERR_INVALID, "a beam order has at least the pseudo-beam's counter");
+    std::vector<uint32_t> host_bases(n);
+    uint32_t lay[4];
+    MCRT_TRY(mcrt_debug_beam_layout(counts, n, host_bases.data(), lay));      // (the length: the order buffer's size, checked against 2^32)
+    const size_t len = lay[3];
+    Buf<uint32_t> ocount, obase, order, lcount;
+    HIP_TRY(ocount.alloc(n)); HIP_TRY(obase.alloc(n)); HIP_TRY(order.alloc(len + 64)); HIP_TRY(lcount.alloc(MCRT_BEAM_COUNTERS));
+    std::vector<uint32_t> fill(len + 64, MCRT_DEBUG_BEAM_SENTINEL);      // (64 guard words past the length)
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(ocount, counts, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(order, fill.data(), (len + 64) * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(obase, 0xff, (size_t)n * 4)); HIP_TRY(hipMemset(lcount, 0, MCRT_BEAM_COUNTERS * 4));
+    mcrt::BeamArgs g = {};
+    g.n_beams = n - 1u; g.ocount = ocount; g.obase = obase; g.order = order; g.lcount = lcount; g.ordered = 1u;
+    HIP_TRY(mcrt::launch_beam_scan(g, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    uint32_t lc[MCRT_BEAM_COUNTERS] = {};
+    HIP_TRY(hipMemcpy(lc, lcount, sizeof lc, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(bases, obase, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (order_words) HIP_TRY(hipMemcpy(order_words, order, (len + 64) * 4, hipMemcpyDeviceToHost));
+    out[0] = lc[8]; out[1] = lc[9]; out[2] = lc[10]; out[3] = lc[12];
     return MCRT_OK;
 }
 

@@ -9,9 +9,9 @@
 //                   Bounce b >= 2: the GROUP (scan-line, the triangle the ray left -- FrameArgs::from_tri, written by k_shade(b - 1) --, medium) claims a slot of
 //                   a hash table with a compare-and-swap on its key word (MCRT_BEAM_PROBES slots are tried); a beam is slot x dominant axis x sign.  A ray whose
 //                   group found no slot, or was not in the sample, is no member of any beam and is walked.
-//   k_beam_rank     (bounces of MCRT_BEAM_ORDER) one lane per ray in queue order: its beam looked up, one atomic per (wavefront, beam) on the beam's counter; every ray
+//   k_beam_rank     (bounces of MCRT_BEAM_ORDER) one lane per ray in queue order: its beam looked up (bounces >= 2: from the word k_shade(b - 1) stored for it, no ray rebuilt), one atomic per (wavefront, beam) on the beam's counter; every ray
 //                   keeps its beam and its rank among the beam's rays.  A ray without a beam is counted into a pseudo-beam behind the last
-//   k_beam_scan     ... one workgroup: where every beam's SEGMENT of the order begins, each rounded up to whole wavefronts; the padding words, the totals
+//   k_beam_scan     ... a workgroup per 256 beams, none waiting for another: where every beam's SEGMENT of the order begins, each rounded up to whole wavefronts; the padding words, the totals
 //   k_beam_place    ... order[base[beam] + rank] = the ray's queue position: a permutation of the queue grouped by beam
 //   k_beam_collect  one workgroup per beam (bounce b >= 2: per slot, its 6 beams in turn): one traversal of the BVH4 with a conservative beam-against-box test, the leaf triangles tested by their own
 //                   padded bounds, sorted by the depth at which they begin, the first `cap` copied into the beam's list (bounce b >= 2: a list of a pool,
@@ -77,18 +77,18 @@ MCRT_DEV bool beam_ray(const FrameArgs &a, const BeamArgs &g, uint32_t i, bool c
     const float4 s0 = a.st0[half + i], s1 = a.st1[half + i];
     const Ray ry = ray_of(mk(s0.x, s0.y, s0.z), mk(s1.x, s1.y, s1.z), s0.w, a);
     r.f2 = ry.f2; r.to = ry.to;
-    const f3 D = ry.to - ry.f2;
-    const float ax = fabsf(D.x), ay = fabsf(D.y), az = fabsf(D.z);
-    r.dom = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
+    const BeamDir bd = beam_dir(ry);      // (the one statement of dominant axis and sign: k_shade stores the same code for k_beam_rank)
+    const f3 D = bd.D;
+    r.dom = bd.dom;
     r.dd = comp(D, r.dom);
     const float ad = fabsf(r.dd);
     r.u = comp(D, (r.dom + 1) % 3) / ad; r.v = comp(D, (r.dom + 2) % 3) / ad;
     r.cmax = fmaxf(fmaxf(fabsf(r.f2.x), fabsf(r.f2.y)), fabsf(r.f2.z));
-    r.neg = r.dd < 0.0f;
+    r.neg = bd.neg;
     // every coordinate a number, the dominant component not 0 (then |u|, |v| <= 1)
     const float sum = fabsf(r.f2.x) + fabsf(r.f2.y) + fabsf(r.f2.z) + fabsf(r.to.x) + fabsf(r.to.y) + fabsf(r.to.z);
     const bool ok = sum < 1e30f && ad > 0.0f && fabsf(r.u) <= 1.0f && fabsf(r.v) <= 1.0f;
-    const uint32_t code = (uint32_t)r.dom * 2u + (r.neg ? 1u : 0u);
+    const uint32_t code = beam_code(bd);
     if (g.groups == 0u) {
         const uint32_t hist = __float_as_int(s1.w) != (int)a.start_mat ? 1u : 0u;
         r.bid = (int)((scan * 2u + hist) * 6u + code);
@@ -153,21 +153,42 @@ __global__ void __launch_bounds__(256) k_beam_bounds(FrameArgs a, BeamArgs g)
 
 // ---- the beam order: the bounce's queue positions grouped by beam, so that a wavefront of k_beam_test runs ONE list.  The order decides which
 // lanes sit together and nothing else: k_beam_test proves every ray a member by the same comparisons and tests it against the same list under the same rule ----
-#define BEAM_ST 1024u         // k_beam_scan: threads of its one workgroup
+#define BEAM_ST 256u          // k_beam_scan: threads of a workgroup, and the counters it owns.  (Four wavefronts, one per SIMD, as a workgroup of k_march: it finds room on a
+                              // compute unit whenever one of those ends.  With 1024 threads the launch ended when k_march on the side stream did: 1495 us, profiles/beam_order_fast)
+
+#define BEAM_RANK_WAYS 128u    // k_beam_rank: pieces of the queue its workgroups interleave (the grid is a multiple of it)
 
 // the members of a (wavefront, beam) get consecutive ranks: they land in the order as one run, and the gathers of st0 / st1 through it come in runs
 __global__ void __launch_bounds__(256) k_beam_rank(FrameArgs a, BeamArgs g)
 {
     const uint32_t n = a.counts[g.b];
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t base = (blockIdx.x * 256u + threadIdx.x) & ~63u;
+    // the workgroups that run at the same time take pieces of the queue that lie far apart (BEAM_RANK_WAYS pieces, launch_beam): neighbours in the queue are rays of
+    // one scan-line, whose wavefronts all add to the same few counters
+    const uint32_t per = gridDim.x / BEAM_RANK_WAYS, blk = (blockIdx.x % BEAM_RANK_WAYS) * per + blockIdx.x / BEAM_RANK_WAYS;
+    const uint32_t base = (blk * 256u + threadIdx.x) & ~63u;
     if (base >= n) return;
     const uint32_t i = base + lane;
     const bool live = i < n;
-    BeamRay r;
-    const bool ok = beam_ray(a, g, live ? i : 0u, false, r);
-    const int bid = ok && r.bid >= 0 ? r.bid : (int)g.n_beams;      // no beam (not a number, no slot): the pseudo-beam, placed last
-    uint32_t rank = 0;
+    int bid = (int)g.n_beams;                                       // no beam (not a number, no slot): the pseudo-beam, placed last
+    if (g.groups == 0u) {                                           // bounce 1: the history is in the state
+        BeamRay r;
+        if (beam_ray(a, g, live ? i : 0u, false, r) && r.bid >= 0) bid = r.bid;
+    } else {
+        // bounces >= 2: the queue word, the word k_shade(b - 1) stored beside it and from_tri are the whole key -- 12 bytes of a ray in place of its 40, no ray
+        // rebuilt.  (A ray beam_ray refuses may get a beam here: k_beam_test refuses it all the same.)
+        const uint32_t at = live ? i : 0u;
+        const uint32_t pid = a.queue[(size_t)(g.b & 1u) * a.ne * a.S + at], word = beam_words(a)[at];
+        const uint32_t line = pid / a.S, scan = line - (line / a.ne_frame) * a.ne_frame;
+        const unsigned long long key = (1ull << 63) | ((unsigned long long)scan << 40) | ((unsigned long long)((word >> 8) & 0xffu) << 32) | (unsigned long long)a.from_tri[pid];
+        const int slot = beam_slot(g, key, false);
+        const uint32_t code = word & 0xffu;
+        if (slot >= 0 && code < 6u) bid = slot * 6 + (int)code;
+    }
+    // the (wavefront, beam) runs first, without memory: every lane learns its run's first lane and its place in the run.  Then the first lanes of ALL runs add to
+    // their beams' counters in ONE instruction -- a round trip per wavefront, not per beam it holds (five at bounce 3 in queue order)
+    uint32_t rank = 0, run = 0;
+    int lead = 0;
     unsigned long long todo = __ballot(live);
     while (todo) {
         const int first = __ffsll((long long)todo) - 1;
@@ -175,42 +196,55 @@ __global__ void __launch_bounds__(256) k_beam_rank(FrameArgs a, BeamArgs g)
         const bool mine = live && bid == cb;
         const unsigned long long mm = __ballot(mine);
         todo &= ~mm;
-        uint32_t at = 0;
-        if ((int)lane == first) at = atomicAdd(&g.ocount[cb], (uint32_t)__popcll(mm));
-        at = (uint32_t)__builtin_amdgcn_readlane((int)at, first);
-        if (mine) rank = at + (uint32_t)__popcll(mm & ((1ull << lane) - 1ull));
+        if (mine) { lead = first; rank = (uint32_t)__popcll(mm & ((1ull << lane) - 1ull)); }
+        if ((int)lane == first) run = (uint32_t)__popcll(mm);
     }
+    uint32_t at = 0;
+    if (live && (int)lane == lead) at = atomicAdd(&g.ocount[bid], run);
+    rank += (uint32_t)__shfl((int)at, lead, 64);
     if (live) { g.rbeam[i] = (uint32_t)bid; g.rrank[i] = rank; }
 }
 
-// exclusive prefix over the n_beams + 1 segments; the pads are written here (a few thousand segments of at most 63 words: cheaper than clearing the order)
+// exclusive prefix over the n_beams + 1 segments; the pads are written here (a few thousand segments of at most 63 words: cheaper than clearing the order).
+// Workgroup w owns the counters [BEAM_ST w, BEAM_ST (w + 1)), one per thread.  It sums the segments of every counter before its own by itself (coalesced loads
+// that hit in L2, one reduction) and so waits for no other workgroup: beside a low-priority k_march nothing says that another workgroup is running.  The last
+// workgroup has then seen every counter and writes the totals.  The layout is mcrt_debug_beam_layout's.
+MCRT_DEV uint32_t wave_sum_u32(uint32_t x) { for (int o = 32; o > 0; o >>= 1) x += (uint32_t)__shfl_xor((int)x, o, 64); return x; }
 __global__ void __launch_bounds__(BEAM_ST) k_beam_scan(BeamArgs g)
 {
-    __shared__ uint32_t part[BEAM_ST];
-    __shared__ uint32_t stat[2];
-    const uint32_t t = threadIdx.x, n = g.n_beams + 1u, per = (n + BEAM_ST - 1u) / BEAM_ST;
-    const uint32_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
-    uint32_t sum = 0, placed = 0, segs = 0;
-    for (uint32_t k = lo; k < hi; k++) { const uint32_t c = g.ocount[k]; sum += beam_segment(c); placed += c; segs += c != 0u ? 1u : 0u; }
-    part[t] = sum;
-    if (t < 2u) stat[t] = 0u;
+    __shared__ uint32_t wsum[3][BEAM_ST / 64u];      // per wavefront: words before (segments), rays, segments with rays
+    __shared__ uint32_t wown[BEAM_ST / 64u];         // per wavefront: words of its own 64 segments
+    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6, n = g.n_beams + 1u, first = blockIdx.x * BEAM_ST;
+    uint32_t before = 0, placed = 0, segs = 0;
+    for (uint32_t k = t; k < first; k += BEAM_ST) { const uint32_t c = g.ocount[k]; before += beam_segment(c); placed += c; segs += c != 0u ? 1u : 0u; }
+    const uint32_t k = first + t;
+    const uint32_t c = k < n ? g.ocount[k] : 0u, w = beam_segment(c);
+    placed += c; segs += c != 0u ? 1u : 0u;
+    // inclusive prefix of the own segments inside the wavefront
+    uint32_t inc = w;
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t v = (uint32_t)__shfl_up((int)inc, o, 64); if ((int)lane >= o) inc += v; }
+    before = wave_sum_u32(before); placed = wave_sum_u32(placed); segs = wave_sum_u32(segs);
+    if (lane == 63u) wown[wv] = inc;
+    if (lane == 0u) { wsum[0][wv] = before; wsum[1][wv] = placed; wsum[2][wv] = segs; }
     __syncthreads();
-    for (uint32_t o = 1u; o < BEAM_ST; o <<= 1) {
-        const uint32_t v = t >= o ? part[t - o] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint32_t at = part[t] - sum;
-    for (uint32_t k = lo; k < hi; k++) {
-        const uint32_t c = g.ocount[k], w = beam_segment(c);
+    uint32_t at = 0, own = 0, all_placed = 0, all_segs = 0;
+    for (uint32_t v = 0; v < BEAM_ST / 64u; v++) { at += wsum[0][v]; all_placed += wsum[1][v]; all_segs += wsum[2][v]; if (v < wv) at += wown[v]; own += wown[v]; }
+    at += inc - w;      // every segment before this workgroup's, before this wavefront's, before this lane's
+    if (k < n) {
         g.obase[k] = at;
         for (uint32_t j = c; j < w; j++) g.order[at + j] = MCRT_BEAM_PAD;
-        at += w;
     }
-    if (placed) { atomicAdd(&stat[0], placed); atomicAdd(&stat[1], segs); }
-    __syncthreads();
-    if (t == 0u) { const uint32_t total = part[BEAM_ST - 1u]; g.lcount[8] = stat[0]; g.lcount[9] = stat[1]; g.lcount[10] = total - stat[0]; g.lcount[12] = total; }
+    if (blockIdx.x == gridDim.x - 1u && t == 0u) {
+        uint32_t len = own;
+        for (uint32_t v = 0; v < BEAM_ST / 64u; v++) len += wsum[0][v];
+        g.lcount[8] = all_placed; g.lcount[9] = all_segs; g.lcount[10] = len - all_placed; g.lcount[12] = len;
+    }
+}
+// k_beam_scan over the n_beams + 1 counters of g (launch_beam; mcrt_debug_beam_scan runs it alone)
+hipError_t launch_beam_scan(const BeamArgs &g, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_beam_scan, dim3((g.n_beams + 1u + BEAM_ST - 1u) / BEAM_ST), dim3(BEAM_ST), 0, st, g);
+    return hipGetLastError();
 }
 
 __global__ void __launch_bounds__(256) k_beam_place(FrameArgs a, BeamArgs g)
@@ -493,8 +527,8 @@ hipError_t launch_beam(const FrameArgs &a, const BeamArgs &g, hipStream_t st)
     hipLaunchKernelGGL(k_beam_clear, dim3((setup + 255u) / 256u), dim3(256), 0, st, g);
     hipLaunchKernelGGL(k_beam_bounds, dim3((blocks + g.stride - 1u) / g.stride), dim3(256), 0, st, a, g);
     if (g.ordered) {      // (the group table holds its keys)
-        hipLaunchKernelGGL(k_beam_rank, dim3(blocks), dim3(256), 0, st, a, g);
-        hipLaunchKernelGGL(k_beam_scan, dim3(1), dim3(BEAM_ST), 0, st, g);
+        hipLaunchKernelGGL(k_beam_rank, dim3((blocks + BEAM_RANK_WAYS - 1u) / BEAM_RANK_WAYS * BEAM_RANK_WAYS), dim3(256), 0, st, a, g);
+        launch_beam_scan(g, st);
         hipLaunchKernelGGL(k_beam_place, dim3(blocks), dim3(256), 0, st, a, g);
     }
     hipLaunchKernelGGL(k_beam_collect, dim3(g.groups != 0u ? g.groups : g.n_beams), dim3(BEAM_CT), 0, st, a, g);

@@ -65,6 +65,7 @@ struct Knobs {
     uint32_t beam_from = MCRT_BEAM_FROM;       // MCRT_BEAM_FROM: ... in passes of at least this many paths (MCRT_BEAM_B1=1)
     uint32_t beam_last = MCRT_BEAM_LAST_DEFAULT;   // MCRT_BEAM_LAST: the last bounce run by beams (1: bounce 1 alone); the bounces 2 .. beam_last of a pass with one probe pose group their rays by the triangle they left
     uint32_t beam_deep_from = MCRT_BEAM_DEEP_FROM; // MCRT_BEAM_DEEP_FROM: ... in passes of at least this many paths (MCRT_BEAM_B1=1; 2 takes them in every staged pass, 0 in none)
+    uint32_t beam_b4_from = MCRT_BEAM_B4_FROM; // MCRT_BEAM_B4_FROM: bounces >= 4 of those only in passes of at least this many paths (a threshold of their own: their tables are fuller and their queues shorter)
     uint32_t beam_groups = 0;                  // MCRT_BEAM_GROUPS: slots of the group table (rounded down to a power of two); 0: MCRT_BEAM_GROUPS_PER_LINE per scan-line
     uint32_t beam_cap = MCRT_BEAM_CAP_DEFAULT, beam_near = MCRT_BEAM_NEAR_DEFAULT;   // MCRT_BEAM_CAP, MCRT_BEAM_NEAR: candidates a beam's list holds, and how many of them the first pass tests
     uint32_t beam_order = MCRT_BEAM_ORDER_DEFAULT;   // MCRT_BEAM_ORDER: a mask of bounces -- bit b: where bounce b runs by beams, k_beam_test reads its rays through a permutation of the queue grouped by beam

@@ -194,6 +194,28 @@ MCRT_DEV Ray ray_of(f3 from, f3 dir, float Ls, const FrameArgs &a)
     return r;
 }
 
+// The direction a beam sorts a ray by (mcrt_beam.hip): D = to - f2 of the ray's segment, its dominant axis and the sign along it; the beam's CODE is
+// 2 * axis + sign, 0 .. 5 whatever D holds.  ONE statement of it: k_shade(b - 1) stores the code of the ray it queues (FrameArgs::beam_word), k_beam_rank(b)
+// sorts by the stored code, k_beam_bounds / k_beam_test rebuild it from the state (beam_ray) -- the same expressions on the same floats, the same bits.
+// (From the segment, not from dir: sx / sy / sz scale the components of `to` differently.)
+struct BeamDir { f3 D; int dom; bool neg; };
+MCRT_DEV BeamDir beam_dir(const Ray &ry)
+{
+    BeamDir r;
+    r.D = ry.to - ry.f2;
+    const float ax = fabsf(r.D.x), ay = fabsf(r.D.y), az = fabsf(r.D.z);
+    r.dom = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
+    r.neg = (r.dom == 0 ? r.D.x : r.dom == 1 ? r.D.y : r.D.z) < 0.0f;
+    return r;
+}
+MCRT_DEV uint32_t beam_code(const BeamDir &d) { return (uint32_t)d.dom * 2u + (d.neg ? 1u : 0u); }
+// the word k_shade stores per queued ray of an ordered bounce: code | (medium & 0xff) << 8 -- with from_tri all of the group key that is not in the path id
+MCRT_DEV uint32_t beam_word_of(f3 from, f3 dir, float Ls, int media, const FrameArgs &a)
+{
+    return beam_code(beam_dir(ray_of(from, dir, Ls, a))) | (((uint32_t)media & 0xffu) << 8);
+}
+MCRT_DEV uint32_t *beam_words(const FrameArgs &a) { return a.from_tri + (size_t)a.ne * a.S; }      // [np] by queue position, behind from_tri's [np] by path
+
 #define MCRT_STATE0_AT(pos, S) ((pos) - (pos) % (S))      /* queue position of the bounce-0 state of the path queued at pos: its scan-line's first sample (k_init) */
 
 // cv::remap(src, dst, map_y, map_x, INTER_LINEAR, BORDER_CONSTANT 0) at one output pixel (rfimage.h:139), exact bilinear: mx = column

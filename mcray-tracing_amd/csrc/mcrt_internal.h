@@ -24,19 +24,23 @@
 #define MCRT_BEAM_FROM 2097152u        // bounce 1 by beams (mcrt_beam.hip) in passes of at least this many paths (16 frames of 128 x 1024), where bounce 1 would run as packets: the stage has fixed parts
                                        // (one collection per beam, the bounds, seven launches) -- against packets, ms per frame at 6 / 8 / 12 / 16 / 20 / 128 frames: 0.520 / 0.446 / 0.377 / 0.341 / 0.319 / 0.252
                                        // against 0.511 / 0.441 / 0.370 / 0.341 / 0.320 / 0.272 (profiles/beam/small_pass.txt)
-#define MCRT_BEAM_LAST_DEFAULT 3u       // the last bounce run by beams (mcrt_beam.hip): bounces 2 and 3 by the triangle their rays left.  Bounce 3 pays once its rays are tested in the beam order
-                                       // (MCRT_BEAM_ORDER_DEFAULT): ms per frame of the headline pass, min / median / max of five alternating runs, 0.2427 / 0.2435 / 0.2467 with bounce 2 alone against
-                                       // 0.2250 / 0.2269 / 0.2282 with bounce 3 ordered too; in queue order bounce 3 loses (0.2444 / 0.2458 / 0.2467).  Bounce 4 ordered: 0.2219 / 0.2268 / 0.2334 at 32 slots per
-                                       // scan-line, 0.2146 / 0.2190 / 0.2235 at 64 -- a gain of 0.0079 inside a spread of 0.0089, and slower than bounce 3 in a 48-frame pass: built, tested, off
-                                       // (profiles/beam_order/ab_configs.txt)
-#define MCRT_BEAM_DEEP_FROM 6291456u   // ... in passes of at least this many paths (48 frames of 128 x 1024), the smallest pass measured to gain: ms per frame without / with bounce 2 by beams at
-                                       // 20 / 48 / 128 frames 0.3195 / 0.2701 / 0.2512 against 0.3381 / 0.2580 / 0.2432 -- below 4 Mi paths the bounds are taken over the whole queue, and the
-                                       // stage's fixed parts weigh against a shorter walk; nothing was measured between 20 and 48 frames
-#define MCRT_BEAM_ORDER_DEFAULT 0x8u    // bounces whose rays k_beam_test reads through the beam order (a mask; only where the bounce runs by beams): bounce 3, which it decides (MCRT_BEAM_LAST_DEFAULT).
-                                       // Bounce 2 ordered gains 0.0028 ms per frame at the median (0.2427 / 0.2435 / 0.2467 -> 0.2382 / 0.2407 / 0.2432), inside the runs' spread of 0.005: off.  Bounce 1 ordered
-                                       // (1.2 beams per wavefront) does not pay for the extra pass over its rays: 0.2286 / 0.2301 / 0.2332 against 0.2250 / 0.2269 / 0.2282 (profiles/beam_order/ab_configs.txt)
-#define MCRT_BEAM_GROUPS_PER_LINE 32u  // slots of the group table per scan-line (rounded up to a power of two in all): the headline pass of 128 x 1024 x 128 paths claims 6 / 20 / 30 slots per
-                                       // scan-line at bounces 2 / 3 / 4 (profiles/beam_deep/debug_counters.txt); a group that finds no slot among MCRT_BEAM_PROBES is walked
+#define MCRT_BEAM_LAST_DEFAULT 4u       // the last bounce run by beams (mcrt_beam.hip): bounces 2 .. 4 by the triangle their rays left, tested in the beam order (MCRT_BEAM_ORDER_DEFAULT).  ms per frame of the
+                                       // headline pass, min / median / max of seven alternating runs on one box (profiles/beam_order_fast/ab_configs.txt): bounces 2-3 ordered 0.2216 / 0.2245 / 0.2261,
+                                       // bounces 2-4 ordered at 64 slots per scan-line 0.2103 / 0.2127 / 0.2157 -- 0.0118 lower, spreads <= 0.0054, every run below.  With bounce 2 in queue order
+                                       // (MCRT_BEAM_ORDER=0x18) 0.2134 / 0.2179 / 0.2230.  (Before the order was cheap bounce 4 gained 0.0079 inside a spread of 0.0089: DESIGN.md A.12, A.13)
+#define MCRT_BEAM_DEEP_FROM 4194304u   // ... in passes of at least this many paths (32 frames of 128 x 1024): ms per frame without bounces >= 2 by beams / with bounces 2-3 ordered, seven alternating runs,
+                                       // at 32 frames 0.2808 / 0.2822 / 0.2831 against 0.2675 / 0.2693 / 0.2726 (0.0129 lower, spreads <= 0.0052, every run below); at 48 frames 0.2681 against 0.2478 at the
+                                       // median.  A 20-frame pass lost 4-14 % with the dearer order (profiles/beam_order); nothing was measured between 20 and 32 frames
+#define MCRT_BEAM_B4_FROM 16777216u    // bounces >= 4 by beams only in passes of at least this many paths (128 frames of 128 x 1024), a threshold of their own: bounces 2-3 / 2-4 ordered, 64 slots, seven
+                                       // alternating runs, median ms per frame at 48 / 64 / 96 / 128 frames 0.2488 / 0.2399 / 0.2267 / 0.2227 against 0.2472 / 0.2331 / 0.2212 / 0.2127.  At 64 and 96 frames
+                                       // every run with bounce 4 is below every run without, but the gains (0.0068, 0.0055) are not beyond the larger spread (0.0170, 0.0058): by the rule only 128 passes
+#define MCRT_BEAM_ORDER_DEFAULT 0x1cu   // bounces whose rays k_beam_test reads through the beam order (a mask; only where the bounce runs by beams): bounces 2, 3 and 4.  Bounce 2 ordered, seven alternating
+                                       // runs: 0.2276 / 0.2302 / 0.2316 -> 0.2216 / 0.2245 / 0.2261 (0.0057 lower, spreads <= 0.0044, every run below) since k_beam_rank reads k_shade's beam word and
+                                       // k_beam_scan runs in workgroups of 256 (rank + scan + place 1111 -> 463 us at bounce 3).  Bounce 1 ordered (1.2 beams per wavefront) did not pay for the extra pass
+                                       // over its rays: 0.2286 / 0.2301 / 0.2332 against 0.2250 / 0.2269 / 0.2282 (profiles/beam_order/ab_configs.txt; not measured again)
+#define MCRT_BEAM_GROUPS_PER_LINE 64u  // slots of the group table per scan-line (rounded up to a power of two in all): the headline pass of 128 x 1024 x 128 paths claims 6 / 20 / 30 slots per
+                                       // scan-line at bounces 2 / 3 / 4 with 32 (profiles/beam_deep/debug_counters.txt), and bounce 4's table was full.  64 cost bounces 2-3 nothing: 0.2216 / 0.2245 / 0.2261
+                                       // at 32 against 0.2221 / 0.2227 / 0.2269 (profiles/beam_order_fast/ab_configs.txt); a group that finds no slot among MCRT_BEAM_PROBES is walked
 #define MCRT_BEAM_LISTS_PER_GROUP 1u   // lists of the pool per slot of the table: nearly every group has one dominant axis and sign
 #define MCRT_BEAM_CAP_DEFAULT 512u     // candidates a beam's list holds (bounce 1 by beams, mcrt_beam.hip), at most MCRT_BEAM_CAP_MAX
 #define MCRT_BEAM_NEAR_DEFAULT 512u    // ... of which the first pass over all rays tests this many; fewer than the capacity: what is undecided then goes on as a compact queue through a second pass

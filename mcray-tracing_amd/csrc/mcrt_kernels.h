@@ -51,7 +51,9 @@ struct FrameArgs {
                                //         (the walk reads st0 + st1 and rebuilds the ray from them: ray_of)
     uint32_t *queue;           // [2][np] live path ids of bounce b in buffer b & 1
     unsigned long long *key0, *key1;   // [np] closest hit per ray: fraction bits << 32 | triangle id (atomicMin), ping-pong by bounce parity
-    uint32_t *from_tri;        // [np] by path: the triangle its ray of the next bounce leaves; k_shade(b) writes it only where bounce b + 1 runs by beams (beam_mask)
+    uint32_t *from_tri;        // [np] by path: the triangle its ray of the next bounce leaves; k_shade(b) writes it only where bounce b + 1 runs by beams (beam_mask).
+                               // Behind it [np] by QUEUE POSITION of the next bounce: the queued ray's beam word (beam_words, beam_word_of), written only where bounce
+                               // b + 1 is ordered (order_mask); k_beam_rank(b + 1) has read it before k_shade(b + 1) writes the next (stream order)
     const uint32_t *tri_slot;  // [T] triangle id -> position in the leaf-order triangle array
     uint32_t *counts;          // [MAX_BOUNCES+1] live rays per bounce
     uint32_t *cursors;         // [MAX_BOUNCES][MCRT_XCDS][MCRT_CURSOR_STRIDE] queue cursors of the persistent walk, one per XCD sub-queue
@@ -74,7 +76,10 @@ struct FrameArgs {
     uint32_t retire_late;      // shade_path ends a path whose next segment would start past max_travel and past the image (off for counting and debug passes)
     uint32_t beam_mask;        // bit b >= 2: bounce b runs by beams (mcrt_beam.hip), so k_shade(b - 1) writes from_tri
     uint32_t fold_b0;          // staged pass in a silent start medium: k_shade(b = 0) adds bounce 0's boundary echoes itself, writes no march record, no k_march(0)
+    uint32_t order_mask;       // bit b >= 2: bounce b is tested in the beam order (mcrt_beam.hip), so k_shade(b - 1) writes the ray's beam word (beam_words).  (In the
+                               // struct's tail padding: its size, and with it the offset of every kernel argument behind a FrameArgs, stays)
 };
+static_assert(sizeof(FrameArgs) % 8 == 0 && offsetof(FrameArgs, order_mask) + 4 == sizeof(FrameArgs), "order_mask fills FrameArgs' tail padding");
 
 // k_beam_* (mcrt_beam.hip): a bounce by beams.  A beam of BOUNCE 1 is a scan-line's rays of one history (reflected or refracted at bounce 0), one dominant axis
 // and one sign along it: MCRT_BEAM_SLOTS per scan-line, addressed directly, most of them empty.  A beam of a bounce b >= 2 is the rays of one GROUP -- scan-line,
@@ -266,6 +271,7 @@ struct RenderLabelArgs {
 
 hipError_t launch_init(const FrameArgs &a, hipStream_t st);
 hipError_t launch_trace(const FrameArgs &a, uint32_t b, bool stats, hipStream_t st);
+hipError_t launch_beam_scan(const BeamArgs &g, hipStream_t st);                   // k_beam_scan alone over g.ocount[0 .. g.n_beams]: obase, the pads of g.order, lcount[8, 9, 10, 12] (launch_beam; mcrt_debug_beam_scan)
 hipError_t launch_beam(const FrameArgs &a, const BeamArgs &g, hipStream_t st);   // bounce g.b's closest hits by beams, in place of launch_trace(a, g.b): the same key words
 hipError_t launch_nodes_walk(const float4 *nodes, uint32_t n_nodes, uint4 *out, hipStream_t st);
 hipError_t launch_nodes_walk_decode(const uint4 *walk, uint32_t n_nodes, float4 *out, hipStream_t st);

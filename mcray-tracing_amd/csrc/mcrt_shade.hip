@@ -159,8 +159,12 @@ MCRT_DEV void shade_bounce(const FrameArgs &a, uint32_t b)
             q_out[pos] = pid;
             ((b & 1u) ? a.key0 : a.key1)[pos] = MCRT_KEY_MISS;            // the next bounce's closest-hit word of this ray
             const size_t so = (size_t)((b + 1u) & 1u) * a.ne * a.S + pos;
-            a.st0[so] = make_float4(from.x, from.y, from.z, ray_len(intensity, tb.mat(2 * media).y, a));   // origin | the next ray's length factor
+            const float Ls = ray_len(intensity, tb.mat(2 * media).y, a);
+            a.st0[so] = make_float4(from.x, from.y, from.z, Ls);   // origin | the next ray's length factor
             a.st1[so] = make_float4(dir.x, dir.y, dir.z, __int_as_float(media));
+            // the next ray's beam code and medium for k_beam_rank (mcrt_beam.hip), which then reads 4 bytes of this ray in place of its state -- only where that
+            // bounce is tested in the beam order: the branch is wave-uniform
+            if ((a.order_mask >> (b + 1u)) & 1u) beam_words(a)[pos] = beam_word_of(from, dir, Ls, media, a);
             a.st2[so] = make_float4(__int_as_float(__double2loint(dist_mm)), __int_as_float(__double2hiint(dist_mm)), __int_as_float(outside), intensity);
         }
     }

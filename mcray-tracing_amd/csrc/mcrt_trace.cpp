@@ -135,7 +135,7 @@ static int ensure_work(Work &w, size_t np, uint32_t B, size_t ovf, int out)
     w.b = PathBufs();                   // (the optional tables survive a re-allocation of the rest when they are large enough)
     PathBufs &b = w.b;
     HIP_TRY(b.st0.alloc(2 * np)); HIP_TRY(b.st1.alloc(2 * np)); HIP_TRY(b.st2.alloc(2 * np));   // two halves: bounce parity
-    HIP_TRY(b.key0.alloc(np)); HIP_TRY(b.key1.alloc(np)); HIP_TRY(b.from_tri.alloc(np));
+    HIP_TRY(b.key0.alloc(np)); HIP_TRY(b.key1.alloc(np)); HIP_TRY(b.from_tri.alloc(2 * np));   // (from_tri: by path, and behind it the beam words by queue position)
     HIP_TRY(b.q.alloc(2 * np)); HIP_TRY(b.seg_count.alloc(np));
     HIP_TRY(b.counts.alloc(MCRT_MAX_BOUNCES + 1));
     HIP_TRY(b.cursors.alloc((size_t)MCRT_MAX_BOUNCES * MCRT_XCDS * MCRT_CURSOR_STRIDE));
@@ -209,7 +209,7 @@ static void fill_group(const mcrt_ctx *c, const Work &w, mcrt::FrameArgs &a, uin
 
 // Bounces by beams (mcrt_beam.hip), as a mask of bounces.  Bounce 1: where it runs as packets today and the pass has ONE probe pose -- every bounce-1 ray of a
 // scan-line then starts at the same point in every frame.  Bounces 2 .. MCRT_BEAM_LAST: in passes of at least MCRT_BEAM_DEEP_FROM paths with one pose (their rays
-// are grouped by the triangle they left, the same in every frame).  Not in the latency form, a counting pass or a pass with per-frame poses; MCRT_BEAM_B1=2 takes
+// are grouped by the triangle they left, the same in every frame), bounces >= 4 of them in passes of at least MCRT_BEAM_B4_FROM.  Not in the latency form, a counting pass or a pass with per-frame poses; MCRT_BEAM_B1=2 takes
 // all of them in every other pass, 0 none.
 static uint32_t beam_wanted(const mcrt_ctx *c, const Plan &P, const mcrt::FrameArgs &a)
 {
@@ -219,7 +219,8 @@ static uint32_t beam_wanted(const mcrt_ctx *c, const Plan &P, const mcrt::FrameA
     uint32_t mask = 0;
     if (force || ((a.packet_mask & 2u) != 0u && np >= c->knobs.beam_from)) mask |= 2u;
     if (force || np >= c->knobs.beam_deep_from)
-        for (uint32_t b = 2; b <= c->knobs.beam_last && b < a.B; b++) mask |= 1u << b;
+        for (uint32_t b = 2; b <= c->knobs.beam_last && b < a.B; b++)
+            if (force || b < 4u || np >= c->knobs.beam_b4_from) mask |= 1u << b;
     return mask;
 }
 // what the beamed bounces of a group share: the buffers, sized for the largest of them; beam_args makes bounce b's block of it
@@ -378,7 +379,7 @@ static int run_pass(mcrt_ctx *c, uint32_t frame, uint32_t n_frames, uint32_t e0,
         args[g] = pass;
         fill_group(c, *ws[g], args[g], n_frames, P.e[g], P.e[g + 1], e0, out);
         MCRT_TRY(check_overflow(c, P, args[g], *ws[g]));
-        if (const uint32_t mask = beam_wanted(c, P, args[g])) { MCRT_TRY(fill_beam(c, *ws[g], args[g], mask, beams[g])); args[g].beam_mask = mask & ~3u; }
+        if (const uint32_t mask = beam_wanted(c, P, args[g])) { MCRT_TRY(fill_beam(c, *ws[g], args[g], mask, beams[g])); args[g].beam_mask = mask & ~3u; args[g].order_mask = beams[g].order & ~3u; }
     }
     c->ins.last_beam_mask = beams[0].mask; c->ins.last_beam_order = beams[0].order; c->ins.last_beam_far = c->knobs.beam_near < c->knobs.beam_cap;
     return enqueue_pass(c, P, args, beams, ws, accumulate);
