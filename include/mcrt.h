@@ -56,7 +56,9 @@ extern "C" {
                                    + mcrt_debug_beam (what bounce 1 by beams did in the last pass; additive);
                                    + mcrt_debug_beam_bounce (the same for any bounce run by beams; additive);
                                    + mcrt_debug_beam_order, mcrt_debug_beam_layout (the beam order of a bounce run by beams, its layout on the host; additive);
-                                   + mcrt_debug_beam_scan (the kernel that lays a beam order out, run alone on given counters; additive) */
+                                   + mcrt_debug_beam_scan (the kernel that lays a beam order out, run alone on given counters; additive);
+                                   + mcrt_noise_opts, mcrt_default_noise_opts, mcrt_noise_draws, mcrt_noise_frames (receiver noise: a Gaussian noise floor
+                                   from integer Philox sums and a gain per transducer element, over the RF stack in place; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -678,6 +680,57 @@ int mcrt_speckle_tables(const mcrt_speckle_opts *o, float *q0sq /* [n_iter] */, 
  * launched and out_dev is untouched.  Groups: call it on mcrt_group_root(). */
 int mcrt_speckle_frames(mcrt_ctx *ctx, const float *in_dev, uint32_t n_frames, uint32_t height, uint32_t width,
                         const mcrt_speckle_opts *o /* NULL = defaults */, float *out_dev);
+
+/* ---- receiver noise: the noise floor of the receive chain and the gain of every transducer element.  The reference has neither: its RF
+ * images hold echoes and exact zeros, so no gain finds a penetration depth and no element is weak or dead.  The stage works on the RF stack
+ * [n_frames][n_images][E][R] that a traced pass left on the device (n_images: the N views of a compounded frame, the K planes of a sweep, or 1),
+ * in place.  It sits after the lateral PSF and before the envelope: receive noise is uncorrelated between scan-lines.  That is a modelling
+ * choice that no measurement backs.
+ *
+ * The draw; integers only.  Image j = f * n_images + i of the stack has the id first_image_id + j.  For scan-line e and row r of it:
+ *   o[0..3] = philox4x32_10(ctr = (e, r, 0x4E4F4953, 0), key = (seed, id))
+ *   S = the sum of the eight 16-bit halves of o[0..3],   d = S - 262140
+ * an Irwin-Hall sum of 8: the mean is exactly 0, the variance exactly 2863311530 = 8 * (65536^2 - 1) / 12, and |d| <= 262140, which is 4.9
+ * standard deviations (excess kurtosis -0.15).  The counter's third word is no bounce number (max_depth <= 16), so a noise stream cannot
+ * coincide with a tracer stream even under equal key words.  mcrt_noise_draws returns exactly these d, on the host.
+ * The rule, per frame f; everything in float, every operation rounded once, no fma:
+ *   a(v)    = |v| where v is finite, else 0                          (step 1 of mcrt_bmode_frames without TGC)
+ *   peak_f  = the largest a over the frame's n_images * E * R INPUT values (exact, independent of the order, taken before the gain)
+ *   sigma_f = sigma (MCRT_NOISE_ABS), or peak_f * c with c = (float)pow(10.0, -(double)snr_db / 20.0) made on the host (MCRT_NOISE_SNR_DB)
+ *   k_f     = sigma_f * inv_std,   inv_std = (float)(1.0 / sqrt(2863311530.0))
+ *   u       = element_gain ? v * element_gain[e] : v
+ *   out     = (k_f == 0.0f) ? u : u + (float)d * k_f
+ * What follows: a NaN or an infinity stays what it is; a frame of zeros in SNR_DB mode only gets its gain; ABS with sigma == 0 and no gain
+ * launches nothing (sigma_dev, when given, is cleared) and the stack keeps its bits, a -0.0 included; the views or planes of one frame share one receiver, hence one peak (the
+ * joint reference of mcrt_bmode_compound_frames).  sigma_dev[f], when given, receives sigma_f.
+ * The ids (applied by the wrappers: Simulator(noise=...), rf_image::add_noise, mattausch_hip --noise-db / --noise-sigma): first_image_id is
+ * the frame id the stack's first image was traced with, by the frame-id rules above ((f0 + f) * N + n, (f0 + f) * K + k) -- a frame carries
+ * the same noise traced alone or inside a pass. */
+enum { MCRT_NOISE_SNR_DB = 0,   /* sigma_f = the frame's own peak * 10^(-snr_db/20) */
+       MCRT_NOISE_ABS    = 1 }; /* sigma_f = sigma */
+typedef struct { uint32_t mode;     /* MCRT_NOISE_*                                   (SNR_DB)     */
+                 float    snr_db;   /* SNR_DB: finite                                 (50)         */
+                 float    sigma;    /* ABS: finite, >= 0                              (0)          */
+                 uint32_t seed;     /* Philox key word 0 of the noise streams         (0x4E4F4953) */
+} mcrt_noise_opts;                  /* 16 bytes: mode 0, snr_db 4, sigma 8, seed 12 */
+/* the defaults above; host only.  MCRT_ERR_INVALID for a null o */
+int mcrt_default_noise_opts(mcrt_noise_opts *o);                                              /* host only */
+/* the draws d of one image; host only.  MCRT_ERR_INVALID: a null d, a zero n_elements or n_rows;  MCRT_ERR_LIMIT: n_rows > 2048.  On an error
+ * nothing is written */
+int mcrt_noise_draws(uint32_t seed, uint32_t image_id, uint32_t n_elements, uint32_t n_rows,
+                     int32_t *d /* [E][R] */);                                                /* host only */
+/* The rule above over the stack, in place.  Asynchronous on the context's stream: in SNR_DB mode a clear of the context's peaks and one
+ * launch of k_bmode_peak (each frame's n_images * E scan-lines as one image), then one launch of k_noise.  element_gain is a HOST table [E],
+ * free the moment the call returns; it lives on the device in a buffer of the context's and is copied only when it differs from what is
+ * there (as tgc_db is).  Nothing is allocated after the first call at a size.
+ * MCRT_ERR_INVALID: null ctx or rf_dev, a zero n_frames, n_images, n_elements or n_rows, an unknown mode, snr_db not finite (SNR_DB),
+ * sigma negative or not finite (ABS), an element_gain entry that is not finite;  MCRT_ERR_LIMIT: n_rows > 2048, n_frames * n_images >
+ * 65535, first_image_id + n_frames * n_images > 2^32, a stack of 2^31 samples or more.  On an error nothing is launched and rf_dev and
+ * sigma_dev are untouched.  Groups: call it on mcrt_group_root(). */
+int mcrt_noise_frames(mcrt_ctx *ctx, float *rf_dev /* [n_frames][n_images][E][R], in place */, uint32_t n_frames,
+                      uint32_t n_images, uint32_t n_elements, uint32_t n_rows, uint32_t first_image_id,
+                      const mcrt_noise_opts *o /* NULL = defaults */, const float *element_gain /* host [E] or NULL */,
+                      float *sigma_dev /* [n_frames] or NULL */);
 
 /* ---- freehand 3-D reconstruction: a tracked 2-D probe moved by hand over the patient, its frames binned into voxels from their poses --
  * pixel-nearest-neighbour binning with hole filling (Rohling, Gee, Berman: "A comparison of freehand three-dimensional ultrasound

@@ -111,13 +111,18 @@ class ReconLabelOpts(C.Structure):
     _fields_ = [("n_labels", C.c_uint32), ("fill_radius", C.c_uint32), ("fill_min", C.c_uint32)]
 
 
+class NoiseOpts(C.Structure):
+    """mcrt_noise_opts (include/mcrt.h): 16 bytes"""
+    _fields_ = [("mode", C.c_uint32), ("snr_db", C.c_float), ("sigma", C.c_float), ("seed", C.c_uint32)]
+
+
 NODE_DTYPE = np.dtype([("lo0", "<f4", 3), ("c0", "<i4"), ("hi0", "<f4", 3), ("c1", "<i4"),
                        ("lo1", "<f4", 3), ("pad0", "<u4"), ("hi1", "<f4", 3), ("pad1", "<u4")])
 SEGMENT_DTYPE = np.dtype([("from", "<f4", 3), ("to", "<f4", 3), ("dir", "<f4", 3),
                           ("reflected_intensity", "<f4"), ("initial_intensity", "<f4"), ("attenuation", "<f4"),
                           ("distance_traveled", "<f8"), ("media", "<i4"), ("tri", "<i4")])
 assert NODE_DTYPE.itemsize == 64 and SEGMENT_DTYPE.itemsize == 64 and C.sizeof(BvhNode) == 64 and C.sizeof(BmodeParams) == 48 and C.sizeof(Focus) == 40 and C.sizeof(Compound) == 68 and C.sizeof(CompoundOpts) == 72
-assert C.sizeof(Sweep) == 12 and C.sizeof(VolumeGrid) == 112 and C.sizeof(LabelOpts) == 8 and C.sizeof(RenderView) == 64 and C.sizeof(RenderOpts) == 32 and C.sizeof(SpeckleOpts) == 16 and C.sizeof(ReconOpts) == 20
+assert C.sizeof(Sweep) == 12 and C.sizeof(VolumeGrid) == 112 and C.sizeof(LabelOpts) == 8 and C.sizeof(RenderView) == 64 and C.sizeof(RenderOpts) == 32 and C.sizeof(SpeckleOpts) == 16 and C.sizeof(NoiseOpts) == 16 and C.sizeof(ReconOpts) == 20
 assert C.sizeof(ReconLabelOpts) == 12
 
 # every symbol include/mcrt.h declares (tests/test_abi.py checks the .so exports each one)
@@ -137,6 +142,7 @@ SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create"
            "mcrt_default_label_opts", "mcrt_label_frames", "mcrt_label_scan_convert_frames", "mcrt_label_volume_frames",
            "mcrt_default_render_opts", "mcrt_render_view_for_grid", "mcrt_render_frames",
            "mcrt_default_speckle_opts", "mcrt_speckle_tables", "mcrt_speckle_frames",
+           "mcrt_default_noise_opts", "mcrt_noise_draws", "mcrt_noise_frames",
            "mcrt_default_recon_opts", "mcrt_recon_transform", "mcrt_recon_frames",
            "mcrt_default_recon_label_opts", "mcrt_recon_label_frames", "mcrt_render_label_frames"]
 
@@ -210,6 +216,9 @@ def load_library():
         "mcrt_default_speckle_opts": [C.POINTER(SpeckleOpts)],
         "mcrt_speckle_tables": [C.POINTER(SpeckleOpts), vp, vp, vp],
         "mcrt_speckle_frames": [vp, vp, u32, u32, u32, C.POINTER(SpeckleOpts), vp],
+        "mcrt_default_noise_opts": [C.POINTER(NoiseOpts)],
+        "mcrt_noise_draws": [u32, u32, u32, u32, vp],
+        "mcrt_noise_frames": [vp, vp, u32, u32, u32, u32, u32, C.POINTER(NoiseOpts), vp, vp],
         "mcrt_default_recon_opts": [C.POINTER(ReconOpts)],
         "mcrt_recon_transform": [C.POINTER(VolumeGrid), C.c_double, vp, vp],
         "mcrt_recon_frames": [vp, vp, u32, u32, u32, vp, vp, C.c_double, C.c_double, C.POINTER(VolumeGrid), C.POINTER(ReconOpts), vp, vp, vp],

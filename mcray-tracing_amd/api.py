@@ -11,7 +11,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, RenderView, RenderOpts, SpeckleOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, RenderView, RenderOpts, SpeckleOpts, NoiseOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 DEFAULT_ANGLE = 1.0471975511965976      # the sector of main.cpp:28: 60 degrees [rad]
 
@@ -370,6 +370,32 @@ def _depth_mm_f(depth_cm, speed_of_sound):
     (float)(unsigned)(max_travel_us * speed_of_sound) * 0.001f with max_travel_us = (unsigned)(depth_cm / speed_of_sound * 10000)"""
     travel = int((depth_cm / float(speed_of_sound)) * 10000.0)
     return float(np.float32(np.float32((travel * int(speed_of_sound)) & 0xffffffff) * np.float32(0.001)))
+
+
+NOISE_SNR_DB, NOISE_ABS = 0, 1      # MCRT_NOISE_*
+
+
+def noise_opts_struct(snr_db=None, sigma=None, seed=None):
+    """mcrt_noise_opts from keywords over mcrt_default_noise_opts: snr_db (the noise floor below each frame's own peak, MCRT_NOISE_SNR_DB) or
+    sigma (an absolute standard deviation: giving it selects MCRT_NOISE_ABS), and the seed of the noise streams.  Both at once: ValueError"""
+    if snr_db is not None and sigma is not None:
+        raise ValueError("noise takes snr_db or sigma, not both")
+    o = NoiseOpts()
+    check(load_library().mcrt_default_noise_opts(C.byref(o)))
+    if snr_db is not None:
+        o.snr_db = float(snr_db)
+    if sigma is not None:
+        o.mode, o.sigma = NOISE_ABS, float(sigma)
+    if seed is not None:
+        o.seed = int(seed) & 0xFFFFFFFF
+    return o
+
+
+def host_noise_draws(seed, image_id, n_elements, n_rows):
+    """mcrt_noise_draws: the integer draws d of one image, int32 [n_elements][n_rows] (noise = d * sigma_f / sqrt(2863311530))"""
+    d = np.zeros((max(int(n_elements), 0), max(int(n_rows), 0)), np.int32)
+    check(load_library().mcrt_noise_draws(int(seed) & 0xFFFFFFFF, int(image_id) & 0xFFFFFFFF, n_elements, n_rows, ptr(d)))
+    return d
 
 
 LABEL_RULES = {"traced": 0, "geometric": 1}
@@ -869,6 +895,19 @@ class Context(_SceneCalls):
         nw, nv, nu = shape
         check(self.L.mcrt_render_label_frames(self.h, ptr(label_dev), n_frames, nu, nv, nw, C.byref(view), ptr(depth_dev), ptr(out_dev)))
 
+    def noise_frames(self, rf_dev, n_frames, n_images, n_elements, n_rows, first_image_id=0, element_gain=None, sigma_dev=None, **opts):
+        """mcrt_noise_frames: receiver noise over the RF stack [n_frames][n_images][n_elements][n_rows], in place -- a Gaussian noise floor
+        (image j of the stack draws from the streams of id first_image_id + j) and a gain per scan-line (element_gain: host floats
+        [n_elements] or None).  sigma_dev: [n_frames] floats on the device that receive each frame's sigma, or None.  opts: the keywords of
+        noise_opts_struct (snr_db or sigma, seed)"""
+        o = noise_opts_struct(**opts)
+        g = None
+        if element_gain is not None:
+            g = np.ascontiguousarray(element_gain, np.float32)
+            if g.shape != (n_elements,):
+                raise ValueError("element_gain takes one gain per scan-line: %d, got shape %s" % (n_elements, g.shape))
+        check(self.L.mcrt_noise_frames(self.h, ptr(rf_dev), n_frames, n_images, n_elements, n_rows, first_image_id, C.byref(o), ptr(g), ptr(sigma_dev)))
+
     def label_frames(self, pos=None, dirs=None, *, rule="traced", start_offset=None, e_begin=0, e_end=None, n_frames=None, tissue_dev=None,
                      interface_dev=None, crossings_dev=None):
         """mcrt_label_frames: the central beam of every scan-line walked through the scene.  pos / dirs None: the context's transducer (one
@@ -1024,7 +1063,7 @@ class Simulator:
 
     def __init__(self, scene_data, transducer, n_samples=5, n_rows=None, device=0, seed=0x5EED, psf=None, texture=None,
                  max_depth=10, sanitize_tir=0, tex_n=256, bvh_builder="sah", elevation=False, compound=None, compound_mode="mean", compound_weights=None,
-                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0, speckle=None):
+                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0, speckle=None, noise=None):
         """elevation=True: slice thickness.  trace() then traces the psf's elevation_size planes of the frame as one pose pass -- plane k of
         frame f with frame id f * K + k, the frame-id rule of include/mcrt.h -- and folds them into rf_dev with psf.elevation_rows();
         everything after (convolve, bmode, frame) is unchanged.
@@ -1040,16 +1079,36 @@ class Simulator:
         raise.  It does not combine with compound= or elevation=.
         speckle=True, or a dict of the keywords of speckle_opts_struct (n_iter, q0, rho, lambda): speckle reduction.  Every picture that
         runs the envelope (bmode, compound_image, volume, bmode_volume, render) then passes the enveloped stack through
-        mcrt_speckle_frames in place (despeckle()) before anything reads it.  frame() returns RF and is left alone."""
+        mcrt_speckle_frames in place (despeckle()) before anything reads it.  frame() returns RF and is left alone.
+        noise=X (an snr_db), or a dict of snr_db= or sigma=, seed=, element_gain= (one gain per scan-line) and dead_elements= (scan-lines
+        whose gain is 0): receiver noise.  Every run then passes the image stack through mcrt_noise_frames in place (add_noise()) after the
+        convolution step -- whether or not convolve ran -- and before the envelope, with first_image_id = frame_id * (images in the stack):
+        the ids the images were traced with, so a frame carries the same noise whatever pass it is part of.  frame() therefore returns
+        noisy RF, and everything downstream (bmode, compound_image, volume, render, freehand) sees it.  The stage sits after the lateral PSF
+        because receive noise is uncorrelated between scan-lines, which the PSF's lateral blur would undo; that is a modelling choice
+        that no measurement backs."""
         if sweep is not None and (compound is not None or elevation):
             raise ValueError("sweep= does not combine with compound= or elevation=")
         if compound is not None and not 1 <= len(tuple(compound)) <= 16:
             raise ValueError("compound takes 1..16 steering angles, got %d" % len(tuple(compound)))
         self.speckle = None if speckle is None or speckle is False else speckle_opts_struct(**({} if speckle is True else dict(speckle)))
+        E = transducer.n_elements
+        self.noise, self.noise_gain = None, None
+        if noise is not None and noise is not False:
+            nd = dict(noise) if isinstance(noise, dict) else dict(snr_db=noise)
+            gain, dead = nd.pop("element_gain", None), nd.pop("dead_elements", None)
+            self.noise = noise_opts_struct(**nd)
+            if gain is not None or dead is not None:
+                self.noise_gain = np.ones(E, np.float32) if gain is None else np.array(gain, np.float32)
+                if self.noise_gain.shape != (E,):
+                    raise ValueError("noise: element_gain takes one gain per scan-line (%d)" % E)
+                for e in (dead or ()):
+                    if not 0 <= int(e) < E:
+                        raise ValueError("noise: dead_elements: scan-line %d is not in 0..%d" % (int(e), E - 1))
+                    self.noise_gain[int(e)] = 0.0
         self.ctx = Context(device)
         self.ctx.set_bvh_builder(bvh_builder)
         self.tr = transducer
-        E = transducer.n_elements
         self.ctx.set_params(n_elements=E, n_samples=n_samples, frequency=transducer.frequency, seed=seed, max_depth=max_depth,
                             sanitize_tir=sanitize_tir, tex_n=tex_n, **({"n_rows": n_rows} if n_rows else {}))
         self.E, self.R, self.S = E, self.ctx.params.n_rows, n_samples
@@ -1126,10 +1185,22 @@ class Simulator:
         o = self.speckle if self.speckle is not None else speckle_opts_struct()
         self.ctx.speckle_frames(*self._stack, self.E, self.R, n_iter=o.n_iter, q0=o.q0, rho=o.rho, lambda_=o.lambda_)
 
+    def add_noise(self, frame_id=0, own_peaks=False):
+        """mcrt_noise_frames over the stack's images, in place, with the options of noise= (the defaults without one): the images are the
+        views or planes of ONE frame (one receiver, one peak) with the ids frame_id * (images in the stack) onwards; own_peaks=True: so many
+        frames of one image each (the tracked frames of freehand())"""
+        o = self.noise if self.noise is not None else noise_opts_struct()
+        dev, n = self._stack
+        kw = dict(sigma=o.sigma) if o.mode == NOISE_ABS else dict(snr_db=o.snr_db)
+        self.ctx.noise_frames(dev, n if own_peaks else 1, 1 if own_peaks else n, self.E, self.R, first_image_id=frame_id * n, element_gain=self.noise_gain,
+                              seed=o.seed, **kw)
+
     def _run(self, frame_id, convolve=True, envelope=True):
         self.trace(frame_id)
         if convolve:
             self.convolve()
+        if self.noise is not None:
+            self.add_noise(frame_id)
         if envelope:
             self.envelope()
             if self.speckle is not None:
@@ -1198,7 +1269,7 @@ class Simulator:
 
     def freehand(self, frame_id, pos, dirs, grid, convolve=True, envelope=True, counts=False, row_mm=None, unit_mm=10.0, **opts):
         """a freehand sweep and its volume: the F poses pos / dirs [F][E][3] (Transducer.poses) traced as one pose pass into a temporary stack
-        -- pose f with frame id frame_id * F + f -- -> convolve -> envelope (-> despeckle with speckle=) -> mcrt_recon_frames -> host: the float
+        -- pose f with frame id frame_id * F + f -- -> convolve (-> add_noise with noise=) -> envelope (-> despeckle with speckle=) -> mcrt_recon_frames -> host: the float
         voxels [nw][nv][nu] of grid (a VolumeGrid in the WORLD frame, mm); with counts=True (voxels, sample counts uint32 of the same shape).
         opts: the keywords of recon_opts_struct.  It raises under compound=, sweep= or elevation=."""
         if self.steers is not None or self.sweep is not None or self.elevation:
@@ -1212,6 +1283,8 @@ class Simulator:
             try:
                 if convolve:
                     self.convolve()
+                if self.noise is not None:
+                    self.add_noise(frame_id, own_peaks=True)       # (every tracked frame is a frame of its own)
                 if envelope:
                     self.envelope()
                     if self.speckle is not None:

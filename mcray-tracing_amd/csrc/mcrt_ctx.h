@@ -182,6 +182,8 @@ struct ImageStages {
     // focal zones (mcrt_convolve_frames_depth): the lateral taps [n_lat][R], and slice thickness (mcrt_elevation_frames): the elevation weights
     // [K][R] (room for MCRT_MAX_ROWS x 32 each).  Two tables: a frame uses both in turn, and one shared buffer would upload both on every frame
     StagedTable lat_rows, elev_rows;
+    // receiver noise (mcrt_noise_frames): the gain of every transducer element [E] of the last table (room for the largest E so far); the peaks are d_disp's
+    StagedTable gain;
     // freehand reconstruction (mcrt_recon_frames): the accumulators of the largest grid so far, n sums (8 B each), then n counts (4 B each)
     Buf<unsigned long long> d_recon;
     // freehand label reconstruction (mcrt_recon_label_frames): the vote table of the largest call so far, voxels x n_labels words

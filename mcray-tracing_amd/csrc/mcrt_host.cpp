@@ -760,6 +760,43 @@ extern "C" int mcrt_default_recon_label_opts(mcrt_recon_label_opts *o, uint32_t 
     return MCRT_OK;
 }
 
+// ---- receiver noise (the contract is in include/mcrt.h) ---------------------------------------
+extern "C" int mcrt_default_noise_opts(mcrt_noise_opts *o)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_noise_opts: null options");
+    o->mode = MCRT_NOISE_SNR_DB; o->snr_db = 50.0f; o->sigma = 0.0f; o->seed = 0x4E4F4953u;
+    return MCRT_OK;
+}
+
+// Philox4x32-10 on the host, as mcrt_detmath.h has it on the device (Salmon, Moraes, Dror, Shaw, SC'11)
+static void host_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4])
+{
+    for (int i = 0; i < 10; i++) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// the draws k_noise makes for one image, [E][R]
+extern "C" int mcrt_noise_draws(uint32_t seed, uint32_t image_id, uint32_t n_elements, uint32_t n_rows, int32_t *d)
+{
+    static const char fn[] = "mcrt_noise_draws";
+    if (!d) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null d", fn);
+    if (n_elements == 0 || n_rows == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_elements %u, n_rows %u)", fn, n_elements, n_rows);
+    if (n_rows > 2048u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: n_rows: at most 2048 rows (%u)", fn, n_rows);
+    for (uint32_t e = 0; e < n_elements; e++)
+        for (uint32_t r = 0; r < n_rows; r++) {
+            uint32_t o[4], s = 0;
+            host_philox4x32_10(e, r, 0x4E4F4953u, 0u, seed, image_id, o);
+            for (int k = 0; k < 4; k++) s += (o[k] & 0xffffu) + (o[k] >> 16);
+            d[(size_t)e * n_rows + r] = (int32_t)s - 262140;
+        }
+    return MCRT_OK;
+}
+
 // ---- volume rendering (the contract is in include/mcrt.h) ---------------------------------------
 extern "C" int mcrt_default_render_opts(mcrt_render_opts *o, int in_u8)
 {

@@ -1,5 +1,5 @@
 // mcrt_image.cpp -- the image stages of the C-ABI (include/mcrt.h): PSF, elevation, envelope, scan conversion, B-mode, compounding,
-// volume imaging and rendering, speckle reduction, freehand reconstruction, RF export / import.  Host C++ only.  Of a context (mcrt_ctx.h) these read
+// volume imaging and rendering, speckle reduction, receiver noise, freehand reconstruction, RF export / import.  Host C++ only.  Of a context (mcrt_ctx.h) these read
 // its device, its stream, p.speed_of_sound, c.max_travel_us, knobs.render_row_tile, knobs.speckle_fuse, the pose staging (mcrt::stage_poses:
 // the two recon calls) and the image stages' own state (ImageStages), nothing else.
 #include "mcrt_ctx.h"
@@ -529,6 +529,53 @@ extern "C" int mcrt_speckle_frames(mcrt_ctx *c, const float *in_dev, uint32_t n_
         HIP_TRY(mcrt::launch_srad(a, n_frames, T, c->stream));
         src = a.dst;
     }
+    return MCRT_OK;
+}
+
+// ---- receiver noise (the contract is in include/mcrt.h; the defaults and the host's draws are host code: mcrt_host.cpp) ----
+// Everything is checked before anything is enqueued; then the gain table (only when it differs from the one on the device), in SNR_DB
+// mode the peaks (memset + k_bmode_peak without TGC, a frame's n_images * E scan-lines as one image: the reduction fits unchanged), and k_noise.
+extern "C" int mcrt_noise_frames(mcrt_ctx *c, float *rf_dev, uint32_t n_frames, uint32_t n_images, uint32_t E, uint32_t R, uint32_t first_image_id,
+                                 const mcrt_noise_opts *o, const float *element_gain, float *sigma_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_noise_frames";
+    if (!rf_dev) return set_error(MCRT_ERR_INVALID, "%s: null rf_dev", fn);
+    if (n_frames == 0 || n_images == 0 || E == 0 || R == 0)
+        return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, n_images %u, n_elements %u, n_rows %u)", fn, n_frames, n_images, E, R);
+    mcrt_noise_opts d;
+    if (!o) { mcrt_default_noise_opts(&d); o = &d; }
+    if (o->mode != MCRT_NOISE_SNR_DB && o->mode != MCRT_NOISE_ABS) return set_error(MCRT_ERR_INVALID, "%s: unknown mode %u", fn, o->mode);
+    const bool snr = o->mode == MCRT_NOISE_SNR_DB;
+    if (snr && !std::isfinite(o->snr_db)) return set_error(MCRT_ERR_INVALID, "%s: snr_db must be finite (%g)", fn, (double)o->snr_db);
+    if (!snr && !(std::isfinite(o->sigma) && o->sigma >= 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: sigma must be finite and >= 0 (%g)", fn, (double)o->sigma);
+    for (uint32_t e = 0; element_gain && e < E; e++)
+        if (!std::isfinite(element_gain[e])) return set_error(MCRT_ERR_INVALID, "%s: element_gain[%u] is not finite", fn, e);
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: n_rows: at most %d rows (%u)", fn, MCRT_MAX_ROWS, R);
+    const uint64_t images = (uint64_t)n_frames * n_images;
+    if (images > 65535ull) return set_error(MCRT_ERR_LIMIT, "%s: n_frames * n_images: at most 65535 images per call (%u x %u)", fn, n_frames, n_images);
+    if ((uint64_t)first_image_id + images > 0x100000000ull)
+        return set_error(MCRT_ERR_LIMIT, "%s: first_image_id: the ids of %llu images from %u on pass 2^32", fn, (unsigned long long)images, first_image_id);
+    if ((double)images * (double)E * (double)R >= 0x1p31)
+        return set_error(MCRT_ERR_LIMIT, "%s: a stack of 2^31 samples or more (%u x %u x %u x %u)", fn, n_frames, n_images, E, R);
+    if (!snr && o->sigma == 0.0f && !element_gain) {            // the identity: nothing is launched
+        if (sigma_dev) HIP_TRY(hipMemsetAsync(sigma_dev, 0, 4 * (size_t)n_frames, c->stream));
+        return MCRT_OK;
+    }
+    if (snr && !c->img.d_disp) HIP_TRY(c->img.d_disp.alloc(65536));   // (the peaks of the largest pass, as mcrt_bmode_frames has them)
+    if (element_gain) MCRT_TRY(c->img.gain.put(element_gain, E, 1, E, c->stream));
+    mcrt::NoiseArgs a;
+    a.rf = rf_dev; a.peak = nullptr; a.gain = element_gain ? c->img.gain.dev.p : nullptr; a.sigma_out = sigma_dev;
+    a.N = n_images; a.E = E; a.R = R; a.lines = (uint32_t)images * E; a.chunks = (R + NOISE_WAVE_ROWS - 1u) / NOISE_WAVE_ROWS;
+    a.seed = o->seed; a.first_id = first_image_id;
+    a.c = snr ? (float)std::pow(10.0, -(double)o->snr_db / 20.0) : o->sigma;
+    a.inv_std = (float)(1.0 / std::sqrt(2863311530.0));
+    if (snr) {
+        a.peak = c->img.d_disp.p;
+        HIP_TRY(hipMemsetAsync(c->img.d_disp.p, 0, 4 * (size_t)n_frames, c->stream));
+        HIP_TRY(mcrt::launch_bmode_peak(rf_dev, n_frames, n_images * E, R, nullptr, c->img.d_disp.p, c->stream));
+    }
+    HIP_TRY(mcrt::launch_noise(a, c->stream));
     return MCRT_OK;
 }
 

@@ -14,6 +14,7 @@
 //   mcrt_volume.hip  k_volume (volume imaging: mcrt_volume_frames, mcrt_bmode_volume_frames)
 //   mcrt_render.hip  k_render (volume rendering: mcrt_render_frames)
 //   mcrt_speckle.hip k_srad (speckle reduction: mcrt_speckle_frames)
+//   mcrt_noise.hip   k_noise (receiver noise: mcrt_noise_frames; its peaks are k_bmode_peak's)
 //   mcrt_recon.hip   k_recon_splat, k_recon_resolve (freehand 3-D reconstruction: mcrt_recon_frames)
 //   mcrt_label.hip   k_label (ground-truth label maps: mcrt_label_frames), k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames)
 //   mcrt_label3d.hip k_recon_label_splat, k_recon_label_resolve (a freehand label volume by majority vote: mcrt_recon_label_frames),
@@ -229,6 +230,21 @@ struct ReconArgs {
     double qscale;
 };
 
+// k_noise (mcrt_noise_frames): the stack [F][N][E][R] in place; a wavefront owns NOISE_WAVE_ROWS consecutive rows of one scan-line
+#define NOISE_LANE_ROWS 4u                          // consecutive rows of a lane: one 16-byte access where the scan-line's base allows
+#define NOISE_WAVE_ROWS (64u * NOISE_LANE_ROWS)
+struct NoiseArgs {
+    float *rf;                          // [F][N][E][R]
+    const float *peak;                  // [F]: sigma_f = peak[f] * c (MCRT_NOISE_SNR_DB), or null: sigma_f = c (MCRT_NOISE_ABS)
+    const float *gain;                  // [E] or null
+    float *sigma_out;                   // [F] or null: receives sigma_f
+    uint32_t N, E, R;
+    uint32_t lines;                     // F * N * E
+    uint32_t chunks;                    // ceil(R / NOISE_WAVE_ROWS)
+    uint32_t seed, first_id;            // Philox key word 0, and the id of image 0
+    float c, inv_std;
+};
+
 // k_label (mcrt_label_frames): beside these, a FrameArgs of which it reads the scene, the probe (el_pos, el_dir, pose_stride, e_begin, ne_frame,
 // ne = ne_frame * frames), the row table (row_thr, R, inv_row_dt, thr_end, max_travel, sos_d), start_mat, offs, the spacing, pad_abs, stack_ovf
 // (label_stack_entries() in LDS, the rest [..][label_blocks * 64]) and error_flag
@@ -297,6 +313,7 @@ hipError_t launch_compound(const CompoundArgs &a, bool out8, hipStream_t st);   
 hipError_t launch_volume(const VolumeArgs &a, bool out8, hipStream_t st);
 hipError_t launch_render(const RenderArgs &a, bool in8, hipStream_t st);
 hipError_t launch_srad(SpeckleArgs a, uint32_t F, uint32_t fuse, hipStream_t st);   // fuse: 2 or 4 (the instantiation); a.n <= fuse
+hipError_t launch_noise(const NoiseArgs &a, hipStream_t st);
 hipError_t launch_recon_splat(const ReconArgs &a, hipStream_t st);
 hipError_t launch_recon_resolve(ReconArgs a, hipStream_t st);
 hipError_t launch_recon_label_splat(const ReconLabelArgs &a, hipStream_t st);

@@ -7,6 +7,7 @@
 //                   [--render DX,DY,DZ --render-box-mm X0,Y0,Z0,X1,Y1,Z1 --render-voxel-mm P [--render-mode mip|mean|surface] [--render-size NX,NY]]
 //                   [--labels FILE.pgm [--label-rule traced|geometric] [--label-offset X]] [--render-labels FILE.pgm] [--freehand-labels FILE.raw]
 //                   [--speckle N [--speckle-q0 X] [--speckle-rho X] [--speckle-lambda X]]
+//                   [--noise-db X | --noise-sigma X [--noise-seed N] [--dead-elements a,b,c]]
 //                   [--freehand N --freehand-step-mm D [--freehand-fan-deg A] --freehand-box-mm X0,Y0,Z0,X1,Y1,Z1 --freehand-voxel-mm P --freehand-out FILE.raw
 //                    [--freehand-mode mean|max] [--freehand-fill H]]
 // --gpus N: the first N GPUs of the node, the frame's scan-lines sharded over them (mcrt_group_*: one tracing context and host thread per
@@ -60,6 +61,12 @@
 // --compound, the planes of --sweep, --render; rf.bin holds the filtered image too.  --speckle-q0 X is the speckle scale (0.5227232, fully
 // developed speckle), --speckle-rho X its decay per iteration (1/6), --speckle-lambda X the time step in (0, 1] (0.5); the three need
 // --speckle.  Without --speckle nothing changes.
+// --noise-db X adds receiver noise to every RF image between the convolution and the envelope (mcrt_noise_frames): a Gaussian noise floor
+// X dB below the frame's own peak -- the views of --compound and the planes of --sweep share one receiver, hence one peak; the frames of
+// --freehand have one each --, drawn from the streams of the frame ids the images were traced with; --noise-sigma X gives the floor's
+// standard deviation in RF units instead (0: no noise).  --noise-seed N is the seed of the noise streams; --dead-elements a,b,c silences
+// those scan-lines (0..511: a gain of 0, the dark radial streak of a dead element).  The last two need one of the first two, which exclude
+// each other.  rf.bin holds the noisy image.  Without these options nothing changes.
 // --freehand N (1..1024) adds a freehand 3-D acquisition after the frames of the run: the probe is moved by hand, here along its elevation axis
 // in N steps of --freehand-step-mm D centred on the scene's pose, step k tilted by (k - (N-1)/2) x --freehand-fan-deg A (0) about the line through
 // the arc's apex; the N frames are traced as one pass with the last frame's number, convolved, enveloped (and despeckled with --speckle) and
@@ -118,6 +125,9 @@ int main(int argc, char **argv)
     mcrt_label_opts lopts; mcrt_default_label_opts(&lopts);
     const char *speckle_n = nullptr, *speckle_q0 = nullptr, *speckle_rho = nullptr, *speckle_lambda = nullptr;   // the options as given
     mcrt_speckle_opts sopts; mcrt_default_speckle_opts(&sopts);
+    const char *noise_db = nullptr, *noise_sigma = nullptr, *noise_seed = nullptr, *dead_elements = nullptr;   // the options as given
+    mcrt_noise_opts nopts; mcrt_default_noise_opts(&nopts);
+    std::vector<float> element_gain;                  // empty: no gain table
     const char *freehand_n = nullptr, *freehand_step = nullptr, *freehand_fan = nullptr, *freehand_box = nullptr, *freehand_voxel = nullptr, *freehand_out = nullptr,
                *freehand_mode = nullptr, *freehand_fill = nullptr;   // the options as given
     mcrt_recon_opts fopts; mcrt_default_recon_opts(&fopts);
@@ -157,6 +167,10 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--speckle-q0") && i + 1 < argc) speckle_q0 = argv[++i];
             else if (!std::strcmp(argv[i], "--speckle-rho") && i + 1 < argc) speckle_rho = argv[++i];
             else if (!std::strcmp(argv[i], "--speckle-lambda") && i + 1 < argc) speckle_lambda = argv[++i];
+            else if (!std::strcmp(argv[i], "--noise-db") && i + 1 < argc) noise_db = argv[++i];
+            else if (!std::strcmp(argv[i], "--noise-sigma") && i + 1 < argc) noise_sigma = argv[++i];
+            else if (!std::strcmp(argv[i], "--noise-seed") && i + 1 < argc) noise_seed = argv[++i];
+            else if (!std::strcmp(argv[i], "--dead-elements") && i + 1 < argc) dead_elements = argv[++i];
             else if (!std::strcmp(argv[i], "--freehand") && i + 1 < argc) freehand_n = argv[++i];
             else if (!std::strcmp(argv[i], "--freehand-step-mm") && i + 1 < argc) freehand_step = argv[++i];
             else if (!std::strcmp(argv[i], "--freehand-fan-deg") && i + 1 < argc) freehand_fan = argv[++i];
@@ -274,6 +288,28 @@ int main(int argc, char **argv)
             float q0sq[256], kq[256], lam4;
             if (mcrt_speckle_tables(&sopts, q0sq, kq, &lam4) != MCRT_OK) throw std::invalid_argument(std::string("--speckle: ") + mcrt_last_error());
         }
+        if (noise_db && noise_sigma) throw std::invalid_argument("--noise-db and --noise-sigma exclude each other");
+        if (!noise_db && !noise_sigma && (noise_seed || dead_elements)) throw std::invalid_argument("--noise-seed and --dead-elements need --noise-db or --noise-sigma");
+        const bool noise = noise_db || noise_sigma;
+        if (noise_db) {
+            nopts.mode = MCRT_NOISE_SNR_DB; nopts.snr_db = (float)std::atof(noise_db);
+            if (!std::isfinite(nopts.snr_db)) throw std::invalid_argument("--noise-db takes a finite number of dB");
+        }
+        if (noise_sigma) {
+            nopts.mode = MCRT_NOISE_ABS; nopts.sigma = (float)std::atof(noise_sigma);
+            if (!(std::isfinite(nopts.sigma) && nopts.sigma >= 0.0f)) throw std::invalid_argument("--noise-sigma takes a finite standard deviation >= 0");
+        }
+        if (noise_seed) nopts.seed = (uint32_t)std::strtoul(noise_seed, nullptr, 0);
+        if (dead_elements) {
+            element_gain.assign(transducer_elements, 1.0f);
+            const std::vector<int> dead = comma_list<int>(dead_elements);
+            if (dead.empty()) throw std::invalid_argument("--dead-elements takes a list of scan-lines a,b,c");
+            for (int e : dead) {
+                if (e < 0 || e >= (int)transducer_elements) throw std::invalid_argument("--dead-elements takes scan-lines 0.." + std::to_string(transducer_elements - 1));
+                element_gain[(size_t)e] = 0.0f;
+            }
+        }
+        const float *gain = element_gain.empty() ? nullptr : element_gain.data();
         if (!freehand_n && (freehand_step || freehand_fan || freehand_box || freehand_voxel || freehand_out || freehand_mode || freehand_fill))
             throw std::invalid_argument("--freehand-step-mm, --freehand-fan-deg, --freehand-box-mm, --freehand-voxel-mm, --freehand-out, --freehand-mode and --freehand-fill need --freehand");
         long freehand_frames = 0; double freehand_step_mm = 0.0, freehand_fan_deg = 0.0;
@@ -343,6 +379,7 @@ int main(int argc, char **argv)
             else if (elevation_given) rf_image.trace((uint32_t)f, transducer, psf, (uint32_t)elevation);   // ... in K elevation planes, folded
             else rf_image.trace((uint32_t)f);      // clear + cast_rays + accumulation (main.cpp:102-144)
             rf_image.convolve(psf);           // main.cpp:146
+            if (noise) rf_image.add_noise(nopts, gain);   // the receiver's noise floor and dead elements, on whatever the convolution ran over
             rf_image.envelope();              // main.cpp:147
             if (speckle_n) rf_image.despeckle(sopts);   // the despeckle filter, on whatever the envelope ran over
             if (render_dir && render_labels && f == frames - 1) {                                   // the box seen from a direction, and what is seen
@@ -364,6 +401,7 @@ int main(int argc, char **argv)
             const auto poses = transducer.freehand((uint32_t)freehand_frames, freehand_step_mm, freehand_fan_deg);
             tracked.trace((uint32_t)std::max(frames - 1, 0), poses.pos, poses.dir);
             tracked.convolve(psf);
+            if (noise) tracked.add_noise(nopts, gain);
             tracked.envelope();
             if (speckle_n) tracked.despeckle(sopts);
             const std::vector<float> vox = tracked.reconstruct(fgrid, &fopts);

@@ -726,7 +726,7 @@ public:
     {
         shape_params();
         check(dev->trace_frames(frame_id, 1, columns, rf.as<float>()), "mcrt_trace_frame");       // (every GPU of a group traces its scan-line shard)
-        where = on_device; holds = stack_of::nothing; n_views = 0;
+        where = on_device; holds = stack_of::nothing; n_views = 0; first_id = frame_id;
     }
     // the same with slice thickness (psf.h:16-18,42,77; mcrt.h): the frame's n_planes elevation planes (0: the psf's elevation_size), spread
     // p.elevation_pitch_um() apart around the transducer's own plane, traced as ONE pose pass -- plane k with frame id frame_id * K + k, the
@@ -739,7 +739,7 @@ public:
         const std::vector<float> &w = p.elevation_rows(max_rows, (double)axial_resolution_um / 1000.0, K);
         pose_pass(frame_id, K, tables, planes, "rf_image::trace: frame_id * n_planes does not fit a frame id");
         check(mcrt_elevation_frames(dev->ctx, planes.as<float>(), 1, K, columns, max_rows, w.data(), rf.as<float>()), "mcrt_elevation_frames");
-        where = on_device; holds = stack_of::nothing; n_views = 0;
+        where = on_device; holds = stack_of::nothing; n_views = 0; first_id = frame_id;
     }
     // spatial compounding (mcrt.h): the frame's views, one per steering angle [rad] of steer_rad (1..16), traced as ONE pose pass -- view n with
     // frame id frame_id * N + n, the frame-id rule of mcrt.h -- into a stack [N][columns][max_rows] this image owns.  convolve() and envelope()
@@ -751,7 +751,7 @@ public:
         const uint32_t V = (uint32_t)steer_rad.size();
         if (V == 0 || V > 16) throw std::invalid_argument("rf_image::trace: 1..16 steering angles");
         pose_pass(frame_id, V, t.steered(steer_rad), stack, "rf_image::trace: frame_id * views does not fit a frame id");
-        holds = stack_of::views; n_views = V;
+        holds = stack_of::views; n_views = V; first_id = frame_id * V;
     }
     // volume imaging (mcrt.h): the K planes of a probe swept in elevation, traced as ONE pose pass -- plane k with frame id frame_id * K + k, the
     // frame-id rule of mcrt.h -- into the stack [K][columns][max_rows] the views of a compounded frame use.  convolve() and envelope() then run
@@ -762,7 +762,7 @@ public:
         static_assert(N == columns, "one scan-line per transducer element");
         if (sw.n_planes == 0 || sw.n_planes > 256) throw std::invalid_argument("rf_image::trace: a sweep has 1..256 planes");
         pose_pass(frame_id, sw.n_planes, t.swept(sw), stack, "rf_image::trace: frame_id * planes does not fit a frame id");
-        holds = stack_of::sweep_planes; n_views = sw.n_planes; sweep = sw;
+        holds = stack_of::sweep_planes; n_views = sw.n_planes; sweep = sw; first_id = frame_id * sw.n_planes;
     }
     // freehand 3-D (mcrt.h: mcrt_recon_frames): the frames of a tracked probe moved by hand, one pose per frame -- a vector of transducers, or the
     // two tables [F][columns][3] (transducer::freehand makes a regular one) --, traced as ONE pose pass -- pose f with frame id frame_id * F + f
@@ -774,7 +774,7 @@ public:
         if (F == 0 || F > 65535 || pos.size() != F * one || dir.size() != pos.size()) throw std::invalid_argument("rf_image::trace: pose tables [F][columns][3], F = 1..65535");
         tracked.pos = pos; tracked.dir = dir;
         pose_pass(frame_id, (uint32_t)F, tracked, stack, "rf_image::trace: frame_id * poses does not fit a frame id");
-        holds = stack_of::tracked_frames; n_views = (uint32_t)F;
+        holds = stack_of::tracked_frames; n_views = (uint32_t)F; first_id = frame_id * (uint32_t)F;
     }
     template <size_t N> void trace(uint32_t frame_id, const std::vector<transducer<N>> &poses)
     {
@@ -843,6 +843,19 @@ public:
     {
         if (n_views) { check(mcrt_envelope_frames(dev->ctx, stack.as<float>(), n_views, columns, max_rows), "mcrt_envelope_frames"); return; }
         to_device(); check(mcrt_envelope(dev->ctx, rf.as<float>(), columns, max_rows), "mcrt_envelope");
+    }
+    // receiver noise (mcrt.h: mcrt_noise_frames): a noise floor and a gain per scan-line (element_gain: [columns] or null) over whatever the
+    // last trace() filled, in place -- this image, or the views of a compounded frame or the planes of a sweep as ONE frame (one receiver,
+    // one peak), or the tracked frames of a freehand pass as so many frames -- with the ids that trace used.  It goes after convolve() and
+    // before envelope(): receive noise is uncorrelated between scan-lines
+    void add_noise(const mcrt_noise_opts &o, const float *element_gain = nullptr)
+    {
+        if (n_views) {
+            const bool own = holds == stack_of::tracked_frames;
+            check(mcrt_noise_frames(dev->ctx, stack.as<float>(), own ? n_views : 1u, own ? 1u : n_views, columns, max_rows, first_id, &o, element_gain, nullptr), "mcrt_noise_frames");
+            return;
+        }
+        to_device(); check(mcrt_noise_frames(dev->ctx, rf.as<float>(), 1, 1, columns, max_rows, first_id, &o, element_gain, nullptr), "mcrt_noise_frames");
     }
     // speckle reduction (mcrt.h: mcrt_speckle_frames): speckle-reducing anisotropic diffusion over the enveloped image -- the views of a
     // compounded frame, the planes of a sweep --, in place; it goes after envelope() and before whatever makes the picture
@@ -1089,6 +1102,7 @@ private:
     device_buffer stack;                         // trace(frame, transducer, steer_rad | sweep): the images [n_views][columns][max_rows]
     enum class stack_of { nothing, views, sweep_planes, tracked_frames } holds = stack_of::nothing;   // ... what the last trace left in it
     uint32_t n_views = 0;                        // ... and how many (nothing: 0)
+    uint32_t first_id = 0;                       // the frame id the last trace() gave its first image (add_noise: the noise streams' ids)
     mcrt_sweep sweep{ 0, 0.0f, 0.0f };           // ... the sweep of sweep_planes
     struct pose_tables { std::vector<float> pos, dir; } tracked;   // ... the poses of tracked_frames, [n_views][columns][3] each
     device_buffer points;                        // volume(), label_picture(), label_volume(): the gathered points, floats or bytes
