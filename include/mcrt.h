@@ -58,7 +58,9 @@ extern "C" {
                                    + mcrt_debug_beam_order, mcrt_debug_beam_layout (the beam order of a bounce run by beams, its layout on the host; additive);
                                    + mcrt_debug_beam_scan (the kernel that lays a beam order out, run alone on given counters; additive);
                                    + mcrt_noise_opts, mcrt_default_noise_opts, mcrt_noise_draws, mcrt_noise_frames (receiver noise: a Gaussian noise floor
-                                   from integer Philox sums and a gain per transducer element, over the RF stack in place; additive) */
+                                   from integer Philox sums and a gain per transducer element, over the RF stack in place; additive);
+                                   + mcrt_transmit_opts, mcrt_default_transmit_opts, mcrt_transmit_boundary, mcrt_transmit_frames (acoustic ground truth:
+                                   the intensity that arrives at every scan-line sample and what each boundary turns back; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -870,6 +872,64 @@ int mcrt_label_scan_convert_frames(mcrt_ctx *ctx, const uint8_t *tissue_dev /* [
 int mcrt_label_volume_frames(mcrt_ctx *ctx, const uint8_t *tissue_dev /* [n_frames][K][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
                              double radius_mm, double total_angle_rad, const mcrt_sweep *sweep, const mcrt_volume_grid *grid,
                              uint8_t *out_dev /* [n_frames][nw][nv][nu] */);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Acoustic ground truth: how much sound gets there.  The label maps say what tissue a sample shows; these say what fraction of the emitted
+ * intensity ARRIVES at it (`transmit`: the shadow behind bone and gas, the enhancement behind fluid) and what fraction each boundary turns
+ * back (`reflect`).  It is the quantity the tracer carries along every path (scene.cpp:122-165, ray.cpp:11-97: the attenuation of a segment,
+ * the impedance rule at its end) and loses in the Monte-Carlo sum, here carried along the label walk's deterministic central beam: it
+ * depends on neither seed, samples, frame id nor texture.  Both maps are float stacks [F][E][R]: mcrt_scan_convert_frames,
+ * mcrt_volume_frames, mcrt_recon_frames and mcrt_render_frames take them as they are, so they are registered to every picture with no
+ * gather of their own.
+ *
+ * THE WALK is mcrt_label_frames' own, steps 1-8 of its comment, unchanged -- the segment arithmetic, the closest hit, the hit point, dist,
+ * t and the stop conditions, the row b, MCRT_LABEL_MAX_CROSSINGS, the medium update of `rule` --, so crossings equals mcrt_label_frames'
+ * bit for bit under the same rule and start_offset.  On top of it the beam carries I (float, 1.0f at the start) and t_prev (double, 0.0);
+ * every float operation is rounded on its own (no fma), expf is the contract's (det_expf), freq is the context's frequency, sos its speed
+ * of sound as a double, imp(m) / att(m) the impedance and the attenuation of material m (in MCRT_TRANSMIT_BOUNDARIES att(m) is 0.0f):
+ *   rows    a row r of [b_prev, b), m the medium the segment runs in:
+ *               dt = (double)r * row_dt_us - t_prev;  if (!(dt > 0.0)) dt = 0.0;   mm_r = (dt * sos) / 1000.0
+ *               transmit[r] = I * expf(-att(m) * ((float)mm_r * 0.01f) * freq)
+ *           -- the tracer's own attenuation with the distance to the row's start in place of the distance to the boundary.  The row that
+ *           holds the previous boundary takes the value just behind it (dt clamps to 0); row 0 is exactly 1.0f
+ *   at the boundary (mm: step 4's double, m: the medium BEFORE the update, m2: the medium after it)
+ *               Ia = I * expf(-att(m) * ((float)mm * 0.01f) * freq)
+ *               nn = normalized(cross(v1 - v0, v2 - v0)) of the hit triangle;  inc = dot(dir, -nn);  if (inc < 0) inc = dot(dir, nn)
+ *               (i_refl, i_refr) = mcrt_transmit_boundary(imp(m), imp(m2), inc, Ia)
+ *               reflect[b] = i_refl if no boundary has written row b yet (the shallowest boundary of a row wins, as for `interface`)
+ *               I = i_refr > 0 ? i_refr : 0.0f;   t_prev = t, b_prev = b, from = p
+ *           A NaN or a negative remainder ends the energy, not the walk: the walk goes on (crossings stays the label walk's), every later
+ *           row is 0 * ...
+ *   after   rows [b_prev, R) are filled from the last segment by the same rule;  reflect is 0.0f wherever no boundary falls
+ * mcrt_transmit_boundary is the tracer's impedance rule (in ray.cpp:11-97), host only, no GPU:
+ *               rr = z_before / z_after;  refa = 1 - rr * rr * (1 - inc * inc)
+ *               refa < 0 (total internal reflection):  i_refl = intensity, i_refr = 0
+ *               else  refa = sqrtf(refa);  num = z_before * inc - z_after * refa;  den = z_before * inc + z_after * refa;  qq = num / den
+ *                     i_refl = (float)((double)intensity * ((double)qq * (double)qq));  i_refr = intensity - i_refl
+ * THIS IS THE ENERGY THE GEOMETRY ALLOWS, NOT ONE SAMPLE'S FATE: no random perturbation of the normal, no thickness penetration, no
+ * intensity_epsilon cut, the beam stays straight (no refraction), and the way back to the probe is not attenuated.  A thresholded shadow
+ * mask is a caller's one comparison; `reflect` is not made into a picture (a one-row arc does not survive scan conversion).
+ * pos, dir, e_begin, e_end, n_frames: as mcrt_label_frames.  Outputs, each a device pointer or NULL, ne = e_end - e_begin: transmit_dev and
+ * reflect_dev float [n_frames][ne][R], crossings_dev uint32 [n_frames][ne]; every element of every non-NULL output is written, whatever
+ * the pointers' alignment beyond a float's.  Asynchronous on the context's stream, one launch; nothing is allocated after the first call
+ * of a size.  Errors and limits: mcrt_label_frames' with these three outputs in its outputs' place, without the limit of 254 materials,
+ * and MCRT_ERR_INVALID for an unknown mode.  On an error nothing is launched and nothing is written.  Groups: as mcrt_label_frames -- take
+ * the maps on mcrt_group_member(grp, 0). */
+enum { MCRT_TRANSMIT_TOTAL = 0,        /* attenuation along the beam and the loss at every boundary */
+       MCRT_TRANSMIT_BOUNDARIES = 1 }; /* the boundaries alone: every attenuation taken as 0.0f (piecewise constant) */
+typedef struct { uint32_t mode;         /* MCRT_TRANSMIT_*                                   (TOTAL)  */
+                 uint32_t rule;         /* MCRT_LABEL_TRACED / MCRT_LABEL_GEOMETRIC          (TRACED) */
+                 float    start_offset; /* as mcrt_label_opts                                (-1)     */
+} mcrt_transmit_opts;                   /* 12 bytes */
+int mcrt_default_transmit_opts(mcrt_transmit_opts *o);                                   /* host only */
+/* the boundary rule alone, on the host (no GPU): what one crossing does to an intensity.  MCRT_ERR_INVALID for a null i_refl or i_refr */
+int mcrt_transmit_boundary(float z_before, float z_after, float inc, float intensity, float *i_refl, float *i_refr);
+int mcrt_transmit_frames(mcrt_ctx *ctx, uint32_t n_frames, uint32_t e_begin, uint32_t e_end,
+                         const float *pos, const float *dir,              /* as mcrt_label_frames */
+                         const mcrt_transmit_opts *o /* NULL = defaults */,
+                         float *transmit_dev  /* [n_frames][ne][R] or NULL */,
+                         float *reflect_dev   /* [n_frames][ne][R] or NULL */,
+                         uint32_t *crossings_dev /* [n_frames][ne] or NULL */);
 
 /* Labels in 3-D, I: a freehand label volume -- the ground truth of mcrt_recon_frames' voxels -- by MAJORITY VOTE.  The input is the tissue
  * stack uint8 [F][E][R] that mcrt_label_frames wrote for the pose tables [F][E][3], those tables, and row_mm, unit_mm and the WORLD-frame

@@ -84,6 +84,11 @@ class LabelOpts(C.Structure):
     _fields_ = [("rule", C.c_uint32), ("start_offset", C.c_float)]
 
 
+class TransmitOpts(C.Structure):
+    """mcrt_transmit_opts (include/mcrt.h): 12 bytes"""
+    _fields_ = [("mode", C.c_uint32), ("rule", C.c_uint32), ("start_offset", C.c_float)]
+
+
 class RenderView(C.Structure):
     """mcrt_render_view (include/mcrt.h): 64 bytes, di at 12, dj at 24, ds at 36, nx at 48"""
     _fields_ = [("origin", C.c_float * 3), ("di", C.c_float * 3), ("dj", C.c_float * 3), ("ds", C.c_float * 3),
@@ -123,7 +128,7 @@ SEGMENT_DTYPE = np.dtype([("from", "<f4", 3), ("to", "<f4", 3), ("dir", "<f4", 3
                           ("distance_traveled", "<f8"), ("media", "<i4"), ("tri", "<i4")])
 assert NODE_DTYPE.itemsize == 64 and SEGMENT_DTYPE.itemsize == 64 and C.sizeof(BvhNode) == 64 and C.sizeof(BmodeParams) == 48 and C.sizeof(Focus) == 40 and C.sizeof(Compound) == 68 and C.sizeof(CompoundOpts) == 72
 assert C.sizeof(Sweep) == 12 and C.sizeof(VolumeGrid) == 112 and C.sizeof(LabelOpts) == 8 and C.sizeof(RenderView) == 64 and C.sizeof(RenderOpts) == 32 and C.sizeof(SpeckleOpts) == 16 and C.sizeof(NoiseOpts) == 16 and C.sizeof(ReconOpts) == 20
-assert C.sizeof(ReconLabelOpts) == 12
+assert C.sizeof(ReconLabelOpts) == 12 and C.sizeof(TransmitOpts) == 12
 
 # every symbol include/mcrt.h declares (tests/test_abi.py checks the .so exports each one)
 SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create", "mcrt_destroy", "mcrt_set_stream",
@@ -140,6 +145,7 @@ SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create"
            "mcrt_default_compound_opts", "mcrt_compound_weights", "mcrt_compound_frames_opts", "mcrt_bmode_compound_frames_opts",
            "mcrt_transducer_swept", "mcrt_volume_maps", "mcrt_volume_frames", "mcrt_bmode_volume_frames",
            "mcrt_default_label_opts", "mcrt_label_frames", "mcrt_label_scan_convert_frames", "mcrt_label_volume_frames",
+           "mcrt_default_transmit_opts", "mcrt_transmit_boundary", "mcrt_transmit_frames",
            "mcrt_default_render_opts", "mcrt_render_view_for_grid", "mcrt_render_frames",
            "mcrt_default_speckle_opts", "mcrt_speckle_tables", "mcrt_speckle_frames",
            "mcrt_default_noise_opts", "mcrt_noise_draws", "mcrt_noise_frames",
@@ -208,6 +214,9 @@ def load_library():
         "mcrt_bmode_volume_frames": [vp, vp, u32, u32, u32, C.POINTER(BmodeParams), C.POINTER(Sweep), C.POINTER(VolumeGrid), vp, vp, vp],
         "mcrt_default_label_opts": [C.POINTER(LabelOpts)],
         "mcrt_label_frames": [vp, u32, u32, u32, vp, vp, C.POINTER(LabelOpts), vp, vp, vp],
+        "mcrt_default_transmit_opts": [C.POINTER(TransmitOpts)],
+        "mcrt_transmit_boundary": [C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)],
+        "mcrt_transmit_frames": [vp, u32, u32, u32, vp, vp, C.POINTER(TransmitOpts), vp, vp, vp],
         "mcrt_label_scan_convert_frames": [vp, vp, u32, u32, u32, C.c_double, C.c_double, vp, u32, u32],
         "mcrt_label_volume_frames": [vp, vp, u32, u32, u32, C.c_double, C.c_double, C.POINTER(Sweep), C.POINTER(VolumeGrid), vp],
         "mcrt_default_render_opts": [C.POINTER(RenderOpts), i32],

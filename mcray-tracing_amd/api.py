@@ -11,7 +11,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, RenderView, RenderOpts, SpeckleOpts, NoiseOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, NoiseOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 DEFAULT_ANGLE = 1.0471975511965976      # the sector of main.cpp:28: 60 degrees [rad]
 
@@ -413,6 +413,29 @@ def label_opts_struct(rule="traced", start_offset=None):
     if start_offset is not None:
         o.start_offset = float(start_offset)
     return o
+
+
+TRANSMIT_MODES = {"total": 0, "boundaries": 1}
+
+
+def transmit_opts_struct(mode="total", rule="traced", start_offset=None):
+    """mcrt_transmit_opts from keywords: mode "total" (the attenuation along the beam and the loss at every boundary) / "boundaries" (the
+    boundaries alone, piecewise constant) or the MCRT_TRANSMIT_* number; rule and start_offset as label_opts_struct"""
+    o = TransmitOpts()
+    check(load_library().mcrt_default_transmit_opts(C.byref(o)))
+    o.mode = TRANSMIT_MODES[mode] if isinstance(mode, str) else int(mode)
+    o.rule = LABEL_RULES[rule] if isinstance(rule, str) else int(rule)
+    if start_offset is not None:
+        o.start_offset = float(start_offset)
+    return o
+
+
+def transmit_boundary(z_before, z_after, inc, intensity):
+    """mcrt_transmit_boundary (host only): what one crossing from impedance z_before into z_after at the cosine inc does to an intensity ->
+    (reflected, transmitted) as float32"""
+    refl, refr = C.c_float(), C.c_float()
+    check(load_library().mcrt_transmit_boundary(float(z_before), float(z_after), float(inc), float(intensity), C.byref(refl), C.byref(refr)))
+    return np.float32(refl.value), np.float32(refr.value)
 
 
 def bmode_params(mode="db", dynamic_range_db=60.0, gain_db=0.0, ref=None, persistence=0.0, reset_state=True, radius_mm=30.0,
@@ -921,6 +944,20 @@ class Context(_SceneCalls):
         o = label_opts_struct(rule, start_offset)
         check(self.L.mcrt_label_frames(self.h, n_frames, e_begin, e_end, ptr(pos), ptr(dirs), C.byref(o), ptr(tissue_dev), ptr(interface_dev), ptr(crossings_dev)))
 
+    def transmit_frames(self, pos=None, dirs=None, *, mode="total", rule="traced", start_offset=None, e_begin=0, e_end=None, n_frames=None, transmit_dev=None,
+                        reflect_dev=None, crossings_dev=None):
+        """mcrt_transmit_frames: the tracer's intensity carried along the central beam of every scan-line.  pos / dirs and the scan-line
+        range as label_frames.  Each output is a device pointer or None: transmit float32 [F][ne][R] (the fraction of the emitted
+        intensity that arrives at a row), reflect float32 [F][ne][R] (what the boundary in a row turns back, 0 elsewhere), crossings
+        uint32 [F][ne] (label_frames' own)"""
+        e_end = self.params.n_elements if e_end is None else e_end
+        if pos is None:
+            n_frames = 1 if n_frames is None else n_frames
+        else:
+            pos, dirs, n_frames = _pose_tables("transmit_frames", pos, dirs, n_frames, self.params.n_elements)
+        o = transmit_opts_struct(mode, rule, start_offset)
+        check(self.L.mcrt_transmit_frames(self.h, n_frames, e_begin, e_end, ptr(pos), ptr(dirs), C.byref(o), ptr(transmit_dev), ptr(reflect_dev), ptr(crossings_dev)))
+
     def label_scan_convert_frames(self, tissue_dev, n_frames, n_elements, n_rows, out_dev, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         """mcrt_label_scan_convert_frames: tissue maps [n_frames][E][R] -> bytes [n_frames][out_rows][out_cols], nearest neighbour through
         scan_convert_frames' own maps; LABEL_NONE outside the sector"""
@@ -1352,6 +1389,61 @@ class Simulator:
         with self._label_pass(rule, start_offset, want_rows=False) as (F, bufs), self.ctx.temp(shape[0] * shape[1] * shape[2]) as out:
             self.ctx.label_volume_frames(bufs[0], 1, self.E, self.R, self.sweep, grid, out, radius_mm=radius_mm, total_angle=total_angle)
             return self.ctx.d2h(out, shape, np.uint8)
+
+    @contextlib.contextmanager
+    def _transmit_pass(self, mode, rule, start_offset, want_rows=True):
+        """the transmission pass of this probe, as _label_pass -> (F, [transmit_dev, reflect_dev, crossings_dev])"""
+        F = self.sweep.n_planes if self.sweep is not None else 1
+        n = F * self.E * self.R
+        with contextlib.ExitStack() as held:
+            sizes = (4 * n, 4 * n, 4 * F * self.E) if want_rows else (4 * n, 0, 0)
+            bufs = [held.enter_context(self.ctx.temp(size)) if size else None for size in sizes]
+            pos, dirs = (self.sweep_pos, self.sweep_dir) if self.sweep is not None else (None, None)
+            self.ctx.transmit_frames(pos, dirs, mode=mode, rule=rule, start_offset=start_offset, transmit_dev=bufs[0], reflect_dev=bufs[1], crossings_dev=bufs[2])
+            yield F, bufs
+
+    def transmission(self, mode="total", rule="traced", start_offset=None, picture=True, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
+        """the acoustic ground truth of this probe's pictures -> dict(transmit float32 [E][R], reflect float32 [E][R], crossings uint32 [E],
+        picture float32 [out_rows][out_cols] or None): the fraction of the emitted intensity that arrives at every scan-line sample (the
+        shadow behind bone, the enhancement behind fluid), the fraction the boundary in a sample turns back, boundaries per scan-line as
+        labels(), and `transmit` scan-converted like the float picture (mcrt_scan_convert_frames: 0 outside the sector;
+        labels()["picture"] == LABEL_NONE is the mask).  Deterministic: it depends on neither seed, samples nor texture.  The probe is
+        labels()' own; with sweep= the arrays gain a leading axis of the K planes and there is no sector picture: use
+        transmission_volume()."""
+        with self._transmit_pass(mode, rule, start_offset) as (F, bufs):
+            lead = (F,) if self.sweep is not None else ()
+            out = dict(transmit=self.ctx.d2h(bufs[0], lead + (self.E, self.R), np.float32), reflect=self.ctx.d2h(bufs[1], lead + (self.E, self.R), np.float32),
+                       crossings=self.ctx.d2h(bufs[2], lead + (self.E,), np.uint32), picture=None)
+            if picture and self.sweep is None:
+                with self.ctx.temp(out_rows * out_cols * 4) as pic_dev:
+                    self.ctx.scan_convert_frames(bufs[0], 1, self.E, self.R, pic_dev, radius_mm=radius_mm, total_angle=total_angle, out_rows=out_rows, out_cols=out_cols)
+                    out["picture"] = self.ctx.d2h(pic_dev, (out_rows, out_cols), np.float32)
+            return out
+
+    def transmission_volume(self, grid, mode="total", rule="traced", start_offset=None, radius_mm=30.0, total_angle=DEFAULT_ANGLE):
+        """`transmit` at every point of grid, float32 [nw][nv][nu]: the transmission of volume()'s voxels, through mcrt_volume_frames (sweep= only)"""
+        if self.sweep is None:
+            raise RuntimeError("transmission_volume() needs Simulator(sweep=...)")
+        shape = (grid.nw, grid.nv, grid.nu)
+        with self._transmit_pass(mode, rule, start_offset, want_rows=False) as (F, bufs), self.ctx.temp(shape[0] * shape[1] * shape[2] * 4) as out:
+            self.ctx.volume_frames(bufs[0], 1, self.E, self.R, self.sweep, grid, out, radius_mm=radius_mm, total_angle=total_angle)
+            return self.ctx.d2h(out, shape, np.float32)
+
+    def freehand_transmission(self, pos, dirs, grid, mode="total", rule="traced", start_offset=None, counts=False, row_mm=None, unit_mm=10.0, **opts):
+        """the transmission of freehand()'s volume: the transmission pass over the F poses pos / dirs [F][E][3], then mcrt_recon_frames in its
+        mean mode with freehand()'s defaults -> host: float32 [nw][nv][nu]; with counts=True (voxels, sample counts uint32).  opts: the
+        keywords of recon_opts_struct.  There is no frame_id (nothing is random); it raises under compound=, sweep= or elevation= as
+        freehand_labels() does, and takes at most 1024 poses per pass."""
+        if self.steers is not None or self.sweep is not None or self.elevation:
+            raise RuntimeError("freehand_transmission() does not combine with compound=, sweep= or elevation=")
+        pos, dirs, F = _pose_tables("freehand_transmission", np.asarray(pos), np.asarray(dirs), None, self.E)
+        shape = (grid.nw, grid.nv, grid.nu)
+        n = shape[0] * shape[1] * shape[2]
+        with self.ctx.temp(F * self.E * self.R * 4) as stack_dev, self.ctx.temp(n * 4) as out, self.ctx.temp(n * 4) as cnt:
+            self.ctx.transmit_frames(pos, dirs, mode=mode, rule=rule, start_offset=start_offset, transmit_dev=stack_dev)
+            self.ctx.recon_frames(stack_dev, pos, dirs, F, self.E, self.R, grid, out, count_dev=cnt if counts else None, row_mm=row_mm, unit_mm=unit_mm, **opts)
+            vox = self.ctx.d2h(out, shape, np.float32)
+            return (vox, self.ctx.d2h(cnt, shape, np.uint32)) if counts else vox
 
     def bmode(self, frame_id=0, **display):
         """trace -> convolve -> envelope -> mcrt_bmode_frames -> host: the displayed 8-bit frame, uint8 [out_rows][out_cols].

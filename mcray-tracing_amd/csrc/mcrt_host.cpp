@@ -7,6 +7,7 @@
 // Plain C++ with no HIP in it: tests/test_host_sanitize.py compiles this file by itself under ASan + UBSan.
 #include "../../include/mcrt.h"
 #include "mcrt_internal.h"
+#include "mcrt_transmit.h"
 
 #include <algorithm>
 #include <cmath>
@@ -750,6 +751,21 @@ extern "C" int mcrt_recon_transform(const mcrt_volume_grid *g, double unit_mm, f
         if (!std::isfinite(fb[i])) return mcrt::set_error(MCRT_ERR_INVALID, "%s: grid: entry %d of b is no finite float (%g)", fn, i, (double)fb[i]);
     for (int i = 0; i < 9; i++) A[i] = fa[i];
     for (int i = 0; i < 3; i++) b[i] = fb[i];
+    return MCRT_OK;
+}
+
+// ---- acoustic ground truth (the contract is in include/mcrt.h): the defaults, and the boundary rule k_transmit applies (mcrt_transmit.h) ----
+extern "C" int mcrt_default_transmit_opts(mcrt_transmit_opts *o)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_transmit_opts: null options");
+    o->mode = MCRT_TRANSMIT_TOTAL; o->rule = MCRT_LABEL_TRACED; o->start_offset = -1.0f;
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_transmit_boundary(float z_before, float z_after, float inc, float intensity, float *i_refl, float *i_refr)
+{
+    if (!i_refl || !i_refr) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_transmit_boundary: null %s", i_refl ? "i_refr" : "i_refl");
+    mcrt::transmit_boundary(z_before, z_after, inc, intensity, *i_refl, *i_refr);
     return MCRT_OK;
 }
 

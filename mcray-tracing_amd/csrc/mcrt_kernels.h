@@ -17,6 +17,7 @@
 //   mcrt_noise.hip   k_noise (receiver noise: mcrt_noise_frames; its peaks are k_bmode_peak's)
 //   mcrt_recon.hip   k_recon_splat, k_recon_resolve (freehand 3-D reconstruction: mcrt_recon_frames)
 //   mcrt_label.hip   k_label (ground-truth label maps: mcrt_label_frames), k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames)
+//   mcrt_transmit.hip k_transmit (acoustic ground truth: mcrt_transmit_frames; the boundary rule it shares with the host is mcrt_transmit.h)
 //   mcrt_label3d.hip k_recon_label_splat, k_recon_label_resolve (a freehand label volume by majority vote: mcrt_recon_label_frames),
 //                    k_render_label (the label of what a rendering shows: mcrt_render_label_frames)
 //   mcrt_scene.hip   k_tris_by_id, k_expand_tris; the probes k_math_probe, k_verify_div, k_philox_probe
@@ -256,6 +257,17 @@ struct LabelArgs {
     float Ls;                           // the beam's length factor: (float)(2.0 * depth_cm)
 };
 
+// k_transmit (mcrt_transmit_frames): beside these, the FrameArgs of k_label and in it the material table (mats), freq and row_dt; stack_ovf is
+// sized by transmit_stack_entries() and transmit_blocks
+struct TransmitArgs {
+    float *transmit;                    // [F][ne][R] or null: the fraction of the emitted intensity that arrives at a row
+    float *reflect;                     // [F][ne][R] or null: what the shallowest boundary of a row turns back, 0 elsewhere
+    uint32_t *crossings;                // [F][ne] or null
+    uint32_t rule;                      // MCRT_LABEL_TRACED / MCRT_LABEL_GEOMETRIC
+    uint32_t mode;                      // MCRT_TRANSMIT_TOTAL / MCRT_TRANSMIT_BOUNDARIES
+    float Ls;                           // the beam's length factor: (float)(2.0 * depth_cm)
+};
+
 // k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames): the tissue maps [F][K][E][R] -> bytes [F][n] through the float
 // calls' own maps (map_plane null: one plane, K = 1)
 struct LabelGatherArgs {
@@ -323,6 +335,9 @@ uint32_t label_blocks(size_t lines);                              // workgroups 
 uint32_t label_stack_entries();
 hipError_t launch_label(const FrameArgs &a, const LabelArgs &l, hipStream_t st);
 hipError_t launch_label_gather(const LabelGatherArgs &a, hipStream_t st);
+uint32_t transmit_blocks(size_t lines);                           // workgroups of a k_transmit launch over `lines` beams (sizes the overflow stacks)
+uint32_t transmit_stack_entries();
+hipError_t launch_transmit(const FrameArgs &a, const TransmitArgs &l, hipStream_t st);
 hipError_t launch_blocks_to_frames(const float *blocks, float *frames, uint32_t F, uint32_t E, uint32_t R, uint32_t G, const uint32_t *off /*[G+1]*/, hipStream_t st);   // at most 64 ranks
 hipError_t launch_transpose(const float *in, float *out, uint32_t E, uint32_t R, hipStream_t st);
 hipError_t launch_math_probe(int op, const double *x, const double *y, double *out, uint32_t n, hipStream_t st);

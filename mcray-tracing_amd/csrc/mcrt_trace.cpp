@@ -499,8 +499,49 @@ extern "C" int mcrt_default_label_opts(mcrt_label_opts *o)
     return MCRT_OK;
 }
 
-// Everything is checked before anything is staged or launched.  k_label walks with the lane walk's steps, so its traversal stack is sized
-// as the traced pass sizes its own: label_stack_entries() in LDS, the tree's worst case beyond that in the context's overflow array.
+// The two walks of the central beams (mcrt_label_frames, mcrt_transmit_frames) share their conditions and their prologue.  Everything is
+// checked before anything is staged or launched.
+struct BeamWalk { uint32_t n_frames, e0, e1; const float *pos, *dir; uint32_t rule; float start_offset; bool any_output; };
+static int beam_walk_check(mcrt_ctx *c, const char *fn, const BeamWalk &w)
+{
+    if (!c->scene.have) return set_error(MCRT_ERR_INVALID, "%s: no scene uploaded", fn);
+    if ((w.pos == nullptr) != (w.dir == nullptr)) return set_error(MCRT_ERR_INVALID, "%s: pos and dir go together (null %s)", fn, w.pos ? "dir" : "pos");
+    if (!w.pos) {
+        if (!c->d_pos) return set_error(MCRT_ERR_INVALID, "%s: no transducer set", fn);
+        if (c->n_el != c->p.n_elements) return set_error(MCRT_ERR_INVALID, "%s: transducer has %u elements but params say %u", fn, c->n_el, c->p.n_elements);
+        if (w.n_frames != 1) return set_error(MCRT_ERR_INVALID, "%s: the context's transducer is one pose: n_frames must be 1 (%u)", fn, w.n_frames);
+    }
+    if (w.e0 >= w.e1 || w.e1 > c->p.n_elements) return set_error(MCRT_ERR_INVALID, "%s: scan-line range [%u,%u) invalid for %u elements", fn, w.e0, w.e1, c->p.n_elements);
+    if (!w.any_output) return set_error(MCRT_ERR_INVALID, "%s: no output asked for", fn);
+    if (w.rule != MCRT_LABEL_TRACED && w.rule != MCRT_LABEL_GEOMETRIC) return set_error(MCRT_ERR_INVALID, "%s: unknown rule %u", fn, w.rule);
+    if (!std::isfinite(w.start_offset) || w.start_offset == 0.0f) return set_error(MCRT_ERR_INVALID, "%s: start_offset must be finite and not 0 (%g)", fn, (double)w.start_offset);
+    if (w.n_frames == 0) return set_error(MCRT_ERR_INVALID, "%s: n_frames must be 1..1024", fn);
+    if (w.n_frames > 1024) return set_error(MCRT_ERR_LIMIT, "%s: n_frames must be 1..1024 (%u)", fn, w.n_frames);
+    return MCRT_OK;
+}
+// The kernels walk with the lane walk's steps, so their traversal stack is sized as the traced pass sizes its own: lds_part entries in LDS,
+// the tree's worst case beyond that in the context's overflow array (blocks workgroups of 64 lanes).  Stages the pose tables and fills what
+// the kernels read of a FrameArgs (mcrt_kernels.h: LabelArgs, TransmitArgs).
+static int beam_walk_args(mcrt_ctx *c, const BeamWalk &w, uint32_t blocks, uint32_t lds_part, mcrt::FrameArgs &a)
+{
+    const size_t ovf = c->scene.bvh4.max_stack > lds_part ? (size_t)(c->scene.bvh4.max_stack - lds_part) * blocks * 64 : 0;
+    if (ovf > c->label_ovf.cap) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(c->label_ovf.alloc(ovf)); }      // (as ensure_work: an earlier pass may run on a stream the context has left)
+    const float *dev[2] = { w.pos, w.dir };
+    if (w.pos) MCRT_TRY(mcrt::stage_poses(c, (size_t)w.n_frames * c->p.n_elements, dev));
+    if (c->scene.update_pending && c->scene.update_stream != c->stream) HIP_TRY(hipStreamWaitEvent(c->stream, c->scene.ev_update, 0));   // a scene update issued on another stream
+    memset(&a, 0, sizeof a);
+    a.nodes_walk = c->scene.d_nodes_walk; a.tris = c->scene.d_tris; a.tris_id = c->scene.d_tris_id; a.meshes = c->scene.d_meshes; a.mats = c->scene.d_mats; a.n_nodes = c->scene.bvh4.n_nodes;
+    a.n_mat = c->scene.n_mat; a.n_mesh = c->scene.n_mesh; a.start_mat = c->scene.start_mat; a.pad_abs = c->scene.bvh.pad_abs;
+    a.sx = c->scene.spacing[0]; a.sy = c->scene.spacing[1]; a.sz = c->scene.spacing[2];
+    a.el_pos = w.pos ? dev[0] : c->d_pos; a.el_dir = w.pos ? dev[1] : c->d_dir; a.pose_stride = w.pos ? c->p.n_elements : 0u;
+    a.e_begin = w.e0; a.ne_frame = w.e1 - w.e0; a.ne = (w.e1 - w.e0) * w.n_frames;
+    a.row_thr = c->tab.d_row_thr; a.R = c->p.n_rows; a.thr_end = c->tab.thr_end; a.inv_row_dt = 1.0 / c->c.row_dt_us; a.row_dt = c->c.row_dt_us;
+    a.max_travel = c->c.max_travel_us; a.sos_d = (double)c->p.speed_of_sound; a.freq = c->p.frequency;
+    a.offs = w.start_offset < 0.0f ? c->p.ray_start_offset : w.start_offset;
+    a.stack_ovf = c->label_ovf; a.error_flag = c->d_error;
+    return MCRT_OK;
+}
+
 extern "C" int mcrt_label_frames(mcrt_ctx *c, uint32_t n_frames, uint32_t e0, uint32_t e1, const float *pos, const float *dir, const mcrt_label_opts *o,
                                  uint8_t *tissue_dev, int32_t *interface_dev, uint32_t *crossings_dev)
 {
@@ -509,39 +550,35 @@ extern "C" int mcrt_label_frames(mcrt_ctx *c, uint32_t n_frames, uint32_t e0, ui
     mcrt_label_opts d;
     mcrt_default_label_opts(&d);
     if (!o) o = &d;
-    if (!c->scene.have) return set_error(MCRT_ERR_INVALID, "%s: no scene uploaded", fn);
-    if ((pos == nullptr) != (dir == nullptr)) return set_error(MCRT_ERR_INVALID, "%s: pos and dir go together (null %s)", fn, pos ? "dir" : "pos");
-    if (!pos) {
-        if (!c->d_pos) return set_error(MCRT_ERR_INVALID, "%s: no transducer set", fn);
-        if (c->n_el != c->p.n_elements) return set_error(MCRT_ERR_INVALID, "%s: transducer has %u elements but params say %u", fn, c->n_el, c->p.n_elements);
-        if (n_frames != 1) return set_error(MCRT_ERR_INVALID, "%s: the context's transducer is one pose: n_frames must be 1 (%u)", fn, n_frames);
-    }
-    if (e0 >= e1 || e1 > c->p.n_elements) return set_error(MCRT_ERR_INVALID, "%s: scan-line range [%u,%u) invalid for %u elements", fn, e0, e1, c->p.n_elements);
-    if (!tissue_dev && !interface_dev && !crossings_dev) return set_error(MCRT_ERR_INVALID, "%s: no output asked for", fn);
-    if (o->rule != MCRT_LABEL_TRACED && o->rule != MCRT_LABEL_GEOMETRIC) return set_error(MCRT_ERR_INVALID, "%s: unknown rule %u", fn, o->rule);
-    if (!std::isfinite(o->start_offset) || o->start_offset == 0.0f) return set_error(MCRT_ERR_INVALID, "%s: start_offset must be finite and not 0 (%g)", fn, (double)o->start_offset);
-    if (n_frames == 0) return set_error(MCRT_ERR_INVALID, "%s: n_frames must be 1..1024", fn);
-    if (n_frames > 1024) return set_error(MCRT_ERR_LIMIT, "%s: n_frames must be 1..1024 (%u)", fn, n_frames);
+    const BeamWalk w = { n_frames, e0, e1, pos, dir, o->rule, o->start_offset, tissue_dev || interface_dev || crossings_dev };
+    MCRT_TRY(beam_walk_check(c, fn, w));
     if (c->scene.n_mat > 254) return set_error(MCRT_ERR_LIMIT, "%s: at most 254 materials fit a tissue byte (%u)", fn, c->scene.n_mat);
-    const uint32_t lines = (e1 - e0) * n_frames, blocks = mcrt::label_blocks(lines), lds_part = mcrt::label_stack_entries();
-    const size_t ovf = c->scene.bvh4.max_stack > lds_part ? (size_t)(c->scene.bvh4.max_stack - lds_part) * blocks * 64 : 0;
-    if (ovf > c->label_ovf.cap) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(c->label_ovf.alloc(ovf)); }      // (as ensure_work: an earlier pass may run on a stream the context has left)
-    const float *dev[2] = { pos, dir };
-    if (pos) MCRT_TRY(mcrt::stage_poses(c, (size_t)n_frames * c->p.n_elements, dev));
-    if (c->scene.update_pending && c->scene.update_stream != c->stream) HIP_TRY(hipStreamWaitEvent(c->stream, c->scene.ev_update, 0));   // a scene update issued on another stream
     mcrt::FrameArgs a;
-    memset(&a, 0, sizeof a);
-    a.nodes_walk = c->scene.d_nodes_walk; a.tris = c->scene.d_tris; a.tris_id = c->scene.d_tris_id; a.meshes = c->scene.d_meshes; a.n_nodes = c->scene.bvh4.n_nodes;
-    a.n_mat = c->scene.n_mat; a.n_mesh = c->scene.n_mesh; a.start_mat = c->scene.start_mat; a.pad_abs = c->scene.bvh.pad_abs;
-    a.sx = c->scene.spacing[0]; a.sy = c->scene.spacing[1]; a.sz = c->scene.spacing[2];
-    a.el_pos = pos ? dev[0] : c->d_pos; a.el_dir = pos ? dev[1] : c->d_dir; a.pose_stride = pos ? c->p.n_elements : 0u;
-    a.e_begin = e0; a.ne_frame = e1 - e0; a.ne = lines;
-    a.row_thr = c->tab.d_row_thr; a.R = c->p.n_rows; a.thr_end = c->tab.thr_end; a.inv_row_dt = 1.0 / c->c.row_dt_us;
-    a.max_travel = c->c.max_travel_us; a.sos_d = (double)c->p.speed_of_sound;
-    a.offs = o->start_offset < 0.0f ? c->p.ray_start_offset : o->start_offset;
-    a.stack_ovf = c->label_ovf; a.error_flag = c->d_error;
+    MCRT_TRY(beam_walk_args(c, w, mcrt::label_blocks((size_t)(e1 - e0) * n_frames), mcrt::label_stack_entries(), a));
     mcrt::LabelArgs l;
     l.tissue = tissue_dev; l.interface = interface_dev; l.crossings = crossings_dev; l.rule = o->rule; l.Ls = (float)(2.0 * c->p.depth_cm);
     HIP_TRY(mcrt::launch_label(a, l, c->stream));
+    return MCRT_OK;
+}
+
+// ---- acoustic ground truth (the contract is in include/mcrt.h; mcrt_default_transmit_opts and mcrt_transmit_boundary are host code: mcrt_host.cpp) ----
+extern "C" int mcrt_transmit_frames(mcrt_ctx *c, uint32_t n_frames, uint32_t e0, uint32_t e1, const float *pos, const float *dir, const mcrt_transmit_opts *o,
+                                    float *transmit_dev, float *reflect_dev, uint32_t *crossings_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_transmit_frames";
+    mcrt_transmit_opts d;
+    mcrt_default_transmit_opts(&d);
+    if (!o) o = &d;
+    const BeamWalk w = { n_frames, e0, e1, pos, dir, o->rule, o->start_offset, transmit_dev || reflect_dev || crossings_dev };
+    MCRT_TRY(beam_walk_check(c, fn, w));
+    if (o->mode != MCRT_TRANSMIT_TOTAL && o->mode != MCRT_TRANSMIT_BOUNDARIES) return set_error(MCRT_ERR_INVALID, "%s: unknown mode %u", fn, o->mode);
+    if (((uintptr_t)transmit_dev | (uintptr_t)reflect_dev | (uintptr_t)crossings_dev) & 3u)
+        return set_error(MCRT_ERR_INVALID, "%s: %s is not aligned to its 4-byte elements", fn, ((uintptr_t)transmit_dev & 3u) ? "transmit_dev" : ((uintptr_t)reflect_dev & 3u) ? "reflect_dev" : "crossings_dev");
+    mcrt::FrameArgs a;
+    MCRT_TRY(beam_walk_args(c, w, mcrt::transmit_blocks((size_t)(e1 - e0) * n_frames), mcrt::transmit_stack_entries(), a));
+    mcrt::TransmitArgs l;
+    l.transmit = transmit_dev; l.reflect = reflect_dev; l.crossings = crossings_dev; l.rule = o->rule; l.mode = o->mode; l.Ls = (float)(2.0 * c->p.depth_cm);
+    HIP_TRY(mcrt::launch_transmit(a, l, c->stream));
     return MCRT_OK;
 }

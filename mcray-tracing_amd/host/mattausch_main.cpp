@@ -6,6 +6,7 @@
 //                   [--sweep K --sweep-step-deg D [--sweep-pivot-mm P] (--cplane-mm Y | --sagittal-mm X | --render DX,DY,DZ ...)]
 //                   [--render DX,DY,DZ --render-box-mm X0,Y0,Z0,X1,Y1,Z1 --render-voxel-mm P [--render-mode mip|mean|surface] [--render-size NX,NY]]
 //                   [--labels FILE.pgm [--label-rule traced|geometric] [--label-offset X]] [--render-labels FILE.pgm] [--freehand-labels FILE.raw]
+//                   [--transmission FILE.pgm [--transmission-mode total|boundaries] [--transmission-db X]]
 //                   [--speckle N [--speckle-q0 X] [--speckle-rho X] [--speckle-lambda X]]
 //                   [--noise-db X | --noise-sigma X [--noise-seed N] [--dead-elements a,b,c]]
 //                   [--freehand N --freehand-step-mm D [--freehand-fan-deg A] --freehand-box-mm X0,Y0,Z0,X1,Y1,Z1 --freehand-voxel-mm P --freehand-out FILE.raw
@@ -80,7 +81,14 @@
 // writes the ground truth of the rendered view: the material of the voxel every pixel shows (mcrt_render_label_frames through the
 // rendering's depth buffer and the label block of the box), 255 where the ray saw nothing -- every pixel of --render-mode mean.
 // --label-rule and --label-offset are taken with either as with --labels.
+// --transmission FILE.pgm writes the acoustic ground truth of the picture: how much of the emitted intensity ARRIVES under every pixel -- the
+// shadow behind bone and gas, the enhancement behind fluid --, the tracer's own attenuation and impedance rule carried along the central beam
+// of every scan-line (mcrt_transmit_frames) and scan-converted like the float picture (mcrt_scan_convert_frames; 0 outside the sector).  The
+// 8-bit grey is made here: min(max(T, 0), 1) * 255 + 0.5, or with --transmission-db X the decibels 10 log10 T over a range of X dB,
+// T > 0 ? clamp((10 log10 T + X) / X) * 255 + 0.5 : 0.  --transmission-mode boundaries leaves the attenuation out (the losses at the
+// boundaries alone); --label-rule and --label-offset are taken as with --labels.  It does not combine with --sweep.
 #include "mcrt_host.hpp"
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -123,6 +131,9 @@ int main(int argc, char **argv)
     const char *render_dir = nullptr, *render_box = nullptr, *render_voxel = nullptr, *render_mode = nullptr, *render_size = nullptr;   // the options as given
     const char *labels_file = nullptr, *label_rule = nullptr, *label_offset = nullptr, *render_labels = nullptr, *freehand_labels = nullptr;
     mcrt_label_opts lopts; mcrt_default_label_opts(&lopts);
+    const char *transmission_file = nullptr, *transmission_mode = nullptr, *transmission_db = nullptr;   // the options as given
+    mcrt_transmit_opts topts; mcrt_default_transmit_opts(&topts);
+    float transmission_range_db = 0.0f;               // 0: the linear grey
     const char *speckle_n = nullptr, *speckle_q0 = nullptr, *speckle_rho = nullptr, *speckle_lambda = nullptr;   // the options as given
     mcrt_speckle_opts sopts; mcrt_default_speckle_opts(&sopts);
     const char *noise_db = nullptr, *noise_sigma = nullptr, *noise_seed = nullptr, *dead_elements = nullptr;   // the options as given
@@ -161,6 +172,9 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--labels") && i + 1 < argc) labels_file = argv[++i];
             else if (!std::strcmp(argv[i], "--render-labels") && i + 1 < argc) render_labels = argv[++i];
             else if (!std::strcmp(argv[i], "--freehand-labels") && i + 1 < argc) freehand_labels = argv[++i];
+            else if (!std::strcmp(argv[i], "--transmission") && i + 1 < argc) transmission_file = argv[++i];
+            else if (!std::strcmp(argv[i], "--transmission-mode") && i + 1 < argc) transmission_mode = argv[++i];
+            else if (!std::strcmp(argv[i], "--transmission-db") && i + 1 < argc) transmission_db = argv[++i];
             else if (!std::strcmp(argv[i], "--label-rule") && i + 1 < argc) label_rule = argv[++i];
             else if (!std::strcmp(argv[i], "--label-offset") && i + 1 < argc) label_offset = argv[++i];
             else if (!std::strcmp(argv[i], "--speckle") && i + 1 < argc) speckle_n = argv[++i];
@@ -267,7 +281,18 @@ int main(int argc, char **argv)
             else { cut.origin_mm[0] = cut_mm; cut.origin_mm[1] = transducer_radius_cm * 10.0; cut.origin_mm[2] = -(400 - 1) * pitch / 2.0; cut.du_mm[2] = pitch; cut.dv_mm[1] = pitch; cut.nu = 400; cut.nv = 500; }
             if (!render_dir) cut.nw = 1;
         }
-        if (!labels_file && !render_labels && !freehand_labels && (label_rule || label_offset)) throw std::invalid_argument(std::string(label_rule ? "--label-rule" : "--label-offset") + " needs --labels");
+        if (!transmission_file && (transmission_mode || transmission_db)) throw std::invalid_argument(std::string(transmission_mode ? "--transmission-mode" : "--transmission-db") + " needs --transmission");
+        if (transmission_file && sweep_given) throw std::invalid_argument("--transmission does not combine with --sweep: it is the sector's picture");
+        if (transmission_mode) {
+            if (!std::strcmp(transmission_mode, "total")) topts.mode = MCRT_TRANSMIT_TOTAL;
+            else if (!std::strcmp(transmission_mode, "boundaries")) topts.mode = MCRT_TRANSMIT_BOUNDARIES;
+            else throw std::invalid_argument("--transmission-mode takes total or boundaries");
+        }
+        if (transmission_db) {
+            transmission_range_db = (float)std::atof(transmission_db);
+            if (!(std::isfinite(transmission_range_db) && transmission_range_db > 0.0f)) throw std::invalid_argument("--transmission-db takes a finite range > 0");
+        }
+        if (!labels_file && !render_labels && !freehand_labels && !transmission_file && (label_rule || label_offset)) throw std::invalid_argument(std::string(label_rule ? "--label-rule" : "--label-offset") + " needs --labels");
         if (label_rule) {
             if (!std::strcmp(label_rule, "traced")) lopts.rule = MCRT_LABEL_TRACED;
             else if (!std::strcmp(label_rule, "geometric")) lopts.rule = MCRT_LABEL_GEOMETRIC;
@@ -429,6 +454,18 @@ int main(int argc, char **argv)
             rf_image.labels(transducer, &lopts);
             if (sweep_given) write_pgm(labels_file, cut.nu, cut.nv, rf_image.label_volume(cut));
             else write_pgm(labels_file, 500, 400, rf_image.label_picture());
+        }
+        if (transmission_file) {   // how much sound gets to every pixel of that picture
+            topts.rule = lopts.rule; topts.start_offset = lopts.start_offset;
+            rf_image.transmission(transducer, &topts);
+            const std::vector<float> T = rf_image.transmission_picture();
+            std::vector<unsigned char> grey(T.size());
+            for (size_t i = 0; i < T.size(); i++) {
+                float g = T[i] > 0.0f ? std::min(T[i], 1.0f) : 0.0f;      // min(max(T, 0), 1), a NaN black
+                if (transmission_db) g = T[i] > 0.0f ? std::min(std::max((10.0f * std::log10(T[i]) + transmission_range_db) / transmission_range_db, 0.0f), 1.0f) : 0.0f;
+                grey[i] = (unsigned char)(g * 255.0f + 0.5f);
+            }
+            write_pgm(transmission_file, 500, 400, grey);
         }
         if (argc > 5) {   // the last frame's RF image after main.cpp:146-147, row-major [465][512] float32 (for the parity test)
             const auto img = sweep_given ? rf_image.view_intensities((uint32_t)sweep_planes / 2u)

@@ -695,7 +695,7 @@ public:
 
     rf_image(double radius_mm, double angle_rad, std::shared_ptr<device> dev_ = nullptr)
         : dev(dev_ ? std::move(dev_) : default_device()), radius_mm(radius_mm), angle(angle_rad), host((size_t)columns * max_rows, 0.0f),
-          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev)
+          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev), sound(dev)
     {
         std::cout << "rf_image: " << max_rows << ", " << columns << std::endl;          // rfimage.h:30
         rf.reserve(sizeof(float) * columns * max_rows);
@@ -990,6 +990,46 @@ public:
         check(mcrt_label_volume_frames(dev->ctx, label_tissue, 1, columns, max_rows, radius_mm, angle, &sweep, &grid, points.as<uint8_t>()), "mcrt_label_volume_frames");
         return download<unsigned char>(points, n);
     }
+    // acoustic ground truth (mcrt.h: mcrt_transmit_frames): the tracer's intensity carried along the central beam of every scan-line of t -- the
+    // probe and the planes are labels()' own --: the fraction of the emitted intensity that arrives at every sample, the fraction the boundary in
+    // a sample turns back, the boundaries per scan-line.  opts: null = everything (attenuation and boundaries) under the tracer's rule at the
+    // tracer's start offset.  The stack stays on the device for transmission_picture(); with several GPUs the pass runs on rank 0's context.
+    struct transmission_maps {
+        uint32_t planes = 1;                     // the leading axis of the three tables: 1, or the sweep's K
+        std::vector<float> transmit;             // [planes][columns][max_rows]  what arrives, 1 at the probe
+        std::vector<float> reflect;              // [planes][columns][max_rows]  what the boundary in a sample turns back, 0: none
+        std::vector<uint32_t> crossings;         // [planes][columns]            boundaries per scan-line; bit 31: stopped at the cap
+    };
+    template <size_t N> transmission_maps transmission(const transducer<N> &t, const mcrt_transmit_opts *opts = nullptr)
+    {
+        static_assert(N == columns, "one scan-line per transducer element");
+        const bool swept = holds == stack_of::sweep_planes;
+        const uint32_t K = swept ? sweep.n_planes : 1u;
+        shape_params();
+        const size_t lines = (size_t)K * columns, taps = lines * max_rows;
+        sound.reserve(4 * (2 * taps + lines));      // transmit, reflect, crossings
+        float *transmit_dev = sound.as<float>(), *reflect_dev = transmit_dev + taps; uint32_t *crossings_dev = sound.as<uint32_t>() + 2 * taps;
+        std::vector<float> pos, dir;
+        if (swept) { auto tab = t.swept(sweep); pos = std::move(tab.pos); dir = std::move(tab.dir); }
+        else { pos = t.pos; dir = t.dir; }
+        mcrt_ctx *tracer = dev->tracer();
+        check(mcrt_transmit_frames(tracer, K, 0, columns, pos.data(), dir.data(), opts, transmit_dev, reflect_dev, crossings_dev), "mcrt_transmit_frames");
+        check(mcrt_synchronize(tracer), "mcrt_synchronize");
+        transmission_maps m;
+        m.planes = K;
+        m.transmit = download<float>(transmit_dev, taps); m.reflect = download<float>(reflect_dev, taps); m.crossings = download<uint32_t>(crossings_dev, lines);
+        sound_planes = K;
+        return m;
+    }
+    // the transmit map of transmission() scan-converted like the float picture (mcrt_scan_convert_frames): floats [400][500], 0 outside the
+    // sector (label_picture() == MCRT_LABEL_NONE is the mask).  The reflect map has no picture: a one-row arc does not survive scan conversion
+    std::vector<float> transmission_picture()
+    {
+        if (sound_planes != 1 || holds == stack_of::sweep_planes) throw std::invalid_argument("rf_image::transmission_picture: transmission(transducer) of an unswept probe first");
+        points.reserve(sizeof(float) * 400 * 500);
+        check(mcrt_scan_convert_frames(dev->ctx, sound.as<float>(), 1, columns, max_rows, radius_mm, angle, points.as<float>(), 400, 500), "mcrt_scan_convert_frames");
+        return download<float>(points, 400 * 500);
+    }
     std::vector<unsigned char> bmode() const { return download<unsigned char>(bmode_buf, bmode_n); }   // the last postprocess(bmode_params) frame, row-major [out_rows][out_cols]
     void save_bmode(const std::string &filename) const { write_pgm(filename, bmode_cols, bmode_rows, bmode()); }   // that frame as a binary PGM, the bytes as they are
     void show() const {}   // rfimage.h:150-158 opens an OpenCV window and blocks on a key: out of scope
@@ -1110,6 +1150,8 @@ private:
     device_buffer label;                         // labels(): interface, crossings and tissue tables in one allocation; reconstruct_labels(): the tissue stack
     enum class labels_of { nothing, one_plane, sweep_planes } labelled = labels_of::nothing;   // ... what they hold (one_plane: a 1-plane sweep's too)
     uint32_t label_planes = 0; const unsigned char *label_tissue = nullptr;   // ... their leading axis (nothing: 0) and the tissue table
+    device_buffer sound;                         // transmission(): the transmit, reflect and crossings tables in one allocation
+    uint32_t sound_planes = 0;                   // ... their leading axis (nothing yet: 0)
 };
 
 }  // namespace mcrt_host
