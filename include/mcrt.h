@@ -60,7 +60,9 @@ extern "C" {
                                    + mcrt_noise_opts, mcrt_default_noise_opts, mcrt_noise_draws, mcrt_noise_frames (receiver noise: a Gaussian noise floor
                                    from integer Philox sums and a gain per transducer element, over the RF stack in place; additive);
                                    + mcrt_transmit_opts, mcrt_default_transmit_opts, mcrt_transmit_boundary, mcrt_transmit_frames (acoustic ground truth:
-                                   the intensity that arrives at every scan-line sample and what each boundary turns back; additive) */
+                                   the intensity that arrives at every scan-line sample and what each boundary turns back; additive);
+                                   + mcrt_speckle3d_opts, mcrt_default_speckle3d_opts, mcrt_speckle3d_weights, mcrt_speckle3d_tables, mcrt_speckle_volume_frames
+                                   (3-D speckle reduction: the diffusion of mcrt_speckle_frames over voxel blocks, six neighbours, a weight per axis; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -682,6 +684,64 @@ int mcrt_speckle_tables(const mcrt_speckle_opts *o, float *q0sq /* [n_iter] */, 
  * launched and out_dev is untouched.  Groups: call it on mcrt_group_root(). */
 int mcrt_speckle_frames(mcrt_ctx *ctx, const float *in_dev, uint32_t n_frames, uint32_t height, uint32_t width,
                         const mcrt_speckle_opts *o /* NULL = defaults */, float *out_dev);
+
+/* ---- 3-D speckle reduction: the rule above with six neighbours, over voxel blocks.  A surface rendering's rays cross the slices of a
+ * block, and a 2-D filter -- over the RF stack before the gather, or over the block as nw frames -- leaves the speckle between slices as it
+ * is; scanners smooth the block before they render it.  The input is a stack [n_frames][nw][nv][nu] of floats on the device, u contiguous:
+ * what mcrt_volume_frames and mcrt_recon_frames write and mcrt_render_frames (in_u8 = 0) reads.  The filter works in index space; the
+ * geometry enters only through one weight per axis, w_a = (h_min / h_a)^2 for voxel pitches h_a (mcrt_speckle3d_weights): the weight of
+ * a finite-difference second derivative along an axis of another pitch, scaled so that the finest axis has weight 1.
+ *
+ * Host tables, computed in double and rounded once (mcrt_speckle3d_tables): q0sq[t] and kq[t] are mcrt_speckle_tables' (the same floats for
+ * the same q0, rho and n_iter), and with sw = (double)wu + wv + ww
+ *   a = (float)(1 / sw),   b = (float)(1 / (4 sw^2)),   hs = (float)(1 / (2 sw)),   lamw = (float)(lambda / (2 sw))
+ * The rule, per block; everything in float, every multiply, add and divide rounded once, no fma:
+ *   0. X = |v| where v is finite, else 0
+ *   1. for t = 0 .. n_iter-1, over the whole block, iteration t reading only iteration t-1's X; neighbour indices are clamped against
+ *      the block (a clamped neighbour is the voxel itself), with X = X[l][j][i]:
+ *        dN = X[l][j-1][i] - X,  dS = X[l][j+1][i] - X,  dW = X[l][j][i-1] - X,  dE = X[l][j][i+1] - X,  dD = X[l-1][j][i] - X,  dU = X[l+1][j][i] - X
+ *        gN = wv*dN,  gS = wv*dS,  gW = wu*dW,  gE = wu*dE,  gD = ww*dD,  gU = ww*dU
+ *        S1 = ((((gN + gS) + gW) + gE) + gD) + gU
+ *        S2 = ((((gN*dN + gS*dS) + gW*dW) + gE*dE) + gD*dD) + gU*dU
+ *        m  = X + hs*S1                                           (the neighbours' weighted mean)
+ *        q2 = (a*S2 - b*(S1*S1)) / (m*m)
+ *        c  = fminf(fmaxf(1.0f / (1.0f + (q2 - q0sq[t]) * kq[t]), 0.0f), 1.0f)
+ *        D  = ((((c*gN + c[S]*gS) + c*gW) + c[E]*gE) + c*gD) + c[U]*gU      (c[S], c[E], c[U]: c at the clamped higher neighbour along v, u, w)
+ *        X' = X + lamw * D
+ * What follows: the flux across every interior face is antisymmetric (face (l, j, i) | (l, j+1, i) carries wv * c[l][j+1][i] * d one way and
+ * the same product of the negated d the other), so a block's sum is kept up to rounding; lamw * (sum of c*w over the six faces) <= lambda
+ * <= 1, so every X' is a convex combination of X and its neighbours; a constant block keeps its bits; scaling the input by a power of two
+ * scales the output exactly (while nothing overflows or goes subnormal); n_iter = 0: out = in bit for bit (step 0 is not applied).
+ * With weight = (1, 1, 0) the constants are exactly 0.5, 0.0625, 0.25 and 0.25 * lambda, every gD and gU is 0, and the block equals
+ * mcrt_speckle_frames over it as nw frames of [nv][nu] bit for bit -- NaN, +-inf, -0.0 and zero patches in the input included, while no
+ * difference of two voxels overflows.  The summation order above is what that property rests on.
+ * The axes are treated as orthogonal: the weights know the axes' lengths only.  No measurement backs the filter on a skewed grid, whose
+ * Laplacian has cross terms that this rule leaves out. */
+typedef struct { uint32_t n_iter;   /* 0..256; 0: out = in bit for bit                                            (20)        */
+                 float q0, rho, lambda;   /* as mcrt_speckle_opts, same ranges and defaults */
+                 float weight[3];   /* per axis u, v, w: each finite and >= 0, their sum > 0                      (1, 1, 1)   */
+} mcrt_speckle3d_opts;              /* 28 bytes: n_iter 0, q0 4, rho 8, lambda 12, weight 16 */
+/* the defaults above; host only.  MCRT_ERR_INVALID for a null o */
+int mcrt_default_speckle3d_opts(mcrt_speckle3d_opts *o);
+/* the weights of a grid; host only.  h_a is the length of du_mm, dv_mm, dw_mm.  An axis with a count of 1 gets weight 0 and takes no part in
+ * the minimum; every other axis gets (float)((h_min / h_a)^2), h_min the smallest of the remaining lengths (nw = 1, a cut: (.., .., 0), the
+ * 2-D filter).  MCRT_ERR_INVALID: null g or weight, a zero count, an entry of the grid that is not finite, a zero-length axis with a count
+ * above 1, all three counts 1.  On an error nothing is written */
+int mcrt_speckle3d_weights(const mcrt_volume_grid *g, float weight[3]);
+/* the tables above; host only.  q0sq and kq may be null when n_iter == 0.  MCRT_ERR_INVALID: null o, q0sq, kq or k, what mcrt_speckle_tables
+ * refuses of q0, rho and lambda, a weight that is negative or not finite, a sum of weights that is not > 0, one of the four constants
+ * not finite or 0;  MCRT_ERR_LIMIT: n_iter > 256.  On an error nothing is written */
+int mcrt_speckle3d_tables(const mcrt_speckle3d_opts *o, float *q0sq /* [n_iter] */, float *kq /* [n_iter] */, float k[4] /* a, b, hs, lamw */);
+/* The rule above over n_frames blocks: in_dev -> out_dev, both [n_frames][nw][nv][nu] on the device.  out_dev == in_dev (in place) is
+ * allowed; any other overlap is MCRT_ERR_INVALID.  o: NULL = the defaults.  Asynchronous on the context's stream: n_iter launches of one
+ * iteration, ping-ponging between out_dev and the context's scratch (the one mcrt_convolve and mcrt_speckle_frames use, grown to the
+ * largest stack: nothing is allocated once it exists) so that the last launch lands in out_dev; in place with an odd number of launches
+ * the stack is first copied into the scratch.  The weights, the constants and the iteration's floats are kernel arguments.  n_iter == 0:
+ * a device copy when the buffers differ, nothing otherwise.  MCRT_ERR_INVALID: null ctx, in_dev or out_dev, a zero n_frames, nu, nv or nw,
+ * options that mcrt_speckle3d_tables refuses, buffers that overlap without being the same;  MCRT_ERR_LIMIT: n_iter > 256, nu, nv or nw >=
+ * 2^24, a stack of 2^31 floats or more.  On an error nothing is launched and out_dev is untouched.  Groups: call it on mcrt_group_root(). */
+int mcrt_speckle_volume_frames(mcrt_ctx *ctx, const float *in_dev, uint32_t n_frames, uint32_t nu, uint32_t nv, uint32_t nw,
+                               const mcrt_speckle3d_opts *o /* NULL = defaults */, float *out_dev);
 
 /* ---- receiver noise: the noise floor of the receive chain and the gain of every transducer element.  The reference has neither: its RF
  * images hold echoes and exact zeros, so no gain finds a penetration depth and no element is weak or dead.  The stage works on the RF stack

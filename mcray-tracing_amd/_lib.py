@@ -106,6 +106,11 @@ class SpeckleOpts(C.Structure):
     _fields_ = [("n_iter", C.c_uint32), ("q0", C.c_float), ("rho", C.c_float), ("lambda_", C.c_float)]
 
 
+class Speckle3dOpts(C.Structure):
+    """mcrt_speckle3d_opts (include/mcrt.h): 28 bytes"""
+    _fields_ = [("n_iter", C.c_uint32), ("q0", C.c_float), ("rho", C.c_float), ("lambda_", C.c_float), ("weight", C.c_float * 3)]
+
+
 class ReconOpts(C.Structure):
     """mcrt_recon_opts (include/mcrt.h): 20 bytes"""
     _fields_ = [("mode", C.c_uint32), ("value_max", C.c_float), ("fill_radius", C.c_uint32), ("fill_min", C.c_uint32), ("empty", C.c_float)]
@@ -128,7 +133,7 @@ SEGMENT_DTYPE = np.dtype([("from", "<f4", 3), ("to", "<f4", 3), ("dir", "<f4", 3
                           ("distance_traveled", "<f8"), ("media", "<i4"), ("tri", "<i4")])
 assert NODE_DTYPE.itemsize == 64 and SEGMENT_DTYPE.itemsize == 64 and C.sizeof(BvhNode) == 64 and C.sizeof(BmodeParams) == 48 and C.sizeof(Focus) == 40 and C.sizeof(Compound) == 68 and C.sizeof(CompoundOpts) == 72
 assert C.sizeof(Sweep) == 12 and C.sizeof(VolumeGrid) == 112 and C.sizeof(LabelOpts) == 8 and C.sizeof(RenderView) == 64 and C.sizeof(RenderOpts) == 32 and C.sizeof(SpeckleOpts) == 16 and C.sizeof(NoiseOpts) == 16 and C.sizeof(ReconOpts) == 20
-assert C.sizeof(ReconLabelOpts) == 12 and C.sizeof(TransmitOpts) == 12
+assert C.sizeof(ReconLabelOpts) == 12 and C.sizeof(TransmitOpts) == 12 and C.sizeof(Speckle3dOpts) == 28 and Speckle3dOpts.weight.offset == 16
 
 # every symbol include/mcrt.h declares (tests/test_abi.py checks the .so exports each one)
 SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create", "mcrt_destroy", "mcrt_set_stream",
@@ -148,6 +153,7 @@ SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create"
            "mcrt_default_transmit_opts", "mcrt_transmit_boundary", "mcrt_transmit_frames",
            "mcrt_default_render_opts", "mcrt_render_view_for_grid", "mcrt_render_frames",
            "mcrt_default_speckle_opts", "mcrt_speckle_tables", "mcrt_speckle_frames",
+           "mcrt_default_speckle3d_opts", "mcrt_speckle3d_weights", "mcrt_speckle3d_tables", "mcrt_speckle_volume_frames",
            "mcrt_default_noise_opts", "mcrt_noise_draws", "mcrt_noise_frames",
            "mcrt_default_recon_opts", "mcrt_recon_transform", "mcrt_recon_frames",
            "mcrt_default_recon_label_opts", "mcrt_recon_label_frames", "mcrt_render_label_frames"]
@@ -225,6 +231,10 @@ def load_library():
         "mcrt_default_speckle_opts": [C.POINTER(SpeckleOpts)],
         "mcrt_speckle_tables": [C.POINTER(SpeckleOpts), vp, vp, vp],
         "mcrt_speckle_frames": [vp, vp, u32, u32, u32, C.POINTER(SpeckleOpts), vp],
+        "mcrt_default_speckle3d_opts": [C.POINTER(Speckle3dOpts)],
+        "mcrt_speckle3d_weights": [C.POINTER(VolumeGrid), vp],
+        "mcrt_speckle3d_tables": [C.POINTER(Speckle3dOpts), vp, vp, vp],
+        "mcrt_speckle_volume_frames": [vp, vp, u32, u32, u32, u32, C.POINTER(Speckle3dOpts), vp],
         "mcrt_default_noise_opts": [C.POINTER(NoiseOpts)],
         "mcrt_noise_draws": [u32, u32, u32, u32, vp],
         "mcrt_noise_frames": [vp, vp, u32, u32, u32, u32, u32, C.POINTER(NoiseOpts), vp, vp],

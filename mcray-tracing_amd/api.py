@@ -11,7 +11,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, NoiseOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, Speckle3dOpts, NoiseOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 DEFAULT_ANGLE = 1.0471975511965976      # the sector of main.cpp:28: 60 degrees [rad]
 
@@ -328,6 +328,46 @@ def host_speckle_tables(opts=None, **kw):
     q0sq = np.zeros(n, np.float32); kq = np.zeros(n, np.float32); lam4 = np.zeros(1, np.float32)
     check(load_library().mcrt_speckle_tables(C.byref(o), ptr(q0sq), ptr(kq), ptr(lam4)))
     return q0sq, kq, np.float32(lam4[0])
+
+
+def speckle3d_opts_struct(n_iter=None, q0=None, rho=None, lambda_=None, weights=None, **kw):
+    """mcrt_speckle3d_opts from keywords over mcrt_default_speckle3d_opts: n_iter, q0, rho, the time step lambda_ (or lam, or "lambda" in a
+    dict) and weights, one per axis (u, v, w)"""
+    o = Speckle3dOpts()
+    check(load_library().mcrt_default_speckle3d_opts(C.byref(o)))
+    for k in ("lambda", "lam"):
+        if k in kw:
+            lambda_ = kw.pop(k)
+    if kw:
+        raise TypeError("unknown speckle3d options: %s" % ", ".join(sorted(kw)))
+    if n_iter is not None:
+        o.n_iter = int(n_iter)
+    for name, val in (("q0", q0), ("rho", rho), ("lambda_", lambda_)):
+        if val is not None:
+            setattr(o, name, float(val))
+    if weights is not None:
+        w = [float(x) for x in weights]
+        if len(w) != 3:
+            raise ValueError("speckle3d: weights takes one weight per axis (u, v, w), got %d" % len(w))
+        o.weight[:] = w
+    return o
+
+
+def host_speckle3d_tables(opts=None, **kw):
+    """mcrt_speckle3d_tables: the floats k_srad3 is given -> (q0sq [n_iter], kq [n_iter], k [4]: a, b, hs, lamw); opts: a Speckle3dOpts, or the
+    keywords of speckle3d_opts_struct"""
+    o = opts if opts is not None else speckle3d_opts_struct(**kw)
+    n = min(int(o.n_iter), 256)
+    q0sq = np.zeros(n, np.float32); kq = np.zeros(n, np.float32); k = np.zeros(4, np.float32)
+    check(load_library().mcrt_speckle3d_tables(C.byref(o), ptr(q0sq), ptr(kq), ptr(k)))
+    return q0sq, kq, k
+
+
+def host_speckle3d_weights(grid):
+    """mcrt_speckle3d_weights: the weights (u, v, w) of a VolumeGrid's pitches, float32 [3]: (h_min / h_a)^2, 0 for an axis of one voxel"""
+    w = np.zeros(3, np.float32)
+    check(load_library().mcrt_speckle3d_weights(C.byref(grid), ptr(w)))
+    return w
 
 
 RECON_MODES = {"mean": 0, "max": 1}
@@ -886,6 +926,14 @@ class Context(_SceneCalls):
         o = speckle_opts_struct(**opts)
         check(self.L.mcrt_speckle_frames(self.h, ptr(in_dev), n_frames, height, width, C.byref(o), ptr(in_dev if out_dev is None else out_dev)))
 
+    def speckle_volume_frames(self, in_dev, n_frames, shape, out_dev=None, **opts):
+        """mcrt_speckle_volume_frames: the diffusion of speckle_frames with six neighbours over the float voxel blocks [n_frames][nw][nv][nu]
+        (shape = (nw, nv, nu)) -> out_dev (None: in place).  opts: the keywords of speckle3d_opts_struct (n_iter, q0, rho, lambda_,
+        weights)"""
+        nw, nv, nu = shape
+        o = speckle3d_opts_struct(**opts)
+        check(self.L.mcrt_speckle_volume_frames(self.h, ptr(in_dev), n_frames, nu, nv, nw, C.byref(o), ptr(in_dev if out_dev is None else out_dev)))
+
     def recon_frames(self, stack_dev, pos, dirs, n_frames, n_elements, n_rows, grid, out_dev, count_dev=None, stats_dev=None, row_mm=None, unit_mm=10.0,
                      **opts):
         """mcrt_recon_frames: the tracked stack [n_frames][n_elements][n_rows] binned into grid's voxels (a VolumeGrid in the WORLD frame, mm)
@@ -1100,7 +1148,7 @@ class Simulator:
 
     def __init__(self, scene_data, transducer, n_samples=5, n_rows=None, device=0, seed=0x5EED, psf=None, texture=None,
                  max_depth=10, sanitize_tir=0, tex_n=256, bvh_builder="sah", elevation=False, compound=None, compound_mode="mean", compound_weights=None,
-                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0, speckle=None, noise=None):
+                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0, speckle=None, noise=None, speckle3d=None):
         """elevation=True: slice thickness.  trace() then traces the psf's elevation_size planes of the frame as one pose pass -- plane k of
         frame f with frame id f * K + k, the frame-id rule of include/mcrt.h -- and folds them into rf_dev with psf.elevation_rows();
         everything after (convolve, bmode, frame) is unchanged.
@@ -1123,7 +1171,15 @@ class Simulator:
         the ids the images were traced with, so a frame carries the same noise whatever pass it is part of.  frame() therefore returns
         noisy RF, and everything downstream (bmode, compound_image, volume, render, freehand) sees it.  The stage sits after the lateral PSF
         because receive noise is uncorrelated between scan-lines, which the PSF's lateral blur would undo; that is a modelling choice
-        that no measurement backs."""
+        that no measurement backs.
+        speckle3d=True, or a dict of the keywords of speckle3d_opts_struct (n_iter, q0, rho, lambda, weights): 3-D speckle reduction over
+        voxel blocks.  volume() and freehand() then pass their float block through mcrt_speckle_volume_frames in place on the device before
+        it is copied out, with the weights of the grid's pitches (host_speckle3d_weights(grid)) unless the dict gives weights.
+        bmode_volume() and render() gather bytes straight from the planes and have no float block to filter: under speckle3d= they
+        raise.  Without the keyword no call changes."""
+        self.speckle3d = None if speckle3d is None or speckle3d is False else ({} if speckle3d is True else dict(speckle3d))
+        if self.speckle3d is not None:
+            speckle3d_opts_struct(**self.speckle3d)         # (unknown keywords and a wrong number of weights end it here)
         if sweep is not None and (compound is not None or elevation):
             raise ValueError("sweep= does not combine with compound= or elevation=")
         if compound is not None and not 1 <= len(tuple(compound)) <= 16:
@@ -1222,6 +1278,14 @@ class Simulator:
         o = self.speckle if self.speckle is not None else speckle_opts_struct()
         self.ctx.speckle_frames(*self._stack, self.E, self.R, n_iter=o.n_iter, q0=o.q0, rho=o.rho, lambda_=o.lambda_)
 
+    def despeckle_volume(self, vox_dev, grid):
+        """mcrt_speckle_volume_frames over the float block of grid on the device, in place, with the options of speckle3d= (the defaults
+        without one); the weights are the grid's pitches' unless the options give them"""
+        o = dict(self.speckle3d or {})
+        if o.get("weights") is None:
+            o["weights"] = host_speckle3d_weights(grid)
+        self.ctx.speckle_volume_frames(vox_dev, 1, (grid.nw, grid.nv, grid.nu), **o)
+
     def add_noise(self, frame_id=0, own_peaks=False):
         """mcrt_noise_frames over the stack's images, in place, with the options of noise= (the defaults without one): the images are the
         views or planes of ONE frame (one receiver, one peak) with the ids frame_id * (images in the stack) onwards; own_peaks=True: so many
@@ -1254,13 +1318,16 @@ class Simulator:
             return self.ctx.d2h(out, (out_rows, out_cols), np.float32)
 
     def volume(self, frame_id, grid, convolve=True, envelope=True, radius_mm=30.0, total_angle=DEFAULT_ANGLE):
-        """trace -> convolve -> envelope -> mcrt_volume_frames -> host: the float voxels [nw][nv][nu] of grid, a volume or any cut (sweep= only)"""
+        """trace -> convolve -> envelope -> mcrt_volume_frames (-> despeckle_volume with speckle3d=) -> host: the float voxels [nw][nv][nu] of
+        grid, a volume or any cut (sweep= only)"""
         if self.sweep is None:
             raise RuntimeError("volume() needs Simulator(sweep=...)")
         self._run(frame_id, convolve, envelope)
         shape = (grid.nw, grid.nv, grid.nu)
         with self.ctx.temp(shape[0] * shape[1] * shape[2] * 4) as out:
             self.ctx.volume_frames(self.sweep_dev, 1, self.E, self.R, self.sweep, grid, out, radius_mm=radius_mm, total_angle=total_angle)
+            if self.speckle3d is not None:
+                self.despeckle_volume(out, grid)
             return self.ctx.d2h(out, shape, np.float32)
 
     def bmode_volume(self, frame_id, grid, **display):
@@ -1268,6 +1335,8 @@ class Simulator:
         display: the keywords of Context.bmode_volume_frames (mode, dynamic_range_db, gain_db, ref, tgc_db, radius_mm, total_angle)"""
         if self.sweep is None:
             raise RuntimeError("bmode_volume() needs Simulator(sweep=...)")
+        if self.speckle3d is not None:
+            raise RuntimeError("bmode_volume() gathers bytes straight from the planes: there is no float block for speckle3d= to filter (use volume())")
         self._run(frame_id)
         shape = (grid.nw, grid.nv, grid.nu)
         with self.ctx.temp(shape[0] * shape[1] * shape[2]) as out:
@@ -1285,6 +1354,9 @@ class Simulator:
         where the ray saw nothing (every pixel of mode "mean") or saw it outside the sweep"""
         if self.sweep is None:
             raise RuntimeError("render() needs Simulator(sweep=...)")
+        if self.speckle3d is not None:
+            raise RuntimeError("render() gathers bytes straight from the planes: there is no float block for speckle3d= to filter "
+                               "(Context.volume_frames -> speckle_volume_frames -> render_frames(in_u8=False) renders a filtered block)")
         ropts = {k: opts.pop(k) for k in ("lo", "hi", "threshold", "ramp", "opacity", "depth_cue", "t_cut") if k in opts}
         if "bmode_mode" in opts:
             opts["mode"] = opts.pop("bmode_mode")
@@ -1308,7 +1380,10 @@ class Simulator:
         """a freehand sweep and its volume: the F poses pos / dirs [F][E][3] (Transducer.poses) traced as one pose pass into a temporary stack
         -- pose f with frame id frame_id * F + f -- -> convolve (-> add_noise with noise=) -> envelope (-> despeckle with speckle=) -> mcrt_recon_frames -> host: the float
         voxels [nw][nv][nu] of grid (a VolumeGrid in the WORLD frame, mm); with counts=True (voxels, sample counts uint32 of the same shape).
-        opts: the keywords of recon_opts_struct.  It raises under compound=, sweep= or elevation=."""
+        opts: the keywords of recon_opts_struct.  It raises under compound=, sweep= or elevation=.
+        With speckle3d= the block is filtered on the device (despeckle_volume) before it is copied out.  A hole's `empty` value is then a
+        value like any other -- step 0 of the rule applies to it (|empty|, or 0 when it is not finite) and it diffuses into its
+        neighbours; counts=True still tells which voxels were empty."""
         if self.steers is not None or self.sweep is not None or self.elevation:
             raise RuntimeError("freehand() does not combine with compound=, sweep= or elevation=")
         pos, dirs, F = _pose_tables("freehand", np.asarray(pos), np.asarray(dirs), None, self.E)
@@ -1329,6 +1404,8 @@ class Simulator:
             finally:
                 self._stack = held
             self.ctx.recon_frames(stack_dev, pos, dirs, F, self.E, self.R, grid, out, count_dev=cnt if counts else None, row_mm=row_mm, unit_mm=unit_mm, **opts)
+            if self.speckle3d is not None:
+                self.despeckle_volume(out, grid)
             vox = self.ctx.d2h(out, shape, np.float32)
             return (vox, self.ctx.d2h(cnt, shape, np.uint32)) if counts else vox
 

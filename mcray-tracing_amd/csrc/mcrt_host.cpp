@@ -689,27 +689,93 @@ extern "C" int mcrt_default_speckle_opts(mcrt_speckle_opts *o)
     return MCRT_OK;
 }
 
-// in double, each float rounded once; everything is checked before anything is written
-extern "C" int mcrt_speckle_tables(const mcrt_speckle_opts *o, float *q0sq, float *kq, float *lam4)
+// what mcrt_speckle_tables and mcrt_speckle3d_tables check of n_iter, q0, rho and lambda, and the tables [n_iter] and 0.25 * lambda they share:
+// in double, each float rounded once, into a, b and l4 (the caller's own: nothing of the user's is written here)
+static int speckle_tables_checked(const char *fn, uint32_t n_iter, float q0, float rho, float lambda, const float *q0sq, const float *kq, float a[256], float b[256], float *l4)
 {
-    static const char fn[] = "mcrt_speckle_tables";
-    if (!o || !lam4) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null %s", fn, o ? "lam4" : "options");
-    if (o->n_iter > 256u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: n_iter must be 0..256 (%u)", fn, o->n_iter);
-    if (o->n_iter && (!q0sq || !kq)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null %s", fn, q0sq ? "kq" : "q0sq");
-    if (!(std::isfinite(o->q0) && o->q0 > 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: q0 must be finite and > 0 (%g)", fn, (double)o->q0);
-    if (!(std::isfinite(o->rho) && o->rho >= 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: rho must be finite and >= 0 (%g)", fn, (double)o->rho);
-    if (!(o->lambda > 0.0f && o->lambda <= 1.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: lambda must be in (0,1] (%g)", fn, (double)o->lambda);
-    float a[256], b[256];
-    const float l4 = (float)(0.25 * (double)o->lambda);
-    if (!(std::isfinite(l4) && l4 != 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: lambda is too small, 0.25 * lambda is no float above 0 (%g)", fn, (double)o->lambda);
-    for (uint32_t t = 0; t < o->n_iter; t++) {
-        const double q = (double)o->q0 * std::exp(-(double)o->rho * (double)t), q2 = q * q;
+    if (n_iter > 256u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: n_iter must be 0..256 (%u)", fn, n_iter);
+    if (n_iter && (!q0sq || !kq)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null %s", fn, q0sq ? "kq" : "q0sq");
+    if (!(std::isfinite(q0) && q0 > 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: q0 must be finite and > 0 (%g)", fn, (double)q0);
+    if (!(std::isfinite(rho) && rho >= 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: rho must be finite and >= 0 (%g)", fn, (double)rho);
+    if (!(lambda > 0.0f && lambda <= 1.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: lambda must be in (0,1] (%g)", fn, (double)lambda);
+    *l4 = (float)(0.25 * (double)lambda);
+    if (!(std::isfinite(*l4) && *l4 != 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: lambda is too small, 0.25 * lambda is no float above 0 (%g)", fn, (double)lambda);
+    for (uint32_t t = 0; t < n_iter; t++) {
+        const double q = (double)q0 * std::exp(-(double)rho * (double)t), q2 = q * q;
         a[t] = (float)q2; b[t] = (float)(1.0 / (q2 * (1.0 + q2)));
         if (!(std::isfinite(a[t]) && a[t] != 0.0f && std::isfinite(b[t]) && b[t] != 0.0f))
             return mcrt::set_error(MCRT_ERR_INVALID, "%s: q0, rho: the speckle scale of iteration %u has no finite non-zero tables (q_t^2 %g)", fn, t, q2);
     }
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_speckle_tables(const mcrt_speckle_opts *o, float *q0sq, float *kq, float *lam4)
+{
+    static const char fn[] = "mcrt_speckle_tables";
+    if (!o || !lam4) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null %s", fn, o ? "lam4" : "options");
+    float a[256], b[256], l4 = 0.0f;
+    if (const int rc = speckle_tables_checked(fn, o->n_iter, o->q0, o->rho, o->lambda, q0sq, kq, a, b, &l4)) return rc;
     for (uint32_t t = 0; t < o->n_iter; t++) { q0sq[t] = a[t]; kq[t] = b[t]; }
     *lam4 = l4;
+    return MCRT_OK;
+}
+
+// ---- 3-D speckle reduction over voxel blocks (the contract is in include/mcrt.h) ---------------------------------------
+extern "C" int mcrt_default_speckle3d_opts(mcrt_speckle3d_opts *o)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_speckle3d_opts: null options");
+    o->n_iter = 20u; o->q0 = 0.5227232f; o->rho = (float)(1.0 / 6.0); o->lambda = 0.5f;
+    o->weight[0] = o->weight[1] = o->weight[2] = 1.0f;
+    return MCRT_OK;
+}
+
+// (h_min / h_a)^2 per axis that has more than one voxel; everything is checked before anything is written
+extern "C" int mcrt_speckle3d_weights(const mcrt_volume_grid *g, float weight[3])
+{
+    static const char fn[] = "mcrt_speckle3d_weights";
+    if (!g || !weight) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null %s", fn, g ? "weight" : "grid");
+    if (g->nu == 0 || g->nv == 0 || g->nw == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: grid: zero size (%u x %u x %u)", fn, g->nu, g->nv, g->nw);
+    for (int i = 0; i < 3; i++)
+        if (!(std::isfinite(g->origin_mm[i]) && std::isfinite(g->du_mm[i]) && std::isfinite(g->dv_mm[i]) && std::isfinite(g->dw_mm[i])))
+            return mcrt::set_error(MCRT_ERR_INVALID, "%s: grid: an entry is not finite (component %d)", fn, i);
+    const double *axis[3] = { g->du_mm, g->dv_mm, g->dw_mm };
+    const uint32_t count[3] = { g->nu, g->nv, g->nw };
+    static const char *const name[3] = { "du_mm", "dv_mm", "dw_mm" };
+    if (count[0] == 1u && count[1] == 1u && count[2] == 1u) return mcrt::set_error(MCRT_ERR_INVALID, "%s: grid: nu, nv and nw are all 1: a single voxel has no neighbours", fn);
+    double h[3], h_min = HUGE_VAL;
+    for (int k = 0; k < 3; k++) {
+        h[k] = std::sqrt(axis[k][0] * axis[k][0] + axis[k][1] * axis[k][1] + axis[k][2] * axis[k][2]);
+        if (count[k] == 1u) continue;
+        if (!(std::isfinite(h[k]) && h[k] > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: grid: %s has length %g on an axis of %u voxels", fn, name[k], h[k], count[k]);
+        h_min = std::min(h_min, h[k]);
+    }
+    float w[3];
+    for (int k = 0; k < 3; k++) {
+        const double q = h_min / h[k];
+        w[k] = count[k] == 1u ? 0.0f : (float)(q * q);
+        if (!std::isfinite(w[k])) return mcrt::set_error(MCRT_ERR_INVALID, "%s: grid: the weight of %s is not finite", fn, name[k]);
+    }
+    for (int k = 0; k < 3; k++) weight[k] = w[k];
+    return MCRT_OK;
+}
+
+// in double, each float rounded once; everything is checked before anything is written
+extern "C" int mcrt_speckle3d_tables(const mcrt_speckle3d_opts *o, float *q0sq, float *kq, float k[4])
+{
+    static const char fn[] = "mcrt_speckle3d_tables";
+    if (!o || !k) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null %s", fn, o ? "k" : "options");
+    float a[256], b[256], l4 = 0.0f;
+    if (const int rc = speckle_tables_checked(fn, o->n_iter, o->q0, o->rho, o->lambda, q0sq, kq, a, b, &l4)) return rc;
+    for (int i = 0; i < 3; i++)
+        if (!(std::isfinite(o->weight[i]) && o->weight[i] >= 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: weight[%d] must be finite and >= 0 (%g)", fn, i, (double)o->weight[i]);
+    const double sw = ((double)o->weight[0] + (double)o->weight[1]) + (double)o->weight[2];
+    if (!(sw > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: weight: the sum of the weights must be > 0 (%g)", fn, sw);
+    const float c[4] = { (float)(1.0 / sw), (float)(1.0 / (4.0 * sw * sw)), (float)(1.0 / (2.0 * sw)), (float)((double)o->lambda / (2.0 * sw)) };
+    static const char *const name[4] = { "a = 1 / sw", "b = 1 / (4 sw^2)", "hs = 1 / (2 sw)", "lamw = lambda / (2 sw)" };
+    for (int i = 0; i < 4; i++)
+        if (!(std::isfinite(c[i]) && c[i] != 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: weight, lambda: %s is no finite float above 0 (sum of the weights %g)", fn, name[i], sw);
+    for (uint32_t t = 0; t < o->n_iter; t++) { q0sq[t] = a[t]; kq[t] = b[t]; }
+    for (int i = 0; i < 4; i++) k[i] = c[i];
     return MCRT_OK;
 }
 

@@ -532,6 +532,50 @@ extern "C" int mcrt_speckle_frames(mcrt_ctx *c, const float *in_dev, uint32_t n_
     return MCRT_OK;
 }
 
+// ---- 3-D speckle reduction over voxel blocks (the contract is in include/mcrt.h; the defaults, the weights and the tables are host code: mcrt_host.cpp) ----
+// mcrt_speckle_frames' scheme with one iteration per launch: launch k = 1..n_iter writes out_dev when n_iter - k is even and the scratch when
+// it is odd; in place with an odd n_iter the stack is first copied into the scratch.
+extern "C" int mcrt_speckle_volume_frames(mcrt_ctx *c, const float *in_dev, uint32_t n_frames, uint32_t nu, uint32_t nv, uint32_t nw, const mcrt_speckle3d_opts *o, float *out_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_speckle_volume_frames";
+    if (!in_dev || !out_dev) return set_error(MCRT_ERR_INVALID, "%s: null %s", fn, in_dev ? "out_dev" : "in_dev");
+    if (n_frames == 0 || nu == 0 || nv == 0 || nw == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, nu %u, nv %u, nw %u)", fn, n_frames, nu, nv, nw);
+    mcrt_speckle3d_opts d;
+    if (!o) { mcrt_default_speckle3d_opts(&d); o = &d; }
+    float q0sq[256], kq[256], k[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+    MCRT_TRY(mcrt_speckle3d_tables(o, q0sq, kq, k));
+    if (nu >= (1u << 24) || nv >= (1u << 24) || nw >= (1u << 24)) return set_error(MCRT_ERR_LIMIT, "%s: nu, nv and nw must be below 2^24 (%u x %u x %u)", fn, nu, nv, nw);
+    if ((double)n_frames * (double)nu * (double)nv * (double)nw >= 0x1p31)
+        return set_error(MCRT_ERR_LIMIT, "%s: a stack of 2^31 floats or more (%u x %u x %u x %u)", fn, n_frames, nw, nv, nu);
+    const size_t n = (size_t)n_frames * nu * nv * nw;
+    if (in_dev != out_dev && ranges_overlap(in_dev, 4 * n, out_dev, 4 * n)) return set_error(MCRT_ERR_INVALID, "%s: in_dev and out_dev overlap without being the same buffer", fn);
+    if (o->n_iter == 0u) {
+        if (in_dev != out_dev) HIP_TRY(hipMemcpyAsync(out_dev, in_dev, 4 * n, hipMemcpyDeviceToDevice, c->stream));
+        return MCRT_OK;
+    }
+    const uint32_t L = o->n_iter;
+    if (L > 1u || in_dev == out_dev) MCRT_TRY(ensure_tmp(c, n));
+    float *tmp = c->img.d_tmp;
+    const float *src = in_dev;
+    if (in_dev == out_dev && (L & 1u)) {
+        HIP_TRY(hipMemcpyAsync(tmp, in_dev, 4 * n, hipMemcpyDeviceToDevice, c->stream));
+        src = tmp;
+    }
+    for (uint32_t t = 1; t <= L; t++) {
+        mcrt::Speckle3Args a;
+        memset(&a, 0, sizeof a);
+        a.src = src; a.dst = ((L - t) & 1u) ? tmp : out_dev;
+        a.nu = nu; a.nv = nv; a.nw = nw; a.first = t == 1u ? 1u : 0u;
+        a.wu = o->weight[0]; a.wv = o->weight[1]; a.ww = o->weight[2];
+        a.a = k[0]; a.b = k[1]; a.hs = k[2]; a.lamw = k[3];
+        a.q0sq = q0sq[t - 1u]; a.kq = kq[t - 1u];
+        HIP_TRY(mcrt::launch_srad3(a, n_frames, c->stream));
+        src = a.dst;
+    }
+    return MCRT_OK;
+}
+
 // ---- receiver noise (the contract is in include/mcrt.h; the defaults and the host's draws are host code: mcrt_host.cpp) ----
 // Everything is checked before anything is enqueued; then the gain table (only when it differs from the one on the device), in SNR_DB
 // mode the peaks (memset + k_bmode_peak without TGC, a frame's n_images * E scan-lines as one image: the reduction fits unchanged), and k_noise.

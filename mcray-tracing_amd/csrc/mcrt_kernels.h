@@ -14,6 +14,7 @@
 //   mcrt_volume.hip  k_volume (volume imaging: mcrt_volume_frames, mcrt_bmode_volume_frames)
 //   mcrt_render.hip  k_render (volume rendering: mcrt_render_frames)
 //   mcrt_speckle.hip k_srad (speckle reduction: mcrt_speckle_frames)
+//   mcrt_speckle3d.hip k_srad3 (3-D speckle reduction over voxel blocks: mcrt_speckle_volume_frames)
 //   mcrt_noise.hip   k_noise (receiver noise: mcrt_noise_frames; its peaks are k_bmode_peak's)
 //   mcrt_recon.hip   k_recon_splat, k_recon_resolve (freehand 3-D reconstruction: mcrt_recon_frames)
 //   mcrt_label.hip   k_label (ground-truth label maps: mcrt_label_frames), k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames)
@@ -203,6 +204,27 @@ struct SpeckleArgs {
     float q0sq[SRAD_FUSE_MAX], kq[SRAD_FUSE_MAX];   // mcrt_speckle_tables' entries of these n iterations
 };
 
+// k_srad3 (mcrt_speckle_volume_frames): one launch carries every block of the stack [F][nw][nv][nu] through one iteration, src -> dst (two buffers)
+#ifndef SRAD3_TV            // (make variant DEFS=-DSRAD3_TV=...: the tile and the chunk are a tuning build's to change)
+#define SRAD3_TV 8          // a workgroup's tile: voxels along v ...
+#endif
+#ifndef SRAD3_TU
+#define SRAD3_TU 32         // ... and along u (contiguous); 8 x 32 x 8 was the fastest of the tiles and chunks measured
+#endif
+#ifndef SRAD3_CW
+#define SRAD3_CW 8          // the slices along w a workgroup marches its tile through
+#endif
+struct Speckle3Args {
+    const float *src;                   // [F][nw][nv][nu]
+    float *dst;                         // [F][nw][nv][nu], not src
+    uint32_t nu, nv, nw;
+    uint32_t first;                     // the call's first launch: step 0 of the contract (|v|, or 0 where v is not finite) is applied while staging
+    uint32_t tx, ty, tc;                // tiles along u and v, chunks along w (launch_srad3 fills them)
+    float wu, wv, ww;                   // the weights of the two neighbours along u, v and w
+    float a, b, hs, lamw;               // mcrt_speckle3d_tables' four constants
+    float q0sq, kq;                     // ... and its entries of this iteration
+};
+
 // k_recon_splat and k_recon_resolve (mcrt_recon_frames): the stack [F][E][R] binned into the accumulators of n = nu * nv * nw voxels, then the
 // accumulators resolved and the holes filled into out [nw][nv][nu]
 #define RECON_TU 32         // k_recon_resolve: a workgroup's tile of voxels along u (contiguous) ...
@@ -324,6 +346,7 @@ hipError_t launch_bmode(const BmodeArgs &a, hipStream_t st);
 hipError_t launch_compound(const CompoundArgs &a, bool out8, hipStream_t st);   // a.mode: the instantiation
 hipError_t launch_volume(const VolumeArgs &a, bool out8, hipStream_t st);
 hipError_t launch_render(const RenderArgs &a, bool in8, hipStream_t st);
+hipError_t launch_srad3(Speckle3Args a, uint32_t F, hipStream_t st);                // one iteration over F blocks
 hipError_t launch_srad(SpeckleArgs a, uint32_t F, uint32_t fuse, hipStream_t st);   // fuse: 2 or 4 (the instantiation); a.n <= fuse
 hipError_t launch_noise(const NoiseArgs &a, hipStream_t st);
 hipError_t launch_recon_splat(const ReconArgs &a, hipStream_t st);

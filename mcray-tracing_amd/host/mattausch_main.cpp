@@ -8,6 +8,7 @@
 //                   [--labels FILE.pgm [--label-rule traced|geometric] [--label-offset X]] [--render-labels FILE.pgm] [--freehand-labels FILE.raw]
 //                   [--transmission FILE.pgm [--transmission-mode total|boundaries] [--transmission-db X]]
 //                   [--speckle N [--speckle-q0 X] [--speckle-rho X] [--speckle-lambda X]]
+//                   [--speckle3d N [--speckle3d-q0 X] [--speckle3d-rho X] [--speckle3d-lambda X]]
 //                   [--noise-db X | --noise-sigma X [--noise-seed N] [--dead-elements a,b,c]]
 //                   [--freehand N --freehand-step-mm D [--freehand-fan-deg A] --freehand-box-mm X0,Y0,Z0,X1,Y1,Z1 --freehand-voxel-mm P --freehand-out FILE.raw
 //                    [--freehand-mode mean|max] [--freehand-fill H]]
@@ -62,6 +63,10 @@
 // --compound, the planes of --sweep, --render; rf.bin holds the filtered image too.  --speckle-q0 X is the speckle scale (0.5227232, fully
 // developed speckle), --speckle-rho X its decay per iteration (1/6), --speckle-lambda X the time step in (0, 1] (0.5); the three need
 // --speckle.  Without --speckle nothing changes.
+// --speckle3d N, with --freehand, runs N iterations (0..256) of the same diffusion with six neighbours over the --freehand-out block on the
+// device before it is written (mcrt_speckle_volume_frames), with the weights of the freehand grid's pitches (mcrt_speckle3d_weights: cubic
+// voxels, so 1 along every axis that has more than one voxel); a hole's value diffuses like any other.  --speckle3d-q0, --speckle3d-rho and
+// --speckle3d-lambda are --speckle's, for this filter; the three need --speckle3d.  Without --speckle3d nothing changes.
 // --noise-db X adds receiver noise to every RF image between the convolution and the envelope (mcrt_noise_frames): a Gaussian noise floor
 // X dB below the frame's own peak -- the views of --compound and the planes of --sweep share one receiver, hence one peak; the frames of
 // --freehand have one each --, drawn from the streams of the frame ids the images were traced with; --noise-sigma X gives the floor's
@@ -136,6 +141,8 @@ int main(int argc, char **argv)
     float transmission_range_db = 0.0f;               // 0: the linear grey
     const char *speckle_n = nullptr, *speckle_q0 = nullptr, *speckle_rho = nullptr, *speckle_lambda = nullptr;   // the options as given
     mcrt_speckle_opts sopts; mcrt_default_speckle_opts(&sopts);
+    const char *speckle3d_n = nullptr, *speckle3d_q0 = nullptr, *speckle3d_rho = nullptr, *speckle3d_lambda = nullptr;   // the options as given
+    mcrt_speckle3d_opts s3opts; mcrt_default_speckle3d_opts(&s3opts);
     const char *noise_db = nullptr, *noise_sigma = nullptr, *noise_seed = nullptr, *dead_elements = nullptr;   // the options as given
     mcrt_noise_opts nopts; mcrt_default_noise_opts(&nopts);
     std::vector<float> element_gain;                  // empty: no gain table
@@ -181,6 +188,10 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--speckle-q0") && i + 1 < argc) speckle_q0 = argv[++i];
             else if (!std::strcmp(argv[i], "--speckle-rho") && i + 1 < argc) speckle_rho = argv[++i];
             else if (!std::strcmp(argv[i], "--speckle-lambda") && i + 1 < argc) speckle_lambda = argv[++i];
+            else if (!std::strcmp(argv[i], "--speckle3d") && i + 1 < argc) speckle3d_n = argv[++i];
+            else if (!std::strcmp(argv[i], "--speckle3d-q0") && i + 1 < argc) speckle3d_q0 = argv[++i];
+            else if (!std::strcmp(argv[i], "--speckle3d-rho") && i + 1 < argc) speckle3d_rho = argv[++i];
+            else if (!std::strcmp(argv[i], "--speckle3d-lambda") && i + 1 < argc) speckle3d_lambda = argv[++i];
             else if (!std::strcmp(argv[i], "--noise-db") && i + 1 < argc) noise_db = argv[++i];
             else if (!std::strcmp(argv[i], "--noise-sigma") && i + 1 < argc) noise_sigma = argv[++i];
             else if (!std::strcmp(argv[i], "--noise-seed") && i + 1 < argc) noise_seed = argv[++i];
@@ -373,6 +384,19 @@ int main(int argc, char **argv)
             if (mcrt_recon_transform(&fgrid, 10.0, A, b) != MCRT_OK) throw std::invalid_argument(std::string("--freehand: ") + mcrt_last_error());
             if ((double)fgrid.nu * fgrid.nv * fgrid.nw >= 2147483648.0) throw std::invalid_argument("--freehand-box-mm: 2^31 voxels or more");
         }
+        if (!speckle3d_n && (speckle3d_q0 || speckle3d_rho || speckle3d_lambda)) throw std::invalid_argument("--speckle3d-q0, --speckle3d-rho and --speckle3d-lambda need --speckle3d");
+        if (speckle3d_n) {
+            if (!freehand_n) throw std::invalid_argument("--speckle3d needs --freehand");
+            const long n = std::atol(speckle3d_n);
+            if (n < 0 || n > 256) throw std::invalid_argument("--speckle3d takes 0..256 iterations");
+            s3opts.n_iter = (uint32_t)n;
+            if (speckle3d_q0) s3opts.q0 = (float)std::atof(speckle3d_q0);
+            if (speckle3d_rho) s3opts.rho = (float)std::atof(speckle3d_rho);
+            if (speckle3d_lambda) s3opts.lambda = (float)std::atof(speckle3d_lambda);
+            if (mcrt_speckle3d_weights(&fgrid, s3opts.weight) != MCRT_OK) throw std::invalid_argument(std::string("--speckle3d: ") + mcrt_last_error());
+            float q0sq[256], kq[256], k[4];
+            if (mcrt_speckle3d_tables(&s3opts, q0sq, kq, k) != MCRT_OK) throw std::invalid_argument(std::string("--speckle3d: ") + mcrt_last_error());
+        }
         std::vector<unsigned char> cut_bytes;         // the last frame's cut, as the PGM holds it
         const mcrt_compound_opts *opts = compound_mode || compound_feather || compound_weights ? &copts : nullptr;
         std::vector<float> steers;                    // centred on the unsteered view, ascending
@@ -429,7 +453,7 @@ int main(int argc, char **argv)
             if (noise) tracked.add_noise(nopts, gain);
             tracked.envelope();
             if (speckle_n) tracked.despeckle(sopts);
-            const std::vector<float> vox = tracked.reconstruct(fgrid, &fopts);
+            const std::vector<float> vox = tracked.reconstruct(fgrid, &fopts, nullptr, speckle3d_n ? &s3opts : nullptr);
             std::ofstream f(freehand_out, std::ios::binary);
             for (float v : vox) {
                 uint32_t w; std::memcpy(&w, &v, 4);

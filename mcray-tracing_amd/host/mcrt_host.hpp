@@ -785,8 +785,10 @@ public:
     }
     // the frames of trace(frame, poses) binned into grid's voxels (a grid in the WORLD frame, mm; scene units are cm) with hole filling: floats
     // [nw][nv][nu].  opts: null = mcrt_default_recon_opts; counts: the samples per voxel, when asked for.  A row of a scan-line is
-    // depth_mm_f / max_rows long, the row pitch of volume(grid)'s maps
-    std::vector<float> reconstruct(const mcrt_volume_grid &grid, const mcrt_recon_opts *opts = nullptr, std::vector<uint32_t> *counts = nullptr)
+    // depth_mm_f / max_rows long, the row pitch of volume(grid)'s maps.  filter: 3-D speckle reduction over the block on the device, in place,
+    // before it is copied (mcrt.h: mcrt_speckle_volume_frames; a hole's `empty` value is a value like any other, counts tell which voxels were empty)
+    std::vector<float> reconstruct(const mcrt_volume_grid &grid, const mcrt_recon_opts *opts = nullptr, std::vector<uint32_t> *counts = nullptr,
+                                   const mcrt_speckle3d_opts *filter = nullptr)
     {
         if (holds != stack_of::tracked_frames) throw std::invalid_argument("rf_image::reconstruct: trace(frame, poses) first");
         const size_t n = (size_t)grid.nu * grid.nv * grid.nw;
@@ -796,6 +798,7 @@ public:
         check(mcrt_recon_frames(dev->ctx, stack.as<float>(), n_views, columns, max_rows, tracked.pos.data(), tracked.dir.data(), (double)depth_mm_f / (double)max_rows, 10.0,
                                 &grid, opts, points.as<float>(), counts ? points.as<uint32_t>() + n : nullptr, nullptr), "mcrt_recon_frames");
         if (counts) *counts = download<uint32_t>(points.as<uint32_t>() + n, n);
+        if (filter) check(mcrt_speckle_volume_frames(dev->ctx, points.as<float>(), 1, grid.nu, grid.nv, grid.nw, filter, points.as<float>()), "mcrt_speckle_volume_frames");
         return download<float>(points, n);
     }
     // the ground truth of reconstruct(grid) (mcrt.h: mcrt_recon_label_frames): the central beams of the poses of trace(frame, poses) walked through
@@ -897,11 +900,14 @@ public:
         else check(mcrt_bmode_compound_frames(dev->ctx, views, 1, columns, max_rows, &p, &cp, tgc_db, st, nullptr, out), "mcrt_bmode_compound_frames");
         state_valid = true; bmode_rows = bp.out_rows; bmode_cols = bp.out_cols;
     }
-    // the planes of trace(frame, transducer, sweep) gathered at grid's points (mcrt_volume_frames): floats [nw][nv][nu], a volume or any cut
-    std::vector<float> volume(const mcrt_volume_grid &grid)
+    // the planes of trace(frame, transducer, sweep) gathered at grid's points (mcrt_volume_frames): floats [nw][nv][nu], a volume or any cut.
+    // filter: 3-D speckle reduction over the block on the device, in place, before it is copied (mcrt.h: mcrt_speckle_volume_frames;
+    // mcrt_speckle3d_weights gives the weights of grid's pitches)
+    std::vector<float> volume(const mcrt_volume_grid &grid, const mcrt_speckle3d_opts *filter = nullptr)
     {
         const size_t n = volume_prepare(grid, sizeof(float));
         check(mcrt_volume_frames(dev->ctx, stack.as<float>(), 1, columns, max_rows, radius_mm, angle, &sweep, &grid, points.as<float>()), "mcrt_volume_frames");
+        if (filter) check(mcrt_speckle_volume_frames(dev->ctx, points.as<float>(), 1, grid.nu, grid.nv, grid.nw, filter, points.as<float>()), "mcrt_speckle_volume_frames");
         return download<float>(points, n);
     }
     // the same as the displayed 8-bit voxels (mcrt_bmode_volume_frames): one reference per volume, the peak of the whole sweep.  The sector is
