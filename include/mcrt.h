@@ -57,6 +57,7 @@ extern "C" {
                                    + mcrt_debug_beam_bounce (the same for any bounce run by beams; additive);
                                    + mcrt_debug_beam_order, mcrt_debug_beam_layout (the beam order of a bounce run by beams, its layout on the host; additive);
                                    + mcrt_debug_beam_scan (the kernel that lays a beam order out, run alone on given counters; additive);
+                                   + mcrt_debug_beam_records (the records, candidate lists and group keys of the last bounce a pass ran by beams; additive);
                                    + mcrt_noise_opts, mcrt_default_noise_opts, mcrt_noise_draws, mcrt_noise_frames (receiver noise: a Gaussian noise floor
                                    from integer Philox sums and a gain per transducer element, over the RF stack in place; additive);
                                    + mcrt_transmit_opts, mcrt_default_transmit_opts, mcrt_transmit_boundary, mcrt_transmit_frames (acoustic ground truth:
@@ -1186,6 +1187,20 @@ int mcrt_debug_beam_layout(const uint32_t *counts, uint32_t n, uint32_t *bases, 
  * nothing (the rays' own places, and the 64 guard words past the length).  order_words may be null.  n >= 1; MCRT_ERR_LIMIT as mcrt_debug_beam_layout.  Buffers of its own; waits for the device. */
 #define MCRT_DEBUG_BEAM_SENTINEL 0x5eed5eedu
 int mcrt_debug_beam_scan(mcrt_ctx *ctx, const uint32_t *counts, uint32_t n, uint32_t *bases, uint32_t out[4], uint32_t *order_words);
+/* what the BEAM STAGE of bounce b left behind in the context's last traced pass or debug call (its first scan-line group), copied as it lies: info[0] beams,
+ * info[1] the capacity of a candidate list, info[2] entries of it the first pass tests, info[3] slots of the group table (0 at bounce 1, whose beams are
+ * addressed directly: (scan-line x 2 + history) x 6 + 2 x dominant axis + sign), info[4] lists;
+ * records[info[0]][MCRT_DEBUG_BEAM_REC] words -- floats unless said: 0-3 the slopes' bounds umin umax vmin vmax | 4-6, 7-9 the start points' bounds lo, hi | 10 the
+ * largest coordinate | 11 the margin m | 12 xref, where depth 0 lies along the dominant axis | 13 s_end, the depth up to which the list is complete (+inf:
+ * all of it; -inf with 0 entries: the collection outgrew its tables) | 14 entries (integer) | 15 its list (integer).  A beam without rays, or refused, has
+ * umin = vmin = +inf, umax = vmax = -inf, s_end = -inf and 0 entries;
+ * lists[info[4]][info[1]][16] words: vertex 0 and the triangle's id (integer) | vertex 1 and the depth at which the triangle's padded bounds begin, less m |
+ * vertex 2 and the triangle's edge tolerance | 0 0 0 0; the entries past a record's count are stale;
+ * keys[info[3]]: the group table, 0 a free slot, else bit 63 | scan-line << 40 | (medium & 0xff) << 32 | the triangle the rays left; the beams of slot s are 6 s .. 6 s + 5.
+ * The beamed bounces of a pass share these buffers, so only the LAST bounce the pass launched by beams can be read: MCRT_ERR_INVALID for any other b, as where
+ * bounce b did not run by beams.  records, lists and keys may each be null (info alone sizes them).  Copies only; waits for the stream. */
+#define MCRT_DEBUG_BEAM_REC 16
+int mcrt_debug_beam_records(mcrt_ctx *ctx, uint32_t b, uint32_t info[5], uint32_t *records, uint32_t *lists, uint64_t *keys);
 /* TEST HOOK, refused (MCRT_ERR_INVALID) unless the context was created with MCRT_TEST_HOOKS set in the environment: ORs `bits` into the
  * context's device error word on its stream, as an abandoned launch would (bit 0: traversal stack ran out, bit 1: kernel watchdog
  * expired) -- what mcrt_synchronize reports and what turns finalised RF images into NaN until it is asked */

@@ -718,6 +718,17 @@ class Context(_SceneCalls):
             check(self.L.mcrt_debug_beam_order(self.h, int(b), out))
         return (bool(out[0]),) + tuple(int(v) for v in out[1:])
 
+    def debug_beam_records(self, b):
+        """mcrt_debug_beam_records: what the beam stage of bounce b -- the LAST bounce the last traced pass or debug call ran by beams -- left behind, as a dict:
+        n_beams, cap, near, groups, n_lists; records uint32 [n_beams][16] (view as float32: include/mcrt.h has the layout); lists uint32 [n_lists][cap][16]
+        (v0 | id, v1 | begin depth, v2 | edge tolerance, 0 0 0 0); keys uint64 [groups].  McrtError where b is not that bounce."""
+        info = (C.c_uint32 * 5)()
+        check(self.L.mcrt_debug_beam_records(self.h, int(b), info, None, None, None))
+        n_beams, cap, near, groups, n_lists = (int(v) for v in info)
+        rec = np.zeros((n_beams, 16), np.uint32); lists = np.zeros((n_lists, cap, 16), np.uint32); keys = np.zeros(groups, np.uint64)
+        check(self.L.mcrt_debug_beam_records(self.h, int(b), info, ptr(rec), ptr(lists), ptr(keys) if groups else None))
+        return {"n_beams": n_beams, "cap": cap, "near": near, "groups": groups, "n_lists": n_lists, "records": rec, "lists": lists, "keys": keys}
+
     def debug_beam_scan(self, counts):
         """mcrt_debug_beam_scan: the kernel that lays a beam order out (csrc/mcrt_beam.hip, k_beam_scan) run alone on `counts` rays per beam, the last the
         pseudo-beam's -> (bases uint32 [n], rays placed, segments, pad lanes, the order's length, the order buffer uint32 [length + 64]: BEAM_PAD in the padding

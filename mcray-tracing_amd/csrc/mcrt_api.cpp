@@ -609,6 +609,28 @@ extern "C" int mcrt_debug_beam_order(mcrt_ctx *c, uint32_t b, uint32_t out[5])
     return MCRT_OK;
 }
 
+// the records, lists and group keys bounce b by beams left in the last traced pass (work set 0).  The buffers are shared by the pass's beamed bounces (stream order):
+// what they hold is the LAST beamed bounce's, and only that bounce is answered
+extern "C" int mcrt_debug_beam_records(mcrt_ctx *c, uint32_t b, uint32_t info[5], uint32_t *records, uint32_t *lists, uint64_t *keys)
+{
+    CTX_TRY(c);
+    if (!info) return set_error(MCRT_ERR_INVALID, "null info pointer");
+    for (int k = 0; k < 5; k++) info[k] = 0u;
+    const uint32_t mask = c->ins.last_beam_depth >= 32u ? c->ins.last_beam_mask : c->ins.last_beam_mask & ((1u << c->ins.last_beam_depth) - 1u);
+    if (b >= MCRT_MAX_BOUNCES || !((mask >> b) & 1u) || c->work.empty()) return set_error(MCRT_ERR_INVALID, "bounce %u did not run by beams in the last traced pass", b);
+    if ((mask >> b) != 1u) return set_error(MCRT_ERR_INVALID, "bounce %u was not the last bounce by beams of the last traced pass: its records and lists have been overwritten", b);
+    const BeamBufs &w = c->work[0].beam;
+    const uint32_t groups = b == 1u ? 0u : c->ins.last_beam_groups, cap = c->ins.last_beam_cap;
+    const uint32_t n_beams = b == 1u ? c->ins.last_beam_b1 : groups * 6u, n_lists = b == 1u ? c->ins.last_beam_b1 : groups * MCRT_BEAM_LISTS_PER_GROUP;
+    if (n_beams > w.beams || n_lists > w.lists || groups > w.groups || cap != w.cap) return set_error(MCRT_ERR_INVALID, "the beam buffers of the last traced pass are gone");
+    info[0] = n_beams; info[1] = cap; info[2] = c->ins.last_beam_near; info[3] = groups; info[4] = n_lists;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (records) HIP_TRY(hipMemcpy(records, w.rec.p, (size_t)n_beams * MCRT_BEAM_REC * 4, hipMemcpyDeviceToHost));
+    if (lists) HIP_TRY(hipMemcpy(lists, w.list.p, (size_t)n_lists * cap * 64, hipMemcpyDeviceToHost));
+    if (keys && groups) HIP_TRY(hipMemcpy(keys, w.gkey.p, (size_t)groups * 8, hipMemcpyDeviceToHost));
+    return MCRT_OK;
+}
+
 // k_beam_scan's arithmetic on the host (no context, no device): the segment bases of n counters -- the last is the pseudo-beam's --, and rays placed, segments,
 // pad lanes and the order's length
 extern "C" int mcrt_debug_beam_layout(const uint32_t *counts, uint32_t n, uint32_t *bases, uint32_t out[4])

@@ -196,6 +196,7 @@ struct Instrumentation {
     uint32_t last_beam_mask = 0;                        // bit b: the last pass ran bounce b by beams (mcrt_debug_beam, mcrt_debug_beam_bounce)
     uint32_t last_beam_order = 0;                       // ... and read its rays through the beam order (mcrt_debug_beam_order)
     bool last_beam_far = false;                         // ... and its leftovers are those of the second pass over the lists
+    uint32_t last_beam_b1 = 0, last_beam_groups = 0, last_beam_cap = 0, last_beam_near = 0, last_beam_depth = 0;   // ... its bounce-1 beams, the slots of its group table, its lists' capacity and first pass, the bounces it launched (mcrt_debug_beam_records)
     float last_lean_bound = 0.0f; uint32_t last_march_rows = 0;   // what the last frame's kernels were given (mcrt_debug_fast_paths)
 };
 

@@ -382,6 +382,7 @@ static int run_pass(mcrt_ctx *c, uint32_t frame, uint32_t n_frames, uint32_t e0,
         if (const uint32_t mask = beam_wanted(c, P, args[g])) { MCRT_TRY(fill_beam(c, *ws[g], args[g], mask, beams[g])); args[g].beam_mask = mask & ~3u; args[g].order_mask = beams[g].order & ~3u; }
     }
     c->ins.last_beam_mask = beams[0].mask; c->ins.last_beam_order = beams[0].order; c->ins.last_beam_far = c->knobs.beam_near < c->knobs.beam_cap;
+    c->ins.last_beam_b1 = beams[0].beams_b1; c->ins.last_beam_groups = beams[0].groups; c->ins.last_beam_cap = beams[0].g.cap; c->ins.last_beam_near = beams[0].g.near; c->ins.last_beam_depth = c->p.max_depth;
     return enqueue_pass(c, P, args, beams, ws, accumulate);
 }
 

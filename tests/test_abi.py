@@ -47,6 +47,16 @@ def test_no_gpu_means_loud_failure(mcrt):
     assert L.mcrt_set_params(None, None) != 0 and b"null context" in L.mcrt_last_error()
 
 
+def test_debug_beam_records_is_bound_and_checks_its_context(mcrt):
+    """mcrt_debug_beam_records (the beam stage's records, lists and group keys; tests/test_gpu_beam_lists.py reads them on the GPU): declared, exported, bound
+    with six arguments, and refused without a context before anything is copied"""
+    L = mcrt.load_library()
+    assert "mcrt_debug_beam_records" in declared_symbols() and len(L.mcrt_debug_beam_records.argtypes) == 6
+    info = (C.c_uint32 * 5)(7, 7, 7, 7, 7)
+    assert L.mcrt_debug_beam_records(None, 1, info, None, None, None) != 0 and b"null context" in L.mcrt_last_error()
+    assert hasattr(mcrt.Context, "debug_beam_records")
+
+
 def test_product_does_not_touch_the_oracle():
     """the oracle is test infrastructure: nothing in the product package may import, load or link it"""
     pkg = os.path.join(ROOT, "mcray-tracing_amd")
