@@ -63,7 +63,9 @@ extern "C" {
                                    + mcrt_transmit_opts, mcrt_default_transmit_opts, mcrt_transmit_boundary, mcrt_transmit_frames (acoustic ground truth:
                                    the intensity that arrives at every scan-line sample and what each boundary turns back; additive);
                                    + mcrt_speckle3d_opts, mcrt_default_speckle3d_opts, mcrt_speckle3d_weights, mcrt_speckle3d_tables, mcrt_speckle_volume_frames
-                                   (3-D speckle reduction: the diffusion of mcrt_speckle_frames over voxel blocks, six neighbours, a weight per axis; additive) */
+                                   (3-D speckle reduction: the diffusion of mcrt_speckle_frames over voxel blocks, six neighbours, a weight per axis; additive);
+                                   + mcrt_autogain_opts, mcrt_default_autogain_opts, mcrt_autogain_curve, mcrt_autogain_frames (automatic gain: a depth gain
+                                   curve estimated from each frame's own amplitude histograms, and the frame's penetration depth; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -745,7 +747,7 @@ int mcrt_speckle_volume_frames(mcrt_ctx *ctx, const float *in_dev, uint32_t n_fr
                                const mcrt_speckle3d_opts *o /* NULL = defaults */, float *out_dev);
 
 /* ---- receiver noise: the noise floor of the receive chain and the gain of every transducer element.  The reference has neither: its RF
- * images hold echoes and exact zeros, so no gain finds a penetration depth and no element is weak or dead.  The stage works on the RF stack
+ * images hold echoes and exact zeros, so no gain finds a penetration depth (mcrt_autogain_frames, below, finds the floor's) and no element is weak or dead.  The stage works on the RF stack
  * [n_frames][n_images][E][R] that a traced pass left on the device (n_images: the N views of a compounded frame, the K planes of a sweep, or 1),
  * in place.  It sits after the lateral PSF and before the envelope: receive noise is uncorrelated between scan-lines.  That is a modelling
  * choice that no measurement backs.
@@ -794,6 +796,68 @@ int mcrt_noise_frames(mcrt_ctx *ctx, float *rf_dev /* [n_frames][n_images][E][R]
                       uint32_t n_images, uint32_t n_elements, uint32_t n_rows, uint32_t first_image_id,
                       const mcrt_noise_opts *o /* NULL = defaults */, const float *element_gain /* host [E] or NULL */,
                       float *sigma_dev /* [n_frames] or NULL */);
+
+/* ---- automatic gain: the "auto-optimise" key of a scanner.  A depth gain curve is estimated from each frame itself: it flattens the tissue
+ * brightness over depth and stops amplifying where only noise is left, which is the frame's penetration depth.  The reference has no gain at
+ * all, and mcrt_bmode_params::tgc_db is a curve that only a caller can write.  The stage works on a float stack [n_frames][n_images][E][R] on the
+ * device, normally enveloped (it goes after mcrt_envelope_frames and mcrt_speckle_frames and before whatever gathers a picture); n_images is
+ * the N views of a compounded frame, the K planes of a sweep, or 1: they share one receiver, hence one curve, as in mcrt_noise_frames.
+ * Integers decide, and the few float operations are rounded once each (no fma, no transcendental, the divisions correctly rounded), so a
+ * numpy reading of this text equals the device bit for bit.
+ *
+ * The rule, per frame f:
+ *   1. amplitude   a(v) = |v| where v is finite, else 0.  bin(a) = bits(a) >> 20: 0 .. 2047, eight bins per octave.  Bin 0 (zeros and the
+ *                  smallest denormals) counts as "no echo".
+ *   2. bands       band b holds the rows [b * band_rows, min((b + 1) * band_rows, R)), n_bands = ceil(R / band_rows).  hist[f][b][bin] is the
+ *                  number of samples of the band, over all n_images * E scan-lines, whose amplitude falls into the bin: integer counts,
+ *                  independent of the order of addition.
+ *   3. floor       thr = floor_f * floor_scale, one float multiply; floor_f = floor_dev[f] when floor_dev is given (a device pointer: the
+ *                  sigma_dev of mcrt_noise_frames), else opts.floor.  thr_bin = bin(thr) when thr is finite and > 0, else 0.  A sample is
+ *                  TISSUE when its bin is greater than thr_bin.  floor_scale = 3 by default: a modelling choice that no measurement backs.
+ *   4. band level  n_t[b] = the tissue samples of the band, n_s[b] = all its samples = n_images * E * (rows of the band).  The band is VALID
+ *                  when n_t * 1000 >= min_permille * n_s (in 64 bits) and n_t > 0.  m[b] = the lower median bin of the tissue samples: the
+ *                  smallest bin whose cumulative tissue count c satisfies 2 * c >= n_t.
+ *   5. target      m* = the lower median of the valid bands' m[b]: element (V - 1) / 2 of the V values sorted.  With no valid band every gain
+ *                  is 1 and the penetration is 0.
+ *   6. band gain   centre(bin) = the float whose bits are (bin << 20) | (1 << 19).  A valid band has
+ *                  k_b = fminf(fmaxf(centre(m*) / centre(m[b]), 1.0f / max_gain), max_gain); an invalid band has the gain of the nearest valid
+ *                  band shallower than it -- noise past the penetration depth and anechoic spans are not amplified further --, and with none
+ *                  shallower the first valid band's gain.
+ *   7. row gain    linear between the band centres.  With n = 2 * r - (band_rows - 1) (signed): n <= 0: k[r] = k_0; else b = n / (2 * band_rows);
+ *                  b >= n_bands - 1: k[r] = k_last; else t = (float)(n - 2 * band_rows * b) / (float)(2 * band_rows) and
+ *                  k[r] = k_b + (k_{b+1} - k_b) * t: a subtraction, a multiplication, an addition.
+ *   8. penetration pen[f] = min(R, (last valid band + 1) * band_rows) rows, or 0 with no valid band.
+ *   9. apply       (opts.apply != 0) out = v * k[f][r], one multiply; a NaN or an infinity stays what it is.  With apply == 0 the stack keeps
+ *                  its bits and only gain_dev, band_bin_dev and pen_dev are written. */
+typedef struct { uint32_t band_rows;     /* rows of a band: 4 .. 256                                     (16)   */
+                 uint32_t min_permille;  /* tissue samples a valid band needs, per mille: 0 .. 1000      (250)  */
+                 float    floor;         /* floor_f where no floor_dev is given: finite, >= 0            (0)    */
+                 float    floor_scale;   /* thr = floor_f * floor_scale: finite, >= 0                    (3)    */
+                 float    max_gain;      /* a band's gain stays in [1 / max_gain, max_gain]: finite, >= 1 (1000: 60 dB) */
+                 uint32_t apply;         /* 0: estimate only, the stack keeps its bits                   (1)    */
+} mcrt_autogain_opts;                    /* 24 bytes: band_rows 0, min_permille 4, floor 8, floor_scale 12, max_gain 16, apply 20 */
+/* the defaults above; host only.  MCRT_ERR_INVALID for a null o */
+int mcrt_default_autogain_opts(mcrt_autogain_opts *o);                                        /* host only */
+/* Steps 3 to 8 for one frame, on the host; no GPU is needed, and k_autogain_curve equals it bit for bit.  hist holds the counts of step 2,
+ * n_lines is n_images * E (n_s[b] = n_lines * the rows of band b, whatever hist adds up to), band_bin[b] receives m[b], or -1 for an
+ * invalid band.  k, band_bin and pen may each be null.  MCRT_ERR_INVALID: a null hist, a zero n_lines or n_rows, floor_f negative or not
+ * finite, an option outside its range (the message names the field);  MCRT_ERR_LIMIT: n_rows > 2048.  On an error nothing is written */
+int mcrt_autogain_curve(const uint32_t *hist /* [n_bands][2048] */, uint32_t n_lines, uint32_t n_rows, float floor_f,
+                        const mcrt_autogain_opts *o /* NULL = defaults */, float *k /* [n_rows] */, int32_t *band_bin /* [n_bands] */,
+                        uint32_t *pen);                                                       /* host only */
+/* The rule above over the stack, in place.  Asynchronous on the context's stream; per chunk of frames a clear of the context's histograms,
+ * k_autogain_hist (one read of the chunk), k_autogain_curve (one workgroup per frame) and, with apply, k_autogain_apply.  The histograms
+ * [frames][n_bands][2048] belong to the context and stay bounded (32 MiB): a pass that needs more is walked in chunks of frames, with the
+ * same result.  The gains of a call without gain_dev live in the context too.  Nothing is allocated after the first call at a size.
+ * floor_dev is read on the device when the kernels run (a NaN, an infinity or a value <= 0 there gives thr_bin = 0).
+ * MCRT_ERR_INVALID: null ctx or rf_dev, a zero n_frames, n_images, n_elements or n_rows, band_rows outside 4 .. 256, min_permille > 1000,
+ * floor or floor_scale negative or not finite, max_gain not finite or < 1 (the message names the field);  MCRT_ERR_LIMIT: n_rows > 2048,
+ * n_frames * n_images > 65535, a stack of 2^31 samples or more.  On an error nothing is launched and nothing is written.  Groups: call it on
+ * mcrt_group_root(). */
+int mcrt_autogain_frames(mcrt_ctx *ctx, float *rf_dev /* [n_frames][n_images][E][R], in place */, uint32_t n_frames, uint32_t n_images,
+                         uint32_t n_elements, uint32_t n_rows, const mcrt_autogain_opts *o /* NULL = defaults */,
+                         const float *floor_dev /* [n_frames] or NULL */, float *gain_dev /* [n_frames][R] or NULL */,
+                         int32_t *band_bin_dev /* [n_frames][n_bands] or NULL */, uint32_t *pen_dev /* [n_frames] or NULL */);
 
 /* ---- freehand 3-D reconstruction: a tracked 2-D probe moved by hand over the patient, its frames binned into voxels from their poses --
  * pixel-nearest-neighbour binning with hole filling (Rohling, Gee, Berman: "A comparison of freehand three-dimensional ultrasound

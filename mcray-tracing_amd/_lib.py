@@ -126,6 +126,12 @@ class NoiseOpts(C.Structure):
     _fields_ = [("mode", C.c_uint32), ("snr_db", C.c_float), ("sigma", C.c_float), ("seed", C.c_uint32)]
 
 
+class AutogainOpts(C.Structure):
+    """mcrt_autogain_opts (include/mcrt.h): 24 bytes"""
+    _fields_ = [("band_rows", C.c_uint32), ("min_permille", C.c_uint32), ("floor", C.c_float), ("floor_scale", C.c_float), ("max_gain", C.c_float),
+                ("apply", C.c_uint32)]
+
+
 NODE_DTYPE = np.dtype([("lo0", "<f4", 3), ("c0", "<i4"), ("hi0", "<f4", 3), ("c1", "<i4"),
                        ("lo1", "<f4", 3), ("pad0", "<u4"), ("hi1", "<f4", 3), ("pad1", "<u4")])
 SEGMENT_DTYPE = np.dtype([("from", "<f4", 3), ("to", "<f4", 3), ("dir", "<f4", 3),
@@ -133,7 +139,7 @@ SEGMENT_DTYPE = np.dtype([("from", "<f4", 3), ("to", "<f4", 3), ("dir", "<f4", 3
                           ("distance_traveled", "<f8"), ("media", "<i4"), ("tri", "<i4")])
 assert NODE_DTYPE.itemsize == 64 and SEGMENT_DTYPE.itemsize == 64 and C.sizeof(BvhNode) == 64 and C.sizeof(BmodeParams) == 48 and C.sizeof(Focus) == 40 and C.sizeof(Compound) == 68 and C.sizeof(CompoundOpts) == 72
 assert C.sizeof(Sweep) == 12 and C.sizeof(VolumeGrid) == 112 and C.sizeof(LabelOpts) == 8 and C.sizeof(RenderView) == 64 and C.sizeof(RenderOpts) == 32 and C.sizeof(SpeckleOpts) == 16 and C.sizeof(NoiseOpts) == 16 and C.sizeof(ReconOpts) == 20
-assert C.sizeof(ReconLabelOpts) == 12 and C.sizeof(TransmitOpts) == 12 and C.sizeof(Speckle3dOpts) == 28 and Speckle3dOpts.weight.offset == 16
+assert C.sizeof(ReconLabelOpts) == 12 and C.sizeof(AutogainOpts) == 24 and C.sizeof(TransmitOpts) == 12 and C.sizeof(Speckle3dOpts) == 28 and Speckle3dOpts.weight.offset == 16
 
 # every symbol include/mcrt.h declares (tests/test_abi.py checks the .so exports each one)
 SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create", "mcrt_destroy", "mcrt_set_stream",
@@ -155,6 +161,7 @@ SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create"
            "mcrt_default_speckle_opts", "mcrt_speckle_tables", "mcrt_speckle_frames",
            "mcrt_default_speckle3d_opts", "mcrt_speckle3d_weights", "mcrt_speckle3d_tables", "mcrt_speckle_volume_frames",
            "mcrt_default_noise_opts", "mcrt_noise_draws", "mcrt_noise_frames",
+           "mcrt_default_autogain_opts", "mcrt_autogain_curve", "mcrt_autogain_frames",
            "mcrt_default_recon_opts", "mcrt_recon_transform", "mcrt_recon_frames",
            "mcrt_default_recon_label_opts", "mcrt_recon_label_frames", "mcrt_render_label_frames"]
 
@@ -238,6 +245,9 @@ def load_library():
         "mcrt_default_noise_opts": [C.POINTER(NoiseOpts)],
         "mcrt_noise_draws": [u32, u32, u32, u32, vp],
         "mcrt_noise_frames": [vp, vp, u32, u32, u32, u32, u32, C.POINTER(NoiseOpts), vp, vp],
+        "mcrt_default_autogain_opts": [C.POINTER(AutogainOpts)],
+        "mcrt_autogain_curve": [vp, u32, u32, C.c_float, C.POINTER(AutogainOpts), vp, vp, vp],
+        "mcrt_autogain_frames": [vp, vp, u32, u32, u32, u32, C.POINTER(AutogainOpts), vp, vp, vp, vp],
         "mcrt_default_recon_opts": [C.POINTER(ReconOpts)],
         "mcrt_recon_transform": [C.POINTER(VolumeGrid), C.c_double, vp, vp],
         "mcrt_recon_frames": [vp, vp, u32, u32, u32, vp, vp, C.c_double, C.c_double, C.POINTER(VolumeGrid), C.POINTER(ReconOpts), vp, vp, vp],

@@ -11,7 +11,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, Speckle3dOpts, NoiseOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, Speckle3dOpts, NoiseOpts, AutogainOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 DEFAULT_ANGLE = 1.0471975511965976      # the sector of main.cpp:28: 60 degrees [rad]
 
@@ -436,6 +436,44 @@ def host_noise_draws(seed, image_id, n_elements, n_rows):
     d = np.zeros((max(int(n_elements), 0), max(int(n_rows), 0)), np.int32)
     check(load_library().mcrt_noise_draws(int(seed) & 0xFFFFFFFF, int(image_id) & 0xFFFFFFFF, n_elements, n_rows, ptr(d)))
     return d
+
+
+def autogain_opts_struct(band_rows=None, min_permille=None, floor=None, floor_scale=None, max_gain=None, max_gain_db=None, apply=None):
+    """mcrt_autogain_opts from keywords over mcrt_default_autogain_opts.  max_gain_db gives max_gain in dB (max_gain = 10^(dB / 20), rounded
+    to float once); both at once: ValueError"""
+    if max_gain is not None and max_gain_db is not None:
+        raise ValueError("autogain takes max_gain or max_gain_db, not both")
+    o = AutogainOpts()
+    check(load_library().mcrt_default_autogain_opts(C.byref(o)))
+    if band_rows is not None:
+        o.band_rows = int(band_rows)
+    if min_permille is not None:
+        o.min_permille = int(min_permille)
+    if floor is not None:
+        o.floor = float(floor)
+    if floor_scale is not None:
+        o.floor_scale = float(floor_scale)
+    if max_gain is not None:
+        o.max_gain = float(max_gain)
+    if max_gain_db is not None:
+        o.max_gain = float(np.float32(10.0 ** (float(max_gain_db) / 20.0)))
+    if apply is not None:
+        o.apply = 1 if apply else 0
+    return o
+
+
+def host_autogain_curve(hist, n_lines, n_rows, floor=0.0, **opts):
+    """mcrt_autogain_curve: steps 3 to 8 of the automatic gain for one frame on the host, from its band histograms uint32 [n_bands][2048]
+    (n_lines = n_images * n_elements) -> (row gains float32 [n_rows], band levels int32 [n_bands] with -1 for an invalid band, the
+    penetration depth in rows).  opts: the keywords of autogain_opts_struct"""
+    o = autogain_opts_struct(**opts)
+    n_bands = (max(int(n_rows), 0) + max(o.band_rows, 1) - 1) // max(o.band_rows, 1)
+    h = np.ascontiguousarray(hist, np.uint32)
+    if o.band_rows >= 4 and 0 < n_rows <= 2048 and h.shape != (n_bands, 2048):
+        raise ValueError("hist takes uint32 [%d][2048], got shape %s" % (n_bands, h.shape))
+    k = np.zeros(max(int(n_rows), 0), np.float32); band = np.zeros(n_bands, np.int32); pen = C.c_uint32(0)
+    check(load_library().mcrt_autogain_curve(ptr(h), n_lines, n_rows, float(floor), C.byref(o), ptr(k), ptr(band), C.byref(pen)))
+    return k, band, int(pen.value)
 
 
 LABEL_RULES = {"traced": 0, "geometric": 1}
@@ -990,6 +1028,16 @@ class Context(_SceneCalls):
                 raise ValueError("element_gain takes one gain per scan-line: %d, got shape %s" % (n_elements, g.shape))
         check(self.L.mcrt_noise_frames(self.h, ptr(rf_dev), n_frames, n_images, n_elements, n_rows, first_image_id, C.byref(o), ptr(g), ptr(sigma_dev)))
 
+    def autogain_frames(self, rf_dev, n_frames, n_images, n_elements, n_rows, floor_dev=None, gain_dev=None, band_bin_dev=None, pen_dev=None, **opts):
+        """mcrt_autogain_frames: automatic gain over the float stack [n_frames][n_images][n_elements][n_rows], in place -- a depth gain
+        curve per frame from its own amplitude histograms.  floor_dev: [n_frames] floats on the device, each frame's noise floor (the
+        sigma_dev of noise_frames), or None: opts' floor.  gain_dev [n_frames][n_rows] floats, band_bin_dev [n_frames][n_bands] int32 and
+        pen_dev [n_frames] uint32 on the device receive the row gains, the band levels and the penetration depths [rows], or None.
+        opts: the keywords of autogain_opts_struct"""
+        o = autogain_opts_struct(**opts)
+        check(self.L.mcrt_autogain_frames(self.h, ptr(rf_dev), n_frames, n_images, n_elements, n_rows, C.byref(o), ptr(floor_dev), ptr(gain_dev),
+                                          ptr(band_bin_dev), ptr(pen_dev)))
+
     def label_frames(self, pos=None, dirs=None, *, rule="traced", start_offset=None, e_begin=0, e_end=None, n_frames=None, tissue_dev=None,
                      interface_dev=None, crossings_dev=None):
         """mcrt_label_frames: the central beam of every scan-line walked through the scene.  pos / dirs None: the context's transducer (one
@@ -1159,7 +1207,7 @@ class Simulator:
 
     def __init__(self, scene_data, transducer, n_samples=5, n_rows=None, device=0, seed=0x5EED, psf=None, texture=None,
                  max_depth=10, sanitize_tir=0, tex_n=256, bvh_builder="sah", elevation=False, compound=None, compound_mode="mean", compound_weights=None,
-                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0, speckle=None, noise=None, speckle3d=None):
+                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0, speckle=None, noise=None, speckle3d=None, autogain=None):
         """elevation=True: slice thickness.  trace() then traces the psf's elevation_size planes of the frame as one pose pass -- plane k of
         frame f with frame id f * K + k, the frame-id rule of include/mcrt.h -- and folds them into rf_dev with psf.elevation_rows();
         everything after (convolve, bmode, frame) is unchanged.
@@ -1187,7 +1235,17 @@ class Simulator:
         voxel blocks.  volume() and freehand() then pass their float block through mcrt_speckle_volume_frames in place on the device before
         it is copied out, with the weights of the grid's pitches (host_speckle3d_weights(grid)) unless the dict gives weights.
         bmode_volume() and render() gather bytes straight from the planes and have no float block to filter: under speckle3d= they
-        raise.  Without the keyword no call changes."""
+        raise.  Without the keyword no call changes.
+        autogain=True, or a dict of the keywords of autogain_opts_struct (band_rows, min_permille, floor, floor_scale, max_gain or
+        max_gain_db, apply): automatic gain.  Every picture that runs the envelope then passes the enveloped (and despeckled) stack through
+        mcrt_autogain_frames in place (auto_gain()) before anything gathers it: the views of a compounded frame and the planes of a sweep
+        share one curve, the tracked frames of freehand() have one each.  With noise= the noise stage's sigma of every frame is the floor;
+        without it the options' floor.  gain_curve() and penetration_mm() return the last run's by-products.  frame() returns RF and is
+        left alone.  Without the keyword no call changes."""
+        self.autogain = None if autogain is None or autogain is False else ({} if autogain is True else dict(autogain))
+        if self.autogain is not None:
+            autogain_opts_struct(**self.autogain)           # (unknown keywords end it here)
+        self._ag_dev, self._ag_frames, self._ag_gain, self._ag_pen = None, 0, None, None
         self.speckle3d = None if speckle3d is None or speckle3d is False else ({} if speckle3d is True else dict(speckle3d))
         if self.speckle3d is not None:
             speckle3d_opts_struct(**self.speckle3d)         # (unknown keywords and a wrong number of weights end it here)
@@ -1255,7 +1313,7 @@ class Simulator:
 
     def close(self):
         if self.ctx.h:
-            for d in (self.rf_dev, self.planes_dev, self.views_dev, self.sweep_dev):
+            for d in (self.rf_dev, self.planes_dev, self.views_dev, self.sweep_dev, self._ag_dev):
                 if d:
                     self.ctx.free(d)
             self.ctx.close()
@@ -1304,8 +1362,42 @@ class Simulator:
         o = self.noise if self.noise is not None else noise_opts_struct()
         dev, n = self._stack
         kw = dict(sigma=o.sigma) if o.mode == NOISE_ABS else dict(snr_db=o.snr_db)
+        sigma_dev = self._autogain_buffers(n if own_peaks else 1)[0] if self.autogain is not None else None   # (auto_gain()'s floor)
         self.ctx.noise_frames(dev, n if own_peaks else 1, 1 if own_peaks else n, self.E, self.R, first_image_id=frame_id * n, element_gain=self.noise_gain,
-                              seed=o.seed, **kw)
+                              sigma_dev=sigma_dev, seed=o.seed, **kw)
+
+    def _autogain_buffers(self, F):
+        """the device side of auto_gain() for F frames: (sigma [F], pen [F], gain [F][R]), one buffer that only grows"""
+        if self._ag_dev is None or self._ag_frames < F:
+            if self._ag_dev is not None:
+                self.ctx.free(self._ag_dev)
+            self._ag_dev, self._ag_frames = None, 0
+            self._ag_dev, self._ag_frames = self.ctx.alloc(F * (2 + self.R) * 4), F
+        return self._ag_dev, self._ag_dev + 4 * F, self._ag_dev + 8 * F
+
+    def auto_gain(self, own_frames=False):
+        """mcrt_autogain_frames over the stack's images, in place, with the options of autogain= (the defaults without one): the images are
+        the views or planes of ONE frame (one receiver, one curve); own_frames=True: so many frames of one image each (the tracked frames
+        of freehand()).  The floor is the sigma that add_noise() left on the device when noise= is on.  It keeps the row gains and the
+        penetration depths for gain_curve() and penetration_mm()"""
+        dev, n = self._stack
+        F = n if own_frames else 1
+        sigma_dev, pen_dev, gain_dev = self._autogain_buffers(F)
+        self.ctx.autogain_frames(dev, F, 1 if own_frames else n, self.E, self.R, floor_dev=sigma_dev if self.noise is not None else None,
+                                 gain_dev=gain_dev, pen_dev=pen_dev, **(self.autogain or {}))
+        self._ag_gain = self.ctx.d2h(gain_dev, (F, self.R), np.float32)
+        self._ag_pen = self.ctx.d2h(pen_dev, (F,), np.uint32)
+
+    def gain_curve(self):
+        """the row gains of the last run under autogain=: float32 [R], or [F][R] after freehand(); None before any"""
+        g = self._ag_gain
+        return None if g is None else (g[0].copy() if g.shape[0] == 1 else g.copy())
+
+    def penetration_mm(self):
+        """the penetration depth of the last run under autogain= [mm]: the rows of mcrt_autogain_frames times the row pitch -- a float, or
+        an array [F] after freehand(); None before any"""
+        p = self._ag_pen
+        return None if p is None else (float(p[0]) * self.row_mm if p.shape[0] == 1 else p.astype(np.float64) * self.row_mm)
 
     def _run(self, frame_id, convolve=True, envelope=True):
         self.trace(frame_id)
@@ -1317,6 +1409,8 @@ class Simulator:
             self.envelope()
             if self.speckle is not None:
                 self.despeckle()
+            if self.autogain is not None:
+                self.auto_gain()
 
     def compound_image(self, frame_id=0, convolve=True, envelope=True, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         """trace -> convolve -> envelope -> mcrt_compound_frames -> host: the compounded float picture [out_rows][out_cols] (compound= only)"""
@@ -1389,7 +1483,7 @@ class Simulator:
 
     def freehand(self, frame_id, pos, dirs, grid, convolve=True, envelope=True, counts=False, row_mm=None, unit_mm=10.0, **opts):
         """a freehand sweep and its volume: the F poses pos / dirs [F][E][3] (Transducer.poses) traced as one pose pass into a temporary stack
-        -- pose f with frame id frame_id * F + f -- -> convolve (-> add_noise with noise=) -> envelope (-> despeckle with speckle=) -> mcrt_recon_frames -> host: the float
+        -- pose f with frame id frame_id * F + f -- -> convolve (-> add_noise with noise=) -> envelope (-> despeckle with speckle=) (-> auto_gain with autogain=) -> mcrt_recon_frames -> host: the float
         voxels [nw][nv][nu] of grid (a VolumeGrid in the WORLD frame, mm); with counts=True (voxels, sample counts uint32 of the same shape).
         opts: the keywords of recon_opts_struct.  It raises under compound=, sweep= or elevation=.
         With speckle3d= the block is filtered on the device (despeckle_volume) before it is copied out.  A hole's `empty` value is then a
@@ -1412,6 +1506,8 @@ class Simulator:
                     self.envelope()
                     if self.speckle is not None:
                         self.despeckle()
+                    if self.autogain is not None:
+                        self.auto_gain(own_frames=True)
             finally:
                 self._stack = held
             self.ctx.recon_frames(stack_dev, pos, dirs, F, self.E, self.R, grid, out, count_dev=cnt if counts else None, row_mm=row_mm, unit_mm=unit_mm, **opts)

@@ -63,6 +63,8 @@ static Knobs read_knobs()
     if (const char *e = tuning_env("MCRT_BEAM_PAIRS")) k.beam_pairs = atoi(e) != 0;
     if (const char *e = tuning_env("MCRT_RENDER_ROW_TILE")) k.render_row_tile = atoi(e) != 0;
     if (const char *e = tuning_env("MCRT_SPECKLE_FUSE")) { int v = atoi(e); if (v == 2 || v == 4) k.speckle_fuse = (uint32_t)v; }
+    if (const char *e = tuning_env("MCRT_AUTOGAIN_COPIES")) { int v = atoi(e); if (v == 1 || v == 4) k.autogain_copies = (uint32_t)v; }
+    if (const char *e = tuning_env("MCRT_AUTOGAIN_HIST_KB")) { int v = atoi(e); if (v >= 8 && v <= 32768) k.autogain_hist_words = (uint32_t)v * 256u; }
     return k;
 }
 

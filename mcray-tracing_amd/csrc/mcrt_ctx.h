@@ -51,6 +51,8 @@ struct Work {
 // tuning knobs from the environment, read ONCE at mcrt_create (never on the frame path) -- and only in a process started with
 // MCRT_TUNING=1 (mcrt::tuning_env): linked into someone else's program the library has its defaults and nothing else.
 #define MCRT_SPECKLE_FUSE_DEFAULT 2u
+#define MCRT_AUTOGAIN_COPIES_DEFAULT 1u
+#define AUTOGAIN_HIST_WORDS (2048u * 4096u)        // 32 MiB: the histograms of 4096 (frame, band) pairs -- 136 frames of 465 rows in bands of 16
 struct Knobs {
     uint32_t ksplit_limit = MCRT_KSPLIT_DEFAULT, trace_blocks = 0, trace_blocks_wide = 0, wide_from = 0 /* 0: the kernels' own default */, wide_max_tree_mb = 128, groups = MCRT_GROUPS_DEFAULT, march_streams = MCRT_SIDE_STREAMS_DEFAULT, march_blocks = 0;   // march_blocks 0: launch_march picks
     bool no_overlap = false, no_priority = false, no_fast_div = false, no_lean = false;
@@ -72,6 +74,8 @@ struct Knobs {
     bool beam_pairs = false;                   // MCRT_BEAM_PAIRS=1: k_beam_test counts the (wavefront, beam) pairs it meets (mcrt_debug_beam_order)
     bool render_row_tile = false;              // MCRT_RENDER_ROW_TILE=1: a wavefront of k_render owns 64 pixels of one picture row in place of an 8 x 8 tile (RenderArgs::row_tile)
     uint32_t speckle_fuse = MCRT_SPECKLE_FUSE_DEFAULT;   // MCRT_SPECKLE_FUSE=2|4: iterations of mcrt_speckle_frames per launch of k_srad; 4 is faster for one frame, 2 for a stack
+    uint32_t autogain_copies = MCRT_AUTOGAIN_COPIES_DEFAULT;   // MCRT_AUTOGAIN_COPIES=1|4: LDS histograms per workgroup of k_autogain_hist; 4 lost
+    uint32_t autogain_hist_words = AUTOGAIN_HIST_WORDS;   // MCRT_AUTOGAIN_HIST_KB: the bound of the histogram scratch [KiB] (tests: a small one walks a small pass in chunks)
     bool test_hooks = false;                   // MCRT_TEST_HOOKS: mcrt_debug_set_error may poison the context (tests only)
 };
 
@@ -184,6 +188,9 @@ struct ImageStages {
     StagedTable lat_rows, elev_rows;
     // receiver noise (mcrt_noise_frames): the gain of every transducer element [E] of the last table (room for the largest E so far); the peaks are d_disp's
     StagedTable gain;
+    // automatic gain (mcrt_autogain_frames): the histograms of a chunk of frames [frames][n_bands][2048], at most AUTOGAIN_HIST_WORDS, and the row
+    // gains [n_frames][R] of the largest call so far that gave no gain_dev
+    Buf<uint32_t> d_aghist; Buf<float> d_aggain;
     // freehand reconstruction (mcrt_recon_frames): the accumulators of the largest grid so far, n sums (8 B each), then n counts (4 B each)
     Buf<unsigned long long> d_recon;
     // freehand label reconstruction (mcrt_recon_label_frames): the vote table of the largest call so far, voxels x n_labels words

@@ -879,6 +879,83 @@ extern "C" int mcrt_noise_draws(uint32_t seed, uint32_t image_id, uint32_t n_ele
     return MCRT_OK;
 }
 
+// ---- automatic gain (the contract is in include/mcrt.h) ---------------------------------------
+extern "C" int mcrt_default_autogain_opts(mcrt_autogain_opts *o)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_autogain_opts: null options");
+    o->band_rows = 16u; o->min_permille = 250u; o->floor = 0.0f; o->floor_scale = 3.0f; o->max_gain = 1000.0f; o->apply = 1u;
+    return MCRT_OK;
+}
+
+int mcrt::autogain_check(const char *fn, const mcrt_autogain_opts *o)
+{
+    if (o->band_rows < 4u || o->band_rows > 256u) return set_error(MCRT_ERR_INVALID, "%s: band_rows must be 4 .. 256 (%u)", fn, o->band_rows);
+    if (o->min_permille > 1000u) return set_error(MCRT_ERR_INVALID, "%s: min_permille must be 0 .. 1000 (%u)", fn, o->min_permille);
+    if (!(std::isfinite(o->floor) && o->floor >= 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: floor must be finite and >= 0 (%g)", fn, (double)o->floor);
+    if (!(std::isfinite(o->floor_scale) && o->floor_scale >= 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: floor_scale must be finite and >= 0 (%g)", fn, (double)o->floor_scale);
+    if (!(std::isfinite(o->max_gain) && o->max_gain >= 1.0f)) return set_error(MCRT_ERR_INVALID, "%s: max_gain must be finite and >= 1 (%g)", fn, (double)o->max_gain);
+    return MCRT_OK;
+}
+
+// steps 3 to 8 of the contract for one frame, as k_autogain_curve (mcrt_autogain.hip) does them; this file is compiled -ffp-contract=off
+extern "C" int mcrt_autogain_curve(const uint32_t *hist, uint32_t n_lines, uint32_t R, float floor_f, const mcrt_autogain_opts *o, float *k,
+                                   int32_t *band_bin, uint32_t *pen)
+{
+    static const char fn[] = "mcrt_autogain_curve";
+    if (!hist) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null hist", fn);
+    if (n_lines == 0 || R == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_lines %u, n_rows %u)", fn, n_lines, R);
+    if (!(std::isfinite(floor_f) && floor_f >= 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: floor_f must be finite and >= 0 (%g)", fn, (double)floor_f);
+    mcrt_autogain_opts d;
+    if (!o) { mcrt_default_autogain_opts(&d); o = &d; }
+    if (const int rc = mcrt::autogain_check(fn, o)) return rc;
+    if (R > MCRT_MAX_ROWS) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: n_rows: at most %d rows (%u)", fn, MCRT_MAX_ROWS, R);
+    auto bits_of = [](float x) { uint32_t u; memcpy(&u, &x, 4); return u; };
+    auto centre = [](int32_t bin) { const uint32_t u = ((uint32_t)bin << 20) | (1u << 19); float x; memcpy(&x, &u, 4); return x; };
+    const uint32_t B = o->band_rows, nB = (R + B - 1u) / B;
+    const float thr = floor_f * o->floor_scale;
+    const uint32_t thr_bin = (std::isfinite(thr) && thr > 0.0f) ? bits_of(thr) >> 20 : 0u;
+    std::vector<int32_t> m(nB, -1);
+    std::vector<int32_t> sorted;
+    int32_t first = -1, last = -1;
+    for (uint32_t b = 0; b < nB; b++) {
+        const uint32_t *h = hist + (size_t)b * 2048u;
+        uint64_t n_t = 0;
+        for (uint32_t i = thr_bin + 1u; i < 2048u; i++) n_t += h[i];
+        const uint64_t n_s = (uint64_t)n_lines * std::min(B, R - b * B);
+        if (n_t == 0 || n_t * 1000ull < (uint64_t)o->min_permille * n_s) continue;
+        uint64_t c = 0;
+        for (uint32_t i = thr_bin + 1u; i < 2048u; i++) { c += h[i]; if (2ull * c >= n_t) { m[b] = (int32_t)i; break; } }
+        sorted.push_back(m[b]);
+        if (first < 0) first = (int32_t)b;
+        last = (int32_t)b;
+    }
+    std::vector<float> kb(nB, 1.0f);
+    if (!sorted.empty()) {
+        std::sort(sorted.begin(), sorted.end());
+        const float ct = centre(sorted[(sorted.size() - 1u) / 2u]), inv_max = 1.0f / o->max_gain;
+        int32_t src = first;
+        for (uint32_t b = 0; b < nB; b++) {
+            if (m[b] >= 0) src = (int32_t)b;
+            kb[b] = std::fmin(std::fmax(ct / centre(m[src]), inv_max), o->max_gain);
+        }
+    }
+    if (k) {
+        const int32_t two_b = 2 * (int32_t)B;
+        for (uint32_t r = 0; r < R; r++) {
+            const int32_t n = 2 * (int32_t)r - ((int32_t)B - 1);
+            if (n <= 0) { k[r] = kb[0]; continue; }
+            const int32_t b = n / two_b;
+            if (b >= (int32_t)nB - 1) { k[r] = kb[nB - 1u]; continue; }
+            const float t = (float)(n - two_b * b) / (float)two_b;
+            const float dk = kb[b + 1] - kb[b], p = dk * t;
+            k[r] = kb[b] + p;
+        }
+    }
+    if (band_bin) for (uint32_t b = 0; b < nB; b++) band_bin[b] = m[b];
+    if (pen) *pen = last < 0 ? 0u : std::min(R, ((uint32_t)last + 1u) * B);
+    return MCRT_OK;
+}
+
 // ---- volume rendering (the contract is in include/mcrt.h) ---------------------------------------
 extern "C" int mcrt_default_render_opts(mcrt_render_opts *o, int in_u8)
 {

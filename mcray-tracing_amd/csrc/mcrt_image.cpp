@@ -1,6 +1,6 @@
 // mcrt_image.cpp -- the image stages of the C-ABI (include/mcrt.h): PSF, elevation, envelope, scan conversion, B-mode, compounding,
-// volume imaging and rendering, speckle reduction, receiver noise, freehand reconstruction, RF export / import.  Host C++ only.  Of a context (mcrt_ctx.h) these read
-// its device, its stream, p.speed_of_sound, c.max_travel_us, knobs.render_row_tile, knobs.speckle_fuse, the pose staging (mcrt::stage_poses:
+// volume imaging and rendering, speckle reduction, receiver noise, automatic gain, freehand reconstruction, RF export / import.  Host C++ only.  Of a context (mcrt_ctx.h) these read
+// its device, its stream, p.speed_of_sound, c.max_travel_us, knobs.render_row_tile, knobs.speckle_fuse, knobs.autogain_copies, knobs.autogain_hist_words, the pose staging (mcrt::stage_poses:
 // the two recon calls) and the image stages' own state (ImageStages), nothing else.
 #include "mcrt_ctx.h"
 #include "mcrt_kernels.h"
@@ -620,6 +620,53 @@ extern "C" int mcrt_noise_frames(mcrt_ctx *c, float *rf_dev, uint32_t n_frames, 
         HIP_TRY(mcrt::launch_bmode_peak(rf_dev, n_frames, n_images * E, R, nullptr, c->img.d_disp.p, c->stream));
     }
     HIP_TRY(mcrt::launch_noise(a, c->stream));
+    return MCRT_OK;
+}
+
+// ---- automatic gain (the contract is in include/mcrt.h; the defaults, the option ranges and the host's curve are host code: mcrt_host.cpp) ----
+// Everything is checked before anything is enqueued.  The histograms [frames][n_bands][2048] are the context's and stay within
+// knobs.autogain_hist_words: the pass is walked in chunks of as many frames as fit (a frame has at most 512 bands, so one always does), per
+// chunk a clear, k_autogain_hist, k_autogain_curve and, with apply, k_autogain_apply -- frames are independent, so chunks change nothing.
+extern "C" int mcrt_autogain_frames(mcrt_ctx *c, float *rf_dev, uint32_t n_frames, uint32_t n_images, uint32_t E, uint32_t R, const mcrt_autogain_opts *o,
+                                    const float *floor_dev, float *gain_dev, int32_t *band_bin_dev, uint32_t *pen_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_autogain_frames";
+    if (!rf_dev) return set_error(MCRT_ERR_INVALID, "%s: null rf_dev", fn);
+    if (n_frames == 0 || n_images == 0 || E == 0 || R == 0)
+        return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, n_images %u, n_elements %u, n_rows %u)", fn, n_frames, n_images, E, R);
+    mcrt_autogain_opts d;
+    if (!o) { mcrt_default_autogain_opts(&d); o = &d; }
+    MCRT_TRY(mcrt::autogain_check(fn, o));
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: n_rows: at most %d rows (%u)", fn, MCRT_MAX_ROWS, R);
+    const uint64_t images = (uint64_t)n_frames * n_images;
+    if (images > 65535ull) return set_error(MCRT_ERR_LIMIT, "%s: n_frames * n_images: at most 65535 images per call (%u x %u)", fn, n_frames, n_images);
+    if ((double)images * (double)E * (double)R >= 0x1p31)
+        return set_error(MCRT_ERR_LIMIT, "%s: a stack of 2^31 samples or more (%u x %u x %u x %u)", fn, n_frames, n_images, E, R);
+    const uint32_t lines = n_images * E, nB = (R + o->band_rows - 1u) / o->band_rows;
+    const size_t band_words = (size_t)nB * AUTOGAIN_BINS;
+    const uint32_t chunk = (uint32_t)std::min<size_t>(n_frames, std::max<size_t>(1u, c->knobs.autogain_hist_words / band_words));
+    HIP_TRY(c->img.d_aghist.grow((size_t)chunk * band_words));
+    if (!gain_dev) HIP_TRY(c->img.d_aggain.grow((size_t)n_frames * R));
+    mcrt::AutogainArgs a;
+    a.hist = c->img.d_aghist.p;
+    a.lines = lines; a.R = R; a.band_rows = o->band_rows; a.n_bands = nB;
+    a.shares = (uint32_t)std::min<uint64_t>(lines, std::max<uint64_t>(1u, ((uint64_t)lines * std::min(o->band_rows, R) + AUTOGAIN_WG_SAMPLES - 1u) / AUTOGAIN_WG_SAMPLES));
+    a.min_permille = o->min_permille; a.floor = o->floor; a.floor_scale = o->floor_scale; a.max_gain = o->max_gain; a.inv_max_gain = 1.0f / o->max_gain;
+    a.chunks = (R + NOISE_WAVE_ROWS - 1u) / NOISE_WAVE_ROWS;
+    float *gain = gain_dev ? gain_dev : c->img.d_aggain.p;
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
+        const uint32_t F = std::min(chunk, n_frames - f0);
+        a.rf = rf_dev + (size_t)f0 * lines * R;
+        a.floor_dev = floor_dev ? floor_dev + f0 : nullptr;
+        a.gain = gain + (size_t)f0 * R;
+        a.band_bin = band_bin_dev ? band_bin_dev + (size_t)f0 * nB : nullptr;
+        a.pen = pen_dev ? pen_dev + f0 : nullptr;
+        HIP_TRY(hipMemsetAsync(a.hist, 0, 4 * (size_t)F * band_words, c->stream));
+        HIP_TRY(mcrt::launch_autogain_hist(a, F, c->knobs.autogain_copies, c->stream));
+        HIP_TRY(mcrt::launch_autogain_curve(a, F, c->stream));
+        if (o->apply) HIP_TRY(mcrt::launch_autogain_apply(a, F, c->stream));
+    }
     return MCRT_OK;
 }
 

@@ -74,5 +74,7 @@ int upload_scene_with_tree(mcrt_ctx *c, const float *tri, const uint32_t *tri_me
 int update_triangles_with_tree(mcrt_ctx *c, const float *tri, uint32_t n_tri, const HostTree *pre);
 // mcrt_host.cpp: the conditions on a sweep and a grid that mcrt_volume_maps and the two device entry points share
 int volume_check(const char *fn, const mcrt_sweep *sw, const mcrt_volume_grid *g);
+// mcrt_host.cpp: the ranges of mcrt_autogain_opts, which mcrt_autogain_curve and mcrt_autogain_frames share
+int autogain_check(const char *fn, const mcrt_autogain_opts *o);
 }
 #endif

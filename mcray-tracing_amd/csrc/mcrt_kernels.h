@@ -16,6 +16,7 @@
 //   mcrt_speckle.hip k_srad (speckle reduction: mcrt_speckle_frames)
 //   mcrt_speckle3d.hip k_srad3 (3-D speckle reduction over voxel blocks: mcrt_speckle_volume_frames)
 //   mcrt_noise.hip   k_noise (receiver noise: mcrt_noise_frames; its peaks are k_bmode_peak's)
+//   mcrt_autogain.hip k_autogain_hist, k_autogain_curve, k_autogain_apply (automatic gain: mcrt_autogain_frames)
 //   mcrt_recon.hip   k_recon_splat, k_recon_resolve (freehand 3-D reconstruction: mcrt_recon_frames)
 //   mcrt_label.hip   k_label (ground-truth label maps: mcrt_label_frames), k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames)
 //   mcrt_transmit.hip k_transmit (acoustic ground truth: mcrt_transmit_frames; the boundary rule it shares with the host is mcrt_transmit.h)
@@ -268,6 +269,24 @@ struct NoiseArgs {
     float c, inv_std;
 };
 
+// k_autogain_hist, k_autogain_curve, k_autogain_apply (mcrt_autogain_frames): a chunk of F frames of the stack [F][N][E][R]
+#define AUTOGAIN_BINS 2048u                         // bin(a) = bits(a) >> 20
+#define AUTOGAIN_MAX_BANDS 512u                     // MCRT_MAX_ROWS / the smallest band_rows
+#define AUTOGAIN_WG_SAMPLES 4096u                   // samples a workgroup of k_autogain_hist reads: 16 per lane
+struct AutogainArgs {
+    float *rf;                          // [F][lines][R]
+    uint32_t *hist;                     // [F][n_bands][AUTOGAIN_BINS], zeroed before k_autogain_hist
+    const float *floor_dev;             // [F] or null: floor_f = floor
+    float *gain;                        // [F][R]: the caller's gain_dev or the context's
+    int32_t *band_bin;                  // [F][n_bands] or null
+    uint32_t *pen;                      // [F] or null
+    uint32_t lines, R;                  // lines = N * E
+    uint32_t band_rows, n_bands, shares;   // shares: workgroups of k_autogain_hist per (frame, band), each a run of scan-lines
+    uint32_t min_permille;
+    float floor, floor_scale, max_gain, inv_max_gain;   // inv_max_gain = 1.0f / max_gain, made on the host
+    uint32_t chunks;                    // k_autogain_apply: ceil(R / NOISE_WAVE_ROWS)
+};
+
 // k_label (mcrt_label_frames): beside these, a FrameArgs of which it reads the scene, the probe (el_pos, el_dir, pose_stride, e_begin, ne_frame,
 // ne = ne_frame * frames), the row table (row_thr, R, inv_row_dt, thr_end, max_travel, sos_d), start_mat, offs, the spacing, pad_abs, stack_ovf
 // (label_stack_entries() in LDS, the rest [..][label_blocks * 64]) and error_flag
@@ -349,6 +368,9 @@ hipError_t launch_render(const RenderArgs &a, bool in8, hipStream_t st);
 hipError_t launch_srad3(Speckle3Args a, uint32_t F, hipStream_t st);                // one iteration over F blocks
 hipError_t launch_srad(SpeckleArgs a, uint32_t F, uint32_t fuse, hipStream_t st);   // fuse: 2 or 4 (the instantiation); a.n <= fuse
 hipError_t launch_noise(const NoiseArgs &a, hipStream_t st);
+hipError_t launch_autogain_hist(const AutogainArgs &a, uint32_t F, uint32_t copies, hipStream_t st);   // copies: 1 or 4 LDS histograms per workgroup (the instantiation)
+hipError_t launch_autogain_curve(const AutogainArgs &a, uint32_t F, hipStream_t st);
+hipError_t launch_autogain_apply(const AutogainArgs &a, uint32_t F, hipStream_t st);
 hipError_t launch_recon_splat(const ReconArgs &a, hipStream_t st);
 hipError_t launch_recon_resolve(ReconArgs a, hipStream_t st);
 hipError_t launch_recon_label_splat(const ReconLabelArgs &a, hipStream_t st);

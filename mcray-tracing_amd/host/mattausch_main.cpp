@@ -10,6 +10,7 @@
 //                   [--speckle N [--speckle-q0 X] [--speckle-rho X] [--speckle-lambda X]]
 //                   [--speckle3d N [--speckle3d-q0 X] [--speckle3d-rho X] [--speckle3d-lambda X]]
 //                   [--noise-db X | --noise-sigma X [--noise-seed N] [--dead-elements a,b,c]]
+//                   [--autogain [--autogain-band N] [--autogain-floor-scale X] [--autogain-max-db X] [--autogain-curve FILE.txt]]
 //                   [--freehand N --freehand-step-mm D [--freehand-fan-deg A] --freehand-box-mm X0,Y0,Z0,X1,Y1,Z1 --freehand-voxel-mm P --freehand-out FILE.raw
 //                    [--freehand-mode mean|max] [--freehand-fill H]]
 // --gpus N: the first N GPUs of the node, the frame's scan-lines sharded over them (mcrt_group_*: one tracing context and host thread per
@@ -73,6 +74,13 @@
 // standard deviation in RF units instead (0: no noise).  --noise-seed N is the seed of the noise streams; --dead-elements a,b,c silences
 // those scan-lines (0..511: a gain of 0, the dark radial streak of a dead element).  The last two need one of the first two, which exclude
 // each other.  rf.bin holds the noisy image.  Without these options nothing changes.
+// --autogain is the scanner's auto-optimise key (mcrt_autogain_frames): after the envelope (and --speckle) every frame's own amplitude
+// histograms, taken in depth bands of --autogain-band N rows (4..256; 16), give a gain curve over depth that flattens the tissue brightness and
+// stops amplifying where only noise is left -- the views of --compound and the planes of --sweep share one curve; the frames of --freehand
+// have one each.  With --noise-db / --noise-sigma the floor is that frame's noise sigma times --autogain-floor-scale X (3), otherwise there is
+// no floor; a band's gain stays within +- --autogain-max-db X (60).  The penetration depth of the last frame is printed, and
+// --autogain-curve FILE.txt writes its row gains, one "row depth_mm gain" line per RF row.  The three need --autogain.  rf.bin holds the
+// gained image.  Without --autogain nothing changes.
 // --freehand N (1..1024) adds a freehand 3-D acquisition after the frames of the run: the probe is moved by hand, here along its elevation axis
 // in N steps of --freehand-step-mm D centred on the scene's pose, step k tilted by (k - (N-1)/2) x --freehand-fan-deg A (0) about the line through
 // the arc's apex; the N frames are traced as one pass with the last frame's number, convolved, enveloped (and despeckled with --speckle) and
@@ -146,6 +154,9 @@ int main(int argc, char **argv)
     const char *noise_db = nullptr, *noise_sigma = nullptr, *noise_seed = nullptr, *dead_elements = nullptr;   // the options as given
     mcrt_noise_opts nopts; mcrt_default_noise_opts(&nopts);
     std::vector<float> element_gain;                  // empty: no gain table
+    bool autogain = false;
+    const char *autogain_band = nullptr, *autogain_scale = nullptr, *autogain_max_db = nullptr, *autogain_curve = nullptr;   // the options as given
+    mcrt_autogain_opts aopts; mcrt_default_autogain_opts(&aopts);
     const char *freehand_n = nullptr, *freehand_step = nullptr, *freehand_fan = nullptr, *freehand_box = nullptr, *freehand_voxel = nullptr, *freehand_out = nullptr,
                *freehand_mode = nullptr, *freehand_fill = nullptr;   // the options as given
     mcrt_recon_opts fopts; mcrt_default_recon_opts(&fopts);
@@ -196,6 +207,11 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--noise-sigma") && i + 1 < argc) noise_sigma = argv[++i];
             else if (!std::strcmp(argv[i], "--noise-seed") && i + 1 < argc) noise_seed = argv[++i];
             else if (!std::strcmp(argv[i], "--dead-elements") && i + 1 < argc) dead_elements = argv[++i];
+            else if (!std::strcmp(argv[i], "--autogain")) autogain = true;
+            else if (!std::strcmp(argv[i], "--autogain-band") && i + 1 < argc) autogain_band = argv[++i];
+            else if (!std::strcmp(argv[i], "--autogain-floor-scale") && i + 1 < argc) autogain_scale = argv[++i];
+            else if (!std::strcmp(argv[i], "--autogain-max-db") && i + 1 < argc) autogain_max_db = argv[++i];
+            else if (!std::strcmp(argv[i], "--autogain-curve") && i + 1 < argc) autogain_curve = argv[++i];
             else if (!std::strcmp(argv[i], "--freehand") && i + 1 < argc) freehand_n = argv[++i];
             else if (!std::strcmp(argv[i], "--freehand-step-mm") && i + 1 < argc) freehand_step = argv[++i];
             else if (!std::strcmp(argv[i], "--freehand-fan-deg") && i + 1 < argc) freehand_fan = argv[++i];
@@ -346,6 +362,22 @@ int main(int argc, char **argv)
             }
         }
         const float *gain = element_gain.empty() ? nullptr : element_gain.data();
+        if (!autogain && (autogain_band || autogain_scale || autogain_max_db || autogain_curve))
+            throw std::invalid_argument("--autogain-band, --autogain-floor-scale, --autogain-max-db and --autogain-curve need --autogain");
+        if (autogain_band) {
+            const long n = std::atol(autogain_band);
+            if (n < 4 || n > 256) throw std::invalid_argument("--autogain-band takes 4..256 rows");
+            aopts.band_rows = (uint32_t)n;
+        }
+        if (autogain_scale) {
+            aopts.floor_scale = (float)std::atof(autogain_scale);
+            if (!(std::isfinite(aopts.floor_scale) && aopts.floor_scale >= 0.0f)) throw std::invalid_argument("--autogain-floor-scale takes a finite factor >= 0");
+        }
+        if (autogain_max_db) {
+            const double db = std::atof(autogain_max_db);
+            aopts.max_gain = (float)std::pow(10.0, db / 20.0);
+            if (!(std::isfinite(db) && db >= 0.0 && std::isfinite(aopts.max_gain))) throw std::invalid_argument("--autogain-max-db takes a finite number of dB >= 0");
+        }
         if (!freehand_n && (freehand_step || freehand_fan || freehand_box || freehand_voxel || freehand_out || freehand_mode || freehand_fill))
             throw std::invalid_argument("--freehand-step-mm, --freehand-fan-deg, --freehand-box-mm, --freehand-voxel-mm, --freehand-out, --freehand-mode and --freehand-fill need --freehand");
         long freehand_frames = 0; double freehand_step_mm = 0.0, freehand_fan_deg = 0.0;
@@ -431,6 +463,7 @@ int main(int argc, char **argv)
             if (noise) rf_image.add_noise(nopts, gain);   // the receiver's noise floor and dead elements, on whatever the convolution ran over
             rf_image.envelope();              // main.cpp:147
             if (speckle_n) rf_image.despeckle(sopts);   // the despeckle filter, on whatever the envelope ran over
+            if (autogain) rf_image.autogain(aopts, noise);   // the gain curve over depth, before anything gathers a picture; the floor is the noise stage's
             if (render_dir && render_labels && f == frames - 1) {                                   // the box seen from a direction, and what is seen
                 rf_image.labels(transducer, &lopts);
                 write_pgm(render_labels, view.nx, view.ny, rf_image.render_labels(cut, view, &ropts, &display, nullptr, &cut_bytes));
@@ -445,6 +478,18 @@ int main(int argc, char **argv)
         check(dev->synchronize(), "mcrt_synchronize");
         const double dt = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
         std::cout << frames / dt << " frames/s, " << (double)frames * transducer_elements * samples / dt << " rays/s on " << devices.size() << " GPU context(s)" << std::endl;
+        if (autogain && frames > 0) {   // the last frame's penetration depth and gain curve
+            const std::vector<float> &k = rf_image.gain_curve();
+            const std::vector<uint32_t> &pen = rf_image.penetration_rows();
+            std::cout << "autogain: penetration depth " << rf_image.penetration_mm() << " mm (" << pen.at(0) << " of " << k.size() << " rows), gain "
+                      << *std::min_element(k.begin(), k.end()) << " .. " << *std::max_element(k.begin(), k.end()) << std::endl;
+            if (autogain_curve) {
+                std::ofstream f(autogain_curve);
+                f.precision(9);
+                for (size_t r = 0; r < k.size(); r++) f << r << " " << (double)r * rf_image_::row_mm() << " " << k[r] << "\n";
+                if (!f) throw std::runtime_error(std::string("cannot write ") + autogain_curve);
+            }
+        }
         if (freehand_n) {   // the freehand sweep and its volume, in an image of its own: the picture below is the run's
             rf_image_ tracked{ dev, transducer_radius_cm * 10.0, transducer_amplitude };
             const auto poses = transducer.freehand((uint32_t)freehand_frames, freehand_step_mm, freehand_fan_deg);
@@ -453,6 +498,7 @@ int main(int argc, char **argv)
             if (noise) tracked.add_noise(nopts, gain);
             tracked.envelope();
             if (speckle_n) tracked.despeckle(sopts);
+            if (autogain) tracked.autogain(aopts, noise);
             const std::vector<float> vox = tracked.reconstruct(fgrid, &fopts, nullptr, speckle3d_n ? &s3opts : nullptr);
             std::ofstream f(freehand_out, std::ios::binary);
             for (float v : vox) {

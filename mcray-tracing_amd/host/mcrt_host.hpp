@@ -695,7 +695,7 @@ public:
 
     rf_image(double radius_mm, double angle_rad, std::shared_ptr<device> dev_ = nullptr)
         : dev(dev_ ? std::move(dev_) : default_device()), radius_mm(radius_mm), angle(angle_rad), host((size_t)columns * max_rows, 0.0f),
-          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev), sound(dev)
+          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev), sound(dev), sigma(dev), curve(dev)
     {
         std::cout << "rf_image: " << max_rows << ", " << columns << std::endl;          // rfimage.h:30
         rf.reserve(sizeof(float) * columns * max_rows);
@@ -726,7 +726,7 @@ public:
     {
         shape_params();
         check(dev->trace_frames(frame_id, 1, columns, rf.as<float>()), "mcrt_trace_frame");       // (every GPU of a group traces its scan-line shard)
-        where = on_device; holds = stack_of::nothing; n_views = 0; first_id = frame_id;
+        where = on_device; holds = stack_of::nothing; n_views = 0; first_id = frame_id; sigma_frames = 0;
     }
     // the same with slice thickness (psf.h:16-18,42,77; mcrt.h): the frame's n_planes elevation planes (0: the psf's elevation_size), spread
     // p.elevation_pitch_um() apart around the transducer's own plane, traced as ONE pose pass -- plane k with frame id frame_id * K + k, the
@@ -739,7 +739,7 @@ public:
         const std::vector<float> &w = p.elevation_rows(max_rows, (double)axial_resolution_um / 1000.0, K);
         pose_pass(frame_id, K, tables, planes, "rf_image::trace: frame_id * n_planes does not fit a frame id");
         check(mcrt_elevation_frames(dev->ctx, planes.as<float>(), 1, K, columns, max_rows, w.data(), rf.as<float>()), "mcrt_elevation_frames");
-        where = on_device; holds = stack_of::nothing; n_views = 0; first_id = frame_id;
+        where = on_device; holds = stack_of::nothing; n_views = 0; first_id = frame_id; sigma_frames = 0;
     }
     // spatial compounding (mcrt.h): the frame's views, one per steering angle [rad] of steer_rad (1..16), traced as ONE pose pass -- view n with
     // frame id frame_id * N + n, the frame-id rule of mcrt.h -- into a stack [N][columns][max_rows] this image owns.  convolve() and envelope()
@@ -751,7 +751,7 @@ public:
         const uint32_t V = (uint32_t)steer_rad.size();
         if (V == 0 || V > 16) throw std::invalid_argument("rf_image::trace: 1..16 steering angles");
         pose_pass(frame_id, V, t.steered(steer_rad), stack, "rf_image::trace: frame_id * views does not fit a frame id");
-        holds = stack_of::views; n_views = V; first_id = frame_id * V;
+        holds = stack_of::views; n_views = V; first_id = frame_id * V; sigma_frames = 0;
     }
     // volume imaging (mcrt.h): the K planes of a probe swept in elevation, traced as ONE pose pass -- plane k with frame id frame_id * K + k, the
     // frame-id rule of mcrt.h -- into the stack [K][columns][max_rows] the views of a compounded frame use.  convolve() and envelope() then run
@@ -762,7 +762,7 @@ public:
         static_assert(N == columns, "one scan-line per transducer element");
         if (sw.n_planes == 0 || sw.n_planes > 256) throw std::invalid_argument("rf_image::trace: a sweep has 1..256 planes");
         pose_pass(frame_id, sw.n_planes, t.swept(sw), stack, "rf_image::trace: frame_id * planes does not fit a frame id");
-        holds = stack_of::sweep_planes; n_views = sw.n_planes; sweep = sw; first_id = frame_id * sw.n_planes;
+        holds = stack_of::sweep_planes; n_views = sw.n_planes; sweep = sw; first_id = frame_id * sw.n_planes; sigma_frames = 0;
     }
     // freehand 3-D (mcrt.h: mcrt_recon_frames): the frames of a tracked probe moved by hand, one pose per frame -- a vector of transducers, or the
     // two tables [F][columns][3] (transducer::freehand makes a regular one) --, traced as ONE pose pass -- pose f with frame id frame_id * F + f
@@ -774,7 +774,7 @@ public:
         if (F == 0 || F > 65535 || pos.size() != F * one || dir.size() != pos.size()) throw std::invalid_argument("rf_image::trace: pose tables [F][columns][3], F = 1..65535");
         tracked.pos = pos; tracked.dir = dir;
         pose_pass(frame_id, (uint32_t)F, tracked, stack, "rf_image::trace: frame_id * poses does not fit a frame id");
-        holds = stack_of::tracked_frames; n_views = (uint32_t)F; first_id = frame_id * (uint32_t)F;
+        holds = stack_of::tracked_frames; n_views = (uint32_t)F; first_id = frame_id * (uint32_t)F; sigma_frames = 0;
     }
     template <size_t N> void trace(uint32_t frame_id, const std::vector<transducer<N>> &poses)
     {
@@ -850,16 +850,43 @@ public:
     // receiver noise (mcrt.h: mcrt_noise_frames): a noise floor and a gain per scan-line (element_gain: [columns] or null) over whatever the
     // last trace() filled, in place -- this image, or the views of a compounded frame or the planes of a sweep as ONE frame (one receiver,
     // one peak), or the tracked frames of a freehand pass as so many frames -- with the ids that trace used.  It goes after convolve() and
-    // before envelope(): receive noise is uncorrelated between scan-lines
+    // before envelope(): receive noise is uncorrelated between scan-lines.  Every frame's sigma stays on the device for autogain()
     void add_noise(const mcrt_noise_opts &o, const float *element_gain = nullptr)
     {
+        const bool own = holds == stack_of::tracked_frames;
+        const uint32_t F = n_views && own ? n_views : 1u;
+        sigma.reserve(4 * (size_t)F);
         if (n_views) {
-            const bool own = holds == stack_of::tracked_frames;
-            check(mcrt_noise_frames(dev->ctx, stack.as<float>(), own ? n_views : 1u, own ? 1u : n_views, columns, max_rows, first_id, &o, element_gain, nullptr), "mcrt_noise_frames");
+            check(mcrt_noise_frames(dev->ctx, stack.as<float>(), F, own ? 1u : n_views, columns, max_rows, first_id, &o, element_gain, sigma.as<float>()), "mcrt_noise_frames");
+            sigma_frames = F;
             return;
         }
-        to_device(); check(mcrt_noise_frames(dev->ctx, rf.as<float>(), 1, 1, columns, max_rows, first_id, &o, element_gain, nullptr), "mcrt_noise_frames");
+        to_device(); check(mcrt_noise_frames(dev->ctx, rf.as<float>(), 1, 1, columns, max_rows, first_id, &o, element_gain, sigma.as<float>()), "mcrt_noise_frames");
+        sigma_frames = 1;
     }
+    // automatic gain (mcrt.h: mcrt_autogain_frames): a depth gain curve estimated from each frame itself over whatever the last trace()
+    // filled, in place -- this image, or the views of a compounded frame or the planes of a sweep as ONE frame (one receiver, one curve), or
+    // the tracked frames of a freehand pass as so many frames.  It goes after envelope() (and despeckle()) and before whatever makes the
+    // picture.  noise_floor: every frame's floor is the sigma that add_noise() left on the device (it throws when add_noise() has not run
+    // on this pass); otherwise o.floor.  gain_curve(), penetration_rows() and penetration_mm() return its by-products
+    void autogain(const mcrt_autogain_opts &o, bool noise_floor = false)
+    {
+        const bool own = holds == stack_of::tracked_frames;
+        const uint32_t F = n_views && own ? n_views : 1u;
+        if (noise_floor && sigma_frames != F) throw std::logic_error("rf_image::autogain: noise_floor needs add_noise() on the same pass");
+        curve.reserve(4 * (size_t)F * (max_rows + 1u));             // the gains [F][max_rows], then the penetration depths [F]
+        float *k = curve.as<float>();
+        uint32_t *pen = reinterpret_cast<uint32_t *>(k + (size_t)F * max_rows);
+        const float *floor_dev = noise_floor ? sigma.as<float>() : nullptr;
+        if (n_views) check(mcrt_autogain_frames(dev->ctx, stack.as<float>(), F, own ? 1u : n_views, columns, max_rows, &o, floor_dev, k, nullptr, pen), "mcrt_autogain_frames");
+        else { to_device(); check(mcrt_autogain_frames(dev->ctx, rf.as<float>(), 1, 1, columns, max_rows, &o, floor_dev, k, nullptr, pen), "mcrt_autogain_frames"); }
+        gains = download<float>(k, (size_t)F * max_rows);
+        pens = download<uint32_t>(pen, F);
+    }
+    const std::vector<float> &gain_curve() const { return gains; }                 // the last autogain()'s row gains, [frames][max_rows]
+    const std::vector<uint32_t> &penetration_rows() const { return pens; }         // ... and penetration depths [frames], in rows
+    static constexpr double row_mm() { return (double)axial_resolution_um / 1000.0; }   // the RF row pitch [mm]
+    double penetration_mm(size_t frame = 0) const { return (double)pens.at(frame) * row_mm(); }   // ... in mm: rows times the row pitch
     // speckle reduction (mcrt.h: mcrt_speckle_frames): speckle-reducing anisotropic diffusion over the enveloped image -- the views of a
     // compounded frame, the planes of a sweep --, in place; it goes after envelope() and before whatever makes the picture
     void despeckle(const mcrt_speckle_opts &o)
@@ -1149,6 +1176,8 @@ private:
     enum class stack_of { nothing, views, sweep_planes, tracked_frames } holds = stack_of::nothing;   // ... what the last trace left in it
     uint32_t n_views = 0;                        // ... and how many (nothing: 0)
     uint32_t first_id = 0;                       // the frame id the last trace() gave its first image (add_noise: the noise streams' ids)
+    uint32_t sigma_frames = 0;                   // ... the frames sigma holds since the last trace() (0: add_noise() has not run)
+    std::vector<float> gains; std::vector<uint32_t> pens;   // autogain()'s by-products on the host
     mcrt_sweep sweep{ 0, 0.0f, 0.0f };           // ... the sweep of sweep_planes
     struct pose_tables { std::vector<float> pos, dir; } tracked;   // ... the poses of tracked_frames, [n_views][columns][3] each
     device_buffer points;                        // volume(), label_picture(), label_volume(): the gathered points, floats or bytes
@@ -1157,6 +1186,7 @@ private:
     enum class labels_of { nothing, one_plane, sweep_planes } labelled = labels_of::nothing;   // ... what they hold (one_plane: a 1-plane sweep's too)
     uint32_t label_planes = 0; const unsigned char *label_tissue = nullptr;   // ... their leading axis (nothing: 0) and the tissue table
     device_buffer sound;                         // transmission(): the transmit, reflect and crossings tables in one allocation
+    device_buffer sigma, curve;                  // add_noise(): every frame's sigma; autogain(): the row gains and the penetration depths
     uint32_t sound_planes = 0;                   // ... their leading axis (nothing yet: 0)
 };
 
