@@ -65,7 +65,9 @@ extern "C" {
                                    + mcrt_speckle3d_opts, mcrt_default_speckle3d_opts, mcrt_speckle3d_weights, mcrt_speckle3d_tables, mcrt_speckle_volume_frames
                                    (3-D speckle reduction: the diffusion of mcrt_speckle_frames over voxel blocks, six neighbours, a weight per axis; additive);
                                    + mcrt_autogain_opts, mcrt_default_autogain_opts, mcrt_autogain_curve, mcrt_autogain_frames (automatic gain: a depth gain
-                                   curve estimated from each frame's own amplitude histograms, and the frame's penetration depth; additive) */
+                                   curve estimated from each frame's own amplitude histograms, and the frame's penetration depth; additive);
+                                   + mcrt_bands, mcrt_default_bands, mcrt_psf_band_kernels, mcrt_convolve_bands_frames, mcrt_band_fold_frames
+                                   (frequency compounding and the depth downshift: an axial kernel per RF row and per band; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -307,6 +309,59 @@ int mcrt_psf_elevation_kernels(float var_z, uint32_t pitch_um, const mcrt_focus 
  * the previous one); nothing is allocated after the first call.  Groups: call it on mcrt_group_root() after mcrt_group_trace_frames_poses. */
 int mcrt_elevation_frames(mcrt_ctx *ctx, const float *planes_dev /* [n_frames][K][E][R] */, uint32_t n_frames, uint32_t n_planes,
                           uint32_t n_elements, uint32_t n_rows, const float *w_rows /* host [n_rows][K] */, float *rf_dev /* [n_frames][E][R] */);
+/* ---- frequency compounding and the depth downshift: an axial kernel per RF row and per band (psf.h:34-58 builds one axial kernel, the
+ * same at every depth).  The received band is split into B sub-bands; the RF stack of a traced pass is convolved with each band's pulse
+ * (mcrt_convolve_bands_frames), every band image is detected on its own (mcrt_envelope_frames over the F * B images) and the detected
+ * images are averaged (mcrt_band_fold_frames): speckle decorrelates between bands and falls, at the price of axial resolution.  No second
+ * trace is needed.  Folding the band images WITHOUT the envelope between is a coherent sum: linear, the same as one convolution with the
+ * weighted sum of the pulses, and it reduces no speckle.
+ *
+ * RF row r lies at depth z_r = (double)r * row_mm (the rule of mcrt_psf_focus_kernels).  Band b at row r has, in double, the centre frequency
+ *   f(b, r)        = max((double)min_mhz, (double)band_mhz[b] - (double)downshift_mhz_per_mm * z_r)
+ *   ax_rows[b][r][i] = (float)(exp(-0.5f * (x_i^2 / (double)var_x)) * cos(2 * 3.14159 * f(b, r) * (double)x_i))
+ * mcrt_psf_kernels' axial expression -- its x_i, half_ax, 3.14159 and order of operations -- with f(b, r) in the place of (double)freq: a
+ * band at freq with downshift 0 and min_mhz <= freq equals mcrt_psf_kernels(freq, var_x, ...)'s axial taps bit for bit on every row.  The
+ * formula multiplies MHz by mm as the reference's does; a band is what the formula gives, not a calibrated spectrum.
+ *   w_rows[r][b]   = (float)((double)band_weight[b] / S),   S the double sum of the weights in b order
+ * the same on every row (the table has the shape mcrt_elevation_frames takes: a caller may hand mcrt_band_fold_frames a depth-dependent blend
+ * of their own).  downshift_mhz_per_mm has no default that the reference backs: the wrappers use 0 and a value is the caller's choice. */
+typedef struct {
+    uint32_t n_bands;               /* 1..8 */
+    float    band_mhz[8];           /* centre frequency of band b at the probe's face: finite, > 0 (any order) */
+    float    band_weight[8];        /* finite, >= 0, their sum > 0 */
+    float    var_x;                 /* mm^2, axial variance of every band's pulse: finite, > 0 */
+    float    downshift_mhz_per_mm;  /* finite, >= 0: how fast the centre frequency falls with depth */
+    float    min_mhz;               /* finite, >= 0: the frequency stops falling here */
+} mcrt_bands;                       /* 80 bytes: n_bands 0, band_mhz 4, band_weight 36, var_x 68, downshift 72, min_mhz 76 */
+/* one band at freq, weight 1, no downshift, min_mhz 0 (the other entries 0).  MCRT_ERR_INVALID for a null b. */
+int mcrt_default_bands(mcrt_bands *b, float freq, float var_x);
+/* the tables of the model above; host only, no GPU needed.  w_rows may be NULL.  MCRT_ERR_INVALID for a null b / ax_rows, n_bands outside
+ * 1..8, any field outside the ranges above, res_um == 0, row_mm <= 0 or not finite, n_ax outside 1..16; MCRT_ERR_LIMIT for n_rows > 2048.
+ * On an error nothing is written. */
+int mcrt_psf_band_kernels(const mcrt_bands *b, uint32_t res_um, uint32_t n_rows, double row_mm,
+                          float *ax_rows /* [B][n_rows][n_ax] */, uint32_t n_ax, float *w_rows /* [n_rows][B] or NULL */);
+/* bands_dev[f][b] is the image that mcrt_convolve_frames (lateral given) or mcrt_convolve_frames_depth (lat_rows given) leaves from
+ * rf_dev[f], with row r's own axial taps:  tmp[e][r] = sum_k rf[e][r+k] * ax_rows[b][r][k]  for r in [n_ax, R-n_ax), summed in k order from
+ * 0.0f, one rounding per multiply and per add, no fma; the lateral pass is unchanged.  Pixels outside the convolved windows hold rf_dev's own
+ * bits (NaN and -0.0 included).  When the rows of ax_rows[b] all equal one `axial`, bands_dev[f][b] equals the existing call's image bit for
+ * bit at every pixel.  rf_dev [F][E][R] is read only; bands_dev [F][B][E][R] must not overlap it (MCRT_ERR_INVALID).  Exactly one of
+ * lateral [n_lat] / lat_rows [R][n_lat] is non-null (MCRT_ERR_INVALID otherwise).  Limits and errors are mcrt_convolve_frames_depth's, plus
+ * MCRT_ERR_INVALID for n_bands outside 1..8, and MCRT_ERR_LIMIT for a band stack of 2^40 floats or more; on any error nothing is launched and
+ * nothing is written.  Asynchronous on the context's stream; the caller may rewrite its tables as soon as the call returns.  The tables live on
+ * the device tap-major -- the axial table [B][n_ax][R] in a buffer of its own (8 x 16 x 2048 floats, made by the first call), lat_rows in
+ * mcrt_convolve_frames_depth's -- and are copied only when they differ from the ones there; nothing is allocated once the table buffers and
+ * the scratch (F * B * E * R floats) exist.  Groups: call it on mcrt_group_root(). */
+int mcrt_convolve_bands_frames(mcrt_ctx *ctx, const float *rf_dev /* [F][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
+                               uint32_t n_bands, const float *ax_rows /* host [B][R][n_ax] */, uint32_t n_ax,
+                               const float *lateral /* host [n_lat] or NULL */, const float *lat_rows /* host [R][n_lat] or NULL */, uint32_t n_lat,
+                               float *bands_dev /* [F][B][E][R] */);
+/* folds the B band images of every frame:  rf[f][e][r] = sum over b of bands[f][b][e][r] * w_rows[r][b].  The contract is
+ * mcrt_elevation_frames' word for word with K = B (the sum in b order from 0.0f, one rounding per multiply and per add; a NaN reaches the
+ * output under a zero weight; B = 1 with weight 1 copies, a -0.0 becomes +0.0; no borders; the buffers must not overlap), except that
+ * n_bands is 1..8 (MCRT_ERR_INVALID outside).  The weights have a device table of their own beside the elevation weights', so that a frame
+ * with slice thickness and bands uploads neither twice. */
+int mcrt_band_fold_frames(mcrt_ctx *ctx, const float *bands_dev /* [F][B][E][R] */, uint32_t n_frames, uint32_t n_bands,
+                          uint32_t n_elements, uint32_t n_rows, const float *w_rows /* host [R][B] */, float *rf_dev /* [F][E][R] */);
 /* rf_image::envelope (rfimage.h:54-91) in place on a device image [E][R].  n_rows <= 2048 (MCRT_ERR_LIMIT beyond: a wavefront holds
  * its scan-line in LDS) -- the limit mcrt_params.n_rows has anyway; an image brought in through mcrt_import_rf is bound by it too.
  * An image of n_rows < 2 has no peak to find and is left unchanged. */

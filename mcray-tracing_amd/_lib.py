@@ -58,6 +58,12 @@ class Focus(C.Structure):
     _fields_ = [("n_focus", C.c_uint32), ("focus_mm", C.c_float * 8), ("focal_range_mm", C.c_float)]
 
 
+class Bands(C.Structure):
+    """mcrt_bands (include/mcrt.h): 80 bytes, band_mhz at offset 4, band_weight at 36, var_x at 68, downshift_mhz_per_mm at 72, min_mhz at 76"""
+    _fields_ = [("n_bands", C.c_uint32), ("band_mhz", C.c_float * 8), ("band_weight", C.c_float * 8), ("var_x", C.c_float),
+                ("downshift_mhz_per_mm", C.c_float), ("min_mhz", C.c_float)]
+
+
 class Compound(C.Structure):
     """mcrt_compound (include/mcrt.h): 68 bytes, steer_rad at offset 4"""
     _fields_ = [("n_views", C.c_uint32), ("steer_rad", C.c_float * 16)]
@@ -140,6 +146,7 @@ SEGMENT_DTYPE = np.dtype([("from", "<f4", 3), ("to", "<f4", 3), ("dir", "<f4", 3
 assert NODE_DTYPE.itemsize == 64 and SEGMENT_DTYPE.itemsize == 64 and C.sizeof(BvhNode) == 64 and C.sizeof(BmodeParams) == 48 and C.sizeof(Focus) == 40 and C.sizeof(Compound) == 68 and C.sizeof(CompoundOpts) == 72
 assert C.sizeof(Sweep) == 12 and C.sizeof(VolumeGrid) == 112 and C.sizeof(LabelOpts) == 8 and C.sizeof(RenderView) == 64 and C.sizeof(RenderOpts) == 32 and C.sizeof(SpeckleOpts) == 16 and C.sizeof(NoiseOpts) == 16 and C.sizeof(ReconOpts) == 20
 assert C.sizeof(ReconLabelOpts) == 12 and C.sizeof(AutogainOpts) == 24 and C.sizeof(TransmitOpts) == 12 and C.sizeof(Speckle3dOpts) == 28 and Speckle3dOpts.weight.offset == 16
+assert C.sizeof(Bands) == 80 and Bands.band_weight.offset == 36 and Bands.var_x.offset == 68 and Bands.min_mhz.offset == 76
 
 # every symbol include/mcrt.h declares (tests/test_abi.py checks the .so exports each one)
 SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create", "mcrt_destroy", "mcrt_set_stream",
@@ -162,6 +169,7 @@ SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create"
            "mcrt_default_speckle3d_opts", "mcrt_speckle3d_weights", "mcrt_speckle3d_tables", "mcrt_speckle_volume_frames",
            "mcrt_default_noise_opts", "mcrt_noise_draws", "mcrt_noise_frames",
            "mcrt_default_autogain_opts", "mcrt_autogain_curve", "mcrt_autogain_frames",
+           "mcrt_default_bands", "mcrt_psf_band_kernels", "mcrt_convolve_bands_frames", "mcrt_band_fold_frames",
            "mcrt_default_recon_opts", "mcrt_recon_transform", "mcrt_recon_frames",
            "mcrt_default_recon_label_opts", "mcrt_recon_label_frames", "mcrt_render_label_frames"]
 
@@ -248,6 +256,10 @@ def load_library():
         "mcrt_default_autogain_opts": [C.POINTER(AutogainOpts)],
         "mcrt_autogain_curve": [vp, u32, u32, C.c_float, C.POINTER(AutogainOpts), vp, vp, vp],
         "mcrt_autogain_frames": [vp, vp, u32, u32, u32, u32, C.POINTER(AutogainOpts), vp, vp, vp, vp],
+        "mcrt_default_bands": [C.POINTER(Bands), C.c_float, C.c_float],
+        "mcrt_psf_band_kernels": [C.POINTER(Bands), u32, u32, C.c_double, vp, u32, vp],
+        "mcrt_convolve_bands_frames": [vp, vp, u32, u32, u32, u32, vp, u32, vp, vp, u32, vp],
+        "mcrt_band_fold_frames": [vp, vp, u32, u32, u32, u32, vp, vp],
         "mcrt_default_recon_opts": [C.POINTER(ReconOpts)],
         "mcrt_recon_transform": [C.POINTER(VolumeGrid), C.c_double, vp, vp],
         "mcrt_recon_frames": [vp, vp, u32, u32, u32, vp, vp, C.c_double, C.c_double, C.POINTER(VolumeGrid), C.POINTER(ReconOpts), vp, vp, vp],

@@ -11,7 +11,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, Speckle3dOpts, NoiseOpts, AutogainOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Bands, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, Speckle3dOpts, NoiseOpts, AutogainOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 DEFAULT_ANGLE = 1.0471975511965976      # the sector of main.cpp:28: 60 degrees [rad]
 
@@ -87,6 +87,30 @@ def host_psf_focus(var_y, res_um, n_rows, row_mm, focus_mm, focal_range_mm=20.0,
     f = focus_struct(focus_mm, focal_range_mm)
     check(load_library().mcrt_psf_focus_kernels(var_y, res_um, C.byref(f), n_rows, row_mm, ptr(out), n_lat))
     return out
+
+
+def bands_struct(band_mhz, weights=None, var_x=0.05, downshift_mhz_per_mm=0.0, min_mhz=0.0):
+    """mcrt_bands from a sequence of centre frequencies [MHz] (more than 8 give n_bands > 8, which the library refuses); weights: one per
+    band, None: equal ones"""
+    b = Bands()
+    fm = [float(x) for x in band_mhz]
+    w = [1.0] * len(fm) if weights is None else [float(x) for x in weights]
+    if len(w) != len(fm):
+        raise ValueError("weights takes one weight per band (%d), got %d" % (len(fm), len(w)))
+    b.n_bands = len(fm)
+    for i, (f, x) in enumerate(list(zip(fm, w))[:8]):
+        b.band_mhz[i] = f; b.band_weight[i] = x
+    b.var_x, b.downshift_mhz_per_mm, b.min_mhz = var_x, downshift_mhz_per_mm, min_mhz
+    return b
+
+
+def host_psf_bands(bands, res_um, n_rows, row_mm, n_ax=7):
+    """mcrt_psf_band_kernels: (ax_rows float32 [B][n_rows][n_ax], w_rows float32 [n_rows][B]) of a Bands struct -- the axial taps of every
+    band and RF row and the bands' weights (frequency compounding and the depth downshift; the model is in include/mcrt.h)"""
+    B = min(max(int(bands.n_bands), 0), 8)
+    ax = np.zeros((B, n_rows, max(int(n_ax), 0)), np.float32); w = np.zeros((n_rows, B), np.float32)
+    check(load_library().mcrt_psf_band_kernels(C.byref(bands), res_um, n_rows, row_mm, ptr(ax), n_ax, ptr(w)))
+    return ax, w
 
 
 def row_pitch_mm(frequency):
@@ -585,10 +609,22 @@ class Psf:
     Slice thickness (psf.h:16-18,42,77; include/mcrt.h): elevation_size planes elevation_pitch_um apart (None: resolution_um) weighted with
     var_z.  elevation_kernel is the constant kernel exp(-z_k^2 / (2 var_z)) as the reference leaves its lateral taps (centre 1);
     elevation_rows() the table mcrt_elevation_frames takes: a row per RF row, widening away from elevation_focus_mm (None: the same row
-    everywhere), each divided by its sum unless elevation_normalize is False."""
+    everywhere), each divided by its sum unless elevation_normalize is False.
+    Frequency compounding and the depth downshift (include/mcrt.h): bands = a sequence of centre frequencies [MHz], or a dict of band_mhz=,
+    weights= and var_x= (the bands' own axial variance; None: var_x), gives an axial kernel per band and per RF row; downshift_mhz_per_mm
+    lets every centre frequency fall with depth down to min_mhz (a downshift without bands is one band at freq).  The downshift has no
+    default that the reference backs: 0, and a value is the caller's choice.  axial_rows() / band_weights() are the tables
+    mcrt_convolve_bands_frames and mcrt_band_fold_frames take."""
 
     def __init__(self, freq=4.5, var_x=0.05, var_y=0.2, var_z=0.1, axial_size=7, lateral_size=13, resolution_um=145, focus_mm=None, focal_range_mm=20.0,
-                 elevation_size=7, elevation_pitch_um=None, elevation_focus_mm=None, elevation_normalize=True):
+                 elevation_size=7, elevation_pitch_um=None, elevation_focus_mm=None, elevation_normalize=True, bands=None, downshift_mhz_per_mm=0.0, min_mhz=0.0):
+        self.bands = None
+        if bands is not None or downshift_mhz_per_mm != 0.0:
+            bd = dict(bands) if isinstance(bands, dict) else dict(band_mhz=(freq,) if bands is None else tuple(bands))
+            if bd.get("var_x") is None:
+                bd["var_x"] = var_x
+            self.bands = bands_struct(downshift_mhz_per_mm=downshift_mhz_per_mm, min_mhz=min_mhz, **bd)
+        self._band_rows = {}
         self.axial_kernel, self.lateral_kernel = host_psf(freq, var_x, var_y, resolution_um, axial_size, lateral_size)
         self.var_y, self.resolution_um = var_y, resolution_um
         self.focus_mm = tuple(float(x) for x in focus_mm) if focus_mm is not None else ()
@@ -614,6 +650,25 @@ class Psf:
     @property
     def has_focus(self):
         return len(self.focus_mm) > 0
+
+    @property
+    def has_bands(self):
+        return self.bands is not None
+
+    def _band_tables(self, n_rows, row_mm):
+        key = (n_rows, row_mm)
+        if key not in self._band_rows:
+            self._band_rows[key] = host_psf_bands(self.bands, self.resolution_um, n_rows, row_mm, self.axial_kernel.size)
+        return self._band_rows[key]
+
+    def axial_rows(self, n_rows, row_mm):
+        """the axial taps of every band and RF row, float32 [B][n_rows][axial_size], for rows row_mm apart (Simulator.row_mm); bands= or a
+        downshift only"""
+        return self._band_tables(n_rows, row_mm)[0]
+
+    def band_weights(self, n_rows, row_mm):
+        """the bands' weights on every RF row, float32 [n_rows][B] (each row the weights over their sum)"""
+        return self._band_tables(n_rows, row_mm)[1]
 
     def lateral_rows(self, n_rows, row_mm):
         """the lateral taps of every RF row, float32 [n_rows][lateral_size], for rows row_mm apart (Simulator.row_mm)"""
@@ -877,6 +932,26 @@ class Context(_SceneCalls):
         if lat.ndim != 2 or lat.shape[0] != n_rows:
             raise ValueError("lat_rows needs one row of taps per RF row: (%d, n_lat), got shape %s" % (n_rows, lat.shape))
         check(self.L.mcrt_convolve_frames_depth(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, ptr(ax), ax.size, ptr(lat), lat.shape[1]))
+
+    def convolve_bands_frames(self, rf_dev, n_frames, n_elements, n_rows, ax_rows, bands_dev, lateral=None, lat_rows=None):
+        """mcrt_convolve_bands_frames: rf_dev [n_frames][E][R] convolved into bands_dev [n_frames][B][E][R] with the axial taps of each band and
+        RF row, ax_rows [B][n_rows][n_ax], and either the lateral taps `lateral` [n_lat] or a row of them per RF row, lat_rows [n_rows][n_lat]"""
+        ax = np.ascontiguousarray(ax_rows, np.float32)
+        if ax.ndim != 3 or ax.shape[1] != n_rows:
+            raise ValueError("ax_rows needs one row of taps per band and RF row: (B, %d, n_ax), got shape %s" % (n_rows, ax.shape))
+        lat = np.ascontiguousarray(lateral, np.float32) if lateral is not None else None
+        rows = np.ascontiguousarray(lat_rows, np.float32) if lat_rows is not None else None
+        if rows is not None and (rows.ndim != 2 or rows.shape[0] != n_rows):
+            raise ValueError("lat_rows needs one row of taps per RF row: (%d, n_lat), got shape %s" % (n_rows, rows.shape))
+        n_lat = rows.shape[1] if rows is not None else lat.size if lat is not None else 0
+        check(self.L.mcrt_convolve_bands_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, ax.shape[0], ptr(ax), ax.shape[2], ptr(lat), ptr(rows), n_lat, ptr(bands_dev)))
+
+    def band_fold_frames(self, bands_dev, n_frames, n_bands, n_elements, n_rows, w_rows, rf_dev):
+        """mcrt_band_fold_frames: the band stacks [n_frames][B][E][R] folded into rf_dev [n_frames][E][R] with w_rows [n_rows][B]"""
+        w = np.ascontiguousarray(w_rows, np.float32)
+        if w.shape != (n_rows, n_bands):
+            raise ValueError("w_rows needs one row of weights per RF row: (%d, %d), got shape %s" % (n_rows, n_bands, w.shape))
+        check(self.L.mcrt_band_fold_frames(self.h, ptr(bands_dev), n_frames, n_bands, n_elements, n_rows, ptr(w), ptr(rf_dev)))
 
     def elevation_frames(self, planes_dev, n_frames, n_planes, n_elements, n_rows, w_rows, rf_dev):
         """mcrt_elevation_frames: the plane stacks [n_frames][K][E][R] folded into rf_dev [n_frames][E][R] with w_rows [n_rows][K]"""
@@ -1241,7 +1316,15 @@ class Simulator:
         mcrt_autogain_frames in place (auto_gain()) before anything gathers it: the views of a compounded frame and the planes of a sweep
         share one curve, the tracked frames of freehand() have one each.  With noise= the noise stage's sigma of every frame is the floor;
         without it the options' floor.  gain_curve() and penetration_mm() return the last run's by-products.  frame() returns RF and is
-        left alone.  Without the keyword no call changes."""
+        left alone.  Without the keyword no call changes.
+        A psf with bands (Psf(bands=...) or a downshift): frequency compounding.  convolve() then writes the stack's n images as n * B band
+        images into a band stack of its own [n][B][E][R] (mcrt_convolve_bands_frames); add_noise() acts on those, as the n * B images of one
+        frame -- one receiver, one peak, image i's band b with the id (frame_id * n + i) * B + b; envelope() detects every band image and
+        folds them back into the usual stack (mcrt_band_fold_frames), so everything downstream -- the speckle filter, auto gain, every gather,
+        compound=, sweep=, elevation=, freehand() -- sees the stack it always saw.  Without the envelope (frame(), envelope=False) the fold
+        runs alone where the envelope would have: a coherent sum of the band images, the same as one pulse that is the weighted sum of the
+        bands' -- it changes the pulse and reduces no speckle.  Without bands no call and no bit changes."""
+        self._bands_dev, self._bands_cap, self._banded = None, 0, False
         self.autogain = None if autogain is None or autogain is False else ({} if autogain is True else dict(autogain))
         if self.autogain is not None:
             autogain_opts_struct(**self.autogain)           # (unknown keywords end it here)
@@ -1313,12 +1396,13 @@ class Simulator:
 
     def close(self):
         if self.ctx.h:
-            for d in (self.rf_dev, self.planes_dev, self.views_dev, self.sweep_dev, self._ag_dev):
+            for d in (self.rf_dev, self.planes_dev, self.views_dev, self.sweep_dev, self._ag_dev, self._bands_dev):
                 if d:
                     self.ctx.free(d)
             self.ctx.close()
 
     def trace(self, frame_id=0):
+        self._banded = False
         if self._pass is None:
             self.ctx.trace_frame(frame_id, self.rf_dev)
             return
@@ -1333,14 +1417,42 @@ class Simulator:
         return row_pitch_mm(self.ctx.params.frequency)
 
     def convolve(self):
-        """over the stack's images as so many frames (mcrt_convolve is mcrt_convolve_frames of one)"""
-        if self.psf.has_focus:
+        """over the stack's images as so many frames (mcrt_convolve is mcrt_convolve_frames of one); with a psf that has bands into the band
+        stack, where the images stay until envelope() or fold_bands() brings them back"""
+        if self.psf.has_bands:
+            dev, n = self._stack
+            lat = dict(lat_rows=self.psf.lateral_rows(self.R, self.row_mm)) if self.psf.has_focus else dict(lateral=self.psf.lateral_kernel)
+            self.ctx.convolve_bands_frames(dev, n, self.E, self.R, self.psf.axial_rows(self.R, self.row_mm), self._band_stack(n), **lat)
+            self._banded = True
+        elif self.psf.has_focus:
             self.ctx.convolve_frames_depth(*self._stack, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_rows(self.R, self.row_mm))
         else:
             self.ctx.convolve_frames(*self._stack, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_kernel)
 
     def envelope(self):
-        self.ctx.envelope_frames(*self._stack, self.E, self.R)
+        if self._banded:                                # every band image is detected on its own, then they are averaged
+            self.ctx.envelope_frames(self._bands_dev, self._stack[1] * self.psf.bands.n_bands, self.E, self.R)
+            self.fold_bands()
+        else:
+            self.ctx.envelope_frames(*self._stack, self.E, self.R)
+
+    def _band_stack(self, n):
+        """the band stack for n images, [n][B][E][R] floats on the device: one buffer that only grows"""
+        need = n * self.psf.bands.n_bands * self.E * self.R * 4
+        if self._bands_cap < need:
+            if self._bands_dev is not None:
+                self.ctx.free(self._bands_dev)
+            self._bands_dev, self._bands_cap = None, 0
+            self._bands_dev, self._bands_cap = self.ctx.alloc(need), need
+        return self._bands_dev
+
+    def fold_bands(self):
+        """mcrt_band_fold_frames: the band images that convolve() left, folded back into the stack with the bands' weights (nothing to do
+        when there are none).  After envelope() that is frequency compounding; on RF it is a coherent sum"""
+        if self._banded:
+            dev, n = self._stack
+            self.ctx.band_fold_frames(self._bands_dev, n, self.psf.bands.n_bands, self.E, self.R, self.psf.band_weights(self.R, self.row_mm), dev)
+            self._banded = False
 
     def despeckle(self):
         """mcrt_speckle_frames over the stack's images, in place, with the options of speckle= (the defaults without one)"""
@@ -1361,6 +1473,13 @@ class Simulator:
         frames of one image each (the tracked frames of freehand())"""
         o = self.noise if self.noise is not None else noise_opts_struct()
         dev, n = self._stack
+        if self._banded:                                # the band images: image i's band b with the id (frame_id * n + i) * B + b
+            B = self.psf.bands.n_bands
+            kw = dict(sigma=o.sigma) if o.mode == NOISE_ABS else dict(snr_db=o.snr_db)
+            sigma_dev = self._autogain_buffers(n if own_peaks else 1)[0] if self.autogain is not None else None
+            self.ctx.noise_frames(self._bands_dev, n if own_peaks else 1, B if own_peaks else n * B, self.E, self.R, first_image_id=frame_id * n * B,
+                                  element_gain=self.noise_gain, sigma_dev=sigma_dev, seed=o.seed, **kw)
+            return
         kw = dict(sigma=o.sigma) if o.mode == NOISE_ABS else dict(snr_db=o.snr_db)
         sigma_dev = self._autogain_buffers(n if own_peaks else 1)[0] if self.autogain is not None else None   # (auto_gain()'s floor)
         self.ctx.noise_frames(dev, n if own_peaks else 1, 1 if own_peaks else n, self.E, self.R, first_image_id=frame_id * n, element_gain=self.noise_gain,
@@ -1411,6 +1530,8 @@ class Simulator:
                 self.despeckle()
             if self.autogain is not None:
                 self.auto_gain()
+        else:
+            self.fold_bands()
 
     def compound_image(self, frame_id=0, convolve=True, envelope=True, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         """trace -> convolve -> envelope -> mcrt_compound_frames -> host: the compounded float picture [out_rows][out_cols] (compound= only)"""
@@ -1496,7 +1617,7 @@ class Simulator:
         n = shape[0] * shape[1] * shape[2]
         with self.ctx.temp(F * self.E * self.R * 4) as stack_dev, self.ctx.temp(n * 4) as out, self.ctx.temp(n * 4) as cnt:
             self.ctx.trace_frames_poses(frame_id * F, pos, dirs, stack_dev)
-            held, self._stack = self._stack, (stack_dev, F)
+            held, self._stack, self._banded = self._stack, (stack_dev, F), False
             try:
                 if convolve:
                     self.convolve()
@@ -1508,6 +1629,8 @@ class Simulator:
                         self.despeckle()
                     if self.autogain is not None:
                         self.auto_gain(own_frames=True)
+                else:
+                    self.fold_bands()
             finally:
                 self._stack = held
             self.ctx.recon_frames(stack_dev, pos, dirs, F, self.E, self.R, grid, out, count_dev=cnt if counts else None, row_mm=row_mm, unit_mm=unit_mm, **opts)

@@ -84,21 +84,23 @@ struct Knobs {
 // are made on first use, all or none; the comparison is bitwise, on the caller's layout; the staging buffer is rewritten only after the
 // previous copy's event; the table has no shape until its copy is enqueued; nothing else waits for the device; and the caller's array is
 // free the moment put() returns.
+// B such tables at once (the axial taps of mcrt_convolve_bands_frames): the caller's [B][R][n] on the device as [B][n][R].
 struct StagedTable : Staging {
-    std::vector<float> on_dev; uint32_t key[2] = { 0, 0 };   // what the device holds (or is about to): the caller's bits, and R, n
-    int put(const float *src, uint32_t R, uint32_t n, size_t room, hipStream_t st)   // room: floats of the largest table this one may be given
+    std::vector<float> on_dev; uint32_t key[3] = { 0, 0, 0 };   // what the device holds (or is about to): the caller's bits, and R, n, B
+    int put(const float *src, uint32_t R, uint32_t n, size_t room, hipStream_t st, uint32_t B = 1)   // room: floats of the largest table this one may be given
     {
-        const size_t len = (size_t)n * R;
-        if (key[0] == R && key[1] == n && !memcmp(src, on_dev.data(), 4 * len)) return MCRT_OK;
+        const size_t one = (size_t)n * R, len = one * B;
+        if (key[0] == R && key[1] == n && key[2] == B && !memcmp(src, on_dev.data(), 4 * len)) return MCRT_OK;
         float *h = nullptr;
         MCRT_TRY(begin(room, st, &h));
         on_dev.resize(room);
-        for (uint32_t r = 0; r < R; r++)
-            for (uint32_t k = 0; k < n; k++) h[(size_t)k * R + r] = src[(size_t)r * n + k];
-        key[0] = key[1] = 0;
+        for (uint32_t b = 0; b < B; b++)
+            for (uint32_t r = 0; r < R; r++)
+                for (uint32_t k = 0; k < n; k++) h[b * one + (size_t)k * R + r] = src[b * one + (size_t)r * n + k];
+        key[0] = key[1] = key[2] = 0;
         MCRT_TRY(commit(len, st));
         memcpy(on_dev.data(), src, 4 * len);
-        key[0] = R; key[1] = n;
+        key[0] = R; key[1] = n; key[2] = B;
         return MCRT_OK;
     }
 };
@@ -186,6 +188,9 @@ struct ImageStages {
     // focal zones (mcrt_convolve_frames_depth): the lateral taps [n_lat][R], and slice thickness (mcrt_elevation_frames): the elevation weights
     // [K][R] (room for MCRT_MAX_ROWS x 32 each).  Two tables: a frame uses both in turn, and one shared buffer would upload both on every frame
     StagedTable lat_rows, elev_rows;
+    // frequency compounding (mcrt_convolve_bands_frames, mcrt_band_fold_frames): the axial taps [B][n_ax][R] (room for 8 x 16 x MCRT_MAX_ROWS) and
+    // the band weights [B][R] (room for MCRT_MAX_ROWS x 8), tables of their own for the same reason
+    StagedTable band_ax, band_w;
     // receiver noise (mcrt_noise_frames): the gain of every transducer element [E] of the last table (room for the largest E so far); the peaks are d_disp's
     StagedTable gain;
     // automatic gain (mcrt_autogain_frames): the histograms of a chunk of frames [frames][n_bands][2048], at most AUTOGAIN_HIST_WORDS, and the row

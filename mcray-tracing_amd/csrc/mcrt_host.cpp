@@ -384,6 +384,55 @@ extern "C" int mcrt_psf_focus_kernels(float var_y, uint32_t res_um, const mcrt_f
     return MCRT_OK;
 }
 
+// Frequency compounding and the depth downshift (the model is in include/mcrt.h): mcrt_psf_kernels' axial taps per band and per RF row, the
+// band's centre frequency falling with the row's depth down to a floor.  With no downshift f == (double)band_mhz[b] exactly, so the row is
+// mcrt_psf_kernels' own expression bit for bit.
+extern "C" int mcrt_default_bands(mcrt_bands *b, float freq, float var_x)
+{
+    if (!b) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_bands: null bands");
+    memset(b, 0, sizeof *b);
+    b->n_bands = 1u; b->band_mhz[0] = freq; b->band_weight[0] = 1.0f; b->var_x = var_x;
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_psf_band_kernels(const mcrt_bands *b, uint32_t res_um, uint32_t n_rows, double row_mm, float *ax_rows, uint32_t n_ax, float *w_rows)
+{
+    static const char fn[] = "mcrt_psf_band_kernels";
+    if (!b || !ax_rows) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null %s", fn, b ? "ax_rows" : "bands");
+    if (b->n_bands == 0 || b->n_bands > 8) return mcrt::set_error(MCRT_ERR_INVALID, "%s: n_bands must be 1..8 (%u)", fn, b->n_bands);
+    double S = 0.0;
+    for (uint32_t k = 0; k < b->n_bands; k++) {
+        if (!(std::isfinite(b->band_mhz[k]) && b->band_mhz[k] > 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: band_mhz[%u] must be finite and > 0", fn, k);
+        if (!(std::isfinite(b->band_weight[k]) && b->band_weight[k] >= 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: band_weight[%u] must be finite and >= 0", fn, k);
+        S += (double)b->band_weight[k];
+    }
+    if (!(S > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: band_weight: every one of the %u bands has weight 0", fn, b->n_bands);
+    if (!(std::isfinite(b->var_x) && b->var_x > 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: var_x must be finite and > 0", fn);
+    if (!(std::isfinite(b->downshift_mhz_per_mm) && b->downshift_mhz_per_mm >= 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: downshift_mhz_per_mm must be finite and >= 0", fn);
+    if (!(std::isfinite(b->min_mhz) && b->min_mhz >= 0.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: min_mhz must be finite and >= 0", fn);
+    if (res_um == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: res_um must be > 0", fn);
+    if (!(std::isfinite(row_mm) && row_mm > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: row_mm must be finite and > 0", fn);
+    if (n_ax == 0 || n_ax > 16) return mcrt::set_error(MCRT_ERR_INVALID, "%s: n_ax must be 1..16 (%u)", fn, n_ax);
+    if (n_rows > MCRT_MAX_ROWS) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: at most %d rows", fn, MCRT_MAX_ROWS);
+    const double pi_psf = 3.14159;
+    const float res = (float)res_um / 1000.0f;
+    const float half_ax = (float)((size_t)n_ax * res_um) / 1000.0f / 2.0f;
+    for (uint32_t k = 0; k < b->n_bands; k++)
+        for (uint32_t r = 0; r < n_rows; r++) {
+            const double z = (double)r * row_mm;
+            const double f = std::max((double)b->min_mhz, (double)b->band_mhz[k] - (double)b->downshift_mhz_per_mm * z);
+            for (uint32_t i = 0; i < n_ax; i++) {
+                const float x = (float)i * res - half_ax;
+                const double x2 = (double)x * (double)x;
+                ax_rows[((size_t)k * n_rows + r) * n_ax + i] = (float)(std::exp(-0.5f * (x2 / (double)b->var_x)) * std::cos(2 * pi_psf * f * (double)x));
+            }
+        }
+    if (w_rows)
+        for (uint32_t r = 0; r < n_rows; r++)
+            for (uint32_t k = 0; k < b->n_bands; k++) w_rows[(size_t)r * b->n_bands + k] = (float)((double)b->band_weight[k] / S);
+    return MCRT_OK;
+}
+
 // ---- transducer<N>::transducer (transducer.h:24-62) -------------------------------------------
 namespace {
 struct F3 { float x, y, z; };

@@ -93,6 +93,47 @@ extern "C" int mcrt_elevation_frames(mcrt_ctx *c, const float *planes_dev, uint3
     return MCRT_OK;
 }
 
+// ---- frequency compounding (the contracts are in include/mcrt.h) ----
+// Everything is checked before anything is launched; the caller's axial table [B][R][n_ax] goes to the device tap-major [B][n_ax][R], lat_rows as
+// mcrt_convolve_frames_depth's does (StagedTable).
+extern "C" int mcrt_convolve_bands_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, uint32_t B, const float *ax_rows, uint32_t n_ax,
+                                          const float *lateral, const float *lat_rows, uint32_t n_lat, float *bands_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_convolve_bands_frames";
+    if (!rf_dev || !bands_dev || !ax_rows || E == 0 || R == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "%s: bad arguments", fn);
+    if (!lateral == !lat_rows) return set_error(MCRT_ERR_INVALID, "%s: exactly one of lateral and lat_rows must be given (%s)", fn, lateral ? "both are" : "neither is");
+    if (B == 0 || B > 8) return set_error(MCRT_ERR_INVALID, "%s: n_bands must be 1..8 (%u)", fn, B);
+    if (n_ax == 0 || n_ax > 16 || n_lat == 0 || n_lat > 32) return set_error(MCRT_ERR_LIMIT, "kernel sizes must be 1..16 axial, 1..32 lateral");
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: at most %d rows", fn, MCRT_MAX_ROWS);
+    if ((double)n_frames * (double)B * (double)E * (double)R >= 0x1p40) return set_error(MCRT_ERR_LIMIT, "%s: the band stack is too large", fn);
+    const size_t n = (size_t)n_frames * E * R;
+    if (ranges_overlap(rf_dev, 4 * n, bands_dev, 4 * n * B)) return set_error(MCRT_ERR_INVALID, "%s: rf_dev and bands_dev overlap", fn);
+    MCRT_TRY(ensure_tmp(c, n * B));
+    MCRT_TRY(c->img.band_ax.put(ax_rows, R, n_ax, (size_t)MCRT_MAX_ROWS * 16 * 8, c->stream, B));
+    if (lat_rows) MCRT_TRY(c->img.lat_rows.put(lat_rows, R, n_lat, (size_t)MCRT_MAX_ROWS * 32, c->stream));
+    mcrt::ConvTaps t; memset(&t, 0, sizeof t);
+    if (lateral) memcpy(t.lat, lateral, 4 * n_lat);
+    t.n_ax = n_ax; t.n_lat = n_lat;
+    HIP_TRY(mcrt::launch_convolve_bands(rf_dev, c->img.d_tmp, bands_dev, n_frames, B, E, R, t, c->img.band_ax.dev, lat_rows ? c->img.lat_rows.dev.p : nullptr, c->stream));
+    return MCRT_OK;
+}
+
+// k_elevation as it is, with the band weights' own table
+extern "C" int mcrt_band_fold_frames(mcrt_ctx *c, const float *bands_dev, uint32_t n_frames, uint32_t B, uint32_t E, uint32_t R, const float *w_rows, float *rf_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_band_fold_frames";
+    if (!bands_dev || !rf_dev || !w_rows || n_frames == 0 || E == 0 || R == 0) return set_error(MCRT_ERR_INVALID, "%s: bad arguments", fn);
+    if (B == 0 || B > 8) return set_error(MCRT_ERR_INVALID, "%s: n_bands must be 1..8 (%u)", fn, B);
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: at most %d rows", fn, MCRT_MAX_ROWS);
+    if ((double)n_frames * (double)B * (double)E * (double)R >= 0x1p40) return set_error(MCRT_ERR_LIMIT, "%s: the band stack is too large", fn);
+    if (ranges_overlap(bands_dev, 4 * (size_t)n_frames * B * E * R, rf_dev, 4 * (size_t)n_frames * E * R)) return set_error(MCRT_ERR_INVALID, "%s: bands_dev and rf_dev overlap", fn);
+    MCRT_TRY(c->img.band_w.put(w_rows, R, B, (size_t)MCRT_MAX_ROWS * 8, c->stream));
+    HIP_TRY(mcrt::launch_elevation(bands_dev, rf_dev, n_frames, B, E, R, c->img.band_w.dev, c->stream));
+    return MCRT_OK;
+}
+
 extern "C" int mcrt_envelope_frames(mcrt_ctx *c, float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R)
 {
     CTX_TRY(c);

@@ -8,7 +8,7 @@
 //                    k_shade_fold (k_shade of bounce 0 with the boundary echoes of a silent start medium added in the kernel)
 //   mcrt_path.hip    k_path (the latency form: every bounce of every path in one launch)
 //   mcrt_march.hip   k_march (RF accumulation of the segments), k_material_table
-//   mcrt_post.hip    k_finalize, k_clear_flags, k_conv_* (k_conv_lateral_rows: focal zones), k_elevation (slice thickness), k_envelope, k_remap, k_transpose, k_blocks_to_frames
+//   mcrt_post.hip    k_finalize, k_clear_flags, k_conv_* (k_conv_lateral_rows: focal zones, k_conv_axial_bands: frequency compounding), k_elevation (slice thickness, the band fold), k_envelope, k_remap, k_transpose, k_blocks_to_frames
 //   mcrt_display.hip k_bmode_peak, k_bmode_grey, k_bmode (mcrt_bmode_frames: log-compressed 8-bit B-mode frames), k_compound (spatial compounding:
 //                    mcrt_compound_frames, mcrt_bmode_compound_frames)
 //   mcrt_volume.hip  k_volume (volume imaging: mcrt_volume_frames, mcrt_bmode_volume_frames)
@@ -354,6 +354,10 @@ hipError_t launch_finalize(long long *acc, uint32_t *flags, float *rf, uint32_t 
 hipError_t launch_convolve(float *img, float *tmp, uint32_t n_img, uint32_t E, uint32_t R, const ConvTaps &taps, hipStream_t st);
 // k_conv_axial, then k_conv_lateral_rows with the device table lat [taps.n_lat][R] (tap-major); taps.lat is not read
 hipError_t launch_convolve_depth(float *img, float *tmp, uint32_t n_img, uint32_t E, uint32_t R, const ConvTaps &taps, const float *lat, hipStream_t st);
+// k_conv_axial_bands (rf [F][E][R] -> tmp and bands [F][B][E][R], the device table ax [B][taps.n_ax][R] tap-major; taps.ax is not read), then the lateral pass of
+// launch_convolve (lat null: taps.lat) or of launch_convolve_depth (the device table lat) over the F * B band images
+hipError_t launch_convolve_bands(const float *rf, float *tmp, float *bands, uint32_t F, uint32_t B, uint32_t E, uint32_t R, const ConvTaps &taps,
+                                 const float *ax, const float *lat, hipStream_t st);
 // k_elevation: planes [F][K][E][R] folded into rf [F][E][R] with the device table w [K][R] (tap-major); float4 lanes where E*R and the pointers allow
 hipError_t launch_elevation(const float *planes, float *rf, uint32_t F, uint32_t K, uint32_t E, uint32_t R, const float *w, hipStream_t st);
 hipError_t launch_envelope(float *img, uint32_t E, uint32_t R, hipStream_t st);

@@ -1,5 +1,6 @@
 // mcrt_post.hip -- after the accumulation: k_finalize (fixed-point RF bins -> float image, rf_image::clear rfimage.h:161), k_conv_*
-// (rf_image::convolve, rfimage.h:93-123; k_conv_lateral_rows its lateral pass with a tap row per RF row: focal zones), k_envelope (rfimage.h:54-91), k_remap (the scan conversion of rf_image::postprocess,
+// (rf_image::convolve, rfimage.h:93-123; k_conv_lateral_rows its lateral pass with a tap row per RF row: focal zones; k_conv_axial_bands its axial pass with a tap row per
+// band and RF row: frequency compounding), k_envelope (rfimage.h:54-91), k_remap (the scan conversion of rf_image::postprocess,
 // rfimage.h:125-140), k_elevation (the elevation planes of a frame folded into one image: slice thickness), k_transpose, and k_blocks_to_frames (the ranks' blocks of an mcrt_group laid out as frames).
 #include "mcrt_device.h"
 
@@ -93,6 +94,63 @@ __global__ void k_conv_lateral_rows(const float *tmp, float *img, uint32_t n_img
 #pragma unroll
     for (int j = 0; j < C; j++)
         if (col0 + (uint32_t)j < col_end) o[(size_t)(col0 + j) * R] = conv[j];
+}
+
+// The axial pass of mcrt_convolve_bands_frames (frequency compounding, the depth downshift): k_conv_axial with taps of their own per band and per row,
+//     tmp[f][b][e][row] = sum_k rf[f][e][row+k] * ax[b][k][row],  row in [na, R-na),   ax tap-major [B][na][R] (the host transposes the caller's [B][R][na]),
+// and out[f][b][e][row] = rf[f][e][row] at EVERY pixel: the band image starts as the input's own bits, and the lateral pass then writes its window over it.
+// A lane owns one row of a strip of MCRT_BANDS_STRIP neighbouring columns, for all B bands: per tap it loads the strip's input values once and each
+// band's tap once, and adds into B x STRIP sums held in registers (indexed by unrolled constants only: no scratch).  So an input value is loaded once
+// for all the bands, a tap once for the whole strip -- (STRIP + B) loads per tap for B * STRIP sums, where B calls of k_conv_axial take B * STRIP --
+// and neighbouring lanes are neighbouring rows: every tap load and every input load of a wavefront is one contiguous line.  Each sum is still
+// sequential over k from 0.0f, one rounding per multiply and per add.  (20 x 128 x 465 images, 3 bands, 7 / 13 taps, the whole
+// call: 46.7 us at 4 columns, 47.9 at 8, 52.1 at 2, 54.7 at 1; three calls of mcrt_convolve_frames 62.4 us -- DESIGN 5.18)
+#ifndef MCRT_BANDS_STRIP
+#define MCRT_BANDS_STRIP 4
+#endif
+#define MCRT_MAX_BANDS 8
+__global__ void k_conv_axial_bands(const float *rf, float *tmp, float *out, uint32_t F, uint32_t B, uint32_t E, uint32_t R, uint32_t na,
+                                   uint32_t n_strips, const float *ax)
+{
+    constexpr int C = MCRT_BANDS_STRIP;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)F * n_strips * R) return;
+    const uint32_t row = (uint32_t)(i % R);
+    const size_t sf = i / R;                                                    // frame * n_strips + strip
+    const uint32_t col0 = (uint32_t)(sf % n_strips) * (uint32_t)C, f = (uint32_t)(sf / n_strips);
+    const bool inside = row >= na && row + na < R;                              // a row of the window: row + k < R for every tap
+    const float *p = rf + ((size_t)f * E + col0) * R + row;                     // column col0 + j at p[j * R]
+    float acc[MCRT_MAX_BANDS][C], first[C];
+#pragma unroll
+    for (int b = 0; b < MCRT_MAX_BANDS; b++)
+#pragma unroll
+        for (int j = 0; j < C; j++) acc[b][j] = 0.0f;
+#pragma unroll
+    for (int j = 0; j < C; j++) first[j] = col0 + (uint32_t)j < E ? p[(size_t)j * R] : 0.0f;
+    const uint32_t nk = inside ? na : 0u;
+    for (uint32_t k = 0; k < nk; k++) {
+        float v[C];
+#pragma unroll
+        for (int j = 0; j < C; j++) v[j] = col0 + (uint32_t)j < E ? p[(size_t)j * R + k] : 0.0f;
+#pragma unroll
+        for (int b = 0; b < MCRT_MAX_BANDS; b++)
+            if ((uint32_t)b < B) {
+                const float w = ax[((size_t)b * na + k) * R + row];
+#pragma unroll
+                for (int j = 0; j < C; j++) acc[b][j] += v[j] * w;
+            }
+    }
+#pragma unroll
+    for (int b = 0; b < MCRT_MAX_BANDS; b++)
+        if ((uint32_t)b < B) {
+            const size_t o = (((size_t)f * B + (uint32_t)b) * E + col0) * R + row;
+#pragma unroll
+            for (int j = 0; j < C; j++)
+                if (col0 + (uint32_t)j < E) {
+                    out[o + (size_t)j * R] = first[j];
+                    if (inside) tmp[o + (size_t)j * R] = acc[b][j];
+                }
+        }
 }
 
 // mcrt_elevation_frames (psf.h:16-18,42,77; the contract is in mcrt.h): the K elevation planes of every frame folded into one RF image,
@@ -231,12 +289,24 @@ hipError_t launch_finalize(long long *acc, uint32_t *flags, float *rf, uint32_t 
     return hipGetLastError();
 }
 
+// the lateral pass over n_img images, tmp -> img: k_conv_lateral_rows with the device table lat [taps.n_lat][R] where one is given, else k_conv_lateral with taps.lat
+static void launch_conv_lateral(const float *tmp, float *img, uint32_t n_img, uint32_t E, uint32_t R, const ConvTaps &taps, const float *lat, hipStream_t st)
+{
+    const size_t n = (size_t)n_img * E * R;
+    const uint32_t na = taps.n_ax, nl = taps.n_lat;
+    if (!lat) hipLaunchKernelGGL(k_conv_lateral, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tmp, img, n_img, E, R, taps);
+    else if (R > 2u * na && E > nl + nl / 2u) {                                 // else the lateral window is empty (as in k_conv_lateral)
+        const uint32_t n_strips = (E - nl - nl / 2u + MCRT_CONV_STRIP - 1u) / MCRT_CONV_STRIP;
+        const size_t m = (size_t)n_img * n_strips * (R - 2u * na);
+        hipLaunchKernelGGL(k_conv_lateral_rows, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, tmp, img, n_img, E, R, na, nl, n_strips, lat);
+    }
+}
+
 hipError_t launch_convolve(float *img, float *tmp, uint32_t n_img, uint32_t E, uint32_t R, const ConvTaps &taps, hipStream_t st)
 {
     const size_t n = (size_t)n_img * E * R;
-    const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
-    hipLaunchKernelGGL(k_conv_axial, grid, blk, 0, st, (const float *)img, tmp, n_img, E, R, taps);
-    hipLaunchKernelGGL(k_conv_lateral, grid, blk, 0, st, (const float *)tmp, img, n_img, E, R, taps);
+    hipLaunchKernelGGL(k_conv_axial, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float *)img, tmp, n_img, E, R, taps);
+    launch_conv_lateral(tmp, img, n_img, E, R, taps, nullptr, st);
     return hipGetLastError();
 }
 
@@ -244,12 +314,17 @@ hipError_t launch_convolve_depth(float *img, float *tmp, uint32_t n_img, uint32_
 {
     const size_t n = (size_t)n_img * E * R;
     hipLaunchKernelGGL(k_conv_axial, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float *)img, tmp, n_img, E, R, taps);
-    const uint32_t na = taps.n_ax, nl = taps.n_lat;
-    if (R > 2u * na && E > nl + nl / 2u) {                                      // else the lateral window is empty (as in k_conv_lateral)
-        const uint32_t n_strips = (E - nl - nl / 2u + MCRT_CONV_STRIP - 1u) / MCRT_CONV_STRIP;
-        const size_t m = (size_t)n_img * n_strips * (R - 2u * na);
-        hipLaunchKernelGGL(k_conv_lateral_rows, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const float *)tmp, img, n_img, E, R, na, nl, n_strips, lat);
-    }
+    launch_conv_lateral(tmp, img, n_img, E, R, taps, lat, st);
+    return hipGetLastError();
+}
+
+hipError_t launch_convolve_bands(const float *rf, float *tmp, float *bands, uint32_t F, uint32_t B, uint32_t E, uint32_t R, const ConvTaps &taps,
+                                 const float *ax, const float *lat, hipStream_t st)
+{
+    const uint32_t n_strips = (E + MCRT_BANDS_STRIP - 1u) / MCRT_BANDS_STRIP;
+    const size_t m = (size_t)F * n_strips * R;
+    hipLaunchKernelGGL(k_conv_axial_bands, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, rf, tmp, bands, F, B, E, R, taps.n_ax, n_strips, ax);
+    launch_conv_lateral(tmp, bands, F * B, E, R, taps, lat, st);
     return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@
 //                   [--speckle N [--speckle-q0 X] [--speckle-rho X] [--speckle-lambda X]]
 //                   [--speckle3d N [--speckle3d-q0 X] [--speckle3d-rho X] [--speckle3d-lambda X]]
 //                   [--noise-db X | --noise-sigma X [--noise-seed N] [--dead-elements a,b,c]]
+//                   [--freq-compound N [--freq-span-mhz X]] [--freq-var-x V] [--downshift-mhz-per-mm X [--downshift-min-mhz X]]
 //                   [--autogain [--autogain-band N] [--autogain-floor-scale X] [--autogain-max-db X] [--autogain-curve FILE.txt]]
 //                   [--freehand N --freehand-step-mm D [--freehand-fan-deg A] --freehand-box-mm X0,Y0,Z0,X1,Y1,Z1 --freehand-voxel-mm P --freehand-out FILE.raw
 //                    [--freehand-mode mean|max] [--freehand-fill H]]
@@ -81,6 +82,14 @@
 // no floor; a band's gain stays within +- --autogain-max-db X (60).  The penetration depth of the last frame is printed, and
 // --autogain-curve FILE.txt writes its row gains, one "row depth_mm gain" line per RF row.  The three need --autogain.  rf.bin holds the
 // gained image.  Without --autogain nothing changes.
+// --freq-compound N (1..8) is receive-side frequency compounding (mcrt_convolve_bands_frames, mcrt_band_fold_frames): the received band is split
+// into N sub-bands, evenly spaced over the probe's 4.5 MHz +- --freq-span-mhz X / 2 (2 MHz) with equal weights; every image is convolved with each
+// band's pulse, every band image is detected on its own and the detected images are averaged -- speckle falls at the price of axial resolution,
+// and no second trace is needed.  It combines with every path above (the views of --compound, the planes of --sweep, --freehand, --noise-db: the
+// noise is then added to the band images).  --freq-var-x V is the axial variance of the bands' pulses in mm^2 (0.05, the reference's; a sub-band's
+// pulse is longer).  --downshift-mhz-per-mm X lets every band's centre frequency fall with depth, down to --downshift-min-mhz X (0): the pulse
+// loses its high frequencies on the way down; alone it is one band at 4.5 MHz.  It has no default that the reference backs: a value is the
+// caller's choice.  --freq-compound 1 alone is the plain run byte for byte.
 // --freehand N (1..1024) adds a freehand 3-D acquisition after the frames of the run: the probe is moved by hand, here along its elevation axis
 // in N steps of --freehand-step-mm D centred on the scene's pose, step k tilted by (k - (N-1)/2) x --freehand-fan-deg A (0) about the line through
 // the arc's apex; the N frames are traced as one pass with the last frame's number, convolved, enveloped (and despeckled with --speckle) and
@@ -157,6 +166,7 @@ int main(int argc, char **argv)
     bool autogain = false;
     const char *autogain_band = nullptr, *autogain_scale = nullptr, *autogain_max_db = nullptr, *autogain_curve = nullptr;   // the options as given
     mcrt_autogain_opts aopts; mcrt_default_autogain_opts(&aopts);
+    const char *freq_compound = nullptr, *freq_span = nullptr, *freq_var_x = nullptr, *downshift = nullptr, *downshift_min = nullptr;   // the options as given
     const char *freehand_n = nullptr, *freehand_step = nullptr, *freehand_fan = nullptr, *freehand_box = nullptr, *freehand_voxel = nullptr, *freehand_out = nullptr,
                *freehand_mode = nullptr, *freehand_fill = nullptr;   // the options as given
     mcrt_recon_opts fopts; mcrt_default_recon_opts(&fopts);
@@ -212,6 +222,11 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--autogain-floor-scale") && i + 1 < argc) autogain_scale = argv[++i];
             else if (!std::strcmp(argv[i], "--autogain-max-db") && i + 1 < argc) autogain_max_db = argv[++i];
             else if (!std::strcmp(argv[i], "--autogain-curve") && i + 1 < argc) autogain_curve = argv[++i];
+            else if (!std::strcmp(argv[i], "--freq-compound") && i + 1 < argc) freq_compound = argv[++i];
+            else if (!std::strcmp(argv[i], "--freq-span-mhz") && i + 1 < argc) freq_span = argv[++i];
+            else if (!std::strcmp(argv[i], "--freq-var-x") && i + 1 < argc) freq_var_x = argv[++i];
+            else if (!std::strcmp(argv[i], "--downshift-mhz-per-mm") && i + 1 < argc) downshift = argv[++i];
+            else if (!std::strcmp(argv[i], "--downshift-min-mhz") && i + 1 < argc) downshift_min = argv[++i];
             else if (!std::strcmp(argv[i], "--freehand") && i + 1 < argc) freehand_n = argv[++i];
             else if (!std::strcmp(argv[i], "--freehand-step-mm") && i + 1 < argc) freehand_step = argv[++i];
             else if (!std::strcmp(argv[i], "--freehand-fan-deg") && i + 1 < argc) freehand_fan = argv[++i];
@@ -378,6 +393,29 @@ int main(int argc, char **argv)
             aopts.max_gain = (float)std::pow(10.0, db / 20.0);
             if (!(std::isfinite(db) && db >= 0.0 && std::isfinite(aopts.max_gain))) throw std::invalid_argument("--autogain-max-db takes a finite number of dB >= 0");
         }
+        if (!freq_compound && freq_span) throw std::invalid_argument("--freq-span-mhz needs --freq-compound");
+        if (!downshift && downshift_min) throw std::invalid_argument("--downshift-min-mhz needs --downshift-mhz-per-mm");
+        mcrt_bands bands; mcrt_default_bands(&bands, transducer_frequency, 0.05f);
+        // (--freq-compound 1 alone leaves the plain run as it is; a pulse or a downshift of its own is one band through the band path)
+        const bool with_bands = (freq_compound && std::atol(freq_compound) != 1) || freq_var_x || downshift;
+        if (freq_compound) {
+            const long n = std::atol(freq_compound);
+            if (n < 1 || n > 8) throw std::invalid_argument("--freq-compound takes 1..8 bands");
+            const double span = freq_span ? std::atof(freq_span) : 2.0;
+            if (!(std::isfinite(span) && span >= 0.0)) throw std::invalid_argument("--freq-span-mhz takes a finite span >= 0");
+            bands.n_bands = (uint32_t)n;
+            for (long b = 0; b < n; b++) {
+                bands.band_mhz[b] = n > 1 ? (float)((double)transducer_frequency - span / 2.0 + span * (double)b / (double)(n - 1)) : transducer_frequency;
+                bands.band_weight[b] = 1.0f;
+            }
+        }
+        if (freq_var_x) bands.var_x = (float)std::atof(freq_var_x);
+        if (downshift) bands.downshift_mhz_per_mm = (float)std::atof(downshift);
+        if (downshift_min) bands.min_mhz = (float)std::atof(downshift_min);
+        if (with_bands) {   // the model's own checks, before anything is traced
+            float taps[8 * 7];
+            if (mcrt_psf_band_kernels(&bands, resolution, 1, rf_image_::row_mm(), taps, 7, nullptr) != MCRT_OK) throw std::invalid_argument(std::string("--freq-compound: ") + mcrt_last_error());
+        }
         if (!freehand_n && (freehand_step || freehand_fan || freehand_box || freehand_voxel || freehand_out || freehand_mode || freehand_fill))
             throw std::invalid_argument("--freehand-step-mm, --freehand-fan-deg, --freehand-box-mm, --freehand-voxel-mm, --freehand-out, --freehand-mode and --freehand-fill need --freehand");
         long freehand_frames = 0; double freehand_step_mm = 0.0, freehand_fan_deg = 0.0;
@@ -440,6 +478,7 @@ int main(int argc, char **argv)
             psf_ p{ transducer_frequency, 0.05f, 0.2f, var_z };
             if (!focus_mm.empty()) p.set_focus(focus_mm.data(), (uint32_t)focus_mm.size(), focal_range_mm);
             if (elevation_given) p.set_elevation((uint32_t)elevation_pitch_um);
+            if (with_bands) p.set_bands(bands);
             return p;
         }();
         const auto &t_pos = cfg.at("transducerPosition");

@@ -407,6 +407,17 @@ public:
         }
         return table;
     }
+    // frequency compounding and the depth downshift (the model in mcrt.h): the received band split into b.n_bands sub-bands, each with an axial
+    // kernel of its own per RF row (mcrt_psf_band_kernels; b.var_x is the bands' own axial variance).  rf_image::convolve then writes a band
+    // stack, add_noise acts on it and envelope() detects every band image and folds them back.  A downshift has no default that the reference
+    // backs: a value is the caller's choice.  The struct is checked when the tables are made (by the first convolve).
+    void set_bands(const mcrt_bands &b) { band = b; with_bands = true; band_table.clear(); band_rows = 0; }
+    bool has_bands() const { return with_bands; }
+    uint32_t n_bands() const { return with_bands ? band.n_bands : 0u; }
+    // the axial taps of every band and RF row [B][n_rows][axial_size] for rows row_mm apart, and the bands' weights [n_rows][B]; made once per
+    // (n_rows, row_mm)
+    const std::vector<float> &axial_rows(uint32_t n_rows, double row_mm) const { band_tables(n_rows, row_mm); return band_table; }
+    const std::vector<float> &band_weights(uint32_t n_rows, double row_mm) const { band_tables(n_rows, row_mm); return band_wtable; }
     constexpr size_t get_axial_size() const { return axial_size; }
     constexpr size_t get_lateral_size() const { return lateral_size; }
     constexpr size_t get_elevation_size() const { return elevation_size; }
@@ -419,6 +430,16 @@ private:
     mutable std::vector<float> table; mutable uint32_t table_rows = 0; mutable double table_row_mm = 0.0;
     mcrt_focus elev_focus{}; uint32_t elev_pitch_um = resolution_micrometers; bool elev_normalize = true;
     mutable std::vector<float> elev_table; mutable uint32_t elev_rows = 0, elev_planes = 0; mutable double elev_row_mm = 0.0;
+    mcrt_bands band{}; bool with_bands = false;
+    mutable std::vector<float> band_table, band_wtable; mutable uint32_t band_rows = 0; mutable double band_row_mm = 0.0;
+    void band_tables(uint32_t n_rows, double row_mm) const
+    {
+        if (!band_table.empty() && band_rows == n_rows && band_row_mm == row_mm) return;
+        const uint32_t B = band.n_bands >= 1 && band.n_bands <= 8 ? band.n_bands : 1u;     // (any other count is refused below: the size only has to exist)
+        std::vector<float> t((size_t)B * n_rows * axial_size), w((size_t)n_rows * B);
+        check(mcrt_psf_band_kernels(&band, resolution_micrometers, n_rows, row_mm, t.data(), (uint32_t)axial_size, w.data()), "psf bands");
+        band_table = std::move(t); band_wtable = std::move(w); band_rows = n_rows; band_row_mm = row_mm;
+    }
 };
 
 // ---------------------------------------------------------------- GPU context shared by scene and rf_image
@@ -695,7 +716,7 @@ public:
 
     rf_image(double radius_mm, double angle_rad, std::shared_ptr<device> dev_ = nullptr)
         : dev(dev_ ? std::move(dev_) : default_device()), radius_mm(radius_mm), angle(angle_rad), host((size_t)columns * max_rows, 0.0f),
-          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev), sound(dev), sigma(dev), curve(dev)
+          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev), sound(dev), sigma(dev), curve(dev), band_stack(dev)
     {
         std::cout << "rf_image: " << max_rows << ", " << columns << std::endl;          // rfimage.h:30
         rf.reserve(sizeof(float) * columns * max_rows);
@@ -713,7 +734,7 @@ public:
     }
     constexpr double get_dt() const { return (double)axial_resolution_um / (double)speed_of_sound; }                      // [us] rfimage.h:43-46
     constexpr double micros_traveled(double microm_from_source) const { return microm_from_source / (double)speed_of_sound; }   // rfimage.h:48-51
-    void clear() { std::fill(host.begin(), host.end(), 0.0f); where = on_host; }                                       // rfimage.h:161-164
+    void clear() { std::fill(host.begin(), host.end(), 0.0f); where = on_host; banded = 0; }                                     // rfimage.h:161-164
     void print(size_t column) const                                                                                       // rfimage.h:166-173
     {
         const auto img = intensities();
@@ -726,7 +747,7 @@ public:
     {
         shape_params();
         check(dev->trace_frames(frame_id, 1, columns, rf.as<float>()), "mcrt_trace_frame");       // (every GPU of a group traces its scan-line shard)
-        where = on_device; holds = stack_of::nothing; n_views = 0; first_id = frame_id; sigma_frames = 0;
+        where = on_device; holds = stack_of::nothing; n_views = 0; first_id = frame_id; sigma_frames = 0; banded = 0;
     }
     // the same with slice thickness (psf.h:16-18,42,77; mcrt.h): the frame's n_planes elevation planes (0: the psf's elevation_size), spread
     // p.elevation_pitch_um() apart around the transducer's own plane, traced as ONE pose pass -- plane k with frame id frame_id * K + k, the
@@ -739,7 +760,7 @@ public:
         const std::vector<float> &w = p.elevation_rows(max_rows, (double)axial_resolution_um / 1000.0, K);
         pose_pass(frame_id, K, tables, planes, "rf_image::trace: frame_id * n_planes does not fit a frame id");
         check(mcrt_elevation_frames(dev->ctx, planes.as<float>(), 1, K, columns, max_rows, w.data(), rf.as<float>()), "mcrt_elevation_frames");
-        where = on_device; holds = stack_of::nothing; n_views = 0; first_id = frame_id; sigma_frames = 0;
+        where = on_device; holds = stack_of::nothing; n_views = 0; first_id = frame_id; sigma_frames = 0; banded = 0;
     }
     // spatial compounding (mcrt.h): the frame's views, one per steering angle [rad] of steer_rad (1..16), traced as ONE pose pass -- view n with
     // frame id frame_id * N + n, the frame-id rule of mcrt.h -- into a stack [N][columns][max_rows] this image owns.  convolve() and envelope()
@@ -751,7 +772,7 @@ public:
         const uint32_t V = (uint32_t)steer_rad.size();
         if (V == 0 || V > 16) throw std::invalid_argument("rf_image::trace: 1..16 steering angles");
         pose_pass(frame_id, V, t.steered(steer_rad), stack, "rf_image::trace: frame_id * views does not fit a frame id");
-        holds = stack_of::views; n_views = V; first_id = frame_id * V; sigma_frames = 0;
+        holds = stack_of::views; n_views = V; first_id = frame_id * V; sigma_frames = 0; banded = 0;
     }
     // volume imaging (mcrt.h): the K planes of a probe swept in elevation, traced as ONE pose pass -- plane k with frame id frame_id * K + k, the
     // frame-id rule of mcrt.h -- into the stack [K][columns][max_rows] the views of a compounded frame use.  convolve() and envelope() then run
@@ -762,7 +783,7 @@ public:
         static_assert(N == columns, "one scan-line per transducer element");
         if (sw.n_planes == 0 || sw.n_planes > 256) throw std::invalid_argument("rf_image::trace: a sweep has 1..256 planes");
         pose_pass(frame_id, sw.n_planes, t.swept(sw), stack, "rf_image::trace: frame_id * planes does not fit a frame id");
-        holds = stack_of::sweep_planes; n_views = sw.n_planes; sweep = sw; first_id = frame_id * sw.n_planes; sigma_frames = 0;
+        holds = stack_of::sweep_planes; n_views = sw.n_planes; sweep = sw; first_id = frame_id * sw.n_planes; sigma_frames = 0; banded = 0;
     }
     // freehand 3-D (mcrt.h: mcrt_recon_frames): the frames of a tracked probe moved by hand, one pose per frame -- a vector of transducers, or the
     // two tables [F][columns][3] (transducer::freehand makes a regular one) --, traced as ONE pose pass -- pose f with frame id frame_id * F + f
@@ -774,7 +795,7 @@ public:
         if (F == 0 || F > 65535 || pos.size() != F * one || dir.size() != pos.size()) throw std::invalid_argument("rf_image::trace: pose tables [F][columns][3], F = 1..65535");
         tracked.pos = pos; tracked.dir = dir;
         pose_pass(frame_id, (uint32_t)F, tracked, stack, "rf_image::trace: frame_id * poses does not fit a frame id");
-        holds = stack_of::tracked_frames; n_views = (uint32_t)F; first_id = frame_id * (uint32_t)F; sigma_frames = 0;
+        holds = stack_of::tracked_frames; n_views = (uint32_t)F; first_id = frame_id * (uint32_t)F; sigma_frames = 0; banded = 0;
     }
     template <size_t N> void trace(uint32_t frame_id, const std::vector<transducer<N>> &poses)
     {
@@ -834,6 +855,18 @@ public:
         float *img = rf.as<float>(); uint32_t frames = 1;
         if (n_views) { img = stack.as<float>(); frames = n_views; }     // the views of a compounded frame (the planes of a sweep) as so many frames
         else to_device();
+        if (p.has_bands()) {   // frequency compounding: the images go to the band stack, where add_noise() finds them and envelope() / fold_bands() brings them back
+            const double row_mm = (double)axial_resolution_um / 1000.0;
+            const std::vector<float> &ax = p.axial_rows(max_rows, row_mm);
+            const uint32_t B = p.n_bands();
+            band_w = p.band_weights(max_rows, row_mm);
+            band_stack.reserve(sizeof(float) * frames * B * columns * max_rows);
+            check(mcrt_convolve_bands_frames(dev->ctx, img, frames, columns, max_rows, B, ax.data(), (uint32_t)p.get_axial_size(),
+                                             p.has_focus() ? nullptr : p.lateral_kernel.data(), p.has_focus() ? p.lateral_rows(max_rows, row_mm).data() : nullptr,
+                                             (uint32_t)p.get_lateral_size(), band_stack.as<float>()), "mcrt_convolve_bands_frames");
+            banded = B;
+            return;
+        }
         if (p.has_focus()) {   // focal zones: a lateral kernel per row, rows axial_resolution_um / 1000 mm apart
             const std::vector<float> &lat = p.lateral_rows(max_rows, (double)axial_resolution_um / 1000.0);
             check(mcrt_convolve_frames_depth(dev->ctx, img, frames, columns, max_rows, p.axial_kernel.data(), (uint32_t)p.get_axial_size(), lat.data(), (uint32_t)p.get_lateral_size()), "mcrt_convolve_frames_depth");
@@ -842,20 +875,42 @@ public:
         if (n_views) check(mcrt_convolve_frames(dev->ctx, img, frames, columns, max_rows, p.axial_kernel.data(), (uint32_t)p.get_axial_size(), p.lateral_kernel.data(), (uint32_t)p.get_lateral_size()), "mcrt_convolve_frames");
         else check(mcrt_convolve(dev->ctx, img, columns, max_rows, p.axial_kernel.data(), (uint32_t)p.get_axial_size(), p.lateral_kernel.data(), (uint32_t)p.get_lateral_size()), "mcrt_convolve");
     }
+    // the band images that convolve(p) left (p.has_bands()) folded back into the images with the bands' weights (mcrt_band_fold_frames); nothing
+    // to do when there are none.  envelope() ends in it: detected band images averaged, frequency compounding.  Called on its own, before any
+    // envelope, it is a coherent sum: the same as one pulse that is the weighted sum of the bands', and it reduces no speckle
+    void fold_bands()
+    {
+        if (!banded) return;
+        float *img = n_views ? stack.as<float>() : rf.as<float>();
+        check(mcrt_band_fold_frames(dev->ctx, band_stack.as<float>(), n_views ? n_views : 1u, banded, columns, max_rows, band_w.data(), img), "mcrt_band_fold_frames");
+        banded = 0;
+    }
     void envelope()
     {
+        if (banded) {
+            check(mcrt_envelope_frames(dev->ctx, band_stack.as<float>(), (n_views ? n_views : 1u) * banded, columns, max_rows), "mcrt_envelope_frames");
+            fold_bands();
+            return;
+        }
         if (n_views) { check(mcrt_envelope_frames(dev->ctx, stack.as<float>(), n_views, columns, max_rows), "mcrt_envelope_frames"); return; }
         to_device(); check(mcrt_envelope(dev->ctx, rf.as<float>(), columns, max_rows), "mcrt_envelope");
     }
     // receiver noise (mcrt.h: mcrt_noise_frames): a noise floor and a gain per scan-line (element_gain: [columns] or null) over whatever the
     // last trace() filled, in place -- this image, or the views of a compounded frame or the planes of a sweep as ONE frame (one receiver,
     // one peak), or the tracked frames of a freehand pass as so many frames -- with the ids that trace used.  It goes after convolve() and
-    // before envelope(): receive noise is uncorrelated between scan-lines.  Every frame's sigma stays on the device for autogain()
+    // before envelope(): receive noise is uncorrelated between scan-lines.  Every frame's sigma stays on the device for autogain().  After a
+    // convolve(p) with bands it acts on the band images, B per image of the same frame, image i's band b with the id (first id + i) * B + b
     void add_noise(const mcrt_noise_opts &o, const float *element_gain = nullptr)
     {
         const bool own = holds == stack_of::tracked_frames;
         const uint32_t F = n_views && own ? n_views : 1u;
         sigma.reserve(4 * (size_t)F);
+        if (banded) {          // the band images: image i's band b with the id (first_id + i) * B + b
+            check(mcrt_noise_frames(dev->ctx, band_stack.as<float>(), F, (own || !n_views ? 1u : n_views) * banded, columns, max_rows, first_id * banded, &o, element_gain,
+                                    sigma.as<float>()), "mcrt_noise_frames");
+            sigma_frames = F;
+            return;
+        }
         if (n_views) {
             check(mcrt_noise_frames(dev->ctx, stack.as<float>(), F, own ? 1u : n_views, columns, max_rows, first_id, &o, element_gain, sigma.as<float>()), "mcrt_noise_frames");
             sigma_frames = F;
@@ -1187,6 +1242,9 @@ private:
     uint32_t label_planes = 0; const unsigned char *label_tissue = nullptr;   // ... their leading axis (nothing: 0) and the tissue table
     device_buffer sound;                         // transmission(): the transmit, reflect and crossings tables in one allocation
     device_buffer sigma, curve;                  // add_noise(): every frame's sigma; autogain(): the row gains and the penetration depths
+    device_buffer band_stack;                    // convolve(p) with p.has_bands(): the band images [images][B][columns][max_rows] (grown, never shrunk)
+    uint32_t banded = 0;                         // ... B while they wait there for envelope() / fold_bands() (0: the images are where trace() left them)
+    std::vector<float> band_w;                   // ... and the bands' weights [max_rows][B] they are folded with
     uint32_t sound_planes = 0;                   // ... their leading axis (nothing yet: 0)
 };
 
