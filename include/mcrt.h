@@ -58,6 +58,7 @@ extern "C" {
                                    + mcrt_debug_beam_order, mcrt_debug_beam_layout (the beam order of a bounce run by beams, its layout on the host; additive);
                                    + mcrt_debug_beam_scan (the kernel that lays a beam order out, run alone on given counters; additive);
                                    + mcrt_debug_beam_records (the records, candidate lists and group keys of the last bounce a pass ran by beams; additive);
+                                   + mcrt_debug_beam_entries (the planes and padded bounds stored with those lists' entries; additive);
                                    + mcrt_noise_opts, mcrt_default_noise_opts, mcrt_noise_draws, mcrt_noise_frames (receiver noise: a Gaussian noise floor
                                    from integer Philox sums and a gain per transducer element, over the RF stack in place; additive);
                                    + mcrt_transmit_opts, mcrt_default_transmit_opts, mcrt_transmit_boundary, mcrt_transmit_frames (acoustic ground truth:
@@ -1320,6 +1321,15 @@ int mcrt_debug_beam_scan(mcrt_ctx *ctx, const uint32_t *counts, uint32_t n, uint
  * bounce b did not run by beams.  records, lists and keys may each be null (info alone sizes them).  Copies only; waits for the stream. */
 #define MCRT_DEBUG_BEAM_REC 16
 int mcrt_debug_beam_records(mcrt_ctx *ctx, uint32_t b, uint32_t info[5], uint32_t *records, uint32_t *lists, uint64_t *keys);
+/* beside every entry of mcrt_debug_beam_records' lists, what the beam stage stored of the entry's TRIANGLE ALONE and tests its rays with: info as
+ * mcrt_debug_beam_records'; entries[info[4]][info[1]][MCRT_DEBUG_BEAM_ENTRY] words of floats: the plane n.x n.y n.z dot(v0, n), n = (v1 - v0) x (v2 - v0) |
+ * the triangle's padded bounds lo.x lo.y lo.z | hi.x hi.y hi.z (pad = 2e-4 x the largest extent + the scene's absolute pad); the entries past a record's
+ * count are stale;
+ * begin_id[info[4]][info[1]][2]: the two further words stored there, which the list test reads in place of the list's own -- the depth at which the padded
+ * bounds begin (the list's word 7) and the triangle's id (the list's word 3).  The same bounce, the same errors; entries and begin_id may each be null.
+ * Copies only; waits for the stream. */
+#define MCRT_DEBUG_BEAM_ENTRY 10
+int mcrt_debug_beam_entries(mcrt_ctx *ctx, uint32_t b, uint32_t info[5], uint32_t *entries, uint32_t *begin_id);
 /* TEST HOOK, refused (MCRT_ERR_INVALID) unless the context was created with MCRT_TEST_HOOKS set in the environment: ORs `bits` into the
  * context's device error word on its stream, as an abandoned launch would (bit 0: traversal stack ran out, bit 1: kernel watchdog
  * expired) -- what mcrt_synchronize reports and what turns finalised RF images into NaN until it is asked */

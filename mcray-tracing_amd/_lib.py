@@ -155,7 +155,7 @@ SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create"
            "mcrt_envelope", "mcrt_scan_convert", "mcrt_default_bmode", "mcrt_bmode_frames", "mcrt_export_rf", "mcrt_alloc", "mcrt_free", "mcrt_memcpy_d2h",
            "mcrt_memcpy_h2d", "mcrt_enable_stats", "mcrt_get_stats", "mcrt_enable_timing", "mcrt_get_kernel_time", "mcrt_get_kernel_times",
            "mcrt_build_bvh", "mcrt_free_bvh", "mcrt_get_bvh", "mcrt_build_bvh4", "mcrt_free_bvh4", "mcrt_get_bvh4", "mcrt_row_thresholds", "mcrt_generate_texture", "mcrt_psf_kernels", "mcrt_psf_focus_kernels",
-           "mcrt_transducer_elements", "mcrt_transducer_elevation_axis", "mcrt_elevation_planes", "mcrt_psf_elevation_kernels", "mcrt_elevation_frames", "mcrt_debug_math", "mcrt_debug_philox", "mcrt_debug_stamps", "mcrt_debug_tail_histograms", "mcrt_debug_set_error", "mcrt_debug_fast_paths", "mcrt_debug_beam", "mcrt_debug_beam_bounce", "mcrt_debug_beam_order", "mcrt_debug_beam_layout", "mcrt_debug_beam_scan", "mcrt_debug_beam_records", "mcrt_scan_maps",
+           "mcrt_transducer_elements", "mcrt_transducer_elevation_axis", "mcrt_elevation_planes", "mcrt_psf_elevation_kernels", "mcrt_elevation_frames", "mcrt_debug_math", "mcrt_debug_philox", "mcrt_debug_stamps", "mcrt_debug_tail_histograms", "mcrt_debug_set_error", "mcrt_debug_fast_paths", "mcrt_debug_beam", "mcrt_debug_beam_bounce", "mcrt_debug_beam_order", "mcrt_debug_beam_layout", "mcrt_debug_beam_scan", "mcrt_debug_beam_records", "mcrt_debug_beam_entries", "mcrt_scan_maps",
            "mcrt_group_create", "mcrt_group_destroy", "mcrt_group_size", "mcrt_group_root", "mcrt_group_member", "mcrt_group_shard", "mcrt_group_set_params",
            "mcrt_group_set_bvh_builder", "mcrt_group_upload_scene", "mcrt_group_update_triangles", "mcrt_group_refit_triangles", "mcrt_group_upload_texture",
            "mcrt_group_set_transducer", "mcrt_group_trace_frames", "mcrt_group_trace_frames_poses", "mcrt_group_synchronize", "mcrt_group_last_pass_ms", "mcrt_group_last_scene_seconds",
@@ -266,7 +266,7 @@ def load_library():
         "mcrt_default_recon_label_opts": [C.POINTER(ReconLabelOpts), u32],
         "mcrt_recon_label_frames": [vp, vp, u32, u32, u32, vp, vp, C.c_double, C.c_double, C.POINTER(VolumeGrid), C.POINTER(ReconLabelOpts), vp, vp, vp, vp],
         "mcrt_render_label_frames": [vp, vp, u32, u32, u32, u32, C.POINTER(RenderView), vp, vp],
-        "mcrt_debug_math": [vp, i32, vp, vp, vp, u32], "mcrt_debug_philox": [vp, vp, vp, vp], "mcrt_debug_stamps": [vp, vp, i32], "mcrt_debug_tail_histograms": [vp, vp, i32], "mcrt_debug_set_error": [vp, u32], "mcrt_debug_fast_paths": [vp, vp], "mcrt_debug_beam": [vp, vp], "mcrt_debug_beam_bounce": [vp, u32, vp], "mcrt_debug_beam_order": [vp, u32, vp], "mcrt_debug_beam_layout": [vp, u32, vp, vp], "mcrt_debug_beam_scan": [vp, vp, u32, vp, vp, vp], "mcrt_debug_beam_records": [vp, u32, vp, vp, vp, vp],
+        "mcrt_debug_math": [vp, i32, vp, vp, vp, u32], "mcrt_debug_philox": [vp, vp, vp, vp], "mcrt_debug_stamps": [vp, vp, i32], "mcrt_debug_tail_histograms": [vp, vp, i32], "mcrt_debug_set_error": [vp, u32], "mcrt_debug_fast_paths": [vp, vp], "mcrt_debug_beam": [vp, vp], "mcrt_debug_beam_bounce": [vp, u32, vp], "mcrt_debug_beam_order": [vp, u32, vp], "mcrt_debug_beam_layout": [vp, u32, vp, vp], "mcrt_debug_beam_scan": [vp, vp, u32, vp, vp, vp], "mcrt_debug_beam_records": [vp, u32, vp, vp, vp, vp], "mcrt_debug_beam_entries": [vp, u32, vp, vp, vp],
         "mcrt_scan_maps": [u32, u32, C.c_double, C.c_double, u32, u32, u32, u32, vp, vp],
         "mcrt_group_create": [vp, u32, C.POINTER(vp)], "mcrt_group_destroy": [vp], "mcrt_group_size": [vp], "mcrt_group_root": [vp], "mcrt_group_member": [vp, u32],
         "mcrt_group_shard": [u32, u32, u32, C.POINTER(u32), C.POINTER(u32)], "mcrt_group_set_params": [vp, C.POINTER(Params)], "mcrt_group_set_bvh_builder": [vp, i32],
@@ -276,7 +276,7 @@ def load_library():
         "mcrt_group_last_scene_seconds": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)],
     }
     for name, args in sig.items():
-        if name in ("mcrt_debug_beam", "mcrt_debug_beam_bounce", "mcrt_debug_beam_order", "mcrt_debug_beam_layout", "mcrt_debug_beam_scan", "mcrt_debug_beam_records") and not hasattr(L, name):
+        if name in ("mcrt_debug_beam", "mcrt_debug_beam_bounce", "mcrt_debug_beam_order", "mcrt_debug_beam_layout", "mcrt_debug_beam_scan", "mcrt_debug_beam_records", "mcrt_debug_beam_entries") and not hasattr(L, name):
             continue       # (a library of before the beams, loaded through MCRT_LIB for a comparison: Context.debug_beam / debug_beam_bounce / debug_beam_order then say that nothing ran)
         f = getattr(L, name)
         f.argtypes = args

@@ -822,6 +822,17 @@ class Context(_SceneCalls):
         check(self.L.mcrt_debug_beam_records(self.h, int(b), info, ptr(rec), ptr(lists), ptr(keys) if groups else None))
         return {"n_beams": n_beams, "cap": cap, "near": near, "groups": groups, "n_lists": n_lists, "records": rec, "lists": lists, "keys": keys}
 
+    def debug_beam_entries(self, b):
+        """mcrt_debug_beam_entries: what k_beam_collect stored of every list entry's triangle alone, for the bounce debug_beam_records(b) answers ->
+        (entries uint32 [n_lists][cap][10] = the plane n.x n.y n.z dot(v0, n) | the padded bounds lo.x lo.y lo.z | hi.x hi.y hi.z, raw words of floats;
+         begin_id uint32 [n_lists][cap][2] = the begin depth and the id stored beside them, which the list test reads in place of the list's words 7 and 3).
+        Entries past a record's count are stale.  McrtError where b is not that bounce."""
+        info = (C.c_uint32 * 5)()
+        check(self.L.mcrt_debug_beam_entries(self.h, int(b), info, None, None))
+        ent = np.zeros((int(info[4]), int(info[1]), 10), np.uint32); begin_id = np.zeros((int(info[4]), int(info[1]), 2), np.uint32)
+        check(self.L.mcrt_debug_beam_entries(self.h, int(b), info, ptr(ent), ptr(begin_id)))
+        return ent, begin_id
+
     def debug_beam_scan(self, counts):
         """mcrt_debug_beam_scan: the kernel that lays a beam order out (csrc/mcrt_beam.hip, k_beam_scan) run alone on `counts` rays per beam, the last the
         pseudo-beam's -> (bases uint32 [n], rays placed, segments, pad lanes, the order's length, the order buffer uint32 [length + 64]: BEAM_PAD in the padding

@@ -633,6 +633,28 @@ extern "C" int mcrt_debug_beam_records(mcrt_ctx *c, uint32_t b, uint32_t info[5]
     return MCRT_OK;
 }
 
+// the hot parts of the same lists (BeamBufs::hot: plane | padded lo, begin | padded hi, id): the ten words of plane and bounds, and apart from them the two
+// words k_beam_test reads there in place of the list's own (begin depth, id)
+extern "C" int mcrt_debug_beam_entries(mcrt_ctx *c, uint32_t b, uint32_t info[5], uint32_t *entries, uint32_t *begin_id)
+{
+    MCRT_TRY(mcrt_debug_beam_records(c, b, info, nullptr, nullptr, nullptr));
+    if (!entries && !begin_id) return MCRT_OK;
+    const size_t n = (size_t)info[4] * info[1];
+    std::vector<uint32_t> hot;
+    try { hot.resize(n * MCRT_BEAM_HOT); } catch (const std::bad_alloc &) { return set_error(MCRT_ERR_NOMEM, "no memory for %zu list entries", n); }
+    HIP_TRY(hipMemcpy(hot.data(), c->work[0].beam.hot.p, hot.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < n; e++) {
+        const uint32_t *h = hot.data() + e * MCRT_BEAM_HOT;
+        if (entries) {
+            uint32_t *o = entries + e * MCRT_DEBUG_BEAM_ENTRY;
+            for (int k = 0; k < 7; k++) o[k] = h[k];
+            for (int k = 0; k < 3; k++) o[7 + k] = h[8 + k];
+        }
+        if (begin_id) { begin_id[2 * e] = h[7]; begin_id[2 * e + 1] = h[11]; }
+    }
+    return MCRT_OK;
+}
+
 // k_beam_scan's arithmetic on the host (no context, no device): the segment bases of n counters -- the last is the pseudo-beam's --, and rays placed, segments,
 // pad lanes and the order's length
 extern "C" int mcrt_debug_beam_layout(const uint32_t *counts, uint32_t n, uint32_t *bases, uint32_t out[4])

@@ -15,9 +15,11 @@
 //   k_beam_place    ... order[base[beam] + rank] = the ray's queue position: a permutation of the queue grouped by beam
 //   k_beam_collect  one workgroup per beam (bounce b >= 2: per slot, its 6 beams in turn): one traversal of the BVH4 with a conservative beam-against-box test, the leaf triangles tested by their own
 //                   padded bounds, sorted by the depth at which they begin, the first `cap` copied into the beam's list (bounce b >= 2: a list of a pool,
-//                   handed out to the beams that have members)
-//   k_beam_test     one lane per ray in queue order, or through the beam order (then every wavefront holds ONE beam's rays): its beam looked up (the group's key compared), the contract's triangle test (packet_tri_test) over the
-//                   beam's list in order, until the hit lies before everything not yet tested; lanes that cannot be decided are appended to a leftover queue
+//                   handed out to the beams that have members).  An entry is stored in two parts: the vertices, id, begin depth and edge tolerance (`list`, 64 bytes,
+//                   mcrt_debug_beam_records' layout) and, beside them, what depends on the triangle alone and every test of the entry needs -- its plane and its
+//                   padded bounds, by tri_plane / tri_padded_bounds -- with the begin depth and the id (`hot`, 48 bytes)
+//   k_beam_test     one lane per ray in queue order, or through the beam order (then every wavefront holds ONE beam's rays): its beam looked up (the group's key compared), the contract's triangle test (list_tri_test: packet_tri_test's expressions on the stored plane and bounds,
+//                   the vertices fetched only for the edge tests) over the beam's list in order, until the hit lies before everything not yet tested; lanes that cannot be decided are appended to a leftover queue
 //   k_beam_gather, the lane walk, k_beam_scatter     the leftovers, walked as any other queue, in the halves of the other bounce parity
 //
 // EXACT: a ray's answer is the smallest (fraction, id) among the triangles that pass the contract's test, whatever the order and
@@ -394,7 +396,14 @@ MCRT_DEV void beam_collect(const FrameArgs &a, const BeamArgs &g, const uint32_t
         const float4 *T = a.tris + (size_t)(uint32_t)x * MCRT_TRI_PIECES;
         const float4 t0 = T[0], t1 = T[1], t2 = T[2];
         float4 *L = (float4 *)(g.list + 4 * ((size_t)li * g.cap + e));
-        L[0] = t0; L[1] = make_float4(t1.x, t1.y, t1.z, funord((uint32_t)(x >> 32))); L[2] = t2; L[3] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const float begin = funord((uint32_t)(x >> 32));
+        L[0] = t0; L[1] = make_float4(t1.x, t1.y, t1.z, begin); L[2] = t2; L[3] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        // the hot part: what packet_tri_test rebuilds of the triangle alone, by the same two functions -- once per entry here, not per wavefront and entry in k_beam_test
+        const float4 P = tri_plane(xyz(t0), xyz(t1), xyz(t2));
+        f3 plo, phi;
+        tri_padded_bounds(xyz(t0), xyz(t1), xyz(t2), a.pad_abs, plo, phi);
+        float4 *H = (float4 *)(g.hot + MCRT_BEAM_HOT * ((size_t)li * g.cap + e));
+        H[0] = P; H[1] = make_float4(plo.x, plo.y, plo.z, begin); H[2] = make_float4(phi.x, phi.y, phi.z, t0.w);
     }
     // s_end: the depth up to which the list is complete
     const float s_end = lost ? -INFINITY : N > g.cap ? funord((uint32_t)(ent[g.cap] >> 32)) : INFINITY;
@@ -415,6 +424,59 @@ __global__ void __launch_bounds__(BEAM_CT) k_beam_collect(FrameArgs a, BeamArgs 
         beam_collect(a, g, blockIdx.x * per + k);
         __syncthreads();
     }
+}
+
+// ---- the contract's triangle test of one list entry.  packet_tri_test (mcrt_walk.h) rebuilds the triangle's plane and padded bounds from its
+// vertices in every wavefront; here the record is a list entry, whose plane and bounds k_beam_collect stored (BeamArgs::hot) -- computed by the same two functions
+// from the same floats, so every expression and comparison below sees packet_tri_test's operands bit for bit.  The vertices (the COLD part, BeamArgs::list) are
+// fetched only by a wavefront that reaches the edge tests ----
+// The wave-level exits are scalar.  `if (!__any(ok)) return;` compiles to a v_cndmask of 0 / 1 and a v_cmp before the branch, and so does a ballot of `ok`: the flag
+// is a combination of compares, not a compare.  A ballot of a COMPARE is the v_cmp itself, written to a scalar pair; so the lanes still in the test are kept as a
+// 64-bit mask `m` beside the lanes' own flag, every compare is balloted by itself, the pairs are combined by scalar instructions and the branch reads the scalar
+// condition code.  `m` starts as the ballot of `on` (the caller has it per beam, outside the loop over the entries).
+MCRT_DEV unsigned long long wave_of(bool c) { return __builtin_amdgcn_ballot_w64(c); }
+// H: plane | padded lo, begin depth; H2: padded hi | id; cold: the entry of BeamArgs::list (v0 | id, v1 | begin, v2 | edge tolerance)
+MCRT_DEV void list_tri_test(const u32x8 H, const u32x4 H2, const char *cold, const f3 f2, const f3 to, const f3 inv, const f3 rc, const bool on, unsigned long long m, Best &best)
+{
+    const f3 nrm = mk(__uint_as_float(H[0]), __uint_as_float(H[1]), __uint_as_float(H[2]));
+    const float pw = __uint_as_float(H[3]);
+    const f3 plo = mk(__uint_as_float(H[4]), __uint_as_float(H[5]), __uint_as_float(H[6])), phi = mk(__uint_as_float(H2[0]), __uint_as_float(H2[1]), __uint_as_float(H2[2]));
+    const int id = (int)H2[3];
+    float tmin, tmax;
+    bool ok = on;
+    const float da = dot(nrm, f2) - pw;
+    const float db = dot(nrm, to) - pw;
+    const bool sides = da * db < 0.0f;
+    ok = ok & sides;
+    m &= wave_of(sides);
+    if (m == 0ull) return;
+    const float proj = da - db;
+    const float frac = da / proj;
+    const bool nearer = frac < best.frac, tie = frac == best.frac, smaller = id < best.tri, ahead = frac >= 0.0f;
+    ok = ok & (nearer | (tie & smaller)) & ahead;
+    m &= (wave_of(nearer) | (wave_of(tie) & wave_of(smaller))) & wave_of(ahead);
+    if (m == 0ull) return;
+    const bool box = slab_c(plo, phi, rc, inv, 0.0f, 1.0f, tmin, tmax), after = frac >= tmin, before = frac <= tmax;
+    ok = ok & box & after & before;
+    m &= wave_of(box) & wave_of(after) & wave_of(before);
+    if (m == 0ull) return;
+    // (wave-uniform control flow up to here: one scalar fetch of the vertices for the wavefront)
+    u32x8 A; u32x4 C2;
+    asm volatile("s_load_dwordx8 %0, %2, 0x0\n\ts_load_dwordx4 %1, %2, 0x20\n\ts_waitcnt lgkmcnt(0)" : "=&s"(A), "=&s"(C2) : "s"(cold) : "memory");
+    const f3 v0 = mk(__uint_as_float(A[0]), __uint_as_float(A[1]), __uint_as_float(A[2])), v1 = mk(__uint_as_float(A[4]), __uint_as_float(A[5]), __uint_as_float(A[6]));
+    const f3 v2 = mk(__uint_as_float(C2[0]), __uint_as_float(C2[1]), __uint_as_float(C2[2]));
+    const float edge_tol = __uint_as_float(C2[3]);
+    const float s = 1.0f - frac;
+    const f3 p = mk(s * f2.x + frac * to.x, s * f2.y + frac * to.y, s * f2.z + frac * to.z);
+    const f3 p0 = v0 - p, p1 = v1 - p, p2 = v2 - p;
+    ok = ok && dot(cross(p0, p1), nrm) >= edge_tol && dot(cross(p1, p2), nrm) >= edge_tol && dot(cross(p2, p0), nrm) >= edge_tol;
+    if (ok) { best.frac = frac; best.tri = id; }
+}
+
+// every lane `on` has its hit (and the margin) before `begin`: nothing that begins there or later can change it
+MCRT_DEV bool beam_all_before(const bool on, const unsigned long long on_m, const float reach, const float begin)
+{
+    return (on_m & wave_of(!(reach < begin))) == 0ull;
 }
 
 // pass 0: every ray of the bounce's queue against entries [0, near) of its beam's list -- in queue order, or (g.ordered) through the beam order, whose length
@@ -453,7 +515,8 @@ __global__ void __launch_bounds__(256) k_beam_test(FrameArgs a, BeamArgs g, uint
     while (todo) {
         const int cb = __builtin_amdgcn_readlane(r.bid, __ffsll((long long)todo) - 1);
         const bool mine = member && r.bid == cb;
-        todo &= ~__ballot(mine);
+        const unsigned long long mine_m = __ballot(mine);
+        todo &= ~mine_m;
         met++;
         const u32x8 R = sload8(g.rec + (size_t)cb * MCRT_BEAM_REC + 8);      // ..., m, xref, s_end, entries, list
         const float m2 = 2.0f * __uint_as_float(R[3]), xref = __uint_as_float(R[4]);
@@ -461,23 +524,23 @@ __global__ void __launch_bounds__(256) k_beam_test(FrameArgs a, BeamArgs g, uint
         // the depth of the hit, plus the margin: what begins beyond it cannot be accepted before it
         float reach = best.tri >= 0 ? sg * ((f2d + best.frac * r.dd) - xref) + m2 : INFINITY;
         float limit = __uint_as_float(R[5]);
-        const char *L = (const char *)(g.list + 4 * (size_t)R[7] * g.cap);
-        // (two entries per round trip to the scalar cache; the second of the last pair may lie past the list: it is fetched, not looked at)
+        const char *L = (const char *)(g.list + 4 * (size_t)R[7] * g.cap), *Hh = (const char *)(g.hot + MCRT_BEAM_HOT * (size_t)R[7] * g.cap);
+        // (the hot parts of two entries per round trip to the scalar cache; the second of the last pair may lie past the list: it is fetched, not looked at)
         for (uint32_t k = first; k < n_ent; k += 2u) {
             u32x8 A, A2; u32x4 C2, C22;
-            const char *E = L + ((size_t)k << 6);
-            asm volatile("s_load_dwordx8 %0, %4, 0x0\n\ts_load_dwordx4 %1, %4, 0x20\n\ts_load_dwordx8 %2, %4, 0x40\n\ts_load_dwordx4 %3, %4, 0x60\n\ts_waitcnt lgkmcnt(0)"
+            const char *E = Hh + (size_t)k * (MCRT_BEAM_HOT * 4u);
+            asm volatile("s_load_dwordx8 %0, %4, 0x0\n\ts_load_dwordx4 %1, %4, 0x20\n\ts_load_dwordx8 %2, %4, 0x30\n\ts_load_dwordx4 %3, %4, 0x50\n\ts_waitcnt lgkmcnt(0)"
                          : "=&s"(A), "=&s"(C2), "=&s"(A2), "=&s"(C22) : "s"(E) : "memory");
             float begin = __uint_as_float(A[7]);
-            if (k >= cut || !__any(mine && !(reach < begin))) { limit = begin; break; }
+            if (k >= cut || beam_all_before(mine, mine_m, reach, begin)) { limit = begin; break; }
             int before = best.tri;
-            packet_tri_test(A, C2, f2, to, inv, rc, a.pad_abs, mine, best);
+            list_tri_test(A, C2, L + ((size_t)k << 6), f2, to, inv, rc, mine, mine_m, best);
             if (best.tri != before) reach = sg * ((f2d + best.frac * r.dd) - xref) + m2;
             if (k + 1u >= n_ent) break;
             begin = __uint_as_float(A2[7]);
-            if (k + 1u >= cut || !__any(mine && !(reach < begin))) { limit = begin; break; }
+            if (k + 1u >= cut || beam_all_before(mine, mine_m, reach, begin)) { limit = begin; break; }
             before = best.tri;
-            packet_tri_test(A2, C22, f2, to, inv, rc, a.pad_abs, mine, best);
+            list_tri_test(A2, C22, L + ((size_t)(k + 1u) << 6), f2, to, inv, rc, mine, mine_m, best);
             if (best.tri != before) reach = sg * ((f2d + best.frac * r.dd) - xref) + m2;
         }
         left = left || (mine && !(reach < limit || limit == INFINITY));

@@ -33,6 +33,7 @@ struct PathBufs {   // sized for `paths` paths of `depth` bounces
 struct BeamBufs {
     Buf<uint32_t> red, rec, lcount, l_counts, l_cursors;
     Buf<uint4> list;
+    Buf<uint32_t> hot;                        // the entries' planes and padded bounds, beside `list` (BeamArgs::hot)
     Buf<unsigned long long> gkey;
     Buf<uint32_t> rbeam, rrank, ocount, obase, order;
     uint32_t beams = 0, lists = 0, groups = 0, cap = 0, order_beams = 0;

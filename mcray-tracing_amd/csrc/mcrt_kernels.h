@@ -96,6 +96,7 @@ static_assert(sizeof(FrameArgs) % 8 == 0 && offsetof(FrameArgs, order_mask) + 4 
 // beam, one list per wavefront.  Buffers of its own (BeamBufs), made only where a bounce is ordered.
 #define MCRT_BEAM_SLOTS 12u
 #define MCRT_BEAM_REC 16u            // words of a beam's reduction block and of its record
+#define MCRT_BEAM_HOT 12u            // words of the hot part of a list entry (BeamArgs::hot)
 #define MCRT_BEAM_CAP_MAX 1024u      // the largest list capacity (k_beam_collect sorts in LDS)
 #define MCRT_BEAM_PROBES 4u          // slots of the group table a key is looked for in
 #define MCRT_BEAM_COUNTERS 16u       // counters of one beamed bounce (0-7: mcrt_debug_beam_bounce's; 8-12: the beam order's, mcrt_debug_beam_order)
@@ -105,6 +106,7 @@ struct BeamArgs {
     uint32_t *red;             // [n_beams][MCRT_BEAM_REC] k_beam_bounds' minima and maxima
     uint32_t *rec;             // [n_beams][MCRT_BEAM_REC] the beams as k_beam_test reads them (k_beam_collect)
     uint4 *list;               // [n_lists][cap][4] (+ one entry of padding) 64-byte candidates, nearest first: v0 | id, v1 | depth at which the padded bounds begin, v2 | edge tolerance, -
+                               // the COLD part of an entry: k_beam_test fetches it only for the edge tests; what every entry's test needs is in `hot`
     unsigned long long *gkey;  // [groups] the group that holds the slot (0: free); bounces >= 2
     uint32_t *lq0, *lq1;       // [np] leftover rays (queue positions) of the near and of the far pass
     uint32_t *lcount;          // [MCRT_BEAM_COUNTERS] of THIS bounce -- 0, 1: leftovers of the two passes; 2: beams whose list is incomplete; 3: beams refused (spread, or no list left);
@@ -122,6 +124,9 @@ struct BeamArgs {
     uint32_t *rbeam, *rrank;   // [np] by queue position: the ray's beam (n_beams: none) and its rank among the beam's rays (k_beam_rank)
     uint32_t *ocount, *obase;  // [n_beams + 1] rays of a beam, and where its segment of the order begins (k_beam_scan); the last is the pseudo-beam of the rays without a beam
     uint32_t *order;           // [np + 64 (n_beams + 1)] queue positions grouped by beam, every segment padded to a multiple of 64 with MCRT_BEAM_PAD (k_beam_place)
+    // what depends on the candidate's triangle alone, computed once per entry by k_beam_collect (behind everything else: the other beam kernels' argument offsets stay)
+    uint32_t *hot;             // [n_lists][cap][MCRT_BEAM_HOT] (+ one entry of padding) 48 bytes beside every entry of `list`: tri_plane's n.x n.y n.z dot(v0, n) |
+                               // tri_padded_bounds' lo.x lo.y lo.z, the depth at which they begin | hi.x hi.y hi.z, id -- bit for bit what packet_tri_test rebuilds
 };
 
 constexpr uint32_t MCRT_ALL_BOUNCES = 0xffffffffu;   // launch_march: accumulate the segments of every bounce in one launch

@@ -242,6 +242,7 @@ static int fill_beam(const mcrt_ctx *c, Work &w, const mcrt::FrameArgs &a, uint3
         HIP_TRY(hipDeviceSynchronize());
         b.beams = b.lists = b.groups = b.cap = 0;
         HIP_TRY(b.red.alloc((size_t)beams * MCRT_BEAM_REC)); HIP_TRY(b.rec.alloc((size_t)beams * MCRT_BEAM_REC)); HIP_TRY(b.list.alloc(((size_t)lists * cap + 1) * 4));
+        HIP_TRY(b.hot.alloc(((size_t)lists * cap + 1) * MCRT_BEAM_HOT));      // (+ one entry, as the list: the second fetch of the last pair)
         HIP_TRY(b.gkey.alloc(std::max(bp.groups, 1u)));
         HIP_TRY(b.lcount.grow((size_t)MCRT_MAX_BOUNCES * MCRT_BEAM_COUNTERS)); HIP_TRY(b.l_counts.grow(MCRT_MAX_BOUNCES + 1)); HIP_TRY(b.l_cursors.grow((size_t)MCRT_MAX_BOUNCES * MCRT_XCDS * MCRT_CURSOR_STRIDE));
         b.beams = beams; b.lists = lists; b.groups = bp.groups; b.cap = cap;
@@ -257,7 +258,7 @@ static int fill_beam(const mcrt_ctx *c, Work &w, const mcrt::FrameArgs &a, uint3
     }
     mcrt::BeamArgs &g = bp.g;
     g.rbeam = b.rbeam; g.rrank = b.rrank; g.ocount = b.ocount; g.obase = b.obase; g.order = b.order; g.pairs = c->knobs.beam_pairs ? 1u : 0u;
-    g.red = b.red; g.rec = b.rec; g.list = b.list; g.gkey = b.gkey; g.lcount = b.lcount; g.l_counts = b.l_counts; g.l_cursors = b.l_cursors;
+    g.red = b.red; g.rec = b.rec; g.list = b.list; g.hot = b.hot; g.gkey = b.gkey; g.lcount = b.lcount; g.l_counts = b.l_counts; g.l_cursors = b.l_cursors;
     g.cap = cap; g.near = std::min(c->knobs.beam_near, cap);
     g.stride = np >= MCRT_BEAM_SAMPLE_FROM ? MCRT_BEAM_SAMPLE_STRIDE : 1u;
     g.spread_cap = MCRT_BEAM_SPREAD;
