@@ -68,7 +68,9 @@ extern "C" {
                                    + mcrt_autogain_opts, mcrt_default_autogain_opts, mcrt_autogain_curve, mcrt_autogain_frames (automatic gain: a depth gain
                                    curve estimated from each frame's own amplitude histograms, and the frame's penetration depth; additive);
                                    + mcrt_bands, mcrt_default_bands, mcrt_psf_band_kernels, mcrt_convolve_bands_frames, mcrt_band_fold_frames
-                                   (frequency compounding and the depth downshift: an axial kernel per RF row and per band; additive) */
+                                   (frequency compounding and the depth downshift: an axial kernel per RF row and per band; additive);
+                                   + mcrt_detect_opts, mcrt_default_detect_opts, mcrt_detect_taps, mcrt_detect_gain, mcrt_psf_carrier, mcrt_detect_frames
+                                   (quadrature detection: an FIR Hilbert transformer along the scan-line, the envelope and the I/Q pair; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -369,6 +371,50 @@ int mcrt_band_fold_frames(mcrt_ctx *ctx, const float *bands_dev /* [F][B][E][R] 
 int mcrt_envelope(mcrt_ctx *ctx, float *rf_dev, uint32_t n_elements, uint32_t n_rows);
 /* the same on the n_frames images [n_frames][E][R] of a pass (main.cpp:147 once per frame), one launch */
 int mcrt_envelope_frames(mcrt_ctx *ctx, float *rf_dev, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows);
+/* ---- quadrature detection: an FIR Hilbert transformer along the scan-line, the envelope and the I/Q pair.  rf_image::envelope calls itself
+ * "a fast approximation of the hilbert transform": it joins the local maxima of the SAMPLES by straight lines.  The axial pulse of
+ * mcrt_psf_kernels has its taps one RF row apart, so its carrier is freq * res_um / 1000 cycles per row -- 0.6525 at 4.5 MHz and 145 um, which
+ * aliases to 0.3475: fewer than three rows per cycle.  The maxima of such samples beat against the carrier, and a reflector of constant
+ * brightness is read as anything between half and all of it (DESIGN.md 5.19 has the table).  A scanner detects in quadrature: the RF line x
+ * and its Hilbert transform q form the analytic signal, whose magnitude is the envelope and whose two parts are the I/Q data.  An opt-in
+ * stage in the place of mcrt_envelope_frames; without it no call and no bit changes.
+ *
+ * The transformer is a type-III FIR (antisymmetric, odd length) under a Hamming window.  With M = (n_taps - 1) / 2, for odd m in 1..M, in
+ * double with pi = 3.141592653589793:
+ *   t_m = (float)((2.0 / (pi * m)) * (0.54 + 0.46 * cos(pi * m / (M + 1))))
+ *   taps[M + m] = t_m,  taps[M - m] = -t_m;  every even offset, the centre included, is exactly +0.0f
+ * Its magnitude response at f cycles per row is G(f) = |2 * sum over odd m of t_m * sin(2 pi f m)|: a line cos(w r) gives q = G sin(w r), and
+ * the envelope sqrt(cos^2 + G^2 sin^2) stays within |G - 1| of 1.  At 31 taps G is within 1 % of 1 from 0.05 to 0.45 cycles per row, at 15
+ * taps from 0.10 to 0.40.  THE LIMIT OF THE MODEL: G falls to 0 at 0 and at 0.5 (Nyquist), where a real line has no separable envelope at
+ * all -- the 3.5 MHz band of three bands spanning 2 MHz about 4.5 has the carrier 0.4925 and G = 0.26 at 31 taps, and comes out darker
+ * under this detector.  mcrt_psf_carrier and mcrt_detect_gain let a caller see that; the library does not refuse it. */
+typedef struct { uint32_t n_taps; } mcrt_detect_opts;          /* 3, 7, 11, ..., 63 (n_taps % 4 == 3); default 31 */
+/* n_taps = 31.  MCRT_ERR_INVALID for a null o.  Host only. */
+int mcrt_default_detect_opts(mcrt_detect_opts *o);
+/* the taps above; host only, no GPU needed.  MCRT_ERR_INVALID for a null pointer or an n_taps outside the set; on an error nothing is written. */
+int mcrt_detect_taps(const mcrt_detect_opts *o, float *taps /* [n_taps] */);
+/* *gain = G(cycles_per_row) of the taps given, in double: the sum over odd m in ascending order of (double)taps[M + m] * sin(2 pi f m), doubled,
+ * its absolute value.  Host only.  MCRT_ERR_INVALID for a null pointer or an n_taps outside the set. */
+int mcrt_detect_gain(const float *taps, uint32_t n_taps, double cycles_per_row, double *gain);
+/* the digital carrier of mcrt_psf_kernels' axial pulse at freq_mhz, and of a band of mcrt_psf_band_kernels at the probe's face: with
+ * c = (double)freq_mhz * ((double)res_um / 1000.0),  *cycles_per_row = |c - rint(c)|, in 0..0.5.  Host only.  MCRT_ERR_INVALID for a null pointer. */
+int mcrt_psf_carrier(float freq_mhz, uint32_t res_um, double *cycles_per_row);
+/* Per scan-line x[0..R) of the stack, with xz[i] = x[i] for 0 <= i < R and +0.0f outside:
+ *   q[r]   = sum over m = 1, 3, 5, ... <= M, in ascending order, starting from 0.0f, of  (xz[r - m] - xz[r + m]) * t_m
+ *   env[r] = sqrtf(x[r] * x[r] + q[r] * q[r])
+ * the difference, every multiply and every add rounded once, no fma; the two squares and their sum rounded once each; the square root
+ * correctly rounded.  env_dev[f][e][r] = env[r]; iq_dev[f][e][r][0] holds x[r]'s own bits and iq_dev[f][e][r][1] = q[r]: the analytic pair
+ * at the RF rate, neither mixed to baseband nor decimated.  A NaN or an infinity at row r reaches the rows r +- m for odd m <= M (and, in
+ * env and in I, row r itself) and no others; a scan-line that is NaN throughout -- the reference's total internal reflection -- stays NaN.
+ * Every (f, e, r) is written: there are no borders, and any R >= 1 is allowed, R <= M included (rows near an end see the zeros of xz).
+ * rf_dev [F][E][R] is device memory; env_dev may EQUAL rf_dev (detection in place, as mcrt_envelope_frames) and rf_dev is otherwise read
+ * only; any other overlap between the three buffers is MCRT_ERR_INVALID.  At least one of env_dev and iq_dev must be given.
+ * Asynchronous on the context's stream.  MCRT_ERR_INVALID for a null ctx, rf_dev or o, zero sizes, an n_taps outside the set, both outputs
+ * null; MCRT_ERR_LIMIT for n_rows > 2048 (a wavefront holds its scan-line in LDS) or a stack of 2^40 floats or more; on any error nothing
+ * is launched and nothing is written.  Nothing is allocated or uploaded by the call: the 16 distinct taps at most travel as kernel
+ * arguments.  Groups: call it on mcrt_group_root(). */
+int mcrt_detect_frames(mcrt_ctx *ctx, const float *rf_dev /* [F][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
+                       const mcrt_detect_opts *o, float *env_dev /* [F][E][R] or NULL */, float *iq_dev /* [F][E][R][2] or NULL */);
 /* rf_image::postprocess scan conversion (rfimage.h:125-140,183-215), exact bilinear;
  * out_dev float [out_rows][out_cols] */
 int mcrt_scan_convert(mcrt_ctx *ctx, const float *rf_dev, uint32_t n_elements, uint32_t n_rows,

@@ -64,6 +64,11 @@ class Bands(C.Structure):
                 ("downshift_mhz_per_mm", C.c_float), ("min_mhz", C.c_float)]
 
 
+class DetectOpts(C.Structure):
+    """mcrt_detect_opts (include/mcrt.h): 4 bytes"""
+    _fields_ = [("n_taps", C.c_uint32)]
+
+
 class Compound(C.Structure):
     """mcrt_compound (include/mcrt.h): 68 bytes, steer_rad at offset 4"""
     _fields_ = [("n_views", C.c_uint32), ("steer_rad", C.c_float * 16)]
@@ -146,7 +151,7 @@ SEGMENT_DTYPE = np.dtype([("from", "<f4", 3), ("to", "<f4", 3), ("dir", "<f4", 3
 assert NODE_DTYPE.itemsize == 64 and SEGMENT_DTYPE.itemsize == 64 and C.sizeof(BvhNode) == 64 and C.sizeof(BmodeParams) == 48 and C.sizeof(Focus) == 40 and C.sizeof(Compound) == 68 and C.sizeof(CompoundOpts) == 72
 assert C.sizeof(Sweep) == 12 and C.sizeof(VolumeGrid) == 112 and C.sizeof(LabelOpts) == 8 and C.sizeof(RenderView) == 64 and C.sizeof(RenderOpts) == 32 and C.sizeof(SpeckleOpts) == 16 and C.sizeof(NoiseOpts) == 16 and C.sizeof(ReconOpts) == 20
 assert C.sizeof(ReconLabelOpts) == 12 and C.sizeof(AutogainOpts) == 24 and C.sizeof(TransmitOpts) == 12 and C.sizeof(Speckle3dOpts) == 28 and Speckle3dOpts.weight.offset == 16
-assert C.sizeof(Bands) == 80 and Bands.band_weight.offset == 36 and Bands.var_x.offset == 68 and Bands.min_mhz.offset == 76
+assert C.sizeof(Bands) == 80 and Bands.band_weight.offset == 36 and Bands.var_x.offset == 68 and Bands.min_mhz.offset == 76 and C.sizeof(DetectOpts) == 4
 
 # every symbol include/mcrt.h declares (tests/test_abi.py checks the .so exports each one)
 SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create", "mcrt_destroy", "mcrt_set_stream",
@@ -170,6 +175,7 @@ SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create"
            "mcrt_default_noise_opts", "mcrt_noise_draws", "mcrt_noise_frames",
            "mcrt_default_autogain_opts", "mcrt_autogain_curve", "mcrt_autogain_frames",
            "mcrt_default_bands", "mcrt_psf_band_kernels", "mcrt_convolve_bands_frames", "mcrt_band_fold_frames",
+           "mcrt_default_detect_opts", "mcrt_detect_taps", "mcrt_detect_gain", "mcrt_psf_carrier", "mcrt_detect_frames",
            "mcrt_default_recon_opts", "mcrt_recon_transform", "mcrt_recon_frames",
            "mcrt_default_recon_label_opts", "mcrt_recon_label_frames", "mcrt_render_label_frames"]
 
@@ -260,6 +266,11 @@ def load_library():
         "mcrt_psf_band_kernels": [C.POINTER(Bands), u32, u32, C.c_double, vp, u32, vp],
         "mcrt_convolve_bands_frames": [vp, vp, u32, u32, u32, u32, vp, u32, vp, vp, u32, vp],
         "mcrt_band_fold_frames": [vp, vp, u32, u32, u32, u32, vp, vp],
+        "mcrt_default_detect_opts": [C.POINTER(DetectOpts)],
+        "mcrt_detect_taps": [C.POINTER(DetectOpts), vp],
+        "mcrt_detect_gain": [vp, u32, C.c_double, C.POINTER(C.c_double)],
+        "mcrt_psf_carrier": [C.c_float, u32, C.POINTER(C.c_double)],
+        "mcrt_detect_frames": [vp, vp, u32, u32, u32, C.POINTER(DetectOpts), vp, vp],
         "mcrt_default_recon_opts": [C.POINTER(ReconOpts)],
         "mcrt_recon_transform": [C.POINTER(VolumeGrid), C.c_double, vp, vp],
         "mcrt_recon_frames": [vp, vp, u32, u32, u32, vp, vp, C.c_double, C.c_double, C.POINTER(VolumeGrid), C.POINTER(ReconOpts), vp, vp, vp],

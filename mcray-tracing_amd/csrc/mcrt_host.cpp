@@ -433,6 +433,53 @@ extern "C" int mcrt_psf_band_kernels(const mcrt_bands *b, uint32_t res_um, uint3
     return MCRT_OK;
 }
 
+// Quadrature detection (the model is in include/mcrt.h): the taps of a type-III FIR Hilbert transformer under a Hamming window, its
+// magnitude response, and the digital carrier of mcrt_psf_kernels' axial pulse.  Host only.
+static bool detect_taps_ok(uint32_t n_taps) { return n_taps >= 3u && n_taps <= 63u && n_taps % 4u == 3u; }
+
+extern "C" int mcrt_default_detect_opts(mcrt_detect_opts *o)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_detect_opts: null options");
+    o->n_taps = 31u;
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_detect_taps(const mcrt_detect_opts *o, float *taps)
+{
+    static const char fn[] = "mcrt_detect_taps";
+    if (!o || !taps) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null %s", fn, o ? "taps" : "options");
+    if (!detect_taps_ok(o->n_taps)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: n_taps must be 3, 7, 11, ..., 63 (%u)", fn, o->n_taps);
+    const double pi = 3.141592653589793;
+    const uint32_t M = (o->n_taps - 1u) / 2u;
+    for (uint32_t i = 0; i < o->n_taps; i++) taps[i] = 0.0f;
+    for (uint32_t m = 1; m <= M; m += 2u) {
+        const float t = (float)((2.0 / (pi * (double)m)) * (0.54 + 0.46 * std::cos(pi * (double)m / (double)(M + 1u))));
+        taps[M + m] = t; taps[M - m] = -t;
+    }
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_detect_gain(const float *taps, uint32_t n_taps, double cycles_per_row, double *gain)
+{
+    static const char fn[] = "mcrt_detect_gain";
+    if (!taps || !gain) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null %s", fn, taps ? "gain" : "taps");
+    if (!detect_taps_ok(n_taps)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: n_taps must be 3, 7, 11, ..., 63 (%u)", fn, n_taps);
+    const double pi = 3.141592653589793;
+    const uint32_t M = (n_taps - 1u) / 2u;
+    double sum = 0.0;
+    for (uint32_t m = 1; m <= M; m += 2u) sum += (double)taps[M + m] * std::sin(2.0 * pi * cycles_per_row * (double)m);
+    *gain = std::fabs(2.0 * sum);
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_psf_carrier(float freq_mhz, uint32_t res_um, double *cycles_per_row)
+{
+    if (!cycles_per_row) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_psf_carrier: null cycles_per_row");
+    const double c = (double)freq_mhz * ((double)res_um / 1000.0);
+    *cycles_per_row = std::fabs(c - std::rint(c));
+    return MCRT_OK;
+}
+
 // ---- transducer<N>::transducer (transducer.h:24-62) -------------------------------------------
 namespace {
 struct F3 { float x, y, z; };

@@ -149,6 +149,31 @@ extern "C" int mcrt_envelope(mcrt_ctx *c, float *rf_dev, uint32_t E, uint32_t R)
     return mcrt_envelope_frames(c, rf_dev, 1, E, R);
 }
 
+// The contract is in include/mcrt.h.  Everything is checked before anything is launched; the taps are built on the host (mcrt_detect_taps) and
+// the ones at the odd offsets travel as kernel arguments, so the call allocates and uploads nothing.
+extern "C" int mcrt_detect_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_detect_opts *o, float *env_dev, float *iq_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_detect_frames";
+    if (!rf_dev || !o || E == 0 || R == 0 || n_frames == 0) return set_error(MCRT_ERR_INVALID, "%s: bad arguments", fn);
+    if (!env_dev && !iq_dev) return set_error(MCRT_ERR_INVALID, "%s: neither env_dev nor iq_dev is given", fn);
+    float taps[63];
+    MCRT_TRY(mcrt_detect_taps(o, taps));
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: at most %d rows", fn, MCRT_MAX_ROWS);
+    if ((double)n_frames * (double)E * (double)R >= 0x1p40) return set_error(MCRT_ERR_LIMIT, "%s: the stack is too large", fn);
+    const size_t n = (size_t)n_frames * E * R;
+    const Range in{ rf_dev, 4 * n, "rf_dev" };
+    const Range outs[2] = { { env_dev == rf_dev ? nullptr : env_dev, 4 * n, "env_dev" }, { iq_dev, 8 * n, "iq_dev" } };   // env_dev == rf_dev: in place
+    MCRT_TRY(check_overlap(fn, in, outs, 2, true));
+    mcrt::DetectArgs a; memset(&a, 0, sizeof a);
+    a.rf = rf_dev; a.env = env_dev; a.iq = (float2 *)iq_dev; a.lines = (size_t)n_frames * E; a.R = R;
+    const uint32_t M = (o->n_taps - 1u) / 2u;
+    a.nt = (M + 1u) / 2u;
+    for (uint32_t k = 0; k < a.nt; k++) a.t[k] = taps[M + 2u * k + 1u];
+    HIP_TRY(mcrt::launch_detect(a, c->stream));
+    return MCRT_OK;
+}
+
 // the scan-conversion maps of a geometry on the device, in cache m: the plain maps (cp null: mcrt_scan_maps, one view) or the N views of a steer
 // list (mcrt_compound_maps), [N][2][n_pad]
 static int ensure_maps(mcrt_ctx *c, MapCache &m, uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t orows, uint32_t ocols, const mcrt_compound *cp, const float **maps)

@@ -16,6 +16,7 @@
 //   mcrt_speckle.hip k_srad (speckle reduction: mcrt_speckle_frames)
 //   mcrt_speckle3d.hip k_srad3 (3-D speckle reduction over voxel blocks: mcrt_speckle_volume_frames)
 //   mcrt_noise.hip   k_noise (receiver noise: mcrt_noise_frames; its peaks are k_bmode_peak's)
+//   mcrt_detect.hip  k_detect<NT> (quadrature detection: mcrt_detect_frames; NT taps, 1..16)
 //   mcrt_autogain.hip k_autogain_hist, k_autogain_curve, k_autogain_apply (automatic gain: mcrt_autogain_frames)
 //   mcrt_recon.hip   k_recon_splat, k_recon_resolve (freehand 3-D reconstruction: mcrt_recon_frames)
 //   mcrt_label.hip   k_label (ground-truth label maps: mcrt_label_frames), k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames)
@@ -366,6 +367,16 @@ hipError_t launch_convolve_bands(const float *rf, float *tmp, float *bands, uint
 // k_elevation: planes [F][K][E][R] folded into rf [F][E][R] with the device table w [K][R] (tap-major); float4 lanes where E*R and the pointers allow
 hipError_t launch_elevation(const float *planes, float *rf, uint32_t F, uint32_t K, uint32_t E, uint32_t R, const float *w, hipStream_t st);
 hipError_t launch_envelope(float *img, uint32_t E, uint32_t R, hipStream_t st);
+// k_detect: the FIR Hilbert transformer along every scan-line of rf [lines][R]; env (may be rf) and iq are written where they are given
+struct DetectArgs {
+    const float *rf;                    // [lines][R]
+    float *env;                         // [lines][R] or null
+    float2 *iq;                         // [lines][R] (x, q) or null
+    size_t lines;
+    uint32_t R, nt;                     // nt: the taps at the odd offsets 1, 3, ..., 2 * nt - 1 (1..16)
+    float t[16];                        // t[k]: the tap at offset 2 * k + 1
+};
+hipError_t launch_detect(const DetectArgs &a, hipStream_t st);
 hipError_t launch_remap(const float *img, uint32_t n_img, uint32_t E, uint32_t R, const float *map_col, const float *map_row, float *out, uint32_t n, hipStream_t st);
 hipError_t launch_bmode_peak(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, float *peak, hipStream_t st);   // peak[F] zeroed before
 hipError_t launch_bmode_grey(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, const float *peak /*[F] or null: ref*/, float ref,

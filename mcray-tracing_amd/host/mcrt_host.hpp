@@ -5,7 +5,7 @@
 //   transducer<N>            transducer.h:24-137   (frequency MHz, radius cm, element separation mm, position, angles deg)
 //   psf<ax,lat,elev,res>     psf.h:34-77
 //   scene                    scene.h:19-76, scene.cpp:16-48,185-247 (JSON keys, "Error while loading scene: ..." wrapping)
-//   rf_image<cols,us,um>     rfimage.h:20-219      (clear / convolve / envelope / postprocess; data lives on the GPU)
+//   rf_image<cols,us,um>     rfimage.h:20-219      (clear / convolve / envelope / postprocess; data lives on the GPU); + detect / iq
 //   ray_physics::segment     ray.h:28-36           (vec3 stands in for btVector3; `media` is held BY VALUE: the reference's
 //                                                   `const material &` dangles by the time main.cpp:126 reads it)
 //   volume<size,res>         volume.h:19-61        (host copy of the texture the GPU samples)
@@ -894,6 +894,31 @@ public:
         }
         if (n_views) { check(mcrt_envelope_frames(dev->ctx, stack.as<float>(), n_views, columns, max_rows), "mcrt_envelope_frames"); return; }
         to_device(); check(mcrt_envelope(dev->ctx, rf.as<float>(), columns, max_rows), "mcrt_envelope");
+    }
+    // quadrature detection (mcrt.h: mcrt_detect_frames) in the place of envelope(): the FIR Hilbert envelope of whatever envelope() would have
+    // detected, in place -- the band images of a convolve(p) with bands, which it then folds; the views, planes or tracked frames of the last
+    // trace(); or this image.  Everything after it sees what it saw after envelope()
+    void detect(const mcrt_detect_opts &o)
+    {
+        if (banded) {
+            check(mcrt_detect_frames(dev->ctx, band_stack.as<float>(), (n_views ? n_views : 1u) * banded, columns, max_rows, &o, band_stack.as<float>(), nullptr), "mcrt_detect_frames");
+            fold_bands();
+            return;
+        }
+        if (n_views) { check(mcrt_detect_frames(dev->ctx, stack.as<float>(), n_views, columns, max_rows, &o, stack.as<float>(), nullptr), "mcrt_detect_frames"); return; }
+        to_device(); check(mcrt_detect_frames(dev->ctx, rf.as<float>(), 1, columns, max_rows, &o, rf.as<float>(), nullptr), "mcrt_detect_frames");
+    }
+    // the analytic pair of this image's RF at the RF rate: interleaved [columns][max_rows][2] = (the RF's own bits, its FIR Hilbert transform
+    // along the scan-line).  The image is left as it is (call it before envelope() / detect()).  A stack of views, planes or tracked
+    // frames is not one image and band images have no one carrier: it throws
+    void iq(const mcrt_detect_opts &o, std::vector<float> &interleaved)
+    {
+        if (n_views || banded) throw std::logic_error("rf_image::iq: the analytic pair is of one RF image, not of a stack or of band images");
+        to_device();
+        const size_t n = (size_t)columns * max_rows;
+        points.reserve(2 * sizeof(float) * n);
+        check(mcrt_detect_frames(dev->ctx, rf.as<float>(), 1, columns, max_rows, &o, nullptr, points.as<float>()), "mcrt_detect_frames");
+        interleaved = download<float>(points.as<float>(), 2 * n);
     }
     // receiver noise (mcrt.h: mcrt_noise_frames): a noise floor and a gain per scan-line (element_gain: [columns] or null) over whatever the
     // last trace() filled, in place -- this image, or the views of a compounded frame or the planes of a sweep as ONE frame (one receiver,
