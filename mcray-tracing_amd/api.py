@@ -5,6 +5,7 @@
   Simulator   <-> scene + rf_image + the frame loop body of main.cpp:102-148
   Context     <-> thin 1:1 wrapper of include/mcrt.h
 """
+import collections
 import contextlib
 import ctypes as C
 import math
@@ -325,7 +326,7 @@ def host_volume_maps(n_elements, n_rows, sweep, grid, radius_mm=30.0, total_angl
     """mcrt_volume_maps: where in the stack [K][E][R] every point of grid lies, (map_plane, map_row, map_col), each [nw][nv][nu].
     sweep: an mcrt_sweep (sweep_struct) or (K, step_rad[, pivot_mm])"""
     sw = _as_sweep(sweep)
-    shape = (grid.nw, grid.nv, grid.nu)
+    shape = _grid_shape(grid)[0]
     mz = np.zeros(shape, np.float32); mr = np.zeros(shape, np.float32); mc = np.zeros(shape, np.float32)
     check(load_library().mcrt_volume_maps(n_elements, n_rows, radius_mm, total_angle, max_travel_us, speed_of_sound, C.byref(sw), C.byref(grid), ptr(mz), ptr(mr), ptr(mc)))
     return mz, mr, mc
@@ -1322,6 +1323,47 @@ class Group(_SceneCalls):
 
 
 # ------------------------------------------------------------------ frame-level mirror of main.cpp:92-152
+# the device images a stage acts on: `images` of them from dev on, as `frames` frames of `per_frame` each, the first with the id first_id
+_Images = collections.namedtuple("_Images", "dev images frames per_frame first_id")
+
+
+class _GrowOnly:
+    """a device buffer of a context that is made on first use and only grows"""
+
+    def __init__(self, ctx):
+        self.ctx, self.dev, self.nbytes = ctx, None, 0
+
+    def reserve(self, nbytes):
+        if self.dev is None or self.nbytes < nbytes:
+            self.release()
+            self.dev, self.nbytes = self.ctx.alloc(nbytes), nbytes
+        return self.dev
+
+    def release(self):
+        if self.dev is not None:
+            self.ctx.free(self.dev)
+        self.dev, self.nbytes = None, 0
+
+
+def _option(value, other=lambda v: {} if v is True else dict(v)):
+    """an option keyword of Simulator -> None (off: None or False) or the dict of its keywords: a dict is copied, anything else goes through
+    `other` (True: the defaults)"""
+    if value is None or value is False:
+        return None
+    return dict(value) if isinstance(value, dict) else other(value)
+
+
+def _detect_word(detect):
+    if isinstance(detect, str) and detect != "quadrature":
+        raise ValueError("detect takes None, \"quadrature\" or a dict of n_taps=, got %r" % (detect,))
+    return {} if isinstance(detect, str) else dict(detect)
+
+
+def _grid_shape(grid):
+    """(the shape of grid's output [nw][nv][nu], its points)"""
+    return (grid.nw, grid.nv, grid.nu), grid.nw * grid.nv * grid.nu
+
+
 class Simulator:
     """scene + transducer + rf_image of the reference, driven frame by frame.
 
@@ -1378,33 +1420,25 @@ class Simulator:
         as before -- so everything downstream sees the stack it always saw.  The detector is flat within 1 % only for carriers between
         0.05 and 0.45 cycles per row at 31 taps (host_psf_carrier, host_detect_gain); a band near Nyquist comes out darker.  iq() returns the
         analytic pair of frame()'s RF whether or not the keyword is given.  Without the keyword no call and no bit changes."""
-        if detect is None or detect is False:
-            self.detect = None
-        elif isinstance(detect, str):
-            if detect != "quadrature":
-                raise ValueError("detect takes None, \"quadrature\" or a dict of n_taps=, got %r" % (detect,))
-            self.detect = {}
-        else:
-            self.detect = dict(detect)
+        self.detect = _option(detect, _detect_word)
         if self.detect is not None:
             host_detect_taps(detect_opts_struct(**self.detect).n_taps)   # (unknown keywords and a bad n_taps end it here)
-        self._bands_dev, self._bands_cap, self._banded = None, 0, False
-        self.autogain = None if autogain is None or autogain is False else ({} if autogain is True else dict(autogain))
+        self.autogain = _option(autogain)
         if self.autogain is not None:
             autogain_opts_struct(**self.autogain)           # (unknown keywords end it here)
-        self._ag_dev, self._ag_frames, self._ag_gain, self._ag_pen = None, 0, None, None
-        self.speckle3d = None if speckle3d is None or speckle3d is False else ({} if speckle3d is True else dict(speckle3d))
+        self._ag_gain, self._ag_pen = None, None
+        self.speckle3d = _option(speckle3d)
         if self.speckle3d is not None:
             speckle3d_opts_struct(**self.speckle3d)         # (unknown keywords and a wrong number of weights end it here)
         if sweep is not None and (compound is not None or elevation):
             raise ValueError("sweep= does not combine with compound= or elevation=")
         if compound is not None and not 1 <= len(tuple(compound)) <= 16:
             raise ValueError("compound takes 1..16 steering angles, got %d" % len(tuple(compound)))
-        self.speckle = None if speckle is None or speckle is False else speckle_opts_struct(**({} if speckle is True else dict(speckle)))
+        self.speckle = None if _option(speckle) is None else speckle_opts_struct(**_option(speckle))
         E = transducer.n_elements
         self.noise, self.noise_gain = None, None
-        if noise is not None and noise is not False:
-            nd = dict(noise) if isinstance(noise, dict) else dict(snr_db=noise)
+        nd = _option(noise, lambda snr_db: dict(snr_db=snr_db))
+        if nd is not None:
             gain, dead = nd.pop("element_gain", None), nd.pop("dead_elements", None)
             self.noise = noise_opts_struct(**nd)
             if gain is not None or dead is not None:
@@ -1427,6 +1461,9 @@ class Simulator:
         self.ctx.set_transducer(transducer.pos, transducer.dir)
         self.psf = psf or Psf(freq=transducer.frequency)
         self.rf_dev = self.ctx.alloc(E * self.R * 4)
+        # the band stack [n][B][E][R] of a psf with bands, auto gain's (sigma [F], pen [F], gain [F][R]), and whether band images of the own stack
+        # wait in the first (between convolve() and envelope() / fold_bands())
+        self._band_buf, self._gain_buf, self._held = _GrowOnly(self.ctx), _GrowOnly(self.ctx), False
         self.elevation, self.planes_dev, self.views_dev, self.sweep, self.sweep_dev = bool(elevation), None, None, None, None
         self.steers = tuple(float(x) for x in compound) if compound is not None else None
         self.N = len(self.steers) if self.steers is not None else 1
@@ -1460,13 +1497,14 @@ class Simulator:
 
     def close(self):
         if self.ctx.h:
-            for d in (self.rf_dev, self.planes_dev, self.views_dev, self.sweep_dev, self._ag_dev, self._bands_dev):
+            for d in (self.rf_dev, self.planes_dev, self.views_dev, self.sweep_dev):
                 if d:
                     self.ctx.free(d)
+            self._gain_buf.release(); self._band_buf.release()
             self.ctx.close()
 
     def trace(self, frame_id=0):
-        self._banded = False
+        self._held = False
         if self._pass is None:
             self.ctx.trace_frame(frame_id, self.rf_dev)
             return
@@ -1480,49 +1518,104 @@ class Simulator:
         """the RF row pitch [mm]: the depth of row r is r * row_mm (path length, as the reference's row index)"""
         return row_pitch_mm(self.ctx.params.frequency)
 
+    # ---- the images a stage acts on, and the stages over any of them
+    def _images(self, frame_id=0, own_frames=False, stack=None):
+        """the n images of a traced pass -- this simulator's stack, or `stack` = (device buffer, n) -- as the views or planes of ONE frame (one
+        receiver, one peak, one curve); own_frames=True: so many frames of one image each (the tracked frames of freehand()).  Image i was
+        traced with the id frame_id * n + i"""
+        dev, n = stack or self._stack
+        return _Images(dev, n, n if own_frames else 1, 1 if own_frames else n, frame_id * n)
+
+    def _band_images(self, s):
+        """the band images of s in the band stack: B per image of the same frame, image i's band b with the id (first id + i) * B + b"""
+        B = self.psf.bands.n_bands
+        return _Images(self._band_buf.reserve(s.images * B * self.E * self.R * 4), s.images * B, s.frames, s.per_frame * B, s.first_id * B)
+
+    def _convolve(self, s):
+        """-> the images that wait for the envelope: s, or with a psf that has bands its band images"""
+        if not self.psf.has_bands:
+            if self.psf.has_focus:
+                self.ctx.convolve_frames_depth(s.dev, s.images, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_rows(self.R, self.row_mm))
+            else:
+                self.ctx.convolve_frames(s.dev, s.images, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_kernel)
+            return s
+        p = self._band_images(s)
+        lat = dict(lat_rows=self.psf.lateral_rows(self.R, self.row_mm)) if self.psf.has_focus else dict(lateral=self.psf.lateral_kernel)
+        self.ctx.convolve_bands_frames(s.dev, s.images, self.E, self.R, self.psf.axial_rows(self.R, self.row_mm), p.dev, **lat)
+        return p
+
+    def _noise(self, p):
+        o = self.noise if self.noise is not None else noise_opts_struct()
+        kw = dict(sigma=o.sigma) if o.mode == NOISE_ABS else dict(snr_db=o.snr_db)
+        sigma_dev = self._gain_bufs(p.frames)[0] if self.autogain is not None else None   # (auto_gain()'s floor)
+        self.ctx.noise_frames(p.dev, p.frames, p.per_frame, self.E, self.R, first_image_id=p.first_id, element_gain=self.noise_gain, sigma_dev=sigma_dev,
+                              seed=o.seed, **kw)
+
+    def _detect(self, p, s):
+        if self.detect is not None:                     # quadrature detection in the place of the reference's envelope
+            self.ctx.detect_frames(p.dev, p.images, self.E, self.R, env_dev=p.dev, **self.detect)
+        else:
+            self.ctx.envelope_frames(p.dev, p.images, self.E, self.R)
+        self._fold(p, s)                                # every band image is detected on its own, then they are averaged (nothing to do without bands)
+
+    def _fold(self, p, s):
+        if p != s:
+            self.ctx.band_fold_frames(p.dev, s.images, self.psf.bands.n_bands, self.E, self.R, self.psf.band_weights(self.R, self.row_mm), s.dev)
+
+    def _despeckle(self, s):
+        o = self.speckle if self.speckle is not None else speckle_opts_struct()
+        self.ctx.speckle_frames(s.dev, s.images, self.E, self.R, n_iter=o.n_iter, q0=o.q0, rho=o.rho, lambda_=o.lambda_)
+
+    def _gain_bufs(self, F):
+        """the device side of auto_gain() for F frames: (sigma [F], pen [F], gain [F][R])"""
+        dev = self._gain_buf.reserve(F * (2 + self.R) * 4)
+        return dev, dev + 4 * F, dev + 8 * F
+
+    def _autogain(self, s):
+        sigma_dev, pen_dev, gain_dev = self._gain_bufs(s.frames)
+        self.ctx.autogain_frames(s.dev, s.frames, s.per_frame, self.E, self.R, floor_dev=sigma_dev if self.noise is not None else None, gain_dev=gain_dev,
+                                 pen_dev=pen_dev, **(self.autogain or {}))
+        self._ag_gain = self.ctx.d2h(gain_dev, (s.frames, self.R), np.float32)
+        self._ag_pen = self.ctx.d2h(pen_dev, (s.frames,), np.uint32)
+
+    def _stages(self, images, frame_id, convolve=True, envelope=True, own_frames=False):
+        """convolve (-> add_noise with noise=) -> envelope (-> despeckle with speckle=) (-> auto_gain with autogain=), or without the envelope the
+        fold alone, over images = (device buffer, n).  p is what waits for the envelope: the images, or their band images"""
+        s = self._images(frame_id, own_frames, images)
+        p = self._convolve(s) if convolve else s
+        if self.noise is not None:
+            self._noise(p)
+        if not envelope:
+            self._fold(p, s)
+            return
+        self._detect(p, s)
+        if self.speckle is not None:
+            self._despeckle(s)
+        if self.autogain is not None:
+            self._autogain(s)
+
+    # ---- the same stages one by one, over this simulator's own stack
+    def _pending(self, s):
+        return self._band_images(s) if self._held else s
+
     def convolve(self):
         """over the stack's images as so many frames (mcrt_convolve is mcrt_convolve_frames of one); with a psf that has bands into the band
         stack, where the images stay until envelope() or fold_bands() brings them back"""
-        if self.psf.has_bands:
-            dev, n = self._stack
-            lat = dict(lat_rows=self.psf.lateral_rows(self.R, self.row_mm)) if self.psf.has_focus else dict(lateral=self.psf.lateral_kernel)
-            self.ctx.convolve_bands_frames(dev, n, self.E, self.R, self.psf.axial_rows(self.R, self.row_mm), self._band_stack(n), **lat)
-            self._banded = True
-        elif self.psf.has_focus:
-            self.ctx.convolve_frames_depth(*self._stack, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_rows(self.R, self.row_mm))
-        else:
-            self.ctx.convolve_frames(*self._stack, self.E, self.R, self.psf.axial_kernel, self.psf.lateral_kernel)
+        self._held = self._convolve(self._images()) != self._images()
 
     def envelope(self):
-        dev, n = (self._bands_dev, self._stack[1] * self.psf.bands.n_bands) if self._banded else self._stack
-        if self.detect is not None:                     # quadrature detection in the place of the reference's envelope
-            self.ctx.detect_frames(dev, n, self.E, self.R, env_dev=dev, **self.detect)
-        else:
-            self.ctx.envelope_frames(dev, n, self.E, self.R)
-        self.fold_bands()                               # every band image is detected on its own, then they are averaged (nothing to do without bands)
-
-    def _band_stack(self, n):
-        """the band stack for n images, [n][B][E][R] floats on the device: one buffer that only grows"""
-        need = n * self.psf.bands.n_bands * self.E * self.R * 4
-        if self._bands_cap < need:
-            if self._bands_dev is not None:
-                self.ctx.free(self._bands_dev)
-            self._bands_dev, self._bands_cap = None, 0
-            self._bands_dev, self._bands_cap = self.ctx.alloc(need), need
-        return self._bands_dev
+        self._detect(self._pending(self._images()), self._images())
+        self._held = False
 
     def fold_bands(self):
         """mcrt_band_fold_frames: the band images that convolve() left, folded back into the stack with the bands' weights (nothing to do
         when there are none).  After envelope() that is frequency compounding; on RF it is a coherent sum"""
-        if self._banded:
-            dev, n = self._stack
-            self.ctx.band_fold_frames(self._bands_dev, n, self.psf.bands.n_bands, self.E, self.R, self.psf.band_weights(self.R, self.row_mm), dev)
-            self._banded = False
+        self._fold(self._pending(self._images()), self._images())
+        self._held = False
 
     def despeckle(self):
         """mcrt_speckle_frames over the stack's images, in place, with the options of speckle= (the defaults without one)"""
-        o = self.speckle if self.speckle is not None else speckle_opts_struct()
-        self.ctx.speckle_frames(*self._stack, self.E, self.R, n_iter=o.n_iter, q0=o.q0, rho=o.rho, lambda_=o.lambda_)
+        self._despeckle(self._images())
 
     def despeckle_volume(self, vox_dev, grid):
         """mcrt_speckle_volume_frames over the float block of grid on the device, in place, with the options of speckle3d= (the defaults
@@ -1530,47 +1623,20 @@ class Simulator:
         o = dict(self.speckle3d or {})
         if o.get("weights") is None:
             o["weights"] = host_speckle3d_weights(grid)
-        self.ctx.speckle_volume_frames(vox_dev, 1, (grid.nw, grid.nv, grid.nu), **o)
+        self.ctx.speckle_volume_frames(vox_dev, 1, _grid_shape(grid)[0], **o)
 
     def add_noise(self, frame_id=0, own_peaks=False):
         """mcrt_noise_frames over the stack's images, in place, with the options of noise= (the defaults without one): the images are the
         views or planes of ONE frame (one receiver, one peak) with the ids frame_id * (images in the stack) onwards; own_peaks=True: so many
-        frames of one image each (the tracked frames of freehand())"""
-        o = self.noise if self.noise is not None else noise_opts_struct()
-        dev, n = self._stack
-        if self._banded:                                # the band images: image i's band b with the id (frame_id * n + i) * B + b
-            B = self.psf.bands.n_bands
-            kw = dict(sigma=o.sigma) if o.mode == NOISE_ABS else dict(snr_db=o.snr_db)
-            sigma_dev = self._autogain_buffers(n if own_peaks else 1)[0] if self.autogain is not None else None
-            self.ctx.noise_frames(self._bands_dev, n if own_peaks else 1, B if own_peaks else n * B, self.E, self.R, first_image_id=frame_id * n * B,
-                                  element_gain=self.noise_gain, sigma_dev=sigma_dev, seed=o.seed, **kw)
-            return
-        kw = dict(sigma=o.sigma) if o.mode == NOISE_ABS else dict(snr_db=o.snr_db)
-        sigma_dev = self._autogain_buffers(n if own_peaks else 1)[0] if self.autogain is not None else None   # (auto_gain()'s floor)
-        self.ctx.noise_frames(dev, n if own_peaks else 1, 1 if own_peaks else n, self.E, self.R, first_image_id=frame_id * n, element_gain=self.noise_gain,
-                              sigma_dev=sigma_dev, seed=o.seed, **kw)
-
-    def _autogain_buffers(self, F):
-        """the device side of auto_gain() for F frames: (sigma [F], pen [F], gain [F][R]), one buffer that only grows"""
-        if self._ag_dev is None or self._ag_frames < F:
-            if self._ag_dev is not None:
-                self.ctx.free(self._ag_dev)
-            self._ag_dev, self._ag_frames = None, 0
-            self._ag_dev, self._ag_frames = self.ctx.alloc(F * (2 + self.R) * 4), F
-        return self._ag_dev, self._ag_dev + 4 * F, self._ag_dev + 8 * F
+        frames of one image each (the tracked frames of freehand()).  After a convolve() with bands it acts on the band images"""
+        self._noise(self._pending(self._images(frame_id, own_peaks)))
 
     def auto_gain(self, own_frames=False):
         """mcrt_autogain_frames over the stack's images, in place, with the options of autogain= (the defaults without one): the images are
         the views or planes of ONE frame (one receiver, one curve); own_frames=True: so many frames of one image each (the tracked frames
         of freehand()).  The floor is the sigma that add_noise() left on the device when noise= is on.  It keeps the row gains and the
         penetration depths for gain_curve() and penetration_mm()"""
-        dev, n = self._stack
-        F = n if own_frames else 1
-        sigma_dev, pen_dev, gain_dev = self._autogain_buffers(F)
-        self.ctx.autogain_frames(dev, F, 1 if own_frames else n, self.E, self.R, floor_dev=sigma_dev if self.noise is not None else None,
-                                 gain_dev=gain_dev, pen_dev=pen_dev, **(self.autogain or {}))
-        self._ag_gain = self.ctx.d2h(gain_dev, (F, self.R), np.float32)
-        self._ag_pen = self.ctx.d2h(pen_dev, (F,), np.uint32)
+        self._autogain(self._images(own_frames=own_frames))
 
     def gain_curve(self):
         """the row gains of the last run under autogain=: float32 [R], or [F][R] after freehand(); None before any"""
@@ -1585,18 +1651,7 @@ class Simulator:
 
     def _run(self, frame_id, convolve=True, envelope=True):
         self.trace(frame_id)
-        if convolve:
-            self.convolve()
-        if self.noise is not None:
-            self.add_noise(frame_id)
-        if envelope:
-            self.envelope()
-            if self.speckle is not None:
-                self.despeckle()
-            if self.autogain is not None:
-                self.auto_gain()
-        else:
-            self.fold_bands()
+        self._stages(self._stack, frame_id, convolve, envelope)
 
     def compound_image(self, frame_id=0, convolve=True, envelope=True, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         """trace -> convolve -> envelope -> mcrt_compound_frames -> host: the compounded float picture [out_rows][out_cols] (compound= only)"""
@@ -1614,8 +1669,8 @@ class Simulator:
         if self.sweep is None:
             raise RuntimeError("volume() needs Simulator(sweep=...)")
         self._run(frame_id, convolve, envelope)
-        shape = (grid.nw, grid.nv, grid.nu)
-        with self.ctx.temp(shape[0] * shape[1] * shape[2] * 4) as out:
+        shape, n = _grid_shape(grid)
+        with self.ctx.temp(n * 4) as out:
             self.ctx.volume_frames(self.sweep_dev, 1, self.E, self.R, self.sweep, grid, out, radius_mm=radius_mm, total_angle=total_angle)
             if self.speckle3d is not None:
                 self.despeckle_volume(out, grid)
@@ -1629,8 +1684,8 @@ class Simulator:
         if self.speckle3d is not None:
             raise RuntimeError("bmode_volume() gathers bytes straight from the planes: there is no float block for speckle3d= to filter (use volume())")
         self._run(frame_id)
-        shape = (grid.nw, grid.nv, grid.nu)
-        with self.ctx.temp(shape[0] * shape[1] * shape[2]) as out:
+        shape, n = _grid_shape(grid)
+        with self.ctx.temp(n) as out:
             self.ctx.bmode_volume_frames(self.sweep_dev, 1, self.E, self.R, self.sweep, grid, out, **display)
             return self.ctx.d2h(out, shape, np.uint8)
 
@@ -1653,8 +1708,8 @@ class Simulator:
             opts["mode"] = opts.pop("bmode_mode")
         view = render_view(grid, direction, up, pixel_mm, step_mm, size[0], size[1])
         self._run(frame_id)
-        shape = (grid.nw, grid.nv, grid.nu)
-        with self.ctx.temp(shape[0] * shape[1] * shape[2]) as vox, self.ctx.temp(size[0] * size[1]) as out:
+        shape, n = _grid_shape(grid)
+        with self.ctx.temp(n) as vox, self.ctx.temp(size[0] * size[1]) as out:
             self.ctx.bmode_volume_frames(self.sweep_dev, 1, self.E, self.R, self.sweep, grid, vox, **opts)
             if not labels:
                 self.ctx.render_frames(vox, 1, shape, view, out8_dev=out, in_u8=True, mode=mode, **ropts)
@@ -1678,26 +1733,10 @@ class Simulator:
         if self.steers is not None or self.sweep is not None or self.elevation:
             raise RuntimeError("freehand() does not combine with compound=, sweep= or elevation=")
         pos, dirs, F = _pose_tables("freehand", np.asarray(pos), np.asarray(dirs), None, self.E)
-        shape = (grid.nw, grid.nv, grid.nu)
-        n = shape[0] * shape[1] * shape[2]
+        shape, n = _grid_shape(grid)
         with self.ctx.temp(F * self.E * self.R * 4) as stack_dev, self.ctx.temp(n * 4) as out, self.ctx.temp(n * 4) as cnt:
             self.ctx.trace_frames_poses(frame_id * F, pos, dirs, stack_dev)
-            held, self._stack, self._banded = self._stack, (stack_dev, F), False
-            try:
-                if convolve:
-                    self.convolve()
-                if self.noise is not None:
-                    self.add_noise(frame_id, own_peaks=True)       # (every tracked frame is a frame of its own)
-                if envelope:
-                    self.envelope()
-                    if self.speckle is not None:
-                        self.despeckle()
-                    if self.autogain is not None:
-                        self.auto_gain(own_frames=True)
-                else:
-                    self.fold_bands()
-            finally:
-                self._stack = held
+            self._stages((stack_dev, F), frame_id, convolve, envelope, own_frames=True)       # (every tracked frame is a frame of its own)
             self.ctx.recon_frames(stack_dev, pos, dirs, F, self.E, self.R, grid, out, count_dev=cnt if counts else None, row_mm=row_mm, unit_mm=unit_mm, **opts)
             if self.speckle3d is not None:
                 self.despeckle_volume(out, grid)
@@ -1715,8 +1754,7 @@ class Simulator:
         if self.steers is not None or self.sweep is not None or self.elevation:
             raise RuntimeError("freehand_labels() does not combine with compound=, sweep= or elevation=")
         pos, dirs, F = _pose_tables("freehand_labels", np.asarray(pos), np.asarray(dirs), None, self.E)
-        shape = (grid.nw, grid.nv, grid.nu)
-        n = shape[0] * shape[1] * shape[2]
+        shape, n = _grid_shape(grid)
         with self.ctx.temp(F * self.E * self.R) as tissue, self.ctx.temp(n) as out, self.ctx.temp(n * 4) as cnt, self.ctx.temp(n * 4) as win:
             self.ctx.label_frames(pos, dirs, rule=rule, start_offset=start_offset, tissue_dev=tissue)
             self.ctx.recon_label_frames(tissue, pos, dirs, F, self.E, self.R, grid, self.n_materials, out, count_dev=cnt if counts else None,
@@ -1725,17 +1763,26 @@ class Simulator:
             return got if len(got) > 1 else got[0]
 
     @contextlib.contextmanager
-    def _label_pass(self, rule, start_offset, want_rows=True):
-        """the label pass of this probe into device buffers that live as long as the block -> (F, [tissue_dev, interface_dev, crossings_dev]): the K
+    def _beam_pass(self, call, tables, want_rows, **opts):
+        """a central-beam pass of this probe (call: Context.label_frames or transmit_frames, with opts) into device buffers that live as long as the
+        block -> (F, [the two row tables named in `tables` = ((keyword, bytes per sample), ...), crossings_dev]; only the first unless want_rows): the K
         planes of a sweep, else the unsteered probe in its own plane, whatever compound= and elevation= are"""
         F = self.sweep.n_planes if self.sweep is not None else 1
         n = F * self.E * self.R
         with contextlib.ExitStack() as held:
-            sizes = (n, 4 * n, 4 * F * self.E) if want_rows else (n, 0, 0)
+            sizes = (tables[0][1] * n, tables[1][1] * n, 4 * F * self.E) if want_rows else (tables[0][1] * n, 0, 0)
             bufs = [held.enter_context(self.ctx.temp(size)) if size else None for size in sizes]
             pos, dirs = (self.sweep_pos, self.sweep_dir) if self.sweep is not None else (None, None)
-            self.ctx.label_frames(pos, dirs, rule=rule, start_offset=start_offset, tissue_dev=bufs[0], interface_dev=bufs[1], crossings_dev=bufs[2])
+            call(pos, dirs, **opts, **{tables[0][0]: bufs[0], tables[1][0]: bufs[1], "crossings_dev": bufs[2]})
             yield F, bufs
+
+    def _label_pass(self, rule, start_offset, want_rows=True):
+        """-> (F, [tissue_dev, interface_dev, crossings_dev])"""
+        return self._beam_pass(self.ctx.label_frames, (("tissue_dev", 1), ("interface_dev", 4)), want_rows, rule=rule, start_offset=start_offset)
+
+    def _transmit_pass(self, mode, rule, start_offset, want_rows=True):
+        """-> (F, [transmit_dev, reflect_dev, crossings_dev])"""
+        return self._beam_pass(self.ctx.transmit_frames, (("transmit_dev", 4), ("reflect_dev", 4)), want_rows, mode=mode, rule=rule, start_offset=start_offset)
 
     def labels(self, rule="traced", start_offset=None, picture=True, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         """the ground truth of this probe's pictures -> dict(tissue uint8 [E][R], interface int32 [E][R], crossings uint32 [E], picture uint8
@@ -1757,22 +1804,10 @@ class Simulator:
         """the tissue of every point of grid, uint8 [nw][nv][nu]: the labels of volume() / bmode_volume() (sweep= only; LABEL_NONE outside the sweep)"""
         if self.sweep is None:
             raise RuntimeError("label_volume() needs Simulator(sweep=...)")
-        shape = (grid.nw, grid.nv, grid.nu)
-        with self._label_pass(rule, start_offset, want_rows=False) as (F, bufs), self.ctx.temp(shape[0] * shape[1] * shape[2]) as out:
+        shape, n = _grid_shape(grid)
+        with self._label_pass(rule, start_offset, want_rows=False) as (F, bufs), self.ctx.temp(n) as out:
             self.ctx.label_volume_frames(bufs[0], 1, self.E, self.R, self.sweep, grid, out, radius_mm=radius_mm, total_angle=total_angle)
             return self.ctx.d2h(out, shape, np.uint8)
-
-    @contextlib.contextmanager
-    def _transmit_pass(self, mode, rule, start_offset, want_rows=True):
-        """the transmission pass of this probe, as _label_pass -> (F, [transmit_dev, reflect_dev, crossings_dev])"""
-        F = self.sweep.n_planes if self.sweep is not None else 1
-        n = F * self.E * self.R
-        with contextlib.ExitStack() as held:
-            sizes = (4 * n, 4 * n, 4 * F * self.E) if want_rows else (4 * n, 0, 0)
-            bufs = [held.enter_context(self.ctx.temp(size)) if size else None for size in sizes]
-            pos, dirs = (self.sweep_pos, self.sweep_dir) if self.sweep is not None else (None, None)
-            self.ctx.transmit_frames(pos, dirs, mode=mode, rule=rule, start_offset=start_offset, transmit_dev=bufs[0], reflect_dev=bufs[1], crossings_dev=bufs[2])
-            yield F, bufs
 
     def transmission(self, mode="total", rule="traced", start_offset=None, picture=True, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         """the acoustic ground truth of this probe's pictures -> dict(transmit float32 [E][R], reflect float32 [E][R], crossings uint32 [E],
@@ -1796,8 +1831,8 @@ class Simulator:
         """`transmit` at every point of grid, float32 [nw][nv][nu]: the transmission of volume()'s voxels, through mcrt_volume_frames (sweep= only)"""
         if self.sweep is None:
             raise RuntimeError("transmission_volume() needs Simulator(sweep=...)")
-        shape = (grid.nw, grid.nv, grid.nu)
-        with self._transmit_pass(mode, rule, start_offset, want_rows=False) as (F, bufs), self.ctx.temp(shape[0] * shape[1] * shape[2] * 4) as out:
+        shape, n = _grid_shape(grid)
+        with self._transmit_pass(mode, rule, start_offset, want_rows=False) as (F, bufs), self.ctx.temp(n * 4) as out:
             self.ctx.volume_frames(bufs[0], 1, self.E, self.R, self.sweep, grid, out, radius_mm=radius_mm, total_angle=total_angle)
             return self.ctx.d2h(out, shape, np.float32)
 
@@ -1809,8 +1844,7 @@ class Simulator:
         if self.steers is not None or self.sweep is not None or self.elevation:
             raise RuntimeError("freehand_transmission() does not combine with compound=, sweep= or elevation=")
         pos, dirs, F = _pose_tables("freehand_transmission", np.asarray(pos), np.asarray(dirs), None, self.E)
-        shape = (grid.nw, grid.nv, grid.nu)
-        n = shape[0] * shape[1] * shape[2]
+        shape, n = _grid_shape(grid)
         with self.ctx.temp(F * self.E * self.R * 4) as stack_dev, self.ctx.temp(n * 4) as out, self.ctx.temp(n * 4) as cnt:
             self.ctx.transmit_frames(pos, dirs, mode=mode, rule=rule, start_offset=start_offset, transmit_dev=stack_dev)
             self.ctx.recon_frames(stack_dev, pos, dirs, F, self.E, self.R, grid, out, count_dev=cnt if counts else None, row_mm=row_mm, unit_mm=unit_mm, **opts)

@@ -747,7 +747,7 @@ public:
     {
         shape_params();
         check(dev->trace_frames(frame_id, 1, columns, rf.as<float>()), "mcrt_trace_frame");       // (every GPU of a group traces its scan-line shard)
-        where = on_device; holds = stack_of::nothing; n_views = 0; first_id = frame_id; sigma_frames = 0; banded = 0;
+        where = on_device; traced_as(stack_of::nothing, 0, frame_id);
     }
     // the same with slice thickness (psf.h:16-18,42,77; mcrt.h): the frame's n_planes elevation planes (0: the psf's elevation_size), spread
     // p.elevation_pitch_um() apart around the transducer's own plane, traced as ONE pose pass -- plane k with frame id frame_id * K + k, the
@@ -757,10 +757,10 @@ public:
         static_assert(N == columns, "one scan-line per transducer element");
         const uint32_t K = n_planes ? n_planes : (uint32_t)p.get_elevation_size();
         const auto tables = t.planes(K, p.elevation_pitch_um());
-        const std::vector<float> &w = p.elevation_rows(max_rows, (double)axial_resolution_um / 1000.0, K);
+        const std::vector<float> &w = p.elevation_rows(max_rows, row_mm(), K);
         pose_pass(frame_id, K, tables, planes, "rf_image::trace: frame_id * n_planes does not fit a frame id");
         check(mcrt_elevation_frames(dev->ctx, planes.as<float>(), 1, K, columns, max_rows, w.data(), rf.as<float>()), "mcrt_elevation_frames");
-        where = on_device; holds = stack_of::nothing; n_views = 0; first_id = frame_id; sigma_frames = 0; banded = 0;
+        where = on_device; traced_as(stack_of::nothing, 0, frame_id);
     }
     // spatial compounding (mcrt.h): the frame's views, one per steering angle [rad] of steer_rad (1..16), traced as ONE pose pass -- view n with
     // frame id frame_id * N + n, the frame-id rule of mcrt.h -- into a stack [N][columns][max_rows] this image owns.  convolve() and envelope()
@@ -772,7 +772,7 @@ public:
         const uint32_t V = (uint32_t)steer_rad.size();
         if (V == 0 || V > 16) throw std::invalid_argument("rf_image::trace: 1..16 steering angles");
         pose_pass(frame_id, V, t.steered(steer_rad), stack, "rf_image::trace: frame_id * views does not fit a frame id");
-        holds = stack_of::views; n_views = V; first_id = frame_id * V; sigma_frames = 0; banded = 0;
+        traced_as(stack_of::views, V, frame_id * V);
     }
     // volume imaging (mcrt.h): the K planes of a probe swept in elevation, traced as ONE pose pass -- plane k with frame id frame_id * K + k, the
     // frame-id rule of mcrt.h -- into the stack [K][columns][max_rows] the views of a compounded frame use.  convolve() and envelope() then run
@@ -783,7 +783,7 @@ public:
         static_assert(N == columns, "one scan-line per transducer element");
         if (sw.n_planes == 0 || sw.n_planes > 256) throw std::invalid_argument("rf_image::trace: a sweep has 1..256 planes");
         pose_pass(frame_id, sw.n_planes, t.swept(sw), stack, "rf_image::trace: frame_id * planes does not fit a frame id");
-        holds = stack_of::sweep_planes; n_views = sw.n_planes; sweep = sw; first_id = frame_id * sw.n_planes; sigma_frames = 0; banded = 0;
+        sweep = sw; traced_as(stack_of::sweep_planes, sw.n_planes, frame_id * sw.n_planes);
     }
     // freehand 3-D (mcrt.h: mcrt_recon_frames): the frames of a tracked probe moved by hand, one pose per frame -- a vector of transducers, or the
     // two tables [F][columns][3] (transducer::freehand makes a regular one) --, traced as ONE pose pass -- pose f with frame id frame_id * F + f
@@ -795,7 +795,7 @@ public:
         if (F == 0 || F > 65535 || pos.size() != F * one || dir.size() != pos.size()) throw std::invalid_argument("rf_image::trace: pose tables [F][columns][3], F = 1..65535");
         tracked.pos = pos; tracked.dir = dir;
         pose_pass(frame_id, (uint32_t)F, tracked, stack, "rf_image::trace: frame_id * poses does not fit a frame id");
-        holds = stack_of::tracked_frames; n_views = (uint32_t)F; first_id = frame_id * (uint32_t)F; sigma_frames = 0; banded = 0;
+        traced_as(stack_of::tracked_frames, (uint32_t)F, frame_id * (uint32_t)F);
     }
     template <size_t N> void trace(uint32_t frame_id, const std::vector<transducer<N>> &poses)
     {
@@ -812,11 +812,9 @@ public:
                                    const mcrt_speckle3d_opts *filter = nullptr)
     {
         if (holds != stack_of::tracked_frames) throw std::invalid_argument("rf_image::reconstruct: trace(frame, poses) first");
-        const size_t n = (size_t)grid.nu * grid.nv * grid.nw;
-        if (n == 0 || n >= ((size_t)1 << 31)) throw std::invalid_argument("rf_image::reconstruct: the grid needs 1 .. 2^31 - 1 voxels");
+        const size_t n = grid_points(grid, "reconstruct");
         points.reserve(8 * n);
-        const float depth_mm_f = (float)(uint32_t)(max_travel_time_us * speed_of_sound) * 0.001f;
-        check(mcrt_recon_frames(dev->ctx, stack.as<float>(), n_views, columns, max_rows, tracked.pos.data(), tracked.dir.data(), (double)depth_mm_f / (double)max_rows, 10.0,
+        check(mcrt_recon_frames(dev->ctx, stack.as<float>(), n_views, columns, max_rows, tracked.pos.data(), tracked.dir.data(), row_pitch_mm(), 10.0,
                                 &grid, opts, points.as<float>(), counts ? points.as<uint32_t>() + n : nullptr, nullptr), "mcrt_recon_frames");
         if (counts) *counts = download<uint32_t>(points.as<uint32_t>() + n, n);
         if (filter) check(mcrt_speckle_volume_frames(dev->ctx, points.as<float>(), 1, grid.nu, grid.nv, grid.nw, filter, points.as<float>()), "mcrt_speckle_volume_frames");
@@ -832,8 +830,7 @@ public:
                                                   std::vector<uint32_t> *counts = nullptr, std::vector<uint32_t> *votes = nullptr)
     {
         if (holds != stack_of::tracked_frames) throw std::invalid_argument("rf_image::reconstruct_labels: trace(frame, poses) first");
-        const size_t n = (size_t)grid.nu * grid.nv * grid.nw, taps = (size_t)n_views * columns * max_rows;
-        if (n == 0 || n >= ((size_t)1 << 31)) throw std::invalid_argument("rf_image::reconstruct_labels: the grid needs 1 .. 2^31 - 1 voxels");
+        const size_t n = grid_points(grid, "reconstruct_labels"), taps = (size_t)n_views * columns * max_rows;
         shape_params();
         label.reserve(taps);
         labelled = labels_of::nothing; label_planes = 0; label_tissue = nullptr;
@@ -843,37 +840,28 @@ public:
         points.reserve(9 * n);                                     // counts, votes, then the labels' bytes (the 32-bit tables first: aligned)
         uint32_t *count_dev = points.as<uint32_t>(), *votes_dev = count_dev + n;
         uint8_t *out_dev = points.as<uint8_t>() + 8 * n;
-        const float depth_mm_f = (float)(uint32_t)(max_travel_time_us * speed_of_sound) * 0.001f;
-        check(mcrt_recon_label_frames(dev->ctx, label.as<uint8_t>(), n_views, columns, max_rows, tracked.pos.data(), tracked.dir.data(), (double)depth_mm_f / (double)max_rows,
-                                      10.0, &grid, &ropts, out_dev, counts ? count_dev : nullptr, votes ? votes_dev : nullptr, nullptr), "mcrt_recon_label_frames");
+        check(mcrt_recon_label_frames(dev->ctx, label.as<uint8_t>(), n_views, columns, max_rows, tracked.pos.data(), tracked.dir.data(), row_pitch_mm(), 10.0, &grid, &ropts,
+                                      out_dev, counts ? count_dev : nullptr, votes ? votes_dev : nullptr, nullptr), "mcrt_recon_label_frames");
         if (counts) *counts = download<uint32_t>(count_dev, n);
         if (votes) *votes = download<uint32_t>(votes_dev, n);
         return download<unsigned char>(out_dev, n);
     }
     template <typename psf_> void convolve(const psf_ &p)
     {
-        float *img = rf.as<float>(); uint32_t frames = 1;
-        if (n_views) { img = stack.as<float>(); frames = n_views; }     // the views of a compounded frame (the planes of a sweep) as so many frames
-        else to_device();
+        const image_set s = traced();     // (the views of a compounded frame, the planes of a sweep, as so many frames)
+        const uint32_t n_ax = (uint32_t)p.get_axial_size(), n_lat = (uint32_t)p.get_lateral_size();
         if (p.has_bands()) {   // frequency compounding: the images go to the band stack, where add_noise() finds them and envelope() / fold_bands() brings them back
-            const double row_mm = (double)axial_resolution_um / 1000.0;
-            const std::vector<float> &ax = p.axial_rows(max_rows, row_mm);
+            const std::vector<float> &ax = p.axial_rows(max_rows, row_mm());
             const uint32_t B = p.n_bands();
-            band_w = p.band_weights(max_rows, row_mm);
-            band_stack.reserve(sizeof(float) * frames * B * columns * max_rows);
-            check(mcrt_convolve_bands_frames(dev->ctx, img, frames, columns, max_rows, B, ax.data(), (uint32_t)p.get_axial_size(),
-                                             p.has_focus() ? nullptr : p.lateral_kernel.data(), p.has_focus() ? p.lateral_rows(max_rows, row_mm).data() : nullptr,
-                                             (uint32_t)p.get_lateral_size(), band_stack.as<float>()), "mcrt_convolve_bands_frames");
+            band_w = p.band_weights(max_rows, row_mm());
+            band_stack.reserve(sizeof(float) * s.images * B * columns * max_rows);
+            check(mcrt_convolve_bands_frames(dev->ctx, s.dev, s.images, columns, max_rows, B, ax.data(), n_ax, p.has_focus() ? nullptr : p.lateral_kernel.data(),
+                                             p.has_focus() ? p.lateral_rows(max_rows, row_mm()).data() : nullptr, n_lat, band_stack.as<float>()), "mcrt_convolve_bands_frames");
             banded = B;
-            return;
-        }
-        if (p.has_focus()) {   // focal zones: a lateral kernel per row, rows axial_resolution_um / 1000 mm apart
-            const std::vector<float> &lat = p.lateral_rows(max_rows, (double)axial_resolution_um / 1000.0);
-            check(mcrt_convolve_frames_depth(dev->ctx, img, frames, columns, max_rows, p.axial_kernel.data(), (uint32_t)p.get_axial_size(), lat.data(), (uint32_t)p.get_lateral_size()), "mcrt_convolve_frames_depth");
-            return;
-        }
-        if (n_views) check(mcrt_convolve_frames(dev->ctx, img, frames, columns, max_rows, p.axial_kernel.data(), (uint32_t)p.get_axial_size(), p.lateral_kernel.data(), (uint32_t)p.get_lateral_size()), "mcrt_convolve_frames");
-        else check(mcrt_convolve(dev->ctx, img, columns, max_rows, p.axial_kernel.data(), (uint32_t)p.get_axial_size(), p.lateral_kernel.data(), (uint32_t)p.get_lateral_size()), "mcrt_convolve");
+        } else if (p.has_focus())   // focal zones: a lateral kernel per row, rows axial_resolution_um / 1000 mm apart
+            check(mcrt_convolve_frames_depth(dev->ctx, s.dev, s.images, columns, max_rows, p.axial_kernel.data(), n_ax, p.lateral_rows(max_rows, row_mm()).data(), n_lat), "mcrt_convolve_frames_depth");
+        else
+            check(mcrt_convolve_frames(dev->ctx, s.dev, s.images, columns, max_rows, p.axial_kernel.data(), n_ax, p.lateral_kernel.data(), n_lat), "mcrt_convolve_frames");
     }
     // the band images that convolve(p) left (p.has_bands()) folded back into the images with the bands' weights (mcrt_band_fold_frames); nothing
     // to do when there are none.  envelope() ends in it: detected band images averaged, frequency compounding.  Called on its own, before any
@@ -881,32 +869,24 @@ public:
     void fold_bands()
     {
         if (!banded) return;
-        float *img = n_views ? stack.as<float>() : rf.as<float>();
-        check(mcrt_band_fold_frames(dev->ctx, band_stack.as<float>(), n_views ? n_views : 1u, banded, columns, max_rows, band_w.data(), img), "mcrt_band_fold_frames");
+        const image_set s = traced();
+        check(mcrt_band_fold_frames(dev->ctx, band_stack.as<float>(), s.images, banded, columns, max_rows, band_w.data(), s.dev), "mcrt_band_fold_frames");
         banded = 0;
     }
     void envelope()
     {
-        if (banded) {
-            check(mcrt_envelope_frames(dev->ctx, band_stack.as<float>(), (n_views ? n_views : 1u) * banded, columns, max_rows), "mcrt_envelope_frames");
-            fold_bands();
-            return;
-        }
-        if (n_views) { check(mcrt_envelope_frames(dev->ctx, stack.as<float>(), n_views, columns, max_rows), "mcrt_envelope_frames"); return; }
-        to_device(); check(mcrt_envelope(dev->ctx, rf.as<float>(), columns, max_rows), "mcrt_envelope");
+        const image_set s = pending();
+        check(mcrt_envelope_frames(dev->ctx, s.dev, s.images, columns, max_rows), "mcrt_envelope_frames");
+        fold_bands();
     }
     // quadrature detection (mcrt.h: mcrt_detect_frames) in the place of envelope(): the FIR Hilbert envelope of whatever envelope() would have
     // detected, in place -- the band images of a convolve(p) with bands, which it then folds; the views, planes or tracked frames of the last
     // trace(); or this image.  Everything after it sees what it saw after envelope()
     void detect(const mcrt_detect_opts &o)
     {
-        if (banded) {
-            check(mcrt_detect_frames(dev->ctx, band_stack.as<float>(), (n_views ? n_views : 1u) * banded, columns, max_rows, &o, band_stack.as<float>(), nullptr), "mcrt_detect_frames");
-            fold_bands();
-            return;
-        }
-        if (n_views) { check(mcrt_detect_frames(dev->ctx, stack.as<float>(), n_views, columns, max_rows, &o, stack.as<float>(), nullptr), "mcrt_detect_frames"); return; }
-        to_device(); check(mcrt_detect_frames(dev->ctx, rf.as<float>(), 1, columns, max_rows, &o, rf.as<float>(), nullptr), "mcrt_detect_frames");
+        const image_set s = pending();
+        check(mcrt_detect_frames(dev->ctx, s.dev, s.images, columns, max_rows, &o, s.dev, nullptr), "mcrt_detect_frames");
+        fold_bands();
     }
     // the analytic pair of this image's RF at the RF rate: interleaved [columns][max_rows][2] = (the RF's own bits, its FIR Hilbert transform
     // along the scan-line).  The image is left as it is (call it before envelope() / detect()).  A stack of views, planes or tracked
@@ -914,10 +894,10 @@ public:
     void iq(const mcrt_detect_opts &o, std::vector<float> &interleaved)
     {
         if (n_views || banded) throw std::logic_error("rf_image::iq: the analytic pair is of one RF image, not of a stack or of band images");
-        to_device();
+        const image_set s = traced();
         const size_t n = (size_t)columns * max_rows;
         points.reserve(2 * sizeof(float) * n);
-        check(mcrt_detect_frames(dev->ctx, rf.as<float>(), 1, columns, max_rows, &o, nullptr, points.as<float>()), "mcrt_detect_frames");
+        check(mcrt_detect_frames(dev->ctx, s.dev, s.images, columns, max_rows, &o, nullptr, points.as<float>()), "mcrt_detect_frames");
         interleaved = download<float>(points.as<float>(), 2 * n);
     }
     // receiver noise (mcrt.h: mcrt_noise_frames): a noise floor and a gain per scan-line (element_gain: [columns] or null) over whatever the
@@ -927,22 +907,10 @@ public:
     // convolve(p) with bands it acts on the band images, B per image of the same frame, image i's band b with the id (first id + i) * B + b
     void add_noise(const mcrt_noise_opts &o, const float *element_gain = nullptr)
     {
-        const bool own = holds == stack_of::tracked_frames;
-        const uint32_t F = n_views && own ? n_views : 1u;
-        sigma.reserve(4 * (size_t)F);
-        if (banded) {          // the band images: image i's band b with the id (first_id + i) * B + b
-            check(mcrt_noise_frames(dev->ctx, band_stack.as<float>(), F, (own || !n_views ? 1u : n_views) * banded, columns, max_rows, first_id * banded, &o, element_gain,
-                                    sigma.as<float>()), "mcrt_noise_frames");
-            sigma_frames = F;
-            return;
-        }
-        if (n_views) {
-            check(mcrt_noise_frames(dev->ctx, stack.as<float>(), F, own ? 1u : n_views, columns, max_rows, first_id, &o, element_gain, sigma.as<float>()), "mcrt_noise_frames");
-            sigma_frames = F;
-            return;
-        }
-        to_device(); check(mcrt_noise_frames(dev->ctx, rf.as<float>(), 1, 1, columns, max_rows, first_id, &o, element_gain, sigma.as<float>()), "mcrt_noise_frames");
-        sigma_frames = 1;
+        const image_set s = pending();
+        sigma.reserve(4 * (size_t)s.frames);
+        check(mcrt_noise_frames(dev->ctx, s.dev, s.frames, s.per_frame, columns, max_rows, s.first_id, &o, element_gain, sigma.as<float>()), "mcrt_noise_frames");
+        sigma_frames = s.frames;
     }
     // automatic gain (mcrt.h: mcrt_autogain_frames): a depth gain curve estimated from each frame itself over whatever the last trace()
     // filled, in place -- this image, or the views of a compounded frame or the planes of a sweep as ONE frame (one receiver, one curve), or
@@ -951,16 +919,14 @@ public:
     // on this pass); otherwise o.floor.  gain_curve(), penetration_rows() and penetration_mm() return its by-products
     void autogain(const mcrt_autogain_opts &o, bool noise_floor = false)
     {
-        const bool own = holds == stack_of::tracked_frames;
-        const uint32_t F = n_views && own ? n_views : 1u;
+        const image_set s = traced();                                      // (band images that wait are not looked at: envelope() comes first)
+        const size_t F = s.frames;
         if (noise_floor && sigma_frames != F) throw std::logic_error("rf_image::autogain: noise_floor needs add_noise() on the same pass");
-        curve.reserve(4 * (size_t)F * (max_rows + 1u));             // the gains [F][max_rows], then the penetration depths [F]
+        curve.reserve(4 * F * (max_rows + 1u));                            // the gains [F][max_rows], then the penetration depths [F]
         float *k = curve.as<float>();
-        uint32_t *pen = reinterpret_cast<uint32_t *>(k + (size_t)F * max_rows);
-        const float *floor_dev = noise_floor ? sigma.as<float>() : nullptr;
-        if (n_views) check(mcrt_autogain_frames(dev->ctx, stack.as<float>(), F, own ? 1u : n_views, columns, max_rows, &o, floor_dev, k, nullptr, pen), "mcrt_autogain_frames");
-        else { to_device(); check(mcrt_autogain_frames(dev->ctx, rf.as<float>(), 1, 1, columns, max_rows, &o, floor_dev, k, nullptr, pen), "mcrt_autogain_frames"); }
-        gains = download<float>(k, (size_t)F * max_rows);
+        uint32_t *pen = reinterpret_cast<uint32_t *>(k + F * max_rows);
+        check(mcrt_autogain_frames(dev->ctx, s.dev, s.frames, s.per_frame, columns, max_rows, &o, noise_floor ? sigma.as<float>() : nullptr, k, nullptr, pen), "mcrt_autogain_frames");
+        gains = download<float>(k, F * max_rows);
         pens = download<uint32_t>(pen, F);
     }
     const std::vector<float> &gain_curve() const { return gains; }                 // the last autogain()'s row gains, [frames][max_rows]
@@ -971,8 +937,8 @@ public:
     // compounded frame, the planes of a sweep --, in place; it goes after envelope() and before whatever makes the picture
     void despeckle(const mcrt_speckle_opts &o)
     {
-        if (n_views) { check(mcrt_speckle_frames(dev->ctx, stack.as<float>(), n_views, columns, max_rows, &o, stack.as<float>()), "mcrt_speckle_frames"); return; }
-        to_device(); check(mcrt_speckle_frames(dev->ctx, rf.as<float>(), 1, columns, max_rows, &o, rf.as<float>()), "mcrt_speckle_frames");
+        const image_set s = traced();
+        check(mcrt_speckle_frames(dev->ctx, s.dev, s.images, columns, max_rows, &o, s.dev), "mcrt_speckle_frames");
     }
     // the views of trace(frame, transducer, steer_rad) compounded into the float picture scan_converted() / save() read (mcrt_compound_frames):
     // every pixel the mean of the views that cover it; with opts (mcrt_compound_opts: weights per view, a lateral edge ramp, max or median)
@@ -1064,19 +1030,14 @@ public:
     };
     template <size_t N> label_maps labels(const transducer<N> &t, const mcrt_label_opts *opts = nullptr)
     {
-        static_assert(N == columns, "one scan-line per transducer element");
-        const bool swept = holds == stack_of::sweep_planes;
-        const uint32_t K = swept ? sweep.n_planes : 1u;
-        shape_params();
+        const beam_poses b = central_beams(t);
+        const uint32_t K = b.planes;
         const size_t lines = (size_t)K * columns, taps = lines * max_rows;
         label.reserve(taps + 4 * taps + 4 * lines);      // bytes: tissue, interface, crossings
         unsigned char *tissue_dev = label.as<unsigned char>() + 4 * taps + 4 * lines;      // (the 32-bit tables first: aligned)
         int32_t *interface_dev = label.as<int32_t>(); uint32_t *crossings_dev = label.as<uint32_t>() + taps;
-        std::vector<float> pos, dir;
-        if (swept) { auto tab = t.swept(sweep); pos = std::move(tab.pos); dir = std::move(tab.dir); }
-        else { pos = t.pos; dir = t.dir; }
         mcrt_ctx *tracer = dev->tracer();
-        check(mcrt_label_frames(tracer, K, 0, columns, pos.data(), dir.data(), opts, tissue_dev, interface_dev, crossings_dev), "mcrt_label_frames");
+        check(mcrt_label_frames(tracer, K, 0, columns, b.pos.data(), b.dir.data(), opts, tissue_dev, interface_dev, crossings_dev), "mcrt_label_frames");
         check(mcrt_synchronize(tracer), "mcrt_synchronize");
         label_maps m;
         m.planes = K;
@@ -1115,18 +1076,13 @@ public:
     };
     template <size_t N> transmission_maps transmission(const transducer<N> &t, const mcrt_transmit_opts *opts = nullptr)
     {
-        static_assert(N == columns, "one scan-line per transducer element");
-        const bool swept = holds == stack_of::sweep_planes;
-        const uint32_t K = swept ? sweep.n_planes : 1u;
-        shape_params();
+        const beam_poses b = central_beams(t);
+        const uint32_t K = b.planes;
         const size_t lines = (size_t)K * columns, taps = lines * max_rows;
         sound.reserve(4 * (2 * taps + lines));      // transmit, reflect, crossings
         float *transmit_dev = sound.as<float>(), *reflect_dev = transmit_dev + taps; uint32_t *crossings_dev = sound.as<uint32_t>() + 2 * taps;
-        std::vector<float> pos, dir;
-        if (swept) { auto tab = t.swept(sweep); pos = std::move(tab.pos); dir = std::move(tab.dir); }
-        else { pos = t.pos; dir = t.dir; }
         mcrt_ctx *tracer = dev->tracer();
-        check(mcrt_transmit_frames(tracer, K, 0, columns, pos.data(), dir.data(), opts, transmit_dev, reflect_dev, crossings_dev), "mcrt_transmit_frames");
+        check(mcrt_transmit_frames(tracer, K, 0, columns, b.pos.data(), b.dir.data(), opts, transmit_dev, reflect_dev, crossings_dev), "mcrt_transmit_frames");
         check(mcrt_synchronize(tracer), "mcrt_synchronize");
         transmission_maps m;
         m.planes = K;
@@ -1159,6 +1115,45 @@ public:
     void save(const std::string &filename) const { write_pgm(filename, 500, 400, to_bytes(scan_converted())); }   // rfimage.h:142-148 writes an 8-bit image; here: binary PGM
     std::shared_ptr<device> dev;
 private:
+    enum class stack_of { nothing, views, sweep_planes, tracked_frames };
+    // the device images a stage acts on: `images` of them from dev on, as `frames` frames of `per_frame` each, the first with the id first_id.
+    // traced() and pending() are the only place that reads n_views, holds, banded, first_id and where together
+    struct image_set { float *dev; uint32_t images, frames, per_frame, first_id; };
+    // what the last trace() left: the RF image (uploaded if it is on the host) as one image of one frame; or the stack's n_views images -- one
+    // frame of n_views (one receiver), or with tracked frames n_views frames of one
+    image_set traced()
+    {
+        if (!n_views) { to_device(); return { rf.as<float>(), 1u, 1u, 1u, first_id }; }
+        const bool own = holds == stack_of::tracked_frames;
+        return { stack.as<float>(), n_views, own ? n_views : 1u, own ? 1u : n_views, first_id };
+    }
+    // traced(); while band images wait for envelope() / fold_bands() the band stack instead: B per image of the same frame, image i's band b with the
+    // id (first id + i) * B + b
+    image_set pending()
+    {
+        const image_set s = traced();
+        return banded ? image_set{ band_stack.as<float>(), s.images * banded, s.frames, s.per_frame * banded, s.first_id * banded } : s;
+    }
+    // the tail of every trace(): what the stack holds now, how many images, the first one's id; no sigma, no band images
+    void traced_as(stack_of what, uint32_t n, uint32_t id) { holds = what; n_views = n; first_id = id; sigma_frames = 0; banded = 0; }
+    // labels() / transmission(): the poses whose central beams they walk -- the K planes of the sweep when the last trace was a sweep, else t's own plane
+    struct beam_poses { uint32_t planes; std::vector<float> pos, dir; };
+    template <size_t N> beam_poses central_beams(const transducer<N> &t)
+    {
+        static_assert(N == columns, "one scan-line per transducer element");
+        shape_params();
+        if (holds != stack_of::sweep_planes) return { 1u, t.pos, t.dir };
+        auto tab = t.swept(sweep);
+        return { sweep.n_planes, std::move(tab.pos), std::move(tab.dir) };
+    }
+    static size_t grid_points(const mcrt_volume_grid &grid, const char *who)   // the points of a grid; 0 or 2^31 and more: it throws
+    {
+        const size_t n = (size_t)grid.nu * grid.nv * grid.nw;
+        if (n == 0 || n >= ((size_t)1 << 31)) throw std::invalid_argument(std::string("rf_image::") + who + ": the grid needs 1 .. 2^31 - 1 points");
+        return n;
+    }
+    // the length of a row of a scan-line [mm] as reconstruct() bins it: depth_mm_f / max_rows, the row pitch of volume(grid)'s maps
+    static double row_pitch_mm() { return (double)((float)(uint32_t)(max_travel_time_us * speed_of_sound) * 0.001f) / (double)max_rows; }
     void to_device()
     {
         if (where == on_host) { check(mcrt_import_rf(dev->ctx, host.data(), columns, max_rows, rf.as<float>()), "mcrt_import_rf"); where = on_device; }
@@ -1216,8 +1211,7 @@ private:
     size_t volume_prepare(const mcrt_volume_grid &grid, size_t size)
     {
         if (holds != stack_of::sweep_planes) throw std::invalid_argument("rf_image::volume: trace(frame, transducer, sweep) first");
-        const size_t n = (size_t)grid.nu * grid.nv * grid.nw;
-        if (n == 0 || n >= ((size_t)1 << 31)) throw std::invalid_argument("rf_image::volume: the grid needs 1 .. 2^31 - 1 points");
+        const size_t n = grid_points(grid, "volume");
         points.reserve(n * size);
         return n;
     }
@@ -1253,7 +1247,7 @@ private:
     size_t bmode_n = 0; uint32_t bmode_rows = 0, bmode_cols = 0; bool state_valid = false;
     device_buffer planes;                        // trace(frame, transducer, psf): the plane stack [K][columns][max_rows]
     device_buffer stack;                         // trace(frame, transducer, steer_rad | sweep): the images [n_views][columns][max_rows]
-    enum class stack_of { nothing, views, sweep_planes, tracked_frames } holds = stack_of::nothing;   // ... what the last trace left in it
+    stack_of holds = stack_of::nothing;          // ... what the last trace left in it
     uint32_t n_views = 0;                        // ... and how many (nothing: 0)
     uint32_t first_id = 0;                       // the frame id the last trace() gave its first image (add_noise: the noise streams' ids)
     uint32_t sigma_frames = 0;                   // ... the frames sigma holds since the last trace() (0: add_noise() has not run)

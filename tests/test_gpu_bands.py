@@ -279,7 +279,7 @@ def test_simulator(mcrt, orc, sphere, tex256):
     try:
         raw = plain.frame(0, convolve=False)
         got = plain.frame(0)
-        assert not plain.psf.has_bands and plain._bands_dev is None
+        assert not plain.psf.has_bands and plain._band_buf.dev is None
         ic.assert_same_bits(got, orc.convolve(raw, plain.psf.axial_kernel, plain.psf.lateral_kernel), "no bands")
         plain._run(0)
         plain_env = plain.ctx.d2h(plain.rf_dev, (plain.E, plain.R)).T
@@ -319,10 +319,10 @@ def test_simulator(mcrt, orc, sphere, tex256):
         fid, opts = 2, dict(snr_db=30.0, seed=77)
         raw2 = _raw_of(noisy, fid)
         noisy.convolve()
-        clean = noisy.ctx.d2h(noisy._bands_dev, (3, E, R))
+        clean = noisy.ctx.d2h(noisy._band_buf.dev, (3, E, R))
         noisy.add_noise(fid)
         want_bands, _ = nm.noise(clean[None], (fid * 1 + 0) * 3, opts)          # one receiver, one peak; image 0's band b has the id (fid * 1 + 0) * 3 + b
-        ic.assert_same_bits(noisy.ctx.d2h(noisy._bands_dev, (3, E, R)), want_bands[0], "noise on the band images")
+        ic.assert_same_bits(noisy.ctx.d2h(noisy._band_buf.dev, (3, E, R)), want_bands[0], "noise on the band images")
         _, want = _chain(orc, raw2, psf, R, row_mm, noise=lambda x: nm.noise(x[None], fid * 3, opts)[0][0])
         noisy._run(fid)
         ic.assert_same_bits(noisy.ctx.d2h(noisy.rf_dev, (E, R)).T, want, "noisy bands")
@@ -346,7 +346,7 @@ def test_simulator_with_compound(mcrt, sphere, tex256):
         try:
             pics.append(sim.compound_image(0, out_rows=100, out_cols=120))
             assert sim._stack == (sim.views_dev, 3)
-            assert (sim._bands_cap == 3 * 3 * sim.E * sim.R * 4) if bands else sim._bands_dev is None
+            assert (sim._band_buf.nbytes == 3 * 3 * sim.E * sim.R * 4) if bands else sim._band_buf.dev is None
         finally:
             sim.close()
     assert pics[0].shape == pics[1].shape == (100, 120) and np.isfinite(pics[1]).all() and pics[1].max() > 0

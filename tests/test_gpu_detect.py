@@ -224,9 +224,9 @@ def test_simulator_chain(mcrt, small, case):
             hand.add_noise(fid)
         if case == "bands":
             B = 2
-            imgs = hand.ctx.d2h(hand._bands_dev, (n * B, E, R))
-            hand.ctx.detect_frames(hand._bands_dev, n * B, E, R, env_dev=hand._bands_dev, n_taps=n_taps)
-            hand.ctx.band_fold_frames(hand._bands_dev, n, B, E, R, hand.psf.band_weights(R, hand.row_mm), stack)
+            imgs = hand.ctx.d2h(hand._band_buf.dev, (n * B, E, R))
+            hand.ctx.detect_frames(hand._band_buf.dev, n * B, E, R, env_dev=hand._band_buf.dev, n_taps=n_taps)
+            hand.ctx.band_fold_frames(hand._band_buf.dev, n, B, E, R, hand.psf.band_weights(R, hand.row_mm), stack)
             mirror = em.fold(dm.detect(imgs, n_taps)[0].reshape(n, B, E, R), hand.psf.band_weights(R, hand.row_mm))
         else:
             imgs = hand.ctx.d2h(stack, (n, E, R))
@@ -244,7 +244,7 @@ def test_simulator_chain(mcrt, small, case):
     try:
         sim._run(fid)
         got = sim.ctx.d2h(sim._stack[0], (n, E, R))
-        assert not sim._banded
+        assert not sim._held
         if case == "compound":
             pic = sim.compound_image(fid, out_rows=60, out_cols=80)
             assert pic.shape == (60, 80) and np.isfinite(pic).all() and pic.max() > 0
