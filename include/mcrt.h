@@ -70,7 +70,11 @@ extern "C" {
                                    + mcrt_bands, mcrt_default_bands, mcrt_psf_band_kernels, mcrt_convolve_bands_frames, mcrt_band_fold_frames
                                    (frequency compounding and the depth downshift: an axial kernel per RF row and per band; additive);
                                    + mcrt_detect_opts, mcrt_default_detect_opts, mcrt_detect_taps, mcrt_detect_gain, mcrt_psf_carrier, mcrt_detect_frames
-                                   (quadrature detection: an FIR Hilbert transformer along the scan-line, the envelope and the I/Q pair; additive) */
+                                   (quadrature detection: an FIR Hilbert transformer along the scan-line, the envelope and the I/Q pair; additive);
+                                   + mcrt_flow_opts, mcrt_default_flow_opts, mcrt_flow_nyquist, mcrt_flow_phasors, mcrt_flow_draws, mcrt_colour_map,
+                                   mcrt_flow_split_frames, mcrt_flow_frames, mcrt_colour_opts, mcrt_default_colour_opts, mcrt_colour_frames
+                                   (colour Doppler: a slow-time ensemble synthesised from one traced frame, the Kasai autocorrelator, the flow overlay and
+                                   the true axial velocity per sample; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -1215,6 +1219,129 @@ int mcrt_recon_label_frames(mcrt_ctx *ctx, const uint8_t *stack_dev /* [F][E][R]
  * MCRT_ERR_INVALID for an out_dev that overlaps label_dev or depth_dev.  On an error nothing is launched.  Groups: call it on mcrt_group_root(). */
 int mcrt_render_label_frames(mcrt_ctx *ctx, const uint8_t *label_dev /* [n_frames][nw][nv][nu] */, uint32_t n_frames, uint32_t nu, uint32_t nv, uint32_t nw,
                              const mcrt_render_view *view, const float *depth_dev /* [n_frames][ny][nx] */, uint8_t *out_dev /* [n_frames][ny][nx] */);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Colour Doppler: a slow-time ensemble, the Kasai autocorrelator, the flow overlay and the true axial velocity per sample.  Every scene
+ * file marks meshes as vascular and carries a BLOOD material; a colour line is N pulses (the ensemble) fired down the same scan-line, and
+ * the phase the moving echo turns by from pulse to pulse is the velocity.  The reference has no counterpart.  THE MODEL: the ensemble is
+ * SYNTHESISED from one traced frame and not traced N times (every frame id has its own Philox key, so the clutter of two traces
+ * decorrelates far more than blood would).  The raw trace is split by tissue label into what stands still and what moves
+ * (mcrt_flow_split_frames); both images go through the existing PSF and mcrt_detect_frames(iq_dev); and the ensemble of a sample is
+ *   z_n = static + moving * p^n + noise_n,   n = 0 .. N-1,
+ * with the phasor p of the sample's material and scan-line: the narrow-band model the autocorrelator of Kasai et al. (1985) is derived under.
+ * LEFT OUT: velocity profiles (a material has ONE velocity vector), transit-time and axial-shift decorrelation of moving speckle, the
+ * blood echo the PSF leaks outside the lumen (it keeps the label of where it lands), power / variance / spectral displays, persistence.
+ * An opt-in chain; without it no call and no bit changes.
+ *
+ * Throughout, every float operation is rounded once: no fma, correctly rounded / and sqrtf, no device transcendental. */
+#define MCRT_FLOW_WALL_NONE 0u
+#define MCRT_FLOW_WALL_MEAN 1u
+#define MCRT_FLOW_WALL_LINEAR 2u
+typedef struct {
+    uint32_t n_packets;     /* N, the pulses of the ensemble: 2..16; default 8 */
+    uint32_t wall;          /* the clutter ("wall") filter over the ensemble, MCRT_FLOW_WALL_*; default MEAN */
+    uint32_t avg_rows;      /* half-window of the spatial average along the scan-line: 0..8; default 2 */
+    uint32_t avg_lines;     /* ... and across scan-lines: 0..4; default 1 */
+    float prf_hz;           /* pulse repetition frequency, finite and > 0; default 4000 (read by mcrt_flow_nyquist alone) */
+    float freq_mhz;         /* the colour pulse's centre frequency; <= 0 (default 0): the caller's (the context's) frequency (mcrt_flow_nyquist alone) */
+    float sigma;            /* the receiver noise per I/Q component, finite and >= 0, used when no sigma_dev is given; default 0 */
+    uint32_t seed;          /* Philox key word 0 of the noise streams; default 0x464C4F57 */
+} mcrt_flow_opts;           /* 32 bytes */
+/* the defaults above.  MCRT_ERR_INVALID for a null o.  Host only. */
+int mcrt_default_flow_opts(mcrt_flow_opts *o);
+/* the velocity whose phase step is pi, in double:  f = o->freq_mhz > 0 ? (double)o->freq_mhz : freq_mhz;
+ *   *v_nyq_mm_s = (speed_of_sound * 1000.0 * (double)o->prf_hz) / (4.0 * (f * 1.0e6))           (1500 m/s, 4.5 MHz, 4 kHz: 333.33 mm/s)
+ * Host only.  MCRT_ERR_INVALID for a null pointer, options out of range, or an f or a speed_of_sound that is not finite and > 0. */
+int mcrt_flow_nyquist(const mcrt_flow_opts *o, double freq_mhz, double speed_of_sound, double *v_nyq_mm_s);
+/* the phasor and the true axial velocity of every (material, scan-line).  vel_mm_s [n_labels][3]: a velocity vector per material
+ * [mm/s]; dir [E][3]: the scan-lines' directions (mcrt_transducer's).  In double, with the floats widened exactly:
+ *   v_t = 0.0 - ((vx * dx + vy * dy) + vz * dz)          the velocity TOWARDS the probe, positive
+ *   truth[l][e] = (float)v_t;      phi = 3.141592653589793 * v_t / v_nyq_mm_s;      phasor[l][e] = ((float)cos(phi), (float)sin(phi))
+ * and a material whose three components are all zero gets exactly truth +0.0f and phasor (1.0f, +0.0f).  Host only.  MCRT_ERR_INVALID
+ * for a null pointer, n_labels == 0 or n_elements == 0, a v_nyq_mm_s that is not finite and > 0, or any vel / dir that is not finite;
+ * MCRT_ERR_LIMIT for n_labels > 254; on an error nothing is written. */
+int mcrt_flow_phasors(double v_nyq_mm_s, const float *vel_mm_s /* [n_labels][3] */, const float *dir /* [E][3] */, uint32_t n_labels, uint32_t n_elements,
+                      float *phasor /* [n_labels][E][2] */, float *truth /* [n_labels][E] */);
+/* the integer noise draws of one image's ensemble, d[n][e][r][0..1] (I, Q): one Philox4x32-10 block o[0..3] per (e, r, n) with the counter
+ * (e, r, 0x464C4F57, n) and the key (seed, image_id);
+ *   d_I = ((o0 & 0xffff) + (o0 >> 16) + (o1 & 0xffff) + (o1 >> 16)) - 131070,   d_Q the same of o2, o3
+ * an Irwin-Hall sum of four 16-bit uniforms about its mean: variance exactly 1431655765, so inv_std = (float)(1.0 / sqrt(1431655765.0)).
+ * Counter word 2 differs from mcrt_noise_frames' (0x4E4F4953) and from the tracer's (a bounce, < 16): the streams cannot coincide.  Host
+ * only.  MCRT_ERR_INVALID for a null d, zero sizes or n_packets outside 2..16; MCRT_ERR_LIMIT for n_rows > 2048. */
+int mcrt_flow_draws(uint32_t seed, uint32_t image_id, uint32_t n_elements, uint32_t n_rows, uint32_t n_packets, int32_t *d /* [N][E][R][2] */);
+/* the colour table of the overlay, lut[i] = (r, g, b).  kind 0, the red-towards / blue-away map, in integer arithmetic:
+ *   i == 128:       (0, 0, 0)
+ *   i = 129..255:   k = i - 128;  (128 + k, k <= 64 ? 0 : (k - 64) * 4, 0)                  red to yellow
+ *   i = 1..127:     k = 128 - i;  (0, k <= 64 ? 0 : (k - 64) * 4, 128 + k)                  blue to cyan
+ *   i == 0:         lut[1]
+ * Host only.  MCRT_ERR_INVALID for a null lut or another kind. */
+int mcrt_colour_map(uint32_t kind, uint8_t *lut /* [256][3] */);
+/* the raw trace split by label, before the PSF:  with l = tissue_dev[f][e][r] and  mv = l < n_labels && moving[l] != 0,
+ *   out_dev[f][0][e][r] = mv ? +0.0f : rf's own bits;      out_dev[f][1][e][r] = mv ? rf's own bits : +0.0f
+ * (MCRT_LABEL_NONE and any label >= n_labels stand still; a NaN goes where its label sends it).  moving [n_labels] is HOST memory, free
+ * when the call returns.  Every element of out_dev [F][2][E][R] is written; rf_dev and tissue_dev are read only.  What follows is
+ * mcrt_convolve_frames* and mcrt_detect_frames(iq_dev) over the 2 F images, untouched.  Asynchronous on the context's stream.
+ * MCRT_ERR_INVALID for a null pointer, zero sizes, n_labels == 0, or an out_dev that overlaps rf_dev or tissue_dev; MCRT_ERR_LIMIT for
+ * n_labels > 254 or a stack of 2^31 samples or more; on any error nothing is launched.  Groups: call it on mcrt_group_root(). */
+int mcrt_flow_split_frames(mcrt_ctx *ctx, const float *rf_dev /* [F][E][R] */, const uint8_t *tissue_dev /* [F][E][R] */, uint32_t n_frames,
+                           uint32_t n_elements, uint32_t n_rows, const uint8_t *moving /* [n_labels] */, uint32_t n_labels, float *out_dev /* [F][2][E][R] */);
+/* the colour processor.  Per sample (f, e, r) with l = tissue_dev[f][e][r], N = o->n_packets, (c, s) = l < n_labels ? phasor[l][e] : (1, 0):
+ * 1. THE ENSEMBLE.  m_0 = iq_moving_dev[f][e][r];  m_(n+1) = (a * c - b * s, a * s + b * c) of m_n = (a, b): four products, one
+ *    subtraction, one addition.  k = sigma_f * inv_std with sigma_f = sigma_dev ? sigma_dev[f] : o->sigma.  Per component
+ *      z_n = (static + m_n) + k * (float)d_n
+ *    where the first addition is skipped when iq_static_dev is NULL and the noise term when k == 0 (no Philox block is computed then);
+ *    d_n are mcrt_flow_draws' of the image id first_image_id + f.
+ * 2. THE WALL FILTER over n, per component.  NONE: w = z.  MEAN: w_n = z_n - (the PAIRWISE sum of z_n) / (float)N -- level by level
+ *    neighbours are added in pairs, (z_0 + z_1), (z_2 + z_3), ..., an odd last term is carried up as it is, until one term is left: N
+ *    equal terms then sum to N times the term exactly where N is a power of two, and what stands still leaves the filter as +0.0f.
+ *    LINEAR: after MEAN, with t_n = (float)(2 n - (N - 1)):  w_n = w_n - t_n * ((sum of t_n * w_n) / (sum of t_n * t_n)), both sums
+ *    ascending from 0.0f.
+ * 3. THE AUTOCORRELATION, every sum ascending from 0.0f, the products before the sums:
+ *      r0 = sum over n of (w_n.re * w_n.re + w_n.im * w_n.im)
+ *      r1 = sum over n = 0 .. N-2 of w_(n+1) * conj(w_n):  re += (a * c + b * d),  im += (b * c - a * d)  with w_(n+1) = (a, b), w_n = (c, d)
+ * 4. THE AVERAGE, for each of the three planes x = r0, Re r1, Im r1, with a = o->avg_rows and b = o->avg_lines:
+ *      s[e][r] = sum over dr = -a .. a ascending, rows r + dr inside [0, R), of x[e][r + dr]              (from 0.0f)
+ *      S[e][r] = sum over de = -b .. b ascending, lines e + de inside [0, E), of s[e + de][r]            (from 0.0f)
+ *      out = S / (float)cnt,  cnt = (rows inside) * (lines inside)
+ *    The separable order is the contract; a window larger than the image is the whole image.
+ * 5. THE OUTPUTS, each a device pointer or NULL, at least one given:
+ *      corr_dev [F][3][E][R]   the planes r0, Re r1, Im r1 (plane-major: mcrt_scan_convert_frames over 3 F frames gathers it as it is)
+ *      vel_dev [F][E][R]       mcrt_det_atan2f(Im, Re) * (float)(v_nyq_mm_s / 3.141592653589793)
+ *      var_dev [F][E][R]       r0 > 0 ? v : 0.0f  with v = 1.0f - sqrtf(Re * Re + Im * Im) / r0, then v < 0 -> 0.0f, v > 1 -> 1.0f (a NaN stays)
+ *      truth_dev [F][E][R]     l < n_labels ? truth[l][e] : 0.0f -- the registered ground truth, not aliased
+ * mcrt_det_atan2f(y, x), float throughout:  ax = |x|, ay = |y|;  ay > ax ? (hi, lo) = (ay, ax) : (hi, lo) = (ax, ay);  hi == 0 gives +0.0f;
+ *   t = lo / hi;  s = t * t;  P = c5;  P = P * s + c_j for j = 4 .. 0 (a multiply, then an add);  a = t * P;
+ *   c0..c5 = 0.99997726f, -0.33262347f, 0.19354346f, -0.11643287f, 0.05265332f, -0.01172120f;
+ *   ay > ax: a = 1.5707964f - a;   x < 0: a = 3.1415927f - a;   y < 0: a = -a.       Within 1e-5 rad of atan2 (measured 1.96e-6).
+ * phasor [n_labels][E][2] and truth [n_labels][E] are HOST tables (mcrt_flow_phasors'), finite, free when the call returns; they live in
+ * buffers of the context and are copied only when they differ from what is there.  Every element of every output given is written; the
+ * inputs are read only; any overlap of an output with an input or with another output is MCRT_ERR_INVALID.  The per-sample correlation
+ * lives in a grow-only buffer of the context: nothing is allocated after the first call at a size.  Asynchronous on the context's stream.
+ * MCRT_ERR_INVALID for a null ctx, iq_moving_dev, tissue_dev, phasor, truth or o, zero sizes, n_labels == 0, options out of range, a
+ * v_nyq_mm_s that is not finite and > 0, a table entry that is not finite, no output; MCRT_ERR_LIMIT for n_rows > 2048, n_labels > 254, a
+ * stack of 2^31 samples or more, image ids that pass 2^32; on any error nothing is launched and nothing is written.  Groups: call it on
+ * mcrt_group_root(). */
+int mcrt_flow_frames(mcrt_ctx *ctx, const float *iq_static_dev /* [F][E][R][2] or NULL */, const float *iq_moving_dev /* [F][E][R][2] */,
+                     const uint8_t *tissue_dev /* [F][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows, const mcrt_flow_opts *o,
+                     double v_nyq_mm_s, const float *phasor /* [n_labels][E][2] */, const float *truth /* [n_labels][E] */, uint32_t n_labels,
+                     uint32_t first_image_id, const float *sigma_dev /* [F] or NULL */, float *corr_dev /* [F][3][E][R] or NULL */,
+                     float *vel_dev /* [F][E][R] or NULL */, float *var_dev /* [F][E][R] or NULL */, float *truth_dev /* [F][E][R] or NULL */);
+/* the overlay.  corr_img_dev [F][3][H][W] is mcrt_flow_frames' corr_dev through mcrt_scan_convert_frames (the autocorrelation is gathered
+ * and not the velocity: r0 and r1 interpolate linearly across an aliasing boundary, an angle does not); grey_dev [F][H][W] the bytes of
+ * mcrt_bmode_frames.  Per pixel, with (r0, re, im) the three planes and g the grey byte:
+ *   ang = mcrt_det_atan2f(im, re);   v = ang * (float)(v_nyq_mm_s / 3.141592653589793)
+ *   show = r0 > power_thr && fabsf(v) >= vel_thr_mm_s && g <= grey_max            (a NaN anywhere: not shown)
+ *   idx = 128 + (int)rintf(ang * (float)(127.0 / 3.141592653589793)), clamped to 1 .. 255
+ *   rgb_dev[f][y][x] = show ? lut[idx] : (g, g, g);      vel_img_dev[f][y][x] = show ? v : 0.0f        (vel_img_dev may be NULL)
+ * lut [256][3] is HOST memory (mcrt_colour_map's or the caller's own), free when the call returns.  Asynchronous on the context's
+ * stream.  MCRT_ERR_INVALID for a null ctx, corr_img_dev, grey_dev, lut, o or rgb_dev, zero sizes, a threshold that is not finite, a
+ * vel_thr_mm_s < 0, grey_max > 255, a v_nyq_mm_s that is not finite and > 0, an output that overlaps an input or the other output;
+ * MCRT_ERR_LIMIT for 2^31 pixels or more; on any error nothing is launched.  Groups: call it on mcrt_group_root(). */
+typedef struct { float power_thr; float vel_thr_mm_s; uint32_t grey_max; } mcrt_colour_opts;      /* defaults 0, 0, 255; 12 bytes */
+int mcrt_default_colour_opts(mcrt_colour_opts *o);
+int mcrt_colour_frames(mcrt_ctx *ctx, const float *corr_img_dev /* [F][3][H][W] */, const uint8_t *grey_dev /* [F][H][W] */, uint32_t n_frames,
+                       uint32_t height, uint32_t width, const uint8_t *lut /* [256][3] */, const mcrt_colour_opts *o, double v_nyq_mm_s,
+                       uint8_t *rgb_dev /* [F][H][W][3] */, float *vel_img_dev /* [F][H][W] or NULL */);
 
 /* device [E][R]  ->  host [R][E] row-major (the cv::Mat layout of rfimage.h:217); synchronous */
 int mcrt_export_rf(mcrt_ctx *ctx, const float *rf_dev, uint32_t n_elements, uint32_t n_rows, float *host_rows_by_cols);

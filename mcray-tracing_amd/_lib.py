@@ -69,6 +69,17 @@ class DetectOpts(C.Structure):
     _fields_ = [("n_taps", C.c_uint32)]
 
 
+class FlowOpts(C.Structure):
+    """mcrt_flow_opts (include/mcrt.h): 32 bytes"""
+    _fields_ = [("n_packets", C.c_uint32), ("wall", C.c_uint32), ("avg_rows", C.c_uint32), ("avg_lines", C.c_uint32), ("prf_hz", C.c_float),
+                ("freq_mhz", C.c_float), ("sigma", C.c_float), ("seed", C.c_uint32)]
+
+
+class ColourOpts(C.Structure):
+    """mcrt_colour_opts (include/mcrt.h): 12 bytes"""
+    _fields_ = [("power_thr", C.c_float), ("vel_thr_mm_s", C.c_float), ("grey_max", C.c_uint32)]
+
+
 class Compound(C.Structure):
     """mcrt_compound (include/mcrt.h): 68 bytes, steer_rad at offset 4"""
     _fields_ = [("n_views", C.c_uint32), ("steer_rad", C.c_float * 16)]
@@ -152,6 +163,7 @@ assert NODE_DTYPE.itemsize == 64 and SEGMENT_DTYPE.itemsize == 64 and C.sizeof(B
 assert C.sizeof(Sweep) == 12 and C.sizeof(VolumeGrid) == 112 and C.sizeof(LabelOpts) == 8 and C.sizeof(RenderView) == 64 and C.sizeof(RenderOpts) == 32 and C.sizeof(SpeckleOpts) == 16 and C.sizeof(NoiseOpts) == 16 and C.sizeof(ReconOpts) == 20
 assert C.sizeof(ReconLabelOpts) == 12 and C.sizeof(AutogainOpts) == 24 and C.sizeof(TransmitOpts) == 12 and C.sizeof(Speckle3dOpts) == 28 and Speckle3dOpts.weight.offset == 16
 assert C.sizeof(Bands) == 80 and Bands.band_weight.offset == 36 and Bands.var_x.offset == 68 and Bands.min_mhz.offset == 76 and C.sizeof(DetectOpts) == 4
+assert C.sizeof(FlowOpts) == 32 and FlowOpts.prf_hz.offset == 16 and FlowOpts.seed.offset == 28 and C.sizeof(ColourOpts) == 12
 
 # every symbol include/mcrt.h declares (tests/test_abi.py checks the .so exports each one)
 SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create", "mcrt_destroy", "mcrt_set_stream",
@@ -176,6 +188,8 @@ SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create"
            "mcrt_default_autogain_opts", "mcrt_autogain_curve", "mcrt_autogain_frames",
            "mcrt_default_bands", "mcrt_psf_band_kernels", "mcrt_convolve_bands_frames", "mcrt_band_fold_frames",
            "mcrt_default_detect_opts", "mcrt_detect_taps", "mcrt_detect_gain", "mcrt_psf_carrier", "mcrt_detect_frames",
+           "mcrt_default_flow_opts", "mcrt_flow_nyquist", "mcrt_flow_phasors", "mcrt_flow_draws", "mcrt_colour_map", "mcrt_flow_split_frames", "mcrt_flow_frames",
+           "mcrt_default_colour_opts", "mcrt_colour_frames",
            "mcrt_default_recon_opts", "mcrt_recon_transform", "mcrt_recon_frames",
            "mcrt_default_recon_label_opts", "mcrt_recon_label_frames", "mcrt_render_label_frames"]
 
@@ -271,6 +285,15 @@ def load_library():
         "mcrt_detect_gain": [vp, u32, C.c_double, C.POINTER(C.c_double)],
         "mcrt_psf_carrier": [C.c_float, u32, C.POINTER(C.c_double)],
         "mcrt_detect_frames": [vp, vp, u32, u32, u32, C.POINTER(DetectOpts), vp, vp],
+        "mcrt_default_flow_opts": [C.POINTER(FlowOpts)],
+        "mcrt_flow_nyquist": [C.POINTER(FlowOpts), C.c_double, C.c_double, C.POINTER(C.c_double)],
+        "mcrt_flow_phasors": [C.c_double, vp, vp, u32, u32, vp, vp],
+        "mcrt_flow_draws": [u32, u32, u32, u32, u32, vp],
+        "mcrt_colour_map": [u32, vp],
+        "mcrt_flow_split_frames": [vp, vp, vp, u32, u32, u32, vp, u32, vp],
+        "mcrt_flow_frames": [vp, vp, vp, vp, u32, u32, u32, C.POINTER(FlowOpts), C.c_double, vp, vp, u32, u32, vp, vp, vp, vp, vp],
+        "mcrt_default_colour_opts": [C.POINTER(ColourOpts)],
+        "mcrt_colour_frames": [vp, vp, vp, u32, u32, u32, vp, C.POINTER(ColourOpts), C.c_double, vp, vp],
         "mcrt_default_recon_opts": [C.POINTER(ReconOpts)],
         "mcrt_recon_transform": [C.POINTER(VolumeGrid), C.c_double, vp, vp],
         "mcrt_recon_frames": [vp, vp, u32, u32, u32, vp, vp, C.c_double, C.c_double, C.POINTER(VolumeGrid), C.POINTER(ReconOpts), vp, vp, vp],

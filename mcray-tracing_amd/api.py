@@ -12,7 +12,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Bands, DetectOpts, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, Speckle3dOpts, NoiseOpts, AutogainOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Bands, DetectOpts, FlowOpts, ColourOpts, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, Speckle3dOpts, NoiseOpts, AutogainOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 DEFAULT_ANGLE = 1.0471975511965976      # the sector of main.cpp:28: 60 degrees [rad]
 
@@ -144,6 +144,72 @@ def host_psf_carrier(freq, res_um=145):
     c = C.c_double()
     check(load_library().mcrt_psf_carrier(freq, res_um, C.byref(c)))
     return c.value
+
+
+FLOW_WALLS = {"none": 0, "mean": 1, "linear": 2}      # MCRT_FLOW_WALL_*
+
+
+def flow_opts_struct(n_packets=None, wall=None, avg_rows=None, avg_lines=None, prf_hz=None, freq_mhz=None, sigma=None, seed=None):
+    """mcrt_flow_opts from keywords over mcrt_default_flow_opts: n_packets (2..16; 8), wall ("none" | "mean" | "linear" or the number; mean),
+    avg_rows (0..8; 2), avg_lines (0..4; 1), prf_hz (4000), freq_mhz (<= 0: the caller's; 0), sigma (0), seed -- the library checks the ranges"""
+    o = FlowOpts()
+    check(load_library().mcrt_default_flow_opts(C.byref(o)))
+    if wall is not None:
+        if isinstance(wall, str) and wall not in FLOW_WALLS:
+            raise ValueError("wall must be one of %s, got %r" % (sorted(FLOW_WALLS), wall))
+        o.wall = FLOW_WALLS[wall] if isinstance(wall, str) else int(wall) & 0xFFFFFFFF
+    for name, v in (("n_packets", n_packets), ("avg_rows", avg_rows), ("avg_lines", avg_lines), ("seed", seed)):
+        if v is not None:
+            setattr(o, name, int(v) & 0xFFFFFFFF)
+    for name, v in (("prf_hz", prf_hz), ("freq_mhz", freq_mhz), ("sigma", sigma)):
+        if v is not None:
+            setattr(o, name, float(v))
+    return o
+
+
+def colour_opts_struct(power_thr=None, vel_thr_mm_s=None, grey_max=None):
+    """mcrt_colour_opts from keywords over mcrt_default_colour_opts (0, 0, 255)"""
+    o = ColourOpts()
+    check(load_library().mcrt_default_colour_opts(C.byref(o)))
+    if power_thr is not None:
+        o.power_thr = float(power_thr)
+    if vel_thr_mm_s is not None:
+        o.vel_thr_mm_s = float(vel_thr_mm_s)
+    if grey_max is not None:
+        o.grey_max = int(grey_max) & 0xFFFFFFFF
+    return o
+
+
+def host_flow_nyquist(freq_mhz, speed_of_sound=1500.0, opts=None, **kw):
+    """mcrt_flow_nyquist: the velocity [mm/s] whose phase step from pulse to pulse is pi (333.33 at 1500 m/s, 4.5 MHz and 4 kHz)"""
+    o = opts if opts is not None else flow_opts_struct(**kw)
+    v = C.c_double()
+    check(load_library().mcrt_flow_nyquist(C.byref(o), float(freq_mhz), float(speed_of_sound), C.byref(v)))
+    return v.value
+
+
+def host_flow_phasors(v_nyq_mm_s, vel_mm_s, dirs):
+    """mcrt_flow_phasors: (phasor float32 [n_labels][E][2], truth float32 [n_labels][E]) of a velocity vector per material [n_labels][3] and
+    the scan-lines' directions [E][3]; truth is the velocity towards the probe"""
+    vel = np.ascontiguousarray(vel_mm_s, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    ph = np.zeros((vel.shape[0], d.shape[0], 2), np.float32); tr = np.zeros((vel.shape[0], d.shape[0]), np.float32)
+    check(load_library().mcrt_flow_phasors(float(v_nyq_mm_s), ptr(vel), ptr(d), vel.shape[0], d.shape[0], ptr(ph), ptr(tr)))
+    return ph, tr
+
+
+def host_flow_draws(seed, image_id, n_elements, n_rows, n_packets):
+    """mcrt_flow_draws: the integer draws of one image's ensemble, int32 [n_packets][n_elements][n_rows][2] (noise = d * sigma / sqrt(1431655765))"""
+    d = np.zeros((min(max(int(n_packets), 0), 16), max(int(n_elements), 0), max(int(n_rows), 0), 2), np.int32)
+    check(load_library().mcrt_flow_draws(int(seed) & 0xFFFFFFFF, int(image_id) & 0xFFFFFFFF, n_elements, n_rows, n_packets, ptr(d)))
+    return d
+
+
+def host_colour_map(kind=0):
+    """mcrt_colour_map: the colour table of the overlay, uint8 [256][3] (kind 0: red towards the probe, blue away, 128 black)"""
+    lut = np.zeros((256, 3), np.uint8)
+    check(load_library().mcrt_colour_map(int(kind) & 0xFFFFFFFF, ptr(lut)))
+    return lut
 
 
 def row_pitch_mm(frequency):
@@ -1020,6 +1086,37 @@ class Context(_SceneCalls):
         o = detect_opts_struct(n_taps)
         check(self.L.mcrt_detect_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, C.byref(o), ptr(env_dev), ptr(iq_dev)))
 
+    def flow_split_frames(self, rf_dev, tissue_dev, n_frames, n_elements, n_rows, moving, out_dev):
+        """mcrt_flow_split_frames: the raw trace [n_frames][E][R] cut by its tissue labels into out_dev [n_frames][2][E][R] -- image 0 what
+        stands still, image 1 what moves; moving: a host byte per label (non-zero: the material moves)"""
+        mv = np.ascontiguousarray(moving, np.uint8).reshape(-1)
+        check(self.L.mcrt_flow_split_frames(self.h, ptr(rf_dev), ptr(tissue_dev), n_frames, n_elements, n_rows, ptr(mv), mv.size, ptr(out_dev)))
+
+    def flow_frames(self, iq_static_dev, iq_moving_dev, tissue_dev, n_frames, n_elements, n_rows, v_nyq_mm_s, phasor, truth, first_image_id=0,
+                    sigma_dev=None, corr_dev=None, vel_dev=None, var_dev=None, truth_dev=None, opts=None, **kw):
+        """mcrt_flow_frames: the colour processor -- the slow-time ensemble of every sample from the detected pairs [n_frames][E][R][2] of what
+        stands still (or None) and what moves, the wall filter, the autocorrelation averaged over a window, and the Kasai estimates.
+        phasor [n_labels][E][2] and truth [n_labels][E]: host tables (host_flow_phasors).  sigma_dev: [n_frames] floats on the device (the
+        sigma_dev of noise_frames) or None: the options' sigma.  Outputs, each a device pointer or None: corr_dev [n_frames][3][E][R],
+        vel_dev, var_dev and truth_dev [n_frames][E][R].  opts: a FlowOpts, or the keywords of flow_opts_struct"""
+        o = opts if opts is not None else flow_opts_struct(**kw)
+        ph = np.ascontiguousarray(phasor, np.float32); tr = np.ascontiguousarray(truth, np.float32)
+        if ph.ndim != 3 or ph.shape[1:] != (n_elements, 2) or tr.shape != ph.shape[:2]:
+            raise ValueError("phasor takes [n_labels][%d][2] and truth [n_labels][%d], got %s and %s" % (n_elements, n_elements, ph.shape, tr.shape))
+        check(self.L.mcrt_flow_frames(self.h, ptr(iq_static_dev), ptr(iq_moving_dev), ptr(tissue_dev), n_frames, n_elements, n_rows, C.byref(o), float(v_nyq_mm_s),
+                                      ptr(ph), ptr(tr), ph.shape[0], first_image_id, ptr(sigma_dev), ptr(corr_dev), ptr(vel_dev), ptr(var_dev), ptr(truth_dev)))
+
+    def colour_frames(self, corr_img_dev, grey_dev, n_frames, height, width, v_nyq_mm_s, rgb_dev, vel_img_dev=None, lut=None, **opts):
+        """mcrt_colour_frames: the flow overlay -- the gathered autocorrelation [n_frames][3][H][W] over the B-mode bytes [n_frames][H][W] ->
+        rgb_dev [n_frames][H][W][3] bytes and, where given, vel_img_dev [n_frames][H][W] floats.  lut: uint8 [256][3] (None: host_colour_map());
+        opts: the keywords of colour_opts_struct"""
+        o = colour_opts_struct(**opts)
+        table = np.ascontiguousarray(host_colour_map() if lut is None else lut, np.uint8)
+        if table.shape != (256, 3):
+            raise ValueError("lut takes uint8 [256][3], got shape %s" % (table.shape,))
+        check(self.L.mcrt_colour_frames(self.h, ptr(corr_img_dev), ptr(grey_dev), n_frames, height, width, ptr(table), C.byref(o), float(v_nyq_mm_s),
+                                        ptr(rgb_dev), ptr(vel_img_dev)))
+
     def scan_convert_frames(self, rf_dev, n_frames, n_elements, n_rows, out_dev, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         check(self.L.mcrt_scan_convert_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, radius_mm, total_angle, ptr(out_dev), out_rows, out_cols))
 
@@ -1373,7 +1470,7 @@ class Simulator:
 
     def __init__(self, scene_data, transducer, n_samples=5, n_rows=None, device=0, seed=0x5EED, psf=None, texture=None,
                  max_depth=10, sanitize_tir=0, tex_n=256, bvh_builder="sah", elevation=False, compound=None, compound_mode="mean", compound_weights=None,
-                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0, speckle=None, noise=None, speckle3d=None, autogain=None, detect=None):
+                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0, speckle=None, noise=None, speckle3d=None, autogain=None, detect=None, flow=None):
         """elevation=True: slice thickness.  trace() then traces the psf's elevation_size planes of the frame as one pose pass -- plane k of
         frame f with frame id f * K + k, the frame-id rule of include/mcrt.h -- and folds them into rf_dev with psf.elevation_rows();
         everything after (convolve, bmode, frame) is unchanged.
@@ -1419,7 +1516,30 @@ class Simulator:
         mcrt_detect_frames in place where it calls mcrt_envelope_frames -- with bands over the band stack's n * B images, then fold_bands(),
         as before -- so everything downstream sees the stack it always saw.  The detector is flat within 1 % only for carriers between
         0.05 and 0.45 cycles per row at 31 taps (host_psf_carrier, host_detect_gain); a band near Nyquist comes out darker.  iq() returns the
-        analytic pair of frame()'s RF whether or not the keyword is given.  Without the keyword no call and no bit changes."""
+        analytic pair of frame()'s RF whether or not the keyword is given.  Without the keyword no call and no bit changes.
+        flow={"BLOOD": (vx, vy, vz)} -- a velocity vector [mm/s] per material name of the scene --, or a dict of velocity_mm_s= (that
+        mapping) and the keywords of flow_opts_struct (n_packets, wall, avg_rows, avg_lines, prf_hz, freq_mhz, sigma, seed), of the label pass
+        (rule, start_offset) and of the display (power_scale, vel_thr_mm_s, grey_max): colour Doppler.  colour_flow() and flow_velocity()
+        then synthesise a slow-time ensemble from ONE traced frame, split by tissue label into what stands still and what moves, and
+        estimate the axial velocity with the Kasai autocorrelator; with noise= the noise stage's sigma is the ensemble's, else the
+        dict's.  The displayed power threshold is power_scale * 2 * N * sigma^2 (default scale 4): a modelling choice that no
+        measurement backs.  Every other method is left alone: without the keyword no call and no bit changes."""
+        self.flow = _option(flow)
+        if self.flow is not None:
+            fd = self.flow if "velocity_mm_s" in self.flow else dict(velocity_mm_s=self.flow)
+            names = list(scene_data.material_names)
+            vel = np.zeros((len(names), 3), np.float32)
+            for name, v in dict(fd.pop("velocity_mm_s")).items():
+                if name not in names:
+                    raise ValueError("flow: the scene has no material %r (it has %s)" % (name, ", ".join(names)))
+                vel[names.index(name)] = np.asarray(v, np.float32).reshape(3)
+            label = dict(rule=fd.pop("rule", "traced"), start_offset=fd.pop("start_offset", None))
+            label_opts_struct(**label)                      # (an unknown rule ends it here)
+            display = dict(power_scale=float(fd.pop("power_scale", 4.0)), vel_thr_mm_s=fd.pop("vel_thr_mm_s", None), grey_max=fd.pop("grey_max", None))
+            colour_opts_struct(vel_thr_mm_s=display["vel_thr_mm_s"], grey_max=display["grey_max"])
+            opts = flow_opts_struct(**fd)                   # (unknown keywords end it here)
+            v_nyq = host_flow_nyquist(transducer.frequency, opts=opts)      # (options out of range end it here; the speed of sound is set below)
+            self.flow = dict(vel=vel, moving=(vel != 0).any(axis=1).astype(np.uint8), opts=opts, label=label, display=display, v_nyq=v_nyq)
         self.detect = _option(detect, _detect_word)
         if self.detect is not None:
             host_detect_taps(detect_opts_struct(**self.detect).n_taps)   # (unknown keywords and a bad n_taps end it here)
@@ -1455,7 +1575,11 @@ class Simulator:
         self.ctx.set_params(n_elements=E, n_samples=n_samples, frequency=transducer.frequency, seed=seed, max_depth=max_depth,
                             sanitize_tir=sanitize_tir, tex_n=tex_n, **({"n_rows": n_rows} if n_rows else {}))
         self.E, self.R, self.S = E, self.ctx.params.n_rows, n_samples
+        if self.flow is not None:
+            self.flow["v_nyq"] = host_flow_nyquist(transducer.frequency, self.ctx.params.speed_of_sound, opts=self.flow["opts"])
+            self.flow["phasor"], self.flow["truth"] = host_flow_phasors(self.flow["v_nyq"], self.flow["vel"], transducer.dir)
         self.n_materials = int(scene_data.materials.shape[0])
+        self.material_names = list(getattr(scene_data, "material_names", ()))   # (flow= resolves its names through them)
         self.ctx.upload_scene(scene_data)
         self.ctx.upload_texture(texture, tex_n)
         self.ctx.set_transducer(transducer.pos, transducer.dir)
@@ -1547,7 +1671,7 @@ class Simulator:
     def _noise(self, p):
         o = self.noise if self.noise is not None else noise_opts_struct()
         kw = dict(sigma=o.sigma) if o.mode == NOISE_ABS else dict(snr_db=o.snr_db)
-        sigma_dev = self._gain_bufs(p.frames)[0] if self.autogain is not None else None   # (auto_gain()'s floor)
+        sigma_dev = self._gain_bufs(p.frames)[0] if self.autogain is not None or self.flow is not None else None   # (auto_gain()'s floor, the colour ensemble's sigma)
         self.ctx.noise_frames(p.dev, p.frames, p.per_frame, self.E, self.R, first_image_id=p.first_id, element_gain=self.noise_gain, sigma_dev=sigma_dev,
                               seed=o.seed, **kw)
 
@@ -1889,3 +2013,61 @@ class Simulator:
             self.ctx.detect_frames(self.rf_dev, 1, self.E, self.R, iq_dev=out, **(self.detect or {}))
             pair = self.ctx.d2h(out, (self.E, self.R, 2), np.float32)
         return np.ascontiguousarray(pair.transpose(1, 0, 2)).view(np.complex64)[..., 0]
+
+    # ---- colour Doppler (flow=)
+    @contextlib.contextmanager
+    def _flow_pass(self, frame_id, want):
+        """ONE trace of the frame -> the label pass -> the raw RF split by label (its device copy: rf_dev goes on through bmode()'s own
+        stages in place, noise= included, which leaves sigma on the device) -> the two parts through the PSF and the detector's I/Q ->
+        mcrt_flow_frames.  Yields dict(tissue, corr, vel, var, truth: device buffers that live as long as the block, those in `want`;
+        sigma: the ensemble's, on the host)"""
+        if self.flow is None:
+            raise RuntimeError("colour flow needs Simulator(flow=...)")
+        for on, what in ((self.sweep is not None, "sweep="), (self.steers is not None, "compound="), (self.elevation, "elevation="), (self.psf.has_bands, "a psf with bands")):
+            if on:
+                raise RuntimeError("colour flow is one plane of one pulse: it does not combine with %s" % what)
+        fl, n = self.flow, self.E * self.R
+        sizes = dict(corr=12 * n, vel=4 * n, var=4 * n, truth=4 * n)
+        with contextlib.ExitStack() as held:
+            tissue, parts, iq = (held.enter_context(self.ctx.temp(size)) for size in (n, 8 * n, 16 * n))
+            out = {k: held.enter_context(self.ctx.temp(sizes[k])) for k in want}
+            self.trace(frame_id)
+            self.ctx.label_frames(tissue_dev=tissue, **fl["label"])
+            self.ctx.flow_split_frames(self.rf_dev, tissue, 1, self.E, self.R, fl["moving"], parts)
+            self._stages(self._stack, frame_id)
+            self._convolve(_Images(parts, 2, 2, 1, 0))
+            self.ctx.detect_frames(parts, 2, self.E, self.R, iq_dev=iq, **(self.detect or {}))
+            sigma_dev = self._gain_bufs(1)[0] if self.noise is not None else None
+            self.ctx.flow_frames(iq, iq + 8 * n, tissue, 1, self.E, self.R, fl["v_nyq"], fl["phasor"], fl["truth"], first_image_id=frame_id, sigma_dev=sigma_dev,
+                                 opts=fl["opts"], **{k + "_dev": p for k, p in out.items()})
+            sigma = float(self.ctx.d2h(sigma_dev, (1,), np.float32)[0]) if sigma_dev is not None else float(fl["opts"].sigma)
+            yield dict(out, tissue=tissue, sigma=sigma)
+
+    def flow_velocity(self, frame_id=0):
+        """the colour processor's estimates in beam space -> dict(vel, var, truth: float32 [E][R]): the Kasai velocity [mm/s, towards the
+        probe positive, aliased beyond the Nyquist velocity], the variance estimate in 0..1, and the true axial velocity of every
+        sample's material (flow= only)"""
+        with self._flow_pass(frame_id, ("vel", "var", "truth")) as b:
+            return {k: self.ctx.d2h(b[k], (self.E, self.R), np.float32) for k in ("vel", "var", "truth")}
+
+    def colour_flow(self, frame_id=0, **display):
+        """the colour-flow picture of a frame -> dict(rgb uint8 [out_rows][out_cols][3], grey uint8 [out_rows][out_cols], velocity float32
+        [out_rows][out_cols] (0 where nothing is shown), truth float32 [E][R], corr float32 [3][E][R]).  It traces ONCE; grey is bmode()'s
+        own picture of that trace (display: the keywords of Context.bmode_frames), the autocorrelation is gathered through
+        mcrt_scan_convert_frames and coloured by mcrt_colour_frames with power_thr = power_scale * 2 * N * sigma^2 (flow= only)"""
+        if display.get("persistence", 0.0) != 0.0:
+            raise ValueError("colour_flow() shows one frame: persistence is left out")
+        rows, cols = display.get("out_rows", 400), display.get("out_cols", 500)
+        geometry = {k: display[k] for k in ("radius_mm", "total_angle", "out_rows", "out_cols") if k in display}
+        n = rows * cols
+        with self._flow_pass(frame_id, ("corr", "truth")) as b, self.ctx.temp(n) as grey, self.ctx.temp(12 * n) as img, self.ctx.temp(3 * n) as rgb, \
+                self.ctx.temp(4 * n) as vel:
+            self.ctx.bmode_frames(self.rf_dev, 1, self.E, self.R, grey, **display)
+            self.ctx.scan_convert_frames(b["corr"], 3, self.E, self.R, img, **geometry)
+            fl = self.flow
+            power_thr = fl["display"]["power_scale"] * 2.0 * fl["opts"].n_packets * b["sigma"] * b["sigma"]
+            self.ctx.colour_frames(img, grey, 1, rows, cols, fl["v_nyq"], rgb, vel_img_dev=vel, power_thr=power_thr, vel_thr_mm_s=fl["display"]["vel_thr_mm_s"],
+                                   grey_max=fl["display"]["grey_max"])
+            return dict(rgb=self.ctx.d2h(rgb, (rows, cols, 3), np.uint8), grey=self.ctx.d2h(grey, (rows, cols), np.uint8),
+                        velocity=self.ctx.d2h(vel, (rows, cols), np.float32), truth=self.ctx.d2h(b["truth"], (self.E, self.R), np.float32),
+                        corr=self.ctx.d2h(b["corr"], (3, self.E, self.R), np.float32))

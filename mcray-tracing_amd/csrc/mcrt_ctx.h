@@ -194,6 +194,9 @@ struct ImageStages {
     StagedTable band_ax, band_w;
     // receiver noise (mcrt_noise_frames): the gain of every transducer element [E] of the last table (room for the largest E so far); the peaks are d_disp's
     StagedTable gain;
+    // colour Doppler (mcrt_flow_frames): the phasors [n_labels][E][2] and the true velocities [n_labels][E] of the last tables, the
+    // per-sample autocorrelation [F][3][E][R] of the largest call so far; (mcrt_colour_frames): the last colour table, 256 packed entries
+    StagedTable flow_phasor, flow_truth, colour_lut; Buf<float> d_flow;
     // automatic gain (mcrt_autogain_frames): the histograms of a chunk of frames [frames][n_bands][2048], at most AUTOGAIN_HIST_WORDS, and the row
     // gains [n_frames][R] of the largest call so far that gave no gain_dev
     Buf<uint32_t> d_aghist; Buf<float> d_aggain;

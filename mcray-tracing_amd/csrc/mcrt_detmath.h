@@ -161,6 +161,29 @@ MCRT_DEV float det_powf(float x, float y)          // std::pow(float,float) ray.
     return (float)r;
 }
 
+// atan2 in float for the colour-flow stages (the contract is in include/mcrt.h, mcrt_flow_frames): the octant's quotient through an odd
+// polynomial of degree 11, every multiply, add and the division rounded once (no fma: the file is compiled -ffp-contract=off), so that a
+// float32 numpy reading gives the same bits.  Within 1e-5 rad of atan2; a NaN in gives a NaN out, (0, 0) of either sign gives +0.0f.
+MCRT_DEV float det_atan2f(float y, float x)
+{
+    const float ax = fabsf(x), ay = fabsf(y);
+    const bool steep = ay > ax;
+    const float hi = steep ? ay : ax, lo = steep ? ax : ay;
+    if (hi == 0.0f) return 0.0f;
+    const float t = lo / hi, s = t * t;
+    float p = -0.01172120f;
+    p = p * s + 0.05265332f;
+    p = p * s + -0.11643287f;
+    p = p * s + 0.19354346f;
+    p = p * s + -0.33262347f;
+    p = p * s + 0.99997726f;
+    float a = t * p;
+    if (steep) a = 1.5707964f - a;
+    if (x < 0.0f) a = 3.1415927f - a;
+    if (y < 0.0f) a = -a;
+    return a;
+}
+
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11)
 MCRT_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4])
 {

@@ -975,6 +975,107 @@ extern "C" int mcrt_noise_draws(uint32_t seed, uint32_t image_id, uint32_t n_ele
     return MCRT_OK;
 }
 
+// ---- colour Doppler (the contracts are in include/mcrt.h) ---------------------------------------
+extern "C" int mcrt_default_flow_opts(mcrt_flow_opts *o)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_flow_opts: null options");
+    o->n_packets = 8u; o->wall = MCRT_FLOW_WALL_MEAN; o->avg_rows = 2u; o->avg_lines = 1u;
+    o->prf_hz = 4000.0f; o->freq_mhz = 0.0f; o->sigma = 0.0f; o->seed = 0x464C4F57u;
+    return MCRT_OK;
+}
+
+int mcrt::flow_check(const char *fn, const mcrt_flow_opts *o)
+{
+    if (o->n_packets < 2u || o->n_packets > 16u) return set_error(MCRT_ERR_INVALID, "%s: n_packets must be 2 .. 16 (%u)", fn, o->n_packets);
+    if (o->wall > MCRT_FLOW_WALL_LINEAR) return set_error(MCRT_ERR_INVALID, "%s: unknown wall filter %u", fn, o->wall);
+    if (o->avg_rows > 8u) return set_error(MCRT_ERR_INVALID, "%s: avg_rows must be 0 .. 8 (%u)", fn, o->avg_rows);
+    if (o->avg_lines > 4u) return set_error(MCRT_ERR_INVALID, "%s: avg_lines must be 0 .. 4 (%u)", fn, o->avg_lines);
+    if (!(std::isfinite(o->prf_hz) && o->prf_hz > 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: prf_hz must be finite and > 0 (%g)", fn, (double)o->prf_hz);
+    if (!std::isfinite(o->freq_mhz)) return set_error(MCRT_ERR_INVALID, "%s: freq_mhz must be finite (%g)", fn, (double)o->freq_mhz);
+    if (!(std::isfinite(o->sigma) && o->sigma >= 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: sigma must be finite and >= 0 (%g)", fn, (double)o->sigma);
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_flow_nyquist(const mcrt_flow_opts *o, double freq_mhz, double speed_of_sound, double *v_nyq_mm_s)
+{
+    static const char fn[] = "mcrt_flow_nyquist";
+    if (!o || !v_nyq_mm_s) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null %s", fn, o ? "v_nyq_mm_s" : "options");
+    if (const int rc = mcrt::flow_check(fn, o)) return rc;
+    const double f = o->freq_mhz > 0.0f ? (double)o->freq_mhz : freq_mhz;
+    if (!(std::isfinite(f) && f > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: the frequency must be finite and > 0 (%g)", fn, f);
+    if (!(std::isfinite(speed_of_sound) && speed_of_sound > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: speed_of_sound must be finite and > 0 (%g)", fn, speed_of_sound);
+    *v_nyq_mm_s = (speed_of_sound * 1000.0 * (double)o->prf_hz) / (4.0 * (f * 1.0e6));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_flow_phasors(double v_nyq_mm_s, const float *vel_mm_s, const float *dir, uint32_t n_labels, uint32_t n_elements, float *phasor, float *truth)
+{
+    static const char fn[] = "mcrt_flow_phasors";
+    if (!vel_mm_s || !dir || !phasor || !truth) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (n_labels == 0 || n_elements == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_labels %u, n_elements %u)", fn, n_labels, n_elements);
+    if (n_labels > 254u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: at most 254 labels (%u)", fn, n_labels);
+    if (!(std::isfinite(v_nyq_mm_s) && v_nyq_mm_s > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: v_nyq_mm_s must be finite and > 0 (%g)", fn, v_nyq_mm_s);
+    for (size_t i = 0; i < (size_t)n_labels * 3u; i++)
+        if (!std::isfinite(vel_mm_s[i])) return mcrt::set_error(MCRT_ERR_INVALID, "%s: vel_mm_s[%zu][%zu] is not finite", fn, i / 3u, i % 3u);
+    for (size_t i = 0; i < (size_t)n_elements * 3u; i++)
+        if (!std::isfinite(dir[i])) return mcrt::set_error(MCRT_ERR_INVALID, "%s: dir[%zu][%zu] is not finite", fn, i / 3u, i % 3u);
+    const double pi = 3.141592653589793;
+    for (uint32_t l = 0; l < n_labels; l++) {
+        const double vx = vel_mm_s[3u * l], vy = vel_mm_s[3u * l + 1u], vz = vel_mm_s[3u * l + 2u];
+        const bool rest = vx == 0.0 && vy == 0.0 && vz == 0.0;
+        for (uint32_t e = 0; e < n_elements; e++) {
+            const size_t i = (size_t)l * n_elements + e;
+            if (rest) { truth[i] = 0.0f; phasor[2u * i] = 1.0f; phasor[2u * i + 1u] = 0.0f; continue; }
+            const double dx = dir[3u * e], dy = dir[3u * e + 1u], dz = dir[3u * e + 2u];
+            const double v_t = 0.0 - ((vx * dx + vy * dy) + vz * dz);
+            const double phi = pi * v_t / v_nyq_mm_s;
+            truth[i] = (float)v_t; phasor[2u * i] = (float)std::cos(phi); phasor[2u * i + 1u] = (float)std::sin(phi);
+        }
+    }
+    return MCRT_OK;
+}
+
+// the draws k_flow makes for one image's ensemble, [N][E][R][2]
+extern "C" int mcrt_flow_draws(uint32_t seed, uint32_t image_id, uint32_t n_elements, uint32_t n_rows, uint32_t n_packets, int32_t *d)
+{
+    static const char fn[] = "mcrt_flow_draws";
+    if (!d) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null d", fn);
+    if (n_elements == 0 || n_rows == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_elements %u, n_rows %u)", fn, n_elements, n_rows);
+    if (n_packets < 2u || n_packets > 16u) return mcrt::set_error(MCRT_ERR_INVALID, "%s: n_packets must be 2 .. 16 (%u)", fn, n_packets);
+    if (n_rows > 2048u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: n_rows: at most 2048 rows (%u)", fn, n_rows);
+    for (uint32_t n = 0; n < n_packets; n++)
+        for (uint32_t e = 0; e < n_elements; e++)
+            for (uint32_t r = 0; r < n_rows; r++) {
+                uint32_t o[4];
+                host_philox4x32_10(e, r, 0x464C4F57u, n, seed, image_id, o);
+                int32_t *p = d + 2u * (((size_t)n * n_elements + e) * n_rows + r);
+                p[0] = (int32_t)((o[0] & 0xffffu) + (o[0] >> 16) + (o[1] & 0xffffu) + (o[1] >> 16)) - 131070;
+                p[1] = (int32_t)((o[2] & 0xffffu) + (o[2] >> 16) + (o[3] & 0xffffu) + (o[3] >> 16)) - 131070;
+            }
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_colour_map(uint32_t kind, uint8_t *lut)
+{
+    static const char fn[] = "mcrt_colour_map";
+    if (!lut) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null lut", fn);
+    if (kind != 0u) return mcrt::set_error(MCRT_ERR_INVALID, "%s: unknown kind %u", fn, kind);
+    for (uint32_t i = 1; i < 256u; i++) {
+        const uint32_t k = i >= 128u ? i - 128u : 128u - i;
+        const uint32_t strong = k == 0u ? 0u : 128u + k, g = k <= 64u ? 0u : (k - 64u) * 4u;
+        lut[3u * i] = (uint8_t)(i > 128u ? strong : 0u); lut[3u * i + 1u] = (uint8_t)g; lut[3u * i + 2u] = (uint8_t)(i < 128u ? strong : 0u);
+    }
+    lut[0] = lut[3]; lut[1] = lut[4]; lut[2] = lut[5];
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_default_colour_opts(mcrt_colour_opts *o)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_colour_opts: null options");
+    o->power_thr = 0.0f; o->vel_thr_mm_s = 0.0f; o->grey_max = 255u;
+    return MCRT_OK;
+}
+
 // ---- automatic gain (the contract is in include/mcrt.h) ---------------------------------------
 extern "C" int mcrt_default_autogain_opts(mcrt_autogain_opts *o)
 {

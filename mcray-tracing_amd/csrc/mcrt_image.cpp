@@ -174,6 +174,72 @@ extern "C" int mcrt_detect_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_f
     return MCRT_OK;
 }
 
+// ---- colour Doppler (the contracts are in include/mcrt.h; the defaults, the option ranges, the phasors, the draws and the colour table are
+// host code: mcrt_host.cpp) ----
+extern "C" int mcrt_flow_split_frames(mcrt_ctx *c, const float *rf_dev, const uint8_t *tissue_dev, uint32_t n_frames, uint32_t E, uint32_t R, const uint8_t *moving,
+                                      uint32_t n_labels, float *out_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_flow_split_frames";
+    if (!rf_dev || !tissue_dev || !moving || !out_dev) return set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (n_frames == 0 || E == 0 || R == 0 || n_labels == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, n_elements %u, n_rows %u, n_labels %u)", fn, n_frames, E, R, n_labels);
+    if (n_labels > 254u) return set_error(MCRT_ERR_LIMIT, "%s: at most 254 labels (%u)", fn, n_labels);
+    if ((double)n_frames * (double)E * (double)R >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: a stack of 2^31 samples or more (%u x %u x %u)", fn, n_frames, E, R);
+    const size_t n = (size_t)n_frames * E * R;
+    const Range out{ out_dev, 8 * n, "out_dev" };
+    const Range ins[2] = { { rf_dev, 4 * n, "rf_dev" }, { tissue_dev, n, "tissue_dev" } };
+    MCRT_TRY(check_overlap(fn, out, ins, 2, false));
+    mcrt::FlowSplitArgs a; memset(&a, 0, sizeof a);
+    a.rf = rf_dev; a.tissue = tissue_dev; a.out = out_dev; a.plane = E * R; a.n = (uint32_t)n;
+    for (uint32_t l = 0; l < n_labels; l++)
+        if (moving[l]) a.moving[l >> 5] |= 1u << (l & 31u);
+    HIP_TRY(mcrt::launch_flow_split(a, c->stream));
+    return MCRT_OK;
+}
+
+// Everything is checked before anything is enqueued; then the two tables (only when they differ from the ones on the device), the
+// per-sample autocorrelation into the context's buffer (k_flow<N, WALL>) and the window average with the estimates (k_flow_avg).
+extern "C" int mcrt_flow_frames(mcrt_ctx *c, const float *iq_static_dev, const float *iq_moving_dev, const uint8_t *tissue_dev, uint32_t n_frames, uint32_t E, uint32_t R,
+                                const mcrt_flow_opts *o, double v_nyq_mm_s, const float *phasor, const float *truth, uint32_t n_labels, uint32_t first_image_id,
+                                const float *sigma_dev, float *corr_dev, float *vel_dev, float *var_dev, float *truth_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_flow_frames";
+    if (!iq_moving_dev || !tissue_dev || !phasor || !truth || !o) return set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (n_frames == 0 || E == 0 || R == 0 || n_labels == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, n_elements %u, n_rows %u, n_labels %u)", fn, n_frames, E, R, n_labels);
+    MCRT_TRY(mcrt::flow_check(fn, o));
+    if (!(std::isfinite(v_nyq_mm_s) && v_nyq_mm_s > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: v_nyq_mm_s must be finite and > 0 (%g)", fn, v_nyq_mm_s);
+    if (!corr_dev && !vel_dev && !var_dev && !truth_dev) return set_error(MCRT_ERR_INVALID, "%s: no output is given", fn);
+    if (n_labels > 254u) return set_error(MCRT_ERR_LIMIT, "%s: at most 254 labels (%u)", fn, n_labels);
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: n_rows: at most %d rows (%u)", fn, MCRT_MAX_ROWS, R);
+    if ((double)n_frames * (double)E * (double)R >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: a stack of 2^31 samples or more (%u x %u x %u)", fn, n_frames, E, R);
+    if ((uint64_t)first_image_id + n_frames > 0x100000000ull) return set_error(MCRT_ERR_LIMIT, "%s: first_image_id: the ids of %u images from %u on pass 2^32", fn, n_frames, first_image_id);
+    const size_t n_tab = (size_t)n_labels * E;
+    for (size_t i = 0; i < n_tab; i++)
+        if (!std::isfinite(phasor[2 * i]) || !std::isfinite(phasor[2 * i + 1]) || !std::isfinite(truth[i]))
+            return set_error(MCRT_ERR_INVALID, "%s: the phasor or the truth of label %zu, scan-line %zu is not finite", fn, i / E, i % E);
+    const size_t n = (size_t)n_frames * E * R;
+    const Range outs[4] = { { corr_dev, 12 * n, "corr_dev" }, { vel_dev, 4 * n, "vel_dev" }, { var_dev, 4 * n, "var_dev" }, { truth_dev, 4 * n, "truth_dev" } };
+    const Range ins[4] = { { iq_static_dev, 8 * n, "iq_static_dev" }, { iq_moving_dev, 8 * n, "iq_moving_dev" }, { tissue_dev, n, "tissue_dev" }, { sigma_dev, 4 * (size_t)n_frames, "sigma_dev" } };
+    for (int i = 0; i < 4; i++)
+        if (ins[i].p) MCRT_TRY(check_overlap(fn, ins[i], outs, 4, i == 1));      // (iq_moving_dev is always there: the outputs among themselves once)
+    if (3 * n > c->img.d_flow.cap) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(c->img.d_flow.alloc(3 * n));
+    }
+    MCRT_TRY(c->img.flow_phasor.put(phasor, (uint32_t)(2 * n_tab), 1, 2 * n_tab, c->stream));
+    MCRT_TRY(c->img.flow_truth.put(truth, (uint32_t)n_tab, 1, n_tab, c->stream));
+    mcrt::FlowArgs a; memset(&a, 0, sizeof a);
+    a.iq_static = (const float2 *)iq_static_dev; a.iq_moving = (const float2 *)iq_moving_dev; a.tissue = tissue_dev;
+    a.phasor = (const float2 *)c->img.flow_phasor.dev.p; a.truth = c->img.flow_truth.dev.p; a.sigma_dev = sigma_dev; a.raw = c->img.d_flow;
+    a.corr = corr_dev; a.vel = vel_dev; a.var = var_dev; a.truth_out = truth_dev;
+    a.F = n_frames; a.E = E; a.R = R; a.n_labels = n_labels; a.lines = n_frames * E; a.chunks = (R + FLOW_WAVE_ROWS - 1u) / FLOW_WAVE_ROWS;
+    a.n_packets = o->n_packets; a.wall = o->wall; a.avg_rows = o->avg_rows; a.avg_lines = o->avg_lines; a.seed = o->seed; a.first_id = first_image_id;
+    a.sigma = o->sigma; a.inv_std = (float)(1.0 / std::sqrt(1431655765.0)); a.vscale = (float)(v_nyq_mm_s / 3.141592653589793);
+    HIP_TRY(mcrt::launch_flow(a, c->stream));
+    return MCRT_OK;
+}
+
 // the scan-conversion maps of a geometry on the device, in cache m: the plain maps (cp null: mcrt_scan_maps, one view) or the N views of a steer
 // list (mcrt_compound_maps), [N][2][n_pad]
 static int ensure_maps(mcrt_ctx *c, MapCache &m, uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t orows, uint32_t ocols, const mcrt_compound *cp, const float **maps)
@@ -302,6 +368,36 @@ extern "C" int mcrt_bmode_frames(mcrt_ctx *c, const float *rf_dev, uint32_t n_fr
     a.grey = c->img.d_tmp; a.map_col = maps; a.map_row = maps + MapCache::pad((size_t)p->out_rows * p->out_cols); a.state = state_dev; a.out = out_dev; a.alpha = p->persistence;
     a.E = E; a.R = R; a.reset = p->reset_state ? 1u : 0u; a.pass = pixel_pass(n_frames, p->out_rows * p->out_cols, a.alpha, out_dev, 1u);
     HIP_TRY(mcrt::launch_bmode(a, c->stream));
+    return MCRT_OK;
+}
+
+// ---- the colour overlay of colour Doppler (the contract is in include/mcrt.h, beside mcrt_flow_frames) ----
+// Everything is checked before anything is enqueued; the colour table goes to the device as 256 floats, each the exact integer
+// r | g << 8 | b << 16 (only when it differs from the one there).
+extern "C" int mcrt_colour_frames(mcrt_ctx *c, const float *corr_img_dev, const uint8_t *grey_dev, uint32_t n_frames, uint32_t H, uint32_t W, const uint8_t *lut,
+                                  const mcrt_colour_opts *o, double v_nyq_mm_s, uint8_t *rgb_dev, float *vel_img_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_colour_frames";
+    if (!corr_img_dev || !grey_dev || !lut || !o || !rgb_dev) return set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (n_frames == 0 || H == 0 || W == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, height %u, width %u)", fn, n_frames, H, W);
+    if (!std::isfinite(o->power_thr)) return set_error(MCRT_ERR_INVALID, "%s: power_thr must be finite (%g)", fn, (double)o->power_thr);
+    if (!(std::isfinite(o->vel_thr_mm_s) && o->vel_thr_mm_s >= 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: vel_thr_mm_s must be finite and >= 0 (%g)", fn, (double)o->vel_thr_mm_s);
+    if (o->grey_max > 255u) return set_error(MCRT_ERR_INVALID, "%s: grey_max must be 0 .. 255 (%u)", fn, o->grey_max);
+    if (!(std::isfinite(v_nyq_mm_s) && v_nyq_mm_s > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: v_nyq_mm_s must be finite and > 0 (%g)", fn, v_nyq_mm_s);
+    if ((double)n_frames * (double)H * (double)W >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: 2^31 pixels or more (%u x %u x %u)", fn, n_frames, H, W);
+    const size_t n = (size_t)n_frames * H * W;
+    const Range outs[2] = { { rgb_dev, 3 * n, "rgb_dev" }, { vel_img_dev, 4 * n, "vel_img_dev" } };
+    MCRT_TRY(check_overlap(fn, Range{ corr_img_dev, 12 * n, "corr_img_dev" }, outs, 2, true));
+    MCRT_TRY(check_overlap(fn, Range{ grey_dev, n, "grey_dev" }, outs, 2, false));
+    float packed[256];
+    for (uint32_t i = 0; i < 256u; i++) packed[i] = (float)((uint32_t)lut[3 * i] | (uint32_t)lut[3 * i + 1] << 8 | (uint32_t)lut[3 * i + 2] << 16);
+    MCRT_TRY(c->img.colour_lut.put(packed, 256, 1, 256, c->stream));
+    mcrt::ColourArgs a; memset(&a, 0, sizeof a);
+    a.corr = corr_img_dev; a.grey = grey_dev; a.lut = c->img.colour_lut.dev.p; a.rgb = rgb_dev; a.vel = vel_img_dev;
+    a.power_thr = o->power_thr; a.vel_thr = o->vel_thr_mm_s; a.vscale = (float)(v_nyq_mm_s / 3.141592653589793); a.iscale = (float)(127.0 / 3.141592653589793);
+    a.grey_max = o->grey_max; a.pass = pixel_pass(n_frames, H * W, 0.0f, vel_img_dev, 4u);
+    HIP_TRY(mcrt::launch_colour(a, c->stream));
     return MCRT_OK;
 }
 

@@ -76,5 +76,7 @@ int update_triangles_with_tree(mcrt_ctx *c, const float *tri, uint32_t n_tri, co
 int volume_check(const char *fn, const mcrt_sweep *sw, const mcrt_volume_grid *g);
 // mcrt_host.cpp: the ranges of mcrt_autogain_opts, which mcrt_autogain_curve and mcrt_autogain_frames share
 int autogain_check(const char *fn, const mcrt_autogain_opts *o);
+// mcrt_host.cpp: the ranges of mcrt_flow_opts, which mcrt_flow_nyquist and mcrt_flow_frames share
+int flow_check(const char *fn, const mcrt_flow_opts *o);
 }
 #endif

@@ -17,6 +17,7 @@
 //   mcrt_speckle3d.hip k_srad3 (3-D speckle reduction over voxel blocks: mcrt_speckle_volume_frames)
 //   mcrt_noise.hip   k_noise (receiver noise: mcrt_noise_frames; its peaks are k_bmode_peak's)
 //   mcrt_detect.hip  k_detect<NT> (quadrature detection: mcrt_detect_frames; NT taps, 1..16)
+//   mcrt_flow.hip    k_flow_split, k_flow<N, WALL>, k_flow_avg (colour Doppler: mcrt_flow_split_frames, mcrt_flow_frames), k_colour (mcrt_colour_frames)
 //   mcrt_autogain.hip k_autogain_hist, k_autogain_curve, k_autogain_apply (automatic gain: mcrt_autogain_frames)
 //   mcrt_recon.hip   k_recon_splat, k_recon_resolve (freehand 3-D reconstruction: mcrt_recon_frames)
 //   mcrt_label.hip   k_label (ground-truth label maps: mcrt_label_frames), k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames)
@@ -28,7 +29,7 @@
 // Shared device code: mcrt_device.h (primitives and the knobs more than one unit reads), mcrt_walk.h (the lane walk's steps, also k_path's),
 // mcrt_shade.h (shade_path, also k_path's), mcrt_voxels.h (the voxel block of the 3-D stages: a sample's voxel, a wavefront's runs,
 // the resolve tile, the picture tile -- included by mcrt_recon / label3d / render.hip and, for recon_tiling, mcrt_image.cpp), mcrt_pixels.h (the pixel tile of k_bmode, k_compound, k_volume and k_label_gather and the byte
-// k_render writes: layout, frame chunks, persistence, quantisation, the word store -- included by mcrt_display / volume / label / render.hip
+// k_render writes: layout, frame chunks, persistence, quantisation, the word store -- included by mcrt_display / volume / label / render / flow.hip
 // only).  Everything is scalar fp32/fp64 VALU + integer work -- no dense contraction, hence no MFMA -- and the arithmetic follows the
 // parity contract expression by expression (compiled -ffp-contract=off).
 #pragma once
@@ -377,6 +378,46 @@ struct DetectArgs {
     float t[16];                        // t[k]: the tap at offset 2 * k + 1
 };
 hipError_t launch_detect(const DetectArgs &a, hipStream_t st);
+// k_flow_split (mcrt_flow_split_frames): the raw trace [F][E][R] -> out [F][2][E][R], what stands still and what moves
+struct FlowSplitArgs {
+    const float *rf;                    // [F][E][R]
+    const uint8_t *tissue;              // [F][E][R]
+    float *out;                         // [F][2][E][R]
+    uint32_t plane, n;                  // E * R, F * E * R
+    uint32_t moving[8];                 // bit l: label l moves (labels >= n_labels: 0)
+};
+hipError_t launch_flow_split(const FlowSplitArgs &a, hipStream_t st);
+// k_flow<N, WALL> and k_flow_avg (mcrt_flow_frames): the ensemble, the wall filter and the autocorrelation of every sample into raw, then the
+// window average and the outputs
+#define FLOW_WAVE_ROWS 64u                          // a wavefront of k_flow owns 64 consecutive rows of one scan-line, a lane one of them
+struct FlowArgs {
+    const float2 *iq_static;            // [F][E][R] (I, Q) or null
+    const float2 *iq_moving;            // [F][E][R]
+    const uint8_t *tissue;              // [F][E][R]
+    const float2 *phasor;               // [n_labels][E] the context's copy
+    const float *truth;                 // [n_labels][E] the context's copy
+    const float *sigma_dev;             // [F] or null: sigma
+    float *raw;                         // [F][3][E][R] the per-sample r0, Re r1, Im r1 (the context's buffer)
+    float *corr, *vel, *var, *truth_out;   // the outputs, each or null
+    uint32_t F, E, R, n_labels;
+    uint32_t lines, chunks;             // F * E, ceil(R / FLOW_WAVE_ROWS)
+    uint32_t n_packets, wall, avg_rows, avg_lines;
+    uint32_t seed, first_id;
+    float sigma, inv_std, vscale;       // vscale: (float)(v_nyq / pi)
+};
+hipError_t launch_flow(const FlowArgs &a, hipStream_t st);       // both kernels, in stream order
+// k_colour (mcrt_colour_frames): corr_img [F][3][n] and the grey bytes [F][n] -> rgb [F][n][3] and vel_img [F][n]
+struct ColourArgs {
+    const float *corr;                  // [F][3][n]
+    const uint8_t *grey;                // [F][n]
+    const float *lut;                   // [256]: (float)(r | g << 8 | b << 16), exact (the context's copy)
+    uint8_t *rgb;                       // [F][n][3]
+    float *vel;                         // [F][n] or null
+    float power_thr, vel_thr, vscale, iscale;      // vscale: (float)(v_nyq / pi), iscale: (float)(127.0 / pi)
+    uint32_t grey_max;
+    PixelPass pass;
+};
+hipError_t launch_colour(const ColourArgs &a, hipStream_t st);
 hipError_t launch_remap(const float *img, uint32_t n_img, uint32_t E, uint32_t R, const float *map_col, const float *map_row, float *out, uint32_t n, hipStream_t st);
 hipError_t launch_bmode_peak(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, float *peak, hipStream_t st);   // peak[F] zeroed before
 hipError_t launch_bmode_grey(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, const float *peak /*[F] or null: ref*/, float ref,

@@ -117,6 +117,14 @@
 // --iq FILE.raw writes the last frame's analytic pair before detection, float32 [512][465][2] scan-line-major: the RF's own bits and its Hilbert
 // transform (the I/Q data at the RF rate), with --detect-taps' taps whether or not --detect is given.  It does not combine with --compound,
 // --sweep or the band options.  --detect-taps needs --detect or --iq.  Without these options nothing changes.
+// --colour-flow FILE.ppm writes the last frame's colour-flow picture, a binary PPM of the B-mode size: the frame's ONE trace is split by tissue
+// label into what stands still and what moves, a slow-time ensemble of --flow-packets N pulses (2..16; 8) at --flow-prf-hz X (4000) is
+// synthesised from the two parts, filtered (--flow-wall none|mean|linear; mean), and the Kasai autocorrelator's velocity is laid over the 8-bit
+// B-mode frame (the display options apply; the picture is log-compressed whether or not one is given), red towards the probe.
+// --flow-velocity NAME:vx,vy,vz [mm/s] gives a material its velocity vector and may be repeated; at least one is needed.  --flow-avg A,B is the
+// averaging half-window in rows and scan-lines (2,1); --flow-vel-thr X [mm/s] and --flow-grey-max G are the display thresholds (0, 255); with
+// --noise the ensemble carries the receiver's sigma and power below 4 * 2 N sigma^2 is not shown.  --flow-truth FILE.raw writes the true axial
+// velocity of every scan-line sample, float32 [512][465].  It does not combine with --compound, --sweep, --elevation or the band options.
 #include "mcrt_host.hpp"
 #include <algorithm>
 #include <chrono>
@@ -176,6 +184,11 @@ int main(int argc, char **argv)
     mcrt_autogain_opts aopts; mcrt_default_autogain_opts(&aopts);
     const char *freq_compound = nullptr, *freq_span = nullptr, *freq_var_x = nullptr, *downshift = nullptr, *downshift_min = nullptr;   // the options as given
     const char *detect = nullptr, *detect_taps = nullptr, *iq_file = nullptr;   // the options as given
+    const char *colour_flow = nullptr, *flow_packets = nullptr, *flow_prf = nullptr, *flow_wall = nullptr, *flow_avg = nullptr, *flow_vel_thr = nullptr,
+               *flow_grey_max = nullptr, *flow_truth = nullptr;   // the options as given
+    std::vector<std::string> flow_velocity;
+    mcrt_flow_opts flopts; mcrt_default_flow_opts(&flopts);
+    mcrt_colour_opts flcol; mcrt_default_colour_opts(&flcol);
     mcrt_detect_opts dopts; mcrt_default_detect_opts(&dopts);
     const char *freehand_n = nullptr, *freehand_step = nullptr, *freehand_fan = nullptr, *freehand_box = nullptr, *freehand_voxel = nullptr, *freehand_out = nullptr,
                *freehand_mode = nullptr, *freehand_fill = nullptr;   // the options as given
@@ -240,6 +253,15 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--detect") && i + 1 < argc) detect = argv[++i];
             else if (!std::strcmp(argv[i], "--detect-taps") && i + 1 < argc) detect_taps = argv[++i];
             else if (!std::strcmp(argv[i], "--iq") && i + 1 < argc) iq_file = argv[++i];
+            else if (!std::strcmp(argv[i], "--colour-flow") && i + 1 < argc) colour_flow = argv[++i];
+            else if (!std::strcmp(argv[i], "--flow-velocity") && i + 1 < argc) flow_velocity.push_back(argv[++i]);
+            else if (!std::strcmp(argv[i], "--flow-packets") && i + 1 < argc) flow_packets = argv[++i];
+            else if (!std::strcmp(argv[i], "--flow-prf-hz") && i + 1 < argc) flow_prf = argv[++i];
+            else if (!std::strcmp(argv[i], "--flow-wall") && i + 1 < argc) flow_wall = argv[++i];
+            else if (!std::strcmp(argv[i], "--flow-avg") && i + 1 < argc) flow_avg = argv[++i];
+            else if (!std::strcmp(argv[i], "--flow-vel-thr") && i + 1 < argc) flow_vel_thr = argv[++i];
+            else if (!std::strcmp(argv[i], "--flow-grey-max") && i + 1 < argc) flow_grey_max = argv[++i];
+            else if (!std::strcmp(argv[i], "--flow-truth") && i + 1 < argc) flow_truth = argv[++i];
             else if (!std::strcmp(argv[i], "--freehand") && i + 1 < argc) freehand_n = argv[++i];
             else if (!std::strcmp(argv[i], "--freehand-step-mm") && i + 1 < argc) freehand_step = argv[++i];
             else if (!std::strcmp(argv[i], "--freehand-fan-deg") && i + 1 < argc) freehand_fan = argv[++i];
@@ -437,6 +459,31 @@ int main(int argc, char **argv)
             if (dopts.n_taps > 63u || mcrt_detect_taps(&dopts, taps) != MCRT_OK) throw std::invalid_argument("--detect-taps takes 3, 7, 11, ..., 63 taps");
         }
         if (iq_file && (compound_given || sweep_given || with_bands)) throw std::invalid_argument("--iq does not combine with --compound, --sweep or the band options");
+        if (!colour_flow && (!flow_velocity.empty() || flow_packets || flow_prf || flow_wall || flow_avg || flow_vel_thr || flow_grey_max || flow_truth))
+            throw std::invalid_argument("--flow-velocity, --flow-packets, --flow-prf-hz, --flow-wall, --flow-avg, --flow-vel-thr, --flow-grey-max and --flow-truth need --colour-flow");
+        if (colour_flow) {
+            if (compound_given || sweep_given || elevation_given || with_bands) throw std::invalid_argument("--colour-flow does not combine with --compound, --sweep, --elevation or the band options");
+            if (flow_velocity.empty()) throw std::invalid_argument("--colour-flow needs --flow-velocity NAME:vx,vy,vz");
+            if (flow_packets) flopts.n_packets = (uint32_t)std::max(std::atol(flow_packets), 0l);
+            if (flow_prf) flopts.prf_hz = (float)std::atof(flow_prf);
+            if (flow_wall) {
+                if (!std::strcmp(flow_wall, "none")) flopts.wall = MCRT_FLOW_WALL_NONE;
+                else if (!std::strcmp(flow_wall, "mean")) flopts.wall = MCRT_FLOW_WALL_MEAN;
+                else if (!std::strcmp(flow_wall, "linear")) flopts.wall = MCRT_FLOW_WALL_LINEAR;
+                else throw std::invalid_argument("--flow-wall takes none, mean or linear");
+            }
+            if (flow_avg) {
+                const auto ab = comma_list<int>(flow_avg);
+                if (ab.size() != 2 || ab[0] < 0 || ab[1] < 0) throw std::invalid_argument("--flow-avg takes A,B: the half-window in rows and scan-lines");
+                flopts.avg_rows = (uint32_t)ab[0]; flopts.avg_lines = (uint32_t)ab[1];
+            }
+            if (flow_vel_thr) flcol.vel_thr_mm_s = (float)std::atof(flow_vel_thr);
+            if (flow_grey_max) flcol.grey_max = (uint32_t)std::max(std::atol(flow_grey_max), 0l);
+            double v_nyq = 0.0;
+            if (mcrt_flow_nyquist(&flopts, transducer_frequency, 1500.0, &v_nyq) != MCRT_OK) throw std::invalid_argument(std::string("--colour-flow: ") + mcrt_last_error());
+            if (!(flcol.vel_thr_mm_s >= 0.0f) || flcol.grey_max > 255u) throw std::invalid_argument("--flow-vel-thr takes a velocity >= 0 and --flow-grey-max 0..255");
+            bmode = true;                               // the colour lies over the 8-bit frame
+        }
         if (!freehand_n && (freehand_step || freehand_fan || freehand_box || freehand_voxel || freehand_out || freehand_mode || freehand_fill))
             throw std::invalid_argument("--freehand-step-mm, --freehand-fan-deg, --freehand-box-mm, --freehand-voxel-mm, --freehand-out, --freehand-mode and --freehand-fill need --freehand");
         long freehand_frames = 0; double freehand_step_mm = 0.0, freehand_fan_deg = 0.0;
@@ -512,6 +559,17 @@ int main(int argc, char **argv)
         scene scene{ cfg, transducer, dev, samples };
         scene.step(1000.0f);
         rf_image_ rf_image{ dev, transducer_radius_cm * 10.0, transducer_amplitude };
+        std::vector<float> flow_vel;                    // --flow-velocity: a vector per material of the scene
+        if (colour_flow) {
+            flow_vel.assign(3 * scene.material_names.size(), 0.0f);
+            for (const std::string &item : flow_velocity) {
+                const size_t colon = item.find(':');
+                const auto v = colon == std::string::npos ? std::vector<float>{} : comma_list<float>(item.c_str() + colon + 1);
+                if (v.size() != 3) throw std::invalid_argument("--flow-velocity takes NAME:vx,vy,vz");
+                const uint32_t m = scene.material_index(item.substr(0, colon));
+                for (int k = 0; k < 3; k++) flow_vel[3 * m + k] = v[k];
+            }
+        }
 
         const auto t0 = std::chrono::high_resolution_clock::now();
         for (int f = 0; f < frames; f++) {
@@ -519,6 +577,7 @@ int main(int argc, char **argv)
             else if (compound_given) rf_image.trace((uint32_t)f, transducer, steers);               // ... in N steered views
             else if (elevation_given) rf_image.trace((uint32_t)f, transducer, psf, (uint32_t)elevation);   // ... in K elevation planes, folded
             else rf_image.trace((uint32_t)f);      // clear + cast_rays + accumulation (main.cpp:102-144)
+            if (colour_flow && f == frames - 1) rf_image.flow_split(transducer, flow_vel);   // the raw trace split by label, before the PSF
             rf_image.convolve(psf);           // main.cpp:146
             if (noise) rf_image.add_noise(nopts, gain);   // the receiver's noise floor and dead elements, on whatever the convolution ran over
             if (iq_file && f == frames - 1) {            // the analytic pair of the last frame's RF, before it is detected
@@ -542,6 +601,16 @@ int main(int argc, char **argv)
             else if (compound_given) { if (bmode) rf_image.postprocess(display, steers, nullptr, opts); else rf_image.postprocess(steers, opts); }   // the views averaged (or opts' mode)
             else if (bmode) rf_image.postprocess(display);   // main.cpp:148, log-compressed to 8-bit grey
             else rf_image.postprocess();      // main.cpp:148
+            if (colour_flow && f == frames - 1) {        // the colour processor and the overlay over the frame just made
+                std::vector<unsigned char> rgb;
+                const auto maps = rf_image.colour_flow(psf, flopts, flcol, rgb, noise, 4.0, detect ? &dopts : nullptr);
+                write_ppm(colour_flow, display.out_cols, display.out_rows, rgb);
+                if (flow_truth) {
+                    std::ofstream out(flow_truth, std::ios::binary);
+                    out.write((const char *)maps.truth.data(), (std::streamsize)(maps.truth.size() * sizeof(float)));
+                    if (!out) throw std::runtime_error(std::string("cannot write ") + flow_truth);
+                }
+            }
         }
         check(dev->synchronize(), "mcrt_synchronize");
         const double dt = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();

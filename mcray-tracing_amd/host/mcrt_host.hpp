@@ -5,7 +5,7 @@
 //   transducer<N>            transducer.h:24-137   (frequency MHz, radius cm, element separation mm, position, angles deg)
 //   psf<ax,lat,elev,res>     psf.h:34-77
 //   scene                    scene.h:19-76, scene.cpp:16-48,185-247 (JSON keys, "Error while loading scene: ..." wrapping)
-//   rf_image<cols,us,um>     rfimage.h:20-219      (clear / convolve / envelope / postprocess; data lives on the GPU); + detect / iq
+//   rf_image<cols,us,um>     rfimage.h:20-219      (clear / convolve / envelope / postprocess; data lives on the GPU); + detect / iq; + flow_split / flow / colour_flow
 //   ray_physics::segment     ray.h:28-36           (vec3 stands in for btVector3; `media` is held BY VALUE: the reference's
 //                                                   `const material &` dangles by the time main.cpp:126 reads it)
 //   volume<size,res>         volume.h:19-61        (host copy of the texture the GPU samples)
@@ -704,6 +704,13 @@ inline void write_pgm(const std::string &path, uint32_t cols, uint32_t rows, con
     f.write((const char *)bytes.data(), (std::streamsize)bytes.size());
 }
 
+inline void write_ppm(const std::string &path, uint32_t cols, uint32_t rows, const std::vector<unsigned char> &rgb)   // binary PPM, the bytes as they are
+{
+    std::ofstream f(path, std::ios::binary);
+    f << "P6\n" << cols << " " << rows << "\n255\n";
+    f.write((const char *)rgb.data(), (std::streamsize)rgb.size());
+}
+
 // ---------------------------------------------------------------- rf_image (rfimage.h)
 // Two ways to fill it, both the reference's semantics:
 //   trace(frame)            clear + cast_rays + the accumulation loop of main.cpp:102-144 fused on the GPU (the fast path)
@@ -716,7 +723,7 @@ public:
 
     rf_image(double radius_mm, double angle_rad, std::shared_ptr<device> dev_ = nullptr)
         : dev(dev_ ? std::move(dev_) : default_device()), radius_mm(radius_mm), angle(angle_rad), host((size_t)columns * max_rows, 0.0f),
-          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev), sound(dev), sigma(dev), curve(dev), band_stack(dev)
+          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev), sound(dev), sigma(dev), curve(dev), band_stack(dev), flow_in(dev), flow_out(dev)
     {
         std::cout << "rf_image: " << max_rows << ", " << columns << std::endl;          // rfimage.h:30
         rf.reserve(sizeof(float) * columns * max_rows);
@@ -899,6 +906,80 @@ public:
         points.reserve(2 * sizeof(float) * n);
         check(mcrt_detect_frames(dev->ctx, s.dev, s.images, columns, max_rows, &o, nullptr, points.as<float>()), "mcrt_detect_frames");
         interleaved = download<float>(points.as<float>(), 2 * n);
+    }
+    // colour Doppler (mcrt.h: mcrt_flow_split_frames, mcrt_flow_frames, mcrt_colour_frames), three steps around the B-mode chain of ONE trace:
+    //   trace(f);  flow_split(t, vel);  convolve(p); [add_noise();] envelope() / detect();  postprocess(bmode_params);  colour_flow(p, fo, co, rgb);
+    // flow_split() goes right after trace(frame_id), while this image holds the raw RF: the label pass of t's central beams (lopts: null =
+    // the tracer's rule) and the split into what stands still and what moves, a device copy this image keeps.  vel_mm_s: a velocity
+    // vector per material of the scene [n_materials][3] (scene::material_index names them).  A stack of views, planes or tracked frames,
+    // or a host-deposited image, has no labels of its own: it throws
+    template <size_t N> void flow_split(const transducer<N> &t, const std::vector<float> &vel_mm_s, const mcrt_label_opts *lopts = nullptr)
+    {
+        static_assert(N == columns, "one scan-line per transducer element");
+        if (n_views || where != on_device) throw std::logic_error("rf_image::flow_split: right after trace(frame_id), on one traced image");
+        const uint32_t L = (uint32_t)(vel_mm_s.size() / 3u);
+        if (L == 0 || L > 254 || vel_mm_s.size() != 3u * L) throw std::invalid_argument("rf_image::flow_split: a velocity [3] per material, 1..254 materials");
+        const size_t n = (size_t)columns * max_rows;
+        flow_in.reserve(4 * 6 * n + n);                              // floats: the parts [2][n], their pairs [2][n][2]; then the tissue bytes
+        mcrt_ctx *tracer = dev->tracer();
+        check(mcrt_label_frames(tracer, 1, 0, columns, t.pos.data(), t.dir.data(), lopts, flow_tissue(), nullptr, nullptr), "mcrt_label_frames");
+        check(mcrt_synchronize(tracer), "mcrt_synchronize");
+        std::vector<uint8_t> moving(L);
+        for (uint32_t l = 0; l < L; l++) moving[l] = vel_mm_s[3 * l] != 0.0f || vel_mm_s[3 * l + 1] != 0.0f || vel_mm_s[3 * l + 2] != 0.0f;
+        check(mcrt_flow_split_frames(dev->ctx, rf.as<float>(), flow_tissue(), 1, columns, max_rows, moving.data(), L, flow_in.as<float>()), "mcrt_flow_split_frames");
+        flow_vel = vel_mm_s; flow_dir = t.dir; flow_frequency = (double)t.frequency;
+    }
+    // the colour processor in beam space: the two parts through p's PSF and the detector's I/Q (dopts: null = 31 taps), then mcrt_flow_frames.
+    // noise_sigma: the ensemble's sigma is the one add_noise() left on the device for this pass (it throws when it has not run), else
+    // fo.sigma.  The maps are [columns][max_rows]; the autocorrelation stays on the device for colour_flow()
+    struct flow_maps { std::vector<float> vel, var, truth; double v_nyq_mm_s = 0.0, sigma = 0.0; };
+    template <typename psf_> flow_maps flow(const psf_ &p, const mcrt_flow_opts &fo, bool noise_sigma = false, const mcrt_detect_opts *dopts = nullptr)
+    {
+        if (flow_vel.empty()) throw std::logic_error("rf_image::flow: flow_split(transducer, velocities) first");
+        if (p.has_bands()) throw std::invalid_argument("rf_image::flow: colour flow is one pulse: a psf without bands");
+        if (noise_sigma && sigma_frames != 1) throw std::logic_error("rf_image::flow: noise_sigma needs add_noise() on the same pass");
+        const size_t n = (size_t)columns * max_rows;
+        const uint32_t L = (uint32_t)(flow_vel.size() / 3u), n_ax = (uint32_t)p.get_axial_size(), n_lat = (uint32_t)p.get_lateral_size();
+        flow_maps m;
+        check(mcrt_flow_nyquist(&fo, flow_frequency, (double)speed_of_sound, &m.v_nyq_mm_s), "mcrt_flow_nyquist");
+        std::vector<float> phasor(2 * (size_t)L * columns), truth((size_t)L * columns);
+        check(mcrt_flow_phasors(m.v_nyq_mm_s, flow_vel.data(), flow_dir.data(), L, columns, phasor.data(), truth.data()), "mcrt_flow_phasors");
+        float *parts = flow_in.as<float>(), *pairs = parts + 2 * n;
+        if (p.has_focus())
+            check(mcrt_convolve_frames_depth(dev->ctx, parts, 2, columns, max_rows, p.axial_kernel.data(), n_ax, p.lateral_rows(max_rows, row_mm()).data(), n_lat), "mcrt_convolve_frames_depth");
+        else
+            check(mcrt_convolve_frames(dev->ctx, parts, 2, columns, max_rows, p.axial_kernel.data(), n_ax, p.lateral_kernel.data(), n_lat), "mcrt_convolve_frames");
+        mcrt_detect_opts d; mcrt_default_detect_opts(&d);
+        check(mcrt_detect_frames(dev->ctx, parts, 2, columns, max_rows, dopts ? dopts : &d, nullptr, pairs), "mcrt_detect_frames");
+        flow_out.reserve(4 * 6 * n);                                 // corr [3][n], vel, var, truth
+        float *corr = flow_out.as<float>(), *vel = corr + 3 * n, *var = vel + n, *tr = var + n;
+        check(mcrt_flow_frames(dev->ctx, pairs, pairs + 2 * n, flow_tissue(), 1, columns, max_rows, &fo, m.v_nyq_mm_s, phasor.data(), truth.data(), L, first_id,
+                               noise_sigma ? sigma.as<float>() : nullptr, corr, vel, var, tr), "mcrt_flow_frames");
+        m.vel = download<float>(vel, n); m.var = download<float>(var, n); m.truth = download<float>(tr, n);
+        m.sigma = noise_sigma ? (double)download<float>(sigma.as<float>(), 1)[0] : (double)fo.sigma;
+        return m;
+    }
+    // the colour-flow picture over the last postprocess(bmode_params) frame: flow(), the autocorrelation gathered through
+    // mcrt_scan_convert_frames at that frame's size, and mcrt_colour_frames with co -- whose power_thr is REPLACED by power_scale * 2 * N *
+    // sigma^2 when power_scale >= 0 (4 by default: a modelling choice nothing measures).  rgb: [out_rows][out_cols][3]; returns flow()'s maps
+    template <typename psf_> flow_maps colour_flow(const psf_ &p, const mcrt_flow_opts &fo, const mcrt_colour_opts &co, std::vector<unsigned char> &rgb,
+                                                   bool noise_sigma = false, double power_scale = 4.0, const mcrt_detect_opts *dopts = nullptr, std::vector<float> *velocity = nullptr)
+    {
+        if (!bmode_n) throw std::logic_error("rf_image::colour_flow: postprocess(bmode_params) first: the picture under the colour");
+        const size_t n = (size_t)columns * max_rows, np = bmode_n;
+        flow_out.reserve(4 * 6 * n + 4 * 4 * np + 3 * np);          // flow()'s six planes, then corr_img [3][np], vel_img [np] and the rgb bytes (before flow(): growing forgets)
+        flow_maps m = flow(p, fo, noise_sigma, dopts);
+        float *corr = flow_out.as<float>(), *img = corr + 6 * n, *vimg = img + 3 * np;
+        uint8_t *out = reinterpret_cast<uint8_t *>(vimg + np);
+        check(mcrt_scan_convert_frames(dev->ctx, corr, 3, columns, max_rows, radius_mm, angle, img, bmode_rows, bmode_cols), "mcrt_scan_convert_frames");
+        mcrt_colour_opts c = co;
+        if (power_scale >= 0.0) c.power_thr = (float)(power_scale * 2.0 * (double)fo.n_packets * m.sigma * m.sigma);
+        uint8_t lut[256 * 3];
+        check(mcrt_colour_map(0, lut), "mcrt_colour_map");
+        check(mcrt_colour_frames(dev->ctx, img, bmode_buf.as<uint8_t>(), 1, bmode_rows, bmode_cols, lut, &c, m.v_nyq_mm_s, out, vimg), "mcrt_colour_frames");
+        rgb = download<unsigned char>(out, 3 * np);
+        if (velocity) *velocity = download<float>(vimg, np);
+        return m;
     }
     // receiver noise (mcrt.h: mcrt_noise_frames): a noise floor and a gain per scan-line (element_gain: [columns] or null) over whatever the
     // last trace() filled, in place -- this image, or the views of a compounded frame or the planes of a sweep as ONE frame (one receiver,
@@ -1136,6 +1217,8 @@ private:
     }
     // the tail of every trace(): what the stack holds now, how many images, the first one's id; no sigma, no band images
     void traced_as(stack_of what, uint32_t n, uint32_t id) { holds = what; n_views = n; first_id = id; sigma_frames = 0; banded = 0; }
+    uint8_t *flow_tissue() { return flow_in.as<uint8_t>() + 4 * 6 * (size_t)columns * max_rows; }      // flow_in's tissue bytes, behind its floats
+    double flow_frequency = 0.0;
     // labels() / transmission(): the poses whose central beams they walk -- the K planes of the sweep when the last trace was a sweep, else t's own plane
     struct beam_poses { uint32_t planes; std::vector<float> pos, dir; };
     template <size_t N> beam_poses central_beams(const transducer<N> &t)
@@ -1262,6 +1345,8 @@ private:
     device_buffer sound;                         // transmission(): the transmit, reflect and crossings tables in one allocation
     device_buffer sigma, curve;                  // add_noise(): every frame's sigma; autogain(): the row gains and the penetration depths
     device_buffer band_stack;                    // convolve(p) with p.has_bands(): the band images [images][B][columns][max_rows] (grown, never shrunk)
+    device_buffer flow_in, flow_out;             // flow_split() / flow(): tissue, the two parts and their I/Q pairs; the correlation, vel, var, truth and the gathered pictures
+    std::vector<float> flow_vel, flow_dir;       // flow_split()'s velocities and scan-line directions, for flow()'s phasors
     uint32_t banded = 0;                         // ... B while they wait there for envelope() / fold_bands() (0: the images are where trace() left them)
     std::vector<float> band_w;                   // ... and the bands' weights [max_rows][B] they are folded with
     uint32_t sound_planes = 0;                   // ... their leading axis (nothing yet: 0)
