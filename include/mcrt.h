@@ -74,7 +74,12 @@ extern "C" {
                                    + mcrt_flow_opts, mcrt_default_flow_opts, mcrt_flow_nyquist, mcrt_flow_phasors, mcrt_flow_draws, mcrt_colour_map,
                                    mcrt_flow_split_frames, mcrt_flow_frames, mcrt_colour_opts, mcrt_default_colour_opts, mcrt_colour_frames
                                    (colour Doppler: a slow-time ensemble synthesised from one traced frame, the Kasai autocorrelator, the flow overlay and
-                                   the true axial velocity per sample; additive) */
+                                   the true axial velocity per sample; additive);
+                                   + mcrt_spectral_opts, mcrt_default_spectral_opts, mcrt_gate, mcrt_spectral_rotor, mcrt_spectral_phase, mcrt_spectral_profile,
+                                   mcrt_spectral_rates, mcrt_spectral_window, mcrt_spectral_twiddles, mcrt_spectral_draws, mcrt_pulse_waveform,
+                                   mcrt_spectral_series_frames, mcrt_spectral_frames, mcrt_sonogram_opts, mcrt_default_sonogram_opts, mcrt_sonogram_frames
+                                   (spectral Doppler: a sample gate's slow-time series under a pulsatile waveform and a velocity profile, its short-time
+                                   FFT and the sonogram; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -1230,7 +1235,8 @@ int mcrt_render_label_frames(mcrt_ctx *ctx, const uint8_t *label_dev /* [n_frame
  *   z_n = static + moving * p^n + noise_n,   n = 0 .. N-1,
  * with the phasor p of the sample's material and scan-line: the narrow-band model the autocorrelator of Kasai et al. (1985) is derived under.
  * LEFT OUT: velocity profiles (a material has ONE velocity vector), transit-time and axial-shift decorrelation of moving speckle, the
- * blood echo the PSF leaks outside the lumen (it keeps the label of where it lands), power / variance / spectral displays, persistence.
+ * blood echo the PSF leaks outside the lumen (it keeps the label of where it lands), power / variance displays, persistence.  (A velocity
+ * profile, a pulsatile waveform and the spectral display are the spectral chain's, below: mcrt_spectral_series_frames and what follows it.)
  * An opt-in chain; without it no call and no bit changes.
  *
  * Throughout, every float operation is rounded once: no fma, correctly rounded / and sqrtf, no device transcendental. */
@@ -1342,6 +1348,141 @@ int mcrt_default_colour_opts(mcrt_colour_opts *o);
 int mcrt_colour_frames(mcrt_ctx *ctx, const float *corr_img_dev /* [F][3][H][W] */, const uint8_t *grey_dev /* [F][H][W] */, uint32_t n_frames,
                        uint32_t height, uint32_t width, const uint8_t *lut /* [256][3] */, const mcrt_colour_opts *o, double v_nyq_mm_s,
                        uint8_t *rgb_dev /* [F][H][W][3] */, float *vel_img_dev /* [F][H][W] or NULL */);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Spectral (pulsed-wave) Doppler: a sample gate on one scan-line, a slow-time series of thousands of pulses under a pulsatile speed
+ * waveform and a velocity profile across the lumen, its short-time FFT, and the sonogram (velocity over time).  The reference has no
+ * counterpart.  THE MODEL is synthesised from ONE traced frame, as the colour ensemble is and for the same reason.  A GATE is G
+ * consecutive RF rows of one scan-line of one image.  The static I/Q of a gate row stands still; the moving I/Q of row r turns by the
+ * phase theta_r(t) = rate_r * Phi(t) at pulse t, where Phi(t) is the accumulated phase of the vessel's centre-line speed waveform (the
+ * pulsatile flow) and rate_r the row's share of that speed times the cosine to the beam (the velocity profile).  Rows at different
+ * depths of the lumen turn at different rates: a small gate on the axis gives a narrow line at the peak velocity, a gate across the
+ * lumen fills the spectrum from 0 to the peak, and the gate's moving speckle decorrelates over the series as a consequence.
+ * PHASES ARE INTEGERS, so the device and any mirror agree whatever the order: Phi(t) is an int64 in units of 2^-32 turn, rate_r an
+ * int32 in Q16 with |rate| <= 65536, and the rotor comes from a 4096-entry cos/sin table built on the host (its worst spur under a Hann
+ * window stays below -68 dB; 1024 entries give -60 dB, too coarse for a 60 dB display).
+ * LEFT OUT: the chord through the lumen stands in for the radial distance (the profile is exact only for a beam that crosses the
+ * vessel's axis); one waveform per call; transit-time broadening; spectral display on swept, compounded or banded frames; audio
+ * resampling (the I/Q series itself is the output); automatic peak-velocity tracing and the indices (PI, RI).
+ * An opt-in chain; without it no call and no bit changes.
+ *
+ * Throughout, every float operation is rounded once: no fma, correctly rounded / and sqrt, no device transcendental except the log10f
+ * of mcrt_sonogram_frames. */
+#define MCRT_SPECTRAL_WALL_NONE 0u
+#define MCRT_SPECTRAL_WALL_MEAN 1u
+typedef struct {
+    uint32_t n_pulses;      /* T, the pulses of the series: 1..16384; default 2048 */
+    uint32_t gate_rows;     /* G, the RF rows of a gate: 1..64; default 8 */
+    uint32_t n_fft;         /* N, the window of the short-time FFT: 32, 64, 128, 256 or 512; default 128 */
+    uint32_t hop;           /* pulses from one spectrum (column) to the next: 1..N; default 32 */
+    uint32_t wall;          /* the clutter filter over a window, MCRT_SPECTRAL_WALL_*; default MEAN */
+    uint32_t wall_bins;     /* bins |i - N/2| < wall_bins of a spectrum are written as +0.0f: 0..N/4; default 2 */
+    float sigma;            /* the receiver noise per I/Q component of ONE row, finite and >= 0, used when no sigma_dev is given; default 0 */
+    uint32_t seed;          /* Philox key word 0 of the noise stream; default 0x53504543 */
+} mcrt_spectral_opts;       /* 32 bytes */
+typedef struct { uint32_t image, line, row0; } mcrt_gate;      /* rows row0 .. row0 + G - 1 of scan-line `line` of image `image`; 12 bytes */
+/* the defaults above.  MCRT_ERR_INVALID for a null o.  Host only. */
+int mcrt_default_spectral_opts(mcrt_spectral_opts *o);
+/* The host-only helpers below refuse null pointers, zero sizes and non-finite input with MCRT_ERR_INVALID and sizes past a limit with
+ * MCRT_ERR_LIMIT; on an error nothing is written.
+ * the rotor table:  a = 6.283185307179586 * i / 4096.0 in double;  lut[i] = ((float)cos(a), (float)sin(a)). */
+int mcrt_spectral_rotor(float *lut /* [4096][2] */);
+/* the accumulated phase of a centre-line speed waveform [mm/s], in units of 2^-32 turn:
+ *   step_t = llrint((double)speed_mm_s[t] / v_nyq_mm_s * 2147483648.0);      phase[0] = 0;   phase[t + 1] = phase[t] + step_t
+ * (the Nyquist velocity is half a turn per pulse).  MCRT_ERR_INVALID for a v_nyq_mm_s that is not finite and > 0 or a speed that is not
+ * finite; MCRT_ERR_LIMIT for n_pulses > 16384 or a |step_t| above 2^32 -- twice the Nyquist velocity: aliasing up to
+ * there is allowed and shows as aliasing. */
+int mcrt_spectral_phase(double v_nyq_mm_s, const float *speed_mm_s /* [T] */, uint32_t n_pulses, int64_t *phase /* [T] */);
+/* the velocity profile across a lumen, a share in [0, 1] of the centre-line speed per gate row r = row0 .. row0 + G - 1 of ONE
+ * scan-line's tissue labels (mcrt_label_frames') tissue_line [R].  With l = tissue_line[r]: a row with l >= n_labels or moving[l] == 0
+ * gets +0.0f.  Otherwise [a, b] is the longest run of rows with label l that holds r, over the whole scan-line and not only the gate, and
+ *   x = (r - (a + b) / 2.0) / ((b - a + 1) / 2.0);      frac = (float)(1.0 - pow(fabs(x), exponent))        in double
+ * exponent == 0 gives 1.0f (plug flow), 2 a parabola.  MCRT_ERR_INVALID for n_labels == 0, row0 + G > R, an exponent that is not finite
+ * or neither 0 nor >= 1; MCRT_ERR_LIMIT for G > 64 or n_labels > 254. */
+int mcrt_spectral_profile(const uint8_t *tissue_line /* [R] */, uint32_t n_rows, uint32_t row0, uint32_t gate_rows, const uint8_t *moving /* [n_labels] */,
+                          uint32_t n_labels, double exponent, float *frac /* [G] */);
+/* the rows' rates in Q16:  rate = (int32_t)llrint(65536.0 * (double)frac * axial).  axial, in [-1, 1], is the cosine towards the probe:
+ * 0.0 - (v^ . dir_e) of the material's unit velocity and the gate line's direction, as in mcrt_flow_phasors.  MCRT_ERR_INVALID for an
+ * axial outside [-1, 1] or a frac outside [0, 1]; MCRT_ERR_LIMIT for G > 64. */
+int mcrt_spectral_rates(const float *frac /* [G] */, uint32_t gate_rows, double axial, int32_t *rate /* [G] */);
+/* the window of the short-time FFT.  kind 0: all 1.0f;  kind 1 (Hann): h[n] = (float)(0.5 - 0.5 * cos(6.283185307179586 * n / N)) in
+ * double.  MCRT_ERR_INVALID for another kind or an N that is not 32, 64, 128, 256 or 512. */
+int mcrt_spectral_window(uint32_t kind, uint32_t n_fft, float *h /* [N] */);
+/* the twiddles of the FFT:  a = 6.283185307179586 * k / N in double;  tw[k] = ((float)cos(a), (float)(0.0 - sin(a))),  k < N/2.  The
+ * library keeps this table per N on the device; the export exists for mirrors.  MCRT_ERR_INVALID for an N as above. */
+int mcrt_spectral_twiddles(uint32_t n_fft, float *tw /* [N/2][2] */);
+/* the integer noise draws of one gate's series, d[t][0..1] (I, Q): one Philox4x32-10 block per pulse with the counter
+ * (line, row0, 0x53504543, t) and the key (seed, image_id); d_I and d_Q are mcrt_flow_draws' Irwin-Hall sums of o0, o1 and o2, o3, with
+ * the same inv_std = (float)(1.0 / sqrt(1431655765.0)).  Counter word 2 differs from the tracer's (< 16), mcrt_noise_frames'
+ * (0x4E4F4953) and mcrt_flow_frames' (0x464C4F57).  MCRT_ERR_LIMIT for n_pulses > 16384. */
+int mcrt_spectral_draws(uint32_t seed, uint32_t image_id, uint32_t line, uint32_t row0, uint32_t n_pulses, int32_t *d /* [T][2] */);
+/* a pulsatile speed waveform -- a convenience, not physiology.  In double, then cast to float:
+ *   u = t * beats_per_min / (60.0 * prf_hz);   x = u - floor(u);   s = sin(3.141592653589793 * x / 0.3)
+ *   speed[t] = (float)(v_min + (v_peak - v_min) * (x < 0.3 ? s * s : 0.0))
+ * MCRT_ERR_INVALID for a prf_hz or a beats_per_min that is not finite and > 0 or a speed that is not finite; MCRT_ERR_LIMIT for
+ * n_pulses > 16384. */
+int mcrt_pulse_waveform(double prf_hz, double beats_per_min, double v_peak_mm_s, double v_min_mm_s, uint32_t n_pulses, float *speed_mm_s /* [T] */);
+/* THE SERIES of every gate, series_dev [n_gates][T][2].  iq_static_dev (or NULL) and iq_moving_dev [F][E][R][2] are the detected pairs of
+ * what stands still and what moves (mcrt_flow_split_frames, the PSF, mcrt_detect_frames(iq_dev)), T = o->n_pulses, G = o->gate_rows.
+ * Per gate j = (image, line, row0), with the rows r = row0 .. row0 + G - 1 ascending, w_r = weight[r - row0], S_r and M_r the static and
+ * the moving pair of (image, line, r):
+ *   zs = sum over r of (w_r * S_r), per component, from 0.0f;  without a static stack zs = (+0.0f, +0.0f)
+ *   A_r = (w_r * M_r.re, w_r * M_r.im)
+ * and per pulse t:
+ *   theta = (uint32_t)((phase[t] * (int64_t)rate[j][r - row0]) >> 16)            (an arithmetic shift: the product may be negative)
+ *   idx = ((theta + 0x80000u) >> 20) & 4095;      (c, s) = lut[idx]              (mcrt_spectral_rotor's table)
+ *   acc.re += (A_r.re * c - A_r.im * s);   acc.im += (A_r.re * s + A_r.im * c)   over r ascending from 0.0f, the products before the sums
+ *   z_t = (zs + acc) + k * (float)d_t                                            per component
+ * with k = (sigma_f * wnorm) * inv_std, sigma_f = sigma_dev ? sigma_dev[image] : o->sigma, wnorm = (float)sqrt(sum of (double)w_r *
+ * (double)w_r, ascending) -- the noise of G summed rows is that of one receiver -- and d_t mcrt_spectral_draws' of (o->seed,
+ * first_image_id + image, line, row0).  At k == 0 the noise term is skipped and no Philox block is computed.
+ * gates [n_gates], weight [G], rate [n_gates][G] and phase [T] are HOST tables, free when the call returns; they live in buffers of the
+ * context and are copied only when they differ from what is there.  Every element of series_dev is written; the inputs are read only.
+ * Asynchronous on the context's stream.  MCRT_ERR_INVALID for a null ctx, iq_moving_dev, gates, weight, rate, phase, o or series_dev,
+ * zero sizes, options out of range, a weight that is not finite, a |rate| above 65536, a gate with image >= F, line >= E or
+ * row0 + G > R, a series_dev that overlaps an input; MCRT_ERR_LIMIT for n_gates > 65535, n_gates * T >= 2^28, a stack of 2^31 samples
+ * or more, image ids that pass 2^32; on any error nothing is launched and nothing is written.  Groups: call it on mcrt_group_root(). */
+int mcrt_spectral_series_frames(mcrt_ctx *ctx, const float *iq_static_dev /* [F][E][R][2] or NULL */, const float *iq_moving_dev /* [F][E][R][2] */,
+                                uint32_t n_frames, uint32_t n_elements, uint32_t n_rows, const mcrt_gate *gates /* [n_gates] */, uint32_t n_gates,
+                                const float *weight /* [G] */, const int32_t *rate /* [n_gates][G] */, const int64_t *phase /* [T] */,
+                                const mcrt_spectral_opts *o, uint32_t first_image_id, const float *sigma_dev /* [F] or NULL */,
+                                float *series_dev /* [n_gates][T][2] */);
+/* THE SPECTRA of every gate's series: n_cols = (T - N) / hop + 1 columns of N = o->n_fft bins (a last partial window is dropped).  Per
+ * (gate, column c), complex floats throughout:
+ * 1. x_n = series[c * hop + n], n < N.  Wall MEAN: x_n = x_n - (the PAIRWISE sum of x) / (float)N per component -- mcrt_flow_frames'
+ *    pairwise sum; N is a power of two, so it is a plain tree: what stands still leaves as +0.0f.
+ * 2. y_n = (x_n.re * h_n, x_n.im * h_n) with the window h (mcrt_spectral_window's or the caller's own).
+ * 3. THE FFT, radix 2, decimation in time: y is permuted by bit reversal (y'[rev(n)] = y[n], rev over log2 N bits), then for the stages
+ *    s = 1 .. log2 N with half = 2^(s-1), for every block base b (a multiple of 2 half) and j < half:
+ *      w = tw[j * (N >> s)];  u = y[b + j];  v = y[b + j + half];     (mcrt_spectral_twiddles' table)
+ *      t = (v.re * w.re - v.im * w.im, v.re * w.im + v.im * w.re);    y[b + j] = u + t;   y[b + j + half] = u - t
+ *    The complex multiply is always done, for w = 1 too: NaN and infinities propagate alike everywhere.
+ * 4. P_k = X_k.re * X_k.re + X_k.im * X_k.im, in VELOCITY ORDER: out[i] = P[(i + N/2) mod N], so i = N/2 is zero velocity and bin i is
+ *    (i - N/2) * 2 v_nyq / N, positive towards the probe.  Bins with |i - N/2| < wall_bins are written as +0.0f.
+ * 5. mean = den > 0 ? (num / den) * (float)(2.0 * v_nyq_mm_s / N) : 0.0f, with num = the pairwise sum over i of
+ *    out[i] * (float)((int)i - N/2) and den = the pairwise sum of out[i].
+ * power_dev [n_gates][n_cols][N] and mean_dev [n_gates][n_cols], each a device pointer or NULL, at least one given; window [N] is a
+ * finite HOST table, kept in the context like the tables above.  series_dev is read only.  Asynchronous on the context's stream.
+ * MCRT_ERR_INVALID for a null ctx, series_dev, window or o, n_gates == 0, options out of range, T < N, a window entry or a v_nyq_mm_s
+ * that is not finite (v_nyq_mm_s > 0), no output, an output that overlaps the series or the other output; MCRT_ERR_LIMIT for
+ * n_gates > 65535 or n_gates * T >= 2^28; on any error nothing is launched and nothing is written.  Groups: on mcrt_group_root(). */
+int mcrt_spectral_frames(mcrt_ctx *ctx, const float *series_dev /* [n_gates][T][2] */, uint32_t n_gates, const float *window /* [N] */,
+                         const mcrt_spectral_opts *o, double v_nyq_mm_s, float *power_dev /* [n_gates][n_cols][N] or NULL */,
+                         float *mean_dev /* [n_gates][n_cols] or NULL */);
+/* THE SONOGRAM as displayed: a row is a velocity, a column a time, row 0 the highest velocity towards the probe:
+ *   out_dev[g][N - 1 - i][c] = byte of p = power_dev[g][c][i],  a NaN or an infinite p counting as 0
+ *   ref = o->ref > 0 ? o->ref : the gate's largest finite power (exact and independent of order; 0 when there is none)
+ *   v = p > 0 ? ((10.0f * log10f(p / ref) + gain_db) + dynamic_range_db) / dynamic_range_db : 0,  clamped to [0, 1];
+ *   byte = (uint8_t)(v * 255.0f + 0.5f)
+ * As in mcrt_bmode_frames, the device's log10f is not correctly rounded and may move a level by one.  peak_dev [n_gates] (or NULL)
+ * receives each gate's largest finite power (0.0f when there is none), whatever ref is.  Asynchronous on the context's stream.
+ * MCRT_ERR_INVALID for a null ctx, power_dev, o or out_dev, zero sizes, an N that is not 32 .. 512 as above, a dynamic_range_db that is
+ * not finite and > 0, a gain_db or ref that is not finite, overlapping buffers; MCRT_ERR_LIMIT for n_gates > 65535 or
+ * n_gates * n_cols >= 2^28; on any error nothing is launched.  Groups: on mcrt_group_root(). */
+typedef struct { float dynamic_range_db; float gain_db; float ref; } mcrt_sonogram_opts;      /* defaults 40, 0, 0; 12 bytes */
+int mcrt_default_sonogram_opts(mcrt_sonogram_opts *o);
+int mcrt_sonogram_frames(mcrt_ctx *ctx, const float *power_dev /* [n_gates][n_cols][N] */, uint32_t n_gates, uint32_t n_cols, uint32_t n_fft,
+                         const mcrt_sonogram_opts *o, float *peak_dev /* [n_gates] or NULL */, uint8_t *out_dev /* [n_gates][N][n_cols] */);
 
 /* device [E][R]  ->  host [R][E] row-major (the cv::Mat layout of rfimage.h:217); synchronous */
 int mcrt_export_rf(mcrt_ctx *ctx, const float *rf_dev, uint32_t n_elements, uint32_t n_rows, float *host_rows_by_cols);

@@ -80,6 +80,22 @@ class ColourOpts(C.Structure):
     _fields_ = [("power_thr", C.c_float), ("vel_thr_mm_s", C.c_float), ("grey_max", C.c_uint32)]
 
 
+class SpectralOpts(C.Structure):
+    """mcrt_spectral_opts (include/mcrt.h): 32 bytes"""
+    _fields_ = [("n_pulses", C.c_uint32), ("gate_rows", C.c_uint32), ("n_fft", C.c_uint32), ("hop", C.c_uint32), ("wall", C.c_uint32),
+                ("wall_bins", C.c_uint32), ("sigma", C.c_float), ("seed", C.c_uint32)]
+
+
+class Gate(C.Structure):
+    """mcrt_gate (include/mcrt.h): 12 bytes"""
+    _fields_ = [("image", C.c_uint32), ("line", C.c_uint32), ("row0", C.c_uint32)]
+
+
+class SonogramOpts(C.Structure):
+    """mcrt_sonogram_opts (include/mcrt.h): 12 bytes"""
+    _fields_ = [("dynamic_range_db", C.c_float), ("gain_db", C.c_float), ("ref", C.c_float)]
+
+
 class Compound(C.Structure):
     """mcrt_compound (include/mcrt.h): 68 bytes, steer_rad at offset 4"""
     _fields_ = [("n_views", C.c_uint32), ("steer_rad", C.c_float * 16)]
@@ -164,6 +180,7 @@ assert C.sizeof(Sweep) == 12 and C.sizeof(VolumeGrid) == 112 and C.sizeof(LabelO
 assert C.sizeof(ReconLabelOpts) == 12 and C.sizeof(AutogainOpts) == 24 and C.sizeof(TransmitOpts) == 12 and C.sizeof(Speckle3dOpts) == 28 and Speckle3dOpts.weight.offset == 16
 assert C.sizeof(Bands) == 80 and Bands.band_weight.offset == 36 and Bands.var_x.offset == 68 and Bands.min_mhz.offset == 76 and C.sizeof(DetectOpts) == 4
 assert C.sizeof(FlowOpts) == 32 and FlowOpts.prf_hz.offset == 16 and FlowOpts.seed.offset == 28 and C.sizeof(ColourOpts) == 12
+assert C.sizeof(SpectralOpts) == 32 and SpectralOpts.sigma.offset == 24 and C.sizeof(Gate) == 12 and C.sizeof(SonogramOpts) == 12
 
 # every symbol include/mcrt.h declares (tests/test_abi.py checks the .so exports each one)
 SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create", "mcrt_destroy", "mcrt_set_stream",
@@ -190,6 +207,9 @@ SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create"
            "mcrt_default_detect_opts", "mcrt_detect_taps", "mcrt_detect_gain", "mcrt_psf_carrier", "mcrt_detect_frames",
            "mcrt_default_flow_opts", "mcrt_flow_nyquist", "mcrt_flow_phasors", "mcrt_flow_draws", "mcrt_colour_map", "mcrt_flow_split_frames", "mcrt_flow_frames",
            "mcrt_default_colour_opts", "mcrt_colour_frames",
+           "mcrt_default_spectral_opts", "mcrt_spectral_rotor", "mcrt_spectral_phase", "mcrt_spectral_profile", "mcrt_spectral_rates", "mcrt_spectral_window",
+           "mcrt_spectral_twiddles", "mcrt_spectral_draws", "mcrt_pulse_waveform", "mcrt_spectral_series_frames", "mcrt_spectral_frames",
+           "mcrt_default_sonogram_opts", "mcrt_sonogram_frames",
            "mcrt_default_recon_opts", "mcrt_recon_transform", "mcrt_recon_frames",
            "mcrt_default_recon_label_opts", "mcrt_recon_label_frames", "mcrt_render_label_frames"]
 
@@ -294,6 +314,19 @@ def load_library():
         "mcrt_flow_frames": [vp, vp, vp, vp, u32, u32, u32, C.POINTER(FlowOpts), C.c_double, vp, vp, u32, u32, vp, vp, vp, vp, vp],
         "mcrt_default_colour_opts": [C.POINTER(ColourOpts)],
         "mcrt_colour_frames": [vp, vp, vp, u32, u32, u32, vp, C.POINTER(ColourOpts), C.c_double, vp, vp],
+        "mcrt_default_spectral_opts": [C.POINTER(SpectralOpts)],
+        "mcrt_spectral_rotor": [vp],
+        "mcrt_spectral_phase": [C.c_double, vp, u32, vp],
+        "mcrt_spectral_profile": [vp, u32, u32, u32, vp, u32, C.c_double, vp],
+        "mcrt_spectral_rates": [vp, u32, C.c_double, vp],
+        "mcrt_spectral_window": [u32, u32, vp],
+        "mcrt_spectral_twiddles": [u32, vp],
+        "mcrt_spectral_draws": [u32, u32, u32, u32, u32, vp],
+        "mcrt_pulse_waveform": [C.c_double, C.c_double, C.c_double, C.c_double, u32, vp],
+        "mcrt_spectral_series_frames": [vp, vp, vp, u32, u32, u32, vp, u32, vp, vp, vp, C.POINTER(SpectralOpts), u32, vp, vp],
+        "mcrt_spectral_frames": [vp, vp, u32, vp, C.POINTER(SpectralOpts), C.c_double, vp, vp],
+        "mcrt_default_sonogram_opts": [C.POINTER(SonogramOpts)],
+        "mcrt_sonogram_frames": [vp, vp, u32, u32, u32, C.POINTER(SonogramOpts), vp, vp],
         "mcrt_default_recon_opts": [C.POINTER(ReconOpts)],
         "mcrt_recon_transform": [C.POINTER(VolumeGrid), C.c_double, vp, vp],
         "mcrt_recon_frames": [vp, vp, u32, u32, u32, vp, vp, C.c_double, C.c_double, C.POINTER(VolumeGrid), C.POINTER(ReconOpts), vp, vp, vp],

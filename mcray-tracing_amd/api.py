@@ -12,7 +12,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Bands, DetectOpts, FlowOpts, ColourOpts, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, Speckle3dOpts, NoiseOpts, AutogainOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Bands, DetectOpts, FlowOpts, ColourOpts, SpectralOpts, Gate, SonogramOpts, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, Speckle3dOpts, NoiseOpts, AutogainOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 DEFAULT_ANGLE = 1.0471975511965976      # the sector of main.cpp:28: 60 degrees [rad]
 
@@ -210,6 +210,100 @@ def host_colour_map(kind=0):
     lut = np.zeros((256, 3), np.uint8)
     check(load_library().mcrt_colour_map(int(kind) & 0xFFFFFFFF, ptr(lut)))
     return lut
+
+
+SPECTRAL_WALLS = {"none": 0, "mean": 1}               # MCRT_SPECTRAL_WALL_*
+SPECTRAL_WINDOWS = {"rect": 0, "hann": 1}             # the kinds of mcrt_spectral_window
+
+
+def spectral_opts_struct(n_pulses=None, gate_rows=None, n_fft=None, hop=None, wall=None, wall_bins=None, sigma=None, seed=None):
+    """mcrt_spectral_opts from keywords over mcrt_default_spectral_opts: n_pulses (1..16384; 2048), gate_rows (1..64; 8), n_fft (32, 64, 128,
+    256, 512; 128), hop (1..n_fft; 32), wall ("none" | "mean" or the number; mean), wall_bins (0..n_fft/4; 2), sigma (0), seed -- the
+    library checks the ranges"""
+    o = SpectralOpts()
+    check(load_library().mcrt_default_spectral_opts(C.byref(o)))
+    if wall is not None:
+        if isinstance(wall, str) and wall not in SPECTRAL_WALLS:
+            raise ValueError("wall must be one of %s, got %r" % (sorted(SPECTRAL_WALLS), wall))
+        o.wall = SPECTRAL_WALLS[wall] if isinstance(wall, str) else int(wall) & 0xFFFFFFFF
+    for name, v in (("n_pulses", n_pulses), ("gate_rows", gate_rows), ("n_fft", n_fft), ("hop", hop), ("wall_bins", wall_bins), ("seed", seed)):
+        if v is not None:
+            setattr(o, name, int(v) & 0xFFFFFFFF)
+    if sigma is not None:
+        o.sigma = float(sigma)
+    return o
+
+
+def sonogram_opts_struct(dynamic_range_db=None, gain_db=None, ref=None):
+    """mcrt_sonogram_opts from keywords over mcrt_default_sonogram_opts (40 dB, 0 dB, ref 0: each gate's own largest finite power)"""
+    o = SonogramOpts()
+    check(load_library().mcrt_default_sonogram_opts(C.byref(o)))
+    for name, v in (("dynamic_range_db", dynamic_range_db), ("gain_db", gain_db), ("ref", ref)):
+        if v is not None:
+            setattr(o, name, float(v))
+    return o
+
+
+def host_spectral_rotor():
+    """mcrt_spectral_rotor: the cos/sin table of the series' rotor, float32 [4096][2]"""
+    lut = np.zeros((4096, 2), np.float32)
+    check(load_library().mcrt_spectral_rotor(ptr(lut)))
+    return lut
+
+
+def host_spectral_phase(v_nyq_mm_s, speed_mm_s):
+    """mcrt_spectral_phase: the accumulated phase int64 [T], in units of 2^-32 turn, of a centre-line speed waveform [T] in mm/s"""
+    s = np.ascontiguousarray(speed_mm_s, np.float32).reshape(-1)
+    ph = np.zeros(s.size, np.int64)
+    check(load_library().mcrt_spectral_phase(float(v_nyq_mm_s), ptr(s), s.size, ptr(ph)))
+    return ph
+
+
+def host_spectral_profile(tissue_line, row0, gate_rows, moving, exponent=2.0):
+    """mcrt_spectral_profile: the share of the centre-line speed per gate row, float32 [gate_rows], from one scan-line's tissue labels
+    uint8 [R] and a byte per label (non-zero: the material moves); exponent 0: plug flow, 2: a parabola"""
+    t = np.ascontiguousarray(tissue_line, np.uint8).reshape(-1); mv = np.ascontiguousarray(moving, np.uint8).reshape(-1)
+    frac = np.zeros(min(max(int(gate_rows), 0), 64), np.float32)
+    check(load_library().mcrt_spectral_profile(ptr(t), t.size, row0, gate_rows, ptr(mv), mv.size, float(exponent), ptr(frac)))
+    return frac
+
+
+def host_spectral_rates(frac, axial):
+    """mcrt_spectral_rates: the rows' rates in Q16, int32 [G], of their shares and the cosine towards the probe"""
+    f = np.ascontiguousarray(frac, np.float32).reshape(-1)
+    rate = np.zeros(min(f.size, 64), np.int32)
+    check(load_library().mcrt_spectral_rates(ptr(f), f.size, float(axial), ptr(rate)))
+    return rate
+
+
+def host_spectral_window(kind, n_fft):
+    """mcrt_spectral_window: float32 [n_fft]; kind "rect" | "hann" or the number"""
+    if isinstance(kind, str) and kind not in SPECTRAL_WINDOWS:
+        raise ValueError("window must be one of %s, got %r" % (sorted(SPECTRAL_WINDOWS), kind))
+    h = np.zeros(min(max(int(n_fft), 0), 512), np.float32)
+    check(load_library().mcrt_spectral_window(SPECTRAL_WINDOWS[kind] if isinstance(kind, str) else int(kind) & 0xFFFFFFFF, n_fft, ptr(h)))
+    return h
+
+
+def host_spectral_twiddles(n_fft):
+    """mcrt_spectral_twiddles: the FFT's twiddles, float32 [n_fft / 2][2]"""
+    tw = np.zeros((min(max(int(n_fft), 0), 512) // 2, 2), np.float32)
+    check(load_library().mcrt_spectral_twiddles(n_fft, ptr(tw)))
+    return tw
+
+
+def host_spectral_draws(seed, image_id, line, row0, n_pulses):
+    """mcrt_spectral_draws: the integer draws of one gate's series, int32 [n_pulses][2] (noise = d * sigma * wnorm / sqrt(1431655765))"""
+    d = np.zeros((min(max(int(n_pulses), 0), 16384), 2), np.int32)
+    check(load_library().mcrt_spectral_draws(int(seed) & 0xFFFFFFFF, int(image_id) & 0xFFFFFFFF, line, row0, n_pulses, ptr(d)))
+    return d
+
+
+def host_pulse_waveform(prf_hz, beats_per_min, v_peak, v_min, n_pulses):
+    """mcrt_pulse_waveform: a pulsatile centre-line speed [mm/s], float32 [n_pulses] -- a sin^2 systole over 0.3 of the beat above v_min"""
+    s = np.zeros(min(max(int(n_pulses), 0), 16384), np.float32)
+    check(load_library().mcrt_pulse_waveform(float(prf_hz), float(beats_per_min), float(v_peak), float(v_min), n_pulses, ptr(s)))
+    return s
 
 
 def row_pitch_mm(frequency):
@@ -1117,6 +1211,41 @@ class Context(_SceneCalls):
         check(self.L.mcrt_colour_frames(self.h, ptr(corr_img_dev), ptr(grey_dev), n_frames, height, width, ptr(table), C.byref(o), float(v_nyq_mm_s),
                                         ptr(rgb_dev), ptr(vel_img_dev)))
 
+    def spectral_series_frames(self, iq_static_dev, iq_moving_dev, n_frames, n_elements, n_rows, gates, weight, rate, phase, series_dev, first_image_id=0,
+                               sigma_dev=None, opts=None, **kw):
+        """mcrt_spectral_series_frames: the slow-time series of every sample gate, series_dev [n_gates][T][2], from the detected pairs
+        [n_frames][E][R][2] of what stands still (or None) and what moves.  gates: (image, line, row0) per gate; weight float32 [G]; rate
+        int32 [n_gates][G] (host_spectral_rates); phase int64 [T] (host_spectral_phase) -- host tables.  n_pulses and gate_rows default to
+        the tables' own lengths.  opts: a SpectralOpts, or the keywords of spectral_opts_struct"""
+        g = np.ascontiguousarray(gates, np.uint32).reshape(-1, 3)
+        w = np.ascontiguousarray(weight, np.float32).reshape(-1); ph = np.ascontiguousarray(phase, np.int64).reshape(-1)
+        rt = np.ascontiguousarray(rate, np.int32)
+        if opts is None:
+            kw.setdefault("n_pulses", ph.size); kw.setdefault("gate_rows", w.size)
+        o = opts if opts is not None else spectral_opts_struct(**kw)
+        if ph.size != o.n_pulses or w.size != o.gate_rows or rt.size != g.shape[0] * o.gate_rows:
+            raise ValueError("the tables take phase [%d], weight [%d] and rate [%d][%d], got %s, %s and %s" % (o.n_pulses, o.gate_rows, g.shape[0], o.gate_rows,
+                                                                                                             ph.shape, w.shape, rt.shape))
+        check(self.L.mcrt_spectral_series_frames(self.h, ptr(iq_static_dev), ptr(iq_moving_dev), n_frames, n_elements, n_rows, ptr(g), g.shape[0], ptr(w), ptr(rt),
+                                                 ptr(ph), C.byref(o), first_image_id, ptr(sigma_dev), ptr(series_dev)))
+
+    def spectral_frames(self, series_dev, n_gates, v_nyq_mm_s, power_dev=None, mean_dev=None, window="hann", opts=None, **kw):
+        """mcrt_spectral_frames: the short-time FFT of every gate's series [n_gates][T][2] -> power_dev [n_gates][n_cols][N] in velocity order
+        and / or mean_dev [n_gates][n_cols], n_cols = (T - N) // hop + 1.  window: "rect" | "hann" or float32 [N]; opts: a SpectralOpts, or the
+        keywords of spectral_opts_struct"""
+        o = opts if opts is not None else spectral_opts_struct(**kw)
+        h = host_spectral_window(window, o.n_fft) if isinstance(window, (str, int)) else np.ascontiguousarray(window, np.float32).reshape(-1)
+        if h.size != o.n_fft:
+            raise ValueError("window takes float32 [%d], got shape %s" % (o.n_fft, h.shape))
+        check(self.L.mcrt_spectral_frames(self.h, ptr(series_dev), n_gates, ptr(h), C.byref(o), float(v_nyq_mm_s), ptr(power_dev), ptr(mean_dev)))
+
+    def sonogram_frames(self, power_dev, n_gates, n_cols, n_fft, out_dev, peak_dev=None, **opts):
+        """mcrt_sonogram_frames: the spectra [n_gates][n_cols][N] -> the displayed bytes out_dev [n_gates][N][n_cols], row 0 the highest
+        velocity towards the probe, and, where given, each gate's largest finite power peak_dev [n_gates].  opts: the keywords of
+        sonogram_opts_struct"""
+        o = sonogram_opts_struct(**opts)
+        check(self.L.mcrt_sonogram_frames(self.h, ptr(power_dev), n_gates, n_cols, n_fft, C.byref(o), ptr(peak_dev), ptr(out_dev)))
+
     def scan_convert_frames(self, rf_dev, n_frames, n_elements, n_rows, out_dev, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         check(self.L.mcrt_scan_convert_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, radius_mm, total_angle, ptr(out_dev), out_rows, out_cols))
 
@@ -1523,7 +1652,9 @@ class Simulator:
         then synthesise a slow-time ensemble from ONE traced frame, split by tissue label into what stands still and what moves, and
         estimate the axial velocity with the Kasai autocorrelator; with noise= the noise stage's sigma is the ensemble's, else the
         dict's.  The displayed power threshold is power_scale * 2 * N * sigma^2 (default scale 4): a modelling choice that no
-        measurement backs.  Every other method is left alone: without the keyword no call and no bit changes."""
+        measurement backs.  spectral_doppler() runs the same chain up to the detected pairs and then synthesises the slow-time series of
+        ONE sample gate under a speed waveform and a velocity profile (its own keywords; of flow= it reads the material's direction, prf_hz,
+        sigma and the label rule).  Every other method is left alone: without the keyword no call and no bit changes."""
         self.flow = _option(flow)
         if self.flow is not None:
             fd = self.flow if "velocity_mm_s" in self.flow else dict(velocity_mm_s=self.flow)
@@ -2020,7 +2151,7 @@ class Simulator:
         """ONE trace of the frame -> the label pass -> the raw RF split by label (its device copy: rf_dev goes on through bmode()'s own
         stages in place, noise= included, which leaves sigma on the device) -> the two parts through the PSF and the detector's I/Q ->
         mcrt_flow_frames.  Yields dict(tissue, corr, vel, var, truth: device buffers that live as long as the block, those in `want`;
-        sigma: the ensemble's, on the host)"""
+        iq_static, iq_moving: the detected pairs [E][R][2] the ensemble was made of; sigma: the ensemble's, on the host)"""
         if self.flow is None:
             raise RuntimeError("colour flow needs Simulator(flow=...)")
         for on, what in ((self.sweep is not None, "sweep="), (self.steers is not None, "compound="), (self.elevation, "elevation="), (self.psf.has_bands, "a psf with bands")):
@@ -2041,7 +2172,7 @@ class Simulator:
             self.ctx.flow_frames(iq, iq + 8 * n, tissue, 1, self.E, self.R, fl["v_nyq"], fl["phasor"], fl["truth"], first_image_id=frame_id, sigma_dev=sigma_dev,
                                  opts=fl["opts"], **{k + "_dev": p for k, p in out.items()})
             sigma = float(self.ctx.d2h(sigma_dev, (1,), np.float32)[0]) if sigma_dev is not None else float(fl["opts"].sigma)
-            yield dict(out, tissue=tissue, sigma=sigma)
+            yield dict(out, tissue=tissue, sigma=sigma, iq_static=iq, iq_moving=iq + 8 * n)
 
     def flow_velocity(self, frame_id=0):
         """the colour processor's estimates in beam space -> dict(vel, var, truth: float32 [E][R]): the Kasai velocity [mm/s, towards the
@@ -2049,6 +2180,72 @@ class Simulator:
         sample's material (flow= only)"""
         with self._flow_pass(frame_id, ("vel", "var", "truth")) as b:
             return {k: self.ctx.d2h(b[k], (self.E, self.R), np.float32) for k in ("vel", "var", "truth")}
+
+    def spectral_doppler(self, frame_id=0, gate=(0, 0.0, 2.0), material="BLOOD", waveform=None, profile=2.0, window="hann", **kw):
+        """the sonogram of one sample gate -> dict(power float32 [n_cols][N] in velocity order, grey uint8 [N][n_cols] as displayed (row 0
+        the highest velocity towards the probe), mean float32 [n_cols], series complex64 [T], truth float32 [n_cols], velocity_axis float64
+        [N] in mm/s, time_axis float64 [n_cols] in seconds (the windows' centres)).  It traces ONCE and runs colour flow's chain up to the
+        detected pairs (flow= only; it refuses what colour_flow() refuses), reads the gate line's tissue labels for the velocity profile
+        and synthesises the slow-time series of the gate.  gate: (scan-line, depth_mm of the gate's centre, length_mm); material: the
+        scene's material whose velocity vector (flow=) gives the direction of the flow -- its length is not used: waveform is the
+        centre-line speed [mm/s] per pulse, an array or dict(beats_per_min=, v_peak=, v_min=) for host_pulse_waveform at the flow's
+        prf_hz (n_pulses pulses, default 2048); profile: the exponent of host_spectral_profile (0: plug flow, 2: a parabola).  truth is
+        the true axial centre-line velocity averaged over each window.  kw: n_pulses, n_fft, hop, wall, wall_bins, sigma (default: the
+        ensemble's), seed, and the sonogram's dynamic_range_db, gain_db, ref"""
+        if self.flow is None:
+            raise RuntimeError("spectral Doppler needs Simulator(flow=...)")
+        fl = self.flow
+        if material not in self.material_names:
+            raise ValueError("spectral_doppler: the scene has no material %r (it has %s)" % (material, ", ".join(self.material_names)))
+        label = self.material_names.index(material)
+        vel = fl["vel"][label].astype(np.float64)
+        if not vel.any():
+            raise ValueError("spectral_doppler: flow= gives material %r no velocity, so the flow has no direction" % material)
+        norm = float(np.sqrt((vel[0] * vel[0] + vel[1] * vel[1]) + vel[2] * vel[2]))
+        display = {k: kw.pop(k) for k in ("dynamic_range_db", "gain_db", "ref") if k in kw}
+        line, depth_mm, length_mm = int(gate[0]), float(gate[1]), float(gate[2])
+        pitch = row_pitch_mm(self.tr.frequency)
+        G = min(max(int(round(length_mm / pitch)), 1), 64, self.R)
+        row0 = min(max(int(round(depth_mm / pitch - G / 2.0)), 0), self.R - G)
+        if not 0 <= line < self.E:
+            raise ValueError("spectral_doppler: scan-line %d is not in 0..%d" % (line, self.E - 1))
+        prf = float(fl["opts"].prf_hz)
+        if waveform is None or isinstance(waveform, dict):
+            w = dict(beats_per_min=72.0, v_peak=norm, v_min=0.0)
+            w.update(waveform or {})
+            speed = host_pulse_waveform(prf, w["beats_per_min"], w["v_peak"], w["v_min"], kw.get("n_pulses", 2048))
+        else:
+            speed = np.ascontiguousarray(waveform, np.float32).reshape(-1)
+        kw["n_pulses"] = speed.size
+        d = self.tr.dir[line].astype(np.float64)
+        unit = (vel / norm).astype(np.float32).astype(np.float64)
+        axial = min(max(0.0 - ((unit[0] * d[0] + unit[1] * d[1]) + unit[2] * d[2]), -1.0), 1.0)
+        moving = np.zeros(len(self.material_names), np.uint8); moving[label] = 1
+        with self._flow_pass(frame_id, ("truth",)) as b:
+            kw.setdefault("sigma", b["sigma"])
+            o = spectral_opts_struct(gate_rows=G, **kw)
+            T, N, hop = o.n_pulses, o.n_fft, o.hop
+            if T < N:
+                raise ValueError("spectral_doppler: %d pulses are fewer than one window of %d" % (T, N))
+            cols = (T - N) // hop + 1
+            tissue_line = self.ctx.d2h(b["tissue"] + line * self.R, (self.R,), np.uint8)
+            frac = host_spectral_profile(tissue_line, row0, G, moving, profile)
+            rate = host_spectral_rates(frac, axial)
+            phase = host_spectral_phase(fl["v_nyq"], speed)
+            with self.ctx.temp(8 * T) as series, self.ctx.temp(4 * cols * N) as power, self.ctx.temp(4 * cols) as mean, self.ctx.temp(cols * N) as grey:
+                self.ctx.spectral_series_frames(b["iq_static"], b["iq_moving"], 1, self.E, self.R, [[0, line, row0]], np.ones(G, np.float32), rate, phase, series,
+                                                first_image_id=frame_id, opts=o)
+                self.ctx.spectral_frames(series, 1, fl["v_nyq"], power_dev=power, mean_dev=mean, window=window, opts=o)
+                self.ctx.sonogram_frames(power, 1, cols, N, grey, **display)
+                z = self.ctx.d2h(series, (T, 2), np.float32)
+                out = dict(power=self.ctx.d2h(power, (cols, N), np.float32), grey=self.ctx.d2h(grey, (N, cols), np.uint8),
+                           mean=self.ctx.d2h(mean, (cols,), np.float32), series=np.ascontiguousarray(z).view(np.complex64)[:, 0])
+        axial_speed = speed.astype(np.float64) * axial
+        out["truth"] = np.array([axial_speed[c * hop:c * hop + N].mean() for c in range(cols)], np.float32)
+        out["velocity_axis"] = (np.arange(N) - N // 2) * (2.0 * fl["v_nyq"] / N)
+        out["time_axis"] = (np.arange(cols) * hop + N / 2.0) / prf
+        out["gate"] = dict(line=line, row0=row0, rows=G, rate=rate, frac=frac, axial=axial)
+        return out
 
     def colour_flow(self, frame_id=0, **display):
         """the colour-flow picture of a frame -> dict(rgb uint8 [out_rows][out_cols][3], grey uint8 [out_rows][out_cols], velocity float32

@@ -690,7 +690,9 @@ extern "C" int mcrt_debug_beam_scan(mcrt_ctx *c, const uint32_t *counts, uint32_
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(ocount, counts, (size_t)n * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(order, fill.data(), (len + 64) * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(obase, 0xff, (size_t)n * 4)); HIP_TRY(hipMemset(lcount, 0, MCRT_BEAM_COUNTERS * 4));
+    // (on the context's stream: a memset of device memory on the null stream does not wait for the host, and the context's stream does
+    // not wait for the null stream -- the counters were once cleared after the kernel had written them)
+    HIP_TRY(hipMemsetAsync(obase, 0xff, (size_t)n * 4, c->stream)); HIP_TRY(hipMemsetAsync(lcount, 0, MCRT_BEAM_COUNTERS * 4, c->stream));
     mcrt::BeamArgs g = {};
     g.n_beams = n - 1u; g.ocount = ocount; g.obase = obase; g.order = order; g.lcount = lcount; g.ordered = 1u;
     HIP_TRY(mcrt::launch_beam_scan(g, c->stream));

@@ -106,6 +106,27 @@ struct StagedTable : Staging {
     }
 };
 
+// A host table of 32-bit words of any type (gates, integer rates, 64-bit phases as word pairs, floats) on the device as it is, under
+// Staging's rules and StagedTable's comparison: uploaded only when its bits or its length differ from what is there.  The buffers only
+// ever grow.
+struct StagedWords : Staging {
+    std::vector<uint32_t> on_dev; bool valid = false;
+    int put(const void *src, size_t words, hipStream_t st)
+    {
+        if (valid && on_dev.size() == words && !memcmp(src, on_dev.data(), 4 * words)) return MCRT_OK;
+        float *h = nullptr;
+        MCRT_TRY(begin(words > dev.cap ? words : dev.cap, st, &h));
+        valid = false;
+        memcpy(h, src, 4 * words);
+        MCRT_TRY(commit(words, st));
+        on_dev.resize(words);
+        memcpy(on_dev.data(), src, 4 * words);
+        valid = true;
+        return MCRT_OK;
+    }
+    template <class T> const T *as() const { return (const T *)dev.p; }
+};
+
 // Maps that a stage's kernels gather through, made on the host from a geometry and kept on the device under that geometry's key: the
 // scan-conversion maps [N][2][n_pad] (per view the column map, then the row map) and the volume maps [3][n_pad] (plane, column, row),
 // n_pad = the output points rounded up to 256 floats and zero-padded, so every map is 16-byte aligned.  The key is the bytes the caller
@@ -197,6 +218,10 @@ struct ImageStages {
     // colour Doppler (mcrt_flow_frames): the phasors [n_labels][E][2] and the true velocities [n_labels][E] of the last tables, the
     // per-sample autocorrelation [F][3][E][R] of the largest call so far; (mcrt_colour_frames): the last colour table, 256 packed entries
     StagedTable flow_phasor, flow_truth, colour_lut; Buf<float> d_flow;
+    // spectral Doppler: the last host tables of mcrt_spectral_series_frames (the rotor [4096][2], gates [n_gates][3], weight [G], rate
+    // [n_gates][G], phase [T] as word pairs) and of mcrt_spectral_frames (window [N]; the twiddles of N = 32 << i, each made once), and
+    // the gates' peaks of a mcrt_sonogram_frames without a peak_dev
+    StagedWords spec_rotor, spec_gates, spec_weight, spec_rate, spec_phase, spec_window, spec_tw[5]; Buf<float> d_sono_peak;
     // automatic gain (mcrt_autogain_frames): the histograms of a chunk of frames [frames][n_bands][2048], at most AUTOGAIN_HIST_WORDS, and the row
     // gains [n_frames][R] of the largest call so far that gave no gain_dev
     Buf<uint32_t> d_aghist; Buf<float> d_aggain;

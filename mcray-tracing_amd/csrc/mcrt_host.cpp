@@ -1076,6 +1076,158 @@ extern "C" int mcrt_default_colour_opts(mcrt_colour_opts *o)
     return MCRT_OK;
 }
 
+// ---- spectral Doppler (the contracts are in include/mcrt.h) ---------------------------------------
+extern "C" int mcrt_default_spectral_opts(mcrt_spectral_opts *o)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_spectral_opts: null options");
+    o->n_pulses = 2048u; o->gate_rows = 8u; o->n_fft = 128u; o->hop = 32u; o->wall = MCRT_SPECTRAL_WALL_MEAN; o->wall_bins = 2u;
+    o->sigma = 0.0f; o->seed = 0x53504543u;
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_default_sonogram_opts(mcrt_sonogram_opts *o)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_sonogram_opts: null options");
+    o->dynamic_range_db = 40.0f; o->gain_db = 0.0f; o->ref = 0.0f;
+    return MCRT_OK;
+}
+
+static bool spectral_fft_size(uint32_t N) { return N == 32u || N == 64u || N == 128u || N == 256u || N == 512u; }
+
+int mcrt::spectral_check(const char *fn, const mcrt_spectral_opts *o)
+{
+    if (o->n_pulses < 1u || o->n_pulses > 16384u) return set_error(MCRT_ERR_INVALID, "%s: n_pulses must be 1 .. 16384 (%u)", fn, o->n_pulses);
+    if (o->gate_rows < 1u || o->gate_rows > 64u) return set_error(MCRT_ERR_INVALID, "%s: gate_rows must be 1 .. 64 (%u)", fn, o->gate_rows);
+    if (!spectral_fft_size(o->n_fft)) return set_error(MCRT_ERR_INVALID, "%s: n_fft must be 32, 64, 128, 256 or 512 (%u)", fn, o->n_fft);
+    if (o->hop < 1u || o->hop > o->n_fft) return set_error(MCRT_ERR_INVALID, "%s: hop must be 1 .. n_fft (%u)", fn, o->hop);
+    if (o->wall > MCRT_SPECTRAL_WALL_MEAN) return set_error(MCRT_ERR_INVALID, "%s: unknown wall filter %u", fn, o->wall);
+    if (o->wall_bins > o->n_fft / 4u) return set_error(MCRT_ERR_INVALID, "%s: wall_bins must be 0 .. n_fft / 4 (%u)", fn, o->wall_bins);
+    if (!(std::isfinite(o->sigma) && o->sigma >= 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: sigma must be finite and >= 0 (%g)", fn, (double)o->sigma);
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_spectral_rotor(float *lut)
+{
+    if (!lut) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_spectral_rotor: null lut");
+    for (uint32_t i = 0; i < 4096u; i++) {
+        const double a = 6.283185307179586 * i / 4096.0;
+        lut[2u * i] = (float)std::cos(a); lut[2u * i + 1u] = (float)std::sin(a);
+    }
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_spectral_phase(double v_nyq_mm_s, const float *speed_mm_s, uint32_t T, int64_t *phase)
+{
+    static const char fn[] = "mcrt_spectral_phase";
+    if (!speed_mm_s || !phase) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (T == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: n_pulses is zero", fn);
+    if (T > 16384u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: at most 16384 pulses (%u)", fn, T);
+    if (!(std::isfinite(v_nyq_mm_s) && v_nyq_mm_s > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: v_nyq_mm_s must be finite and > 0 (%g)", fn, v_nyq_mm_s);
+    for (uint32_t t = 0; t < T; t++) {
+        if (!std::isfinite(speed_mm_s[t])) return mcrt::set_error(MCRT_ERR_INVALID, "%s: speed_mm_s[%u] is not finite", fn, t);
+        if (std::fabs((double)speed_mm_s[t] / v_nyq_mm_s * 2147483648.0) > 4294967296.5)
+            return mcrt::set_error(MCRT_ERR_LIMIT, "%s: speed_mm_s[%u] = %g is more than twice the Nyquist velocity %g", fn, t, (double)speed_mm_s[t], v_nyq_mm_s);
+    }
+    std::vector<int64_t> step(T);
+    for (uint32_t t = 0; t < T; t++) {
+        step[t] = (int64_t)std::llrint((double)speed_mm_s[t] / v_nyq_mm_s * 2147483648.0);
+        if (step[t] > 4294967296ll || step[t] < -4294967296ll)
+            return mcrt::set_error(MCRT_ERR_LIMIT, "%s: speed_mm_s[%u] = %g is more than twice the Nyquist velocity %g", fn, t, (double)speed_mm_s[t], v_nyq_mm_s);
+    }
+    int64_t p = 0;
+    for (uint32_t t = 0; t < T; t++) { phase[t] = p; p += step[t]; }
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_spectral_profile(const uint8_t *tissue_line, uint32_t R, uint32_t row0, uint32_t G, const uint8_t *moving, uint32_t n_labels, double exponent,
+                                     float *frac)
+{
+    static const char fn[] = "mcrt_spectral_profile";
+    if (!tissue_line || !moving || !frac) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (R == 0 || G == 0 || n_labels == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_rows %u, gate_rows %u, n_labels %u)", fn, R, G, n_labels);
+    if (G > 64u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: at most 64 gate rows (%u)", fn, G);
+    if (n_labels > 254u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: at most 254 labels (%u)", fn, n_labels);
+    if ((uint64_t)row0 + G > R) return mcrt::set_error(MCRT_ERR_INVALID, "%s: the gate's rows %u .. %llu pass the scan-line's %u", fn, row0, (unsigned long long)row0 + G - 1u, R);
+    if (!(std::isfinite(exponent) && (exponent == 0.0 || exponent >= 1.0))) return mcrt::set_error(MCRT_ERR_INVALID, "%s: exponent must be 0 or >= 1 (%g)", fn, exponent);
+    for (uint32_t i = 0; i < G; i++) {
+        const uint32_t r = row0 + i, l = tissue_line[r];
+        if (l >= n_labels || moving[l] == 0) { frac[i] = 0.0f; continue; }
+        uint32_t a = r, b = r;
+        while (a > 0u && tissue_line[a - 1u] == l) a--;
+        while (b + 1u < R && tissue_line[b + 1u] == l) b++;
+        const double x = ((double)r - ((double)a + (double)b) / 2.0) / (((double)b - (double)a + 1.0) / 2.0);
+        frac[i] = exponent == 0.0 ? 1.0f : (float)(1.0 - std::pow(std::fabs(x), exponent));
+    }
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_spectral_rates(const float *frac, uint32_t G, double axial, int32_t *rate)
+{
+    static const char fn[] = "mcrt_spectral_rates";
+    if (!frac || !rate) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (G == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: gate_rows is zero", fn);
+    if (G > 64u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: at most 64 gate rows (%u)", fn, G);
+    if (!(axial >= -1.0 && axial <= 1.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: axial must be in [-1, 1] (%g)", fn, axial);
+    for (uint32_t i = 0; i < G; i++)
+        if (!(frac[i] >= 0.0f && frac[i] <= 1.0f)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: frac[%u] must be in [0, 1] (%g)", fn, i, (double)frac[i]);
+    for (uint32_t i = 0; i < G; i++) rate[i] = (int32_t)std::llrint(65536.0 * (double)frac[i] * axial);
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_spectral_window(uint32_t kind, uint32_t N, float *h)
+{
+    static const char fn[] = "mcrt_spectral_window";
+    if (!h) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null h", fn);
+    if (kind > 1u) return mcrt::set_error(MCRT_ERR_INVALID, "%s: unknown kind %u", fn, kind);
+    if (!spectral_fft_size(N)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: n_fft must be 32, 64, 128, 256 or 512 (%u)", fn, N);
+    for (uint32_t n = 0; n < N; n++) h[n] = kind == 0u ? 1.0f : (float)(0.5 - 0.5 * std::cos(6.283185307179586 * n / N));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_spectral_twiddles(uint32_t N, float *tw)
+{
+    static const char fn[] = "mcrt_spectral_twiddles";
+    if (!tw) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null tw", fn);
+    if (!spectral_fft_size(N)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: n_fft must be 32, 64, 128, 256 or 512 (%u)", fn, N);
+    for (uint32_t k = 0; k < N / 2u; k++) {
+        const double a = 6.283185307179586 * k / N;
+        tw[2u * k] = (float)std::cos(a); tw[2u * k + 1u] = (float)(0.0 - std::sin(a));
+    }
+    return MCRT_OK;
+}
+
+// the draws k_gate_series makes for one gate's series, [T][2]
+extern "C" int mcrt_spectral_draws(uint32_t seed, uint32_t image_id, uint32_t line, uint32_t row0, uint32_t T, int32_t *d)
+{
+    static const char fn[] = "mcrt_spectral_draws";
+    if (!d) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null d", fn);
+    if (T == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: n_pulses is zero", fn);
+    if (T > 16384u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: at most 16384 pulses (%u)", fn, T);
+    for (uint32_t t = 0; t < T; t++) {
+        uint32_t o[4];
+        host_philox4x32_10(line, row0, 0x53504543u, t, seed, image_id, o);
+        d[2u * t] = (int32_t)((o[0] & 0xffffu) + (o[0] >> 16) + (o[1] & 0xffffu) + (o[1] >> 16)) - 131070;
+        d[2u * t + 1u] = (int32_t)((o[2] & 0xffffu) + (o[2] >> 16) + (o[3] & 0xffffu) + (o[3] >> 16)) - 131070;
+    }
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_pulse_waveform(double prf_hz, double beats_per_min, double v_peak, double v_min, uint32_t T, float *speed)
+{
+    static const char fn[] = "mcrt_pulse_waveform";
+    if (!speed) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null speed_mm_s", fn);
+    if (T == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: n_pulses is zero", fn);
+    if (T > 16384u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: at most 16384 pulses (%u)", fn, T);
+    if (!(std::isfinite(prf_hz) && prf_hz > 0.0) || !(std::isfinite(beats_per_min) && beats_per_min > 0.0))
+        return mcrt::set_error(MCRT_ERR_INVALID, "%s: prf_hz and beats_per_min must be finite and > 0 (%g, %g)", fn, prf_hz, beats_per_min);
+    if (!std::isfinite(v_peak) || !std::isfinite(v_min)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: the speeds must be finite (%g, %g)", fn, v_peak, v_min);
+    for (uint32_t t = 0; t < T; t++) {
+        const double u = t * beats_per_min / (60.0 * prf_hz), x = u - std::floor(u), s = std::sin(3.141592653589793 * x / 0.3);
+        speed[t] = (float)(v_min + (v_peak - v_min) * (x < 0.3 ? s * s : 0.0));
+    }
+    return MCRT_OK;
+}
+
 // ---- automatic gain (the contract is in include/mcrt.h) ---------------------------------------
 extern "C" int mcrt_default_autogain_opts(mcrt_autogain_opts *o)
 {

@@ -240,6 +240,132 @@ extern "C" int mcrt_flow_frames(mcrt_ctx *c, const float *iq_static_dev, const f
     return MCRT_OK;
 }
 
+// ---- spectral Doppler (the contracts are in include/mcrt.h; the defaults, the option ranges and the table builders are host code:
+// mcrt_host.cpp).  Each call checks everything before anything is enqueued; then its host tables (only those that differ from what the
+// device holds) and its kernel. ----
+static int spectral_sizes(const char *fn, uint32_t n_gates, uint32_t T)
+{
+    if (n_gates > 65535u) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 gates (%u)", fn, n_gates);
+    if ((uint64_t)n_gates * T >= (1ull << 28)) return set_error(MCRT_ERR_LIMIT, "%s: n_gates * n_pulses must stay below 2^28 (%u x %u)", fn, n_gates, T);
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_spectral_series_frames(mcrt_ctx *c, const float *iq_static_dev, const float *iq_moving_dev, uint32_t n_frames, uint32_t E, uint32_t R,
+                                           const mcrt_gate *gates, uint32_t n_gates, const float *weight, const int32_t *rate, const int64_t *phase,
+                                           const mcrt_spectral_opts *o, uint32_t first_image_id, const float *sigma_dev, float *series_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_spectral_series_frames";
+    if (!iq_moving_dev || !gates || !weight || !rate || !phase || !o || !series_dev) return set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (n_frames == 0 || E == 0 || R == 0 || n_gates == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, n_elements %u, n_rows %u, n_gates %u)", fn, n_frames, E, R, n_gates);
+    MCRT_TRY(mcrt::spectral_check(fn, o));
+    const uint32_t G = o->gate_rows, T = o->n_pulses;
+    MCRT_TRY(spectral_sizes(fn, n_gates, T));
+    if ((double)n_frames * (double)E * (double)R >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: a stack of 2^31 samples or more (%u x %u x %u)", fn, n_frames, E, R);
+    if ((uint64_t)first_image_id + n_frames > 0x100000000ull) return set_error(MCRT_ERR_LIMIT, "%s: first_image_id: the ids of %u images from %u on pass 2^32", fn, n_frames, first_image_id);
+    double w2 = 0.0;
+    for (uint32_t i = 0; i < G; i++) {
+        if (!std::isfinite(weight[i])) return set_error(MCRT_ERR_INVALID, "%s: weight[%u] is not finite", fn, i);
+        w2 += (double)weight[i] * (double)weight[i];
+    }
+    for (uint32_t j = 0; j < n_gates; j++) {
+        if (gates[j].image >= n_frames || gates[j].line >= E || (uint64_t)gates[j].row0 + G > R)
+            return set_error(MCRT_ERR_INVALID, "%s: gate %u (image %u, line %u, rows %u + %u) is outside the stack %u x %u x %u", fn, j, gates[j].image, gates[j].line, gates[j].row0, G, n_frames, E, R);
+        for (uint32_t i = 0; i < G; i++)
+            if (rate[(size_t)j * G + i] > 65536 || rate[(size_t)j * G + i] < -65536) return set_error(MCRT_ERR_INVALID, "%s: rate[%u][%u] = %d is outside +-65536", fn, j, i, rate[(size_t)j * G + i]);
+    }
+    const size_t n = (size_t)n_frames * E * R;
+    const Range out{ series_dev, 8 * (size_t)n_gates * T, "series_dev" };
+    const Range ins[3] = { { iq_static_dev, 8 * n, "iq_static_dev" }, { iq_moving_dev, 8 * n, "iq_moving_dev" }, { sigma_dev, 4 * (size_t)n_frames, "sigma_dev" } };
+    MCRT_TRY(check_overlap(fn, out, ins, 3, false));
+    static const std::vector<float> rotor = [] { std::vector<float> l(8192); mcrt_spectral_rotor(l.data()); return l; }();
+    MCRT_TRY(c->img.spec_rotor.put(rotor.data(), 8192, c->stream));
+    MCRT_TRY(c->img.spec_gates.put(gates, 3 * (size_t)n_gates, c->stream));
+    MCRT_TRY(c->img.spec_weight.put(weight, G, c->stream));
+    MCRT_TRY(c->img.spec_rate.put(rate, (size_t)n_gates * G, c->stream));
+    MCRT_TRY(c->img.spec_phase.put(phase, 2 * (size_t)T, c->stream));
+    mcrt::GateSeriesArgs a; memset(&a, 0, sizeof a);
+    a.iq_static = (const float2 *)iq_static_dev; a.iq_moving = (const float2 *)iq_moving_dev; a.sigma_dev = sigma_dev; a.series = (float2 *)series_dev;
+    a.gates = c->img.spec_gates.as<uint32_t>(); a.weight = c->img.spec_weight.as<float>(); a.rate = c->img.spec_rate.as<int32_t>();
+    a.phase = c->img.spec_phase.as<long long>(); a.lut = c->img.spec_rotor.as<float2>();
+    a.E = E; a.R = R; a.G = G; a.T = T; a.n_gates = n_gates; a.chunks = (T + 63u) / 64u; a.seed = o->seed; a.first_id = first_image_id;
+    a.sigma = o->sigma; a.wnorm = (float)std::sqrt(w2); a.inv_std = (float)(1.0 / std::sqrt(1431655765.0));
+    HIP_TRY(mcrt::launch_gate_series(a, c->stream));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_spectral_frames(mcrt_ctx *c, const float *series_dev, uint32_t n_gates, const float *window, const mcrt_spectral_opts *o, double v_nyq_mm_s,
+                                    float *power_dev, float *mean_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_spectral_frames";
+    if (!series_dev || !window || !o) return set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (n_gates == 0) return set_error(MCRT_ERR_INVALID, "%s: n_gates is zero", fn);
+    MCRT_TRY(mcrt::spectral_check(fn, o));
+    const uint32_t T = o->n_pulses, N = o->n_fft;
+    if (T < N) return set_error(MCRT_ERR_INVALID, "%s: a series of %u pulses is shorter than one window of %u", fn, T, N);
+    if (!(std::isfinite(v_nyq_mm_s) && v_nyq_mm_s > 0.0)) return set_error(MCRT_ERR_INVALID, "%s: v_nyq_mm_s must be finite and > 0 (%g)", fn, v_nyq_mm_s);
+    if (!power_dev && !mean_dev) return set_error(MCRT_ERR_INVALID, "%s: no output is given", fn);
+    for (uint32_t i = 0; i < N; i++)
+        if (!std::isfinite(window[i])) return set_error(MCRT_ERR_INVALID, "%s: window[%u] is not finite", fn, i);
+    MCRT_TRY(spectral_sizes(fn, n_gates, T));
+    const uint32_t n_cols = (T - N) / o->hop + 1u;
+    const Range in{ series_dev, 8 * (size_t)n_gates * T, "series_dev" };
+    const Range outs[2] = { { power_dev, 4 * (size_t)n_gates * n_cols * N, "power_dev" }, { mean_dev, 4 * (size_t)n_gates * n_cols, "mean_dev" } };
+    MCRT_TRY(check_overlap(fn, in, outs, 2, true));
+    uint32_t slot = 0;
+    while ((32u << slot) != N) slot++;
+    StagedWords &tw = c->img.spec_tw[slot];
+    if (!tw.valid) {
+        std::vector<float> t(N);
+        MCRT_TRY(mcrt_spectral_twiddles(N, t.data()));
+        MCRT_TRY(tw.put(t.data(), N, c->stream));
+    }
+    MCRT_TRY(c->img.spec_window.put(window, N, c->stream));
+    mcrt::SpectrumArgs a; memset(&a, 0, sizeof a);
+    a.series = (const float2 *)series_dev; a.window = c->img.spec_window.as<float>(); a.tw = tw.as<float2>(); a.power = power_dev; a.mean = mean_dev;
+    a.n_gates = n_gates; a.T = T; a.n_cols = n_cols; a.N = N; a.hop = o->hop; a.wall = o->wall; a.wall_bins = o->wall_bins;
+    a.vscale = (float)(2.0 * v_nyq_mm_s / N);
+    HIP_TRY(mcrt::launch_spectrum(a, c->stream));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_sonogram_frames(mcrt_ctx *c, const float *power_dev, uint32_t n_gates, uint32_t n_cols, uint32_t N, const mcrt_sonogram_opts *o, float *peak_dev,
+                                    uint8_t *out_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_sonogram_frames";
+    if (!power_dev || !o || !out_dev) return set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (n_gates == 0 || n_cols == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_gates %u, n_cols %u)", fn, n_gates, n_cols);
+    if (N != 32u && N != 64u && N != 128u && N != 256u && N != 512u) return set_error(MCRT_ERR_INVALID, "%s: n_fft must be 32, 64, 128, 256 or 512 (%u)", fn, N);
+    if (!(std::isfinite(o->dynamic_range_db) && o->dynamic_range_db > 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: dynamic_range_db must be finite and > 0 (%g)", fn, (double)o->dynamic_range_db);
+    if (!std::isfinite(o->gain_db) || !std::isfinite(o->ref)) return set_error(MCRT_ERR_INVALID, "%s: gain_db and ref must be finite (%g, %g)", fn, (double)o->gain_db, (double)o->ref);
+    MCRT_TRY(spectral_sizes(fn, n_gates, n_cols));
+    const size_t n = (size_t)n_gates * n_cols * N;
+    const Range in{ power_dev, 4 * n, "power_dev" };
+    const Range outs[2] = { { peak_dev, 4 * (size_t)n_gates, "peak_dev" }, { out_dev, n, "out_dev" } };
+    MCRT_TRY(check_overlap(fn, in, outs, 2, true));
+    const bool own_ref = o->ref > 0.0f;
+    float *peak = peak_dev;
+    if (!peak && !own_ref) {
+        if (n_gates > c->img.d_sono_peak.cap) {
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            HIP_TRY(c->img.d_sono_peak.alloc(n_gates));
+        }
+        peak = c->img.d_sono_peak;
+    }
+    mcrt::SonogramArgs a; memset(&a, 0, sizeof a);
+    a.power = power_dev; a.peak = peak; a.out = out_dev; a.n_gates = n_gates; a.n_cols = n_cols; a.N = N;
+    a.ref = o->ref; a.gain = o->gain_db; a.dr = o->dynamic_range_db;
+    if (peak) {
+        HIP_TRY(hipMemsetAsync(peak, 0, 4 * (size_t)n_gates, c->stream));
+        HIP_TRY(mcrt::launch_sonogram_peak(a, c->stream));
+    }
+    if (own_ref) a.peak = nullptr;
+    HIP_TRY(mcrt::launch_sonogram(a, c->stream));
+    return MCRT_OK;
+}
+
 // the scan-conversion maps of a geometry on the device, in cache m: the plain maps (cp null: mcrt_scan_maps, one view) or the N views of a steer
 // list (mcrt_compound_maps), [N][2][n_pad]
 static int ensure_maps(mcrt_ctx *c, MapCache &m, uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t orows, uint32_t ocols, const mcrt_compound *cp, const float **maps)

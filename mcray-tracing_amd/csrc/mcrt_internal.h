@@ -78,5 +78,7 @@ int volume_check(const char *fn, const mcrt_sweep *sw, const mcrt_volume_grid *g
 int autogain_check(const char *fn, const mcrt_autogain_opts *o);
 // mcrt_host.cpp: the ranges of mcrt_flow_opts, which mcrt_flow_nyquist and mcrt_flow_frames share
 int flow_check(const char *fn, const mcrt_flow_opts *o);
+// mcrt_host.cpp: the ranges of mcrt_spectral_opts, which mcrt_spectral_series_frames and mcrt_spectral_frames share
+int spectral_check(const char *fn, const mcrt_spectral_opts *o);
 }
 #endif

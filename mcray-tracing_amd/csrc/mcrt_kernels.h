@@ -18,6 +18,7 @@
 //   mcrt_noise.hip   k_noise (receiver noise: mcrt_noise_frames; its peaks are k_bmode_peak's)
 //   mcrt_detect.hip  k_detect<NT> (quadrature detection: mcrt_detect_frames; NT taps, 1..16)
 //   mcrt_flow.hip    k_flow_split, k_flow<N, WALL>, k_flow_avg (colour Doppler: mcrt_flow_split_frames, mcrt_flow_frames), k_colour (mcrt_colour_frames)
+//   mcrt_spectral.hip k_gate_series (spectral Doppler: mcrt_spectral_series_frames), k_spectrum<N> (mcrt_spectral_frames), k_sonogram_peak, k_sonogram (mcrt_sonogram_frames)
 //   mcrt_autogain.hip k_autogain_hist, k_autogain_curve, k_autogain_apply (automatic gain: mcrt_autogain_frames)
 //   mcrt_recon.hip   k_recon_splat, k_recon_resolve (freehand 3-D reconstruction: mcrt_recon_frames)
 //   mcrt_label.hip   k_label (ground-truth label maps: mcrt_label_frames), k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames)
@@ -418,6 +419,42 @@ struct ColourArgs {
     PixelPass pass;
 };
 hipError_t launch_colour(const ColourArgs &a, hipStream_t st);
+// k_gate_series (mcrt_spectral_series_frames): the detected pairs and the context's copies of the host tables -> series [n_gates][T]
+struct GateSeriesArgs {
+    const float2 *iq_static;            // [F][E][R] (I, Q) or null
+    const float2 *iq_moving;            // [F][E][R]
+    const uint32_t *gates;              // [n_gates][3]: image, line, row0
+    const float *weight;                // [G]
+    const int32_t *rate;                // [n_gates][G], Q16
+    const long long *phase;             // [T], 2^-32 turn
+    const float2 *lut;                  // [4096] the rotor
+    const float *sigma_dev;             // [F] or null: sigma
+    float2 *series;                     // [n_gates][T]
+    uint32_t E, R, G, T, n_gates, chunks;   // chunks: ceil(T / 64)
+    uint32_t seed, first_id;
+    float sigma, wnorm, inv_std;
+};
+hipError_t launch_gate_series(const GateSeriesArgs &a, hipStream_t st);
+// k_spectrum<N> (mcrt_spectral_frames): series [n_gates][T] -> power [n_gates][n_cols][N] and mean [n_gates][n_cols], each or null
+struct SpectrumArgs {
+    const float2 *series;
+    const float *window;                // [N] the context's copy
+    const float2 *tw;                   // [N / 2] the context's table of this N
+    float *power, *mean;
+    uint32_t n_gates, T, n_cols, N, hop, wall, wall_bins;
+    float vscale;                       // (float)(2 v_nyq / N)
+};
+hipError_t launch_spectrum(const SpectrumArgs &a, hipStream_t st);
+// k_sonogram_peak and k_sonogram (mcrt_sonogram_frames): power [n_gates][n_cols][N] -> the gates' largest finite powers and the bytes [n_gates][N][n_cols]
+struct SonogramArgs {
+    const float *power;
+    float *peak;                        // [n_gates], zeroed before k_sonogram_peak; null: ref
+    uint8_t *out;
+    uint32_t n_gates, n_cols, N;
+    float ref, gain, dr;
+};
+hipError_t launch_sonogram_peak(const SonogramArgs &a, hipStream_t st);
+hipError_t launch_sonogram(const SonogramArgs &a, hipStream_t st);
 hipError_t launch_remap(const float *img, uint32_t n_img, uint32_t E, uint32_t R, const float *map_col, const float *map_row, float *out, uint32_t n, hipStream_t st);
 hipError_t launch_bmode_peak(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, float *peak, hipStream_t st);   // peak[F] zeroed before
 hipError_t launch_bmode_grey(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, const float *peak /*[F] or null: ref*/, float ref,

@@ -125,6 +125,13 @@
 // averaging half-window in rows and scan-lines (2,1); --flow-vel-thr X [mm/s] and --flow-grey-max G are the display thresholds (0, 255); with
 // --noise the ensemble carries the receiver's sigma and power below 4 * 2 N sigma^2 is not shown.  --flow-truth FILE.raw writes the true axial
 // velocity of every scan-line sample, float32 [512][465].  It does not combine with --compound, --sweep, --elevation or the band options.
+// --spectral FILE.pgm writes the last frame's sonogram (pulsed-wave spectral Doppler), a binary PGM of N rows (velocities, row 0 the highest towards
+// the probe) by (T - N) / H + 1 columns (times): --gate LINE,DEPTH_MM,LEN_MM is the sample gate -- a scan-line, the depth of its centre and its
+// length --, whose slow-time series of --spectral-pulses T pulses (1..16384; 2048) is synthesised from that frame's ONE trace (colour flow's chain
+// up to the detected pairs) under a parabolic velocity profile across the lumen and the pulsatile centre-line speed --flow-waveform BPM,PEAK,MIN
+// [1/min, mm/s, mm/s] (72, the speed of --flow-velocity, 0) along the FIRST --flow-velocity's direction; a Hann-windowed FFT of --spectral-fft N
+// pulses (32, 64, 128, 256, 512; 128) every --spectral-hop H pulses (32) is shown over --spectral-db X dB (40).  --spectral-iq FILE.raw writes the
+// series itself, float32 [T][2].  --flow-prf-hz applies; it does not combine with --compound, --sweep, --elevation or the band options.
 #include "mcrt_host.hpp"
 #include <algorithm>
 #include <chrono>
@@ -187,6 +194,12 @@ int main(int argc, char **argv)
     const char *colour_flow = nullptr, *flow_packets = nullptr, *flow_prf = nullptr, *flow_wall = nullptr, *flow_avg = nullptr, *flow_vel_thr = nullptr,
                *flow_grey_max = nullptr, *flow_truth = nullptr;   // the options as given
     std::vector<std::string> flow_velocity;
+    const char *spectral = nullptr, *spectral_gate = nullptr, *spectral_pulses = nullptr, *spectral_fft = nullptr, *spectral_hop = nullptr, *spectral_db = nullptr,
+               *flow_waveform = nullptr, *spectral_iq = nullptr;   // the options as given
+    mcrt_spectral_opts spopts; mcrt_default_spectral_opts(&spopts);
+    mcrt_sonogram_opts sgopts; mcrt_default_sonogram_opts(&sgopts);
+    double gate_depth_mm = 0.0, gate_len_mm = 0.0, wave_bpm = 72.0, wave_peak = -1.0, wave_min = 0.0;   // wave_peak < 0: the speed of --flow-velocity
+    uint32_t gate_line = 0;
     mcrt_flow_opts flopts; mcrt_default_flow_opts(&flopts);
     mcrt_colour_opts flcol; mcrt_default_colour_opts(&flcol);
     mcrt_detect_opts dopts; mcrt_default_detect_opts(&dopts);
@@ -262,6 +275,14 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--flow-vel-thr") && i + 1 < argc) flow_vel_thr = argv[++i];
             else if (!std::strcmp(argv[i], "--flow-grey-max") && i + 1 < argc) flow_grey_max = argv[++i];
             else if (!std::strcmp(argv[i], "--flow-truth") && i + 1 < argc) flow_truth = argv[++i];
+            else if (!std::strcmp(argv[i], "--spectral") && i + 1 < argc) spectral = argv[++i];
+            else if (!std::strcmp(argv[i], "--gate") && i + 1 < argc) spectral_gate = argv[++i];
+            else if (!std::strcmp(argv[i], "--spectral-pulses") && i + 1 < argc) spectral_pulses = argv[++i];
+            else if (!std::strcmp(argv[i], "--spectral-fft") && i + 1 < argc) spectral_fft = argv[++i];
+            else if (!std::strcmp(argv[i], "--spectral-hop") && i + 1 < argc) spectral_hop = argv[++i];
+            else if (!std::strcmp(argv[i], "--spectral-db") && i + 1 < argc) spectral_db = argv[++i];
+            else if (!std::strcmp(argv[i], "--flow-waveform") && i + 1 < argc) flow_waveform = argv[++i];
+            else if (!std::strcmp(argv[i], "--spectral-iq") && i + 1 < argc) spectral_iq = argv[++i];
             else if (!std::strcmp(argv[i], "--freehand") && i + 1 < argc) freehand_n = argv[++i];
             else if (!std::strcmp(argv[i], "--freehand-step-mm") && i + 1 < argc) freehand_step = argv[++i];
             else if (!std::strcmp(argv[i], "--freehand-fan-deg") && i + 1 < argc) freehand_fan = argv[++i];
@@ -459,7 +480,35 @@ int main(int argc, char **argv)
             if (dopts.n_taps > 63u || mcrt_detect_taps(&dopts, taps) != MCRT_OK) throw std::invalid_argument("--detect-taps takes 3, 7, 11, ..., 63 taps");
         }
         if (iq_file && (compound_given || sweep_given || with_bands)) throw std::invalid_argument("--iq does not combine with --compound, --sweep or the band options");
-        if (!colour_flow && (!flow_velocity.empty() || flow_packets || flow_prf || flow_wall || flow_avg || flow_vel_thr || flow_grey_max || flow_truth))
+        if (!spectral && (spectral_gate || spectral_pulses || spectral_fft || spectral_hop || spectral_db || flow_waveform || spectral_iq))
+            throw std::invalid_argument("--gate, --spectral-pulses, --spectral-fft, --spectral-hop, --spectral-db, --flow-waveform and --spectral-iq need --spectral");
+        if (spectral) {
+            if (compound_given || sweep_given || elevation_given || with_bands) throw std::invalid_argument("--spectral does not combine with --compound, --sweep, --elevation or the band options");
+            if (!spectral_gate) throw std::invalid_argument("--spectral needs --gate LINE,DEPTH_MM,LEN_MM");
+            if (flow_velocity.empty()) throw std::invalid_argument("--spectral needs --flow-velocity NAME:vx,vy,vz");
+            const auto g = comma_list<double>(spectral_gate);
+            if (g.size() != 3 || !(g[0] >= 0.0 && g[0] < (double)transducer_elements) || !(g[1] >= 0.0) || !(g[2] > 0.0))
+                throw std::invalid_argument("--gate takes LINE,DEPTH_MM,LEN_MM: a scan-line of the probe, a depth >= 0 and a length > 0");
+            gate_line = (uint32_t)g[0]; gate_depth_mm = g[1]; gate_len_mm = g[2];
+            if (spectral_pulses) spopts.n_pulses = (uint32_t)std::max(std::atol(spectral_pulses), 0l);
+            if (spectral_fft) spopts.n_fft = (uint32_t)std::max(std::atol(spectral_fft), 0l);
+            if (spectral_hop) spopts.hop = (uint32_t)std::max(std::atol(spectral_hop), 0l);
+            if (spectral_db) sgopts.dynamic_range_db = (float)std::atof(spectral_db);
+            float h[512];
+            if (spopts.n_fft > 512u || mcrt_spectral_window(1, spopts.n_fft, h) != MCRT_OK) throw std::invalid_argument("--spectral-fft: n_fft takes 32, 64, 128, 256 or 512");
+            if (spopts.n_pulses < spopts.n_fft || spopts.n_pulses > 16384u) throw std::invalid_argument("--spectral-pulses takes n_fft .. 16384 pulses");
+            if (spopts.hop < 1u || spopts.hop > spopts.n_fft) throw std::invalid_argument("--spectral-hop takes 1 .. n_fft pulses");
+            if (!(sgopts.dynamic_range_db > 0.0f)) throw std::invalid_argument("--spectral-db takes a dynamic range > 0");
+            if (flow_waveform) {
+                const auto w = comma_list<double>(flow_waveform);
+                if (w.size() != 3 || !(w[0] > 0.0)) throw std::invalid_argument("--flow-waveform takes BPM,PEAK,MIN: beats per minute > 0 and two speeds in mm/s");
+                wave_bpm = w[0]; wave_peak = w[1]; wave_min = w[2];
+            }
+            if (flow_prf) flopts.prf_hz = (float)std::atof(flow_prf);
+            double v_nyq = 0.0;
+            if (mcrt_flow_nyquist(&flopts, transducer_frequency, 1500.0, &v_nyq) != MCRT_OK) throw std::invalid_argument(std::string("--spectral: ") + mcrt_last_error());
+        }
+        if (!colour_flow && ((!spectral && (!flow_velocity.empty() || flow_prf)) || flow_packets || flow_wall || flow_avg || flow_vel_thr || flow_grey_max || flow_truth))
             throw std::invalid_argument("--flow-velocity, --flow-packets, --flow-prf-hz, --flow-wall, --flow-avg, --flow-vel-thr, --flow-grey-max and --flow-truth need --colour-flow");
         if (colour_flow) {
             if (compound_given || sweep_given || elevation_given || with_bands) throw std::invalid_argument("--colour-flow does not combine with --compound, --sweep, --elevation or the band options");
@@ -560,7 +609,9 @@ int main(int argc, char **argv)
         scene.step(1000.0f);
         rf_image_ rf_image{ dev, transducer_radius_cm * 10.0, transducer_amplitude };
         std::vector<float> flow_vel;                    // --flow-velocity: a vector per material of the scene
-        if (colour_flow) {
+        uint32_t spectral_material = 0;                 // --spectral: the material of the first --flow-velocity
+        if (colour_flow || spectral) {
+            spectral_material = scene.material_index(flow_velocity.front().substr(0, flow_velocity.front().find(':')));
             flow_vel.assign(3 * scene.material_names.size(), 0.0f);
             for (const std::string &item : flow_velocity) {
                 const size_t colon = item.find(':');
@@ -577,7 +628,7 @@ int main(int argc, char **argv)
             else if (compound_given) rf_image.trace((uint32_t)f, transducer, steers);               // ... in N steered views
             else if (elevation_given) rf_image.trace((uint32_t)f, transducer, psf, (uint32_t)elevation);   // ... in K elevation planes, folded
             else rf_image.trace((uint32_t)f);      // clear + cast_rays + accumulation (main.cpp:102-144)
-            if (colour_flow && f == frames - 1) rf_image.flow_split(transducer, flow_vel);   // the raw trace split by label, before the PSF
+            if ((colour_flow || spectral) && f == frames - 1) rf_image.flow_split(transducer, flow_vel);   // the raw trace split by label, before the PSF
             rf_image.convolve(psf);           // main.cpp:146
             if (noise) rf_image.add_noise(nopts, gain);   // the receiver's noise floor and dead elements, on whatever the convolution ran over
             if (iq_file && f == frames - 1) {            // the analytic pair of the last frame's RF, before it is detected
@@ -609,6 +660,38 @@ int main(int argc, char **argv)
                     std::ofstream out(flow_truth, std::ios::binary);
                     out.write((const char *)maps.truth.data(), (std::streamsize)(maps.truth.size() * sizeof(float)));
                     if (!out) throw std::runtime_error(std::string("cannot write ") + flow_truth);
+                }
+            }
+            if (spectral && f == frames - 1) {           // the sample gate's series, its spectra and the sonogram
+                double v_nyq = 0.0;
+                check(mcrt_flow_nyquist(&flopts, transducer_frequency, 1500.0, &v_nyq), "mcrt_flow_nyquist");
+                if (!colour_flow) rf_image.flow(psf, flopts, noise, detect ? &dopts : nullptr);     // (colour_flow() has detected the two parts already)
+                const uint32_t L = (uint32_t)scene.material_names.size(), R = (uint32_t)rf_image_::max_rows, m = spectral_material;
+                const double pitch = rf_image_::row_mm();
+                const uint32_t G = (uint32_t)std::min(std::max(std::nearbyint(gate_len_mm / pitch), 1.0), 64.0);
+                const uint32_t row0 = (uint32_t)std::min(std::max(std::nearbyint(gate_depth_mm / pitch - G / 2.0), 0.0), (double)(R - G));
+                spopts.gate_rows = G;
+                const double vx = flow_vel[3 * m], vy = flow_vel[3 * m + 1], vz = flow_vel[3 * m + 2], norm = std::sqrt((vx * vx + vy * vy) + vz * vz);
+                if (!(norm > 0.0)) throw std::invalid_argument("--spectral: the first --flow-velocity gives its material no velocity, so the flow has no direction");
+                const double ux = (float)(vx / norm), uy = (float)(vy / norm), uz = (float)(vz / norm);
+                const double dx = transducer.dir[3 * gate_line], dy = transducer.dir[3 * gate_line + 1], dz = transducer.dir[3 * gate_line + 2];
+                const double axial = std::min(std::max(0.0 - ((ux * dx + uy * dy) + uz * dz), -1.0), 1.0);
+                std::vector<uint8_t> moving(L, 0); moving[m] = 1;
+                const std::vector<uint8_t> line_labels = rf_image.tissue_line(gate_line);
+                std::vector<float> frac(G), speed(spopts.n_pulses);
+                std::vector<int32_t> rate(G);
+                std::vector<int64_t> phase(spopts.n_pulses);
+                check(mcrt_spectral_profile(line_labels.data(), R, row0, G, moving.data(), L, 2.0, frac.data()), "mcrt_spectral_profile");
+                check(mcrt_spectral_rates(frac.data(), G, axial, rate.data()), "mcrt_spectral_rates");
+                check(mcrt_pulse_waveform((double)flopts.prf_hz, wave_bpm, wave_peak < 0.0 ? norm : wave_peak, wave_min, spopts.n_pulses, speed.data()), "mcrt_pulse_waveform");
+                check(mcrt_spectral_phase(v_nyq, speed.data(), spopts.n_pulses, phase.data()), "mcrt_spectral_phase");
+                const std::vector<float> series = rf_image.spectral_series(gate_line, row0, spopts, rate, phase, noise);
+                const auto sp = rf_image.spectrum(spopts, v_nyq);
+                write_pgm(spectral, sp.n_cols, sp.n_fft, rf_image.sonogram(sgopts));
+                if (spectral_iq) {
+                    std::ofstream out(spectral_iq, std::ios::binary);
+                    out.write((const char *)series.data(), (std::streamsize)(series.size() * sizeof(float)));
+                    if (!out) throw std::runtime_error(std::string("cannot write ") + spectral_iq);
                 }
             }
         }

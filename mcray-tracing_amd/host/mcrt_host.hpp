@@ -5,7 +5,7 @@
 //   transducer<N>            transducer.h:24-137   (frequency MHz, radius cm, element separation mm, position, angles deg)
 //   psf<ax,lat,elev,res>     psf.h:34-77
 //   scene                    scene.h:19-76, scene.cpp:16-48,185-247 (JSON keys, "Error while loading scene: ..." wrapping)
-//   rf_image<cols,us,um>     rfimage.h:20-219      (clear / convolve / envelope / postprocess; data lives on the GPU); + detect / iq; + flow_split / flow / colour_flow
+//   rf_image<cols,us,um>     rfimage.h:20-219      (clear / convolve / envelope / postprocess; data lives on the GPU); + detect / iq; + flow_split / flow / colour_flow; + spectral_series / spectrum / sonogram
 //   ray_physics::segment     ray.h:28-36           (vec3 stands in for btVector3; `media` is held BY VALUE: the reference's
 //                                                   `const material &` dangles by the time main.cpp:126 reads it)
 //   volume<size,res>         volume.h:19-61        (host copy of the texture the GPU samples)
@@ -723,7 +723,7 @@ public:
 
     rf_image(double radius_mm, double angle_rad, std::shared_ptr<device> dev_ = nullptr)
         : dev(dev_ ? std::move(dev_) : default_device()), radius_mm(radius_mm), angle(angle_rad), host((size_t)columns * max_rows, 0.0f),
-          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev), sound(dev), sigma(dev), curve(dev), band_stack(dev), flow_in(dev), flow_out(dev)
+          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev), sound(dev), sigma(dev), curve(dev), band_stack(dev), flow_in(dev), flow_out(dev), spectral_buf(dev)
     {
         std::cout << "rf_image: " << max_rows << ", " << columns << std::endl;          // rfimage.h:30
         rf.reserve(sizeof(float) * columns * max_rows);
@@ -927,7 +927,7 @@ public:
         std::vector<uint8_t> moving(L);
         for (uint32_t l = 0; l < L; l++) moving[l] = vel_mm_s[3 * l] != 0.0f || vel_mm_s[3 * l + 1] != 0.0f || vel_mm_s[3 * l + 2] != 0.0f;
         check(mcrt_flow_split_frames(dev->ctx, rf.as<float>(), flow_tissue(), 1, columns, max_rows, moving.data(), L, flow_in.as<float>()), "mcrt_flow_split_frames");
-        flow_vel = vel_mm_s; flow_dir = t.dir; flow_frequency = (double)t.frequency;
+        flow_vel = vel_mm_s; flow_dir = t.dir; flow_frequency = (double)t.frequency; flow_detected = false; spectral_T = spectral_cols = 0;
     }
     // the colour processor in beam space: the two parts through p's PSF and the detector's I/Q (dopts: null = 31 taps), then mcrt_flow_frames.
     // noise_sigma: the ensemble's sigma is the one add_noise() left on the device for this pass (it throws when it has not run), else
@@ -956,6 +956,7 @@ public:
         check(mcrt_flow_frames(dev->ctx, pairs, pairs + 2 * n, flow_tissue(), 1, columns, max_rows, &fo, m.v_nyq_mm_s, phasor.data(), truth.data(), L, first_id,
                                noise_sigma ? sigma.as<float>() : nullptr, corr, vel, var, tr), "mcrt_flow_frames");
         m.vel = download<float>(vel, n); m.var = download<float>(var, n); m.truth = download<float>(tr, n);
+        flow_detected = true;
         m.sigma = noise_sigma ? (double)download<float>(sigma.as<float>(), 1)[0] : (double)fo.sigma;
         return m;
     }
@@ -980,6 +981,67 @@ public:
         rgb = download<unsigned char>(out, 3 * np);
         if (velocity) *velocity = download<float>(vimg, np);
         return m;
+    }
+    // spectral Doppler (mcrt.h: mcrt_spectral_series_frames, mcrt_spectral_frames, mcrt_sonogram_frames), three steps after flow() or
+    // colour_flow(), which leave the detected pairs of what stands still and what moves on the device:
+    //   ...;  flow(p, fo);  tissue_line(line);  spectral_series(line, row0, so, rate, phase);  spectrum(so, v_nyq);  sonogram(go);
+    // the tissue labels [max_rows] of one scan-line of the last flow_split(), for mcrt_spectral_profile
+    std::vector<uint8_t> tissue_line(uint32_t line)
+    {
+        if (flow_vel.empty() || line >= columns) throw std::logic_error("rf_image::tissue_line: flow_split() first, and a scan-line of this image");
+        return download<uint8_t>(flow_tissue() + (size_t)line * max_rows, max_rows);
+    }
+    // the slow-time series [T][2] of ONE gate -- rows row0 .. row0 + so.gate_rows - 1 of scan-line `line`, every row's weight 1 -- from rate
+    // [gate_rows] (mcrt_spectral_rates) and phase [T] (mcrt_spectral_phase).  noise_sigma as in flow().  It stays on the device for spectrum()
+    std::vector<float> spectral_series(uint32_t line, uint32_t row0, const mcrt_spectral_opts &so, const std::vector<int32_t> &rate, const std::vector<int64_t> &phase,
+                                       bool noise_sigma = false)
+    {
+        if (!flow_detected) throw std::logic_error("rf_image::spectral_series: flow() or colour_flow() first: they detect the two parts");
+        if (noise_sigma && sigma_frames != 1) throw std::logic_error("rf_image::spectral_series: noise_sigma needs add_noise() on the same pass");
+        if (rate.size() != so.gate_rows || phase.size() != so.n_pulses) throw std::invalid_argument("rf_image::spectral_series: rate [gate_rows] and phase [n_pulses]");
+        const size_t n = (size_t)columns * max_rows, T = so.n_pulses;
+        spectral_buf.reserve(8 * T);
+        const float *pairs = flow_in.as<float>() + 2 * n;
+        const mcrt_gate gate{ 0u, line, row0 };
+        const std::vector<float> weight(so.gate_rows, 1.0f);
+        spectral_cols = 0;
+        check(mcrt_spectral_series_frames(dev->ctx, pairs, pairs + 2 * n, 1, columns, max_rows, &gate, 1, weight.data(), rate.data(), phase.data(), &so, first_id,
+                                          noise_sigma ? sigma.as<float>() : nullptr, spectral_buf.as<float>()), "mcrt_spectral_series_frames");
+        spectral_T = (uint32_t)T;
+        return download<float>(spectral_buf.as<float>(), 2 * T);
+    }
+    // the spectra of the last spectral_series(): power [n_cols][n_fft] in velocity order and the mean velocity [n_cols]; window_kind:
+    // mcrt_spectral_window's (1: Hann).  The power stays on the device for sonogram()
+    struct spectra { std::vector<float> power, mean; uint32_t n_cols = 0, n_fft = 0; };
+    spectra spectrum(const mcrt_spectral_opts &so, double v_nyq_mm_s, uint32_t window_kind = 1)
+    {
+        if (!spectral_T || spectral_T != so.n_pulses) throw std::logic_error("rf_image::spectrum: spectral_series() with the same options first");
+        std::vector<float> h(so.n_fft >= 32 && so.n_fft <= 512 ? so.n_fft : 512);
+        check(mcrt_spectral_window(window_kind, so.n_fft, h.data()), "mcrt_spectral_window");
+        if (so.hop == 0 || so.n_pulses < so.n_fft) throw std::invalid_argument("rf_image::spectrum: hop >= 1 and n_pulses >= n_fft");
+        spectra out;
+        out.n_fft = so.n_fft; out.n_cols = (so.n_pulses - so.n_fft) / so.hop + 1u;
+        const size_t T = so.n_pulses, np = (size_t)out.n_cols * so.n_fft;
+        {   // the series moves into a buffer with room for the spectra, their means and the picture behind it (growing forgets)
+            const std::vector<float> z = download<float>(spectral_buf.as<float>(), 2 * T);
+            spectral_buf.reserve(8 * T + 4 * np + 4 * out.n_cols + np);
+            check(mcrt_memcpy_h2d(dev->ctx, spectral_buf.as<float>(), z.data(), 8 * T), "mcrt_memcpy_h2d");
+        }
+        float *power = spectral_buf.as<float>() + 2 * T, *mean = power + np;
+        check(mcrt_spectral_frames(dev->ctx, spectral_buf.as<float>(), 1, h.data(), &so, v_nyq_mm_s, power, mean), "mcrt_spectral_frames");
+        out.power = download<float>(power, np); out.mean = download<float>(mean, out.n_cols);
+        spectral_cols = out.n_cols; spectral_N = so.n_fft;
+        return out;
+    }
+    // the picture of the last spectrum(), bytes [n_fft][n_cols], row 0 the highest velocity towards the probe
+    std::vector<unsigned char> sonogram(const mcrt_sonogram_opts &go)
+    {
+        if (!spectral_cols) throw std::logic_error("rf_image::sonogram: spectrum() first");
+        const size_t T = spectral_T, np = (size_t)spectral_cols * spectral_N;
+        float *power = spectral_buf.as<float>() + 2 * T;
+        uint8_t *grey = reinterpret_cast<uint8_t *>(power + np + spectral_cols);
+        check(mcrt_sonogram_frames(dev->ctx, power, 1, spectral_cols, spectral_N, &go, nullptr, grey), "mcrt_sonogram_frames");
+        return download<unsigned char>(grey, np);
     }
     // receiver noise (mcrt.h: mcrt_noise_frames): a noise floor and a gain per scan-line (element_gain: [columns] or null) over whatever the
     // last trace() filled, in place -- this image, or the views of a compounded frame or the planes of a sweep as ONE frame (one receiver,
@@ -1347,6 +1409,9 @@ private:
     device_buffer band_stack;                    // convolve(p) with p.has_bands(): the band images [images][B][columns][max_rows] (grown, never shrunk)
     device_buffer flow_in, flow_out;             // flow_split() / flow(): tissue, the two parts and their I/Q pairs; the correlation, vel, var, truth and the gathered pictures
     std::vector<float> flow_vel, flow_dir;       // flow_split()'s velocities and scan-line directions, for flow()'s phasors
+    bool flow_detected = false;                  // flow() has left the two parts' I/Q pairs in flow_in since the last flow_split()
+    device_buffer spectral_buf;                  // spectral_series() / spectrum() / sonogram(): the series [T][2], then power [n_cols][N], mean [n_cols] and the bytes
+    uint32_t spectral_T = 0, spectral_cols = 0, spectral_N = 0;   // ... the shapes of what it holds (0: nothing yet)
     uint32_t banded = 0;                         // ... B while they wait there for envelope() / fold_bands() (0: the images are where trace() left them)
     std::vector<float> band_w;                   // ... and the bands' weights [max_rows][B] they are folded with
     uint32_t sound_planes = 0;                   // ... their leading axis (nothing yet: 0)
