@@ -79,7 +79,11 @@ extern "C" {
                                    mcrt_spectral_rates, mcrt_spectral_window, mcrt_spectral_twiddles, mcrt_spectral_draws, mcrt_pulse_waveform,
                                    mcrt_spectral_series_frames, mcrt_spectral_frames, mcrt_sonogram_opts, mcrt_default_sonogram_opts, mcrt_sonogram_frames
                                    (spectral Doppler: a sample gate's slow-time series under a pulsatile waveform and a velocity profile, its short-time
-                                   FFT and the sonogram; additive) */
+                                   FFT and the sonogram; additive);
+                                   + mcrt_strain_opts, mcrt_default_strain_opts, mcrt_strain_table, mcrt_strain_draws, mcrt_strain_map,
+                                   mcrt_strain_compress_frames, mcrt_strain_frames, mcrt_elastogram_opts, mcrt_default_elastogram_opts, mcrt_elastogram_frames
+                                   (strain elastography: a quasi-static compression synthesised from one traced frame, speckle tracking by normalised
+                                   cross-correlation, the strain, its ground truth and the elastogram; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -1483,6 +1487,128 @@ typedef struct { float dynamic_range_db; float gain_db; float ref; } mcrt_sonogr
 int mcrt_default_sonogram_opts(mcrt_sonogram_opts *o);
 int mcrt_sonogram_frames(mcrt_ctx *ctx, const float *power_dev /* [n_gates][n_cols][N] */, uint32_t n_gates, uint32_t n_cols, uint32_t n_fft,
                          const mcrt_sonogram_opts *o, float *peak_dev /* [n_gates] or NULL */, uint8_t *out_dev /* [n_gates][N][n_cols] */);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Strain elastography: quasi-static strain imaging compares a scan-line's analytic signal before and after a slight compression by
+ * the probe; stiff tissue strains less than soft tissue.  The reference has no counterpart.  THE MODEL is synthesised from ONE traced
+ * frame, as the Doppler ensembles are and for the same reason (a second trace has another Philox key and decorrelates completely).
+ * COMPRESSION: every scan-line is a column of springs in series under one stress; the caller gives a Young's modulus per material, a
+ * row's strain is applied * ref_modulus / modulus[label], the displacement U is the running sum of the strains down the line, and the
+ * post-compression line is the pre-compression ANALYTIC line (mcrt_detect_frames' iq_dev) read at q + U(q) by a linear interpolation of
+ * its baseband: each of the two neighbouring samples is first turned by the carrier phase of its fractional offset (a plain linear
+ * interpolation at 0.3475 cycles per row would lose up to half the amplitude).  Optional receiver noise on the post frame is the only
+ * other decorrelation.  TRACKING: per sample the complex cross-correlation of a window of the pre line with the post line at the
+ * integer lags -L .. L; the lag of the largest normalised magnitude wins, the sub-sample part is the PHASE of the winning correlation
+ * over 2 pi carrier (the phase-sensitive estimator scanners use at low sampling rates), and the strain is the least-squares slope of
+ * the displacement over a row window.  Displacements are integers in Q24 rows and phases integers in 2^-32 turn, so the device and any
+ * mirror agree whatever the order.  Past about 2 % of strain the estimator degrades, as a real one does (the window decorrelates and at
+ * 3 % a search of 16 rows loses lock); the table caps a row's strain at 1/32.
+ * LEFT OUT: lateral and elevational motion; stress decay and stress concentration (the model is one-dimensional); a rigid compressor
+ * plate (each scan-line takes its own total displacement); guided or multi-level search; lateral averaging of the correlation;
+ * shear-wave methods; the strain ratio as a call; elastograms of swept, compounded, elevation-summed or banded frames.
+ * An opt-in chain; without it no call and no bit changes.
+ *
+ * Throughout, every float operation is rounded once: no fma, correctly rounded / and sqrtf, no device transcendental; every sum
+ * ascends from 0.0f. */
+typedef struct {
+    uint32_t window_rows;   /* a, the half-window of the cross-correlation: 0..32; default 16 */
+    uint32_t search_rows;   /* L, the largest lag searched: 0..16; default 8 */
+    uint32_t lsq_rows;      /* g, the half-window of the least-squares slope: 1..32; default 12 */
+    float sigma;            /* the receiver noise per I/Q component of the post frame, finite and >= 0, used when no sigma_dev is given; default 0 */
+    uint32_t seed;          /* Philox key word 0 of the noise stream; default 0x5354524E */
+} mcrt_strain_opts;         /* 20 bytes */
+/* the defaults above.  MCRT_ERR_INVALID for a null o.  Host only. */
+int mcrt_default_strain_opts(mcrt_strain_opts *o);
+/* the strain of every material in Q24, in double:
+ *   eps_q24[l] = modulus[l] == 0 ? 0 : llrint(applied * ref_modulus / modulus[l] * 16777216.0)
+ * A modulus of exactly 0 is rigid (strain 0); a negative `applied` is a decompression.  Host only.  MCRT_ERR_INVALID for a null
+ * pointer, n_labels == 0, an applied or a modulus that is not finite, a modulus < 0, a ref_modulus that is not finite and > 0, or an
+ * |eps_q24[l]| above 2^19 (a strain above 1/32); MCRT_ERR_LIMIT for n_labels > 254; on an error nothing is written. */
+int mcrt_strain_table(const double *modulus /* [n_labels] */, uint32_t n_labels, double applied, double ref_modulus, int32_t *eps_q24 /* [n_labels] */);
+/* the integer noise draws of one post-compression image, d[e][r][0..1] (I, Q): one Philox4x32-10 block per sample with the counter
+ * (e, r, 0x5354524E, 0) and the key (seed, image_id); d_I and d_Q are mcrt_flow_draws' Irwin-Hall sums of o0, o1 and o2, o3, with the
+ * same inv_std = (float)(1.0 / sqrt(1431655765.0)).  Counter word 2 differs from the tracer's (< 16), mcrt_noise_frames' (0x4E4F4953),
+ * mcrt_flow_frames' (0x464C4F57) and mcrt_spectral_series_frames' (0x53504543).  Host only.  MCRT_ERR_INVALID for a null d or zero
+ * sizes; MCRT_ERR_LIMIT for n_rows > 2048. */
+int mcrt_strain_draws(uint32_t seed, uint32_t image_id, uint32_t n_elements, uint32_t n_rows, int32_t *d /* [E][R][2] */);
+/* the colour table of the elastogram, lut[i] = (r, g, b), i = 128 the reference strain.  kind 0, stiff blue through green to soft red,
+ * in integer arithmetic:
+ *   i = 0..128:     u = min(255, 2 i);      (0, u, 255 - u)              blue (no strain) to green (the reference strain)
+ *   i = 129..255:   u = 2 (i - 128);        (u, 255 - u, 0)              green to red (twice the reference strain)
+ * Host only.  MCRT_ERR_INVALID for a null lut or another kind.  (mcrt_colour_map keeps its one kind.) */
+int mcrt_strain_map(uint32_t kind, uint8_t *lut /* [256][3] */);
+/* THE COMPRESSION.  iq_dev [F][E][R][2] is mcrt_detect_frames' iq_dev, tissue_dev [F][E][R] mcrt_label_frames' labels, eps_q24
+ * [n_labels] mcrt_strain_table's (or the caller's own, |eps| <= 2^19), carrier_q32 = llrint(cycles_per_row * 4294967296.0) with
+ * cycles_per_row in (0, 0.5] (mcrt_psf_carrier's), lut mcrt_spectral_rotor's table.  With eps(l) = l < n_labels ? eps_q24[l] : 0
+ * (MCRT_LABEL_NONE and any label past the table do not strain), per scan-line (f, e) and row q, pre = iq_dev[f][e]:
+ *   U[0] = 0;   U[q] = U[q-1] + eps(tissue[q-1])                                   (int32: |U| < 2^30)
+ *   s = ((int64)q << 24) + U[q];   s0 = s >> 24 (an arithmetic shift);   fr = s & 0xFFFFFF
+ *   A = 0 <= s0 < R ? pre[s0] : (+0.0f, +0.0f);      B = 0 <= s0 + 1 < R ? pre[s0 + 1] : (+0.0f, +0.0f)
+ *   w1 = (float)fr * 0x1p-24f (exact);   w0 = 1.0f - w1
+ *   th0 = (uint32_t)((carrier_q32 * (int64)fr) >> 24);   th1 = (uint32_t)((carrier_q32 * ((int64)fr - (1 << 24))) >> 24)     (arithmetic shifts)
+ *   (c, s) = lut[((th + 0x80000u) >> 20) & 4095];    turn(z, th) = (z.re * c - z.im * s, z.re * s + z.im * c)   (four products, one subtraction, one addition)
+ *   post[q] = (w0 * turn(A, th0) + w1 * turn(B, th1)) + k * (float)d[e][q]           per component: two products, their sum, then the noise
+ * with k = sigma_f * inv_std, sigma_f = sigma_dev ? sigma_dev[f] : o->sigma, and d mcrt_strain_draws' of (o->seed, first_image_id + f).
+ * At k == 0 the noise term is skipped and no Philox block is computed.  With all strains 0 and k == 0, post equals pre wherever pre is
+ * finite (fr = 0: the rotor is (1, 0), w1 * B = 0).  The outputs, each a device pointer or NULL, at least one given:
+ *   post_iq_dev [F][E][R][2]     the post-compression pairs
+ *   truth_disp_dev [F][E][R]     (float)U[q] * 0x1p-24f     the true displacement in rows, positive: the sample is read from deeper down
+ *   truth_strain_dev [F][E][R]   (float)eps(tissue[q]) * 0x1p-24f
+ * eps_q24 is a HOST table, free when the call returns; it lives in a buffer of the context and is copied only when it differs from
+ * what is there (o->window_rows, search_rows and lsq_rows are checked and not read).  Every element of every output given is written;
+ * the inputs are read only.  Asynchronous on the context's stream.  MCRT_ERR_INVALID for a null ctx, iq_dev, tissue_dev, eps_q24 or o,
+ * zero sizes, n_labels == 0, a cycles_per_row outside (0, 0.5], options out of range, an |eps_q24[l]| above 2^19, no output, an output
+ * that overlaps an input or another output; MCRT_ERR_LIMIT for n_rows > 2048, n_labels > 254, a stack of 2^31 samples or more, image
+ * ids that pass 2^32; on any error nothing is launched and nothing is written.  Groups: call it on mcrt_group_root(). */
+int mcrt_strain_compress_frames(mcrt_ctx *ctx, const float *iq_dev /* [F][E][R][2] */, const uint8_t *tissue_dev /* [F][E][R] */, uint32_t n_frames,
+                                uint32_t n_elements, uint32_t n_rows, const int32_t *eps_q24 /* [n_labels] */, uint32_t n_labels, double cycles_per_row,
+                                const mcrt_strain_opts *o, uint32_t first_image_id, const float *sigma_dev /* [F] or NULL */,
+                                float *post_iq_dev /* [F][E][R][2] or NULL */, float *truth_disp_dev /* [F][E][R] or NULL */,
+                                float *truth_strain_dev /* [F][E][R] or NULL */);
+/* THE TRACKER.  pre and post are the two stacks of pairs [F][E][R][2], a = o->window_rows, L = o->search_rows, g = o->lsq_rows.  Per
+ * scan-line and row r, with the window offsets i = -a .. a ascending and every sum from 0.0f:
+ *   e1 = sum over i, row r + i inside [0, R), of (pre[r+i].re * pre[r+i].re + pre[r+i].im * pre[r+i].im)
+ *   P[q] = the same sum of post about row q (rows q + i inside [0, R)); the energy at lag k is P[r + k]
+ *   c_k = sum over i, rows r + i AND r + i + k inside [0, R), of post[r+i+k] * conj(pre[r+i]):
+ *         re += (a * c + b * d),  im += (b * c - a * d)   with post[r+i+k] = (a, b), pre[r+i] = (c, d)   (the products before the sums)
+ *   rho2_k = (c_k.re * c_k.re + c_k.im * c_k.im) / (e1 * P[r + k])
+ * THE LAG.  The best candidate starts as k = 0; then k = -1, +1, -2, +2, ..., -L, +L are visited in this order, a candidate whose row
+ * r + k lies outside [0, R) is skipped, and a candidate replaces the best only when its rho2 is strictly greater.  A NaN never
+ * compares greater: it never wins, and a NaN at lag 0 stays (the outputs of such a sample are those of c_0).
+ * THE OUTPUTS, each a device pointer or NULL, at least one given, all [F][E][R]:
+ *   disp_dev     mcrt_det_atan2f(c_k.im, c_k.re) * (float)(1.0 / (6.283185307179586 * cycles_per_row)) - (float)k       of the best k, in rows;
+ *                positive is compression: the U of mcrt_strain_compress_frames
+ *   rho_dev      sqrtf(rho2_k), the correlation coefficient of the best k
+ *   strain_dev   with j_lo = max(0, r - g), j_hi = min(R - 1, r + g) and t_j = (float)(2 j - (j_lo + j_hi)):
+ *                (2.0f * (sum over j = j_lo .. j_hi of t_j * disp[j])) / (sum of t_j * t_j),   +0.0f where j_lo == j_hi
+ * A zero window (e1 * P == 0) gives rho NaN and disp from c_0.  Without a disp_dev the displacement lives in a grow-only buffer of the
+ * context: nothing is allocated after the first call at a size.  The inputs are read only; every element of every output given is
+ * written.  Asynchronous on the context's stream.  MCRT_ERR_INVALID for a null ctx, pre_iq_dev, post_iq_dev or o, zero sizes, options
+ * out of range, a cycles_per_row outside (0, 0.5], no output, an output that overlaps an input or another output; MCRT_ERR_LIMIT for
+ * n_rows > 2048 or a stack of 2^31 samples or more; on any error nothing is launched and nothing is written.  Groups: on
+ * mcrt_group_root(). */
+int mcrt_strain_frames(mcrt_ctx *ctx, const float *pre_iq_dev /* [F][E][R][2] */, const float *post_iq_dev /* [F][E][R][2] */, uint32_t n_frames,
+                       uint32_t n_elements, uint32_t n_rows, const mcrt_strain_opts *o, double cycles_per_row, float *disp_dev /* [F][E][R] or NULL */,
+                       float *rho_dev /* [F][E][R] or NULL */, float *strain_dev /* [F][E][R] or NULL */);
+/* THE ELASTOGRAM.  strain_img_dev and rho_img_dev [F][H][W] are mcrt_strain_frames' strain_dev and rho_dev through
+ * mcrt_scan_convert_frames, grey_dev [F][H][W] the bytes of mcrt_bmode_frames.  Per pixel, with g the grey byte:
+ *   x = strain / ref_strain;   t = rintf(x * 128.0f);   idx = t < 0 ? 0 : t > 255 ? 255 : (int)t
+ *   show = x == x && rho >= rho_min && g >= grey_min                                  (a NaN anywhere: not shown)
+ *   rgb_dev[f][y][x][ch] = show ? (g * (256 - alpha) + lut[idx][ch] * alpha + 128) >> 8 : g
+ * lut [256][3] is HOST memory (mcrt_strain_map's or the caller's own), free when the call returns.  Asynchronous on the context's
+ * stream.  MCRT_ERR_INVALID for a null pointer, zero sizes, a ref_strain that is not finite or is 0, a rho_min that is not finite,
+ * grey_min > 255, alpha > 256, an rgb_dev that overlaps an input; MCRT_ERR_LIMIT for 2^31 pixels or more; on any error nothing is
+ * launched.  Groups: call it on mcrt_group_root(). */
+typedef struct {
+    float ref_strain;       /* the strain shown as the table's middle (green), finite and not 0; default 0.01 */
+    float rho_min;          /* pixels with a smaller correlation coefficient stay grey; default 0.7 */
+    uint32_t grey_min;      /* pixels with a darker B-mode byte stay grey: 0..255; default 0 */
+    uint32_t alpha;         /* the colour's share in 1/256: 0..256; default 160 */
+} mcrt_elastogram_opts;     /* 16 bytes */
+int mcrt_default_elastogram_opts(mcrt_elastogram_opts *o);
+int mcrt_elastogram_frames(mcrt_ctx *ctx, const float *strain_img_dev /* [F][H][W] */, const float *rho_img_dev /* [F][H][W] */,
+                           const uint8_t *grey_dev /* [F][H][W] */, uint32_t n_frames, uint32_t height, uint32_t width, const uint8_t *lut /* [256][3] */,
+                           const mcrt_elastogram_opts *o, uint8_t *rgb_dev /* [F][H][W][3] */);
 
 /* device [E][R]  ->  host [R][E] row-major (the cv::Mat layout of rfimage.h:217); synchronous */
 int mcrt_export_rf(mcrt_ctx *ctx, const float *rf_dev, uint32_t n_elements, uint32_t n_rows, float *host_rows_by_cols);

@@ -96,6 +96,16 @@ class SonogramOpts(C.Structure):
     _fields_ = [("dynamic_range_db", C.c_float), ("gain_db", C.c_float), ("ref", C.c_float)]
 
 
+class StrainOpts(C.Structure):
+    """mcrt_strain_opts (include/mcrt.h): 20 bytes"""
+    _fields_ = [("window_rows", C.c_uint32), ("search_rows", C.c_uint32), ("lsq_rows", C.c_uint32), ("sigma", C.c_float), ("seed", C.c_uint32)]
+
+
+class ElastogramOpts(C.Structure):
+    """mcrt_elastogram_opts (include/mcrt.h): 16 bytes"""
+    _fields_ = [("ref_strain", C.c_float), ("rho_min", C.c_float), ("grey_min", C.c_uint32), ("alpha", C.c_uint32)]
+
+
 class Compound(C.Structure):
     """mcrt_compound (include/mcrt.h): 68 bytes, steer_rad at offset 4"""
     _fields_ = [("n_views", C.c_uint32), ("steer_rad", C.c_float * 16)]
@@ -181,6 +191,7 @@ assert C.sizeof(ReconLabelOpts) == 12 and C.sizeof(AutogainOpts) == 24 and C.siz
 assert C.sizeof(Bands) == 80 and Bands.band_weight.offset == 36 and Bands.var_x.offset == 68 and Bands.min_mhz.offset == 76 and C.sizeof(DetectOpts) == 4
 assert C.sizeof(FlowOpts) == 32 and FlowOpts.prf_hz.offset == 16 and FlowOpts.seed.offset == 28 and C.sizeof(ColourOpts) == 12
 assert C.sizeof(SpectralOpts) == 32 and SpectralOpts.sigma.offset == 24 and C.sizeof(Gate) == 12 and C.sizeof(SonogramOpts) == 12
+assert C.sizeof(StrainOpts) == 20 and StrainOpts.sigma.offset == 12 and C.sizeof(ElastogramOpts) == 16 and ElastogramOpts.grey_min.offset == 8
 
 # every symbol include/mcrt.h declares (tests/test_abi.py checks the .so exports each one)
 SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create", "mcrt_destroy", "mcrt_set_stream",
@@ -210,6 +221,8 @@ SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create"
            "mcrt_default_spectral_opts", "mcrt_spectral_rotor", "mcrt_spectral_phase", "mcrt_spectral_profile", "mcrt_spectral_rates", "mcrt_spectral_window",
            "mcrt_spectral_twiddles", "mcrt_spectral_draws", "mcrt_pulse_waveform", "mcrt_spectral_series_frames", "mcrt_spectral_frames",
            "mcrt_default_sonogram_opts", "mcrt_sonogram_frames",
+           "mcrt_default_strain_opts", "mcrt_strain_table", "mcrt_strain_draws", "mcrt_strain_map", "mcrt_strain_compress_frames", "mcrt_strain_frames",
+           "mcrt_default_elastogram_opts", "mcrt_elastogram_frames",
            "mcrt_default_recon_opts", "mcrt_recon_transform", "mcrt_recon_frames",
            "mcrt_default_recon_label_opts", "mcrt_recon_label_frames", "mcrt_render_label_frames"]
 
@@ -327,6 +340,14 @@ def load_library():
         "mcrt_spectral_frames": [vp, vp, u32, vp, C.POINTER(SpectralOpts), C.c_double, vp, vp],
         "mcrt_default_sonogram_opts": [C.POINTER(SonogramOpts)],
         "mcrt_sonogram_frames": [vp, vp, u32, u32, u32, C.POINTER(SonogramOpts), vp, vp],
+        "mcrt_default_strain_opts": [C.POINTER(StrainOpts)],
+        "mcrt_strain_table": [vp, u32, C.c_double, C.c_double, vp],
+        "mcrt_strain_draws": [u32, u32, u32, u32, vp],
+        "mcrt_strain_map": [u32, vp],
+        "mcrt_strain_compress_frames": [vp, vp, vp, u32, u32, u32, vp, u32, C.c_double, C.POINTER(StrainOpts), u32, vp, vp, vp, vp],
+        "mcrt_strain_frames": [vp, vp, vp, u32, u32, u32, C.POINTER(StrainOpts), C.c_double, vp, vp, vp],
+        "mcrt_default_elastogram_opts": [C.POINTER(ElastogramOpts)],
+        "mcrt_elastogram_frames": [vp, vp, vp, vp, u32, u32, u32, vp, C.POINTER(ElastogramOpts), vp],
         "mcrt_default_recon_opts": [C.POINTER(ReconOpts)],
         "mcrt_recon_transform": [C.POINTER(VolumeGrid), C.c_double, vp, vp],
         "mcrt_recon_frames": [vp, vp, u32, u32, u32, vp, vp, C.c_double, C.c_double, C.POINTER(VolumeGrid), C.POINTER(ReconOpts), vp, vp, vp],

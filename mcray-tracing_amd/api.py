@@ -12,7 +12,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Bands, DetectOpts, FlowOpts, ColourOpts, SpectralOpts, Gate, SonogramOpts, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, Speckle3dOpts, NoiseOpts, AutogainOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Bands, DetectOpts, FlowOpts, ColourOpts, SpectralOpts, Gate, SonogramOpts, StrainOpts, ElastogramOpts, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, Speckle3dOpts, NoiseOpts, AutogainOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 DEFAULT_ANGLE = 1.0471975511965976      # the sector of main.cpp:28: 60 degrees [rad]
 
@@ -304,6 +304,55 @@ def host_pulse_waveform(prf_hz, beats_per_min, v_peak, v_min, n_pulses):
     s = np.zeros(min(max(int(n_pulses), 0), 16384), np.float32)
     check(load_library().mcrt_pulse_waveform(float(prf_hz), float(beats_per_min), float(v_peak), float(v_min), n_pulses, ptr(s)))
     return s
+
+
+def strain_opts_struct(window_rows=None, search_rows=None, lsq_rows=None, sigma=None, seed=None):
+    """mcrt_strain_opts from keywords over mcrt_default_strain_opts: window_rows (0..32; 16), search_rows (0..16; 8), lsq_rows (1..32; 12),
+    sigma (0), seed -- the library checks the ranges"""
+    o = StrainOpts()
+    check(load_library().mcrt_default_strain_opts(C.byref(o)))
+    for name, v in (("window_rows", window_rows), ("search_rows", search_rows), ("lsq_rows", lsq_rows), ("seed", seed)):
+        if v is not None:
+            setattr(o, name, int(v) & 0xFFFFFFFF)
+    if sigma is not None:
+        o.sigma = float(sigma)
+    return o
+
+
+def elastogram_opts_struct(ref_strain=None, rho_min=None, grey_min=None, alpha=None):
+    """mcrt_elastogram_opts from keywords over mcrt_default_elastogram_opts (0.01, 0.7, 0, 160)"""
+    o = ElastogramOpts()
+    check(load_library().mcrt_default_elastogram_opts(C.byref(o)))
+    for name, v in (("ref_strain", ref_strain), ("rho_min", rho_min)):
+        if v is not None:
+            setattr(o, name, float(v))
+    for name, v in (("grey_min", grey_min), ("alpha", alpha)):
+        if v is not None:
+            setattr(o, name, int(v) & 0xFFFFFFFF)
+    return o
+
+
+def host_strain_table(modulus, applied=0.01, ref_modulus=1.0):
+    """mcrt_strain_table: the strain of every material in Q24, int32 [n_labels], of a Young's modulus per material (0: rigid), the applied
+    strain of the reference modulus and that modulus"""
+    m = np.ascontiguousarray(modulus, np.float64).reshape(-1)
+    eps = np.zeros(min(m.size, 254), np.int32)
+    check(load_library().mcrt_strain_table(ptr(m), m.size, float(applied), float(ref_modulus), ptr(eps)))
+    return eps
+
+
+def host_strain_draws(seed, image_id, n_elements, n_rows):
+    """mcrt_strain_draws: the integer draws of one post-compression image, int32 [n_elements][n_rows][2] (noise = d * sigma / sqrt(1431655765))"""
+    d = np.zeros((max(int(n_elements), 0), min(max(int(n_rows), 0), 2048), 2), np.int32)
+    check(load_library().mcrt_strain_draws(int(seed) & 0xFFFFFFFF, int(image_id) & 0xFFFFFFFF, n_elements, n_rows, ptr(d)))
+    return d
+
+
+def host_strain_map(kind=0):
+    """mcrt_strain_map: the colour table of the elastogram, uint8 [256][3] (kind 0: stiff blue, the reference strain green at 128, soft red)"""
+    lut = np.zeros((256, 3), np.uint8)
+    check(load_library().mcrt_strain_map(int(kind) & 0xFFFFFFFF, ptr(lut)))
+    return lut
 
 
 def row_pitch_mm(frequency):
@@ -1246,6 +1295,36 @@ class Context(_SceneCalls):
         o = sonogram_opts_struct(**opts)
         check(self.L.mcrt_sonogram_frames(self.h, ptr(power_dev), n_gates, n_cols, n_fft, C.byref(o), ptr(peak_dev), ptr(out_dev)))
 
+    def strain_compress_frames(self, iq_dev, tissue_dev, n_frames, n_elements, n_rows, eps_q24, cycles_per_row, first_image_id=0, sigma_dev=None,
+                               post_iq_dev=None, truth_disp_dev=None, truth_strain_dev=None, opts=None, **kw):
+        """mcrt_strain_compress_frames: the post-compression pairs of every scan-line from the detected pairs [n_frames][E][R][2] and the
+        tissue labels [n_frames][E][R].  eps_q24: int32 [n_labels], a host table (host_strain_table); cycles_per_row: host_psf_carrier's.
+        Outputs, each a device pointer or None: post_iq_dev [n_frames][E][R][2], truth_disp_dev and truth_strain_dev [n_frames][E][R].
+        opts: a StrainOpts, or the keywords of strain_opts_struct"""
+        o = opts if opts is not None else strain_opts_struct(**kw)
+        eps = np.ascontiguousarray(eps_q24, np.int32).reshape(-1)
+        check(self.L.mcrt_strain_compress_frames(self.h, ptr(iq_dev), ptr(tissue_dev), n_frames, n_elements, n_rows, ptr(eps), eps.size, float(cycles_per_row),
+                                                 C.byref(o), first_image_id, ptr(sigma_dev), ptr(post_iq_dev), ptr(truth_disp_dev), ptr(truth_strain_dev)))
+
+    def strain_frames(self, pre_iq_dev, post_iq_dev, n_frames, n_elements, n_rows, cycles_per_row, disp_dev=None, rho_dev=None, strain_dev=None, opts=None, **kw):
+        """mcrt_strain_frames: speckle tracking between the two stacks of pairs [n_frames][E][R][2] -> disp_dev (rows, positive: compression),
+        rho_dev (the correlation coefficient) and strain_dev (the least-squares slope of the displacement), each [n_frames][E][R] or None.
+        opts: a StrainOpts, or the keywords of strain_opts_struct"""
+        o = opts if opts is not None else strain_opts_struct(**kw)
+        check(self.L.mcrt_strain_frames(self.h, ptr(pre_iq_dev), ptr(post_iq_dev), n_frames, n_elements, n_rows, C.byref(o), float(cycles_per_row),
+                                        ptr(disp_dev), ptr(rho_dev), ptr(strain_dev)))
+
+    def elastogram_frames(self, strain_img_dev, rho_img_dev, grey_dev, n_frames, height, width, rgb_dev, lut=None, **opts):
+        """mcrt_elastogram_frames: the strain overlay -- the gathered strain and correlation coefficient [n_frames][H][W] over the B-mode bytes
+        [n_frames][H][W] -> rgb_dev [n_frames][H][W][3] bytes.  lut: uint8 [256][3] (None: host_strain_map()); opts: the keywords of
+        elastogram_opts_struct"""
+        o = elastogram_opts_struct(**opts)
+        table = np.ascontiguousarray(host_strain_map() if lut is None else lut, np.uint8)
+        if table.shape != (256, 3):
+            raise ValueError("lut takes uint8 [256][3], got shape %s" % (table.shape,))
+        check(self.L.mcrt_elastogram_frames(self.h, ptr(strain_img_dev), ptr(rho_img_dev), ptr(grey_dev), n_frames, height, width, ptr(table), C.byref(o),
+                                            ptr(rgb_dev)))
+
     def scan_convert_frames(self, rf_dev, n_frames, n_elements, n_rows, out_dev, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         check(self.L.mcrt_scan_convert_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, radius_mm, total_angle, ptr(out_dev), out_rows, out_cols))
 
@@ -1599,7 +1678,7 @@ class Simulator:
 
     def __init__(self, scene_data, transducer, n_samples=5, n_rows=None, device=0, seed=0x5EED, psf=None, texture=None,
                  max_depth=10, sanitize_tir=0, tex_n=256, bvh_builder="sah", elevation=False, compound=None, compound_mode="mean", compound_weights=None,
-                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0, speckle=None, noise=None, speckle3d=None, autogain=None, detect=None, flow=None):
+                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0, speckle=None, noise=None, speckle3d=None, autogain=None, detect=None, flow=None, strain=None):
         """elevation=True: slice thickness.  trace() then traces the psf's elevation_size planes of the frame as one pose pass -- plane k of
         frame f with frame id f * K + k, the frame-id rule of include/mcrt.h -- and folds them into rf_dev with psf.elevation_rows();
         everything after (convolve, bmode, frame) is unchanged.
@@ -1654,7 +1733,29 @@ class Simulator:
         dict's.  The displayed power threshold is power_scale * 2 * N * sigma^2 (default scale 4): a modelling choice that no
         measurement backs.  spectral_doppler() runs the same chain up to the detected pairs and then synthesises the slow-time series of
         ONE sample gate under a speed waveform and a velocity profile (its own keywords; of flow= it reads the material's direction, prf_hz,
-        sigma and the label rule).  Every other method is left alone: without the keyword no call and no bit changes."""
+        sigma and the label rule).  Every other method is left alone: without the keyword no call and no bit changes.
+        strain={"LIVER": 1.0, "TUMOR": 5.0} -- a Young's modulus per material name of the scene (any unit; 0: rigid) --, or a dict of
+        modulus= (that mapping), applied= (the strain of a material of the reference modulus, 0.01), ref_modulus= (1.0; a material that
+        is not named takes it), the keywords of strain_opts_struct (window_rows, search_rows, lsq_rows, seed), noise= (the receiver noise
+        per I/Q component of the post-compression frame, 0) and of the label pass (rule, start_offset): strain elastography.  strain()
+        and elastogram() then synthesise the post-compression frame from ONE traced frame's analytic signal and its tissue labels, and
+        track the speckle between the two.  Every other method is left alone: without the keyword no call and no bit changes."""
+        self.strain_opts = _option(strain)
+        if self.strain_opts is not None:
+            sd = self.strain_opts if "modulus" in self.strain_opts else dict(modulus=self.strain_opts)
+            names = list(scene_data.material_names)
+            ref_modulus = float(sd.pop("ref_modulus", 1.0))
+            modulus = np.full(len(names), ref_modulus, np.float64)
+            for name, v in dict(sd.pop("modulus")).items():
+                if name not in names:
+                    raise ValueError("strain: the scene has no material %r (it has %s)" % (name, ", ".join(names)))
+                modulus[names.index(name)] = float(v)
+            applied = float(sd.pop("applied", 0.01))
+            label = dict(rule=sd.pop("rule", "traced"), start_offset=sd.pop("start_offset", None))
+            label_opts_struct(**label)                      # (an unknown rule ends it here)
+            opts = strain_opts_struct(sigma=sd.pop("noise", None), **sd)       # (unknown keywords end it here)
+            self.strain_opts = dict(modulus=modulus, applied=applied, ref_modulus=ref_modulus, eps=host_strain_table(modulus, applied, ref_modulus),
+                                    opts=opts, label=label)         # (a strain above the cap ends it here)
         self.flow = _option(flow)
         if self.flow is not None:
             fd = self.flow if "velocity_mm_s" in self.flow else dict(velocity_mm_s=self.flow)
@@ -2246,6 +2347,66 @@ class Simulator:
         out["time_axis"] = (np.arange(cols) * hop + N / 2.0) / prf
         out["gate"] = dict(line=line, row0=row0, rows=G, rate=rate, frac=frac, axial=axial)
         return out
+
+    # ---- strain elastography (strain=)
+    @contextlib.contextmanager
+    def _strain_pass(self, frame_id):
+        """ONE trace of the frame -> the label pass -> frame()'s stages -> the detector's I/Q -> mcrt_strain_compress_frames ->
+        mcrt_strain_frames.  Yields dict(tissue, post, truth_disp, truth_strain, disp, rho, strain: device buffers that live as long as
+        the block); rf_dev holds the frame's RF before the envelope"""
+        if self.strain_opts is None:
+            raise RuntimeError("strain imaging needs Simulator(strain=...)")
+        for on, what in ((self.sweep is not None, "sweep="), (self.steers is not None, "compound="), (self.elevation, "elevation="), (self.psf.has_bands, "a psf with bands")):
+            if on:
+                raise RuntimeError("strain imaging is one plane of one pulse: it does not combine with %s" % what)
+        st, n = self.strain_opts, self.E * self.R
+        cycles = host_psf_carrier(self.tr.frequency, self.psf.resolution_um)
+        with contextlib.ExitStack() as held:
+            tissue, iq, post = (held.enter_context(self.ctx.temp(size)) for size in (n, 8 * n, 8 * n))
+            out = {k: held.enter_context(self.ctx.temp(4 * n)) for k in ("truth_disp", "truth_strain", "disp", "rho", "strain")}
+            self.trace(frame_id)
+            self.ctx.label_frames(tissue_dev=tissue, **st["label"])
+            self._stages(self._stack, frame_id, envelope=False)
+            self.ctx.detect_frames(self.rf_dev, 1, self.E, self.R, iq_dev=iq, **(self.detect or {}))
+            self.ctx.strain_compress_frames(iq, tissue, 1, self.E, self.R, st["eps"], cycles, first_image_id=frame_id, post_iq_dev=post,
+                                            truth_disp_dev=out["truth_disp"], truth_strain_dev=out["truth_strain"], opts=st["opts"])
+            self.ctx.strain_frames(iq, post, 1, self.E, self.R, cycles, disp_dev=out["disp"], rho_dev=out["rho"], strain_dev=out["strain"], opts=st["opts"])
+            yield dict(out, tissue=tissue, iq=iq, post=post)
+
+    def _strain_host(self, b):
+        return {k: self.ctx.d2h(b[k], (self.E, self.R), np.float32) for k in ("strain", "rho", "disp", "truth_strain", "truth_disp")}
+
+    def strain(self, frame_id=0):
+        """the tracker's estimates in beam space -> dict(strain, rho, disp, truth_strain, truth_disp: float32 [E][R]): the estimated strain
+        (positive: compression), the correlation coefficient of the winning lag, the displacement in rows, and the true strain and
+        displacement of every sample, registered sample for sample (strain= only)"""
+        with self._strain_pass(frame_id) as b:
+            return self._strain_host(b)
+
+    def elastogram(self, frame_id=0, ref_strain=None, rho_min=None, grey_min=None, alpha=None, lut=None, **display):
+        """the elastogram of a frame -> dict(rgb uint8 [out_rows][out_cols][3], grey uint8 [out_rows][out_cols], strain_img and rho_img
+        float32 [out_rows][out_cols], and strain()'s beam-space outputs).  It traces ONCE; grey is bmode()'s own picture of that trace
+        (display: the keywords of Context.bmode_frames), the strain and the correlation coefficient are gathered through
+        mcrt_scan_convert_frames and laid over it by mcrt_elastogram_frames; ref_strain defaults to the applied strain (strain= only)"""
+        if display.get("persistence", 0.0) != 0.0:
+            raise ValueError("elastogram() shows one frame: persistence is left out")
+        rows, cols = display.get("out_rows", 400), display.get("out_cols", 500)
+        geometry = {k: display[k] for k in ("radius_mm", "total_angle", "out_rows", "out_cols") if k in display}
+        n = rows * cols
+        with self._strain_pass(frame_id) as b, self.ctx.temp(n) as grey, self.ctx.temp(8 * n) as img, self.ctx.temp(3 * n) as rgb:
+            s = self._images(frame_id)
+            self._detect(s, s)                              # bmode()'s remaining stages over the same trace
+            if self.speckle is not None:
+                self._despeckle(s)
+            if self.autogain is not None:
+                self._autogain(s)
+            self.ctx.bmode_frames(self.rf_dev, 1, self.E, self.R, grey, **display)
+            self.ctx.scan_convert_frames(b["strain"], 1, self.E, self.R, img, **geometry)
+            self.ctx.scan_convert_frames(b["rho"], 1, self.E, self.R, img + 4 * n, **geometry)
+            self.ctx.elastogram_frames(img, img + 4 * n, grey, 1, rows, cols, rgb, lut=lut, rho_min=rho_min, grey_min=grey_min, alpha=alpha,
+                                       ref_strain=self.strain_opts["applied"] if ref_strain is None else ref_strain)
+            return dict(self._strain_host(b), rgb=self.ctx.d2h(rgb, (rows, cols, 3), np.uint8), grey=self.ctx.d2h(grey, (rows, cols), np.uint8),
+                        strain_img=self.ctx.d2h(img, (rows, cols), np.float32), rho_img=self.ctx.d2h(img + 4 * n, (rows, cols), np.float32))
 
     def colour_flow(self, frame_id=0, **display):
         """the colour-flow picture of a frame -> dict(rgb uint8 [out_rows][out_cols][3], grey uint8 [out_rows][out_cols], velocity float32

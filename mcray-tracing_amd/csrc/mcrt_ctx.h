@@ -222,6 +222,9 @@ struct ImageStages {
     // [n_gates][G], phase [T] as word pairs) and of mcrt_spectral_frames (window [N]; the twiddles of N = 32 << i, each made once), and
     // the gates' peaks of a mcrt_sonogram_frames without a peak_dev
     StagedWords spec_rotor, spec_gates, spec_weight, spec_rate, spec_phase, spec_window, spec_tw[5]; Buf<float> d_sono_peak;
+    // strain elastography: the last strain table [n_labels] of mcrt_strain_compress_frames (its rotor is spec_rotor), the displacement
+    // [F][E][R] of the largest mcrt_strain_frames so far that gave no disp_dev, and the last colour table of mcrt_elastogram_frames
+    StagedWords strain_eps; Buf<float> d_strain_disp; StagedTable elasto_lut;
     // automatic gain (mcrt_autogain_frames): the histograms of a chunk of frames [frames][n_bands][2048], at most AUTOGAIN_HIST_WORDS, and the row
     // gains [n_frames][R] of the largest call so far that gave no gain_dev
     Buf<uint32_t> d_aghist; Buf<float> d_aggain;

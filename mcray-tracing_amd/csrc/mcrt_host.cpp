@@ -1228,6 +1228,83 @@ extern "C" int mcrt_pulse_waveform(double prf_hz, double beats_per_min, double v
     return MCRT_OK;
 }
 
+// ---- strain elastography (the contracts are in include/mcrt.h) ---------------------------------------
+extern "C" int mcrt_default_strain_opts(mcrt_strain_opts *o)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_strain_opts: null options");
+    o->window_rows = 16u; o->search_rows = 8u; o->lsq_rows = 12u; o->sigma = 0.0f; o->seed = 0x5354524Eu;
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_default_elastogram_opts(mcrt_elastogram_opts *o)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_elastogram_opts: null options");
+    o->ref_strain = 0.01f; o->rho_min = 0.7f; o->grey_min = 0u; o->alpha = 160u;
+    return MCRT_OK;
+}
+
+int mcrt::strain_check(const char *fn, const mcrt_strain_opts *o)
+{
+    if (o->window_rows > 32u) return set_error(MCRT_ERR_INVALID, "%s: window_rows must be 0 .. 32 (%u)", fn, o->window_rows);
+    if (o->search_rows > 16u) return set_error(MCRT_ERR_INVALID, "%s: search_rows must be 0 .. 16 (%u)", fn, o->search_rows);
+    if (o->lsq_rows < 1u || o->lsq_rows > 32u) return set_error(MCRT_ERR_INVALID, "%s: lsq_rows must be 1 .. 32 (%u)", fn, o->lsq_rows);
+    if (!(std::isfinite(o->sigma) && o->sigma >= 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: sigma must be finite and >= 0 (%g)", fn, (double)o->sigma);
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_strain_table(const double *modulus, uint32_t n_labels, double applied, double ref_modulus, int32_t *eps_q24)
+{
+    static const char fn[] = "mcrt_strain_table";
+    if (!modulus || !eps_q24) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (n_labels == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: n_labels is zero", fn);
+    if (n_labels > 254u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: at most 254 labels (%u)", fn, n_labels);
+    if (!std::isfinite(applied)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: applied must be finite (%g)", fn, applied);
+    if (!(std::isfinite(ref_modulus) && ref_modulus > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: ref_modulus must be finite and > 0 (%g)", fn, ref_modulus);
+    for (uint32_t l = 0; l < n_labels; l++) {
+        if (!(std::isfinite(modulus[l]) && modulus[l] >= 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: modulus[%u] must be finite and >= 0 (%g)", fn, l, modulus[l]);
+        if (modulus[l] != 0.0 && !(std::fabs(applied * ref_modulus / modulus[l] * 16777216.0) <= 524288.5))
+            return mcrt::set_error(MCRT_ERR_INVALID, "%s: the strain of label %u, %g, is above 1/32", fn, l, applied * ref_modulus / modulus[l]);
+    }
+    std::vector<int32_t> eps(n_labels);
+    for (uint32_t l = 0; l < n_labels; l++) {
+        const long long q = modulus[l] == 0.0 ? 0ll : std::llrint(applied * ref_modulus / modulus[l] * 16777216.0);
+        if (q > 524288ll || q < -524288ll) return mcrt::set_error(MCRT_ERR_INVALID, "%s: the strain of label %u, %g, is above 1/32", fn, l, applied * ref_modulus / modulus[l]);
+        eps[l] = (int32_t)q;
+    }
+    memcpy(eps_q24, eps.data(), 4 * (size_t)n_labels);
+    return MCRT_OK;
+}
+
+// the draws k_strain_warp makes for one image, [E][R][2]
+extern "C" int mcrt_strain_draws(uint32_t seed, uint32_t image_id, uint32_t n_elements, uint32_t n_rows, int32_t *d)
+{
+    static const char fn[] = "mcrt_strain_draws";
+    if (!d) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null d", fn);
+    if (n_elements == 0 || n_rows == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_elements %u, n_rows %u)", fn, n_elements, n_rows);
+    if (n_rows > 2048u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: n_rows: at most 2048 rows (%u)", fn, n_rows);
+    for (uint32_t e = 0; e < n_elements; e++)
+        for (uint32_t r = 0; r < n_rows; r++) {
+            uint32_t o[4];
+            host_philox4x32_10(e, r, 0x5354524Eu, 0u, seed, image_id, o);
+            int32_t *p = d + 2u * ((size_t)e * n_rows + r);
+            p[0] = (int32_t)((o[0] & 0xffffu) + (o[0] >> 16) + (o[1] & 0xffffu) + (o[1] >> 16)) - 131070;
+            p[1] = (int32_t)((o[2] & 0xffffu) + (o[2] >> 16) + (o[3] & 0xffffu) + (o[3] >> 16)) - 131070;
+        }
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_strain_map(uint32_t kind, uint8_t *lut)
+{
+    static const char fn[] = "mcrt_strain_map";
+    if (!lut) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null lut", fn);
+    if (kind != 0u) return mcrt::set_error(MCRT_ERR_INVALID, "%s: unknown kind %u", fn, kind);
+    for (uint32_t i = 0; i < 256u; i++) {
+        const uint32_t u = i <= 128u ? (2u * i > 255u ? 255u : 2u * i) : 2u * (i - 128u);
+        lut[3u * i] = (uint8_t)(i <= 128u ? 0u : u); lut[3u * i + 1u] = (uint8_t)(i <= 128u ? u : 255u - u); lut[3u * i + 2u] = (uint8_t)(i <= 128u ? 255u - u : 0u);
+    }
+    return MCRT_OK;
+}
+
 // ---- automatic gain (the contract is in include/mcrt.h) ---------------------------------------
 extern "C" int mcrt_default_autogain_opts(mcrt_autogain_opts *o)
 {

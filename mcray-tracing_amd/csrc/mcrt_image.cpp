@@ -366,6 +366,78 @@ extern "C" int mcrt_sonogram_frames(mcrt_ctx *c, const float *power_dev, uint32_
     return MCRT_OK;
 }
 
+// ---- strain elastography (the contracts are in include/mcrt.h; the defaults, the option ranges, the strain table, the draws and the
+// colour table are host code: mcrt_host.cpp).  Each call checks everything before anything is enqueued. ----
+static int strain_sizes(const char *fn, uint32_t n_frames, uint32_t E, uint32_t R, double cycles_per_row)
+{
+    if (n_frames == 0 || E == 0 || R == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, n_elements %u, n_rows %u)", fn, n_frames, E, R);
+    if (!(cycles_per_row > 0.0 && cycles_per_row <= 0.5)) return set_error(MCRT_ERR_INVALID, "%s: cycles_per_row must be in (0, 0.5] (%g)", fn, cycles_per_row);
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: n_rows: at most %d rows (%u)", fn, MCRT_MAX_ROWS, R);
+    if ((double)n_frames * (double)E * (double)R >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: a stack of 2^31 samples or more (%u x %u x %u)", fn, n_frames, E, R);
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_strain_compress_frames(mcrt_ctx *c, const float *iq_dev, const uint8_t *tissue_dev, uint32_t n_frames, uint32_t E, uint32_t R,
+                                           const int32_t *eps_q24, uint32_t n_labels, double cycles_per_row, const mcrt_strain_opts *o, uint32_t first_image_id,
+                                           const float *sigma_dev, float *post_iq_dev, float *truth_disp_dev, float *truth_strain_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_strain_compress_frames";
+    if (!iq_dev || !tissue_dev || !eps_q24 || !o) return set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (n_labels == 0) return set_error(MCRT_ERR_INVALID, "%s: n_labels is zero", fn);
+    MCRT_TRY(strain_sizes(fn, n_frames, E, R, cycles_per_row));
+    MCRT_TRY(mcrt::strain_check(fn, o));
+    if (!post_iq_dev && !truth_disp_dev && !truth_strain_dev) return set_error(MCRT_ERR_INVALID, "%s: no output is given", fn);
+    if (n_labels > 254u) return set_error(MCRT_ERR_LIMIT, "%s: at most 254 labels (%u)", fn, n_labels);
+    if ((uint64_t)first_image_id + n_frames > 0x100000000ull) return set_error(MCRT_ERR_LIMIT, "%s: first_image_id: the ids of %u images from %u on pass 2^32", fn, n_frames, first_image_id);
+    for (uint32_t l = 0; l < n_labels; l++)
+        if (eps_q24[l] > 524288 || eps_q24[l] < -524288) return set_error(MCRT_ERR_INVALID, "%s: eps_q24[%u] = %d is outside +-2^19", fn, l, eps_q24[l]);
+    const size_t n = (size_t)n_frames * E * R;
+    const Range outs[3] = { { post_iq_dev, 8 * n, "post_iq_dev" }, { truth_disp_dev, 4 * n, "truth_disp_dev" }, { truth_strain_dev, 4 * n, "truth_strain_dev" } };
+    const Range ins[3] = { { iq_dev, 8 * n, "iq_dev" }, { tissue_dev, n, "tissue_dev" }, { sigma_dev, 4 * (size_t)n_frames, "sigma_dev" } };
+    for (int i = 0; i < 3; i++)
+        if (ins[i].p) MCRT_TRY(check_overlap(fn, ins[i], outs, 3, i == 0));      // (iq_dev is always there: the outputs among themselves once)
+    static const std::vector<float> rotor = [] { std::vector<float> l(8192); mcrt_spectral_rotor(l.data()); return l; }();
+    MCRT_TRY(c->img.spec_rotor.put(rotor.data(), 8192, c->stream));
+    MCRT_TRY(c->img.strain_eps.put(eps_q24, n_labels, c->stream));
+    mcrt::StrainWarpArgs a; memset(&a, 0, sizeof a);
+    a.iq = (const float2 *)iq_dev; a.tissue = tissue_dev; a.eps = c->img.strain_eps.as<int32_t>(); a.lut = c->img.spec_rotor.as<float2>(); a.sigma_dev = sigma_dev;
+    a.post = (float2 *)post_iq_dev; a.truth_disp = truth_disp_dev; a.truth_strain = truth_strain_dev;
+    a.carrier_q32 = std::llrint(cycles_per_row * 4294967296.0); a.E = E; a.R = R; a.lines = n_frames * E; a.n_labels = n_labels;
+    a.seed = o->seed; a.first_id = first_image_id; a.sigma = o->sigma; a.inv_std = (float)(1.0 / std::sqrt(1431655765.0));
+    HIP_TRY(mcrt::launch_strain_warp(a, c->stream));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_strain_frames(mcrt_ctx *c, const float *pre_iq_dev, const float *post_iq_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_strain_opts *o,
+                                  double cycles_per_row, float *disp_dev, float *rho_dev, float *strain_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_strain_frames";
+    if (!pre_iq_dev || !post_iq_dev || !o) return set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    MCRT_TRY(strain_sizes(fn, n_frames, E, R, cycles_per_row));
+    MCRT_TRY(mcrt::strain_check(fn, o));
+    if (!disp_dev && !rho_dev && !strain_dev) return set_error(MCRT_ERR_INVALID, "%s: no output is given", fn);
+    const size_t n = (size_t)n_frames * E * R;
+    const Range outs[3] = { { disp_dev, 4 * n, "disp_dev" }, { rho_dev, 4 * n, "rho_dev" }, { strain_dev, 4 * n, "strain_dev" } };
+    MCRT_TRY(check_overlap(fn, Range{ pre_iq_dev, 8 * n, "pre_iq_dev" }, outs, 3, true));
+    MCRT_TRY(check_overlap(fn, Range{ post_iq_dev, 8 * n, "post_iq_dev" }, outs, 3, false));
+    float *disp = disp_dev;
+    if (!disp) {
+        if (n > c->img.d_strain_disp.cap) {
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            HIP_TRY(c->img.d_strain_disp.alloc(n));
+        }
+        disp = c->img.d_strain_disp;
+    }
+    mcrt::StrainTrackArgs a; memset(&a, 0, sizeof a);
+    a.pre = (const float2 *)pre_iq_dev; a.post = (const float2 *)post_iq_dev; a.disp = disp; a.rho = rho_dev; a.strain = strain_dev;
+    a.R = R; a.lines = n_frames * E; a.chunks = (R + STRAIN_TILE_ROWS - 1u) / STRAIN_TILE_ROWS;
+    a.window = o->window_rows; a.search = o->search_rows; a.lsq = o->lsq_rows; a.scale = (float)(1.0 / (6.283185307179586 * cycles_per_row));
+    HIP_TRY(mcrt::launch_strain_track(a, c->stream));
+    return MCRT_OK;
+}
+
 // the scan-conversion maps of a geometry on the device, in cache m: the plain maps (cp null: mcrt_scan_maps, one view) or the N views of a steer
 // list (mcrt_compound_maps), [N][2][n_pad]
 static int ensure_maps(mcrt_ctx *c, MapCache &m, uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t orows, uint32_t ocols, const mcrt_compound *cp, const float **maps)
@@ -524,6 +596,35 @@ extern "C" int mcrt_colour_frames(mcrt_ctx *c, const float *corr_img_dev, const 
     a.power_thr = o->power_thr; a.vel_thr = o->vel_thr_mm_s; a.vscale = (float)(v_nyq_mm_s / 3.141592653589793); a.iscale = (float)(127.0 / 3.141592653589793);
     a.grey_max = o->grey_max; a.pass = pixel_pass(n_frames, H * W, 0.0f, vel_img_dev, 4u);
     HIP_TRY(mcrt::launch_colour(a, c->stream));
+    return MCRT_OK;
+}
+
+// ---- the overlay of strain elastography (the contract is in include/mcrt.h, beside mcrt_strain_frames) ----
+// Everything is checked before anything is enqueued; the colour table goes to the device as mcrt_colour_frames' does, in a table of its own.
+extern "C" int mcrt_elastogram_frames(mcrt_ctx *c, const float *strain_img_dev, const float *rho_img_dev, const uint8_t *grey_dev, uint32_t n_frames, uint32_t H, uint32_t W,
+                                      const uint8_t *lut, const mcrt_elastogram_opts *o, uint8_t *rgb_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_elastogram_frames";
+    if (!strain_img_dev || !rho_img_dev || !grey_dev || !lut || !o || !rgb_dev) return set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (n_frames == 0 || H == 0 || W == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, height %u, width %u)", fn, n_frames, H, W);
+    if (!(std::isfinite(o->ref_strain) && o->ref_strain != 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: ref_strain must be finite and not 0 (%g)", fn, (double)o->ref_strain);
+    if (!std::isfinite(o->rho_min)) return set_error(MCRT_ERR_INVALID, "%s: rho_min must be finite (%g)", fn, (double)o->rho_min);
+    if (o->grey_min > 255u) return set_error(MCRT_ERR_INVALID, "%s: grey_min must be 0 .. 255 (%u)", fn, o->grey_min);
+    if (o->alpha > 256u) return set_error(MCRT_ERR_INVALID, "%s: alpha must be 0 .. 256 (%u)", fn, o->alpha);
+    if ((double)n_frames * (double)H * (double)W >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: 2^31 pixels or more (%u x %u x %u)", fn, n_frames, H, W);
+    const size_t n = (size_t)n_frames * H * W;
+    const Range out{ rgb_dev, 3 * n, "rgb_dev" };
+    const Range ins[3] = { { strain_img_dev, 4 * n, "strain_img_dev" }, { rho_img_dev, 4 * n, "rho_img_dev" }, { grey_dev, n, "grey_dev" } };
+    MCRT_TRY(check_overlap(fn, out, ins, 3, false));
+    float packed[256];
+    for (uint32_t i = 0; i < 256u; i++) packed[i] = (float)((uint32_t)lut[3 * i] | (uint32_t)lut[3 * i + 1] << 8 | (uint32_t)lut[3 * i + 2] << 16);
+    MCRT_TRY(c->img.elasto_lut.put(packed, 256, 1, 256, c->stream));
+    mcrt::ElastogramArgs a; memset(&a, 0, sizeof a);
+    a.strain = strain_img_dev; a.rho = rho_img_dev; a.grey = grey_dev; a.lut = c->img.elasto_lut.dev.p; a.rgb = rgb_dev;
+    a.ref_strain = o->ref_strain; a.rho_min = o->rho_min; a.grey_min = o->grey_min; a.alpha = o->alpha;
+    a.pass = pixel_pass(n_frames, H * W, 0.0f, rgb_dev, 1u);
+    HIP_TRY(mcrt::launch_elastogram(a, c->stream));
     return MCRT_OK;
 }
 

@@ -80,5 +80,7 @@ int autogain_check(const char *fn, const mcrt_autogain_opts *o);
 int flow_check(const char *fn, const mcrt_flow_opts *o);
 // mcrt_host.cpp: the ranges of mcrt_spectral_opts, which mcrt_spectral_series_frames and mcrt_spectral_frames share
 int spectral_check(const char *fn, const mcrt_spectral_opts *o);
+// mcrt_host.cpp: the ranges of mcrt_strain_opts, which mcrt_strain_compress_frames and mcrt_strain_frames share
+int strain_check(const char *fn, const mcrt_strain_opts *o);
 }
 #endif

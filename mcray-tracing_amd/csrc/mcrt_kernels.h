@@ -19,6 +19,7 @@
 //   mcrt_detect.hip  k_detect<NT> (quadrature detection: mcrt_detect_frames; NT taps, 1..16)
 //   mcrt_flow.hip    k_flow_split, k_flow<N, WALL>, k_flow_avg (colour Doppler: mcrt_flow_split_frames, mcrt_flow_frames), k_colour (mcrt_colour_frames)
 //   mcrt_spectral.hip k_gate_series (spectral Doppler: mcrt_spectral_series_frames), k_spectrum<N> (mcrt_spectral_frames), k_sonogram_peak, k_sonogram (mcrt_sonogram_frames)
+//   mcrt_strain.hip  k_strain_warp (strain elastography: mcrt_strain_compress_frames), k_strain_track, k_strain_slope (mcrt_strain_frames), k_elastogram (mcrt_elastogram_frames)
 //   mcrt_autogain.hip k_autogain_hist, k_autogain_curve, k_autogain_apply (automatic gain: mcrt_autogain_frames)
 //   mcrt_recon.hip   k_recon_splat, k_recon_resolve (freehand 3-D reconstruction: mcrt_recon_frames)
 //   mcrt_label.hip   k_label (ground-truth label maps: mcrt_label_frames), k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames)
@@ -30,7 +31,7 @@
 // Shared device code: mcrt_device.h (primitives and the knobs more than one unit reads), mcrt_walk.h (the lane walk's steps, also k_path's),
 // mcrt_shade.h (shade_path, also k_path's), mcrt_voxels.h (the voxel block of the 3-D stages: a sample's voxel, a wavefront's runs,
 // the resolve tile, the picture tile -- included by mcrt_recon / label3d / render.hip and, for recon_tiling, mcrt_image.cpp), mcrt_pixels.h (the pixel tile of k_bmode, k_compound, k_volume and k_label_gather and the byte
-// k_render writes: layout, frame chunks, persistence, quantisation, the word store -- included by mcrt_display / volume / label / render / flow.hip
+// k_render writes: layout, frame chunks, persistence, quantisation, the word store -- included by mcrt_display / volume / label / render / flow / strain.hip
 // only).  Everything is scalar fp32/fp64 VALU + integer work -- no dense contraction, hence no MFMA -- and the arithmetic follows the
 // parity contract expression by expression (compiled -ffp-contract=off).
 #pragma once
@@ -455,6 +456,45 @@ struct SonogramArgs {
 };
 hipError_t launch_sonogram_peak(const SonogramArgs &a, hipStream_t st);
 hipError_t launch_sonogram(const SonogramArgs &a, hipStream_t st);
+// k_strain_warp (mcrt_strain_compress_frames): the detected pairs and the tissue labels -> the post-compression pairs and the true displacement and strain
+struct StrainWarpArgs {
+    const float2 *iq;                   // [F][E][R] (I, Q)
+    const uint8_t *tissue;              // [F][E][R]
+    const int32_t *eps;                 // [n_labels] Q24 strains (the context's copy)
+    const float2 *lut;                  // [4096] the rotor (the context's copy)
+    const float *sigma_dev;             // [F] or null: sigma
+    float2 *post;                       // [F][E][R] or null
+    float *truth_disp, *truth_strain;   // [F][E][R], each or null
+    long long carrier_q32;              // llrint(cycles_per_row * 2^32)
+    uint32_t E, R, lines, n_labels;     // lines: F * E
+    uint32_t seed, first_id;
+    float sigma, inv_std;
+};
+hipError_t launch_strain_warp(const StrainWarpArgs &a, hipStream_t st);
+// k_strain_track and k_strain_slope (mcrt_strain_frames): the two stacks of pairs -> the displacement, the correlation coefficient and the strain
+#define STRAIN_TILE_ROWS 64u                        // a wavefront of k_strain_track owns 64 consecutive rows of one scan-line, a lane one of them
+#define STRAIN_MAX_WINDOW 32u                       // the largest window_rows and search_rows: they size the tile's LDS
+#define STRAIN_MAX_SEARCH 16u
+struct StrainTrackArgs {
+    const float2 *pre, *post;           // [F][E][R]
+    float *disp;                        // [F][E][R]: the caller's, or the context's buffer
+    float *rho, *strain;                // [F][E][R], each or null
+    uint32_t R, lines, chunks;          // F * E, ceil(R / STRAIN_TILE_ROWS)
+    uint32_t window, search, lsq;
+    float scale;                        // (float)(1.0 / (2 pi cycles_per_row))
+};
+hipError_t launch_strain_track(const StrainTrackArgs &a, hipStream_t st);      // both kernels, in stream order (the slope only with a strain output)
+// k_elastogram (mcrt_elastogram_frames): the gathered strain and rho [F][n] and the grey bytes [F][n] -> rgb [F][n][3]
+struct ElastogramArgs {
+    const float *strain, *rho;          // [F][n]
+    const uint8_t *grey;                // [F][n]
+    const float *lut;                   // [256]: (float)(r | g << 8 | b << 16), exact (the context's copy)
+    uint8_t *rgb;                       // [F][n][3]
+    float ref_strain, rho_min;
+    uint32_t grey_min, alpha;
+    PixelPass pass;
+};
+hipError_t launch_elastogram(const ElastogramArgs &a, hipStream_t st);
 hipError_t launch_remap(const float *img, uint32_t n_img, uint32_t E, uint32_t R, const float *map_col, const float *map_row, float *out, uint32_t n, hipStream_t st);
 hipError_t launch_bmode_peak(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, float *peak, hipStream_t st);   // peak[F] zeroed before
 hipError_t launch_bmode_grey(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, const float *peak /*[F] or null: ref*/, float ref,

@@ -132,6 +132,12 @@
 // [1/min, mm/s, mm/s] (72, the speed of --flow-velocity, 0) along the FIRST --flow-velocity's direction; a Hann-windowed FFT of --spectral-fft N
 // pulses (32, 64, 128, 256, 512; 128) every --spectral-hop H pulses (32) is shown over --spectral-db X dB (40).  --spectral-iq FILE.raw writes the
 // series itself, float32 [T][2].  --flow-prf-hz applies; it does not combine with --compound, --sweep, --elevation or the band options.
+// --elastogram FILE.ppm writes the last frame's elastogram (quasi-static strain imaging), a binary PPM of the B-mode size: every scan-line of the
+// frame's ONE trace is compressed as a column of springs -- --stiffness NAME:E[,NAME:E...] gives materials their Young's modulus (any unit; the
+// others have 1; 0 is rigid), --compress X (0.01) is the strain of modulus 1 --, the speckle is tracked between the two analytic frames over
+// --strain-window N rows (0..32; 16) and lags up to --strain-search N (0..16; 8), and the least-squares strain over --strain-lsq N rows (1..32; 12)
+// is laid over the 8-bit B-mode frame: stiff blue, the applied strain green, soft red.  --strain-truth FILE.raw writes the true strain of every
+// scan-line sample, float32 [512][465].  It does not combine with --compound, --sweep, --elevation or the band options.
 #include "mcrt_host.hpp"
 #include <algorithm>
 #include <chrono>
@@ -194,6 +200,11 @@ int main(int argc, char **argv)
     const char *colour_flow = nullptr, *flow_packets = nullptr, *flow_prf = nullptr, *flow_wall = nullptr, *flow_avg = nullptr, *flow_vel_thr = nullptr,
                *flow_grey_max = nullptr, *flow_truth = nullptr;   // the options as given
     std::vector<std::string> flow_velocity;
+    const char *elastogram = nullptr, *stiffness = nullptr, *compress = nullptr, *strain_window = nullptr, *strain_search = nullptr, *strain_lsq = nullptr,
+               *strain_truth = nullptr;   // the options as given
+    double applied = 0.01;
+    mcrt_strain_opts stopts; mcrt_default_strain_opts(&stopts);
+    mcrt_elastogram_opts elopts; mcrt_default_elastogram_opts(&elopts);
     const char *spectral = nullptr, *spectral_gate = nullptr, *spectral_pulses = nullptr, *spectral_fft = nullptr, *spectral_hop = nullptr, *spectral_db = nullptr,
                *flow_waveform = nullptr, *spectral_iq = nullptr;   // the options as given
     mcrt_spectral_opts spopts; mcrt_default_spectral_opts(&spopts);
@@ -275,6 +286,13 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--flow-vel-thr") && i + 1 < argc) flow_vel_thr = argv[++i];
             else if (!std::strcmp(argv[i], "--flow-grey-max") && i + 1 < argc) flow_grey_max = argv[++i];
             else if (!std::strcmp(argv[i], "--flow-truth") && i + 1 < argc) flow_truth = argv[++i];
+            else if (!std::strcmp(argv[i], "--elastogram") && i + 1 < argc) elastogram = argv[++i];
+            else if (!std::strcmp(argv[i], "--stiffness") && i + 1 < argc) stiffness = argv[++i];
+            else if (!std::strcmp(argv[i], "--compress") && i + 1 < argc) compress = argv[++i];
+            else if (!std::strcmp(argv[i], "--strain-window") && i + 1 < argc) strain_window = argv[++i];
+            else if (!std::strcmp(argv[i], "--strain-search") && i + 1 < argc) strain_search = argv[++i];
+            else if (!std::strcmp(argv[i], "--strain-lsq") && i + 1 < argc) strain_lsq = argv[++i];
+            else if (!std::strcmp(argv[i], "--strain-truth") && i + 1 < argc) strain_truth = argv[++i];
             else if (!std::strcmp(argv[i], "--spectral") && i + 1 < argc) spectral = argv[++i];
             else if (!std::strcmp(argv[i], "--gate") && i + 1 < argc) spectral_gate = argv[++i];
             else if (!std::strcmp(argv[i], "--spectral-pulses") && i + 1 < argc) spectral_pulses = argv[++i];
@@ -510,6 +528,21 @@ int main(int argc, char **argv)
         }
         if (!colour_flow && ((!spectral && (!flow_velocity.empty() || flow_prf)) || flow_packets || flow_wall || flow_avg || flow_vel_thr || flow_grey_max || flow_truth))
             throw std::invalid_argument("--flow-velocity, --flow-packets, --flow-prf-hz, --flow-wall, --flow-avg, --flow-vel-thr, --flow-grey-max and --flow-truth need --colour-flow");
+        if (!elastogram && (stiffness || compress || strain_window || strain_search || strain_lsq || strain_truth))
+            throw std::invalid_argument("--stiffness, --compress, --strain-window, --strain-search, --strain-lsq and --strain-truth need --elastogram");
+        if (elastogram) {
+            if (compound_given || sweep_given || elevation_given || with_bands) throw std::invalid_argument("--elastogram does not combine with --compound, --sweep, --elevation or the band options");
+            if (!stiffness) throw std::invalid_argument("--elastogram needs --stiffness NAME:E[,NAME:E...]");
+            if (compress) applied = std::atof(compress);
+            if (strain_window) stopts.window_rows = (uint32_t)std::max(std::atol(strain_window), 0l);
+            if (strain_search) stopts.search_rows = (uint32_t)std::max(std::atol(strain_search), 0l);
+            if (strain_lsq) stopts.lsq_rows = (uint32_t)std::max(std::atol(strain_lsq), 0l);
+            if (stopts.window_rows > 32u || stopts.search_rows > 16u || stopts.lsq_rows < 1u || stopts.lsq_rows > 32u)
+                throw std::invalid_argument("--strain-window takes 0..32, --strain-search 0..16 and --strain-lsq 1..32");
+            if (!(std::fabs(applied) > 0.0 && std::fabs(applied) <= 0.03125)) throw std::invalid_argument("--compress takes a strain that is not 0, up to 1/32");
+            elopts.ref_strain = (float)applied;
+            bmode = true;                               // the colour lies over the 8-bit frame
+        }
         if (colour_flow) {
             if (compound_given || sweep_given || elevation_given || with_bands) throw std::invalid_argument("--colour-flow does not combine with --compound, --sweep, --elevation or the band options");
             if (flow_velocity.empty()) throw std::invalid_argument("--colour-flow needs --flow-velocity NAME:vx,vy,vz");
@@ -621,6 +654,19 @@ int main(int argc, char **argv)
                 for (int k = 0; k < 3; k++) flow_vel[3 * m + k] = v[k];
             }
         }
+        std::vector<double> modulus;                    // --stiffness: a Young's modulus per material of the scene
+        if (elastogram) {
+            modulus.assign(scene.material_names.size(), 1.0);
+            std::string list = stiffness;
+            for (size_t at = 0; at <= list.size();) {
+                const size_t comma = std::min(list.find(',', at), list.size());
+                const std::string item = list.substr(at, comma - at);
+                const size_t colon = item.find(':');
+                if (colon == std::string::npos || colon + 1 >= item.size()) throw std::invalid_argument("--stiffness takes NAME:E[,NAME:E...]");
+                modulus[scene.material_index(item.substr(0, colon))] = std::atof(item.c_str() + colon + 1);
+                at = comma + 1;
+            }
+        }
 
         const auto t0 = std::chrono::high_resolution_clock::now();
         for (int f = 0; f < frames; f++) {
@@ -637,6 +683,12 @@ int main(int argc, char **argv)
                 std::ofstream out(iq_file, std::ios::binary);
                 out.write((const char *)pair.data(), (std::streamsize)(pair.size() * sizeof(float)));
                 if (!out) throw std::runtime_error(std::string("cannot write ") + iq_file);
+            }
+            rf_image_::strain_truth strain_true;
+            if (elastogram && f == frames - 1) {         // the labels, the analytic pair and the post-compression pair of the RF, before it is detected
+                double cycles = 0.0;
+                check(mcrt_psf_carrier(transducer_frequency, resolution, &cycles), "mcrt_psf_carrier");
+                strain_true = rf_image.compress(transducer, modulus, applied, 1.0, stopts, cycles, nullptr, detect ? &dopts : nullptr);
             }
             if (detect) rf_image.detect(dopts);          // quadrature detection in the place of ...
             else rf_image.envelope();         // main.cpp:147
@@ -660,6 +712,17 @@ int main(int argc, char **argv)
                     std::ofstream out(flow_truth, std::ios::binary);
                     out.write((const char *)maps.truth.data(), (std::streamsize)(maps.truth.size() * sizeof(float)));
                     if (!out) throw std::runtime_error(std::string("cannot write ") + flow_truth);
+                }
+            }
+            if (elastogram && f == frames - 1) {         // the tracker and the overlay over the frame just made
+                std::vector<unsigned char> rgb;
+                rf_image.track(stopts);
+                rf_image.elastogram(elopts, rgb);
+                write_ppm(elastogram, display.out_cols, display.out_rows, rgb);
+                if (strain_truth) {
+                    std::ofstream out(strain_truth, std::ios::binary);
+                    out.write((const char *)strain_true.strain.data(), (std::streamsize)(strain_true.strain.size() * sizeof(float)));
+                    if (!out) throw std::runtime_error(std::string("cannot write ") + strain_truth);
                 }
             }
             if (spectral && f == frames - 1) {           // the sample gate's series, its spectra and the sonogram

@@ -5,7 +5,7 @@
 //   transducer<N>            transducer.h:24-137   (frequency MHz, radius cm, element separation mm, position, angles deg)
 //   psf<ax,lat,elev,res>     psf.h:34-77
 //   scene                    scene.h:19-76, scene.cpp:16-48,185-247 (JSON keys, "Error while loading scene: ..." wrapping)
-//   rf_image<cols,us,um>     rfimage.h:20-219      (clear / convolve / envelope / postprocess; data lives on the GPU); + detect / iq; + flow_split / flow / colour_flow; + spectral_series / spectrum / sonogram
+//   rf_image<cols,us,um>     rfimage.h:20-219      (clear / convolve / envelope / postprocess; data lives on the GPU); + detect / iq; + flow_split / flow / colour_flow; + spectral_series / spectrum / sonogram; + compress / track / elastogram
 //   ray_physics::segment     ray.h:28-36           (vec3 stands in for btVector3; `media` is held BY VALUE: the reference's
 //                                                   `const material &` dangles by the time main.cpp:126 reads it)
 //   volume<size,res>         volume.h:19-61        (host copy of the texture the GPU samples)
@@ -723,7 +723,7 @@ public:
 
     rf_image(double radius_mm, double angle_rad, std::shared_ptr<device> dev_ = nullptr)
         : dev(dev_ ? std::move(dev_) : default_device()), radius_mm(radius_mm), angle(angle_rad), host((size_t)columns * max_rows, 0.0f),
-          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev), sound(dev), sigma(dev), curve(dev), band_stack(dev), flow_in(dev), flow_out(dev), spectral_buf(dev)
+          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev), sound(dev), sigma(dev), curve(dev), band_stack(dev), flow_in(dev), flow_out(dev), spectral_buf(dev), strain_buf(dev), strain_pic(dev)
     {
         std::cout << "rf_image: " << max_rows << ", " << columns << std::endl;          // rfimage.h:30
         rf.reserve(sizeof(float) * columns * max_rows);
@@ -1042,6 +1042,68 @@ public:
         uint8_t *grey = reinterpret_cast<uint8_t *>(power + np + spectral_cols);
         check(mcrt_sonogram_frames(dev->ctx, power, 1, spectral_cols, spectral_N, &go, nullptr, grey), "mcrt_sonogram_frames");
         return download<unsigned char>(grey, np);
+    }
+    // strain elastography (mcrt.h: mcrt_strain_compress_frames, mcrt_strain_frames, mcrt_elastogram_frames), three steps around the B-mode
+    // chain of ONE trace:
+    //   trace(f);  convolve(p); [add_noise();]  compress(t, modulus, applied, ref, so, cycles);  envelope() / detect();  postprocess(bmode_params);
+    //   track(so);  elastogram(eo, rgb);
+    // compress() goes while this image holds the RF before the envelope: the label pass of t's central beams (lopts: null = the tracer's
+    // rule), the detector's I/Q (dopts: null = 31 taps) and the post-compression pairs, device copies this image keeps.  modulus: a
+    // Young's modulus per material of the scene [n_materials] (scene::material_index names them; 0: rigid); applied: the strain of a
+    // material of ref_modulus; cycles_per_row: mcrt_psf_carrier's.  A stack of views, planes or tracked frames, band images or a
+    // host-deposited image has no one analytic line: it throws.  The maps are [columns][max_rows]
+    struct strain_truth { std::vector<float> disp, strain; };
+    template <size_t N> strain_truth compress(const transducer<N> &t, const std::vector<double> &modulus, double applied, double ref_modulus, const mcrt_strain_opts &so,
+                                              double cycles_per_row, const mcrt_label_opts *lopts = nullptr, const mcrt_detect_opts *dopts = nullptr)
+    {
+        static_assert(N == columns, "one scan-line per transducer element");
+        if (n_views || banded || where != on_device) throw std::logic_error("rf_image::compress: after trace(frame_id) and convolve(psf), on one traced image");
+        const uint32_t L = (uint32_t)modulus.size();
+        if (L == 0 || L > 254) throw std::invalid_argument("rf_image::compress: a modulus per material, 1..254 materials");
+        std::vector<int32_t> eps(L);
+        check(mcrt_strain_table(modulus.data(), L, applied, ref_modulus, eps.data()), "mcrt_strain_table");
+        const size_t n = (size_t)columns * max_rows;
+        strain_buf.reserve(4 * 9 * n + n);                           // floats: the pairs [n][2], post [n][2], truth_disp, truth_strain, disp, rho, strain; then the tissue bytes
+        uint8_t *tissue = strain_buf.as<uint8_t>() + 4 * 9 * n;
+        mcrt_ctx *tracer = dev->tracer();
+        check(mcrt_label_frames(tracer, 1, 0, columns, t.pos.data(), t.dir.data(), lopts, tissue, nullptr, nullptr), "mcrt_label_frames");
+        check(mcrt_synchronize(tracer), "mcrt_synchronize");
+        float *pairs = strain_buf.as<float>(), *post = pairs + 2 * n, *td = post + 2 * n, *ts = td + n;
+        mcrt_detect_opts d; mcrt_default_detect_opts(&d);
+        check(mcrt_detect_frames(dev->ctx, rf.as<float>(), 1, columns, max_rows, dopts ? dopts : &d, nullptr, pairs), "mcrt_detect_frames");
+        check(mcrt_strain_compress_frames(dev->ctx, pairs, tissue, 1, columns, max_rows, eps.data(), L, cycles_per_row, &so, first_id, nullptr, post, td, ts),
+              "mcrt_strain_compress_frames");
+        strain_cycles = cycles_per_row; strain_tracked = false;
+        return { download<float>(td, n), download<float>(ts, n) };
+    }
+    // the tracker between the pairs compress() left: the displacement [rows], the correlation coefficient and the strain in beam space;
+    // they stay on the device for elastogram()
+    struct strain_maps { std::vector<float> disp, rho, strain; };
+    strain_maps track(const mcrt_strain_opts &so)
+    {
+        if (strain_cycles == 0.0) throw std::logic_error("rf_image::track: compress() first");
+        const size_t n = (size_t)columns * max_rows;
+        float *pairs = strain_buf.as<float>(), *post = pairs + 2 * n, *disp = post + 4 * n, *rho = disp + n, *st = rho + n;
+        check(mcrt_strain_frames(dev->ctx, pairs, post, 1, columns, max_rows, &so, strain_cycles, disp, rho, st), "mcrt_strain_frames");
+        strain_tracked = true;
+        return { download<float>(disp, n), download<float>(rho, n), download<float>(st, n) };
+    }
+    // the elastogram over the last postprocess(bmode_params) frame: track()'s strain and correlation coefficient gathered through
+    // mcrt_scan_convert_frames at that frame's size, and mcrt_elastogram_frames with eo and mcrt_strain_map's table.  rgb: [out_rows][out_cols][3]
+    void elastogram(const mcrt_elastogram_opts &eo, std::vector<unsigned char> &rgb)
+    {
+        if (!strain_tracked) throw std::logic_error("rf_image::elastogram: track() first");
+        if (!bmode_n) throw std::logic_error("rf_image::elastogram: postprocess(bmode_params) first: the picture under the colour");
+        const size_t n = (size_t)columns * max_rows, np = bmode_n;
+        strain_pic.reserve(4 * 2 * np + 3 * np);                     // strain_img, rho_img, then the rgb bytes
+        float *st = strain_buf.as<float>() + 8 * n, *rho = st - n, *img = strain_pic.as<float>();
+        uint8_t *out = reinterpret_cast<uint8_t *>(img + 2 * np);
+        check(mcrt_scan_convert_frames(dev->ctx, st, 1, columns, max_rows, radius_mm, angle, img, bmode_rows, bmode_cols), "mcrt_scan_convert_frames");
+        check(mcrt_scan_convert_frames(dev->ctx, rho, 1, columns, max_rows, radius_mm, angle, img + np, bmode_rows, bmode_cols), "mcrt_scan_convert_frames");
+        uint8_t lut[256 * 3];
+        check(mcrt_strain_map(0, lut), "mcrt_strain_map");
+        check(mcrt_elastogram_frames(dev->ctx, img, img + np, bmode_buf.as<uint8_t>(), 1, bmode_rows, bmode_cols, lut, &eo, out), "mcrt_elastogram_frames");
+        rgb = download<unsigned char>(out, 3 * np);
     }
     // receiver noise (mcrt.h: mcrt_noise_frames): a noise floor and a gain per scan-line (element_gain: [columns] or null) over whatever the
     // last trace() filled, in place -- this image, or the views of a compounded frame or the planes of a sweep as ONE frame (one receiver,
@@ -1412,6 +1474,8 @@ private:
     bool flow_detected = false;                  // flow() has left the two parts' I/Q pairs in flow_in since the last flow_split()
     device_buffer spectral_buf;                  // spectral_series() / spectrum() / sonogram(): the series [T][2], then power [n_cols][N], mean [n_cols] and the bytes
     uint32_t spectral_T = 0, spectral_cols = 0, spectral_N = 0;   // ... the shapes of what it holds (0: nothing yet)
+    device_buffer strain_buf, strain_pic;        // compress() / track(): the pairs, the post-compression pairs, five maps and the tissue bytes; elastogram(): the gathered pictures and the rgb bytes
+    double strain_cycles = 0.0; bool strain_tracked = false;   // compress()'s carrier (0: it has not run); track() has run since
     uint32_t banded = 0;                         // ... B while they wait there for envelope() / fold_bands() (0: the images are where trace() left them)
     std::vector<float> band_w;                   // ... and the bands' weights [max_rows][B] they are folded with
     uint32_t sound_planes = 0;                   // ... their leading axis (nothing yet: 0)
