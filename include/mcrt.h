@@ -83,7 +83,11 @@ extern "C" {
                                    + mcrt_strain_opts, mcrt_default_strain_opts, mcrt_strain_table, mcrt_strain_draws, mcrt_strain_map,
                                    mcrt_strain_compress_frames, mcrt_strain_frames, mcrt_elastogram_opts, mcrt_default_elastogram_opts, mcrt_elastogram_frames
                                    (strain elastography: a quasi-static compression synthesised from one traced frame, speckle tracking by normalised
-                                   cross-correlation, the strain, its ground truth and the elastogram; additive) */
+                                   cross-correlation, the strain, its ground truth and the elastogram; additive);
+                                   + mcrt_shear_opts, mcrt_default_shear_opts, mcrt_shear_table, mcrt_shear_pitch, mcrt_shear_shape, mcrt_shear_decay,
+                                   mcrt_shear_draws, mcrt_shear_map, mcrt_shear_wave_frames, mcrt_shear_speed_frames
+                                   (shear-wave elastography: a push, the shear wave tracked over slow time from one traced frame, the time to peak,
+                                   the shear speed, the modulus and their ground truth; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -1609,6 +1613,144 @@ int mcrt_default_elastogram_opts(mcrt_elastogram_opts *o);
 int mcrt_elastogram_frames(mcrt_ctx *ctx, const float *strain_img_dev /* [F][H][W] */, const float *rho_img_dev /* [F][H][W] */,
                            const uint8_t *grey_dev /* [F][H][W] */, uint32_t n_frames, uint32_t height, uint32_t width, const uint8_t *lut /* [256][3] */,
                            const mcrt_elastogram_opts *o, uint8_t *rgb_dev /* [F][H][W][3] */);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Shear-wave elastography: the quantitative mode.  A radiation-force push on one scan-line launches a shear wave sideways, the
+ * scanner tracks the tissue's axial displacement at a few kHz, and the wave's local speed c gives the stiffness, E = 3 rho c^2.  The
+ * reference has no counterpart.  THE MODEL is one-dimensional and lateral, as the strain model is one-dimensional and axial, and is
+ * synthesised from ONE traced frame, as the Doppler ensembles and the compression are and for the same reason (a second trace has
+ * another Philox key and decorrelates completely).  A push on scan-line push_line over the rows [row0, row1) starts a wave that
+ * leaves that line in both directions and travels along each RF row on its own; each material has a shear speed, and a speed of
+ * exactly 0 is a fluid: the wave does not pass, and nothing behind it ever arrives.  TRACKING: pulse n's analytic line is the pre line
+ * read at q + u(n) by mcrt_strain_compress_frames' interpolation; the displacement estimate is the phase of the lag-0 correlation of a
+ * window of that line with the pre line (the displacements are a small fraction of a row: no lag search); a sample's arrival is its
+ * time to peak, refined by a parabola through the maximum and its neighbours; the speed is the pitch over the least-squares slope of
+ * the time to peak across scan-lines.  Arrival times and displacements are integers, so the device and any mirror agree whatever
+ * the order of the sums.
+ * LEFT OUT: reflection and refraction of the shear wave; dispersion and viscosity; axial propagation and the push's real beam shape;
+ * multiple pushes and directional filtering; time-profile cross-correlation in place of time to peak; Voigt or other models.
+ * An opt-in chain; without it no call and no bit changes.
+ *
+ * Throughout, every float operation is rounded once: no fma, correctly rounded / and sqrtf, no device transcendental; every sum
+ * ascends from 0.0f.
+ *
+ * THE INTEGERS.  A tick is 2^-16 of a tracking pulse interval.  NEVER = 2^40 ticks.
+ *   slow_q16[l]  = llrint(65536.0 * 65536.0 * prf_hz / (speed_m_s[l] * 1e6))      ticks per um in Q16; 0 for a speed of exactly 0 (a fluid)
+ *   pitch_q8[r]  = llrint(256.0 * pitch_um(r)),  pitch_um(r) = 1000 (radius_mm + r depth_mm / R) total_angle / E: the arc between
+ *                  neighbouring scan-lines at the depth of row r.  THE CONVENTION is mcrt_scan_maps': E scan-lines share the total
+ *                  angle, neighbours are total_angle / E apart (its column coordinate is (angle + total_angle / 2) / total_angle * E), row
+ *                  r lies r depth_mm / R below the arc, depth_mm = max_travel_us * speed_of_sound * 0.001.
+ *   cost(l, r)   = l < n_labels && slow_q16[l] != 0 ? (slow_q16[l] * (int64)pitch_q8[r]) >> 24 : NEVER       (MCRT_LABEL_NONE, a label
+ *                  past the table and a fluid block the crossing; slow_q16 <= 2^38 and pitch_q8 < 2^24: the product is below 2^62)
+ *   A[p][r] = 0 on the push line p;  A[e][r] = min(NEVER, A[e-1][r] + cost(tissue[e-1][r], r)) for e > p,
+ *                                    A[e][r] = min(NEVER, A[e+1][r] + cost(tissue[e+1][r], r)) for e < p:
+ *                  a crossing costs what the tissue it LEAVES costs, as the strain sum takes the row it leaves.  Saturating sums of
+ *                  non-negative terms: the order is free, and A == NEVER means "never".
+ *   pa(e)        = ((int64)peak_q24 * amp(|e - p|)) >> 16,   amp(d) = d < n_amp ? amp_q16[d] : 0                (arithmetic shifts)
+ *   t            = ((int64)n << 16) - A[e][r];    idx = t >> 10          (the shape table's step is 1/64 pulse)
+ *   u(e, r, n)   = row0 <= r < row1 && A[e][r] < NEVER && t >= 0 && idx < n_shape ? (pa(e) * (int64)shape_q16[idx]) >> 16 : 0
+ *                  the particle displacement in Q24 rows, |u| <= 2^23 (|peak_q24| <= 2^23, table entries <= 65536); positive reads deeper
+ * row0 = push_row0, row1 = push_rows ? push_row0 + push_rows : R. */
+typedef struct {
+    uint32_t n_pulses;      /* T, the tracking pulses: 4..256; default 64 */
+    uint32_t window_rows;   /* a, the half-window of the correlation: 0..16; default 8 */
+    float prf_hz;           /* the tracking pulse rate, finite and > 0; default 10000 (the speed call's scale; the table has its own) */
+    float sigma;            /* the receiver noise per I/Q component of every tracking line, finite and >= 0, used when no sigma_dev is given; default 0 */
+    uint32_t seed;          /* Philox key word 0 of the noise stream; default 0x53484552 */
+    uint32_t push_line;     /* p, the pushed scan-line, < n_elements; default 0 */
+    uint32_t push_row0;     /* the first pushed row, < n_rows; default 0 */
+    uint32_t push_rows;     /* the pushed rows; 0: to the end of the line; push_row0 + push_rows <= n_rows; default 0 */
+    int32_t peak_q24;       /* the peak displacement on the push line in Q24 rows, |peak_q24| <= 2^23; default 1677722 (0.1 row) */
+    uint32_t speed_lines;   /* b, the half-window of the slope across scan-lines: 1..16; default 4 */
+    uint32_t avg_rows;      /* the peak times are averaged over +- avg_rows rows before the fit: 0..16; default 2 */
+    float density;          /* g/cm^3, finite and > 0: modulus [kPa] = 3 density speed^2; default 1 */
+} mcrt_shear_opts;          /* 48 bytes */
+/* the defaults above.  MCRT_ERR_INVALID for a null o.  Host only. */
+int mcrt_default_shear_opts(mcrt_shear_opts *o);
+/* slow_q16 (above, in double) and speed_f[l] = (float)speed_m_s[l], the truth table.  Host only.  MCRT_ERR_INVALID for a null pointer,
+ * n_labels == 0, a prf_hz that is not finite and > 0, a speed that is not finite or is < 0, or a slow_q16[l] of a speed > 0 outside
+ * [1, 2^38]; MCRT_ERR_LIMIT for n_labels > 254; on an error nothing is written. */
+int mcrt_shear_table(const double *speed_m_s /* [n_labels] */, uint32_t n_labels, double prf_hz, int64_t *slow_q16 /* [n_labels] */,
+                     float *speed_f /* [n_labels] */);
+/* pitch_q8 (above, in double) and pitch_mm[r] = (float)(pitch_um(r) * 0.001), each [n_rows] or NULL, at least one given.  Host only.
+ * MCRT_ERR_INVALID for both null, zero sizes, a radius_mm that is not finite or is < 0, a total_angle_rad that is not finite and > 0,
+ * max_travel_us * speed_of_sound == 0; MCRT_ERR_LIMIT for n_rows > 2048 or a pitch_q8 of 0 or >= 2^24; on an error nothing is written. */
+int mcrt_shear_pitch(uint32_t n_elements, uint32_t n_rows, double radius_mm, double total_angle_rad, uint32_t max_travel_us, uint32_t speed_of_sound,
+                     uint32_t *pitch_q8 /* [n_rows] or NULL */, float *pitch_mm /* [n_rows] or NULL */);
+/* the default time profile, a raised cosine of width_pulses, n_shape = 64 width_pulses entries, in double:
+ *   shape_q16[i] = llrint(65536.0 * (0.5 - 0.5 * cos(6.283185307179586 * (i + 0.5) / n_shape)))
+ * Host only.  MCRT_ERR_INVALID for a null table or width_pulses == 0; MCRT_ERR_LIMIT for width_pulses > 256. */
+int mcrt_shear_shape(uint32_t width_pulses, uint32_t *shape_q16 /* [64 * width_pulses] */);
+/* the default geometric decay over line distance, in double: amp_q16[d] = llrint(65536.0 / sqrt(1.0 + d / d0_lines)).  Host only.
+ * MCRT_ERR_INVALID for a null table, n == 0 or a d0_lines that is not finite and > 0. */
+int mcrt_shear_decay(uint32_t n, double d0_lines, uint32_t *amp_q16 /* [n] */);
+/* the integer noise draws of tracking pulse `pulse` of one image, d[e][r][0..1] (I, Q): one Philox4x32-10 block per sample with the
+ * counter (e, r, 0x53484552, pulse) and the key (seed, image_id); mcrt_flow_draws' Irwin-Hall sums and inv_std.  Counter word 2 differs
+ * from the tracer's (< 16), mcrt_noise_frames' (0x4E4F4953), mcrt_flow_frames' (0x464C4F57), mcrt_spectral_series_frames' (0x53504543)
+ * and mcrt_strain_compress_frames' (0x5354524E).  Host only.  MCRT_ERR_INVALID for a null d or zero sizes; MCRT_ERR_LIMIT for
+ * n_rows > 2048 or pulse >= 256. */
+int mcrt_shear_draws(uint32_t seed, uint32_t image_id, uint32_t n_elements, uint32_t n_rows, uint32_t pulse, int32_t *d /* [E][R][2] */);
+/* the colour table of the shear-wave elastogram, lut[i] = (r, g, b), i = 128 the reference modulus.  kind 0, SOFT blue through green to
+ * STIFF red, the convention of shear-wave displays and the opposite of mcrt_strain_map's reading, in integer arithmetic:
+ *   i = 0..128:     u = min(255, 2 i);      (0, u, 255 - u)              blue (no stiffness) to green (the reference modulus)
+ *   i = 129..255:   u = 2 (i - 128);        (u, 255 - u, 0)              green to red (twice the reference modulus)
+ * mcrt_elastogram_frames shows it as it is: the gathered modulus for strain_img_dev, the gathered quality for rho_img_dev, ref_strain =
+ * the reference kPa.  Host only.  MCRT_ERR_INVALID for a null lut or another kind. */
+int mcrt_shear_map(uint32_t kind, uint8_t *lut /* [256][3] */);
+/* THE WAVE AND THE TRACKER.  iq_dev [F][E][R][2] is mcrt_detect_frames' iq_dev, tissue_dev [F][E][R] mcrt_label_frames' labels; slow_q16,
+ * speed_f, pitch_q8, shape_q16 and amp_q16 are HOST tables (the helpers' or the caller's own within the helpers' ranges), free when the
+ * call returns: they live in buffers of the context and are copied only when they differ from what is there.  T = o->n_pulses, a =
+ * o->window_rows.  Per frame f, scan-line e, row r and pulse n = 0 .. T-1, with pre = iq_dev[f][e]:
+ *   z_n[q]  = warp(pre, q, u(e, q, n)) + k * (float)d_n[e][q]            warp: mcrt_strain_compress_frames' post[q] with U[q] = u (s0, fr, w0, w1,
+ *             th0, th1 and the rotor lookup are its own); k = sigma_f * inv_std, sigma_f = sigma_dev ? sigma_dev[f] : o->sigma, d_n
+ *             mcrt_shear_draws' of (o->seed, first_image_id + f, n); at k == 0 the noise term is skipped and no block is computed
+ *   c_n     = sum over i = -a .. a ascending, rows r + i inside [0, R), of z_n[r+i] * conj(pre[r+i]):
+ *             re += (a * c + b * d),  im += (b * c - a * d)   with z_n[r+i] = (a, b), pre[r+i] = (c, d)   (the products before the sums)
+ *   d_n     = mcrt_det_atan2f(c_n.im, c_n.re) * (float)(1.0 / (6.283185307179586 * cycles_per_row))          the displacement estimate, rows
+ * THE PEAK.  The best pulse starts as n = 0; a later pulse replaces it only when its d_n is strictly greater: the first maximum wins, a
+ * NaN never wins, and a NaN at n = 0 stays.  With m the best pulse and (um, u0, up) = (d_{m-1}, d_m, d_{m+1}):
+ * THE OUTPUTS, each a device pointer or NULL, at least one given:
+ *   peak_time_dev [F][E][R]      (float)m + (0.5f * (um - up)) / ((um - 2.0f * u0) + up);  NaN where m == 0, m == T-1 or the denominator is 0
+ *   peak_disp_dev [F][E][R]      u0
+ *   disp_dev [F][T][E][R]        d_n, the movie
+ *   truth_arrival_dev [F][E][R]  (float)A[e][r] * 0x1p-16f, in pulses;  +inf where A == NEVER
+ *   truth_speed_dev [F][E][R]    speed_f[tissue[e][r]];  +0.0f for MCRT_LABEL_NONE and a label past the table
+ * With peak_q24 == 0 and k == 0 every d_n is +0.0f wherever pre is finite and not zero, as pulse n's line is pre (the zero-strain
+ * identity).  A lives in a grow-only buffer of the context: nothing is allocated after the first call at a size.  The inputs are read
+ * only; every element of every output given is written.  Asynchronous on the context's stream.  MCRT_ERR_INVALID for a null ctx, iq_dev,
+ * tissue_dev, table or o, zero sizes, n_labels, n_shape or n_amp == 0, a cycles_per_row outside (0, 0.5], options out of range (n_pulses,
+ * window_rows, prf_hz, sigma, |peak_q24|, push_line >= n_elements, push_row0 >= n_rows, push_row0 + push_rows > n_rows, speed_lines,
+ * avg_rows, density), a slow_q16[l] outside [0, 2^38], a pitch_q8[r] of 0 or >= 2^24, a shape_q16 or amp_q16 entry above 65536, no
+ * output, an output that overlaps an input or another output; MCRT_ERR_LIMIT for n_rows > 2048, n_labels > 254, n_shape > 16384, n_amp >
+ * 65536, a stack or a movie of 2^31 samples or more, image ids that pass 2^32; on any error nothing is launched and nothing is written.
+ * Groups: call it on mcrt_group_root(). */
+int mcrt_shear_wave_frames(mcrt_ctx *ctx, const float *iq_dev /* [F][E][R][2] */, const uint8_t *tissue_dev /* [F][E][R] */, uint32_t n_frames,
+                           uint32_t n_elements, uint32_t n_rows, const int64_t *slow_q16 /* [n_labels] */, const float *speed_f /* [n_labels] */,
+                           uint32_t n_labels, const uint32_t *pitch_q8 /* [R] */, const uint32_t *shape_q16 /* [n_shape] */, uint32_t n_shape,
+                           const uint32_t *amp_q16 /* [n_amp] */, uint32_t n_amp, double cycles_per_row, const mcrt_shear_opts *o,
+                           uint32_t first_image_id, const float *sigma_dev /* [F] or NULL */, float *peak_time_dev /* [F][E][R] or NULL */,
+                           float *peak_disp_dev /* [F][E][R] or NULL */, float *disp_dev /* [F][T][E][R] or NULL */,
+                           float *truth_arrival_dev /* [F][E][R] or NULL */, float *truth_speed_dev /* [F][E][R] or NULL */);
+/* THE SPEED.  peak_time_dev [F][E][R] is mcrt_shear_wave_frames'; pitch_mm [R] is a HOST table (mcrt_shear_pitch's), kept as the others
+ * are.  b = o->speed_lines, v = o->avg_rows, p = o->push_line, kf = (float)((double)o->prf_hz * 0.001), d3 = 3.0f * o->density.  Per
+ * sample (e, r) the window of lines j = e - b .. e + b is NOT clipped: where e - b < 0, e + b >= E or e - b <= p <= e + b the sample is
+ * not valid.  Otherwise, with the rows i = max(0, r - v) .. min(R - 1, r + v) ascending:
+ *   y_j   = (sum of peak_time[j][i] over the rows where it is not NaN) / (float)(their count);  no such row: the sample is not valid
+ *   t_j   = (float)(2 j - 2 e);   den = sum of t_j * t_j;   mean = (sum of y_j) / (float)(2 b + 1)                (j ascending)
+ *   num   = sum of t_j * y_j;     syy = sum of (y_j - mean) * (y_j - mean)
+ *   slope = (2.0f * num) / den, negated where e < p: pulses per scan-line, signed away from the push; not > 0: the sample is not valid
+ *   r2    = (num * num) / (den * syy)
+ * THE OUTPUTS, each a device pointer or NULL, at least one given, all [F][E][R]:
+ *   speed_dev     (pitch_mm[r] * kf) / slope, in m/s;                NaN where the sample is not valid
+ *   modulus_dev   d3 * (speed * speed), in kPa;                      NaN where the sample is not valid
+ *   quality_dev   r2 > 1 ? 1 : r2 >= 0 ? r2 : +0.0f  (a NaN: 0);     +0.0f where the sample is not valid
+ * The input is read only; every element of every output given is written.  Asynchronous on the context's stream.  MCRT_ERR_INVALID
+ * for a null ctx, peak_time_dev, pitch_mm or o, zero sizes, options out of range (mcrt_shear_wave_frames' list), a pitch_mm[r] that is
+ * not finite and > 0, no output, an output that overlaps the input or another output; MCRT_ERR_LIMIT for n_rows > 2048 or a stack of
+ * 2^31 samples or more; on any error nothing is launched and nothing is written.  Groups: on mcrt_group_root(). */
+int mcrt_shear_speed_frames(mcrt_ctx *ctx, const float *peak_time_dev /* [F][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
+                            const float *pitch_mm /* [R] */, const mcrt_shear_opts *o, float *speed_dev /* [F][E][R] or NULL */,
+                            float *modulus_dev /* [F][E][R] or NULL */, float *quality_dev /* [F][E][R] or NULL */);
 
 /* device [E][R]  ->  host [R][E] row-major (the cv::Mat layout of rfimage.h:217); synchronous */
 int mcrt_export_rf(mcrt_ctx *ctx, const float *rf_dev, uint32_t n_elements, uint32_t n_rows, float *host_rows_by_cols);

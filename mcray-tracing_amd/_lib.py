@@ -101,6 +101,12 @@ class StrainOpts(C.Structure):
     _fields_ = [("window_rows", C.c_uint32), ("search_rows", C.c_uint32), ("lsq_rows", C.c_uint32), ("sigma", C.c_float), ("seed", C.c_uint32)]
 
 
+class ShearOpts(C.Structure):
+    """mcrt_shear_opts (include/mcrt.h): 48 bytes"""
+    _fields_ = [("n_pulses", C.c_uint32), ("window_rows", C.c_uint32), ("prf_hz", C.c_float), ("sigma", C.c_float), ("seed", C.c_uint32), ("push_line", C.c_uint32),
+                ("push_row0", C.c_uint32), ("push_rows", C.c_uint32), ("peak_q24", C.c_int32), ("speed_lines", C.c_uint32), ("avg_rows", C.c_uint32), ("density", C.c_float)]
+
+
 class ElastogramOpts(C.Structure):
     """mcrt_elastogram_opts (include/mcrt.h): 16 bytes"""
     _fields_ = [("ref_strain", C.c_float), ("rho_min", C.c_float), ("grey_min", C.c_uint32), ("alpha", C.c_uint32)]
@@ -192,6 +198,7 @@ assert C.sizeof(Bands) == 80 and Bands.band_weight.offset == 36 and Bands.var_x.
 assert C.sizeof(FlowOpts) == 32 and FlowOpts.prf_hz.offset == 16 and FlowOpts.seed.offset == 28 and C.sizeof(ColourOpts) == 12
 assert C.sizeof(SpectralOpts) == 32 and SpectralOpts.sigma.offset == 24 and C.sizeof(Gate) == 12 and C.sizeof(SonogramOpts) == 12
 assert C.sizeof(StrainOpts) == 20 and StrainOpts.sigma.offset == 12 and C.sizeof(ElastogramOpts) == 16 and ElastogramOpts.grey_min.offset == 8
+assert C.sizeof(ShearOpts) == 48 and ShearOpts.sigma.offset == 12 and ShearOpts.peak_q24.offset == 32 and ShearOpts.density.offset == 44
 
 # every symbol include/mcrt.h declares (tests/test_abi.py checks the .so exports each one)
 SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create", "mcrt_destroy", "mcrt_set_stream",
@@ -223,6 +230,8 @@ SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create"
            "mcrt_default_sonogram_opts", "mcrt_sonogram_frames",
            "mcrt_default_strain_opts", "mcrt_strain_table", "mcrt_strain_draws", "mcrt_strain_map", "mcrt_strain_compress_frames", "mcrt_strain_frames",
            "mcrt_default_elastogram_opts", "mcrt_elastogram_frames",
+           "mcrt_default_shear_opts", "mcrt_shear_table", "mcrt_shear_pitch", "mcrt_shear_shape", "mcrt_shear_decay", "mcrt_shear_draws", "mcrt_shear_map",
+           "mcrt_shear_wave_frames", "mcrt_shear_speed_frames",
            "mcrt_default_recon_opts", "mcrt_recon_transform", "mcrt_recon_frames",
            "mcrt_default_recon_label_opts", "mcrt_recon_label_frames", "mcrt_render_label_frames"]
 
@@ -346,6 +355,15 @@ def load_library():
         "mcrt_strain_map": [u32, vp],
         "mcrt_strain_compress_frames": [vp, vp, vp, u32, u32, u32, vp, u32, C.c_double, C.POINTER(StrainOpts), u32, vp, vp, vp, vp],
         "mcrt_strain_frames": [vp, vp, vp, u32, u32, u32, C.POINTER(StrainOpts), C.c_double, vp, vp, vp],
+        "mcrt_default_shear_opts": [C.POINTER(ShearOpts)],
+        "mcrt_shear_table": [vp, u32, C.c_double, vp, vp],
+        "mcrt_shear_pitch": [u32, u32, C.c_double, C.c_double, u32, u32, vp, vp],
+        "mcrt_shear_shape": [u32, vp],
+        "mcrt_shear_decay": [u32, C.c_double, vp],
+        "mcrt_shear_draws": [u32, u32, u32, u32, u32, vp],
+        "mcrt_shear_map": [u32, vp],
+        "mcrt_shear_wave_frames": [vp, vp, vp, u32, u32, u32, vp, vp, u32, vp, vp, u32, vp, u32, C.c_double, C.POINTER(ShearOpts), u32, vp, vp, vp, vp, vp, vp],
+        "mcrt_shear_speed_frames": [vp, vp, u32, u32, u32, vp, C.POINTER(ShearOpts), vp, vp, vp],
         "mcrt_default_elastogram_opts": [C.POINTER(ElastogramOpts)],
         "mcrt_elastogram_frames": [vp, vp, vp, vp, u32, u32, u32, vp, C.POINTER(ElastogramOpts), vp],
         "mcrt_default_recon_opts": [C.POINTER(ReconOpts)],

@@ -12,7 +12,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Bands, DetectOpts, FlowOpts, ColourOpts, SpectralOpts, Gate, SonogramOpts, StrainOpts, ElastogramOpts, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, Speckle3dOpts, NoiseOpts, AutogainOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Bands, DetectOpts, FlowOpts, ColourOpts, SpectralOpts, Gate, SonogramOpts, StrainOpts, ElastogramOpts, ShearOpts, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, Speckle3dOpts, NoiseOpts, AutogainOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 DEFAULT_ANGLE = 1.0471975511965976      # the sector of main.cpp:28: 60 degrees [rad]
 
@@ -352,6 +352,71 @@ def host_strain_map(kind=0):
     """mcrt_strain_map: the colour table of the elastogram, uint8 [256][3] (kind 0: stiff blue, the reference strain green at 128, soft red)"""
     lut = np.zeros((256, 3), np.uint8)
     check(load_library().mcrt_strain_map(int(kind) & 0xFFFFFFFF, ptr(lut)))
+    return lut
+
+
+def shear_opts_struct(n_pulses=None, window_rows=None, prf_hz=None, sigma=None, seed=None, push_line=None, push_row0=None, push_rows=None, peak_q24=None,
+                      speed_lines=None, avg_rows=None, density=None):
+    """mcrt_shear_opts from keywords over mcrt_default_shear_opts: n_pulses (4..256; 64), window_rows (0..16; 8), prf_hz (10000), sigma (0), seed,
+    push_line (0), push_row0 (0), push_rows (0: to the end of the line), peak_q24 (|.| <= 2^23; 1677722, 0.1 row), speed_lines (1..16; 4),
+    avg_rows (0..16; 2), density (g/cm^3; 1) -- the library checks the ranges"""
+    o = ShearOpts()
+    check(load_library().mcrt_default_shear_opts(C.byref(o)))
+    for name, v in (("n_pulses", n_pulses), ("window_rows", window_rows), ("seed", seed), ("push_line", push_line), ("push_row0", push_row0), ("push_rows", push_rows),
+                    ("speed_lines", speed_lines), ("avg_rows", avg_rows)):
+        if v is not None:
+            setattr(o, name, int(v) & 0xFFFFFFFF)
+    if peak_q24 is not None:
+        o.peak_q24 = int(peak_q24)
+    for name, v in (("prf_hz", prf_hz), ("sigma", sigma), ("density", density)):
+        if v is not None:
+            setattr(o, name, float(v))
+    return o
+
+
+def host_shear_table(speed_m_s, prf_hz=10000.0):
+    """mcrt_shear_table: (slow_q16 int64 [n_labels], speed_f float32 [n_labels]) of a shear speed per material [m/s] (0: a fluid, the wave
+    does not pass) at the tracking pulse rate"""
+    c = np.ascontiguousarray(speed_m_s, np.float64).reshape(-1)
+    slow = np.zeros(min(c.size, 254), np.int64); speed = np.zeros(min(c.size, 254), np.float32)
+    check(load_library().mcrt_shear_table(ptr(c), c.size, float(prf_hz), ptr(slow), ptr(speed)))
+    return slow, speed
+
+
+def host_shear_pitch(n_elements, n_rows, radius_mm, total_angle, max_travel_us=100, speed_of_sound=1500):
+    """mcrt_shear_pitch: (pitch_q8 uint32 [n_rows], pitch_mm float32 [n_rows]): the arc between neighbouring scan-lines at the depth of
+    every row, by host_scan_maps' geometry"""
+    rows = min(max(int(n_rows), 0), 2048)
+    q8 = np.zeros(rows, np.uint32); mm = np.zeros(rows, np.float32)
+    check(load_library().mcrt_shear_pitch(n_elements, n_rows, float(radius_mm), float(total_angle), max_travel_us, speed_of_sound, ptr(q8), ptr(mm)))
+    return q8, mm
+
+
+def host_shear_shape(width_pulses=12):
+    """mcrt_shear_shape: the default time profile of the particle displacement, a raised cosine of width_pulses, uint32 [64 * width_pulses] in Q16"""
+    s = np.zeros(64 * min(max(int(width_pulses), 0), 256), np.uint32)
+    check(load_library().mcrt_shear_shape(width_pulses, ptr(s) if s.size else None))
+    return s
+
+
+def host_shear_decay(n, d0_lines=8.0):
+    """mcrt_shear_decay: the default decay of the amplitude over line distance, 1 / sqrt(1 + d / d0_lines), uint32 [n] in Q16"""
+    a = np.zeros(max(int(n), 0), np.uint32)
+    check(load_library().mcrt_shear_decay(n, float(d0_lines), ptr(a) if a.size else None))
+    return a
+
+
+def host_shear_draws(seed, image_id, n_elements, n_rows, pulse):
+    """mcrt_shear_draws: the integer draws of one tracking pulse of one image, int32 [n_elements][n_rows][2] (noise = d * sigma / sqrt(1431655765))"""
+    d = np.zeros((max(int(n_elements), 0), min(max(int(n_rows), 0), 2048), 2), np.int32)
+    check(load_library().mcrt_shear_draws(int(seed) & 0xFFFFFFFF, int(image_id) & 0xFFFFFFFF, n_elements, n_rows, pulse, ptr(d)))
+    return d
+
+
+def host_shear_map(kind=0):
+    """mcrt_shear_map: the colour table of the shear-wave elastogram, uint8 [256][3] (kind 0: soft blue, the reference modulus green at 128, stiff red)"""
+    lut = np.zeros((256, 3), np.uint8)
+    check(load_library().mcrt_shear_map(int(kind) & 0xFFFFFFFF, ptr(lut)))
     return lut
 
 
@@ -1325,6 +1390,37 @@ class Context(_SceneCalls):
         check(self.L.mcrt_elastogram_frames(self.h, ptr(strain_img_dev), ptr(rho_img_dev), ptr(grey_dev), n_frames, height, width, ptr(table), C.byref(o),
                                             ptr(rgb_dev)))
 
+    def shear_wave_frames(self, iq_dev, tissue_dev, n_frames, n_elements, n_rows, slow_q16, speed_f, pitch_q8, shape_q16, amp_q16, cycles_per_row,
+                          first_image_id=0, sigma_dev=None, peak_time_dev=None, peak_disp_dev=None, disp_dev=None, truth_arrival_dev=None,
+                          truth_speed_dev=None, opts=None, **kw):
+        """mcrt_shear_wave_frames: the shear wave of a push, tracked over slow time, from the detected pairs [n_frames][E][R][2] and the tissue
+        labels [n_frames][E][R].  Host tables: slow_q16 int64 and speed_f float32 [n_labels] (host_shear_table), pitch_q8 uint32 [R]
+        (host_shear_pitch), shape_q16 (host_shear_shape) and amp_q16 (host_shear_decay) uint32; cycles_per_row: host_psf_carrier's.
+        Outputs, each a device pointer or None: peak_time_dev, peak_disp_dev, truth_arrival_dev, truth_speed_dev [n_frames][E][R] and disp_dev
+        [n_frames][n_pulses][E][R].  opts: a ShearOpts, or the keywords of shear_opts_struct"""
+        o = opts if opts is not None else shear_opts_struct(**kw)
+        slow = np.ascontiguousarray(slow_q16, np.int64).reshape(-1); speed = np.ascontiguousarray(speed_f, np.float32).reshape(-1)
+        if slow.size != speed.size:
+            raise ValueError("slow_q16 and speed_f take one entry per label, got %d and %d" % (slow.size, speed.size))
+        pitch = np.ascontiguousarray(pitch_q8, np.uint32).reshape(-1)
+        if pitch.size != n_rows:
+            raise ValueError("pitch_q8 takes one entry per row, got %d for %d rows" % (pitch.size, n_rows))
+        shape = np.ascontiguousarray(shape_q16, np.uint32).reshape(-1); amp = np.ascontiguousarray(amp_q16, np.uint32).reshape(-1)
+        check(self.L.mcrt_shear_wave_frames(self.h, ptr(iq_dev), ptr(tissue_dev), n_frames, n_elements, n_rows, ptr(slow), ptr(speed), slow.size, ptr(pitch),
+                                            ptr(shape), shape.size, ptr(amp), amp.size, float(cycles_per_row), C.byref(o), first_image_id, ptr(sigma_dev),
+                                            ptr(peak_time_dev), ptr(peak_disp_dev), ptr(disp_dev), ptr(truth_arrival_dev), ptr(truth_speed_dev)))
+
+    def shear_speed_frames(self, peak_time_dev, n_frames, n_elements, n_rows, pitch_mm, speed_dev=None, modulus_dev=None, quality_dev=None, opts=None, **kw):
+        """mcrt_shear_speed_frames: the least-squares slope of the time to peak [n_frames][E][R] across scan-lines -> speed_dev (m/s),
+        modulus_dev (kPa) and quality_dev (the r^2 of the fit), each [n_frames][E][R] or None.  pitch_mm: float32 [R], a host table
+        (host_shear_pitch).  opts: a ShearOpts, or the keywords of shear_opts_struct"""
+        o = opts if opts is not None else shear_opts_struct(**kw)
+        pitch = np.ascontiguousarray(pitch_mm, np.float32).reshape(-1)
+        if pitch.size != n_rows:
+            raise ValueError("pitch_mm takes one entry per row, got %d for %d rows" % (pitch.size, n_rows))
+        check(self.L.mcrt_shear_speed_frames(self.h, ptr(peak_time_dev), n_frames, n_elements, n_rows, ptr(pitch), C.byref(o), ptr(speed_dev), ptr(modulus_dev),
+                                             ptr(quality_dev)))
+
     def scan_convert_frames(self, rf_dev, n_frames, n_elements, n_rows, out_dev, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         check(self.L.mcrt_scan_convert_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, radius_mm, total_angle, ptr(out_dev), out_rows, out_cols))
 
@@ -1678,7 +1774,7 @@ class Simulator:
 
     def __init__(self, scene_data, transducer, n_samples=5, n_rows=None, device=0, seed=0x5EED, psf=None, texture=None,
                  max_depth=10, sanitize_tir=0, tex_n=256, bvh_builder="sah", elevation=False, compound=None, compound_mode="mean", compound_weights=None,
-                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0, speckle=None, noise=None, speckle3d=None, autogain=None, detect=None, flow=None, strain=None):
+                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0, speckle=None, noise=None, speckle3d=None, autogain=None, detect=None, flow=None, strain=None, shear=None):
         """elevation=True: slice thickness.  trace() then traces the psf's elevation_size planes of the frame as one pose pass -- plane k of
         frame f with frame id f * K + k, the frame-id rule of include/mcrt.h -- and folds them into rf_dev with psf.elevation_rows();
         everything after (convolve, bmode, frame) is unchanged.
@@ -1756,6 +1852,33 @@ class Simulator:
             opts = strain_opts_struct(sigma=sd.pop("noise", None), **sd)       # (unknown keywords end it here)
             self.strain_opts = dict(modulus=modulus, applied=applied, ref_modulus=ref_modulus, eps=host_strain_table(modulus, applied, ref_modulus),
                                     opts=opts, label=label)         # (a strain above the cap ends it here)
+        # shear={"LIVER": 1.5, "TUMOR": 3.0} -- a shear speed per material name of the scene [m/s] (0: a fluid, the wave does not pass) --, or a
+        # dict of speed_m_s= (that mapping), ref_speed_m_s= (2.0; a material that is not named takes it), push=(scan-line, depth_mm of the
+        # push's centre, length_mm) (None: push_line / push_row0 / push_rows as they are), width_pulses= (12) and decay_lines= (8.0) of the
+        # default time profile and decay, radius_mm= and total_angle= of the sector the pitch is taken from, ref_kpa= (the elastogram's
+        # middle; None: 3 density ref_speed^2), the keywords of shear_opts_struct (n_pulses, window_rows, prf_hz, seed, peak_q24,
+        # speed_lines, avg_rows, density, ...), noise= (the receiver noise per I/Q component of every tracking line, 0) and of the label
+        # pass (rule, start_offset): shear-wave elastography.  shear_wave() and shear_elastogram() then trace the frame ONCE, synthesise
+        # the tracked wave from that frame and estimate its speed.  Every other method is left alone.
+        self.shear_opts = _option(shear)
+        if self.shear_opts is not None:
+            sd = self.shear_opts if "speed_m_s" in self.shear_opts else dict(speed_m_s=self.shear_opts)
+            names = list(scene_data.material_names)
+            ref_speed = float(sd.pop("ref_speed_m_s", 2.0))
+            speeds = np.full(len(names), ref_speed, np.float64)
+            for name, v in dict(sd.pop("speed_m_s")).items():
+                if name not in names:
+                    raise ValueError("shear: the scene has no material %r (it has %s)" % (name, ", ".join(names)))
+                speeds[names.index(name)] = float(v)
+            label = dict(rule=sd.pop("rule", "traced"), start_offset=sd.pop("start_offset", None))
+            label_opts_struct(**label)                      # (an unknown rule ends it here)
+            push, ref_kpa = sd.pop("push", None), sd.pop("ref_kpa", None)
+            geometry = dict(radius_mm=float(sd.pop("radius_mm", 30.0)), total_angle=float(sd.pop("total_angle", DEFAULT_ANGLE)))
+            shape, decay = host_shear_shape(int(sd.pop("width_pulses", 12))), float(sd.pop("decay_lines", 8.0))
+            opts = shear_opts_struct(sigma=sd.pop("noise", None), **sd)        # (unknown keywords end it here)
+            slow, speed_f = host_shear_table(speeds, opts.prf_hz)             # (a speed out of range ends it here)
+            self.shear_opts = dict(speeds=speeds, slow=slow, speed_f=speed_f, shape=shape, decay=decay, push=push, geometry=geometry, opts=opts, label=label,
+                                   ref_kpa=3.0 * opts.density * ref_speed * ref_speed if ref_kpa is None else float(ref_kpa))
         self.flow = _option(flow)
         if self.flow is not None:
             fd = self.flow if "velocity_mm_s" in self.flow else dict(velocity_mm_s=self.flow)
@@ -2407,6 +2530,86 @@ class Simulator:
                                        ref_strain=self.strain_opts["applied"] if ref_strain is None else ref_strain)
             return dict(self._strain_host(b), rgb=self.ctx.d2h(rgb, (rows, cols, 3), np.uint8), grey=self.ctx.d2h(grey, (rows, cols), np.uint8),
                         strain_img=self.ctx.d2h(img, (rows, cols), np.float32), rho_img=self.ctx.d2h(img + 4 * n, (rows, cols), np.float32))
+
+    # ---- shear-wave elastography (shear=)
+    SHEAR_MAPS = ("speed", "modulus", "quality", "peak_time", "peak_disp", "truth_arrival", "truth_speed")
+
+    @contextlib.contextmanager
+    def _shear_pass(self, frame_id):
+        """ONE trace of the frame -> the label pass -> frame()'s stages -> the detector's I/Q -> mcrt_shear_wave_frames ->
+        mcrt_shear_speed_frames.  Yields dict(tissue, iq and SHEAR_MAPS: device buffers that live as long as the block); rf_dev holds the
+        frame's RF before the envelope"""
+        if self.shear_opts is None:
+            raise RuntimeError("shear-wave imaging needs Simulator(shear=...)")
+        for on, what in ((self.sweep is not None, "sweep="), (self.steers is not None, "compound="), (self.elevation, "elevation="), (self.psf.has_bands, "a psf with bands")):
+            if on:
+                raise RuntimeError("shear-wave imaging is one plane of one pulse: it does not combine with %s" % what)
+        sh, n, o = self.shear_opts, self.E * self.R, self.shear_opts["opts"]
+        if sh["push"] is not None:
+            line, depth_mm, length_mm = int(sh["push"][0]), float(sh["push"][1]), float(sh["push"][2])
+            if not 0 <= line < self.E:
+                raise ValueError("shear: scan-line %d is not in 0..%d" % (line, self.E - 1))
+            pitch = row_pitch_mm(self.tr.frequency)
+            rows = min(max(int(round(length_mm / pitch)), 1), self.R)
+            o.push_line, o.push_rows = line, rows
+            o.push_row0 = min(max(int(round(depth_mm / pitch - rows / 2.0)), 0), self.R - rows)
+        prm = self.ctx.params
+        travel = int((prm.depth_cm / float(prm.speed_of_sound)) * 10000.0)
+        pitch_q8, pitch_mm = host_shear_pitch(self.E, self.R, max_travel_us=travel, speed_of_sound=int(prm.speed_of_sound), **sh["geometry"])
+        cycles = host_psf_carrier(self.tr.frequency, self.psf.resolution_um)
+        with contextlib.ExitStack() as held:
+            tissue, iq = (held.enter_context(self.ctx.temp(size)) for size in (n, 8 * n))
+            out = {k: held.enter_context(self.ctx.temp(4 * n)) for k in self.SHEAR_MAPS}
+            self.trace(frame_id)
+            self.ctx.label_frames(tissue_dev=tissue, **sh["label"])
+            self._stages(self._stack, frame_id, envelope=False)
+            self.ctx.detect_frames(self.rf_dev, 1, self.E, self.R, iq_dev=iq, **(self.detect or {}))
+            self.ctx.shear_wave_frames(iq, tissue, 1, self.E, self.R, sh["slow"], sh["speed_f"], pitch_q8, sh["shape"], host_shear_decay(self.E, sh["decay"]), cycles,
+                                       first_image_id=frame_id, peak_time_dev=out["peak_time"], peak_disp_dev=out["peak_disp"],
+                                       truth_arrival_dev=out["truth_arrival"], truth_speed_dev=out["truth_speed"], opts=o)
+            self.ctx.shear_speed_frames(out["peak_time"], 1, self.E, self.R, pitch_mm, speed_dev=out["speed"], modulus_dev=out["modulus"],
+                                        quality_dev=out["quality"], opts=o)
+            yield dict(out, tissue=tissue, iq=iq)
+
+    def _shear_host(self, b):
+        return {k: self.ctx.d2h(b[k], (self.E, self.R), np.float32) for k in self.SHEAR_MAPS}
+
+    def shear_wave(self, frame_id=0):
+        """the shear wave of a push in beam space -> dict(speed [m/s], modulus [kPa], quality (the r^2 of the fit), peak_time [pulses],
+        peak_disp [rows], truth_arrival [pulses, +inf: never] and truth_speed [m/s]: float32 [E][R]), the truths registered sample for
+        sample (shear= only)"""
+        with self._shear_pass(frame_id) as b:
+            return self._shear_host(b)
+
+    def shear_elastogram(self, frame_id=0, ref_kpa=None, quality_min=None, grey_min=None, alpha=None, lut=None, **display):
+        """the shear-wave elastogram of a frame -> dict(rgb uint8 [out_rows][out_cols][3], grey uint8 [out_rows][out_cols], modulus_img and
+        quality_img float32 [out_rows][out_cols], and shear_wave()'s beam-space outputs).  It traces ONCE; grey is bmode()'s own picture of
+        that trace (display: the keywords of Context.bmode_frames), the modulus and the quality are gathered through
+        mcrt_scan_convert_frames and laid over it by mcrt_elastogram_frames as they are, with host_shear_map()'s table (soft blue, stiff
+        red); ref_kpa defaults to shear=...'s; a radius_mm or total_angle other than shear=...'s, the sector the pitch was taken from, is
+        refused (shear= only)"""
+        if display.get("persistence", 0.0) != 0.0:
+            raise ValueError("shear_elastogram() shows one frame: persistence is left out")
+        for k, v in (self.shear_opts or {}).get("geometry", {}).items():
+            if float(display.get(k, v)) != v:               # the speed is scaled by the pitch of one sector: the picture is drawn in the same
+                raise ValueError("shear_elastogram(): %s=%r differs from shear=...'s %r, the sector the scan-line pitch was taken from" % (k, display[k], v))
+        rows, cols = display.get("out_rows", 400), display.get("out_cols", 500)
+        geometry = {k: display[k] for k in ("radius_mm", "total_angle", "out_rows", "out_cols") if k in display}
+        n = rows * cols
+        with self._shear_pass(frame_id) as b, self.ctx.temp(n) as grey, self.ctx.temp(8 * n) as img, self.ctx.temp(3 * n) as rgb:
+            s = self._images(frame_id)
+            self._detect(s, s)                              # bmode()'s remaining stages over the same trace
+            if self.speckle is not None:
+                self._despeckle(s)
+            if self.autogain is not None:
+                self._autogain(s)
+            self.ctx.bmode_frames(self.rf_dev, 1, self.E, self.R, grey, **display)
+            self.ctx.scan_convert_frames(b["modulus"], 1, self.E, self.R, img, **geometry)
+            self.ctx.scan_convert_frames(b["quality"], 1, self.E, self.R, img + 4 * n, **geometry)
+            self.ctx.elastogram_frames(img, img + 4 * n, grey, 1, rows, cols, rgb, lut=host_shear_map() if lut is None else lut, rho_min=quality_min,
+                                       grey_min=grey_min, alpha=alpha, ref_strain=self.shear_opts["ref_kpa"] if ref_kpa is None else ref_kpa)
+            return dict(self._shear_host(b), rgb=self.ctx.d2h(rgb, (rows, cols, 3), np.uint8), grey=self.ctx.d2h(grey, (rows, cols), np.uint8),
+                        modulus_img=self.ctx.d2h(img, (rows, cols), np.float32), quality_img=self.ctx.d2h(img + 4 * n, (rows, cols), np.float32))
 
     def colour_flow(self, frame_id=0, **display):
         """the colour-flow picture of a frame -> dict(rgb uint8 [out_rows][out_cols][3], grey uint8 [out_rows][out_cols], velocity float32

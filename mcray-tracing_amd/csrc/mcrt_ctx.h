@@ -225,6 +225,10 @@ struct ImageStages {
     // strain elastography: the last strain table [n_labels] of mcrt_strain_compress_frames (its rotor is spec_rotor), the displacement
     // [F][E][R] of the largest mcrt_strain_frames so far that gave no disp_dev, and the last colour table of mcrt_elastogram_frames
     StagedWords strain_eps; Buf<float> d_strain_disp; StagedTable elasto_lut;
+    // shear-wave elastography: the last host tables of mcrt_shear_wave_frames (the slownesses [n_labels] as word pairs, the true speeds
+    // [n_labels], the pitches [R], the time profile [n_shape] and the decay [n_amp]; its rotor is spec_rotor) and of mcrt_shear_speed_frames
+    // (the pitches in mm [R]), and the arrival ticks [F][E][R] of the largest mcrt_shear_wave_frames so far
+    StagedWords shear_slow, shear_speed, shear_pitch, shear_shape, shear_amp, shear_pitch_mm; Buf<long long> d_shear_arrival;
     // automatic gain (mcrt_autogain_frames): the histograms of a chunk of frames [frames][n_bands][2048], at most AUTOGAIN_HIST_WORDS, and the row
     // gains [n_frames][R] of the largest call so far that gave no gain_dev
     Buf<uint32_t> d_aghist; Buf<float> d_aggain;

@@ -1293,15 +1293,142 @@ extern "C" int mcrt_strain_draws(uint32_t seed, uint32_t image_id, uint32_t n_el
     return MCRT_OK;
 }
 
+// kind 0 of mcrt_strain_map and of mcrt_shear_map: blue at 0 through green at 128 to red, in integer arithmetic
+static void blue_green_red(uint8_t *lut)
+{
+    for (uint32_t i = 0; i < 256u; i++) {
+        const uint32_t u = i <= 128u ? (2u * i > 255u ? 255u : 2u * i) : 2u * (i - 128u);
+        lut[3u * i] = (uint8_t)(i <= 128u ? 0u : u); lut[3u * i + 1u] = (uint8_t)(i <= 128u ? u : 255u - u); lut[3u * i + 2u] = (uint8_t)(i <= 128u ? 255u - u : 0u);
+    }
+}
+
 extern "C" int mcrt_strain_map(uint32_t kind, uint8_t *lut)
 {
     static const char fn[] = "mcrt_strain_map";
     if (!lut) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null lut", fn);
     if (kind != 0u) return mcrt::set_error(MCRT_ERR_INVALID, "%s: unknown kind %u", fn, kind);
-    for (uint32_t i = 0; i < 256u; i++) {
-        const uint32_t u = i <= 128u ? (2u * i > 255u ? 255u : 2u * i) : 2u * (i - 128u);
-        lut[3u * i] = (uint8_t)(i <= 128u ? 0u : u); lut[3u * i + 1u] = (uint8_t)(i <= 128u ? u : 255u - u); lut[3u * i + 2u] = (uint8_t)(i <= 128u ? 255u - u : 0u);
+    blue_green_red(lut);
+    return MCRT_OK;
+}
+
+// ---- shear-wave elastography (the contracts are in include/mcrt.h) ---------------------------------------
+extern "C" int mcrt_default_shear_opts(mcrt_shear_opts *o)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_shear_opts: null options");
+    o->n_pulses = 64u; o->window_rows = 8u; o->prf_hz = 10000.0f; o->sigma = 0.0f; o->seed = 0x53484552u;
+    o->push_line = 0u; o->push_row0 = 0u; o->push_rows = 0u; o->peak_q24 = 1677722; o->speed_lines = 4u; o->avg_rows = 2u; o->density = 1.0f;
+    return MCRT_OK;
+}
+
+int mcrt::shear_check(const char *fn, const mcrt_shear_opts *o, uint32_t E, uint32_t R)
+{
+    if (o->n_pulses < 4u || o->n_pulses > 256u) return set_error(MCRT_ERR_INVALID, "%s: n_pulses must be 4 .. 256 (%u)", fn, o->n_pulses);
+    if (o->window_rows > 16u) return set_error(MCRT_ERR_INVALID, "%s: window_rows must be 0 .. 16 (%u)", fn, o->window_rows);
+    if (!(std::isfinite(o->prf_hz) && o->prf_hz > 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: prf_hz must be finite and > 0 (%g)", fn, (double)o->prf_hz);
+    if (!(std::isfinite(o->sigma) && o->sigma >= 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: sigma must be finite and >= 0 (%g)", fn, (double)o->sigma);
+    if (o->peak_q24 > 8388608 || o->peak_q24 < -8388608) return set_error(MCRT_ERR_INVALID, "%s: peak_q24 must be within +-2^23 (%d)", fn, o->peak_q24);
+    if (o->push_line >= E) return set_error(MCRT_ERR_INVALID, "%s: push_line %u is not one of the %u scan-lines", fn, o->push_line, E);
+    if (o->push_row0 >= R || (uint64_t)o->push_row0 + o->push_rows > R)
+        return set_error(MCRT_ERR_INVALID, "%s: the pushed rows %u + %u pass the scan-line's %u", fn, o->push_row0, o->push_rows, R);
+    if (o->speed_lines < 1u || o->speed_lines > 16u) return set_error(MCRT_ERR_INVALID, "%s: speed_lines must be 1 .. 16 (%u)", fn, o->speed_lines);
+    if (o->avg_rows > 16u) return set_error(MCRT_ERR_INVALID, "%s: avg_rows must be 0 .. 16 (%u)", fn, o->avg_rows);
+    if (!(std::isfinite(o->density) && o->density > 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: density must be finite and > 0 (%g)", fn, (double)o->density);
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_shear_table(const double *speed_m_s, uint32_t n_labels, double prf_hz, int64_t *slow_q16, float *speed_f)
+{
+    static const char fn[] = "mcrt_shear_table";
+    if (!speed_m_s || !slow_q16 || !speed_f) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (n_labels == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: n_labels is zero", fn);
+    if (n_labels > 254u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: at most 254 labels (%u)", fn, n_labels);
+    if (!(std::isfinite(prf_hz) && prf_hz > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: prf_hz must be finite and > 0 (%g)", fn, prf_hz);
+    std::vector<int64_t> slow(n_labels);
+    for (uint32_t l = 0; l < n_labels; l++) {
+        const double c = speed_m_s[l];
+        if (!(std::isfinite(c) && c >= 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: speed_m_s[%u] must be finite and >= 0 (%g)", fn, l, c);
+        slow[l] = 0;
+        if (c == 0.0) continue;
+        const double s = 65536.0 * 65536.0 * prf_hz / (c * 1e6);
+        if (!(s >= 0.5 && s <= 274877906944.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: the slowness of label %u (%g m/s at %g Hz) is outside [1, 2^38] ticks per um in Q16", fn, l, c, prf_hz);
+        slow[l] = (int64_t)std::llrint(s);
+        if (slow[l] < 1) return mcrt::set_error(MCRT_ERR_INVALID, "%s: the slowness of label %u (%g m/s at %g Hz) is outside [1, 2^38] ticks per um in Q16", fn, l, c, prf_hz);
     }
+    memcpy(slow_q16, slow.data(), 8 * (size_t)n_labels);
+    for (uint32_t l = 0; l < n_labels; l++) speed_f[l] = (float)speed_m_s[l];
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_shear_pitch(uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t max_travel_us, uint32_t speed_of_sound,
+                                uint32_t *pitch_q8, float *pitch_mm)
+{
+    static const char fn[] = "mcrt_shear_pitch";
+    if (!pitch_q8 && !pitch_mm) return mcrt::set_error(MCRT_ERR_INVALID, "%s: no output is given", fn);
+    if (E == 0 || R == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_elements %u, n_rows %u)", fn, E, R);
+    if (!(std::isfinite(radius_mm) && radius_mm >= 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: radius_mm must be finite and >= 0 (%g)", fn, radius_mm);
+    if (!(std::isfinite(total_angle) && total_angle > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: total_angle_rad must be finite and > 0 (%g)", fn, total_angle);
+    if ((uint32_t)(max_travel_us * speed_of_sound) == 0u) return mcrt::set_error(MCRT_ERR_INVALID, "%s: max_travel_us * speed_of_sound is zero", fn);
+    if (R > 2048u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: n_rows: at most 2048 rows (%u)", fn, R);
+    const double depth_mm = (double)(uint32_t)(max_travel_us * speed_of_sound) * 0.001;
+    std::vector<double> um(R);
+    for (uint32_t r = 0; r < R; r++) {
+        um[r] = 1000.0 * (radius_mm + (double)r * depth_mm / (double)R) * total_angle / (double)E;
+        if (!(256.0 * um[r] >= 0.5 && 256.0 * um[r] < 16777215.5)) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: the pitch of row %u, %g um, is outside (0, 65536)", fn, r, um[r]);
+    }
+    for (uint32_t r = 0; r < R; r++) {
+        if (pitch_q8) pitch_q8[r] = (uint32_t)std::llrint(256.0 * um[r]);
+        if (pitch_mm) pitch_mm[r] = (float)(um[r] * 0.001);
+    }
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_shear_shape(uint32_t width_pulses, uint32_t *shape_q16)
+{
+    static const char fn[] = "mcrt_shear_shape";
+    if (!shape_q16) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null table", fn);
+    if (width_pulses == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: width_pulses is zero", fn);
+    if (width_pulses > 256u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: at most 256 pulses (%u)", fn, width_pulses);
+    const uint32_t n = 64u * width_pulses;
+    for (uint32_t i = 0; i < n; i++) shape_q16[i] = (uint32_t)std::llrint(65536.0 * (0.5 - 0.5 * std::cos(6.283185307179586 * ((double)i + 0.5) / (double)n)));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_shear_decay(uint32_t n, double d0_lines, uint32_t *amp_q16)
+{
+    static const char fn[] = "mcrt_shear_decay";
+    if (!amp_q16) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null table", fn);
+    if (n == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: n is zero", fn);
+    if (!(std::isfinite(d0_lines) && d0_lines > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: d0_lines must be finite and > 0 (%g)", fn, d0_lines);
+    for (uint32_t d = 0; d < n; d++) amp_q16[d] = (uint32_t)std::llrint(65536.0 / std::sqrt(1.0 + (double)d / d0_lines));
+    return MCRT_OK;
+}
+
+// the draws k_shear_track makes for one tracking pulse of one image, [E][R][2]
+extern "C" int mcrt_shear_draws(uint32_t seed, uint32_t image_id, uint32_t n_elements, uint32_t n_rows, uint32_t pulse, int32_t *d)
+{
+    static const char fn[] = "mcrt_shear_draws";
+    if (!d) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null d", fn);
+    if (n_elements == 0 || n_rows == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_elements %u, n_rows %u)", fn, n_elements, n_rows);
+    if (n_rows > 2048u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: n_rows: at most 2048 rows (%u)", fn, n_rows);
+    if (pulse >= 256u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: pulse: at most 256 pulses (%u)", fn, pulse);
+    for (uint32_t e = 0; e < n_elements; e++)
+        for (uint32_t r = 0; r < n_rows; r++) {
+            uint32_t o[4];
+            host_philox4x32_10(e, r, 0x53484552u, pulse, seed, image_id, o);
+            int32_t *p = d + 2u * ((size_t)e * n_rows + r);
+            p[0] = (int32_t)((o[0] & 0xffffu) + (o[0] >> 16) + (o[1] & 0xffffu) + (o[1] >> 16)) - 131070;
+            p[1] = (int32_t)((o[2] & 0xffffu) + (o[2] >> 16) + (o[3] & 0xffffu) + (o[3] >> 16)) - 131070;
+        }
+    return MCRT_OK;
+}
+
+// (mcrt_strain_map's table: the index is the modulus over the reference, so blue is soft here where it is stiff there)
+extern "C" int mcrt_shear_map(uint32_t kind, uint8_t *lut)
+{
+    static const char fn[] = "mcrt_shear_map";
+    if (!lut) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null lut", fn);
+    if (kind != 0u) return mcrt::set_error(MCRT_ERR_INVALID, "%s: unknown kind %u", fn, kind);
+    blue_green_red(lut);
     return MCRT_OK;
 }
 

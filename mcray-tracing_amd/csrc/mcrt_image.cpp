@@ -438,6 +438,99 @@ extern "C" int mcrt_strain_frames(mcrt_ctx *c, const float *pre_iq_dev, const fl
     return MCRT_OK;
 }
 
+// ---- shear-wave elastography (the contracts are in include/mcrt.h; the defaults, the option ranges, the tables, the draws and the colour
+// table are host code: mcrt_host.cpp).  Each call checks everything before anything is enqueued. ----
+static int shear_sizes(const char *fn, uint32_t n_frames, uint32_t E, uint32_t R)
+{
+    if (n_frames == 0 || E == 0 || R == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_frames %u, n_elements %u, n_rows %u)", fn, n_frames, E, R);
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: n_rows: at most %d rows (%u)", fn, MCRT_MAX_ROWS, R);
+    if ((double)n_frames * (double)E * (double)R >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: a stack of 2^31 samples or more (%u x %u x %u)", fn, n_frames, E, R);
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_shear_wave_frames(mcrt_ctx *c, const float *iq_dev, const uint8_t *tissue_dev, uint32_t n_frames, uint32_t E, uint32_t R, const int64_t *slow_q16,
+                                      const float *speed_f, uint32_t n_labels, const uint32_t *pitch_q8, const uint32_t *shape_q16, uint32_t n_shape,
+                                      const uint32_t *amp_q16, uint32_t n_amp, double cycles_per_row, const mcrt_shear_opts *o, uint32_t first_image_id,
+                                      const float *sigma_dev, float *peak_time_dev, float *peak_disp_dev, float *disp_dev, float *truth_arrival_dev,
+                                      float *truth_speed_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_shear_wave_frames";
+    if (!iq_dev || !tissue_dev || !slow_q16 || !speed_f || !pitch_q8 || !shape_q16 || !amp_q16 || !o) return set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (n_labels == 0 || n_shape == 0 || n_amp == 0) return set_error(MCRT_ERR_INVALID, "%s: an empty table (n_labels %u, n_shape %u, n_amp %u)", fn, n_labels, n_shape, n_amp);
+    MCRT_TRY(shear_sizes(fn, n_frames, E, R));
+    if (!(cycles_per_row > 0.0 && cycles_per_row <= 0.5)) return set_error(MCRT_ERR_INVALID, "%s: cycles_per_row must be in (0, 0.5] (%g)", fn, cycles_per_row);
+    MCRT_TRY(mcrt::shear_check(fn, o, E, R));
+    if (!peak_time_dev && !peak_disp_dev && !disp_dev && !truth_arrival_dev && !truth_speed_dev) return set_error(MCRT_ERR_INVALID, "%s: no output is given", fn);
+    if (n_labels > 254u) return set_error(MCRT_ERR_LIMIT, "%s: at most 254 labels (%u)", fn, n_labels);
+    if (n_shape > 16384u) return set_error(MCRT_ERR_LIMIT, "%s: at most 16384 entries of the time profile (%u)", fn, n_shape);
+    if (n_amp > 65536u) return set_error(MCRT_ERR_LIMIT, "%s: at most 65536 entries of the decay (%u)", fn, n_amp);
+    const uint32_t T = o->n_pulses;
+    if (disp_dev && (double)n_frames * (double)T * (double)E * (double)R >= 0x1p31)
+        return set_error(MCRT_ERR_LIMIT, "%s: a movie of 2^31 samples or more (%u x %u x %u x %u)", fn, n_frames, T, E, R);
+    if ((uint64_t)first_image_id + n_frames > 0x100000000ull) return set_error(MCRT_ERR_LIMIT, "%s: first_image_id: the ids of %u images from %u on pass 2^32", fn, n_frames, first_image_id);
+    for (uint32_t l = 0; l < n_labels; l++)
+        if (slow_q16[l] < 0 || slow_q16[l] > (1ll << 38)) return set_error(MCRT_ERR_INVALID, "%s: slow_q16[%u] = %lld is outside [0, 2^38]", fn, l, (long long)slow_q16[l]);
+    for (uint32_t r = 0; r < R; r++)
+        if (pitch_q8[r] == 0u || pitch_q8[r] >= (1u << 24)) return set_error(MCRT_ERR_INVALID, "%s: pitch_q8[%u] = %u is outside [1, 2^24)", fn, r, pitch_q8[r]);
+    for (uint32_t i = 0; i < n_shape; i++)
+        if (shape_q16[i] > 65536u) return set_error(MCRT_ERR_INVALID, "%s: shape_q16[%u] = %u is above 65536", fn, i, shape_q16[i]);
+    for (uint32_t i = 0; i < n_amp; i++)
+        if (amp_q16[i] > 65536u) return set_error(MCRT_ERR_INVALID, "%s: amp_q16[%u] = %u is above 65536", fn, i, amp_q16[i]);
+    const size_t n = (size_t)n_frames * E * R;
+    const Range outs[5] = { { peak_time_dev, 4 * n, "peak_time_dev" }, { peak_disp_dev, 4 * n, "peak_disp_dev" }, { disp_dev, 4 * n * T, "disp_dev" },
+                            { truth_arrival_dev, 4 * n, "truth_arrival_dev" }, { truth_speed_dev, 4 * n, "truth_speed_dev" } };
+    const Range ins[3] = { { iq_dev, 8 * n, "iq_dev" }, { tissue_dev, n, "tissue_dev" }, { sigma_dev, 4 * (size_t)n_frames, "sigma_dev" } };
+    for (int i = 0; i < 3; i++)
+        if (ins[i].p) MCRT_TRY(check_overlap(fn, ins[i], outs, 5, i == 0));      // (iq_dev is always there: the outputs among themselves once)
+    if (n > c->img.d_shear_arrival.cap) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(c->img.d_shear_arrival.alloc(n));
+    }
+    static const std::vector<float> rotor = [] { std::vector<float> l(8192); mcrt_spectral_rotor(l.data()); return l; }();
+    MCRT_TRY(c->img.spec_rotor.put(rotor.data(), 8192, c->stream));
+    MCRT_TRY(c->img.shear_slow.put(slow_q16, 2 * (size_t)n_labels, c->stream));
+    MCRT_TRY(c->img.shear_speed.put(speed_f, n_labels, c->stream));
+    MCRT_TRY(c->img.shear_pitch.put(pitch_q8, R, c->stream));
+    MCRT_TRY(c->img.shear_shape.put(shape_q16, n_shape, c->stream));
+    MCRT_TRY(c->img.shear_amp.put(amp_q16, n_amp, c->stream));
+    mcrt::ShearWaveArgs a; memset(&a, 0, sizeof a);
+    a.iq = (const float2 *)iq_dev; a.tissue = tissue_dev; a.slow = c->img.shear_slow.as<long long>(); a.speed_f = c->img.shear_speed.as<float>();
+    a.pitch = c->img.shear_pitch.as<uint32_t>(); a.shape = c->img.shear_shape.as<uint32_t>(); a.amp = c->img.shear_amp.as<uint32_t>();
+    a.lut = c->img.spec_rotor.as<float2>(); a.sigma_dev = sigma_dev; a.arrival = c->img.d_shear_arrival;
+    a.peak_time = peak_time_dev; a.peak_disp = peak_disp_dev; a.disp = disp_dev; a.truth_arrival = truth_arrival_dev; a.truth_speed = truth_speed_dev;
+    a.carrier_q32 = std::llrint(cycles_per_row * 4294967296.0);
+    a.F = n_frames; a.E = E; a.R = R; a.chunks = (R + SHEAR_TILE_ROWS - 1u) / SHEAR_TILE_ROWS; a.n_labels = n_labels; a.n_shape = n_shape; a.n_amp = n_amp;
+    a.T = T; a.window = o->window_rows; a.push_line = o->push_line; a.row0 = o->push_row0; a.row1 = o->push_rows ? o->push_row0 + o->push_rows : R;
+    a.peak_q24 = o->peak_q24; a.seed = o->seed; a.first_id = first_image_id; a.sigma = o->sigma; a.inv_std = (float)(1.0 / std::sqrt(1431655765.0));
+    a.scale = (float)(1.0 / (6.283185307179586 * cycles_per_row));
+    HIP_TRY(mcrt::launch_shear_wave(a, c->stream));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_shear_speed_frames(mcrt_ctx *c, const float *peak_time_dev, uint32_t n_frames, uint32_t E, uint32_t R, const float *pitch_mm,
+                                       const mcrt_shear_opts *o, float *speed_dev, float *modulus_dev, float *quality_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_shear_speed_frames";
+    if (!peak_time_dev || !pitch_mm || !o) return set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    MCRT_TRY(shear_sizes(fn, n_frames, E, R));
+    MCRT_TRY(mcrt::shear_check(fn, o, E, R));
+    if (!speed_dev && !modulus_dev && !quality_dev) return set_error(MCRT_ERR_INVALID, "%s: no output is given", fn);
+    for (uint32_t r = 0; r < R; r++)
+        if (!(std::isfinite(pitch_mm[r]) && pitch_mm[r] > 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: pitch_mm[%u] must be finite and > 0 (%g)", fn, r, (double)pitch_mm[r]);
+    const size_t n = (size_t)n_frames * E * R;
+    const Range outs[3] = { { speed_dev, 4 * n, "speed_dev" }, { modulus_dev, 4 * n, "modulus_dev" }, { quality_dev, 4 * n, "quality_dev" } };
+    MCRT_TRY(check_overlap(fn, Range{ peak_time_dev, 4 * n, "peak_time_dev" }, outs, 3, true));
+    MCRT_TRY(c->img.shear_pitch_mm.put(pitch_mm, R, c->stream));
+    mcrt::ShearSpeedArgs a; memset(&a, 0, sizeof a);
+    a.peak_time = peak_time_dev; a.pitch_mm = c->img.shear_pitch_mm.as<float>(); a.speed = speed_dev; a.modulus = modulus_dev; a.quality = quality_dev;
+    a.F = n_frames; a.E = E; a.R = R; a.chunks = (R + SHEAR_TILE_ROWS - 1u) / SHEAR_TILE_ROWS; a.push_line = o->push_line; a.lines = o->speed_lines; a.avg = o->avg_rows;
+    a.kf = (float)((double)o->prf_hz * 0.001); a.d3 = 3.0f * o->density;
+    HIP_TRY(mcrt::launch_shear_speed(a, c->stream));
+    return MCRT_OK;
+}
+
 // the scan-conversion maps of a geometry on the device, in cache m: the plain maps (cp null: mcrt_scan_maps, one view) or the N views of a steer
 // list (mcrt_compound_maps), [N][2][n_pad]
 static int ensure_maps(mcrt_ctx *c, MapCache &m, uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t orows, uint32_t ocols, const mcrt_compound *cp, const float **maps)

@@ -82,5 +82,7 @@ int flow_check(const char *fn, const mcrt_flow_opts *o);
 int spectral_check(const char *fn, const mcrt_spectral_opts *o);
 // mcrt_host.cpp: the ranges of mcrt_strain_opts, which mcrt_strain_compress_frames and mcrt_strain_frames share
 int strain_check(const char *fn, const mcrt_strain_opts *o);
+// mcrt_host.cpp: the ranges of mcrt_shear_opts against a stack of E scan-lines of R rows, which mcrt_shear_wave_frames and mcrt_shear_speed_frames share
+int shear_check(const char *fn, const mcrt_shear_opts *o, uint32_t E, uint32_t R);
 }
 #endif

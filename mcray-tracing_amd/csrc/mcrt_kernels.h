@@ -20,6 +20,7 @@
 //   mcrt_flow.hip    k_flow_split, k_flow<N, WALL>, k_flow_avg (colour Doppler: mcrt_flow_split_frames, mcrt_flow_frames), k_colour (mcrt_colour_frames)
 //   mcrt_spectral.hip k_gate_series (spectral Doppler: mcrt_spectral_series_frames), k_spectrum<N> (mcrt_spectral_frames), k_sonogram_peak, k_sonogram (mcrt_sonogram_frames)
 //   mcrt_strain.hip  k_strain_warp (strain elastography: mcrt_strain_compress_frames), k_strain_track, k_strain_slope (mcrt_strain_frames), k_elastogram (mcrt_elastogram_frames)
+//   mcrt_shear.hip   k_shear_arrival, k_shear_track (shear-wave elastography: mcrt_shear_wave_frames), k_shear_speed (mcrt_shear_speed_frames); mcrt_warp.h: the line reading it shares with k_strain_warp
 //   mcrt_autogain.hip k_autogain_hist, k_autogain_curve, k_autogain_apply (automatic gain: mcrt_autogain_frames)
 //   mcrt_recon.hip   k_recon_splat, k_recon_resolve (freehand 3-D reconstruction: mcrt_recon_frames)
 //   mcrt_label.hip   k_label (ground-truth label maps: mcrt_label_frames), k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames)
@@ -495,6 +496,42 @@ struct ElastogramArgs {
     PixelPass pass;
 };
 hipError_t launch_elastogram(const ElastogramArgs &a, hipStream_t st);
+// k_shear_arrival and k_shear_track (mcrt_shear_wave_frames): the detected pairs and the tissue labels -> the arrival ticks, the tracked displacement's
+// peak and the truths
+#define SHEAR_TILE_ROWS 64u                         // a wavefront of k_shear_track owns 64 consecutive rows of one scan-line, a lane one of them
+#define SHEAR_MAX_WINDOW 16u                        // the largest window_rows: it sizes the tile's LDS
+#define SHEAR_NEVER (1ll << 40)                     // ticks: a blocked crossing, and the arrival that never comes
+#define SHEAR_SHAPE_SHIFT 10                        // ticks per entry of the shape table: 1/64 pulse
+struct ShearWaveArgs {
+    const float2 *iq;                   // [F][E][R] (I, Q)
+    const uint8_t *tissue;              // [F][E][R]
+    const long long *slow;              // [n_labels] Q16 ticks per um, 0: blocked (the context's copy, as the next four)
+    const float *speed_f;               // [n_labels]
+    const uint32_t *pitch;              // [R] Q8 um
+    const uint32_t *shape, *amp;        // [n_shape], [n_amp] Q16
+    const float2 *lut;                  // [4096] the rotor (the context's copy)
+    const float *sigma_dev;             // [F] or null: sigma
+    long long *arrival;                 // [F][E][R] ticks: the context's buffer
+    float *peak_time, *peak_disp;       // [F][E][R], each or null
+    float *disp;                        // [F][T][E][R] or null
+    float *truth_arrival, *truth_speed; // [F][E][R], each or null
+    long long carrier_q32;              // llrint(cycles_per_row * 2^32)
+    uint32_t F, E, R, chunks, n_labels, n_shape, n_amp, T, window;   // chunks: ceil(R / SHEAR_TILE_ROWS)
+    uint32_t push_line, row0, row1;     // the pushed rows [row0, row1)
+    int32_t peak_q24;
+    uint32_t seed, first_id;
+    float sigma, inv_std, scale;        // scale: (float)(1.0 / (2 pi cycles_per_row))
+};
+hipError_t launch_shear_wave(const ShearWaveArgs &a, hipStream_t st);          // both kernels, in stream order (the tracker only with one of its outputs)
+// k_shear_speed (mcrt_shear_speed_frames): the peak times -> the shear speed, the modulus and the quality of the fit
+struct ShearSpeedArgs {
+    const float *peak_time;             // [F][E][R]
+    const float *pitch_mm;              // [R] (the context's copy)
+    float *speed, *modulus, *quality;   // [F][E][R], each or null
+    uint32_t F, E, R, chunks, push_line, lines, avg;    // lines: b, avg: v
+    float kf, d3;                       // (float)(prf_hz * 0.001), 3.0f * density
+};
+hipError_t launch_shear_speed(const ShearSpeedArgs &a, hipStream_t st);
 hipError_t launch_remap(const float *img, uint32_t n_img, uint32_t E, uint32_t R, const float *map_col, const float *map_row, float *out, uint32_t n, hipStream_t st);
 hipError_t launch_bmode_peak(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, float *peak, hipStream_t st);   // peak[F] zeroed before
 hipError_t launch_bmode_grey(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, const float *peak /*[F] or null: ref*/, float ref,

@@ -5,16 +5,9 @@
 // k_elastogram lays the gathered strain over the B-mode picture.  The reference has no counterpart.
 #include "mcrt_device.h"
 #include "mcrt_pixels.h"
+#include "mcrt_warp.h"              // warp_read: the reading of a line at a sub-row displacement, shared with mcrt_shear.hip
 
 namespace mcrt {
-
-// (c, s) of theta in 2^-32 turn from the rotor table, and z turned by it: mcrt_spectral_series_frames' index and product
-MCRT_DEV float2 strain_turn(float2 z, uint32_t theta, const float2 *lut)
-{
-    const float2 cs = lut[((theta + 0x80000u) >> 20) & 4095u];
-    const float rc = z.x * cs.x, is = z.y * cs.y, rs = z.x * cs.y, ic = z.y * cs.x;
-    return make_float2(rc - is, rs + ic);
-}
 
 // ONE wavefront is the workgroup and owns one scan-line: the pre-compression line sits in its LDS (8 R bytes, 16 KB at the most), because
 // row q reads the rows q + U(q) >> 24 and the next one, wherever the displacement sends them; the launch sizes it by R, so that short
@@ -53,20 +46,13 @@ __global__ void __launch_bounds__(64) k_strain_warp(StrainWarpArgs a)
         if (a.truth_disp) a.truth_disp[at] = (float)U * 0x1p-24f;
         if (a.truth_strain) a.truth_strain[at] = (float)eps * 0x1p-24f;
         if (!a.post) continue;
-        const int32_t s0 = (int32_t)q + (U >> 24), fr = U & 0xFFFFFF;      // s = (q << 24) + U: its whole rows and its fraction
-        const float2 zero = make_float2(0.0f, 0.0f);
-        const float2 A = s0 >= 0 && s0 < (int32_t)R ? pre[s0] : zero;
-        const float2 B = s0 + 1 >= 0 && s0 + 1 < (int32_t)R ? pre[s0 + 1] : zero;
-        const float w1 = (float)fr * 0x1p-24f, w0 = 1.0f - w1;
-        const uint32_t th0 = (uint32_t)((carrier * (long long)fr) >> 24);
-        const uint32_t th1 = (uint32_t)((carrier * ((long long)fr - (1ll << 24))) >> 24);
-        const float2 ra = strain_turn(A, th0, a.lut), rb = strain_turn(B, th1, a.lut);
-        float xr = w0 * ra.x + w1 * rb.x, xi = w0 * ra.y + w1 * rb.y;
+        const float2 x = warp_read(pre, 0, (int32_t)R, (int32_t)q, U, carrier, a.lut);
+        float xr = x.x, xi = x.y;
         if (k != 0.0f) {
             uint32_t o[4];
             philox4x32_10(e, q, 0x5354524Eu, 0u, a.seed, a.first_id + f, o);
-            const int32_t di = (int32_t)(((o[0] & 0xffffu) + (o[0] >> 16)) + ((o[1] & 0xffffu) + (o[1] >> 16))) - 131070;   // |d| < 2^24: the conversions are exact
-            const int32_t dq = (int32_t)(((o[2] & 0xffffu) + (o[2] >> 16)) + ((o[3] & 0xffffu) + (o[3] >> 16))) - 131070;
+            int32_t di, dq;
+            irwin_hall(o, di, dq);
             xr = xr + k * (float)di; xi = xi + k * (float)dq;
         }
         a.post[at] = make_float2(xr, xi);

@@ -138,6 +138,12 @@
 // --strain-window N rows (0..32; 16) and lags up to --strain-search N (0..16; 8), and the least-squares strain over --strain-lsq N rows (1..32; 12)
 // is laid over the 8-bit B-mode frame: stiff blue, the applied strain green, soft red.  --strain-truth FILE.raw writes the true strain of every
 // scan-line sample, float32 [512][465].  It does not combine with --compound, --sweep, --elevation or the band options.
+// --shear-elastogram FILE.ppm writes the last frame's shear-wave elastogram, a binary PPM of the B-mode size: a push on scan-line LINE over
+// LEN_MM about DEPTH_MM (--push LINE,DEPTH_MM,LEN_MM) launches a shear wave along every RF row of the frame's ONE trace, --shear-speed
+// NAME:c[,NAME:c...] gives materials their shear speed [m/s] (the others have 2; 0 is a fluid, the wave does not pass), the wave is tracked over
+// --shear-pulses N pulses (4..256; 64) at --shear-prf HZ (10000), and the modulus 3 rho c^2 of the time-to-peak speed is laid over the 8-bit
+// B-mode frame: soft blue, 12 kPa (2 m/s) green, stiff red.  --shear-truth FILE.raw writes the true shear speed of every scan-line sample,
+// float32 [512][465].  It does not combine with --compound, --sweep, --elevation or the band options.
 #include "mcrt_host.hpp"
 #include <algorithm>
 #include <chrono>
@@ -202,6 +208,10 @@ int main(int argc, char **argv)
     std::vector<std::string> flow_velocity;
     const char *elastogram = nullptr, *stiffness = nullptr, *compress = nullptr, *strain_window = nullptr, *strain_search = nullptr, *strain_lsq = nullptr,
                *strain_truth = nullptr;   // the options as given
+    const char *shear_elastogram = nullptr, *shear_speed = nullptr, *shear_push = nullptr, *shear_pulses = nullptr, *shear_prf = nullptr, *shear_truth = nullptr;
+    mcrt_shear_opts shopts; mcrt_default_shear_opts(&shopts);
+    mcrt_elastogram_opts shelopts; mcrt_default_elastogram_opts(&shelopts);
+    double push_depth_mm = 0.0, push_len_mm = 0.0;
     double applied = 0.01;
     mcrt_strain_opts stopts; mcrt_default_strain_opts(&stopts);
     mcrt_elastogram_opts elopts; mcrt_default_elastogram_opts(&elopts);
@@ -293,6 +303,12 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--strain-search") && i + 1 < argc) strain_search = argv[++i];
             else if (!std::strcmp(argv[i], "--strain-lsq") && i + 1 < argc) strain_lsq = argv[++i];
             else if (!std::strcmp(argv[i], "--strain-truth") && i + 1 < argc) strain_truth = argv[++i];
+            else if (!std::strcmp(argv[i], "--shear-elastogram") && i + 1 < argc) shear_elastogram = argv[++i];
+            else if (!std::strcmp(argv[i], "--shear-speed") && i + 1 < argc) shear_speed = argv[++i];
+            else if (!std::strcmp(argv[i], "--push") && i + 1 < argc) shear_push = argv[++i];
+            else if (!std::strcmp(argv[i], "--shear-pulses") && i + 1 < argc) shear_pulses = argv[++i];
+            else if (!std::strcmp(argv[i], "--shear-prf") && i + 1 < argc) shear_prf = argv[++i];
+            else if (!std::strcmp(argv[i], "--shear-truth") && i + 1 < argc) shear_truth = argv[++i];
             else if (!std::strcmp(argv[i], "--spectral") && i + 1 < argc) spectral = argv[++i];
             else if (!std::strcmp(argv[i], "--gate") && i + 1 < argc) spectral_gate = argv[++i];
             else if (!std::strcmp(argv[i], "--spectral-pulses") && i + 1 < argc) spectral_pulses = argv[++i];
@@ -543,6 +559,24 @@ int main(int argc, char **argv)
             elopts.ref_strain = (float)applied;
             bmode = true;                               // the colour lies over the 8-bit frame
         }
+        if (!shear_elastogram && (shear_speed || shear_push || shear_pulses || shear_prf || shear_truth))
+            throw std::invalid_argument("--shear-speed, --push, --shear-pulses, --shear-prf and --shear-truth need --shear-elastogram");
+        if (shear_elastogram) {
+            if (compound_given || sweep_given || elevation_given || with_bands) throw std::invalid_argument("--shear-elastogram does not combine with --compound, --sweep, --elevation or the band options");
+            if (!shear_speed) throw std::invalid_argument("--shear-elastogram needs --shear-speed NAME:c[,NAME:c...]");
+            if (!shear_push) throw std::invalid_argument("--shear-elastogram needs --push LINE,DEPTH_MM,LEN_MM");
+            const auto push = comma_list<double>(shear_push);
+            if (push.size() != 3 || !(push[0] >= 0.0 && push[0] == std::floor(push[0])) || !(push[1] >= 0.0) || !(push[2] > 0.0))
+                throw std::invalid_argument("--push takes LINE,DEPTH_MM,LEN_MM: a scan-line, a depth >= 0 and a length > 0");
+            if (push[0] >= (double)transducer_elements) throw std::invalid_argument("--push: the scan-line is not one of the transducer's");
+            shopts.push_line = (uint32_t)push[0]; push_depth_mm = push[1]; push_len_mm = push[2];
+            if (shear_pulses) shopts.n_pulses = (uint32_t)std::max(std::atol(shear_pulses), 0l);
+            if (shear_prf) shopts.prf_hz = (float)std::atof(shear_prf);
+            if (shopts.n_pulses < 4u || shopts.n_pulses > 256u) throw std::invalid_argument("--shear-pulses takes 4..256");
+            if (!(std::isfinite(shopts.prf_hz) && shopts.prf_hz > 0.0f)) throw std::invalid_argument("--shear-prf takes a pulse rate > 0");
+            shelopts.ref_strain = 3.0f * shopts.density * 2.0f * 2.0f;      // the modulus of the speed a material has that is not named
+            bmode = true;                               // the colour lies over the 8-bit frame
+        }
         if (colour_flow) {
             if (compound_given || sweep_given || elevation_given || with_bands) throw std::invalid_argument("--colour-flow does not combine with --compound, --sweep, --elevation or the band options");
             if (flow_velocity.empty()) throw std::invalid_argument("--colour-flow needs --flow-velocity NAME:vx,vy,vz");
@@ -667,6 +701,23 @@ int main(int argc, char **argv)
                 at = comma + 1;
             }
         }
+        std::vector<double> shear_c;                    // --shear-speed: a shear speed per material of the scene
+        if (shear_elastogram) {
+            shear_c.assign(scene.material_names.size(), 2.0);
+            std::string list = shear_speed;
+            for (size_t at = 0; at <= list.size();) {
+                const size_t comma = std::min(list.find(',', at), list.size());
+                const std::string item = list.substr(at, comma - at);
+                const size_t colon = item.find(':');
+                if (colon == std::string::npos || colon + 1 >= item.size()) throw std::invalid_argument("--shear-speed takes NAME:c[,NAME:c...]");
+                shear_c[scene.material_index(item.substr(0, colon))] = std::atof(item.c_str() + colon + 1);
+                at = comma + 1;
+            }
+            const double pitch = rf_image_::row_mm(), R = (double)rf_image_::max_rows;
+            const double rows = std::min(std::max(std::nearbyint(push_len_mm / pitch), 1.0), R);
+            shopts.push_rows = (uint32_t)rows;
+            shopts.push_row0 = (uint32_t)std::min(std::max(std::nearbyint(push_depth_mm / pitch - rows / 2.0), 0.0), R - rows);
+        }
 
         const auto t0 = std::chrono::high_resolution_clock::now();
         for (int f = 0; f < frames; f++) {
@@ -689,6 +740,12 @@ int main(int argc, char **argv)
                 double cycles = 0.0;
                 check(mcrt_psf_carrier(transducer_frequency, resolution, &cycles), "mcrt_psf_carrier");
                 strain_true = rf_image.compress(transducer, modulus, applied, 1.0, stopts, cycles, nullptr, detect ? &dopts : nullptr);
+            }
+            rf_image_::shear_wave_maps shear_true;
+            if (shear_elastogram && f == frames - 1) {   // the labels, the analytic pair, the push and its tracked wave, before the RF is detected
+                double cycles = 0.0;
+                check(mcrt_psf_carrier(transducer_frequency, resolution, &cycles), "mcrt_psf_carrier");
+                shear_true = rf_image.shear_wave(transducer, shear_c, shopts, cycles, 12, 8.0, nullptr, detect ? &dopts : nullptr);
             }
             if (detect) rf_image.detect(dopts);          // quadrature detection in the place of ...
             else rf_image.envelope();         // main.cpp:147
@@ -723,6 +780,17 @@ int main(int argc, char **argv)
                     std::ofstream out(strain_truth, std::ios::binary);
                     out.write((const char *)strain_true.strain.data(), (std::streamsize)(strain_true.strain.size() * sizeof(float)));
                     if (!out) throw std::runtime_error(std::string("cannot write ") + strain_truth);
+                }
+            }
+            if (shear_elastogram && f == frames - 1) {   // the fit across scan-lines and the overlay over the frame just made
+                std::vector<unsigned char> rgb;
+                rf_image.shear_speed(shopts);
+                rf_image.shear_elastogram(shelopts, rgb);
+                write_ppm(shear_elastogram, display.out_cols, display.out_rows, rgb);
+                if (shear_truth) {
+                    std::ofstream out(shear_truth, std::ios::binary);
+                    out.write((const char *)shear_true.truth_speed.data(), (std::streamsize)(shear_true.truth_speed.size() * sizeof(float)));
+                    if (!out) throw std::runtime_error(std::string("cannot write ") + shear_truth);
                 }
             }
             if (spectral && f == frames - 1) {           // the sample gate's series, its spectra and the sonogram

@@ -5,7 +5,7 @@
 //   transducer<N>            transducer.h:24-137   (frequency MHz, radius cm, element separation mm, position, angles deg)
 //   psf<ax,lat,elev,res>     psf.h:34-77
 //   scene                    scene.h:19-76, scene.cpp:16-48,185-247 (JSON keys, "Error while loading scene: ..." wrapping)
-//   rf_image<cols,us,um>     rfimage.h:20-219      (clear / convolve / envelope / postprocess; data lives on the GPU); + detect / iq; + flow_split / flow / colour_flow; + spectral_series / spectrum / sonogram; + compress / track / elastogram
+//   rf_image<cols,us,um>     rfimage.h:20-219      (clear / convolve / envelope / postprocess; data lives on the GPU); + detect / iq; + flow_split / flow / colour_flow; + spectral_series / spectrum / sonogram; + compress / track / elastogram; + shear_wave / shear_speed / shear_elastogram
 //   ray_physics::segment     ray.h:28-36           (vec3 stands in for btVector3; `media` is held BY VALUE: the reference's
 //                                                   `const material &` dangles by the time main.cpp:126 reads it)
 //   volume<size,res>         volume.h:19-61        (host copy of the texture the GPU samples)
@@ -723,7 +723,7 @@ public:
 
     rf_image(double radius_mm, double angle_rad, std::shared_ptr<device> dev_ = nullptr)
         : dev(dev_ ? std::move(dev_) : default_device()), radius_mm(radius_mm), angle(angle_rad), host((size_t)columns * max_rows, 0.0f),
-          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev), sound(dev), sigma(dev), curve(dev), band_stack(dev), flow_in(dev), flow_out(dev), spectral_buf(dev), strain_buf(dev), strain_pic(dev)
+          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev), sound(dev), sigma(dev), curve(dev), band_stack(dev), flow_in(dev), flow_out(dev), spectral_buf(dev), strain_buf(dev), strain_pic(dev), shear_buf(dev), shear_pic(dev)
     {
         std::cout << "rf_image: " << max_rows << ", " << columns << std::endl;          // rfimage.h:30
         rf.reserve(sizeof(float) * columns * max_rows);
@@ -1105,6 +1105,79 @@ public:
         check(mcrt_elastogram_frames(dev->ctx, img, img + np, bmode_buf.as<uint8_t>(), 1, bmode_rows, bmode_cols, lut, &eo, out), "mcrt_elastogram_frames");
         rgb = download<unsigned char>(out, 3 * np);
     }
+    // shear-wave elastography (mcrt.h: mcrt_shear_wave_frames, mcrt_shear_speed_frames, mcrt_elastogram_frames), three steps around the B-mode
+    // chain of ONE trace:
+    //   trace(f);  convolve(p); [add_noise();]  shear_wave(t, speed_m_s, so, cycles);  envelope() / detect();  postprocess(bmode_params);
+    //   shear_speed(so);  shear_elastogram(eo, rgb);
+    // shear_wave() goes while this image holds the RF before the envelope: the label pass of t's central beams (lopts: null = the tracer's
+    // rule), the detector's I/Q (dopts: null = 31 taps), then the push of so and its tracked wave.  speed_m_s: a shear speed per material
+    // of the scene [n_materials] (scene::material_index names them; 0: a fluid, the wave does not pass); the tables are the helpers' own:
+    // mcrt_shear_table at so.prf_hz, mcrt_shear_pitch of this image's sector, a raised cosine of width_pulses, a decay of decay_lines;
+    // cycles_per_row: mcrt_psf_carrier's.  A stack of views, planes or tracked frames, band images or a host-deposited image has no one
+    // analytic line: it throws.  The maps are [columns][max_rows]
+    struct shear_wave_maps { std::vector<float> peak_time, peak_disp, truth_arrival, truth_speed; };
+    template <size_t N> shear_wave_maps shear_wave(const transducer<N> &t, const std::vector<double> &speed_m_s, const mcrt_shear_opts &so, double cycles_per_row,
+                                                   uint32_t width_pulses = 12, double decay_lines = 8.0, const mcrt_label_opts *lopts = nullptr,
+                                                   const mcrt_detect_opts *dopts = nullptr)
+    {
+        static_assert(N == columns, "one scan-line per transducer element");
+        if (n_views || banded || where != on_device) throw std::logic_error("rf_image::shear_wave: after trace(frame_id) and convolve(psf), on one traced image");
+        const uint32_t L = (uint32_t)speed_m_s.size();
+        if (L == 0 || L > 254) throw std::invalid_argument("rf_image::shear_wave: a shear speed per material, 1..254 materials");
+        if (width_pulses == 0 || width_pulses > 256) throw std::invalid_argument("rf_image::shear_wave: width_pulses takes 1..256");
+        std::vector<int64_t> slow(L);
+        std::vector<float> speed_f(L);
+        check(mcrt_shear_table(speed_m_s.data(), L, (double)so.prf_hz, slow.data(), speed_f.data()), "mcrt_shear_table");
+        std::vector<uint32_t> pitch(max_rows), shape(64u * width_pulses), amp(columns);
+        shear_pitch_mm.assign(max_rows, 0.0f);
+        check(mcrt_shear_pitch(columns, max_rows, radius_mm, angle, max_travel_time_us, speed_of_sound, pitch.data(), shear_pitch_mm.data()), "mcrt_shear_pitch");
+        check(mcrt_shear_shape(width_pulses, shape.data()), "mcrt_shear_shape");
+        check(mcrt_shear_decay(columns, decay_lines, amp.data()), "mcrt_shear_decay");
+        const size_t n = (size_t)columns * max_rows;
+        shear_buf.reserve(4 * 9 * n + n);                            // floats: the pairs [n][2], peak_time, peak_disp, truth_arrival, truth_speed, speed, modulus, quality; then the tissue bytes
+        uint8_t *tissue = shear_buf.as<uint8_t>() + 4 * 9 * n;
+        mcrt_ctx *tracer = dev->tracer();
+        check(mcrt_label_frames(tracer, 1, 0, columns, t.pos.data(), t.dir.data(), lopts, tissue, nullptr, nullptr), "mcrt_label_frames");
+        check(mcrt_synchronize(tracer), "mcrt_synchronize");
+        float *pairs = shear_buf.as<float>(), *pt = pairs + 2 * n, *pd = pt + n, *ta = pd + n, *ts = ta + n;
+        mcrt_detect_opts d; mcrt_default_detect_opts(&d);
+        check(mcrt_detect_frames(dev->ctx, rf.as<float>(), 1, columns, max_rows, dopts ? dopts : &d, nullptr, pairs), "mcrt_detect_frames");
+        shear_stage = 0;
+        check(mcrt_shear_wave_frames(dev->ctx, pairs, tissue, 1, columns, max_rows, slow.data(), speed_f.data(), L, pitch.data(), shape.data(), (uint32_t)shape.size(),
+                                     amp.data(), columns, cycles_per_row, &so, first_id, nullptr, pt, pd, nullptr, ta, ts), "mcrt_shear_wave_frames");
+        shear_stage = 1;
+        return { download<float>(pt, n), download<float>(pd, n), download<float>(ta, n), download<float>(ts, n) };
+    }
+    // the fit across scan-lines over the peak times shear_wave() left: the speed [m/s], the modulus [kPa] and the quality in beam space;
+    // they stay on the device for shear_elastogram()
+    struct shear_maps { std::vector<float> speed, modulus, quality; };
+    shear_maps shear_speed(const mcrt_shear_opts &so)
+    {
+        if (shear_stage < 1) throw std::logic_error("rf_image::shear_speed: shear_wave() first");
+        const size_t n = (size_t)columns * max_rows;
+        float *pt = shear_buf.as<float>() + 2 * n, *sp = pt + 4 * n, *mo = sp + n, *qu = mo + n;
+        check(mcrt_shear_speed_frames(dev->ctx, pt, 1, columns, max_rows, shear_pitch_mm.data(), &so, sp, mo, qu), "mcrt_shear_speed_frames");
+        shear_stage = 2;
+        return { download<float>(sp, n), download<float>(mo, n), download<float>(qu, n) };
+    }
+    // the shear-wave elastogram over the last postprocess(bmode_params) frame: shear_speed()'s modulus and quality gathered through
+    // mcrt_scan_convert_frames at that frame's size, and mcrt_elastogram_frames as it is with eo (ref_strain: the reference kPa, rho_min: the
+    // smallest quality shown) and mcrt_shear_map's table.  rgb: [out_rows][out_cols][3]
+    void shear_elastogram(const mcrt_elastogram_opts &eo, std::vector<unsigned char> &rgb)
+    {
+        if (shear_stage < 2) throw std::logic_error("rf_image::shear_elastogram: shear_speed() first");
+        if (!bmode_n) throw std::logic_error("rf_image::shear_elastogram: postprocess(bmode_params) first: the picture under the colour");
+        const size_t n = (size_t)columns * max_rows, np = bmode_n;
+        shear_pic.reserve(4 * 2 * np + 3 * np);                      // modulus_img, quality_img, then the rgb bytes
+        float *mo = shear_buf.as<float>() + 7 * n, *qu = mo + n, *img = shear_pic.as<float>();
+        uint8_t *out = reinterpret_cast<uint8_t *>(img + 2 * np);
+        check(mcrt_scan_convert_frames(dev->ctx, mo, 1, columns, max_rows, radius_mm, angle, img, bmode_rows, bmode_cols), "mcrt_scan_convert_frames");
+        check(mcrt_scan_convert_frames(dev->ctx, qu, 1, columns, max_rows, radius_mm, angle, img + np, bmode_rows, bmode_cols), "mcrt_scan_convert_frames");
+        uint8_t lut[256 * 3];
+        check(mcrt_shear_map(0, lut), "mcrt_shear_map");
+        check(mcrt_elastogram_frames(dev->ctx, img, img + np, bmode_buf.as<uint8_t>(), 1, bmode_rows, bmode_cols, lut, &eo, out), "mcrt_elastogram_frames");
+        rgb = download<unsigned char>(out, 3 * np);
+    }
     // receiver noise (mcrt.h: mcrt_noise_frames): a noise floor and a gain per scan-line (element_gain: [columns] or null) over whatever the
     // last trace() filled, in place -- this image, or the views of a compounded frame or the planes of a sweep as ONE frame (one receiver,
     // one peak), or the tracked frames of a freehand pass as so many frames -- with the ids that trace used.  It goes after convolve() and
@@ -1475,6 +1548,8 @@ private:
     device_buffer spectral_buf;                  // spectral_series() / spectrum() / sonogram(): the series [T][2], then power [n_cols][N], mean [n_cols] and the bytes
     uint32_t spectral_T = 0, spectral_cols = 0, spectral_N = 0;   // ... the shapes of what it holds (0: nothing yet)
     device_buffer strain_buf, strain_pic;        // compress() / track(): the pairs, the post-compression pairs, five maps and the tissue bytes; elastogram(): the gathered pictures and the rgb bytes
+    device_buffer shear_buf, shear_pic;          // shear_wave() / shear_speed(): the pairs, seven maps and the tissue bytes; shear_elastogram(): the gathered pictures and the rgb bytes
+    std::vector<float> shear_pitch_mm; int shear_stage = 0;   // shear_wave()'s pitch table [max_rows]; 0: nothing yet, 1: shear_wave() has run, 2: shear_speed() since
     double strain_cycles = 0.0; bool strain_tracked = false;   // compress()'s carrier (0: it has not run); track() has run since
     uint32_t banded = 0;                         // ... B while they wait there for envelope() / fold_bands() (0: the images are where trace() left them)
     std::vector<float> band_w;                   // ... and the bands' weights [max_rows][B] they are folded with
