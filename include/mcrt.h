@@ -87,7 +87,11 @@ extern "C" {
                                    + mcrt_shear_opts, mcrt_default_shear_opts, mcrt_shear_table, mcrt_shear_pitch, mcrt_shear_shape, mcrt_shear_decay,
                                    mcrt_shear_draws, mcrt_shear_map, mcrt_shear_wave_frames, mcrt_shear_speed_frames
                                    (shear-wave elastography: a push, the shear wave tracked over slow time from one traced frame, the time to peak,
-                                   the shear speed, the modulus and their ground truth; additive) */
+                                   the shear speed, the modulus and their ground truth; additive);
+                                   + mcrt_mline, mcrt_mmode_opts, mcrt_default_mmode_opts, mcrt_mmode_table, mcrt_mmode_waveform, mcrt_mmode_bulk, mcrt_mmode_draws,
+                                   mcrt_mmode_display_opts, mcrt_default_mmode_display_opts, mcrt_mmode_rows, mcrt_mmode_lines_frames, mcrt_mmode_picture_frames
+                                   (M-mode: tissue that moves over slow time, the pulses of one scan-line synthesised from one traced frame, the sweep
+                                   display and its ground truth; additive) */
 
 typedef enum {
     MCRT_OK = 0,
@@ -1751,6 +1755,140 @@ int mcrt_shear_wave_frames(mcrt_ctx *ctx, const float *iq_dev /* [F][E][R][2] */
 int mcrt_shear_speed_frames(mcrt_ctx *ctx, const float *peak_time_dev /* [F][E][R] */, uint32_t n_frames, uint32_t n_elements, uint32_t n_rows,
                             const float *pitch_mm /* [R] */, const mcrt_shear_opts *o, float *speed_dev /* [F][E][R] or NULL */,
                             float *modulus_dev /* [F][E][R] or NULL */, float *quality_dev /* [F][E][R] or NULL */);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * M-mode: one scan-line fired at the pulse repetition rate, depth down the picture, time across it -- the mode that measures wall
+ * motion, vessel distension and the fetal heart rate.  The reference has no counterpart.  THE MODEL is strain's column of springs with
+ * a time axis, anchored at the probe face, and is synthesised from ONE traced frame, as the Doppler ensembles, the compression and the
+ * shear wave are and for the same reason (a second trace has another Philox key and decorrelates completely).  Each material has a
+ * DILATION dil_q24[l], the peak axial strain of that material over the cycle in Q24, with mcrt_strain_compress_frames' sign: positive
+ * is compression, so a lumen that widens in systole has a negative one.  A waveform w_q16[t] in [-65536, 65536] (the heart beat, a
+ * palpation) scales the column's displacement at pulse t, and bulk_q24[t] (|bulk| <= 32 rows) shifts the whole line rigidly (breathing,
+ * a probe that slips).  Pulse t's analytic line is the pre line read at q + U(q, t) by mcrt_strain_compress_frames' interpolation, plus
+ * optional receiver noise; its envelope is the M-line.  The display sweeps the M-lines across the picture: a column is a time, a row a
+ * depth.
+ * LEFT OUT: lateral and elevational motion; motion that differs between scan-lines; speckle decorrelation other than receiver noise;
+ * anatomical (oblique) M-mode; colour M-mode; tissue Doppler as a call (iq_out_dev has the moving analytic lines for it); more than one
+ * waveform per call; M-mode of swept, compounded, elevation-summed or banded frames.
+ * An opt-in chain; without it no call and no bit changes.
+ *
+ * Throughout, every float operation is rounded once: no fma, correctly rounded / and sqrtf, no device transcendental except the one
+ * log10f of the display; every sum ascends from 0.0f.
+ *
+ * THE INTEGERS.  Per M-line (image f, scan-line e), row q and pulse t, with tissue = tissue_dev[f][e] and
+ * dil(l) = l < n_labels ? dil_q24[l] : 0 (MCRT_LABEL_NONE and any label past the table do not move):
+ *   D[0] = 0;   D[q] = D[q-1] + dil(tissue[q-1])                                       (int64: |D| <= 2048 * 2^22 = 2^33; the order is free)
+ *   u64    = ((D[q] * (int64)w_q16[t]) >> 16) + (int64)bulk_q24[t]                     (an arithmetic shift; |u64| < 2^34)
+ *   U(q,t) = u64 < -(127 << 24) ? -(127 << 24) : u64 > (127 << 24) ? (127 << 24) : u64     a displacement past 127 rows saturates there
+ * in Q24 rows; positive reads deeper down, as the U of mcrt_strain_compress_frames does. */
+typedef struct { uint32_t image, line; } mcrt_mline;      /* an M-line: scan-line `line` of image `image` of the stack; 8 bytes */
+typedef struct {
+    uint32_t n_pulses;      /* T, the pulses of every M-line: 1..16384; default 1024 */
+    float sigma;            /* the receiver noise per I/Q component of every pulse, finite and >= 0, used when no sigma_dev is given; default 0 */
+    uint32_t seed;          /* Philox key word 0 of the noise stream; default 0x4D4D4F44 */
+} mcrt_mmode_opts;          /* 12 bytes */
+/* the defaults above.  MCRT_ERR_INVALID for a null o.  Host only. */
+int mcrt_default_mmode_opts(mcrt_mmode_opts *o);
+/* the dilation of every material in Q24, in double: dil_q24[l] = llrint(dilation[l] * 16777216.0).  Host only.  MCRT_ERR_INVALID for a
+ * null pointer, n_labels == 0, a dilation that is not finite, or a |dil_q24[l]| above 2^22 (a dilation above 25 %); MCRT_ERR_LIMIT for
+ * n_labels > 254; on an error nothing is written. */
+int mcrt_mmode_table(const double *dilation /* [n_labels] */, uint32_t n_labels, int32_t *dil_q24 /* [n_labels] */);
+/* a default waveform, a convenience, not physiology: mcrt_pulse_waveform's systolic half-sine squared over the first 30 % of every
+ * cycle, in double, per pulse t:
+ *   u = t * beats_per_min / (60.0 * prf_hz);   x = u - floor(u);   s = sin(3.141592653589793 * x / 0.3)
+ *   w_q16[t] = llrint(65536.0 * (x < 0.3 ? s * s : 0.0))
+ * Host only.  MCRT_ERR_INVALID for a null table, n_pulses == 0, a prf_hz or beats_per_min that is not finite and > 0; MCRT_ERR_LIMIT for
+ * n_pulses > 16384; on an error nothing is written. */
+int mcrt_mmode_waveform(double prf_hz, double beats_per_min, uint32_t n_pulses, int32_t *w_q16 /* [n_pulses] */);
+/* a default bulk motion, a sinusoid of amplitude_rows rows at cycles_per_min, in double, per pulse t:
+ *   bulk_q24[t] = llrint(amplitude_rows * 16777216.0 * sin(6.283185307179586 * t * cycles_per_min / (60.0 * prf_hz)))
+ * Host only.  MCRT_ERR_INVALID for a null table, n_pulses == 0, a prf_hz that is not finite and > 0, a cycles_per_min or amplitude_rows
+ * that is not finite, or an |amplitude_rows| above 32; MCRT_ERR_LIMIT for n_pulses > 16384; on an error nothing is written. */
+int mcrt_mmode_bulk(double prf_hz, double cycles_per_min, double amplitude_rows, uint32_t n_pulses, int32_t *bulk_q24 /* [n_pulses] */);
+/* the integer noise draws of one M-line, d[t][r][0..1] (I, Q): one Philox4x32-10 block per (line, row, pulse) with the counter
+ * (line, r, 0x4D4D4F44, t) and the key (seed, image_id); mcrt_flow_draws' Irwin-Hall sums and inv_std.  Counter word 2 differs from the
+ * tracer's (< 16), mcrt_noise_frames' (0x4E4F4953), mcrt_flow_frames' (0x464C4F57), mcrt_spectral_series_frames' (0x53504543),
+ * mcrt_strain_compress_frames' (0x5354524E) and mcrt_shear_wave_frames' (0x53484552).  Host only.  MCRT_ERR_INVALID for a null d or
+ * zero sizes; MCRT_ERR_LIMIT for n_rows > 2048 or n_pulses > 16384. */
+int mcrt_mmode_draws(uint32_t seed, uint32_t image_id, uint32_t line, uint32_t n_rows, uint32_t n_pulses, int32_t *d /* [T][R][2] */);
+/* THE M-LINES.  iq_dev [F][E][R][2] is mcrt_detect_frames' iq_dev, tissue_dev [F][E][R] mcrt_label_frames' labels; lines [n_lines],
+ * dil_q24 [n_labels] (mcrt_mmode_table's or the caller's own, |dil| <= 2^22), w_q16 [T] (|w| <= 65536) and bulk_q24 [T]
+ * (|bulk| <= 32 << 24) are HOST tables, free when the call returns: they live in buffers of the context and are copied only when they
+ * differ from what is there.  T = o->n_pulses, carrier_q32 = llrint(cycles_per_row * 4294967296.0) with cycles_per_row in (0, 0.5]
+ * (mcrt_psf_carrier's), lut mcrt_spectral_rotor's table.  Per M-line j = (f, e), pulse t and row q, with pre = iq_dev[f][e] and U(q,t)
+ * of THE INTEGERS:
+ *   z(q,t)   = warp(pre, q, U(q,t)) + k * (float)d[t][q]      warp: mcrt_strain_compress_frames' post[q] with U[q] = U(q,t) (s0, fr, w0, w1,
+ *              th0, th1 and the rotor lookup are its own: s0 = q + (U >> 24), fr = U & 0xFFFFFF); k = sigma_f * inv_std, sigma_f =
+ *              sigma_dev ? sigma_dev[f] : o->sigma, d mcrt_mmode_draws' of (o->seed, first_image_id + f, e); at k == 0 the noise term is
+ *              skipped and no Philox block is computed
+ *   env(q,t) = sqrtf(z.re * z.re + z.im * z.im)                (two products, their sum, the root)
+ * THE OUTPUTS, each a device pointer or NULL, at least one given:
+ *   env_dev [n_lines][T][R]           env(q,t), the M-line of every pulse
+ *   iq_out_dev [n_lines][T][R][2]     z(q,t), the moving analytic lines
+ *   truth_disp_dev [n_lines][T][R]    (float)U(q,t) * 0x1p-24f      the true displacement in rows, positive: the sample is read from deeper down
+ *   truth_label_dev [n_lines][T][R]   (uint8) the material of the sample each output shows: tissue[sr] with sr = s0 + (fr >> 23), the
+ *                                     nearer of the two samples read; MCRT_LABEL_NONE where sr is outside [0, R)
+ * With all dilations 0, every bulk 0 and k == 0, env(q,t) is sqrtf(re * re + im * im) of the pre line for every t wherever pre is
+ * finite (the zero-strain identity); a bulk of k << 24 shows the pre line k rows further down, zeros beyond its ends.  The same line
+ * may be named more than once.  The inputs are read only; every element of every output given is written.  Nothing is allocated after
+ * the first call at a size.  Asynchronous on the context's stream.  MCRT_ERR_INVALID for a null ctx, iq_dev, tissue_dev, table or o,
+ * zero sizes, n_labels == 0, n_lines == 0, a cycles_per_row outside (0, 0.5], options out of range (n_pulses, sigma), a line with
+ * image >= n_frames or line >= n_elements, a |dil_q24[l]| above 2^22, a |w_q16[t]| above 65536, a |bulk_q24[t]| above 32 << 24, no
+ * output, an output that overlaps an input or another output; MCRT_ERR_LIMIT for n_rows > 2048, n_labels > 254, n_lines > 65535, a
+ * stack of 2^31 samples or more, n_lines * T * n_rows >= 2^31, image ids that pass 2^32; on any error nothing is launched and nothing
+ * is written.  Groups: call it on mcrt_group_root(). */
+int mcrt_mmode_lines_frames(mcrt_ctx *ctx, const float *iq_dev /* [F][E][R][2] */, const uint8_t *tissue_dev /* [F][E][R] */, uint32_t n_frames,
+                            uint32_t n_elements, uint32_t n_rows, const mcrt_mline *lines /* [n_lines] */, uint32_t n_lines,
+                            const int32_t *dil_q24 /* [n_labels] */, uint32_t n_labels, const int32_t *w_q16 /* [T] */, const int32_t *bulk_q24 /* [T] */,
+                            double cycles_per_row, const mcrt_mmode_opts *o, uint32_t first_image_id, const float *sigma_dev /* [F] or NULL */,
+                            float *env_dev /* [n_lines][T][R] or NULL */, float *iq_out_dev /* [n_lines][T][R][2] or NULL */,
+                            float *truth_disp_dev /* [n_lines][T][R] or NULL */, uint8_t *truth_label_dev /* [n_lines][T][R] or NULL */);
+typedef struct {
+    uint32_t hop;               /* pulses per picture column, >= 1; default 4 */
+    uint32_t height;            /* H, the picture's rows: 1..4096; default 400 */
+    uint32_t row_lo, row_hi;    /* the rows [row_lo, row_hi) of the line that are shown; row_hi 0: n_rows; defaults 0, 0 */
+    float dynamic_range_db;     /* finite and > 0; default 60 */
+    float gain_db;              /* finite; default 0 */
+    float ref;                  /* finite; > 0: the amplitude shown as 0 dB; otherwise each line's own peak; default 0 */
+} mcrt_mmode_display_opts;      /* 28 bytes */
+/* the defaults above.  MCRT_ERR_INVALID for a null o.  Host only. */
+int mcrt_default_mmode_display_opts(mcrt_mmode_display_opts *o);
+/* the depth resampling table of the sweep, H picture rows over the line's rows [row_lo, row_hi) (row_hi spelled out), in double, per
+ * picture row y:
+ *   p = row_lo + (y + 0.5) * (row_hi - row_lo) / H - 0.5;   f = floor(p)
+ *   idx[y] = f < row_lo ? row_lo : f > row_hi - 1 ? row_hi - 1 : f                     the first tap i0; the second is min(i0 + 1, row_hi - 1)
+ *   wt[y]  = f clamped either way ? 0.0f : min(1.0f, max(0.0f, (float)(p - f)))        the second tap's weight
+ * Host only.  MCRT_ERR_INVALID for a null table, H == 0 or H > 4096, row_lo >= row_hi; MCRT_ERR_LIMIT for row_hi > 2048; on an error
+ * nothing is written. */
+int mcrt_mmode_rows(uint32_t row_lo, uint32_t row_hi, uint32_t height, uint32_t *idx /* [H] */, float *wt /* [H] */);
+/* THE SWEEP as displayed.  env_dev [n_lines][T][R] is mcrt_mmode_lines_frames'; W = T / o->hop columns (a last partial column is
+ * dropped), H = o->height rows, the shown rows [row_lo, row_hi) with row_hi = o->row_hi ? o->row_hi : R, and (idx, wt) mcrt_mmode_rows'
+ * table of them (made by the call, kept in the context as the other tables are).  Per line j, column c and row r, with DR =
+ * o->dynamic_range_db:
+ *   a[c][r] = (sum over k = 0 .. hop-1 ascending, from 0.0f, of env[j][c * hop + k][r]) / (float)hop
+ *   a NaN or an infinite a counts as 0;   peak = the largest a that counts over all columns and the shown rows (exact, whatever the
+ *   order; 0 when there is none);   ref = o->ref > 0 ? o->ref : peak
+ *   g[c][r] = a > 0 ? min(1, max(0, ((20.0f * log10f(a / ref) + o->gain_db) + DR) / DR)) : 0      compression before interpolation, as in mcrt_bmode_frames
+ *   v = (1.0f - wt[y]) * g[c][i0] + wt[y] * g[c][i1],   i0 = idx[y], i1 = min(i0 + 1, row_hi - 1)
+ *   out_dev[j][y][c] = (uint8_t)(v * 255.0f + 0.5f)
+ * The optional outputs, each a device pointer or NULL:
+ *   peak_dev [n_lines]            peak, whatever ref is
+ *   mean_dev [n_lines][W][R]      a[c][r] of EVERY row, before the NaN rule (the float a test can hold bit for bit)
+ *   label_out_dev [n_lines][H][W] truth_label_dev[j][c * hop][rn], rn = min(i0 + (wt[y] >= 0.5f), row_hi - 1): pulse c * hop at the
+ *                                 nearest shown row, registered with out_dev pixel for pixel; needs truth_label_dev [n_lines][T][R]
+ *   disp_out_dev [n_lines][H][W]  truth_disp_dev[j][c * hop][rn] likewise; needs truth_disp_dev [n_lines][T][R]
+ * The inputs are read only; every element of every output given is written.  Without a peak_dev the peaks live in a grow-only buffer
+ * of the context: nothing is allocated after the first call at a size.  Asynchronous on the context's stream.  MCRT_ERR_INVALID for a
+ * null ctx, env_dev, o or out_dev, zero sizes, hop == 0, W == 0 (hop > T), height outside 1..4096, row_lo >= row_hi or row_hi > R,
+ * a dynamic_range_db that is not finite and > 0, a gain_db or ref that is not finite, a label_out_dev without truth_label_dev or a
+ * disp_out_dev without truth_disp_dev, an output that overlaps an input or another output; MCRT_ERR_LIMIT for n_rows > 2048,
+ * n_pulses > 16384, n_lines > 65535, n_lines * T * R >= 2^31 or n_lines * H * W >= 2^31; on any error nothing is launched and nothing
+ * is written.  Groups: on mcrt_group_root(). */
+int mcrt_mmode_picture_frames(mcrt_ctx *ctx, const float *env_dev /* [n_lines][T][R] */, const uint8_t *truth_label_dev /* [n_lines][T][R] or NULL */,
+                              const float *truth_disp_dev /* [n_lines][T][R] or NULL */, uint32_t n_lines, uint32_t n_pulses, uint32_t n_rows,
+                              const mcrt_mmode_display_opts *o, float *peak_dev /* [n_lines] or NULL */, float *mean_dev /* [n_lines][W][R] or NULL */,
+                              uint8_t *out_dev /* [n_lines][H][W] */, uint8_t *label_out_dev /* [n_lines][H][W] or NULL */,
+                              float *disp_out_dev /* [n_lines][H][W] or NULL */);
 
 /* device [E][R]  ->  host [R][E] row-major (the cv::Mat layout of rfimage.h:217); synchronous */
 int mcrt_export_rf(mcrt_ctx *ctx, const float *rf_dev, uint32_t n_elements, uint32_t n_rows, float *host_rows_by_cols);

@@ -107,6 +107,22 @@ class ShearOpts(C.Structure):
                 ("push_row0", C.c_uint32), ("push_rows", C.c_uint32), ("peak_q24", C.c_int32), ("speed_lines", C.c_uint32), ("avg_rows", C.c_uint32), ("density", C.c_float)]
 
 
+class Mline(C.Structure):
+    """mcrt_mline (include/mcrt.h): 8 bytes"""
+    _fields_ = [("image", C.c_uint32), ("line", C.c_uint32)]
+
+
+class MmodeOpts(C.Structure):
+    """mcrt_mmode_opts (include/mcrt.h): 12 bytes"""
+    _fields_ = [("n_pulses", C.c_uint32), ("sigma", C.c_float), ("seed", C.c_uint32)]
+
+
+class MmodeDisplayOpts(C.Structure):
+    """mcrt_mmode_display_opts (include/mcrt.h): 28 bytes"""
+    _fields_ = [("hop", C.c_uint32), ("height", C.c_uint32), ("row_lo", C.c_uint32), ("row_hi", C.c_uint32), ("dynamic_range_db", C.c_float),
+                ("gain_db", C.c_float), ("ref", C.c_float)]
+
+
 class ElastogramOpts(C.Structure):
     """mcrt_elastogram_opts (include/mcrt.h): 16 bytes"""
     _fields_ = [("ref_strain", C.c_float), ("rho_min", C.c_float), ("grey_min", C.c_uint32), ("alpha", C.c_uint32)]
@@ -199,6 +215,7 @@ assert C.sizeof(FlowOpts) == 32 and FlowOpts.prf_hz.offset == 16 and FlowOpts.se
 assert C.sizeof(SpectralOpts) == 32 and SpectralOpts.sigma.offset == 24 and C.sizeof(Gate) == 12 and C.sizeof(SonogramOpts) == 12
 assert C.sizeof(StrainOpts) == 20 and StrainOpts.sigma.offset == 12 and C.sizeof(ElastogramOpts) == 16 and ElastogramOpts.grey_min.offset == 8
 assert C.sizeof(ShearOpts) == 48 and ShearOpts.sigma.offset == 12 and ShearOpts.peak_q24.offset == 32 and ShearOpts.density.offset == 44
+assert C.sizeof(Mline) == 8 and C.sizeof(MmodeOpts) == 12 and MmodeOpts.seed.offset == 8 and C.sizeof(MmodeDisplayOpts) == 28 and MmodeDisplayOpts.dynamic_range_db.offset == 16
 
 # every symbol include/mcrt.h declares (tests/test_abi.py checks the .so exports each one)
 SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create", "mcrt_destroy", "mcrt_set_stream",
@@ -232,6 +249,8 @@ SYMBOLS = ["mcrt_last_error", "mcrt_version", "mcrt_device_count", "mcrt_create"
            "mcrt_default_elastogram_opts", "mcrt_elastogram_frames",
            "mcrt_default_shear_opts", "mcrt_shear_table", "mcrt_shear_pitch", "mcrt_shear_shape", "mcrt_shear_decay", "mcrt_shear_draws", "mcrt_shear_map",
            "mcrt_shear_wave_frames", "mcrt_shear_speed_frames",
+           "mcrt_default_mmode_opts", "mcrt_mmode_table", "mcrt_mmode_waveform", "mcrt_mmode_bulk", "mcrt_mmode_draws", "mcrt_default_mmode_display_opts",
+           "mcrt_mmode_rows", "mcrt_mmode_lines_frames", "mcrt_mmode_picture_frames",
            "mcrt_default_recon_opts", "mcrt_recon_transform", "mcrt_recon_frames",
            "mcrt_default_recon_label_opts", "mcrt_recon_label_frames", "mcrt_render_label_frames"]
 
@@ -364,6 +383,15 @@ def load_library():
         "mcrt_shear_map": [u32, vp],
         "mcrt_shear_wave_frames": [vp, vp, vp, u32, u32, u32, vp, vp, u32, vp, vp, u32, vp, u32, C.c_double, C.POINTER(ShearOpts), u32, vp, vp, vp, vp, vp, vp],
         "mcrt_shear_speed_frames": [vp, vp, u32, u32, u32, vp, C.POINTER(ShearOpts), vp, vp, vp],
+        "mcrt_default_mmode_opts": [C.POINTER(MmodeOpts)],
+        "mcrt_mmode_table": [vp, u32, vp],
+        "mcrt_mmode_waveform": [C.c_double, C.c_double, u32, vp],
+        "mcrt_mmode_bulk": [C.c_double, C.c_double, C.c_double, u32, vp],
+        "mcrt_mmode_draws": [u32, u32, u32, u32, u32, vp],
+        "mcrt_default_mmode_display_opts": [C.POINTER(MmodeDisplayOpts)],
+        "mcrt_mmode_rows": [u32, u32, u32, vp, vp],
+        "mcrt_mmode_lines_frames": [vp, vp, vp, u32, u32, u32, vp, u32, vp, u32, vp, vp, C.c_double, C.POINTER(MmodeOpts), u32, vp, vp, vp, vp, vp],
+        "mcrt_mmode_picture_frames": [vp, vp, vp, vp, u32, u32, u32, C.POINTER(MmodeDisplayOpts), vp, vp, vp, vp, vp],
         "mcrt_default_elastogram_opts": [C.POINTER(ElastogramOpts)],
         "mcrt_elastogram_frames": [vp, vp, vp, vp, u32, u32, u32, vp, C.POINTER(ElastogramOpts), vp],
         "mcrt_default_recon_opts": [C.POINTER(ReconOpts)],

@@ -12,7 +12,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Bands, DetectOpts, FlowOpts, ColourOpts, SpectralOpts, Gate, SonogramOpts, StrainOpts, ElastogramOpts, ShearOpts, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, Speckle3dOpts, NoiseOpts, AutogainOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
+from ._lib import Params, MeshRec, Stats, Bvh, Bvh4, BmodeParams, Focus, Bands, DetectOpts, FlowOpts, ColourOpts, SpectralOpts, Gate, SonogramOpts, StrainOpts, ElastogramOpts, ShearOpts, Mline, MmodeOpts, MmodeDisplayOpts, Compound, Sweep, VolumeGrid, CompoundOpts, LabelOpts, TransmitOpts, RenderView, RenderOpts, SpeckleOpts, Speckle3dOpts, NoiseOpts, AutogainOpts, ReconOpts, ReconLabelOpts, NODE_DTYPE, SEGMENT_DTYPE, check, ptr, load_library
 
 DEFAULT_ANGLE = 1.0471975511965976      # the sector of main.cpp:28: 60 degrees [rad]
 
@@ -418,6 +418,72 @@ def host_shear_map(kind=0):
     lut = np.zeros((256, 3), np.uint8)
     check(load_library().mcrt_shear_map(int(kind) & 0xFFFFFFFF, ptr(lut)))
     return lut
+
+
+def mmode_opts_struct(n_pulses=None, sigma=None, seed=None):
+    """mcrt_mmode_opts from keywords over mcrt_default_mmode_opts: n_pulses (1..16384; 1024), sigma (0), seed -- the library checks the ranges"""
+    o = MmodeOpts()
+    check(load_library().mcrt_default_mmode_opts(C.byref(o)))
+    for name, v in (("n_pulses", n_pulses), ("seed", seed)):
+        if v is not None:
+            setattr(o, name, int(v) & 0xFFFFFFFF)
+    if sigma is not None:
+        o.sigma = float(sigma)
+    return o
+
+
+def mmode_display_opts_struct(hop=None, height=None, row_lo=None, row_hi=None, dynamic_range_db=None, gain_db=None, ref=None):
+    """mcrt_mmode_display_opts from keywords over mcrt_default_mmode_display_opts: hop (pulses per column, >= 1; 4), height (1..4096; 400),
+    row_lo and row_hi (the rows shown; 0, 0: the whole line), dynamic_range_db (60), gain_db (0), ref (0: each line's own peak)"""
+    o = MmodeDisplayOpts()
+    check(load_library().mcrt_default_mmode_display_opts(C.byref(o)))
+    for name, v in (("hop", hop), ("height", height), ("row_lo", row_lo), ("row_hi", row_hi)):
+        if v is not None:
+            setattr(o, name, int(v) & 0xFFFFFFFF)
+    for name, v in (("dynamic_range_db", dynamic_range_db), ("gain_db", gain_db), ("ref", ref)):
+        if v is not None:
+            setattr(o, name, float(v))
+    return o
+
+
+def host_mmode_table(dilation):
+    """mcrt_mmode_table: the dilation of every material in Q24, int32 [n_labels], of a peak axial strain per material (positive: compression;
+    at most 25 %)"""
+    d = np.ascontiguousarray(dilation, np.float64).reshape(-1)
+    q = np.zeros(min(d.size, 254), np.int32)
+    check(load_library().mcrt_mmode_table(ptr(d), d.size, ptr(q)))
+    return q
+
+
+def host_mmode_waveform(prf_hz, beats_per_min, n_pulses):
+    """mcrt_mmode_waveform: a default waveform in Q16, int32 [n_pulses] -- host_pulse_waveform's systolic half-sine squared (a convenience,
+    not physiology)"""
+    w = np.zeros(min(max(int(n_pulses), 0), 16384), np.int32)
+    check(load_library().mcrt_mmode_waveform(float(prf_hz), float(beats_per_min), n_pulses, ptr(w) if w.size else None))
+    return w
+
+
+def host_mmode_bulk(prf_hz, cycles_per_min, amplitude_rows, n_pulses):
+    """mcrt_mmode_bulk: a sinusoidal rigid shift of the whole line in Q24 rows, int32 [n_pulses] (|amplitude_rows| <= 32)"""
+    b = np.zeros(min(max(int(n_pulses), 0), 16384), np.int32)
+    check(load_library().mcrt_mmode_bulk(float(prf_hz), float(cycles_per_min), float(amplitude_rows), n_pulses, ptr(b) if b.size else None))
+    return b
+
+
+def host_mmode_draws(seed, image_id, line, n_rows, n_pulses):
+    """mcrt_mmode_draws: the integer draws of one M-line, int32 [n_pulses][n_rows][2] (noise = d * sigma / sqrt(1431655765))"""
+    d = np.zeros((min(max(int(n_pulses), 0), 16384), min(max(int(n_rows), 0), 2048), 2), np.int32)
+    check(load_library().mcrt_mmode_draws(int(seed) & 0xFFFFFFFF, int(image_id) & 0xFFFFFFFF, int(line) & 0xFFFFFFFF, n_rows, n_pulses, ptr(d)))
+    return d
+
+
+def host_mmode_rows(row_lo, row_hi, height):
+    """mcrt_mmode_rows: the depth resampling table of the sweep, (idx uint32 [height], wt float32 [height]): the first tap and the second
+    tap's weight of every picture row over the line's rows [row_lo, row_hi)"""
+    H = min(max(int(height), 0), 4096)
+    idx = np.zeros(H, np.uint32); wt = np.zeros(H, np.float32)
+    check(load_library().mcrt_mmode_rows(row_lo, row_hi, height, ptr(idx) if H else None, ptr(wt) if H else None))
+    return idx, wt
 
 
 def row_pitch_mm(frequency):
@@ -1421,6 +1487,36 @@ class Context(_SceneCalls):
         check(self.L.mcrt_shear_speed_frames(self.h, ptr(peak_time_dev), n_frames, n_elements, n_rows, ptr(pitch), C.byref(o), ptr(speed_dev), ptr(modulus_dev),
                                              ptr(quality_dev)))
 
+    def mmode_lines_frames(self, iq_dev, tissue_dev, n_frames, n_elements, n_rows, lines, dil_q24, w_q16, bulk_q24, cycles_per_row, first_image_id=0,
+                           sigma_dev=None, env_dev=None, iq_out_dev=None, truth_disp_dev=None, truth_label_dev=None, opts=None, **kw):
+        """mcrt_mmode_lines_frames: the pulses of the named scan-lines from the detected pairs [n_frames][E][R][2] and the tissue labels
+        [n_frames][E][R].  lines: [n_lines][2] (image, scan-line); dil_q24: int32 [n_labels] (host_mmode_table); w_q16 and bulk_q24: int32
+        [T] each (host_mmode_waveform, host_mmode_bulk), all host tables; n_pulses is their length; cycles_per_row: host_psf_carrier's.
+        Outputs, each a device pointer or None: env_dev, truth_disp_dev (float32) and truth_label_dev (uint8) [n_lines][T][R], iq_out_dev
+        [n_lines][T][R][2].  opts: a MmodeOpts, or the keywords of mmode_opts_struct (sigma, seed)"""
+        ln = np.ascontiguousarray(lines, np.uint32).reshape(-1, 2)
+        dil = np.ascontiguousarray(dil_q24, np.int32).reshape(-1)
+        w = np.ascontiguousarray(w_q16, np.int32).reshape(-1)
+        bulk = np.ascontiguousarray(bulk_q24, np.int32).reshape(-1)
+        if w.size != bulk.size:
+            raise ValueError("w_q16 and bulk_q24 take one entry per pulse each, got %d and %d" % (w.size, bulk.size))
+        o = opts if opts is not None else mmode_opts_struct(n_pulses=w.size, **kw)
+        if o.n_pulses != w.size:
+            raise ValueError("the tables hold %d pulses, the options ask for %d" % (w.size, o.n_pulses))
+        check(self.L.mcrt_mmode_lines_frames(self.h, ptr(iq_dev), ptr(tissue_dev), n_frames, n_elements, n_rows, ptr(ln), ln.shape[0], ptr(dil), dil.size, ptr(w),
+                                             ptr(bulk), float(cycles_per_row), C.byref(o), first_image_id, ptr(sigma_dev), ptr(env_dev), ptr(iq_out_dev),
+                                             ptr(truth_disp_dev), ptr(truth_label_dev)))
+
+    def mmode_picture_frames(self, env_dev, n_lines, n_pulses, n_rows, out_dev, truth_label_dev=None, truth_disp_dev=None, peak_dev=None, mean_dev=None,
+                             label_out_dev=None, disp_out_dev=None, opts=None, **kw):
+        """mcrt_mmode_picture_frames: the sweep display of the M-lines' envelopes [n_lines][T][R] -> out_dev uint8 [n_lines][H][W], W = T // hop;
+        optional peak_dev [n_lines], mean_dev [n_lines][W][R], and the truths registered pixel for pixel: label_out_dev uint8 (from
+        truth_label_dev) and disp_out_dev float32 (from truth_disp_dev), each [n_lines][H][W].  opts: a MmodeDisplayOpts, or the keywords of
+        mmode_display_opts_struct"""
+        o = opts if opts is not None else mmode_display_opts_struct(**kw)
+        check(self.L.mcrt_mmode_picture_frames(self.h, ptr(env_dev), ptr(truth_label_dev), ptr(truth_disp_dev), n_lines, n_pulses, n_rows, C.byref(o), ptr(peak_dev),
+                                               ptr(mean_dev), ptr(out_dev), ptr(label_out_dev), ptr(disp_out_dev)))
+
     def scan_convert_frames(self, rf_dev, n_frames, n_elements, n_rows, out_dev, radius_mm=30.0, total_angle=DEFAULT_ANGLE, out_rows=400, out_cols=500):
         check(self.L.mcrt_scan_convert_frames(self.h, ptr(rf_dev), n_frames, n_elements, n_rows, radius_mm, total_angle, ptr(out_dev), out_rows, out_cols))
 
@@ -1774,7 +1870,7 @@ class Simulator:
 
     def __init__(self, scene_data, transducer, n_samples=5, n_rows=None, device=0, seed=0x5EED, psf=None, texture=None,
                  max_depth=10, sanitize_tir=0, tex_n=256, bvh_builder="sah", elevation=False, compound=None, compound_mode="mean", compound_weights=None,
-                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0, speckle=None, noise=None, speckle3d=None, autogain=None, detect=None, flow=None, strain=None, shear=None):
+                 compound_feather=0.0, sweep=None, sweep_pivot_mm=0.0, speckle=None, noise=None, speckle3d=None, autogain=None, detect=None, flow=None, strain=None, shear=None, motion=None):
         """elevation=True: slice thickness.  trace() then traces the psf's elevation_size planes of the frame as one pose pass -- plane k of
         frame f with frame id f * K + k, the frame-id rule of include/mcrt.h -- and folds them into rf_dev with psf.elevation_rows();
         everything after (convolve, bmode, frame) is unchanged.
@@ -1879,6 +1975,28 @@ class Simulator:
             slow, speed_f = host_shear_table(speeds, opts.prf_hz)             # (a speed out of range ends it here)
             self.shear_opts = dict(speeds=speeds, slow=slow, speed_f=speed_f, shape=shape, decay=decay, push=push, geometry=geometry, opts=opts, label=label,
                                    ref_kpa=3.0 * opts.density * ref_speed * ref_speed if ref_kpa is None else float(ref_kpa))
+        # motion={"BLOOD": -0.05} -- a dilation per material name of the scene: the peak axial strain of that material over the cycle,
+        # positive: compression, so a lumen that widens in systole has a negative one; at most 25 % --, or a dict of dilation= (that
+        # mapping), prf_hz= (1000), beats_per_min= (72; the default waveform, host_mmode_waveform), n_pulses= (1024), bulk_mm= and
+        # bulk_per_min= (a rigid sinusoidal shift of the whole line, host_mmode_bulk; 0 and 15), noise= (the receiver noise per I/Q
+        # component of every pulse, 0), seed= and of the label pass (rule, start_offset): M-mode.  m_mode() then traces the frame ONCE and
+        # synthesises the pulses of one scan-line from that frame.  Every other method is left alone.
+        self.motion = _option(motion)
+        if self.motion is not None:
+            md = self.motion if "dilation" in self.motion else dict(dilation=self.motion)
+            names = list(scene_data.material_names)
+            dilation = np.zeros(len(names), np.float64)
+            for name, v in dict(md.pop("dilation")).items():
+                if name not in names:
+                    raise ValueError("motion: the scene has no material %r (it has %s)" % (name, ", ".join(names)))
+                dilation[names.index(name)] = float(v)
+            label = dict(rule=md.pop("rule", "traced"), start_offset=md.pop("start_offset", None))
+            label_opts_struct(**label)                      # (an unknown rule ends it here)
+            timing = dict(prf_hz=float(md.pop("prf_hz", 1000.0)), beats_per_min=float(md.pop("beats_per_min", 72.0)), bulk_mm=float(md.pop("bulk_mm", 0.0)),
+                          bulk_per_min=float(md.pop("bulk_per_min", 15.0)))
+            opts = mmode_opts_struct(sigma=md.pop("noise", None), **md)        # (unknown keywords end it here)
+            host_mmode_waveform(timing["prf_hz"], timing["beats_per_min"], opts.n_pulses)      # (a rate or a pulse count out of range ends it here)
+            self.motion = dict(dilation=dilation, dil=host_mmode_table(dilation), opts=opts, label=label, **timing)     # (a dilation above the cap ends it here)
         self.flow = _option(flow)
         if self.flow is not None:
             fd = self.flow if "velocity_mm_s" in self.flow else dict(velocity_mm_s=self.flow)
@@ -2610,6 +2728,53 @@ class Simulator:
                                        grey_min=grey_min, alpha=alpha, ref_strain=self.shear_opts["ref_kpa"] if ref_kpa is None else ref_kpa)
             return dict(self._shear_host(b), rgb=self.ctx.d2h(rgb, (rows, cols, 3), np.uint8), grey=self.ctx.d2h(grey, (rows, cols), np.uint8),
                         modulus_img=self.ctx.d2h(img, (rows, cols), np.float32), quality_img=self.ctx.d2h(img + 4 * n, (rows, cols), np.float32))
+
+    # ---- M-mode (motion=)
+    def m_mode(self, frame_id=0, line=None, depth_mm=None, hop=None, height=None, waveform=None, bulk=None, **display):
+        """the M-mode sweep of one scan-line -> dict(picture uint8 [H][W] (a column is a time, a row a depth), labels uint8 [H][W] and
+        truth_disp float32 [H][W] (rows; positive: read from deeper down) registered with it pixel for pixel, env float32 [T][R] (the
+        M-line of every pulse), time_s float64 [W] (each column's first pulse) and depth_mm float64 [H]).  It makes ONE trace of the frame,
+        one label pass and frame()'s stages before the envelope, detects the analytic lines, then mcrt_mmode_lines_frames and
+        mcrt_mmode_picture_frames (motion= only).  line: the scan-line (default: the middle one); depth_mm: (lo, hi), the depths shown
+        (default: the whole line); hop: pulses per column (4); height: H (400); waveform: int32 [n_pulses] in Q16 (default:
+        host_mmode_waveform at motion='s prf_hz and beats_per_min); bulk: int32 [n_pulses] in Q24 rows (default: host_mmode_bulk of
+        motion='s bulk_mm and bulk_per_min); display: dynamic_range_db, gain_db, ref of mmode_display_opts_struct"""
+        if self.motion is None:
+            raise RuntimeError("M-mode needs Simulator(motion=...)")
+        for on, what in ((self.sweep is not None, "sweep="), (self.steers is not None, "compound="), (self.elevation, "elevation="), (self.psf.has_bands, "a psf with bands")):
+            if on:
+                raise RuntimeError("M-mode is one scan-line of one plane and one pulse shape: it does not combine with %s" % what)
+        mo, E, R = self.motion, self.E, self.R
+        line = E // 2 if line is None else int(line)
+        if not 0 <= line < E:
+            raise ValueError("m_mode: scan-line %d is not in 0..%d" % (line, E - 1))
+        T, prf, pitch = int(mo["opts"].n_pulses), mo["prf_hz"], row_pitch_mm(self.tr.frequency)
+        w = host_mmode_waveform(prf, mo["beats_per_min"], T) if waveform is None else np.ascontiguousarray(waveform, np.int32).reshape(-1)
+        b = host_mmode_bulk(prf, mo["bulk_per_min"], mo["bulk_mm"] / pitch, T) if bulk is None else np.ascontiguousarray(bulk, np.int32).reshape(-1)
+        if w.size != T or b.size != T:
+            raise ValueError("m_mode: waveform and bulk take one entry per pulse (%d), got %d and %d" % (T, w.size, b.size))
+        o = mmode_display_opts_struct(hop=hop, height=height, **display)
+        if depth_mm is not None:
+            o.row_lo = min(max(int(round(float(depth_mm[0]) / pitch)), 0), R - 1)
+            o.row_hi = min(max(int(round(float(depth_mm[1]) / pitch)), o.row_lo + 1), R)
+        if o.hop == 0 or o.hop > T:
+            raise ValueError("m_mode: a hop of %d pulses leaves no column of %d pulses" % (o.hop, T))
+        W, H, n, m = T // o.hop, int(o.height), E * R, T * R
+        row_lo, row_hi = int(o.row_lo), int(o.row_hi) if o.row_hi else R
+        cycles = host_psf_carrier(self.tr.frequency, self.psf.resolution_um)
+        with contextlib.ExitStack() as held:
+            tissue, iq, env, lab, disp, pic, lab_pic, disp_pic = (held.enter_context(self.ctx.temp(size)) for size in (n, 8 * n, 4 * m, m, 4 * m, H * W, H * W, 4 * H * W))
+            self.trace(frame_id)
+            self.ctx.label_frames(tissue_dev=tissue, **mo["label"])
+            self._stages(self._stack, frame_id, envelope=False)
+            self.ctx.detect_frames(self.rf_dev, 1, E, R, iq_dev=iq, **(self.detect or {}))
+            self.ctx.mmode_lines_frames(iq, tissue, 1, E, R, [[0, line]], mo["dil"], w, b, cycles, first_image_id=frame_id, env_dev=env, truth_disp_dev=disp,
+                                        truth_label_dev=lab, opts=mo["opts"])
+            self.ctx.mmode_picture_frames(env, 1, T, R, pic, truth_label_dev=lab, truth_disp_dev=disp, label_out_dev=lab_pic, disp_out_dev=disp_pic, opts=o)
+            rows = np.clip(row_lo + (np.arange(H) + 0.5) * (row_hi - row_lo) / H - 0.5, row_lo, row_hi - 1)
+            return dict(picture=self.ctx.d2h(pic, (H, W), np.uint8), labels=self.ctx.d2h(lab_pic, (H, W), np.uint8), truth_disp=self.ctx.d2h(disp_pic, (H, W), np.float32),
+                        env=self.ctx.d2h(env, (T, R), np.float32), time_s=np.arange(W) * int(o.hop) / prf, depth_mm=rows * pitch,
+                        lines=dict(line=line, row_lo=row_lo, row_hi=row_hi, hop=int(o.hop), w_q16=w, bulk_q24=b))
 
     def colour_flow(self, frame_id=0, **display):
         """the colour-flow picture of a frame -> dict(rgb uint8 [out_rows][out_cols][3], grey uint8 [out_rows][out_cols], velocity float32

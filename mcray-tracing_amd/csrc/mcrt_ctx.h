@@ -229,6 +229,10 @@ struct ImageStages {
     // [n_labels], the pitches [R], the time profile [n_shape] and the decay [n_amp]; its rotor is spec_rotor) and of mcrt_shear_speed_frames
     // (the pitches in mm [R]), and the arrival ticks [F][E][R] of the largest mcrt_shear_wave_frames so far
     StagedWords shear_slow, shear_speed, shear_pitch, shear_shape, shear_amp, shear_pitch_mm; Buf<long long> d_shear_arrival;
+    // M-mode: the last host tables of mcrt_mmode_lines_frames (the lines [n_lines][2], the dilations [n_labels], the waveform [T] and the
+    // bulk motion [T]; its rotor is spec_rotor) and of mcrt_mmode_picture_frames (the depth table: first taps [H] and weights [H]), and
+    // the lines' peaks of a mcrt_mmode_picture_frames without a peak_dev
+    StagedWords mmode_lines, mmode_dil, mmode_w, mmode_bulk, mmode_idx, mmode_wt; Buf<float> d_mmode_peak;
     // automatic gain (mcrt_autogain_frames): the histograms of a chunk of frames [frames][n_bands][2048], at most AUTOGAIN_HIST_WORDS, and the row
     // gains [n_frames][R] of the largest call so far that gave no gain_dev
     Buf<uint32_t> d_aghist; Buf<float> d_aggain;

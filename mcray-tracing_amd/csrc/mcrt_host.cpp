@@ -1432,6 +1432,130 @@ extern "C" int mcrt_shear_map(uint32_t kind, uint8_t *lut)
     return MCRT_OK;
 }
 
+// ---- M-mode (the contracts are in include/mcrt.h) ---------------------------------------
+extern "C" int mcrt_default_mmode_opts(mcrt_mmode_opts *o)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_mmode_opts: null options");
+    o->n_pulses = 1024u; o->sigma = 0.0f; o->seed = 0x4D4D4F44u;
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_default_mmode_display_opts(mcrt_mmode_display_opts *o)
+{
+    if (!o) return mcrt::set_error(MCRT_ERR_INVALID, "mcrt_default_mmode_display_opts: null options");
+    o->hop = 4u; o->height = 400u; o->row_lo = 0u; o->row_hi = 0u; o->dynamic_range_db = 60.0f; o->gain_db = 0.0f; o->ref = 0.0f;
+    return MCRT_OK;
+}
+
+int mcrt::mmode_check(const char *fn, const mcrt_mmode_opts *o)
+{
+    if (o->n_pulses < 1u || o->n_pulses > 16384u) return set_error(MCRT_ERR_INVALID, "%s: n_pulses must be 1 .. 16384 (%u)", fn, o->n_pulses);
+    if (!(std::isfinite(o->sigma) && o->sigma >= 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: sigma must be finite and >= 0 (%g)", fn, (double)o->sigma);
+    return MCRT_OK;
+}
+
+int mcrt::mmode_display_check(const char *fn, const mcrt_mmode_display_opts *o, uint32_t T, uint32_t R)
+{
+    if (o->hop == 0u) return set_error(MCRT_ERR_INVALID, "%s: hop is zero", fn);
+    if (o->hop > T) return set_error(MCRT_ERR_INVALID, "%s: a hop of %u pulses leaves no column of %u pulses", fn, o->hop, T);
+    if (o->height < 1u || o->height > 4096u) return set_error(MCRT_ERR_INVALID, "%s: height must be 1 .. 4096 (%u)", fn, o->height);
+    const uint32_t hi = o->row_hi ? o->row_hi : R;
+    if (o->row_lo >= hi || hi > R) return set_error(MCRT_ERR_INVALID, "%s: the rows [%u, %u) are not rows of a line of %u", fn, o->row_lo, hi, R);
+    if (!(std::isfinite(o->dynamic_range_db) && o->dynamic_range_db > 0.0f)) return set_error(MCRT_ERR_INVALID, "%s: dynamic_range_db must be finite and > 0 (%g)", fn, (double)o->dynamic_range_db);
+    if (!std::isfinite(o->gain_db) || !std::isfinite(o->ref)) return set_error(MCRT_ERR_INVALID, "%s: gain_db and ref must be finite (%g, %g)", fn, (double)o->gain_db, (double)o->ref);
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_mmode_table(const double *dilation, uint32_t n_labels, int32_t *dil_q24)
+{
+    static const char fn[] = "mcrt_mmode_table";
+    if (!dilation || !dil_q24) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (n_labels == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: n_labels is zero", fn);
+    if (n_labels > 254u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: at most 254 labels (%u)", fn, n_labels);
+    for (uint32_t l = 0; l < n_labels; l++)
+        if (!(std::fabs(dilation[l] * 16777216.0) <= 4194304.5))      // (a NaN and an infinity fail here too)
+            return mcrt::set_error(MCRT_ERR_INVALID, "%s: the dilation of label %u, %g, is not finite or is above 25 %%", fn, l, dilation[l]);
+    std::vector<int32_t> dil(n_labels);
+    for (uint32_t l = 0; l < n_labels; l++) {
+        const long long q = std::llrint(dilation[l] * 16777216.0);
+        if (q > 4194304ll || q < -4194304ll) return mcrt::set_error(MCRT_ERR_INVALID, "%s: the dilation of label %u, %g, is above 25 %%", fn, l, dilation[l]);
+        dil[l] = (int32_t)q;
+    }
+    memcpy(dil_q24, dil.data(), 4 * (size_t)n_labels);
+    return MCRT_OK;
+}
+
+// the pulses of a slow-time table: mcrt_mmode_waveform's and mcrt_mmode_bulk's common refusals
+static int mmode_pulses(const char *fn, const void *table, uint32_t T, double prf_hz)
+{
+    if (!table) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null table", fn);
+    if (T == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: n_pulses is zero", fn);
+    if (T > 16384u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: at most 16384 pulses (%u)", fn, T);
+    if (!(std::isfinite(prf_hz) && prf_hz > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: prf_hz must be finite and > 0 (%g)", fn, prf_hz);
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_mmode_waveform(double prf_hz, double beats_per_min, uint32_t T, int32_t *w_q16)
+{
+    static const char fn[] = "mcrt_mmode_waveform";
+    if (const int rc = mmode_pulses(fn, w_q16, T, prf_hz)) return rc;
+    if (!(std::isfinite(beats_per_min) && beats_per_min > 0.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: beats_per_min must be finite and > 0 (%g)", fn, beats_per_min);
+    for (uint32_t t = 0; t < T; t++) {
+        const double u = t * beats_per_min / (60.0 * prf_hz), x = u - std::floor(u), s = std::sin(3.141592653589793 * x / 0.3);
+        w_q16[t] = (int32_t)std::llrint(65536.0 * (x < 0.3 ? s * s : 0.0));
+    }
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_mmode_bulk(double prf_hz, double cycles_per_min, double amplitude_rows, uint32_t T, int32_t *bulk_q24)
+{
+    static const char fn[] = "mcrt_mmode_bulk";
+    if (const int rc = mmode_pulses(fn, bulk_q24, T, prf_hz)) return rc;
+    if (!std::isfinite(cycles_per_min)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: cycles_per_min must be finite (%g)", fn, cycles_per_min);
+    if (!(std::fabs(amplitude_rows) <= 32.0)) return mcrt::set_error(MCRT_ERR_INVALID, "%s: amplitude_rows must be finite and at most 32 rows (%g)", fn, amplitude_rows);
+    for (uint32_t t = 0; t < T; t++)
+        bulk_q24[t] = (int32_t)std::llrint(amplitude_rows * 16777216.0 * std::sin(6.283185307179586 * t * cycles_per_min / (60.0 * prf_hz)));
+    return MCRT_OK;
+}
+
+// the draws k_mmode_lines makes for one M-line, [T][R][2]
+extern "C" int mcrt_mmode_draws(uint32_t seed, uint32_t image_id, uint32_t line, uint32_t n_rows, uint32_t T, int32_t *d)
+{
+    static const char fn[] = "mcrt_mmode_draws";
+    if (!d) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null d", fn);
+    if (n_rows == 0 || T == 0) return mcrt::set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_rows %u, n_pulses %u)", fn, n_rows, T);
+    if (n_rows > 2048u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: n_rows: at most 2048 rows (%u)", fn, n_rows);
+    if (T > 16384u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: at most 16384 pulses (%u)", fn, T);
+    for (uint32_t t = 0; t < T; t++)
+        for (uint32_t r = 0; r < n_rows; r++) {
+            uint32_t o[4];
+            host_philox4x32_10(line, r, 0x4D4D4F44u, t, seed, image_id, o);
+            int32_t *p = d + 2u * ((size_t)t * n_rows + r);
+            p[0] = (int32_t)((o[0] & 0xffffu) + (o[0] >> 16) + (o[1] & 0xffffu) + (o[1] >> 16)) - 131070;
+            p[1] = (int32_t)((o[2] & 0xffffu) + (o[2] >> 16) + (o[3] & 0xffffu) + (o[3] >> 16)) - 131070;
+        }
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_mmode_rows(uint32_t row_lo, uint32_t row_hi, uint32_t H, uint32_t *idx, float *wt)
+{
+    static const char fn[] = "mcrt_mmode_rows";
+    if (!idx || !wt) return mcrt::set_error(MCRT_ERR_INVALID, "%s: null table", fn);
+    if (H == 0 || H > 4096u) return mcrt::set_error(MCRT_ERR_INVALID, "%s: height must be 1 .. 4096 (%u)", fn, H);
+    if (row_lo >= row_hi) return mcrt::set_error(MCRT_ERR_INVALID, "%s: the rows [%u, %u) are empty", fn, row_lo, row_hi);
+    if (row_hi > 2048u) return mcrt::set_error(MCRT_ERR_LIMIT, "%s: at most 2048 rows (%u)", fn, row_hi);
+    for (uint32_t y = 0; y < H; y++) {
+        const double p = (double)row_lo + (y + 0.5) * (double)(row_hi - row_lo) / (double)H - 0.5, f = std::floor(p);
+        if (f < (double)row_lo) { idx[y] = row_lo; wt[y] = 0.0f; }
+        else if (f > (double)(row_hi - 1u)) { idx[y] = row_hi - 1u; wt[y] = 0.0f; }
+        else {
+            const float w = (float)(p - f);
+            idx[y] = (uint32_t)f; wt[y] = w < 0.0f ? 0.0f : w > 1.0f ? 1.0f : w;
+        }
+    }
+    return MCRT_OK;
+}
+
 // ---- automatic gain (the contract is in include/mcrt.h) ---------------------------------------
 extern "C" int mcrt_default_autogain_opts(mcrt_autogain_opts *o)
 {

@@ -531,6 +531,111 @@ extern "C" int mcrt_shear_speed_frames(mcrt_ctx *c, const float *peak_time_dev, 
     return MCRT_OK;
 }
 
+// ---- M-mode (the contracts are in include/mcrt.h; the defaults, the option ranges, the tables, the draws and the depth table are host
+// code: mcrt_host.cpp).  Each call checks everything before anything is enqueued. ----
+static int mmode_sizes(const char *fn, uint32_t n_lines, uint32_t T, uint32_t R)
+{
+    if (R > MCRT_MAX_ROWS) return set_error(MCRT_ERR_LIMIT, "%s: n_rows: at most %d rows (%u)", fn, MCRT_MAX_ROWS, R);
+    if (T > 16384u) return set_error(MCRT_ERR_LIMIT, "%s: at most 16384 pulses (%u)", fn, T);
+    if (n_lines > 65535u) return set_error(MCRT_ERR_LIMIT, "%s: at most 65535 lines (%u)", fn, n_lines);
+    if ((double)n_lines * (double)T * (double)R >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: 2^31 samples or more (%u lines x %u pulses x %u rows)", fn, n_lines, T, R);
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_mmode_lines_frames(mcrt_ctx *c, const float *iq_dev, const uint8_t *tissue_dev, uint32_t n_frames, uint32_t E, uint32_t R, const mcrt_mline *lines,
+                                       uint32_t n_lines, const int32_t *dil_q24, uint32_t n_labels, const int32_t *w_q16, const int32_t *bulk_q24, double cycles_per_row,
+                                       const mcrt_mmode_opts *o, uint32_t first_image_id, const float *sigma_dev, float *env_dev, float *iq_out_dev,
+                                       float *truth_disp_dev, uint8_t *truth_label_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_mmode_lines_frames";
+    if (!iq_dev || !tissue_dev || !lines || !dil_q24 || !w_q16 || !bulk_q24 || !o) return set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (n_labels == 0 || n_lines == 0) return set_error(MCRT_ERR_INVALID, "%s: an empty table (n_labels %u, n_lines %u)", fn, n_labels, n_lines);
+    MCRT_TRY(strain_sizes(fn, n_frames, E, R, cycles_per_row));
+    MCRT_TRY(mcrt::mmode_check(fn, o));
+    if (!env_dev && !iq_out_dev && !truth_disp_dev && !truth_label_dev) return set_error(MCRT_ERR_INVALID, "%s: no output is given", fn);
+    if (n_labels > 254u) return set_error(MCRT_ERR_LIMIT, "%s: at most 254 labels (%u)", fn, n_labels);
+    const uint32_t T = o->n_pulses;
+    MCRT_TRY(mmode_sizes(fn, n_lines, T, R));
+    if ((uint64_t)first_image_id + n_frames > 0x100000000ull) return set_error(MCRT_ERR_LIMIT, "%s: first_image_id: the ids of %u images from %u on pass 2^32", fn, n_frames, first_image_id);
+    for (uint32_t j = 0; j < n_lines; j++)
+        if (lines[j].image >= n_frames || lines[j].line >= E)
+            return set_error(MCRT_ERR_INVALID, "%s: line %u (image %u, scan-line %u) is outside the stack %u x %u", fn, j, lines[j].image, lines[j].line, n_frames, E);
+    for (uint32_t l = 0; l < n_labels; l++)
+        if (dil_q24[l] > 4194304 || dil_q24[l] < -4194304) return set_error(MCRT_ERR_INVALID, "%s: dil_q24[%u] = %d is outside +-2^22", fn, l, dil_q24[l]);
+    for (uint32_t t = 0; t < T; t++) {
+        if (w_q16[t] > 65536 || w_q16[t] < -65536) return set_error(MCRT_ERR_INVALID, "%s: w_q16[%u] = %d is outside +-65536", fn, t, w_q16[t]);
+        if (bulk_q24[t] > (32 << 24) || bulk_q24[t] < -(32 << 24)) return set_error(MCRT_ERR_INVALID, "%s: bulk_q24[%u] = %d is outside +-32 rows", fn, t, bulk_q24[t]);
+    }
+    const size_t n = (size_t)n_frames * E * R, m = (size_t)n_lines * T * R;
+    const Range outs[4] = { { env_dev, 4 * m, "env_dev" }, { iq_out_dev, 8 * m, "iq_out_dev" }, { truth_disp_dev, 4 * m, "truth_disp_dev" }, { truth_label_dev, m, "truth_label_dev" } };
+    const Range ins[3] = { { iq_dev, 8 * n, "iq_dev" }, { tissue_dev, n, "tissue_dev" }, { sigma_dev, 4 * (size_t)n_frames, "sigma_dev" } };
+    for (int i = 0; i < 3; i++)
+        if (ins[i].p) MCRT_TRY(check_overlap(fn, ins[i], outs, 4, i == 0));      // (iq_dev is always there: the outputs among themselves once)
+    static const std::vector<float> rotor = [] { std::vector<float> l(8192); mcrt_spectral_rotor(l.data()); return l; }();
+    MCRT_TRY(c->img.spec_rotor.put(rotor.data(), 8192, c->stream));
+    MCRT_TRY(c->img.mmode_lines.put(lines, 2 * (size_t)n_lines, c->stream));
+    MCRT_TRY(c->img.mmode_dil.put(dil_q24, n_labels, c->stream));
+    MCRT_TRY(c->img.mmode_w.put(w_q16, T, c->stream));
+    MCRT_TRY(c->img.mmode_bulk.put(bulk_q24, T, c->stream));
+    mcrt::MmodeLinesArgs a; memset(&a, 0, sizeof a);
+    a.iq = (const float2 *)iq_dev; a.tissue = tissue_dev; a.lines = c->img.mmode_lines.as<uint32_t>(); a.dil = c->img.mmode_dil.as<int32_t>();
+    a.w = c->img.mmode_w.as<int32_t>(); a.bulk = c->img.mmode_bulk.as<int32_t>(); a.lut = c->img.spec_rotor.as<float2>(); a.sigma_dev = sigma_dev;
+    a.env = env_dev; a.iq_out = (float2 *)iq_out_dev; a.truth_disp = truth_disp_dev; a.truth_label = truth_label_dev;
+    a.carrier_q32 = std::llrint(cycles_per_row * 4294967296.0); a.E = E; a.R = R; a.T = T; a.n_lines = n_lines;
+    a.chunks = (T + MMODE_PULSE_CHUNK - 1u) / MMODE_PULSE_CHUNK; a.n_labels = n_labels;
+    a.seed = o->seed; a.first_id = first_image_id; a.sigma = o->sigma; a.inv_std = (float)(1.0 / std::sqrt(1431655765.0));
+    HIP_TRY(mcrt::launch_mmode_lines(a, c->stream));
+    return MCRT_OK;
+}
+
+extern "C" int mcrt_mmode_picture_frames(mcrt_ctx *c, const float *env_dev, const uint8_t *truth_label_dev, const float *truth_disp_dev, uint32_t n_lines, uint32_t T,
+                                         uint32_t R, const mcrt_mmode_display_opts *o, float *peak_dev, float *mean_dev, uint8_t *out_dev, uint8_t *label_out_dev,
+                                         float *disp_out_dev)
+{
+    CTX_TRY(c);
+    static const char fn[] = "mcrt_mmode_picture_frames";
+    if (!env_dev || !o || !out_dev) return set_error(MCRT_ERR_INVALID, "%s: null pointer", fn);
+    if (n_lines == 0 || T == 0 || R == 0) return set_error(MCRT_ERR_INVALID, "%s: zero sizes (n_lines %u, n_pulses %u, n_rows %u)", fn, n_lines, T, R);
+    MCRT_TRY(mmode_sizes(fn, n_lines, T, R));
+    MCRT_TRY(mcrt::mmode_display_check(fn, o, T, R));
+    if (label_out_dev && !truth_label_dev) return set_error(MCRT_ERR_INVALID, "%s: label_out_dev needs truth_label_dev", fn);
+    if (disp_out_dev && !truth_disp_dev) return set_error(MCRT_ERR_INVALID, "%s: disp_out_dev needs truth_disp_dev", fn);
+    const uint32_t W = T / o->hop, H = o->height, row_hi = o->row_hi ? o->row_hi : R;
+    if ((double)n_lines * (double)H * (double)W >= 0x1p31) return set_error(MCRT_ERR_LIMIT, "%s: pictures of 2^31 pixels or more (%u x %u x %u)", fn, n_lines, H, W);
+    const size_t m = (size_t)n_lines * T * R, px = (size_t)n_lines * H * W;
+    const Range outs[5] = { { peak_dev, 4 * (size_t)n_lines, "peak_dev" }, { mean_dev, 4 * (size_t)n_lines * W * R, "mean_dev" }, { out_dev, px, "out_dev" },
+                            { label_out_dev, px, "label_out_dev" }, { disp_out_dev, 4 * px, "disp_out_dev" } };
+    const Range ins[3] = { { env_dev, 4 * m, "env_dev" }, { truth_label_dev, m, "truth_label_dev" }, { truth_disp_dev, 4 * m, "truth_disp_dev" } };
+    for (int i = 0; i < 3; i++)
+        if (ins[i].p) MCRT_TRY(check_overlap(fn, ins[i], outs, 5, i == 0));      // (env_dev is always there: the outputs among themselves once)
+    std::vector<uint32_t> idx(H); std::vector<float> wt(H);
+    MCRT_TRY(mcrt_mmode_rows(o->row_lo, row_hi, H, idx.data(), wt.data()));
+    const bool own_ref = o->ref > 0.0f;
+    float *peak = peak_dev;
+    if (!peak && !own_ref) {
+        if (n_lines > c->img.d_mmode_peak.cap) {
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            HIP_TRY(c->img.d_mmode_peak.alloc(n_lines));
+        }
+        peak = c->img.d_mmode_peak;
+    }
+    MCRT_TRY(c->img.mmode_idx.put(idx.data(), H, c->stream));
+    MCRT_TRY(c->img.mmode_wt.put(wt.data(), H, c->stream));
+    mcrt::MmodePictureArgs a; memset(&a, 0, sizeof a);
+    a.env = env_dev; a.truth_label = truth_label_dev; a.truth_disp = truth_disp_dev; a.idx = c->img.mmode_idx.as<uint32_t>(); a.wt = c->img.mmode_wt.as<float>();
+    a.peak = peak; a.mean = mean_dev; a.out = out_dev; a.label_out = label_out_dev; a.disp_out = disp_out_dev;
+    a.n_lines = n_lines; a.T = T; a.R = R; a.W = W; a.H = H; a.hop = o->hop; a.row_lo = o->row_lo; a.row_hi = row_hi;
+    a.ref = o->ref; a.gain = o->gain_db; a.dr = o->dynamic_range_db;
+    if (peak || mean_dev) {
+        if (peak) HIP_TRY(hipMemsetAsync(peak, 0, 4 * (size_t)n_lines, c->stream));
+        HIP_TRY(mcrt::launch_mmode_peak(a, c->stream));
+    }
+    if (own_ref) a.peak = nullptr;
+    HIP_TRY(mcrt::launch_mmode_picture(a, c->stream));
+    return MCRT_OK;
+}
+
 // the scan-conversion maps of a geometry on the device, in cache m: the plain maps (cp null: mcrt_scan_maps, one view) or the N views of a steer
 // list (mcrt_compound_maps), [N][2][n_pad]
 static int ensure_maps(mcrt_ctx *c, MapCache &m, uint32_t E, uint32_t R, double radius_mm, double total_angle, uint32_t orows, uint32_t ocols, const mcrt_compound *cp, const float **maps)

@@ -84,5 +84,8 @@ int spectral_check(const char *fn, const mcrt_spectral_opts *o);
 int strain_check(const char *fn, const mcrt_strain_opts *o);
 // mcrt_host.cpp: the ranges of mcrt_shear_opts against a stack of E scan-lines of R rows, which mcrt_shear_wave_frames and mcrt_shear_speed_frames share
 int shear_check(const char *fn, const mcrt_shear_opts *o, uint32_t E, uint32_t R);
+// mcrt_host.cpp: the ranges of mcrt_mmode_opts (mcrt_mmode_lines_frames) and of mcrt_mmode_display_opts against lines of T pulses and R rows (mcrt_mmode_picture_frames)
+int mmode_check(const char *fn, const mcrt_mmode_opts *o);
+int mmode_display_check(const char *fn, const mcrt_mmode_display_opts *o, uint32_t T, uint32_t R);
 }
 #endif

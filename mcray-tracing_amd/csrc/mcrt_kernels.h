@@ -21,6 +21,7 @@
 //   mcrt_spectral.hip k_gate_series (spectral Doppler: mcrt_spectral_series_frames), k_spectrum<N> (mcrt_spectral_frames), k_sonogram_peak, k_sonogram (mcrt_sonogram_frames)
 //   mcrt_strain.hip  k_strain_warp (strain elastography: mcrt_strain_compress_frames), k_strain_track, k_strain_slope (mcrt_strain_frames), k_elastogram (mcrt_elastogram_frames)
 //   mcrt_shear.hip   k_shear_arrival, k_shear_track (shear-wave elastography: mcrt_shear_wave_frames), k_shear_speed (mcrt_shear_speed_frames); mcrt_warp.h: the line reading it shares with k_strain_warp
+//   mcrt_mmode.hip   k_mmode_lines (M-mode: mcrt_mmode_lines_frames; it reads its lines through mcrt_warp.h too), k_mmode_peak, k_mmode_picture (mcrt_mmode_picture_frames)
 //   mcrt_autogain.hip k_autogain_hist, k_autogain_curve, k_autogain_apply (automatic gain: mcrt_autogain_frames)
 //   mcrt_recon.hip   k_recon_splat, k_recon_resolve (freehand 3-D reconstruction: mcrt_recon_frames)
 //   mcrt_label.hip   k_label (ground-truth label maps: mcrt_label_frames), k_label_gather (mcrt_label_scan_convert_frames, mcrt_label_volume_frames)
@@ -532,6 +533,44 @@ struct ShearSpeedArgs {
     float kf, d3;                       // (float)(prf_hz * 0.001), 3.0f * density
 };
 hipError_t launch_shear_speed(const ShearSpeedArgs &a, hipStream_t st);
+// k_mmode_lines (mcrt_mmode_lines_frames): the detected pairs and the tissue labels of the named scan-lines -> T moving lines of each, their envelopes and the truths
+#define MMODE_PULSE_CHUNK 16u                       // a workgroup of k_mmode_lines owns one M-line and at most this many consecutive pulses
+#define MMODE_THREADS 256u
+struct MmodeLinesArgs {
+    const float2 *iq;                   // [F][E][R] (I, Q)
+    const uint8_t *tissue;              // [F][E][R]
+    const uint32_t *lines;              // [n_lines][2]: image, line (the context's copy, as the next three)
+    const int32_t *dil;                 // [n_labels] Q24
+    const int32_t *w, *bulk;            // [T] Q16, [T] Q24
+    const float2 *lut;                  // [4096] the rotor (the context's copy)
+    const float *sigma_dev;             // [F] or null: sigma
+    float *env;                         // [n_lines][T][R] or null
+    float2 *iq_out;                     // [n_lines][T][R] or null
+    float *truth_disp;                  // [n_lines][T][R] or null
+    uint8_t *truth_label;               // [n_lines][T][R] or null
+    long long carrier_q32;              // llrint(cycles_per_row * 2^32)
+    uint32_t E, R, T, n_lines, chunks, n_labels;    // chunks: ceil(T / MMODE_PULSE_CHUNK)
+    uint32_t seed, first_id;
+    float sigma, inv_std;
+};
+hipError_t launch_mmode_lines(const MmodeLinesArgs &a, hipStream_t st);       // the instantiation: the outputs that are given
+// k_mmode_peak and k_mmode_picture (mcrt_mmode_picture_frames): env [n_lines][T][R] -> the column means, the lines' peaks and the bytes [n_lines][H][W]
+struct MmodePictureArgs {
+    const float *env;                   // [n_lines][T][R]
+    const uint8_t *truth_label;         // [n_lines][T][R] or null
+    const float *truth_disp;            // [n_lines][T][R] or null
+    const uint32_t *idx;                // [H] the first tap (the context's copy, as wt)
+    const float *wt;                    // [H] the second tap's weight
+    float *peak;                        // [n_lines], zeroed before k_mmode_peak; null in k_mmode_picture: ref
+    float *mean;                        // [n_lines][W][R] or null
+    uint8_t *out;                       // [n_lines][H][W]
+    uint8_t *label_out;                 // [n_lines][H][W] or null
+    float *disp_out;                    // [n_lines][H][W] or null
+    uint32_t n_lines, T, R, W, H, hop, row_lo, row_hi;
+    float ref, gain, dr;
+};
+hipError_t launch_mmode_peak(const MmodePictureArgs &a, hipStream_t st);
+hipError_t launch_mmode_picture(const MmodePictureArgs &a, hipStream_t st);
 hipError_t launch_remap(const float *img, uint32_t n_img, uint32_t E, uint32_t R, const float *map_col, const float *map_row, float *out, uint32_t n, hipStream_t st);
 hipError_t launch_bmode_peak(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, float *peak, hipStream_t st);   // peak[F] zeroed before
 hipError_t launch_bmode_grey(const float *rf, uint32_t F, uint32_t E, uint32_t R, const float *tgc, const float *peak /*[F] or null: ref*/, float ref,

@@ -144,6 +144,12 @@
 // --shear-pulses N pulses (4..256; 64) at --shear-prf HZ (10000), and the modulus 3 rho c^2 of the time-to-peak speed is laid over the 8-bit
 // B-mode frame: soft blue, 12 kPa (2 m/s) green, stiff red.  --shear-truth FILE.raw writes the true shear speed of every scan-line sample,
 // float32 [512][465].  It does not combine with --compound, --sweep, --elevation or the band options.
+// --m-mode FILE.pgm writes the M-mode sweep of scan-line --m-line LINE of the last frame, a binary PGM of --m-height H (400) rows and
+// T / N columns: --motion NAME:e[,NAME:e...] gives materials their dilation (the peak axial strain over the cycle, positive: compression, at
+// most 0.25; the others have 0), the frame's ONE trace is moved over --m-pulses T pulses (1..16384; 1024) at --m-prf HZ (1000) under the default
+// waveform of --m-bpm X beats per minute (72) and a rigid sinusoidal shift of --m-bulk-mm A,PER_MIN (0,15), --m-hop N (4) pulses make a
+// column, and --m-depth-mm LO,HI shows those depths (the whole line).  --m-labels FILE.pgm writes the material and --m-truth FILE.raw the true
+// displacement [rows] of every pixel, float32 [H][T / N].  It does not combine with --compound, --sweep, --elevation or the band options.
 #include "mcrt_host.hpp"
 #include <algorithm>
 #include <chrono>
@@ -210,6 +216,12 @@ int main(int argc, char **argv)
                *strain_truth = nullptr;   // the options as given
     const char *shear_elastogram = nullptr, *shear_speed = nullptr, *shear_push = nullptr, *shear_pulses = nullptr, *shear_prf = nullptr, *shear_truth = nullptr;
     mcrt_shear_opts shopts; mcrt_default_shear_opts(&shopts);
+    const char *m_mode = nullptr, *m_line = nullptr, *motion = nullptr, *m_prf = nullptr, *m_bpm = nullptr, *m_pulses = nullptr, *m_hop = nullptr, *m_height = nullptr,
+               *m_depth = nullptr, *m_bulk = nullptr, *m_labels = nullptr, *m_truth = nullptr;
+    mcrt_mmode_opts mmopts; mcrt_default_mmode_opts(&mmopts);
+    mcrt_mmode_display_opts mdopts; mcrt_default_mmode_display_opts(&mdopts);
+    double m_prf_hz = 1000.0, m_beats = 72.0, m_bulk_mm = 0.0, m_bulk_per_min = 15.0, m_depth_lo = 0.0, m_depth_hi = 0.0;
+    uint32_t m_scan_line = 0;
     mcrt_elastogram_opts shelopts; mcrt_default_elastogram_opts(&shelopts);
     double push_depth_mm = 0.0, push_len_mm = 0.0;
     double applied = 0.01;
@@ -309,6 +321,18 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "--shear-pulses") && i + 1 < argc) shear_pulses = argv[++i];
             else if (!std::strcmp(argv[i], "--shear-prf") && i + 1 < argc) shear_prf = argv[++i];
             else if (!std::strcmp(argv[i], "--shear-truth") && i + 1 < argc) shear_truth = argv[++i];
+            else if (!std::strcmp(argv[i], "--m-mode") && i + 1 < argc) m_mode = argv[++i];
+            else if (!std::strcmp(argv[i], "--m-line") && i + 1 < argc) m_line = argv[++i];
+            else if (!std::strcmp(argv[i], "--motion") && i + 1 < argc) motion = argv[++i];
+            else if (!std::strcmp(argv[i], "--m-prf") && i + 1 < argc) m_prf = argv[++i];
+            else if (!std::strcmp(argv[i], "--m-bpm") && i + 1 < argc) m_bpm = argv[++i];
+            else if (!std::strcmp(argv[i], "--m-pulses") && i + 1 < argc) m_pulses = argv[++i];
+            else if (!std::strcmp(argv[i], "--m-hop") && i + 1 < argc) m_hop = argv[++i];
+            else if (!std::strcmp(argv[i], "--m-height") && i + 1 < argc) m_height = argv[++i];
+            else if (!std::strcmp(argv[i], "--m-depth-mm") && i + 1 < argc) m_depth = argv[++i];
+            else if (!std::strcmp(argv[i], "--m-bulk-mm") && i + 1 < argc) m_bulk = argv[++i];
+            else if (!std::strcmp(argv[i], "--m-labels") && i + 1 < argc) m_labels = argv[++i];
+            else if (!std::strcmp(argv[i], "--m-truth") && i + 1 < argc) m_truth = argv[++i];
             else if (!std::strcmp(argv[i], "--spectral") && i + 1 < argc) spectral = argv[++i];
             else if (!std::strcmp(argv[i], "--gate") && i + 1 < argc) spectral_gate = argv[++i];
             else if (!std::strcmp(argv[i], "--spectral-pulses") && i + 1 < argc) spectral_pulses = argv[++i];
@@ -577,6 +601,35 @@ int main(int argc, char **argv)
             shelopts.ref_strain = 3.0f * shopts.density * 2.0f * 2.0f;      // the modulus of the speed a material has that is not named
             bmode = true;                               // the colour lies over the 8-bit frame
         }
+        if (!m_mode && (m_line || motion || m_prf || m_bpm || m_pulses || m_hop || m_height || m_depth || m_bulk || m_labels || m_truth))
+            throw std::invalid_argument("--m-line, --motion, --m-prf, --m-bpm, --m-pulses, --m-hop, --m-height, --m-depth-mm, --m-bulk-mm, --m-labels and --m-truth need --m-mode");
+        if (m_mode) {
+            if (compound_given || sweep_given || elevation_given || with_bands) throw std::invalid_argument("--m-mode does not combine with --compound, --sweep, --elevation or the band options");
+            if (!motion) throw std::invalid_argument("--m-mode needs --motion NAME:e[,NAME:e...]");
+            if (!m_line) throw std::invalid_argument("--m-mode needs --m-line LINE");
+            const long line = std::atol(m_line);
+            if (line < 0 || line >= (long)transducer_elements) throw std::invalid_argument("--m-line: the scan-line is not one of the transducer's");
+            m_scan_line = (uint32_t)line;
+            if (m_prf) m_prf_hz = std::atof(m_prf);
+            if (m_bpm) m_beats = std::atof(m_bpm);
+            if (!(std::isfinite(m_prf_hz) && m_prf_hz > 0.0) || !(std::isfinite(m_beats) && m_beats > 0.0)) throw std::invalid_argument("--m-prf and --m-bpm take rates > 0");
+            if (m_pulses) mmopts.n_pulses = (uint32_t)std::max(std::atol(m_pulses), 0l);
+            if (mmopts.n_pulses < 1u || mmopts.n_pulses > 16384u) throw std::invalid_argument("--m-pulses takes 1..16384");
+            if (m_hop) mdopts.hop = (uint32_t)std::max(std::atol(m_hop), 0l);
+            if (mdopts.hop < 1u || mdopts.hop > mmopts.n_pulses) throw std::invalid_argument("--m-hop takes 1..the pulses");
+            if (m_height) mdopts.height = (uint32_t)std::max(std::atol(m_height), 0l);
+            if (mdopts.height < 1u || mdopts.height > 4096u) throw std::invalid_argument("--m-height takes 1..4096");
+            if (m_depth) {
+                const auto d = comma_list<double>(m_depth);
+                if (d.size() != 2 || !(d[0] >= 0.0) || !(d[1] > d[0])) throw std::invalid_argument("--m-depth-mm takes LO,HI: two depths, 0 <= LO < HI");
+                m_depth_lo = d[0]; m_depth_hi = d[1];
+            }
+            if (m_bulk) {
+                const auto b = comma_list<double>(m_bulk);
+                if (b.size() != 2 || !std::isfinite(b[0]) || !std::isfinite(b[1])) throw std::invalid_argument("--m-bulk-mm takes A,PER_MIN: an amplitude [mm] and cycles per minute");
+                m_bulk_mm = b[0]; m_bulk_per_min = b[1];
+            }
+        }
         if (colour_flow) {
             if (compound_given || sweep_given || elevation_given || with_bands) throw std::invalid_argument("--colour-flow does not combine with --compound, --sweep, --elevation or the band options");
             if (flow_velocity.empty()) throw std::invalid_argument("--colour-flow needs --flow-velocity NAME:vx,vy,vz");
@@ -718,6 +771,29 @@ int main(int argc, char **argv)
             shopts.push_rows = (uint32_t)rows;
             shopts.push_row0 = (uint32_t)std::min(std::max(std::nearbyint(push_depth_mm / pitch - rows / 2.0), 0.0), R - rows);
         }
+        std::vector<double> dilation;                   // --motion: a dilation per material of the scene
+        std::vector<int32_t> m_wave, m_shift;           // ... the waveform and the bulk motion of every pulse
+        if (m_mode) {
+            dilation.assign(scene.material_names.size(), 0.0);
+            std::string list = motion;
+            for (size_t at = 0; at <= list.size();) {
+                const size_t comma = std::min(list.find(',', at), list.size());
+                const std::string item = list.substr(at, comma - at);
+                const size_t colon = item.find(':');
+                if (colon == std::string::npos || colon + 1 >= item.size()) throw std::invalid_argument("--motion takes NAME:e[,NAME:e...]");
+                dilation[scene.material_index(item.substr(0, colon))] = std::atof(item.c_str() + colon + 1);
+                at = comma + 1;
+            }
+            const double pitch = rf_image_::row_mm();
+            const long R = (long)rf_image_::max_rows;
+            m_wave.assign(mmopts.n_pulses, 0); m_shift.assign(mmopts.n_pulses, 0);
+            check(mcrt_mmode_waveform(m_prf_hz, m_beats, mmopts.n_pulses, m_wave.data()), "mcrt_mmode_waveform");
+            check(mcrt_mmode_bulk(m_prf_hz, m_bulk_per_min, m_bulk_mm / pitch, mmopts.n_pulses, m_shift.data()), "mcrt_mmode_bulk");
+            if (m_depth) {
+                mdopts.row_lo = (uint32_t)std::min(std::max((long)std::nearbyint(m_depth_lo / pitch), 0l), R - 1);
+                mdopts.row_hi = (uint32_t)std::min(std::max((long)std::nearbyint(m_depth_hi / pitch), (long)mdopts.row_lo + 1), R);
+            }
+        }
 
         const auto t0 = std::chrono::high_resolution_clock::now();
         for (int f = 0; f < frames; f++) {
@@ -746,6 +822,19 @@ int main(int argc, char **argv)
                 double cycles = 0.0;
                 check(mcrt_psf_carrier(transducer_frequency, resolution, &cycles), "mcrt_psf_carrier");
                 shear_true = rf_image.shear_wave(transducer, shear_c, shopts, cycles, 12, 8.0, nullptr, detect ? &dopts : nullptr);
+            }
+            if (m_mode && f == frames - 1) {             // the labels, the analytic pair and the pulses of one scan-line, before the RF is detected; then their sweep
+                double cycles = 0.0;
+                check(mcrt_psf_carrier(transducer_frequency, resolution, &cycles), "mcrt_psf_carrier");
+                rf_image.m_lines(transducer, m_scan_line, dilation, m_wave, m_shift, mmopts, cycles, nullptr, detect ? &dopts : nullptr);
+                const auto sweep_pic = rf_image.m_mode(mdopts);
+                write_pgm(m_mode, sweep_pic.width, sweep_pic.height, sweep_pic.picture);
+                if (m_labels) write_pgm(m_labels, sweep_pic.width, sweep_pic.height, sweep_pic.labels);
+                if (m_truth) {
+                    std::ofstream out(m_truth, std::ios::binary);
+                    out.write((const char *)sweep_pic.truth_disp.data(), (std::streamsize)(sweep_pic.truth_disp.size() * sizeof(float)));
+                    if (!out) throw std::runtime_error(std::string("cannot write ") + m_truth);
+                }
             }
             if (detect) rf_image.detect(dopts);          // quadrature detection in the place of ...
             else rf_image.envelope();         // main.cpp:147

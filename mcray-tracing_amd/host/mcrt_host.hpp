@@ -5,7 +5,7 @@
 //   transducer<N>            transducer.h:24-137   (frequency MHz, radius cm, element separation mm, position, angles deg)
 //   psf<ax,lat,elev,res>     psf.h:34-77
 //   scene                    scene.h:19-76, scene.cpp:16-48,185-247 (JSON keys, "Error while loading scene: ..." wrapping)
-//   rf_image<cols,us,um>     rfimage.h:20-219      (clear / convolve / envelope / postprocess; data lives on the GPU); + detect / iq; + flow_split / flow / colour_flow; + spectral_series / spectrum / sonogram; + compress / track / elastogram; + shear_wave / shear_speed / shear_elastogram
+//   rf_image<cols,us,um>     rfimage.h:20-219      (clear / convolve / envelope / postprocess; data lives on the GPU); + detect / iq; + flow_split / flow / colour_flow; + spectral_series / spectrum / sonogram; + compress / track / elastogram; + shear_wave / shear_speed / shear_elastogram; + m_lines / m_mode
 //   ray_physics::segment     ray.h:28-36           (vec3 stands in for btVector3; `media` is held BY VALUE: the reference's
 //                                                   `const material &` dangles by the time main.cpp:126 reads it)
 //   volume<size,res>         volume.h:19-61        (host copy of the texture the GPU samples)
@@ -723,7 +723,7 @@ public:
 
     rf_image(double radius_mm, double angle_rad, std::shared_ptr<device> dev_ = nullptr)
         : dev(dev_ ? std::move(dev_) : default_device()), radius_mm(radius_mm), angle(angle_rad), host((size_t)columns * max_rows, 0.0f),
-          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev), sound(dev), sigma(dev), curve(dev), band_stack(dev), flow_in(dev), flow_out(dev), spectral_buf(dev), strain_buf(dev), strain_pic(dev), shear_buf(dev), shear_pic(dev)
+          rf(dev), scan(dev), bmode_buf(dev), state(dev), planes(dev), stack(dev), points(dev), rendered(dev), label(dev), sound(dev), sigma(dev), curve(dev), band_stack(dev), flow_in(dev), flow_out(dev), spectral_buf(dev), strain_buf(dev), strain_pic(dev), shear_buf(dev), shear_pic(dev), mmode_buf(dev), mmode_pic(dev)
     {
         std::cout << "rf_image: " << max_rows << ", " << columns << std::endl;          // rfimage.h:30
         rf.reserve(sizeof(float) * columns * max_rows);
@@ -1178,6 +1178,55 @@ public:
         check(mcrt_elastogram_frames(dev->ctx, img, img + np, bmode_buf.as<uint8_t>(), 1, bmode_rows, bmode_cols, lut, &eo, out), "mcrt_elastogram_frames");
         rgb = download<unsigned char>(out, 3 * np);
     }
+    // M-mode (mcrt.h: mcrt_mmode_lines_frames, mcrt_mmode_picture_frames), two steps after ONE trace:
+    //   trace(f);  convolve(p); [add_noise();]  m_lines(t, line, dilation, w_q16, bulk_q24, mo, cycles);  m_mode(display);
+    // m_lines() goes while this image holds the RF before the envelope: the label pass of t's central beams (lopts: null = the tracer's
+    // rule), the detector's I/Q (dopts: null = 31 taps), then mo.n_pulses pulses of scan-line `line`.  dilation: the peak axial strain per
+    // material of the scene [n_materials] (scene::material_index names them; positive: compression); w_q16 and bulk_q24: one entry per
+    // pulse (mcrt_mmode_waveform's, mcrt_mmode_bulk's or the caller's own); cycles_per_row: mcrt_psf_carrier's.  A stack of views, planes
+    // or tracked frames, band images or a host-deposited image has no one analytic line: it throws.  The maps are [n_pulses][max_rows]
+    struct m_line_maps { std::vector<float> env, truth_disp; std::vector<unsigned char> truth_label; };
+    template <size_t N> m_line_maps m_lines(const transducer<N> &t, uint32_t line, const std::vector<double> &dilation, const std::vector<int32_t> &w_q16,
+                                            const std::vector<int32_t> &bulk_q24, const mcrt_mmode_opts &mo, double cycles_per_row,
+                                            const mcrt_label_opts *lopts = nullptr, const mcrt_detect_opts *dopts = nullptr)
+    {
+        static_assert(N == columns, "one scan-line per transducer element");
+        if (n_views || banded || where != on_device) throw std::logic_error("rf_image::m_lines: after trace(frame_id) and convolve(psf), on one traced image");
+        const uint32_t L = (uint32_t)dilation.size(), T = mo.n_pulses;
+        if (L == 0 || L > 254) throw std::invalid_argument("rf_image::m_lines: a dilation per material, 1..254 materials");
+        if (w_q16.size() != T || bulk_q24.size() != T) throw std::invalid_argument("rf_image::m_lines: w_q16 and bulk_q24 take one entry per pulse");
+        std::vector<int32_t> dil(L);
+        check(mcrt_mmode_table(dilation.data(), L, dil.data()), "mcrt_mmode_table");
+        const size_t n = (size_t)columns * max_rows, m = (size_t)T * max_rows;
+        mmode_buf.reserve(4 * 2 * n + 4 * 2 * m + m + n);            // floats: the pairs [n][2], env [m], truth_disp [m]; then the label bytes [m] and the tissue bytes [n]
+        float *pairs = mmode_buf.as<float>(), *env = pairs + 2 * n, *td = env + m;
+        uint8_t *tl = reinterpret_cast<uint8_t *>(td + m), *tissue = tl + m;
+        mcrt_ctx *tracer = dev->tracer();
+        check(mcrt_label_frames(tracer, 1, 0, columns, t.pos.data(), t.dir.data(), lopts, tissue, nullptr, nullptr), "mcrt_label_frames");
+        check(mcrt_synchronize(tracer), "mcrt_synchronize");
+        mcrt_detect_opts d; mcrt_default_detect_opts(&d);
+        check(mcrt_detect_frames(dev->ctx, rf.as<float>(), 1, columns, max_rows, dopts ? dopts : &d, nullptr, pairs), "mcrt_detect_frames");
+        mmode_pulses = 0;
+        const mcrt_mline which{ 0u, line };
+        check(mcrt_mmode_lines_frames(dev->ctx, pairs, tissue, 1, columns, max_rows, &which, 1, dil.data(), L, w_q16.data(), bulk_q24.data(), cycles_per_row, &mo, first_id,
+                                      nullptr, env, nullptr, td, tl), "mcrt_mmode_lines_frames");
+        mmode_pulses = T;
+        return { download<float>(env, m), download<float>(td, m), download<unsigned char>(tl, m) };
+    }
+    // the sweep display of the pulses m_lines() left: the grey bytes and, registered with them pixel for pixel, the material and the true
+    // displacement [rows], each [height][n_pulses / hop]
+    struct m_mode_picture { std::vector<unsigned char> picture, labels; std::vector<float> truth_disp; uint32_t height = 0, width = 0; };
+    m_mode_picture m_mode(const mcrt_mmode_display_opts &o)
+    {
+        if (!mmode_pulses) throw std::logic_error("rf_image::m_mode: m_lines() first");
+        if (o.hop == 0 || o.hop > mmode_pulses) throw std::invalid_argument("rf_image::m_mode: hop takes 1..n_pulses");
+        const size_t n = (size_t)columns * max_rows, m = (size_t)mmode_pulses * max_rows, np = (size_t)o.height * (mmode_pulses / o.hop);
+        mmode_pic.reserve(4 * np + 2 * np);                          // truth_disp's picture, then the grey and the label bytes
+        float *env = mmode_buf.as<float>() + 2 * n, *td = env + m, *dp = mmode_pic.as<float>();
+        uint8_t *tl = reinterpret_cast<uint8_t *>(td + m), *grey = reinterpret_cast<uint8_t *>(dp + np), *lp = grey + np;
+        check(mcrt_mmode_picture_frames(dev->ctx, env, tl, td, 1, mmode_pulses, max_rows, &o, nullptr, nullptr, grey, lp, dp), "mcrt_mmode_picture_frames");
+        return { download<unsigned char>(grey, np), download<unsigned char>(lp, np), download<float>(dp, np), o.height, mmode_pulses / o.hop };
+    }
     // receiver noise (mcrt.h: mcrt_noise_frames): a noise floor and a gain per scan-line (element_gain: [columns] or null) over whatever the
     // last trace() filled, in place -- this image, or the views of a compounded frame or the planes of a sweep as ONE frame (one receiver,
     // one peak), or the tracked frames of a freehand pass as so many frames -- with the ids that trace used.  It goes after convolve() and
@@ -1550,6 +1599,8 @@ private:
     device_buffer strain_buf, strain_pic;        // compress() / track(): the pairs, the post-compression pairs, five maps and the tissue bytes; elastogram(): the gathered pictures and the rgb bytes
     device_buffer shear_buf, shear_pic;          // shear_wave() / shear_speed(): the pairs, seven maps and the tissue bytes; shear_elastogram(): the gathered pictures and the rgb bytes
     std::vector<float> shear_pitch_mm; int shear_stage = 0;   // shear_wave()'s pitch table [max_rows]; 0: nothing yet, 1: shear_wave() has run, 2: shear_speed() since
+    device_buffer mmode_buf, mmode_pic;          // m_lines(): the pairs, the pulses' envelopes, displacements and labels and the tissue bytes; m_mode(): the three pictures
+    uint32_t mmode_pulses = 0;                   // the pulses m_lines() left on the device; 0: nothing yet
     double strain_cycles = 0.0; bool strain_tracked = false;   // compress()'s carrier (0: it has not run); track() has run since
     uint32_t banded = 0;                         // ... B while they wait there for envelope() / fold_bands() (0: the images are where trace() left them)
     std::vector<float> band_w;                   // ... and the bands' weights [max_rows][B] they are folded with
